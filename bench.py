@@ -12,9 +12,13 @@ The timed corpus is the reference's clustered recall recipe (nidx_vector/src/seg
 size, so recall@10 is measured on the corpus the throughput is quoted on; the uniform-random corpus of the reference's
 other tests is a second, labelled figure (config.uniform_corpus).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement), extended with
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step = one batch; exactly
+`--steps` steps are timed after `--warmup` untimed ones) and the configuration.  A plain run does only that: set up, warm up, time
+the steps, write the last step's hits when `--dump-outputs DIR` is given, print the line.  `--full` adds every other figure and check
+of the default workload, extending the line with
   roofline      dominant kernel (hnsw_search_kernel): algorithmic bytes per launch / HIP-event time vs 8 TB/s
   cpu_baseline  the CPU oracle (restated reference algorithm) on this box's host cores, bounded sample
+and recall@k, oracle parity, the serving shapes, the uniform corpus, the bf16 fallback, the BM25 and hybrid blocks.
 """
 from __future__ import annotations
 
@@ -47,8 +51,13 @@ T_PROCESS_START = time.time()   # the headline line carries the wall-clock time 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--steps", type=int, default=20, help="timed steps (hnsw: exactly this many batches are timed)")
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="hnsw: also every figure and check beside the headline (recall, roofline, oracle parity, CPU baselines, serving shapes, "
+                        "uniform corpus, bf16 fallback, BM25 / hybrid blocks); a plain run times the headline alone")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="hnsw: after the timed steps, write the hits of the last timed step as DIR/<name>.npy (float32 / float64)")
     p.add_argument("--n-vectors", type=int, default=0,
                    help="vectors per shard (per GPU); 0 = BASELINE.json: 10 M on one GPU (configs[2]), 12.5 M per GPU otherwise (configs[3]: 100 M over 8)")
     p.add_argument("--corpus", choices=["clustered", "uniform", "both"], default="both",
@@ -72,7 +81,8 @@ def parse():
                         "of rebuilt (profiling runs: rocprofv3 --pmc crashes over the thousands of dispatches of a 10 M build)")
     p.add_argument("--single-query-calls", type=int, default=2048, help="hnsw: nidx_gpu_vector_search_one calls for the p50/p99 figure (0 = skip)")
     p.add_argument("--min-timed-s", type=float, default=1.0,
-                   help="the timed pass of --steps steps is repeated until the timed region is at least this long (ms_per_step = mean over all)")
+                   help="bm25 / hybrid: the timed region lasts at least this long; hnsw --full: the side legs that time the headline's pipeline "
+                        "again (serving shapes, iso-recall, reference constants) are sized to about this long")
     p.add_argument("--build-ef-upper", type=int, default=4,
                    help="hnsw: tunable build_ef_upper of the timed flat graph: results kept per layer while an insertion descends to its "
                         "node's top layer (0 = 1 = the reference's greedy descent, hnsw/build.rs:137-146).  A greedy descent into a graph of "
@@ -151,6 +161,9 @@ def main():
         a.gpus = world
     if a.waves_per_query:
         os.environ["NIDX_GPU_WAVES_PER_QUERY"] = str(a.waves_per_query)
+    if a.dump_outputs and a.workload != "hnsw":
+        print("ERROR: --dump-outputs writes the hits of the hnsw workload; --workload %s has none to write" % a.workload, file=sys.stderr)
+        sys.exit(2)
     # NIDX_BENCH_SAME_DEVICE=1 (validation only): every rank uses GPU 0; torch.distributed (control traffic: query broadcast, barriers)
     # goes over gloo and the DATA-PATH exchange over the library's shared-memory transport, so the N>1 code path — the library's own
     # exchange included — can be exercised on a single-GPU box.  The driver never sets it.
@@ -551,7 +564,7 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
     open_s = time.time() - t0
     del cached
     # the host copy feeds the oracle legs (rank 0 of the headline corpus only): the product never reads it
-    need_host = rank == 0 and headline and (a.parity_queries > 0 or a.cpu_queries > 0 or a.scan_check_queries > 0 or a.ref_build_n > 0)
+    need_host = a.full and rank == 0 and headline and (a.parity_queries > 0 or a.cpu_queries > 0 or a.scan_check_queries > 0 or a.ref_build_n > 0)
     x_host = x.cpu().numpy() if need_host else None
     del x
     torch.cuda.empty_cache()
@@ -568,7 +581,7 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
             del g_, _e
     build_s = time.time() - t0
     build_blk = None
-    if not (gpath and cached_used):
+    if a.full and not (gpath and cached_used):
         # the build on the roofline (north_star: "build + k-NN query distance kernels"; HnswBuilder, hnsw/build.rs:28-167): the build
         # kernels count their distance evaluations, expansions and the rows the neighbour-selection heuristic reads, like the search kernel
         bst = (C.c_uint64 * 10)()
@@ -742,67 +755,43 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
     torch.cuda.synchronize()
     device_flags()  # clear: the word below covers exactly the timed launches
     retried_total[0] = 0
-    # EXACTLY `--steps` steps are timed per pass; the pass is repeated until the timed region is at least `--min-timed-s` long (20
-    # steps of this workload are 6 ms: too short to time honestly), and `ms_per_step` is the mean over every timed step
-    repeats, elapsed = 1, 0.0
-    if a.steps > 0:
-        # the pass count is sized from a WARM probe: the first pass over the pool runs up to 2 x slower than the steady state (cold
-        # TLBs / caches / clocks), and a count taken from it left the timed region at half the length asked for (round 4: 0.49 s)
-        probe = 0.0
-        for _ in range(3):
-            barrier()
-            t0 = time.perf_counter()
-            for i in range(a.steps):
-                step(a.warmup + i)
-            drain()
-            barrier()
-            probe = time.perf_counter() - t0
-        repeats = max(1, int(np.ceil(1.1 * a.min_timed_s / max(probe, 1e-6))))
-        if world > 1:
-            t = torch.tensor([repeats], dtype=torch.int64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            repeats = int(t.item())
-    # (a 20-step probe is mostly pipeline fill and drain — it ran at half the steady rate and the region sized from it came out at 0.55 s:
-    # the region is timed, and when it falls short of --min-timed-s it is sized again from its own rate and timed once more)
-    for _attempt in range(3):
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(a.steps * repeats):
-            step(a.warmup + i)
-        drain()
-        barrier()
-        elapsed = time.perf_counter() - t0
-        again = a.steps > 0 and elapsed < a.min_timed_s and _attempt < 2
-        if world > 1:
-            t = torch.tensor([1 if again else 0, repeats], dtype=torch.int64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            again = bool(int(t[0].item()))
-        if not again:
-            break
-        repeats = max(repeats + 1, int(np.ceil(repeats * 1.15 * a.min_timed_s / max(elapsed, 1e-6))))
-        if world > 1:
-            t = torch.tensor([repeats], dtype=torch.int64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            repeats = int(t.item())
-        trace_acc[0] = trace_acc[1] = 0.0
-        trace_acc[2] = 0
-        retried_total[0] = 0
-        if do_exchange:
-            device_flags()
+    # EXACTLY `--steps` steps are timed (ms_per_step = the region / --steps): the caller sizes --steps so that the region is long
+    # enough to time honestly (20 steps of this workload are ~6 ms, mostly pipeline fill and drain)
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(a.steps):
+        step(a.warmup + i)
+    drain()
+    barrier()
+    elapsed = time.perf_counter() - t0
     if trace_steps and trace_acc[2]:
         print("[bench trace] rank %d: %d exchange steps: host time in search launch %.3f ms, in exchange %.3f ms per step; elapsed %.3f ms per step"
-              % (rank, trace_acc[2], trace_acc[0] / trace_acc[2] * 1e3, trace_acc[1] / trace_acc[2] * 1e3, elapsed / max(1, a.steps * repeats) * 1e3), file=sys.stderr)
+              % (rank, trace_acc[2], trace_acc[0] / trace_acc[2] * 1e3, trace_acc[1] / trace_acc[2] * 1e3, elapsed / max(1, a.steps) * 1e3), file=sys.stderr)
     # every timed launch ORs the overflow flags of its queries into one word: wait() re-runs flagged queries exactly and counts them
     # (N = 1); the device-entry launches of the exchange path leave the word for the poll below
     timed_flags = device_flags() if do_exchange else 0
     timed_retried = retried_total[0]
+    # the hits of the last timed step, as its caller received them: host arrays from nidx_gpu_vector_search_wait (N = 1), the merged
+    # lists of the exchange (N > 1); the slots past a query's count are -1 / 0
+    last_out = None
+    if headline and rank == 0 and a.steps > 0:
+        if do_exchange:
+            msc, mid, mcn = (t_.cpu().numpy() for t_ in last_merged[0])
+        else:
+            mid, msc, mcn = host_out[(a.warmup + a.steps - 1) % nfl_now[0]]
+        cnt = mcn.astype(np.int64)
+        valid = np.arange(k)[None, :] < cnt[:, None]
+        last_out = {"ids": np.where(valid, mid.astype(np.float64), -1.0), "scores": np.where(valid, msc, np.float32(0)).astype(np.float32),
+                    "counts": cnt.astype(np.float64)}
+    # steps the side legs of --full time the same pipeline for: about --min-timed-s at the rate just measured
+    steps_side = max(a.steps, a.steps * int(np.ceil(1.1 * a.min_timed_s / max(elapsed, 1e-6)))) if a.steps > 0 else 0
     if crowded_by_hand:
         _lib.check(L.nidx_gpu_vector_set_tunable(h, b"launch_shape", 0))
     exchange_check = None
-    if do_exchange and a.steps > 0:
+    if a.full and do_exchange and a.steps > 0:
         # the overlapped pipeline must give what a plain search -> exchange of the same batch gives — and the library's RCCL
         # exchange what the same exchange through torch.distributed gives
-        i_last = a.warmup + a.steps * repeats - 1
+        i_last = a.warmup + a.steps - 1
         torch.cuda.synchronize()
         got = [t.clone() for t in last_merged[0]]
         search(qpool[i_last % n_pool], out=out_sets[0])
@@ -823,7 +812,17 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    steps_timed = a.steps * repeats
+    steps_timed = a.steps
+    recall, got0, exact0, recall_hist = None, None, None, None
+    if not a.full:
+        res = None
+        if rank == 0:
+            res = {"corpus": kind, "elapsed": elapsed, "nfl": nfl, "timed_flags": timed_flags, "gen_s": gen_s, "open_s": open_s, "build_s": build_s,
+                   "exchange_check": None, "library_exchange": comm is not None, "exchange_transport": (None if comm is None else "shm" if same_device else "rccl"),
+                   "launch_shape_set_by_bench": crowded_by_hand, "build": None, "steps_timed": steps_timed,
+                   "timed_retried": timed_retried, "recall": None, "last_out": last_out}
+        L.nidx_gpu_vector_close(h)
+        return res
     # per-launch duration: HIP events on the launch's own stream around launches issued one at a time (the overlapped launches of
     # the timed region also span their wait for workgroup slots, which no profiler counts as kernel time)
     ea = [torch.cuda.Event(enable_timing=True) for _ in range(2 * max(1, min(a.steps, 8)))]
@@ -851,7 +850,6 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
     traffic, traffic_src = pmc_traffic(kind, n, d, B, k)
 
     # ---- recall@k of the timed configuration against the exact scan of the same shard (merged over the shards when N > 1)
-    recall, got0, exact0, recall_hist = None, None, None, None
     if a.recall_queries > 0:
         rq = min(a.recall_queries, B)
         search(qpool[0])
@@ -885,7 +883,8 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
             "corpus": kind, "elapsed": elapsed, "kernel_ms": kernel_ms, "alone_ms": alone_ms, "nfl": nfl, "alg_bytes": alg_bytes, "achieved": achieved,
             "traffic": traffic, "traffic_src": traffic_src, "recall": recall, "recall_hist": recall_hist, "evals": float(np.mean(evals_q)),
             "expansions": float(np.mean(exp_q)), "edge_hits": float(np.mean(hits_q)), "flags": flags, "timed_flags": timed_flags, "gen_s": gen_s, "open_s": open_s,
-            "build_s": build_s, "exchange_check": exchange_check, "library_exchange": comm is not None, "exchange_transport": (None if comm is None else "shm" if same_device else "rccl"), "launch_shape_set_by_bench": crowded_by_hand, "build": build_blk, "steps_timed": steps_timed, "repeats": repeats, "timed_retried": timed_retried,
+            "build_s": build_s, "exchange_check": exchange_check, "library_exchange": comm is not None, "exchange_transport": (None if comm is None else "shm" if same_device else "rccl"), "launch_shape_set_by_bench": crowded_by_hand, "build": build_blk, "steps_timed": steps_timed, "timed_retried": timed_retried,
+            "last_out": last_out,
         }
     if not headline:
         L.nidx_gpu_vector_close(h)
@@ -957,7 +956,7 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
                     hv_, hs2_, hc_ = host_out_h[j_]
                     _lib.check(L.nidx_gpu_vector_search_wait(h, t_, None, None, hv_.ctypes.data, hs2_.ctypes.data, hc_.ctypes.data, None))
 
-            n_host = max(a.steps, int(steps_timed * 0.5))
+            n_host = max(a.steps, int(steps_side * 0.5))
             drv = native_host_driver()
             # two threads with two tickets each (measured round 6 at 4 M vectors, fraction of the device-resident rate: 1 thread x 3 tickets
             # 0.86, 2 x 2 0.96, 3 x 2 0.92; a thread with ONE ticket stages its next batch only after its last one has landed: 3 x 1 0.64)
@@ -1059,7 +1058,7 @@ def hnsw_leg(a, L, dev, rank, world, kind, headline):
             for i in range(max(2, a.warmup)):
                 step(i)
             drain()
-            n_iso = max(a.steps, int(steps_timed * 0.4))
+            n_iso = max(a.steps, int(steps_side * 0.4))
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(n_iso):
@@ -1546,9 +1545,13 @@ def bench_hnsw(a, L, dev, rank, world):
     n, d, B, k = a.n_vectors, a.dim, a.batch, a.k
     kinds = ["clustered", "uniform"] if a.corpus == "both" else [a.corpus]
     head = hnsw_leg(a, L, dev, rank, world, kinds[0], True)
-    second = hnsw_leg(a, L, dev, rank, world, kinds[1], False) if len(kinds) > 1 else None
+    if rank == 0 and a.dump_outputs and head["last_out"] is not None:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in head["last_out"].items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+    second = hnsw_leg(a, L, dev, rank, world, kinds[1], False) if (a.full and len(kinds) > 1) else None
     bf16_blk = None
-    if world == 1 and a.bf16_block_n > 0:
+    if a.full and world == 1 and a.bf16_block_n > 0:
         try:
             bf16_blk = bf16_block(a, L, dev)
         except Exception as e:  # noqa: BLE001 — a side block: its failure must not cost the measured line
@@ -1565,14 +1568,14 @@ def bench_hnsw(a, L, dev, rank, world):
                                     ": uniform(-1,1) normalised (segment.rs:682-695)"),
         "vectors_per_shard": n, "dim": d, "batch": B, "k": k, "shards": world, "corpus_vectors": n * world,
         "merged_queries_per_s": B * head["steps_timed"] / head["elapsed"],
-        "recall_at_%d" % k: head["recall"], "recall_queries": min(a.recall_queries, B), "recall_queries_by_hits": head.get("recall_hist"),
+        "recall_at_%d" % k: head["recall"], "recall_queries": min(a.recall_queries, B) if a.full else None, "recall_queries_by_hits": head.get("recall_hist"),
         "recall_at_%d_reference_regime" % k: ((head.get("cpu") or {}).get("segment_regime") or {}).get("recall_at_%d" % k),
         "search_knobs": {"ef_upper": max(1, a.ef_upper), "ef_search": 30},
         "iso_recall": head.get("iso_recall"), "reference_constants": head.get("reference_constants"), "bm25": head.get("bm25"), "hybrid": head.get("hybrid"),
-        "distance_evals_per_query": head["evals"], "expansions_per_query": head["expansions"],
-        "expansions_with_edge_record_fetched_ahead_per_query": head["edge_hits"],
-        "kernel_flags": head["flags"], "timed_launch_flags": head["timed_flags"], "timed_queries_re_run_exactly": head["timed_retried"],
-        "timed_region": {"steps_per_pass": a.steps, "passes": head["repeats"], "steps_timed": head["steps_timed"], "seconds": head["elapsed"],
+        "distance_evals_per_query": head.get("evals"), "expansions_per_query": head.get("expansions"),
+        "expansions_with_edge_record_fetched_ahead_per_query": head.get("edge_hits"),
+        "kernel_flags": head.get("flags"), "timed_launch_flags": head["timed_flags"], "timed_queries_re_run_exactly": head["timed_retried"],
+        "timed_region": {"steps_timed": head["steps_timed"], "seconds": head["elapsed"],
                          "entry": "nidx_gpu_vector_search_submit / _wait: device-resident queries in, hits in host arrays out" if world == 1 else
                                   ("nidx_gpu_vector_segment_search_device + nidx_gpu_shard_exchange_merge_vector (%s)" % ("RCCL inside the library" if head.get("exchange_transport") == "rccl" else "the library's shared-memory transport: the ranks share one GPU, validation") if head.get("library_exchange")
                                    else "nidx_gpu_vector_segment_search_device + the same exchange through torch.distributed (validation mode, or the library's communicator could not be set up)")},
@@ -1580,6 +1583,9 @@ def bench_hnsw(a, L, dev, rank, world):
         "parallelism": "shard-per-gpu x%d, RCCL all-gather of top-k" % world, "exchange_check": head["exchange_check"],
         "batches_in_flight": head["nfl"],
         "parity": head.get("parity"),
+        "full": a.full,
+        "dump_outputs": ({"dir": a.dump_outputs, "step": a.warmup + a.steps - 1, "arrays": sorted(head["last_out"])}
+                         if a.dump_outputs and head["last_out"] is not None else None),
     }
     cfgd.update(extra)
     # the figures of the nested blocks a reader of the top level needs, as scalars
@@ -1654,7 +1660,7 @@ def bench_hnsw(a, L, dev, rank, world):
         # measured on the same launches issued one at a time right after the timed region (HIP events on the launch stream; this is
         # the figure rocprofv3 --kernel-trace of `bench.py --batches-in-flight 1` reproduces: profiles/r02_pmc_hnsw10m_clustered.txt);
         # the overlapped durations and the sustained rate of the timed region are given beside it.
-        "roofline": {"kernel": "hnsw_search_kernel<3,4,4,1>", "bound": "hbm", "achieved": head["alg_bytes"] / (head["alone_ms"] * 1e-3) / 1e9,
+        "roofline": None if not a.full else {"kernel": "hnsw_search_kernel<3,4,4,1>", "bound": "hbm", "achieved": head["alg_bytes"] / (head["alone_ms"] * 1e-3) / 1e9,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": head["alg_bytes"] / (head["alone_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                      "traffic": head["traffic"], "traffic_source": head["traffic_src"],
                      "algorithmic_bytes_per_launch": head["alg_bytes"], "kernel_ms": head["alone_ms"],

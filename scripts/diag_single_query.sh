@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/sq
 for i in 1 2 3 4 5; do
     NIDX_GPU_TRACE_SLOW_US=${TRACE_US:-5000} timeout 200 python bench.py --corpus clustered --steps 2 --warmup 1 --batches-in-flight 1 \
-        --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --ref-build-n 0 --cpu-queries 0 --recall-queries 8 \
+        --full --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --ref-build-n 0 --cpu-queries 0 --recall-queries 8 \
         --single-query-calls 2048 --graph-cache /tmp/gc > gpurun_out/sq/run$i.json 2> gpurun_out/sq/run$i.err
     python - $i <<'P'
 import json, sys

@@ -8,10 +8,10 @@ mkdir -p $OUT
 cd $ROOT
 timeout 600 python -m pytest tests -x -q -m gpu 2>&1 | tail -2
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 200 $OUT/bench_default.json; echo
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --corpus clustered --steps 10 --warmup 2 --cpu-queries 0 --parity-queries 0 --scan-check-queries 0 --ref-build-n 0 --single-query-calls 0 --recall-queries 0 --segment-regime 0 --batches-in-flight 1"
+BENCH="python $ROOT/bench.py --full --corpus clustered --steps 10 --warmup 2 --cpu-queries 0 --parity-queries 0 --scan-check-queries 0 --ref-build-n 0 --single-query-calls 0 --recall-queries 0 --segment-regime 0 --batches-in-flight 1"
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/prof_c -- $BENCH > $OUT/bench_hnsw10m_clustered_profiled.json 2> /dev/null
 db=$(ls $OUT/prof_c/*/*.db 2>/dev/null | head -1)
 [ -n "$db" ] && python $ROOT/scripts/prof_summary.py $db "clustered corpus, trace pass: $BENCH" > $OUT/summary_trace_clustered.txt 2>&1

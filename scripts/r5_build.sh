@@ -1,7 +1,7 @@
 #!/bin/bash
 # build-time A/B on the 10 M clustered shard (side blocks off): register budget of the heuristic kernels, visited-table size
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; mkdir -p gpurun_out/r5build
-ARGS="--corpus clustered --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --bf16-block-n 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 --bm25-block 0 --iso-recall 0 --steps 5 --min-timed-s 0.2"
+ARGS="--full --corpus clustered --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --bf16-block-n 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 --bm25-block 0 --iso-recall 0 --steps 5 --min-timed-s 0.2"
 for v in "3 0" "4 0" "2 0" "3 14"; do
   set -- $v
   if [ "$2" = 0 ]; then VIS=""; else VIS="NIDX_GPU_BUILD_VIS_LOG2=$2"; fi

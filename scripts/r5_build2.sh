@@ -1,7 +1,7 @@
 #!/bin/bash
 # build-time A/B on the 10 M clustered shard (side blocks off): the cap on a batch of insertions
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; mkdir -p gpurun_out/r5build
-ARGS="--corpus clustered --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --bf16-block-n 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 --bm25-block 0 --iso-recall 0 --steps 5 --min-timed-s 0.2"
+ARGS="--full --corpus clustered --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --bf16-block-n 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 --bm25-block 0 --iso-recall 0 --steps 5 --min-timed-s 0.2"
 for v in ${@:-8192 16384 32768}; do
   env NIDX_GPU_BUILD_MAX_BATCH=$v timeout 300 python bench.py $ARGS > gpurun_out/r5build/mb_$v.json 2> gpurun_out/r5build/mb_$v.err
   python - <<PY

@@ -26,7 +26,7 @@ pmc() {  # name, counter, bench args...
 for PART in $PARTS; do
 case $PART in
 headline)
-  timeout 900 python $ROOT/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout 900 python $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   tail -c 300 $OUT/bench_default.json; echo
   bash $ROOT/scripts/refresh_profiles.sh ;;
 bm25)
@@ -47,9 +47,9 @@ rabitq)
   pmc rabitq_1m WRITE_SIZE --workload rabitq --n-vectors 1000000 --steps 3 --warmup 1 --cpu-queries 0 --batches-in-flight 1
   NIDX_GPU_RABITQ_WAVES=2 prof rabitq_1m_two_waves --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 0 ;;
 hnsw1m)
-  prof hnsw1m --n-vectors 1000000 --corpus clustered --bf16-block-n 0 --bm25-block 0 --single-query-calls 0 --segment-regime 0 --ref-build-n 0 ;;
+  prof hnsw1m --full --n-vectors 1000000 --corpus clustered --bf16-block-n 0 --bm25-block 0 --single-query-calls 0 --segment-regime 0 --ref-build-n 0 ;;
 others)
-  prof hnsw1m --n-vectors 1000000 --corpus clustered --bf16-block-n 0 --bm25-block 0 --single-query-calls 0 --segment-regime 0 --ref-build-n 0
+  prof hnsw1m --full --n-vectors 1000000 --corpus clustered --bf16-block-n 0 --bm25-block 0 --single-query-calls 0 --segment-regime 0 --ref-build-n 0
   prof scan_1m --workload scan --n-vectors 1000000 --steps 3 --warmup 1
   prof mfma_1m_k10 --workload mfma --n-vectors 1000000 --steps 5 --warmup 1
   prof mfma_1m_k64 --workload mfma --n-vectors 1000000 --steps 5 --warmup 1 --k 64

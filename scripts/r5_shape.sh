@@ -2,6 +2,7 @@
 # launch shape of hnsw_search_kernel on the 10 M clustered shard (side blocks off): register class x visited-table size
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; mkdir -p gpurun_out/r5shape
 ARGS="--corpus clustered --parity-queries 64 --scan-check-queries 0 --segment-regime 0 --bf16-block-n 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 --bm25-block 0 --iso-recall 0 --graph-cache /tmp/nidx_graphs"
+ARGS="--full $ARGS"   # roofline, recall and parity are --full figures
 for v in ${@:-"" "min_waves=5,vis_log2=12" "min_waves=5" "vis_log2=12" "min_waves=6,vis_log2=12"}; do
   name=$(echo "x$v" | tr ',=' '__')
   env NIDX_BENCH_TUNABLES="$v" timeout 400 python bench.py $ARGS > gpurun_out/r5shape/$name.json 2> gpurun_out/r5shape/$name.err

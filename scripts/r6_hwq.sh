@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/hwq
 mkdir -p $OUT
 cd $ROOT
 for hq in ${HQS:-4 8 16}; do
-  GPU_MAX_HW_QUEUES=$hq timeout 900 python bench.py --bm25-block 0 --bf16-block-n 0 --segment-regime 0 --cpu-queries 0 --parity-queries 0 --single-query-calls 0 --ref-build-n 0 --corpus clustered --scan-check-queries 0 --iso-target 0.9 > $OUT/b_$hq.json 2> $OUT/b_$hq.err
+  GPU_MAX_HW_QUEUES=$hq timeout 900 python bench.py --full --bm25-block 0 --bf16-block-n 0 --segment-regime 0 --cpu-queries 0 --parity-queries 0 --single-query-calls 0 --ref-build-n 0 --corpus clustered --scan-check-queries 0 --iso-target 0.9 > $OUT/b_$hq.json 2> $OUT/b_$hq.err
   python - <<PY
 import json
 try:

@@ -22,11 +22,11 @@ pmc() {  # name, counter, bench args...
   [ -n "$db" ] && python $ROOT/scripts/prof_summary.py $db "rocprofv3 --pmc $c --kernel-trace -- python bench.py $*" > $OUT/pmc_${name}_$c.txt 2>&1
   rm -rf /tmp/pmc_${name}_$c
 }
-HNSW_OFF="--cpu-queries 0 --parity-queries 0 --scan-check-queries 0 --ref-build-n 0 --single-query-calls 0 --bf16-block-n 0 --bm25-block 0 --iso-recall 0 --segment-regime 0 --corpus clustered"
+HNSW_OFF="--full --cpu-queries 0 --parity-queries 0 --scan-check-queries 0 --ref-build-n 0 --single-query-calls 0 --bf16-block-n 0 --bm25-block 0 --iso-recall 0 --segment-regime 0 --corpus clustered"
 for PART in $PARTS; do
 case $PART in
 headline)
-  ( cd $ROOT && timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err )
+  ( cd $ROOT && timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err )
   tail -c 300 $OUT/bench_default.json; echo ;;
 bm25)
   export NIDX_BENCH_BM25_SEGMENTS=0

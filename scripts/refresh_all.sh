@@ -16,7 +16,7 @@ prof() {  # name, bench args...
   tail -c 400 $OUT/bench_$name.json; echo
 }
 if [ "$PART" = headline ] || [ "$PART" = all ]; then
-  timeout 1500 python $ROOT/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout 1500 python $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   tail -c 300 $OUT/bench_default.json; echo
   bash $ROOT/scripts/refresh_profiles.sh
 fi

@@ -6,7 +6,7 @@ ONLY="$*"
 run() {  # name, batches in flight, env...
     local name=$1 f=$2; shift 2
     if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $name "; then return; fi
-    env "$@" timeout 240 python bench.py --corpus clustered --steps 40 --warmup 5 --batches-in-flight $f \
+    env "$@" timeout 240 python bench.py --full --corpus clustered --steps 40 --warmup 5 --batches-in-flight $f \
         --parity-queries 0 --scan-check-queries 0 --segment-regime 0 --ref-build-n 0 --single-query-calls 0 --cpu-queries 0 \
         --recall-queries 64 --graph-cache /tmp/gc > gpurun_out/occ/$name.json 2> gpurun_out/occ/$name.err
     python - "$name" <<'P'

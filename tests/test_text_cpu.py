@@ -130,7 +130,7 @@ def test_tricky_resource_of_the_reference_at_the_host_level():
     """nidx_paragraph/tests/reader.rs:71-91 (create_tricky_resource) and :452-500 (test_query_parsing_weird_stuff), :418-450
     (test_query_parsing): what those cases pin on the host side — the document tokenizer ("default": split on non-alphanumerics,
     lower-case), the keyword grammar and the stop-word rule (every stop word but the last token goes; the lists are the
-    reference's own data files, read from /root/reference when it is there)."""
+    reference's own data files, nidx_paragraph/stop_words/*.json (NLTK's lists), kept in tests/golden/stop_words)."""
     import glob
     import json
     import os
@@ -153,9 +153,7 @@ def test_tricky_resource_of_the_reference_at_the_host_level():
     assert sum(contains_phrase(t, quoted[0][1].split()) for t in tokens) == 1            # `total` == 1
     assert parse_query("some ' document") == lit("some", "document")                      # the stray quote goes (PR 3216)
 
-    base = "/root/reference/nidx/nidx_paragraph/stop_words"
-    if not os.path.isdir(base):
-        pytest.skip("the reference's stop-word data files are not on this machine")
+    base = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stop_words")
     stop = set()
     for code in ("fr", "it", "es", "en", "ca", "de", "nl", "pt"):   # LOADED_LANGUAGES, query_parser/stop_words.rs:84-93
         with open(os.path.join(base, code + ".json")) as f:

@@ -263,7 +263,7 @@ def test_bench_launches_its_own_ranks_and_runs_the_library_exchange():
     """`python bench.py --gpus 2` without a launcher spawns its two ranks itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set per
     child); on this 1-GPU box NIDX_BENCH_SAME_DEVICE=1 lets them share GPU 0 with the DATA-PATH exchange running through the
     library (nidx_gpu_shard_exchange_merge_vector over its shared-memory transport: pack, gather layout, shard order and merge
-    kernels are the RCCL path's own code).  The one JSON line must say n_gpus = 2, carry the recall of the MERGED hits against the
+    kernels are the RCCL path's own code).  The one JSON line of --full must say n_gpus = 2, carry the recall of the MERGED hits against the
     merged exact scan, and `exchange_check: ok` (overlapped pipeline == plain search -> exchange; library exchange == the same
     exchange through torch.distributed).  Without the variable, asking for more GPUs than the node has is an error, not a 1-GPU run.
     Merge semantics: nidx/src/searcher/shard_merge.rs:332-348."""
@@ -274,7 +274,7 @@ def test_bench_launches_its_own_ranks_and_runs_the_library_exchange():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--n-vectors", "200000", "--corpus", "clustered", "--steps", "5", "--warmup", "2",
+    args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--n-vectors", "200000", "--corpus", "clustered", "--steps", "5", "--warmup", "2",
             "--min-timed-s", "0.2", "--parity-queries", "0", "--scan-check-queries", "0", "--segment-regime", "0", "--bf16-block-n", "0", "--ref-build-n", "0",
             "--single-query-calls", "0", "--cpu-queries", "0", "--bm25-block", "0", "--iso-recall", "0"]
     import torch
