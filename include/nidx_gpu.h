@@ -52,10 +52,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len);
  * 6: nidx_gpu_build_features; nidx_gpu_vector_build_stats fills ten words (round 6). */
 #define NIDX_GPU_ABI_VERSION 6
 int32_t nidx_gpu_abi_version(void);
-/* What this build of the library contains beyond the product paths: NIDX_GPU_FEATURE_RABITQ_EXPERIMENTS = the two-wave RaBitQ walk
- * and the unrolled instances of the plain one (`make EXPERIMENTS=1`; measurement material, selected by NIDX_GPU_RABITQ_WAVES=2 /
- * NIDX_GPU_RABITQ_PIPE=0 — without the feature the former is ignored and the latter runs the generic instance). */
-#define NIDX_GPU_FEATURE_RABITQ_EXPERIMENTS 1
+/* Bits of optional content this build of the library holds.  No feature bit is currently defined: every build returns 0. */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16

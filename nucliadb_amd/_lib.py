@@ -194,7 +194,6 @@ class Bm25SearchAfterC(C.Structure):
 
 
 ABI_VERSION = 6   # include/nidx_gpu.h: NIDX_GPU_ABI_VERSION
-FEATURE_RABITQ_EXPERIMENTS = 1   # nidx_gpu_build_features()
 
 # name -> (restype, argtypes); the list every `-m "not gpu"` export test walks.
 SIGNATURES = {

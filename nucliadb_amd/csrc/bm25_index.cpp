@@ -76,7 +76,7 @@ struct Bm25Ctx {
     std::vector<uint8_t> w_q_union;
     std::vector<uint64_t> w_postings, w_clause_len;
     std::vector<Bm25ClauseDev> w_dev_clauses;
-    std::vector<Bm25UClause> w_ucl;   // (entries of queries that are not union queries keep whatever they held: never read)
+    std::vector<Bm25StreamClause> w_ucl;   // (entries of queries that are not union queries keep whatever they held: never read)
     std::vector<Bm25AfterDev> w_after;
     DevBuf s_after, s_count, s_total, s_postings, s_key;
     DevBuf s_fuse_done, s_fuse_key, s_fuse_count, s_fuse_total, s_fuse_postings;   // Bm25FusedMerge (s_fuse_done is zeroed when it grows and stays zero between launches)
@@ -84,7 +84,7 @@ struct Bm25Ctx {
     DevBuf s_set_terms, s_set_bits, s_aux_off, s_aux_out_off, s_aux_ids, s_set_counts, s_match_bits, s_match_slot, s_pair_term, s_pair_slot,
         s_facet_counts;
     // packed staging: [clauses | clause offsets], [item_first | work list] in; [doc | score | count | total | postings] out
-    DevBuf s_in_q, s_in_w, s_outpack;
+    DevBuf s_in_q, s_in_w;
     PinBuf h_in_q, h_in_w, h_outpack;
     float kernel_ms = 0.f;   // scoring kernels of the last call through this context
     Bm25Ctx() = default;
@@ -889,12 +889,9 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
     uint64_t slice_postings = BM25_SLICE_POSTINGS;
     const bool force_wide = getenv("NIDX_GPU_BM25_WIDE") != nullptr;   // every query through the general kernel (tests)
     // NIDX_GPU_BM25_UNION: 0 = never a union kernel, 1 = rare-meeting unions through bm25_stream_kernel (default), 2 = every query of
-    // <= 8 plain term clauses through it (tests drive its slow paths with it); 3 / 4 = the same two with bm25_union_kernel (round 3's
-    // first union kernel, kept for comparison)
+    // <= 8 plain term clauses through it (tests drive its slow paths with it)
     int union_mode = 1;
     if (const char *e = getenv("NIDX_GPU_BM25_UNION")) union_mode = atoi(e);
-    const bool lockstep_union = union_mode >= 3;
-    if (lockstep_union) union_mode -= 2;
     (void)max_clauses;
     if (const char *e = getenv("NIDX_GPU_BM25_SLICE")) slice_postings = (uint64_t)std::max(256, atoi(e));
     for (uint64_t c = 0; c < n_clauses; c++) {
@@ -949,9 +946,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
     }
     // The merged hits are written by bm25_merge_kernel straight into the pinned result block (device-visible host memory: ~190 KB of
     // fire-and-forget stores over PCIe per batch) instead of into HBM + a device-to-host transfer queued behind it: one dependent
-    // operation less per batch.  NIDX_GPU_BM25_ZERO_COPY_OUT=0 keeps the transfer (comparison).
-    bool zc_out = true;
-    if (const char *e = getenv("NIDX_GPU_BM25_ZERO_COPY_OUT")) zc_out = atoi(e) != 0;
+    // operation less per batch.
     static_assert(sizeof(Bm25AfterDev) == sizeof(nidx_gpu_bm25_search_after_t), "search-after layout");
     if (after) {
         NIDX_HIP(cx.s_after.reserve((size_t)nq * sizeof(Bm25AfterDev)));
@@ -1205,21 +1200,19 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         // collisions of the kernel's two bitmaps (bm25_stream.hip: 32 Kibit A, 2 Kibit B) — stays inside the 192-entry list:
         // a balanced query keeps ~1 900 postings per slice (the bitmaps allow no more), a long list with two short ones gets ~8 000.
         // A batch alone on the GPU (the blocking entries, the first ticket) keeps the latency shape below.
-        const bool crowded_shape = crowded && !getenv("NIDX_GPU_BM25_SLICE") && !lockstep_union;
+        const bool crowded_shape = crowded && !getenv("NIDX_GPU_BM25_SLICE");
         if (crowded_shape) {
             slice_now = BM25_SLICE_CROWDED;
-            if (const char *e = getenv("NIDX_GPU_BM25_CROWDED_SLICE")) slice_now = (uint64_t)std::max(1024, atoi(e));   // (measurement)
         } else if (!getenv("NIDX_GPU_BM25_SLICE")) {
             const uint64_t budget = (uint64_t)idx->n_cus * 5u * 4u * 15u / 16u;
             // A launch alone lasts as long as its slowest item, so the items are cut to equal COST, not equal length: a posting of the
             // longest clause is streamed once (phase 2), one of any other clause twice (marked in phase 1, scored in phase 3).  Measured on
-            // the bench batch (scripts/r6_bm25_weight.sh): with one-bit bitmaps, when a third of the kernel went into falsely involved
+            // the bench batch (DESIGN-LOG R6.8): with one-bit bitmaps, when a third of the kernel went into falsely involved
             // postings, weight 3 took a launch from 49.5 to 44.5 us; with the three-bit filter of bitmap A weights 1 .. 3 are within
             // 2 us of each other (43.3 - 45.7) and 2 is kept.
             std::vector<uint64_t> &pq = cx.w_postings;
             pq.assign(nq, 0);
             short_weight = 2;
-            if (const char *e = getenv("NIDX_GPU_BM25_SHORT_WEIGHT")) short_weight = (uint64_t)std::max(1, atoi(e));   // (measurement)
             for (uint32_t q = 0; q < nq; q++) {
                 uint64_t sum = 0, longest = 0;
                 for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1]; c++) sum += clen[c], longest = std::max<uint64_t>(longest, clen[c]);
@@ -1287,7 +1280,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 }
                 if (union_mode == 2) q_union[q] = 1;
                 else if (shared * 8.0 <= sum && want <= (double)BM25_MAX_SLICES) q_union[q] = 1;
-                if (q_union[q] && !lockstep_union) slices = (uint32_t)std::min<double>(BM25_MAX_SLICES, std::max<double>(slices, want));
+                if (q_union[q]) slices = (uint32_t)std::min<double>(BM25_MAX_SLICES, std::max<double>(slices, want));
 
             }
             const Bm25Work w{q, 0, slices, (uint32_t)c0, (uint32_t)(c1 - c0)};
@@ -1315,8 +1308,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 }
             }
         }
-        // the union kernel's clause table: list base / length / weight / attributes per clause of this segment
-        std::vector<Bm25UClause> &ucl = cx.w_ucl;
+        // the stream kernel's clause table: list base / length / weight / attributes per clause of this segment
+        std::vector<Bm25StreamClause> &ucl = cx.w_ucl;
         ucl.resize(n_union ? n_clauses : 0);
         // A floor under the k-th best score of a query whose clauses are all Should terms (every document of any clause is a hit): clause c
         // alone gives >= BM25_FLOOR_RANKS[j] >= k documents a score >= weight(c) * quotient(tf = 1, floor_fn[term][j]); the best clause's bound
@@ -1345,8 +1338,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 const uint64_t b = seg.term_offsets_host[clauses[c].term];
                 const uint64_t l = clen[c];
                 if (l > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a posting list of one segment holds more than 2^32 - 1 postings");
-                ucl[c] = Bm25UClause{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)l, dev_clauses[c].weight,
-                                     (uint32_t)dev_clauses[c].occur | ((uint32_t)dev_clauses[c].mode << 8), floor_bits, 0u, 0u};
+                ucl[c] = Bm25StreamClause{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)l, dev_clauses[c].weight,
+                                          (uint32_t)dev_clauses[c].occur | ((uint32_t)dev_clauses[c].mode << 8), floor_bits, 0u, 0u};
             }
         }
         t_work += now_us() - t_w0;
@@ -1355,7 +1348,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         const size_t if_bytes = ((size_t)(nq + 1) * 4 + 31) & ~(size_t)31;   // 32-byte pieces: the clause table is read with 16-byte scalar loads
         const size_t work_bytes = (nw * sizeof(Bm25Work) + 31) & ~(size_t)31;
         const size_t items_bytes = (nw * 4 + 31) & ~(size_t)31;
-        const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl.size() * sizeof(Bm25UClause);
+        const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl.size() * sizeof(Bm25StreamClause);
         const size_t w_at = fused_in ? inq_al : 0;   // the work list's place in the block: behind the clause block, or at its head
         NIDX_HIP(cx.s_in_w.reserve(w_at + inw_bytes));
         NIDX_HIP(cx.h_in_w.reserve(w_at + inw_bytes));
@@ -1369,7 +1362,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         memcpy(h_w, item_first.data(), (size_t)(nq + 1) * 4);
         memcpy(h_w + if_bytes, work.data(), nw * sizeof(Bm25Work));
         memcpy(h_w + if_bytes + work_bytes, item_list.data(), nw * 4);
-        if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl.size() * sizeof(Bm25UClause));
+        if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl.size() * sizeof(Bm25StreamClause));
         NIDX_HIP(hipMemcpyAsync(cx.s_in_w.p, cx.h_in_w.p, w_at + inw_bytes, hipMemcpyHostToDevice, cx.stream));
         const uint32_t *d_item_first = reinterpret_cast<const uint32_t *>(d_w);
         const Bm25Work *d_work = reinterpret_cast<const Bm25Work *>(d_w + if_bytes);
@@ -1380,15 +1373,9 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         const bool cat = idx->concatenated();
         const size_t out_bytes = o_seg + (cat ? (size_t)nq * kk * 4 : 0);   // concatenated layout: + segment u32 [nq][kk]
         NIDX_HIP(cx.h_outpack.reserve(out_bytes));
-        unsigned char *d_out = nullptr;
-        if (zc_out) {
-            void *dp = nullptr;
-            NIDX_HIP(hipHostGetDevicePointer(&dp, cx.h_outpack.p, 0));
-            d_out = static_cast<unsigned char *>(dp);
-        } else {
-            NIDX_HIP(cx.s_outpack.reserve(out_bytes));
-            d_out = cx.s_outpack.as<unsigned char>();
-        }
+        void *dp = nullptr;
+        NIDX_HIP(hipHostGetDevicePointer(&dp, cx.h_outpack.p, 0));
+        unsigned char *d_out = static_cast<unsigned char *>(dp);
         NIDX_HIP(cx.s_count.reserve(nw * 4));
         NIDX_HIP(cx.s_total.reserve(nw * 8));
         NIDX_HIP(cx.s_postings.reserve(nw * 8));
@@ -1428,7 +1415,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         a.match_bits = n_slots ? cx.s_match_bits.as<uint32_t>() : nullptr;
         a.match_slot = n_slots ? cx.s_match_slot.as<int>() : nullptr;
         a.match_words = match_words;
-        a.uclauses = reinterpret_cast<const Bm25UClause *>(d_w + if_bytes + work_bytes + items_bytes);
+        a.uclauses = reinterpret_cast<const Bm25StreamClause *>(d_w + if_bytes + work_bytes + items_bytes);
         a.dbg = nullptr;
         DevBuf dbgbuf;
         if (getenv("NIDX_GPU_BM25_DEBUG")) {
@@ -1454,11 +1441,9 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             mg.n_seg = idx->n_segments;
             mg.out_seg = reinterpret_cast<uint32_t *>(d_out + o_seg);
         }
-        const char *ab = getenv("NIDX_GPU_BM25_ABLATE_MERGE");   // measurement (wrong hits): 1 no merge launch, 2 an empty one, 3 one that writes nothing
-        mg.ablate = ab ? atoi(ab) : 0;
         // When every item of the batch goes through the stream kernel and k <= 64, the scoring launch merges as well (Bm25FusedMerge): the last wave
         // of every query's slices does what bm25_merge_kernel would do in a launch of its own.  NIDX_GPU_BM25_FUSED_MERGE=0 keeps the two launches.
-        bool fused_merge = n_union == nw && nw > 0 && kk <= 64 && !lockstep_union && !a.dbg && (mg.ablate == 0 || mg.ablate == 3);
+        bool fused_merge = n_union == nw && nw > 0 && kk <= 64 && !a.dbg;
         if (const char *fe = getenv("NIDX_GPU_BM25_FUSED_MERGE")) fused_merge = fused_merge && atoi(fe) != 0;
         if (fused_merge) {
             const size_t done_bytes = (size_t)nq * (BM25_FUSE_MAX_GROUPS + 1u) * 4;
@@ -1483,21 +1468,19 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             a.fm.seg_base = mg.seg_base;
             a.fm.n_seg = mg.n_seg;
             a.fm.out_seg = mg.out_seg;
-            a.fm.ablate = mg.ablate;
         }
         NIDX_HIP(hipEventRecord(cx.ev0, cx.stream));
         {
             const bool extras = a.alive != nullptr || a.match_bits != nullptr || a.order_key != nullptr || a.after != nullptr;
-            NIDX_HIP((lockstep_union ? launch_bm25_union : launch_bm25_stream)(a, d_items, n_union, extras, cx.stream));
+            NIDX_HIP(launch_bm25_stream(a, d_items, n_union, extras, cx.stream));
         }
         NIDX_HIP(launch_bm25_search(a, d_items + n_union, n_fast, d_items + n_union + n_fast, n_wide, wide_max_clauses, cx.stream));
         NIDX_HIP(hipEventRecord(cx.ev1, cx.stream));
-        if (!fused_merge && mg.ablate != 1) NIDX_HIP(launch_bm25_merge(mg, nq, cx.stream));
+        if (!fused_merge) NIDX_HIP(launch_bm25_merge(mg, nq, cx.stream));
         if (n_slots)
             NIDX_HIP(launch_facet_count(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), cx.s_pair_term.as<uint32_t>(),
                                         cx.s_pair_slot.as<int>(), (uint32_t)n_pairs, cx.s_match_bits.as<uint32_t>(), match_words,
                                         cx.s_facet_counts.as<unsigned long long>(), cx.stream));
-        if (!zc_out) NIDX_HIP(hipMemcpyAsync(cx.h_outpack.p, cx.s_outpack.p, out_bytes, hipMemcpyDeviceToHost, cx.stream));
         const unsigned char *h_out = cx.h_outpack.as<unsigned char>();
         const uint32_t *h_doc = reinterpret_cast<const uint32_t *>(h_out + o_doc);
         const float *h_score = reinterpret_cast<const float *>(h_out + o_score);

@@ -1,14 +1,13 @@
 // bm25_stream.hip — BM25 scoring for term unions whose posting lists rarely meet, term at a time (gfx950).
 //
-// Same contract as bm25_fast_kernel (bm25.hip) and bm25_union_kernel (bm25_union.hip): one WAVE per work item = (query, doc-id slice),
+// Same contract as bm25_fast_kernel (bm25.hip): one WAVE per work item = (query, doc-id slice),
 // a query of <= 8 plain term clauses; it computes what tantivy computes under TextReaderService::do_search / the paragraph
 // Searcher::do_search (nidx_text/src/reader.rs:433-435, nidx_paragraph/src/reader.rs:244-348): Bm25Weight::score per posting,
 // BooleanQuery sums in clause order, TopDocs (score desc, DocAddress asc), Count.
 //
-// bm25_union_kernel walks all lists in lockstep doc-id windows of 8 rows held in registers; its bookkeeping (window plan, row
-// descriptors, three filter passes per row, one serial list insertion per candidate) costs ~290 instruction issues per 64-posting row,
-// and instruction issue is what bounds it.  Here every clause's part of the slice is STREAMED on its own — the
-// two bounds of the slice are found by the side-by-side search first, so a clause is a plain counted loop over rows with nothing to plan:
+// Every clause's part of the slice is STREAMED on its own — the two bounds of the slice are found by the side-by-side search first, so a
+// clause is a plain counted loop over rows with nothing to plan (a kernel that walked all lists in lockstep doc-id windows was bound by
+// the instruction issue of its per-row bookkeeping and lost to this form: DESIGN-LOG.md section 4.4):
 //   phase 1  every clause but the longest: doc ids only; each posting sets its bit of bitmap A (32 Kibit, ds_or_rtn).  A bit that was
 //            already set marks a POSSIBLE second posting of the same document: that posting sets the document's bit in bitmap B (2 Kibit).
 //   phase 2  the longest clause (it sets nothing — its documents are distinct; its first four rows have been in flight since before phase 1):
@@ -172,10 +171,6 @@ __device__ inline void bs_fused_merge(const Bm25Args &a, uint32_t q, uint32_t it
             acc = bs_merge_sorted(acc, key);
         }
     }
-    if (f.ablate == 3) {
-        if (acc == 12345ull && lane == 0) f.out_count[q] = 1;   // (keeps the merge alive)
-        return;
-    }
     // what bm25_merge_kernel writes (bm25.hip)
     const bool valid = acc != NIDX_EMPTY_KEY && (uint32_t)lane < k;
     const uint32_t cnt = (uint32_t)__popcll(__ballot(valid));
@@ -256,7 +251,7 @@ __global__ __launch_bounds__(256, (KL == 1 ? BS_MIN_WAVES : 4)) void bm25_stream
     uint32_t len_l = 0, attr_l = 0, w_bits_l = 0, floor_bits_l = 0xff800000u;
     unsigned long long b_l = 0;
     if (lane < C) {
-        const Bm25UClause uc = a.uclauses[clause_first + lane];
+        const Bm25StreamClause uc = a.uclauses[clause_first + lane];
         b_l = ((unsigned long long)uc.b_hi << 32) | uc.b_lo;
         len_l = uc.len;
         attr_l = uc.attr;
@@ -646,10 +641,6 @@ __global__ __launch_bounds__(256, (KL == 1 ? BS_MIN_WAVES : 4)) void bm25_stream
                                     inv[r] = in[r] && __builtin_amdgcn_ubfe(bw[r], h[r], 1u) != 0u;
                                 }
                             }
-#ifdef BS_ABLATE_NOINV   /* measurement only (wrong results): no posting is ever involved — the upper bound of what a sharper filter could save */
-#pragma unroll
-                            for (int r = 0; r < 4; r++) inv[r] = false;
-#endif
                             if (__ballot(inv[0] || inv[1] || inv[2] || inv[3])) {
 #pragma unroll
                                 for (int r = 0; r < 4; r++) {

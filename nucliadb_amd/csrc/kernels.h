@@ -286,8 +286,6 @@ struct RabitqSearchArgs {
     uint32_t *out_count;
     uint32_t *stats;          // nullptr or [n_queries][NIDX_STAT_STRIDE]: estimates, expansions, rows re-ranked, flags
     uint32_t *flag_word = nullptr;  // nullptr or [1]: OR of the flags any query raised (see HnswSearchArgs)
-    uint32_t no_speculation = 0;    // two-wave walk, measurement: 1 = the fetcher never runs ahead of the controller
-    unsigned long long *dbg = nullptr;   // two-wave walk, measurement: [16] cycle totals of the two waves (NIDX_GPU_RABITQ_DEBUG)
     uint32_t seen_log2 = 0;         // pipelined walk: log2 words of the LDS cache of known-visited ids, 0 = none (rabitq_seen_log2())
     // hnsw: [n_queries][tie_stride] — where a walk keeps the evicted candidates that still tie with its worst result once the 64 in
     // LDS are full (the reference's BinaryHeap is unbounded, hnsw/search.rs:252-299); rabitq_tie_stride(ef) entries per query always
@@ -303,8 +301,6 @@ hipError_t launch_rabitq_query(const float *queries, uint32_t nq, uint32_t dp, u
 hipError_t launch_rabitq_bf(const RabitqSearchArgs &a, hipStream_t s);
 hipError_t launch_rabitq_hnsw(const RabitqSearchArgs &a, hipStream_t s);
 // several segments' walks in one launch: `table` (device, n_table records agreeing in shape with `shape`); block b = query b % nq of record b / nq
-bool rabitq_two_waves();   // true with NIDX_GPU_RABITQ_WAVES=2 in a `make EXPERIMENTS=1` library (the two-wave walk: measured slower, kept for comparison)
-bool rabitq_has_experiments();
 uint32_t rabitq_seen_log2();   // 9; NIDX_GPU_RABITQ_SEEN=0 / 8...13 (measurement)
 hipError_t launch_rabitq_hnsw_segments(const RabitqSearchArgs *table, uint32_t n_table, const RabitqSearchArgs &shape, hipStream_t s);
 
@@ -365,13 +361,14 @@ struct Bm25AfterDev {  // same layout as nidx_gpu_bm25_search_after_t
 struct Bm25Work {  // one work item: query `query`, doc-id slice `slice` of `n_slices`; its clause records [clause_first, + n_clauses)
     uint32_t query, slice, n_slices, clause_first, n_clauses;
 };
-// bm25_union_kernel's clause table (one record per query clause, per segment): the list's first posting, its length, the
-// Bm25Weight (or constant score) and occur | mode << 8 — everything the kernel needs of a clause without touching term_offsets
-struct Bm25UClause {
+// bm25_stream_kernel's clause table (one record per query clause, per segment): the list's first posting, its length, the
+// Bm25Weight (or constant score), occur | mode << 8 and the query's score floor — everything the kernel needs of a clause without
+// touching term_offsets
+struct Bm25StreamClause {
     uint32_t b_lo, b_hi, len;
     float weight;
     uint32_t attr;
-    uint32_t floor_bits;   // f32: a score at least k documents of the QUERY reach (the same value in every clause of a query; -inf = none): bm25_stream_kernel
+    uint32_t floor_bits;   // f32: a score at least k documents of the QUERY reach (the same value in every clause of a query; -inf = none)
     uint32_t pad1, pad2;
 };
 #define BM25_ITEM_THREADS 64      /* threads per work item (64 = one wave: no block barriers) */
@@ -380,7 +377,7 @@ struct Bm25UClause {
 #define BM25_MAX_SLICES 256
 // bm25_stream_kernel's fused merge (k <= 64, every item of the launch a stream item): the LAST wave to finish among a group of eight slices of
 // a query merges the group's lists, the last group to finish merges the groups' lists and writes what bm25_merge_kernel would have written —
-// no second launch behind the scoring kernel (3.4 us of every 30 us batch in the pipelined bench; scripts/r6_ab_merge.sh).  A wave merges at
+// no second launch behind the scoring kernel (3.4 us of every 30 us batch in the pipelined bench; DESIGN-LOG R6.8).  A wave merges at
 // most 7 + 31 lists whatever the query's length.  `done` holds the arrival counters ([n_queries][33]: the query's, then one per group); whoever
 // completes a count resets it, so the array is zero between launches.
 #define BM25_FUSE_GROUP 8u
@@ -397,7 +394,6 @@ struct Bm25FusedMerge {
     const uint32_t *seg_base = nullptr;
     uint32_t n_seg = 0;
     uint32_t *out_seg = nullptr;
-    int ablate = 0;                 // measurement (NIDX_GPU_BM25_ABLATE_MERGE=3 with the fused merge): merge, write nothing
 };
 struct Bm25Args {
     const Bm25Work *work;
@@ -429,7 +425,7 @@ struct Bm25Args {
     uint32_t *match_bits;                   // [n_slots][match_words]
     const int *match_slot;                  // [n_queries] or nullptr
     uint32_t match_words;
-    const Bm25UClause *uclauses;            // [n_clauses of the batch] (bm25_union_kernel), parallel to `clauses`
+    const Bm25StreamClause *uclauses;       // [n_clauses of the batch] (bm25_stream_kernel), parallel to `clauses`
     Bm25FusedMerge fm;                      // bm25_stream_kernel only
 };
 #define BM25_AUX_TERM 0x80000000u
@@ -448,16 +444,14 @@ struct Bm25MergeArgs {  // per query: merge the key lists of its work items [ite
     const uint32_t *seg_base = nullptr;
     uint32_t n_seg = 0;
     uint32_t *out_seg = nullptr;
-    int ablate = 0;   // measurement (NIDX_GPU_BM25_ABLATE_MERGE = 2 / 3): return at once / merge but write nothing
 };
 hipError_t launch_bm25_merge(const Bm25MergeArgs &m, uint32_t n_queries, hipStream_t s);
 #define BM25_FAST_CLAUSES 8   /* queries of at most this many clauses take bm25_fast_kernel */
 #define BM25_LIST_PAD_BYTES 8192  /* slack behind the posting arrays: the kernels load whole 64-posting rows unconditionally */
 hipError_t launch_bm25_search(const Bm25Args &a, const uint32_t *fast_items, uint32_t n_fast, const uint32_t *wide_items, uint32_t n_wide,
                               uint32_t max_clauses, hipStream_t s);
-// term unions whose lists rarely meet (bm25_union.hip); extras = alive bitset / facet bitsets / order by a fast field / search-after
-hipError_t launch_bm25_union(const Bm25Args &a, const uint32_t *items, uint32_t n_items, bool extras, hipStream_t s);
-// the same queries term at a time (bm25_stream.hip): the default; launch_bm25_union stays selectable for comparison
+// term unions whose lists rarely meet, term at a time (bm25_stream.hip); extras = alive bitset / facet bitsets / order by a fast field /
+// search-after
 hipError_t launch_bm25_stream(const Bm25Args &a, const uint32_t *items, uint32_t n_items, bool extras, hipStream_t s);
 
 // ---- BM25 surroundings (bm25_aux.hip) ----

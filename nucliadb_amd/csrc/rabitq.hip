@@ -928,57 +928,6 @@ __global__ __launch_bounds__(64) void rabitq_hnsw_segments_kernel(const RabitqSe
 
 #define RQ_NONE 0xffffffffu
 
-#ifdef NIDX_RABITQ_EXPERIMENTS   /* make EXPERIMENTS=1: the two-wave walk, measured slower (DESIGN-LOG: RaBitQ, round 5), kept for the comparison */
-// ---- HNSW, RaBitQ arm, TWO waves per query (round 5; NOT the default: see the measurements below) ------------------------------
-// The walk above is a chain of ~1 100 dependent expansions per query, and a lone wave pays every link in full: the edge record and
-// the neighbours' codes are two memory round trips (43 % of the walk's cycles), the admissions ~150 dependent instructions each
-// (36 %), with nothing to overlap either (one wave per SIMD at batch 1 024: 0.026 of the HBM roofline, rounds 1-4).  Here a
-// workgroup of two waves walks one query:
-//   wave 0, the controller  keeps the result set (RqLayer: the directory in its registers), pops, replays the admission rule
-//                           `score > ws || len < k` in edge order (search.rs:287-295) — the code of the one-wave kernel;
-//   wave 1, the fetcher     expands a node: edge record, the visited test-and-set of every neighbour (layer 0: the per-query
-//                           bitset in HBM, atomicOr; above: the LDS hash), the codes of the fresh ones, their estimates; it
-//                           leaves (address, estimate) of the fresh neighbours in edge order in LDS.
-// While the controller admits the neighbours of expansion i, the fetcher already expands the node the NEXT pop will return —
-// predicted exactly: the best of {best unexpanded entry of the result set, best admissible new neighbour}; the best new neighbour
-// that beats the current worst result is always admitted, and nothing admitted can rank above it.  The speculation is complete
-// (it sets the visited bits), so a confirmed one costs nothing more; the pop that follows the admissions verifies it, and a
-// mismatch — possible with exactly tied scores or when the ties side list decides — rolls it back: the fetcher clears exactly
-// the bits it set (nobody else writes this query's bitset) and expands the popped node instead.  Upper layers (k = 1, a handful
-// of expansions, the LDS hash has no removal) run without speculation.  The fetcher also keeps the edge record of the runner-up
-// candidate (read-only, so no rollback): when that node is expanded next, its fetch starts at the codes.
-// Results are the one-wave kernel's bit for bit — same admission replay on the same values in the same order; only the moment a
-// visited bit is set moves, never whether it is set when an expansion that was really popped tests it
-// (tests/test_rabitq_gpu.py, tests/test_serving_gpu.py::test_rabitq_segments_share_one_launch run both kernels).
-//
-// MEASURED (1 M x 768 clustered, batch 1 024, k = 10; gpurun_out/r5ab): the prediction is right for 99.2 % of the
-// expansions and 84 % of them find their edge record held — and the launch is SLOWER than the one-wave kernel's: 7.6 ms against 6.6 ms.
-// Per expansion (NIDX_GPU_RABITQ_DEBUG): the fetcher's expansion takes 4.3 k cycles and the controller's admissions + pop 3.6 k, but the
-// two stand at their second meeting point for another 2.1 k / 2.7 k cycles each — a meeting costs ~2 k cycles whatever implements it
-// (s_barrier, or two sequence words polled in LDS: 8.0 ms), with the waves on one SIMD or on two (a four-wave workgroup whose other
-// two waves leave at once), so the overlap the design was made for (4.3 k beside 3.6 k instead of behind it) is spent on the meetings,
-// and the prediction + hand-over add 1.7 k more.  The one-wave kernel therefore stays the default (NIDX_GPU_RABITQ_WAVES=2 selects this
-// one); what would help is fewer meetings per walk — a fetcher that runs several expansions ahead through a queue — which needs the
-// speculation to be exact more than one step ahead (it is not: the best new neighbour of expansion i + 1 is unknown at i).
-struct RqFetchBuf {      // one expansion, written by the fetcher
-    uint32_t node, n, flags, pad;
-    uint32_t addr[64];   // the fresh neighbours in edge order
-    float est[64];
-};
-#define RQ_EDGE_CACHE 3
-struct RqCtl {
-    uint32_t pred, pred2, pred3, state, fetch_node, abort, ep, pad;
-    uint32_t seq[4];                        // [0] / [1]: meeting counts of the controller / the fetcher
-    uint32_t cache_node[4];                 // the layer-0 edge records the fetcher holds (RQ_NONE = free)
-    uint32_t cache_w[RQ_EDGE_CACHE][64];
-};
-enum { RQ_STATE_HIT = 0, RQ_STATE_MISS = 1, RQ_STATE_DONE = 2 };
-
-static size_t rq_smem2_bytes(uint32_t nw, uint32_t dp, uint32_t k, uint32_t ef) {
-    return rq_smem_bytes(nw, dp, k, ef, true) + 2 * sizeof(RqFetchBuf) + sizeof(RqCtl);
-}
-#endif  // NIDX_RABITQ_EXPERIMENTS
-
 // the best and (when they sit in the same chunk) second- and third-best unexpanded keys of the result set; 0 = none.  Changes nothing
 // but the hint dcur (chunks before it hold expanded keys only — still true afterwards).
 __device__ inline void rq_peek3(RqLayer &L, int lane, uint64_t &k1, uint64_t &k2, uint64_t &k3) {
@@ -1003,386 +952,12 @@ __device__ inline void rq_peek3(RqLayer &L, int lane, uint64_t &k1, uint64_t &k2
     }
 }
 
-// the fetcher's expansion of `node` on `layer` -> out.  n2 / n3 (layer 0, or RQ_NONE): the candidates most likely to be expanded after
-// it — their edge records are requested along with this expansion's loads and kept in a three-record cache (read-only data: nothing to
-// roll back), so that an expansion whose node was foreseen starts at its neighbours' codes: one memory round trip instead of two.
-#ifdef NIDX_RABITQ_EXPERIMENTS
-template <int NW>
-__device__ inline void rq_fetch(const RabitqSearchArgs &a, const RqShared &sh, RqCtl *ctl, RqFetchBuf *out, uint32_t node, uint32_t n2, uint32_t n3,
-                                int layer, uint32_t *gvis, const RabitqQueryDev &qc, uint32_t nw, uint32_t &vis_count, uint32_t &cache_hits, int lane) {
-    uint32_t w;
-    uint32_t pf_node[2] = {RQ_NONE, RQ_NONE}, pf_w[2] = {0u, 0u};
-    int pf_slot[2] = {-1, -1};
-    if (layer == 0) {
-        uint32_t cn[RQ_EDGE_CACHE];
-#pragma unroll
-        for (int i = 0; i < RQ_EDGE_CACHE; i++) cn[i] = (uint32_t)uni((int)ctl->cache_node[i]);
-        int hit = -1;
-#pragma unroll
-        for (int i = 0; i < RQ_EDGE_CACHE; i++)
-            if (cn[i] == node) hit = i;
-        // what to request ahead: n2 / n3 unless already held (or the node itself); they take the slots that hold neither of them
-        // (the record of `node` is read into registers first, so its slot is free too)
-        const uint32_t want[2] = {n2, n3 == n2 ? RQ_NONE : n3};
-        bool keep[RQ_EDGE_CACHE];
-#pragma unroll
-        for (int i = 0; i < RQ_EDGE_CACHE; i++) keep[i] = cn[i] != RQ_NONE && cn[i] != node && (cn[i] == want[0] || cn[i] == want[1]);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            if (want[j] == RQ_NONE || want[j] == node) continue;
-            bool held = false;
-#pragma unroll
-            for (int i = 0; i < RQ_EDGE_CACHE; i++) held |= cn[i] == want[j];
-            if (held) continue;
-            int slot = -1;
-#pragma unroll
-            for (int i = RQ_EDGE_CACHE - 1; i >= 0; i--)
-                if (!keep[i]) slot = i;
-            if (slot < 0) continue;
-            keep[slot] = true;
-            pf_node[j] = want[j];
-            pf_slot[j] = slot;
-            pf_w[j] = load_edge_raw(a.g, want[j], 0, lane);
-        }
-        // (two separate loads and a select of their VALUES: a select of the two addresses made the compiler emit one FLAT load behind an
-        // s_waitcnt vmcnt(0) — the records requested ahead just above had to land before this expansion's own loads could even start)
-        const uint32_t w_held = ctl->cache_w[hit >= 0 ? hit : 0][lane];
-        uint32_t w_mem = 0;
-        if (hit < 0) w_mem = load_edge_raw(a.g, node, 0, lane);
-        else cache_hits++;
-        asm volatile("" : "+v"(w_mem));   // keeps the two loads apart
-        w = hit >= 0 ? w_held : w_mem;
-    } else {
-        w = load_edge_raw(a.g, node, layer, lane);
-    }
-    const uint32_t deg = lane_u32(w, 0);
-    const bool is_edge = lane >= 1 && lane <= (int)deg;
-    // the code of every neighbour is requested together with the visited test (one round trip); codes of visited ones are dropped
-    RqCode<NW> code;
-    const uint8_t *rec = a.quant + (size_t)(is_edge ? w : 0u) * a.rec_len;
-    if (is_edge) rq_load_code<NW>(rec, code);
-    bool fresh = false;
-    if (is_edge) {
-        if (layer > 0) fresh = vis_insert(sh.vis, RABITQ_UPPER_VIS_LOG2, w);
-        else fresh = (atomicOr(&gvis[w >> 5], 1u << (w & 31)) & (1u << (w & 31))) == 0;
-    }
-    const unsigned long long fm = __ballot(fresh);
-    uint32_t oflags = 0;
-    if (layer > 0) {
-        vis_count += (uint32_t)__popcll(fm);
-        if (vis_count > (3u << RABITQ_UPPER_VIS_LOG2) / 4u) oflags = NIDX_FLAG_VISITED_OVERFLOW;
-    }
-    float est = 0.f, err = 0.f;
-    if (fresh) rq_score_code<NW>(code, rec, sh.planes, nw, qc, est, err);
-    (void)err;
-    const uint32_t pos = (uint32_t)__popcll(fm & ((1ull << lane) - 1ull));
-    if (fresh) {
-        out->addr[pos] = w;
-        out->est[pos] = est;
-    }
-    if (lane == 0) {
-        out->node = node;
-        out->n = (uint32_t)__popcll(fm);
-        out->flags = oflags;
-    }
-    if (layer == 0) {
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-            if (pf_slot[j] >= 0) {
-                ctl->cache_w[pf_slot[j]][lane] = pf_w[j];
-                if (lane == 0) ctl->cache_node[pf_slot[j]] = pf_node[j];
-            }
-    }
-}
-
-// undo a speculative layer-0 fetch that was not confirmed: clear exactly the visited bits it set; returns after they are cleared
-__device__ inline void rq_rollback(const RqFetchBuf *b, uint32_t *gvis, int lane) {
-    const uint32_t n = (uint32_t)uni((int)b->n);
-    uint32_t old = 0;
-    if ((uint32_t)lane < n) {
-        const uint32_t x = b->addr[lane];
-        old = atomicAnd(&gvis[x >> 5], ~(1u << (x & 31)));
-    }
-    asm volatile("" ::"v"(old));   // the returned words are waited for: the next fetch must find the bits cleared
-}
-
-template <int NW>
-__device__ inline void rabitq_hnsw2_body(const RabitqSearchArgs &a, uint32_t qi, unsigned char *smem) {
-    const int lane = threadIdx.x & 63;
-    const bool w0 = (threadIdx.x >> 6) == 0;
-    const uint32_t nw = a.seg.dim / 64u;
-    RqShared sh = rq_carve(smem, nw, a.seg.dp, a.k, a.ef);
-    RqFetchBuf *buf = reinterpret_cast<RqFetchBuf *>(reinterpret_cast<unsigned char *>(sh.vis) + ((size_t)4 << RABITQ_UPPER_VIS_LOG2));
-    RqCtl *ctl = reinterpret_cast<RqCtl *>(buf + 2);
-    {
-        const uint64_t *gp = a.planes + (size_t)qi * 4u * nw;
-        for (uint32_t i = threadIdx.x; i < 4u * nw; i += 128) sh.planes[i] = gp[i];
-        const float *gq = a.queries + (size_t)qi * a.seg.dp;
-        for (uint32_t i = threadIdx.x; i < a.seg.dp; i += 128) sh.q[i] = gq[i];
-    }
-    const RabitqQueryDev qc = a.qd[qi];
-    uint32_t *gvis = a.visited + (size_t)qi * a.vis_words;  // layer-0 visited bitset (zeroed by the host)
-    uint32_t n_est = 0, n_exp = 0, n_hit = 0, flags = 0;   // controller
-    uint32_t vis_count = 0, cache_hits = 0;                // fetcher (upper layers' visited count; layer-0 expansions whose edge record was held)
-    uint64_t cyc_ctl = 0, cyc_wait = 0, cyc_ins = 0, cyc_fetch = 0;
-    uint64_t dbg_b1 = 0, dbg_b2 = 0, dbg_nf = 0;   // this wave's cycles inside barrier 1 / barrier 2 / the need_fetch barrier (NIDX_GPU_RABITQ_DEBUG)
-    // (s_memtime is a scalar MEMORY instruction, ~100+ cycles each with its s_waitcnt: the cycle split is taken only when the caller asked
-    // for counters or the debug totals — the timed launches of bench.py do not)
-    const bool timing = a.stats != nullptr || a.dbg != nullptr;
-    auto now = [&]() -> uint64_t { return timing ? (uint64_t)clock64() : 0ull; };
-    const uint64_t t_start = now();
-    if (threadIdx.x == 0) ctl->seq[0] = ctl->seq[1] = 0;
-    __syncthreads();
-    // NIDX_GPU_RABITQ_SPEC=0 (measurement): no speculation — the two waves take turns (admit + pop, then fetch)
-    const bool speculate = (a.no_speculation & 1u) == 0;
-    // The two waves meet twice per expansion: s_barrier.  NIDX_GPU_RABITQ_SPEC=2/3 meets through two sequence words in LDS instead — each
-    // wave publishes its count and polls the other's (measured slower: 8.0 ms against 7.6 ms).
-    const bool spin = (a.no_speculation & 2u) != 0;
-    uint32_t my_seq = 0;
-    typedef volatile __attribute__((address_space(3))) uint32_t lds_u32;   // (a generic pointer made these FLAT accesses with system-scope bits)
-    lds_u32 *seqw = (lds_u32 *)(&ctl->seq[0]);
-    auto meet = [&]() {
-        if (!spin) {
-            __syncthreads();
-            return;
-        }
-        my_seq++;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        seqw[w0 ? 0 : 1] = my_seq;
-        while ((uint32_t)uni((int)seqw[w0 ? 1 : 0]) < my_seq) __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
-
-    uint32_t ep = a.g.ep_node;
-    RqLayer L;
-    L.res = sh.res;
-    L.ties = sh.ties;
-    L.spill = a.tie_spill ? a.tie_spill + (size_t)qi * a.tie_stride : nullptr;
-    L.spill_cap = (int)a.tie_stride;
-    for (int layer = (int)a.g.ep_layer; layer >= 0; layer--) {
-        const int kk = layer == 0 ? (int)a.ef : 1;
-        if (w0) {
-            L.init((int)rq_chunks((uint32_t)kk));
-            // the entry point is admitted unconditionally (search.rs:256-261) and is the first pop
-            float est, err;
-            rabitq_estimate<NW>(a.quant + (size_t)ep * a.rec_len, sh.planes, nw, qc, est, err);
-            n_est++;
-            rq_admit(L, kk, est, ep, lane, flags);
-            uint32_t node = ep, next;
-            rq_pop(L, lane, node, next);
-            if (lane == 0) {
-                ctl->fetch_node = node;
-                ctl->pred = RQ_NONE;
-                ctl->pred2 = RQ_NONE;
-                ctl->pred3 = RQ_NONE;
-                ctl->abort = 0;
-            }
-        } else {
-            if (layer > 0) {
-                for (uint32_t i = lane; i < (1u << RABITQ_UPPER_VIS_LOG2); i += 64) sh.vis[i] = NIDX_VIS_EMPTY;
-                if (lane == 0) vis_insert(sh.vis, RABITQ_UPPER_VIS_LOG2, ep);
-                vis_count = 1;
-            } else if (lane == 0) {
-                atomicOr(&gvis[ep >> 5], 1u << (ep & 31));
-                for (int i = 0; i < 4; i++) ctl->cache_node[i] = RQ_NONE;
-            }
-        }
-        meet();
-        int cur = 0;
-        bool need_fetch = true;
-        for (;;) {
-            if (need_fetch) {
-                if (!w0) rq_fetch<NW>(a, sh, ctl, &buf[cur], (uint32_t)uni((int)ctl->fetch_node), RQ_NONE, RQ_NONE, layer, gvis, qc, nw, vis_count, cache_hits, lane);
-                const uint64_t tw = now();
-                meet();
-                cyc_wait += now() - tw;
-                dbg_nf += now() - tw;
-            }
-            // ---- the controller takes the expansion in buf[cur] and names the node the next pop will return ----
-            bool fresh = false;
-            float fest = 0.f;
-            uint32_t faddr = 0;
-            const uint64_t tc = now();
-            if (w0) {
-                const RqFetchBuf *b = &buf[cur];
-                const uint32_t fn = (uint32_t)uni((int)b->n), bflags = (uint32_t)uni((int)b->flags);
-                n_exp++;
-                if (bflags) {
-                    flags |= bflags;   // the upper-layer visited table is 3/4 full: this layer ends here (like the one-wave kernel)
-                    if (lane == 0) {
-                        ctl->abort = 1;
-                        ctl->pred = RQ_NONE;
-                        ctl->pred2 = RQ_NONE;
-                        ctl->pred3 = RQ_NONE;
-                    }
-                } else {
-                    n_est += fn;
-                    fresh = (uint32_t)lane < fn;
-                    fest = fresh ? b->est[lane] : 0.f;
-                    faddr = fresh ? b->addr[lane] : 0u;
-                    uint32_t p1 = RQ_NONE, p2 = RQ_NONE, p3 = RQ_NONE;
-                    if (layer == 0 && speculate) {
-                        L.len = uni(L.len);
-                        L.worst = uni64(L.worst);
-                        const float ws = rank_key_score(L.worst);
-                        const bool full = L.len >= kk;
-                        const uint64_t key_new = (fresh && (!full || fest > ws)) ? rq_key(fest, faddr, 1u) : 0ull;
-                        const uint64_t best_new = wave_max_u64(key_new);
-                        uint64_t pk1, pk2, pk3;
-                        rq_peek3(L, lane, pk1, pk2, pk3);
-                        // the three best of {best new neighbour, pk1 >= pk2 >= pk3}: the first is the prediction, the others the
-                        // candidates whose edge records the fetcher requests ahead
-                        uint64_t a1, a2, a3;
-                        if (best_new > pk1) a1 = best_new, a2 = pk1, a3 = pk2;
-                        else if (best_new > pk2) a1 = pk1, a2 = best_new, a3 = pk2;
-                        else if (best_new > pk3) a1 = pk1, a2 = pk2, a3 = best_new;
-                        else a1 = pk1, a2 = pk2, a3 = pk3;
-                        if (a1) p1 = rq_addr(a1);
-                        if (a2) p2 = rq_addr(a2);
-                        if (a3) p3 = rq_addr(a3);
-                    }
-                    if (lane == 0) {
-                        ctl->pred = p1;
-                        ctl->pred2 = p2;
-                        ctl->pred3 = p3;
-                    }
-                }
-            }
-            cyc_ctl += now() - tc;
-            const uint64_t tb1 = now();
-            meet();
-            dbg_b1 += now() - tb1;
-            const uint32_t pred = (uint32_t)uni((int)ctl->pred);
-            const bool aborted = uni((int)ctl->abort) != 0;
-            if (!w0) {
-                if (pred != RQ_NONE) {
-                    const uint64_t tf = now();
-                    rq_fetch<NW>(a, sh, ctl, &buf[cur ^ 1], pred, (uint32_t)uni((int)ctl->pred2), (uint32_t)uni((int)ctl->pred3), layer, gvis, qc, nw, vis_count, cache_hits, lane);
-                    cyc_fetch += now() - tf;
-                }
-            } else {
-                uint32_t st = RQ_STATE_DONE, node = 0, next;
-                if (!aborted) {
-                    const uint64_t t3 = now();
-                    // `if similarity.score > ws.score || len < k` replayed in edge order (search.rs:287-295)
-                    unsigned long long todo = __ballot(fresh);
-                    while (todo) {
-                        todo = uni64(todo);
-                        L.len = uni(L.len);
-                        L.worst = uni64(L.worst);
-                        const float ws = rank_key_score(L.worst);
-                        if (L.len >= kk) {
-                            todo &= __ballot(fresh && fest > ws);
-                            if (!todo) break;
-                        }
-                        const int j = __ffsll((long long)todo) - 1;
-                        todo &= ~(1ull << j);
-                        const float sj = lane_f32(fest, j);
-                        if (sj > ws || L.len < kk) rq_admit(L, kk, sj, lane_u32(faddr, j), lane, flags);
-                    }
-                    const uint64_t t4 = now();
-                    cyc_ins += t4 - t3;
-                    if (rq_pop(L, lane, node, next)) st = node == pred ? RQ_STATE_HIT : RQ_STATE_MISS;
-                    cyc_ctl += now() - t4;
-                }
-                if (st == RQ_STATE_HIT) n_hit++;
-                if (lane == 0) {
-                    ctl->state = st;
-                    ctl->fetch_node = node;
-                }
-            }
-            const uint64_t tw2 = now();
-            meet();
-            cyc_wait += now() - tw2;
-            dbg_b2 += now() - tw2;
-            const uint32_t st = (uint32_t)uni((int)ctl->state);
-            if (st == RQ_STATE_HIT) {
-                cur ^= 1;
-                need_fetch = false;
-                continue;
-            }
-            if (!w0 && pred != RQ_NONE) rq_rollback(&buf[cur ^ 1], gvis, lane);   // (layer 0 only: pred is RQ_NONE above it)
-            if (st == RQ_STATE_DONE) break;
-            need_fetch = true;
-        }
-        if (w0) {
-            ep = rq_addr(lane_u64(L.dir_first, 0));  // layer result (k = 1) = next entry point; layer 0 keeps the whole list
-            if (lane == 0) ctl->ep = ep;
-        } else if (lane == 0) {
-            ctl->pad = cache_hits;
-            ctl->cache_node[3] = (uint32_t)(cyc_fetch >> 8);   // (the fourth id slot is not a cache slot)
-        }
-        meet();
-        ep = (uint32_t)uni((int)ctl->ep);
-    }
-    if (a.dbg && lane == 0) {   // [0..5] controller: barrier 1, barrier 2, fetch barrier, ctl, admissions, walks; [8..13] fetcher: the same barriers, fetches
-        unsigned long long *d = a.dbg + (w0 ? 0 : 8);
-        atomicAdd(&d[0], (unsigned long long)dbg_b1);
-        atomicAdd(&d[1], (unsigned long long)dbg_b2);
-        atomicAdd(&d[2], (unsigned long long)dbg_nf);
-        atomicAdd(&d[3], (unsigned long long)(w0 ? cyc_ctl : cyc_fetch));
-        atomicAdd(&d[4], (unsigned long long)cyc_ins);
-        atomicAdd(&d[5], 1ull);
-        atomicAdd(&d[6], (unsigned long long)(now() - t_start));
-    }
-    if (!w0) return;
-
-    // ---- rerank_top over the ef neighbours, best estimate first (search.rs:354-363): the controller alone ----
-    Reranker rr;
-    rr.init(sh.best, (int)a.k, a.min_score, a.seg.vectors, a.seg.dp, sh.q);
-    for (int dch = 0; dch < uni(L.n_dir); dch++) {  // the chunks in rank order = the neighbours best first
-        const uint32_t meta = lane_u32(L.dir_meta, dch);
-        const bool ok = lane < (int)(meta >> 8);
-        uint32_t addr = 0;
-        float ub = 0.f;
-        if (ok) {
-            const uint64_t key = L.chunk(meta & 0xffu)[lane];
-            addr = rq_addr(key);
-            ub = rank_key_score(key) + rabitq_error(a.quant + (size_t)addr * a.rec_len, qc);
-        }
-        rr.feed(ok, addr, ub, lane);
-    }
-    rr.write(a.out_vec + (size_t)qi * a.k, a.out_score + (size_t)qi * a.k, a.out_count + qi, lane);
-    if (flags && a.flag_word && lane == 0) atomicOr(a.flag_word, flags);
-    if (a.stats && lane == 0) {
-        uint32_t *o = a.stats + (size_t)qi * NIDX_STAT_STRIDE;
-        o[NIDX_STAT_EVALS] = n_est;
-        o[NIDX_STAT_EXPANSIONS] = n_exp;
-        o[NIDX_STAT_VISITED] = rr.n_eval;
-        o[NIDX_STAT_FLAGS] = flags;
-        // the controller's cycles: prediction + pop / expansions whose fetch was speculated and confirmed / admissions; [7] = total incl. re-rank
-        // (cycles / 256, 16 bits each) the fetcher's speculative fetches | the controller's prediction + pop + waiting for the fetcher
-        o[NIDX_STAT_CYC_CTL] = ((uint32_t)uni((int)ctl->cache_node[3]) & 0xffffu) | ((uint32_t)(((cyc_ctl + cyc_wait) >> 8) & 0xffffu) << 16);
-        o[NIDX_STAT_EDGE_HITS] = (n_hit & 0xffffu) | ((uint32_t)uni((int)ctl->pad) << 16);   // confirmed speculations | expansions whose edge record was held
-        o[NIDX_STAT_CYC_INS] = (uint32_t)cyc_ins;
-        o[NIDX_STAT_CYC_TOTAL] = (uint32_t)(now() - t_start);
-    }
-}
-
-// (experiment NIDX_GPU_RABITQ_WG=256: the workgroup is launched with four waves of which two leave at once — the hardware deals the
-// waves of a workgroup round-robin over the CU's SIMDs, so the controller and the fetcher then surely sit on different SIMDs)
-template <int NW>
-__global__ __launch_bounds__(256) void rabitq_hnsw2_kernel(RabitqSearchArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (threadIdx.x >= 128) return;
-    rabitq_hnsw2_body<NW>(a, blockIdx.x, smem);
-}
-
-// every RaBitQ segment of an index in ONE launch: block b walks query b % n_queries of segment b / n_queries, whose arguments
-// come from a table in HBM (uniform address, read only: scalar loads) — like hnsw_search_segments_kernel
-template <int NW>
-__global__ __launch_bounds__(128) void rabitq_hnsw2_segments_kernel(const RabitqSearchArgs *table, uint32_t n_queries) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const RabitqSearchArgs &a = table[blockIdx.x / n_queries];
-    rabitq_hnsw2_body<NW>(a, blockIdx.x % n_queries, smem);
-}
-#endif  // NIDX_RABITQ_EXPERIMENTS
-
 // ---- HNSW, RaBitQ arm, ONE wave per query with the next expansion's loads in flight under the admissions (round 5) --------------------
-// What the two-wave walk above was built for — the memory round trip of expansion i + 1 hidden behind the admissions of expansion i —
-// without a second wave and without meetings: a wave's own loads are asynchronous.  After the estimates of an expansion are known, the node
-// the next pop will return is predicted exactly as above (best of {best unexpanded entry of the result set, best admissible new
-// neighbour}); when its layer-0 edge record is already in registers (the records of the three best candidates are requested one
+// The memory round trip of expansion i + 1 is hidden behind the admissions of expansion i without a second wave: a wave's own loads are
+// asynchronous (a fetcher wave beside a controller wave, with a meeting per expansion, measured slower: DESIGN-LOG.md section 4.7).  After
+// the estimates of an expansion are known, the node the next pop will return is predicted exactly (best of {best unexpanded entry of the
+// result set, best admissible new neighbour}: the best new neighbour that beats the current worst result is always admitted, and nothing
+// admitted can rank above it); when its layer-0 edge record is already in registers (the records of the three best candidates are requested one
 // expansion ahead: read-only, 84 % of the expansions find theirs), the codes of its neighbours and their visited test-and-set are ISSUED
 // — and only then the admission rule is replayed for the current expansion's neighbours (LDS and scalar work, ~3 000 cycles): the
 // loads land meanwhile.  The pop verifies the prediction; a mismatch clears exactly the bits the speculative test-and-set set (nobody else
@@ -1718,23 +1293,6 @@ hipError_t launch_rabitq_bf(const RabitqSearchArgs &a, hipStream_t s) {
     const size_t smem = rq_smem_bytes(a.seg.dim / 64u, a.seg.dp, a.k, 0, false);
     RQ_DISPATCH(launch_bf_nw, a.seg.dim / 64u, a, smem, s)
 }
-#ifdef NIDX_RABITQ_EXPERIMENTS
-template <int NW>
-static hipError_t launch_hnsw2_nw(const RabitqSearchArgs &a, size_t smem, hipStream_t s) {
-    hipError_t e = rq_allow_lds(reinterpret_cast<const void *>(&rabitq_hnsw2_kernel<NW>), smem);
-    if (e != hipSuccess) return e;
-    const char *wg = getenv("NIDX_GPU_RABITQ_WG");
-    hipLaunchKernelGGL(rabitq_hnsw2_kernel<NW>, dim3(a.n_queries), dim3(wg && atoi(wg) == 256 ? 256 : 128), smem, s, a);
-    return hipGetLastError();
-}
-template <int NW>
-static hipError_t launch_hnsw2_segments_nw(const RabitqSearchArgs *table, uint32_t n_table, uint32_t nq, size_t smem, hipStream_t s) {
-    hipError_t e = rq_allow_lds(reinterpret_cast<const void *>(&rabitq_hnsw2_segments_kernel<NW>), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rabitq_hnsw2_segments_kernel<NW>, dim3(n_table * nq), dim3(128), smem, s, table, nq);
-    return hipGetLastError();
-}
-#endif
 template <int NW>
 static hipError_t launch_hnsw1_segments_nw(const RabitqSearchArgs *table, uint32_t n_table, uint32_t nq, size_t smem, hipStream_t s) {
     hipError_t e = rq_allow_lds(reinterpret_cast<const void *>(&rabitq_hnsw_segments_kernel<NW>), smem);
@@ -1763,14 +1321,6 @@ static bool rabitq_pipelined(uint32_t nw) {
     if (e && atoi(e) == 0) return false;
     return nw == 2 || nw == 4 || nw == 6 || nw == 8 || nw == 12 || nw == 16 || nw == 24 || nw == 32;
 }
-// measurement switches of the two-wave walk -> RabitqSearchArgs::no_speculation: NIDX_GPU_RABITQ_SPEC=0: no speculation (bit 0);
-// =2: the waves meet through polled LDS words instead of s_barrier (bit 1); =3: both
-[[maybe_unused]] static uint32_t rabitq_walk_mode() {
-    const char *e = getenv("NIDX_GPU_RABITQ_SPEC");
-    if (!e) return 0u;
-    const int v = atoi(e);
-    return v == 0 ? 1u : v == 2 ? 2u : v == 3 ? 3u : 0u;
-}
 // log2 of the pipelined walk's LDS cache of known-visited ids: 9 (512 ids, 2 KiB) by default; NIDX_GPU_RABITQ_SEEN=0: none (every neighbour
 // asks the bitset in HBM), 8 ... 13: that size — measurement.  1 M x 768, k = 10, three batches of 1 024 in flight (scripts/r5_ab.sh rqseen /
 // rqflight): no cache 50.1 k neighbours per query ask memory, 251 k queries/s; 2^9: 22.5 k, 276 k (286 k with six in flight); 2^10: 16.9 k,
@@ -1782,59 +1332,14 @@ uint32_t rabitq_seen_log2() {
     const int v = atoi(e);
     return v <= 0 ? 0u : v < 8 ? 8u : v > 13 ? 13u : (uint32_t)v;
 }
-// NIDX_GPU_RABITQ_WAVES=2: the two-wave walk (slower on MI355X as measured, kept for the comparison); default: one wave per query
-bool rabitq_two_waves() {
-#ifdef NIDX_RABITQ_EXPERIMENTS
-    const char *e = getenv("NIDX_GPU_RABITQ_WAVES");
-    return e && atoi(e) == 2;
-#else
-    return false;   // (the two-wave walk is only in a `make EXPERIMENTS=1` library)
-#endif
-}
 bool rabitq_tie_spill_enabled() {
     const char *e = getenv("NIDX_GPU_RABITQ_TIE_SPILL");
     return !(e && atoi(e) == 0);
 }
-bool rabitq_has_experiments() {
-#ifdef NIDX_RABITQ_EXPERIMENTS
-    return true;
-#else
-    return false;
-#endif
-}
 // the plain one-wave walk: the product runs it for dimensions whose code fetch is not unrolled (NW = 0: D / 64 read at run time) and under
-// NIDX_GPU_RABITQ_PIPE=0 (parity tests); its unrolled instances are measurement material
-#ifdef NIDX_RABITQ_EXPERIMENTS
-#define RQ_DISPATCH_PLAIN(fn, nw, ...) RQ_DISPATCH(fn, nw, __VA_ARGS__)
-#else
-#define RQ_DISPATCH_PLAIN(fn, nw, ...) return fn<0>(__VA_ARGS__);
-#endif
+// NIDX_GPU_RABITQ_PIPE=0 (parity tests); it is instantiated for NW = 0 only
 hipError_t launch_rabitq_hnsw(const RabitqSearchArgs &a, hipStream_t s) {
     if (a.n_queries == 0) return hipSuccess;
-#ifdef NIDX_RABITQ_EXPERIMENTS
-    if (rabitq_two_waves()) {
-        const size_t smem2 = rq_smem2_bytes(a.seg.dim / 64u, a.seg.dp, a.k, a.ef);
-        RabitqSearchArgs b = a;
-        b.no_speculation = rabitq_walk_mode();
-        if (getenv("NIDX_GPU_RABITQ_DEBUG")) {
-            // measurement only: where the two waves of a walk spend their cycles (synchronises; prints one line per launch)
-            static unsigned long long *d_dbg = nullptr;
-            if (!d_dbg && hipMalloc(&d_dbg, 16 * 8) != hipSuccess) return hipErrorOutOfMemory;
-            (void)hipMemsetAsync(d_dbg, 0, 16 * 8, s);
-            b.dbg = d_dbg;
-            hipError_t e = [&]() -> hipError_t { RQ_DISPATCH(launch_hnsw2_nw, a.seg.dim / 64u, b, smem2, s) }();
-            if (e != hipSuccess) return e;
-            unsigned long long h[16];
-            (void)hipMemcpyAsync(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            const double n = h[5] ? (double)h[5] : 1.0;
-            fprintf(stderr, "[rabitq dbg] per walk, controller: barrier1 %.0f barrier2 %.0f fetch-barrier %.0f ctl %.0f admissions %.0f walk %.0f | fetcher: barrier1 %.0f barrier2 %.0f "
-                            "fetch-barrier %.0f speculative fetches %.0f walk %.0f cycles\n", h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, h[6] / n, h[8] / n, h[9] / n, h[10] / n, h[11] / n, h[14] / n);
-            return hipSuccess;
-        }
-        RQ_DISPATCH(launch_hnsw2_nw, a.seg.dim / 64u, b, smem2, s)
-    }
-#endif
     const size_t smem = rq_smem_bytes(a.seg.dim / 64u, a.seg.dp, a.k, a.ef, true);
     if (rabitq_pipelined(a.seg.dim / 64u)) {
         RabitqSearchArgs b = a;
@@ -1842,23 +1347,17 @@ hipError_t launch_rabitq_hnsw(const RabitqSearchArgs &a, hipStream_t s) {
         const size_t smem3 = rq_smem3_bytes(a.seg.dim / 64u, a.k, a.ef, b.seen_log2);
         RQ_DISPATCH(launch_hnsw3_nw, a.seg.dim / 64u, b, smem3, s)
     }
-    RQ_DISPATCH_PLAIN(launch_hnsw_nw, a.seg.dim / 64u, a, smem, s)
+    return launch_hnsw_nw<0>(a, smem, s);
 }
 // `table` (device) holds n_table argument records that agree in dim / dp / k / ef / n_queries (`shape`: one of them, host side)
 hipError_t launch_rabitq_hnsw_segments(const RabitqSearchArgs *table, uint32_t n_table, const RabitqSearchArgs &shape, hipStream_t s) {
     if (n_table == 0 || shape.n_queries == 0) return hipSuccess;
-#ifdef NIDX_RABITQ_EXPERIMENTS
-    if (rabitq_two_waves()) {
-        const size_t smem2 = rq_smem2_bytes(shape.seg.dim / 64u, shape.seg.dp, shape.k, shape.ef);
-        RQ_DISPATCH(launch_hnsw2_segments_nw, shape.seg.dim / 64u, table, n_table, shape.n_queries, smem2, s)
-    }
-#endif
     const size_t smem = rq_smem_bytes(shape.seg.dim / 64u, shape.seg.dp, shape.k, shape.ef, true);
     if (rabitq_pipelined(shape.seg.dim / 64u)) {
         const size_t smem3 = rq_smem3_bytes(shape.seg.dim / 64u, shape.k, shape.ef, shape.seen_log2);   // (every record of the table: rabitq_seen_log2())
         RQ_DISPATCH(launch_hnsw3_segments_nw, shape.seg.dim / 64u, table, n_table, shape.n_queries, smem3, s)
     }
-    RQ_DISPATCH_PLAIN(launch_hnsw1_segments_nw, shape.seg.dim / 64u, table, n_table, shape.n_queries, smem, s)
+    return launch_hnsw1_segments_nw<0>(table, n_table, shape.n_queries, smem, s);
 }
 
 }  // namespace nidx

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_scan_kernel(Bf16ScanArgs a
 // publishes the next KC chunks; the fragment reads of chunk c and the two LDS-DMA pieces a wave requests per chunk sit in the issue gaps
 // between the 8 MFMAs of chunk c - 1 (two register sets), so the first MFMA after a barrier never waits for LDS.  Measured (12.5 M x 1024,
 // batch 1 024, three interleaved runs on one box): 24.24 ms per batch against 24.95 ms — the gain is small because the wait was not
-// latency: the ablations of profiles/r06_bf16_ablation.txt (library built with -DNIDX_BF16_ABLATE) show the requests alone (no MFMAs,
+// latency: the ablations of profiles/r06_bf16_ablation.txt (DESIGN-LOG R6.7: parts of the mainloop switched off) show the requests alone (no MFMAs,
 // no fragment reads) take 0.6 of the batch and the MFMAs alone 0.65 — the LDS port (16 KiB of DMA writes at 64 B/clk + 48 KiB of
 // fragment reads at 256 B/clk = 448 of the 512 cycles a chunk's MFMAs take per SIMD pair) and the L2 -> LDS path at the clock the matrix
 // pipe's power leaves (1.6 GHz with every MFMA slot used) are what the 256 x 256 tile saturates.  Two shorter epilogues (eight v_max3 and
@@ -391,11 +391,6 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_append_kernel(Bf16ScanArgs
     const uint32_t skip = keep_sample ? a.round_skip : 0u;
     const uint32_t n_tiles = (a.n + BF_BN - 1) / BF_BN;
     const uint32_t nk = a.dp16 / BF_BK;               // chunks per tile (a multiple of 4)
-#ifdef NIDX_BF16_ABLATE
-    const int abl = a.debug;   // experiment builds only (wrong results): 1 no requests, 2 no MFMAs, 4 no epilogue, 8 corpus from eight tiles, 16 no fragment reads, 32 no barriers
-#else
-    constexpr int abl = 0;
-#endif
 
     if (tid < BF_BM) {
         const bool real = q0 + tid < a.n_queries;
@@ -457,8 +452,8 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_append_kernel(Bf16ScanArgs
     uint32_t is_kc = 0, is_round = round0, is_left = C;   // the next chunk to request; chunks not requested yet
     uint32_t wr_off = 0, rd_off = 0;
     constexpr uint32_t SLOT = 2 * BF_BLOCK_BYTES, RING = (uint32_t)R * SLOT;
-    auto issue_q = [&]() __attribute__((always_inline)) { if (!(abl & 1)) bf_glds16<0>(qp, &sh.slot[0][0] + wr_off + (uint32_t)wave * 1024u); };
-    auto issue_x = [&]() __attribute__((always_inline)) { if (!(abl & 1)) bf_glds16<0>(xp, &sh.slot[0][0] + wr_off + BF_BLOCK_BYTES + (uint32_t)wave * 1024u); };
+    auto issue_q = [&]() __attribute__((always_inline)) { bf_glds16<0>(qp, &sh.slot[0][0] + wr_off + (uint32_t)wave * 1024u); };
+    auto issue_x = [&]() __attribute__((always_inline)) { bf_glds16<0>(xp, &sh.slot[0][0] + wr_off + BF_BLOCK_BYTES + (uint32_t)wave * 1024u); };
     // past the stream's last chunk the same chunk is requested again into a slot nobody reads: the counts behind `s_waitcnt vmcnt(N)` stay true to the end
     auto advance = [&]() __attribute__((always_inline)) {
         wr_off = wr_off + SLOT == RING ? 0u : wr_off + SLOT;
@@ -470,7 +465,6 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_append_kernel(Bf16ScanArgs
                 is_kc = 0;
                 qp -= tile_bytes;
                 const uint32_t nr = next_round(is_round);
-                if ((abl & 8) && (nr & 7u) == 0) xp -= (size_t)8 * gridDim.x * tile_bytes;
                 xp += ((size_t)(nr - is_round) * gridDim.x - 1u) * tile_bytes;
                 is_round = nr;
             }
@@ -486,7 +480,6 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_append_kernel(Bf16ScanArgs
     const int a_off = (64 * wq + li) * 32 + frag, b_off = BF_BLOCK_BYTES + (128 * wr + li) * 32 + frag;
 
     auto epilogue = [&](uint32_t tile) __attribute__((always_inline)) {   // `tile`: the corpus tile
-        if (abl & 4) return;
         const uint32_t r0 = tile * BF_BN;
         int half = lane >> 5, li = lane & 31;
         asm volatile("" : "+v"(half), "+v"(li));   // (keeps hipcc from hoisting this rare path's addresses into the mainloop's registers)
@@ -550,19 +543,17 @@ __global__ __launch_bounds__(BF_THREADS, 1) void bf16_append_kernel(Bf16ScanArgs
             __builtin_amdgcn_s_waitcnt(bar ? WAIT_BAR : WAIT_LDS);
             // the previous chunk's fragments are complete now; re-defining them keeps the compiler from waiting for them again behind the new reads
             asm volatile("" : "+v"(pav[0]), "+v"(pav[1]), "+v"(pbv[0]), "+v"(pbv[1]), "+v"(pbv[2]), "+v"(pbv[3]));
-            if constexpr (bar) if (!(abl & 32)) __builtin_amdgcn_s_barrier();
+            if constexpr (bar) __builtin_amdgcn_s_barrier();
             const unsigned char *base = &sh.slot[0][0] + rd_off;
             rd_off = rd_off + SLOT == RING ? 0u : rd_off + SLOT;
-            const bool with_reads = !(abl & 16);
-            with_mma = with_mma && !(abl & 2);
 #define BF_MMA(I) if (with_mma) acc[I] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pav[(I) >> 2], pbv[(I) & 3], acc[I], 0, 0, 0)
 #define BF_GAP() __builtin_amdgcn_sched_barrier(0)
-            BF_MMA(0); if (with_reads) av[0] = *reinterpret_cast<const bf16x8 *>(base + a_off); BF_GAP();
-            BF_MMA(1); if (with_reads) av[1] = *reinterpret_cast<const bf16x8 *>(base + a_off + 32 * 32); BF_GAP();
-            BF_MMA(2); if (with_reads) bv[0] = *reinterpret_cast<const bf16x8 *>(base + b_off); BF_GAP();
-            BF_MMA(3); if (with_reads) bv[1] = *reinterpret_cast<const bf16x8 *>(base + b_off + 32 * 32); BF_GAP();
-            BF_MMA(4); if (with_reads) bv[2] = *reinterpret_cast<const bf16x8 *>(base + b_off + 2 * 32 * 32); BF_GAP();
-            BF_MMA(5); if (with_reads) bv[3] = *reinterpret_cast<const bf16x8 *>(base + b_off + 3 * 32 * 32); BF_GAP();
+            BF_MMA(0); av[0] = *reinterpret_cast<const bf16x8 *>(base + a_off); BF_GAP();
+            BF_MMA(1); av[1] = *reinterpret_cast<const bf16x8 *>(base + a_off + 32 * 32); BF_GAP();
+            BF_MMA(2); bv[0] = *reinterpret_cast<const bf16x8 *>(base + b_off); BF_GAP();
+            BF_MMA(3); bv[1] = *reinterpret_cast<const bf16x8 *>(base + b_off + 32 * 32); BF_GAP();
+            BF_MMA(4); bv[2] = *reinterpret_cast<const bf16x8 *>(base + b_off + 2 * 32 * 32); BF_GAP();
+            BF_MMA(5); bv[3] = *reinterpret_cast<const bf16x8 *>(base + b_off + 3 * 32 * 32); BF_GAP();
             BF_MMA(6); issue_q(); BF_GAP();
             BF_MMA(7); issue_x(); advance(); BF_GAP();
 #undef BF_MMA
@@ -691,23 +682,15 @@ hipError_t launch_bf16_scan(const Bf16ScanArgs &a, uint32_t stripes, hipStream_t
     return hipGetLastError();
 }
 
-template <typename K, typename S>
-static hipError_t bf16_append_launch_as(K kernel, const Bf16ScanArgs &a, uint32_t stripes, hipStream_t s) {
-    const size_t smem = sizeof(S);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(stripes, (a.n_queries + BF_BM - 1) / BF_BM), dim3(BF_THREADS), smem, s, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_bf16_append(const Bf16ScanArgs &a, uint32_t stripes, hipStream_t s) {
     if (a.n_queries == 0) return hipSuccess;
     if (a.n == 0 || (a.dp16 % 64u) || !a.floor_score || !a.overflow) return hipErrorInvalidValue;
-    // NIDX_GPU_BF16_MAINLOOP=1: a ring of nine chunks with a barrier per chunk (measured 1 % behind the shipped ring of eight with a barrier per two)
-    const char *fe = getenv("NIDX_GPU_BF16_MAINLOOP");
-    const int form = fe ? atoi(fe) : 2;
-    if (form == 1) return bf16_append_launch_as<decltype(&bf16_append_kernel<1, 9>), Bf16RingShared<9>>(&bf16_append_kernel<1, 9>, a, stripes, s);
-    return bf16_append_launch_as<decltype(&bf16_append_kernel<2, 8>), Bf16RingShared<8>>(&bf16_append_kernel<2, 8>, a, stripes, s);
+    // a ring of eight chunks with a barrier per two (a ring of nine with a barrier per chunk measured 1 % slower: DESIGN-LOG R6.7)
+    const size_t smem = sizeof(Bf16RingShared<8>);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&bf16_append_kernel<2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((bf16_append_kernel<2, 8>), dim3(stripes, (a.n_queries + BF_BM - 1) / BF_BM), dim3(BF_THREADS), smem, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_rescore_select(const RescoreArgs &a, hipStream_t s) {

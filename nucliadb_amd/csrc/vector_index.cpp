@@ -723,8 +723,6 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
         // that block again: the candidates are the list kernel's in every case.  NIDX_GPU_BF16_APPEND=0 keeps the list kernel alone.
         const char *const append_env = getenv("NIDX_GPU_BF16_APPEND");
         const bool append_enabled = !(append_env && atoi(append_env) == 0);
-        int ablate = 0;
-        if (const char *e = getenv("NIDX_GPU_BF16_ABLATE")) ablate = atoi(e);   // (read by experiment builds of the ring kernel only)
         if (b.floor_score && append_enabled && stripes >= 32 && !b.debug) {
             const uint32_t qb = (nq + 255u) / 256u;
             NIDX_HIP(scratch_bf16_flags.reserve((size_t)qb * 8));
@@ -749,7 +747,6 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
                 NIDX_HIP(hipMemsetAsync(b.partial, 0, partial_bytes, st));
                 NIDX_HIP(hipMemsetAsync(flags_sample, 0, (size_t)qb * 4, st));
                 Bf16ScanArgs ap = b;
-                ap.debug = ablate;
                 ap.round_step = rs;
                 ap.overflow = flags_sample;
                 ap.cnt_inout = scratch_bf16_counts.as<uint32_t>();
@@ -766,7 +763,6 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
             if (!last_rs) NIDX_HIP(hipMemsetAsync(b.partial, 0, partial_bytes, st));   // (else the slots hold the last sample's candidates)
             NIDX_HIP(hipMemsetAsync(flags_full, 0, (size_t)qb * 4, st));
             Bf16ScanArgs ap = b;
-            ap.debug = ablate;
             ap.overflow = flags_full;
             if (last_rs) {
                 ap.round_skip = last_rs;
@@ -1264,7 +1260,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len) try {
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
-int32_t nidx_gpu_build_features(void) { return nidx::rabitq_has_experiments() ? NIDX_GPU_FEATURE_RABITQ_EXPERIMENTS : 0; }
+int32_t nidx_gpu_build_features(void) { return 0; }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
     if (!count_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "count_out is NULL");

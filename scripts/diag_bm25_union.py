@@ -1,4 +1,4 @@
-"""Debug aid: the same queries through bm25_union_kernel (NIDX_GPU_BM25_UNION=2) and the hash kernels (=0); prints the first
+"""Debug aid: the same queries through bm25_stream_kernel (NIDX_GPU_BM25_UNION=2) and the hash kernels (=0); prints the first
 differences with the per-clause membership of the documents involved."""
 import os
 import sys

@@ -29,12 +29,10 @@ if [ "$PART" = rabitq ] || [ "$PART" = all ]; then
   run rabitq_pipe -- --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 256
   run rabitq_no_seen NIDX_GPU_RABITQ_SEEN=0 -- --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 0
   run rabitq_plain NIDX_GPU_RABITQ_PIPE=0 -- --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 0
-  run rabitq_2w_barrier NIDX_GPU_RABITQ_WAVES=2 -- --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 0
 fi
 if [ "$PART" = bm25 ] || [ "$PART" = all ]; then
   run bm25_default -- --workload bm25 --cpu-queries 0 --steps 200
   run bm25_prio0 NIDX_GPU_BM25_PRIORITY=0 NIDX_BENCH_BM25_SEGMENTS=0 -- --workload bm25 --cpu-queries 0 --steps 200
-  run bm25_copy_out NIDX_GPU_BM25_ZERO_COPY_OUT=0 NIDX_BENCH_BM25_SEGMENTS=0 -- --workload bm25 --cpu-queries 0 --steps 200
   run bm25_depth4 NIDX_BENCH_BM25_DEPTH=4 NIDX_BENCH_BM25_SEGMENTS=0 -- --workload bm25 --cpu-queries 0 --steps 200
 fi
 if [ "$PART" = bm25t ]; then

@@ -44,8 +44,7 @@ hybrid)
 rabitq)
   prof rabitq_1m --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1
   pmc rabitq_1m FETCH_SIZE --workload rabitq --n-vectors 1000000 --steps 3 --warmup 1 --cpu-queries 0 --batches-in-flight 1
-  pmc rabitq_1m WRITE_SIZE --workload rabitq --n-vectors 1000000 --steps 3 --warmup 1 --cpu-queries 0 --batches-in-flight 1
-  NIDX_GPU_RABITQ_WAVES=2 prof rabitq_1m_two_waves --workload rabitq --n-vectors 1000000 --steps 5 --warmup 1 --cpu-queries 0 ;;
+  pmc rabitq_1m WRITE_SIZE --workload rabitq --n-vectors 1000000 --steps 3 --warmup 1 --cpu-queries 0 --batches-in-flight 1 ;;
 hnsw1m)
   prof hnsw1m --full --n-vectors 1000000 --corpus clustered --bf16-block-n 0 --bm25-block 0 --single-query-calls 0 --segment-regime 0 --ref-build-n 0 ;;
 others)

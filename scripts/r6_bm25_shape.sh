@@ -20,8 +20,5 @@ except Exception as e:
 PY
 }
 run auto
-NIDX_GPU_BM25_CROWDED_SLICE=4096 run crowded4096
-NIDX_GPU_BM25_CROWDED_SLICE=16384 run crowded16384
-NIDX_GPU_BM25_CROWDED_SLICE=32768 run crowded32768
 NIDX_GPU_BM25_CROWDED=1 run always_crowded
 run auto2

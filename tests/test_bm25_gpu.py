@@ -192,11 +192,11 @@ def test_general_kernel_on_narrow_queries(orc, corpus, monkeypatch):
     s.close()
 
 
-@pytest.mark.parametrize("union_mode", ["2", "2-throughput-shape", "4", "0"])
+@pytest.mark.parametrize("union_mode", ["2", "2-throughput-shape", "0"])
 def test_union_kernel_and_hash_kernel_agree_with_the_oracle(orc, corpus, monkeypatch, union_mode):
-    """The union kernels (postings are final unless a bitmap filter says their document may occur twice; those are resolved
-    exactly) against the oracle, on query families that make their slow paths the common ones: NIDX_GPU_BM25_UNION=2 sends every
-    query of <= 8 plain term clauses through bm25_stream_kernel (4: through bm25_union_kernel) — dense terms (term 0 is in nearly
+    """The union kernel (postings are final unless a bitmap filter says their document may occur twice; those are resolved
+    exactly) against the oracle, on query families that make its slow paths the common ones: NIDX_GPU_BM25_UNION=2 sends every
+    query of <= 8 plain term clauses through bm25_stream_kernel — dense terms (term 0 is in nearly
     every document: the involved list overflows, the doc range is cut in half and retried), Must / MustNot / required Should
     groups, constant scores, negative and zero boosts, k from 1 to 501, the alive bitset and the search-after cursor.  Mode 0 never
     uses them: the same answers from the hash kernels."""

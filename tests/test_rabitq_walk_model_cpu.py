@@ -15,8 +15,8 @@ plain walk for any graph and any scores, exact ties included.  The model also sh
 path that runs: a speculation needs the predicted node's edge record in registers, only nodes that were candidates one expansion ago
 have theirs there, and when the predicted node is such an existing candidate — i.e. it outranks every neighbour about to be admitted
 — the admissions cannot put anything in front of it nor evict it.  The prediction only fails for a brand-new neighbour (ties at the
-admission threshold), whose record is never held.  (The two-wave kernel's fetcher does fetch records of new nodes; there the
-roll-back runs.)  The algorithm, not the instruction stream: the kernel itself is checked bit for bit against the oracle on the GPU,
+admission threshold), whose record is never held.  (A two-wave form of the walk, measured slower and removed, fetched records of
+new nodes; there the roll-back ran.)  The algorithm, not the instruction stream: the kernel itself is checked bit for bit against the oracle on the GPU,
 tests/test_rabitq_gpu.py."""
 import numpy as np
 import pytest

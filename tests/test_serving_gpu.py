@@ -290,8 +290,7 @@ def test_rabitq_segments_share_one_launch(orc, monkeypatch):
     hnsw/search.rs:333-366): the walks of every RaBitQ segment of an index run in ONE table-driven launch (rabitq_hnsw_segments_kernel),
     their closest_up_nodes in the plain segments' grid in entry mode, Fssc on the device.  Identical — segments, vectors, ranks, score
     bits — to the oracle's Searcher::_search over the same quantized segments, to the segment-at-a-time path (tunable
-    serial_segments), to a launch per segment (NIDX_GPU_SEGMENT_LAUNCHES) and to the two-wave walk (NIDX_GPU_RABITQ_WAVES=2: a fetcher
-    wave expands the predicted next candidate while the controller admits; exact, measured slower, not the default)."""
+    serial_segments), to a launch per segment (NIDX_GPU_SEGMENT_LAUNCHES) and to the plain walk (NIDX_GPU_RABITQ_PIPE=0)."""
     rng = np.random.default_rng(77)
     d = 128
     sizes = (3000, 1200, 2500, 800, 1700)
@@ -323,17 +322,13 @@ def test_rabitq_segments_share_one_launch(orc, monkeypatch):
                 c = int(sc[i])
                 assert np.array_equal(auto[0][i, :c], sg[i, :c]) and np.array_equal(auto[2][i, :c], sv[i, :c]), (k, with_dup, i)
                 assert np.array_equal(auto[3][i, :c].view(np.uint32), ss[i, :c].view(np.uint32)), (k, with_dup, i)
-            # every segment forced onto the RaBitQ walk: one launch == segment at a time == a launch per segment == the two-wave walk
+            # every segment forced onto the RaBitQ walk: one launch == segment at a time == a launch per segment == the plain walk
             got = idx.search(q, k, _lib.METHOD_RABITQ_HNSW, with_dup, min_score=min_score)
             idx.tunable("serial_segments", 1)
             serial = idx.search(q, k, _lib.METHOD_RABITQ_HNSW, with_dup, min_score=min_score)
-            monkeypatch.setenv("NIDX_GPU_RABITQ_WAVES", "2")
-            serial_two_waves = idx.search(q, k, _lib.METHOD_RABITQ_HNSW, with_dup, min_score=min_score)
-            monkeypatch.delenv("NIDX_GPU_RABITQ_WAVES")
             idx.tunable("serial_segments", 0)
             assert same(got, serial), (k, with_dup)
-            assert same(serial_two_waves, serial), (k, with_dup)
-            for var, val in (("NIDX_GPU_SEGMENT_LAUNCHES", "1"), ("NIDX_GPU_RABITQ_WAVES", "2"), ("NIDX_GPU_RABITQ_PIPE", "0")):
+            for var, val in (("NIDX_GPU_SEGMENT_LAUNCHES", "1"), ("NIDX_GPU_RABITQ_PIPE", "0")):
                 monkeypatch.setenv(var, val)
                 assert same(idx.search(q, k, _lib.METHOD_RABITQ_HNSW, with_dup, min_score=min_score), got), (var, k, with_dup)
                 monkeypatch.delenv(var)
