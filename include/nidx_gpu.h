@@ -260,6 +260,31 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
                                         uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                                         uint32_t *out_count, int32_t *out_method, uint64_t *out_matching);
 
+/* One batch in which every query carries its own filter (nucliadb builds one per request from the prefilter, the label / field
+ * formula and filter_operator: nidx_vector/src/searcher.rs:292-343, segment.rs:516-534).  Query q uses filter filter_of_query[q]
+ * (filter_of_query NULL, or an entry UINT32_MAX: unfiltered on every segment); filter f on segment s is programs[f * n_segments + s]
+ * (ops == NULL / n_ops == 0: no filter on that segment, as in nidx_gpu_vector_search_filtered).  Query q's hits are bit-identical to
+ * nidx_gpu_vector_search_filtered on a batch of that query alone with segment_programs = programs + f * n_segments.
+ *   - The distinct filters of the batch are evaluated together (two launches per segment, however many there are), their
+ *     |filter ∩ alive| counts come back in one transfer, and every (query, segment) is routed on the host with use_hnsw as
+ *     OpenSegment::_search routes a segment (segment.rs:506-555): HNSW, brute force or the RaBitQ arms; 0 matching = skipped.
+ *     Each arm of a segment then runs once over the queries routed to it.
+ *   - params->method: AUTO, HNSW, BRUTE_FORCE, RABITQ_HNSW, RABITQ_BRUTE_FORCE.  BRUTE_FORCE_MFMA / _BF16: NIDX_ERR_UNSUPPORTED.
+ *   - NIDX_ERR_INVALID_ARGUMENT, before anything is launched, for a filter index >= n_filters or a malformed program (the message
+ *     names the filter and the segment).  A program that needs more than 32 bitsets on its stack is evaluated op by op, as
+ *     nidx_gpu_vector_search_filtered evaluates it (a launch per operator and one synchronisation, for that filter alone).
+ *   - The filter rows of one pass stay under 1 GiB (a row of n_paragraphs bits per filter and segment, plus one per posting-list
+ *     operand) and 65 535 filters: a batch whose distinct filters need more is searched in consecutive chunks of queries.
+ *   - Each (segment, arm) with queries is one search plus one synchronisation: up to 4 per segment.
+ * out_method: NULL or [n_queries][n_segments] (0 = segment not searched for that query); out_matching: NULL or
+ * [n_filters][n_segments] (0 for a filter no query names). */
+int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                  uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                  const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                  const uint32_t *filter_of_query, uint32_t *out_segment, uint32_t *out_paragraph,
+                                                  uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method,
+                                                  uint64_t *out_matching);
+
 /* OpenSegment::search on ONE segment with everything resident in HBM (segment.rs:477-567):
  * device pointers, asynchronous on `stream` (a hipStream_t; NULL = the null stream).
  *   d_queries [n_queries][dimension] f32 (already normalised if the index wants that)
@@ -331,6 +356,15 @@ int32_t nidx_gpu_vector_search_submit(nidx_gpu_vector_index_t *index, const floa
                                       uint64_t *ticket_out);
 int32_t nidx_gpu_vector_search_wait(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,
                                     uint32_t *out_vector, float *out_score, uint32_t *out_count, uint32_t *n_retried_out);
+/* nidx_gpu_vector_search_filtered_per_query through the ticket interface (queries in host memory; programs are read before the call
+ * returns).  Routing needs the filters' counts on the host, so this submit synchronises: it evaluates the filters, reads the counts
+ * back, runs the searches and the exact fallback, and returns a ticket whose hits nidx_gpu_vector_search_wait hands over
+ * (*n_retried_out = 0).  Tickets of both kinds may be outstanding together and are waited for in any order; together they are
+ * bounded by "pipeline_depth" (NIDX_ERR_BUSY when that many are outstanding, nothing searched). */
+int32_t nidx_gpu_vector_search_submit_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                         uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                         const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                         const uint32_t *filter_of_query, uint64_t *ticket_out);
 
 /* One query per call, the shape of the reference's request path (one blocking thread per Search request,
  * src/searcher/shard_search.rs:139-153; one vector per request, nodereader.proto:402).  Thread safe:
@@ -345,6 +379,16 @@ int32_t nidx_gpu_vector_search_wait(nidx_gpu_vector_index_t *index, uint64_t tic
 int32_t nidx_gpu_vector_search_one(nidx_gpu_vector_index_t *index, const float *query, uint32_t query_dimension,
                                    const nidx_gpu_vector_search_params_t *params, uint32_t *out_segment,
                                    uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count);
+/* nidx_gpu_vector_search_one with this request's filter (segment_programs: NULL = unfiltered, or [n_segments] as in
+ * nidx_gpu_vector_search_filtered).  Filtered and unfiltered callers with equal params share batches: a batch with a filtered
+ * member runs as one nidx_gpu_vector_search_filtered_per_query call, each member's programs one filter of it (members with equal
+ * ops and lists share one).  The programs must stay valid until the call returns.  They are checked before the caller joins a
+ * batch: a malformed program fails this call alone (NIDX_ERR_INVALID_ARGUMENT, the message names the segment).  Hits equal
+ * nidx_gpu_vector_search_filtered on this query alone. */
+int32_t nidx_gpu_vector_search_one_filtered(nidx_gpu_vector_index_t *index, const float *query, uint32_t query_dimension,
+                                            const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *segment_programs,
+                                            uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                            uint32_t *out_count);
 /* Launches and queries served through nidx_gpu_vector_search_one so far. */
 int32_t nidx_gpu_vector_coalescer_stats(nidx_gpu_vector_index_t *index, uint64_t *batches_out, uint64_t *queries_out);
 /* Queries whose closest_up_nodes walk (hnsw/search.rs:188-240) outgrew the on-chip candidate pool / visited table

@@ -236,6 +236,14 @@ SIGNATURES = {
                                                   C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_search_wait": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint32)]),
+    "nidx_gpu_vector_search_filtered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(VectorSearchParamsC),
+                                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nidx_gpu_vector_search_submit_filtered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                     C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                     C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_one_filtered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(VectorSearchParamsC), C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "nidx_gpu_vector_spill_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_coalescer_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nidx_gpu_use_hnsw": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32]),

@@ -29,6 +29,8 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <unordered_map>
+#include <vector>
 
 #include "host_common.h"
 #include "vector_index.h"
@@ -54,6 +56,7 @@ struct CoBatch {
     // when it closes the batch first (with more callers than cores a member can lose its time slice between taking its slot and
     // copying its row: the gatherer must never wait for a descheduled thread).  0 = not copied, 1 = being copied, 2 = in `q`.
     std::unique_ptr<const float *[]> src;
+    std::unique_ptr<const nidx_gpu_filter_program_t *[]> progs;   // per member: its [n_segments] programs, nullptr = unfiltered
     std::unique_ptr<std::atomic<uint8_t>[]> row_state;
     std::atomic<uint32_t> done{0};        // futex word: 0 = gathering / on the device, 1 = results (or rc) published
     std::unique_ptr<float[]> q;           // [cap][d]
@@ -93,7 +96,8 @@ static bool same_params(const nidx_gpu_vector_search_params_t &a, const nidx_gpu
 }
 
 int32_t VectorIndex::search_one(const float *query, const nidx_gpu_vector_search_params_t &p, uint32_t *out_segment,
-                                uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count) {
+                                uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                                const nidx_gpu_filter_program_t *segment_programs) {
     Coalescer &c = *coalescer;  // created with the handle (nidx_gpu_vector_open)
     if (p.k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, p.k);
     if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
@@ -178,6 +182,7 @@ int32_t VectorIndex::search_one(const float *query, const nidx_gpu_vector_search
                 b->d = d;
                 b->q.reset(new float[(size_t)b->cap * d]);
                 b->src.reset(new const float *[b->cap]);
+                b->progs.reset(new const nidx_gpu_filter_program_t *[b->cap]);
                 b->row_state.reset(new std::atomic<uint8_t>[b->cap]);
                 if (c.pool.size() < 32) c.pool.push_back(b);
             }
@@ -192,6 +197,7 @@ int32_t VectorIndex::search_one(const float *query, const nidx_gpu_vector_search
         }
         slot = b->n++;
         b->src[slot] = query;
+        b->progs[slot] = segment_programs;
         if (!gatherer && b->n == b->cap) c.cv_gather.notify_all();   // full: its gatherer need not sit out the window
     }
     {
@@ -249,9 +255,56 @@ int32_t VectorIndex::search_one(const float *query, const nidx_gpu_vector_search
         // the members of this batch are parked: whatever happens here, they must be released
         try {
             b->seg.resize(B * kk), b->par.resize(B * kk), b->vec.resize(B * kk), b->cnt.resize(B), b->sc.resize(B * kk);
-            uint64_t ticket = 0;
-            rc = pipeline_submit(b->q.get(), B, b->params, nullptr, /*blocking=*/true, &ticket);
-            if (rc == NIDX_OK) rc = pipeline_wait(ticket, b->seg.data(), b->par.data(), b->vec.data(), b->sc.data(), b->cnt.data(), nullptr);
+            bool filtered = false;
+            for (uint32_t i = 0; i < B && !filtered; i++) filtered = b->progs[i] != nullptr;
+            if (!filtered) {
+                uint64_t ticket = 0;
+                rc = pipeline_submit(b->q.get(), B, b->params, nullptr, /*blocking=*/true, &ticket);
+                if (rc == NIDX_OK) rc = pipeline_wait(ticket, b->seg.data(), b->par.data(), b->vec.data(), b->sc.data(), b->cnt.data(), nullptr);
+            } else {
+                // every member's programs are one filter of the batch; members with equal programs (ops and lists) share it.  Each
+                // member is parked until this returns, so the programs it points at stay valid.
+                const size_t S = segs.size();
+                std::vector<nidx_gpu_filter_program_t> programs;
+                std::vector<uint32_t> filter_of(B, UINT32_MAX);
+                std::unordered_map<uint64_t, std::vector<uint32_t>> by_hash;   // hash -> filters
+                auto same = [&](const nidx_gpu_filter_program_t *a, const nidx_gpu_filter_program_t *c) {
+                    for (size_t s = 0; s < S; s++) {
+                        const bool ha = a[s].ops && a[s].n_ops, hc = c[s].ops && c[s].n_ops;
+                        if (ha != hc) return false;
+                        if (!ha) continue;
+                        if (a[s].n_ops != c[s].n_ops || a[s].n_lists != c[s].n_lists) return false;
+                        if (std::memcmp(a[s].ops, c[s].ops, (size_t)a[s].n_ops * sizeof(nidx_gpu_filter_op_t)) != 0) return false;
+                        if (a[s].n_lists && std::memcmp(a[s].lists, c[s].lists, (size_t)a[s].n_lists * 4) != 0) return false;
+                    }
+                    return true;
+                };
+                for (uint32_t i = 0; i < B; i++) {
+                    const nidx_gpu_filter_program_t *pr = b->progs[i];
+                    if (!pr) continue;
+                    uint64_t h = 1469598103934665603ull;   // FNV-1a over the programs' ops and lists
+                    auto mix = [&](const void *data, size_t n) {
+                        const unsigned char *c = static_cast<const unsigned char *>(data);
+                        for (size_t j = 0; j < n; j++) h = (h ^ c[j]) * 1099511628211ull;
+                    };
+                    for (size_t s = 0; s < S; s++) {
+                        if (!pr[s].ops || !pr[s].n_ops) { mix("-", 1); continue; }
+                        mix(pr[s].ops, (size_t)pr[s].n_ops * sizeof(nidx_gpu_filter_op_t));
+                        if (pr[s].n_lists && pr[s].lists) mix(pr[s].lists, (size_t)pr[s].n_lists * 4);
+                        mix("|", 1);
+                    }
+                    std::vector<uint32_t> &cands = by_hash[h];
+                    for (uint32_t f : cands)
+                        if (same(programs.data() + (size_t)f * S, pr)) { filter_of[i] = f; break; }
+                    if (filter_of[i] != UINT32_MAX) continue;
+                    filter_of[i] = (uint32_t)(programs.size() / S);
+                    cands.push_back(filter_of[i]);
+                    programs.insert(programs.end(), pr, pr + S);
+                }
+                rc = search_per_query(b->q.get(), B, b->params, programs.data(), (uint32_t)(programs.size() / std::max<size_t>(S, 1)),
+                                      filter_of.data(), b->seg.data(), b->par.data(), b->vec.data(), b->sc.data(), b->cnt.data(), nullptr,
+                                      nullptr);
+            }
         } catch (...) {
             rc = abi_exception();
         }
@@ -344,6 +397,25 @@ int32_t nidx_gpu_vector_search_one(nidx_gpu_vector_index_t *index, const float *
     *out_count = 0;
     if (params->k == 0) return NIDX_OK;
     return idx->search_one(query, *params, out_segment, out_paragraph, out_vector, out_score, out_count);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_one_filtered(nidx_gpu_vector_index_t *index, const float *query, uint32_t query_dimension,
+                                            const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *segment_programs,
+                                            uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                            uint32_t *out_count) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !query || !params || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension,
+                    query_dimension);
+    *out_count = 0;
+    if (params->k == 0) return NIDX_OK;
+    if (segment_programs && (params->method == NIDX_METHOD_BRUTE_FORCE_MFMA || params->method == NIDX_METHOD_BRUTE_FORCE_BF16))
+        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
+    // a malformed program fails this caller alone, before it joins a batch that other callers share
+    const int32_t rc = idx->check_request_programs(segment_programs);
+    if (rc != NIDX_OK) return rc;
+    return idx->search_one(query, *params, out_segment, out_paragraph, out_vector, out_score, out_count, segment_programs);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_coalescer_stats(nidx_gpu_vector_index_t *index, uint64_t *batches_out, uint64_t *queries_out) try {

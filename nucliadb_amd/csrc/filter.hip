@@ -7,6 +7,7 @@
 // of a segment live in HBM (CSR); the host only resolves strings to list ids (the FST lookups of
 // inverted_index/fst_index.rs stay host side) and sends a postfix program.  Pure HBM-bound bit work:
 // n_paragraphs/8 bytes per operator, 4 bytes per posting.
+#include "../../include/nidx_gpu.h"
 #include "device_common.h"
 #include "kernels.h"
 
@@ -65,6 +66,72 @@ __global__ void bitset_and_count_kernel(const uint64_t *a, const uint64_t *alive
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 
+// ---- all filter programs of a batch on one segment (VectorIndex::search_per_query) ----------------------------------------------
+// work item i = (operand row, posting list): one grid row per work item, the list's postings spread over the x blocks
+__global__ void filter_scatter_kernel(const unsigned long long *__restrict__ list_offsets, const uint32_t *__restrict__ ids,
+                                      const uint32_t *__restrict__ work, uint32_t n_work, uint32_t n_bits, uint32_t words,
+                                      unsigned int *__restrict__ operands32) {
+    for (uint32_t w = blockIdx.y; w < n_work; w += gridDim.y) {
+        unsigned int *out32 = operands32 + (size_t)work[2 * w] * words * 2;
+        const uint32_t list = work[2 * w + 1];
+        const unsigned long long b = list_offsets[list], e = list_offsets[list + 1];
+        for (unsigned long long i = b + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < e;
+             i += (unsigned long long)gridDim.x * blockDim.x) {
+            const uint32_t id = ids[i];
+            if (id < n_bits) atomicOr(&out32[id >> 5], 1u << (id & 31));
+        }
+    }
+}
+
+// The per-op kernels above, fused: one thread per word runs filter blockIdx.y's postfix program over its operand rows (the same tail
+// masks as bitset_fill / bitset_not), then the word & alive goes to the filter's row and its popcount to matching[f].
+__global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__restrict__ ops, const uint32_t *__restrict__ prog_first,
+                                                             const uint64_t *__restrict__ operands, const uint64_t *__restrict__ alive,
+                                                             uint32_t words, uint32_t n_bits, uint64_t *__restrict__ table,
+                                                             unsigned long long *__restrict__ matching) {
+    const uint32_t f = blockIdx.y;
+    const uint32_t o0 = prog_first[f], o1 = prog_first[f + 1];
+    if (o0 == o1) return;   // no program on this segment (uniform per workgroup)
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t v = 0;
+    if (w < words) {
+        const uint64_t tail = (w == words - 1 && (n_bits & 63)) ? (1ull << (n_bits & 63)) - 1ull : ~0ull;
+        uint64_t st[NIDX_FILTER_STACK];
+        int d = 0;
+        for (uint32_t i = o0; i < o1; i++) {
+            const uint32_t op = ops[i];
+            switch (op & 7u) {
+                case NIDX_FILTER_PUSH_LISTS: st[d++] = operands[(size_t)(op >> 3) * words + w]; break;
+                case NIDX_FILTER_PUSH_ALL: st[d++] = tail; break;
+                case NIDX_FILTER_PUSH_NONE: st[d++] = 0; break;
+                case NIDX_FILTER_AND: d--; st[d - 1] &= st[d]; break;
+                case NIDX_FILTER_OR: d--; st[d - 1] |= st[d]; break;
+                case NIDX_FILTER_NOT: st[d - 1] = ~st[d - 1] & tail; break;
+            }
+        }
+        v = st[0];
+        if (alive) v &= alive[w];
+        table[(size_t)f * words + w] = v;
+    }
+    unsigned long long c = (unsigned long long)__popcll(v);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
+        if (t) atomicAdd(&matching[f], t);
+    }
+}
+
+__global__ __launch_bounds__(64) void gather_rows_kernel(const float *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t dp,
+                                                         float *__restrict__ dst) {
+    const float *s = src + (size_t)idx[blockIdx.x] * dp;
+    float *o = dst + (size_t)blockIdx.x * dp;
+    for (uint32_t i = threadIdx.x; i < dp; i += 64) o[i] = s[i];
+}
+
 static inline dim3 words_grid(uint32_t n_words) { return dim3((n_words + 255) / 256); }
 
 hipError_t launch_bitset_fill(uint64_t *out, uint32_t n_words, uint32_t n_bits, int ones, hipStream_t s) {
@@ -88,6 +155,28 @@ hipError_t launch_bitset_binop(uint64_t *a, const uint64_t *b, uint32_t n_words,
 hipError_t launch_bitset_not(uint64_t *a, uint32_t n_words, uint32_t n_bits, hipStream_t s) {
     if (!n_words) return hipSuccess;
     hipLaunchKernelGGL(bitset_not_kernel, words_grid(n_words), dim3(256), 0, s, a, n_words, n_bits);
+    return hipGetLastError();
+}
+hipError_t launch_filter_scatter(const unsigned long long *list_offsets, const uint32_t *ids, const uint32_t *work, uint32_t n_work,
+                                 uint32_t n_bits, uint32_t words, uint64_t *operands, hipStream_t s) {
+    if (!n_work) return hipSuccess;
+    dim3 grid(64, n_work < 65535 ? n_work : 65535);
+    hipLaunchKernelGGL(filter_scatter_kernel, grid, dim3(256), 0, s, list_offsets, ids, work, n_work, n_bits, words,
+                       reinterpret_cast<unsigned int *>(operands));
+    return hipGetLastError();
+}
+hipError_t launch_filter_combine(const uint32_t *ops, const uint32_t *prog_first, uint32_t n_filters, const uint64_t *operands,
+                                 const uint64_t *alive, uint32_t words, uint32_t n_bits, uint64_t *table, unsigned long long *matching,
+                                 hipStream_t s) {
+    if (!n_filters || !words) return hipSuccess;
+    if (n_filters > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_combine_kernel, dim3((words + 255) / 256, n_filters), dim3(256), 0, s, ops, prog_first, operands, alive, words,
+                       n_bits, table, matching);
+    return hipGetLastError();
+}
+hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(64), 0, s, src, idx, dp, dst);
     return hipGetLastError();
 }
 hipError_t launch_bitset_and_count(const uint64_t *a, const uint64_t *alive, uint64_t *out, uint32_t n_words,

@@ -43,6 +43,12 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
 
     QueryRegs<NJ> q;
     load_query<NJ>(q, a.queries + (size_t)qi * a.seg.dp, a.seg.dp, lane, cosine);
+    // the filter closest_up_nodes tests: the launch's, or this query's own row (per-query filters)
+    const uint64_t *filter = a.filter;
+    if (a.filter_row) {
+        const uint32_t row = a.filter_row[qi];
+        filter = row == NIDX_FILTER_ROW_NONE ? nullptr : a.filter_table + (size_t)row * a.filter_words;
+    }
 
     SearchCounters st = {0, 0, 0, 0, 0, 0, 0};
     const uint64_t t_start = clock64();
@@ -140,7 +146,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
                     const uint32_t p = a.seg.para_of_vec ? a.seg.para_of_vec[c] : c;
                     if (accept) {
                         if (a.seg.alive && !bit_test(a.seg.alive, p)) accept = false;
-                        if (accept && a.filter && !bit_test(a.filter, p)) accept = false;
+                        if (accept && filter && !bit_test(filter, p)) accept = false;
                     }
                     if (accept && !a.with_duplicates) {
                         // identical bytes => identical score bits: only then compare the rows

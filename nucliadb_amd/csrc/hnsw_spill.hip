@@ -100,6 +100,11 @@ __global__ __launch_bounds__(256) void hnsw_closest_spill_kernel(HnswSpillArgs a
     const bool ctl = (nidx_tid() >> 6) == 0;
     const uint32_t slot = blockIdx.x;
     const uint32_t qi = a.query_ids[slot];
+    const uint64_t *filter = a.filter;   // the launch's, or this query's own row (per-query filters)
+    if (a.filter_row) {
+        const uint32_t row = a.filter_row[qi];
+        filter = row == NIDX_FILTER_ROW_NONE ? nullptr : a.filter_table + (size_t)row * a.filter_words;
+    }
     const bool cosine = a.seg.similarity == 1;
     const int k = (int)a.k;
 
@@ -141,7 +146,7 @@ __global__ __launch_bounds__(256) void hnsw_closest_spill_kernel(HnswSpillArgs a
                     const uint32_t p = a.seg.para_of_vec ? a.seg.para_of_vec[c] : c;
                     if (accept) {
                         if (a.seg.alive && !bit_test(a.seg.alive, p)) accept = false;
-                        if (accept && a.filter && !bit_test(a.filter, p)) accept = false;
+                        if (accept && filter && !bit_test(filter, p)) accept = false;
                     }
                     if (accept && !a.with_duplicates) {
                         for (int i = 0; i < n_res && accept; i++) {

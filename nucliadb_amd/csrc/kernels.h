@@ -22,6 +22,11 @@ struct ScanArgs {
     uint32_t qt;                  // query tile (filled by launch_scan)
     uint64_t *partial;            // [n_queries][nblk][k] rank keys
     const uint64_t *row_mask;     // shared-row scan only: bit r = row r is scanned (launch_bf16_row_mask); nullptr otherwise
+    // per-query filters (VectorIndex::search_per_query): nullptr, or [n_queries] the row of filter_table query qi tests in place of
+    // `filter`; launch_scan only (launch_scan_segments refuses it) (NIDX_FILTER_ROW_NONE: no filter for that query)
+    const uint32_t *filter_row = nullptr;
+    const uint64_t *filter_table = nullptr;   // [rows][filter_words]: filter & alive of each distinct filter (launch_filter_batch)
+    uint32_t filter_words = 0;
 };
 uint32_t scan_query_tile(uint32_t n_queries, uint32_t dp, uint32_t k);
 uint32_t scan_num_blocks(uint32_t n);
@@ -203,6 +208,11 @@ struct HnswSearchArgs {
     // walks (hnsw_search_segments_kernel); the kernels never read these two fields
     const HnswSearchArgs *seg_table = nullptr;
     uint32_t n_table = 0;
+    // per-query filters (VectorIndex::search_per_query): nullptr, or [n_queries] the row of filter_table query qi tests in place of
+    // `filter` (NIDX_FILTER_ROW_NONE: no filter for that query)
+    const uint32_t *filter_row = nullptr;
+    const uint64_t *filter_table = nullptr;   // [rows][filter_words]: filter & alive of each distinct filter (launch_filter_batch)
+    uint32_t filter_words = 0;
 };
 #define NIDX_DUMP_STRIDE 512
 hipError_t launch_hnsw_search(const HnswSearchArgs &a, int waves_per_query, hipStream_t s);
@@ -252,6 +262,11 @@ struct HnswSpillArgs {
     uint32_t *out_vec;           // [*][k]
     float *out_score;
     uint32_t *out_count;
+    // per-query filters (VectorIndex::search_per_query): nullptr, or [*] (indexed by query id) the row of filter_table query qi tests in place of
+    // `filter` (NIDX_FILTER_ROW_NONE: no filter for that query)
+    const uint32_t *filter_row = nullptr;
+    const uint64_t *filter_table = nullptr;   // [rows][filter_words]: filter & alive of each distinct filter (launch_filter_batch)
+    uint32_t filter_words = 0;
 };
 hipError_t launch_hnsw_closest_spill(const HnswSpillArgs &a, hipStream_t s);
 
@@ -292,6 +307,11 @@ struct RabitqSearchArgs {
     // suffice (see RqLayer).  Not initialised by the host.  nullptr: such a walk raises NIDX_FLAG_POOL_INEXACT instead.
     uint64_t *tie_spill = nullptr;
     uint32_t tie_stride = 0;
+    // per-query filters (VectorIndex::search_per_query): nullptr, or [n_queries] the row of filter_table query qi tests in place of
+    // `filter`; brute force only (NIDX_FILTER_ROW_NONE: no filter for that query)
+    const uint32_t *filter_row = nullptr;
+    const uint64_t *filter_table = nullptr;   // [rows][filter_words]: filter & alive of each distinct filter (launch_filter_batch)
+    uint32_t filter_words = 0;
 };
 inline uint32_t rabitq_tie_stride(uint32_t ef) { return (ef + 63u) / 64u * 64u + 64u; }
 bool rabitq_tie_spill_enabled();   // false with NIDX_GPU_RABITQ_TIE_SPILL=0 (tests: shows that a scenario does overflow the 64 ties in LDS)
@@ -343,6 +363,20 @@ hipError_t launch_key_range(const uint8_t *tbl, const unsigned long long *tbl_of
                             const uint8_t *q_prefix, uint32_t n_q, uint32_t *first, uint32_t *last, hipStream_t s);
 hipError_t launch_bitset_and_count(const uint64_t *a, const uint64_t *alive, uint64_t *out, uint32_t n_words,
                                    unsigned long long *count, hipStream_t s);
+// Every filter program of a batch on one segment in two launches, whatever their number (F):
+//   scatter: operands[o] |= the ids of posting list `list` for every work item (o, list); operands zeroed by the caller
+//   combine: one workgroup per (filter f, 256 words): the postfix program ops[prog_first[f] .. prog_first[f + 1]) over the operand rows
+//            with a stack of NIDX_FILTER_STACK words per thread, & alive -> table[f][words]; matching[f] += popcount (one atomic per
+//            workgroup).  An op is (NIDX_FILTER_* | operand << 3); an empty program writes nothing.
+#define NIDX_FILTER_STACK 32
+#define NIDX_FILTER_ROW_NONE 0xffffffffu
+hipError_t launch_filter_scatter(const unsigned long long *list_offsets, const uint32_t *ids, const uint32_t *work /*[n_work][2]*/,
+                                 uint32_t n_work, uint32_t n_bits, uint32_t words, uint64_t *operands, hipStream_t s);
+hipError_t launch_filter_combine(const uint32_t *ops, const uint32_t *prog_first, uint32_t n_filters, const uint64_t *operands,
+                                 const uint64_t *alive, uint32_t words, uint32_t n_bits, uint64_t *table, unsigned long long *matching,
+                                 hipStream_t s);
+// dst[i] = src[idx[i]] for rows of dp floats (the queries one search arm of a batch takes)
+hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s);
 
 // ---- BM25 (bm25.hip) ----
 #define BM25_MAX_CLAUSES 64

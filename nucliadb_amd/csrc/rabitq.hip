@@ -491,6 +491,11 @@ __global__ __launch_bounds__(64) void rabitq_bf_kernel(RabitqSearchArgs a) {
     RqShared sh = rq_carve(smem, nw, a.seg.dp, a.k, 0);
     rq_load_query(sh, a, qi, nw, lane);
     const RabitqQueryDev qc = a.qd[qi];
+    const uint64_t *filter = a.filter;   // the launch's, or this query's own row (per-query filters)
+    if (a.filter_row) {
+        const uint32_t row = a.filter_row[qi];
+        filter = row == NIDX_FILTER_ROW_NONE ? nullptr : a.filter_table + (size_t)row * a.filter_words;
+    }
     Reranker rr;
     rr.init(sh.best, (int)a.k, a.min_score, a.seg.vectors, a.seg.dp, sh.q);
     uint32_t n_est = 0;
@@ -502,7 +507,7 @@ __global__ __launch_bounds__(64) void rabitq_bf_kernel(RabitqSearchArgs a) {
         bool ok = p < n_para;
         if (ok) {
             if (a.seg.alive && !bit_test(a.seg.alive, p)) ok = false;
-            if (ok && a.filter && !bit_test(a.filter, p)) ok = false;
+            if (ok && filter && !bit_test(filter, p)) ok = false;
         }
         const uint32_t first = ok ? (a.para_first ? a.para_first[p] : p) : 0u;
         const uint32_t num = ok ? (a.para_first ? a.para_num[p] : 1u) : 0u;

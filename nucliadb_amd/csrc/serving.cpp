@@ -24,6 +24,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <unordered_map>
 #include <thread>
 
 #include "host_common.h"
@@ -207,6 +208,13 @@ struct Pipeline {
     uint32_t walks = 3;
     uint64_t launched = 0;            // batches whose launches were queued
     hipEvent_t gate[GATES] = {};      // gate[i % GATES]: completion of batch i
+    // tickets of nidx_gpu_vector_search_submit_filtered_per_query: searched when submitted, their hits wait here for the ticket
+    struct DoneBatch {
+        uint32_t nq = 0, k = 0;
+        std::vector<uint32_t> seg, par, vec, cnt;
+        std::vector<float> sc;
+    };
+    std::unordered_map<uint64_t, std::unique_ptr<DoneBatch>> done;
     ~Pipeline() {
         for (hipEvent_t e : gate)
             if (e) (void)hipEventDestroy(e);
@@ -578,6 +586,29 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
     Pipeline &P = *pipe;
     SearchSlot *slot = nullptr;
     {
+        std::unique_ptr<Pipeline::DoneBatch> db;
+        {
+            std::lock_guard<std::mutex> lk(P.mu);
+            auto it = P.done.find(ticket);
+            if (it != P.done.end() && it->second) {
+                db = std::move(it->second);
+                P.done.erase(it);
+            }
+        }
+        if (db) {
+            if (n_retried_out) *n_retried_out = 0;
+            for (uint32_t q = 0; q < db->nq; q++) {
+                const size_t at = (size_t)q * db->k, c = db->cnt[q];
+                out_count[q] = db->cnt[q];
+                if (out_segment) memcpy(out_segment + at, db->seg.data() + at, c * 4);
+                if (out_paragraph) memcpy(out_paragraph + at, db->par.data() + at, c * 4);
+                if (out_vector) memcpy(out_vector + at, db->vec.data() + at, c * 4);
+                if (out_score) memcpy(out_score + at, db->sc.data() + at, c * 4);
+            }
+            return NIDX_OK;
+        }
+    }
+    {
         std::lock_guard<std::mutex> lk(P.mu);
         for (auto &s : P.slots)
             if (s->busy && s->ticket == ticket && ticket != 0) { slot = s.get(); break; }
@@ -655,6 +686,39 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
     return fssc_merge(nq, sl.params, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
 }
 
+// The per-query filtered batch through the ticket interface: the filters are evaluated and their counts read back once (the one
+// synchronisation routing needs), the searches and the exact fallback run, and the hits wait for nidx_gpu_vector_search_wait.
+int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                               const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
+                                               uint64_t *ticket_out) {
+    Pipeline &P = *pipe;
+    uint64_t ticket = 0;
+    {
+        // these tickets count against pipeline_depth like the others: a caller that never waits meets NIDX_ERR_BUSY
+        std::lock_guard<std::mutex> lk(P.mu);
+        uint32_t held = (uint32_t)P.done.size();
+        for (auto &sl : P.slots) held += sl->busy ? 1u : 0u;
+        if (held >= P.depth) return fail(NIDX_ERR_BUSY, "%u tickets are outstanding (pipeline_depth)", held);
+        ticket = P.next_ticket++;
+        P.done.emplace(ticket, nullptr);   // reserved: filled below, erased on failure
+    }
+    auto db = std::make_unique<Pipeline::DoneBatch>();
+    db->nq = nq;
+    db->k = p.k;
+    const size_t kk = std::max<uint32_t>(p.k, 1);
+    db->seg.resize(nq * kk), db->par.resize(nq * kk), db->vec.resize(nq * kk), db->sc.resize(nq * kk), db->cnt.resize(nq);
+    const int32_t rc = search_per_query(queries, nq, p, programs, n_filters, filter_of_query, db->seg.data(), db->par.data(), db->vec.data(),
+                                        db->sc.data(), db->cnt.data(), nullptr, nullptr);
+    std::lock_guard<std::mutex> lk(P.mu);
+    if (rc != NIDX_OK) {
+        P.done.erase(ticket);
+        return rc;
+    }
+    P.done[ticket] = std::move(db);
+    *ticket_out = ticket;
+    return NIDX_OK;
+}
+
 }  // namespace nidx
 
 using namespace nidx;
@@ -670,6 +734,18 @@ int32_t nidx_gpu_vector_search_submit(nidx_gpu_vector_index_t *index, const floa
     if (query_dimension != idx->cfg.dimension)
         return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
     return idx->pipeline_submit(queries, n_queries, *params, segment_filters, false, ticket_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_submit_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                         uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                         const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                         const uint32_t *filter_of_query, uint64_t *ticket_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !ticket_out || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    return idx->pipeline_submit_per_query(queries, n_queries, *params, programs, n_filters, filter_of_query, ticket_out);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_search_wait(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,

@@ -302,6 +302,9 @@ int32_t VectorIndex::segment_spill_search(uint32_t s, const float *d_queries, ui
     sp.out_vec = d_out_vec;
     sp.out_score = d_out_score;
     sp.out_count = d_out_count;
+    sp.filter_row = pq_filter_row;
+    sp.filter_table = pq_filter_table;
+    sp.filter_words = pq_filter_words;
     if (method == NIDX_METHOD_RABITQ_HNSW) {
         // the re-ranked entry points of the RaBitQ arm are still in the scratch of the call that flagged
         sp.entry_vec = scratch_entry_vec.as<uint32_t>();
@@ -338,6 +341,9 @@ int32_t VectorIndex::segment_spill_search(uint32_t s, const float *d_queries, ui
         a.dump_count = scratch_dump_count.as<uint32_t>();
         a.ef_search = ef_search;
         a.ef_upper = ef_upper;
+        a.filter_row = pq_filter_row;
+        a.filter_table = pq_filter_table;
+        a.filter_words = pq_filter_words;
         NIDX_HIP(launch_hnsw_search(a, waves_per_query, st));
         std::vector<uint32_t> stats((size_t)nq * NIDX_STAT_STRIDE);
         NIDX_HIP(hipMemcpyAsync(stats.data(), scratch_stats.p, stats.size() * 4, hipMemcpyDeviceToHost, st));
@@ -443,6 +449,9 @@ HnswSearchArgs VectorIndex::hnsw_args(uint32_t s, const float *d_queries, uint32
     a.ef_search = ef_search;
     a.ef_upper = ef_upper;
     a.closest_prefetch = closest_prefetch ? 1 : 0;
+    a.filter_row = pq_filter_row;
+    a.filter_table = pq_filter_table;
+    a.filter_words = pq_filter_words;
     return a;
 }
 
@@ -465,6 +474,9 @@ ScanArgs VectorIndex::scan_args(uint32_t s, const float *d_queries, uint32_t nq,
     a.qt = 0;
     a.partial = nullptr;
     a.row_mask = nullptr;
+    a.filter_row = pq_filter_row;
+    a.filter_table = pq_filter_table;
+    a.filter_words = pq_filter_words;
     return a;
 }
 // true when segment s's exact scan of this batch takes the register-tile kernel (the shared-row scan needs large batches over
@@ -547,6 +559,9 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
         r.stats = d_stats;
         r.flag_word = d_flag_word;
         if (!hnsw) {
+            r.filter_row = pq_filter_row;
+            r.filter_table = pq_filter_table;
+            r.filter_words = pq_filter_words;
             r.n_queries = nq;
             r.out_vec = d_out_vec;
             r.out_score = d_out_score;
@@ -607,9 +622,14 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
         a.dump_score = nullptr;
         a.dump_count = nullptr;
         a.flag_word = d_flag_word;
+        a.filter_row = pq_filter_row;
+        a.filter_table = pq_filter_table;
+        a.filter_words = pq_filter_words;
         NIDX_HIP(launch_hnsw_search(a, waves_per_query, st));
         return NIDX_OK;
     }
+    if (pq_filter_row && (method == NIDX_METHOD_BRUTE_FORCE_MFMA || method == NIDX_METHOD_BRUTE_FORCE_BF16))
+        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
     const bool multi = seg.vmax > 1;
     // multi-vector paragraphs on the matrix-core scans: like the plain scan below, the k best paragraphs are covered by the k * vmax
     // best vectors, which para_best_kernel reduces to one hit per paragraph (segment.rs:582-593)
@@ -814,6 +834,7 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
         else if (!seg.all_alive) matching = seg.alive_count;
         shared_stripes = scan_shared_stripes(seg.n, nq, seg.dp, k, matching);
         if (const char *e = getenv("NIDX_GPU_SCAN_SHARED")) shared_stripes = atoi(e) ? shared_stripes : 0;
+        if (pq_filter_row) shared_stripes = 0;   // per-query filters: the register-tile scan only
         if (shared_stripes) nblk = shared_stripes;
     }
     size_t need = (size_t)nq * nblk * k * 8;
@@ -834,6 +855,9 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
     a.qt = 0;
     a.partial = scratch_partial.as<uint64_t>();
     a.row_mask = nullptr;
+    a.filter_row = pq_filter_row;
+    a.filter_table = pq_filter_table;
+    a.filter_words = pq_filter_words;
     if (shared_stripes) {
         NIDX_HIP(scratch_rowmask.reserve((size_t)((seg.n + 255u) / 256u) * 32));
         NIDX_HIP(launch_bf16_row_mask(seg.n, a.para_of_vec, a.alive, a.filter, scratch_rowmask.as<uint64_t>(), st));
@@ -1240,6 +1264,325 @@ uint64_t VectorIndex::popcount_filter(uint32_t s, const uint64_t *filt) const {
     return popcount_and(segs[s].alive_host.data(), filt, segs[s].n_paragraphs);
 }
 
+// ---- one batch, a filter per query (nidx_gpu_vector_search_filtered_per_query) -----------------------------------------------------
+// The reference builds every request's filter on its own (searcher.rs:292-343, segment.rs:516-534).  Here the distinct filters of a
+// batch are evaluated together, two launches per segment (filter.hip: launch_filter_scatter / launch_filter_combine), their
+// |filter ∩ alive| counts come back in one transfer, use_hnsw routes every (query, segment) on the host as search_host routes a
+// segment, and each arm of a segment runs once over the queries routed to it, every query testing its own filter row.
+namespace {
+// filter rows + operand rows of one chunk of a batch; a larger batch is split into chunks of queries (never refused)
+constexpr uint64_t kPqFilterScratchCap = 1ull << 30;
+constexpr size_t kPqMaxFilters = 65535;   // filters per chunk: the combine launch's grid rows
+
+bool has_program(const nidx_gpu_filter_program_t &prog) { return prog.ops && prog.n_ops; }
+
+// the checks of eval_filter_program; counts the PUSH_LISTS operands and tells whether the program needs more than the combine kernel's
+// NIDX_FILTER_STACK bitsets of stack (`deep`: such a program is evaluated op by op, as search_host evaluates it).  `who` names the
+// program in the message ("filter 3", "the request's program").
+int32_t check_program(const VectorSegment &seg, const char *who, uint32_t s, const nidx_gpu_filter_program_t &prog, uint32_t &n_operands,
+                      bool &deep) {
+    n_operands = 0;
+    deep = false;
+    if (!has_program(prog)) return NIDX_OK;
+    if (prog.n_lists && !prog.lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: %u lists but no list table", who, s, prog.n_lists);
+    int depth = 0;
+    for (uint32_t i = 0; i < prog.n_ops; i++) {
+        const nidx_gpu_filter_op_t &op = prog.ops[i];
+        switch (op.op) {
+            case NIDX_FILTER_PUSH_LISTS:
+                if (op.a > op.b || op.b > prog.n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: list range out of bounds", who, s);
+                if (op.b > op.a && !seg.f_n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: the segment has no filter index", who, s);
+                for (uint32_t l = op.a; l < op.b; l++)
+                    if (prog.lists[l] >= seg.f_n_lists)
+                        return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown posting list %u", who, s, prog.lists[l]);
+                n_operands++;
+                depth++;
+                break;
+            case NIDX_FILTER_PUSH_ALL:
+            case NIDX_FILTER_PUSH_NONE: depth++; break;
+            case NIDX_FILTER_AND:
+            case NIDX_FILTER_OR:
+                if (depth < 2) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: stack underflow", who, s);
+                depth--;
+                break;
+            case NIDX_FILTER_NOT:
+                if (depth < 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: stack underflow", who, s);
+                break;
+            default: return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown op %d", who, s, op.op);
+        }
+        if (depth > NIDX_FILTER_STACK) deep = true;
+    }
+    if (depth != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: the program must leave exactly one bitset (leaves %d)", who, s, depth);
+    return NIDX_OK;
+}
+}  // namespace
+
+int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *segment_programs) {
+    if (!segment_programs) return NIDX_OK;
+    std::lock_guard<std::mutex> lock(mu);
+    for (size_t s = 0; s < segs.size(); s++) {
+        uint32_t n_operands = 0;
+        bool dp = false;
+        const int32_t rc = check_program(segs[s], "the request's program", (uint32_t)s, segment_programs[s], n_operands, dp);
+        if (rc != NIDX_OK) return rc;
+    }
+    return NIDX_OK;
+}
+
+int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                      const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
+                                      uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                      uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) {
+    std::lock_guard<std::mutex> lock(mu);
+    NIDX_HIP(hipSetDevice(device));
+    const uint32_t k = p.k;
+    const size_t S = segs.size();
+    for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
+    if (out_method) std::fill(out_method, out_method + (size_t)nq * S, 0);
+    if (out_matching) std::fill(out_matching, out_matching + (size_t)n_filters * S, 0);
+    if (nq == 0 || k == 0 || S == 0) return NIDX_OK;
+    if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
+    if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
+    if (p.method == NIDX_METHOD_BRUTE_FORCE_MFMA || p.method == NIDX_METHOD_BRUTE_FORCE_BF16)
+        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
+    if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
+    // everything is checked before anything is launched
+    if (filter_of_query)
+        for (uint32_t q = 0; q < nq; q++)
+            if (filter_of_query[q] != UINT32_MAX && filter_of_query[q] >= n_filters)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u names filter %u of %u", q, filter_of_query[q], n_filters);
+    // scratch of a filter: a row on every segment (the table of a segment holds a row per filter of the chunk) + its operand rows
+    std::vector<uint8_t> deep((size_t)n_filters * S, 0);
+    std::vector<uint64_t> cost(n_filters, 0);
+    for (uint32_t f = 0; f < n_filters; f++) {
+        char who[32];
+        snprintf(who, sizeof(who), "filter %u", f);
+        for (size_t s = 0; s < S; s++) {
+            uint32_t n_operands = 0;
+            bool dp = false;
+            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp);
+            if (rc != NIDX_OK) return rc;
+            deep[(size_t)f * S + s] = dp ? 1 : 0;
+            cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
+        }
+    }
+    // chunks of consecutive queries whose distinct filters fit the scratch cap and the combine grid (one query at least)
+    std::vector<uint8_t> in_chunk(n_filters, 0);
+    std::vector<uint32_t> filters;
+    const uint32_t d = cfg.dimension;
+    for (uint32_t q0 = 0; q0 < nq;) {
+        filters.clear();
+        uint64_t bytes = 0;
+        uint32_t q1 = q0;
+        for (; q1 < nq; q1++) {
+            const uint32_t f = filter_of_query ? filter_of_query[q1] : UINT32_MAX;
+            if (f == UINT32_MAX || in_chunk[f]) continue;
+            if (q1 > q0 && (bytes + cost[f] > kPqFilterScratchCap || filters.size() == kPqMaxFilters)) break;
+            in_chunk[f] = 1;
+            bytes += cost[f];
+            filters.push_back(f);
+        }
+        for (uint32_t f : filters) in_chunk[f] = 0;
+        const size_t at = (size_t)q0 * k;
+        const int32_t rc = search_per_query_chunk(queries + (size_t)q0 * d, q1 - q0, p, programs, filter_of_query ? filter_of_query + q0 : nullptr,
+                                                  filters, deep, out_segment ? out_segment + at : nullptr,
+                                                  out_paragraph ? out_paragraph + at : nullptr, out_vector ? out_vector + at : nullptr,
+                                                  out_score ? out_score + at : nullptr, out_count + q0,
+                                                  out_method ? out_method + (size_t)q0 * S : nullptr, out_matching);
+        if (rc != NIDX_OK) return rc;
+        q0 = q1;
+    }
+    return NIDX_OK;
+}
+
+int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                            const nidx_gpu_filter_program_t *programs, const uint32_t *filter_of_query,
+                                            const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
+                                            uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                            uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) {
+    const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const size_t S = segs.size();
+    const uint32_t F = (uint32_t)filters.size();
+    // query batch -> HBM, as search_host stages it
+    NIDX_HIP(pin_in.reserve((size_t)nq * dp * 4));
+    stage_query_rows(queries, pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
+    NIDX_HIP(scratch_queries.reserve((size_t)nq * dp * 4));
+    NIDX_HIP(hipMemcpyAsync(scratch_queries.p, pin_in.p, (size_t)nq * dp * 4, hipMemcpyHostToDevice, stream));
+    const size_t block_words = out_block_words(nq, k);
+    NIDX_HIP(scratch_out_block.reserve(block_words * 4));
+    NIDX_HIP(pin_out.reserve(block_words * 4));
+    std::unordered_map<uint32_t, uint32_t> local;   // filter -> its row in this chunk's tables
+    for (uint32_t i = 0; i < F; i++) local.emplace(filters[i], i);
+    auto prog_of = [&](uint32_t lf, size_t s) -> const nidx_gpu_filter_program_t & { return programs[(size_t)filters[lf] * S + s]; };
+
+    // ---- every filter of the chunk on every segment: [ops][prog_first][work] per segment, one upload, two launches per segment ----
+    std::vector<uint32_t> host;
+    std::vector<size_t> at_ops(S), at_first(S), at_work(S), tab_off(S);
+    std::vector<uint32_t> n_work(S, 0), n_opnd(S, 0);
+    std::vector<uint8_t> any_prog(S, 0);
+    size_t tab_words = 0, opnd_words = 0;
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
+        std::vector<uint32_t> ops, first(F + 1, 0), work;
+        for (uint32_t lf = 0; lf < F; lf++) {
+            const nidx_gpu_filter_program_t &prog = prog_of(lf, s);
+            first[lf] = (uint32_t)ops.size();
+            if (!has_program(prog)) continue;
+            any_prog[s] = 1;
+            if (deep[(size_t)filters[lf] * S + s]) continue;   // evaluated op by op below (its combine program stays empty)
+            for (uint32_t i = 0; i < prog.n_ops; i++) {
+                const nidx_gpu_filter_op_t &op = prog.ops[i];
+                if (op.op == NIDX_FILTER_PUSH_LISTS) {
+                    const uint32_t o = n_opnd[s]++;
+                    for (uint32_t l = op.a; l < op.b; l++) {
+                        work.push_back(o);
+                        work.push_back(prog.lists[l]);
+                    }
+                    ops.push_back((uint32_t)op.op | (o << 3));
+                } else {
+                    ops.push_back((uint32_t)op.op);
+                }
+            }
+        }
+        first[F] = (uint32_t)ops.size();
+        if (!any_prog[s]) continue;
+        n_work[s] = (uint32_t)(work.size() / 2);
+        at_ops[s] = host.size();
+        host.insert(host.end(), ops.begin(), ops.end());
+        at_first[s] = host.size();
+        host.insert(host.end(), first.begin(), first.end());
+        at_work[s] = host.size();
+        host.insert(host.end(), work.begin(), work.end());
+        tab_off[s] = tab_words;
+        tab_words += (size_t)F * words;
+        opnd_words = std::max(opnd_words, (size_t)n_opnd[s] * words);
+    }
+    std::vector<unsigned long long> counts((size_t)S * F, 0);   // [segment][filter] |filter ∩ alive|
+    if (!host.empty()) {
+        NIDX_HIP(scratch_pq_prog.reserve(host.size() * 4));
+        NIDX_HIP(scratch_pq_table.reserve(std::max<size_t>(tab_words, 1) * 8));
+        NIDX_HIP(scratch_pq_operands.reserve(std::max<size_t>(opnd_words, 1) * 8));
+        NIDX_HIP(scratch_pq_count.reserve(counts.size() * 8));
+        NIDX_HIP(hipMemcpyAsync(scratch_pq_prog.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
+        NIDX_HIP(hipMemsetAsync(scratch_pq_count.p, 0, counts.size() * 8, stream));
+        const uint32_t *dprog = scratch_pq_prog.as<uint32_t>();
+        for (size_t s = 0; s < S; s++) {
+            if (!any_prog[s]) continue;
+            VectorSegment &seg = segs[s];
+            const uint32_t n_bits = seg.n_paragraphs, words = (n_bits + 63) / 64;
+            if (n_opnd[s]) NIDX_HIP(hipMemsetAsync(scratch_pq_operands.p, 0, (size_t)n_opnd[s] * words * 8, stream));
+            NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), dprog + at_work[s], n_work[s], n_bits,
+                                           words, scratch_pq_operands.as<uint64_t>(), stream));
+            NIDX_HIP(launch_filter_combine(dprog + at_ops[s], dprog + at_first[s], F, scratch_pq_operands.as<uint64_t>(),
+                                           seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), words, n_bits,
+                                           scratch_pq_table.as<uint64_t>() + tab_off[s], scratch_pq_count.as<unsigned long long>() + s * F, stream));
+        }
+        NIDX_HIP(hipMemcpyAsync(counts.data(), scratch_pq_count.p, counts.size() * 8, hipMemcpyDeviceToHost, stream));
+    }
+    NIDX_HIP(hipStreamSynchronize(stream));
+    // programs deeper than the combine kernel's stack: the per-op evaluation of search_host, copied into their rows
+    for (uint32_t lf = 0; lf < F; lf++)
+        for (size_t s = 0; s < S; s++) {
+            if (!deep[(size_t)filters[lf] * S + s]) continue;
+            uint64_t m = 0;
+            const int32_t rc = eval_filter_program((uint32_t)s, prog_of(lf, s), m);
+            if (rc != NIDX_OK) return rc;
+            const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
+            NIDX_HIP(hipMemcpyAsync(scratch_pq_table.as<uint64_t>() + tab_off[s] + (size_t)lf * words, scratch_filter.p, (size_t)words * 8,
+                                    hipMemcpyDeviceToDevice, stream));
+            counts[s * F + lf] = m;
+        }
+
+    // ---- routing of every (query, segment): OpenSegment::_search (segment.rs:506-555), exactly as search_host decides a segment ----
+    auto lf_of = [&](uint32_t q) -> uint32_t {
+        const uint32_t f = filter_of_query ? filter_of_query[q] : UINT32_MAX;
+        return f == UINT32_MAX ? NIDX_FILTER_ROW_NONE : local.at(f);
+    };
+    auto row_of = [&](uint32_t lf, size_t s) -> uint32_t { return lf != NIDX_FILTER_ROW_NONE && has_program(prog_of(lf, s)) ? lf : NIDX_FILTER_ROW_NONE; };
+    auto matching_of = [&](uint32_t row, size_t s) -> uint64_t { return row == NIDX_FILTER_ROW_NONE ? segs[s].alive_count : counts[s * F + row]; };
+    if (out_matching)
+        for (uint32_t lf = 0; lf < F; lf++)
+            for (size_t s = 0; s < S; s++) out_matching[(size_t)filters[lf] * S + s] = matching_of(row_of(lf, s), s);
+    std::vector<int32_t> method((size_t)nq * S, 0);
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint32_t lf = lf_of(q);
+        for (size_t s = 0; s < S; s++) {
+            const VectorSegment &seg = segs[s];
+            const uint64_t matching = matching_of(row_of(lf, s), s);
+            if (matching == 0 || seg.n == 0) continue;
+            int m = p.method;
+            if (m == NIDX_METHOD_AUTO) {
+                const bool rabitq = rabitq_enabled(seg);
+                const bool hnsw = seg.has_graph && use_hnsw(seg.n_paragraphs, matching, k, rabitq);
+                m = rabitq ? (hnsw ? NIDX_METHOD_RABITQ_HNSW : NIDX_METHOD_RABITQ_BRUTE_FORCE) : (hnsw ? NIDX_METHOD_HNSW : NIDX_METHOD_BRUTE_FORCE);
+            }
+            if ((m == NIDX_METHOD_HNSW || m == NIDX_METHOD_RABITQ_HNSW) && !seg.has_graph)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %zu has no HNSW graph", s);
+            method[(size_t)q * S + s] = m;
+        }
+    }
+    if (out_method) std::copy(method.begin(), method.end(), out_method);
+
+    // ---- per segment, each arm once over the queries routed to it (gathered rows; hits scattered back to their rows) ----
+    std::vector<std::vector<uint32_t>> hv(S), hc(S);
+    std::vector<std::vector<float>> hs(S);
+    static const int arms[4] = {NIDX_METHOD_HNSW, NIDX_METHOD_BRUTE_FORCE, NIDX_METHOD_RABITQ_HNSW, NIDX_METHOD_RABITQ_BRUTE_FORCE};
+    std::vector<uint32_t> idx_rows;
+    NIDX_HIP(scratch_pq_queries.reserve((size_t)nq * dp * 4));
+    NIDX_HIP(scratch_pq_rows.reserve((size_t)nq * 2 * 4));
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
+        for (int arm : arms) {
+            idx_rows.clear();
+            bool filtered = false;
+            for (uint32_t q = 0; q < nq; q++)
+                if (method[(size_t)q * S + s] == arm) idx_rows.push_back(q);
+            const uint32_t n = (uint32_t)idx_rows.size();
+            if (!n) continue;
+            for (uint32_t i = 0; i < n; i++) {
+                const uint32_t row = row_of(lf_of(idx_rows[i]), s);
+                filtered = filtered || row != NIDX_FILTER_ROW_NONE;
+                idx_rows.push_back(row);
+            }
+            if (hc[s].empty()) {
+                hv[s].assign((size_t)nq * k, 0);
+                hs[s].assign((size_t)nq * k, 0.f);
+                hc[s].assign(nq, 0);
+            }
+            uint32_t *d_idx = scratch_pq_rows.as<uint32_t>();
+            NIDX_HIP(hipMemcpyAsync(d_idx, idx_rows.data(), (size_t)n * 2 * 4, hipMemcpyHostToDevice, stream));
+            NIDX_HIP(launch_gather_rows(scratch_queries.as<float>(), d_idx, n, dp, scratch_pq_queries.as<float>(), stream));
+            if (filtered) {   // (an arm whose queries are all unfiltered here runs the plain launches)
+                pq_filter_row = d_idx + n;
+                pq_filter_table = scratch_pq_table.as<uint64_t>() + tab_off[s];
+                pq_filter_words = words;
+            }
+            const int32_t rc = segment_search_exact((uint32_t)s, scratch_pq_queries.as<float>(), n, k, p.min_score, p.with_duplicates != 0, arm,
+                                                    nullptr, scratch_out_block.as<uint32_t>(), pin_out.as<uint32_t>(), stream, nullptr);
+            pq_filter_row = nullptr;
+            pq_filter_table = nullptr;
+            pq_filter_words = 0;
+            if (rc != NIDX_OK) return rc;
+            const uint32_t *blk = pin_out.as<uint32_t>();
+            for (uint32_t i = 0; i < n; i++) {
+                const uint32_t q = idx_rows[i];
+                memcpy(hv[s].data() + (size_t)q * k, blk + (size_t)i * k, (size_t)k * 4);
+                memcpy(hs[s].data() + (size_t)q * k, blk + (size_t)n * k + (size_t)i * k, (size_t)k * 4);
+                hc[s][q] = blk[(size_t)n * k * 2 + i];
+            }
+        }
+    }
+    std::vector<const uint32_t *> pv(S), pc(S);
+    std::vector<const float *> ps(S);
+    for (size_t s = 0; s < S; s++) {
+        const bool any = !hc[s].empty();
+        pv[s] = any ? hv[s].data() : nullptr;
+        ps[s] = any ? hs[s].data() : nullptr;
+        pc[s] = any ? hc[s].data() : nullptr;
+    }
+    return fssc_merge(nq, p, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
+}
+
 }  // namespace nidx
 
 // =====================================================================================================
@@ -1625,6 +1968,20 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
                     query_dimension);
     return idx->search_host(queries, n_queries, *params, nullptr, segment_programs, out_segment, out_paragraph, out_vector,
                             out_score, out_count, out_method, out_matching);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                  uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                  const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
+                                                  uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                                  uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !out_count || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension,
+                    query_dimension);
+    return idx->search_per_query(queries, n_queries, *params, programs, n_filters, filter_of_query, out_segment, out_paragraph, out_vector,
+                                 out_score, out_count, out_method, out_matching);
 } NIDX_ABI_CATCH
 
 static int32_t device_entry_method(VectorIndex *idx, uint32_t segment, const nidx_gpu_vector_search_params_t *params,

@@ -122,6 +122,12 @@ struct VectorIndex {
         scratch_stats, scratch_rq, scratch_planes, scratch_vis, scratch_ties, scratch_entry_vec, scratch_entry_score, scratch_entry_count,
         scratch_dump_vec, scratch_dump_score, scratch_dump_count, scratch_spill_pool, scratch_spill_cmax, scratch_spill_vis, scratch_spill_ids, scratch_rowmask, scratch_floor, scratch_floor2, scratch_bf16_flags, scratch_bf16_counts;
     uint64_t scan_matching_hint = ~0ull;  // paragraphs passing the current filter when the caller knows (search_host), ~0 = unknown
+    // per-query filters (search_per_query): while set, every launch of one segment_search_exact resolves its filter per query —
+    // query i tests row pq_filter_row[i] of pq_filter_table (NIDX_FILTER_ROW_NONE: none) — and the shared-row scan is not used
+    const uint32_t *pq_filter_row = nullptr;
+    const uint64_t *pq_filter_table = nullptr;
+    uint32_t pq_filter_words = 0;
+    DevBuf scratch_pq_table, scratch_pq_operands, scratch_pq_prog, scratch_pq_count, scratch_pq_rows, scratch_pq_queries;
     uint64_t spill_queries = 0;  // queries re-run by the exact fallback since open (tunable "spill_queries" reads it)
     bool rabitq_enabled(const VectorSegment &seg) const { return seg.has_quant && !(cfg.flags & NIDX_CONFIG_DISABLE_RABITQ_SEARCH); }
     int32_t quantize(uint32_t segment);
@@ -165,6 +171,19 @@ struct VectorIndex {
                         const uint64_t *const *segment_filters, const nidx_gpu_filter_program_t *programs,
                         uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                         uint32_t *out_count, int32_t *out_method, uint64_t *out_matching);
+    // one batch in which query q uses filter filter_of_query[q] (nidx_gpu_vector_search_filtered_per_query); chunks of queries whose
+    // filter rows fit kPqFilterScratchCap go through search_per_query_chunk one after the other
+    int32_t search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
+                             uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment, uint32_t *out_paragraph,
+                             uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method, uint64_t *out_matching);
+    int32_t search_per_query_chunk(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
+                                   const uint32_t *filter_of_query, const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
+                                   uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                                   int32_t *out_method, uint64_t *out_matching);
+    // the checks search_per_query makes of one request's [n_segments] programs (nullptr: unfiltered), before it joins a coalesced batch
+    int32_t check_request_programs(const nidx_gpu_filter_program_t *segment_programs);
+    int32_t pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
+                                      uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out);
     // Fssc over per-segment result rows (nullptr = segment not searched); shared by search_host and the pipeline's wait
     int32_t fssc_merge(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const uint32_t *const *seg_vec, const float *const *seg_score,
                        const uint32_t *const *seg_count, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,
@@ -187,7 +206,8 @@ struct VectorIndex {
     int32_t reserve_search(uint32_t nq_max, uint32_t k);
     uint32_t reserved_nq = 0, reserved_k = 0;
     int32_t search_one(const float *query, const nidx_gpu_vector_search_params_t &p, uint32_t *out_segment,
-                       uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count);
+                       uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                       const nidx_gpu_filter_program_t *segment_programs = nullptr);
     void coalescer_stats(uint64_t &batches, uint64_t &queries);
     void coalescer_config(int32_t window_us, int32_t max_batch, int32_t in_flight);
     void coalescer_admission(int32_t max_callers, int32_t reject_when_full);

@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void pair_similarity_kernel(const float *__res
 // ---------------------------------------------------------------------------------------------
 // scan + per-block top-k
 // ---------------------------------------------------------------------------------------------
-template <int NJ, int QT, int KL>
+// PQ: per-query filters (a.filter_row): a row is skipped only when no query of the tile passes it; admission tests the lane's own query
+template <int NJ, int QT, int KL, bool PQ = false>
 __device__ inline void scan_topk_body(const ScanArgs &a) {
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;  // wave in block
@@ -111,10 +112,30 @@ __device__ inline void scan_topk_body(const ScanArgs &a) {
     uint64_t thr = NIDX_EMPTY_KEY;  // k-th key of this lane's query (EMPTY while the list is short)
     const int k = (int)a.k;
 
+    // PQ: the filter row of each query of the tile (nullptr = unfiltered); tile slots past n_queries repeat the last query
+    const uint64_t *qf[QT];
+    const uint64_t *myf = nullptr;
+    if constexpr (PQ) {
+#pragma unroll
+        for (int q = 0; q < QT; q++) {
+            const uint32_t qi = q0 + q < a.n_queries ? q0 + q : a.n_queries - 1;
+            const uint32_t row = a.filter_row[qi];
+            qf[q] = row == NIDX_FILTER_ROW_NONE ? nullptr : a.filter_table + (size_t)row * a.filter_words;
+            if (myq == q) myf = qf[q];
+        }
+    }
+
     auto passes = [&](uint32_t r) -> bool {
         uint32_t p = a.para_of_vec ? a.para_of_vec[r] : r;
         if (a.alive && !bit_test(a.alive, p)) return false;
-        if (a.filter && !bit_test(a.filter, p)) return false;
+        if constexpr (PQ) {
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < QT; q++) any = any || !qf[q] || bit_test(qf[q], p);
+            return any;
+        } else {
+            if (a.filter && !bit_test(a.filter, p)) return false;
+        }
         return true;
     };
 
@@ -160,6 +181,9 @@ __device__ inline void scan_topk_body(const ScanArgs &a) {
         }
         uint64_t ck = rank_key(score, r);
         bool ok = (score >= a.min_score) && (ck > thr) && ((lane & QReduce<QT>::group_mask()) == 0);
+        if constexpr (PQ) {
+            if (ok && myf) ok = bit_test(myf, a.para_of_vec ? a.para_of_vec[r] : r);
+        }
         unsigned long long m = __ballot(ok);
         while (m) {
             int src = __ffsll((long long)m) - 1;
@@ -209,9 +233,9 @@ __device__ inline void scan_topk_body(const ScanArgs &a) {
     }
 }
 
-template <int NJ, int QT, int KL>
+template <int NJ, int QT, int KL, bool PQ = false>
 __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
-    scan_topk_body<NJ, QT, KL>(a);
+    scan_topk_body<NJ, QT, KL, PQ>(a);
 }
 // The exact scans of SEVERAL segments in one launch (a multi-segment index under a selective filter: OpenSegment::_search routes
 // every segment to brute force, segment.rs:506-555 — a launch pair per segment was 100 launches per batch on the reference's
@@ -292,19 +316,19 @@ __global__ __launch_bounds__(256) void merge_topk_segments_kernel(const ScanMerg
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-template <int NJ, bool WIDE>
+template <int NJ, bool WIDE, bool PQ>
 static hipError_t launch_scan_nj(const ScanArgs &a, uint32_t nblk, hipStream_t s) {
     if (a.k > 256) {  // k up to 512 (rank-fusion / reranker windows reach 500): 8 chained lists, one query per pass
-        hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 8>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 8, PQ>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
     } else if (a.k > 64) {  // large result pages: 4 chained lists per query, at most 4 queries per pass
-        if (a.qt == 1) hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 4>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((scan_topk_kernel<NJ, 4, 4>), dim3(nblk, (a.n_queries + 3) / 4), dim3(256), 0, s, a);
+        if (a.qt == 1) hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 4, PQ>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((scan_topk_kernel<NJ, 4, 4, PQ>), dim3(nblk, (a.n_queries + 3) / 4), dim3(256), 0, s, a);
     } else if (a.qt == 1) {
-        hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 1>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((scan_topk_kernel<NJ, 1, 1, PQ>), dim3(nblk, a.n_queries), dim3(256), 0, s, a);
     } else if (a.qt == 4 || !WIDE) {
-        hipLaunchKernelGGL((scan_topk_kernel<NJ, 4, 1>), dim3(nblk, (a.n_queries + 3) / 4), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((scan_topk_kernel<NJ, 4, 1, PQ>), dim3(nblk, (a.n_queries + 3) / 4), dim3(256), 0, s, a);
     } else {
-        hipLaunchKernelGGL((scan_topk_kernel<NJ, (WIDE ? 8 : 4), 1>), dim3(nblk, (a.n_queries + 7) / 8), dim3(256), 0, s,
+        hipLaunchKernelGGL((scan_topk_kernel<NJ, (WIDE ? 8 : 4), 1, PQ>), dim3(nblk, (a.n_queries + 7) / 8), dim3(256), 0, s,
                            a);
     }
     return hipGetLastError();
@@ -346,20 +370,21 @@ hipError_t launch_scan(ScanArgs a, uint32_t nblk, hipStream_t s) {
     if (a.k == 0 || a.k > NIDX_K_MAX) return hipErrorInvalidValue;
     a.qt = scan_query_tile(a.n_queries, a.dp, a.k);
     int nj = (int)((a.dp + 255u) / 256u);
-    if (nj <= 1) return launch_scan_nj<1, true>(a, nblk, s);
-    if (nj <= 2) return launch_scan_nj<2, true>(a, nblk, s);
-    if (nj <= 3) return launch_scan_nj<3, true>(a, nblk, s);
-    if (nj <= 4) return launch_scan_nj<4, true>(a, nblk, s);
-    if (nj <= 6) return launch_scan_nj<6, false>(a, nblk, s);
-    if (nj <= 8) return launch_scan_nj<8, false>(a, nblk, s);
-    if (nj <= 12) return launch_scan_nj<12, false>(a, nblk, s);
-    if (nj <= 16) return launch_scan_nj<16, false>(a, nblk, s);
+    if (nj <= 1) return a.filter_row ? launch_scan_nj<1, true, true>(a, nblk, s) : launch_scan_nj<1, true, false>(a, nblk, s);
+    if (nj <= 2) return a.filter_row ? launch_scan_nj<2, true, true>(a, nblk, s) : launch_scan_nj<2, true, false>(a, nblk, s);
+    if (nj <= 3) return a.filter_row ? launch_scan_nj<3, true, true>(a, nblk, s) : launch_scan_nj<3, true, false>(a, nblk, s);
+    if (nj <= 4) return a.filter_row ? launch_scan_nj<4, true, true>(a, nblk, s) : launch_scan_nj<4, true, false>(a, nblk, s);
+    if (nj <= 6) return a.filter_row ? launch_scan_nj<6, false, true>(a, nblk, s) : launch_scan_nj<6, false, false>(a, nblk, s);
+    if (nj <= 8) return a.filter_row ? launch_scan_nj<8, false, true>(a, nblk, s) : launch_scan_nj<8, false, false>(a, nblk, s);
+    if (nj <= 12) return a.filter_row ? launch_scan_nj<12, false, true>(a, nblk, s) : launch_scan_nj<12, false, false>(a, nblk, s);
+    if (nj <= 16) return a.filter_row ? launch_scan_nj<16, false, true>(a, nblk, s) : launch_scan_nj<16, false, false>(a, nblk, s);
     return hipErrorInvalidValue;
 }
 
 // `table` (device): n_seg records that agree with `shape` (host: one of them, qt filled like launch_scan does) in dp, k, n_queries, qt;
 // every record's `partial` has room for [n_queries][nblk][k] keys.  The grid's y dimension carries the query tiles (<= 65 535).
 hipError_t launch_scan_segments(const ScanArgs *table, uint32_t n_seg, ScanArgs shape, uint32_t nblk, hipStream_t s) {
+    if (shape.filter_row) return hipErrorInvalidValue;   // (per-query filters run through launch_scan, one segment per launch)
     if (shape.k == 0 || shape.k > NIDX_K_MAX || n_seg == 0 || n_seg > 65535u) return hipErrorInvalidValue;
     shape.qt = scan_query_tile(shape.n_queries, shape.dp, shape.k);
     int nj = (int)((shape.dp + 255u) / 256u);

@@ -956,6 +956,102 @@ class VectorSearcher:
             docs.append(DocumentScored(sg.keys[p], float(score[0, i]), md if md else None, list(sg.labels[p])))
         return VectorSearchResponse(docs)
 
+    # -- many requests, each with its own filter (nidx_gpu_vector_search_filtered_per_query) ----------------------------------------
+    def _request_programs(self, request: VectorSearchRequest, prefilter: PrefilterResult):
+        """The per-segment programs search_batch would send for this request, as hashable (ops, lists) tuples (None: no filter on
+        that segment); None when the request is unfiltered everywhere."""
+        formula = self._formula(request, prefilter)
+        progs = []
+        for s, seg in enumerate(self._segments):
+            if request.segment_filtering_formula is not None and not _segment_matches(request.segment_filtering_formula, seg.tags):
+                progs.append((((_lib.FILTER_PUSH_NONE, 0, 0),), ()))
+            elif formula is not None:
+                ops, lists = seg.compile(formula, lookup=lambda queries, s=s: self._lookup(s, queries))
+                progs.append((tuple(tuple(int(x) for x in o) for o in ops), tuple(int(x) for x in lists)))
+            else:
+                progs.append(None)
+        return None if all(p is None for p in progs) else tuple(progs)
+
+    def search_many(self, requests: Sequence[VectorSearchRequest], prefilters: Optional[Sequence[PrefilterResult]] = None,
+                    method: int = _lib.METHOD_AUTO) -> List[VectorSearchResponse]:
+        """[self.search(r, p, method) for r, p in zip(requests, prefilters)] in one native call per group of requests with equal
+        (result_per_page, min_score, with_duplicates); every request keeps its own filter (formula, segment formula, operator and
+        prefilter), identical programs share one.  Multi-vector indexes search request by request."""
+        requests = list(requests)
+        prefilters = [None] * len(requests) if prefilters is None else list(prefilters)
+        if len(prefilters) != len(requests):
+            raise ValueError("one prefilter per request")
+        prefilters = [p or PrefilterResult.all() for p in prefilters]
+        if self.config.vector_cardinality == VectorCardinality.Multi:
+            return [self.search(r, p, method) for r, p in zip(requests, prefilters)]
+        d = self.config.dimension
+        S = len(self._segments)
+        out: List[Optional[VectorSearchResponse]] = [None] * len(requests)
+        for members in group_requests(requests):
+            r0 = requests[members[0]]
+            k = max(0, int(r0.result_per_page))
+            queries = np.zeros((len(members), d), dtype=np.float32)
+            for row, i in enumerate(members):
+                v = np.asarray(requests[i].vector, dtype=np.float32).reshape(-1)
+                if v.size != d:
+                    raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS, f"Inconsistent dimensions. Index={d} Vector={v.size}")
+                queries[row] = v
+            uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
+            progs = (_lib.FilterProgramC * max(1, len(uniq) * S))()
+            keep = []
+            for f, prog in enumerate(uniq):
+                for s, sp in enumerate(prog):
+                    if sp is None:
+                        continue
+                    ops, lists = sp
+                    c_ops = (_lib.FilterOpC * len(ops))(*[_lib.FilterOpC(*o) for o in ops])
+                    c_lists = np.array(lists, dtype=np.uint32)
+                    keep += [c_ops, c_lists]
+                    progs[f * S + s] = _lib.FilterProgramC(C.addressof(c_ops), len(ops), c_lists.ctypes.data if len(lists) else None, len(lists))
+            foq = np.array(filter_of, dtype=np.uint32)
+            B, kk = len(members), max(1, k)
+            out_seg, out_par = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.uint32)
+            out_vec, out_score, out_count = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.float32), np.zeros(B, np.uint32)
+            params = _lib.VectorSearchParamsC(k, float(r0.min_score), int(r0.with_duplicates), method)
+            _lib.check(_lib.lib().nidx_gpu_vector_search_filtered_per_query(
+                self._handle, queries.ctypes.data, B, d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
+                out_seg.ctypes.data, out_par.ctypes.data, out_vec.ctypes.data, out_score.ctypes.data, out_count.ctypes.data, None, None))
+            for row, i in enumerate(members):
+                docs = []
+                for j in range(int(out_count[row])):
+                    s_, p = int(out_seg[row, j]), int(out_par[row, j])
+                    sg = self._segments[s_]
+                    md = sg.metadata[p]
+                    docs.append(DocumentScored(sg.keys[p], float(out_score[row, j]), md if md else None, list(sg.labels[p])))
+                out[i] = VectorSearchResponse(docs)
+        return out  # type: ignore[return-value]
+
+
+def group_requests(requests: Sequence[VectorSearchRequest]) -> List[List[int]]:
+    """Indices of the requests one native batch can serve together: equal (result_per_page, min_score as f32, with_duplicates), in
+    order of first appearance."""
+    groups: dict = {}
+    for i, r in enumerate(requests):
+        key = (max(0, int(r.result_per_page)), int(np.float32(r.min_score).view(np.uint32)), bool(r.with_duplicates))
+        groups.setdefault(key, []).append(i)
+    return list(groups.values())
+
+
+def dedup_programs(programs: Sequence) -> Tuple[list, List[int]]:
+    """Distinct filters of a batch: (unique programs in order of first use, filter index per request; 0xFFFFFFFF = unfiltered)."""
+    uniq: list = []
+    index: dict = {}
+    filter_of = []
+    for p in programs:
+        if p is None:
+            filter_of.append(0xFFFFFFFF)
+            continue
+        if p not in index:
+            index[p] = len(uniq)
+            uniq.append(p)
+        filter_of.append(index[p])
+    return uniq, filter_of
+
 
 def fst_map_build(entries: Sequence[Tuple[bytes, int]]) -> bytes:
     """fst::MapBuilder over strictly ascending (key, value) pairs (nidx_gpu_fst_map_build) -> the image."""
