@@ -21,6 +21,8 @@ namespace nidx {
 
 #define NIDX_POOL_CAP 512
 #define NIDX_VIS_EMPTY 0xffffffffu
+// closest_up_nodes: fresh neighbours listed instead of scored (hnsw_search.hip); the list lives in SearchShared::eps
+#define NIDX_DEFER_CAP 256
 
 // The neighbours of one expansion: their addresses and, after the distance phase, the two sums of each.
 struct NbBuf {
@@ -31,7 +33,7 @@ struct NbBuf {
 struct SearchShared {
     uint64_t pool[NIDX_POOL_CAP];  // unexpanded candidates (rank keys), unsorted
     NbBuf nb[2];                   // two expansions: the one being admitted and the one being evaluated (layer_search_block)
-    uint32_t eps[256];             // entry points for the next layer search
+    uint32_t eps[256];             // entry points for the next layer search; closest_up_nodes: the deferred neighbours
     int ctrl[12];                  // [0] continue, [1] n_new (single-buffer loops), [2] n_eps, [3] next row to evaluate,
                                    // [4] redo, [5] the speculated expansion exists, [6..7] n_new of nb[0], nb[1]
 };

@@ -5,6 +5,7 @@
 //   closest_up_nodes (filter / de-duplication / min_score walk), final stable sort by score.
 // Bound: HBM (random 4*D-byte row gathers + 256-byte edge records).  Algorithmic bytes per query =
 // evals * 4*D + expansions * 256 (both counted by the kernel).
+// closest_up_nodes counts the rows of deferred evaluations without reading them (see there): bytes moved are below that figure.
 #include "hnsw_device.h"
 
 namespace nidx {
@@ -101,12 +102,29 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     // candidates = the ef neighbours; visited = exactly those; pop best, accept if it passes the
     // filter, stop at k accepted, otherwise expand its unvisited layer-0 neighbours that score
     // >= min_score.
+    //
+    // Deferred expansions.  The reference scores every fresh neighbour of an expanded candidate at once.  After a complete layer-0
+    // search those scores rarely matter: every member of the result set was expanded there (the search only stops when the best
+    // unexpanded candidate is BELOW the worst member), so each neighbour of a member was visited, and a visited node outside the
+    // final set scores <= ws, the worst member's score (never admitted, or evicted as the worst; ws only grows).  A fresh neighbour
+    // can therefore be popped only after every candidate that scores strictly above ws.  While that holds, an expansion does the
+    // bookkeeping the reference does (visited marks, counters, overflow check) and only lists the fresh addresses in sh.eps, idle in
+    // this phase; wave 0 walks on alone, without a barrier.  When the popped candidate does not score above ws, the pool is empty
+    // or the list is full, the listed rows are scored by all waves (same loads, fma chain and butterfly: same bits) and pushed in
+    // their original order, and the walk goes on as the reference's.  ef + NIDX_DEFER_CAP <= NIDX_POOL_CAP: no eviction can fall
+    // into the deferred stretch, so the pool after the pushes is, as a set of distinct keys, exactly the eager walk's.
+    // Not deferred: entry mode (re-ranked candidates, not a layer-0 set), a search that raised a flag, a set with a NaN score
+    // (first or last in the total order), more entry points than ef (the set then is larger than ef).
     const uint32_t vis_cap = 1u << a.vis_log2;
     vis_clear(vis, vis_cap);
     __syncthreads();
     int pool_len = 0, n_res = 0;
     uint32_t vis_count = 0;
     uint64_t dropped_best = NIDX_EMPTY_KEY;
+    // wave 0's state of the deferral, kept in LDS (registers are what bounds the walks per CU): sh.ctrl[8] = the bits of ws,
+    // sh.ctrl[9] = the number of addresses listed in sh.eps, expansion after expansion in edge order, or -1: not deferring;
+    // sh.ctrl[10] = rows of a list being scored that are still waiting in sh.eps (an NbBuf takes 64 at a time), from sh.ctrl[11] on.
+    //
     // The edge record of the candidate that will most likely be popped next — the best one left in the pool: a new neighbour rarely
     // beats it, the pool holds the ef best nodes the layer search found — is requested while this expansion's rows are scored, so the
     // next expansion starts without the edge round trip in front of its rows (wave 0; pf_word = word `lane` of pf_node's record).
@@ -121,6 +139,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         }
         pool_len = n_entry;
         vis_count = n_entry;
+        if (lane == 0) {
+            sh.ctrl[9] = -1;
+            sh.ctrl[10] = 0;
+        }
     } else if (ctl) {
 #pragma unroll
         for (int i = 0; i < EFL; i++) {
@@ -132,77 +154,124 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         }
         pool_len = res.len;
         vis_count = res.len;
+        bool lazy = false;
+        float ws = 0.f;
+        if (res.len > 0 && st.flags == 0 && sh.ctrl[2] <= ef && ef + NIDX_DEFER_CAP <= NIDX_POOL_CAP) {
+            const float s0 = rank_key_score(res.at(0));
+            ws = res.worst_score();
+            lazy = s0 == s0 && ws == ws;
+        }
+        if (lane == 0) {
+            sh.ctrl[8] = __builtin_bit_cast(int, ws);
+            sh.ctrl[9] = lazy ? 0 : -1;
+            sh.ctrl[10] = 0;
+        }
     }
     for (;;) {
         if (ctl) {
-            int cont = 0, n_new = 0;
-            uint64_t ck = pool_pop(sh.pool, pool_len, lane);
-            if (ck != NIDX_EMPTY_KEY) {
-                float cs = rank_key_score(ck);
-                uint32_t c = rank_key_addr(ck);
-                if (dropped_best > ck) st.flags |= NIDX_FLAG_POOL_INEXACT;
-                if (!(cs < a.min_score)) {
-                    bool accept = !(cs != cs);
-                    const uint32_t p = a.seg.para_of_vec ? a.seg.para_of_vec[c] : c;
-                    if (accept) {
-                        if (a.seg.alive && !bit_test(a.seg.alive, p)) accept = false;
-                        if (accept && filter && !bit_test(filter, p)) accept = false;
+            // cont: the walk goes on, once the n_new addresses in sh.eps[from ..) are scored and pushed, 64 per turn of this loop
+            int cont = 1, n_new = 0, from = 0;
+            const int waiting = sh.ctrl[10];
+            if (waiting > 0) {
+                n_new = waiting;
+                from = sh.ctrl[11];
+            } else for (;;) {   // more than one turn only while expansions are deferred
+                cont = 0;
+                n_new = 0;
+                bool again = false;
+                uint64_t ck = pool_pop(sh.pool, pool_len, lane);
+                const int n_def = sh.ctrl[9];
+                if (n_def > 0 && !(ck != NIDX_EMPTY_KEY && rank_key_score(ck) > __builtin_bit_cast(float, sh.ctrl[8]))) {
+                    // a listed node may rank before ck: score them all, then pop again
+                    if (ck != NIDX_EMPTY_KEY) {
+                        if (lane == 0) sh.pool[pool_len] = ck;
+                        pool_len++;
                     }
-                    if (accept && !a.with_duplicates) {
-                        // identical bytes => identical score bits: only then compare the rows
-                        for (int i = 0; i < n_res && accept; i++) {
-                            if (__builtin_bit_cast(uint32_t, res_score[i]) == __builtin_bit_cast(uint32_t, cs) &&
-                                rows_equal<NJ>(a.seg, res_addr[i], c, lane))
-                                accept = false;
+                    cont = 1;
+                    n_new = n_def;
+                    if (lane == 0) sh.ctrl[9] = -1;
+                    break;
+                }
+                if (ck != NIDX_EMPTY_KEY) {
+                    float cs = rank_key_score(ck);
+                    uint32_t c = rank_key_addr(ck);
+                    if (dropped_best > ck) st.flags |= NIDX_FLAG_POOL_INEXACT;
+                    if (!(cs < a.min_score)) {
+                        bool accept = !(cs != cs);
+                        const uint32_t p = a.seg.para_of_vec ? a.seg.para_of_vec[c] : c;
+                        if (accept) {
+                            if (a.seg.alive && !bit_test(a.seg.alive, p)) accept = false;
+                            if (accept && filter && !bit_test(filter, p)) accept = false;
                         }
-                    }
-                    if (accept && a.multi) {
-                        // one hit per paragraph (checked after the duplicate test, like NodeFilter::passes)
-                        for (int base = 0; base < n_res && accept; base += 64)
-                            if (__ballot(base + lane < n_res && res_para[base + lane] == p)) accept = false;
-                    }
-                    if (accept) {
-                        if (lane == 0) {
-                            res_addr[n_res] = c;
-                            res_score[n_res] = cs;
-                            res_para[n_res] = p;
+                        if (accept && !a.with_duplicates) {
+                            // identical bytes => identical score bits: only then compare the rows
+                            for (int i = 0; i < n_res && accept; i++) {
+                                if (__builtin_bit_cast(uint32_t, res_score[i]) == __builtin_bit_cast(uint32_t, cs) &&
+                                    rows_equal<NJ>(a.seg, res_addr[i], c, lane))
+                                    accept = false;
+                            }
                         }
-                        n_res++;
-                    }
-                    if (n_res < k) {
-                        cont = 1;
-                        uint32_t deg;
-                        uint32_t w;
-                        if (c == pf_node) {
-                            w = pf_word;
-                            deg = lane_bcast_u32(w, 0);
-                            st.edge_hits++;
-                        } else {
-                            w = load_edge_word(a.g, c, 0, lane, deg);
+                        if (accept && a.multi) {
+                            // one hit per paragraph (checked after the duplicate test, like NodeFilter::passes)
+                            for (int base = 0; base < n_res && accept; base += 64)
+                                if (__ballot(base + lane < n_res && res_para[base + lane] == p)) accept = false;
                         }
-                        if (a.closest_prefetch) {
-                            const uint64_t nk = pool_peek(sh.pool, pool_len, lane);
-                            pf_node = nk != NIDX_EMPTY_KEY ? rank_key_addr(nk) : 0xffffffffu;
-                            if (pf_node != 0xffffffffu) pf_word = a.g.l0[(size_t)pf_node * NIDX_L0_STRIDE + lane];
+                        if (accept) {
+                            if (lane == 0) {
+                                res_addr[n_res] = c;
+                                res_score[n_res] = cs;
+                                res_para[n_res] = p;
+                            }
+                            n_res++;
                         }
-                        bool is_edge = lane >= 1 && lane <= (int)deg;
-                        bool fresh = is_edge && vis_insert(vis, a.vis_log2, w);
-                        unsigned long long m = __ballot(fresh);
-                        int pos = __popcll(m & ((1ull << lane) - 1ull));
-                        if (fresh) sh.nb[0].addr[pos] = w;
-                        n_new = __popcll(m);
-                        st.expansions++;
-                        vis_count += n_new;
-                        if (vis_count > vis_cap - vis_cap / 4) {
-                            st.flags |= NIDX_FLAG_VISITED_OVERFLOW;
-                            cont = 0;
+                        if (n_res < k) {
+                            cont = 1;
+                            uint32_t deg;
+                            uint32_t w;
+                            if (c == pf_node) {
+                                w = pf_word;
+                                deg = lane_bcast_u32(w, 0);
+                                st.edge_hits++;
+                            } else {
+                                w = load_edge_word(a.g, c, 0, lane, deg);
+                            }
+                            if (a.closest_prefetch) {
+                                const uint64_t nk = pool_peek(sh.pool, pool_len, lane);
+                                pf_node = nk != NIDX_EMPTY_KEY ? rank_key_addr(nk) : 0xffffffffu;
+                                if (pf_node != 0xffffffffu) pf_word = a.g.l0[(size_t)pf_node * NIDX_L0_STRIDE + lane];
+                            }
+                            bool is_edge = lane >= 1 && lane <= (int)deg;
+                            bool fresh = is_edge && vis_insert(vis, a.vis_log2, w);
+                            unsigned long long m = __ballot(fresh);
+                            int pos = __popcll(m & ((1ull << lane) - 1ull));
+                            const int at = n_def > 0 ? n_def : 0;
+                            if (fresh) sh.eps[at + pos] = w;
+                            n_new = __popcll(m);
+                            st.expansions++;
+                            vis_count += n_new;
+                            if (vis_count > vis_cap - vis_cap / 4) {
+                                st.flags |= NIDX_FLAG_VISITED_OVERFLOW;
+                                cont = 0;
+                            } else {
+                                // counted as evaluated (the reference does evaluate them), read only if a pop can depend on them
+                                st.evals += n_new;
+                                if (n_def >= 0) {
+                                    n_new += n_def;
+                                    again = n_new <= NIDX_DEFER_CAP - 63;   // else the next record may not fit: score the list now
+                                    if (lane == 0) sh.ctrl[9] = again ? n_new : -1;
+                                }
+                            }
                         }
                     }
                 }
+                if (!again) break;
             }
+            sh.nb[0].addr[lane] = sh.eps[from + lane];
             if (lane == 0) {
                 sh.ctrl[0] = cont;
-                sh.ctrl[1] = n_new;
+                sh.ctrl[1] = n_new > 64 ? 64 : n_new;
+                sh.ctrl[10] = n_new > 64 ? n_new - 64 : 0;
+                sh.ctrl[11] = from + 64;
             }
         }
         __syncthreads();
@@ -213,7 +282,6 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         if (ctl && n_new > 0) {
             float s = lane < n_new ? score_from_sums(sh.nb[0].ab[lane], sh.nb[0].xx[lane], q.qq, q.sqrt_qq, cosine) : 0.f;
             uint32_t addr = sh.nb[0].addr[lane];
-            st.evals += n_new;
             unsigned long long todo = __ballot(lane < n_new && s >= a.min_score);
             while (todo) {
                 int j = __ffsll((long long)todo) - 1;

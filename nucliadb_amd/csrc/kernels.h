@@ -152,6 +152,9 @@ struct SegDev {
 };
 
 // per-query counters written by the search kernel
+// EVALS / EXPANSIONS are what the reference's walk evaluates (equal to the oracle's).  closest_up_nodes lists the fresh neighbours of
+// an expansion and scores them only when a pop can depend on them (hnsw_search.hip): those rows are counted here at once but READ
+// only if the list is scored, so evals * row bytes overstates the bytes moved by that share (about a fifth at k = 10, ef = 30).
 #define NIDX_STAT_EVALS 0
 #define NIDX_STAT_EXPANSIONS 1
 #define NIDX_STAT_VISITED 2
