@@ -33,7 +33,8 @@ struct NbBuf {
 struct SearchShared {
     uint64_t pool[NIDX_POOL_CAP];  // unexpanded candidates (rank keys), unsorted
     NbBuf nb[2];                   // two expansions: the one being admitted and the one being evaluated (layer_search_block)
-    uint32_t eps[256];             // entry points for the next layer search; closest_up_nodes: the deferred neighbours
+    uint32_t eps[256];             // entry points of the top layer's search, then the parked edge records of a layer's entry
+                                   // points (layer_search_block); closest_up_nodes: the deferred neighbours
     int ctrl[12];                  // [0] continue, [1] n_new (single-buffer loops), [2] n_eps, [3] next row to evaluate,
                                    // [4] redo, [5] the speculated expansion exists, [6..7] n_new of nb[0], nb[1]
 };
@@ -350,15 +351,30 @@ __device__ inline uint32_t load_edge_word(const GraphDev &g, uint32_t node, int 
 }
 
 // ---- HnswSearcher::layer_search (search.rs:242-304) ------------------------------------------
-// Entry points: sh.eps[0..sh.ctrl[2]).  Result: `res` (wave 0), best first.  All threads call.
+// Result: `res` (wave 0), best first.  All threads call.  Entry points, by `ep_mode`:
+//   NIDX_EPS_BARE     sh.eps[0..sh.ctrl[2]): bare addresses, scored here and inserted one by one (the build kernels);
+//   NIDX_EPS_PARKED   the same, and the entry points' edge records are fetched in one go (below);
+//   NIDX_EPS_CARRIED  `res` as it stands (sh.ctrl[2] = its length): the result set of the layer above, whose scores are the ones
+//                     the entry evaluation would compute again; edge records fetched in one go as well.
+// Edge records in one go (wave 0): a layer search begins by expanding its entry points, and they are known when it starts.  Their
+// upper_base words are gathered in one round trip (one lane each) and their records at this layer in a second one, all together,
+// instead of two round trips in front of the rows of each; on layer 0 the records take one.  They are parked in sh.eps, idle from
+// the moment the entry addresses are consumed to the end of the layer search (NIDX_PARK_SLOTS = four records of 64 words on every
+// layer; entry points beyond that take the plain path), and prepare() looks a node up there first.  A parked record is a copy of read-only
+// memory: nothing about the walk changes.
+#define NIDX_PARK_SLOTS 4   // 64 words each in sh.eps
+#define NIDX_EPS_BARE 0
+#define NIDX_EPS_PARKED 1
+#define NIDX_EPS_CARRIED 2
 template <int NJ, int EFL, int EVR>
 __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, int layer, int k,
                                           const QueryRegs<NJ> &q, SearchShared &sh, uint32_t *vis, uint32_t vis_log2,
-                                          WaveTopK<EFL> &res, SearchCounters &st) {
+                                          WaveTopK<EFL> &res, SearchCounters &st, int ep_mode = NIDX_EPS_BARE) {
     const int lane = threadIdx.x & 63;
     const bool ctl = (nidx_tid() >> 6) == 0;
     const bool cosine = seg.similarity == 1;
     const uint32_t vis_cap = 1u << vis_log2;
+    const bool carried = ep_mode == NIDX_EPS_CARRIED;
     int pool_len = 0;
     uint32_t vis_count = 0;
 
@@ -370,18 +386,42 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
     if (n_new > k) k = n_new < 64 * EFL ? n_new : 64 * EFL;
     CandSet<EFL> cand;
     cand.init();
-    if (ctl) {
+    const int n_eps = carried ? 0 : n_new;
+    // parked records: ptag = the entry point of slot `lane` and pbase = its upper_base word (wave 0, until the records are
+    // requested); pt0..pt3 = whose record each slot holds, wave-uniform scalars (DESIGN.md 4.1 has what they cost in the capped shapes)
+    uint32_t ptag = 0xffffffffu, pbase = 0xffffffffu;
+    uint32_t pt0 = 0xffffffffu, pt1 = 0xffffffffu, pt2 = 0xffffffffu, pt3 = 0xffffffffu;
+    int n_park = 0;
+    if (ep_mode != NIDX_EPS_BARE && n_new <= 64) n_park = n_new < NIDX_PARK_SLOTS ? n_new : NIDX_PARK_SLOTS;
+    if (carried && ctl) {
+        // `res` as it stands IS the sorted list the serial inserts below would rebuild: the same rows, fma chain and butterfly give
+        // the same score bits, the addresses are distinct, rank_key() is a strict total order and the cap 64 * EFL evicts nothing.
+        // Only the bookkeeping is left: every member unexpanded and visited, and counted as evaluated (the reference does
+        // evaluate them: the counter keeps the reference's meaning).
+#pragma unroll
+        for (int i = 0; i < EFL; i++) {
+            const int left = res.len - 64 * i;
+            cand.unexp[i] = left >= 64 ? ~0ull : (left > 0 ? (1ull << left) - 1ull : 0ull);
+            if (lane < left) vis_insert(vis, vis_log2, rank_key_addr(res.mine(i)));
+        }
+        st.evals += n_new;
+        vis_count += n_new;
+        if (lane < n_park) ptag = rank_key_addr(res.mine(0));
+    }
+    if (ctl && !carried) {
         res.init();
         if (lane < n_new) {
             uint32_t ep = sh.eps[lane];
             vis_insert(vis, vis_log2, ep);
             sh.nb[0].addr[lane] = ep;
+            if (lane < n_park) ptag = ep;
         }
         // entry points beyond 64 (only the ef=100 build path) are handled in a second round below
     }
+    // requested beside the entry evaluation's rows
+    if (layer >= 1 && ptag != 0xffffffffu) pbase = g.upper_base[ptag];
     // entry points are admitted unconditionally (search.rs:256-261)
     int ep_done = 0;
-    const int n_eps = n_new;
     while (ep_done < n_eps) {
         int chunk = n_eps - ep_done < 64 ? n_eps - ep_done : 64;
         if (ctl && ep_done > 0 && lane < chunk) {
@@ -405,6 +445,26 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
         }
         ep_done += chunk;
     }
+    if (ctl && n_park > 0) {
+        // sh.eps is free from here on (n_new <= 64: wave 0 itself has read every entry address)
+        pt0 = lane_bcast_u32(ptag, 0);
+        pt1 = lane_bcast_u32(ptag, 1);
+        pt2 = lane_bcast_u32(ptag, 2);
+        pt3 = lane_bcast_u32(ptag, 3);
+        uint32_t w[NIDX_PARK_SLOTS];
+#pragma unroll
+        for (int r = 0; r < NIDX_PARK_SLOTS; r++) {
+            w[r] = 0;
+            if (r < n_park) {
+                const uint32_t node = lane_bcast_u32(ptag, r), b = lane_bcast_u32(pbase, r);
+                if (layer == 0) w[r] = g.l0[(size_t)node * NIDX_L0_STRIDE + lane];
+                else if (b != 0xffffffffu && lane < NIDX_UP_STRIDE) w[r] = g.upper[((size_t)b + (layer - 1)) * NIDX_UP_STRIDE + lane];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < NIDX_PARK_SLOTS; r++)
+            if (r < n_park) sh.eps[r * 64 + lane] = w[r];
+    }
 
     // ---- the expansion loop, software-pipelined ---------------------------------------------------------------------------
     // The reference's loop is: pop the best candidate c, stop if it is worse than the worst result, score c's unvisited
@@ -425,7 +485,12 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
         uint32_t deg;
         const uint32_t node = rank_key_addr(ck);
         uint32_t w;
-        if (node == tg0) {
+        const int slot = node == pt0 ? 0 : (node == pt1 ? 1 : (node == pt2 ? 2 : (node == pt3 ? 3 : -1)));
+        if (slot >= 0) {
+            w = sh.eps[slot * 64 + lane];
+            deg = lane_bcast_u32(w, 0);
+            edge_hits++;
+        } else if (node == tg0) {
             w = pw0;
             deg = lane_bcast_u32(w, 0);
             edge_hits++;

@@ -6,6 +6,9 @@
 // Bound: HBM (random 4*D-byte row gathers + 256-byte edge records).  Algorithmic bytes per query =
 // evals * 4*D + expansions * 256 (both counted by the kernel).
 // closest_up_nodes counts the rows of deferred evaluations without reading them (see there): bytes moved are below that figure.
+// Dependent round trips a walk's hits do not need are left out: a layer search below the top layer starts from the result set of
+// the layer above as it stands in registers, the edge records of a layer's entry points are fetched together (hnsw_device.h), and
+// a launch that returns no counters takes the hits from the sorted layer-0 set when closest_up_nodes would pop them in that order.
 #include "hnsw_device.h"
 
 namespace nidx {
@@ -64,19 +67,19 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     __syncthreads();
     const bool entry_mode = a.entry_vec != nullptr;
     const int efu = a.ef_upper ? (int)a.ef_upper : 1;
-    for (int layer = entry_mode ? 0 : (int)a.g.ep_layer; layer >= 1; layer--) {
-        layer_search_block<NJ, EFL, EVR>(a.seg, a.g, layer, efu, q, sh, vis, a.vis_log2, res, st);
-        if (ctl) {
-            uint64_t key = res.l[0].key;
-            if (lane < res.len) sh.eps[lane] = rank_key_addr(key);
-            if (lane == 0) sh.ctrl[2] = res.len;
-        }
-        __syncthreads();
+    // The top layer starts from the graph's entry point; every layer below starts from the result set of the layer above, which
+    // stays in `res` (NIDX_EPS_CARRIED): only its size is published, for the `n_new > k` rule and the deferral's test below.
+    // No barrier between two layers: the next one begins with vis_clear and a barrier, and nothing in between touches the words
+    // the other waves may still be reading (ctrl[0], ctrl[4]).
+    const int top = entry_mode ? 0 : (int)a.g.ep_layer;
+    for (int layer = top; layer >= 1; layer--) {
+        layer_search_block<NJ, EFL, EVR>(a.seg, a.g, layer, efu, q, sh, vis, a.vis_log2, res, st, layer == top ? NIDX_EPS_PARKED : NIDX_EPS_CARRIED);
+        if (ctl && lane == 0) sh.ctrl[2] = res.len;
     }
     // ---- layer 0 with ef = max(k, EF_SEARCH) (search.rs:333-349) ----
     const int efs = a.ef_search ? (int)a.ef_search : NIDX_EF_SEARCH;
     const int ef = k > efs ? k : efs;
-    if (!entry_mode) layer_search_block<NJ, EFL, EVR>(a.seg, a.g, 0, ef, q, sh, vis, a.vis_log2, res, st);
+    if (!entry_mode) layer_search_block<NJ, EFL, EVR>(a.seg, a.g, 0, ef, q, sh, vis, a.vis_log2, res, st, top >= 1 ? NIDX_EPS_CARRIED : NIDX_EPS_PARKED);
     if (a.dump_vec) {
         // spill path: the walk below runs in hnsw_closest_spill_kernel, from these candidates
         if (ctl) {
@@ -115,10 +118,94 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     // into the deferred stretch, so the pool after the pushes is, as a set of distinct keys, exactly the eager walk's.
     // Not deferred: entry mode (re-ranked candidates, not a layer-0 set), a search that raised a flag, a set with a NaN score
     // (first or last in the total order), more entry points than ef (the set then is larger than ef).
+    //
+    // The hits from the sorted set.  While expansions are deferred nothing is pushed before a pop fails to score strictly above ws
+    // (a list that fills up is scored early, but what it pushes scores <= ws), so the pops come off the pool in the rank order of
+    // `res`: the hits are the first k members, in order, that pass the acceptance tests below, provided k of them (or a member
+    // below min_score, where the walk ends too) are found before a member that does not score above ws.  Everything else the
+    // walk does in that stretch (the visited table, the pool, an arg-max per pop, the edge records) feeds only the counters.  A
+    // launch that asks for no counters therefore scans `res` first (wave 0 alone, the same tests in the same order; the other
+    // waves wait at one barrier for the verdict in sh.ctrl[1]) and walks only if the scan fails, or if the walk it replaces could
+    // have overflowed the visited table (<= NIDX_L0_STRIDE - 1 edges per record: `lane <= deg`), whose flag and re-run then decide.  With
+    // counters every launch walks, so they stay the reference's.  k >= ef never succeeds: the k-th member is the worst one.
     const uint32_t vis_cap = 1u << a.vis_log2;
-    vis_clear(vis, vis_cap);
-    __syncthreads();
-    int pool_len = 0, n_res = 0;
+    int n_res = 0;
+    if (a.stats == nullptr && !entry_mode) {
+        if (ctl) {
+            bool done = false;
+            if (res.len > 0 && st.flags == 0 && sh.ctrl[2] <= ef && ef + NIDX_DEFER_CAP <= NIDX_POOL_CAP) {
+                const float s0 = rank_key_score(res.at(0)), ws = res.worst_score();
+                if (s0 == s0 && ws == ws) {
+                    // paragraph and alive / filter bits of every member in one round trip instead of one per pop
+                    uint32_t mp[EFL], mok[EFL];
+#pragma unroll
+                    for (int i = 0; i < EFL; i++) {
+                        mp[i] = 0;
+                        mok[i] = 0;
+                        if (64 * i + lane < res.len) {
+                            const uint32_t c = rank_key_addr(res.mine(i));
+                            const uint32_t p = a.seg.para_of_vec ? a.seg.para_of_vec[c] : c;
+                            mp[i] = p;
+                            mok[i] = (!a.seg.alive || bit_test(a.seg.alive, p)) && (!filter || bit_test(filter, p));
+                        }
+                    }
+                    int expansions = 0;
+                    for (int r = 0; r < res.len; r++) {
+                        const uint64_t ck = res.at(r);
+                        const float cs = rank_key_score(ck);
+                        const uint32_t c = rank_key_addr(ck);
+                        if (!(cs > ws)) break;   // from here on a deferred neighbour may rank first: the walk decides
+                        if (cs < a.min_score) {
+                            done = true;
+                            break;
+                        }
+                        uint32_t p = lane_bcast_u32(mp[0], r & 63);
+                        bool accept = lane_bcast_u32(mok[0], r & 63) != 0;
+#pragma unroll
+                        for (int i = 1; i < EFL; i++)
+                            if ((r >> 6) == i) {
+                                p = lane_bcast_u32(mp[i], r & 63);
+                                accept = lane_bcast_u32(mok[i], r & 63) != 0;
+                            }
+                        if (accept && !a.with_duplicates) {
+                            for (int i = 0; i < n_res && accept; i++) {
+                                if (__builtin_bit_cast(uint32_t, res_score[i]) == __builtin_bit_cast(uint32_t, cs) &&
+                                    rows_equal<NJ>(a.seg, res_addr[i], c, lane))
+                                    accept = false;
+                            }
+                        }
+                        if (accept && a.multi) {
+                            for (int base = 0; base < n_res && accept; base += 64)
+                                if (__ballot(base + lane < n_res && res_para[base + lane] == p)) accept = false;
+                        }
+                        if (accept) {
+                            if (lane == 0) {
+                                res_addr[n_res] = c;
+                                res_score[n_res] = cs;
+                                res_para[n_res] = p;
+                            }
+                            n_res++;
+                        }
+                        if (n_res >= k) {
+                            done = true;
+                            break;
+                        }
+                        expansions++;   // the walk would expand this member
+                    }
+                    if (done && (uint32_t)ef + (uint32_t)(NIDX_L0_STRIDE - 1) * (uint32_t)expansions > vis_cap - vis_cap / 4) done = false;
+                }
+            }
+            if (!done) n_res = 0;
+            if (lane == 0) sh.ctrl[1] = done;
+        }
+        __syncthreads();
+    }
+    const bool from_set = a.stats == nullptr && !entry_mode && sh.ctrl[1] != 0;
+    if (!from_set) {
+        vis_clear(vis, vis_cap);
+        __syncthreads();
+    }
+    int pool_len = 0;
     uint32_t vis_count = 0;
     uint64_t dropped_best = NIDX_EMPTY_KEY;
     // wave 0's state of the deferral, kept in LDS (registers are what bounds the walks per CU): sh.ctrl[8] = the bits of ws,
@@ -143,7 +230,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
             sh.ctrl[9] = -1;
             sh.ctrl[10] = 0;
         }
-    } else if (ctl) {
+    } else if (ctl && !from_set) {
 #pragma unroll
         for (int i = 0; i < EFL; i++) {
             uint64_t key = res.mine(i);
@@ -167,7 +254,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
             sh.ctrl[10] = 0;
         }
     }
-    for (;;) {
+    while (!from_set) {
         if (ctl) {
             // cont: the walk goes on, once the n_new addresses in sh.eps[from ..) are scored and pushed, 64 per turn of this loop
             int cont = 1, n_new = 0, from = 0;
