@@ -40,7 +40,8 @@ extern "C" {
 #define NIDX_ERR_INEXACT (-9)                 /* a bounded on-chip pool overflowed: result would differ from the reference */
 #define NIDX_ERR_OUT_OF_MEMORY (-10)          /* a host allocation failed inside the library */
 #define NIDX_ERR_INTERNAL (-11)               /* any other C++ exception, caught at the boundary */
-#define NIDX_ERR_BUSY (-12)                   /* nidx_gpu_vector_search_submit: every pipeline slot holds an unwaited ticket */
+#define NIDX_ERR_BUSY (-12)                   /* nidx_gpu_vector_search_submit: every pipeline slot holds an unwaited ticket, or a
+                                               * nidx_gpu_vector_sync is pending; nidx_gpu_vector_sync: tickets outlived timeout_ms */
 
 /* Copies the calling thread's last error message (NUL terminated) and returns its length. */
 int32_t nidx_gpu_last_error(char *buf, size_t len);
@@ -52,7 +53,8 @@ int32_t nidx_gpu_last_error(char *buf, size_t len);
  * 6: nidx_gpu_build_features; nidx_gpu_vector_build_stats fills ten words (round 6). */
 #define NIDX_GPU_ABI_VERSION 6
 int32_t nidx_gpu_abi_version(void);
-/* Bits of optional content this build of the library holds.  No feature bit is currently defined: every build returns 0. */
+/* Bits of optional content this build of the library holds (NIDX_FEATURE_*). */
+#define NIDX_FEATURE_VECTOR_SYNC 1 /* nidx_gpu_vector_sync / nidx_gpu_vector_generation */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -223,6 +225,64 @@ int32_t nidx_gpu_vector_set_filter_keys(nidx_gpu_vector_index_t *index, uint32_t
 int32_t nidx_gpu_vector_lookup_filter_keys(nidx_gpu_vector_index_t *index, uint32_t segment, const uint8_t *query_bytes,
                                            const uint64_t *query_offsets, const uint8_t *query_is_prefix, uint32_t n_queries,
                                            uint32_t *out_first, uint32_t *out_last);
+
+/* ---- moving an open index to a new generation ------------------------------------------------------
+ * Replaces IndexCache::reload (nidx/src/searcher/index_cache.rs:180-241), which opens the index again for every indexed
+ * resource: there open only mmaps files, here it uploads every segment to HBM.  nidx_gpu_vector_sync instead moves the open
+ * index to the generation the metadata describes — segments kept where they lie, new ones uploaded, the others dropped and
+ * their HBM freed — with the semantics of VectorSearcher::open (nidx_vector/src/lib.rs:150-200) and
+ * OpenSegment::apply_deletions (segment.rs:428-445): a segment loses every paragraph filed under a field key that a
+ * deletion's FieldKey bytes are a byte prefix of, for each deletion with seq > the segment's seq.  For a kept segment that
+ * happens on top of the alive set it already has; deletions only ever remove, so repeating a call changes nothing.
+ *
+ *   entries               the new segment array, in search order (nidx_gpu_vector_open's order).  An old segment may be named
+ *                         once; old segments no entry names are dropped.
+ *   deletion_prefix_*     n_deletions byte strings ([offsets[i], offsets[i + 1]) of the bytes) in the caller's encoding of
+ *                         the key tables, as a query of nidx_gpu_vector_lookup_filter_keys with query_is_prefix != 0; the
+ *                         library does not parse field ids.  An empty prefix is NIDX_ERR_INVALID_ARGUMENT.
+ *   deletion_seqs         nidx_types::Seq of each deletion
+ *   timeout_ms            how long to wait for outstanding tickets and searches in progress (0: not at all)
+ *
+ * Everything is validated first (a keep that is out of range or repeated, a NULL segment where keep == -1, a deletion that
+ * applies to a segment with paragraphs but no key table: NIDX_ERR_INVALID_ARGUMENT, the message names the segment), and on
+ * ANY error — out of memory during an upload, a bad graph image, a timeout, a HIP error — the open index is exactly what it
+ * was: segments, alive sets, generation, space usage.  New alive bitsets are built in fresh buffers and swapped in at commit.
+ *
+ * Concurrency: uploads and the deletion kernel run while searches continue; only the commit is exclusive.  From the moment
+ * the sync starts to wait for exclusivity until it returns, ticket submits return NIDX_ERR_BUSY (back-pressure, as for a
+ * full pipeline) and blocking entries — nidx_gpu_vector_search*, _search_one* — wait; the sync itself waits until every
+ * outstanding ticket has been waited for (a ticket never outlives its generation) and every search in progress, coalesced
+ * batches included, has returned.  If that takes longer than timeout_ms the result is NIDX_ERR_BUSY and nothing has
+ * changed.  A thread must not call a blocking entry while it holds tickets that a pending sync waits for.  Work a caller
+ * has queued on streams of its own through nidx_gpu_vector_segment_search_device(_exact) is invisible to the library: the
+ * caller synchronises those streams before it syncs.  Per-segment arguments (filters, programs, segment numbers in hits)
+ * belong to a generation; nidx_gpu_vector_generation says which one the index is in (0 after open, + 1 per successful
+ * sync).  Graphs of added segments are built afterwards (nidx_gpu_vector_build_hnsw / _extend_hnsw), as after open. */
+typedef struct nidx_gpu_vector_sync_entry {
+    int32_t keep;                                /* >= 0: that segment of the open index, moved, nothing copied; -1: upload `segment` */
+    int64_t seq;                                 /* nidx_types::Seq of the segment */
+    const nidx_gpu_vector_segment_t *segment;    /* keep == -1: as for nidx_gpu_vector_open (alive_bitset = its starting alive set) */
+    const nidx_gpu_filter_index_t *filter_index; /* keep == -1: as nidx_gpu_vector_set_filter_index, NULL = none */
+    const uint8_t *key_bytes;                    /* keep == -1: as nidx_gpu_vector_set_filter_keys (key_offsets NULL = no key table) */
+    const uint64_t *key_offsets;
+    uint32_t n_keys;
+} nidx_gpu_vector_sync_entry_t;
+
+typedef struct nidx_gpu_vector_sync_stats {
+    uint64_t generation;         /* the generation the index is in now */
+    uint64_t bytes_uploaded;     /* host-to-device bytes of the call: new segments with their lists and keys, the deletion blob
+                                  * and its table; nothing of a kept segment */
+    uint64_t paragraphs_cleared; /* alive bits this call cleared */
+    uint64_t hbm_released;       /* bytes of the dropped segments */
+    uint32_t kept, added, dropped;
+    uint32_t deletions_applied;  /* deletions that reached at least one segment's seq */
+} nidx_gpu_vector_sync_stats_t;
+
+int32_t nidx_gpu_vector_sync(nidx_gpu_vector_index_t *index, const nidx_gpu_vector_sync_entry_t *entries, uint32_t n_entries,
+                             const uint8_t *deletion_prefix_bytes, const uint64_t *deletion_prefix_offsets,
+                             const int64_t *deletion_seqs, uint32_t n_deletions, uint32_t timeout_ms,
+                             nidx_gpu_vector_sync_stats_t *stats_out);
+int32_t nidx_gpu_vector_generation(const nidx_gpu_vector_index_t *index, uint64_t *generation_out);
 
 enum {
     NIDX_FILTER_PUSH_LISTS = 0, /* push the union of posting lists lists[a .. b) (an AtomClause) */

@@ -139,6 +139,21 @@ MERGE_ORDER_SCORE, MERGE_ORDER_VALUE_DESC, MERGE_ORDER_VALUE_ASC = 0, 1, 2
 SHARD_COMM_ID_BYTES = 128
 
 
+class VectorSyncEntryC(C.Structure):
+    """nidx_gpu_vector_sync_entry_t"""
+    _fields_ = [("keep", C.c_int32), ("seq", C.c_int64), ("segment", C.POINTER(VectorSegmentC)), ("filter_index", C.POINTER(FilterIndexC)),
+                ("key_bytes", C.c_void_p), ("key_offsets", C.c_void_p), ("n_keys", C.c_uint32)]
+
+
+class VectorSyncStatsC(C.Structure):
+    """nidx_gpu_vector_sync_stats_t"""
+    _fields_ = [("generation", C.c_uint64), ("bytes_uploaded", C.c_uint64), ("paragraphs_cleared", C.c_uint64), ("hbm_released", C.c_uint64),
+                ("kept", C.c_uint32), ("added", C.c_uint32), ("dropped", C.c_uint32), ("deletions_applied", C.c_uint32)]
+
+
+FEATURE_VECTOR_SYNC = 1   # nidx_gpu_build_features() bit: nidx_gpu_vector_sync / nidx_gpu_vector_generation
+
+
 class FilterOpC(C.Structure):
     _fields_ = [("op", C.c_int32), ("a", C.c_uint32), ("b", C.c_uint32)]
 
@@ -204,6 +219,9 @@ SIGNATURES = {
     "nidx_gpu_set_device": (C.c_int32, [C.c_int32]),
     "nidx_gpu_vector_open": (C.c_int32, [C.POINTER(VectorConfigC), C.POINTER(VectorSegmentC), C.c_uint32, C.POINTER(C.c_void_p)]),
     "nidx_gpu_vector_close": (None, [C.c_void_p]),
+    "nidx_gpu_vector_sync": (C.c_int32, [C.c_void_p, C.POINTER(VectorSyncEntryC), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                         C.c_uint32, C.POINTER(VectorSyncStatsC)]),
+    "nidx_gpu_vector_generation": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_set_tunable": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int32]),
     "nidx_gpu_vector_space_usage": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_num_segments": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -396,6 +396,7 @@ int32_t nidx_gpu_vector_search_one(nidx_gpu_vector_index_t *index, const float *
                     query_dimension);
     *out_count = 0;
     if (params->k == 0) return NIDX_OK;
+    GenShared gen(idx->gate);   // every member of a coalesced batch holds the generation until it has its hits: no batch outlives it
     return idx->search_one(query, *params, out_segment, out_paragraph, out_vector, out_score, out_count);
 } NIDX_ABI_CATCH
 
@@ -412,6 +413,7 @@ int32_t nidx_gpu_vector_search_one_filtered(nidx_gpu_vector_index_t *index, cons
     if (params->k == 0) return NIDX_OK;
     if (segment_programs && (params->method == NIDX_METHOD_BRUTE_FORCE_MFMA || params->method == NIDX_METHOD_BRUTE_FORCE_BF16))
         return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
+    GenShared gen(idx->gate);   // (the programs name posting lists of this generation's segments)
     // a malformed program fails this caller alone, before it joins a batch that other callers share
     const int32_t rc = idx->check_request_programs(segment_programs);
     if (rc != NIDX_OK) return rc;

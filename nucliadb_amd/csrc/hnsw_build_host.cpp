@@ -260,7 +260,9 @@ using namespace nidx;
 
 extern "C" int32_t nidx_gpu_vector_build_hnsw(nidx_gpu_vector_index_t *index, uint32_t segment, uint64_t level_seed) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     return idx->build_hnsw(segment, level_seed, false);
 } NIDX_ABI_CATCH
 
@@ -276,6 +278,8 @@ extern "C" int32_t nidx_gpu_vector_build_stats(nidx_gpu_vector_index_t *index, u
 
 extern "C" int32_t nidx_gpu_vector_extend_hnsw(nidx_gpu_vector_index_t *index, uint32_t segment, uint64_t level_seed) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     return idx->build_hnsw(segment, level_seed, true);
 } NIDX_ABI_CATCH

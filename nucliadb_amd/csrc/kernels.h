@@ -364,6 +364,19 @@ hipError_t launch_bitset_not(uint64_t *a, uint32_t n_words, uint32_t n_bits, hip
 // sorted key table -> [first, last) of the entries equal to / prefixed by each query (filter.hip)
 hipError_t launch_key_range(const uint8_t *tbl, const unsigned long long *tbl_off, uint32_t n_keys, const uint8_t *qb, const unsigned long long *q_off,
                             const uint8_t *q_prefix, uint32_t n_q, uint32_t *first, uint32_t *last, hipStream_t s);
+// ---- nidx_gpu_vector_sync: every (segment, deletion) pair of a new generation in one launch (vector_sync.hip) -------------------
+struct SyncSegDev {
+    const uint8_t *key_bytes;                  // the segment's sorted key table
+    const unsigned long long *key_offsets;     // [n_keys + 1]
+    const unsigned long long *list_offsets;    // [n_keys + 1] into ids: list j belongs to key j
+    const uint32_t *ids;                       // paragraph addresses
+    unsigned int *alive32;                     // the generation's fresh alive bitset, as 32-bit words
+    uint32_t n_keys, n_paragraphs;
+};
+// work item w in [work_first[s], work_first[s + 1]) = segment s x the (w - work_first[s])-th newest deletion; del_offsets index
+// del_bytes (prefixes sorted by seq, descending); cleared[s] += alive bits this launch cleared in segment s
+hipError_t launch_sync_deletions(const SyncSegDev *segs, uint32_t n_segs, const uint32_t *work_first, uint32_t n_work, const uint8_t *del_bytes,
+                                 const unsigned long long *del_offsets, uint32_t *cleared, hipStream_t s);
 hipError_t launch_bitset_and_count(const uint64_t *a, const uint64_t *alive, uint64_t *out, uint32_t n_words,
                                    unsigned long long *count, hipStream_t s);
 // Every filter program of a batch on one segment in two launches, whatever their number (F):

@@ -269,6 +269,15 @@ bool is_device_pointer(const void *p) {
 int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                      const uint64_t *const *segment_filters, bool blocking, uint64_t *ticket_out) {
     Pipeline &P = *pipe;
+    // the ticket's hold on the generation (released by pipeline_wait): a blocking caller is inside the gate already, a ticket submit is
+    // turned away while a sync is pending
+    if (blocking) gate.enter_nested();
+    else if (!gate.try_enter())
+        return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
+    struct GenHold {
+        GenGate *g;
+        ~GenHold() { if (g) g->leave(); }
+    } gen_hold{&gate};
     const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
     const size_t S = segs.size();
     if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
@@ -578,6 +587,7 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
     }
     *ticket_out = sl.ticket;
     release.slot = nullptr;   // the ticket owns the slot until it is waited for
+    gen_hold.g = nullptr;     // ... and its hold on the generation
     return NIDX_OK;
 }
 
@@ -596,6 +606,7 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
             }
         }
         if (db) {
+            struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};   // the ticket's hold (pipeline_submit_per_query)
             if (n_retried_out) *n_retried_out = 0;
             for (uint32_t q = 0; q < db->nq; q++) {
                 const size_t at = (size_t)q * db->k, c = db->cnt[q];
@@ -615,6 +626,7 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
         if (!slot || slot->waiting) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown ticket %llu (a ticket is waited for once)", (unsigned long long)ticket);
         slot->waiting = true;
     }
+    struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};   // the ticket's hold, after the slot is back (declared first)
     SlotRelease release{P, slot};
     SearchSlot &sl = *slot;
     const uint32_t nq = sl.nq, k = sl.params.k;
@@ -693,6 +705,11 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
                                                uint64_t *ticket_out) {
     Pipeline &P = *pipe;
     uint64_t ticket = 0;
+    if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
+    struct GenHold {
+        GenGate *g;
+        ~GenHold() { if (g) g->leave(); }
+    } gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
     {
         // these tickets count against pipeline_depth like the others: a caller that never waits meets NIDX_ERR_BUSY
         std::lock_guard<std::mutex> lk(P.mu);
@@ -716,6 +733,7 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     }
     P.done[ticket] = std::move(db);
     *ticket_out = ticket;
+    gen_hold.g = nullptr;
     return NIDX_OK;
 }
 

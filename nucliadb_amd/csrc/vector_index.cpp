@@ -284,6 +284,255 @@ static int32_t open_segment(const nidx_gpu_vector_config_t &cfg, const nidx_gpu_
     return NIDX_OK;
 }
 
+// ---- a segment's posting lists and their key table (nidx_gpu_vector_set_filter_index / _set_filter_keys, nidx_gpu_vector_sync) ----
+static int32_t upload_filter_index(VectorSegment &seg, const nidx_gpu_filter_index_t &lists) {
+    if (lists.n_lists && !lists.list_offsets) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL list_offsets");
+    const uint64_t n_ids = lists.n_lists ? lists.list_offsets[lists.n_lists] : 0;
+    if (n_ids && !lists.paragraph_ids) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL paragraph_ids");
+    for (uint64_t i = 0; i < n_ids; i++)
+        if (lists.paragraph_ids[i] >= seg.n_paragraphs) return fail(NIDX_ERR_INVALID_ARGUMENT, "posting %llu out of range", (unsigned long long)i);
+    NIDX_HIP(seg.f_offsets.alloc((size_t)(lists.n_lists + 1) * 8));
+    NIDX_HIP(seg.f_ids.alloc(std::max<size_t>(n_ids, 1) * 4));
+    if (lists.n_lists) NIDX_HIP(hipMemcpy(seg.f_offsets.p, lists.list_offsets, (size_t)(lists.n_lists + 1) * 8, hipMemcpyHostToDevice));
+    else NIDX_HIP(hipMemset(seg.f_offsets.p, 0, 8));
+    if (n_ids) NIDX_HIP(hipMemcpy(seg.f_ids.p, lists.paragraph_ids, n_ids * 4, hipMemcpyHostToDevice));
+    seg.f_n_lists = lists.n_lists;
+    seg.f_n_ids = n_ids;
+    return NIDX_OK;
+}
+
+static int32_t upload_filter_keys(VectorSegment &seg, const uint8_t *key_bytes, const uint64_t *key_offsets, uint32_t n_keys) {
+    if (n_keys && (!key_offsets || (key_offsets[n_keys] && !key_bytes))) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment/keys");
+    if (n_keys != seg.f_n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%u keys for %u posting lists", n_keys, seg.f_n_lists);
+    // sorted, strictly: the lookups are binary searches
+    for (uint32_t j = 1; j < n_keys; j++) {
+        const uint64_t la = key_offsets[j] - key_offsets[j - 1], lb = key_offsets[j + 1] - key_offsets[j];
+        const int c = memcmp(key_bytes + key_offsets[j - 1], key_bytes + key_offsets[j], (size_t)std::min(la, lb));
+        if (c > 0 || (c == 0 && la >= lb)) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter keys are not sorted (key %u)", j);
+    }
+    const uint64_t n_bytes = n_keys ? key_offsets[n_keys] : 0;
+    NIDX_HIP(seg.f_key_bytes.alloc(std::max<uint64_t>(n_bytes, 1)));
+    NIDX_HIP(seg.f_key_offsets.alloc((size_t)(n_keys + 1) * 8));
+    if (n_bytes) NIDX_HIP(hipMemcpy(seg.f_key_bytes.p, key_bytes, n_bytes, hipMemcpyHostToDevice));
+    if (n_keys) NIDX_HIP(hipMemcpy(seg.f_key_offsets.p, key_offsets, (size_t)(n_keys + 1) * 8, hipMemcpyHostToDevice));
+    else NIDX_HIP(hipMemset(seg.f_key_offsets.p, 0, 8));
+    seg.f_n_keys = n_keys;
+    return NIDX_OK;
+}
+
+// ---- nidx_gpu_vector_sync: the open index moves to a new generation ---------------------------------------------------------------
+void GenGate::enter() {
+    for (;;) {
+        // holders / pending is a store-buffering pattern (a reader publishes its hold, then reads `pending`; a sync publishes `pending`,
+        // then reads the holders): sequentially consistent on both sides, so one of the two always sees the other
+        holders.fetch_add(1, std::memory_order_seq_cst);
+        if (!pending.load(std::memory_order_seq_cst)) return;
+        leave();
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !pending.load(std::memory_order_seq_cst); });
+    }
+}
+bool GenGate::try_enter() {
+    holders.fetch_add(1, std::memory_order_seq_cst);
+    if (!pending.load(std::memory_order_seq_cst)) return true;
+    leave();
+    return false;
+}
+void GenGate::leave() {
+    if (holders.fetch_sub(1, std::memory_order_seq_cst) == 1 && pending.load(std::memory_order_seq_cst)) {
+        std::lock_guard<std::mutex> lk(mu);   // (the sync either has not looked at the holders yet or sleeps: it cannot miss this)
+        cv.notify_all();
+    }
+}
+bool GenGate::lock_exclusive(uint32_t timeout_ms) {
+    std::unique_lock<std::mutex> lk(mu);
+    pending.store(true, std::memory_order_seq_cst);
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(timeout_ms);
+    while (holders.load(std::memory_order_seq_cst) != 0) {
+        if (timeout_ms == 0 || cv.wait_until(lk, deadline) == std::cv_status::timeout) {
+            if (holders.load(std::memory_order_seq_cst) == 0) break;
+            pending.store(false, std::memory_order_seq_cst);
+            cv.notify_all();
+            return false;
+        }
+    }
+    return true;
+}
+void GenGate::unlock_exclusive() {
+    std::lock_guard<std::mutex> lk(mu);
+    pending.store(false, std::memory_order_seq_cst);
+    cv.notify_all();
+}
+
+int32_t VectorIndex::sync(const nidx_gpu_vector_sync_entry_t *entries, uint32_t n_entries, const uint8_t *del_bytes, const uint64_t *del_offsets,
+                          const int64_t *del_seqs, uint32_t n_deletions, uint32_t timeout_ms, nidx_gpu_vector_sync_stats_t *stats_out) {
+    std::lock_guard<std::mutex> one_sync(sync_mu);   // `segs` itself changes only below: its size and the segments' geometry are stable here
+    const uint32_t S_old = (uint32_t)segs.size();
+    // ---- validation: all of it before anything changes -------------------------------------------------------------------------
+    std::vector<int32_t> entry_of_old(S_old, -1);
+    uint32_t n_new = 0;
+    for (uint32_t e = 0; e < n_entries; e++) {
+        const nidx_gpu_vector_sync_entry_t &en = entries[e];
+        if (en.keep == -1) {
+            if (!en.segment) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: keep == -1 needs a segment", e);
+            n_new++;
+            continue;
+        }
+        if (en.keep < 0 || (uint32_t)en.keep >= S_old)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: keep = %d, the open index has %u segments", e, en.keep, S_old);
+        if (entry_of_old[en.keep] >= 0)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "entries %d and %u both keep segment %d", entry_of_old[en.keep], e, en.keep);
+        entry_of_old[en.keep] = (int32_t)e;
+    }
+    for (uint32_t i = 0; i < n_deletions; i++) {
+        if (del_offsets[i + 1] < del_offsets[i]) return fail(NIDX_ERR_INVALID_ARGUMENT, "deletion_prefix_offsets are not ascending (deletion %u)", i);
+        if (del_offsets[i + 1] == del_offsets[i]) return fail(NIDX_ERR_INVALID_ARGUMENT, "deletion %u has an empty prefix", i);
+    }
+    if (n_deletions && del_offsets[n_deletions] && !del_bytes) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL deletion_prefix_bytes");
+    // deletions newest first: segment s takes the first n_del[s] of them (SegmentDeletions::next, lib.rs:188-199)
+    std::vector<uint32_t> order(n_deletions);
+    for (uint32_t i = 0; i < n_deletions; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return del_seqs[a] > del_seqs[b]; });
+    std::vector<uint32_t> n_del(n_entries, 0);
+    uint32_t max_del = 0;
+    {
+        std::lock_guard<std::mutex> lock(mu);   // (the key tables of the open segments are set under it)
+        for (uint32_t e = 0; e < n_entries; e++) {
+            const nidx_gpu_vector_sync_entry_t &en = entries[e];
+            // deletions with seq > the segment's: a deletion of the segment's own seq does not apply (lib.rs:191)
+            n_del[e] = (uint32_t)(std::partition_point(order.begin(), order.end(), [&](uint32_t i) { return del_seqs[i] > en.seq; }) - order.begin());
+            const uint32_t paragraphs = en.keep >= 0 ? segs[en.keep].n_paragraphs : en.segment->n_paragraphs;
+            if (paragraphs == 0) n_del[e] = 0;
+            if (n_del[e] == 0) continue;
+            const bool has_keys = en.keep >= 0 ? segs[en.keep].f_key_offsets.p != nullptr : en.key_offsets != nullptr;
+            if (!has_keys)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u (%s %d): %u deletions apply to its %u paragraphs but it has no key table", e,
+                            en.keep >= 0 ? "segment" : "new segment, keep", en.keep, n_del[e], paragraphs);
+            max_del = std::max(max_del, n_del[e]);
+        }
+    }
+    NIDX_HIP(hipSetDevice(device));
+    if (!sync_stream) NIDX_HIP(hipStreamCreateWithFlags(&sync_stream, hipStreamNonBlocking));
+    uint64_t uploaded = 0;
+    // ---- new segments: uploaded while searches go on; nothing of the open index is touched -------------------------------------------
+    std::vector<VectorSegment> fresh(n_new);
+    std::vector<int32_t> fresh_of(n_entries, -1);
+    for (uint32_t e = 0, f = 0; e < n_entries; e++) {
+        const nidx_gpu_vector_sync_entry_t &en = entries[e];
+        if (en.keep >= 0) continue;
+        VectorSegment &seg = fresh[f];
+        fresh_of[e] = (int32_t)f++;
+        int32_t rc = open_segment(cfg, *en.segment, seg, sync_stream);
+        if (rc == NIDX_OK && en.filter_index) rc = upload_filter_index(seg, *en.filter_index);
+        if (rc == NIDX_OK && en.key_offsets) rc = upload_filter_keys(seg, en.key_bytes, en.key_offsets, en.n_keys);
+        if (rc != NIDX_OK) return rc;   // (`fresh` frees what was uploaded)
+        uploaded += seg.bytes() - seg.norm2.bytes + seg.para_first.bytes + seg.para_num.bytes + seg.key_ids_dev.bytes;
+    }
+    // ---- deletions: fresh alive bitsets (a copy of the old bits, or all ones), every (segment, deletion) pair in one launch ------------
+    std::vector<uint32_t> work;   // entries with deletions to apply
+    for (uint32_t e = 0; e < n_entries; e++)
+        if (n_del[e]) work.push_back(e);
+    const uint32_t W = (uint32_t)work.size();
+    std::vector<DevBuf> new_alive(W);
+    std::vector<std::vector<uint64_t>> new_alive_host(W);
+    std::vector<uint32_t> cleared(W, 0);
+    uint64_t total_cleared = 0;
+    if (W) {
+        uint64_t blob_bytes = 0;
+        for (uint32_t j = 0; j < max_del; j++) blob_bytes += del_offsets[order[j] + 1] - del_offsets[order[j]];
+        uint64_t n_work = 0;
+        for (uint32_t w = 0; w < W; w++) n_work += n_del[work[w]];
+        if (n_work > 0xFFFFFFFFull) return fail(NIDX_ERR_UNSUPPORTED, "%llu (segment, deletion) pairs in one sync", (unsigned long long)n_work);
+        // [SyncSegDev x W][del_offsets x (max_del + 1)][work_first x (W + 1)][cleared x W][prefix bytes]
+        const size_t tab_at = 0, off_at = tab_at + (size_t)W * sizeof(SyncSegDev), first_at = off_at + (size_t)(max_del + 1) * 8,
+                     cleared_at = first_at + (size_t)(W + 1) * 4, blob_at = cleared_at + (size_t)W * 4, total = blob_at + (size_t)blob_bytes;
+        NIDX_HIP(sync_pin.reserve(total));
+        NIDX_HIP(sync_dev.reserve(total));
+        unsigned char *h = sync_pin.as<unsigned char>(), *d = sync_dev.as<unsigned char>();
+        SyncSegDev *h_tab = reinterpret_cast<SyncSegDev *>(h + tab_at);
+        uint64_t *h_off = reinterpret_cast<uint64_t *>(h + off_at);
+        uint32_t *h_first = reinterpret_cast<uint32_t *>(h + first_at), *h_cleared = reinterpret_cast<uint32_t *>(h + cleared_at);
+        h_off[0] = 0;
+        for (uint32_t j = 0; j < max_del; j++) {
+            const uint64_t b = del_offsets[order[j]], len = del_offsets[order[j] + 1] - b;
+            memcpy(h + blob_at + h_off[j], del_bytes + b, (size_t)len);
+            h_off[j + 1] = h_off[j] + len;
+        }
+        h_first[0] = 0;
+        for (uint32_t w = 0; w < W; w++) {
+            const uint32_t e = work[w];
+            const VectorSegment &seg = entries[e].keep >= 0 ? segs[entries[e].keep] : fresh[fresh_of[e]];
+            const uint32_t words = (seg.n_paragraphs + 63) / 64;
+            NIDX_HIP(new_alive[w].alloc((size_t)words * 8));
+            if (seg.all_alive) NIDX_HIP(launch_bitset_fill(new_alive[w].as<uint64_t>(), words, seg.n_paragraphs, 1, sync_stream));
+            else NIDX_HIP(hipMemcpyAsync(new_alive[w].p, seg.alive.p, (size_t)words * 8, hipMemcpyDeviceToDevice, sync_stream));
+            h_tab[w] = SyncSegDev{seg.f_key_bytes.as<uint8_t>(), seg.f_key_offsets.as<unsigned long long>(), seg.f_offsets.as<unsigned long long>(),
+                                  seg.f_ids.as<uint32_t>(), new_alive[w].as<unsigned int>(), seg.f_n_keys, seg.n_paragraphs};
+            h_first[w + 1] = h_first[w] + n_del[e];
+            h_cleared[w] = 0;
+        }
+        NIDX_HIP(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, sync_stream));
+        uploaded += total;
+        NIDX_HIP(launch_sync_deletions(reinterpret_cast<const SyncSegDev *>(d + tab_at), W, reinterpret_cast<const uint32_t *>(d + first_at), (uint32_t)n_work,
+                                       d + blob_at, reinterpret_cast<const unsigned long long *>(d + off_at), reinterpret_cast<uint32_t *>(d + cleared_at),
+                                       sync_stream));
+        NIDX_HIP(hipMemcpyAsync(h_cleared, d + cleared_at, (size_t)W * 4, hipMemcpyDeviceToHost, sync_stream));
+        NIDX_HIP(hipStreamSynchronize(sync_stream));
+        // the alive words of the segments that lost paragraphs come back: host filters are counted against alive_host
+        for (uint32_t w = 0; w < W; w++) {
+            cleared[w] = h_cleared[w];
+            total_cleared += cleared[w];
+            if (!cleared[w]) continue;
+            new_alive_host[w].resize(new_alive[w].bytes / 8);
+            NIDX_HIP(hipMemcpyAsync(new_alive_host[w].data(), new_alive[w].p, new_alive[w].bytes, hipMemcpyDeviceToHost, sync_stream));
+        }
+        if (total_cleared) NIDX_HIP(hipStreamSynchronize(sync_stream));
+    }
+    std::vector<VectorSegment> next, dropped;
+    next.reserve(n_entries);
+    dropped.reserve(S_old);
+    // ---- commit: alone in the index, nothing below can fail ------------------------------------------------------------------------
+    if (!gate.lock_exclusive(timeout_ms))
+        return fail(NIDX_ERR_BUSY, "searches or unwaited tickets of generation %llu were still outstanding after %u ms",
+                    (unsigned long long)gate.generation.load(), timeout_ms);
+    uint64_t released = 0;
+    uint32_t n_dropped = 0;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        for (uint32_t e = 0; e < n_entries; e++)
+            next.emplace_back(std::move(entries[e].keep >= 0 ? segs[entries[e].keep] : fresh[fresh_of[e]]));
+        for (uint32_t w = 0; w < W; w++) {
+            if (!cleared[w]) continue;   // (an all-alive segment that lost nothing stays all alive; the fresh buffer goes)
+            VectorSegment &seg = next[work[w]];
+            std::swap(seg.alive, new_alive[w]);   // (the old bitset, if any, is freed with new_alive: after the commit)
+            seg.alive_host.swap(new_alive_host[w]);
+            seg.alive_count -= std::min<uint64_t>(seg.alive_count, cleared[w]);
+            seg.all_alive = false;
+        }
+        for (uint32_t s = 0; s < S_old; s++)
+            if (entry_of_old[s] < 0) {
+                released += segs[s].bytes();
+                n_dropped++;
+                dropped.emplace_back(std::move(segs[s]));
+            }
+        segs.swap(next);
+        scan_matching_hint = ~0ull;   // (keyed by segment number)
+    }
+    const uint64_t gen = gate.generation.fetch_add(1, std::memory_order_seq_cst) + 1;
+    gate.unlock_exclusive();
+    if (stats_out) {
+        stats_out->generation = gen;
+        stats_out->bytes_uploaded = uploaded;
+        stats_out->paragraphs_cleared = total_cleared;
+        stats_out->hbm_released = released;
+        stats_out->kept = n_entries - n_new;
+        stats_out->added = n_new;
+        stats_out->dropped = n_dropped;
+        stats_out->deletions_applied = max_del;
+    }
+    return NIDX_OK;   // (`dropped`, `next` — the moved-from shells — and the replaced bitsets are freed here, searches already running again)
+}
+
 // ---- exact fallback: closest_up_nodes with the pool and the visited set in HBM ---------------------------------------
 int32_t VectorIndex::segment_spill_search(uint32_t s, const float *d_queries, uint32_t nq, uint32_t k, float min_score, bool with_duplicates,
                                           int method, const uint64_t *d_filter, uint32_t *d_out_vec, float *d_out_score,
@@ -1603,7 +1852,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len) try {
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
-int32_t nidx_gpu_build_features(void) { return 0; }
+int32_t nidx_gpu_build_features(void) { return NIDX_FEATURE_VECTOR_SYNC; }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
     if (!count_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "count_out is NULL");
@@ -1665,6 +1914,23 @@ void nidx_gpu_vector_close(nidx_gpu_vector_index_t *index) {
     delete idx;
 }
 
+int32_t nidx_gpu_vector_sync(nidx_gpu_vector_index_t *index, const nidx_gpu_vector_sync_entry_t *entries, uint32_t n_entries,
+                             const uint8_t *deletion_prefix_bytes, const uint64_t *deletion_prefix_offsets,
+                             const int64_t *deletion_seqs, uint32_t n_deletions, uint32_t timeout_ms,
+                             nidx_gpu_vector_sync_stats_t *stats_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || (n_entries && !entries) || (n_deletions && (!deletion_prefix_offsets || !deletion_seqs)))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    return idx->sync(entries, n_entries, deletion_prefix_bytes, deletion_prefix_offsets, deletion_seqs, n_deletions, timeout_ms, stats_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_generation(const nidx_gpu_vector_index_t *index, uint64_t *generation_out) try {
+    const VectorIndex *idx = reinterpret_cast<const VectorIndex *>(index);
+    if (!idx || !generation_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *generation_out = idx->gate.generation.load(std::memory_order_seq_cst);
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !name) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1705,6 +1971,7 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
 int32_t nidx_gpu_vector_space_usage(const nidx_gpu_vector_index_t *index, uint64_t *bytes_out) try {
     const VectorIndex *idx = reinterpret_cast<const VectorIndex *>(index);
     if (!idx || !bytes_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     uint64_t b = 0;
     for (const VectorSegment &s : idx->segs) b += s.bytes();
     *bytes_out = b;
@@ -1714,27 +1981,34 @@ int32_t nidx_gpu_vector_space_usage(const nidx_gpu_vector_index_t *index, uint64
 int32_t nidx_gpu_vector_num_segments(const nidx_gpu_vector_index_t *index, uint32_t *n_out) try {
     const VectorIndex *idx = reinterpret_cast<const VectorIndex *>(index);
     if (!idx || !n_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     *n_out = (uint32_t)idx->segs.size();
     return NIDX_OK;
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, uint32_t segment, uint32_t *n_out) try {
     const VectorIndex *idx = reinterpret_cast<const VectorIndex *>(index);
-    if (!idx || !n_out || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    if (!idx || !n_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
     *n_out = idx->segs[segment].n_paragraphs;
     return NIDX_OK;
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_quantize(nidx_gpu_vector_index_t *index, uint32_t segment) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
     return idx->quantize(segment);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_serialize_quantized(nidx_gpu_vector_index_t *index, uint32_t segment, uint8_t *out, uint64_t out_cap,
                                             uint64_t *len_out) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size() || !len_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    if (!idx || !len_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad segment");
     std::lock_guard<std::mutex> lock(idx->mu);
     VectorSegment &seg = idx->segs[segment];
     if (!seg.has_quant) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u has no quantized store", segment);
@@ -1752,6 +2026,7 @@ int32_t nidx_gpu_vector_search(nidx_gpu_vector_index_t *index, const float *quer
                                uint32_t *out_count, int32_t *out_method) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !params || !out_count || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     if (idx->segs.size() > 1 && !out_method && !idx->serial_segments && n_queries && params->k && params->k <= NIDX_K_MAX && params->method >= 0 &&
         params->method <= 6) {
         // Searcher::_search over several segments (searcher.rs:270-287): every segment in one pass of the device and Fssc there too
@@ -1781,54 +2056,32 @@ int32_t nidx_gpu_vector_search_dim(nidx_gpu_vector_index_t *index, const float *
 
 int32_t nidx_gpu_vector_set_filter_index(nidx_gpu_vector_index_t *index, uint32_t segment, const nidx_gpu_filter_index_t *lists) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || !lists || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
-    if (lists->n_lists && !lists->list_offsets) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL list_offsets");
+    if (!idx || !lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     std::lock_guard<std::mutex> lock(idx->mu);
     NIDX_HIP(hipSetDevice(idx->device));
-    VectorSegment &seg = idx->segs[segment];
-    const uint64_t n_ids = lists->n_lists ? lists->list_offsets[lists->n_lists] : 0;
-    if (n_ids && !lists->paragraph_ids) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL paragraph_ids");
-    for (uint64_t i = 0; i < n_ids; i++)
-        if (lists->paragraph_ids[i] >= seg.n_paragraphs) return fail(NIDX_ERR_INVALID_ARGUMENT, "posting %llu out of range", (unsigned long long)i);
-    NIDX_HIP(seg.f_offsets.alloc((size_t)(lists->n_lists + 1) * 8));
-    NIDX_HIP(seg.f_ids.alloc(std::max<size_t>(n_ids, 1) * 4));
-    if (lists->n_lists) NIDX_HIP(hipMemcpy(seg.f_offsets.p, lists->list_offsets, (size_t)(lists->n_lists + 1) * 8, hipMemcpyHostToDevice));
-    if (n_ids) NIDX_HIP(hipMemcpy(seg.f_ids.p, lists->paragraph_ids, n_ids * 4, hipMemcpyHostToDevice));
-    seg.f_n_lists = lists->n_lists;
-    seg.f_n_ids = n_ids;
-    return NIDX_OK;
+    return upload_filter_index(idx->segs[segment], *lists);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_set_filter_keys(nidx_gpu_vector_index_t *index, uint32_t segment, const uint8_t *key_bytes, const uint64_t *key_offsets,
                                         uint32_t n_keys) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size() || (n_keys && (!key_offsets || (key_offsets[n_keys] && !key_bytes))))
-        return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment/keys");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment/keys");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment/keys");
     std::lock_guard<std::mutex> lock(idx->mu);
     NIDX_HIP(hipSetDevice(idx->device));
-    VectorSegment &seg = idx->segs[segment];
-    if (n_keys != seg.f_n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%u keys for %u posting lists", n_keys, seg.f_n_lists);
-    // sorted, strictly: the lookups are binary searches
-    for (uint32_t j = 1; j < n_keys; j++) {
-        const uint64_t la = key_offsets[j] - key_offsets[j - 1], lb = key_offsets[j + 1] - key_offsets[j];
-        const int c = memcmp(key_bytes + key_offsets[j - 1], key_bytes + key_offsets[j], (size_t)std::min(la, lb));
-        if (c > 0 || (c == 0 && la >= lb)) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter keys are not sorted (key %u)", j);
-    }
-    const uint64_t n_bytes = n_keys ? key_offsets[n_keys] : 0;
-    NIDX_HIP(seg.f_key_bytes.alloc(std::max<uint64_t>(n_bytes, 1)));
-    NIDX_HIP(seg.f_key_offsets.alloc((size_t)(n_keys + 1) * 8));
-    if (n_bytes) NIDX_HIP(hipMemcpy(seg.f_key_bytes.p, key_bytes, n_bytes, hipMemcpyHostToDevice));
-    if (n_keys) NIDX_HIP(hipMemcpy(seg.f_key_offsets.p, key_offsets, (size_t)(n_keys + 1) * 8, hipMemcpyHostToDevice));
-    else NIDX_HIP(hipMemset(seg.f_key_offsets.p, 0, 8));
-    seg.f_n_keys = n_keys;
-    return NIDX_OK;
+    return upload_filter_keys(idx->segs[segment], key_bytes, key_offsets, n_keys);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_lookup_filter_keys(nidx_gpu_vector_index_t *index, uint32_t segment, const uint8_t *query_bytes,
                                            const uint64_t *query_offsets, const uint8_t *query_is_prefix, uint32_t n_queries,
                                            uint32_t *out_first, uint32_t *out_last) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     if (n_queries == 0) return NIDX_OK;
     if (!query_offsets || !query_is_prefix || !out_first || !out_last || (query_offsets[n_queries] && !query_bytes))
         return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1863,6 +2116,7 @@ int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const floa
                                       uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !params || !out_count || !qoff || (nq && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     const uint32_t k = params->k, d = idx->cfg.dimension;
     for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
     if (nq == 0 || k == 0) return NIDX_OK;
@@ -1963,6 +2217,7 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
                                         int32_t *out_method, uint64_t *out_matching) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !params || !out_count || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     if (query_dimension != idx->cfg.dimension)
         return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension,
                     query_dimension);
@@ -1977,6 +2232,7 @@ int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index
                                                   uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !params || !out_count || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
     if (query_dimension != idx->cfg.dimension)
         return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension,
                     query_dimension);
@@ -2010,7 +2266,9 @@ int32_t nidx_gpu_vector_segment_search_device(nidx_gpu_vector_index_t *index, ui
                                               const uint64_t *d_filter, uint32_t *d_out_vector, float *d_out_score,
                                               uint32_t *d_out_count, uint32_t *d_stats, void *stream) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || !params || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx || !params) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);   // for the launch calls; what they queue on the caller's stream is the caller's to synchronise before a sync
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     std::lock_guard<std::mutex> lock(idx->mu);
     int method = 0;
     int32_t rc = device_entry_method(idx, segment, params, d_filter, method);
@@ -2037,7 +2295,9 @@ int32_t nidx_gpu_vector_segment_search_device_exact(nidx_gpu_vector_index_t *ind
                                                     const uint64_t *d_filter, uint32_t *d_out_block, uint32_t *host_out_block,
                                                     void *stream, uint32_t *n_retried_out) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
-    if (!idx || !params || segment >= idx->segs.size() || !d_out_block) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx || !params || !d_out_block) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     if (n_queries == 0) return NIDX_OK;
     std::lock_guard<std::mutex> lock(idx->mu);
     int method = 0;
@@ -2087,7 +2347,9 @@ int32_t nidx_gpu_vector_serialize_hnsw(const nidx_gpu_vector_index_t *index, uin
                                        uint64_t graph_cap, uint64_t *graph_len_out, float *edges_out, uint64_t edges_cap,
                                        uint64_t *n_edges_out) try {
     const VectorIndex *idx = reinterpret_cast<const VectorIndex *>(index);
-    if (!idx || segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    GenShared gen(idx->gate);
+    if (segment >= idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
     const VectorSegment &seg = idx->segs[segment];
     if (!seg.has_graph) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment has no HNSW graph");
     HostGraph hg;

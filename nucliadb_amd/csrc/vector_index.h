@@ -1,5 +1,7 @@
 // vector_index.h — the opaque nidx_gpu_vector_index_t (one process-local, device-resident Searcher).
 #pragma once
+#include <atomic>
+#include <condition_variable>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -59,6 +61,30 @@ struct VectorSegment {
     uint64_t bytes() const;
 };
 
+// The generation gate (nidx_gpu_vector_sync).  Whoever reads `segs` holds it shared: a blocking entry point for the length of the
+// call, a ticket from its submit until it has been waited for (pipeline_wait reads `segs`, so a ticket may not outlive its
+// generation).  The commit of a sync holds it alone.  Entering costs two atomic operations while no sync is pending — the mutex is
+// touched only to sleep or to wake a sleeper.
+struct GenGate {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::atomic<uint32_t> holders{0};
+    std::atomic<bool> pending{false};        // a sync waits for, or holds, exclusivity
+    std::atomic<uint64_t> generation{0};     // + 1 per successful sync
+    void enter();                            // blocking entries: waits at the gate while a sync is pending
+    bool try_enter();                        // ticket submits: false while a sync is pending (NIDX_ERR_BUSY)
+    void enter_nested() { holders.fetch_add(1, std::memory_order_seq_cst); }   // the caller already holds it (a ticket taken inside a blocking entry)
+    void leave();
+    bool lock_exclusive(uint32_t timeout_ms);   // false: holders remained after timeout_ms, nothing is locked
+    void unlock_exclusive();
+};
+struct GenShared {   // a blocking entry point's hold
+    GenGate &g;
+    explicit GenShared(GenGate &gate) : g(gate) { g.enter(); }
+    GenShared(const GenShared &) = delete;
+    ~GenShared() { g.leave(); }
+};
+
 struct Coalescer;
 std::shared_ptr<Coalescer> make_coalescer();
 struct Pipeline;
@@ -77,11 +103,23 @@ struct VectorIndex {
             (void)hipStreamSynchronize(stream);
             (void)hipStreamDestroy(stream);
         }
+        if (sync_stream) {
+            (void)hipStreamSynchronize(sync_stream);
+            (void)hipStreamDestroy(sync_stream);
+        }
         if (scratch_event) (void)hipEventDestroy(scratch_event);
         pipe.reset();   // synchronises and destroys the slot streams before the segments they read go away
     }
     std::mutex mu;
     std::vector<VectorSegment> segs;
+    // nidx_gpu_vector_sync: `segs` is replaced only by a sync's commit, under `gate` held alone AND `mu`
+    mutable GenGate gate;
+    std::mutex sync_mu;                 // one sync at a time, uploads included
+    hipStream_t sync_stream = nullptr;  // uploads and the deletion kernel of a sync (created by the first one)
+    DevBuf sync_dev;                    // the deletion launch's table, blob and counters (grow-only, under sync_mu)
+    PinBuf sync_pin;
+    int32_t sync(const nidx_gpu_vector_sync_entry_t *entries, uint32_t n_entries, const uint8_t *del_bytes, const uint64_t *del_offsets,
+                 const int64_t *del_seqs, uint32_t n_deletions, uint32_t timeout_ms, nidx_gpu_vector_sync_stats_t *stats_out);
     // tunables
     int waves_per_query = 4;
     int eval_rows = 4;   // rows in flight per wave (HNSW distance phase); tuned on MI355X (profiles/r02_tune_hnsw.txt: 4 rows fit the 128-VGPR budget since the pipelined loop)

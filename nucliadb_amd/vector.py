@@ -184,6 +184,50 @@ def _field_key(key: str) -> Optional[str]:
     return f"{rid}/{parts[1]}/{parts[2]}"
 
 
+def deletion_key_prefix(key: str) -> Optional[str]:
+    """FieldKey::from_field_id (utils.rs:84-115) of a deletion key, in the text form of _field_key: `uuidhex` for a resource (every
+    field key of the resource starts with it: the hex form has a fixed length), `uuidhex/type/name` for a field; None for a key
+    the reference rejects (no uuid, or a type without a name).  A deletion removes the paragraphs whose field key STARTS WITH it."""
+    parts = key.split("/")
+    try:
+        rid = _uuid.UUID(parts[0]).hex
+    except ValueError:
+        return None
+    if len(parts) == 1:
+        return rid
+    if len(parts) >= 3:
+        return f"{rid}/{parts[1]}/{parts[2]}"
+    return None
+
+
+def deletion_prefix_bytes(key: str) -> Optional[bytes]:
+    """The same prefix as a query of the segments' key tables (VectorSegment.list_keys: field keys are filed under "F:")."""
+    prefix = deletion_key_prefix(key)
+    return None if prefix is None else ("F:" + prefix).encode("utf-8")
+
+
+def deletions_per_segment(segment_seqs: Sequence[int], deletion_seqs: Sequence[int]) -> Tuple[List[int], List[int]]:
+    """nidx_gpu_vector_sync's assignment: (order, n_del) — the deletions' indices by seq, newest first, and for every segment how
+    many of them, from the front, apply to it: those with seq > the segment's (SegmentDeletions::next, lib.rs:188-199)."""
+    order = sorted(range(len(deletion_seqs)), key=lambda i: -deletion_seqs[i])
+    n_del = [sum(1 for i in order if deletion_seqs[i] > seq) for seq in segment_seqs]
+    return order, n_del
+
+
+@dataclass
+class VectorSyncStats:
+    """nidx_gpu_vector_sync_stats_t"""
+
+    generation: int
+    bytes_uploaded: int
+    paragraphs_cleared: int
+    hbm_released: int
+    kept: int
+    added: int
+    dropped: int
+    deletions_applied: int
+
+
 class VectorSegment:
     """An in-memory vector segment: what segment::create writes to disk (segment.rs:199-239) minus
     the files.  `graph` is an hnsw.graph image (DiskHnswV2) or None."""
@@ -326,18 +370,10 @@ class VectorSegment:
         """apply_deletions' lookup (segment.rs:428-445): a resource uuid or `uuid/type/name`, as
         field_index.get_prefix(FieldKey::from_field_id(key)) (inverted_index/paragraph.rs:118-120) — a BYTE prefix of the
         indexed `uuid type/name` keys, so deleting `uuid/t/title` also reaches a field named `title2` of that resource."""
-        parts = key.split("/")
-        try:
-            rid = _uuid.UUID(parts[0]).hex
-        except ValueError:
+        prefix = deletion_key_prefix(key)
+        if prefix is None:
             return []
-        if len(parts) == 1:
-            prefix = rid + "/"
-        elif len(parts) >= 3:
-            prefix = f"{rid}/{parts[1]}/{parts[2]}"
-        else:
-            return []
-        return [i for i, fk in enumerate(self._field_keys) if fk is not None and (fk + "/").startswith(prefix)]
+        return [i for i, fk in enumerate(self._field_keys) if fk is not None and fk.startswith(prefix)]
 
     # ---- segment directories (data_store/v2, hnsw/disk/v2) ----------------------------------------------------------
     def save(self, path: str, dimension: Optional[int] = None) -> None:
@@ -704,7 +740,9 @@ class VectorSearcher:
     def __init__(self):
         self._handle = C.c_void_p()
         self._segments: List[VectorSegment] = []
-        self._keep = []  # buffers referenced by the C structs during open
+        self._keep = []  # buffers referenced by the C structs during open / sync
+        self._key_table: dict = {}   # paragraph key -> the 64-bit identity Fssc compares (interned for the life of the searcher)
+        self._has_keys: List[bool] = []   # per segment: its posting lists and key table are in HBM
         self.config: Optional[VectorConfig] = None
         self.last_methods: List[int] = []
 
@@ -718,31 +756,8 @@ class VectorSearcher:
         ordered = _segments_with_deletions(segments, deletions)
         # open_segments pushes in that (newest first) order and _search walks them in it
         c_segs = (_lib.VectorSegmentC * max(1, len(ordered)))()
-        key_table: dict = {}  # Fssc equates hits by paragraph id string (searcher.rs:67-96): intern the keys
         for i, (seg, alive) in enumerate(ordered):
-            if seg.vectors.shape[1] != config.dimension and seg.records:
-                raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS,
-                                   f"Inconsistent dimensions. Index={config.dimension} Vector={seg.vectors.shape[1]}")
-            bits = _bitset(alive)
-            graph = np.frombuffer(seg.graph, dtype=np.uint8) if seg.graph else None
-            key_ids = np.array([key_table.setdefault(k, len(key_table)) for k in seg.keys], dtype=np.uint64)
-            self._keep += [bits, graph, seg.vectors, key_ids]
-            c_segs[i].vectors = seg.vectors.ctypes.data
-            c_segs[i].row_stride_bytes = config.dimension * 4
-            c_segs[i].n_vectors = seg.vectors.shape[0]
-            c_segs[i].paragraph_of_vector = None if seg.para_of_vec is None else seg.para_of_vec.ctypes.data
-            c_segs[i].n_paragraphs = seg.records
-            c_segs[i].hnsw_graph = graph.ctypes.data if graph is not None else None
-            c_segs[i].hnsw_graph_len = len(seg.graph) if seg.graph else 0
-            c_segs[i].hnsw_graph_nodes = seg.graph_nodes if seg.graph else 0
-            has_edges = seg.graph is not None and seg.graph_edges is not None and len(seg.graph_edges)
-            c_segs[i].hnsw_edges = seg.graph_edges.ctypes.data if has_edges else None
-            c_segs[i].n_hnsw_edges = len(seg.graph_edges) if has_edges else 0
-            c_segs[i].alive_bitset = bits.ctypes.data
-            c_segs[i].paragraph_key_ids = key_ids.ctypes.data if seg.records else None
-            if seg.quantized is not None and seg.records:
-                c_segs[i].quantized = seg.quantized.ctypes.data
-                c_segs[i].quantized_len = seg.quantized.size
+            self._fill_segment_c(c_segs[i], seg, alive)
             self._segments.append(seg)
         cfg = config.to_c()
         _lib.check(_lib.lib().nidx_gpu_vector_open(C.byref(cfg), c_segs, len(ordered), C.byref(self._handle)))
@@ -754,17 +769,109 @@ class VectorSearcher:
                     self.quantize(i)
         for i, seg in enumerate(self._segments):
             if len(seg.list_keys):
-                fi = _lib.FilterIndexC(len(seg.list_keys), seg.list_offsets.ctypes.data, seg.list_ids.ctypes.data if len(seg.list_ids) else None)
+                fi, blob, offs, n_keys = self._filter_tables(seg)
                 _lib.check(_lib.lib().nidx_gpu_vector_set_filter_index(self._handle, i, C.byref(fi)))
                 # the lists' keys as a sorted table in HBM: label-prefix and field-key lookups of a request run on the device
-                enc = [k.encode("utf-8") for k in seg.list_keys]
-                assert enc == sorted(enc)
-                offs = np.zeros(len(enc) + 1, np.uint64)
-                offs[1:] = np.cumsum([len(e) for e in enc])
-                blob = np.frombuffer(b"".join(enc) + b"\0", np.uint8)
-                _lib.check(_lib.lib().nidx_gpu_vector_set_filter_keys(self._handle, i, blob.ctypes.data, offs.ctypes.data, len(enc)))
+                _lib.check(_lib.lib().nidx_gpu_vector_set_filter_keys(self._handle, i, blob.ctypes.data, offs.ctypes.data, n_keys))
+            self._has_keys.append(bool(len(seg.list_keys)))
         self._keep = []  # everything was copied to HBM / host vectors by open
         return self
+
+    def _fill_segment_c(self, c_seg, seg: VectorSegment, alive: np.ndarray) -> None:
+        """One nidx_gpu_vector_segment_t over the segment's host arrays (kept alive in self._keep until the call has copied them)."""
+        config = self.config
+        if seg.vectors.shape[1] != config.dimension and seg.records:
+            raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS,
+                               f"Inconsistent dimensions. Index={config.dimension} Vector={seg.vectors.shape[1]}")
+        bits = _bitset(alive)
+        graph = np.frombuffer(seg.graph, dtype=np.uint8) if seg.graph else None
+        # Fssc equates hits by paragraph id string (searcher.rs:67-96): the keys are interned, across generations too
+        key_ids = np.array([self._key_table.setdefault(k, len(self._key_table)) for k in seg.keys], dtype=np.uint64)
+        self._keep += [bits, graph, seg.vectors, key_ids]
+        c_seg.vectors = seg.vectors.ctypes.data
+        c_seg.row_stride_bytes = config.dimension * 4
+        c_seg.n_vectors = seg.vectors.shape[0]
+        c_seg.paragraph_of_vector = None if seg.para_of_vec is None else seg.para_of_vec.ctypes.data
+        c_seg.n_paragraphs = seg.records
+        c_seg.hnsw_graph = graph.ctypes.data if graph is not None else None
+        c_seg.hnsw_graph_len = len(seg.graph) if seg.graph else 0
+        c_seg.hnsw_graph_nodes = seg.graph_nodes if seg.graph else 0
+        has_edges = seg.graph is not None and seg.graph_edges is not None and len(seg.graph_edges)
+        c_seg.hnsw_edges = seg.graph_edges.ctypes.data if has_edges else None
+        c_seg.n_hnsw_edges = len(seg.graph_edges) if has_edges else 0
+        c_seg.alive_bitset = bits.ctypes.data
+        c_seg.paragraph_key_ids = key_ids.ctypes.data if seg.records else None
+        if seg.quantized is not None and seg.records:
+            c_seg.quantized = seg.quantized.ctypes.data
+            c_seg.quantized_len = seg.quantized.size
+
+    @staticmethod
+    def _filter_tables(seg: VectorSegment):
+        """(nidx_gpu_filter_index_t, key bytes, key offsets, n_keys) of a segment's posting lists, keys sorted bytewise."""
+        fi = _lib.FilterIndexC(len(seg.list_keys), seg.list_offsets.ctypes.data, seg.list_ids.ctypes.data if len(seg.list_ids) else None)
+        enc = [k.encode("utf-8") for k in seg.list_keys]
+        assert enc == sorted(enc)
+        offs = np.zeros(len(enc) + 1, np.uint64)
+        offs[1:] = np.cumsum([len(e) for e in enc])
+        blob = np.frombuffer(b"".join(enc) + b"\0", np.uint8)
+        return fi, blob, offs, len(enc)
+
+    def sync(self, segments: Sequence[Tuple[VectorSegment, int]], deletions: Sequence[Tuple[str, int]] = (),
+             timeout_ms: int = 10000, quantize: bool = True) -> VectorSyncStats:
+        """IndexCache::reload (searcher/index_cache.rs:180-241) without opening again: the open index moves to the generation
+        (segments, deletions) — the arguments of open().  Segments that are open already (the same objects) stay where they lie in
+        HBM, new ones are uploaded, the others dropped; every segment loses the paragraphs of the deletions with seq > its own, on
+        top of what it has lost already (nidx_gpu_vector_sync).  On an error nothing has changed."""
+        L = _lib.lib()
+        ordered = list(reversed(sorted(segments, key=lambda t: t[1])))   # newest first, as open() orders them
+        old_index = {id(seg): i for i, seg in enumerate(self._segments)}
+        dels = [(deletion_prefix_bytes(key), seq) for key, seq in deletions]
+        dels = [(p, seq) for p, seq in dels if p is not None]   # keys FieldKey::from_field_id rejects delete nothing (segment.rs:433-436)
+        entries = (_lib.VectorSyncEntryC * max(1, len(ordered)))()
+        c_new = (_lib.VectorSegmentC * max(1, len(ordered)))()
+        self._keep = []
+        try:
+            for e, (seg, seq) in enumerate(ordered):
+                entries[e].seq = int(seq)
+                i = old_index.get(id(seg), -1)
+                entries[e].keep = i
+                if i >= 0:
+                    if not self._has_keys[i] and dels:
+                        # a deletion needs a key table to look its prefix up in, were it an empty one
+                        fi, blob, offs, n_keys = self._filter_tables(seg)
+                        _lib.check(L.nidx_gpu_vector_set_filter_index(self._handle, i, C.byref(fi)))
+                        _lib.check(L.nidx_gpu_vector_set_filter_keys(self._handle, i, blob.ctypes.data, offs.ctypes.data, n_keys))
+                        self._has_keys[i] = True
+                    continue
+                self._fill_segment_c(c_new[e], seg, np.ones(seg.records, dtype=bool))
+                fi, blob, offs, n_keys = self._filter_tables(seg)
+                self._keep += [fi, blob, offs]
+                entries[e].segment = C.pointer(c_new[e])
+                entries[e].filter_index = C.pointer(fi)
+                entries[e].key_bytes, entries[e].key_offsets, entries[e].n_keys = blob.ctypes.data, offs.ctypes.data, n_keys
+            blob = np.frombuffer(b"".join(p for p, _ in dels) + b"\0", np.uint8)
+            offs = np.zeros(len(dels) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(p) for p, _ in dels])
+            seqs = np.array([seq for _, seq in dels], dtype=np.int64)
+            st = _lib.VectorSyncStatsC()
+            _lib.check(L.nidx_gpu_vector_sync(self._handle, entries, len(ordered), blob.ctypes.data, offs.ctypes.data,
+                                              seqs.ctypes.data if len(dels) else None, len(dels), int(timeout_ms), C.byref(st)))
+        finally:
+            self._keep = []
+        self._has_keys = [True if old_index.get(id(seg), -1) < 0 else self._has_keys[old_index[id(seg)]] for seg, _ in ordered]
+        self._segments = [seg for seg, _ in ordered]
+        if quantize and self.config.quantizable_vectors():   # as open() does for segments that arrive without their codes
+            for i, seg in enumerate(self._segments):
+                if id(seg) not in old_index and seg.quantized is None and seg.records:
+                    self.quantize(i)
+        return VectorSyncStats(st.generation, st.bytes_uploaded, st.paragraphs_cleared, st.hbm_released, st.kept, st.added, st.dropped,
+                               st.deletions_applied)
+
+    def generation(self) -> int:
+        """Generations since open: 0, + 1 per successful sync.  Per-segment arguments and the segment numbers in hits belong to one."""
+        out = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_vector_generation(self._handle, C.byref(out)))
+        return out.value
 
     def close(self):
         if self._handle:
