@@ -55,6 +55,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len);
 int32_t nidx_gpu_abi_version(void);
 /* Bits of optional content this build of the library holds (NIDX_FEATURE_*). */
 #define NIDX_FEATURE_VECTOR_SYNC 1 /* nidx_gpu_vector_sync / nidx_gpu_vector_generation */
+#define NIDX_FEATURE_BM25_SYNC 2 /* nidx_gpu_bm25_sync / nidx_gpu_bm25_generation */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -837,6 +838,77 @@ int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
  * n_alive_out: NULL or the segment's live documents afterwards. */
 int32_t nidx_gpu_bm25_apply_deletions(nidx_gpu_bm25_index_t *index, uint32_t segment, const uint32_t *terms, uint32_t n_terms,
                                       uint64_t *n_alive_out);
+
+/* ---- moving an open BM25 index to a new generation --------------------------------------------------
+ * Replaces IndexCache::reload (nidx/src/searcher/index_cache.rs:180-241), which reopens the text and paragraph indexes for
+ * every generation (open_index_with_deletions, nidx_tantivy/src/index_reader.rs:39-74): there open only mmaps files, here it
+ * uploads every posting and lays the segments out as one term-major list per term.  nidx_gpu_bm25_sync instead moves the open
+ * index to the generation the metadata describes on the device: a term's resident list is the concatenation of its per-segment
+ * runs over doc + base[segment], so a dropped segment's runs are left out, a kept segment's runs are copied with their doc ids
+ * shifted by a constant, and a new segment's runs are uploaded and appended — the BM25 counterpart of nidx_gpu_vector_sync.
+ *
+ *   entries          the new segment array, in search order.  Segment ordinals in DocAddresses, cursors, _apply_deletions,
+ *                    _set_fast_field and _prefilter name positions in it from the commit on.  An old segment may be named once
+ *                    (keep); old segments no entry names are dropped.
+ *   n_terms_new      size of the new generation's term-id space (a term-id space belongs to a generation: the dictionary order
+ *                    of the union of its segments).  A new segment's n_terms must equal it.
+ *   term_map         term_map[t_old] = the new id of an old term, or 0xFFFFFFFF for a term that is gone; injective.  A gone
+ *                    term that still has postings in a kept segment is NIDX_ERR_INVALID_ARGUMENT.  NULL = the identity, which
+ *                    requires n_terms_new >= the old number of terms.
+ *   deletion_*       open_index_with_deletions: segment s loses every document in the posting list of deletion_terms[i] (new
+ *                    term space) for each i with deletion_seqs[i] > seq(s) — new segments too.  For a kept segment that lands on
+ *                    top of the alive set it already has, what nidx_gpu_bm25_apply_deletions cleared included; deletions only
+ *                    remove, so repeating a call changes nothing.
+ *   dict_*           NULL, or the new term dictionary as for nidx_gpu_bm25_set_dictionary ([n_terms_new + 1] offsets).  When
+ *                    NULL the dictionary is kept if the term space did not change (term_map NULL and n_terms_new equal to the
+ *                    old size) and dropped if it did.
+ *
+ * Statistics are tantivy's, searcher-wide: n_docs and total_num_tokens summed over the new generation's segments (a kept
+ * segment's token total is remembered), idf from the new document frequencies, the K / quotient table from the new average;
+ * the score floors are recomputed on the new layout.  Fast fields: a kept segment keeps its registered values, a new one takes
+ * them from its entry; ranks are taken over all segments and a field is registered once every segment has it.
+ *
+ * NIDX_ERR_UNSUPPORTED, index untouched: an index that keeps one resident layout per segment (opened under
+ * NIDX_GPU_BM25_SEGMENT_LOOP=1, or with segments that disagree on positions); a new generation whose segments disagree on
+ * positions; more than 2^32 - 1 documents; a term frequency >= 2^24.
+ *
+ * Everything is validated first (a keep that is out of range or repeated, a NULL segment where keep == -1, a term id out of
+ * range, a term_map that is not injective, and every check nidx_gpu_bm25_open makes of a segment: NIDX_ERR_INVALID_ARGUMENT),
+ * and on ANY error the open index is exactly what it was: hits, totals, alive counts, generation, space usage.
+ *
+ * Concurrency: the new layout is built in fresh buffers on a stream of its own — uploads, the carry, the floors, the alive set,
+ * the deletions — while searches of every kind go on.  The call serialises with _apply_deletions, _set_fast_field,
+ * _set_dictionary and other syncs from start to end; only the commit (a swap of pointers, after the kernels of outstanding
+ * tickets have finished) excludes searches, and it cannot fail.  A ticket submitted before the commit delivers the answer of
+ * the generation it was submitted in.  PEAK MEMORY: the old and the new layout are resident together until the commit, plus
+ * one new segment's postings as scratch: about twice nidx_gpu_bm25_space_usage.
+ * nidx_gpu_bm25_generation: 0 after open, + 1 per successful sync. */
+typedef struct nidx_gpu_bm25_sync_entry {
+    int32_t keep;                           /* >= 0: that segment of the open index, carried on the device; -1: upload `segment` */
+    int64_t seq;                            /* nidx_types::Seq of the segment (tantivy's delete_opstamp) */
+    const nidx_gpu_bm25_segment_t *segment; /* keep == -1: as for nidx_gpu_bm25_open, term ids in the NEW term space */
+    const int64_t *fast_created;            /* keep == -1: NULL or [n_docs], as nidx_gpu_bm25_set_fast_field(field 0) */
+    const int64_t *fast_modified;           /* keep == -1: NULL or [n_docs], field 1 */
+} nidx_gpu_bm25_sync_entry_t;
+
+typedef struct nidx_gpu_bm25_sync_stats {
+    uint64_t generation;        /* the generation the index is in now */
+    uint64_t bytes_uploaded;    /* host-to-device bytes of the call: the new segments' arrays, the dictionary, the per-run tables
+                                 * (O(terms x segments)), the fast-field ranks; no posting of a kept segment */
+    uint64_t postings_carried;  /* postings of kept segments, moved on the device */
+    uint64_t postings_uploaded; /* postings of new segments */
+    uint64_t docs_cleared;      /* alive bits this call's deletions cleared */
+    uint64_t hbm_released;      /* the dropped segments' share of the old layout: 8 bytes per posting, 1 per document, and with
+                                 * positions 8 per posting + 4 per position */
+    uint32_t kept, added, dropped;
+    uint32_t deletions_applied; /* deletions whose seq is above at least one segment's seq */
+} nidx_gpu_bm25_sync_stats_t;
+
+int32_t nidx_gpu_bm25_sync(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_sync_entry_t *entries, uint32_t n_entries,
+                           uint32_t n_terms_new, const uint32_t *term_map, const uint32_t *deletion_terms,
+                           const int64_t *deletion_seqs, uint32_t n_deletions, const uint8_t *dict_bytes,
+                           const uint64_t *dict_offsets, nidx_gpu_bm25_sync_stats_t *stats_out);
+int32_t nidx_gpu_bm25_generation(const nidx_gpu_bm25_index_t *index, uint64_t *generation_out);
 
 /* Device time (HIP events on the handle's stream) spent in the scoring kernel(s) of the last
  * nidx_gpu_bm25_search call, summed over segments.  For batches of term unions with k <= 64 the scoring launch

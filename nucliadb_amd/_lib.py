@@ -152,6 +152,7 @@ class VectorSyncStatsC(C.Structure):
 
 
 FEATURE_VECTOR_SYNC = 1   # nidx_gpu_build_features() bit: nidx_gpu_vector_sync / nidx_gpu_vector_generation
+FEATURE_BM25_SYNC = 2     # nidx_gpu_build_features() bit: nidx_gpu_bm25_sync / nidx_gpu_bm25_generation
 
 
 class FilterOpC(C.Structure):
@@ -198,6 +199,19 @@ class Bm25SegmentC(C.Structure):
         ("pos_offsets", C.c_void_p),
         ("positions", C.c_void_p),
     ]
+
+
+class Bm25SyncEntryC(C.Structure):
+    """nidx_gpu_bm25_sync_entry_t"""
+    _fields_ = [("keep", C.c_int32), ("seq", C.c_int64), ("segment", C.POINTER(Bm25SegmentC)), ("fast_created", C.c_void_p),
+                ("fast_modified", C.c_void_p)]
+
+
+class Bm25SyncStatsC(C.Structure):
+    """nidx_gpu_bm25_sync_stats_t"""
+    _fields_ = [("generation", C.c_uint64), ("bytes_uploaded", C.c_uint64), ("postings_carried", C.c_uint64), ("postings_uploaded", C.c_uint64),
+                ("docs_cleared", C.c_uint64), ("hbm_released", C.c_uint64), ("kept", C.c_uint32), ("added", C.c_uint32), ("dropped", C.c_uint32),
+                ("deletions_applied", C.c_uint32)]
 
 
 class Bm25ClauseC(C.Structure):
@@ -287,6 +301,9 @@ SIGNATURES = {
     "nidx_gpu_bm25_search_wait": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nidx_gpu_bm25_set_fast_field": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "nidx_gpu_bm25_set_dictionary": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nidx_gpu_bm25_sync": (C.c_int32, [C.c_void_p, C.POINTER(Bm25SyncEntryC), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(Bm25SyncStatsC)]),
+    "nidx_gpu_bm25_generation": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_segment_dir_open": (C.c_int32, [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "nidx_gpu_segment_dir_close": (None, [C.c_void_p]),
     "nidx_gpu_segment_dir_index_source": (C.c_int32, [C.c_void_p]),

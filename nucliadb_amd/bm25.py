@@ -115,6 +115,88 @@ class Bm25Segment:
                                  None if self.positions is None else self.positions.ctypes.data)
 
 
+@dataclass
+class SyncEntry:
+    """One segment of the generation nidx_gpu_bm25_sync moves to: `keep` = a segment of the open index (by its position there), or
+    `segment` = a new one (term ids in the new term space) with its fast fields."""
+    seq: int
+    keep: int = -1
+    segment: Optional[Bm25Segment] = None
+    created: Optional[Sequence[int]] = None
+    modified: Optional[Sequence[int]] = None
+
+
+@dataclass
+class Bm25SyncStats:
+    """nidx_gpu_bm25_sync_stats_t"""
+    generation: int
+    bytes_uploaded: int
+    postings_carried: int
+    postings_uploaded: int
+    docs_cleared: int
+    hbm_released: int
+    kept: int
+    added: int
+    dropped: int
+    deletions_applied: int
+
+
+def sync_layout_model(old, entries, n_terms: int, term_map=None):
+    """The layout transform of nidx_gpu_bm25_sync in numpy: `old` = dict(term_offsets [T_old + 1], doc_ids, words, seg_base [S_old + 1],
+    seg_term_offsets [S_old][T_old + 1]) — the term-major concatenation of the old segments over doc + seg_base[segment] — and
+    `entries` = ("keep", s_old) or ("new", term_offsets [T + 1], doc_ids, words, n_docs) each -> the same dict for the new generation.  A term's
+    new list is the concatenation of its runs in entry order; a kept run is the old run with its doc ids shifted by new base - old base."""
+    T_old = len(old["term_offsets"]) - 1
+    tm = np.arange(T_old, dtype=np.int64) if term_map is None else np.asarray(term_map, dtype=np.int64)
+    inv = np.full(n_terms, -1, np.int64)
+    for t_old, t_new in enumerate(tm):
+        if t_new != 0xFFFFFFFF:
+            assert inv[t_new] < 0, "term_map is not injective"
+            inv[t_new] = t_old
+    # where segment s's run of old term t starts in the old layout
+    run_start = []
+    cursor = np.asarray(old["term_offsets"][:-1], dtype=np.int64).copy()
+    for so in old["seg_term_offsets"]:
+        run_start.append(cursor.copy())
+        cursor += np.diff(np.asarray(so, dtype=np.int64))
+    n_docs, seg_offs = [], []
+    for en in entries:
+        if en[0] == "keep":
+            s = en[1]
+            ln = np.zeros(n_terms, np.int64)
+            has = inv >= 0
+            ln[has] = np.diff(np.asarray(old["seg_term_offsets"][s], dtype=np.int64))[inv[has]]
+            n_docs.append(int(old["seg_base"][s + 1] - old["seg_base"][s]))
+        else:
+            ln = np.diff(np.asarray(en[1], dtype=np.int64))
+            n_docs.append(int(en[4]))
+        seg_offs.append(np.concatenate([[0], np.cumsum(ln)]).astype(np.uint64))
+    base = np.concatenate([[0], np.cumsum(n_docs)]).astype(np.int64)
+    total = np.zeros(n_terms, np.int64)
+    for so in seg_offs:
+        total += np.diff(so.astype(np.int64))
+    offs = np.concatenate([[0], np.cumsum(total)]).astype(np.uint64)
+    doc = np.zeros(int(offs[-1]), np.uint32)
+    words = np.zeros(int(offs[-1]), np.uint32)
+    cursor = offs[:-1].astype(np.int64).copy()
+    for e, en in enumerate(entries):
+        so = seg_offs[e].astype(np.int64)
+        for t in np.nonzero(np.diff(so))[0]:
+            n = int(so[t + 1] - so[t])
+            if en[0] == "keep":
+                b = int(run_start[en[1]][inv[t]])
+                d = old["doc_ids"][b: b + n].astype(np.int64) + (base[e] - int(old["seg_base"][en[1]]))
+                w = old["words"][b: b + n]
+            else:
+                b = int(en[1][t])
+                d = np.asarray(en[2][b: b + n], dtype=np.int64) + base[e]
+                w = en[3][b: b + n]
+            doc[cursor[t]: cursor[t] + n] = d
+            words[cursor[t]: cursor[t] + n] = w
+            cursor[t] += n
+    return {"term_offsets": offs, "doc_ids": doc, "words": words, "seg_base": base.astype(np.uint64), "seg_term_offsets": seg_offs}
+
+
 class Bm25Searcher:
     """The scoring core shared by TextSearcher::search and ParagraphSearcher::search."""
 
@@ -140,6 +222,52 @@ class Bm25Searcher:
             self.close()
         except Exception:
             pass
+
+    def sync(self, entries: Sequence[SyncEntry], n_terms: int, term_map=None, deletions: Sequence[Tuple[int, int]] = (),
+             dictionary: Optional[Sequence[str]] = None) -> Bm25SyncStats:
+        """nidx_gpu_bm25_sync: the open index moves to the generation `entries` describes (search order); `term_map[t_old]` = the new
+        id of an old term (0xFFFFFFFF: gone; None: the identity), `deletions` = (term id in the new space, seq) pairs that apply to
+        the segments of a lower seq, `dictionary` = the new term dictionary.  On an error nothing has changed."""
+        arr = (_lib.Bm25SyncEntryC * max(1, len(entries)))()
+        hold, new_segments = [], []
+        for i, en in enumerate(entries):
+            arr[i].keep, arr[i].seq = en.keep, en.seq
+            if en.keep >= 0:
+                new_segments.append(self.segments[en.keep] if en.keep < len(self.segments) else None)
+                continue
+            new_segments.append(en.segment)
+            if en.segment is not None:
+                c = en.segment.to_c()
+                hold.append(c)
+                arr[i].segment = C.pointer(c)
+                for name, values in (("fast_created", en.created), ("fast_modified", en.modified)):
+                    if values is not None:
+                        v = np.ascontiguousarray(values, dtype=np.int64)
+                        assert v.size == en.segment.n_docs
+                        hold.append(v)
+                        setattr(arr[i], name, v.ctypes.data if v.size else None)
+        tm = None if term_map is None else np.ascontiguousarray(term_map, dtype=np.uint32)
+        dt = np.ascontiguousarray([t for t, _ in deletions], dtype=np.uint32)
+        ds = np.ascontiguousarray([s for _, s in deletions], dtype=np.int64)
+        blob = offs = None
+        if dictionary is not None:
+            enc = [t.encode("utf-8") for t in dictionary]
+            offs = np.zeros(len(enc) + 1, np.uint64)
+            offs[1:] = np.cumsum([len(e) for e in enc])
+            blob = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+        st = _lib.Bm25SyncStatsC()
+        _lib.check(_lib.lib().nidx_gpu_bm25_sync(self._handle, arr, len(entries), n_terms, None if tm is None else tm.ctypes.data,
+                                                 dt.ctypes.data if dt.size else None, ds.ctypes.data if ds.size else None, dt.size,
+                                                 None if blob is None else blob.ctypes.data, None if offs is None else offs.ctypes.data,
+                                                 C.byref(st)))
+        self.segments = new_segments
+        return Bm25SyncStats(*[int(getattr(st, f)) for f, _t in _lib.Bm25SyncStatsC._fields_])
+
+    def generation(self) -> int:
+        """0 after open, + 1 per successful sync."""
+        out = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_bm25_generation(self._handle, C.byref(out)))
+        return out.value
 
     def space_usage(self) -> int:
         out = C.c_uint64(0)

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <limits>
 #include <chrono>
 #include <memory>
@@ -59,6 +60,7 @@ struct Bm25Segment {
     std::vector<int64_t> fast_uniq[2];  // the distinct values, ascending: value -> rank for range filters
     DevBuf order_key[2];
     int64_t n_alive = -1;  // live documents, counted on first use
+    std::vector<uint64_t> pos_run_len;  // positions of every term's run (empty: none); a segment of its own only (nidx_gpu_bm25_sync carries runs)
     uint64_t bytes() const {
         return term_offsets.bytes + doc_ids.bytes + tfs.bytes + fieldnorm_ids.bytes + alive.bytes + order_key[0].bytes + order_key[1].bytes +
                pos_offsets.bytes + positions.bytes;
@@ -121,6 +123,7 @@ struct Bm25Slot {
     Bm25Ctx cx;
     // layout of cx.h_outpack for the collect step
     uint32_t nq = 0, k = 0, kk = 0;
+    bool cat = false;   // the resident layout at submit was the concatenation (a sync may have replaced it by the time of the wait)
     size_t o_doc = 0, o_score = 0, o_count = 0, o_total = 0, o_post = 0, o_seg = 0;
     // a request the pipeline does not cover (term sets, phrases, nested queries, facets, order by a field) runs synchronously inside
     // submit; its results wait here
@@ -135,6 +138,10 @@ struct Bm25RealSegment {
     std::vector<uint64_t> term_offsets_host;
     std::vector<int64_t> fast_host[2];
     bool has_fast[2] = {false, false};
+    // what nidx_gpu_bm25_sync needs of a segment it carries into the next generation: its share of the searcher-wide token total and
+    // the number of positions of each of its term runs (empty: none)
+    uint64_t total_tokens = 0;
+    std::vector<uint64_t> pos_run_len;
 };
 
 struct Bm25Index {
@@ -142,8 +149,11 @@ struct Bm25Index {
     int n_cus = 256;   // compute units of the device (the work-item budget of one launch round follows it)
     // mu: the blocking entries (they share `main`) and the mutators; rw: searches hold it shared, mutators (deletions, fast fields)
     // exclusively; slots_mu: the slot table and tickets; ms_mu: last_kernel_ms
-    std::mutex mu, slots_mu, ms_mu;
+    // mut_mu: the mutators (deletions, fast fields, dictionary, nidx_gpu_bm25_sync) from start to end, taken before every other lock —
+    // a sync builds its generation under it alone, so searches go on, and takes mu and rw only for the swap
+    std::mutex mu, slots_mu, ms_mu, mut_mu;
     std::shared_mutex rw;
+    std::atomic<uint64_t> generation{0};   // + 1 per nidx_gpu_bm25_sync
     // The resident segments.  One per opened segment — or, for an index of several segments, ONE: the term-major concatenation over
     // doc + seg_base[segment] (bm25_aux.hip: bm25_concat_postings_kernel), which every kernel walks like a single segment.
     std::vector<Bm25Segment> segs;
@@ -251,6 +261,8 @@ static int32_t bm25_upload_segment(Bm25Index *idx, const nidx_gpu_bm25_segment_t
         NIDX_HIP(hipMemcpy(seg.pos_offsets.p, in.pos_offsets, (size_t)(n_post + 1) * 8, hipMemcpyHostToDevice));
         NIDX_HIP(seg.positions.alloc(std::max<uint64_t>(n_pos, 1) * 4));
         if (n_pos) NIDX_HIP(hipMemcpy(seg.positions.p, in.positions, n_pos * 4, hipMemcpyHostToDevice));
+        seg.pos_run_len.resize(in.n_terms);
+        for (uint32_t t = 0; t < in.n_terms; t++) seg.pos_run_len[t] = in.pos_offsets[in.term_offsets[t + 1]] - in.pos_offsets[in.term_offsets[t]];
     }
     return NIDX_OK;
 }
@@ -268,6 +280,7 @@ static int32_t bm25_upload_concatenated(Bm25Index *idx, const nidx_gpu_bm25_segm
         const nidx_gpu_bm25_segment_t &in = segments[s];
         idx->real[s].n_docs = in.n_docs;
         idx->real[s].term_offsets_host.assign(in.term_offsets, in.term_offsets + T + 1);
+        idx->real[s].total_tokens = in.total_num_tokens;
         n_docs_all += in.n_docs;
         if (n_docs_all > 0xffffffffull)
             return fail(NIDX_ERR_UNSUPPORTED, "the segments of one index hold more than 2^32 - 1 documents together (doc ids are 32-bit on the device)");
@@ -334,6 +347,8 @@ static int32_t bm25_upload_concatenated(Bm25Index *idx, const nidx_gpu_bm25_segm
             // laid down here and summed below
             for (uint32_t t = 0; t < T; t++)
                 for (uint64_t j = o[t]; j < o[t + 1]; j++) vpos_off[dst_start[t] + (j - o[t]) + 1] = in.pos_offsets[j + 1] - in.pos_offsets[j];
+            idx->real[s].pos_run_len.resize(T);
+            for (uint32_t t = 0; t < T; t++) idx->real[s].pos_run_len[t] = in.pos_offsets[o[t + 1]] - in.pos_offsets[o[t]];
         }
     }
     if (with_pos) {
@@ -378,6 +393,44 @@ static int32_t bm25_upload_concatenated(Bm25Index *idx, const nidx_gpu_bm25_segm
         NIDX_HIP(v.alive.alloc(std::max<size_t>(words, 1) * 8));
         if (words) NIDX_HIP(hipMemcpy(v.alive.p, bits.data(), words * 8, hipMemcpyHostToDevice));
     }
+    return NIDX_OK;
+}
+
+// [0, 256): K1 * (1 - B + B * fieldnorm / avg) per fieldnorm id; [256 t, 256 t + 256), t = 1 .. 3: the quotient tf / (tf + that) for
+// tf = t — the same two correctly rounded f32 operations the kernels would make per posting (bm25_stream.hip reads the four rows).
+// -> avg
+static float bm25_tf_table(uint64_t total_docs, uint64_t total_tokens, float cache[4 * 256]) {
+    const float avg = total_docs ? (float)total_tokens / (float)total_docs : 0.0f;
+    for (int id = 0; id < 256; id++) {
+        float fieldnorm = (float)fieldnorm_from_id((uint8_t)id);
+        cache[id] = kK1 * (1.0f - kB + kB * fieldnorm / avg);
+        for (int t = 1; t <= 3; t++) cache[256 * t + id] = (float)t / ((float)t + cache[id]);
+    }
+    return avg;
+}
+
+// The score floors rest on the quotient being monotone: not below the tf = 1 row for larger frequencies, not rising with the fieldnorm
+// id — checked on the very table the kernels read.  quot1 = its tf = 1 row.  NIDX_GPU_BM25_FLOOR=0: no floors.
+static bool bm25_floors_wanted(uint64_t total_docs, float avg, const float cache[4 * 256], float quot1[256]) {
+    bool monotone = total_docs > 0 && avg > 0.0f;
+    for (int id = 0; id < 256 && monotone; id++) {
+        quot1[id] = cache[256 + id];
+        if (!(cache[256 + id] > 0.0f) || !(cache[512 + id] >= cache[256 + id]) || !(cache[768 + id] >= cache[512 + id])) monotone = false;
+        if (id > 0 && !(cache[256 + id] <= cache[256 + id - 1])) monotone = false;
+        if (id > 0 && !(cache[id] >= cache[id - 1])) monotone = false;   // K(fieldnorm id): what the division of tf > 3 adds to tf
+    }
+    const char *fe = getenv("NIDX_GPU_BM25_FLOOR");
+    return monotone && !(fe && atoi(fe) == 0);
+}
+
+static int32_t bm25_term_floors(Bm25Segment &sg, uint32_t n_terms, hipStream_t st, std::vector<uint8_t> &floor_fn) {
+    DevBuf d_floor;
+    const size_t bytes = (size_t)n_terms * BM25_FLOOR_NR;
+    NIDX_HIP(d_floor.alloc(bytes));
+    NIDX_HIP(launch_bm25_term_floors(sg.term_offsets.as<unsigned long long>(), sg.tfs.as<uint32_t>(), n_terms, 1u << 16, d_floor.as<uint8_t>(), st));
+    floor_fn.resize(bytes);
+    NIDX_HIP(hipMemcpyAsync(floor_fn.data(), d_floor.p, bytes, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));
     return NIDX_OK;
 }
 
@@ -427,40 +480,13 @@ int32_t nidx_gpu_bm25_open(const nidx_gpu_bm25_segment_t *segments, uint32_t n_s
         for (const Bm25Segment &sg : idx->segs) df += sg.term_offsets_host[t + 1] - sg.term_offsets_host[t];
         idx->idf_of_term[t] = bm25_idf(df, idx->total_docs);
     }
-    float avg = idx->total_docs ? (float)idx->total_tokens / (float)idx->total_docs : 0.0f;
-    // [0, 256): K1 * (1 - B + B * fieldnorm / avg) per fieldnorm id; [256 t, 256 t + 256), t = 1 .. 3: the quotient tf / (tf + that) for
-    // tf = t — the same two correctly rounded f32 operations the kernels would make per posting (bm25_stream.hip reads the four rows)
     float cache[4 * 256];
-    for (int id = 0; id < 256; id++) {
-        float fieldnorm = (float)fieldnorm_from_id((uint8_t)id);
-        cache[id] = kK1 * (1.0f - kB + kB * fieldnorm / avg);
-        for (int t = 1; t <= 3; t++) cache[256 * t + id] = (float)t / ((float)t + cache[id]);
-    }
+    const float avg = bm25_tf_table(idx->total_docs, idx->total_tokens, cache);
     NIDX_HIP(idx->tf_cache.alloc(sizeof(cache)));
     NIDX_HIP(hipMemcpy(idx->tf_cache.p, cache, sizeof(cache), hipMemcpyHostToDevice));
-    // Per-term score floors for the streaming scorer (one resident layout only).  They rest on the quotient being monotone: not below
-    // the tf = 1 row for larger frequencies, not rising with the fieldnorm id — checked on the very table the kernels read.
-    {
-        bool monotone = idx->total_docs > 0 && avg > 0.0f;
-        for (int id = 0; id < 256 && monotone; id++) {
-            idx->quot1[id] = cache[256 + id];
-            if (!(cache[256 + id] > 0.0f) || !(cache[512 + id] >= cache[256 + id]) || !(cache[768 + id] >= cache[512 + id])) monotone = false;
-            if (id > 0 && !(cache[256 + id] <= cache[256 + id - 1])) monotone = false;
-            if (id > 0 && !(cache[id] >= cache[id - 1])) monotone = false;   // K(fieldnorm id): what the division of tf > 3 adds to tf
-        }
-        const char *fe = getenv("NIDX_GPU_BM25_FLOOR");
-        if (monotone && idx->segs.size() == 1 && idx->n_terms && !(fe && atoi(fe) == 0)) {
-            Bm25Segment &sg = idx->segs[0];
-            DevBuf d_floor;
-            const size_t bytes = (size_t)idx->n_terms * BM25_FLOOR_NR;
-            NIDX_HIP(d_floor.alloc(bytes));
-            NIDX_HIP(launch_bm25_term_floors(sg.term_offsets.as<unsigned long long>(), sg.tfs.as<uint32_t>(), idx->n_terms, 1u << 16, d_floor.as<uint8_t>(),
-                                             idx->main.stream));
-            idx->floor_fn.resize(bytes);
-            NIDX_HIP(hipMemcpyAsync(idx->floor_fn.data(), d_floor.p, bytes, hipMemcpyDeviceToHost, idx->main.stream));
-            NIDX_HIP(hipStreamSynchronize(idx->main.stream));
-        }
-    }
+    // Per-term score floors for the streaming scorer (one resident layout only).
+    if (bm25_floors_wanted(idx->total_docs, avg, cache, idx->quot1) && idx->segs.size() == 1 && idx->n_terms)
+        if (int32_t rc = bm25_term_floors(idx->segs[0], idx->n_terms, idx->main.stream, idx->floor_fn)) return rc;
     *index_out = reinterpret_cast<nidx_gpu_bm25_index_t *>(idx.release());
     return NIDX_OK;
 } NIDX_ABI_CATCH
@@ -516,6 +542,7 @@ static int32_t bm25_upload_fast_field(Bm25Segment &seg, uint32_t field) {
 int32_t nidx_gpu_bm25_set_fast_field(nidx_gpu_bm25_index_t *index, uint32_t segment, uint32_t field, const int64_t *values) try {
     Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
     if (!idx || segment >= idx->n_segments || field > 1 || !values) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad fast field");
+    std::lock_guard<std::mutex> mut_lock(idx->mut_mu);
     std::lock_guard<std::mutex> lock(idx->mu);
     std::unique_lock<std::shared_mutex> wlock(idx->rw);
     NIDX_HIP(hipSetDevice(idx->device));
@@ -546,6 +573,7 @@ int32_t nidx_gpu_bm25_set_fast_field(nidx_gpu_bm25_index_t *index, uint32_t segm
 int32_t nidx_gpu_bm25_set_dictionary(nidx_gpu_bm25_index_t *index, const uint8_t *bytes, const uint64_t *offsets) try {
     Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
     if (!idx || !offsets) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> mut_lock(idx->mut_mu);
     std::lock_guard<std::mutex> lock(idx->mu);
     NIDX_HIP(hipSetDevice(idx->device));
     const uint64_t total = offsets[idx->n_terms];
@@ -1496,6 +1524,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             Bm25Slot &sl = *async_slot;
             sl.launched = true;
             sl.nq = nq, sl.k = k, sl.kk = kk;
+            sl.cat = cat;
             sl.o_doc = o_doc, sl.o_score = o_score, sl.o_count = o_count, sl.o_total = o_total, sl.o_post = o_post, sl.o_seg = o_seg;
             return NIDX_OK;
         }
@@ -1735,7 +1764,7 @@ int32_t nidx_gpu_bm25_search_wait(nidx_gpu_bm25_index_t *index, uint64_t ticket,
         const unsigned long long *h_total = reinterpret_cast<const unsigned long long *>(h_out + slot->o_total);
         const unsigned long long *h_post = reinterpret_cast<const unsigned long long *>(h_out + slot->o_post);
         const uint32_t kk = slot->kk;
-        const bool cat = idx->concatenated();
+        const bool cat = slot->cat;   // (as it was at submit: the index may be in a later generation by now)
         const uint32_t *h_seg = reinterpret_cast<const uint32_t *>(h_out + slot->o_seg);   // (concatenated layout only)
         for (uint32_t q = 0; q < nq; q++) {   // one resident segment: the device list is the answer
             if (out_total) out_total[q] = h_total[q];
@@ -1768,6 +1797,7 @@ int32_t nidx_gpu_bm25_apply_deletions(nidx_gpu_bm25_index_t *index, uint32_t seg
                                       uint64_t *n_alive_out) try {
     Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
     if (!idx || segment >= idx->n_segments || (n_terms && !terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad index/segment");
+    std::lock_guard<std::mutex> mut_lock(idx->mut_mu);
     std::lock_guard<std::mutex> lock(idx->mu);
     std::unique_lock<std::shared_mutex> wlock(idx->rw);
     NIDX_HIP(hipSetDevice(idx->device));
@@ -1860,6 +1890,503 @@ int32_t nidx_gpu_bm25_search(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_c
     opt.after = after;
     opt.order_field = -1;
     return nidx_gpu_bm25_search_ex(index, clauses, clause_offsets, nq, &opt, out_docaddr, out_score, out_count, out_total, out_postings);
+} NIDX_ABI_CATCH
+
+// ---- nidx_gpu_bm25_sync: the open index moves to a new generation (include/nidx_gpu.h; kernels: bm25_sync.hip) --------------------
+namespace {
+
+const uint32_t kNoTerm = 0xffffffffu;
+
+// everything a generation is: built aside, swapped with the index's members at the commit
+struct Bm25Generation {
+    std::vector<Bm25Segment> segs;
+    std::vector<Bm25RealSegment> real;
+    std::vector<uint32_t> seg_base;
+    DevBuf d_seg_base, tf_cache, dict_bytes, dict_offsets;
+    uint32_t n_segments = 0, n_terms = 0;
+    uint64_t total_docs = 0, total_tokens = 0;
+    std::vector<float> idf_of_term;
+    std::vector<uint8_t> floor_fn;
+    float quot1[256] = {};
+    bool has_dict = false;
+};
+
+// device scratch of one sync (it outlives the stream's work: see nidx_gpu_bm25_sync)
+struct Bm25SyncScratch {
+    DevBuf tab, t_doc, t_tf, t_pos_off, t_positions, alive_in, alive_tab, pairs, cleared, flag;
+};
+
+// a segment of the open index as the sync reads it, whichever layout it is in
+struct Bm25OldSegment {
+    uint32_t n_docs = 0, base = 0;
+    uint64_t total_tokens = 0;
+    const uint64_t *off = nullptr;                    // [n_terms_old + 1]
+    const std::vector<uint64_t> *pos_run_len = nullptr;
+    const std::vector<int64_t> *fast[2] = {nullptr, nullptr};
+    bool has_fast[2] = {false, false};
+    std::vector<uint64_t> run_start, pos_run_start;   // of every term's run in the old resident postings / positions
+};
+
+}  // namespace
+
+static int32_t bm25_sync_build(Bm25Index *idx, hipStream_t st, Bm25SyncScratch &sc, Bm25Generation &g, const nidx_gpu_bm25_sync_entry_t *entries,
+                               uint32_t S, uint32_t T, const uint32_t *term_map, const uint32_t *del_terms, const int64_t *del_seqs, uint32_t n_del,
+                               const uint8_t *dict_bytes, const uint64_t *dict_offsets, nidx_gpu_bm25_sync_stats_t &stats) {
+    if (idx->segs.size() > 1)
+        return fail(NIDX_ERR_UNSUPPORTED, "nidx_gpu_bm25_sync: the index keeps one resident layout per segment (NIDX_GPU_BM25_SEGMENT_LOOP, or segments that "
+                                          "disagree on positions)");
+    const uint32_t T_old = idx->n_terms, S_old = idx->n_segments;
+    const Bm25Segment *ov = idx->segs.empty() ? nullptr : &idx->segs[0];
+    const bool old_pos = ov && ov->pos_offsets.p != nullptr;
+    // ---- the old generation ----
+    std::vector<Bm25OldSegment> old(S_old);
+    for (uint32_t s = 0; s < S_old; s++) {
+        Bm25OldSegment &o = old[s];
+        if (idx->concatenated()) {
+            const Bm25RealSegment &r = idx->real[s];
+            o.n_docs = r.n_docs, o.base = idx->seg_base[s], o.total_tokens = r.total_tokens, o.off = r.term_offsets_host.data();
+            o.pos_run_len = &r.pos_run_len;
+            for (int f = 0; f < 2; f++) o.fast[f] = &r.fast_host[f], o.has_fast[f] = r.has_fast[f];
+        } else {
+            o.n_docs = ov->n_docs, o.base = 0, o.total_tokens = idx->total_tokens, o.off = ov->term_offsets_host.data();
+            o.pos_run_len = &ov->pos_run_len;
+            for (int f = 0; f < 2; f++) o.fast[f] = &ov->fast_host[f], o.has_fast[f] = ov->order_key[f].p != nullptr;
+        }
+    }
+    // ---- validation: nothing below this block can fail for a reason the caller's arguments give ----
+    std::vector<uint32_t> inv(T, kNoTerm);   // new term -> old term
+    if (!term_map) {
+        if (T < T_old) return fail(NIDX_ERR_INVALID_ARGUMENT, "term_map NULL (identity) needs n_terms_new >= %u (got %u)", T_old, T);
+        for (uint32_t t = 0; t < T_old; t++) inv[t] = t;
+    } else {
+        for (uint32_t t = 0; t < T_old; t++) {
+            const uint32_t n = term_map[t];
+            if (n == kNoTerm) continue;
+            if (n >= T) return fail(NIDX_ERR_INVALID_ARGUMENT, "term_map[%u] = %u is out of range (n_terms_new %u)", t, n, T);
+            if (inv[n] != kNoTerm) return fail(NIDX_ERR_INVALID_ARGUMENT, "term_map is not injective: old terms %u and %u both map to %u", inv[n], t, n);
+            inv[n] = t;
+        }
+    }
+    std::vector<uint8_t> named(S_old, 0);
+    uint64_t n_docs_all = 0;
+    bool some_pos = false, some_without = false;
+    for (uint32_t e = 0; e < S; e++) {
+        const nidx_gpu_bm25_sync_entry_t &en = entries[e];
+        if (en.keep >= 0) {
+            if ((uint32_t)en.keep >= S_old) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: keep = %d but the open index has %u segments", e, en.keep, S_old);
+            if (named[en.keep]) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: segment %d of the open index is named twice", e, en.keep);
+            named[en.keep] = 1;
+            const Bm25OldSegment &o = old[en.keep];
+            if (term_map)
+                for (uint32_t t = 0; t < T_old; t++)
+                    if (term_map[t] == kNoTerm && o.off[t + 1] > o.off[t])
+                        return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: term %u is gone but still has postings in kept segment %d", e, t, en.keep);
+            n_docs_all += o.n_docs;
+            if (o.off[T_old]) (old_pos ? some_pos : some_without) = true;
+        } else if (en.keep == -1) {
+            if (!en.segment) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: keep = -1 with a NULL segment", e);
+            if (en.segment->n_terms != T) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: the segment has %u terms, the new term space %u", e, en.segment->n_terms, T);
+            if (int32_t rc = bm25_check_segment(*en.segment, e)) return rc;
+            n_docs_all += en.segment->n_docs;
+            if (en.segment->term_offsets[T]) (en.segment->pos_offsets ? some_pos : some_without) = true;
+        } else {
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: keep = %d", e, en.keep);
+        }
+        if (n_docs_all > 0xffffffffull)
+            return fail(NIDX_ERR_UNSUPPORTED, "the segments of one index hold more than 2^32 - 1 documents together (doc ids are 32-bit on the device)");
+    }
+    if (some_pos && some_without) return fail(NIDX_ERR_UNSUPPORTED, "nidx_gpu_bm25_sync: the new generation's segments disagree on positions");
+    for (uint32_t i = 0; i < n_del; i++)
+        if (del_terms[i] >= T) return fail(NIDX_ERR_INVALID_ARGUMENT, "deletion term id %u out of range", del_terms[i]);
+    if (dict_offsets && dict_offsets[T] && !dict_bytes) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL dictionary bytes");
+    // ---- where the old runs lie ----
+    if (ov) {
+        std::vector<uint64_t> cursor(T_old);
+        for (uint32_t t = 0; t < T_old; t++) cursor[t] = ov->term_offsets_host[t];
+        for (uint32_t s = 0; s < S_old; s++) {
+            old[s].run_start.resize(T_old);
+            for (uint32_t t = 0; t < T_old; t++) old[s].run_start[t] = cursor[t], cursor[t] += old[s].off[t + 1] - old[s].off[t];
+        }
+        if (old_pos) {
+            for (uint32_t s = 0; s < S_old; s++) old[s].pos_run_start.assign(T_old, 0);
+            uint64_t at = 0;
+            for (uint32_t t = 0; t < T_old; t++)
+                for (uint32_t s = 0; s < S_old; s++) {
+                    old[s].pos_run_start[t] = at;
+                    if (!old[s].pos_run_len->empty()) at += (*old[s].pos_run_len)[t];
+                }
+        }
+    }
+    // ---- the new generation's run tables (host, O(terms x segments)): lengths, then starts by a scan in (term, segment) order ----
+    uint64_t bytes_up = 0;
+    auto upload = [&](void *dst, const void *src, size_t bytes) {
+        bytes_up += bytes;
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    };
+    const bool with_pos_runs = some_pos;
+    std::vector<std::vector<uint64_t>> len(S), plen(S), dst_start(S), pdst_start(S);
+    g.real.resize(S);
+    g.seg_base.assign((size_t)S + 1, 0);
+    g.n_segments = S, g.n_terms = T;
+    uint64_t n_post_all = 0, n_pos_all = 0;
+    int64_t min_seq = std::numeric_limits<int64_t>::max();
+    for (uint32_t e = 0; e < S; e++) {
+        const nidx_gpu_bm25_sync_entry_t &en = entries[e];
+        Bm25RealSegment &r = g.real[e];
+        len[e].assign(T, 0);
+        if (with_pos_runs) plen[e].assign(T, 0);
+        r.term_offsets_host.assign((size_t)T + 1, 0);
+        if (en.keep >= 0) {
+            const Bm25OldSegment &o = old[en.keep];
+            r.n_docs = o.n_docs, r.total_tokens = o.total_tokens;
+            for (uint32_t t = 0; t < T; t++) {
+                const uint32_t to = inv[t];
+                if (to == kNoTerm) continue;
+                len[e][t] = o.off[to + 1] - o.off[to];
+                if (with_pos_runs && !o.pos_run_len->empty()) plen[e][t] = (*o.pos_run_len)[to];
+            }
+            for (int f = 0; f < 2; f++)
+                if (o.has_fast[f]) r.fast_host[f] = *o.fast[f], r.has_fast[f] = true;
+            stats.kept++;
+        } else {
+            const nidx_gpu_bm25_segment_t &in = *en.segment;
+            r.n_docs = in.n_docs, r.total_tokens = in.total_num_tokens;
+            for (uint32_t t = 0; t < T; t++) {
+                len[e][t] = in.term_offsets[t + 1] - in.term_offsets[t];
+                if (with_pos_runs && in.pos_offsets) plen[e][t] = in.pos_offsets[in.term_offsets[t + 1]] - in.pos_offsets[in.term_offsets[t]];
+            }
+            const int64_t *fv[2] = {en.fast_created, en.fast_modified};
+            for (int f = 0; f < 2; f++)
+                if (fv[f] || in.n_docs == 0) r.fast_host[f].assign(fv[f], fv[f] + (fv[f] ? in.n_docs : 0)), r.has_fast[f] = true;
+            stats.added++;
+        }
+        for (uint32_t t = 0; t < T; t++) r.term_offsets_host[t + 1] = r.term_offsets_host[t] + len[e][t];
+        if (with_pos_runs) r.pos_run_len = plen[e];
+        (en.keep >= 0 ? stats.postings_carried : stats.postings_uploaded) += r.term_offsets_host[T];
+        n_post_all += r.term_offsets_host[T];
+        g.seg_base[e + 1] = g.seg_base[e] + r.n_docs;
+        g.total_docs += r.n_docs, g.total_tokens += r.total_tokens;
+        min_seq = std::min(min_seq, en.seq);
+    }
+    for (uint32_t s = 0; s < S_old; s++) {
+        if (named[s]) continue;
+        stats.dropped++;
+        uint64_t b = 8ull * old[s].off[T_old] + old[s].n_docs;
+        if (old_pos) {
+            b += 8ull * old[s].off[T_old];
+            for (uint64_t v : *old[s].pos_run_len) b += 4ull * v;
+        }
+        stats.hbm_released += b;
+    }
+    for (uint32_t i = 0; i < n_del; i++)
+        if (S && del_seqs[i] > min_seq) stats.deletions_applied++;
+    if (S == 0) {   // an index of no segments: as nidx_gpu_bm25_open leaves it
+        g.seg_base.clear();
+        g.idf_of_term.assign(T, bm25_idf(0, 0));
+    }
+    float cache[4 * 256];
+    const float avg = bm25_tf_table(g.total_docs, g.total_tokens, cache);
+    NIDX_HIP(g.tf_cache.alloc(sizeof(cache)));
+    NIDX_HIP(upload(g.tf_cache.p, cache, sizeof(cache)));
+    NIDX_HIP(hipStreamSynchronize(st));   // (`cache` is on this frame; the early return of S == 0 below)
+    // the dictionary: replaced, kept (same term space) or dropped
+    if (dict_offsets) {
+        const uint64_t total = dict_offsets[T];
+        NIDX_HIP(g.dict_bytes.alloc(std::max<uint64_t>(total, 1)));
+        NIDX_HIP(g.dict_offsets.alloc((size_t)(T + 1) * 8));
+        NIDX_HIP(upload(g.dict_bytes.p, dict_bytes, total));
+        NIDX_HIP(upload(g.dict_offsets.p, dict_offsets, (size_t)(T + 1) * 8));
+        g.has_dict = true;
+    } else if (!term_map && T == T_old && idx->has_dict) {
+        // (set_dictionary is excluded by mut_mu; the copy is device to device)
+        NIDX_HIP(g.dict_bytes.alloc(idx->dict_bytes.bytes));
+        NIDX_HIP(g.dict_offsets.alloc(idx->dict_offsets.bytes));
+        NIDX_HIP(hipMemcpyAsync(g.dict_bytes.p, idx->dict_bytes.p, idx->dict_bytes.bytes, hipMemcpyDeviceToDevice, st));
+        NIDX_HIP(hipMemcpyAsync(g.dict_offsets.p, idx->dict_offsets.p, idx->dict_offsets.bytes, hipMemcpyDeviceToDevice, st));
+        g.has_dict = true;
+    }
+    if (S == 0) {
+        NIDX_HIP(hipStreamSynchronize(st));
+        stats.bytes_uploaded = bytes_up;
+        return NIDX_OK;
+    }
+    g.segs.resize(1);
+    Bm25Segment &nv = g.segs[0];
+    nv.n_docs = (uint32_t)n_docs_all, nv.n_terms = T;
+    std::vector<uint64_t> &voff = nv.term_offsets_host;
+    voff.assign((size_t)T + 1, 0);
+    for (uint32_t t = 0; t < T; t++) {
+        uint64_t l = 0;
+        for (uint32_t e = 0; e < S; e++) {
+            l += len[e][t];
+        }
+        voff[t + 1] = voff[t] + l;
+    }
+    {
+        std::vector<uint64_t> cursor(voff.begin(), voff.end() - 1);
+        for (uint32_t e = 0; e < S; e++) {
+            dst_start[e].resize(T);
+            for (uint32_t t = 0; t < T; t++) dst_start[e][t] = cursor[t], cursor[t] += len[e][t];
+        }
+    }
+    const bool with_pos = with_pos_runs && n_post_all > 0;
+    if (with_pos) {
+        for (uint32_t e = 0; e < S; e++) pdst_start[e].resize(T);
+        for (uint32_t t = 0; t < T; t++)
+            for (uint32_t e = 0; e < S; e++) pdst_start[e][t] = n_pos_all, n_pos_all += plen[e][t];
+    }
+    g.idf_of_term.resize(T);
+    for (uint32_t t = 0; t < T; t++) g.idf_of_term[t] = bm25_idf(voff[t + 1] - voff[t], g.total_docs);
+    // ---- the new resident layout, in fresh buffers ----
+    NIDX_HIP(g.d_seg_base.alloc((size_t)(S + 1) * 4));
+    NIDX_HIP(upload(g.d_seg_base.p, g.seg_base.data(), (size_t)(S + 1) * 4));
+    NIDX_HIP(nv.term_offsets.alloc((size_t)(T + 1) * 8));
+    NIDX_HIP(upload(nv.term_offsets.p, voff.data(), (size_t)(T + 1) * 8));
+    NIDX_HIP(nv.doc_ids.alloc(std::max<size_t>(n_post_all, 1) * 4 + BM25_LIST_PAD_BYTES));
+    NIDX_HIP(nv.tfs.alloc(std::max<size_t>(n_post_all, 1) * 4 + BM25_LIST_PAD_BYTES));
+    NIDX_HIP(nv.fieldnorm_ids.alloc(std::max<size_t>(nv.n_docs, 1)));
+    if (with_pos) {
+        NIDX_HIP(nv.pos_offsets.alloc((size_t)(n_post_all + 1) * 8));
+        NIDX_HIP(nv.positions.alloc(std::max<uint64_t>(n_pos_all, 1) * 4));
+        NIDX_HIP(upload(nv.pos_offsets.as<uint64_t>() + n_post_all, &n_pos_all, 8));
+    }
+    NIDX_HIP(sc.flag.alloc(4));
+    NIDX_HIP(hipMemsetAsync(sc.flag.p, 0, 4, st));
+    // per segment: [seg_off T + 1 | src_delta T | dst_delta T | pos_delta T | pos seg_off T + 1 | pos src_delta T | pos dst_delta T]
+    const size_t tab_words = 7 * (size_t)T + 2;
+    std::vector<unsigned long long> tab(tab_words);
+    NIDX_HIP(sc.tab.alloc(tab_words * 8));
+    unsigned long long *const h_off = tab.data(), *const h_src = h_off + T + 1, *const h_dst = h_src + T, *const h_pd = h_dst + T,
+                             *const h_poff = h_pd + T, *const h_psrc = h_poff + T + 1, *const h_pdst = h_psrc + T;
+    const unsigned long long *const d_tab = sc.tab.as<unsigned long long>();
+    // NIDX_GPU_BM25_SYNC_TRACE=1 (measurement, scripts/bm25_sync.py): the carry launches and the deletion launch between HIP events
+    const bool trace = getenv("NIDX_GPU_BM25_SYNC_TRACE") != nullptr;
+    struct Events {
+        hipEvent_t a = nullptr, b = nullptr;
+        ~Events() {
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+        }
+    } ev;
+    if (trace) {
+        NIDX_HIP(hipEventCreate(&ev.a));
+        NIDX_HIP(hipEventCreate(&ev.b));
+    }
+    float carry_ms = 0.f, place_ms = 0.f, del_ms = 0.f;
+    for (uint32_t e = 0; e < S; e++) {
+        const nidx_gpu_bm25_sync_entry_t &en = entries[e];
+        const Bm25RealSegment &r = g.real[e];
+        const uint64_t n_post = r.term_offsets_host[T];
+        const Bm25OldSegment *o = en.keep >= 0 ? &old[en.keep] : nullptr;
+        const nidx_gpu_bm25_segment_t *in = o ? nullptr : en.segment;
+        uint8_t *fn_dst = nv.fieldnorm_ids.as<uint8_t>() + g.seg_base[e];
+        if (o) {
+            if (o->n_docs) NIDX_HIP(hipMemcpyAsync(fn_dst, ov->fieldnorm_ids.as<uint8_t>() + o->base, o->n_docs, hipMemcpyDeviceToDevice, st));
+        } else {
+            NIDX_HIP(upload(fn_dst, in->fieldnorm_ids, in->n_docs));
+        }
+        if (!n_post) continue;
+        uint64_t n_pos = 0;
+        for (uint32_t t = 0; t < T; t++) {
+            const uint32_t to = o ? inv[t] : t;
+            const bool run = len[e][t] != 0;   // (a term without a run here is never looked up: its deltas stay 0)
+            const uint64_t src = !run ? 0 : o ? o->run_start[to] : in->term_offsets[t];
+            h_off[t] = r.term_offsets_host[t];
+            h_src[t] = run ? src - h_off[t] : 0;
+            h_dst[t] = run ? dst_start[e][t] - h_off[t] : 0;
+            if (with_pos) {
+                const uint64_t psrc = !run ? 0 : o ? o->pos_run_start[to] : in->pos_offsets[in->term_offsets[t]];
+                h_pd[t] = run ? pdst_start[e][t] - psrc : 0;
+                h_poff[t] = n_pos;
+                h_psrc[t] = run ? psrc - n_pos : 0;
+                h_pdst[t] = run ? pdst_start[e][t] - n_pos : 0;
+                n_pos += plen[e][t];
+            }
+        }
+        h_off[T] = n_post;
+        h_poff[T] = n_pos;
+        NIDX_HIP(upload(sc.tab.p, tab.data(), (with_pos ? tab_words : 3 * (size_t)T + 1) * 8));
+        Bm25SyncCarry a;
+        memset(&a, 0, sizeof(a));
+        a.seg_off = d_tab, a.src_delta = d_tab + (h_src - h_off), a.dst_delta = d_tab + (h_dst - h_off), a.pos_delta = d_tab + (h_pd - h_off);
+        a.n_items = n_post, a.n_terms = T;
+        a.dst_a = nv.doc_ids.as<uint32_t>(), a.dst_b = nv.tfs.as<uint32_t>();
+        a.add_a = g.seg_base[e] - (o ? o->base : 0u);   // (modulo 2^32, like the addition in the kernel)
+        Bm25SyncCarry p;
+        memset(&p, 0, sizeof(p));
+        p.seg_off = d_tab + (h_poff - h_off), p.src_delta = d_tab + (h_psrc - h_off), p.dst_delta = d_tab + (h_pdst - h_off);
+        p.n_items = n_pos, p.n_terms = T, p.dst_a = nv.positions.as<uint32_t>();
+        if (o) {
+            a.src_a = ov->doc_ids.as<uint32_t>(), a.src_b = ov->tfs.as<uint32_t>();
+            if (with_pos) a.src_pos = ov->pos_offsets.as<unsigned long long>(), p.src_a = ov->positions.as<uint32_t>();
+        } else {
+            // a new segment passes through device scratch: uploaded as it is, its posting words packed there
+            // (tf | fieldnorm id << 24, with open's refusals), then placed like a kept segment's runs
+            NIDX_HIP(sc.t_doc.reserve(n_post * 4));
+            NIDX_HIP(sc.t_tf.reserve(n_post * 4));
+            NIDX_HIP(upload(sc.t_doc.p, in->doc_ids, n_post * 4));
+            NIDX_HIP(upload(sc.t_tf.p, in->tfs, n_post * 4));
+            NIDX_HIP(launch_bm25_pack_fieldnorm(sc.t_doc.as<uint32_t>(), sc.t_tf.as<uint32_t>(), fn_dst, n_post, in->n_docs, sc.flag.as<uint32_t>(), st));
+            a.src_a = sc.t_doc.as<uint32_t>(), a.src_b = sc.t_tf.as<uint32_t>();
+            if (with_pos) {
+                NIDX_HIP(sc.t_pos_off.reserve((size_t)(n_post + 1) * 8));
+                NIDX_HIP(sc.t_positions.reserve(std::max<uint64_t>(in->pos_offsets[n_post], 1) * 4));
+                NIDX_HIP(upload(sc.t_pos_off.p, in->pos_offsets, (size_t)(n_post + 1) * 8));
+                NIDX_HIP(upload(sc.t_positions.p, in->positions, (size_t)in->pos_offsets[n_post] * 4));
+                a.src_pos = sc.t_pos_off.as<unsigned long long>(), p.src_a = sc.t_positions.as<uint32_t>();
+            }
+        }
+        if (with_pos) a.dst_pos = nv.pos_offsets.as<unsigned long long>();
+        if (trace) NIDX_HIP(hipEventRecord(ev.a, st));
+        NIDX_HIP(launch_bm25_sync_carry(a, st));
+        if (with_pos) NIDX_HIP(launch_bm25_sync_carry(p, st));
+        if (trace) NIDX_HIP(hipEventRecord(ev.b, st));
+        uint32_t f = 0;
+        NIDX_HIP(hipMemcpyAsync(&f, sc.flag.p, 4, hipMemcpyDeviceToHost, st));
+        NIDX_HIP(hipStreamSynchronize(st));   // the tables and the scratch are rewritten for the next segment
+        if (trace) {
+            float ms = 0.f;
+            NIDX_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+            (o ? carry_ms : place_ms) += ms;
+        }
+        if (f & 1u) return fail(NIDX_ERR_UNSUPPORTED, "entry %u: a term frequency >= 2^24 does not fit the resident posting word", e);
+        if (f & 2u) return fail(NIDX_ERR_INVALID_ARGUMENT, "entry %u: a posting's doc id is >= n_docs", e);
+    }
+    // ---- alive set and deletions ----
+    std::vector<Bm25SyncDeletion> pairs;
+    for (uint32_t e = 0; e < S; e++)
+        for (uint32_t i = 0; i < n_del; i++) {
+            const uint32_t t = del_terms[i];
+            if (del_seqs[i] > entries[e].seq && len[e][t]) pairs.push_back(Bm25SyncDeletion{dst_start[e][t], dst_start[e][t] + len[e][t], e, 0u});
+        }
+    if (pairs.size() > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "more than 2^32 - 1 (segment, deletion) pairs in one sync");
+    bool need_bits = !pairs.empty(), had_bits = false;
+    for (uint32_t e = 0; e < S; e++) {
+        if (entries[e].keep >= 0 ? !ov->all_alive : entries[e].segment->alive_bitset != nullptr) need_bits = had_bits = true;
+    }
+    nv.all_alive = !need_bits;
+    const uint32_t words = (uint32_t)(((uint64_t)nv.n_docs + 63) / 64);
+    if (need_bits && words) {
+        std::vector<Bm25SyncAliveSeg> at(S);
+        size_t in_words = 0;
+        for (uint32_t e = 0; e < S; e++)
+            if (entries[e].keep < 0 && entries[e].segment->alive_bitset) in_words += ((size_t)entries[e].segment->n_docs + 63) / 64;
+        NIDX_HIP(sc.alive_in.alloc(std::max<size_t>(in_words, 1) * 8));
+        in_words = 0;
+        for (uint32_t e = 0; e < S; e++) {
+            Bm25SyncAliveSeg &a = at[e];
+            a.new_base = g.seg_base[e], a.n_docs = g.real[e].n_docs, a.src = nullptr, a.src_bit0 = 0, a.reserved = 0;
+            if (entries[e].keep >= 0) {
+                if (!ov->all_alive) a.src = ov->alive.as<uint64_t>(), a.src_bit0 = old[entries[e].keep].base;
+            } else if (entries[e].segment->alive_bitset) {
+                const size_t w = ((size_t)a.n_docs + 63) / 64;
+                a.src = sc.alive_in.as<uint64_t>() + in_words;
+                NIDX_HIP(upload(sc.alive_in.as<uint64_t>() + in_words, entries[e].segment->alive_bitset, w * 8));
+                in_words += w;
+            }
+        }
+        NIDX_HIP(sc.alive_tab.alloc(at.size() * sizeof(Bm25SyncAliveSeg)));
+        NIDX_HIP(upload(sc.alive_tab.p, at.data(), at.size() * sizeof(Bm25SyncAliveSeg)));
+        NIDX_HIP(nv.alive.alloc((size_t)words * 8));
+        NIDX_HIP(launch_bm25_sync_alive(sc.alive_tab.as<Bm25SyncAliveSeg>(), S, words, nv.alive.as<uint64_t>(), st));
+        std::vector<uint32_t> cleared(S, 0);
+        if (!pairs.empty()) {
+            NIDX_HIP(sc.pairs.alloc(pairs.size() * sizeof(Bm25SyncDeletion)));
+            NIDX_HIP(upload(sc.pairs.p, pairs.data(), pairs.size() * sizeof(Bm25SyncDeletion)));
+            NIDX_HIP(sc.cleared.alloc((size_t)S * 4));
+            NIDX_HIP(hipMemsetAsync(sc.cleared.p, 0, (size_t)S * 4, st));
+            if (trace) NIDX_HIP(hipEventRecord(ev.a, st));
+            NIDX_HIP(launch_bm25_sync_deletions(sc.pairs.as<Bm25SyncDeletion>(), (uint32_t)pairs.size(), nv.doc_ids.as<uint32_t>(), nv.n_docs,
+                                                nv.alive.as<unsigned int>(), sc.cleared.as<uint32_t>(), st));
+            if (trace) NIDX_HIP(hipEventRecord(ev.b, st));
+            NIDX_HIP(hipMemcpyAsync(cleared.data(), sc.cleared.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+        }
+        NIDX_HIP(hipStreamSynchronize(st));   // `at`, `pairs` and the caller's bitsets are pageable host memory
+        for (uint32_t c : cleared) stats.docs_cleared += c;
+        if (trace && !pairs.empty()) NIDX_HIP(hipEventElapsedTime(&del_ms, ev.a, ev.b));
+        if (!had_bits && stats.docs_cleared == 0) {   // the deletions found every segment all alive and cleared nothing: it stays that way
+            nv.alive.release();
+            nv.all_alive = true;
+        }
+    } else if (need_bits) {
+        NIDX_HIP(nv.alive.alloc(8));   // (no documents at all)
+        NIDX_HIP(hipMemsetAsync(nv.alive.p, 0, 8, st));
+    }
+    // ---- score floors on the new layout, fast fields ----
+    if (bm25_floors_wanted(g.total_docs, avg, cache, g.quot1) && T)
+        if (int32_t rc = bm25_term_floors(nv, T, st, g.floor_fn)) return rc;
+    for (uint32_t f = 0; f < 2; f++) {
+        bool all = true;
+        for (const Bm25RealSegment &r : g.real) all = all && r.has_fast[f];
+        if (!all) continue;
+        nv.fast_host[f].reserve(nv.n_docs);
+        for (const Bm25RealSegment &r : g.real) nv.fast_host[f].insert(nv.fast_host[f].end(), r.fast_host[f].begin(), r.fast_host[f].end());
+        if (int32_t rc = bm25_upload_fast_field(nv, f)) return rc;
+        bytes_up += (uint64_t)nv.n_docs * 4;
+    }
+    NIDX_HIP(hipStreamSynchronize(st));
+    stats.bytes_uploaded = bytes_up;
+    if (trace)
+        fprintf(stderr, "[bm25 sync] carry %.3f ms over %llu postings of kept segments, placing %.3f ms over %llu uploaded postings, deletions %.3f ms over %zu pairs\n",
+                carry_ms, (unsigned long long)stats.postings_carried, place_ms, (unsigned long long)stats.postings_uploaded, del_ms, pairs.size());
+    return NIDX_OK;
+}
+
+int32_t nidx_gpu_bm25_sync(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_sync_entry_t *entries, uint32_t n_entries, uint32_t n_terms_new,
+                           const uint32_t *term_map, const uint32_t *deletion_terms, const int64_t *deletion_seqs, uint32_t n_deletions,
+                           const uint8_t *dict_bytes, const uint64_t *dict_offsets, nidx_gpu_bm25_sync_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || (n_entries && !entries) || (n_deletions && (!deletion_terms || !deletion_seqs))) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> mut_lock(idx->mut_mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    nidx_gpu_bm25_sync_stats_t stats;
+    memset(&stats, 0, sizeof(stats));
+    // Declared in this order on purpose: the stream is drained (StreamOwner's destructor) before the scratch and a generation that
+    // was not committed are freed, whichever way the call ends.
+    Bm25Generation g;
+    Bm25SyncScratch sc;
+    struct StreamOwner {
+        hipStream_t st = nullptr;
+        ~StreamOwner() {
+            if (st) {
+                (void)hipStreamSynchronize(st);
+                (void)hipStreamDestroy(st);
+            }
+        }
+    } so;
+    NIDX_HIP(hipStreamCreateWithFlags(&so.st, hipStreamNonBlocking));
+    if (int32_t rc = bm25_sync_build(idx, so.st, sc, g, entries, n_entries, n_terms_new, term_map, deletion_terms, deletion_seqs, n_deletions, dict_bytes,
+                                     dict_offsets, stats))
+        return rc;
+    {
+        // the commit: the blocking entries and the collectors are out (mu), no submit is between its planning and its launches (rw), and
+        // the kernels of the tickets already out have finished on the old layout (the drain) — then only members change hands
+        std::lock_guard<std::mutex> lock(idx->mu);
+        std::unique_lock<std::shared_mutex> wlock(idx->rw);
+        if (int32_t rc = bm25_drain_tickets(idx)) return rc;
+        idx->segs.swap(g.segs);
+        idx->real.swap(g.real);
+        idx->seg_base.swap(g.seg_base);
+        std::swap(idx->d_seg_base, g.d_seg_base);
+        std::swap(idx->tf_cache, g.tf_cache);
+        std::swap(idx->dict_bytes, g.dict_bytes);
+        std::swap(idx->dict_offsets, g.dict_offsets);
+        std::swap(idx->has_dict, g.has_dict);
+        idx->n_segments = g.n_segments, idx->n_terms = g.n_terms, idx->total_docs = g.total_docs, idx->total_tokens = g.total_tokens;
+        idx->idf_of_term.swap(g.idf_of_term);
+        idx->floor_fn.swap(g.floor_fn);
+        memcpy(idx->quot1, g.quot1, sizeof(idx->quot1));
+        stats.generation = idx->generation.fetch_add(1) + 1;
+    }
+    if (stats_out) *stats_out = stats;
+    return NIDX_OK;   // (the old generation, now in `g`, is freed here: outside the locks)
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_bm25_generation(const nidx_gpu_bm25_index_t *index, uint64_t *generation_out) try {
+    const Bm25Index *idx = reinterpret_cast<const Bm25Index *>(index);
+    if (!idx || !generation_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *generation_out = idx->generation.load();
+    return NIDX_OK;
 } NIDX_ABI_CATCH
 
 }  // extern "C"

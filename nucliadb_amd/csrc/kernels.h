@@ -578,6 +578,36 @@ hipError_t launch_bm25_term_floors(const unsigned long long *term_offsets, const
 hipError_t launch_bm25_concat_postings(const unsigned long long *seg_off, uint32_t n_terms, const unsigned long long *dst_start, const uint32_t *src_doc,
                                        const uint32_t *src_tf, unsigned long long n_post, uint32_t doc_base, uint32_t *dst_doc, uint32_t *dst_tf,
                                        hipStream_t s);
+// ---- nidx_gpu_bm25_sync: the resident layout of a new generation from the old one (bm25_sync.hip) ----
+#define BM25_SYNC_SPAN 4096ull   /* items (postings or positions) of one workgroup */
+// items [0, n_items) of one segment, term-major: item j of term t (seg_off[t] <= j < seg_off[t + 1]) goes from index j + src_delta[t]
+// to index j + dst_delta[t] (run start - seg_off[t], modulo 2^64): dst_a = src_a + add_a; dst_b = src_b (NULL: none);
+// dst_pos = src_pos + pos_delta[t] (NULL: none)
+struct Bm25SyncCarry {
+    const unsigned long long *seg_off;   // [n_terms + 1]
+    const unsigned long long *src_delta, *dst_delta, *pos_delta;   // [n_terms]
+    const uint32_t *src_a, *src_b;
+    const unsigned long long *src_pos;
+    uint32_t *dst_a, *dst_b;
+    unsigned long long *dst_pos;
+    unsigned long long n_items;
+    uint32_t n_terms, add_a;
+};
+hipError_t launch_bm25_sync_carry(const Bm25SyncCarry &a, hipStream_t s);
+// segment e of the new generation owns bits [new_base, new_base + n_docs) of the new bitset: bit src_bit0 + i of src, or ones (src NULL)
+struct Bm25SyncAliveSeg {
+    const uint64_t *src;
+    unsigned long long src_bit0, new_base;
+    uint32_t n_docs, reserved;
+};
+hipError_t launch_bm25_sync_alive(const Bm25SyncAliveSeg *segs, uint32_t n_segs, uint32_t n_words, uint64_t *out, hipStream_t s);
+// the documents of postings [begin, end) leave alive32; cleared[segment] += the bits this launch cleared
+struct Bm25SyncDeletion {
+    unsigned long long begin, end;
+    uint32_t segment, reserved;
+};
+hipError_t launch_bm25_sync_deletions(const Bm25SyncDeletion *pairs, uint32_t n_pairs, const uint32_t *doc_ids, uint32_t n_docs, unsigned int *alive32,
+                                      uint32_t *cleared, hipStream_t s);
 // FacetCollector: counts[p] += |postings(term[p]) ∩ match bitset slot[p]|
 hipError_t launch_facet_count(const unsigned long long *term_offsets, const uint32_t *doc_ids, const uint32_t *pair_term,
                               const int *pair_slot, uint32_t n_pairs, const uint32_t *match_bits, uint32_t match_words,
