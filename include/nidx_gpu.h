@@ -56,6 +56,7 @@ int32_t nidx_gpu_abi_version(void);
 /* Bits of optional content this build of the library holds (NIDX_FEATURE_*). */
 #define NIDX_FEATURE_VECTOR_SYNC 1 /* nidx_gpu_vector_sync / nidx_gpu_vector_generation */
 #define NIDX_FEATURE_BM25_SYNC 2 /* nidx_gpu_bm25_sync / nidx_gpu_bm25_generation */
+#define NIDX_FEATURE_VECTOR_MAXSIM_BATCH 4 /* nidx_gpu_vector_search_maxsim_filtered_per_query / _submit* / _wait, nidx_gpu_vector_maxsim_stats */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -312,6 +313,46 @@ int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const floa
                                       uint32_t n_queries, const nidx_gpu_vector_search_params_t *params,
                                       const uint64_t *const *segment_filters, uint32_t *out_segment, uint32_t *out_paragraph,
                                       float *out_score, uint32_t *out_count);
+
+/* ---- search_multi_vector for batches: per-query filters, tickets, second stage on the device -------------------------------
+ * The same search as nidx_gpu_vector_search_maxsim, hit for hit and bit for bit, for the shapes a serving loop has.
+ *   first pass   the flattened query vectors with k1 = max(k, 10), min_score = f32::MIN, duplicates kept, through
+ *                nidx_gpu_vector_search_filtered_per_query (blocking and per-query tickets) or nidx_gpu_vector_search_submit / _wait
+ *                (bitset tickets), with their routing, exact fallback and Fssc.  Query q's filter applies to each of its vectors;
+ *                programs / n_filters / filter_of_query / UINT32_MAX mean what they mean there.  What those entries refuse is refused
+ *                here with their message: k > 512, k1 x (vectors of the largest paragraph) beyond the scan's page, BRUTE_FORCE_MFMA /
+ *                _BF16 with per-query filters.
+ *   second stage one upload of the hit block, ONE launch of maxsim_rerank_kernel for the whole batch and every segment (a workgroup per
+ *                query: de-duplication by paragraph address, maxsim_similarity on the RAW query rows, `> min_score`, order by score
+ *                desc / segment / paragraph, cut to k) and one read-back, on the index's stream once the first pass's hits are final.
+ *                The kernel holds NIDX_MAXSIM_DEVICE_CANDIDATES (2 048) first-pass hits of one query on chip; a query with more (more
+ *                than 204 query vectors at k <= 10) is finished on the host by the stage nidx_gpu_vector_search_maxsim runs — the
+ *                result is the same, nidx_gpu_vector_maxsim_stats counts how often that happened.
+ * query_dimension != dimension: NIDX_ERR_INCONSISTENT_DIMENSIONS.  n_queries == 0, k == 0, no query vectors: counts of 0.
+ * Queries live in host memory.  out_segment / out_paragraph / out_score: [n_queries][k]. */
+int32_t nidx_gpu_vector_search_maxsim_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
+                                                         uint32_t n_queries, uint32_t query_dimension,
+                                                         const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *programs,
+                                                         uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment,
+                                                         uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
+/* The ticket forms.  The ticket is the one of the first pass: maxsim tickets count against "pipeline_depth" together with the other kinds
+ * (NIDX_ERR_BUSY beyond it, nothing searched), hold the generation from submit until waited for (nidx_gpu_vector_sync treats them like
+ * any ticket), and are waited for once, in any order, from any thread.  Queries, offsets, bitsets and programs are copied or read
+ * before submit returns.  The second stage runs inside the wait.  A maxsim ticket handed to nidx_gpu_vector_search_wait, or another
+ * ticket handed to the maxsim wait, returns NIDX_ERR_INVALID_ARGUMENT and stays valid for the wait of its kind. */
+int32_t nidx_gpu_vector_search_maxsim_submit(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
+                                             uint32_t n_queries, uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                             const uint64_t *const *segment_filters, uint64_t *ticket_out);
+int32_t nidx_gpu_vector_search_maxsim_submit_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries,
+                                                                const uint64_t *query_vec_offsets, uint32_t n_queries, uint32_t query_dimension,
+                                                                const nidx_gpu_vector_search_params_t *params,
+                                                                const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                                const uint32_t *filter_of_query, uint64_t *ticket_out);
+int32_t nidx_gpu_vector_search_maxsim_wait(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,
+                                           float *out_score, uint32_t *out_count);
+/* Since open: queries re-ranked by the device stage, and how many of them outgrew its on-chip candidate list and were finished on the
+ * host (either pointer may be NULL). */
+int32_t nidx_gpu_vector_maxsim_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *host_finished_out);
 
 /* nidx_gpu_vector_search_dim with the filter of every segment given as a program (segment_programs:
  * NULL or [n_segments]).  out_matching: NULL or [n_segments] = |filter ∩ alive| per segment. */

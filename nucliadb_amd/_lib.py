@@ -153,6 +153,8 @@ class VectorSyncStatsC(C.Structure):
 
 FEATURE_VECTOR_SYNC = 1   # nidx_gpu_build_features() bit: nidx_gpu_vector_sync / nidx_gpu_vector_generation
 FEATURE_BM25_SYNC = 2     # nidx_gpu_build_features() bit: nidx_gpu_bm25_sync / nidx_gpu_bm25_generation
+FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
+MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
 
 
 class FilterOpC(C.Structure):
@@ -286,6 +288,16 @@ SIGNATURES = {
     "nidx_gpu_vector_extend_hnsw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64]),
     "nidx_gpu_vector_search_maxsim": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(VectorSearchParamsC), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nidx_gpu_vector_search_maxsim_filtered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                     C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nidx_gpu_vector_search_maxsim_submit": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                         C.POINTER(VectorSearchParamsC), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_maxsim_submit_filtered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                            C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32,
+                                                                            C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_maxsim_wait": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nidx_gpu_vector_maxsim_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_quantize": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "nidx_gpu_vector_serialize_quantized": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_serialize_hnsw": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),

@@ -49,6 +49,35 @@ hipError_t launch_merge_topk_segments(const ScanMergeTab *table, uint32_t n_seg,
 hipError_t launch_maxsim(const float *vectors, const float *norm2, uint32_t dp, int similarity, const float *queries,
                          const uint32_t *cand_qfirst, const uint32_t *cand_qnum, const uint32_t *cand_first, const uint32_t *cand_num,
                          uint32_t n_cand, float *out, hipStream_t s);
+// ---- the second stage of search_multi_vector on the device (maxsim.hip): one launch for a whole batch and every segment ----
+#define NIDX_MAXSIM_DEVICE_CANDIDATES 2048   /* first-pass hits of ONE query held in LDS before de-duplication; a query with more is flagged */
+struct MaxsimSegDev {
+    const float *vectors;                   // [n][dp]
+    const float *norm2;                     // [n] WAVE64-order |x|^2
+    const uint32_t *para_first, *para_num;  // [n_paragraphs]; unread when identity
+    uint32_t identity;                      // paragraph p is vector p
+    uint32_t n_paragraphs;
+};
+struct MaxsimRerankArgs {
+    const MaxsimSegDev *segs;      // [n_segs] in HBM, index order
+    uint32_t n_segs, n_queries;
+    const uint32_t *hit_segment;   // [T][k1] the first pass's hits of every query vector
+    const uint32_t *hit_paragraph; // [T][k1]
+    const uint32_t *hit_count;     // [T]
+    uint32_t k1;
+    const uint32_t *query_vec_offsets;   // [n_queries + 1]
+    const float *queries;          // [T][dp] the RAW query rows, zero padded
+    float *query_norm2;            // [T] scratch (cosine): |q|^2 of every query vector, written once per query
+    uint32_t dp;
+    int similarity;
+    float min_score;
+    uint32_t k;                    // <= NIDX_K_MAX
+    uint32_t *out_segment, *out_paragraph;   // [n_queries][k]
+    float *out_score;              // [n_queries][k]
+    uint32_t *out_count;           // [n_queries]
+    uint32_t *out_flag;            // [n_queries] 1 = more than NIDX_MAXSIM_DEVICE_CANDIDATES hits: nothing was written, the host stage finishes it
+};
+hipError_t launch_maxsim_rerank(const MaxsimRerankArgs &a, hipStream_t s);
 hipError_t launch_para_best(const uint32_t *in_vec, const float *in_score, const uint32_t *in_count, uint32_t n_queries, uint32_t k_in,
                             const uint32_t *para_of_vec, uint32_t k, uint32_t *out_vec, float *out_score, uint32_t *out_count,
                             hipStream_t s);

@@ -215,6 +215,15 @@ struct Pipeline {
         std::vector<float> sc;
     };
     std::unordered_map<uint64_t, std::unique_ptr<DoneBatch>> done;
+    // tickets of nidx_gpu_vector_search_maxsim_submit*: the ticket IS the one of the first pass (so it counts against `depth` and holds
+    // the generation like any other); what the second stage needs waits here for nidx_gpu_vector_search_maxsim_wait
+    struct MaxsimBatch {
+        uint32_t nq = 0, k1 = 0;
+        nidx_gpu_vector_search_params_t params{};
+        std::vector<uint64_t> qoff;   // [nq + 1]; all zero when nothing was searched (no query vector, or k == 0)
+        std::vector<float> rows;      // the raw query rows [T][dimension]
+    };
+    std::unordered_map<uint64_t, std::unique_ptr<MaxsimBatch>> maxsim;
     ~Pipeline() {
         for (hipEvent_t e : gate)
             if (e) (void)hipEventDestroy(e);
@@ -293,7 +302,8 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
             // A blocking search (nidx_gpu_vector_search of a multi-segment index) may take one of 4 slots beyond the budget: its caller
             // may itself hold `depth` tickets it has not waited for yet and would otherwise wait here for a slot only it can free;
             // the extra slots are held by blocking calls alone, which give them back by themselves.
-            uint32_t n_busy = 0;
+            // (a ticket submit also counts the per-query tickets whose hits wait in `done`: all kinds share the one budget)
+            uint32_t n_busy = blocking ? 0u : (uint32_t)P.done.size();
             for (auto &s : P.slots) n_busy += s->busy ? 1u : 0u;
             const uint32_t budget = blocking ? P.depth + 4u : P.depth;
             if (n_busy < budget)
@@ -737,6 +747,180 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     return NIDX_OK;
 }
 
+// ---- search_multi_vector for batches (searcher.rs:345-394): first pass through the entries above, second stage on the device ----
+namespace {
+// first-pass parameters (searcher.rs:352-372): max(k, 10) hits per query vector, duplicates kept, no min_score
+nidx_gpu_vector_search_params_t maxsim_first_pass(const nidx_gpu_vector_search_params_t &p) {
+    nidx_gpu_vector_search_params_t p1 = p;
+    p1.k = std::max<uint32_t>(p.k, 10);
+    p1.min_score = -3.40282347e38f;  // f32::MIN
+    p1.with_duplicates = 1;
+    return p1;
+}
+int32_t maxsim_check_offsets(const uint64_t *qoff, uint32_t nq) {
+    if (nq && qoff[0] != 0) return fail(NIDX_ERR_INVALID_ARGUMENT, "query_vec_offsets[0] must be 0");
+    for (uint32_t q = 0; q < nq; q++)
+        if (qoff[q + 1] < qoff[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "query_vec_offsets are not ascending (query %u)", q);
+    if (nq && qoff[nq] > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "more than 2^32 - 1 query vectors in one batch");
+    return NIDX_OK;
+}
+// query q's filter applies to each of its vectors
+void maxsim_filter_of_vector(const uint64_t *qoff, uint32_t nq, const uint32_t *filter_of_query, std::vector<uint32_t> &fov) {
+    fov.resize(qoff[nq]);
+    for (uint32_t q = 0; q < nq; q++)
+        for (uint64_t t = qoff[q]; t < qoff[q + 1]; t++) fov[t] = filter_of_query[q];
+}
+inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+}  // namespace
+
+int32_t VectorIndex::maxsim_rerank(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p, uint32_t k1,
+                                   const uint32_t *hit_segment, const uint32_t *hit_paragraph, const uint32_t *hit_count, uint32_t *out_segment,
+                                   uint32_t *out_paragraph, float *out_score, uint32_t *out_count) {
+    const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const size_t S = segs.size(), T = (size_t)qoff[nq];
+    // ---- one upload: [segment table | offsets | hits: segments, paragraphs, counts | raw query rows] ----
+    const size_t at_off = align16(S * sizeof(MaxsimSegDev)), at_seg = at_off + align16((size_t)(nq + 1) * 4), at_par = at_seg + align16(T * k1 * 4),
+                 at_cnt = at_par + align16(T * k1 * 4), at_rows = at_cnt + align16(T * 4), in_bytes = at_rows + T * dp * 4;
+    NIDX_HIP(pin_maxsim_in.reserve(in_bytes));
+    NIDX_HIP(scratch_maxsim_in.reserve(in_bytes));
+    unsigned char *h = pin_maxsim_in.as<unsigned char>();
+    MaxsimSegDev *tab = reinterpret_cast<MaxsimSegDev *>(h);
+    for (size_t s = 0; s < S; s++) {
+        const VectorSegment &seg = segs[s];
+        tab[s] = MaxsimSegDev{seg.vectors.as<float>(), seg.norm2.as<float>(), seg.identity_para ? nullptr : seg.para_first.as<uint32_t>(),
+                              seg.identity_para ? nullptr : seg.para_num.as<uint32_t>(), seg.identity_para ? 1u : 0u, seg.n_paragraphs};
+    }
+    uint32_t *h_off = reinterpret_cast<uint32_t *>(h + at_off);
+    for (uint32_t q = 0; q <= nq; q++) h_off[q] = (uint32_t)qoff[q];
+    memcpy(h + at_seg, hit_segment, T * k1 * 4);
+    memcpy(h + at_par, hit_paragraph, T * k1 * 4);
+    memcpy(h + at_cnt, hit_count, T * 4);
+    // maxsim uses the vectors as given (searcher.rs:346-350, 384), also on an index that normalises its queries for the first pass
+    stage_query_rows(queries, reinterpret_cast<float *>(h + at_rows), (uint32_t)T, d, dp, false);
+    NIDX_HIP(hipMemcpyAsync(scratch_maxsim_in.p, h, in_bytes, hipMemcpyHostToDevice, stream));
+    // ---- one launch, one read-back: [nq*k segments | nq*k paragraphs | nq*k scores | nq counts | nq flags] ----
+    const size_t out_words = (size_t)nq * k * 3 + (size_t)nq * 2;
+    NIDX_HIP(scratch_maxsim_out.reserve(out_words * 4));
+    NIDX_HIP(pin_maxsim_out.reserve(out_words * 4));
+    NIDX_HIP(scratch_maxsim_qnorm.reserve(std::max<size_t>(T, 1) * 4));
+    const unsigned char *din = scratch_maxsim_in.as<unsigned char>();
+    uint32_t *dout = scratch_maxsim_out.as<uint32_t>();
+    MaxsimRerankArgs a;
+    a.segs = reinterpret_cast<const MaxsimSegDev *>(din);
+    a.n_segs = (uint32_t)S, a.n_queries = nq;
+    a.hit_segment = reinterpret_cast<const uint32_t *>(din + at_seg);
+    a.hit_paragraph = reinterpret_cast<const uint32_t *>(din + at_par);
+    a.hit_count = reinterpret_cast<const uint32_t *>(din + at_cnt);
+    a.k1 = k1;
+    a.query_vec_offsets = reinterpret_cast<const uint32_t *>(din + at_off);
+    a.queries = reinterpret_cast<const float *>(din + at_rows);
+    a.query_norm2 = scratch_maxsim_qnorm.as<float>();
+    a.dp = dp, a.similarity = cfg.similarity, a.min_score = p.min_score, a.k = k;
+    a.out_segment = dout, a.out_paragraph = dout + (size_t)nq * k;
+    a.out_score = reinterpret_cast<float *>(dout + (size_t)nq * k * 2);
+    a.out_count = dout + (size_t)nq * k * 3, a.out_flag = a.out_count + nq;
+    NIDX_HIP(launch_maxsim_rerank(a, stream));
+    NIDX_HIP(hipMemcpyAsync(pin_maxsim_out.p, dout, out_words * 4, hipMemcpyDeviceToHost, stream));
+    NIDX_HIP(hipStreamSynchronize(stream));
+    const uint32_t *o = pin_maxsim_out.as<uint32_t>(), *o_cnt = o + (size_t)nq * k * 3, *o_flag = o_cnt + nq;
+    std::vector<uint32_t> flagged;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (o_flag[q]) { flagged.push_back(q); continue; }
+        const uint32_t c = std::min(o_cnt[q], k);
+        const size_t at = (size_t)q * k;
+        out_count[q] = c;
+        if (out_segment) memcpy(out_segment + at, o + at, (size_t)c * 4);
+        if (out_paragraph) memcpy(out_paragraph + at, o + (size_t)nq * k + at, (size_t)c * 4);
+        if (out_score) memcpy(out_score + at, o + (size_t)nq * k * 2 + at, (size_t)c * 4);
+    }
+    maxsim_queries.fetch_add(nq, std::memory_order_relaxed);
+    if (flagged.empty()) return NIDX_OK;
+    // more first-pass hits than the on-chip list holds: the host stage finishes those queries alone, from the same hits and rows
+    maxsim_host_finished.fetch_add(flagged.size(), std::memory_order_relaxed);
+    return maxsim_host_stage(a.queries, qoff, nq, &flagged, p, k1, hit_segment, hit_paragraph, hit_count, out_segment, out_paragraph, out_score,
+                             out_count);
+}
+
+int32_t VectorIndex::maxsim_blocking(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                     const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
+                                     uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count) {
+    for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
+    if (nq == 0 || p.k == 0) return NIDX_OK;
+    int32_t rc = maxsim_check_offsets(qoff, nq);
+    if (rc != NIDX_OK) return rc;
+    const size_t T = (size_t)qoff[nq];
+    if (T == 0) return NIDX_OK;
+    const nidx_gpu_vector_search_params_t p1 = maxsim_first_pass(p);
+    std::vector<uint32_t> fov;
+    if (filter_of_query) maxsim_filter_of_vector(qoff, nq, filter_of_query, fov);
+    std::vector<uint32_t> s1(T * p1.k), pa1(T * p1.k), c1(T);
+    rc = search_per_query(queries, (uint32_t)T, p1, programs, n_filters, filter_of_query ? fov.data() : nullptr, s1.data(), pa1.data(), nullptr, nullptr,
+                          c1.data(), nullptr, nullptr);
+    if (rc != NIDX_OK) return rc;
+    std::lock_guard<std::mutex> lock(mu);
+    NIDX_HIP(hipSetDevice(device));
+    return maxsim_rerank(queries, qoff, nq, p, p1.k, s1.data(), pa1.data(), c1.data(), out_segment, out_paragraph, out_score, out_count);
+}
+
+int32_t VectorIndex::maxsim_submit(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                   const uint64_t *const *segment_filters, bool per_query, const nidx_gpu_filter_program_t *programs,
+                                   uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out) {
+    int32_t rc = maxsim_check_offsets(qoff, nq);
+    if (rc != NIDX_OK) return rc;
+    auto mb = std::make_unique<Pipeline::MaxsimBatch>();
+    const bool nothing = nq == 0 || p.k == 0 || qoff[nq] == 0;   // the ticket then carries a first pass of no rows
+    const uint32_t T = nothing ? 0u : (uint32_t)qoff[nq];
+    const nidx_gpu_vector_search_params_t p1 = maxsim_first_pass(p);
+    mb->nq = nq, mb->k1 = p1.k, mb->params = p;
+    mb->qoff.assign((size_t)nq + 1, 0);
+    if (!nothing) {
+        mb->qoff.assign(qoff, qoff + nq + 1);
+        mb->rows.assign(queries, queries + (size_t)T * cfg.dimension);
+    }
+    std::vector<uint32_t> fov;
+    if (per_query && filter_of_query && !nothing) maxsim_filter_of_vector(qoff, nq, filter_of_query, fov);
+    uint64_t ticket = 0;
+    rc = per_query ? pipeline_submit_per_query(queries, T, p1, programs, n_filters, fov.empty() ? nullptr : fov.data(), &ticket)
+                   : pipeline_submit(queries, T, p1, segment_filters, false, &ticket);
+    if (rc != NIDX_OK) return rc;
+    std::lock_guard<std::mutex> lk(pipe->mu);
+    pipe->maxsim.emplace(ticket, std::move(mb));
+    *ticket_out = ticket;
+    return NIDX_OK;
+}
+
+bool VectorIndex::is_maxsim_ticket(uint64_t ticket) {
+    std::lock_guard<std::mutex> lk(pipe->mu);
+    return pipe->maxsim.count(ticket) != 0;
+}
+
+int32_t VectorIndex::maxsim_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count) {
+    std::unique_ptr<Pipeline::MaxsimBatch> mb;
+    {
+        std::lock_guard<std::mutex> lk(pipe->mu);
+        auto it = pipe->maxsim.find(ticket);
+        if (it != pipe->maxsim.end()) {
+            mb = std::move(it->second);
+            pipe->maxsim.erase(it);
+        }
+    }
+    if (!mb) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown maxsim ticket %llu (a ticket is waited for once, by the wait of its kind)", (unsigned long long)ticket);
+    // the ticket holds the generation until its first pass has been waited for; the second stage reads `segs` too
+    gate.enter_nested();
+    struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};
+    const uint32_t nq = mb->nq, k1 = mb->k1;
+    const size_t T = (size_t)mb->qoff[nq];
+    std::vector<uint32_t> s1(T * k1), pa1(T * k1), c1(std::max<size_t>(T, 1));
+    const int32_t rc = pipeline_wait(ticket, s1.data(), pa1.data(), nullptr, nullptr, c1.data(), nullptr);
+    if (rc != NIDX_OK) return rc;
+    for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
+    if (T == 0) return NIDX_OK;
+    std::lock_guard<std::mutex> lock(mu);
+    NIDX_HIP(hipSetDevice(device));
+    return maxsim_rerank(mb->rows.data(), mb->qoff.data(), nq, mb->params, k1, s1.data(), pa1.data(), c1.data(), out_segment, out_paragraph, out_score,
+                         out_count);
+}
+
 }  // namespace nidx
 
 using namespace nidx;
@@ -770,7 +954,65 @@ int32_t nidx_gpu_vector_search_wait(nidx_gpu_vector_index_t *index, uint64_t tic
                                     uint32_t *out_vector, float *out_score, uint32_t *out_count, uint32_t *n_retried_out) try {
     VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
     if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (idx->is_maxsim_ticket(ticket))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "ticket %llu belongs to nidx_gpu_vector_search_maxsim_wait", (unsigned long long)ticket);
     return idx->pipeline_wait(ticket, out_segment, out_paragraph, out_vector, out_score, out_count, n_retried_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_maxsim_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
+                                                         uint32_t n_queries, uint32_t query_dimension,
+                                                         const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *programs,
+                                                         uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment,
+                                                         uint32_t *out_paragraph, float *out_score, uint32_t *out_count) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !out_count || !query_vec_offsets || (n_queries && query_vec_offsets[n_queries] && !queries))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    return idx->maxsim_blocking(queries, query_vec_offsets, n_queries, *params, programs, n_filters, filter_of_query, out_segment, out_paragraph,
+                                out_score, out_count);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_maxsim_submit(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
+                                             uint32_t n_queries, uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                             const uint64_t *const *segment_filters, uint64_t *ticket_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !ticket_out || !query_vec_offsets || (n_queries && query_vec_offsets[n_queries] && !queries))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    return idx->maxsim_submit(queries, query_vec_offsets, n_queries, *params, segment_filters, false, nullptr, 0, nullptr, ticket_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_maxsim_submit_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries,
+                                                                const uint64_t *query_vec_offsets, uint32_t n_queries, uint32_t query_dimension,
+                                                                const nidx_gpu_vector_search_params_t *params,
+                                                                const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                                const uint32_t *filter_of_query, uint64_t *ticket_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !ticket_out || !query_vec_offsets || (n_queries && query_vec_offsets[n_queries] && !queries))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    return idx->maxsim_submit(queries, query_vec_offsets, n_queries, *params, nullptr, true, programs, n_filters, filter_of_query, ticket_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_maxsim_wait(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,
+                                           float *out_score, uint32_t *out_count) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    return idx->maxsim_wait(ticket, out_segment, out_paragraph, out_score, out_count);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_maxsim_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *host_finished_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (queries_out) *queries_out = idx->maxsim_queries.load(std::memory_order_relaxed);
+    if (host_finished_out) *host_finished_out = idx->maxsim_host_finished.load(std::memory_order_relaxed);
+    return NIDX_OK;
 } NIDX_ABI_CATCH
 
 }  // extern "C"

@@ -204,6 +204,8 @@ static int32_t open_segment(const nidx_gpu_vector_config_t &cfg, const nidx_gpu_
                 NIDX_HIP(hipMemcpy(seg.para_first.p, first.data(), (size_t)in.n_paragraphs * 4, hipMemcpyHostToDevice));
                 NIDX_HIP(hipMemcpy(seg.para_num.p, num.data(), (size_t)in.n_paragraphs * 4, hipMemcpyHostToDevice));
             }
+            seg.para_first_host = std::move(first);   // kept for the host stage of maxsim
+            seg.para_num_host = std::move(num);
         }
     }
     seg.para_host = pov;
@@ -1832,6 +1834,78 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     return fssc_merge(nq, p, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
 }
 
+// ---- the host stage of search_multi_vector (searcher.rs:373-393): nidx_gpu_vector_search_maxsim's second stage, and what finishes
+//      the queries of a batch whose first-pass hits outgrow the on-chip list of maxsim_rerank_kernel.  Under `mu`, on `stream`. ----
+int32_t VectorIndex::maxsim_host_stage(const float *d_queries, const uint64_t *qoff, uint32_t nq, const std::vector<uint32_t> *which,
+                                       const nidx_gpu_vector_search_params_t &p, uint32_t k1, const uint32_t *hit_segment,
+                                       const uint32_t *hit_paragraph, const uint32_t *hit_count, uint32_t *out_segment, uint32_t *out_paragraph,
+                                       float *out_score, uint32_t *out_count) {
+    const uint32_t k = p.k;
+    const uint32_t n_which = which ? (uint32_t)which->size() : nq;
+    auto query_at = [&](uint32_t w) { return which ? (*which)[w] : w; };
+    // candidates: the paragraphs found by any of the query's vectors, once per ADDRESS (searcher.rs:375-377)
+    struct Cand { uint32_t q, seg, para; };
+    std::vector<Cand> cands;
+    for (uint32_t w = 0; w < n_which; w++) {
+        const uint32_t q = query_at(w);
+        std::vector<std::pair<uint32_t, uint32_t>> found;  // (paragraph address, segment)
+        for (uint64_t t = qoff[q]; t < qoff[q + 1]; t++)
+            for (uint32_t i = 0; i < hit_count[t]; i++) found.emplace_back(hit_paragraph[t * k1 + i], hit_segment[t * k1 + i]);
+        std::sort(found.begin(), found.end());
+        for (size_t i = 0; i < found.size(); i++)
+            if (i == 0 || found[i].first != found[i - 1].first) cands.push_back(Cand{q, found[i].second, found[i].first});
+    }
+    std::vector<float> score(cands.size(), 0.f);
+    for (size_t sgi = 0; sgi < segs.size(); sgi++) {
+        VectorSegment &seg = segs[sgi];
+        std::vector<uint32_t> meta;  // qfirst, qnum, first, num per candidate of this segment
+        std::vector<size_t> where;
+        for (size_t i = 0; i < cands.size(); i++)
+            if (cands[i].seg == sgi) where.push_back(i);
+        if (where.empty()) continue;
+        const size_t n = where.size();
+        meta.resize(4 * n);
+        for (size_t j = 0; j < n; j++) {
+            const Cand &c = cands[where[j]];
+            meta[j] = (uint32_t)qoff[c.q];
+            meta[n + j] = (uint32_t)(qoff[c.q + 1] - qoff[c.q]);
+            meta[2 * n + j] = seg.identity_para ? c.para : seg.para_first_host[c.para];
+            meta[3 * n + j] = seg.identity_para ? 1u : seg.para_num_host[c.para];
+        }
+        NIDX_HIP(scratch_cand_vec.reserve(meta.size() * 4));
+        NIDX_HIP(scratch_cand_score.reserve(n * 4));
+        NIDX_HIP(hipMemcpyAsync(scratch_cand_vec.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, stream));
+        const uint32_t *dm = scratch_cand_vec.as<uint32_t>();
+        NIDX_HIP(launch_maxsim(seg.vectors.as<float>(), seg.norm2.as<float>(), seg.dp, cfg.similarity, d_queries, dm, dm + n, dm + 2 * n, dm + 3 * n,
+                               (uint32_t)n, scratch_cand_score.as<float>(), stream));
+        std::vector<float> sc(n);
+        NIDX_HIP(hipMemcpyAsync(sc.data(), scratch_cand_score.p, n * 4, hipMemcpyDeviceToHost, stream));
+        NIDX_HIP(hipStreamSynchronize(stream));
+        for (size_t j = 0; j < n; j++) score[where[j]] = sc[j];
+    }
+    // `sp.score() > min_score`, sort by score desc, truncate (searcher.rs:381-391)
+    size_t i = 0;
+    for (uint32_t w = 0; w < n_which; w++) {
+        const uint32_t q = query_at(w);
+        std::vector<size_t> mine;
+        for (; i < cands.size() && cands[i].q == q; i++)
+            if (score[i] > p.min_score) mine.push_back(i);
+        std::sort(mine.begin(), mine.end(), [&](size_t a, size_t b) {
+            if (score[a] != score[b]) return score[a] > score[b];
+            if (cands[a].seg != cands[b].seg) return cands[a].seg < cands[b].seg;
+            return cands[a].para < cands[b].para;
+        });
+        const uint32_t n = (uint32_t)std::min<size_t>(mine.size(), k);
+        out_count[q] = n;
+        for (uint32_t j = 0; j < n; j++) {
+            if (out_segment) out_segment[(size_t)q * k + j] = cands[mine[j]].seg;
+            if (out_paragraph) out_paragraph[(size_t)q * k + j] = cands[mine[j]].para;
+            if (out_score) out_score[(size_t)q * k + j] = score[mine[j]];
+        }
+    }
+    return NIDX_OK;
+}
+
 }  // namespace nidx
 
 // =====================================================================================================
@@ -1852,7 +1926,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len) try {
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
-int32_t nidx_gpu_build_features(void) { return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC; }
+int32_t nidx_gpu_build_features(void) { return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH; }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
     if (!count_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "count_out is NULL");
@@ -2134,80 +2208,14 @@ int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const floa
     if (rc != NIDX_OK) return rc;
     std::lock_guard<std::mutex> lock(idx->mu);
     NIDX_HIP(hipSetDevice(idx->device));
-    // candidates: the paragraphs found by any of the query's vectors, once per ADDRESS (searcher.rs:375-377)
-    struct Cand { uint32_t q, seg, para; };
-    std::vector<Cand> cands;
-    for (uint32_t q = 0; q < nq; q++) {
-        std::vector<std::pair<uint32_t, uint32_t>> found;  // (paragraph address, segment)
-        for (uint64_t t = qoff[q]; t < qoff[q + 1]; t++)
-            for (uint32_t i = 0; i < c1[t]; i++) found.emplace_back(pa1[t * k1 + i], s1[t * k1 + i]);
-        std::sort(found.begin(), found.end());
-        for (size_t i = 0; i < found.size(); i++)
-            if (i == 0 || found[i].first != found[i - 1].first) cands.push_back(Cand{q, found[i].second, found[i].first});
-    }
     // raw query vectors on the device (maxsim uses the vectors as given, searcher.rs:346-350,384)
     const uint32_t dp = (d + 3u) & ~3u;
     std::vector<float> qpad((size_t)T * dp, 0.f);
     for (uint64_t t = 0; t < T; t++) memcpy(&qpad[t * dp], queries + t * d, (size_t)d * 4);
     NIDX_HIP(idx->scratch_queries.reserve(qpad.size() * 4));
     NIDX_HIP(hipMemcpyAsync(idx->scratch_queries.p, qpad.data(), qpad.size() * 4, hipMemcpyHostToDevice, idx->stream));
-    std::vector<float> score(cands.size(), 0.f);
-    for (size_t sgi = 0; sgi < idx->segs.size(); sgi++) {
-        VectorSegment &seg = idx->segs[sgi];
-        std::vector<uint32_t> meta;  // qfirst, qnum, first, num per candidate of this segment
-        std::vector<size_t> where;
-        std::vector<uint32_t> first, num;
-        if (!seg.identity_para) {
-            first.assign(seg.n_paragraphs, 0);
-            num.assign(seg.n_paragraphs, 0);
-            for (uint32_t v = 0; v < seg.n; v++) {
-                if (num[seg.para_host[v]] == 0) first[seg.para_host[v]] = v;
-                num[seg.para_host[v]]++;
-            }
-        }
-        for (size_t i = 0; i < cands.size(); i++)
-            if (cands[i].seg == sgi) where.push_back(i);
-        if (where.empty()) continue;
-        const size_t n = where.size();
-        meta.resize(4 * n);
-        for (size_t j = 0; j < n; j++) {
-            const Cand &c = cands[where[j]];
-            meta[j] = (uint32_t)qoff[c.q];
-            meta[n + j] = (uint32_t)(qoff[c.q + 1] - qoff[c.q]);
-            meta[2 * n + j] = seg.identity_para ? c.para : first[c.para];
-            meta[3 * n + j] = seg.identity_para ? 1u : num[c.para];
-        }
-        NIDX_HIP(idx->scratch_cand_vec.reserve(meta.size() * 4));
-        NIDX_HIP(idx->scratch_cand_score.reserve(n * 4));
-        NIDX_HIP(hipMemcpyAsync(idx->scratch_cand_vec.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, idx->stream));
-        const uint32_t *dm = idx->scratch_cand_vec.as<uint32_t>();
-        NIDX_HIP(launch_maxsim(seg.vectors.as<float>(), seg.norm2.as<float>(), seg.dp, idx->cfg.similarity, idx->scratch_queries.as<float>(), dm,
-                               dm + n, dm + 2 * n, dm + 3 * n, (uint32_t)n, idx->scratch_cand_score.as<float>(), idx->stream));
-        std::vector<float> sc(n);
-        NIDX_HIP(hipMemcpyAsync(sc.data(), idx->scratch_cand_score.p, n * 4, hipMemcpyDeviceToHost, idx->stream));
-        NIDX_HIP(hipStreamSynchronize(idx->stream));
-        for (size_t j = 0; j < n; j++) score[where[j]] = sc[j];
-    }
-    // `sp.score() > min_score`, sort by score desc, truncate (searcher.rs:381-391)
-    size_t i = 0;
-    for (uint32_t q = 0; q < nq; q++) {
-        std::vector<size_t> mine;
-        for (; i < cands.size() && cands[i].q == q; i++)
-            if (score[i] > params->min_score) mine.push_back(i);
-        std::sort(mine.begin(), mine.end(), [&](size_t a, size_t b) {
-            if (score[a] != score[b]) return score[a] > score[b];
-            if (cands[a].seg != cands[b].seg) return cands[a].seg < cands[b].seg;
-            return cands[a].para < cands[b].para;
-        });
-        const uint32_t n = (uint32_t)std::min<size_t>(mine.size(), k);
-        out_count[q] = n;
-        for (uint32_t j = 0; j < n; j++) {
-            if (out_segment) out_segment[(size_t)q * k + j] = cands[mine[j]].seg;
-            if (out_paragraph) out_paragraph[(size_t)q * k + j] = cands[mine[j]].para;
-            if (out_score) out_score[(size_t)q * k + j] = score[mine[j]];
-        }
-    }
-    return NIDX_OK;
+    return idx->maxsim_host_stage(idx->scratch_queries.as<float>(), qoff, nq, nullptr, *params, k1, s1.data(), pa1.data(), c1.data(), out_segment,
+                                  out_paragraph, out_score, out_count);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,

@@ -32,6 +32,7 @@ struct VectorSegment {
     DevBuf alive;        // bitset over paragraph addrs (absent when all alive)
     bool identity_para = true, all_alive = true;
     std::vector<uint32_t> para_host;   // empty when identity
+    std::vector<uint32_t> para_first_host, para_num_host;   // host copies of para_first / para_num (the host stage of maxsim); empty when identity
     std::vector<uint64_t> alive_host;  // always present
     uint64_t alive_count = 0;
     std::vector<uint64_t> key_ids;     // Fssc identity of each paragraph (optional)
@@ -166,6 +167,28 @@ struct VectorIndex {
     const uint64_t *pq_filter_table = nullptr;
     uint32_t pq_filter_words = 0;
     DevBuf scratch_pq_table, scratch_pq_operands, scratch_pq_prog, scratch_pq_count, scratch_pq_rows, scratch_pq_queries;
+    // search_multi_vector (searcher.rs:345-394).  The second stage of a batch whose first-pass hits [T][k1] are final, under `mu`:
+    // maxsim_rerank (serving.cpp) = one upload, one launch of maxsim_rerank_kernel over every query and segment, one read-back;
+    // the queries whose hits outgrow NIDX_MAXSIM_DEVICE_CANDIDATES are finished by maxsim_host_stage, the stage of
+    // nidx_gpu_vector_search_maxsim (d_queries: the raw rows [T][dp] in HBM; `which`: the queries to finish, nullptr = all).
+    int32_t maxsim_rerank(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p, uint32_t k1,
+                          const uint32_t *hit_segment, const uint32_t *hit_paragraph, const uint32_t *hit_count, uint32_t *out_segment,
+                          uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
+    int32_t maxsim_host_stage(const float *d_queries, const uint64_t *qoff, uint32_t nq, const std::vector<uint32_t> *which,
+                              const nidx_gpu_vector_search_params_t &p, uint32_t k1, const uint32_t *hit_segment, const uint32_t *hit_paragraph,
+                              const uint32_t *hit_count, uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
+    // the first pass of a maxsim batch through the per-query-filter search / the ticket interface, and its wait (serving.cpp)
+    int32_t maxsim_blocking(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                            const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment,
+                            uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
+    int32_t maxsim_submit(const float *queries, const uint64_t *qoff, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                          const uint64_t *const *segment_filters, bool per_query, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                          const uint32_t *filter_of_query, uint64_t *ticket_out);
+    int32_t maxsim_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
+    bool is_maxsim_ticket(uint64_t ticket);
+    DevBuf scratch_maxsim_in, scratch_maxsim_out, scratch_maxsim_qnorm;
+    PinBuf pin_maxsim_in, pin_maxsim_out;
+    std::atomic<uint64_t> maxsim_queries{0}, maxsim_host_finished{0};   // nidx_gpu_vector_maxsim_stats
     uint64_t spill_queries = 0;  // queries re-run by the exact fallback since open (tunable "spill_queries" reads it)
     bool rabitq_enabled(const VectorSegment &seg) const { return seg.has_quant && !(cfg.flags & NIDX_CONFIG_DISABLE_RABITQ_SEARCH); }
     int32_t quantize(uint32_t segment);

@@ -1079,18 +1079,75 @@ class VectorSearcher:
                 progs.append(None)
         return None if all(p is None for p in progs) else tuple(progs)
 
+    def _programs_c(self, uniq):
+        """The distinct filters of a batch ([filter][segment] (ops, lists) tuples or None) as the C table; (table, keep-alive list)."""
+        S = len(self._segments)
+        progs = (_lib.FilterProgramC * max(1, len(uniq) * S))()
+        keep = []
+        for f, prog in enumerate(uniq):
+            for s, sp in enumerate(prog):
+                if sp is None:
+                    continue
+                ops, lists = sp
+                c_ops = (_lib.FilterOpC * len(ops))(*[_lib.FilterOpC(*o) for o in ops])
+                c_lists = np.array(lists, dtype=np.uint32)
+                keep += [c_ops, c_lists]
+                progs[f * S + s] = _lib.FilterProgramC(C.addressof(c_ops), len(ops), c_lists.ctypes.data if len(lists) else None, len(lists))
+        return progs, keep
+
+    def _search_many_multi_vector(self, requests, prefilters, method: int) -> List[VectorSearchResponse]:
+        """search_many on a VectorCardinality::Multi index: every group of requests with equal (result_per_page, min_score) is one
+        nidx_gpu_vector_search_maxsim_filtered_per_query call, each request with its own filter programs."""
+        d = self.config.dimension
+        out: List[Optional[VectorSearchResponse]] = [None] * len(requests)
+        groups: dict = {}
+        for i, r in enumerate(requests):
+            groups.setdefault((max(0, int(r.result_per_page)), int(np.float32(r.min_score).view(np.uint32))), []).append(i)
+        for members in groups.values():
+            r0 = requests[members[0]]
+            k = max(0, int(r0.result_per_page))
+            rows, qoff = [], [0]
+            for i in members:
+                flat = np.ascontiguousarray(requests[i].vector, dtype=np.float32).reshape(-1)
+                if flat.size == 0 or flat.size % d:
+                    raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS, f"Inconsistent dimensions. Index={d} Vector={flat.size}")
+                rows.append(flat)
+                qoff.append(qoff[-1] + flat.size // d)
+            flat = np.ascontiguousarray(np.concatenate(rows))
+            qoff = np.array(qoff, dtype=np.uint64)
+            uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
+            progs, _keep = self._programs_c(uniq)
+            foq = np.array(filter_of, dtype=np.uint32)
+            B, kk = len(members), max(1, k)
+            out_seg, out_par = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.uint32)
+            out_score, out_count = np.zeros((B, kk), np.float32), np.zeros(B, np.uint32)
+            params = _lib.VectorSearchParamsC(k, float(r0.min_score), 1, method)
+            _lib.check(_lib.lib().nidx_gpu_vector_search_maxsim_filtered_per_query(
+                self._handle, flat.ctypes.data, qoff.ctypes.data, B, d, C.byref(params), progs if uniq else None, len(uniq),
+                foq.ctypes.data, out_seg.ctypes.data, out_par.ctypes.data, out_score.ctypes.data, out_count.ctypes.data))
+            for row, i in enumerate(members):
+                docs = []
+                for j in range(int(out_count[row])):
+                    sg = self._segments[int(out_seg[row, j])]
+                    p = int(out_par[row, j])
+                    md = sg.metadata[p]
+                    docs.append(DocumentScored(sg.keys[p], float(out_score[row, j]), md if md else None, list(sg.labels[p])))
+                out[i] = VectorSearchResponse(docs)
+        return out  # type: ignore[return-value]
+
     def search_many(self, requests: Sequence[VectorSearchRequest], prefilters: Optional[Sequence[PrefilterResult]] = None,
                     method: int = _lib.METHOD_AUTO) -> List[VectorSearchResponse]:
         """[self.search(r, p, method) for r, p in zip(requests, prefilters)] in one native call per group of requests with equal
         (result_per_page, min_score, with_duplicates); every request keeps its own filter (formula, segment formula, operator and
-        prefilter), identical programs share one.  Multi-vector indexes search request by request."""
+        prefilter), identical programs share one.  Multi-vector indexes: one nidx_gpu_vector_search_maxsim_filtered_per_query call per
+        group of equal (result_per_page, min_score)."""
         requests = list(requests)
         prefilters = [None] * len(requests) if prefilters is None else list(prefilters)
         if len(prefilters) != len(requests):
             raise ValueError("one prefilter per request")
         prefilters = [p or PrefilterResult.all() for p in prefilters]
         if self.config.vector_cardinality == VectorCardinality.Multi:
-            return [self.search(r, p, method) for r, p in zip(requests, prefilters)]
+            return self._search_many_multi_vector(requests, prefilters, method)
         d = self.config.dimension
         S = len(self._segments)
         out: List[Optional[VectorSearchResponse]] = [None] * len(requests)
