@@ -57,6 +57,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_SYNC 1 /* nidx_gpu_vector_sync / nidx_gpu_vector_generation */
 #define NIDX_FEATURE_BM25_SYNC 2 /* nidx_gpu_bm25_sync / nidx_gpu_bm25_generation */
 #define NIDX_FEATURE_VECTOR_MAXSIM_BATCH 4 /* nidx_gpu_vector_search_maxsim_filtered_per_query / _submit* / _wait, nidx_gpu_vector_maxsim_stats */
+#define NIDX_FEATURE_BM25_FUZZY_BATCH 8 /* nidx_gpu_bm25_fuzzy_terms_batch */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -836,6 +837,19 @@ int32_t nidx_gpu_bm25_set_dictionary(nidx_gpu_bm25_index_t *index, const uint8_t
  * terms, ascending.  n_out receives the full count even when it exceeds cap. */
 int32_t nidx_gpu_bm25_fuzzy_terms(nidx_gpu_bm25_index_t *index, const uint8_t *query_utf8, uint32_t query_len,
                                   int32_t prefix, uint32_t *out_terms, uint32_t cap, uint32_t *n_out);
+/* The same automaton for a batch of words in one call (the fuzzy half of ParagraphSearcher::suggest, nidx_paragraph/src/reader.rs:58-90,
+ * for every request of a serving batch that found nothing exactly): word w = words_utf8[word_offsets[w] .. word_offsets[w + 1]), with
+ * the prefix DFA when word_prefix[w] != 0.  The dictionary is read once per chunk of up to 256 words, every term is tried against
+ * every word of the chunk, and the lists are compacted on the device.  out_offsets[w] .. out_offsets[w + 1] delimit word w's
+ * accepted term ids, ascending, in the concatenation of all lists; out_offsets is always complete (the prefix sums of the true
+ * counts), out_terms receives the first min(cap, total) ids of the concatenation and *n_total_out = total: call again with a larger
+ * buffer when it exceeds cap.  An empty word and a word of more than 48 code points accept nothing; n_words == 0 and an empty
+ * dictionary give empty lists.  NULL arguments (out_terms may be NULL when cap == 0) and decreasing word_offsets are
+ * NIDX_ERR_INVALID_ARGUMENT.  The call holds the index like nidx_gpu_bm25_fuzzy_terms: it answers for one generation of the
+ * dictionary with respect to nidx_gpu_bm25_sync.  Present when nidx_gpu_build_features() & NIDX_FEATURE_BM25_FUZZY_BATCH. */
+int32_t nidx_gpu_bm25_fuzzy_terms_batch(nidx_gpu_bm25_index_t *index, const uint8_t *words_utf8, const uint64_t *word_offsets,
+                                        const uint8_t *word_prefix, uint32_t n_words, uint64_t *out_offsets, uint32_t *out_terms,
+                                        uint64_t cap, uint64_t *n_total_out);
 
 /* TextReaderService::prefilter (nidx_text/src/reader.rs:148-180): the documents (fields) that satisfy a boolean
  * filter expression, evaluated as bitset algebra on the device.  The expression is what filter_to_query

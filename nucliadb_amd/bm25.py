@@ -308,6 +308,27 @@ class Bm25Searcher:
                 return out[: n.value].copy()
             cap = n.value
 
+    def fuzzy_terms_batch(self, words: Sequence[str], prefix: Sequence[bool]) -> List[np.ndarray]:
+        """fuzzy_terms for a batch of words in one library call (nidx_gpu_bm25_fuzzy_terms_batch): the dictionary is read once per
+        chunk of words and the lists are compacted on the device.  -> one ascending id array per word."""
+        W = len(words)
+        assert len(prefix) == W
+        enc = [w.encode("utf-8") for w in words]
+        woffs = np.zeros(W + 1, np.uint64)
+        woffs[1:] = np.cumsum([len(e) for e in enc])
+        blob = np.frombuffer(b"".join(enc) or b"\0", np.uint8)
+        pre = np.ascontiguousarray([1 if p else 0 for p in prefix], dtype=np.uint8)
+        offs = np.zeros(W + 1, np.uint64)
+        total = C.c_uint64(0)
+        cap = max(1024, 64 * W)
+        while True:
+            out = np.zeros(cap, np.uint32)
+            _lib.check(_lib.lib().nidx_gpu_bm25_fuzzy_terms_batch(self._handle, blob.ctypes.data, woffs.ctypes.data, pre.ctypes.data if W else None, W,
+                                                                  offs.ctypes.data, out.ctypes.data, cap, C.byref(total)))
+            if total.value <= cap:
+                return [out[int(offs[w]): int(offs[w + 1])].copy() for w in range(W)]
+            cap = total.value
+
     def prefilter(self, ops: Sequence[Tuple[int, int, int]], lists: Sequence[int] = (), ranges: Sequence[Tuple[int, Optional[int], Optional[int]]] = (),
                   phrases: Sequence[Sequence[int]] = ()) -> Tuple[np.ndarray, int]:
         """TextReaderService::prefilter (nidx_text/src/reader.rs:148-180) on the device: `ops` is a postfix filter program

@@ -174,6 +174,9 @@ struct Bm25Index {
     // term dictionary (fuzzy expansion) and the scratch of the collectors (under mu, on main.stream)
     DevBuf dict_bytes, dict_offsets, s_fuzzy_q, s_fuzzy_flags;
     bool has_dict = false;
+    // nidx_gpu_bm25_fuzzy_terms_batch: [meta | code points] in, the chunk's bit matrix and counts, [offsets | term ids] out
+    DevBuf s_fzb_in, s_fzb_bits, s_fzb_counts, s_fzb_res;
+    PinBuf h_fzb_in, h_fzb_res;
     DevBuf s_pf_stack, s_pf_lists, s_pf_result, s_pf_blocks, s_pf_total, s_pf_out;  // prefilter
     float last_kernel_ms = 0.f;
     std::vector<std::unique_ptr<Bm25Slot>> slots;   // nidx_gpu_bm25_search_submit / _wait
@@ -623,6 +626,107 @@ int32_t nidx_gpu_bm25_fuzzy_terms(nidx_gpu_bm25_index_t *index, const uint8_t *q
             n++;
         }
     *n_out = n;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// One chunk of a fuzzy batch = one pass over the dictionary (bm25_fuzzy.hip).  A chunk ends at FUZZY_BATCH_MAX_WORDS words or
+// FUZZY_BATCH_MAX_CPS code points (the kernel's LDS staging) or when its bit matrix — one row of ceil(n_terms / 64) words per word —
+// would pass FUZZY_BATCH_BITS_BYTES: 64 MiB holds 256 words against 2 M terms; a dictionary of 10 M terms is read once per 53 words.
+static const size_t FUZZY_BATCH_BITS_BYTES = (size_t)64 << 20;
+// The ids that travel to the host in the same copy as the offsets; a call whose lists are longer fetches the rest in a second copy.
+static const uint64_t FUZZY_BATCH_FIRST_IDS = 1u << 16;
+// The device's id buffer of a first run (64 MiB), whatever capacity the caller offers: 256 words x 1 M terms would otherwise reserve 1 GiB.
+static const uint64_t FUZZY_BATCH_DEVICE_IDS = 1u << 24;
+
+int32_t nidx_gpu_bm25_fuzzy_terms_batch(nidx_gpu_bm25_index_t *index, const uint8_t *words_utf8, const uint64_t *word_offsets,
+                                        const uint8_t *word_prefix, uint32_t n_words, uint64_t *out_offsets, uint32_t *out_terms, uint64_t cap,
+                                        uint64_t *n_total_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !word_offsets || !out_offsets || !n_total_out || (n_words && !word_prefix) || (cap && !out_terms))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t w = 0; w < n_words; w++)
+        if (word_offsets[w + 1] < word_offsets[w]) return fail(NIDX_ERR_INVALID_ARGUMENT, "word_offsets decrease at word %u", w);
+    if (word_offsets[n_words] > word_offsets[0] && !words_utf8) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    *n_total_out = 0;
+    std::fill(out_offsets, out_offsets + (size_t)n_words + 1, 0ull);
+    if (!idx->has_dict) return fail(NIDX_ERR_INVALID_ARGUMENT, "no term dictionary: call nidx_gpu_bm25_set_dictionary first");
+    if (n_words == 0 || idx->n_terms == 0) return NIDX_OK;
+    const uint32_t row_words = (idx->n_terms + 63u) / 64u;
+    const uint32_t max_rows = (uint32_t)std::min<size_t>(FUZZY_BATCH_MAX_WORDS, std::max<size_t>(1, FUZZY_BATCH_BITS_BYTES / ((size_t)row_words * 8)));
+    // unicode scalar values of every word, decoded like the single call's; chunks as they fill
+    struct Chunk { uint32_t first, n, cp_begin, n_cps, n_max; };
+    std::vector<Chunk> chunks;
+    std::vector<uint32_t> meta(n_words), cps, cp;
+    Chunk cur{0, 0, 0, 0, 0};
+    for (uint32_t w = 0; w < n_words; w++) {
+        const uint8_t *query = words_utf8 + word_offsets[w];
+        const uint64_t query_len = word_offsets[w + 1] - word_offsets[w];
+        cp.clear();
+        for (uint64_t i = 0; i < query_len && cp.size() <= FUZZY_BATCH_MAX_CP;) {
+            uint32_t c = query[i];
+            int extra = c < 0x80 ? 0 : (c >> 5) == 6 ? 1 : (c >> 4) == 14 ? 2 : (c >> 3) == 30 ? 3 : 0;
+            if (extra == 1) c &= 0x1f;
+            else if (extra == 2) c &= 0x0f;
+            else if (extra == 3) c &= 0x07;
+            i++;
+            for (int e = 0; e < extra && i < query_len; e++, i++) c = (c << 6) | (query[i] & 0x3f);
+            cp.push_back(c);
+        }
+        if (cp.size() > FUZZY_BATCH_MAX_CP) cp.clear();  // nothing within one edit of an indexed token (<= 40 bytes)
+        const uint32_t n = (uint32_t)cp.size();
+        if (cur.n == max_rows || cur.n_cps + n > FUZZY_BATCH_MAX_CPS) {
+            chunks.push_back(cur);
+            cur = Chunk{w, 0, (uint32_t)cps.size(), 0, 0};
+        }
+        meta[w] = cur.n_cps | (n << 16) | ((n && word_prefix[w]) ? 1u << 24 : 0u);
+        cps.insert(cps.end(), cp.begin(), cp.end());
+        cur.n++;
+        cur.n_cps += n;
+        cur.n_max = std::max(cur.n_max, n);
+    }
+    chunks.push_back(cur);
+    hipStream_t st = idx->main.stream;
+    const size_t in_bytes = ((size_t)n_words + cps.size()) * 4, off_bytes = ((size_t)n_words + 1) * 8;
+    NIDX_HIP(idx->h_fzb_in.reserve(in_bytes));
+    NIDX_HIP(idx->s_fzb_in.reserve(in_bytes));
+    NIDX_HIP(idx->s_fzb_bits.reserve((size_t)std::min<uint32_t>(max_rows, n_words) * row_words * 8));
+    NIDX_HIP(idx->s_fzb_counts.reserve((size_t)n_words * 4));
+    memcpy(idx->h_fzb_in.p, meta.data(), (size_t)n_words * 4);
+    if (!cps.empty()) memcpy(idx->h_fzb_in.as<uint32_t>() + n_words, cps.data(), cps.size() * 4);
+    NIDX_HIP(hipMemcpyAsync(idx->s_fzb_in.p, idx->h_fzb_in.p, in_bytes, hipMemcpyHostToDevice, st));
+    // The id buffer on the device is sized before the total is known: what the caller can take, but no more than
+    // FUZZY_BATCH_DEVICE_IDS at first.  A call whose lists outgrow that (and whose caller has room for them) runs a second time
+    // with a buffer of exactly min(cap, total) ids.
+    const uint64_t want_cap = std::min<uint64_t>(cap, (uint64_t)n_words * idx->n_terms);
+    uint64_t dev_cap = std::min(want_cap, FUZZY_BATCH_DEVICE_IDS), total = 0, filled = 0;
+    for (;;) {
+        NIDX_HIP(idx->s_fzb_res.reserve(off_bytes + std::max<uint64_t>(dev_cap, 1) * 4));
+        unsigned long long *d_off = idx->s_fzb_res.as<unsigned long long>();
+        uint32_t *d_ids = reinterpret_cast<uint32_t *>(idx->s_fzb_res.as<uint8_t>() + off_bytes);
+        NIDX_HIP(hipMemsetAsync(d_off, 0, 8, st));
+        for (const Chunk &c : chunks)
+            NIDX_HIP(launch_fuzzy_batch(idx->dict_bytes.as<uint8_t>(), idx->dict_offsets.as<unsigned long long>(), idx->n_terms,
+                                        idx->s_fzb_in.as<uint32_t>() + c.first, idx->s_fzb_in.as<uint32_t>() + n_words + c.cp_begin, c.n, c.n_cps, c.n_max,
+                                        idx->s_fzb_bits.as<uint64_t>(), idx->s_fzb_counts.as<uint32_t>() + c.first, d_off + c.first, dev_cap, d_ids, st));
+        // one copy, one synchronise: the offsets and the head of the id list
+        const uint64_t first_ids = std::min(dev_cap, FUZZY_BATCH_FIRST_IDS);
+        NIDX_HIP(idx->h_fzb_res.reserve(off_bytes + first_ids * 4));
+        NIDX_HIP(hipMemcpyAsync(idx->h_fzb_res.p, idx->s_fzb_res.p, off_bytes + first_ids * 4, hipMemcpyDeviceToHost, st));
+        NIDX_HIP(hipStreamSynchronize(st));
+        memcpy(out_offsets, idx->h_fzb_res.p, off_bytes);
+        total = out_offsets[n_words];
+        filled = std::min(total, want_cap);
+        if (filled > dev_cap) {
+            dev_cap = filled;
+            continue;
+        }
+        if (filled) memcpy(out_terms, idx->h_fzb_res.as<uint8_t>() + off_bytes, std::min(filled, first_ids) * 4);
+        if (filled > first_ids) NIDX_HIP(hipMemcpy(out_terms + first_ids, d_ids + first_ids, (filled - first_ids) * 4, hipMemcpyDeviceToHost));
+        break;
+    }
+    *n_total_out = total;
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

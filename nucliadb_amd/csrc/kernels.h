@@ -538,6 +538,20 @@ hipError_t launch_bm25_stream(const Bm25Args &a, const uint32_t *items, uint32_t
 // (distance <= 1 in unicode scalar values, transposition = 1 edit; prefix: some prefix of the term)
 hipError_t launch_fuzzy_match(const uint8_t *dict_bytes, const unsigned long long *dict_offsets, uint32_t n_terms,
                               const uint32_t *query_cp, uint32_t n_query_cp, int prefix, uint8_t *flags, hipStream_t s);
+// The same automaton for a chunk of words at once (bm25_fuzzy.hip): word w = cps[meta[w] & 0xffff ..) of (meta[w] >> 16) & 0xff code
+// points (0: accepts nothing), prefix DFA when meta[w] >> 24.  Every term's head is decoded once and tried against every word;
+// bits = scratch of n_words x ceil(n_terms / 64) words, counts = scratch of n_words.  offsets[0] is read (the ids written by the
+// chunks before this one), offsets[1 .. n_words] are written; word w's accepted term ids go, ascending, to out[offsets[w] ..)
+// as far as they lie below `cap`.  A chunk holds at most FUZZY_BATCH_MAX_WORDS words and FUZZY_BATCH_MAX_CPS code points (its LDS
+// staging: 12 KiB of code points + 1 KiB of meta + (n_max + 2) KiB of term heads <= 63 KiB, under the 64 KiB a block gets by default);
+// n_max = the longest word of the chunk.
+#define FUZZY_BATCH_THREADS 256
+#define FUZZY_BATCH_MAX_WORDS 256
+#define FUZZY_BATCH_MAX_CPS 3072
+#define FUZZY_BATCH_MAX_CP 48   /* a longer word is within one edit of no indexed token (RemoveLongFilter: 40 bytes) */
+hipError_t launch_fuzzy_batch(const uint8_t *dict_bytes, const unsigned long long *dict_offsets, uint32_t n_terms, const uint32_t *meta,
+                              const uint32_t *cps, uint32_t n_words, uint32_t n_cps, uint32_t n_max, uint64_t *bits, uint32_t *counts,
+                              unsigned long long *offsets, unsigned long long cap, uint32_t *out, hipStream_t s);
 // set bits -> ascending ids (one block per bitset): out[out_offsets[b] ..), counts[b] = number written
 hipError_t launch_bitset_compact(const uint64_t *bits, uint32_t n_words, uint32_t n_sets, const unsigned long long *out_offsets,
                                  uint32_t *out, uint32_t *counts, hipStream_t s);

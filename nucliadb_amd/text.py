@@ -243,6 +243,11 @@ class _Index:
         """FuzzyTermQuery's automaton over the text field's dictionary, evaluated on the device."""
         return [int(t) for t in self.searcher.fuzzy_terms(word, prefix) if not self.terms[int(t)].startswith("\x00")]
 
+    def fuzzy_terms_batch(self, pairs: Sequence[Tuple[str, bool]]) -> List[List[int]]:
+        """fuzzy_terms for every (word, prefix) pair in one library call."""
+        lists = self.searcher.fuzzy_terms_batch([w for w, _ in pairs], [p for _, p in pairs])
+        return [[int(t) for t in ids if not self.terms[int(t)].startswith("\x00")] for ids in lists]
+
     def facet_children(self, facet: str) -> List[Tuple[str, int]]:
         """(child path, term id) of every direct child of `facet` present in the index"""
         pre = "\x00label:" + facet.rstrip("/") + "/"
@@ -871,6 +876,15 @@ class ParagraphSearchRequest:
 
 
 @dataclass
+class ParagraphSuggestRequest:
+    """nidx_paragraph/src/request_types.rs:53-59"""
+    body: str = ""
+    top_k: int = 0
+    filtering_formula: Optional[object] = None
+    filter_or: bool = False   # FilterOperator::Or
+
+
+@dataclass
 class FormulaLiteral:
     label: str
 
@@ -962,6 +976,7 @@ def parse_query(body: str, stop_words: Optional[Set[str]] = None) -> List[Tuple[
 MIN_FUZZY_LEN = 3          # fuzzy_parser.rs:35
 MIN_FUZZY_PREFIX_LEN = 4   # fuzzy_parser.rs:39
 FUZZY_BOOST = 0.5          # search_query.rs:235-239
+SUGGEST_RESULTS_PER_PAGE = 10   # reader.rs:86
 
 
 class ParagraphSearcher:
@@ -1128,13 +1143,23 @@ class ParagraphSearcher:
         that does not contain the word, scored AllQuery's 1.0: the complement of the term's posting list, on the device."""
         return Clause(0, _lib.OCCUR_SHOULD_GROUP, _lib.CONST_SCORE, boost, term_set=[self._index.term(word)], complement=True)
 
-    def _fuzzy_clauses(self, request: ParagraphSearchRequest, prefilter: Optional[PrefilterResult] = None) -> List[Clause]:
-        """The fuzzy query (fuzzy_parser.rs:52-123 under search_query.rs:200-240)."""
+    @staticmethod
+    def _fuzzy_words(tokens: List[Tuple[str, str]]) -> Dict[int, Tuple[str, bool]]:
+        """token index -> (word, prefix DFA?) of the tokens the fuzzy query expands (fuzzy_parser.rs:35-93): literals of at least
+        MIN_FUZZY_LEN bytes, the last literal as a prefix when it has MIN_FUZZY_PREFIX_LEN; quotes and exclusions stay exact."""
+        last_literal = max((i for i, t in enumerate(tokens) if t[0] == "literal"), default=None)
+        return {i: (w, i == last_literal and len(w.encode("utf-8")) >= MIN_FUZZY_PREFIX_LEN)
+                for i, (kind, w) in enumerate(tokens) if kind == "literal" and len(w.encode("utf-8")) >= MIN_FUZZY_LEN}
+
+    def _fuzzy_clauses(self, request: ParagraphSearchRequest, prefilter: Optional[PrefilterResult] = None, expand=None) -> List[Clause]:
+        """The fuzzy query (fuzzy_parser.rs:52-123 under search_query.rs:200-240).  `expand(word, prefix)` -> the term ids the
+        automaton accepts; None = one fuzzy_terms call per word."""
+        expand = expand or self._index.fuzzy_terms
         tokens = self._tokens(request)
         some = prefilter is not None and prefilter.kind == "Some" and prefilter.fields
         filters_present = bool(request.label_filter) or not request.with_duplicates or request.filtering_formula is not None or bool(some)
         boost = FUZZY_BOOST if filters_present else 1.0  # BoostQuery(0.5) only wraps a multi-clause Boolean (:229-240)
-        last_literal = max((i for i, t in enumerate(tokens) if t[0] == "literal"), default=None)
+        fuzzy_words = self._fuzzy_words(tokens)
         clauses = []
         if not tokens:
             clauses.append(Clause(self._index.term(ALL_DOCS), _lib.OCCUR_MUST, _lib.CONST_SCORE, boost))
@@ -1142,11 +1167,10 @@ class ParagraphSearcher:
             if kind == "excluded":
                 clauses.append(self._excluded(w, boost))
                 continue
-            if kind == "quoted" or len(w.encode("utf-8")) < MIN_FUZZY_LEN:  # quotes stay exact; too short to be fuzzy
+            if i not in fuzzy_words:  # quotes stay exact; too short to be fuzzy
                 clauses.append(self._word_or_phrase(kind, w, boost))
                 continue
-            prefix = i == last_literal and len(w.encode("utf-8")) >= MIN_FUZZY_PREFIX_LEN
-            members = self._index.fuzzy_terms(w, prefix) or [self._index.empty_term]
+            members = expand(*fuzzy_words[i]) or [self._index.empty_term]
             clauses.append(Clause(0, _lib.OCCUR_SHOULD_GROUP, _lib.CONST_SCORE, boost, term_set=members))
         return clauses + self._filters(request, prefilter, boost)
 
@@ -1191,3 +1215,90 @@ class ParagraphSearcher:
         if not response.results and request.result_per_page > 0 and request.min_score == 0.0 and not request.only_faceted:
             response = self._run(request, self._fuzzy_clauses(request, prefilter), True)
         return response
+
+    # ---- suggest ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _suggest_as_search(request: ParagraphSuggestRequest) -> ParagraphSearchRequest:
+        """suggest_query (search_query.rs:148-183) builds what search_query builds for a request without duplicates, label filter
+        and advanced query: Must keyword / fuzzy group, Must TermQuery(repeated_in_field = 0), Must filter query."""
+        return ParagraphSearchRequest(body=request.body, result_per_page=int(request.top_k), with_duplicates=False,
+                                      filtering_formula=request.filtering_formula, filter_or=request.filter_or)
+
+    def _suggest_clauses(self, request: ParagraphSuggestRequest, prefilter: Optional[PrefilterResult] = None, expand=None) -> Tuple[List[Clause], List[Clause]]:
+        """-> (keyword query, fuzzy query) of suggest_query (search_query.rs:148-183).  Both carry Must TermQuery(repeated_in_field =
+        0) whatever else is asked, so the Boolean always has at least two clauses: the AllQuery shortcut of search_query.rs:174-177
+        is never taken and the fuzzy query is always BoostQuery(0.5)."""
+        inner = self._suggest_as_search(request)
+        return self._clauses(inner, prefilter), self._fuzzy_clauses(inner, prefilter, expand)
+
+    def _suggest_response(self, request: ParagraphSuggestRequest, r, row: int, obtained: int, fuzzy: bool) -> ParagraphSearchResponse:
+        """search_response.rs:218-311 with results_per_page = 10 and min_score = 0 (reader.rs:78-89): total = the hits obtained."""
+        scores = [float(r["score"][row, i]) for i in range(obtained)]
+        results = []
+        for i in range(min(obtained, SUGGEST_RESULTS_PER_PAGE)):
+            addr = int(r["docaddr"][row, i])
+            d = self._index.doc(addr)
+            results.append(ParagraphResult(d.uuid, d.field, d.text, ResultScore(scores[i], addr), list(d.labels)))
+        next_page = sum(1 for s in scores if s > 0.0) > SUGGEST_RESULTS_PER_PAGE
+        return ParagraphSearchResponse(obtained, results, next_page, request.body, {}, fuzzy)
+
+    def suggest_batch(self, requests: Sequence[ParagraphSuggestRequest],
+                      prefilters: Optional[Sequence[Optional[PrefilterResult]]] = None) -> List[ParagraphSearchResponse]:
+        """ParagraphReaderService::suggest (reader.rs:58-90) for a batch of type-ahead requests in at most three library calls: every
+        keyword query in one search (TopDocs of the largest top_k: a larger TopDocs has the smaller one as its prefix), the fuzzy
+        expansion of every distinct (word, prefix) of the requests that found nothing in one fuzzy_terms_batch, their fuzzy queries
+        in one search.  top_k == 0 asks for nothing (query_planner/suggest.rs:36-39) and a prefilter of kind None matches nothing:
+        both are answered without a search."""
+        n = len(requests)
+        prefilters = [None] * n if prefilters is None else list(prefilters)
+        assert len(prefilters) == n
+        out: List[Optional[ParagraphSearchResponse]] = [None] * n
+        live = []
+        for i, (rq, pf) in enumerate(zip(requests, prefilters)):
+            if int(rq.top_k) <= 0 or (pf is not None and pf.kind == "None"):
+                out[i] = ParagraphSearchResponse(0, [], False, rq.body, {}, False)
+            else:
+                live.append(i)
+        if not live:
+            return out
+        inner = {i: self._suggest_as_search(requests[i]) for i in live}
+        r = self._index.searcher.search_batch_ex([self._clauses(inner[i], prefilters[i]) for i in live], max(int(requests[i].top_k) for i in live))
+        missed = []
+        for row, i in enumerate(live):
+            obtained = min(int(r["count"][row]), int(requests[i].top_k))
+            if obtained:
+                out[i] = self._suggest_response(requests[i], r, row, obtained, False)
+            else:
+                missed.append(i)
+        if not missed:
+            return out
+        # the words to expand, each distinct (word, prefix) once
+        pairs: Dict[Tuple[str, bool], List[int]] = {}
+        for i in missed:
+            for key in self._fuzzy_words(self._tokens(inner[i])).values():
+                pairs[key] = []
+        if pairs:
+            keys = list(pairs)
+            for key, members in zip(keys, self._index.fuzzy_terms_batch(keys)):
+                pairs[key] = members
+        fuzzy = [self._fuzzy_clauses(inner[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in missed]
+        r = self._index.searcher.search_batch_ex(fuzzy, max(int(requests[i].top_k) for i in missed))
+        for row, i in enumerate(missed):
+            out[i] = self._suggest_response(requests[i], r, row, min(int(r["count"][row]), int(requests[i].top_k)), True)
+        return out
+
+    def suggest(self, request: ParagraphSuggestRequest, prefilter: Optional[PrefilterResult] = None) -> ParagraphSearchResponse:
+        """ParagraphSearcher::suggest (lib.rs:148-156, reader.rs:58-90): TopDocs(top_k) of the keyword query; when it has no hit at
+        all, TopDocs(top_k) of the fuzzy query instead."""
+        return self.suggest_batch([request], [prefilter])[0]
+
+
+def split_suggest_query(query: str, max_group: int = 3) -> List[str]:
+    """split_suggest_query (src/searcher/query_planner/suggest.rs:87-102): the queries made of the last 1 .. max_group words of
+    `query`, the longest first; a query of fewer words leaves the remaining entries empty."""
+    words = query.split(" ")[-max_group:] if max_group > 0 else []
+    prefixes = [""] * max_group
+    for index, word in enumerate(words):
+        for p in range(index + 1):
+            prefixes[p] = prefixes[p] + " " + word if prefixes[p] else word
+    return prefixes
