@@ -108,13 +108,17 @@ __device__ inline unsigned long long bs_ld_u64(const unsigned long long *p) { re
 // What the fence is for — making earlier NON-atomic stores visible, keeping later NON-atomic loads from stale lines — is not needed when every
 // value that crosses workgroups is moved by agent-scope atomic accesses (sc1: written through / read past the non-coherent levels, the LLVM AMDGPU
 // memory model's code for monotonic agent-scope stores and loads): the producer's atomic stores only have to be COMPLETE before its arrival is
-// (s_waitcnt vmcnt(0): what the workgroup-scope release fence below compiles to, and it pins the compiler's order), the consumer's atomic loads are
-// issued after its arrival returned.  bs_st_* / bs_ld_* are those accesses; nothing else crosses.
+// issued, the consumer's atomic loads are issued after its arrival returned.  bs_st_* / bs_ld_* are those accesses; nothing else crosses.
+// "Complete" is an explicit `s_waitcnt vmcnt(0)` in bs_arrive_last.  The workgroup-scope release fence in front of it does NOT emit one: outside
+// tgsplit mode the waves of a workgroup share an L1, so the memory model gives that fence `s_waitcnt lgkmcnt(0)` alone — it only pins the
+// compiler's order.  Without the wait the arrival could be performed at L2 before the sc1 stores were written through, and the wave that saw
+// the completed count could load stale keys, counts or totals (DESIGN-LOG R10.1;tests/test_bm25_fused_handover_cpu.py reads the compiled code).
 __device__ inline void bs_st_u32(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void bs_st_u64(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // one more arrival at `counter`; true for the arrival that completes `n` (it resets the counter: nobody else touches it during this launch)
 __device__ inline bool bs_arrive_last(uint32_t *counter, uint32_t n, int lane) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's atomic stores have completed before its arrival is issued
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the compiler keeps this wave's atomic stores in front of its arrival ...
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // ... and they have completed before the arrival is issued
     uint32_t old = 0;
     if (lane == 0) old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     old = bs_rl(old, 0);

@@ -1,0 +1,365 @@
+"""Directed tests of the merge inside bm25_stream_kernel (kernels.h: Bm25FusedMerge; bm25_stream.hip: bs_fused_merge / bs_arrive_last) at the
+slice counts where it changes shape: one slice, a group of one next to full groups, exactly 8 / 9, 64 / 65, 255 / 256 slices, the
+BM25_MAX_SLICES cap, slices and whole groups without a hit, the seg_base search at segment borders, and the arrival counters when a query
+slot changes its slice count from one launch to the next.
+
+NIDX_GPU_BM25_UNION=2 sends every query through the stream kernel and NIDX_GPU_BM25_SLICE=256 pins the slice length at its minimum, so a
+one-clause query over a list of L postings is cut into min(256, ceil(L / 256)) slices (n_slices below).  The corpus has one term per target
+slice count, laid out five ways; documents are at most 40 tokens long (exact fieldnorm ids), every query scores with TF_BASIC, so a
+score falls strictly with the document's length and the expected page is plain numpy: the term's documents by (length, doc id), cut at k.
+Score bits come from the oracle; every answer is also compared byte for byte with the two-launch path (NIDX_GPU_BM25_FUSED_MERGE=0)."""
+import time
+
+import numpy as np
+import pytest
+
+from nucliadb_amd import _lib
+from nucliadb_amd.bm25 import Bm25Searcher, Bm25Segment, Clause
+
+pytestmark = pytest.mark.gpu
+S, M = _lib.OCCUR_SHOULD, _lib.OCCUR_MUST
+BASIC = _lib.TF_BASIC
+SLICE = 256        # NIDX_GPU_BM25_SLICE (bm25_index.cpp clamps it to >= 256)
+MAX_SLICES = 256   # kernels.h: BM25_MAX_SLICES
+GROUP = 8          # kernels.h: BM25_FUSE_GROUP
+
+N_DOCS = 66_560
+COUNTS = (1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 249, 255, 256)
+# the counts just above a boundary of the merge (one slice | several, one group | two, two | three, eight | nine, 255 | 256) get the SHORTEST
+# list that still has that many slices, 256 * n - 255 postings; the others the longest, 256 * n
+LOWER_EDGE = (2, 9, 17, 65, 256)
+# five terms per count.  first / last / groups: postings spread evenly over the corpus, the winners (documents shorter than all others, of
+# distinct lengths) all in the first slice, all in the last slice, or one per group of eight slices, round-robin.  low / high: every posting
+# in the lowest / highest doc ids, so that the other slices — and, from 63 slices on, whole groups — hand over empty lists; for "high" with
+# 9, 17, 65 and 249 slices the last slice, which always has hits, is a group of one.
+LAYOUTS = ("first", "last", "groups", "low", "high")
+N_WINNERS = 12
+WINNER_LEN = 20    # winners are 20 .. 31 tokens long, the other documents 33 .. 40
+
+
+def n_slices(list_lens, n_docs):
+    """Slices of a plain query with these (distinct) terms' list lengths under NIDX_GPU_BM25_UNION=2 and NIDX_GPU_BM25_SLICE=256 — a restatement
+    of bm25_index.cpp, bm25_search_locked ("work list: every query cut into doc-id slices"): slices = min(BM25_MAX_SLICES, max(1, ceil(weigh(p,
+    longest) / slice_now))) with weigh(p, longest) = p while the slice is pinned (short_weight stays 1), then for a union query
+    slices = min(BM25_MAX_SLICES, max(slices, want)), want = ceil(shared * 2 / 96), shared = (sum^2 - sum of squares) / 2 / n_docs."""
+    p = int(sum(list_lens))
+    slices = min(MAX_SLICES, max(1, (p + SLICE - 1) // SLICE))
+    shared = (float(p) * float(p) - float(sum(float(l) * float(l) for l in list_lens))) * 0.5 / max(1.0, float(n_docs))
+    return int(min(float(MAX_SLICES), max(float(slices), float(np.ceil(shared * 2.0 / 96.0)))))
+
+
+def slice_range(s, n, n_docs):
+    """documents of slice s of n (bm25_stream.hip: lo_doc / hi_doc)"""
+    return n_docs * s // n, n_docs * (s + 1) // n
+
+
+def bits(a):
+    return np.asarray(a, np.float32).view(np.uint32)
+
+
+def same(a, b):
+    return all(np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8)) for x, y in zip(a, b))
+
+
+def pin(monkeypatch, fused=True):
+    monkeypatch.setenv("NIDX_GPU_BM25_UNION", "2")
+    monkeypatch.setenv("NIDX_GPU_BM25_SLICE", str(SLICE))
+    if fused:
+        monkeypatch.delenv("NIDX_GPU_BM25_FUSED_MERGE", raising=False)
+    else:
+        monkeypatch.setenv("NIDX_GPU_BM25_FUSED_MERGE", "0")
+
+
+def docs_from_postings(postings, doc_len, filler):
+    """docs[d] = term ids of document d: the terms whose posting list holds d, then `filler` up to doc_len[d] tokens"""
+    n = doc_len.size
+    member = np.zeros(n, np.int64)
+    for d in postings:
+        member[d] += 1
+    assert (member <= doc_len).all()
+    doc = np.concatenate([np.asarray(d, np.int64) for d in postings] + [np.repeat(np.arange(n, dtype=np.int64), doc_len - member)])
+    term = np.concatenate([np.full(len(d), t, np.int64) for t, d in enumerate(postings)] + [np.full(int((doc_len - member).sum()), filler, np.int64)])
+    order = np.argsort(doc, kind="stable")
+    return np.split(term[order], np.cumsum(doc_len)[:-1])
+
+
+class Edges:
+    """The corpus, the numpy model of every term's page and the oracle's score bits (computed once, at k = 64: a page is a prefix of it)."""
+
+    def __init__(self, orc):
+        rng = np.random.default_rng(20251018)
+        n = N_DOCS
+        self.term = {}       # (count, layout) -> term id
+        self.postings = []   # term id -> ascending doc ids
+        reserved = np.zeros(n, bool)
+        winners = {}         # term id -> its N_WINNERS reserved documents
+        # pass 1: the winners of the spread terms.  A reserved document belongs to ONE spread term, so the placement of that term's winners is
+        # what the layout says (the contiguous low / high lists and the every-document term take the winners that fall into them)
+        for c in COUNTS:
+            for layout in LAYOUTS:
+                self.term[(c, layout)] = len(self.postings)
+                self.postings.append(None)
+            n_groups = (c + GROUP - 1) // GROUP
+            for layout in ("first", "last", "groups"):
+                mine = []
+                for j in range(N_WINNERS):
+                    if layout == "groups":
+                        g = j % n_groups
+                        g_n = min(GROUP, c - g * GROUP)
+                        sl = g * GROUP + (5 * j) % g_n
+                    else:
+                        sl = 0 if layout == "first" else c - 1
+                    lo, hi = slice_range(sl, c, n)
+                    free = lo + np.nonzero(~reserved[lo:hi])[0]
+                    # the slice's first free document, its last one, then evenly between them: winners sit ON the slice borders
+                    d = int(free[0] if j % 3 == 0 else free[-1] if j % 3 == 1 else free[(len(free) * (j + 1)) // (N_WINNERS + 2)])
+                    reserved[d] = True
+                    mine.append(d)
+                winners[self.term[(c, layout)]] = np.array(mine, np.int64)
+        free = np.nonzero(~reserved)[0]
+        self.list_len = {}
+        for c in COUNTS:
+            L = SLICE * c - (SLICE - 1 if c in LOWER_EDGE else 0)
+            assert n_slices([L], n) == c
+            for layout in LAYOUTS:
+                t = self.term[(c, layout)]
+                if layout == "low":
+                    d = np.arange(L, dtype=np.int64)
+                elif layout == "high":
+                    d = np.arange(n - L, n, dtype=np.int64)
+                else:
+                    m = L - N_WINNERS   # evenly over the free documents, at a phase of the term's own
+                    rest = free[((np.arange(m) + rng.random()) * free.size / m).astype(np.int64)]
+                    d = np.sort(np.concatenate([rest, winners[t]]))
+                assert d.size == L and np.unique(d).size == L
+                self.postings[t] = d
+                self.list_len[t] = L
+        # what the layouts promise, in terms of the two helpers above
+        for c in (63, 64, 65, 249):
+            hit = {int(x) * c // n for x in self.postings[self.term[(c, "low")]][[0, -1]]}
+            assert max(hit) < c - GROUP, "low: the last group hands over an empty list"
+        for c in (9, 17, 65, 249):
+            assert (c - 1) % GROUP == 0 and self.postings[self.term[(c, "high")]][-1] >= slice_range(c - 1, c, n)[0]   # a group of one, with hits
+        assert self.postings[self.term[(9, "high")]][0] >= slice_range(8, 9, n)[0]   # ... and here nobody else has any
+        self.every = len(self.postings)   # a term of every document: more than 256 * 256 postings, the count is capped
+        self.postings.append(np.arange(n, dtype=np.int64))
+        assert (n + SLICE - 1) // SLICE > MAX_SLICES and n_slices([n], n) == MAX_SLICES
+        # a rare term for the pages with fewer hits than k: five documents of the 65-slice "groups" list, two outside it
+        long_list = self.postings[self.term[(65, "groups")]]
+        inside = long_list[~reserved[long_list]]
+        outside = np.setdiff1d(free, long_list)
+        self.rare = len(self.postings)
+        self.postings.append(np.sort(np.concatenate([inside[[0, 1, inside.size // 3, inside.size // 2, -1]], outside[[7, -7]]])))
+        filler = len(self.postings)
+        member = np.zeros(n, np.int64)
+        for d in self.postings:
+            member[d] += 1
+        doc_len = np.maximum(rng.integers(33, 41, n), member)
+        perm = rng.permutation(N_WINNERS)   # the winners' ranks do not follow their doc ids
+        for t, w in winners.items():
+            doc_len[w] = WINNER_LEN + perm
+        assert doc_len.max() <= 40 and (member <= doc_len).all(), (int(doc_len.max()), int(member.max()))
+        self.doc_len = doc_len
+        self.n_terms = filler + 1
+        self.seg = Bm25Segment.from_term_docs(docs_from_postings(self.postings, doc_len, filler), self.n_terms)
+        assert np.array_equal(self.seg.fieldnorm_ids, doc_len.astype(np.uint8))
+        for t, d in enumerate(self.postings):
+            assert np.array_equal(self.seg.doc_ids[int(self.seg.term_offsets[t]): int(self.seg.term_offsets[t + 1])], d)
+        self.oidx = orc.Bm25Index(self.seg.term_offsets, self.seg.doc_ids, self.seg.tfs, self.seg.fieldnorm_ids, self.seg.total_num_tokens, None)
+        self._want = {}
+
+    def want(self, terms, k):
+        """(docs, score bits, total) of the query Must(term) for every term in `terms` (one term: the plain query), TF_BASIC"""
+        key = tuple(terms)
+        if key not in self._want:
+            d = self.postings[key[0]]
+            for t in key[1:]:
+                d = np.intersect1d(d, self.postings[t])
+            page = d[np.lexsort((d, self.doc_len[d]))][:64]   # length ascending, doc id ascending
+            od, os_, ot = self.oidx.search([(t, M if len(key) > 1 else S, BASIC, 1.0) for t in key], 64)
+            assert ot == d.size and np.array_equal(od, page), ("the model and the oracle disagree", key)
+            self._want[key] = (page, bits(os_), int(d.size))
+        page, sb, total = self._want[key]
+        return page[:k], sb[:k], total
+
+    def query(self, terms):
+        return [Clause(int(t), M if len(terms) > 1 else S, BASIC) for t in terms]
+
+    def check(self, got, term_sets, k):
+        docaddr, score, count, total, postings = got
+        for i, terms in enumerate(term_sets):
+            wd, ws, wt = self.want(terms, k)
+            assert total[i] == wt, (i, terms, int(total[i]), wt)
+            assert count[i] == wd.size, (i, terms, int(count[i]), wd.size)
+            assert np.array_equal(docaddr[i, : wd.size], wd.astype(np.uint64)), (i, terms, docaddr[i, : wd.size], wd)
+            assert np.array_equal(bits(score[i, : wd.size]), ws), (i, terms)
+            assert postings[i] == sum(self.list_len.get(t, self.postings[t].size) for t in terms), (i, terms)
+
+
+@pytest.fixture(scope="module")
+def edges(orc):
+    return Edges(orc)
+
+
+@pytest.fixture(scope="module")
+def searcher(edges):
+    s = Bm25Searcher.open([edges.seg])
+    yield s
+    s.close()
+
+
+@pytest.mark.parametrize("k", [1, 20, 63, 64])
+def test_every_slice_count_layout_and_winner_placement(edges, searcher, monkeypatch, k):
+    """All 71 terms in one batch: 14 slice counts x 5 layouts and the capped every-document term, against the model (hits, count, total), the
+    oracle (score bits) and the two-launch path (byte for byte)."""
+    term_sets = [(edges.term[(c, layout)],) for c in COUNTS for layout in LAYOUTS] + [(edges.every,)]
+    queries = [edges.query(t) for t in term_sets]
+    pin(monkeypatch)
+    fused = searcher.search_batch(queries, k)
+    edges.check(fused, term_sets, k)
+    pin(monkeypatch, fused=False)
+    assert same(fused, searcher.search_batch(queries, k))
+
+
+def test_tie_storm_across_slices_and_groups(orc, monkeypatch):
+    """Every document has the same length, so every posting of a term scores the same and the LOWEST doc ids must win.  The term has five
+    postings in each of its first 31 slices (the rest of the list sits at the top of the corpus): a page of 64 is put together from the first
+    13 slices, two groups, and every other slice and group offers candidates of exactly the winning score that must lose."""
+    n, c = 40_000, 65
+    L = SLICE * c
+    sparse = np.concatenate([slice_range(s, c, n)[0] + 10 * np.arange(5) for s in range(31)])
+    term0 = np.concatenate([sparse, np.arange(n - (L - sparse.size), n)]).astype(np.int64)
+    assert np.unique(term0).size == L and n_slices([L], n) == c and np.all(np.diff(term0) > 0)
+    every = np.arange(n, dtype=np.int64)   # ceil(40 000 / 256) = 157 slices
+    seg = Bm25Segment.from_term_docs(docs_from_postings([term0, every], np.full(n, 6, np.int64), 2), 3)
+    oidx = orc.Bm25Index(seg.term_offsets, seg.doc_ids, seg.tfs, seg.fieldnorm_ids, seg.total_num_tokens, None)
+    s = Bm25Searcher.open([seg])
+    queries = [[Clause(0, S, BASIC)], [Clause(1, S, BASIC)]]
+    for k in (1, 20, 63, 64):
+        pin(monkeypatch)
+        got = s.search_batch(queries, k)
+        for i, d in enumerate((term0, every)):
+            assert got[2][i] == k and got[3][i] == d.size and got[4][i] == d.size
+            assert np.array_equal(got[0][i], d[:k].astype(np.uint64)), (k, i, got[0][i])
+            _, os_, _ = oidx.search([(i, S, BASIC, 1.0)], k)
+            assert np.array_equal(bits(got[1][i]), bits(os_)) and np.unique(bits(os_)).size == 1
+        pin(monkeypatch, fused=False)
+        assert same(got, s.search_batch(queries, k))
+    s.close()
+
+
+def test_fewer_hits_than_k_over_many_slices(edges, searcher, monkeypatch):
+    """Must(long list) AND Must(a term of seven documents): the long list sets the slice count, at most seven slices have a hit, and the
+    other slices and whole groups hand over empty lists (valid == false, c_mine == 0).  count < k, total and postings are checked."""
+    term_sets = [(edges.term[(65, "groups")], edges.rare), (edges.every, edges.rare), (edges.term[(249, "first")], edges.rare),
+                 (edges.term[(17, "low")], edges.rare), (edges.term[(64, "high")], edges.rare)]
+    for terms in term_sets:
+        assert n_slices([edges.postings[t].size for t in terms], N_DOCS) >= 17
+    assert edges.want(term_sets[0], 64)[2] == 5 and edges.want(term_sets[1], 64)[2] == 7
+    queries = [edges.query(t) for t in term_sets]
+    for k in (20, 64):
+        pin(monkeypatch)
+        got = searcher.search_batch(queries, k)
+        assert (got[2] < k).all()
+        edges.check(got, term_sets, k)
+        pin(monkeypatch, fused=False)
+        assert same(got, searcher.search_batch(queries, k))
+
+
+def test_counters_when_a_slot_changes_its_slice_count(edges, monkeypatch):
+    """The arrival counters are per query SLOT and whoever completes a count resets it: consecutive batches on one searcher in which slot 0
+    takes 9, then 17, then 1, then 256 slices (the other slots change as well) must each be right, and equal to a fresh searcher's answer."""
+    pin(monkeypatch)
+    s = Bm25Searcher.open([edges.seg])
+    for c0, c1, c2 in ((9, 65, 8), (17, 1, 249), (1, 256, 9), (256, 7, 17)):
+        term_sets = [(edges.term[(c0, "groups")],), (edges.term[(c1, "low")],), (edges.term[(c2, "high")],)]
+        queries = [edges.query(t) for t in term_sets]
+        got = s.search_batch(queries, 20)
+        edges.check(got, term_sets, 20)
+        fresh = Bm25Searcher.open([edges.seg])
+        assert same(got, fresh.search_batch(queries, 20))
+        fresh.close()
+    s.close()
+
+
+def test_repeated_batches_give_the_same_bytes(edges, searcher, monkeypatch):
+    """Batches of 64 queries of 17, 65 and 256 slices each, repeated for about two seconds in all; every repetition byte for byte like the
+    first, which is checked against the model.  This CANNOT prove that the hand-over is ordered — a missing wait loses a race of a few hundred
+    cycles once in very many launches, if ever; tests/test_bm25_fused_handover_cpu.py is the guard for that.  It only keeps a gross regression
+    (a hand-over that is usually wrong) from passing."""
+    pin(monkeypatch)
+    for c in (17, 65, 256):
+        term_sets = [(edges.term[(c, LAYOUTS[i % len(LAYOUTS)])],) for i in range(64)]
+        queries = [edges.query(t) for t in term_sets]
+        first = searcher.search_batch(queries, 20)
+        edges.check(first, term_sets, 20)
+        reps, t_end = 0, time.monotonic() + 0.65
+        while time.monotonic() < t_end:
+            assert same(first, searcher.search_batch(queries, 20)), (c, reps)
+            reps += 1
+        assert reps >= 1
+
+
+def test_segment_borders_and_an_empty_segment(orc, monkeypatch):
+    """Three segments resident as one, the middle one empty (seg_base = 0, 5 000, 5 000, 10 000): the fused merge turns a resident doc into
+    (segment, doc) with its own binary search.  The best four documents are the first and the last of each non-empty segment; 40 slices, five
+    groups.  Fused against the oracle's searcher over the same segments and against the two-launch path: out_seg, out_doc, scores."""
+    rng = np.random.default_rng(7)
+    n_a = n_c = 5_000
+    n = n_a + n_c
+    doc_len = rng.integers(12, 21, n)
+    doc_len[[0, n_a - 1, n_a, n - 1]] = [5, 3, 4, 2]
+    every = np.arange(n, dtype=np.int64)
+    some = np.sort(np.concatenate([[0, n_a - 1, n_a, n - 1], 1 + rng.choice(n_a - 2, 1020, replace=False), n_a + 1 + rng.choice(n_c - 2, 1024, replace=False)]))
+    assert n_slices([n], n) == 40 and n_slices([some.size], n) == 8
+    docs = docs_from_postings([every, some], doc_len, 2)
+    segs = [Bm25Segment.from_term_docs(docs[:n_a], 3), Bm25Segment.from_term_docs([], 3), Bm25Segment.from_term_docs(docs[n_a:], 3)]
+    osr = orc.Bm25Searcher([orc.Bm25Index(g.term_offsets, g.doc_ids, g.tfs, g.fieldnorm_ids, g.total_num_tokens, None) for g in segs])
+    s = Bm25Searcher.open(segs)
+    queries = [[Clause(0, S, BASIC)], [Clause(1, S, BASIC)], [Clause(0, M, BASIC), Clause(1, M, BASIC)]]
+    for k in (1, 4, 20, 64):
+        pin(monkeypatch)
+        got = s.search_batch(queries, k)
+        for i, q in enumerate(queries):
+            wd, ws, _, wt, _ = osr.search_ex([(cl.term, cl.occur, cl.mode, cl.boost) for cl in q], k)
+            assert got[3][i] == wt and got[2][i] == len(wd) == k
+            assert np.array_equal(got[0][i], wd), (k, i, got[0][i], wd)
+            assert np.array_equal(bits(got[1][i]), bits(ws)), (k, i)
+            assert [int(a) for a in got[0][i, : min(k, 4)]] == [(2 << 32) | (n_c - 1), n_a - 1, 2 << 32, 0][: min(k, 4)]
+        pin(monkeypatch, fused=False)
+        assert same(got, s.search_batch(queries, k))
+    s.close()
+
+
+def test_crowded_shape_changes_no_result(orc, monkeypatch):
+    """One batch of 200 plain union queries through submit / wait with floors and the fused merge at their defaults, cut for a GPU of its own
+    (NIDX_GPU_BM25_CROWDED=0) and for a crowded one (=1: up to 8 192 postings per slice): hits, score bits, counts and totals are the same bit
+    for bit, and the oracle's.  out_postings is documented as the postings scored (include/nidx_gpu.h), whatever the slicing: the sum of the
+    query's list lengths in both shapes."""
+    rng = np.random.default_rng(31)
+    n, vocab = 40_000, 3_000
+    lens = np.clip(np.round(rng.lognormal(np.log(24), 0.5, n)), 4, 300).astype(np.int64)
+    p = 1.0 / np.arange(1, vocab + 1)
+    p /= p.sum()
+    docs = np.split(rng.choice(vocab, size=int(lens.sum()), p=p), np.cumsum(lens)[:-1])
+    seg = Bm25Segment.from_term_docs(docs, vocab)
+    oidx = orc.Bm25Index(seg.term_offsets, seg.doc_ids, seg.tfs, seg.fieldnorm_ids, seg.total_num_tokens, None)
+    # unions whose lists rarely meet (the planner's own routing sends them to the stream kernel): terms past the 30 densest, and the densest alone
+    queries = [[Clause(int(t)) for t in rng.choice(np.arange(30, vocab), int(rng.integers(1, 5)), replace=False)] for _ in range(194)]
+    queries += [[Clause(t)] for t in (0, 1, 2, 3, 10, 29)]
+    for name in ("NIDX_GPU_BM25_UNION", "NIDX_GPU_BM25_SLICE", "NIDX_GPU_BM25_FUSED_MERGE", "NIDX_GPU_BM25_FLOOR"):
+        monkeypatch.delenv(name, raising=False)
+    s = Bm25Searcher.open([seg])
+    got = {}
+    for crowded in ("0", "1"):
+        monkeypatch.setenv("NIDX_GPU_BM25_CROWDED", crowded)
+        got[crowded] = s.wait(s.submit(queries, 20))
+    s.close()
+    assert same(got["0"], got["1"])
+    docaddr, score, count, total, postings = got["0"]
+    for i, q in enumerate(queries):
+        wd, ws, wt = oidx.search([(c.term, c.occur, c.mode, c.boost) for c in q], 20)
+        assert total[i] == wt and count[i] == len(wd), (i, int(total[i]), wt)
+        assert np.array_equal(docaddr[i, : count[i]], wd), i
+        assert np.array_equal(bits(score[i, : count[i]]), bits(ws)), i
+        assert postings[i] == sum(int(seg.term_offsets[c.term + 1] - seg.term_offsets[c.term]) for c in q), i
