@@ -58,6 +58,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_SYNC 2 /* nidx_gpu_bm25_sync / nidx_gpu_bm25_generation */
 #define NIDX_FEATURE_VECTOR_MAXSIM_BATCH 4 /* nidx_gpu_vector_search_maxsim_filtered_per_query / _submit* / _wait, nidx_gpu_vector_maxsim_stats */
 #define NIDX_FEATURE_BM25_FUZZY_BATCH 8 /* nidx_gpu_bm25_fuzzy_terms_batch */
+#define NIDX_FEATURE_BM25_PREFILTER_BATCH 16 /* nidx_gpu_bm25_prefilter_batch */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -885,6 +886,42 @@ typedef struct {
 } nidx_gpu_bm25_prefilter_t;
 int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *request,
                                 uint64_t *out_docaddr, uint64_t capacity, uint64_t *n_matching, uint64_t *num_docs);
+
+/* The prefilters of a serving batch in one call: request i means exactly what it means to nidx_gpu_bm25_prefilter (n_ops == 0 = every
+ * live document), out_matching[i] is that call's *n_matching and *num_docs_out (may be NULL) its *num_docs.  Identical requests are
+ * evaluated once, and so is every leaf (a union of posting lists, a date range, a phrase) that several programs share: a distinct
+ * leaf becomes one operand row of n_docs bits, one launch scatters all list leaves, one launch per fast field reads its ranks once
+ * for all ranges, one launch runs every distinct program over the rows and one scan + one emit launch write the lists.  Apart from
+ * phrase leaves (two launches per distinct phrase) and fallbacks, neither the launches nor the stream synchronisations (two per
+ * pass: the counts, the lists) of a pass depend on n_requests.
+ *
+ * A request contributes a list only when 0 < matching < num_docs (PrefilterResult::Some, reader.rs:166-179; None and All are all
+ * the query planner needs of the other two): its DocAddresses (segment << 32) | doc, ascending, at out_offsets[i] ..
+ * out_offsets[i + 1] of the concatenation of all lists.  out_offsets [n_requests + 1] is always complete (the prefix sums of the
+ * true list lengths), out_docaddr receives the first min(capacity, total) entries of the concatenation and *n_total_out = total:
+ * call again with a larger buffer when it exceeds capacity.
+ *
+ * max_scratch_bytes (0 = 1 GiB) bounds the operand + result rows on the device; the requests are cut into passes that fit.  A
+ * program that needs a stack deeper than 32, whose own rows exceed the budget or that names more than 1024 distinct ranges of one
+ * fast field is evaluated op by op like the single call, with the same result (stats: fallback_requests).
+ *
+ * Every request is checked before anything is launched, with the single call's checks and messages behind "request i: ":
+ * NIDX_ERR_INVALID_ARGUMENT / NIDX_ERR_UNSUPPORTED, and no output is written.  NULL index / out_offsets / n_total_out, NULL requests
+ * or out_matching with n_requests != 0, NULL out_docaddr with capacity != 0 are NIDX_ERR_INVALID_ARGUMENT; n_requests == 0 gives
+ * out_offsets[0] = 0 and a total of 0.  The call holds the index like nidx_gpu_bm25_prefilter: it answers for one generation with
+ * respect to nidx_gpu_bm25_sync.  Present when nidx_gpu_build_features() & NIDX_FEATURE_BM25_PREFILTER_BATCH. */
+typedef struct nidx_gpu_bm25_prefilter_batch_stats {
+    uint32_t distinct_programs; /* after de-duplication of identical requests */
+    uint32_t operand_rows;      /* distinct leaves (list unions, ranges, phrases) materialised as bitset rows, over all passes */
+    uint32_t passes;            /* chunks of requests evaluated together */
+    uint32_t fallback_requests; /* requests evaluated op by op */
+    uint32_t launches;          /* kernels and memsets the batched passes and the live-document count queued (not the fallbacks' own) */
+    uint32_t synchronisations;  /* stream synchronisations of the same */
+} nidx_gpu_bm25_prefilter_batch_stats_t;
+int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
+                                      uint64_t max_scratch_bytes, uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr,
+                                      uint64_t capacity, uint64_t *n_total_out, uint64_t *num_docs_out,
+                                      nidx_gpu_bm25_prefilter_batch_stats_t *stats_out);
 
 /* open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74), the device half: the caller maps the deletion keys that
  * are newer than the segment (`Seq(segment) < del_seq`) to term ids the way the DeletionQueryBuilders do (a key longer than 32

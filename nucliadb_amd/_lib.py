@@ -154,6 +154,7 @@ class VectorSyncStatsC(C.Structure):
 FEATURE_VECTOR_SYNC = 1   # nidx_gpu_build_features() bit: nidx_gpu_vector_sync / nidx_gpu_vector_generation
 FEATURE_BM25_SYNC = 2     # nidx_gpu_build_features() bit: nidx_gpu_bm25_sync / nidx_gpu_bm25_generation
 FEATURE_BM25_FUZZY_BATCH = 8   # nidx_gpu_build_features() bit: nidx_gpu_bm25_fuzzy_terms_batch
+FEATURE_BM25_PREFILTER_BATCH = 16   # nidx_gpu_build_features() bit: nidx_gpu_bm25_prefilter_batch
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
 
@@ -178,6 +179,12 @@ class Bm25DateRangeC(C.Structure):
 class Bm25PrefilterC(C.Structure):
     _fields_ = [("program", FilterProgramC), ("ranges", C.c_void_p), ("n_ranges", C.c_uint32), ("n_phrases", C.c_uint32),
                 ("phrase_terms", C.c_void_p), ("phrase_offsets", C.c_void_p)]
+
+
+class Bm25PrefilterBatchStatsC(C.Structure):
+    """nidx_gpu_bm25_prefilter_batch_stats_t"""
+    _fields_ = [("distinct_programs", C.c_uint32), ("operand_rows", C.c_uint32), ("passes", C.c_uint32), ("fallback_requests", C.c_uint32),
+                ("launches", C.c_uint32), ("synchronisations", C.c_uint32)]
 
 
 class VectorSearchParamsC(C.Structure):
@@ -338,6 +345,8 @@ SIGNATURES = {
     "nidx_gpu_segment_dir_merge": (C.c_int32, [C.c_char_p, C.c_uint32, C.POINTER(MergeOperandC), C.c_uint32, C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "nidx_gpu_bm25_prefilter": (C.c_int32, [C.c_void_p, C.POINTER(Bm25PrefilterC), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nidx_gpu_bm25_prefilter_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Bm25PrefilterBatchStatsC)]),
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),

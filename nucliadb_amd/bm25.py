@@ -197,6 +197,29 @@ def sync_layout_model(old, entries, n_terms: int, term_map=None):
     return {"term_offsets": offs, "doc_ids": doc, "words": words, "seg_base": base.astype(np.uint64), "seg_term_offsets": seg_offs}
 
 
+def prefilter_requests_c(requests: Sequence[Tuple]):
+    """requests[i] = (ops, lists, ranges, phrases) (trailing members may be left out) -> (the nidx_gpu_bm25_prefilter_t array, the
+    objects its pointers refer to: keep them alive for the call)."""
+    n = len(requests)
+    c_reqs = (_lib.Bm25PrefilterC * max(1, n))()
+    keep = []
+    for i, rq in enumerate(requests):
+        ops, lists, ranges, phrases = (tuple(rq) + ((), (), (), ()))[:4]
+        c_ops = (_lib.FilterOpC * max(1, len(ops)))(*[_lib.FilterOpC(*o) for o in ops])
+        c_lists = np.ascontiguousarray(lists, dtype=np.uint32)
+        c_ranges = (_lib.Bm25DateRangeC * max(1, len(ranges)))(
+            *[_lib.Bm25DateRangeC(f, int(lo is not None), int(hi is not None), 0, int(lo or 0), int(hi or 0)) for f, lo, hi in ranges])
+        p_terms = np.ascontiguousarray([t for ph in phrases for t in ph], dtype=np.uint32)
+        p_offs = np.zeros(len(phrases) + 1, np.uint64)
+        p_offs[1:] = np.cumsum([len(ph) for ph in phrases])
+        keep.append((c_ops, c_lists, c_ranges, p_terms, p_offs))
+        c_reqs[i] = _lib.Bm25PrefilterC(
+            _lib.FilterProgramC(C.addressof(c_ops) if len(ops) else None, len(ops), c_lists.ctypes.data if c_lists.size else None, c_lists.size),
+            C.addressof(c_ranges) if len(ranges) else None, len(ranges), len(phrases),
+            p_terms.ctypes.data if p_terms.size else None, p_offs.ctypes.data)
+    return c_reqs, keep
+
+
 class Bm25Searcher:
     """The scoring core shared by TextSearcher::search and ParagraphSearcher::search."""
 
@@ -353,6 +376,30 @@ class Bm25Searcher:
             if n.value <= cap:
                 return out[: n.value].copy(), live.value
             cap = n.value
+
+    def prefilter_batch(self, requests: Sequence[Tuple], max_scratch_bytes: int = 0, capacity: Optional[int] = None):
+        """prefilter for a serving batch in one library call (nidx_gpu_bm25_prefilter_batch): requests[i] = (ops, lists, ranges, phrases)
+        as for prefilter (trailing members may be left out).  Identical requests and shared leaves are evaluated once.
+        -> (matching [n] uint64, lists, live, stats): lists[i] = the ascending docaddrs of request i when 0 < matching[i] < live, else
+        an empty array (None and All need no list); stats = the call's Bm25PrefilterBatchStatsC.  `capacity` (tests): a fixed output
+        buffer instead of one grown to the total -> (matching, offsets, docaddr[:min(capacity, total)], total, live, stats)."""
+        n = len(requests)
+        c_reqs, _keep = prefilter_requests_c(requests)
+        matching = np.zeros(n, np.uint64)
+        offs = np.zeros(n + 1, np.uint64)
+        total, live = C.c_uint64(0), C.c_uint64(0)
+        stats = _lib.Bm25PrefilterBatchStatsC()
+        cap = max(1 << 16, 64 * n) if capacity is None else int(capacity)
+        while True:
+            out = np.zeros(max(cap, 1), np.uint64)
+            _lib.check(_lib.lib().nidx_gpu_bm25_prefilter_batch(self._handle, C.addressof(c_reqs) if n else None, n, int(max_scratch_bytes),
+                                                                matching.ctypes.data if n else None, offs.ctypes.data, out.ctypes.data if cap else None,
+                                                                cap, C.byref(total), C.byref(live), C.byref(stats)))
+            if capacity is not None:
+                return matching, offs, out[: min(cap, total.value)].copy(), total.value, live.value, stats
+            if total.value <= cap:
+                return matching, [out[int(offs[i]): int(offs[i + 1])].copy() for i in range(n)], live.value, stats
+            cap = total.value
 
     def search_batch_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
                         order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None):

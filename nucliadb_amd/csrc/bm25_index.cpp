@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <limits>
+#include <map>
 #include <chrono>
 #include <memory>
 #include <mutex>
@@ -178,6 +179,9 @@ struct Bm25Index {
     DevBuf s_fzb_in, s_fzb_bits, s_fzb_counts, s_fzb_res;
     PinBuf h_fzb_in, h_fzb_res;
     DevBuf s_pf_stack, s_pf_lists, s_pf_result, s_pf_blocks, s_pf_total, s_pf_out;  // prefilter
+    // nidx_gpu_bm25_prefilter_batch: the plan of a pass in, [operand rows | result rows], [matching | block counts], the emit table, the lists
+    DevBuf s_pfb_in, s_pfb_rows, s_pfb_counts, s_pfb_emit, s_pfb_out;
+    PinBuf h_pfb_in, h_pfb_res;
     float last_kernel_ms = 0.f;
     std::vector<std::unique_ptr<Bm25Slot>> slots;   // nidx_gpu_bm25_search_submit / _wait
     uint64_t next_ticket = 1;
@@ -730,16 +734,11 @@ int32_t nidx_gpu_bm25_fuzzy_terms_batch(nidx_gpu_bm25_index_t *index, const uint
     return NIDX_OK;
 } NIDX_ABI_CATCH
 
-int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *req, uint64_t *out_docaddr, uint64_t capacity,
-                                uint64_t *n_matching, uint64_t *num_docs) try {
-    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
-    if (!idx || !req || !n_matching || (capacity && !out_docaddr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    NIDX_HIP(hipSetDevice(idx->device));
-    *n_matching = 0;
-    if (num_docs) *num_docs = 0;
+// The checks of one prefilter request (the term-id space is shared by the segments); -> the stack depth its program needs.  `where`
+// goes in front of every message ("" for the single call, "request i: " for a batch).
+static int32_t bm25_prefilter_validate(const Bm25Index *idx, const nidx_gpu_bm25_prefilter_t *req, const char *where, int *max_depth_out) {
     const nidx_gpu_filter_program_t &prog = req->program;
-    if (prog.n_ops && !prog.ops) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program without ops");
+    if (prog.n_ops && !prog.ops) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program without ops", where);
     // validate once (the term-id space is shared by the segments) and find the stack depth
     int depth = 0, max_depth = 1;
     for (uint32_t i = 0; i < prog.n_ops; i++) {
@@ -747,24 +746,24 @@ int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
         switch (op.op) {
             case NIDX_FILTER_PUSH_LISTS:
                 if (op.a > op.b || op.b > prog.n_lists || (op.b > op.a && !prog.lists))
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: list range out of bounds");
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: list range out of bounds", where);
                 for (uint32_t l = op.a; l < op.b; l++)
-                    if (prog.lists[l] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: term id %u out of range", prog.lists[l]);
+                    if (prog.lists[l] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: term id %u out of range", where, prog.lists[l]);
                 depth++;
                 break;
             case NIDX_FILTER_PUSH_RANGE:
-                if (op.a >= req->n_ranges || !req->ranges) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: range %u out of bounds", op.a);
-                if (req->ranges[op.a].field > 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "range %u: unknown fast field %u", op.a, req->ranges[op.a].field);
+                if (op.a >= req->n_ranges || !req->ranges) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: range %u out of bounds", where, op.a);
+                if (req->ranges[op.a].field > 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%srange %u: unknown fast field %u", where, op.a, req->ranges[op.a].field);
                 depth++;
                 break;
             case NIDX_FILTER_PUSH_PHRASE: {
                 if (op.a >= req->n_phrases || !req->phrase_offsets || !req->phrase_terms)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: phrase %u out of bounds", op.a);
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: phrase %u out of bounds", where, op.a);
                 const uint64_t m = req->phrase_offsets[op.a + 1] - req->phrase_offsets[op.a];
                 if (m == 0 || m > BM25_MAX_PHRASE_TERMS)
-                    return fail(NIDX_ERR_UNSUPPORTED, "a phrase has 1..%d terms (got %llu)", BM25_MAX_PHRASE_TERMS, (unsigned long long)m);
+                    return fail(NIDX_ERR_UNSUPPORTED, "%sa phrase has 1..%d terms (got %llu)", where, BM25_MAX_PHRASE_TERMS, (unsigned long long)m);
                 for (uint64_t t = req->phrase_offsets[op.a]; t < req->phrase_offsets[op.a + 1]; t++)
-                    if (req->phrase_terms[t] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "phrase: term id %u out of range", req->phrase_terms[t]);
+                    if (req->phrase_terms[t] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sphrase: term id %u out of range", where, req->phrase_terms[t]);
                 depth++;
                 break;
             }
@@ -772,17 +771,49 @@ int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
             case NIDX_FILTER_PUSH_NONE: depth++; break;
             case NIDX_FILTER_AND:
             case NIDX_FILTER_OR:
-                if (depth < 2) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: stack underflow");
+                if (depth < 2) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: stack underflow", where);
                 depth--;
                 break;
             case NIDX_FILTER_NOT:
-                if (depth < 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: stack underflow");
+                if (depth < 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: stack underflow", where);
                 break;
-            default: return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: unknown op %d", op.op);
+            default: return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program: unknown op %d", where, op.op);
         }
         max_depth = std::max(max_depth, depth);
     }
-    if (prog.n_ops && depth != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program must leave exactly one bitset (leaves %d)", depth);
+    if (prog.n_ops && depth != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%sfilter program must leave exactly one bitset (leaves %d)", where, depth);
+    *max_depth_out = max_depth;
+    return NIDX_OK;
+}
+
+// searcher.num_docs() of one resident segment: the documents not deleted, counted on first use (seg.n_alive)
+static int32_t bm25_segment_live(Bm25Index *idx, Bm25Segment &seg) {
+    if (seg.n_alive >= 0) return NIDX_OK;
+    if (seg.all_alive) {
+        seg.n_alive = seg.n_docs;
+        return NIDX_OK;
+    }
+    hipStream_t st = idx->main.stream;
+    const uint32_t n_bits = seg.n_docs, words = (n_bits + 63) / 64;
+    NIDX_HIP(idx->s_pf_stack.reserve((size_t)std::max<uint32_t>(words, 1) * 8));
+    NIDX_HIP(idx->s_pf_result.reserve((size_t)std::max<uint32_t>(words, 1) * 8));
+    NIDX_HIP(idx->s_pf_total.reserve(16));
+    unsigned long long *d_total = idx->s_pf_total.as<unsigned long long>();
+    NIDX_HIP(hipMemsetAsync(d_total, 0, 8, st));
+    NIDX_HIP(launch_bitset_fill(idx->s_pf_stack.as<uint64_t>(), words, n_bits, 1, st));
+    NIDX_HIP(launch_bitset_and_count(idx->s_pf_stack.as<uint64_t>(), seg.alive.as<uint64_t>(), idx->s_pf_result.as<uint64_t>(), words, d_total, st));
+    unsigned long long c = 0;
+    NIDX_HIP(hipMemcpyAsync(&c, d_total, 8, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));
+    seg.n_alive = (int64_t)c;
+    return NIDX_OK;
+}
+
+// The op-by-op evaluation of one validated request (the caller holds idx->mu and has set the device).
+static int32_t bm25_prefilter_locked(Bm25Index *idx, const nidx_gpu_bm25_prefilter_t *req, int max_depth, uint64_t *out_docaddr, uint64_t capacity,
+                                     uint64_t *n_matching, uint64_t *num_docs) {
+    const nidx_gpu_filter_program_t &prog = req->program;
+    int depth = 0;
     hipStream_t st = idx->main.stream;
     if (prog.n_lists) {
         NIDX_HIP(idx->s_pf_lists.reserve((size_t)prog.n_lists * 4));
@@ -801,19 +832,7 @@ int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
         uint64_t *stack = idx->s_pf_stack.as<uint64_t>();
         auto slot = [&](int d) { return stack + (size_t)d * words; };
         unsigned long long *d_total = idx->s_pf_total.as<unsigned long long>();
-        if (seg.n_alive < 0) {  // searcher.num_docs(): documents not deleted
-            if (seg.all_alive) {
-                seg.n_alive = seg.n_docs;
-            } else {
-                NIDX_HIP(hipMemsetAsync(d_total, 0, 8, st));
-                NIDX_HIP(launch_bitset_fill(slot(0), words, n_bits, 1, st));
-                NIDX_HIP(launch_bitset_and_count(slot(0), seg.alive.as<uint64_t>(), idx->s_pf_result.as<uint64_t>(), words, d_total, st));
-                unsigned long long c = 0;
-                NIDX_HIP(hipMemcpyAsync(&c, d_total, 8, hipMemcpyDeviceToHost, st));
-                NIDX_HIP(hipStreamSynchronize(st));
-                seg.n_alive = (int64_t)c;
-            }
-        }
+        if (int32_t rc = bm25_segment_live(idx, seg)) return rc;
         live += (uint64_t)seg.n_alive;
         depth = 0;
         if (prog.n_ops == 0) NIDX_HIP(launch_bitset_fill(slot(depth++), words, n_bits, 1, st));
@@ -896,6 +915,429 @@ int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
     }
     *n_matching = matched;
     if (num_docs) *num_docs = live;
+    return NIDX_OK;
+}
+
+int32_t nidx_gpu_bm25_prefilter(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *req, uint64_t *out_docaddr, uint64_t capacity,
+                                uint64_t *n_matching, uint64_t *num_docs) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !req || !n_matching || (capacity && !out_docaddr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    *n_matching = 0;
+    if (num_docs) *num_docs = 0;
+    int max_depth = 1;
+    if (int32_t rc = bm25_prefilter_validate(idx, req, "", &max_depth)) return rc;
+    return bm25_prefilter_locked(idx, req, max_depth, out_docaddr, capacity, n_matching, num_docs);
+} NIDX_ABI_CATCH
+
+// ---- nidx_gpu_bm25_prefilter_batch: the host plan (kernels: bm25_prefilter.hip) -----------------------------------------------------
+namespace {
+struct PfLeaf {
+    int kind = 0;                  // NIDX_FILTER_PUSH_LISTS / _RANGE / _PHRASE
+    std::vector<uint32_t> data;    // list: its term ids, sorted, distinct; range: field, then (lo, hi) per resident segment; phrase: its terms
+};
+struct PfProgram {
+    std::vector<uint32_t> code;    // (NIDX_FILTER_* | leaf << 3): a leaf is pushed by NIDX_FILTER_PUSH_LISTS whatever its kind
+    std::vector<uint32_t> leaves;  // the distinct leaves of the code
+    uint32_t first_request = 0;
+    int max_depth = 1;
+    bool fallback = false, counted = false;
+    uint64_t matching = 0;
+};
+}  // namespace
+
+int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
+                                      uint64_t max_scratch_bytes, uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr,
+                                      uint64_t capacity, uint64_t *n_total_out, uint64_t *num_docs_out,
+                                      nidx_gpu_bm25_prefilter_batch_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !out_offsets || !n_total_out || (n_requests && (!requests || !out_matching)) || (capacity && !out_docaddr))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    // ---- every request is checked before anything is launched or written
+    std::vector<int> depth_of(n_requests, 1);
+    for (uint32_t i = 0; i < n_requests; i++) {
+        char where[32];
+        snprintf(where, sizeof where, "request %u: ", i);
+        if (int32_t rc = bm25_prefilter_validate(idx, &requests[i], where, &depth_of[i])) return rc;
+    }
+    const size_t S = idx->segs.size();
+    // a row spans the resident segments: segment s owns words [word0[s], word0[s + 1]) and 256-word blocks [block0[s], block0[s + 1])
+    std::vector<size_t> word0(S + 1, 0);
+    std::vector<uint32_t> block0(S + 1, 0);
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t words = (uint32_t)(((uint64_t)idx->segs[s].n_docs + 63) / 64);
+        word0[s + 1] = word0[s] + words;
+        block0[s + 1] = block0[s] + (words + 255) / 256;
+    }
+    const size_t W = word0[S];
+    const uint32_t NB = block0[S];
+    // ---- distinct leaves, distinct programs
+    std::vector<PfLeaf> leaves;
+    std::map<std::pair<int, std::vector<uint32_t>>, uint32_t> leaf_ids;
+    std::vector<PfProgram> programs;
+    std::map<std::vector<uint32_t>, uint32_t> program_ids;
+    std::vector<uint32_t> program_of(n_requests);
+    std::vector<uint32_t> code, data;
+    for (uint32_t i = 0; i < n_requests; i++) {
+        const nidx_gpu_bm25_prefilter_t &req = requests[i];
+        const nidx_gpu_filter_program_t &prog = req.program;
+        code.clear();
+        if (prog.n_ops == 0) code.push_back(NIDX_FILTER_PUSH_ALL);   // no expression: every live document
+        for (uint32_t o = 0; o < prog.n_ops; o++) {
+            const nidx_gpu_filter_op_t &op = prog.ops[o];
+            int kind = op.op;
+            data.clear();
+            if (op.op == NIDX_FILTER_PUSH_LISTS) {
+                data.assign(prog.lists + op.a, prog.lists + op.b);
+                std::sort(data.begin(), data.end());
+                data.erase(std::unique(data.begin(), data.end()), data.end());
+                if (data.empty()) kind = NIDX_FILTER_PUSH_NONE;   // the union of no list
+            } else if (op.op == NIDX_FILTER_PUSH_RANGE) {
+                const nidx_gpu_bm25_date_range_t &r = req.ranges[op.a];
+                if (!r.has_since && !r.has_until) {   // produce_date_range_query returns None -> AllQuery
+                    kind = NIDX_FILTER_PUSH_ALL;
+                } else {
+                    data.push_back(r.field);
+                    bool any = false;
+                    for (size_t s = 0; s < S; s++) {
+                        const Bm25Segment &seg = idx->segs[s];
+                        uint32_t lo = 1, hi = 0;
+                        if (seg.n_docs) {
+                            if (!seg.order_key[r.field].p)
+                                return fail(NIDX_ERR_INVALID_ARGUMENT, "request %u: segment %zu has no fast field %u (nidx_gpu_bm25_set_fast_field)", i, s, r.field);
+                            const std::vector<int64_t> &u = seg.fast_uniq[r.field];
+                            // ranks are 1-based positions in the distinct values: first value >= since .. last value <= until
+                            lo = r.has_since ? (uint32_t)(std::lower_bound(u.begin(), u.end(), r.since) - u.begin()) + 1u : 1u;
+                            hi = r.has_until ? (uint32_t)(std::upper_bound(u.begin(), u.end(), r.until) - u.begin()) : (uint32_t)u.size();
+                            if (lo > hi) lo = 1, hi = 0;
+                        }
+                        any |= lo <= hi;
+                        data.push_back(lo);
+                        data.push_back(hi);
+                    }
+                    if (!any) kind = NIDX_FILTER_PUSH_NONE;   // empty in every segment
+                }
+            } else if (op.op == NIDX_FILTER_PUSH_PHRASE) {
+                data.assign(req.phrase_terms + req.phrase_offsets[op.a], req.phrase_terms + req.phrase_offsets[op.a + 1]);
+                for (size_t s = 0; s < S; s++) {
+                    const Bm25Segment &seg = idx->segs[s];
+                    if (!seg.n_docs || seg.pos_offsets.p) continue;
+                    uint64_t best = ~0ull;
+                    for (uint32_t t : data) best = std::min<uint64_t>(best, seg.term_offsets_host[t + 1] - seg.term_offsets_host[t]);
+                    if (best) return fail(NIDX_ERR_INVALID_ARGUMENT, "request %u: phrase filter on an index opened without positions", i);
+                }
+            }
+            if (kind == NIDX_FILTER_PUSH_LISTS || kind == NIDX_FILTER_PUSH_RANGE || kind == NIDX_FILTER_PUSH_PHRASE) {
+                auto it = leaf_ids.emplace(std::make_pair(kind, data), (uint32_t)leaves.size());
+                if (it.second) {
+                    leaves.emplace_back();
+                    leaves.back().kind = kind;
+                    leaves.back().data = data;
+                }
+                code.push_back((uint32_t)NIDX_FILTER_PUSH_LISTS | (it.first->second << 3));
+            } else {
+                code.push_back((uint32_t)kind);
+            }
+        }
+        auto it = program_ids.emplace(code, (uint32_t)programs.size());
+        if (it.second) {
+            programs.emplace_back();
+            PfProgram &p = programs.back();
+            p.code = code;
+            p.first_request = i;
+            p.max_depth = depth_of[i];
+            for (uint32_t c : code)
+                if ((c & 7u) == NIDX_FILTER_PUSH_LISTS) p.leaves.push_back(c >> 3);
+            std::sort(p.leaves.begin(), p.leaves.end());
+            p.leaves.erase(std::unique(p.leaves.begin(), p.leaves.end()), p.leaves.end());
+        }
+        program_of[i] = it.first->second;
+    }
+    nidx_gpu_bm25_prefilter_batch_stats_t stats;
+    memset(&stats, 0, sizeof stats);
+    stats.distinct_programs = (uint32_t)programs.size();
+    hipStream_t st = idx->main.stream;
+    // ---- searcher.num_docs()
+    uint64_t live = 0;
+    for (Bm25Segment &seg : idx->segs) {
+        if (seg.n_alive < 0 && !seg.all_alive) stats.launches += 3, stats.synchronisations += 1;
+        if (int32_t rc = bm25_segment_live(idx, seg)) return rc;
+        live += (uint64_t)seg.n_alive;
+    }
+    // ---- passes: runs of distinct programs, in the order of their first requests, whose operand + result rows fit the budget.  A
+    // program that does not fit a pass of its own, or needs a deeper stack than the combine kernel has, is evaluated op by op.
+    const uint64_t budget = max_scratch_bytes ? max_scratch_bytes : (1ull << 30);
+    const uint64_t row_bytes = (uint64_t)W * 8;
+    std::vector<std::vector<uint32_t>> passes;
+    {
+        std::vector<uint32_t> cur;
+        std::vector<uint32_t> seen(leaves.size(), 0xffffffffu);   // the pass that has the leaf
+        uint64_t rows = 0;
+        uint32_t n_ranges[2] = {0, 0};
+        for (uint32_t p = 0; p < programs.size() && W; p++) {
+            PfProgram &pg = programs[p];
+            if (pg.max_depth > NIDX_FILTER_STACK || (pg.leaves.size() + 1) * row_bytes > budget) {
+                pg.fallback = true;
+                continue;
+            }
+            for (int attempt = 0; attempt < 2; attempt++) {
+                uint64_t add = 0;
+                uint32_t add_ranges[2] = {0, 0};
+                for (uint32_t l : pg.leaves)
+                    if (seen[l] != (uint32_t)passes.size()) {
+                        add++;
+                        if (leaves[l].kind == NIDX_FILTER_PUSH_RANGE) add_ranges[leaves[l].data[0]]++;
+                    }
+                const bool fits = (rows + add + cur.size() + 1) * row_bytes <= budget && cur.size() < BM25_PREFILTER_MAX_PROGRAMS &&
+                                  n_ranges[0] + add_ranges[0] <= BM25_PREFILTER_MAX_RANGES && n_ranges[1] + add_ranges[1] <= BM25_PREFILTER_MAX_RANGES;
+                if (!fits && !cur.empty()) {   // close the pass and try the empty one (which holds any program that is not a fallback)
+                    passes.push_back(cur);
+                    cur.clear();
+                    rows = 0;
+                    n_ranges[0] = n_ranges[1] = 0;
+                    continue;
+                }
+                if (!fits) pg.fallback = true;   // more than BM25_PREFILTER_MAX_RANGES distinct ranges in one program
+                else {
+                    for (uint32_t l : pg.leaves) seen[l] = (uint32_t)passes.size();
+                    rows += add;
+                    n_ranges[0] += add_ranges[0];
+                    n_ranges[1] += add_ranges[1];
+                    cur.push_back(p);
+                }
+                break;
+            }
+        }
+        if (!cur.empty()) passes.push_back(cur);
+    }
+    // ---- the fallback programs' counts first: every offset below follows from the counts of the requests before it
+    for (PfProgram &pg : programs) {
+        if (W == 0) pg.counted = true;   // an index without documents: nothing matches
+        if (!pg.fallback) continue;
+        uint64_t lv = 0;
+        if (int32_t rc = bm25_prefilter_locked(idx, &requests[pg.first_request], pg.max_depth, nullptr, 0, &pg.matching, &lv)) return rc;
+        pg.counted = true;
+    }
+    auto list_len = [&](const PfProgram &pg) -> uint64_t { return pg.matching > 0 && pg.matching < live ? pg.matching : 0; };
+    std::vector<uint64_t> offsets((size_t)n_requests + 1, 0);
+    uint32_t known = 0;   // offsets[0 .. known] are final
+    auto advance = [&]() {
+        while (known < n_requests && programs[program_of[known]].counted) {
+            offsets[known + 1] = offsets[known] + list_len(programs[program_of[known]]);
+            known++;
+        }
+    };
+    advance();
+    std::vector<uint32_t> row_of(leaves.size(), 0), plan, listed;
+    std::vector<unsigned long long> emit;
+    for (const std::vector<uint32_t> &pass : passes) {
+        stats.passes++;
+        const uint32_t P = (uint32_t)pass.size();
+        // rows of the pass's leaves, in the order the programs name them
+        std::vector<uint32_t> pass_leaves;
+        {
+            std::vector<uint8_t> has(leaves.size(), 0);
+            for (uint32_t p : pass)
+                for (uint32_t l : programs[p].leaves)
+                    if (!has[l]) {
+                        has[l] = 1;
+                        row_of[l] = (uint32_t)pass_leaves.size();
+                        pass_leaves.push_back(l);
+                    }
+        }
+        const uint32_t R = (uint32_t)pass_leaves.size();
+        stats.operand_rows += R;
+        // the plan block: [ops | prog_first (P + 1) | scatter work (row, term) | per segment and field: intervals (lo, hi, row)]
+        plan.clear();
+        for (uint32_t p : pass)
+            for (uint32_t c : programs[p].code) plan.push_back((c & 7u) == NIDX_FILTER_PUSH_LISTS ? (uint32_t)NIDX_FILTER_PUSH_LISTS | (row_of[c >> 3] << 3) : c);
+        const size_t o_first = plan.size();
+        uint32_t at = 0;
+        for (uint32_t p : pass) {
+            plan.push_back(at);
+            at += (uint32_t)programs[p].code.size();
+        }
+        plan.push_back(at);
+        const size_t o_work = plan.size();
+        uint32_t n_work = 0;
+        uint64_t max_driver = 0;
+        for (uint32_t l : pass_leaves) {
+            if (leaves[l].kind == NIDX_FILTER_PUSH_LISTS)
+                for (uint32_t t : leaves[l].data) {
+                    plan.push_back(row_of[l]);
+                    plan.push_back(t);
+                    n_work++;
+                }
+        }
+        std::vector<size_t> o_iv(S * 2 + 1, 0);
+        for (size_t s = 0; s < S; s++)
+            for (uint32_t f = 0; f < 2; f++) {
+                o_iv[s * 2 + f] = plan.size();
+                for (uint32_t l : pass_leaves) {
+                    const PfLeaf &lf = leaves[l];
+                    if (lf.kind != NIDX_FILTER_PUSH_RANGE || lf.data[0] != f || lf.data[1 + 2 * s] > lf.data[2 + 2 * s]) continue;
+                    plan.push_back(lf.data[1 + 2 * s]);
+                    plan.push_back(lf.data[2 + 2 * s]);
+                    plan.push_back(row_of[l]);
+                }
+            }
+        o_iv[S * 2] = plan.size();
+        NIDX_HIP(idx->h_pfb_in.reserve(plan.size() * 4));
+        NIDX_HIP(idx->s_pfb_in.reserve(plan.size() * 4));
+        memcpy(idx->h_pfb_in.p, plan.data(), plan.size() * 4);
+        NIDX_HIP(hipMemcpyAsync(idx->s_pfb_in.p, idx->h_pfb_in.p, plan.size() * 4, hipMemcpyHostToDevice, st));
+        const uint32_t *d_plan = idx->s_pfb_in.as<uint32_t>();
+        // scratch: [operand rows | result rows], [matching (P x S) | block counts (P x NB)]
+        NIDX_HIP(idx->s_pfb_rows.reserve((size_t)((uint64_t)(R + P) * row_bytes)));
+        uint64_t *d_operands = idx->s_pfb_rows.as<uint64_t>(), *d_results = d_operands + (size_t)R * W;
+        const size_t match_bytes = (size_t)P * S * 8;
+        NIDX_HIP(idx->s_pfb_counts.reserve(match_bytes + (size_t)P * NB * 4));
+        unsigned long long *d_matching = idx->s_pfb_counts.as<unsigned long long>();
+        uint32_t *d_blocks = reinterpret_cast<uint32_t *>(idx->s_pfb_counts.as<uint8_t>() + match_bytes);
+        if (R) {
+            NIDX_HIP(hipMemsetAsync(d_operands, 0, (size_t)R * row_bytes, st));
+            stats.launches++;
+        }
+        NIDX_HIP(hipMemsetAsync(d_matching, 0, match_bytes, st));
+        stats.launches++;
+        // the phrases' scratch, sized once (growing it between two launches would free what the first still reads)
+        for (uint32_t l : pass_leaves)
+            if (leaves[l].kind == NIDX_FILTER_PUSH_PHRASE)
+                for (const Bm25Segment &seg : idx->segs) {
+                    uint64_t best = ~0ull;
+                    for (uint32_t t : leaves[l].data) best = std::min<uint64_t>(best, seg.term_offsets_host[t + 1] - seg.term_offsets_host[t]);
+                    max_driver = std::max(max_driver, best);
+                }
+        if (max_driver) NIDX_HIP(idx->main.s_phrase_tf.reserve(max_driver * 4));
+        for (size_t s = 0; s < S; s++) {
+            Bm25Segment &seg = idx->segs[s];
+            if (!seg.n_docs) continue;
+            uint64_t *seg_operands = d_operands + word0[s];
+            if (n_work) {
+                NIDX_HIP(launch_filter_scatter(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), d_plan + o_work, n_work, seg.n_docs,
+                                               (uint32_t)W, seg_operands, st));
+                stats.launches++;
+            }
+            for (uint32_t f = 0; f < 2; f++) {
+                const uint32_t n_iv = (uint32_t)((o_iv[s * 2 + f + 1] - o_iv[s * 2 + f]) / 3);
+                if (!n_iv) continue;
+                NIDX_HIP(launch_prefilter_range_rows(seg.order_key[f].as<uint32_t>(), seg.n_docs, d_plan + o_iv[s * 2 + f], n_iv, seg_operands, W, st));
+                stats.launches++;
+            }
+            for (uint32_t l : pass_leaves) {
+                if (leaves[l].kind != NIDX_FILTER_PUSH_PHRASE) continue;
+                PhraseDev ph;
+                ph.slop = 0;
+                ph.n_terms = (uint32_t)leaves[l].data.size();
+                ph.driver = 0;
+                uint64_t best = ~0ull;
+                for (uint32_t t = 0; t < ph.n_terms; t++) {
+                    ph.terms[t] = leaves[l].data[t];
+                    const uint64_t df = seg.term_offsets_host[ph.terms[t] + 1] - seg.term_offsets_host[ph.terms[t]];
+                    if (df < best) { best = df; ph.driver = t; }
+                }
+                if (!best) continue;
+                NIDX_HIP(launch_phrase_match(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.pos_offsets.as<unsigned long long>(),
+                                             seg.positions.as<uint32_t>(), ph, (uint32_t)best, idx->main.s_phrase_tf.as<uint32_t>(), nullptr, st));
+                NIDX_HIP(launch_phrase_bits(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), ph, (uint32_t)best,
+                                            idx->main.s_phrase_tf.as<uint32_t>(), seg_operands + (size_t)row_of[l] * W, st));
+                stats.launches += 2;
+            }
+            NIDX_HIP(launch_prefilter_combine(d_plan, d_plan + o_first, P, seg_operands, W, seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), seg.n_docs,
+                                              d_results + word0[s], d_matching + s, (uint32_t)S, d_blocks + block0[s], NB, st));
+            stats.launches++;
+        }
+        // one transfer for the counts
+        NIDX_HIP(idx->h_pfb_res.reserve(match_bytes));
+        NIDX_HIP(hipMemcpyAsync(idx->h_pfb_res.p, d_matching, match_bytes, hipMemcpyDeviceToHost, st));
+        NIDX_HIP(hipStreamSynchronize(st));
+        stats.synchronisations++;
+        std::vector<unsigned long long> counts(idx->h_pfb_res.as<unsigned long long>(), idx->h_pfb_res.as<unsigned long long>() + (size_t)P * S);
+        for (uint32_t j = 0; j < P; j++) {
+            PfProgram &pg = programs[pass[j]];
+            pg.matching = 0;
+            for (size_t s = 0; s < S; s++) pg.matching += counts[(size_t)j * S + s];
+            pg.counted = true;
+        }
+        advance();
+        // the listed programs: Some (neither nothing nor everything) and a first request that starts below the capacity.  Their slices
+        // follow each other in the pass's output like their first requests do in the caller's.
+        listed.clear();
+        emit.clear();   // [begin (n_listed x S) | end (n_listed)]
+        std::vector<unsigned long long> ends;
+        uint64_t n_out = 0;
+        for (uint32_t j = 0; j < P; j++) {
+            const PfProgram &pg = programs[pass[j]];
+            const uint64_t len = list_len(pg), off = offsets[pg.first_request];
+            if (!len || off >= capacity) continue;
+            listed.push_back(j);
+            uint64_t begin = n_out;
+            for (size_t s = 0; s < S; s++) {
+                emit.push_back(begin);
+                begin += counts[(size_t)j * S + s];
+            }
+            n_out += std::min<uint64_t>(len, capacity - off);
+            ends.push_back(n_out);
+        }
+        const uint32_t n_listed = (uint32_t)listed.size();
+        if (!n_listed) continue;
+        emit.insert(emit.end(), ends.begin(), ends.end());
+        const size_t emit_bytes = emit.size() * 8, table_bytes = emit_bytes + (size_t)n_listed * 4;
+        NIDX_HIP(idx->h_pfb_in.reserve(table_bytes));
+        NIDX_HIP(idx->s_pfb_emit.reserve(table_bytes));
+        memcpy(idx->h_pfb_in.p, emit.data(), emit_bytes);
+        memcpy(idx->h_pfb_in.as<uint8_t>() + emit_bytes, listed.data(), (size_t)n_listed * 4);
+        NIDX_HIP(hipMemcpyAsync(idx->s_pfb_emit.p, idx->h_pfb_in.p, table_bytes, hipMemcpyHostToDevice, st));
+        const unsigned long long *d_begin = idx->s_pfb_emit.as<unsigned long long>(), *d_end = d_begin + (size_t)n_listed * S;
+        const uint32_t *d_listed = reinterpret_cast<const uint32_t *>(idx->s_pfb_emit.as<uint8_t>() + emit_bytes);
+        NIDX_HIP(idx->s_pfb_out.reserve(n_out * 8));
+        for (size_t s = 0; s < S; s++) {
+            const Bm25Segment &seg = idx->segs[s];
+            if (!seg.n_docs) continue;
+            const bool cat = idx->concatenated();
+            NIDX_HIP(launch_prefilter_emit(d_results + word0[s], W, seg.n_docs, d_blocks + block0[s], NB, d_listed, n_listed, d_begin + s, (uint32_t)S, d_end,
+                                           cat ? idx->d_seg_base.as<uint32_t>() : nullptr, cat ? (uint32_t)idx->real.size() : 0u, (uint32_t)s,
+                                           idx->s_pfb_out.as<uint64_t>(), st));
+            stats.launches += 2;
+        }
+        // one transfer for the lists
+        NIDX_HIP(idx->h_pfb_res.reserve(n_out * 8));
+        NIDX_HIP(hipMemcpyAsync(idx->h_pfb_res.p, idx->s_pfb_out.p, n_out * 8, hipMemcpyDeviceToHost, st));
+        NIDX_HIP(hipStreamSynchronize(st));
+        stats.synchronisations++;
+        for (uint32_t k = 0; k < n_listed; k++) {
+            const PfProgram &pg = programs[pass[listed[k]]];
+            const uint64_t begin = emit[(size_t)k * S], n = ends[k] - begin;
+            memcpy(out_docaddr + offsets[pg.first_request], idx->h_pfb_res.as<uint64_t>() + begin, (size_t)n * 8);
+        }
+    }
+    advance();
+    if (known != n_requests) return fail(NIDX_ERR_DEVICE, "prefilter batch: %u of %u requests were not evaluated", n_requests - known, n_requests);
+    // the lists of the fallback programs, then every repeated request's copy of its program's list
+    for (const PfProgram &pg : programs) {
+        const uint64_t len = list_len(pg), off = offsets[pg.first_request];
+        if (!pg.fallback || !len || off >= capacity) continue;
+        uint64_t m = 0;
+        if (int32_t rc = bm25_prefilter_locked(idx, &requests[pg.first_request], pg.max_depth, out_docaddr + off, std::min<uint64_t>(len, capacity - off), &m,
+                                               nullptr))
+            return rc;
+        if (m != pg.matching) return fail(NIDX_ERR_DEVICE, "prefilter batch: count mismatch (%llu vs %llu)", (unsigned long long)m, (unsigned long long)pg.matching);
+    }
+    for (uint32_t i = 0; i < n_requests; i++) {
+        const PfProgram &pg = programs[program_of[i]];
+        out_matching[i] = pg.matching;
+        if (pg.fallback) stats.fallback_requests++;
+        const uint64_t len = list_len(pg), off = offsets[i];
+        if (i == pg.first_request || !len || off >= capacity) continue;
+        memcpy(out_docaddr + off, out_docaddr + offsets[pg.first_request], (size_t)std::min<uint64_t>(len, capacity - off) * 8);
+    }
+    memcpy(out_offsets, offsets.data(), offsets.size() * 8);
+    *n_total_out = offsets[n_requests];
+    if (num_docs_out) *num_docs_out = live;
+    if (stats_out) *stats_out = stats;
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

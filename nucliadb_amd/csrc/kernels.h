@@ -666,5 +666,25 @@ hipError_t launch_phrase_bits(const unsigned long long *term_offsets, const uint
 hipError_t launch_bitset_to_docaddr(const uint64_t *bits, uint32_t n_words, uint32_t segment, uint32_t *block_scratch,
                                     unsigned long long *total, unsigned long long out_begin, unsigned long long out_cap, uint64_t *out,
                                     hipStream_t s);
+// ---- nidx_gpu_bm25_prefilter_batch (bm25_prefilter.hip): all distinct programs of a pass over one resident segment ----------------
+// Rows are bitsets of row_stride words that span every resident segment; the pointers handed over are already at the segment's first
+// word, n_docs / n_bits are the segment's.
+//   range_rows: rows[row][w] = ballot(lo <= order_key[64 w + lane] <= hi) for every interval (lo, hi, row); order_key read once
+//   combine:    program f = ops[prog_first[f] .. prog_first[f + 1]) (NIDX_FILTER_* | row << 3) over the operand rows, & alive ->
+//               results[f], matching[f * match_stride] += popcount, block_counts[f * blocks_stride + b] = popcount of 256-word block b
+//   emit:       scans the block counts of the listed programs in place, then writes program listed_prog[j]'s set bits as DocAddresses
+//               at out[listed_begin[j * begin_stride] ..), never at or beyond out[listed_end[j]]; seg_base (nullable) = the n_real + 1
+//               document bases of the concatenated layout, else every document is of `segment`
+#define BM25_PREFILTER_MAX_RANGES 1024      // distinct bounded intervals of one fast field per pass (they sit in LDS)
+#define BM25_PREFILTER_MAX_PROGRAMS 65535   // distinct programs per pass (a grid dimension)
+hipError_t launch_prefilter_range_rows(const uint32_t *order_key, uint32_t n_docs, const uint32_t *intervals /*[n][3]*/, uint32_t n_intervals,
+                                       uint64_t *rows, size_t row_stride, hipStream_t s);
+hipError_t launch_prefilter_combine(const uint32_t *ops, const uint32_t *prog_first, uint32_t n_programs, const uint64_t *operands, size_t row_stride,
+                                    const uint64_t *alive, uint32_t n_bits, uint64_t *results, unsigned long long *matching, uint32_t match_stride,
+                                    uint32_t *block_counts, uint32_t blocks_stride, hipStream_t s);
+hipError_t launch_prefilter_emit(const uint64_t *results, size_t row_stride, uint32_t n_bits, uint32_t *block_counts, uint32_t blocks_stride,
+                                 const uint32_t *listed_prog, uint32_t n_listed, const unsigned long long *listed_begin, uint32_t begin_stride,
+                                 const unsigned long long *listed_end, const uint32_t *seg_base, uint32_t n_real, uint32_t segment, uint64_t *out,
+                                 hipStream_t s);
 
 }  // namespace nidx
