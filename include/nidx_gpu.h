@@ -59,6 +59,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_MAXSIM_BATCH 4 /* nidx_gpu_vector_search_maxsim_filtered_per_query / _submit* / _wait, nidx_gpu_vector_maxsim_stats */
 #define NIDX_FEATURE_BM25_FUZZY_BATCH 8 /* nidx_gpu_bm25_fuzzy_terms_batch */
 #define NIDX_FEATURE_BM25_PREFILTER_BATCH 16 /* nidx_gpu_bm25_prefilter_batch */
+#define NIDX_FEATURE_BM25_HIT_TERMS 32 /* nidx_gpu_bm25_hit_terms_batch */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -851,6 +852,44 @@ int32_t nidx_gpu_bm25_fuzzy_terms(nidx_gpu_bm25_index_t *index, const uint8_t *q
 int32_t nidx_gpu_bm25_fuzzy_terms_batch(nidx_gpu_bm25_index_t *index, const uint8_t *words_utf8, const uint64_t *word_offsets,
                                         const uint8_t *word_prefix, uint32_t n_words, uint64_t *out_offsets, uint32_t *out_terms,
                                         uint64_t cap, uint64_t *n_total_out);
+
+/* ParagraphResult::matches for a batch of responses (nidx_paragraph/src/search_query.rs:35-71 TermCollector::log_fterm / get_fterms,
+ * filled by AutomatonWeight::scorer, fuzzy_query.rs:88-116, read at search_response.rs:180-191 and :275-287): which of the terms the
+ * fuzzy query's automata accepted occur in which hit.  Query q has the hits hit_docaddr[hit_offsets[q] .. hit_offsets[q + 1]) —
+ * DocAddresses (segment << 32) | doc, at most 513 — and the term sets query_set_offsets[q] .. query_set_offsets[q + 1]); set j =
+ * set_terms[set_offsets[j] .. set_offsets[j + 1]), one per fuzzy word: the arrays handed to nidx_gpu_bm25_search_ex as term_set_terms /
+ * term_set_offsets.  For a hit h = (s, d) and a term t
+ *     c(h, t) = sum over the sets j of q that hold t, sum over the opened segments s' with d < n_docs(s'), of [d in postings(t, s')]
+ * and hit h's list is every t repeated c(h, t) times, ascending.  The rule is keyed by the segment-LOCAL doc id alone, as the
+ * reference's map is (fterms: HashMap<DocId, ..>): a hit receives what any segment holds under its local id, and documents that
+ * deletions removed count (the scorer that logs does not look at the alive set).  Two sets that both hold a term give it twice.
+ * Terms of fewer than min_term_bytes bytes are dropped (the reference keeps len > 2: pass 3; this needs
+ * nidx_gpu_bm25_set_dictionary); 0 keeps every term and needs no dictionary.
+ *
+ * out_offsets [n_hits + 1] (n_hits = hit_offsets[n_queries] - hit_offsets[0], hits in the order given) is always complete,
+ * out_terms receives the first min(cap, total) ids of the concatenation of all lists and *n_total_out = total: call again with a
+ * larger buffer when it exceeds cap.  The lists are joined against the resident posting lists and ordered on the device; a list of
+ * more than 2048 ids is ordered by the host (stats: host_finished_hits).  Neither the launches nor the stream synchronisations of a
+ * pass depend on n_queries.
+ *
+ * Everything is checked before anything is launched, the message names the query, and no output is written on error:
+ * NIDX_ERR_INVALID_ARGUMENT for NULL arguments (hit_docaddr / set_terms may be NULL when there are no hits / no members, out_terms
+ * when cap == 0, stats_out always), decreasing offsets, a DocAddress whose segment or doc is out of range, a term id >= n_terms,
+ * more than 513 hits in a query, min_term_bytes > 0 without a dictionary.  n_queries == 0, queries without hits and queries without
+ * sets give empty lists.  The call holds the index like nidx_gpu_bm25_fuzzy_terms_batch: it answers for one generation with respect
+ * to nidx_gpu_bm25_sync.  Present when nidx_gpu_build_features() & NIDX_FEATURE_BM25_HIT_TERMS. */
+typedef struct nidx_gpu_bm25_hit_terms_stats {
+    uint32_t passes, launches, synchronisations;
+    uint32_t host_finished_hits;   /* lists that outgrew the on-chip sort */
+    uint64_t postings_read, probes;
+} nidx_gpu_bm25_hit_terms_stats_t;
+int32_t nidx_gpu_bm25_hit_terms_batch(nidx_gpu_bm25_index_t *index,
+    const uint64_t *hit_docaddr, const uint64_t *hit_offsets /* [n_queries+1] */, uint32_t n_queries,
+    const uint32_t *set_terms, const uint64_t *set_offsets /* [n_sets+1] */, uint32_t n_sets,
+    const uint64_t *query_set_offsets /* [n_queries+1] into the sets */,
+    uint32_t min_term_bytes /* reference: 3; 0 = keep every term, no dictionary needed */,
+    uint64_t *out_offsets /* [n_hits+1] */, uint32_t *out_terms, uint64_t cap, uint64_t *n_total_out,
+    nidx_gpu_bm25_hit_terms_stats_t *stats_out /* may be NULL */);
 
 /* TextReaderService::prefilter (nidx_text/src/reader.rs:148-180): the documents (fields) that satisfy a boolean
  * filter expression, evaluated as bitset algebra on the device.  The expression is what filter_to_query

@@ -155,6 +155,7 @@ FEATURE_VECTOR_SYNC = 1   # nidx_gpu_build_features() bit: nidx_gpu_vector_sync 
 FEATURE_BM25_SYNC = 2     # nidx_gpu_build_features() bit: nidx_gpu_bm25_sync / nidx_gpu_bm25_generation
 FEATURE_BM25_FUZZY_BATCH = 8   # nidx_gpu_build_features() bit: nidx_gpu_bm25_fuzzy_terms_batch
 FEATURE_BM25_PREFILTER_BATCH = 16   # nidx_gpu_build_features() bit: nidx_gpu_bm25_prefilter_batch
+FEATURE_BM25_HIT_TERMS = 32   # nidx_gpu_build_features() bit: nidx_gpu_bm25_hit_terms_batch
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
 
@@ -185,6 +186,12 @@ class Bm25PrefilterBatchStatsC(C.Structure):
     """nidx_gpu_bm25_prefilter_batch_stats_t"""
     _fields_ = [("distinct_programs", C.c_uint32), ("operand_rows", C.c_uint32), ("passes", C.c_uint32), ("fallback_requests", C.c_uint32),
                 ("launches", C.c_uint32), ("synchronisations", C.c_uint32)]
+
+
+class Bm25HitTermsStatsC(C.Structure):
+    """nidx_gpu_bm25_hit_terms_stats_t"""
+    _fields_ = [("passes", C.c_uint32), ("launches", C.c_uint32), ("synchronisations", C.c_uint32), ("host_finished_hits", C.c_uint32),
+                ("postings_read", C.c_uint64), ("probes", C.c_uint64)]
 
 
 class VectorSearchParamsC(C.Structure):
@@ -350,6 +357,9 @@ SIGNATURES = {
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),
+    "nidx_gpu_bm25_hit_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(Bm25HitTermsStatsC)]),
     "nidx_gpu_bm25_last_kernel_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_float)]),
     "nidx_gpu_bm25_idf": (C.c_float, [C.c_uint64, C.c_uint64]),
     "nidx_gpu_fieldnorm_from_id": (C.c_uint32, [C.c_uint8]),

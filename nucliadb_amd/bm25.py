@@ -352,6 +352,43 @@ class Bm25Searcher:
                 return [out[int(offs[w]): int(offs[w + 1])].copy() for w in range(W)]
             cap = total.value
 
+    def hit_terms_batch(self, hits_per_query: Sequence[Sequence[int]], sets_per_query: Sequence[Sequence[Sequence[int]]], min_term_bytes: int = 3,
+                        capacity: Optional[int] = None):
+        """ParagraphResult::matches for a batch in one library call (nidx_gpu_bm25_hit_terms_batch): hits_per_query[q] = the DocAddresses
+        of query q's hits (at most 513), sets_per_query[q] = the term-id sets of its fuzzy words (what search_batch_ex got as term
+        sets).  -> per query, per hit, the ascending ids of the set members that occur under the hit's LOCAL doc id in any segment, a
+        member of two sets twice; terms shorter than min_term_bytes bytes dropped (0: none, and no dictionary is needed).  The call's
+        Bm25HitTermsStatsC is kept in last_hit_terms_stats.  `capacity` (tests): a fixed output buffer instead of one grown to the
+        total -> (offsets, terms[:min(capacity, total)], total, stats)."""
+        Q = len(hits_per_query)
+        assert len(sets_per_query) == Q
+        hit_offs = np.zeros(Q + 1, np.uint64)
+        hit_offs[1:] = np.cumsum([len(h) for h in hits_per_query])
+        hits = np.ascontiguousarray([a for h in hits_per_query for a in h], dtype=np.uint64)
+        sets = [np.ascontiguousarray(s, dtype=np.uint32) for qs in sets_per_query for s in qs]
+        qset_offs = np.zeros(Q + 1, np.uint64)
+        qset_offs[1:] = np.cumsum([len(qs) for qs in sets_per_query])
+        set_offs = np.zeros(len(sets) + 1, np.uint64)
+        set_offs[1:] = np.cumsum([s.size for s in sets])
+        members = np.concatenate(sets) if sets else np.zeros(0, np.uint32)
+        n_hits = int(hit_offs[Q])
+        offs = np.zeros(n_hits + 1, np.uint64)
+        total = C.c_uint64(0)
+        stats = _lib.Bm25HitTermsStatsC()
+        cap = max(1024, 8 * n_hits) if capacity is None else int(capacity)
+        while True:
+            out = np.zeros(max(cap, 1), np.uint32)
+            _lib.check(_lib.lib().nidx_gpu_bm25_hit_terms_batch(self._handle, hits.ctypes.data if hits.size else None, hit_offs.ctypes.data, Q,
+                                                                members.ctypes.data if members.size else None, set_offs.ctypes.data, len(sets),
+                                                                qset_offs.ctypes.data, int(min_term_bytes), offs.ctypes.data,
+                                                                out.ctypes.data if cap else None, cap, C.byref(total), C.byref(stats)))
+            self.last_hit_terms_stats = stats
+            if capacity is not None:
+                return offs, out[: min(cap, total.value)].copy(), total.value, stats
+            if total.value <= cap:
+                return [[out[int(offs[h]): int(offs[h + 1])].copy() for h in range(int(hit_offs[q]), int(hit_offs[q + 1]))] for q in range(Q)]
+            cap = total.value
+
     def prefilter(self, ops: Sequence[Tuple[int, int, int]], lists: Sequence[int] = (), ranges: Sequence[Tuple[int, Optional[int], Optional[int]]] = (),
                   phrases: Sequence[Sequence[int]] = ()) -> Tuple[np.ndarray, int]:
         """TextReaderService::prefilter (nidx_text/src/reader.rs:148-180) on the device: `ops` is a postfix filter program

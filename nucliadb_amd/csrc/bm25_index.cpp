@@ -178,6 +178,9 @@ struct Bm25Index {
     // nidx_gpu_bm25_fuzzy_terms_batch: [meta | code points] in, the chunk's bit matrix and counts, [offsets | term ids] out
     DevBuf s_fzb_in, s_fzb_bits, s_fzb_counts, s_fzb_res;
     PinBuf h_fzb_in, h_fzb_res;
+    // nidx_gpu_bm25_hit_terms_batch: the plan in, [offsets | per-query statistics | counts], the lists
+    DevBuf s_ht_in, s_ht_res, s_ht_out;
+    PinBuf h_ht_in, h_ht_res;
     DevBuf s_pf_stack, s_pf_lists, s_pf_result, s_pf_blocks, s_pf_total, s_pf_out;  // prefilter
     // nidx_gpu_bm25_prefilter_batch: the plan of a pass in, [operand rows | result rows], [matching | block counts], the emit table, the lists
     DevBuf s_pfb_in, s_pfb_rows, s_pfb_counts, s_pfb_emit, s_pfb_out;
@@ -731,6 +734,154 @@ int32_t nidx_gpu_bm25_fuzzy_terms_batch(nidx_gpu_bm25_index_t *index, const uint
         break;
     }
     *n_total_out = total;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// ParagraphResult::matches for a batch (bm25_hit_terms.hip).  One pass: the plan goes up in one copy, the count pass and its scan run,
+// the offsets come back (first synchronisation: the total sizes the list buffer), the emit pass and the two sort kernels run, the lists
+// come back (second synchronisation).  A list longer than HIT_TERMS_SORT_CAP is ordered here.
+int32_t nidx_gpu_bm25_hit_terms_batch(nidx_gpu_bm25_index_t *index, const uint64_t *hit_docaddr, const uint64_t *hit_offsets, uint32_t n_queries,
+                                      const uint32_t *set_terms, const uint64_t *set_offsets, uint32_t n_sets, const uint64_t *query_set_offsets,
+                                      uint32_t min_term_bytes, uint64_t *out_offsets, uint32_t *out_terms, uint64_t cap, uint64_t *n_total_out,
+                                      nidx_gpu_bm25_hit_terms_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !hit_offsets || !set_offsets || !query_set_offsets || !out_offsets || !n_total_out || (cap && !out_terms))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t j = 0; j < n_sets; j++)
+        if (set_offsets[j + 1] < set_offsets[j]) return fail(NIDX_ERR_INVALID_ARGUMENT, "set_offsets decrease at set %u", j);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        if (hit_offsets[q + 1] < hit_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: hit_offsets decrease", q);
+        if (hit_offsets[q + 1] - hit_offsets[q] > HIT_TERMS_MAX_HITS)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: %llu hits (at most %d: k <= 512 and one more)", q,
+                        (unsigned long long)(hit_offsets[q + 1] - hit_offsets[q]), HIT_TERMS_MAX_HITS);
+        if (query_set_offsets[q + 1] < query_set_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: query_set_offsets decrease", q);
+        if (query_set_offsets[q + 1] > n_sets)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: its sets end at %llu of %u", q, (unsigned long long)query_set_offsets[q + 1], n_sets);
+    }
+    const uint64_t h0 = hit_offsets[0], n_hits = hit_offsets[n_queries] - h0;
+    const uint64_t s0 = set_offsets[0], n_mem = set_offsets[n_sets] - s0;
+    if ((n_hits && !hit_docaddr) || (n_mem && !set_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    const bool cat = idx->concatenated();
+    for (uint32_t q = 0; q < n_queries; q++) {
+        for (uint64_t h = hit_offsets[q]; h < hit_offsets[q + 1]; h++) {
+            const uint64_t s = hit_docaddr[h] >> 32, d = hit_docaddr[h] & 0xffffffffull;
+            if (s >= idx->n_segments)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: hit %llu is of segment %llu of %u", q, (unsigned long long)(h - hit_offsets[q]),
+                            (unsigned long long)s, idx->n_segments);
+            const uint32_t n_docs = cat ? idx->real[s].n_docs : idx->segs[s].n_docs;
+            if (d >= n_docs)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: hit %llu is document %llu of %u in segment %llu", q,
+                            (unsigned long long)(h - hit_offsets[q]), (unsigned long long)d, n_docs, (unsigned long long)s);
+        }
+        for (uint64_t m = set_offsets[query_set_offsets[q]]; m < set_offsets[query_set_offsets[q + 1]]; m++)
+            if (set_terms[m] >= idx->n_terms)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u: term id %u >= n_terms %u", q, set_terms[m], idx->n_terms);
+    }
+    if (min_term_bytes && !idx->has_dict)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "min_term_bytes without a term dictionary: call nidx_gpu_bm25_set_dictionary first");
+    nidx_gpu_bm25_hit_terms_stats_t stats;
+    memset(&stats, 0, sizeof(stats));
+    if (n_hits == 0) {
+        out_offsets[0] = 0;
+        *n_total_out = 0;
+        if (stats_out) *stats_out = stats;
+        return NIDX_OK;
+    }
+    // the plan: [hit ranges | member ranges | resident layouts | entries: local doc ids, ascending per query | their hits | members | bases]
+    const size_t nq1 = (size_t)n_queries + 1, n_res = idx->segs.size();
+    const size_t o_qm = nq1 * 8, o_segs = 2 * nq1 * 8, o_doc = o_segs + n_res * sizeof(HitTermsSeg), o_hit = o_doc + n_hits * 4,
+                 o_mem = o_hit + n_hits * 4, o_sub = o_mem + n_mem * 4, in_bytes = o_sub + (cat ? 0 : 2 * n_res * 4);
+    NIDX_HIP(idx->h_ht_in.reserve(in_bytes));
+    NIDX_HIP(idx->s_ht_in.reserve(in_bytes));
+    uint8_t *hp = idx->h_ht_in.as<uint8_t>(), *dp = idx->s_ht_in.as<uint8_t>();
+    uint64_t *p_qh = reinterpret_cast<uint64_t *>(hp), *p_qm = reinterpret_cast<uint64_t *>(hp + o_qm);
+    HitTermsSeg *p_segs = reinterpret_cast<HitTermsSeg *>(hp + o_segs);
+    uint32_t *p_doc = reinterpret_cast<uint32_t *>(hp + o_doc), *p_hit = reinterpret_cast<uint32_t *>(hp + o_hit);
+    uint32_t *p_sub = reinterpret_cast<uint32_t *>(hp + o_sub);
+    std::vector<uint64_t> keys;
+    for (uint32_t q = 0; q <= n_queries; q++) {
+        p_qh[q] = hit_offsets[q] - h0;
+        p_qm[q] = set_offsets[query_set_offsets[q]] - s0;
+    }
+    for (uint32_t q = 0; q < n_queries; q++) {
+        // DocId-keyed: the segment of a hit plays no part; equal local ids stay separate entries, each with its own list
+        const uint64_t b = hit_offsets[q], n = hit_offsets[q + 1] - b;
+        keys.resize(n);
+        for (uint64_t i = 0; i < n; i++) keys[i] = ((hit_docaddr[b + i] & 0xffffffffull) << 32) | i;
+        std::sort(keys.begin(), keys.end());
+        for (uint64_t i = 0; i < n; i++) p_doc[b - h0 + i] = (uint32_t)(keys[i] >> 32), p_hit[b - h0 + i] = (uint32_t)keys[i];
+    }
+    if (n_mem) memcpy(hp + o_mem, set_terms + s0, n_mem * 4);
+    for (size_t r = 0; r < n_res; r++) {
+        const Bm25Segment &sg = idx->segs[r];
+        HitTermsSeg &d = p_segs[r];
+        d.term_offsets = sg.term_offsets.as<unsigned long long>();
+        d.doc_ids = sg.doc_ids.as<uint32_t>();
+        d.reserved = 0;
+        if (cat) {
+            d.sub_base = idx->d_seg_base.as<uint32_t>();
+            d.n_sub = (uint32_t)idx->real.size();
+        } else {
+            p_sub[2 * r] = 0, p_sub[2 * r + 1] = sg.n_docs;
+            d.sub_base = reinterpret_cast<const uint32_t *>(dp + o_sub) + 2 * r;
+            d.n_sub = 1;
+        }
+    }
+    hipStream_t st = idx->main.stream;
+    NIDX_HIP(hipMemcpyAsync(dp, hp, in_bytes, hipMemcpyHostToDevice, st));
+    const size_t off_bytes = (n_hits + 1) * 8, res_bytes = off_bytes + (size_t)n_queries * 16;
+    NIDX_HIP(idx->s_ht_res.reserve(res_bytes + n_hits * 4));
+    NIDX_HIP(idx->h_ht_res.reserve(res_bytes));
+    HitTermsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q_hit_off = reinterpret_cast<const unsigned long long *>(dp);
+    a.q_mem_off = reinterpret_cast<const unsigned long long *>(dp + o_qm);
+    a.ent_doc = reinterpret_cast<const uint32_t *>(dp + o_doc);
+    a.ent_hit = reinterpret_cast<const uint32_t *>(dp + o_hit);
+    a.members = reinterpret_cast<const uint32_t *>(dp + o_mem);
+    a.segs = reinterpret_cast<const HitTermsSeg *>(dp + o_segs);
+    a.n_segs = (uint32_t)n_res;
+    a.min_term_bytes = min_term_bytes;
+    a.dict_offsets = min_term_bytes ? idx->dict_offsets.as<unsigned long long>() : nullptr;
+    unsigned long long *d_off = idx->s_ht_res.as<unsigned long long>();
+    a.qstats = d_off + (n_hits + 1);
+    a.counts = reinterpret_cast<uint32_t *>(idx->s_ht_res.as<uint8_t>() + res_bytes);
+    stats.passes = 1;
+    NIDX_HIP(launch_hit_terms_count(a, n_queries, n_hits, d_off, st));
+    stats.launches += 2;
+    NIDX_HIP(hipMemcpyAsync(idx->h_ht_res.p, idx->s_ht_res.p, res_bytes, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));
+    stats.synchronisations++;
+    const uint64_t *r_off = idx->h_ht_res.as<uint64_t>(), *r_stat = r_off + (n_hits + 1);
+    for (uint32_t q = 0; q < n_queries; q++) stats.postings_read += r_stat[2 * (size_t)q], stats.probes += r_stat[2 * (size_t)q + 1];
+    const uint64_t total = r_off[n_hits], filled = std::min(total, cap);
+    if (total) {
+        NIDX_HIP(idx->s_ht_out.reserve(total * 4));
+        a.offsets = d_off;
+        a.out = idx->s_ht_out.as<uint32_t>();
+        NIDX_HIP(launch_hit_terms_emit(a, n_queries, n_hits, st));
+        stats.launches += 3;
+        for (uint64_t h = 0; h < n_hits; h++)
+            if (r_off[h + 1] - r_off[h] > HIT_TERMS_SORT_CAP) stats.host_finished_hits++;
+        if (!stats.host_finished_hits) {
+            if (filled) NIDX_HIP(hipMemcpyAsync(out_terms, idx->s_ht_out.p, filled * 4, hipMemcpyDeviceToHost, st));
+            NIDX_HIP(hipStreamSynchronize(st));
+        } else {
+            // a list cut by `cap` still needs all of itself to know its smallest ids: the whole concatenation comes over
+            std::vector<uint32_t> all(total);
+            NIDX_HIP(hipMemcpyAsync(all.data(), idx->s_ht_out.p, total * 4, hipMemcpyDeviceToHost, st));
+            NIDX_HIP(hipStreamSynchronize(st));
+            for (uint64_t h = 0; h < n_hits; h++)
+                if (r_off[h + 1] - r_off[h] > HIT_TERMS_SORT_CAP) std::sort(all.begin() + r_off[h], all.begin() + r_off[h + 1]);
+            if (filled) memcpy(out_terms, all.data(), filled * 4);
+        }
+        stats.synchronisations++;
+    }
+    memcpy(out_offsets, r_off, off_bytes);
+    *n_total_out = total;
+    if (stats_out) *stats_out = stats;
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

@@ -686,5 +686,37 @@ hipError_t launch_prefilter_emit(const uint64_t *results, size_t row_stride, uin
                                  const uint32_t *listed_prog, uint32_t n_listed, const unsigned long long *listed_begin, uint32_t begin_stride,
                                  const unsigned long long *listed_end, const uint32_t *seg_base, uint32_t n_real, uint32_t segment, uint64_t *out,
                                  hipStream_t s);
+// ---- nidx_gpu_bm25_hit_terms_batch (bm25_hit_terms.hip): the accepted terms of the fuzzy query that occur in each hit ---------------
+// Query q owns the hits [q_hit_off[q], q_hit_off[q + 1]) and the set members [q_mem_off[q], q_mem_off[q + 1]) (its sets laid end to end).
+// ent_doc = the local doc ids of its hits, ascending per query, ent_hit[i] = which hit of the query entry i is.  A resident posting
+// layout is a HitTermsSeg: sub_base = the n_sub + 1 document bases of the opened segments it concatenates ({0, n_docs} for a layout that
+// holds one segment).  The count pass writes counts[hit] and qstats[q] = {postings streamed, probe steps} and scans counts into
+// offsets[n_hits + 1]; the emit pass writes hit h's ids at out[offsets[h] .. offsets[h + 1]) and orders every list of at most
+// HIT_TERMS_SORT_CAP ids (a longer one stays in emission order: the host orders it).
+#define HIT_TERMS_THREADS 1024
+#define HIT_TERMS_MAX_HITS 513       /* hits of one query: k <= 512, and the paragraph search asks for k + 1 */
+#define HIT_TERMS_STREAM_MAX 4096    /* a posting run up to this long is streamed against the hits in LDS; a longer one is binary-searched per (hit, segment) */
+#define HIT_TERMS_SORT_CAP 2048      /* ids of one hit's list ordered on chip (8 KiB of LDS) */
+struct HitTermsSeg {
+    const unsigned long long *term_offsets;
+    const uint32_t *doc_ids;
+    const uint32_t *sub_base;
+    uint32_t n_sub, reserved;
+};
+struct HitTermsArgs {
+    const unsigned long long *q_hit_off, *q_mem_off;   // [n_queries + 1]
+    const uint32_t *ent_doc, *ent_hit;                 // [n_hits]
+    const uint32_t *members;
+    const HitTermsSeg *segs;
+    uint32_t n_segs;
+    uint32_t min_term_bytes;                           // 0: every term counts and dict_offsets is not read
+    const unsigned long long *dict_offsets;
+    uint32_t *counts;                                  // [n_hits]       (count pass)
+    unsigned long long *qstats;                        // [n_queries][2] (count pass)
+    const unsigned long long *offsets;                 // [n_hits + 1]   (emit pass)
+    uint32_t *out;                                     // (emit pass)
+};
+hipError_t launch_hit_terms_count(const HitTermsArgs &a, uint32_t n_queries, unsigned long long n_hits, unsigned long long *offsets, hipStream_t s);
+hipError_t launch_hit_terms_emit(const HitTermsArgs &a, uint32_t n_queries, unsigned long long n_hits, hipStream_t s);
 
 }  // namespace nidx

@@ -933,6 +933,9 @@ class ParagraphResult:
     score: Optional[ResultScore]
     labels: List[str]
     sort_value: Optional[int] = None
+    # the dictionary terms the fuzzy query's automata accepted that occur in the hit (search_response.rs:180-191, :275-287), sorted
+    # bytewise, a term two fuzzy words accept twice; empty for hits of the keyword query
+    matches: List[str] = field(default_factory=list)
 
 
 @dataclass
@@ -943,6 +946,7 @@ class ParagraphSearchResponse:
     query: str
     facets: Dict[str, List[FacetResult]] = field(default_factory=dict)
     fuzzy: bool = False  # the hits come from the fuzzy fallback query
+    ematches: List[str] = field(default_factory=list)   # the exact words of the query (search_response.rs:213, :308), sorted here
 
 
 def parse_query(body: str, stop_words: Optional[Set[str]] = None) -> List[Tuple[str, str]]:
@@ -998,7 +1002,19 @@ def parse_query(body: str, stop_words: Optional[Set[str]] = None) -> List[Tuple[
     return tokens
 
 
+def paragraph_ematches(tokens: Sequence[Tuple[str, str]], fuzzy_rerun: bool, suggest: bool = False, only_faceted: bool = False) -> List[str]:
+    """ParagraphSearchResponse::ematches as a function of the parsed tokens and of which query answered.  eterms = the values of the
+    Literal and Quoted tokens after stop-word removal, as a set (query_parser.rs:69-82).  `search` (reader.rs:104-139): every
+    do_search TAKES the collector (get_termc is a mem::take), so the keyword response carries them and the fuzzy re-run finds the
+    collector empty; `suggest` (reader.rs:58-90) takes it once, at the end: always.  only_faceted responses have no such field
+    filled.  The reference's set has no order; sorted here."""
+    if only_faceted or (fuzzy_rerun and not suggest):
+        return []
+    return sorted({w for kind, w in tokens if kind in ("literal", "quoted")})
+
+
 MIN_FUZZY_LEN = 3          # fuzzy_parser.rs:35
+MIN_TERM_MATCH_BYTES = 3   # search_query.rs:65: get_fterms keeps terms of more than two bytes
 MIN_FUZZY_PREFIX_LEN = 4   # fuzzy_parser.rs:39
 FUZZY_BOOST = 0.5          # search_query.rs:235-239
 SUGGEST_RESULTS_PER_PAGE = 10   # reader.rs:86
@@ -1199,9 +1215,24 @@ class ParagraphSearcher:
             clauses.append(Clause(0, _lib.OCCUR_SHOULD_GROUP, _lib.CONST_SCORE, boost, term_set=members))
         return clauses + self._filters(request, prefilter, boost)
 
-    def _run(self, request: ParagraphSearchRequest, clauses: List[Clause], fuzzy: bool) -> ParagraphSearchResponse:
-        """Searcher::do_search (reader.rs:244-348) + the response assembly (search_response.rs:218-311)."""
+    def _set_matches(self, items: Sequence[Tuple[List[ParagraphResult], List[int], List[List[int]]]]) -> None:
+        """ParagraphResult::matches of every (results, their DocAddresses, the fuzzy words' term sets) in ONE hit_terms_batch call:
+        TermCollector::get_fterms (search_query.rs:57-70) + terms.sort().  The term ids of this mirror are in insertion order, so the
+        bytewise sort happens here, on the strings."""
+        items = [it for it in items if it[0] and any(len(members) for members in it[2])]   # (no hit or no accepted term: nothing can match)
+        if not items:
+            return
+        lists = self._index.searcher.hit_terms_batch([addrs for _, addrs, _ in items], [sets for _, _, sets in items], MIN_TERM_MATCH_BYTES)
+        for (results, _, _), per_hit in zip(items, lists):
+            for res, ids in zip(results, per_hit):
+                res.matches = sorted((self._index.terms[int(t)] for t in ids), key=lambda t: t.encode("utf-8"))
+
+    def _run(self, request: ParagraphSearchRequest, clauses: List[Clause], fuzzy: bool,
+             fuzzy_sets: Optional[List[List[int]]] = None) -> ParagraphSearchResponse:
+        """Searcher::do_search (reader.rs:244-348) + the response assembly (search_response.rs:218-311).  `fuzzy_sets` = the accepted
+        terms of every fuzzy word when `clauses` is the fuzzy query: its hits get their `matches`."""
         k = max(0, int(request.result_per_page))
+        ematches = paragraph_ematches(self._tokens(request), fuzzy, only_faceted=request.only_faceted)
         facets, pairs = self._index.facet_request(request.faceted)
         fterms = [[tid for _, _, tid in pairs]] if pairs else None
         if request.only_faceted:
@@ -1214,12 +1245,15 @@ class ParagraphSearcher:
         docaddr, score, total = r["docaddr"], r["score"], r["total"]
         obtained = int(r["count"][0])
         fc = self._index.produce_facets(facets, pairs, r["facet_counts"][0]) if pairs else {}
-        results = []
+        results, addrs = [], []
         if order is not None:  # SearchIntResponse: no min_score, next_page = total > requested
             for i in range(min(obtained, k)):
                 d = self._index.doc(int(docaddr[0, i]))
                 results.append(ParagraphResult(d.uuid, d.field, d.text, None, list(d.labels), sort_value=int(r["order_value"][0, i])))
-            return ParagraphSearchResponse(int(total[0]), results, int(total[0]) > k, request.body, fc, fuzzy)
+                addrs.append(int(docaddr[0, i]))
+            if fuzzy_sets is not None:
+                self._set_matches([(results, addrs, fuzzy_sets)])
+            return ParagraphSearchResponse(int(total[0]), results, int(total[0]) > k, request.body, fc, fuzzy, ematches)
         scores = [float(score[0, i]) for i in range(obtained)]
         # search_response.rs:218-311: next_page counts scores above min_score, results stop at the first below it
         next_page = sum(1 for s in scores if s > request.min_score) > k
@@ -1228,7 +1262,10 @@ class ParagraphSearcher:
                 break
             d = self._index.doc(int(docaddr[0, i]))
             results.append(ParagraphResult(d.uuid, d.field, d.text, ResultScore(scores[i], int(docaddr[0, i])), list(d.labels)))
-        return ParagraphSearchResponse(int(total[0]), results, next_page, request.body, fc, fuzzy)
+            addrs.append(int(docaddr[0, i]))
+        if fuzzy_sets is not None:
+            self._set_matches([(results, addrs, fuzzy_sets)])
+        return ParagraphSearchResponse(int(total[0]), results, next_page, request.body, fc, fuzzy, ematches)
 
     def search(self, request: ParagraphSearchRequest, prefilter: Optional[PrefilterResult] = None) -> ParagraphSearchResponse:
         """ParagraphReaderService::search (reader.rs:104-139): the keyword query first; when it finds nothing (and results
@@ -1238,7 +1275,17 @@ class ParagraphSearcher:
             return ParagraphSearchResponse(0, [], False, request.body, {}, False)
         response = self._run(request, self._clauses(request, prefilter), False)
         if not response.results and request.result_per_page > 0 and request.min_score == 0.0 and not request.only_faceted:
-            response = self._run(request, self._fuzzy_clauses(request, prefilter), True)
+            expanded: Dict[Tuple[str, bool], List[int]] = {}
+
+            def expand(word: str, prefix: bool) -> List[int]:
+                if (word, prefix) not in expanded:
+                    expanded[(word, prefix)] = self._index.fuzzy_terms(word, prefix)
+                return expanded[(word, prefix)]
+
+            clauses = self._fuzzy_clauses(request, prefilter, expand)
+            # one FuzzyTermQuery per fuzzy word, each logging on its own: a word given twice is two sets
+            sets = [expand(*key) for key in self._fuzzy_words(self._tokens(request)).values()]
+            response = self._run(request, clauses, True, sets)
         return response
 
     # ---- suggest ------------------------------------------------------------------------------------------------------------
@@ -1257,7 +1304,8 @@ class ParagraphSearcher:
         return self._clauses(inner, prefilter), self._fuzzy_clauses(inner, prefilter, expand)
 
     def _suggest_response(self, request: ParagraphSuggestRequest, r, row: int, obtained: int, fuzzy: bool) -> ParagraphSearchResponse:
-        """search_response.rs:218-311 with results_per_page = 10 and min_score = 0 (reader.rs:78-89): total = the hits obtained."""
+        """search_response.rs:218-311 with results_per_page = 10 and min_score = 0 (reader.rs:78-89): total = the hits obtained.  The
+        collector is taken once, here at the end: ematches whichever query answered (`matches` are filled by the caller)."""
         scores = [float(r["score"][row, i]) for i in range(obtained)]
         results = []
         for i in range(min(obtained, SUGGEST_RESULTS_PER_PAGE)):
@@ -1265,14 +1313,15 @@ class ParagraphSearcher:
             d = self._index.doc(addr)
             results.append(ParagraphResult(d.uuid, d.field, d.text, ResultScore(scores[i], addr), list(d.labels)))
         next_page = sum(1 for s in scores if s > 0.0) > SUGGEST_RESULTS_PER_PAGE
-        return ParagraphSearchResponse(obtained, results, next_page, request.body, {}, fuzzy)
+        ematches = paragraph_ematches(self._tokens(self._suggest_as_search(request)), fuzzy, suggest=True)
+        return ParagraphSearchResponse(obtained, results, next_page, request.body, {}, fuzzy, ematches)
 
     def suggest_batch(self, requests: Sequence[ParagraphSuggestRequest],
                       prefilters: Optional[Sequence[Optional[PrefilterResult]]] = None) -> List[ParagraphSearchResponse]:
-        """ParagraphReaderService::suggest (reader.rs:58-90) for a batch of type-ahead requests in at most three library calls: every
+        """ParagraphReaderService::suggest (reader.rs:58-90) for a batch of type-ahead requests in at most four library calls: every
         keyword query in one search (TopDocs of the largest top_k: a larger TopDocs has the smaller one as its prefix), the fuzzy
         expansion of every distinct (word, prefix) of the requests that found nothing in one fuzzy_terms_batch, their fuzzy queries
-        in one search.  top_k == 0 asks for nothing (query_planner/suggest.rs:36-39) and a prefilter of kind None matches nothing:
+        in one search, the `matches` of all their hits in one hit_terms_batch.  top_k == 0 asks for nothing (query_planner/suggest.rs:36-39) and a prefilter of kind None matches nothing:
         both are answered without a search."""
         n = len(requests)
         prefilters = [None] * n if prefilters is None else list(prefilters)
@@ -1308,8 +1357,12 @@ class ParagraphSearcher:
                 pairs[key] = members
         fuzzy = [self._fuzzy_clauses(inner[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in missed]
         r = self._index.searcher.search_batch_ex(fuzzy, max(int(requests[i].top_k) for i in missed))
+        items = []
         for row, i in enumerate(missed):
             out[i] = self._suggest_response(requests[i], r, row, min(int(r["count"][row]), int(requests[i].top_k)), True)
+            sets = [pairs[key] for key in self._fuzzy_words(self._tokens(inner[i])).values()]
+            items.append((out[i].results, [res.score.docaddr for res in out[i].results], sets))
+        self._set_matches(items)
         return out
 
     def suggest(self, request: ParagraphSuggestRequest, prefilter: Optional[PrefilterResult] = None) -> ParagraphSearchResponse:
