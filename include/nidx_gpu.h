@@ -60,6 +60,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_FUZZY_BATCH 8 /* nidx_gpu_bm25_fuzzy_terms_batch */
 #define NIDX_FEATURE_BM25_PREFILTER_BATCH 16 /* nidx_gpu_bm25_prefilter_batch */
 #define NIDX_FEATURE_BM25_HIT_TERMS 32 /* nidx_gpu_bm25_hit_terms_batch */
+#define NIDX_FEATURE_PREFILTER_HANDOVER 64 /* nidx_gpu_bm25_prefilter_batch_resident, nidx_gpu_prefilter_rows_* / _link_*, nidx_gpu_vector_search_prefiltered_per_query */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -961,6 +962,89 @@ int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_g
                                       uint64_t max_scratch_bytes, uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr,
                                       uint64_t capacity, uint64_t *n_total_out, uint64_t *num_docs_out,
                                       nidx_gpu_bm25_prefilter_batch_stats_t *stats_out);
+
+/* ---- the prefilter hand-over: a batch's prefilter results go to the vector search without leaving the device ----------------------
+ * In the reference PrefilterResult::Some(fields) becomes a KeyPrefixSet clause of the vector search's formula
+ * (nidx/src/searcher/shard_search.rs:251-275, nidx_vector/src/searcher.rs:298-313, inverted_index/paragraph.rs:147-151).  Three
+ * pieces do that here, all present when nidx_gpu_build_features() & NIDX_FEATURE_PREFILTER_HANDOVER:
+ *
+ * 1. nidx_gpu_bm25_prefilter_batch_resident: nidx_gpu_bm25_prefilter_batch (same plan, passes, fallbacks, checks, out_matching and
+ *    num_docs_out) that scans, emits and transfers no list.  The result row (one bit per document of every resident segment, already
+ *    & alive) of every distinct program that is Some (0 < matching < num_docs) is copied device to device into memory the handle
+ *    *rows_out owns; the handle knows the row of every request, or that the request is All or None (those own no row), the index's
+ *    generation and the row layout.  The stream is synchronised before the call returns: other streams may read the rows.  The rows
+ *    stay valid (and keep their generation) after nidx_gpu_bm25_sync or a close of the index.  Rows that together exceed
+ *    max_rows_bytes (0 = 2 GiB): NIDX_ERR_UNSUPPORTED (split the batch), no handle, nothing stays allocated.
+ *    nidx_gpu_prefilter_rows_read: the DocAddresses of one request, ascending, as nidx_gpu_bm25_prefilter lists them (at most
+ *    `capacity`; *n_out = the full count; an All or None request gives 0) — a host loop over the downloaded row, for tests and debugging.
+ *
+ * 2. nidx_gpu_prefilter_link_create: which posting lists of the vector index's segments belong to which text document.  The caller
+ *    gives every document's field key per OPENED text segment (doc_key_offsets[s] is [n_docs + 1]; an empty key links to nothing), in
+ *    the encoding of the vector segments' key tables (nidx_gpu_vector_set_filter_keys).  List j of a vector segment is linked to
+ *    document d when key j equals d's key or — child_separator >= 0 — starts with d's key followed by that byte (-1: equality only).
+ *    A vector segment without a key table links to nothing.  The link lives in HBM as a CSR over the bit positions of a prefilter row:
+ *    document -> its (vector segment, list) entries; it records both indexes' generations and is stale (refused by the search) after
+ *    a sync of either.  The two indexes must be on the same device (NIDX_ERR_INVALID_ARGUMENT otherwise).
+ *    nidx_gpu_prefilter_link_read: for tests, the (DocAddress, list) pairs of one vector segment, ascending by (DocAddress, list).
+ *
+ * 3. nidx_gpu_vector_search_prefiltered_per_query: nidx_gpu_vector_search_filtered_per_query whose programs may hold
+ *    NIDX_FILTER_PUSH_PREFILTER (a, b unused).  In a program of filter f it pushes the bitset of the segment's paragraphs that lie in
+ *    lists linked to a document set in the row of request prefilter_of_filter[f] (a None request: the empty set, an All request:
+ *    every paragraph).  The distinct rows a chunk of the batch names are projected onto all segments by ONE launch
+ *    (vector_prefilter.hip) into operand rows that the filters naming the same row share; their bytes count against the chunk's
+ *    scratch cap.  A program deeper than 32 is evaluated op by op with one launch of the same kernel for its row.  Before anything is
+ *    launched or written, NIDX_ERR_INVALID_ARGUMENT for: a link whose vector generation is not the index's, rows whose generation
+ *    or layout is not the link's, a request index out of range, PUSH_PREFILTER in a filter whose prefilter_of_filter is UINT32_MAX
+ *    (prefilter_of_filter NULL: every entry UINT32_MAX) — the message names the filter.  link and rows may be NULL when no program
+ *    holds the op.  Every other entry answers "unknown op" to it. */
+#define NIDX_FILTER_PUSH_PREFILTER 8
+typedef struct nidx_gpu_prefilter_rows nidx_gpu_prefilter_rows_t;
+typedef struct nidx_gpu_prefilter_link nidx_gpu_prefilter_link_t;
+typedef struct nidx_gpu_prefilter_rows_info {
+    uint32_t requests;   /* requests of the batch */
+    uint32_t rows;       /* resident rows: the distinct programs that are Some */
+    uint64_t bytes;      /* HBM the rows take */
+    uint64_t generation; /* nidx_gpu_bm25_generation when the batch was evaluated */
+    uint64_t row_words;  /* 64-bit words of one row */
+} nidx_gpu_prefilter_rows_info_t;
+int32_t nidx_gpu_bm25_prefilter_batch_resident(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
+                                               uint64_t max_scratch_bytes, uint64_t max_rows_bytes, uint64_t *out_matching,
+                                               uint64_t *num_docs_out, nidx_gpu_bm25_prefilter_batch_stats_t *stats_out,
+                                               nidx_gpu_prefilter_rows_t **rows_out);
+void nidx_gpu_prefilter_rows_free(nidx_gpu_prefilter_rows_t *rows);
+int32_t nidx_gpu_prefilter_rows_info(const nidx_gpu_prefilter_rows_t *rows, nidx_gpu_prefilter_rows_info_t *info_out);
+int32_t nidx_gpu_prefilter_rows_read(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint64_t *out_docaddr, uint64_t capacity,
+                                     uint64_t *n_out);
+
+typedef struct nidx_gpu_prefilter_link_stats {
+    uint64_t linked_documents; /* documents with at least one entry */
+    uint64_t entries;          /* (vector segment, list) entries over all documents */
+    uint64_t bytes;            /* HBM the link takes */
+    uint64_t bm25_generation, vector_generation;
+} nidx_gpu_prefilter_link_stats_t;
+int32_t nidx_gpu_prefilter_link_create(nidx_gpu_bm25_index_t *bm25_index, nidx_gpu_vector_index_t *vector_index,
+                                       const uint8_t *const *doc_key_bytes, const uint64_t *const *doc_key_offsets, uint32_t n_text_segments,
+                                       int32_t child_separator, nidx_gpu_prefilter_link_t **link_out,
+                                       nidx_gpu_prefilter_link_stats_t *stats_out);
+void nidx_gpu_prefilter_link_free(nidx_gpu_prefilter_link_t *link);
+int32_t nidx_gpu_prefilter_link_read(const nidx_gpu_prefilter_link_t *link, uint32_t vector_segment, uint64_t *out_docaddr, uint32_t *out_list,
+                                     uint64_t capacity, uint64_t *n_out);
+
+typedef struct nidx_gpu_prefilter_search_stats {
+    uint32_t rows_projected;       /* distinct prefilter rows projected, over all chunks and deep programs */
+    uint32_t projection_launches;  /* one per chunk that names a row, plus one per deep program and segment with the op */
+    uint32_t chunks;               /* chunks of queries the batch was cut into */
+    uint32_t filter_synchronisations; /* stream synchronisations of the filter stage (one per chunk, one per deep program and segment) */
+    uint64_t documents_visited;    /* set bits of the projected rows */
+    uint64_t paragraphs_written;   /* paragraph ids ORed into operand rows */
+} nidx_gpu_prefilter_search_stats_t;
+int32_t nidx_gpu_vector_search_prefiltered_per_query(nidx_gpu_vector_index_t *index, const nidx_gpu_prefilter_link_t *link,
+                                                     const nidx_gpu_prefilter_rows_t *rows, const float *queries, uint32_t n_queries,
+                                                     uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                     const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                     const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint32_t *out_segment,
+                                                     uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                                                     int32_t *out_method, uint64_t *out_matching, nidx_gpu_prefilter_search_stats_t *stats_out);
 
 /* open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74), the device half: the caller maps the deletion keys that
  * are newer than the segment (`Seq(segment) < del_seq`) to term ids the way the DeletionQueryBuilders do (a key longer than 32

@@ -156,6 +156,8 @@ FEATURE_BM25_SYNC = 2     # nidx_gpu_build_features() bit: nidx_gpu_bm25_sync / 
 FEATURE_BM25_FUZZY_BATCH = 8   # nidx_gpu_build_features() bit: nidx_gpu_bm25_fuzzy_terms_batch
 FEATURE_BM25_PREFILTER_BATCH = 16   # nidx_gpu_build_features() bit: nidx_gpu_bm25_prefilter_batch
 FEATURE_BM25_HIT_TERMS = 32   # nidx_gpu_build_features() bit: nidx_gpu_bm25_hit_terms_batch
+FEATURE_PREFILTER_HANDOVER = 64   # nidx_gpu_build_features() bit: resident prefilter rows, the text-to-vector link, nidx_gpu_vector_search_prefiltered_per_query
+FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
 
@@ -186,6 +188,23 @@ class Bm25PrefilterBatchStatsC(C.Structure):
     """nidx_gpu_bm25_prefilter_batch_stats_t"""
     _fields_ = [("distinct_programs", C.c_uint32), ("operand_rows", C.c_uint32), ("passes", C.c_uint32), ("fallback_requests", C.c_uint32),
                 ("launches", C.c_uint32), ("synchronisations", C.c_uint32)]
+
+
+class PrefilterRowsInfoC(C.Structure):
+    """nidx_gpu_prefilter_rows_info_t"""
+    _fields_ = [("requests", C.c_uint32), ("rows", C.c_uint32), ("bytes", C.c_uint64), ("generation", C.c_uint64), ("row_words", C.c_uint64)]
+
+
+class PrefilterLinkStatsC(C.Structure):
+    """nidx_gpu_prefilter_link_stats_t"""
+    _fields_ = [("linked_documents", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64), ("bm25_generation", C.c_uint64),
+                ("vector_generation", C.c_uint64)]
+
+
+class PrefilterSearchStatsC(C.Structure):
+    """nidx_gpu_prefilter_search_stats_t"""
+    _fields_ = [("rows_projected", C.c_uint32), ("projection_launches", C.c_uint32), ("chunks", C.c_uint32), ("filter_synchronisations", C.c_uint32),
+                ("documents_visited", C.c_uint64), ("paragraphs_written", C.c_uint64)]
 
 
 class Bm25HitTermsStatsC(C.Structure):
@@ -354,6 +373,19 @@ SIGNATURES = {
     "nidx_gpu_bm25_prefilter": (C.c_int32, [C.c_void_p, C.POINTER(Bm25PrefilterC), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nidx_gpu_bm25_prefilter_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(Bm25PrefilterBatchStatsC)]),
+    "nidx_gpu_bm25_prefilter_batch_resident": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                           C.POINTER(C.c_uint64), C.POINTER(Bm25PrefilterBatchStatsC), C.POINTER(C.c_void_p)]),
+    "nidx_gpu_prefilter_rows_free": (None, [C.c_void_p]),
+    "nidx_gpu_prefilter_rows_info": (C.c_int32, [C.c_void_p, C.POINTER(PrefilterRowsInfoC)]),
+    "nidx_gpu_prefilter_rows_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_prefilter_link_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p),
+                                                   C.POINTER(PrefilterLinkStatsC)]),
+    "nidx_gpu_prefilter_link_free": (None, [C.c_void_p]),
+    "nidx_gpu_prefilter_link_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_prefiltered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                 C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                 C.POINTER(PrefilterSearchStatsC)]),
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),

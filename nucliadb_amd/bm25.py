@@ -220,6 +220,53 @@ def prefilter_requests_c(requests: Sequence[Tuple]):
     return c_reqs, keep
 
 
+class ResidentPrefilters:
+    """The prefilter results of a batch, resident in HBM (nidx_gpu_prefilter_rows_t): what VectorSearcher.search_many takes instead of
+    the host PrefilterResults.  kinds[i] is "All", "None" or "Some"; only Some requests own a row on the device.  `request_of[i]` is
+    request i's index in the handle (None: the request had neither security nor expression and never reached the library) and
+    `same_as[i]` the first request with the same program (its row is the same row).  The rows own their memory: they outlive a sync or
+    a close of the index they came from, and are freed by close()."""
+
+    def __init__(self, handle, kinds, matching, live, stats=None, request_of=None, same_as=None):
+        self.handle = handle
+        self.kinds = list(kinds)
+        self.matching = matching
+        self.live = live
+        self.stats = stats
+        self.request_of = list(range(len(self.kinds))) if request_of is None else list(request_of)
+        self.same_as = list(range(len(self.kinds))) if same_as is None else list(same_as)
+
+    def __len__(self):
+        return len(self.kinds)
+
+    def info(self) -> "_lib.PrefilterRowsInfoC":
+        out = _lib.PrefilterRowsInfoC()
+        _lib.check(_lib.lib().nidx_gpu_prefilter_rows_info(self.handle, C.byref(out)))
+        return out
+
+    def read(self, i: int) -> np.ndarray:
+        """The ascending docaddrs of request i's row (empty for All and None), read back from the device: tests and debugging."""
+        r = self.request_of[i]
+        if r is None or not self.handle:
+            return np.zeros(0, np.uint64)
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_rows_read(self.handle, r, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), np.uint64)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_rows_read(self.handle, r, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().nidx_gpu_prefilter_rows_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Bm25Searcher:
     """The scoring core shared by TextSearcher::search and ParagraphSearcher::search."""
 
@@ -437,6 +484,21 @@ class Bm25Searcher:
             if total.value <= cap:
                 return matching, [out[int(offs[i]): int(offs[i + 1])].copy() for i in range(n)], live.value, stats
             cap = total.value
+
+    def prefilter_batch_resident(self, requests: Sequence[Tuple], max_scratch_bytes: int = 0, max_rows_bytes: int = 0) -> ResidentPrefilters:
+        """prefilter_batch whose Some results stay on the device (nidx_gpu_bm25_prefilter_batch_resident): no list is emitted or
+        transferred; the rows go to VectorSearcher.search_many through the returned ResidentPrefilters."""
+        n = len(requests)
+        c_reqs, _keep = prefilter_requests_c(requests)
+        matching = np.zeros(n, np.uint64)
+        live = C.c_uint64(0)
+        stats = _lib.Bm25PrefilterBatchStatsC()
+        handle = C.c_void_p()
+        _lib.check(_lib.lib().nidx_gpu_bm25_prefilter_batch_resident(self._handle, C.addressof(c_reqs) if n else None, n, int(max_scratch_bytes),
+                                                                     int(max_rows_bytes), matching.ctypes.data if n else None, C.byref(live),
+                                                                     C.byref(stats), C.byref(handle)))
+        kinds = ["None" if int(m) == 0 else "All" if int(m) == live.value else "Some" for m in matching]
+        return ResidentPrefilters(handle, kinds, matching, live.value, stats)
 
     def search_batch_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
                         order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None):

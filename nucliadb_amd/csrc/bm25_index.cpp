@@ -21,6 +21,7 @@
 #include "device_common.h"
 #include "host_common.h"
 #include "kernels.h"
+#include "prefilter_handover.h"
 
 namespace nidx {
 
@@ -961,8 +962,9 @@ static int32_t bm25_segment_live(Bm25Index *idx, Bm25Segment &seg) {
 }
 
 // The op-by-op evaluation of one validated request (the caller holds idx->mu and has set the device).
+// With d_row_out nothing is listed: segment si's result words (already & alive) go to d_row_out + word0[si] instead, device to device.
 static int32_t bm25_prefilter_locked(Bm25Index *idx, const nidx_gpu_bm25_prefilter_t *req, int max_depth, uint64_t *out_docaddr, uint64_t capacity,
-                                     uint64_t *n_matching, uint64_t *num_docs) {
+                                     uint64_t *n_matching, uint64_t *num_docs, uint64_t *d_row_out = nullptr, const size_t *word0 = nullptr) {
     const nidx_gpu_filter_program_t &prog = req->program;
     int depth = 0;
     hipStream_t st = idx->main.stream;
@@ -1049,12 +1051,15 @@ static int32_t bm25_prefilter_locked(Bm25Index *idx, const nidx_gpu_bm25_prefilt
         NIDX_HIP(hipMemsetAsync(d_total, 0, 16, st));
         NIDX_HIP(launch_bitset_and_count(slot(0), seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), idx->s_pf_result.as<uint64_t>(), words,
                                          d_total, st));
-        NIDX_HIP(launch_bitset_to_docaddr(idx->s_pf_result.as<uint64_t>(), words, (uint32_t)si, idx->s_pf_blocks.as<uint32_t>(), d_total + 1,
-                                          matched, capacity, idx->s_pf_out.as<uint64_t>(), st));
+        if (d_row_out)
+            NIDX_HIP(hipMemcpyAsync(d_row_out + word0[si], idx->s_pf_result.p, (size_t)words * 8, hipMemcpyDeviceToDevice, st));
+        else
+            NIDX_HIP(launch_bitset_to_docaddr(idx->s_pf_result.as<uint64_t>(), words, (uint32_t)si, idx->s_pf_blocks.as<uint32_t>(), d_total + 1,
+                                              matched, capacity, idx->s_pf_out.as<uint64_t>(), st));
         unsigned long long c[2] = {0, 0};
         NIDX_HIP(hipMemcpyAsync(c, d_total, 16, hipMemcpyDeviceToHost, st));
         NIDX_HIP(hipStreamSynchronize(st));
-        if (c[0] != c[1]) return fail(NIDX_ERR_DEVICE, "prefilter: count mismatch (%llu vs %llu)", c[0], c[1]);
+        if (!d_row_out && c[0] != c[1]) return fail(NIDX_ERR_DEVICE, "prefilter: count mismatch (%llu vs %llu)", c[0], c[1]);
         matched += c[0];
     }
     const uint64_t n_copy = std::min<uint64_t>(matched, capacity);
@@ -1098,15 +1103,13 @@ struct PfProgram {
 };
 }  // namespace
 
-int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
-                                      uint64_t max_scratch_bytes, uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr,
-                                      uint64_t capacity, uint64_t *n_total_out, uint64_t *num_docs_out,
-                                      nidx_gpu_bm25_prefilter_batch_stats_t *stats_out) try {
-    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
-    if (!idx || !out_offsets || !n_total_out || (n_requests && (!requests || !out_matching)) || (capacity && !out_docaddr))
-        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    NIDX_HIP(hipSetDevice(idx->device));
+// nidx_gpu_bm25_prefilter_batch and nidx_gpu_bm25_prefilter_batch_resident (the caller holds idx->mu and has set the device).  With
+// `resident` no list is scanned, emitted or transferred (out_offsets, out_docaddr and n_total_out are not written): the result row of
+// every distinct program that is Some is copied device to device into memory `resident` owns, at most max_rows_bytes of it.
+static int32_t bm25_prefilter_batch_locked(Bm25Index *idx, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests, uint64_t max_scratch_bytes,
+                                           uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr, uint64_t capacity,
+                                           uint64_t *n_total_out, uint64_t *num_docs_out, nidx_gpu_bm25_prefilter_batch_stats_t *stats_out,
+                                           PrefilterRows *resident, uint64_t max_rows_bytes) {
     // ---- every request is checked before anything is launched or written
     std::vector<int> depth_of(n_requests, 1);
     for (uint32_t i = 0; i < n_requests; i++) {
@@ -1265,14 +1268,36 @@ int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_g
         if (!cur.empty()) passes.push_back(cur);
     }
     // ---- the fallback programs' counts first: every offset below follows from the counts of the requests before it
-    for (PfProgram &pg : programs) {
+    auto list_len = [&](const PfProgram &pg) -> uint64_t { return pg.matching > 0 && pg.matching < live ? pg.matching : 0; };
+    // resident rows: the row of every distinct program that is Some
+    const uint64_t rows_budget = max_rows_bytes ? max_rows_bytes : (2ull << 30);
+    std::vector<uint32_t> row_of_program(programs.size(), kPrefilterRowNone);
+    auto rows_fit = [&](uint64_t n_rows) -> int32_t {
+        if (resident->bytes + n_rows * row_bytes <= rows_budget) return NIDX_OK;
+        return fail(NIDX_ERR_UNSUPPORTED, "prefilter batch: the resident rows need more than %llu bytes (%llu bytes per row): split the batch",
+                    (unsigned long long)rows_budget, (unsigned long long)row_bytes);
+    };
+    for (size_t p = 0; p < programs.size(); p++) {
+        PfProgram &pg = programs[p];
         if (W == 0) pg.counted = true;   // an index without documents: nothing matches
         if (!pg.fallback) continue;
         uint64_t lv = 0;
-        if (int32_t rc = bm25_prefilter_locked(idx, &requests[pg.first_request], pg.max_depth, nullptr, 0, &pg.matching, &lv)) return rc;
+        DevBuf row;
+        if (resident) {
+            if (int32_t rc = rows_fit(1)) return rc;
+            NIDX_HIP(row.alloc((size_t)row_bytes));
+        }
+        if (int32_t rc = bm25_prefilter_locked(idx, &requests[pg.first_request], pg.max_depth, nullptr, 0, &pg.matching, &lv, row.as<uint64_t>(),
+                                               word0.data()))
+            return rc;
         pg.counted = true;
+        if (resident && list_len(pg)) {
+            row_of_program[p] = (uint32_t)resident->row_ptr.size();
+            resident->row_ptr.push_back(row.as<uint64_t>());
+            resident->bytes += row_bytes;
+            resident->chunks.push_back(std::move(row));
+        }
     }
-    auto list_len = [&](const PfProgram &pg) -> uint64_t { return pg.matching > 0 && pg.matching < live ? pg.matching : 0; };
     std::vector<uint64_t> offsets((size_t)n_requests + 1, 0);
     uint32_t known = 0;   // offsets[0 .. known] are final
     auto advance = [&]() {
@@ -1414,6 +1439,25 @@ int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_g
             pg.counted = true;
         }
         advance();
+        if (resident) {   // the Some rows of the pass, device to device into one allocation
+            uint64_t n_some = 0;
+            for (uint32_t j = 0; j < P; j++) n_some += list_len(programs[pass[j]]) ? 1 : 0;
+            if (!n_some) continue;
+            if (int32_t rc = rows_fit(n_some)) return rc;
+            DevBuf chunk;
+            NIDX_HIP(chunk.alloc((size_t)(n_some * row_bytes)));
+            uint64_t at_row = 0;
+            for (uint32_t j = 0; j < P; j++) {
+                if (!list_len(programs[pass[j]])) continue;
+                uint64_t *dst = chunk.as<uint64_t>() + (size_t)at_row++ * W;
+                NIDX_HIP(hipMemcpyAsync(dst, d_results + (size_t)j * W, (size_t)row_bytes, hipMemcpyDeviceToDevice, st));
+                row_of_program[pass[j]] = (uint32_t)resident->row_ptr.size();
+                resident->row_ptr.push_back(dst);
+            }
+            resident->bytes += n_some * row_bytes;
+            resident->chunks.push_back(std::move(chunk));
+            continue;
+        }
         // the listed programs: Some (neither nothing nor everything) and a first request that starts below the capacity.  Their slices
         // follow each other in the pass's output like their first requests do in the caller's.
         listed.clear();
@@ -1467,6 +1511,20 @@ int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_g
     }
     advance();
     if (known != n_requests) return fail(NIDX_ERR_DEVICE, "prefilter batch: %u of %u requests were not evaluated", n_requests - known, n_requests);
+    if (resident) {
+        NIDX_HIP(hipStreamSynchronize(st));   // the rows are complete: other streams may read them
+        stats.synchronisations++;
+        resident->row_of_request.resize(n_requests);
+        for (uint32_t i = 0; i < n_requests; i++) {
+            const PfProgram &pg = programs[program_of[i]];
+            out_matching[i] = pg.matching;
+            if (pg.fallback) stats.fallback_requests++;
+            resident->row_of_request[i] = list_len(pg) ? row_of_program[program_of[i]] : (pg.matching ? kPrefilterRowAll : kPrefilterRowNone);
+        }
+        if (num_docs_out) *num_docs_out = live;
+        if (stats_out) *stats_out = stats;
+        return NIDX_OK;
+    }
     // the lists of the fallback programs, then every repeated request's copy of its program's list
     for (const PfProgram &pg : programs) {
         const uint64_t len = list_len(pg), off = offsets[pg.first_request];
@@ -1490,9 +1548,107 @@ int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_g
     if (num_docs_out) *num_docs_out = live;
     if (stats_out) *stats_out = stats;
     return NIDX_OK;
+}
+
+int32_t nidx_gpu_bm25_prefilter_batch(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
+                                      uint64_t max_scratch_bytes, uint64_t *out_matching, uint64_t *out_offsets, uint64_t *out_docaddr,
+                                      uint64_t capacity, uint64_t *n_total_out, uint64_t *num_docs_out,
+                                      nidx_gpu_bm25_prefilter_batch_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !out_offsets || !n_total_out || (n_requests && (!requests || !out_matching)) || (capacity && !out_docaddr))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    return bm25_prefilter_batch_locked(idx, requests, n_requests, max_scratch_bytes, out_matching, out_offsets, out_docaddr, capacity, n_total_out,
+                                       num_docs_out, stats_out, nullptr, 0);
+} NIDX_ABI_CATCH
+
+// ---- the resident form: the rows stay in HBM for nidx_gpu_vector_search_prefiltered_per_query (prefilter_handover.h) --------------
+static void bm25_row_layout_locked(const Bm25Index *idx, PrefilterRowLayout &layout) {
+    const size_t S = idx->segs.size();
+    layout.word0.assign(S + 1, 0);
+    layout.seg_docs.resize(S);
+    for (size_t s = 0; s < S; s++) {
+        layout.seg_docs[s] = idx->segs[s].n_docs;
+        layout.word0[s + 1] = layout.word0[s] + ((uint64_t)idx->segs[s].n_docs + 63) / 64;
+    }
+    layout.seg_base = idx->concatenated() ? idx->seg_base : std::vector<uint32_t>();
+    layout.n_opened = idx->concatenated() ? (uint32_t)idx->real.size() : (uint32_t)S;
+}
+
+int32_t nidx_gpu_bm25_prefilter_batch_resident(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_prefilter_t *requests, uint32_t n_requests,
+                                               uint64_t max_scratch_bytes, uint64_t max_rows_bytes, uint64_t *out_matching,
+                                               uint64_t *num_docs_out, nidx_gpu_bm25_prefilter_batch_stats_t *stats_out,
+                                               nidx_gpu_prefilter_rows_t **rows_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !rows_out || (n_requests && (!requests || !out_matching))) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    NIDX_HIP(hipSetDevice(idx->device));
+    std::unique_ptr<PrefilterRows> rows(new PrefilterRows());   // (a failure below frees whatever rows were already copied)
+    rows->device = idx->device;
+    rows->generation = idx->generation.load();
+    bm25_row_layout_locked(idx, rows->layout);
+    if (int32_t rc = bm25_prefilter_batch_locked(idx, requests, n_requests, max_scratch_bytes, out_matching, nullptr, nullptr, 0, nullptr, num_docs_out,
+                                                 stats_out, rows.get(), max_rows_bytes))
+        return rc;
+    *rows_out = reinterpret_cast<nidx_gpu_prefilter_rows_t *>(rows.release());
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+void nidx_gpu_prefilter_rows_free(nidx_gpu_prefilter_rows_t *rows) {
+    PrefilterRows *r = reinterpret_cast<PrefilterRows *>(rows);
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    delete r;
+}
+
+int32_t nidx_gpu_prefilter_rows_info(const nidx_gpu_prefilter_rows_t *rows, nidx_gpu_prefilter_rows_info_t *info_out) try {
+    const PrefilterRows *r = reinterpret_cast<const PrefilterRows *>(rows);
+    if (!r || !info_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    info_out->requests = (uint32_t)r->row_of_request.size();
+    info_out->rows = (uint32_t)r->row_ptr.size();
+    info_out->bytes = r->bytes;
+    info_out->generation = r->generation;
+    info_out->row_words = r->layout.words();
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_prefilter_rows_read(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint64_t *out_docaddr, uint64_t capacity,
+                                     uint64_t *n_out) try {
+    const PrefilterRows *r = reinterpret_cast<const PrefilterRows *>(rows);
+    if (!r || !n_out || (capacity && !out_docaddr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (request >= r->row_of_request.size())
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "request %u of %zu", request, r->row_of_request.size());
+    const uint32_t row = r->row_of_request[request];
+    uint64_t n = 0;
+    if (row != kPrefilterRowAll && row != kPrefilterRowNone) {
+        NIDX_HIP(hipSetDevice(r->device));
+        std::vector<uint64_t> host((size_t)r->layout.words());
+        if (!host.empty()) NIDX_HIP(hipMemcpy(host.data(), r->row_ptr[row], host.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t s = 0; s < r->layout.seg_docs.size(); s++)
+            for (uint64_t w = r->layout.word0[s]; w < r->layout.word0[s + 1]; w++)
+                for (uint64_t v = host[(size_t)w]; v; v &= v - 1) {
+                    const uint32_t d = (uint32_t)((w - r->layout.word0[s]) * 64 + (uint64_t)__builtin_ctzll(v));
+                    if (n < capacity) out_docaddr[n] = r->layout.docaddr(s, d);
+                    n++;
+                }
+    }
+    *n_out = n;
+    return NIDX_OK;
 } NIDX_ABI_CATCH
 
 }  // extern "C"
+
+namespace nidx {
+int32_t bm25_prefilter_row_layout(nidx_gpu_bm25_index_t *index, PrefilterRowLayout &layout, int &device, uint64_t &generation) {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    bm25_row_layout_locked(idx, layout);
+    device = idx->device;
+    generation = idx->generation.load();
+    return NIDX_OK;
+}
+}  // namespace nidx
 
 // The search itself, on the context `cx` (the caller owns it for the duration and holds idx->rw shared).  With `async_slot` set and a
 // request the pipeline covers it returns after the last asynchronous call (launches + the device-to-host transfer of the result block

@@ -420,6 +420,29 @@ hipError_t launch_filter_scatter(const unsigned long long *list_offsets, const u
 hipError_t launch_filter_combine(const uint32_t *ops, const uint32_t *prog_first, uint32_t n_filters, const uint64_t *operands,
                                  const uint64_t *alive, uint32_t words, uint32_t n_bits, uint64_t *table, unsigned long long *matching,
                                  hipStream_t s);
+// ---- the prefilter hand-over (vector_prefilter.hip) ----
+// The link between text documents and the vector segments' posting lists, built per vector segment over a chunk of documents whose
+// keys sit in qb / q_off (key d followed by the child separator byte when has_sep): document d is linked to the lists whose key equals
+// its key, and with has_sep to those whose key starts with key + separator.
+//   count: counts[d] += the lists linked to document d            fill: entries[doc_off[d] + cursor[d]++] = (segment, list)
+hipError_t launch_prefilter_link(const uint8_t *tbl, const unsigned long long *tbl_off, uint32_t n_keys, const uint8_t *qb,
+                                 const unsigned long long *q_off, uint32_t n_q, int has_sep, uint32_t segment, uint32_t *counts,
+                                 const uint32_t *doc_off /* nullptr: count */, uint2 *entries, hipStream_t s);
+// One vector segment as the projection sees it: its posting lists, and where its operand rows begin (row j of the launch at 64-bit word
+// out_word + j * words of `out`; out_word == ~0: the segment is not projected by this launch).
+struct PrefilterProjSeg {
+    const unsigned long long *list_off;
+    const uint32_t *ids;
+    unsigned long long out_word;
+    uint32_t words, n_bits;
+};
+// Projects prefilter rows (bitsets over text documents, n_words words each) onto the vector segments' paragraph bitsets: grid = (64-word
+// spans of a row, rows).  A wave reads 64 consecutive words, skips the zero ones by ballot, spreads the set bits of a word over its
+// lanes, and every set document's link entries OR the paragraph ids of their lists into operand row (row, segment) with 32-bit
+// atomicOr — a list of more than 64 paragraphs by the whole wave, a shorter one by its lane.  out is zeroed by the caller.
+// stats[0] += documents visited, stats[1] += paragraph ids written.
+hipError_t launch_prefilter_project(const uint64_t *const *rows, uint32_t n_rows, uint32_t n_words, const uint32_t *doc_off, const uint2 *entries,
+                                    const PrefilterProjSeg *segs, uint64_t *out, unsigned long long *stats, hipStream_t s);
 // dst[i] = src[idx[i]] for rows of dp floats (the queries one search arm of a batch takes)
 hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s);
 

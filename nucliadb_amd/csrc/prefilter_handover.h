@@ -1,0 +1,64 @@
+// prefilter_handover.h — what the three pieces of the prefilter hand-over share: the resident rows of a prefilter batch
+// (bm25_index.cpp), the document -> (vector segment, list) link (prefilter_link.cpp) and the search that projects the rows through the
+// link (vector_index.cpp, vector_prefilter.hip).
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "host_common.h"
+
+namespace nidx {
+
+// Where the documents of the opened text segments sit in a prefilter row: a row spans the resident segments, resident segment r owns
+// words [word0[r], word0[r + 1]).  One resident segment per opened one — or, for the term-major concatenation, ONE whose documents are
+// doc + seg_base[opened segment].
+struct PrefilterRowLayout {
+    std::vector<uint64_t> word0;      // [resident + 1]
+    std::vector<uint32_t> seg_docs;   // [resident] documents of every resident segment
+    std::vector<uint32_t> seg_base;   // [opened + 1] running sum of the opened segments' documents; empty unless concatenated
+    uint32_t n_opened = 0;
+    uint64_t words() const { return word0.empty() ? 0 : word0.back(); }
+    uint32_t opened_docs(uint32_t s) const { return seg_base.empty() ? seg_docs[s] : seg_base[s + 1] - seg_base[s]; }
+    uint64_t bit_of(uint32_t opened_segment, uint32_t doc) const {
+        return seg_base.empty() ? word0[opened_segment] * 64 + doc : (uint64_t)seg_base[opened_segment] + doc;
+    }
+    // DocAddress of resident (segment, doc), as Bm25Index::docaddr gives it
+    uint64_t docaddr(size_t resident_segment, uint32_t d) const {
+        if (seg_base.empty()) return ((uint64_t)resident_segment << 32) | d;
+        const size_t s = (size_t)(std::upper_bound(seg_base.begin() + 1, seg_base.end(), d) - (seg_base.begin() + 1));
+        return ((uint64_t)s << 32) | (uint64_t)(d - seg_base[s]);
+    }
+    bool operator==(const PrefilterRowLayout &o) const {
+        return word0 == o.word0 && seg_docs == o.seg_docs && seg_base == o.seg_base && n_opened == o.n_opened;
+    }
+};
+
+constexpr uint32_t kPrefilterRowAll = 0xffffffffu, kPrefilterRowNone = 0xfffffffeu;
+
+// nidx_gpu_prefilter_rows_t
+struct PrefilterRows {
+    int device = 0;
+    uint64_t generation = 0;
+    PrefilterRowLayout layout;
+    std::vector<DevBuf> chunks;                 // the rows' memory: one allocation per pass or fallback program with Some rows
+    std::vector<const uint64_t *> row_ptr;      // [rows] in HBM, layout.words() words each
+    std::vector<uint32_t> row_of_request;       // a row, kPrefilterRowAll or kPrefilterRowNone
+    uint64_t bytes = 0;
+};
+
+// nidx_gpu_prefilter_link_t: CSR over the bit positions of a row
+struct PrefilterLink {
+    int device = 0;
+    uint64_t bm25_generation = 0, vector_generation = 0;
+    PrefilterRowLayout layout;
+    uint32_t n_vector_segments = 0;
+    std::vector<uint32_t> segment_lists;   // posting lists of every vector segment when the link was built
+    DevBuf doc_off;                        // [words * 64 + 1] u32
+    DevBuf entries;                        // [n_entries] (vector segment, list)
+    uint64_t n_entries = 0, linked_documents = 0;
+};
+
+// bm25_index.cpp: the layout, device and generation of an open index (takes the index's lock)
+int32_t bm25_prefilter_row_layout(nidx_gpu_bm25_index_t *index, PrefilterRowLayout &layout, int &device, uint64_t &generation);
+
+}  // namespace nidx

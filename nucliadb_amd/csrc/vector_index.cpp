@@ -21,6 +21,7 @@
 #include "host_common.h"
 #include "kernels.h"
 #include "vector_index.h"
+#include "prefilter_handover.h"
 
 namespace nidx {
 
@@ -1210,15 +1211,22 @@ int32_t VectorIndex::rows_equal_host(uint32_t sa, uint32_t va, uint32_t sb, uint
 }
 
 // ParagraphInvertedIndexes::filter on the device (filter.hip): postfix program over posting-list unions.
-int32_t VectorIndex::eval_filter_program(uint32_t si, const nidx_gpu_filter_program_t &prog, uint64_t &matching) {
+int32_t VectorIndex::eval_filter_program(uint32_t si, const nidx_gpu_filter_program_t &prog, uint64_t &matching, PrefilterSearch *pf,
+                                         uint32_t filter) {
     VectorSegment &seg = segs[si];
     const uint32_t n_bits = seg.n_paragraphs, words = (n_bits + 63) / 64;
     matching = 0;
     // validate + stack depth
     int depth = 0, max_depth = 0;
+    bool pf_projected = false;   // the filter's prefilter row is projected once, whatever the number of ops that push it
+    const uint32_t pf_row = pf ? pf->row_of_filter(filter) : kPrefilterRowNone;
     for (uint32_t i = 0; i < prog.n_ops; i++) {
         const nidx_gpu_filter_op_t &op = prog.ops[i];
         switch (op.op) {
+            case NIDX_FILTER_PUSH_PREFILTER:
+                if (!pf) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: unknown op %d", op.op);
+                depth++;
+                break;
             case NIDX_FILTER_PUSH_LISTS:
                 if (op.a > op.b || op.b > prog.n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "filter program: list range out of bounds");
                 if (op.b > op.a && !seg.f_n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u has no filter index", si);
@@ -1261,6 +1269,23 @@ int32_t VectorIndex::eval_filter_program(uint32_t si, const nidx_gpu_filter_prog
                                                scratch_flists.as<uint32_t>() + op.a, op.b - op.a, n_bits, slot(depth), stream));
                 depth++;
                 break;
+            case NIDX_FILTER_PUSH_PREFILTER:
+                if (pf_row == kPrefilterRowAll || pf_row == kPrefilterRowNone) {
+                    NIDX_HIP(launch_bitset_fill(slot(depth++), words, n_bits, pf_row == kPrefilterRowAll ? 1 : 0, stream));
+                    break;
+                }
+                if (!pf_projected) {   // the projection kernel, launched for this one row and segment
+                    NIDX_HIP(scratch_pf_row.reserve((size_t)std::max<uint32_t>(words, 1) * 8));
+                    if (words) NIDX_HIP(hipMemsetAsync(scratch_pf_row.p, 0, (size_t)words * 8, stream));
+                    NIDX_HIP(hipMemsetAsync(scratch_pf_stats.p, 0, 16, stream));
+                    std::vector<unsigned long long> out_word(segs.size(), ~0ull);
+                    out_word[si] = 0;
+                    const int32_t rc = project_prefilter_rows(*pf, std::vector<uint32_t>(1, pf_row), out_word, scratch_pf_row.as<uint64_t>());
+                    if (rc != NIDX_OK) return rc;
+                    pf_projected = true;
+                }
+                NIDX_HIP(hipMemcpyAsync(slot(depth++), scratch_pf_row.p, (size_t)words * 8, hipMemcpyDeviceToDevice, stream));
+                break;
             case NIDX_FILTER_PUSH_ALL: NIDX_HIP(launch_bitset_fill(slot(depth++), words, n_bits, 1, stream)); break;
             case NIDX_FILTER_PUSH_NONE: NIDX_HIP(launch_bitset_fill(slot(depth++), words, n_bits, 0, stream)); break;
             case NIDX_FILTER_AND:
@@ -1273,9 +1298,15 @@ int32_t VectorIndex::eval_filter_program(uint32_t si, const nidx_gpu_filter_prog
     }
     NIDX_HIP(launch_bitset_and_count(slot(0), seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), scratch_filter.as<uint64_t>(),
                                      words, scratch_fcount.as<unsigned long long>(), stream));
-    unsigned long long c = 0;
+    unsigned long long c = 0, pfc[2] = {0, 0};
     NIDX_HIP(hipMemcpyAsync(&c, scratch_fcount.p, 8, hipMemcpyDeviceToHost, stream));
+    if (pf_projected) NIDX_HIP(hipMemcpyAsync(pfc, scratch_pf_stats.p, 16, hipMemcpyDeviceToHost, stream));
     NIDX_HIP(hipStreamSynchronize(stream));
+    if (pf) {
+        pf->stats.filter_synchronisations++;
+        pf->stats.documents_visited += pfc[0];
+        pf->stats.paragraphs_written += pfc[1];
+    }
     matching = c;
     return NIDX_OK;
 }
@@ -1521,8 +1552,8 @@ uint64_t VectorIndex::popcount_filter(uint32_t s, const uint64_t *filt) const {
 // |filter ∩ alive| counts come back in one transfer, use_hnsw routes every (query, segment) on the host as search_host routes a
 // segment, and each arm of a segment runs once over the queries routed to it, every query testing its own filter row.
 namespace {
-// filter rows + operand rows of one chunk of a batch; a larger batch is split into chunks of queries (never refused)
-constexpr uint64_t kPqFilterScratchCap = 1ull << 30;
+// filter rows + operand rows of one chunk of a batch stay under VectorIndex::pq_scratch_cap (1 GiB); a larger batch is split into chunks
+// of queries (never refused)
 constexpr size_t kPqMaxFilters = 65535;   // filters per chunk: the combine launch's grid rows
 
 bool has_program(const nidx_gpu_filter_program_t &prog) { return prog.ops && prog.n_ops; }
@@ -1531,9 +1562,10 @@ bool has_program(const nidx_gpu_filter_program_t &prog) { return prog.ops && pro
 // NIDX_FILTER_STACK bitsets of stack (`deep`: such a program is evaluated op by op, as search_host evaluates it).  `who` names the
 // program in the message ("filter 3", "the request's program").
 int32_t check_program(const VectorSegment &seg, const char *who, uint32_t s, const nidx_gpu_filter_program_t &prog, uint32_t &n_operands,
-                      bool &deep) {
+                      bool &deep, uint32_t *n_prefilter = nullptr /* non-null: NIDX_FILTER_PUSH_PREFILTER is an op, counted here */) {
     n_operands = 0;
     deep = false;
+    if (n_prefilter) *n_prefilter = 0;
     if (!has_program(prog)) return NIDX_OK;
     if (prog.n_lists && !prog.lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: %u lists but no list table", who, s, prog.n_lists);
     int depth = 0;
@@ -1547,6 +1579,11 @@ int32_t check_program(const VectorSegment &seg, const char *who, uint32_t s, con
                     if (prog.lists[l] >= seg.f_n_lists)
                         return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown posting list %u", who, s, prog.lists[l]);
                 n_operands++;
+                depth++;
+                break;
+            case NIDX_FILTER_PUSH_PREFILTER:
+                if (!n_prefilter) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown op %d", who, s, op.op);
+                ++*n_prefilter;
                 depth++;
                 break;
             case NIDX_FILTER_PUSH_ALL:
@@ -1568,6 +1605,39 @@ int32_t check_program(const VectorSegment &seg, const char *who, uint32_t s, con
 }
 }  // namespace
 
+uint32_t PrefilterSearch::row_of_filter(uint32_t f) const {
+    const uint32_t r = prefilter_of_filter ? prefilter_of_filter[f] : UINT32_MAX;
+    return r == UINT32_MAX || !rows ? kPrefilterRowNone : rows->row_of_request[r];
+}
+
+int32_t VectorIndex::project_prefilter_rows(PrefilterSearch &pf, const std::vector<uint32_t> &rows, const std::vector<unsigned long long> &out_word,
+                                            uint64_t *d_out) {
+    const size_t S = segs.size(), D = rows.size();
+    const size_t seg_bytes = S * sizeof(PrefilterProjSeg);
+    pf_stage.resize(seg_bytes + D * sizeof(uint64_t *));   // (kept until the caller's synchronisation: the upload reads it)
+    PrefilterProjSeg *hs = reinterpret_cast<PrefilterProjSeg *>(pf_stage.data());
+    for (size_t s = 0; s < S; s++) {
+        const VectorSegment &seg = segs[s];
+        const bool on = out_word[s] != ~0ull && seg.f_n_lists && seg.f_offsets.p;
+        hs[s].list_off = seg.f_offsets.as<unsigned long long>();
+        hs[s].ids = seg.f_ids.as<uint32_t>();
+        hs[s].out_word = on ? out_word[s] : ~0ull;
+        hs[s].words = (seg.n_paragraphs + 63) / 64;
+        hs[s].n_bits = seg.n_paragraphs;
+    }
+    const uint64_t **hr = reinterpret_cast<const uint64_t **>(pf_stage.data() + seg_bytes);
+    for (size_t j = 0; j < D; j++) hr[j] = pf.rows->row_ptr[rows[j]];
+    NIDX_HIP(scratch_pf_in.reserve(pf_stage.size()));
+    NIDX_HIP(hipMemcpyAsync(scratch_pf_in.p, pf_stage.data(), pf_stage.size(), hipMemcpyHostToDevice, stream));
+    const uint8_t *dv = scratch_pf_in.as<uint8_t>();
+    NIDX_HIP(launch_prefilter_project(reinterpret_cast<const uint64_t *const *>(dv + seg_bytes), (uint32_t)D, (uint32_t)pf.rows->layout.words(),
+                                      pf.link->doc_off.as<uint32_t>(), pf.link->entries.as<uint2>(), reinterpret_cast<const PrefilterProjSeg *>(dv),
+                                      d_out, scratch_pf_stats.as<unsigned long long>(), stream));
+    pf.stats.projection_launches++;
+    pf.stats.rows_projected += (uint32_t)D;
+    return NIDX_OK;
+}
+
 int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *segment_programs) {
     if (!segment_programs) return NIDX_OK;
     std::lock_guard<std::mutex> lock(mu);
@@ -1583,11 +1653,50 @@ int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *seg
 int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                       const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
                                       uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
-                                      uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) {
+                                      uint32_t *out_count, int32_t *out_method, uint64_t *out_matching, PrefilterSearch *pf) {
     std::lock_guard<std::mutex> lock(mu);
     NIDX_HIP(hipSetDevice(device));
     const uint32_t k = p.k;
     const size_t S = segs.size();
+    // the prefilter hand-over: everything about the link, the rows and the filters' requests is checked before any output is written
+    uint64_t pf_row_cost = 0;   // a projected row's operand rows: one on every segment
+    if (pf) {
+        if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
+        if ((pf->link == nullptr) != (pf->rows == nullptr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "a link without rows, or rows without a link");
+        if (pf->link) {
+            const PrefilterLink &lk = *pf->link;
+            if (lk.device != device || pf->rows->device != device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link, the rows and the index are on different devices");
+            if (lk.vector_generation != gate.generation.load() || lk.n_vector_segments != S)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the vector index, which is in generation %llu (build it again)",
+                            (unsigned long long)lk.vector_generation, (unsigned long long)gate.generation.load());
+            for (size_t s = 0; s < S; s++)
+                if (lk.segment_lists[s] != segs[s].f_n_lists)
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: segment %zu had %u posting lists when it was built, now %u (build it again)", s,
+                                lk.segment_lists[s], segs[s].f_n_lists);
+            if (pf->rows->generation != lk.bm25_generation || !(pf->rows->layout == lk.layout))
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the text index, the rows are of generation %llu (build it again)",
+                            (unsigned long long)lk.bm25_generation, (unsigned long long)pf->rows->generation);
+        }
+        pf->has_op.assign((size_t)n_filters * S, 0);
+        for (uint32_t f = 0; f < n_filters; f++) {
+            char who[32];
+            snprintf(who, sizeof(who), "filter %u", f);
+            const uint32_t r = pf->prefilter_of_filter ? pf->prefilter_of_filter[f] : UINT32_MAX;
+            if (r != UINT32_MAX && (!pf->rows || r >= pf->rows->row_of_request.size()))
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u of %zu", f, r, pf->rows ? pf->rows->row_of_request.size() : (size_t)0);
+            for (size_t s = 0; s < S; s++) {
+                uint32_t n_operands = 0, n_pf = 0;
+                bool dp = false;
+                const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, &n_pf);
+                if (rc != NIDX_OK) return rc;
+                if (n_pf && r == UINT32_MAX)
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u, segment %zu: NIDX_FILTER_PUSH_PREFILTER in a filter without a prefilter request", f, s);
+                pf->has_op[(size_t)f * S + s] = n_pf ? 1 : 0;
+            }
+        }
+        for (size_t s = 0; s < S; s++) pf_row_cost += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8;
+        NIDX_HIP(scratch_pf_stats.reserve(16));
+    }
     for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
     if (out_method) std::fill(out_method, out_method + (size_t)nq * S, 0);
     if (out_matching) std::fill(out_matching, out_matching + (size_t)n_filters * S, 0);
@@ -1611,7 +1720,8 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
         for (size_t s = 0; s < S; s++) {
             uint32_t n_operands = 0;
             bool dp = false;
-            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp);
+            uint32_t n_pf = 0;
+            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, pf ? &n_pf : nullptr);
             if (rc != NIDX_OK) return rc;
             deep[(size_t)f * S + s] = dp ? 1 : 0;
             cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
@@ -1620,26 +1730,40 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
     // chunks of consecutive queries whose distinct filters fit the scratch cap and the combine grid (one query at least)
     std::vector<uint8_t> in_chunk(n_filters, 0);
     std::vector<uint32_t> filters;
+    // the projected rows of a chunk are shared by the filters that name them: a row costs once per chunk
+    auto projected_row = [&](uint32_t f) -> uint32_t {
+        if (!pf) return kPrefilterRowNone;
+        bool named = false;
+        for (size_t s = 0; s < S; s++) named = named || (pf->has_op[(size_t)f * S + s] && !deep[(size_t)f * S + s]);
+        return named ? pf->row_of_filter(f) : kPrefilterRowNone;   // (All and None rows are no rows)
+    };
+    std::vector<uint32_t> chunk_rows;
     const uint32_t d = cfg.dimension;
     for (uint32_t q0 = 0; q0 < nq;) {
         filters.clear();
+        chunk_rows.clear();
         uint64_t bytes = 0;
         uint32_t q1 = q0;
         for (; q1 < nq; q1++) {
             const uint32_t f = filter_of_query ? filter_of_query[q1] : UINT32_MAX;
             if (f == UINT32_MAX || in_chunk[f]) continue;
-            if (q1 > q0 && (bytes + cost[f] > kPqFilterScratchCap || filters.size() == kPqMaxFilters)) break;
+            const uint32_t row = projected_row(f);
+            const bool new_row = row != kPrefilterRowAll && row != kPrefilterRowNone && std::find(chunk_rows.begin(), chunk_rows.end(), row) == chunk_rows.end();
+            const uint64_t add = cost[f] + (new_row ? pf_row_cost : 0);
+            if (q1 > q0 && (bytes + add > pq_scratch_cap || filters.size() == kPqMaxFilters)) break;
             in_chunk[f] = 1;
-            bytes += cost[f];
+            bytes += add;
             filters.push_back(f);
+            if (new_row) chunk_rows.push_back(row);
         }
         for (uint32_t f : filters) in_chunk[f] = 0;
+        if (pf) pf->stats.chunks++;
         const size_t at = (size_t)q0 * k;
         const int32_t rc = search_per_query_chunk(queries + (size_t)q0 * d, q1 - q0, p, programs, filter_of_query ? filter_of_query + q0 : nullptr,
                                                   filters, deep, out_segment ? out_segment + at : nullptr,
                                                   out_paragraph ? out_paragraph + at : nullptr, out_vector ? out_vector + at : nullptr,
                                                   out_score ? out_score + at : nullptr, out_count + q0,
-                                                  out_method ? out_method + (size_t)q0 * S : nullptr, out_matching);
+                                                  out_method ? out_method + (size_t)q0 * S : nullptr, out_matching, pf);
         if (rc != NIDX_OK) return rc;
         q0 = q1;
     }
@@ -1650,10 +1774,25 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
                                             const nidx_gpu_filter_program_t *programs, const uint32_t *filter_of_query,
                                             const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
                                             uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
-                                            uint32_t *out_count, int32_t *out_method, uint64_t *out_matching) {
+                                            uint32_t *out_count, int32_t *out_method, uint64_t *out_matching, PrefilterSearch *pf) {
     const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
     const size_t S = segs.size();
     const uint32_t F = (uint32_t)filters.size();
+    // the distinct prefilter rows the chunk's programs push (not the deep ones': those project their own): operand rows 0 .. D of every
+    // segment, filled by one launch before the segments' loop and shared by the filters that name the same row
+    std::vector<uint32_t> pf_rows;
+    std::unordered_map<uint32_t, uint32_t> pf_slot;
+    if (pf)
+        for (uint32_t f : filters) {
+            const uint32_t row = pf->row_of_filter(f);
+            if (row == kPrefilterRowAll || row == kPrefilterRowNone || pf_slot.count(row)) continue;
+            bool named = false;
+            for (size_t s = 0; s < S; s++) named = named || (pf->has_op[(size_t)f * S + s] && !deep[(size_t)f * S + s]);
+            if (!named) continue;
+            pf_slot.emplace(row, (uint32_t)pf_rows.size());
+            pf_rows.push_back(row);
+        }
+    const uint32_t D = (uint32_t)pf_rows.size();
     // query batch -> HBM, as search_host stages it
     NIDX_HIP(pin_in.reserve((size_t)nq * dp * 4));
     stage_query_rows(queries, pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
@@ -1669,8 +1808,11 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     // ---- every filter of the chunk on every segment: [ops][prog_first][work] per segment, one upload, two launches per segment ----
     std::vector<uint32_t> host;
     std::vector<size_t> at_ops(S), at_first(S), at_work(S), tab_off(S);
-    std::vector<uint32_t> n_work(S, 0), n_opnd(S, 0);
+    std::vector<uint32_t> n_work(S, 0), n_opnd(S, D);
     std::vector<uint8_t> any_prog(S, 0);
+    // operand rows: without projected rows the segments use the same memory one after the other; with them every segment has a region
+    // of its own, [D projected rows | its posting-list operands], because the projection fills all segments' rows at once
+    std::vector<size_t> opnd_off(S, 0);
     size_t tab_words = 0, opnd_words = 0;
     for (size_t s = 0; s < S; s++) {
         const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
@@ -1690,6 +1832,11 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
                         work.push_back(prog.lists[l]);
                     }
                     ops.push_back((uint32_t)op.op | (o << 3));
+                } else if (op.op == NIDX_FILTER_PUSH_PREFILTER) {   // an operand row like any other for the combine kernel
+                    const uint32_t row = pf->row_of_filter(filters[lf]);
+                    if (row == kPrefilterRowAll) ops.push_back((uint32_t)NIDX_FILTER_PUSH_ALL);
+                    else if (row == kPrefilterRowNone) ops.push_back((uint32_t)NIDX_FILTER_PUSH_NONE);
+                    else ops.push_back((uint32_t)NIDX_FILTER_PUSH_LISTS | (pf_slot.at(row) << 3));
                 } else {
                     ops.push_back((uint32_t)op.op);
                 }
@@ -1706,9 +1853,15 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
         host.insert(host.end(), work.begin(), work.end());
         tab_off[s] = tab_words;
         tab_words += (size_t)F * words;
-        opnd_words = std::max(opnd_words, (size_t)n_opnd[s] * words);
+        if (D) {
+            opnd_off[s] = opnd_words;
+            opnd_words += (size_t)n_opnd[s] * words;
+        } else {
+            opnd_words = std::max(opnd_words, (size_t)n_opnd[s] * words);
+        }
     }
     std::vector<unsigned long long> counts((size_t)S * F, 0);   // [segment][filter] |filter ∩ alive|
+    unsigned long long pf_counts[2] = {0, 0};                  // the projection's documents visited, paragraph ids written
     if (!host.empty()) {
         NIDX_HIP(scratch_pq_prog.reserve(host.size() * 4));
         NIDX_HIP(scratch_pq_table.reserve(std::max<size_t>(tab_words, 1) * 8));
@@ -1717,26 +1870,42 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
         NIDX_HIP(hipMemcpyAsync(scratch_pq_prog.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
         NIDX_HIP(hipMemsetAsync(scratch_pq_count.p, 0, counts.size() * 8, stream));
         const uint32_t *dprog = scratch_pq_prog.as<uint32_t>();
+        if (D) {   // every projected row onto every segment with programs: one launch
+            NIDX_HIP(hipMemsetAsync(scratch_pq_operands.p, 0, opnd_words * 8, stream));
+            NIDX_HIP(hipMemsetAsync(scratch_pf_stats.p, 0, 16, stream));
+            std::vector<unsigned long long> out_word(S, ~0ull);
+            for (size_t s = 0; s < S; s++)
+                if (any_prog[s] && segs[s].n_paragraphs) out_word[s] = opnd_off[s];
+            const int32_t rc = project_prefilter_rows(*pf, pf_rows, out_word, scratch_pq_operands.as<uint64_t>());
+            if (rc != NIDX_OK) return rc;
+            NIDX_HIP(hipMemcpyAsync(pf_counts, scratch_pf_stats.p, 16, hipMemcpyDeviceToHost, stream));
+        }
         for (size_t s = 0; s < S; s++) {
             if (!any_prog[s]) continue;
             VectorSegment &seg = segs[s];
             const uint32_t n_bits = seg.n_paragraphs, words = (n_bits + 63) / 64;
-            if (n_opnd[s]) NIDX_HIP(hipMemsetAsync(scratch_pq_operands.p, 0, (size_t)n_opnd[s] * words * 8, stream));
+            uint64_t *seg_operands = scratch_pq_operands.as<uint64_t>() + opnd_off[s];
+            if (!D && n_opnd[s]) NIDX_HIP(hipMemsetAsync(seg_operands, 0, (size_t)n_opnd[s] * words * 8, stream));
             NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), dprog + at_work[s], n_work[s], n_bits,
-                                           words, scratch_pq_operands.as<uint64_t>(), stream));
-            NIDX_HIP(launch_filter_combine(dprog + at_ops[s], dprog + at_first[s], F, scratch_pq_operands.as<uint64_t>(),
+                                           words, seg_operands, stream));
+            NIDX_HIP(launch_filter_combine(dprog + at_ops[s], dprog + at_first[s], F, seg_operands,
                                            seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), words, n_bits,
                                            scratch_pq_table.as<uint64_t>() + tab_off[s], scratch_pq_count.as<unsigned long long>() + s * F, stream));
         }
         NIDX_HIP(hipMemcpyAsync(counts.data(), scratch_pq_count.p, counts.size() * 8, hipMemcpyDeviceToHost, stream));
     }
     NIDX_HIP(hipStreamSynchronize(stream));
+    if (pf) {
+        pf->stats.filter_synchronisations++;
+        pf->stats.documents_visited += pf_counts[0];
+        pf->stats.paragraphs_written += pf_counts[1];
+    }
     // programs deeper than the combine kernel's stack: the per-op evaluation of search_host, copied into their rows
     for (uint32_t lf = 0; lf < F; lf++)
         for (size_t s = 0; s < S; s++) {
             if (!deep[(size_t)filters[lf] * S + s]) continue;
             uint64_t m = 0;
-            const int32_t rc = eval_filter_program((uint32_t)s, prog_of(lf, s), m);
+            const int32_t rc = eval_filter_program((uint32_t)s, prog_of(lf, s), m, pf, filters[lf]);
             if (rc != NIDX_OK) return rc;
             const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
             NIDX_HIP(hipMemcpyAsync(scratch_pq_table.as<uint64_t>() + tab_off[s] + (size_t)lf * words, scratch_filter.p, (size_t)words * 8,
@@ -1928,7 +2097,7 @@ int32_t nidx_gpu_last_error(char *buf, size_t len) try {
 int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
 int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
-           NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS;
+           NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2027,6 +2196,7 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "pipeline_walks") idx->pipeline_config(-1, value);   // batches whose search launches may run on the device at once (default 3); tickets beyond it upload ahead
     else if (n == "stage_threads") set_stage_threads(value);   // helper threads that share the copy of host query rows into pinned staging (process-wide; 0 = the caller alone)
     else if (n == "closest_prefetch") idx->closest_prefetch = value != 0;   // measurement knob of closest_up_nodes' edge prefetch: no result depends on it
+    else if (n == "per_query_filter_scratch_kib") idx->pq_scratch_cap = value > 0 ? (uint64_t)value << 10 : 1ull << 30;   // the chunking cap of the per-query filter searches (0 = 1 GiB)
     else if (n == "serial_segments") idx->serial_segments = value != 0;   // nidx_gpu_vector_search: one launch + transfer + wait per segment, Fssc on the host
     else if (n == "build_vis_log2") { idx->build_vis_log2 = (uint32_t)std::max(10, std::min(15, (int)value)); idx->build_vis_pinned = true; }
     else if (n == "ef_search") {   // 0 = the reference's EF_SEARCH (30)
@@ -2249,6 +2419,29 @@ int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index
                     query_dimension);
     return idx->search_per_query(queries, n_queries, *params, programs, n_filters, filter_of_query, out_segment, out_paragraph, out_vector,
                                  out_score, out_count, out_method, out_matching);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_prefiltered_per_query(nidx_gpu_vector_index_t *index, const nidx_gpu_prefilter_link_t *link,
+                                                     const nidx_gpu_prefilter_rows_t *rows, const float *queries, uint32_t n_queries,
+                                                     uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                     const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                     const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint32_t *out_segment,
+                                                     uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                                                     int32_t *out_method, uint64_t *out_matching, nidx_gpu_prefilter_search_stats_t *stats_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !out_count || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    GenShared gen(idx->gate);
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension,
+                    query_dimension);
+    PrefilterSearch pf;
+    pf.link = reinterpret_cast<const PrefilterLink *>(link);
+    pf.rows = reinterpret_cast<const PrefilterRows *>(rows);
+    pf.prefilter_of_filter = prefilter_of_filter;
+    const int32_t rc = idx->search_per_query(queries, n_queries, *params, programs, n_filters, filter_of_query, out_segment, out_paragraph, out_vector,
+                                             out_score, out_count, out_method, out_matching, &pf);
+    if (rc == NIDX_OK && stats_out) *stats_out = pf.stats;
+    return rc;
 } NIDX_ABI_CATCH
 
 static int32_t device_entry_method(VectorIndex *idx, uint32_t segment, const nidx_gpu_vector_search_params_t *params,

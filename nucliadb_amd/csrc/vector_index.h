@@ -86,6 +86,18 @@ struct GenShared {   // a blocking entry point's hold
     ~GenShared() { g.leave(); }
 };
 
+// nidx_gpu_vector_search_prefiltered_per_query: what search_per_query needs beyond its programs (prefilter_handover.h)
+struct PrefilterLink;
+struct PrefilterRows;
+struct PrefilterSearch {
+    const PrefilterLink *link = nullptr;
+    const PrefilterRows *rows = nullptr;
+    const uint32_t *prefilter_of_filter = nullptr;   // [n_filters] request in `rows`, UINT32_MAX = none (nullptr: none for every filter)
+    std::vector<uint8_t> has_op;                     // [n_filters][n_segments] the program holds NIDX_FILTER_PUSH_PREFILTER
+    nidx_gpu_prefilter_search_stats_t stats{};
+    uint32_t row_of_filter(uint32_t f) const;        // the filter's resident row, kPrefilterRowAll or kPrefilterRowNone
+};
+
 struct Coalescer;
 std::shared_ptr<Coalescer> make_coalescer();
 struct Pipeline;
@@ -167,6 +179,14 @@ struct VectorIndex {
     const uint64_t *pq_filter_table = nullptr;
     uint32_t pq_filter_words = 0;
     DevBuf scratch_pq_table, scratch_pq_operands, scratch_pq_prog, scratch_pq_count, scratch_pq_rows, scratch_pq_queries;
+    uint64_t pq_scratch_cap = 1ull << 30;   // filter + operand rows of one chunk; tunable "per_query_filter_scratch_kib" (tests: small caps)
+    // the prefilter hand-over: [segment table | row pointers] of a projection launch, its two counters, the row of a deep program
+    DevBuf scratch_pf_in, scratch_pf_stats, scratch_pf_row;
+    std::vector<uint8_t> pf_stage;
+    // One launch of prefilter_project_kernel: resident rows `rows` onto every segment s with out_word[s] != ~0 (row j of the launch at
+    // word out_word[s] + j * words(s) of d_out, zeroed by the caller); the counters are added to scratch_pf_stats
+    int32_t project_prefilter_rows(PrefilterSearch &pf, const std::vector<uint32_t> &rows, const std::vector<unsigned long long> &out_word,
+                                   uint64_t *d_out);
     // search_multi_vector (searcher.rs:345-394).  The second stage of a batch whose first-pass hits [T][k1] are final, under `mu`:
     // maxsim_rerank (serving.cpp) = one upload, one launch of maxsim_rerank_kernel over every query and segment, one read-back;
     // the queries whose hits outgrow NIDX_MAXSIM_DEVICE_CANDIDATES are finished by maxsim_host_stage, the stage of
@@ -236,11 +256,12 @@ struct VectorIndex {
     // filter rows fit kPqFilterScratchCap go through search_per_query_chunk one after the other
     int32_t search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                              uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment, uint32_t *out_paragraph,
-                             uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method, uint64_t *out_matching);
+                             uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method, uint64_t *out_matching,
+                             PrefilterSearch *pf = nullptr);
     int32_t search_per_query_chunk(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                                    const uint32_t *filter_of_query, const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
                                    uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
-                                   int32_t *out_method, uint64_t *out_matching);
+                                   int32_t *out_method, uint64_t *out_matching, PrefilterSearch *pf = nullptr);
     // the checks search_per_query makes of one request's [n_segments] programs (nullptr: unfiltered), before it joins a coalesced batch
     int32_t check_request_programs(const nidx_gpu_filter_program_t *segment_programs);
     int32_t pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
@@ -258,7 +279,9 @@ struct VectorIndex {
                           uint32_t *out_count, uint32_t *n_retried_out);
     void pipeline_config(int32_t depth, int32_t walks = -1);
     // evaluates `prog` for segment s into scratch_filter (already intersected with alive); returns |filter ∩ alive|
-    int32_t eval_filter_program(uint32_t s, const nidx_gpu_filter_program_t &prog, uint64_t &matching);
+    // (pf: the program is filter `filter` of a prefiltered search and may hold NIDX_FILTER_PUSH_PREFILTER)
+    int32_t eval_filter_program(uint32_t s, const nidx_gpu_filter_program_t &prog, uint64_t &matching, PrefilterSearch *pf = nullptr,
+                                uint32_t filter = 0);
     int32_t build_hnsw(uint32_t segment, uint64_t level_seed, bool extend = false);
     // request coalescing for single-query callers (coalescer.cpp)
     std::shared_ptr<Coalescer> coalescer = make_coalescer();

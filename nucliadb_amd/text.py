@@ -851,6 +851,27 @@ class TextSearcher:
                 results[i] = self._prefilter_result(lists[j])
         return results
 
+    def prefilter_batch_resident(self, requests: Sequence[PreFilterRequest]):
+        """prefilter_batch whose Some results stay in HBM as bit rows (nidx_gpu_bm25_prefilter_batch_resident): a ResidentPrefilters
+        with one kind per request, for VectorSearcher.search_many(..., prefilters=<it>, link=vector_searcher.link_text(self)).
+        Requests with neither security nor expression are All without reaching the library; identical programs share a row."""
+        from .bm25 import ResidentPrefilters
+
+        programs = [self._prefilter_program(r) for r in requests]
+        asked = [i for i, p in enumerate(programs) if p is not None]
+        sent = self._index.searcher.prefilter_batch_resident([programs[i] for i in asked])
+        kinds, request_of, same_as = ["All"] * len(programs), [None] * len(programs), list(range(len(programs)))
+        matching = np.full(len(programs), sent.live, np.uint64)
+        first: dict = {}
+        for j, i in enumerate(asked):
+            kinds[i], request_of[i], matching[i] = sent.kinds[j], j, sent.matching[j]
+            ops, lists, ranges, phrases = programs[i]
+            key = (tuple(map(tuple, ops)), tuple(lists), tuple(map(tuple, ranges)), tuple(map(tuple, phrases)))
+            same_as[i] = first.setdefault(key, i)
+        out = ResidentPrefilters(sent.handle, kinds, matching, sent.live, sent.stats, request_of, same_as)
+        sent.handle = None   # (the handle has moved)
+        return out
+
     def search(self, request: DocumentSearchRequest) -> DocumentSearchResponse:
         k = max(0, int(request.result_per_page))
         facets, pairs = self._index.facet_request(request.faceted)

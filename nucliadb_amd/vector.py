@@ -302,7 +302,7 @@ class VectorSegment:
             atoms = []
 
             def collect(e):
-                if isinstance(e, (Literal, _KeyPrefixSet)):
+                if isinstance(e, (Literal, _KeyPrefixSet)):   # (a _PrefilterAtom names no list: nothing to look up)
                     atoms.append(e)
                 elif isinstance(e, Not):
                     collect(e.operand)
@@ -325,6 +325,8 @@ class VectorSegment:
                 ids = resolved[id(e)] if lookup is not None else self.lists_for(e)
                 ops.append((_lib.FILTER_PUSH_LISTS, len(lists), len(lists) + len(ids)))
                 lists.extend(ids)
+            elif isinstance(e, _PrefilterAtom):
+                ops.append((_lib.FILTER_PUSH_PREFILTER, 0, 0))
             elif isinstance(e, Not):
                 emit(e.operand)
                 ops.append((_lib.FILTER_NOT, 0, 0))
@@ -531,6 +533,47 @@ def segment_dir_merge(path: str, dimension: int, operands: Sequence[Tuple["Segme
     _lib.check(_lib.lib().nidx_gpu_segment_dir_merge(path.encode(), dimension, ops, len(operands), C.byref(rec), C.byref(vec),
                                                    C.byref(gn), C.byref(hq)))
     return rec.value, vec.value, gn.value, bool(hq.value)
+
+
+class _PrefilterAtom:
+    """The prefilter of the request as a resident row (NIDX_FILTER_PUSH_PREFILTER): stands where _formula puts a _KeyPrefixSet."""
+
+    def __repr__(self):
+        return "_PrefilterAtom()"
+
+    def __eq__(self, other):
+        return isinstance(other, _PrefilterAtom)
+
+    def __hash__(self):
+        return hash("_PrefilterAtom")
+
+
+class PrefilterLink:
+    """nidx_gpu_prefilter_link_t: which posting lists of the vector segments belong to which text document, for one generation of
+    both indexes (VectorSearcher.link_text).  A sync of either index makes it stale: build it again."""
+
+    def __init__(self, handle, stats):
+        self.handle = handle
+        self.stats = stats
+
+    def read(self, vector_segment: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(docaddr, list) pairs of one vector segment, ascending: tests."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_read(self.handle, vector_segment, None, None, 0, C.byref(n)))
+        docs, lists = np.zeros(max(1, n.value), np.uint64), np.zeros(max(1, n.value), np.uint32)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_read(self.handle, vector_segment, docs.ctypes.data, lists.ctypes.data, n.value, C.byref(n)))
+        return docs[: n.value], lists[: n.value]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().nidx_gpu_prefilter_link_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 @dataclass
@@ -939,9 +982,13 @@ class VectorSearcher:
         return graph[: glen.value].tobytes(), edges[: nedges.value]
 
     # -- Searcher::search (searcher.rs:292-343) ---------------------------------------------------------
-    def _formula(self, request: VectorSearchRequest, prefilter: PrefilterResult):
+    def _formula(self, request: VectorSearchRequest, prefilter):
+        """`prefilter`: a PrefilterResult, or the kind ("All" / "None" / "Some") of a resident one — its Some is a _PrefilterAtom."""
         clauses = []
-        if prefilter.kind == "some":
+        if isinstance(prefilter, str):
+            if prefilter == "Some":
+                clauses.append(_PrefilterAtom())
+        elif prefilter.kind == "some":
             prefixes = []
             for f in prefilter.fields:
                 prefixes.append(f.resource_id.hex + (f.field_id or ""))
@@ -1079,6 +1126,53 @@ class VectorSearcher:
                 progs.append(None)
         return None if all(p is None for p in progs) else tuple(progs)
 
+    @staticmethod
+    def text_link_keys(text_segments) -> List[List[bytes]]:
+        """The key of every document of every opened text segment as the vector segments' key tables spell a field: "F:" + the
+        resource uuid's 32 hex digits + the field id — what _formula's _KeyPrefixSet looks up (atom_queries)."""
+        return [[("F:" + str(d.uuid).replace("-", "") + (d.field or "")).encode("utf-8") for d in seg.docs] for seg in text_segments]
+
+    def link_text(self, text_searcher) -> PrefilterLink:
+        """The link between the text searcher's documents and this searcher's posting lists (nidx_gpu_prefilter_link_create), with
+        "/" as the child separator: a list is linked to a document when its key is the document's key or lies below it, exactly the
+        lookups atom_queries makes for a _KeyPrefixSet."""
+        index = text_searcher._index
+        keys = self.text_link_keys(index.segments)
+        n = len(keys)
+        blobs = [np.frombuffer(b"".join(k) + b"\0", np.uint8) for k in keys]
+        offs = []
+        for k in keys:
+            o = np.zeros(len(k) + 1, np.uint64)
+            o[1:] = np.cumsum([len(x) for x in k])
+            offs.append(o)
+        c_bytes = (C.c_void_p * max(1, n))(*[b.ctypes.data for b in blobs])
+        c_offs = (C.c_void_p * max(1, n))(*[o.ctypes.data for o in offs])
+        handle, stats = C.c_void_p(), _lib.PrefilterLinkStatsC()
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_create(index.searcher._handle, self._handle, c_bytes, c_offs, n, ord("/"), C.byref(handle),
+                                                             C.byref(stats)))
+        return PrefilterLink(handle, stats)
+
+    def _resident_filters(self, requests, members, resident):
+        """The distinct filters of one group of requests whose prefilters are resident rows: (unique programs, filter per member,
+        prefilter request per filter — 0xFFFFFFFF: the filter pushes no row).  Requests with equal programs and the same row share
+        one filter."""
+        uniq: list = []
+        index: dict = {}
+        filter_of, prefilter_of = [], []
+        for i in members:
+            progs = self._request_programs(requests[i], resident.kinds[i])
+            if progs is None:
+                filter_of.append(0xFFFFFFFF)
+                continue
+            row = resident.request_of[resident.same_as[i]] if resident.kinds[i] == "Some" else None
+            key = (progs, row)
+            if key not in index:
+                index[key] = len(uniq)
+                uniq.append(progs)
+                prefilter_of.append(0xFFFFFFFF if row is None else row)
+            filter_of.append(index[key])
+        return uniq, filter_of, prefilter_of
+
     def _programs_c(self, uniq):
         """The distinct filters of a batch ([filter][segment] (ops, lists) tuples or None) as the C table; (table, keep-alive list)."""
         S = len(self._segments)
@@ -1135,13 +1229,24 @@ class VectorSearcher:
                 out[i] = VectorSearchResponse(docs)
         return out  # type: ignore[return-value]
 
-    def search_many(self, requests: Sequence[VectorSearchRequest], prefilters: Optional[Sequence[PrefilterResult]] = None,
-                    method: int = _lib.METHOD_AUTO) -> List[VectorSearchResponse]:
+    def search_many(self, requests: Sequence[VectorSearchRequest], prefilters=None, method: int = _lib.METHOD_AUTO,
+                    link: Optional[PrefilterLink] = None) -> List[VectorSearchResponse]:
         """[self.search(r, p, method) for r, p in zip(requests, prefilters)] in one native call per group of requests with equal
         (result_per_page, min_score, with_duplicates); every request keeps its own filter (formula, segment formula, operator and
         prefilter), identical programs share one.  Multi-vector indexes: one nidx_gpu_vector_search_maxsim_filtered_per_query call per
-        group of equal (result_per_page, min_score)."""
+        group of equal (result_per_page, min_score).
+
+        prefilters may be the ResidentPrefilters of TextSearcher.prefilter_batch_resident with link = self.link_text(that searcher):
+        the Some results are then never listed — every program pushes its request's resident row where _formula puts the
+        _KeyPrefixSet (nidx_gpu_vector_search_prefiltered_per_query) — and the responses are those of the host PrefilterResults."""
         requests = list(requests)
+        resident = prefilters if hasattr(prefilters, "kinds") else None
+        if resident is not None:
+            if link is None or len(resident) != len(requests):
+                raise ValueError("resident prefilters need their link and one entry per request")
+            if self.config.vector_cardinality == VectorCardinality.Multi:
+                raise NidxGpuError(_lib.NIDX_ERR_UNSUPPORTED, "resident prefilters are not taken by the multi-vector search")
+            prefilters = None
         prefilters = [None] * len(requests) if prefilters is None else list(prefilters)
         if len(prefilters) != len(requests):
             raise ValueError("one prefilter per request")
@@ -1160,26 +1265,26 @@ class VectorSearcher:
                 if v.size != d:
                     raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS, f"Inconsistent dimensions. Index={d} Vector={v.size}")
                 queries[row] = v
-            uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
-            progs = (_lib.FilterProgramC * max(1, len(uniq) * S))()
-            keep = []
-            for f, prog in enumerate(uniq):
-                for s, sp in enumerate(prog):
-                    if sp is None:
-                        continue
-                    ops, lists = sp
-                    c_ops = (_lib.FilterOpC * len(ops))(*[_lib.FilterOpC(*o) for o in ops])
-                    c_lists = np.array(lists, dtype=np.uint32)
-                    keep += [c_ops, c_lists]
-                    progs[f * S + s] = _lib.FilterProgramC(C.addressof(c_ops), len(ops), c_lists.ctypes.data if len(lists) else None, len(lists))
+            if resident is not None:
+                uniq, filter_of, prefilter_of = self._resident_filters(requests, members, resident)
+            else:
+                uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
+            progs, keep = self._programs_c(uniq)
             foq = np.array(filter_of, dtype=np.uint32)
             B, kk = len(members), max(1, k)
             out_seg, out_par = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.uint32)
             out_vec, out_score, out_count = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.float32), np.zeros(B, np.uint32)
             params = _lib.VectorSearchParamsC(k, float(r0.min_score), int(r0.with_duplicates), method)
-            _lib.check(_lib.lib().nidx_gpu_vector_search_filtered_per_query(
-                self._handle, queries.ctypes.data, B, d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
-                out_seg.ctypes.data, out_par.ctypes.data, out_vec.ctypes.data, out_score.ctypes.data, out_count.ctypes.data, None, None))
+            if resident is not None:
+                pof = np.array(prefilter_of + [0], dtype=np.uint32)
+                _lib.check(_lib.lib().nidx_gpu_vector_search_prefiltered_per_query(
+                    self._handle, link.handle, resident.handle, queries.ctypes.data, B, d, C.byref(params), progs if uniq else None, len(uniq),
+                    pof.ctypes.data, foq.ctypes.data, out_seg.ctypes.data, out_par.ctypes.data, out_vec.ctypes.data, out_score.ctypes.data,
+                    out_count.ctypes.data, None, None, None))
+            else:
+                _lib.check(_lib.lib().nidx_gpu_vector_search_filtered_per_query(
+                    self._handle, queries.ctypes.data, B, d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
+                    out_seg.ctypes.data, out_par.ctypes.data, out_vec.ctypes.data, out_score.ctypes.data, out_count.ctypes.data, None, None))
             for row, i in enumerate(members):
                 docs = []
                 for j in range(int(out_count[row])):
