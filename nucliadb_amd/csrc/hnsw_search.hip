@@ -96,6 +96,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
                 a.dump_count[qi] = (uint32_t)res.len;
                 if (a.stats) a.stats[(size_t)qi * NIDX_STAT_STRIDE + NIDX_STAT_FLAGS] = st.flags;
                 if (st.flags && a.flag_word) atomicOr(a.flag_word, st.flags);
+                if (a.flag_rows) a.flag_rows[qi] = st.flags;
             }
         }
         return;
@@ -422,6 +423,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         if (lane == 0) {
             a.out_count[qi] = (uint32_t)n_res;
             if (st.flags && a.flag_word) atomicOr(a.flag_word, st.flags);
+            if (a.flag_rows) a.flag_rows[qi] = st.flags;
             if (a.stats && entry_mode) {
                 // the RaBitQ kernel's counters stay; only overflow flags are added
                 a.stats[(size_t)qi * NIDX_STAT_STRIDE + NIDX_STAT_FLAGS] |= st.flags;

@@ -10,12 +10,14 @@
 //           slot's stream into the slot's result block — every segment that takes the plain HNSW arm in ONE launch of
 //           n_queries x n_segments walks (hnsw_search_segments_kernel: the reference's index at 10 M vectors IS 50 segments,
 //           nidx/src/settings.rs:258-278), the other arms one launch each — merges them per query on the device (Fssc,
-//           fssc_device.hip), queues ONE device-to-host transfer of [flag words | merged hits] and returns;
-//   wait    blocks until the transfer has landed and fills the caller's arrays; only when a segment's flag word says a bounded
+//           fssc_device.hip) and returns.  When every searched segment takes the plain HNSW arm the kernels store the hits and
+//           one flag word per walk straight into the slot's pinned block (SearchSlot::host_block) and nothing follows them;
+//           otherwise ONE device-to-host transfer of [flag words | merged hits] is queued behind them;
+//   wait    blocks until the slot's event has passed and fills the caller's arrays; only when a segment's flags say a bounded
 //           on-chip structure overflowed it fetches the per-segment rows, re-runs that segment through the exact fallback
 //           (segment_search_exact) and merges on the host (the same Fssc, csrc/vector_index.cpp: fssc_merge).
 //
-// Results are those of nidx_gpu_vector_search for the same batch (tests/test_serving_gpu.py).
+// Results are those of nidx_gpu_vector_search for the same batch (tests/test_serving_gpu.py, tests/test_serving_host_block_gpu.py).
 #include <pthread.h>
 #include <atomic>
 #include <condition_variable>
@@ -175,6 +177,7 @@ struct SearchSlot {
     PinBuf pin_in, pin_out, pin_tables, pin_rq_table, pin_bf_table;
     bool dirty = false;                      // work may be queued on `stream` / the flag words may be set: clean before reuse
     bool merged = false;                     // the block carries the device Fssc's hits
+    bool host_block = false;                 // the kernels of the batch wrote hits and flag rows into pin_out themselves (no copy follows them)
     size_t flag_bytes = 0;                   // flag words at the head of d_block
     size_t mw = 0;                           // words of the merged region behind them (0: the batch is merged on the host)
     // the batch in flight
@@ -240,7 +243,8 @@ void VectorIndex::pipeline_config(int32_t depth, int32_t walks) {
 
 namespace {
 // result block of a slot: [flag word per segment, padded to 16 words][merged hits: nq*k segments | paragraphs | vectors | scores,
-// nq counts][per segment: nq*k vectors | nq*k scores | nq counts]
+// nq counts][per segment: nq*k vectors | nq*k scores | nq counts]; the host block of an all-HNSW batch (SearchSlot::host_block) has the
+// same layout, its flag words unused, and behind it [per segment: nq flag rows] (HnswSearchArgs::flag_rows)
 inline size_t flag_words(size_t S) { return (S + 15) / 16 * 16; }
 inline size_t merged_words(uint32_t nq, uint32_t k) { return (size_t)nq * k * 4 + nq; }
 inline size_t seg_words(uint32_t nq, uint32_t k) { return (size_t)nq * k * 2 + nq; }
@@ -343,6 +347,7 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
     sl.d_seg_filter.assign(S, nullptr);
     sl.launched = false;
     sl.merged = false;
+    sl.host_block = false;
     sl.dq = nullptr;
     if (nq > 0 && k > 0 && S > 0) {
         // ---- queries: a device pointer is searched where it lies; host rows go through the slot's pinned staging --------------
@@ -358,10 +363,37 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
             NIDX_HIP(hipMemcpyAsync(sl.d_queries.p, qpad, (size_t)nq * dp * 4, hipMemcpyHostToDevice, sl.stream));
             sl.dq = sl.d_queries.as<float>();
         }
+        // ---- what every segment runs (OpenSegment::_search's routing): decided before the result block is laid out, because a batch
+        // whose searched segments all run the plain HNSW walk gets its hits written straight into host memory ------------------------
+        std::vector<uint64_t> matching(S, 0);
+        bool host_block = true;
+        {
+            std::lock_guard<std::mutex> lock(mu);   // (rabitq_enabled / use_hnsw read tunables)
+            for (size_t s = 0; s < S; s++) {
+                const VectorSegment &seg = segs[s];
+                const uint64_t *filt = segment_filters ? segment_filters[s] : nullptr;
+                // matching = |filter ∩ alive| (segment.rs:516-531)
+                matching[s] = filt ? popcount_filter((uint32_t)s, filt) : seg.alive_count;
+                if (matching[s] == 0 || seg.n == 0) continue;
+                int method = p.method;
+                if (method == NIDX_METHOD_AUTO) {
+                    // OpenSegment::_search (segment.rs:506-513,535-555), like search_host
+                    const bool rabitq = rabitq_enabled(seg);
+                    const bool hnsw = seg.has_graph && use_hnsw(seg.n_paragraphs, matching[s], k, rabitq);
+                    method = rabitq ? (hnsw ? NIDX_METHOD_RABITQ_HNSW : NIDX_METHOD_RABITQ_BRUTE_FORCE)
+                                    : (hnsw ? NIDX_METHOD_HNSW : NIDX_METHOD_BRUTE_FORCE);
+                }
+                if ((method == NIDX_METHOD_HNSW || method == NIDX_METHOD_RABITQ_HNSW) && !seg.has_graph)
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %zu has no HNSW graph", s);
+                sl.method[s] = method;
+                if (method != NIDX_METHOD_HNSW) host_block = false;   // the other kernels keep device rows and the copy behind them
+            }
+        }
+        sl.host_block = host_block;
         // ---- result block; its flag words are zero whenever the slot is idle (a flagged batch clears them in wait) -------------
         // One plain segment (no cross-segment paragraph keys): Fssc is the identity on a falling score list, which the host checks while it
         // copies the row (fssc_merge's fast path) — a merge kernel would only add a launch that, with other batches in flight, waits for
-        // workgroup slots behind their walks (8 us alone, 60 us in the hybrid trace) and a larger transfer.
+        // workgroup slots behind their walks (8 us alone, 60 us in the hybrid trace) for nothing.
         // Fssc's `seen` set (with_duplicates = false, the default) compares a candidate with everything offered before it: on the device
         // that is one wave scanning the offered list per candidate, O((segments x k)^2 / 64) dependent steps — fine at the 500 candidates
         // of 50 segments x k = 10, seconds at nucliadb's page sizes (k up to 500).  Past 4 096 candidates per query the per-segment rows go
@@ -372,11 +404,19 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
         sl.mw = mw;
         sl.dirty = true;   // from here on work is queued on the slot's stream: an error path must drain it (SlotRelease)
         sl.flag_bytes = fw * 4;
-        if (words * 4 > sl.d_block.bytes) {
+        // An all-HNSW batch: the rows pipeline_wait reads live in pin_out and the kernels get pointers into it — the walks' final sort
+        // writes [vectors | scores | counts] and one flag row per walk there, or, when the device merges, Fssc writes the merged block
+        // there and the per-segment rows stay on the device for it (they are fetched only for a flagged batch).  No copy follows the
+        // last kernel.  pin_out is hipHostMalloc memory with the default flags: host memory mapped into the device's address space,
+        // coherent and fine-grained, which the download kernel of the other route writes from the device as well.  The kernels only
+        // store to it (plain stores, no atomic, nothing read back), the end of a kernel releases its stores to the system for such
+        // memory, and the host reads the block only after hipEventSynchronize(sl.done), recorded behind the last kernel.
+        const bool dev_rows = !host_block || sl.merged;
+        if (dev_rows && words * 4 > sl.d_block.bytes) {
             NIDX_HIP(sl.d_block.reserve(words * 4));
             NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
         }
-        NIDX_HIP(sl.pin_out.reserve(words * 4));
+        NIDX_HIP(sl.pin_out.reserve((words + (host_block ? S * (size_t)nq : 0)) * 4));
         // ---- per-segment filters (bitsets over paragraph addresses) ------------------------------------------------------------
         if (segment_filters) {
             size_t fwords = 0;
@@ -401,7 +441,8 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
             if (my_seq >= P.walks && P.gate[(my_seq - P.walks) % Pipeline::GATES])
                 NIDX_HIP(hipStreamWaitEvent(sl.stream, P.gate[(my_seq - P.walks) % Pipeline::GATES], 0));
         }
-        uint32_t *blk = sl.d_block.as<uint32_t>();
+        uint32_t *blk = sl.d_block.as<uint32_t>(), *hblk = sl.pin_out.as<uint32_t>();
+        uint32_t *rows = dev_rows ? blk : hblk;   // where the per-segment rows go
         // the argument tables of the two table-driven kernels travel as one pinned block: [HnswSearchArgs x S | FsscSegDev x S]
         const size_t hnsw_tab_bytes = (S * sizeof(HnswSearchArgs) + 63) & ~(size_t)63, tab_bytes = hnsw_tab_bytes + S * sizeof(FsscSegDev);
         NIDX_HIP(sl.pin_tables.reserve(tab_bytes));
@@ -430,43 +471,32 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
             const uint32_t walks = one_launch ? nq * (uint32_t)std::min<size_t>(S, 64) : nq;   // the launch shape follows the grid
             for (size_t s = 0; s < S; s++) {
                 VectorSegment &seg = segs[s];
-                uint32_t *d_vec = blk + fw + mw + s * sw;
+                uint32_t *d_vec = rows + fw + mw + s * sw;
                 float *d_score = reinterpret_cast<float *>(d_vec + (size_t)nq * k);
                 uint32_t *d_count = d_vec + (size_t)nq * k * 2;
                 h_fssc[s] = FsscSegDev{seg.vectors.as<float>(), seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>(),
                                        seg.key_ids.empty() ? nullptr : seg.key_ids_dev.as<unsigned long long>(), d_vec, nullptr, d_score, seg.dp, 0u};
-                const uint64_t *filt = segment_filters ? segment_filters[s] : nullptr;
-                // matching = |filter ∩ alive| (segment.rs:516-531)
-                const uint64_t matching = filt ? popcount_filter((uint32_t)s, filt) : seg.alive_count;
-                if (matching == 0 || seg.n == 0) continue;
-                int method = p.method;
-                if (method == NIDX_METHOD_AUTO) {
-                    // OpenSegment::_search (segment.rs:506-513,535-555), like search_host
-                    const bool rabitq = rabitq_enabled(seg);
-                    const bool hnsw = seg.has_graph && use_hnsw(seg.n_paragraphs, matching, k, rabitq);
-                    method = rabitq ? (hnsw ? NIDX_METHOD_RABITQ_HNSW : NIDX_METHOD_RABITQ_BRUTE_FORCE)
-                                    : (hnsw ? NIDX_METHOD_HNSW : NIDX_METHOD_BRUTE_FORCE);
-                }
-                if ((method == NIDX_METHOD_HNSW || method == NIDX_METHOD_RABITQ_HNSW) && !seg.has_graph)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %zu has no HNSW graph", s);
+                const int method = sl.method[s];
+                if (!method) continue;   // nothing of it can match
                 h_fssc[s].count = d_count;
                 n_searched++;
-                sl.method[s] = method;
-                if (method == NIDX_METHOD_HNSW && one_launch) {
-                    // its walks join the one grid below
-                    h_hnsw[n_hnsw++] = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], d_vec, d_score,
-                                                 d_count, nullptr, vis_for(walks), blk + s);
+                if (method == NIDX_METHOD_HNSW && (one_launch || host_block)) {
+                    HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], d_vec, d_score,
+                                                  d_count, nullptr, vis_for(walks), host_block ? nullptr : blk + s);
+                    if (host_block) ha.flag_rows = hblk + words + s * (size_t)nq;
+                    if (one_launch) h_hnsw[n_hnsw++] = ha;   // its walks join the one grid below
+                    else NIDX_HIP(launch_hnsw_search(ha, waves_per_query, sl.stream));
                     continue;
                 }
                 if (method == NIDX_METHOD_RABITQ_HNSW && rq_one_launch && seg.has_quant) {
                     rq_segs.push_back((uint32_t)s);   // launched together behind this loop
                     continue;
                 }
-                if (method == NIDX_METHOD_BRUTE_FORCE && one_launch && k <= NIDX_K_MAX && scan_takes_tile_kernel((uint32_t)s, nq, k, matching)) {
+                if (method == NIDX_METHOD_BRUTE_FORCE && one_launch && k <= NIDX_K_MAX && scan_takes_tile_kernel((uint32_t)s, nq, k, matching[s])) {
                     bf_segs.push_back((uint32_t)s);   // their scans share one launch, their merges another
                     continue;
                 }
-                scan_matching_hint = matching;
+                scan_matching_hint = matching[s];
                 const int32_t rc = segment_search_device((uint32_t)s, sl.dq, nq, k, p.min_score, p.with_duplicates != 0, method, sl.d_seg_filter[s],
                                                          d_vec, d_score, d_count, nullptr, vis_for(nq), sl.stream, blk + s);
                 scan_matching_hint = ~0ull;
@@ -482,8 +512,7 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
                 if (per_seg * n_bf > ((size_t)2 << 30)) {
                     for (uint32_t s : bf_segs) {
                         uint32_t *d_vec = blk + fw + mw + (size_t)s * sw;
-                        const uint64_t *filt = segment_filters ? segment_filters[s] : nullptr;
-                        scan_matching_hint = filt ? popcount_filter(s, filt) : segs[s].alive_count;
+                        scan_matching_hint = matching[s];
                         const int32_t rc = segment_search_device(s, sl.dq, nq, k, p.min_score, p.with_duplicates != 0, NIDX_METHOD_BRUTE_FORCE, sl.d_seg_filter[s],
                                                                  d_vec, reinterpret_cast<float *>(d_vec + (size_t)nq * k), d_vec + (size_t)nq * k * 2, nullptr,
                                                                  vis_for(nq), sl.stream, blk + s);
@@ -556,7 +585,8 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
                 NIDX_HIP(hipMemcpyAsync(sl.d_rq_table.p, sl.pin_rq_table.p, (size_t)n_rq * sizeof(RabitqSearchArgs), hipMemcpyHostToDevice, sl.stream));
                 NIDX_HIP(launch_rabitq_hnsw_segments(sl.d_rq_table.as<RabitqSearchArgs>(), n_rq, h_rq[0], sl.stream));
             }
-            NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, tab_bytes, hipMemcpyHostToDevice, sl.stream));
+            // the tables go up only for a kernel of this batch that reads them: the table-driven walk or Fssc
+            if (n_hnsw || sl.merged) NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, tab_bytes, hipMemcpyHostToDevice, sl.stream));
             if (n_hnsw) {
                 HnswSearchArgs a = h_hnsw[0];
                 a.seg_table = sl.d_tables.as<HnswSearchArgs>();
@@ -576,14 +606,14 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
                 NIDX_HIP(sl.d_offered.reserve((size_t)nq * f.offered_stride * 12));
                 f.offered = sl.d_offered.as<uint32_t>();
             }
-            f.out_seg = blk + fw;
+            f.out_seg = (host_block ? hblk : blk) + fw;
             f.out_para = f.out_seg + (size_t)nq * k;
             f.out_vec = f.out_para + (size_t)nq * k;
             f.out_score = reinterpret_cast<float *>(f.out_vec + (size_t)nq * k);
             f.out_count = f.out_vec + (size_t)nq * k * 2;
             NIDX_HIP(launch_fssc_merge(f, sl.stream));
-            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, (fw + mw) * 4, hipMemcpyDeviceToHost, sl.stream));
-        } else {
+            if (!host_block) NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, (fw + mw) * 4, hipMemcpyDeviceToHost, sl.stream));
+        } else if (!host_block) {
             NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, words * 4, hipMemcpyDeviceToHost, sl.stream));
         }
         NIDX_HIP(hipEventRecord(sl.done, sl.stream));
@@ -648,9 +678,20 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
     NIDX_HIP(hipEventSynchronize(sl.done));   // (a failure leaves the slot dirty: SlotRelease drains its stream)
     const size_t fw = flag_words(S), mw = sl.mw, sw = seg_words(nq, k);
     uint32_t *host = sl.pin_out.as<uint32_t>();
+    // per searched segment: did a walk raise a flag?  The copy route reads the device's flag word of the segment; the host block
+    // carries one row per walk (written unconditionally, so a row of an earlier batch never shows through), ORed here
+    std::vector<uint32_t> seg_flags(S, 0);
     bool flagged = false;
-    for (size_t s = 0; s < S; s++)
-        if (host[s] && sl.method[s]) flagged = true;
+    for (size_t s = 0; s < S; s++) {
+        if (!sl.method[s]) continue;
+        if (sl.host_block) {
+            const uint32_t *row = host + fw + mw + S * sw + s * (size_t)nq;
+            for (uint32_t q = 0; q < nq; q++) seg_flags[s] |= row[q];
+        } else {
+            seg_flags[s] = host[s];
+        }
+        if (seg_flags[s]) flagged = true;
+    }
     if (!flagged) {
         sl.dirty = false;   // everything queued has completed and no flag word is set
         if (k == 0) return NIDX_OK;
@@ -675,7 +716,7 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
             NIDX_HIP(hipStreamSynchronize(sl.stream));
         }
         for (size_t s = 0; s < S; s++) {
-            if (!host[s] || !sl.method[s]) continue;
+            if (!seg_flags[s]) continue;
             if (sl.method[s] != NIDX_METHOD_HNSW && sl.method[s] != NIDX_METHOD_RABITQ_HNSW) continue;
             // a bounded on-chip structure overflowed for some query of this segment: the complete OpenSegment::search (larger visited
             // table / HBM-resident walk for the flagged queries), synchronously, into the index's own block, then over the slot's rows
@@ -690,8 +731,10 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
             memcpy(host + fw + mw + s * sw, pin_out.p, sw * 4);
             if (n_retried_out) *n_retried_out += retried;
         }
-        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
-        NIDX_HIP(hipStreamSynchronize(sl.stream));
+        if (!sl.host_block) {   // (the host block's flag rows are rewritten by the next batch: nothing to clear)
+            NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
+            NIDX_HIP(hipStreamSynchronize(sl.stream));
+        }
         sl.dirty = false;
     }
     if (k == 0) return NIDX_OK;
