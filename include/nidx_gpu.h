@@ -61,6 +61,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_PREFILTER_BATCH 16 /* nidx_gpu_bm25_prefilter_batch */
 #define NIDX_FEATURE_BM25_HIT_TERMS 32 /* nidx_gpu_bm25_hit_terms_batch */
 #define NIDX_FEATURE_PREFILTER_HANDOVER 64 /* nidx_gpu_bm25_prefilter_batch_resident, nidx_gpu_prefilter_rows_* / _link_*, nidx_gpu_vector_search_prefiltered_per_query */
+#define NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER 128 /* nidx_gpu_prefilter_term_link_*, nidx_gpu_bm25_search_prefiltered */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1045,6 +1046,68 @@ int32_t nidx_gpu_vector_search_prefiltered_per_query(nidx_gpu_vector_index_t *in
                                                      const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint32_t *out_segment,
                                                      uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
                                                      int32_t *out_method, uint64_t *out_matching, nidx_gpu_prefilter_search_stats_t *stats_out);
+
+/* ---- the paragraph half of the hand-over: the same resident rows go to the paragraph search ---------------------------------------
+ * The reference hands the one PrefilterResult of a request to the paragraph search as well, where Some(fields) becomes a SetQuery over
+ * the field_uuid terms (nidx/src/searcher/shard_search.rs:176-275, nidx_paragraph/src/search_query.rs:87-146).  Two pieces do that
+ * here for the rows of nidx_gpu_bm25_prefilter_batch_resident, both present when nidx_gpu_build_features() &
+ * NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER:
+ *
+ * 1. nidx_gpu_prefilter_term_link_create: the paragraph index's term of every text document.  doc_terms[s][d] is the term id of the
+ *    field_uuid term of document d of OPENED text segment s (UINT32_MAX: none; the caller resolves them once per pair of generations,
+ *    a term-dictionary lookup per field).  The link lives in HBM as one uint32 per bit position of a prefilter row; it records both
+ *    generations and the text index's row layout and is stale (refused by the search) after a sync of either index.
+ *    NIDX_ERR_INVALID_ARGUMENT, and no handle, for a term id >= the paragraph index's n_terms, indexes on different devices, or an
+ *    n_text_segments that is not the text index's opened count.  stats_out->postings: the postings the linked documents reach, summed
+ *    over the paragraph index's resident segments (a term linked from two documents counts twice).
+ *    nidx_gpu_prefilter_term_link_read: for tests, the term of every document of one opened text segment (at most `capacity`;
+ *    *n_out = the segment's documents).
+ *
+ * 2. nidx_gpu_bm25_search_prefiltered: nidx_gpu_bm25_search_ex in which term set j with prefilter_of_term_set[j] != UINT32_MAX is a
+ *    ROW SET: its own term range must be empty and its complement flag clear, and its documents are the union of the posting lists
+ *    linked to the documents set in the row of request prefilter_of_term_set[j] of `rows` (a None request: the empty set, an All
+ *    request: every document of the segment).  Clauses name it as NIDX_BM25_TERM_SET | j like any term set, at top level or as a
+ *    leaf of a nested query; occur, ConstScorer(boost) scoring and place in the clause order are a term set's, so every output equals
+ *    that of the same call with the set spelled out as terms.  Per resident segment ONE launch (bm25_prefilter_project.hip) projects
+ *    all distinct rows the call names and ONE compaction turns them into ascending doc-id lists; sets that name the same row (or
+ *    requests that share a row) share one list, and the All requests share one.  Scratch per resident segment: per DISTINCT row one
+ *    bitset (documents / 8 bytes) and one list region of min(documents, postings the link reaches) ids — of every document when an
+ *    All request is among them — of 4 bytes each; the lists are ConstScorer lists and have no parallel frequency region.  A row set
+ *    itself, like any term set without terms and without the complement flag, owns no bitset and takes part in no compaction, so
+ *    nothing is sized by the number of queries.  NIDX_ERR_UNSUPPORTED (split the batch) when the distinct rows are more than 65 535
+ *    or their scratch on one resident segment exceeds 16 GiB (NIDX_GPU_BM25_ROW_SCRATCH_MAX, bytes, read when the index is opened).  Before anything is launched or written to an
+ *    output, NIDX_ERR_INVALID_ARGUMENT with a message naming the set for: a link whose paragraph generation is not the index's, rows
+ *    whose generation or layout is not the link's text side, a request index out of range, a row set with terms of its own or with
+ *    the complement flag, a row set while link or rows is NULL.  With prefilter_of_term_set NULL or all UINT32_MAX the call is
+ *    nidx_gpu_bm25_search_ex, and link / rows may be NULL. */
+typedef struct nidx_gpu_prefilter_term_link nidx_gpu_prefilter_term_link_t;
+typedef struct nidx_gpu_prefilter_term_link_stats {
+    uint64_t linked_documents; /* text documents with a term */
+    uint64_t postings;         /* postings reachable through the link, summed over the paragraph index's resident segments */
+    uint64_t bytes;            /* HBM the link takes */
+    uint64_t text_generation, paragraph_generation;
+} nidx_gpu_prefilter_term_link_stats_t;
+int32_t nidx_gpu_prefilter_term_link_create(nidx_gpu_bm25_index_t *text_index, nidx_gpu_bm25_index_t *paragraph_index,
+                                            const uint32_t *const *doc_terms, uint32_t n_text_segments,
+                                            nidx_gpu_prefilter_term_link_t **link_out, nidx_gpu_prefilter_term_link_stats_t *stats_out);
+void nidx_gpu_prefilter_term_link_free(nidx_gpu_prefilter_term_link_t *link);
+int32_t nidx_gpu_prefilter_term_link_read(const nidx_gpu_prefilter_term_link_t *link, uint32_t text_segment, uint32_t *out_terms,
+                                          uint64_t capacity, uint64_t *n_out);
+
+typedef struct nidx_gpu_bm25_prefilter_search_stats {
+    uint32_t rows_projected;      /* distinct prefilter rows the call names (the shared row of the All requests not counted) */
+    uint32_t projection_launches; /* one per resident segment */
+    uint32_t compaction_launches; /* one per resident segment, over all distinct rows */
+    uint32_t reserved;
+    uint64_t documents_visited;   /* set bits of the projected rows, once per resident segment */
+    uint64_t postings_written;    /* doc ids ORed into the rows' bitsets */
+    uint64_t list_entries;        /* entries of the materialised lists over all segments, a shared list counted once */
+} nidx_gpu_bm25_prefilter_search_stats_t;
+int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
+                                         const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
+                                         const uint64_t *clause_offsets, uint32_t n_queries, const nidx_gpu_bm25_search_options_t *options,
+                                         const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
+                                         uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out);
 
 /* open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74), the device half: the caller maps the deletion keys that
  * are newer than the segment (`Seq(segment) < del_seq`) to term ids the way the DeletionQueryBuilders do (a key longer than 32

@@ -157,6 +157,7 @@ FEATURE_BM25_FUZZY_BATCH = 8   # nidx_gpu_build_features() bit: nidx_gpu_bm25_fu
 FEATURE_BM25_PREFILTER_BATCH = 16   # nidx_gpu_build_features() bit: nidx_gpu_bm25_prefilter_batch
 FEATURE_BM25_HIT_TERMS = 32   # nidx_gpu_build_features() bit: nidx_gpu_bm25_hit_terms_batch
 FEATURE_PREFILTER_HANDOVER = 64   # nidx_gpu_build_features() bit: resident prefilter rows, the text-to-vector link, nidx_gpu_vector_search_prefiltered_per_query
+FEATURE_PARAGRAPH_PREFILTER_HANDOVER = 128   # nidx_gpu_build_features() bit: the text-to-paragraph term link, nidx_gpu_bm25_search_prefiltered
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -205,6 +206,18 @@ class PrefilterSearchStatsC(C.Structure):
     """nidx_gpu_prefilter_search_stats_t"""
     _fields_ = [("rows_projected", C.c_uint32), ("projection_launches", C.c_uint32), ("chunks", C.c_uint32), ("filter_synchronisations", C.c_uint32),
                 ("documents_visited", C.c_uint64), ("paragraphs_written", C.c_uint64)]
+
+
+class PrefilterTermLinkStatsC(C.Structure):
+    """nidx_gpu_prefilter_term_link_stats_t"""
+    _fields_ = [("linked_documents", C.c_uint64), ("postings", C.c_uint64), ("bytes", C.c_uint64), ("text_generation", C.c_uint64),
+                ("paragraph_generation", C.c_uint64)]
+
+
+class Bm25PrefilterSearchStatsC(C.Structure):
+    """nidx_gpu_bm25_prefilter_search_stats_t"""
+    _fields_ = [("rows_projected", C.c_uint32), ("projection_launches", C.c_uint32), ("compaction_launches", C.c_uint32), ("reserved", C.c_uint32),
+                ("documents_visited", C.c_uint64), ("postings_written", C.c_uint64), ("list_entries", C.c_uint64)]
 
 
 class Bm25HitTermsStatsC(C.Structure):
@@ -382,6 +395,13 @@ SIGNATURES = {
                                                    C.POINTER(PrefilterLinkStatsC)]),
     "nidx_gpu_prefilter_link_free": (None, [C.c_void_p]),
     "nidx_gpu_prefilter_link_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_prefilter_term_link_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
+                                                        C.POINTER(PrefilterTermLinkStatsC)]),
+    "nidx_gpu_prefilter_term_link_free": (None, [C.c_void_p]),
+    "nidx_gpu_prefilter_term_link_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_bm25_search_prefiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                     C.POINTER(Bm25SearchOptionsC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(Bm25PrefilterSearchStatsC)]),
     "nidx_gpu_vector_search_prefiltered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                                  C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

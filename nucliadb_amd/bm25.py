@@ -39,6 +39,9 @@ class Clause:
     # a nested BooleanQuery (NIDX_BM25_SUBQUERY): its leaves — clauses of any kind, nested queries included; the outer clause
     # contributes boost x the nested query's own score; `term` and `mode` are ignored
     subquery: Optional[Sequence["Clause"]] = None
+    # a row set (nidx_gpu_bm25_search_prefiltered): ConstScorer(boost) over the documents of the posting lists linked to the text
+    # documents set in the resident prefilter row of this request of the `rows` handed to search_batch_ex; `term` and `mode` are ignored
+    prefilter_request: Optional[int] = None
 
 
 @dataclass
@@ -267,12 +270,41 @@ class ResidentPrefilters:
             pass
 
 
+class PrefilterTermLink:
+    """nidx_gpu_prefilter_term_link_t: the paragraph index's term of every text document, resident in HBM; stale after a sync of
+    either index.  `stats` is the PrefilterTermLinkStatsC of its creation."""
+
+    def __init__(self, handle, stats):
+        self.handle = handle
+        self.stats = stats
+
+    def read(self, text_segment: int) -> np.ndarray:
+        """The term of every document of one opened text segment (0xFFFFFFFF: none), read back from the device: tests."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_read(self.handle, text_segment, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), np.uint32)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_read(self.handle, text_segment, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
+    def close(self):
+        if self.handle:
+            _lib.lib().nidx_gpu_prefilter_term_link_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Bm25Searcher:
     """The scoring core shared by TextSearcher::search and ParagraphSearcher::search."""
 
     def __init__(self):
         self._handle = C.c_void_p()
         self.segments: List[Bm25Segment] = []
+        self.last_prefilter_search_stats = None   # Bm25PrefilterSearchStatsC of the last search_batch_ex call that had row sets
 
     @classmethod
     def open(cls, segments: Sequence[Bm25Segment]) -> "Bm25Searcher":
@@ -501,9 +533,12 @@ class Bm25Searcher:
         return ResidentPrefilters(handle, kinds, matching, live.value, stats)
 
     def search_batch_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
-                        order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None):
+                        order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None,
+                        link: Optional[PrefilterTermLink] = None, rows: Optional[ResidentPrefilters] = None):
         """The collectors around the scoring (nidx_text/src/reader.rs:367-451): term-set clauses, TopDocs ordered by a
-        fast field, facet counts (facets[q] = term ids to count among query q's matching documents).
+        fast field, facet counts (facets[q] = term ids to count among query q's matching documents).  Clauses with
+        `prefilter_request` are lowered to empty term sets that read a row of `rows` through `link`
+        (nidx_gpu_bm25_search_prefiltered, called only when there is one; its stats are kept in last_prefilter_search_stats).
         -> dict(docaddr, score, count, total, postings, order_value, facet_counts[q] = counts aligned with facets[q])"""
         B = len(queries)
         offsets = np.zeros(B + 1, dtype=np.uint64)
@@ -515,6 +550,14 @@ class Bm25Searcher:
         set_terms: List[int] = []
         set_offsets = [0]
         set_comp: List[int] = []
+        # Row sets come behind the sets of terms, one per distinct request: the sets that scatter stay consecutive (one compaction on the
+        # device), and clauses naming the same request name the same set.
+        def count_sets(clauses) -> int:
+            return sum(count_sets(c.subquery) if c.subquery is not None else
+                       int(c.prefilter_request is None and c.term_set is not None and not c.phrase) for c in clauses)
+
+        n_term_sets = count_sets(flat)
+        row_set_of: Dict[int, int] = {}   # request -> its row set's index
         phrase_terms: List[int] = []
         phrase_offsets = [0]
         phrase_slops: List[int] = []
@@ -529,6 +572,9 @@ class Bm25Searcher:
                 sub_leaves.extend((t, l.occur, m, l.boost) for t, m, l in leaves)
                 sub_offsets.append(len(sub_leaves))
                 return _lib.BM25_SUBQUERY | (len(sub_offsets) - 2), c.mode
+            if c.prefilter_request is not None:
+                j = row_set_of.setdefault(int(c.prefilter_request), n_term_sets + len(row_set_of))
+                return _lib.BM25_TERM_SET | j, _lib.CONST_SCORE
             if c.term_set is not None and c.phrase:
                 phrase_terms.extend(int(t) for t in c.term_set)
                 phrase_offsets.append(len(phrase_terms))
@@ -550,6 +596,10 @@ class Bm25Searcher:
             for i, a in enumerate(after):
                 if a is not None:
                     af[i].has_after, af[i].score, af[i].tie_break, af[i].docaddr = 1, a.score, a.tie_break, a.docaddr
+        assert len(set_offsets) - 1 == n_term_sets
+        set_offsets.extend([len(set_terms)] * len(row_set_of))   # (dict order = index order)
+        set_comp.extend([0] * len(row_set_of))
+        set_prefilter = [0xFFFFFFFF] * n_term_sets + list(row_set_of)   # per term set: the request whose row it reads, or none
         kk = max(1, k)
         docaddr = np.zeros((B, kk), dtype=np.uint64)
         score = np.zeros((B, kk), dtype=np.float32)
@@ -592,8 +642,17 @@ class Bm25Searcher:
             opt.facet_offsets = fo.ctypes.data
             opt.out_facet_counts = fc.ctypes.data
         opt.out_order_value = order_value.ctypes.data
-        _lib.check(_lib.lib().nidx_gpu_bm25_search_ex(self._handle, cl, offsets.ctypes.data, B, C.byref(opt), docaddr.ctypes.data,
-                                                      score.ctypes.data, count.ctypes.data, total.ctypes.data, postings.ctypes.data))
+        if row_set_of:
+            sp = np.ascontiguousarray(set_prefilter, dtype=np.uint32)
+            stats = _lib.Bm25PrefilterSearchStatsC()
+            _lib.check(_lib.lib().nidx_gpu_bm25_search_prefiltered(self._handle, None if link is None else link.handle,
+                                                                   None if rows is None else rows.handle, cl, offsets.ctypes.data, B, C.byref(opt),
+                                                                   sp.ctypes.data, docaddr.ctypes.data, score.ctypes.data, count.ctypes.data,
+                                                                   total.ctypes.data, postings.ctypes.data, C.byref(stats)))
+            self.last_prefilter_search_stats = stats
+        else:
+            _lib.check(_lib.lib().nidx_gpu_bm25_search_ex(self._handle, cl, offsets.ctypes.data, B, C.byref(opt), docaddr.ctypes.data,
+                                                          score.ctypes.data, count.ctypes.data, total.ctypes.data, postings.ctypes.data))
         facet_counts = None
         if facets is not None:
             facet_counts = [fc[int(fo[q]): int(fo[q + 1])].astype(np.int64) for q in range(B)]

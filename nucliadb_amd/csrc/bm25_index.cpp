@@ -85,6 +85,8 @@ struct Bm25Ctx {
     DevBuf s_after, s_count, s_total, s_postings, s_key;
     DevBuf s_fuse_done, s_fuse_key, s_fuse_count, s_fuse_total, s_fuse_postings;   // Bm25FusedMerge (s_fuse_done is zeroed when it grows and stays zero between launches)
     DevBuf s_phrase_tf, s_aux_tfs, s_slop_left, s_sub_bits, s_sub_union;
+    DevBuf s_row_bits, s_row_ptrs, s_row_stats;   // nidx_gpu_bm25_search_prefiltered: the projected rows, their sources, the kernel's counters
+    std::vector<const uint64_t *> w_row_ptrs;
     DevBuf s_set_terms, s_set_bits, s_aux_off, s_aux_out_off, s_aux_ids, s_set_counts, s_match_bits, s_match_slot, s_pair_term, s_pair_slot,
         s_facet_counts;
     // packed staging: [clauses | clause offsets], [item_first | work list] in; [doc | score | count | total | postings] out
@@ -165,6 +167,7 @@ struct Bm25Index {
     uint32_t n_segments = 0;               // segments the caller opened
     uint64_t total_docs = 0, total_tokens = 0;
     uint32_t n_terms = 0;
+    uint64_t row_scratch_max = 16ull << 30;   // bitsets + list regions of the distinct rows of one search call, per resident segment
     std::vector<float> idf_of_term;   // Bm25Weight's idf per term over all segments (filled at open)
     // Score floors (bm25_aux.hip: bm25_term_floor_kernel): floor_fn[t][j] = fieldnorm id under which >= BM25_FLOOR_RANKS[j] postings of term t
     // lie; quot1[id] = 1 / (1 + K(id)), the tf = 1 row of tf_cache.  Empty = no floors (several resident layouts, a quotient row that is not
@@ -468,6 +471,9 @@ int32_t nidx_gpu_bm25_open(const nidx_gpu_bm25_segment_t *segments, uint32_t n_s
     // NIDX_GPU_BM25_SEGMENT_LOOP=1 keeps one resident segment per opened segment and the search a loop over them (launches, a
     // transfer and a host merge per segment): the path the one-launch layout is tested against
     const char *loop_env = getenv("NIDX_GPU_BM25_SEGMENT_LOOP");
+    // NIDX_GPU_BM25_ROW_SCRATCH_MAX: bytes the distinct prefilter rows of one nidx_gpu_bm25_search_prefiltered call may take per resident
+    // segment (tests reach the refusal with a small value)
+    if (const char *e = getenv("NIDX_GPU_BM25_ROW_SCRATCH_MAX")) idx->row_scratch_max = strtoull(e, nullptr, 10);
     // Segments that disagree on positions (some indexed WithFreqsAndPositions, some not) keep their own resident layouts too: the one
     // layout would have to drop the positions of ALL of them, and a phrase over a field only the positioned segments hold would fail.
     bool some_pos = false, some_without = false;
@@ -1648,14 +1654,41 @@ int32_t bm25_prefilter_row_layout(nidx_gpu_bm25_index_t *index, PrefilterRowLayo
     generation = idx->generation.load();
     return NIDX_OK;
 }
+
+int32_t bm25_term_link_target(nidx_gpu_bm25_index_t *index, const std::vector<uint32_t> &doc_term, int &device, uint64_t &generation,
+                              std::vector<uint64_t> &segment_postings) {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    device = idx->device;
+    generation = idx->generation.load();
+    segment_postings.assign(idx->segs.size(), 0);
+    for (size_t b = 0; b < doc_term.size(); b++) {
+        const uint32_t t = doc_term[b];
+        if (t == 0xffffffffu) continue;
+        if (t >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "term link: term id %u out of range (the paragraph index has %u terms)", t, idx->n_terms);
+        for (size_t s = 0; s < idx->segs.size(); s++)
+            segment_postings[s] += idx->segs[s].term_offsets_host[t + 1] - idx->segs[s].term_offsets_host[t];
+    }
+    return NIDX_OK;
+}
 }  // namespace nidx
+
+// The row sets of nidx_gpu_bm25_search_prefiltered, checked by the entry: term set j with row_of_set[j] != UINT32_MAX reads the list
+// of distinct row row_of_set[j] — aux list n_sets + n_phrases + n_sub + row_of_set[j] of every segment — instead of its own (empty) one.
+struct Bm25RowSets {
+    const PrefilterTermLink *link = nullptr;
+    const PrefilterRows *rows = nullptr;
+    std::vector<uint32_t> row_of_set;   // [n_term_sets]; UINT32_MAX: an ordinary term set (a row set of a None request is one: empty)
+    std::vector<uint32_t> distinct;     // rows->row_ptr index of every distinct row, kPrefilterRowAll for the shared row of the All requests
+    nidx_gpu_bm25_prefilter_search_stats_t stats = {};
+};
 
 // The search itself, on the context `cx` (the caller owns it for the duration and holds idx->rw shared).  With `async_slot` set and a
 // request the pipeline covers it returns after the last asynchronous call (launches + the device-to-host transfer of the result block
 // are queued on the slot's stream).
 static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_slot, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
                                   uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *out_docaddr, float *out_score,
-                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings) {
+                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings, Bm25RowSets *rs = nullptr) {
     const double t_entry = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     NIDX_HIP(hipSetDevice(idx->device));
     // other tickets are out: this batch's launches will share the GPU with theirs (the throughput shape of the work list, below)
@@ -1691,6 +1724,9 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         return fail(NIDX_ERR_INVALID_ARGUMENT, "term sets without terms");
     for (uint64_t i = 0; n_sets && i < opt->term_set_offsets[n_sets]; i++)
         if (opt->term_set_terms[i] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set: term id %u out of range", opt->term_set_terms[i]);
+    // row sets (nidx_gpu_bm25_search_prefiltered): the distinct rows are aux lists behind the term sets, phrases and nested queries
+    const uint32_t n_rows_d = rs ? (uint32_t)rs->distinct.size() : 0u;
+    auto row_of_set = [&](uint32_t j) { return n_rows_d ? rs->row_of_set[j] : 0xffffffffu; };
     const uint32_t n_phrases = opt->n_phrases;
     if (n_phrases && (!opt->phrase_offsets || !opt->phrase_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "phrases without terms");
     for (uint32_t j = 0; j < n_phrases; j++) {
@@ -1736,7 +1772,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             if (cl.term & NIDX_BM25_TERM_SET) {   // ConstScorer(boost) over the union
                 const uint32_t a = cl.term & ~NIDX_BM25_TERM_SET;
                 if (a >= n_sets) return fail(NIDX_ERR_INVALID_ARGUMENT, "nested query %u: term set %u out of range", j, a);
-                sq.src[t] = BM25_AUX_TERM | a, sq.mode[t] = NIDX_CONST_SCORE, sq.weight[t] = cl.boost;
+                sq.src[t] = BM25_AUX_TERM | (row_of_set(a) == 0xffffffffu ? a : n_sets + n_phrases + opt->n_subqueries + row_of_set(a));
+                sq.mode[t] = NIDX_CONST_SCORE, sq.weight[t] = cl.boost;
             } else if (cl.term & NIDX_BM25_PHRASE) {
                 const uint32_t a = cl.term & ~NIDX_BM25_PHRASE;
                 if (a >= n_phrases) return fail(NIDX_ERR_INVALID_ARGUMENT, "nested query %u: phrase %u out of range", j, a);
@@ -1794,7 +1831,9 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         }
         if (cl.term & NIDX_BM25_TERM_SET) {
             if ((cl.term & ~NIDX_BM25_TERM_SET) >= n_sets) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u out of range", cl.term & ~NIDX_BM25_TERM_SET);
-            dev_clauses[c] = Bm25ClauseDev{cl.term, cl.occur, NIDX_CONST_SCORE, cl.boost};  // ConstScorer(boost)
+            const uint32_t j = cl.term & ~NIDX_BM25_TERM_SET, r = row_of_set(j);
+            dev_clauses[c] = Bm25ClauseDev{r == 0xffffffffu ? cl.term : BM25_AUX_TERM | (n_sets + n_phrases + n_sub + r), cl.occur, NIDX_CONST_SCORE,
+                                           cl.boost};  // ConstScorer(boost)
             continue;
         }
         if (cl.term >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "term id %u out of range", cl.term);
@@ -1889,15 +1928,23 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
     struct Hit { float score; uint64_t docaddr; int64_t value; };
     std::vector<std::vector<Hit>> merged(idx->segs.size() == 1 ? 0 : nq);
     std::vector<Bm25Work> &work = cx.w_work;
+    unsigned long long row_stats[2] = {0, 0};   // documents visited, postings written by the projections of this call
+    if (n_rows_d) {
+        NIDX_HIP(cx.s_row_stats.reserve(16));
+        NIDX_HIP(hipMemsetAsync(cx.s_row_stats.p, 0, 16, cx.stream));
+    }
     for (size_t s = 0; s < idx->segs.size(); s++) {
         Bm25Segment &seg = idx->segs[s];
         // ---- the aux lists of this segment, in dependency order: term sets (union bitset -> ascending doc list,
         // AutomatonWeight::scorer), phrases, nested queries (children before parents); one host round trip for all their counts ----
-        const uint32_t n_aux = n_sets + n_phrases + n_sub;
+        const uint32_t n_own = n_sets + n_phrases + n_sub, n_aux = n_own + n_rows_d;   // (the distinct rows of the row sets come last)
         std::vector<unsigned long long> aux_pairs(2 * (size_t)n_aux + 2, 0);  // [begin, end) per aux list into s_aux_ids
         std::vector<uint32_t> set_counts(n_aux, 0);
         // layout of the aux arrays: one region per list, sized by an upper bound of its length
         std::vector<unsigned long long> out_off(n_aux + 1, 0);
+        // a projected row holds at most the postings the link reaches in this segment, and at most every document
+        const uint64_t row_bound = !n_rows_d ? 0 : rs->distinct.back() == kPrefilterRowAll ? (uint64_t)seg.n_docs
+                                                 : std::min<uint64_t>(seg.n_docs, rs->link->segment_postings[s]);
         std::vector<PhraseDev> phrases(n_phrases);
         for (uint32_t j = 0; j < n_sets; j++) {
             uint64_t df = 0;
@@ -1928,7 +1975,10 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         for (uint32_t j = 0; j < n_sub; j++) {
             SubqueryDev &sq = subs[j];
             auto upper = [&](uint32_t t) -> uint64_t {
-                if (sq.src[t] & BM25_AUX_TERM) { const uint32_t a = sq.src[t] & ~BM25_AUX_TERM; return out_off[a + 1] - out_off[a]; }
+                if (sq.src[t] & BM25_AUX_TERM) {
+                    const uint32_t a = sq.src[t] & ~BM25_AUX_TERM;
+                    return a >= n_own ? row_bound : out_off[a + 1] - out_off[a];   // (the rows' regions are laid out behind this loop)
+                }
                 return seg.term_offsets_host[sq.src[t] + 1] - seg.term_offsets_host[sq.src[t]];
             };
             uint64_t best = ~0ull, group_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, should_sum = 0;
@@ -1958,29 +2008,75 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             max_cand = std::max(max_cand, pl.n_cand_max);
             out_off[n_sets + n_phrases + j + 1] = out_off[n_sets + n_phrases + j] + pl.n_cand_max;
         }
+        for (uint32_t r = 0; r < n_rows_d; r++) out_off[n_own + r + 1] = out_off[n_own + r] + row_bound;
         const uint32_t words = (seg.n_docs + 63) / 64;
         if (n_aux) {
             NIDX_HIP(cx.s_aux_ids.reserve(std::max<uint64_t>(out_off[n_aux], 1) * 4 + BM25_LIST_PAD_BYTES));
-            NIDX_HIP(cx.s_aux_tfs.reserve(std::max<uint64_t>(out_off[n_aux], 1) * 4 + BM25_LIST_PAD_BYTES));
+            // (the rows' lists come last and are ConstScorer lists, whose frequencies no kernel reads: no parallel region for them)
+            NIDX_HIP(cx.s_aux_tfs.reserve(std::max<uint64_t>(out_off[n_own], 1) * 4 + BM25_LIST_PAD_BYTES));
             NIDX_HIP(cx.s_set_counts.reserve((size_t)n_aux * 4 + 4));   // + the count of the union candidates
             NIDX_HIP(hipMemsetAsync(cx.s_set_counts.p, 0, (size_t)n_aux * 4 + 4, cx.stream));
             NIDX_HIP(cx.s_aux_out_off.reserve((size_t)(n_aux + 1) * 8));
             NIDX_HIP(hipMemcpyAsync(cx.s_aux_out_off.p, out_off.data(), (size_t)(n_aux + 1) * 8, hipMemcpyHostToDevice, cx.stream));
         }
-        if (n_sets && words) {
-            NIDX_HIP(cx.s_set_bits.reserve(std::max<size_t>((size_t)n_sets * words, 1) * 8));
-            NIDX_HIP(launch_bitset_fill(cx.s_set_bits.as<uint64_t>(), n_sets * words, n_sets * words * 64u, 0, cx.stream));
+        // A set owns a bitset when it has terms or the complement flag.  A set with neither — every row set is one — is the empty
+        // list its zeroed count already says: no bitset, no place in a compaction.  Scratch follows the sets that scatter, not the queries.
+        auto owns_bits = [&](uint32_t j) {
+            return opt->term_set_offsets[j + 1] != opt->term_set_offsets[j] || (opt->term_set_complement && opt->term_set_complement[j]);
+        };
+        uint32_t n_bitsets = 0;
+        for (uint32_t j = 0; j < n_sets; j++) n_bitsets += owns_bits(j) ? 1u : 0u;
+        if (n_bitsets && words) {
+            NIDX_HIP(cx.s_set_bits.reserve(std::max<size_t>((size_t)n_bitsets * words, 1) * 8));
+            NIDX_HIP(launch_bitset_fill(cx.s_set_bits.as<uint64_t>(), n_bitsets * words, 0, 0, cx.stream));   // (n_bits matters when filling with ones only)
+            uint32_t slot = 0;
             for (uint32_t j = 0; j < n_sets; j++) {
+                if (!owns_bits(j)) continue;
                 const uint32_t nl = (uint32_t)(opt->term_set_offsets[j + 1] - opt->term_set_offsets[j]);
                 if (nl)
                     NIDX_HIP(launch_bitset_scatter(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(),
                                                    cx.s_set_terms.as<uint32_t>() + opt->term_set_offsets[j], nl, seg.n_docs,
-                                                   cx.s_set_bits.as<uint64_t>() + (size_t)j * words, cx.stream));
+                                                   cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, cx.stream));
                 if (opt->term_set_complement && opt->term_set_complement[j])
-                    NIDX_HIP(launch_bitset_not(cx.s_set_bits.as<uint64_t>() + (size_t)j * words, words, seg.n_docs, cx.stream));
+                    NIDX_HIP(launch_bitset_not(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, seg.n_docs, cx.stream));
+                slot++;
             }
-            NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>(), words, n_sets, cx.s_aux_out_off.as<unsigned long long>(),
-                                           cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>(), cx.stream));
+            // one compaction per run of consecutive sets that own a bitset (all sets do, and it is one, unless empty sets lie between)
+            slot = 0;
+            for (uint32_t j = 0; j < n_sets;) {
+                if (!owns_bits(j)) { j++; continue; }
+                uint32_t j1 = j;
+                while (j1 < n_sets && owns_bits(j1)) j1++;
+                NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, j1 - j,
+                                               cx.s_aux_out_off.as<unsigned long long>() + j, cx.s_aux_ids.as<uint32_t>(),
+                                               cx.s_set_counts.as<uint32_t>() + j, cx.stream));
+                slot += j1 - j;
+                j = j1;
+            }
+        }
+        if (n_rows_d && words) {
+            // every distinct row onto this segment in one launch, every row's list in one compaction; the All requests share a row of ones
+            NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
+            NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
+            uint32_t n_proj = n_rows_d;
+            if (rs->distinct.back() == kPrefilterRowAll) {   // (the entry lists it last)
+                n_proj--;
+                NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
+            }
+            if (n_proj) {
+                cx.w_row_ptrs.resize(n_proj);
+                for (uint32_t r = 0; r < n_proj; r++) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]];
+                NIDX_HIP(cx.s_row_ptrs.reserve((size_t)n_proj * sizeof(uint64_t *)));
+                NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), (size_t)n_proj * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
+                NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, (uint32_t)rs->rows->layout.words(),
+                                                       rs->link->doc_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
+                                                       seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
+                                                       cx.s_row_stats.as<unsigned long long>(), cx.stream));
+                rs->stats.projection_launches++;
+            }
+            NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, cx.s_aux_out_off.as<unsigned long long>() + n_own,
+                                           cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_own, cx.stream));
+            rs->stats.compaction_launches++;
         }
         for (uint32_t j = 0; j < n_phrases; j++) {
             const uint64_t n_driver = out_off[n_sets + j + 1] - out_off[n_sets + j];
@@ -2031,7 +2127,10 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         }
         if (n_aux) {
             NIDX_HIP(hipMemcpyAsync(set_counts.data(), cx.s_set_counts.p, (size_t)n_aux * 4, hipMemcpyDeviceToHost, cx.stream));
+            if (n_rows_d) NIDX_HIP(hipMemcpyAsync(row_stats, cx.s_row_stats.p, 16, hipMemcpyDeviceToHost, cx.stream));   // (running sums over the segments)
             NIDX_HIP(hipStreamSynchronize(cx.stream));
+            for (uint32_t r = 0; r < n_rows_d; r++) rs->stats.list_entries += set_counts[n_own + r];
+            if (n_rows_d) rs->stats.documents_visited = row_stats[0], rs->stats.postings_written = row_stats[1];
             for (uint32_t j = 0; j < n_aux; j++) {
                 aux_pairs[2 * j] = out_off[j];
                 aux_pairs[2 * j + 1] = out_off[j] + set_counts[j];
@@ -2041,7 +2140,10 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         }
         const double t_seg0 = now_us();
         auto postings_of = [&](const nidx_gpu_bm25_clause_t &cl) -> uint64_t {
-            if (cl.term & NIDX_BM25_TERM_SET) return set_counts[cl.term & ~NIDX_BM25_TERM_SET];
+            if (cl.term & NIDX_BM25_TERM_SET) {
+                const uint32_t j = cl.term & ~NIDX_BM25_TERM_SET, r = row_of_set(j);
+                return set_counts[r == 0xffffffffu ? j : n_own + r];
+            }
             if (cl.term & NIDX_BM25_PHRASE) return set_counts[n_sets + (cl.term & ~NIDX_BM25_PHRASE)];
             if (cl.term & NIDX_BM25_SUBQUERY) return set_counts[n_sets + n_phrases + (cl.term & ~NIDX_BM25_SUBQUERY)];
             return seg.term_offsets_host[cl.term + 1] - seg.term_offsets_host[cl.term];
@@ -2514,6 +2616,85 @@ int32_t nidx_gpu_bm25_search_ex(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
         std::lock_guard<std::mutex> ms(idx->ms_mu);
         idx->last_kernel_ms = idx->main.kernel_ms;
     }
+    return rc;
+} NIDX_ABI_CATCH
+
+// nidx_gpu_bm25_search_ex whose term sets may be row sets: the documents of the posting lists linked to the documents set in a
+// resident prefilter row (prefilter_handover.h).  Everything is checked here, before the search writes an output.
+int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
+                                         const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
+                                         const uint64_t *clause_offsets, uint32_t nq, const nidx_gpu_bm25_search_options_t *opt,
+                                         const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
+                                         uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !clause_offsets || !out_count || !opt) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    const PrefilterTermLink *l = reinterpret_cast<const PrefilterTermLink *>(link);
+    const PrefilterRows *r = reinterpret_cast<const PrefilterRows *>(rows);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rlock(idx->rw);
+    Bm25RowSets rs;
+    rs.link = l, rs.rows = r;
+    const uint32_t n_sets = opt->n_term_sets;
+    bool any = false;
+    for (uint32_t j = 0; prefilter_of_term_set && j < n_sets; j++) any |= prefilter_of_term_set[j] != 0xffffffffu;
+    if (any) {
+        if (!opt->term_set_offsets) return fail(NIDX_ERR_INVALID_ARGUMENT, "term sets without offsets");
+        rs.row_of_set.assign(n_sets, 0xffffffffu);
+        std::vector<uint32_t> slot_of_row;   // row -> its place in rs.distinct
+        bool any_all = false;
+        for (uint32_t j = 0; j < n_sets; j++) {
+            const uint32_t q = prefilter_of_term_set[j];
+            if (q == 0xffffffffu) continue;
+            if (!l || !r) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u is a row set, but there is no %s", j, !l ? "link" : "prefilter rows handle");
+            if (opt->term_set_offsets[j + 1] != opt->term_set_offsets[j])
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u is a row set and has terms of its own", j);
+            if (opt->term_set_complement && opt->term_set_complement[j])
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u is a row set and has the complement flag", j);
+            if (l->device != idx->device || r->device != idx->device)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: the link or the rows are on another device than the index", j);
+            if (l->paragraph_generation != idx->generation.load())
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: the link was built for generation %llu of this index, which is at %llu", j,
+                            (unsigned long long)l->paragraph_generation, (unsigned long long)idx->generation.load());
+            if (l->segment_postings.size() != idx->segs.size()) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: the link was built for another resident layout", j);
+            if (r->generation != l->text_generation || !(r->layout == l->layout))
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: the rows are of generation %llu of the text index, the link of %llu (or of another layout)", j,
+                            (unsigned long long)r->generation, (unsigned long long)l->text_generation);
+            if (q >= r->row_of_request.size())
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: request %u of %zu", j, q, r->row_of_request.size());
+            const uint32_t row = r->row_of_request[q];
+            if (row == kPrefilterRowNone) continue;   // the empty set: the term set as it stands
+            if (row == kPrefilterRowAll) { any_all = true; rs.row_of_set[j] = 0xfffffffeu; continue; }   // (placed below)
+            if (slot_of_row.empty()) slot_of_row.assign(r->row_ptr.size(), 0xffffffffu);
+            if (slot_of_row[row] == 0xffffffffu) {
+                slot_of_row[row] = (uint32_t)rs.distinct.size();
+                rs.distinct.push_back(row);
+            }
+            rs.row_of_set[j] = slot_of_row[row];
+        }
+        if (any_all) {
+            for (uint32_t &x : rs.row_of_set)
+                if (x == 0xfffffffeu) x = (uint32_t)rs.distinct.size();
+            rs.distinct.push_back(kPrefilterRowAll);   // last: bm25_search_locked fills it with ones
+        }
+        if (rs.distinct.size() > 65535) return fail(NIDX_ERR_UNSUPPORTED, "more than 65535 distinct prefilter rows in one search call");
+        // the rows' scratch, as bm25_search_locked lays it out per resident segment: a bitset and a list region per distinct row
+        const uint64_t scratch_max = idx->row_scratch_max;   // (read at open)
+        for (size_t s = 0; s < idx->segs.size(); s++) {
+            const uint64_t n_docs = idx->segs[s].n_docs, bound = any_all ? n_docs : std::min<uint64_t>(n_docs, l->segment_postings[s]);
+            const uint64_t bytes = (uint64_t)rs.distinct.size() * ((n_docs + 63) / 64 * 8 + bound * 4);
+            if (bytes > scratch_max)
+                return fail(NIDX_ERR_UNSUPPORTED, "%zu distinct prefilter rows need %llu bytes of scratch on resident segment %zu (at most %llu): split the batch",
+                            rs.distinct.size(), (unsigned long long)bytes, s, (unsigned long long)scratch_max);
+        }
+    }
+    rs.stats.rows_projected = (uint32_t)rs.distinct.size() - (!rs.distinct.empty() && rs.distinct.back() == kPrefilterRowAll ? 1u : 0u);
+    const int32_t rc = bm25_search_locked(idx, idx->main, nullptr, clauses, clause_offsets, nq, opt, out_docaddr, out_score, out_count, out_total, out_postings,
+                                          rs.distinct.empty() ? nullptr : &rs);
+    {
+        std::lock_guard<std::mutex> ms(idx->ms_mu);
+        idx->last_kernel_ms = idx->main.kernel_ms;
+    }
+    if (rc == NIDX_OK && stats_out) *stats_out = rs.stats;
     return rc;
 } NIDX_ABI_CATCH
 

@@ -447,6 +447,14 @@ struct PrefilterProjSeg {
 // stats[0] += documents visited, stats[1] += paragraph ids written.
 hipError_t launch_prefilter_project(const uint64_t *const *rows, uint32_t n_rows, uint32_t n_words, const uint32_t *doc_off, const uint2 *entries,
                                     const PrefilterProjSeg *segs, uint64_t *out, unsigned long long *stats, hipStream_t s);
+// The paragraph half (bm25_prefilter_project.hip): projects prefilter rows onto ONE resident segment of the paragraph index through
+// doc_term (the paragraph index's term id of every bit position of a row, UINT32_MAX = none): grid = (64-word spans of a row, rows),
+// one wave per span, zero words skipped by ballot; every set document ORs the doc ids of its term's posting list into output row
+// `row` (out_words 64-bit words each, zeroed by the caller) with 32-bit atomicOr — a list of more than 64 postings by the whole
+// wave, a shorter one by its lane.  stats[0] += documents visited, stats[1] += postings written (one atomic each per wave).
+hipError_t launch_bm25_prefilter_project(const uint64_t *const *rows, uint32_t n_rows, uint32_t n_words, const uint32_t *doc_term,
+                                         const unsigned long long *term_offsets, const uint32_t *doc_ids, uint32_t n_bits, uint32_t out_words,
+                                         uint64_t *out, unsigned long long *stats, hipStream_t s);
 // dst[i] = src[idx[i]] for rows of dp floats (the queries one search arm of a batch takes)
 hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s);
 

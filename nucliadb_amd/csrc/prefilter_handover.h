@@ -1,6 +1,7 @@
 // prefilter_handover.h — what the three pieces of the prefilter hand-over share: the resident rows of a prefilter batch
 // (bm25_index.cpp), the document -> (vector segment, list) link (prefilter_link.cpp) and the search that projects the rows through the
-// link (vector_index.cpp, vector_prefilter.hip).
+// link (vector_index.cpp, vector_prefilter.hip) — and of the paragraph half: the document -> term link (prefilter_link.cpp) and the
+// BM25 search whose term sets may name a row (bm25_index.cpp, bm25_prefilter_project.hip).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -58,7 +59,21 @@ struct PrefilterLink {
     uint64_t n_entries = 0, linked_documents = 0;
 };
 
+// nidx_gpu_prefilter_term_link_t: the paragraph index's term id of every bit position of a row (UINT32_MAX: none)
+struct PrefilterTermLink {
+    int device = 0;
+    uint64_t text_generation = 0, paragraph_generation = 0;
+    PrefilterRowLayout layout;             // of the text index
+    DevBuf doc_term;                       // [words * 64] u32
+    std::vector<uint64_t> segment_postings;   // [resident paragraph segment] postings reachable through the link
+    uint64_t linked_documents = 0, postings = 0;
+};
+
 // bm25_index.cpp: the layout, device and generation of an open index (takes the index's lock)
 int32_t bm25_prefilter_row_layout(nidx_gpu_bm25_index_t *index, PrefilterRowLayout &layout, int &device, uint64_t &generation);
+// bm25_index.cpp: the paragraph side of a term link (takes the index's lock) — its device and generation, and for the terms of the bit
+// positions (UINT32_MAX: none; any other id must be below the index's n_terms) the postings they reach in every resident segment
+int32_t bm25_term_link_target(nidx_gpu_bm25_index_t *index, const std::vector<uint32_t> &doc_term, int &device, uint64_t &generation,
+                              std::vector<uint64_t> &segment_postings);
 
 }  // namespace nidx

@@ -174,4 +174,67 @@ int32_t nidx_gpu_prefilter_link_read(const nidx_gpu_prefilter_link_t *link, uint
     return NIDX_OK;
 } NIDX_ABI_CATCH
 
+// ---- the paragraph half: text document -> term of the paragraph index ---------------------------------------------------------------
+// The reference turns a prefilter's fields into the paragraph index's field_uuid terms on each request
+// (nidx_paragraph/src/search_query.rs:87-146).  Which term a text document's field has depends on the two generations only: one u32
+// per bit position of a prefilter row, which bm25_prefilter_project.hip reads for the set bits of a row.
+int32_t nidx_gpu_prefilter_term_link_create(nidx_gpu_bm25_index_t *text_index, nidx_gpu_bm25_index_t *paragraph_index,
+                                            const uint32_t *const *doc_terms, uint32_t n_text_segments,
+                                            nidx_gpu_prefilter_term_link_t **link_out, nidx_gpu_prefilter_term_link_stats_t *stats_out) try {
+    if (!text_index || !paragraph_index || !link_out || (n_text_segments && !doc_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::unique_ptr<PrefilterTermLink> link(new PrefilterTermLink());
+    if (int32_t rc = bm25_prefilter_row_layout(text_index, link->layout, link->device, link->text_generation)) return rc;
+    const PrefilterRowLayout &layout = link->layout;
+    if (n_text_segments != layout.n_opened)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "terms for %u text segments, the index has %u", n_text_segments, layout.n_opened);
+    const uint64_t n_bits = layout.words() * 64;
+    std::vector<uint32_t> terms((size_t)n_bits, 0xffffffffu);   // (the bits between two resident segments belong to no document)
+    for (uint32_t s = 0; s < n_text_segments; s++) {
+        const uint32_t n = layout.opened_docs(s);
+        if (n && !doc_terms[s]) return fail(NIDX_ERR_INVALID_ARGUMENT, "text segment %u: NULL terms", s);
+        for (uint32_t d = 0; d < n; d++) {
+            terms[(size_t)layout.bit_of(s, d)] = doc_terms[s][d];
+            link->linked_documents += doc_terms[s][d] != 0xffffffffu ? 1 : 0;
+        }
+    }
+    int device = 0;
+    if (int32_t rc = bm25_term_link_target(paragraph_index, terms, device, link->paragraph_generation, link->segment_postings)) return rc;
+    if (device != link->device)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "the text index is on device %d, the paragraph index on device %d", link->device, device);
+    for (uint64_t p : link->segment_postings) link->postings += p;
+    NIDX_HIP(hipSetDevice(link->device));
+    NIDX_HIP(link->doc_term.alloc(std::max<size_t>((size_t)n_bits, 1) * 4));
+    if (n_bits) NIDX_HIP(hipMemcpy(link->doc_term.p, terms.data(), (size_t)n_bits * 4, hipMemcpyHostToDevice));
+    if (stats_out) {
+        stats_out->linked_documents = link->linked_documents;
+        stats_out->postings = link->postings;
+        stats_out->bytes = link->doc_term.bytes;
+        stats_out->text_generation = link->text_generation;
+        stats_out->paragraph_generation = link->paragraph_generation;
+    }
+    *link_out = reinterpret_cast<nidx_gpu_prefilter_term_link_t *>(link.release());
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+void nidx_gpu_prefilter_term_link_free(nidx_gpu_prefilter_term_link_t *link) {
+    PrefilterTermLink *l = reinterpret_cast<PrefilterTermLink *>(link);
+    if (!l) return;
+    (void)hipSetDevice(l->device);
+    delete l;
+}
+
+int32_t nidx_gpu_prefilter_term_link_read(const nidx_gpu_prefilter_term_link_t *link, uint32_t text_segment, uint32_t *out_terms,
+                                          uint64_t capacity, uint64_t *n_out) try {
+    const PrefilterTermLink *l = reinterpret_cast<const PrefilterTermLink *>(link);
+    if (!l || !n_out || (capacity && !out_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    const PrefilterRowLayout &layout = l->layout;
+    if (text_segment >= layout.n_opened) return fail(NIDX_ERR_INVALID_ARGUMENT, "text segment %u of %u", text_segment, layout.n_opened);
+    const uint64_t n = layout.opened_docs(text_segment), got = std::min<uint64_t>(n, capacity);
+    NIDX_HIP(hipSetDevice(l->device));
+    // (the documents of an opened segment sit at consecutive bit positions in both layouts)
+    if (got) NIDX_HIP(hipMemcpy(out_terms, l->doc_term.as<uint32_t>() + layout.bit_of(text_segment, 0), (size_t)got * 4, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
 }  // extern "C"

@@ -2097,7 +2097,8 @@ int32_t nidx_gpu_last_error(char *buf, size_t len) try {
 int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
 int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
-           NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER;
+           NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
+           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {

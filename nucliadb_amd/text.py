@@ -26,6 +26,7 @@ PhraseQuery's (positions in HBM, phrase lists materialised on the device).
 from __future__ import annotations
 
 import bisect
+import ctypes as C
 
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Set, Tuple
@@ -33,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import _lib
-from .bm25 import Bm25Searcher, Bm25Segment, Clause, SearchAfter, tokenize
+from .bm25 import Bm25Searcher, Bm25Segment, Clause, PrefilterTermLink, ResidentPrefilters, SearchAfter, tokenize
 
 ALL_DOCS = "\x00all"            # pseudo term: every document (AllQuery, scored by ConstScorer)
 NOT_REPEATED = "\x00repeated:0"  # pseudo term: paragraphs with repeated_in_field == 0
@@ -1041,6 +1042,20 @@ FUZZY_BOOST = 0.5          # search_query.rs:235-239
 SUGGEST_RESULTS_PER_PAGE = 10   # reader.rs:86
 
 
+@dataclass(frozen=True)
+class ResidentPrefilter:
+    """One request's verdict out of a ResidentPrefilters (TextSearcher.prefilter_batch_resident): where a host PrefilterResult of
+    kind Some carries its fields, this one names the request whose row on the device holds them."""
+    kind: str
+    request: Optional[int] = None
+
+
+def _prefilter_is_some(prefilter) -> bool:
+    if prefilter is None or prefilter.kind != "Some":
+        return False
+    return isinstance(prefilter, ResidentPrefilter) or bool(prefilter.fields)
+
+
 class ParagraphSearcher:
     """nidx_paragraph::ParagraphSearcher (lib.rs:117-169) — `search`: keyword query, fuzzy fallback, facets, order."""
 
@@ -1144,6 +1159,9 @@ class ParagraphSearcher:
                 members.append(nested(expr, occur))
 
         def prefilter_sets(occur: int, out: List[Clause]):
+            if isinstance(prefilter, ResidentPrefilter):   # the row stands for the field_uuid set; rows are field-granular: no uuid set
+                out.append(Clause(0, occur, _lib.CONST_SCORE, boost, prefilter_request=prefilter.request))
+                return
             fields = sorted({"\x00fid:" + rid + "/" + fid.lstrip("/") for rid, fid in prefilter.fields if fid is not None})
             resources = sorted({"\x00uuid:" + rid for rid, fid in prefilter.fields if fid is None})
             for keys in (fields, resources):   # SetQuery = TermSetQuery: ConstScorer over the union of the terms
@@ -1151,7 +1169,7 @@ class ParagraphSearcher:
                     terms = [self._index.term(t) for t in keys]
                     out.append(Clause(0, occur, _lib.CONST_SCORE, boost, term_set=terms))
 
-        some = prefilter is not None and prefilter.kind == "Some" and prefilter.fields
+        some = _prefilter_is_some(prefilter)
         if request.filter_or and (request.filtering_formula is not None or some):
             g = new_group()
             if request.filtering_formula is not None:
@@ -1218,7 +1236,7 @@ class ParagraphSearcher:
         automaton accepts; None = one fuzzy_terms call per word."""
         expand = expand or self._index.fuzzy_terms
         tokens = self._tokens(request)
-        some = prefilter is not None and prefilter.kind == "Some" and prefilter.fields
+        some = _prefilter_is_some(prefilter)
         filters_present = bool(request.label_filter) or not request.with_duplicates or request.filtering_formula is not None or bool(some)
         boost = FUZZY_BOOST if filters_present else 1.0  # BoostQuery(0.5) only wraps a multi-clause Boolean (:229-240)
         fuzzy_words = self._fuzzy_words(tokens)
@@ -1248,45 +1266,66 @@ class ParagraphSearcher:
             for res, ids in zip(results, per_hit):
                 res.matches = sorted((self._index.terms[int(t)] for t in ids), key=lambda t: t.encode("utf-8"))
 
-    def _run(self, request: ParagraphSearchRequest, clauses: List[Clause], fuzzy: bool,
-             fuzzy_sets: Optional[List[List[int]]] = None) -> ParagraphSearchResponse:
-        """Searcher::do_search (reader.rs:244-348) + the response assembly (search_response.rs:218-311).  `fuzzy_sets` = the accepted
-        terms of every fuzzy word when `clauses` is the fuzzy query: its hits get their `matches`."""
+    def _assemble(self, request: ParagraphSearchRequest, r, row: int, fuzzy: bool, facets, pairs) -> Tuple[ParagraphSearchResponse, List[int]]:
+        """The response assembly (search_response.rs:218-311) from row `row` of a search_batch_ex result -> (response, the
+        DocAddresses of its results: what `matches` are looked up under)."""
         k = max(0, int(request.result_per_page))
         ematches = paragraph_ematches(self._tokens(request), fuzzy, only_faceted=request.only_faceted)
-        facets, pairs = self._index.facet_request(request.faceted)
-        fterms = [[tid for _, _, tid in pairs]] if pairs else None
         if request.only_faceted:
-            r = self._index.searcher.search_batch_ex([clauses], 0, facets=fterms)
-            return ParagraphSearchResponse(0, [], False, "", self._index.produce_facets(facets, pairs, r["facet_counts"][0] if pairs else []), fuzzy)
+            return ParagraphSearchResponse(0, [], False, "", self._index.produce_facets(facets, pairs, r["facet_counts"][row] if pairs else []), fuzzy), []
         order = request.order
-        after = [request.search_after] if request.search_after is not None and order is None else None
-        r = self._index.searcher.search_batch_ex([clauses], k + 1, after, order_field=-1 if order is None else order.field,
-                                                order_desc=True if order is None else order.desc, facets=fterms)
         docaddr, score, total = r["docaddr"], r["score"], r["total"]
-        obtained = int(r["count"][0])
-        fc = self._index.produce_facets(facets, pairs, r["facet_counts"][0]) if pairs else {}
+        obtained = int(r["count"][row])
+        fc = self._index.produce_facets(facets, pairs, r["facet_counts"][row]) if pairs else {}
         results, addrs = [], []
         if order is not None:  # SearchIntResponse: no min_score, next_page = total > requested
             for i in range(min(obtained, k)):
-                d = self._index.doc(int(docaddr[0, i]))
-                results.append(ParagraphResult(d.uuid, d.field, d.text, None, list(d.labels), sort_value=int(r["order_value"][0, i])))
-                addrs.append(int(docaddr[0, i]))
-            if fuzzy_sets is not None:
-                self._set_matches([(results, addrs, fuzzy_sets)])
-            return ParagraphSearchResponse(int(total[0]), results, int(total[0]) > k, request.body, fc, fuzzy, ematches)
-        scores = [float(score[0, i]) for i in range(obtained)]
+                d = self._index.doc(int(docaddr[row, i]))
+                results.append(ParagraphResult(d.uuid, d.field, d.text, None, list(d.labels), sort_value=int(r["order_value"][row, i])))
+                addrs.append(int(docaddr[row, i]))
+            return ParagraphSearchResponse(int(total[row]), results, int(total[row]) > k, request.body, fc, fuzzy, ematches), addrs
+        scores = [float(score[row, i]) for i in range(obtained)]
         # search_response.rs:218-311: next_page counts scores above min_score, results stop at the first below it
         next_page = sum(1 for s in scores if s > request.min_score) > k
         for i in range(min(obtained, k)):
             if scores[i] < request.min_score:
                 break
-            d = self._index.doc(int(docaddr[0, i]))
-            results.append(ParagraphResult(d.uuid, d.field, d.text, ResultScore(scores[i], int(docaddr[0, i])), list(d.labels)))
-            addrs.append(int(docaddr[0, i]))
-        if fuzzy_sets is not None:
-            self._set_matches([(results, addrs, fuzzy_sets)])
-        return ParagraphSearchResponse(int(total[0]), results, next_page, request.body, fc, fuzzy, ematches)
+            d = self._index.doc(int(docaddr[row, i]))
+            results.append(ParagraphResult(d.uuid, d.field, d.text, ResultScore(scores[i], int(docaddr[row, i])), list(d.labels)))
+            addrs.append(int(docaddr[row, i]))
+        return ParagraphSearchResponse(int(total[row]), results, next_page, request.body, fc, fuzzy, ematches), addrs
+
+    @staticmethod
+    def _group_key(request: ParagraphSearchRequest):
+        """What one search_batch_ex call shares among its queries: TopDocs' limit, the order, whether hits are wanted at all and
+        whether cursors travel (facets and the cursors themselves are per query)."""
+        order = request.order
+        return (max(0, int(request.result_per_page)), None if order is None else (order.field, bool(order.desc)), bool(request.only_faceted),
+                request.search_after is not None and order is None)
+
+    def _run_group(self, requests: Sequence[ParagraphSearchRequest], queries: Sequence[List[Clause]], fuzzy: bool, link=None, rows=None):
+        """Searcher::do_search (reader.rs:244-348) for requests of one _group_key in ONE search_batch_ex call
+        -> [(response, DocAddresses of its results)]."""
+        k, order, only_faceted, cursors = self._group_key(requests[0])
+        requested = [self._index.facet_request(rq.faceted) for rq in requests]
+        fterms = [[tid for _, _, tid in pairs] for _, pairs in requested] if any(pairs for _, pairs in requested) else None
+        extra = {} if link is None and rows is None else {"link": link, "rows": rows}
+        if only_faceted:
+            r = self._index.searcher.search_batch_ex(list(queries), 0, facets=fterms, **extra)
+        else:
+            after = [rq.search_after for rq in requests] if cursors else None
+            r = self._index.searcher.search_batch_ex(list(queries), k + 1, after, order_field=-1 if order is None else order[0],
+                                                    order_desc=True if order is None else order[1], facets=fterms, **extra)
+        return [self._assemble(rq, r, row, fuzzy, *requested[row]) for row, rq in enumerate(requests)]
+
+    def _run(self, request: ParagraphSearchRequest, clauses: List[Clause], fuzzy: bool,
+             fuzzy_sets: Optional[List[List[int]]] = None) -> ParagraphSearchResponse:
+        """One request through _run_group.  `fuzzy_sets` = the accepted terms of every fuzzy word when `clauses` is the fuzzy query:
+        its hits get their `matches`."""
+        response, addrs = self._run_group([request], [clauses], fuzzy)[0]
+        if fuzzy_sets is not None and not request.only_faceted:
+            self._set_matches([(response.results, addrs, fuzzy_sets)])
+        return response
 
     def search(self, request: ParagraphSearchRequest, prefilter: Optional[PrefilterResult] = None) -> ParagraphSearchResponse:
         """ParagraphReaderService::search (reader.rs:104-139): the keyword query first; when it finds nothing (and results
@@ -1308,6 +1347,83 @@ class ParagraphSearcher:
             sets = [expand(*key) for key in self._fuzzy_words(self._tokens(request)).values()]
             response = self._run(request, clauses, True, sets)
         return response
+
+    # ---- the batch form and the resident hand-over -----------------------------------------------------------------------------
+    def link_text(self, text_searcher) -> PrefilterTermLink:
+        """The link between the text searcher's documents and this index's field_uuid terms (nidx_gpu_prefilter_term_link_create):
+        per document the id of "\\x00fid:" + uuid + "/" + field — the term prefilter_sets looks up for a host PrefilterResult —
+        or 0xFFFFFFFF when this index has no such term (or the document no field)."""
+        index = text_searcher._index
+        doc_terms = []
+        for seg in index.segments:
+            ids = [None if d.field is None else self._index.vocab.lookup("\x00fid:" + d.uuid + "/" + d.field.lstrip("/")) for d in seg.docs]
+            doc_terms.append(np.ascontiguousarray([0xFFFFFFFF if t is None else t for t in ids], dtype=np.uint32))
+        n = len(doc_terms)
+        c_terms = (C.c_void_p * max(1, n))(*[t.ctypes.data if t.size else None for t in doc_terms])
+        handle, stats = C.c_void_p(), _lib.PrefilterTermLinkStatsC()
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_create(index.searcher._handle, self._index.searcher._handle, c_terms, n, C.byref(handle),
+                                                                  C.byref(stats)))
+        return PrefilterTermLink(handle, stats)
+
+    @staticmethod
+    def _per_request_prefilters(prefilters, n: int):
+        """-> (one prefilter per request, the ResidentPrefilters they came from or None).  Requests of a resident batch that share a
+        program name the same request of the handle: they share a row there, and one list in the search."""
+        if prefilters is None:
+            return [None] * n, None
+        if isinstance(prefilters, ResidentPrefilters):
+            assert len(prefilters) == n
+            return [ResidentPrefilter(kind, prefilters.request_of[prefilters.same_as[i]] if kind == "Some" else None)
+                    for i, kind in enumerate(prefilters.kinds)], prefilters
+        prefilters = list(prefilters)
+        assert len(prefilters) == n
+        return prefilters, None
+
+    def search_many(self, requests: Sequence[ParagraphSearchRequest], prefilters=None, link: Optional[PrefilterTermLink] = None) -> List[ParagraphSearchResponse]:
+        """[self.search(r, p) for r, p in zip(requests, prefilters)] for a serving batch.  `prefilters`: host PrefilterResults, or the
+        ResidentPrefilters of TextSearcher.prefilter_batch_resident together with link = self.link_text(text_searcher) — then no
+        list leaves the device and the requests that share a row share one projected list.  Requests with equal _group_key go
+        through one search_batch_ex call; those that found nothing and qualify for the fuzzy rerun share ONE fuzzy_terms_batch, one
+        fuzzy search per group and ONE hit_terms_batch: at most four library calls for a batch of one group."""
+        n = len(requests)
+        prefilters, rows = self._per_request_prefilters(prefilters, n)
+        out: List[Optional[ParagraphSearchResponse]] = [None] * n
+        groups: Dict[tuple, List[int]] = {}
+        for i, (rq, pf) in enumerate(zip(requests, prefilters)):
+            if pf is not None and pf.kind == "None":
+                out[i] = ParagraphSearchResponse(0, [], False, rq.body, {}, False)
+            else:
+                groups.setdefault(self._group_key(rq), []).append(i)
+        missed: Dict[tuple, List[int]] = {}
+        for key, members in groups.items():
+            answers = self._run_group([requests[i] for i in members], [self._clauses(requests[i], prefilters[i]) for i in members], False, link, rows)
+            for i, (response, _) in zip(members, answers):
+                out[i] = response
+                rq = requests[i]
+                if not response.results and rq.result_per_page > 0 and rq.min_score == 0.0 and not rq.only_faceted:
+                    missed.setdefault(key, []).append(i)
+        if not missed:
+            return out
+        # the words to expand, each distinct (word, prefix) once
+        pairs: Dict[Tuple[str, bool], List[int]] = {}
+        for members in missed.values():
+            for i in members:
+                for key in self._fuzzy_words(self._tokens(requests[i])).values():
+                    pairs[key] = []
+        if pairs:
+            keys = list(pairs)
+            for key, found in zip(keys, self._index.fuzzy_terms_batch(keys)):
+                pairs[key] = found
+        items = []
+        for members in missed.values():
+            fuzzy = [self._fuzzy_clauses(requests[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in members]
+            answers = self._run_group([requests[i] for i in members], fuzzy, True, link, rows)
+            for i, (response, addrs) in zip(members, answers):
+                out[i] = response
+                # one FuzzyTermQuery per fuzzy word, each logging on its own: a word given twice is two sets
+                items.append((response.results, addrs, [pairs[key] for key in self._fuzzy_words(self._tokens(requests[i])).values()]))
+        self._set_matches(items)
+        return out
 
     # ---- suggest ------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -1337,16 +1453,16 @@ class ParagraphSearcher:
         ematches = paragraph_ematches(self._tokens(self._suggest_as_search(request)), fuzzy, suggest=True)
         return ParagraphSearchResponse(obtained, results, next_page, request.body, {}, fuzzy, ematches)
 
-    def suggest_batch(self, requests: Sequence[ParagraphSuggestRequest],
-                      prefilters: Optional[Sequence[Optional[PrefilterResult]]] = None) -> List[ParagraphSearchResponse]:
+    def suggest_batch(self, requests: Sequence[ParagraphSuggestRequest], prefilters=None,
+                      link: Optional[PrefilterTermLink] = None) -> List[ParagraphSearchResponse]:
         """ParagraphReaderService::suggest (reader.rs:58-90) for a batch of type-ahead requests in at most four library calls: every
         keyword query in one search (TopDocs of the largest top_k: a larger TopDocs has the smaller one as its prefix), the fuzzy
         expansion of every distinct (word, prefix) of the requests that found nothing in one fuzzy_terms_batch, their fuzzy queries
         in one search, the `matches` of all their hits in one hit_terms_batch.  top_k == 0 asks for nothing (query_planner/suggest.rs:36-39) and a prefilter of kind None matches nothing:
-        both are answered without a search."""
+        both are answered without a search.  `prefilters`: host PrefilterResults, or a ResidentPrefilters with `link`, as for search_many."""
         n = len(requests)
-        prefilters = [None] * n if prefilters is None else list(prefilters)
-        assert len(prefilters) == n
+        prefilters, rows = self._per_request_prefilters(prefilters, n)
+        extra = {} if link is None and rows is None else {"link": link, "rows": rows}
         out: List[Optional[ParagraphSearchResponse]] = [None] * n
         live = []
         for i, (rq, pf) in enumerate(zip(requests, prefilters)):
@@ -1357,7 +1473,7 @@ class ParagraphSearcher:
         if not live:
             return out
         inner = {i: self._suggest_as_search(requests[i]) for i in live}
-        r = self._index.searcher.search_batch_ex([self._clauses(inner[i], prefilters[i]) for i in live], max(int(requests[i].top_k) for i in live))
+        r = self._index.searcher.search_batch_ex([self._clauses(inner[i], prefilters[i]) for i in live], max(int(requests[i].top_k) for i in live), **extra)
         missed = []
         for row, i in enumerate(live):
             obtained = min(int(r["count"][row]), int(requests[i].top_k))
@@ -1377,7 +1493,7 @@ class ParagraphSearcher:
             for key, members in zip(keys, self._index.fuzzy_terms_batch(keys)):
                 pairs[key] = members
         fuzzy = [self._fuzzy_clauses(inner[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in missed]
-        r = self._index.searcher.search_batch_ex(fuzzy, max(int(requests[i].top_k) for i in missed))
+        r = self._index.searcher.search_batch_ex(fuzzy, max(int(requests[i].top_k) for i in missed), **extra)
         items = []
         for row, i in enumerate(missed):
             out[i] = self._suggest_response(requests[i], r, row, min(int(r["count"][row]), int(requests[i].top_k)), True)
