@@ -62,6 +62,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_HIT_TERMS 32 /* nidx_gpu_bm25_hit_terms_batch */
 #define NIDX_FEATURE_PREFILTER_HANDOVER 64 /* nidx_gpu_bm25_prefilter_batch_resident, nidx_gpu_prefilter_rows_* / _link_*, nidx_gpu_vector_search_prefiltered_per_query */
 #define NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER 128 /* nidx_gpu_prefilter_term_link_*, nidx_gpu_bm25_search_prefiltered */
+#define NIDX_FEATURE_JSON_PREFILTER 256 /* nidx_gpu_json_*, nidx_gpu_prefilter_rows_combine / _state / _read_resources */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1108,6 +1109,161 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
                                          const uint64_t *clause_offsets, uint32_t n_queries, const nidx_gpu_bm25_search_options_t *options,
                                          const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
                                          uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out);
+
+/* ---- the JSON prefilter on the device, combined with the text prefilter's rows -------------------------------------------------------
+ * Prefilter::run (src/searcher/query_planner/prefilter.rs:41-91) runs the text prefilter and the JSON prefilter side by side:
+ * JsonSearcher::search (nidx_json/src/search.rs, reader.rs) evaluates fast-field range queries over typed JSON paths and collects a
+ * set of resource uuids, and PrefilterResult::combine (nidx_types/src/prefilter.rs:46-92) joins the two.  Four pieces do that here on
+ * bit rows in HBM, all present when the build features hold NIDX_FEATURE_JSON_PREFILTER:
+ *
+ * 1. The resident JSON index.  Per segment the caller hands over n_docs, the alive bitset (NULL: every document is alive; the reference
+ *    opens with open_index_with_deletions), every document's encoded_resource_id as two uint64 words (as_u64_pair, nidx_json/src/
+ *    schema.rs:59-71; first word major) and its fast-field columns.  A column has a path of opaque bytes (the shim spells it as tantivy
+ *    does, "{field_id}.{json_path}"), a type, docs[n_values] ascending (a document may repeat: multi-valued; or be absent) and
+ *    values[n_values] as uint64; a STR column also has its sorted dictionary, and its values are ordinals into it.  The library sees
+ *    only ORDER-PRESERVING uint64 values; the mapping is the caller's: i64 x -> x ^ 2^63; f64 -> flip the sign bit when it is clear,
+ *    else complement all bits (the caller never hands over a NaN); date -> tantivy's i64 nanoseconds mapped like i64; bool -> 0 or 1.
+ *    (The mapping restates tantivy's and, like the other oracle-defined values, is not yet pinned against the crate: DESIGN.md §8
+ *    item 4.)  The index owns a RESOURCE TABLE: the distinct uuids of all segments, ascending as unsigned 128-bit numbers, and per
+ *    document the ordinal of its resource.  A segment holds at most one column per (path, type).  There is no sync of a JSON index: a
+ *    new generation is close and open.
+ *
+ * 2. A batch of JSON prefilters.  Request i is a postfix program over its leaves: NIDX_FILTER_PUSH_LISTS with a = the leaf's index
+ *    in the request (b is not read), AND, OR, NOT (every alive document minus the operand: the AllQuery + MustNot of search.rs:181-189),
+ *    PUSH_ALL, PUSH_NONE.  A document satisfies a leaf when ANY of its values in that segment's column of the leaf's (path, type) lies
+ *    in lo <= v <= hi (has_lo / has_hi; for STR the string to match exactly instead); a segment without such a column, or whose
+ *    dictionary lacks the string, contributes nothing; lo > hi is the empty leaf.  An empty program is NIDX_ERR_INVALID_ARGUMENT (the
+ *    reference refuses an empty JsonFilterExpression).  Every request is checked before anything is launched or written; messages
+ *    begin with "request i: ".  Identical requests and identical leaves are evaluated once; each (segment, column) a pass names is
+ *    read by ONE launch per chunk of at most NIDX_JSON_MAX_INTERVALS distinct intervals; all distinct programs of a pass run in one
+ *    launch, their result rows become RESOURCE ROWS (one bit per resource ordinal: a resource matches when any of its documents
+ *    does, RidSegmentCollector, reader.rs:36-47) in one launch and are counted in one.  Programs deeper than the combine kernel's
+ *    32-word stack are evaluated op by op with the same result; rows are cut into passes under max_scratch_bytes (0: 1 GiB).
+ *    out_matching[i] = the number of matching resources.  The rows handle keeps the resource row of EVERY distinct program, empty
+ *    or full (combine treats only the empty set specially); the read entry gives the matching resource ordinals of one request, ascending
+ *    (at most `capacity`; n_out = their number).
+ *
+ * 3. The resource link: the resource ordinal of every text document (UINT32_MAX: its resource is not in the JSON index), one uint32 per
+ *    bit position of a text prefilter row, filled by a device binary search over the resource table.  doc_resource_ids[s] = the
+ *    uuid pairs of the documents of opened text segment s.  It records the text index's generation (stale after nidx_gpu_bm25_sync);
+ *    both indexes must be on one device.
+ *
+ * 4. nidx_gpu_prefilter_rows_combine: PrefilterResult::combine.  text_rows may be NULL (every text request is All: the unwrap_or(All)
+ *    of prefilter.rs:83).  Output request i joins text request text_request and JSON request json_request (UINT32_MAX: the text result
+ *    passes through) under op.  The result is a new rows handle of the text rows' layout and generation in which a request is None, All
+ *    or Some, and a Some request has a field-granular part (a row over text documents), a resource-granular part (a row over resource
+ *    ordinals) or both:  J empty: Or -> the text result, And -> None.  Or: All -> All; None -> resources J; Some(F) -> resources J plus
+ *    the fields of F whose resource is not in J (an empty field part is absent).  And: None -> None; All -> resources J; Some(F) -> the
+ *    fields of F whose resource is in J, None when there are none.  One launch computes every field row; identical (text row, JSON row,
+ *    op) triples share one.  nidx_gpu_prefilter_rows_read keeps its meaning (the field part); the _read_resources entry gives the
+ *    resource part as ascending ordinals of the JSON index's table.  Refused: rows or link of another device, layout or generation
+ *    ("stale link"), JSON rows of another JSON index than the link's, a request index out of range, an unknown op.
+ *
+ * A combined handle whose request has no resource part is an ordinary field-row handle to both prefiltered searches.  A filter or term
+ * set that names a request WITH a resource-granular part is refused before any launch with NIDX_ERR_UNSUPPORTED (the message names
+ * the request); the other requests of the handle remain usable. */
+#define NIDX_JSON_MAX_INTERVALS 512 /* distinct intervals of one (segment, column) per launch (they sit in LDS) */
+enum { NIDX_JSON_STR = 0, NIDX_JSON_I64 = 1, NIDX_JSON_F64 = 2, NIDX_JSON_BOOL = 3, NIDX_JSON_DATE = 4 };
+enum { NIDX_PREFILTER_AND = 0, NIDX_PREFILTER_OR = 1 };
+enum { NIDX_PREFILTER_STATE_NONE = 0, NIDX_PREFILTER_STATE_ALL = 1, NIDX_PREFILTER_STATE_SOME = 2 };
+#define NIDX_PREFILTER_PART_FIELDS 1u
+#define NIDX_PREFILTER_PART_RESOURCES 2u
+typedef struct nidx_gpu_json_index nidx_gpu_json_index_t;
+typedef struct nidx_gpu_json_rows nidx_gpu_json_rows_t;
+typedef struct nidx_gpu_json_resource_link nidx_gpu_json_resource_link_t;
+typedef struct nidx_gpu_json_column {
+    const uint8_t *path;
+    uint32_t path_len;
+    int32_t type;                 /* NIDX_JSON_* */
+    const uint32_t *docs;         /* [n_values] ascending, each < n_docs */
+    const uint64_t *values;       /* [n_values] order-preserving; STR: ordinals into the dictionary */
+    uint64_t n_values;
+    const uint8_t *dict_bytes;    /* STR: the sorted, distinct strings */
+    const uint64_t *dict_offsets; /* STR: [n_dict + 1] */
+    uint32_t n_dict;
+} nidx_gpu_json_column_t;
+typedef struct nidx_gpu_json_segment {
+    uint32_t n_docs;
+    const uint64_t *alive_bitset;  /* NULL: every document is alive */
+    const uint64_t *resource_ids;  /* [n_docs][2] */
+    const nidx_gpu_json_column_t *columns;
+    uint32_t n_columns;
+} nidx_gpu_json_segment_t;
+typedef struct nidx_gpu_json_open_stats {
+    uint64_t documents, resources, columns, bytes;
+} nidx_gpu_json_open_stats_t;
+int32_t nidx_gpu_json_open(const nidx_gpu_json_segment_t *segments, uint32_t n_segments, nidx_gpu_json_index_t **index_out,
+                           nidx_gpu_json_open_stats_t *stats_out);
+void nidx_gpu_json_close(nidx_gpu_json_index_t *index);
+/* the resource table: at most `capacity` uuid pairs, ascending; n_out = their number */
+int32_t nidx_gpu_json_resources_read(const nidx_gpu_json_index_t *index, uint64_t *out_ids, uint64_t capacity, uint64_t *n_out);
+
+typedef struct nidx_gpu_json_leaf {
+    const uint8_t *path;
+    uint32_t path_len;
+    int32_t type;          /* NIDX_JSON_* */
+    int32_t has_lo, has_hi;
+    uint64_t lo, hi;       /* inclusive, in the column's order-preserving values (not read for STR) */
+    const uint8_t *str;    /* STR: the string to match exactly */
+    uint32_t str_len;
+} nidx_gpu_json_leaf_t;
+typedef struct nidx_gpu_json_prefilter {
+    nidx_gpu_filter_program_t program; /* lists / n_lists are not read */
+    const nidx_gpu_json_leaf_t *leaves;
+    uint32_t n_leaves;
+} nidx_gpu_json_prefilter_t;
+typedef struct nidx_gpu_json_prefilter_batch_stats {
+    uint32_t distinct_programs;
+    uint32_t operand_rows;      /* distinct leaves that own a row, summed over the passes */
+    uint32_t passes;
+    uint32_t fallback_requests; /* distinct programs evaluated op by op */
+    uint32_t launches;          /* kernels and device memsets */
+    uint32_t synchronisations;
+} nidx_gpu_json_prefilter_batch_stats_t;
+int32_t nidx_gpu_json_prefilter_batch_resident(nidx_gpu_json_index_t *index, const nidx_gpu_json_prefilter_t *requests, uint32_t n_requests,
+                                               uint64_t max_scratch_bytes, uint64_t *out_matching,
+                                               nidx_gpu_json_prefilter_batch_stats_t *stats_out, nidx_gpu_json_rows_t **rows_out);
+typedef struct nidx_gpu_json_rows_info {
+    uint32_t requests, rows;
+    uint64_t bytes, resources, row_words;
+} nidx_gpu_json_rows_info_t;
+void nidx_gpu_json_rows_free(nidx_gpu_json_rows_t *rows);
+int32_t nidx_gpu_json_rows_info(const nidx_gpu_json_rows_t *rows, nidx_gpu_json_rows_info_t *info_out);
+int32_t nidx_gpu_json_rows_read(const nidx_gpu_json_rows_t *rows, uint32_t request, uint32_t *out_resources, uint64_t capacity,
+                                uint64_t *n_out);
+
+typedef struct nidx_gpu_json_resource_link_stats {
+    uint64_t linked_documents; /* text documents whose resource is in the JSON index */
+    uint64_t bytes, text_generation, resources;
+} nidx_gpu_json_resource_link_stats_t;
+int32_t nidx_gpu_json_resource_link_create(nidx_gpu_bm25_index_t *text_index, nidx_gpu_json_index_t *json_index,
+                                           const uint64_t *const *doc_resource_ids, uint32_t n_text_segments,
+                                           nidx_gpu_json_resource_link_t **link_out, nidx_gpu_json_resource_link_stats_t *stats_out);
+void nidx_gpu_json_resource_link_free(nidx_gpu_json_resource_link_t *link);
+/* for tests: the resource ordinal of every document of one opened text segment (at most `capacity`; n_out = its documents) */
+int32_t nidx_gpu_json_resource_link_read(const nidx_gpu_json_resource_link_t *link, uint32_t text_segment, uint32_t *out_resources,
+                                         uint64_t capacity, uint64_t *n_out);
+
+typedef struct nidx_gpu_prefilter_combine_request {
+    uint32_t text_request;
+    uint32_t json_request; /* UINT32_MAX: the text result passes through */
+    int32_t op;            /* NIDX_PREFILTER_AND / _OR */
+} nidx_gpu_prefilter_combine_request_t;
+typedef struct nidx_gpu_prefilter_combine_stats {
+    uint32_t field_rows;       /* distinct (text row, JSON row, op) triples: the rows the launch computed */
+    uint32_t resource_rows;    /* distinct JSON rows the result refers to */
+    uint32_t launches, synchronisations;
+    uint32_t none, all, some;  /* the requests by state */
+    uint32_t reserved;
+} nidx_gpu_prefilter_combine_stats_t;
+int32_t nidx_gpu_prefilter_rows_combine(const nidx_gpu_prefilter_rows_t *text_rows, const nidx_gpu_json_rows_t *json_rows,
+                                        const nidx_gpu_json_resource_link_t *link, const nidx_gpu_prefilter_combine_request_t *requests,
+                                        uint32_t n_requests, nidx_gpu_prefilter_rows_t **rows_out,
+                                        nidx_gpu_prefilter_combine_stats_t *stats_out);
+/* state_out: NIDX_PREFILTER_STATE_*; parts_out: NIDX_PREFILTER_PART_* of a Some request (rows of a prefilter batch: fields) */
+int32_t nidx_gpu_prefilter_rows_state(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint32_t *state_out, uint32_t *parts_out);
+int32_t nidx_gpu_prefilter_rows_read_resources(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint32_t *out_resources,
+                                               uint64_t capacity, uint64_t *n_out);
 
 /* open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74), the device half: the caller maps the deletion keys that
  * are newer than the segment (`Seq(segment) < del_seq`) to term ids the way the DeletionQueryBuilders do (a key longer than 32

@@ -158,6 +158,7 @@ FEATURE_BM25_PREFILTER_BATCH = 16   # nidx_gpu_build_features() bit: nidx_gpu_bm
 FEATURE_BM25_HIT_TERMS = 32   # nidx_gpu_build_features() bit: nidx_gpu_bm25_hit_terms_batch
 FEATURE_PREFILTER_HANDOVER = 64   # nidx_gpu_build_features() bit: resident prefilter rows, the text-to-vector link, nidx_gpu_vector_search_prefiltered_per_query
 FEATURE_PARAGRAPH_PREFILTER_HANDOVER = 128   # nidx_gpu_build_features() bit: the text-to-paragraph term link, nidx_gpu_bm25_search_prefiltered
+FEATURE_JSON_PREFILTER = 256   # nidx_gpu_build_features() bit: the resident JSON index, its prefilter batch, the resource link, nidx_gpu_prefilter_rows_combine
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -218,6 +219,68 @@ class Bm25PrefilterSearchStatsC(C.Structure):
     """nidx_gpu_bm25_prefilter_search_stats_t"""
     _fields_ = [("rows_projected", C.c_uint32), ("projection_launches", C.c_uint32), ("compaction_launches", C.c_uint32), ("reserved", C.c_uint32),
                 ("documents_visited", C.c_uint64), ("postings_written", C.c_uint64), ("list_entries", C.c_uint64)]
+
+
+JSON_STR, JSON_I64, JSON_F64, JSON_BOOL, JSON_DATE = 0, 1, 2, 3, 4
+JSON_MAX_INTERVALS = 512   # NIDX_JSON_MAX_INTERVALS
+PREFILTER_AND, PREFILTER_OR = 0, 1
+PREFILTER_STATE_NONE, PREFILTER_STATE_ALL, PREFILTER_STATE_SOME = 0, 1, 2
+PREFILTER_PART_FIELDS, PREFILTER_PART_RESOURCES = 1, 2
+
+
+class JsonColumnC(C.Structure):
+    """nidx_gpu_json_column_t"""
+    _fields_ = [("path", C.c_void_p), ("path_len", C.c_uint32), ("type", C.c_int32), ("docs", C.c_void_p), ("values", C.c_void_p),
+                ("n_values", C.c_uint64), ("dict_bytes", C.c_void_p), ("dict_offsets", C.c_void_p), ("n_dict", C.c_uint32)]
+
+
+class JsonSegmentC(C.Structure):
+    """nidx_gpu_json_segment_t"""
+    _fields_ = [("n_docs", C.c_uint32), ("alive_bitset", C.c_void_p), ("resource_ids", C.c_void_p), ("columns", C.c_void_p),
+                ("n_columns", C.c_uint32)]
+
+
+class JsonOpenStatsC(C.Structure):
+    """nidx_gpu_json_open_stats_t"""
+    _fields_ = [("documents", C.c_uint64), ("resources", C.c_uint64), ("columns", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class JsonLeafC(C.Structure):
+    """nidx_gpu_json_leaf_t"""
+    _fields_ = [("path", C.c_void_p), ("path_len", C.c_uint32), ("type", C.c_int32), ("has_lo", C.c_int32), ("has_hi", C.c_int32),
+                ("lo", C.c_uint64), ("hi", C.c_uint64), ("str", C.c_void_p), ("str_len", C.c_uint32)]
+
+
+class JsonPrefilterC(C.Structure):
+    """nidx_gpu_json_prefilter_t"""
+    _fields_ = [("program", FilterProgramC), ("leaves", C.c_void_p), ("n_leaves", C.c_uint32)]
+
+
+class JsonPrefilterBatchStatsC(C.Structure):
+    """nidx_gpu_json_prefilter_batch_stats_t"""
+    _fields_ = [("distinct_programs", C.c_uint32), ("operand_rows", C.c_uint32), ("passes", C.c_uint32), ("fallback_requests", C.c_uint32),
+                ("launches", C.c_uint32), ("synchronisations", C.c_uint32)]
+
+
+class JsonRowsInfoC(C.Structure):
+    """nidx_gpu_json_rows_info_t"""
+    _fields_ = [("requests", C.c_uint32), ("rows", C.c_uint32), ("bytes", C.c_uint64), ("resources", C.c_uint64), ("row_words", C.c_uint64)]
+
+
+class JsonResourceLinkStatsC(C.Structure):
+    """nidx_gpu_json_resource_link_stats_t"""
+    _fields_ = [("linked_documents", C.c_uint64), ("bytes", C.c_uint64), ("text_generation", C.c_uint64), ("resources", C.c_uint64)]
+
+
+class PrefilterCombineRequestC(C.Structure):
+    """nidx_gpu_prefilter_combine_request_t"""
+    _fields_ = [("text_request", C.c_uint32), ("json_request", C.c_uint32), ("op", C.c_int32)]
+
+
+class PrefilterCombineStatsC(C.Structure):
+    """nidx_gpu_prefilter_combine_stats_t"""
+    _fields_ = [("field_rows", C.c_uint32), ("resource_rows", C.c_uint32), ("launches", C.c_uint32), ("synchronisations", C.c_uint32),
+                ("none", C.c_uint32), ("all", C.c_uint32), ("some", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Bm25HitTermsStatsC(C.Structure):
@@ -406,6 +469,22 @@ SIGNATURES = {
                                                                  C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                  C.POINTER(PrefilterSearchStatsC)]),
+    "nidx_gpu_json_open": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(JsonOpenStatsC)]),
+    "nidx_gpu_json_close": (None, [C.c_void_p]),
+    "nidx_gpu_json_resources_read": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_json_prefilter_batch_resident": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                           C.POINTER(JsonPrefilterBatchStatsC), C.POINTER(C.c_void_p)]),
+    "nidx_gpu_json_rows_free": (None, [C.c_void_p]),
+    "nidx_gpu_json_rows_info": (C.c_int32, [C.c_void_p, C.POINTER(JsonRowsInfoC)]),
+    "nidx_gpu_json_rows_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_json_resource_link_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
+                                                       C.POINTER(JsonResourceLinkStatsC)]),
+    "nidx_gpu_json_resource_link_free": (None, [C.c_void_p]),
+    "nidx_gpu_json_resource_link_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_prefilter_rows_combine": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
+                                                    C.POINTER(PrefilterCombineStatsC)]),
+    "nidx_gpu_prefilter_rows_state": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nidx_gpu_prefilter_rows_read_resources": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),

@@ -2661,6 +2661,8 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
                             (unsigned long long)r->generation, (unsigned long long)l->text_generation);
             if (q >= r->row_of_request.size())
                 return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: request %u of %zu", j, q, r->row_of_request.size());
+            if (r->has_resources(q))   // (projecting resource rows needs a link to the paragraph index's uuid terms: DESIGN.md §8 item 5)
+                return fail(NIDX_ERR_UNSUPPORTED, "term set %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", j, q);
             const uint32_t row = r->row_of_request[q];
             if (row == kPrefilterRowNone) continue;   // the empty set: the term set as it stands
             if (row == kPrefilterRowAll) { any_all = true; rs.row_of_set[j] = 0xfffffffeu; continue; }   // (placed below)

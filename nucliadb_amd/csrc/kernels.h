@@ -721,6 +721,29 @@ hipError_t launch_prefilter_emit(const uint64_t *results, size_t row_stride, uin
                                  const uint32_t *listed_prog, uint32_t n_listed, const unsigned long long *listed_begin, uint32_t begin_stride,
                                  const unsigned long long *listed_end, const uint32_t *seg_base, uint32_t n_real, uint32_t segment, uint64_t *out,
                                  hipStream_t s);
+// ---- the JSON prefilter and PrefilterResult::combine (json_prefilter.hip) -----------------------------------------------------------
+//   scan:          one (segment, column) against a chunk of at most NIDX_JSON_MAX_INTERVALS intervals [n][3] = (lo, hi, row): the bit of
+//                  docs[i] is ORed into row `row` (rows = the segment's first word of operand row 0) for every interval holding values[i]
+//   resource rows: result row r's set documents -> the bits of their resources in resource row r (zeroed by the caller)
+//   count:         counts[r] = set bits of resource row r
+//   link:          out[i] = the ordinal of uuid pair ids[i] in the ascending table, UINT32_MAX when it is not there
+//   combine rows:  item = (text row, JSON resource row or nullptr, op, output row); op 0: text & in-J, 1: text & ~in-J, 2: text;
+//                  counts[item] += the output's set bits (zeroed by the caller)
+#define JSON_SCAN_TILE 1024   // (docs, values) pairs of a column per workgroup
+struct JsonCombineItem {
+    const uint64_t *text_row;
+    const uint64_t *json_row;
+    uint64_t *out_row;
+    uint32_t op, reserved;
+};
+hipError_t launch_json_scan(const uint32_t *docs, const uint64_t *values, uint64_t n_values, const uint64_t *intervals, uint32_t n_intervals,
+                            uint64_t *rows, size_t row_stride, hipStream_t s);
+hipError_t launch_json_resource_rows(const uint64_t *results, size_t row_stride, uint32_t n_rows, uint32_t n_words, const uint32_t *doc_resource,
+                                     uint32_t n_resources, uint64_t *resource_rows, size_t resource_words, hipStream_t s);
+hipError_t launch_json_count_rows(const uint64_t *rows, size_t row_words, uint32_t n_rows, unsigned long long *counts, hipStream_t s);
+hipError_t launch_json_link(const uint64_t *table, uint32_t n_resources, const uint64_t *ids, uint32_t n, uint32_t *out, hipStream_t s);
+hipError_t launch_json_combine_rows(const JsonCombineItem *items, uint32_t n_items, uint32_t n_words, const uint32_t *doc_resource,
+                                    unsigned long long *counts, hipStream_t s);
 // ---- nidx_gpu_bm25_hit_terms_batch (bm25_hit_terms.hip): the accepted terms of the fuzzy query that occur in each hit ---------------
 // Query q owns the hits [q_hit_off[q], q_hit_off[q + 1]) and the set members [q_mem_off[q], q_mem_off[q + 1]) (its sets laid end to end).
 // ent_doc = the local doc ids of its hits, ascending per query, ent_hit[i] = which hit of the query entry i is.  A resident posting

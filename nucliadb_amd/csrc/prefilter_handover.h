@@ -1,9 +1,11 @@
 // prefilter_handover.h — what the three pieces of the prefilter hand-over share: the resident rows of a prefilter batch
 // (bm25_index.cpp), the document -> (vector segment, list) link (prefilter_link.cpp) and the search that projects the rows through the
 // link (vector_index.cpp, vector_prefilter.hip) — and of the paragraph half: the document -> term link (prefilter_link.cpp) and the
-// BM25 search whose term sets may name a row (bm25_index.cpp, bm25_prefilter_project.hip).
+// BM25 search whose term sets may name a row (bm25_index.cpp, bm25_prefilter_project.hip).  json_index.cpp joins the rows with the JSON
+// prefilter's resource rows into a combined handle (PrefilterResult::combine).
 #pragma once
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "host_common.h"
@@ -45,6 +47,14 @@ struct PrefilterRows {
     std::vector<const uint64_t *> row_ptr;      // [rows] in HBM, layout.words() words each
     std::vector<uint32_t> row_of_request;       // a row, kPrefilterRowAll or kPrefilterRowNone
     uint64_t bytes = 0;
+    // the resource-granular part of a combined handle (json_index.cpp); empty for the rows of a prefilter batch
+    std::shared_ptr<const void> res_owner;      // keeps the JSON rows' memory
+    std::vector<const uint64_t *> res_row_ptr;  // [resource rows] in HBM, res_words words each
+    std::vector<uint32_t> res_row_of_request;   // empty, or per request a resource row or kPrefilterRowNone
+    uint64_t res_words = 0;
+    bool has_resources(uint32_t request) const {
+        return request < res_row_of_request.size() && res_row_of_request[request] != kPrefilterRowNone;
+    }
 };
 
 // nidx_gpu_prefilter_link_t: CSR over the bit positions of a row

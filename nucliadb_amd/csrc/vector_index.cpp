@@ -1684,6 +1684,8 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
             const uint32_t r = pf->prefilter_of_filter ? pf->prefilter_of_filter[f] : UINT32_MAX;
             if (r != UINT32_MAX && (!pf->rows || r >= pf->rows->row_of_request.size()))
                 return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u of %zu", f, r, pf->rows ? pf->rows->row_of_request.size() : (size_t)0);
+            if (r != UINT32_MAX && pf->rows->has_resources(r))   // (projecting resource rows needs a resource-to-lists link: DESIGN.md §8 item 5)
+                return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
             for (size_t s = 0; s < S; s++) {
                 uint32_t n_operands = 0, n_pf = 0;
                 bool dp = false;
@@ -2098,7 +2100,7 @@ int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
 int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
-           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER;
+           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
