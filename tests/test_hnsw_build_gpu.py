@@ -1,6 +1,7 @@
 """Device HNSW build (HnswBuilder, hnsw/build.rs): the graph is not unique in the reference either
 (rayon inserts, segment.rs:908), so parity is structural invariants + recall, against the oracle's
-sequential build and against the reference's own recall floor (segment.rs:841-912)."""
+sequential build and against the reference's own recall floor (segment.rs:841-912).  What the device's batch-synchronous build
+computes exactly, record by record, is held by test_hnsw_build_exact_gpu.py against the model of _hnsw_build_model.py."""
 import numpy as np
 import pytest
 
@@ -89,6 +90,16 @@ def test_levels_match_reference_rng(orc):
     assert (deg0 > 0).all(), "every node must be linked on layer 0"
     assert deg0.mean() > 20
     assert len(edges) > 0 and np.isfinite(edges).all()
+    # hnsw.edges: every stored weight is the similarity of its two rows, bit for bit (later prunes and graph reuse in merges read them)
+    g = orc.Hnsw.deserialize_v2(np.frombuffer(graph, np.uint8), edges)
+    sim_fn, row0, stride, checked = orc.lib().orc_similarity, x.ctypes.data, d * 4, 0
+    for layer in range(int(levels.max()) + 1):
+        for node in np.flatnonzero(levels >= layer):
+            e, w = g.edges(layer, int(node))
+            want = np.array([sim_fn(row0 + int(node) * stride, row0 + int(t) * stride, d, orc.SIM_DOT, orc.ORDER_WAVE64) for t in e], np.float32)
+            assert np.array_equal(w.view(np.uint32), want.view(np.uint32)), (layer, node)
+            checked += len(e)
+    assert checked == len(edges)
 
 
 def test_recall_clustered_data_reference_floor(orc):
