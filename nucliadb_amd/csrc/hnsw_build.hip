@@ -54,7 +54,7 @@ struct BuildArgs {
 #define REQ_STRIDE NIDX_BUILD_REQ_STRIDE
 
 template <int NJ>
-__global__ __launch_bounds__(256, 4) void insert_search_kernel(BuildArgs a) {   // (<= 128 VGPRs: four construction searches per CU, like the query kernel; it compiled to 132 = three)
+__global__ __launch_bounds__(256, 4) void insert_search_kernel(BuildArgs a) {   // (<= 128 VGPRs: four construction searches per CU, like the query kernel's combined form; it compiles to 128 with 48 B of scratch per lane: four waves per SIMD)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     SearchShared &sh = *reinterpret_cast<SearchShared *>(smem);
     uint32_t *vis = reinterpret_cast<uint32_t *>(smem + sizeof(SearchShared));

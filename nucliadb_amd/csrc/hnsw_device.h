@@ -7,7 +7,8 @@
 // then evaluate the similarity of the unvisited neighbours, each row as NJ coalesced 1 KiB loads
 // (16 B per lane), four rows in flight per wave, reduced with the transposed butterfly (WAVE64
 // order — bit-identical to the oracle).  The controller finally replays the reference's
-// sequential admission rule over the scores in edge order.
+// sequential admission rule over the scores in edge order.  In the query kernel's launches with two or
+// more waves the controller scores no row and the other waves run nothing else ("role split" below).
 //
 // Restates HnswSearcher::layer_search / closest_up_nodes / search
 // (nidx_vector/src/hnsw/search.rs:188-383).  Where the reference leaves tie order to BinaryHeap
@@ -337,7 +338,35 @@ __device__ inline void eval_neighbours_dynamic(const SegDev &seg, const QueryReg
     }
 }
 
-// ---- edge record of `node` at `layer`: lane i gets word i (wave 0) ----------------------------
+// ---- role split: launches with two or more waves per query (hnsw_search.hip) ------------------------------------------------
+// The controller wave and the other waves (workers) run disjoint code after the query load, so the kernel's register allocation is
+// max(controller, worker) instead of their sum: the controller holds the result list, the masks and the edge records and never a
+// row; a worker holds the query and EVR rows and nothing of the walk.  The workers sit in ONE loop (split_worker_loop): barrier,
+// read the command word sh.ctrl[0], act, barrier.  The controller drives it in turns: split_post() writes the command and passes
+// the first barrier, split_close() passes the second; what the controller does in between overlaps the workers' rows.  A barrier
+// the controller passes anywhere else would have no counterpart, so there is none: every wait is one of these turns.
+//
+//   command                  controller, between post and close        where
+//   CLEAR                    clears its share of the visited table     start of a layer search; closest_up_nodes' walk
+//   EVAL nb[p], n rows       nothing                                   a chunk of <= 64 entry points; the first expansion;
+//                                                                      the `redo` turn (speculation missed);
+//                                                                      a 64-row turn of closest_up_nodes (deferred list or not)
+//   EVAL nb[p ^ 1], n rows   admission of nb[p], the real pop          every expansion of the pipelined loop (n = 0: none speculated)
+//   EXIT                     nothing                                   after the walk (or the dump of the spill path)
+//
+// The verdict of the hits-from-the-set scan needs no turn: only the controller acts on it.  Rows are claimed EVR at a time from
+// sh.ctrl[3], which split_post() resets; which worker scores a row does not change a bit of it.
+#define NIDX_CMD_EVAL 0
+#define NIDX_CMD_CLEAR 1
+#define NIDX_CMD_EXIT 2
+__device__ inline void split_post(SearchShared &sh, int op, int p, int n, int lane) {
+    if (lane == 0) {
+        sh.ctrl[0] = op | (p << 2) | (n << 3);
+        sh.ctrl[3] = 0;
+    }
+    lds_barrier();
+}
+__device__ inline void split_close() { lds_barrier(); }
 __device__ inline uint32_t load_edge_word(const GraphDev &g, uint32_t node, int layer, int lane, uint32_t &deg) {
     uint32_t w = 0;
     if (layer == 0) {
@@ -350,8 +379,22 @@ __device__ inline uint32_t load_edge_word(const GraphDev &g, uint32_t node, int 
     return w;
 }
 
+template <int NJ, int EVR>
+__device__ inline void split_worker_loop(const SegDev &seg, const QueryRegs<NJ> &q, SearchShared &sh, uint32_t *vis, uint32_t vis_cap, bool cosine) {
+    for (;;) {
+        lds_barrier();
+        const int cmd = __builtin_amdgcn_readfirstlane(sh.ctrl[0]);
+        const int op = cmd & 3;
+        if (op == NIDX_CMD_EVAL) eval_neighbours_dynamic<NJ, EVR>(seg, q, sh.nb[(cmd >> 2) & 1], cmd >> 3, cosine, &sh.ctrl[3]);
+        else if (op == NIDX_CMD_CLEAR) vis_clear(vis, vis_cap);
+        lds_barrier();
+        if (op == NIDX_CMD_EXIT) return;
+    }
+}
+
 // ---- HnswSearcher::layer_search (search.rs:242-304) ------------------------------------------
-// Result: `res` (wave 0), best first.  All threads call.  Entry points, by `ep_mode`:
+// Result: `res` (wave 0), best first.  All threads call; SPLIT: the controller wave alone, the others are in split_worker_loop.
+// Entry points, by `ep_mode`:
 //   NIDX_EPS_BARE     sh.eps[0..sh.ctrl[2]): bare addresses, scored here and inserted one by one (the build kernels);
 //   NIDX_EPS_PARKED   the same, and the entry points' edge records are fetched in one go (below);
 //   NIDX_EPS_CARRIED  `res` as it stands (sh.ctrl[2] = its length): the result set of the layer above, whose scores are the ones
@@ -366,20 +409,26 @@ __device__ inline uint32_t load_edge_word(const GraphDev &g, uint32_t node, int 
 #define NIDX_EPS_BARE 0
 #define NIDX_EPS_PARKED 1
 #define NIDX_EPS_CARRIED 2
-template <int NJ, int EFL, int EVR>
+template <int NJ, int EFL, int EVR, bool SPLIT = false>
 __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, int layer, int k,
                                           const QueryRegs<NJ> &q, SearchShared &sh, uint32_t *vis, uint32_t vis_log2,
                                           WaveTopK<EFL> &res, SearchCounters &st, int ep_mode = NIDX_EPS_BARE) {
     const int lane = threadIdx.x & 63;
-    const bool ctl = (nidx_tid() >> 6) == 0;
+    const bool ctl = SPLIT ? true : (nidx_tid() >> 6) == 0;
     const bool cosine = seg.similarity == 1;
     const uint32_t vis_cap = 1u << vis_log2;
     const bool carried = ep_mode == NIDX_EPS_CARRIED;
     int pool_len = 0;
     uint32_t vis_count = 0;
 
-    vis_clear(vis, vis_cap);
-    __syncthreads();
+    if constexpr (SPLIT) {
+        split_post(sh, NIDX_CMD_CLEAR, 0, 0, lane);
+        vis_clear(vis, vis_cap);
+        split_close();
+    } else {
+        vis_clear(vis, vis_cap);
+        __syncthreads();
+    }
     int n_new = sh.ctrl[2];
     // more entry points than k (a descent kept wider than this layer's k): every entry point is admitted and each later push
     // pops ONE result (search.rs:256-261,289-292), so the set keeps the size the entry points gave it
@@ -429,9 +478,14 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
             vis_insert(vis, vis_log2, ep);
             sh.nb[0].addr[lane] = ep;
         }
-        __syncthreads();
-        eval_neighbours<NJ, EVR>(seg, q, sh.nb[0], chunk, cosine);
-        __syncthreads();
+        if constexpr (SPLIT) {
+            split_post(sh, NIDX_CMD_EVAL, 0, chunk, lane);
+            split_close();
+        } else {
+            __syncthreads();
+            eval_neighbours<NJ, EVR>(seg, q, sh.nb[0], chunk, cosine);
+            __syncthreads();
+        }
         if (ctl) {
             float s = lane < chunk ? score_from_sums(sh.nb[0].ab[lane], sh.nb[0].xx[lane], q.qq, q.sqrt_qq, cosine) : 0.f;
             uint32_t addr = sh.nb[0].addr[lane];
@@ -508,34 +562,48 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
     };
     int p = 0;
     uint64_t cur = NIDX_EMPTY_KEY;
+    // SPLIT: what the combined form publishes in sh.ctrl[0], [4], [5], [6..7] stays in the controller's registers
+    int cont = 0, n_cur_reg = 0;
     if (ctl) {
         const uint64_t t_a = clock64();
-        int cont = 0, n0 = 0;
+        int n0 = 0;
         cur = cand.pop(res);
         if (cur != NIDX_EMPTY_KEY && !(rank_key_score(cur) < res.worst_score())) {
             cont = 1;
             n0 = prepare(cur, sh.nb[0]);
         }
-        if (lane == 0) {
+        n_cur_reg = n0;
+        if (!SPLIT && lane == 0) {
             sh.ctrl[0] = cont;
             sh.ctrl[6] = n0;
             sh.ctrl[3] = 0;
         }
         st.cyc_ctl += clock64() - t_a;
     }
-    lds_barrier();
-    if (sh.ctrl[0]) {
-        eval_neighbours_dynamic<NJ, EVR>(seg, q, sh.nb[0], sh.ctrl[6], cosine, &sh.ctrl[3]);
+    if constexpr (SPLIT) {
+        if (cont) {
+            split_post(sh, NIDX_CMD_EVAL, 0, n_cur_reg, lane);
+            split_close();
+        }
+    } else {
         lds_barrier();
+        cont = sh.ctrl[0];
+        if (cont) {
+            eval_neighbours_dynamic<NJ, EVR>(seg, q, sh.nb[0], sh.ctrl[6], cosine, &sh.ctrl[3]);
+            lds_barrier();
+        }
+    }
+    if (cont) {
         for (;;) {
             NbBuf &nb_cur = sh.nb[p], &nb_next = sh.nb[p ^ 1];
-            const int n_cur = sh.ctrl[6 + p];
+            const int n_cur = SPLIT ? n_cur_reg : sh.ctrl[6 + p];
             // ---- wave 0: commit the expansion whose sums are in nb_cur, pick the next candidate, list its neighbours ----
             float s = 0.f;
             uint32_t addr = 0;
             unsigned long long todo = 0;
             uint64_t nxt = NIDX_EMPTY_KEY;
             bool overflow = false;
+            int n_next_reg = 0, redo_reg = 0;
             const uint64_t t_a = clock64();
             if (ctl) {
                 const bool mine = lane < n_cur;
@@ -586,17 +654,19 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
                         }
                     }
                 }
-                if (lane == 0) {
+                n_next_reg = n_next;
+                if (!SPLIT && lane == 0) {
                     sh.ctrl[5] = nxt != NIDX_EMPTY_KEY;
                     sh.ctrl[6 + (p ^ 1)] = n_next;
                     sh.ctrl[3] = 0;
                 }
             }
-            lds_barrier();
+            if constexpr (SPLIT) split_post(sh, NIDX_CMD_EVAL, p ^ 1, n_next_reg, lane);   // 0 rows when nothing is speculated
+            else lds_barrier();
             const uint64_t t_b = clock64();
             st.cyc_ctl += t_b - t_a;
-            const bool has_next = sh.ctrl[5] != 0;
-            const int n_next = sh.ctrl[6 + (p ^ 1)];
+            const bool has_next = SPLIT ? false : sh.ctrl[5] != 0;   // SPLIT: the controller scores no row
+            const int n_next = SPLIT ? n_next_reg : sh.ctrl[6 + (p ^ 1)];
             if (!ctl && has_next) eval_neighbours_dynamic<NJ, EVR>(seg, q, nb_next, n_next, cosine, &sh.ctrl[3]);
             if (ctl) {
                 // `if similarity > ws || len < k` replayed in edge order (search.rs:287-295).  Once the
@@ -628,7 +698,8 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
                         }
                     }
                 }
-                int cont = 0, redo = 0;
+                int redo = 0;
+                cont = 0;
                 if (overflow) {
                     st.flags |= NIDX_FLAG_VISITED_OVERFLOW;
                 } else {
@@ -637,7 +708,8 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
                     cont = cur != NIDX_EMPTY_KEY && !(rank_key_score(cur) < res.worst_score());
                     redo = cont && cur != nxt;
                 }
-                if (lane == 0) {
+                redo_reg = redo;
+                if (!SPLIT && lane == 0) {
                     sh.ctrl[0] = cont;
                     sh.ctrl[4] = redo;
                 }
@@ -646,20 +718,33 @@ __device__ inline void layer_search_block(const SegDev &seg, const GraphDev &g, 
                 if (has_next) eval_neighbours_dynamic<NJ, EVR>(seg, q, nb_next, n_next, cosine, &sh.ctrl[3]);
                 st.cyc_eval += clock64() - t_c;
             }
-            lds_barrier();
-            if (!sh.ctrl[0]) break;
-            if (sh.ctrl[4]) {
+            if constexpr (SPLIT) {
+                split_close();
+            } else {
+                lds_barrier();
+                cont = sh.ctrl[0];
+                redo_reg = sh.ctrl[4];
+            }
+            if (!cont) break;
+            n_cur_reg = n_next;
+            if (redo_reg) {
                 // the pop did not return the speculated candidate: expand the real one (nothing of the other was committed)
                 if (ctl) {
                     const int n1 = prepare(cur, nb_next);
-                    if (lane == 0) {
+                    n_cur_reg = n1;
+                    if (!SPLIT && lane == 0) {
                         sh.ctrl[6 + (p ^ 1)] = n1;
                         sh.ctrl[3] = 0;
                     }
                 }
-                lds_barrier();
-                eval_neighbours_dynamic<NJ, EVR>(seg, q, nb_next, sh.ctrl[6 + (p ^ 1)], cosine, &sh.ctrl[3]);
-                lds_barrier();
+                if constexpr (SPLIT) {
+                    split_post(sh, NIDX_CMD_EVAL, p ^ 1, n_cur_reg, lane);
+                    split_close();
+                } else {
+                    lds_barrier();
+                    eval_neighbours_dynamic<NJ, EVR>(seg, q, nb_next, sh.ctrl[6 + (p ^ 1)], cosine, &sh.ctrl[3]);
+                    lds_barrier();
+                }
             }
             p ^= 1;
         }

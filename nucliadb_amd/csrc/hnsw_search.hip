@@ -32,7 +32,9 @@ __device__ inline bool rows_equal(const SegDev &seg, uint32_t a, uint32_t b, int
 
 // One query's whole search in one workgroup.  Shared by the two launch forms below: one segment per launch (arguments in the
 // kernel-argument segment) and every HNSW segment of an index in ONE launch (arguments of block b's segment read from a table in HBM).
-template <int NJ, int EVR, int EFL>
+// SPLIT (launches with two or more waves per query): the controller wave runs everything below alone and the other waves leave for
+// split_worker_loop right after the query load; hnsw_device.h has the protocol.  One-wave launches keep the combined form.
+template <int NJ, int EVR, int EFL, bool SPLIT>
 __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const uint32_t qi, unsigned char *smem) {
     SearchShared &sh = *reinterpret_cast<SearchShared *>(smem);
     uint32_t *vis = reinterpret_cast<uint32_t *>(smem + sizeof(SearchShared));
@@ -41,12 +43,18 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     __shared__ uint32_t res_para[64 * EFL];
 
     const int lane = threadIdx.x & 63;
-    const bool ctl = (nidx_tid() >> 6) == 0;
     const bool cosine = a.seg.similarity == 1;
     const int k = (int)a.k;
 
     QueryRegs<NJ> q;
     load_query<NJ>(q, a.queries + (size_t)qi * a.seg.dp, a.seg.dp, lane, cosine);
+    if constexpr (SPLIT) {
+        if ((nidx_tid() >> 6) != 0) {
+            split_worker_loop<NJ, EVR>(a.seg, q, sh, vis, 1u << a.vis_log2, cosine);
+            return;
+        }
+    }
+    const bool ctl = SPLIT ? true : (nidx_tid() >> 6) == 0;
     // the filter closest_up_nodes tests: the launch's, or this query's own row (per-query filters)
     const uint64_t *filter = a.filter;
     if (a.filter_row) {
@@ -64,7 +72,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         sh.eps[0] = a.g.ep_node;
         sh.ctrl[2] = 1;
     }
-    __syncthreads();
+    if constexpr (!SPLIT) __syncthreads();
     const bool entry_mode = a.entry_vec != nullptr;
     const int efu = a.ef_upper ? (int)a.ef_upper : 1;
     // The top layer starts from the graph's entry point; every layer below starts from the result set of the layer above, which
@@ -73,13 +81,13 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     // the other waves may still be reading (ctrl[0], ctrl[4]).
     const int top = entry_mode ? 0 : (int)a.g.ep_layer;
     for (int layer = top; layer >= 1; layer--) {
-        layer_search_block<NJ, EFL, EVR>(a.seg, a.g, layer, efu, q, sh, vis, a.vis_log2, res, st, layer == top ? NIDX_EPS_PARKED : NIDX_EPS_CARRIED);
+        layer_search_block<NJ, EFL, EVR, SPLIT>(a.seg, a.g, layer, efu, q, sh, vis, a.vis_log2, res, st, layer == top ? NIDX_EPS_PARKED : NIDX_EPS_CARRIED);
         if (ctl && lane == 0) sh.ctrl[2] = res.len;
     }
     // ---- layer 0 with ef = max(k, EF_SEARCH) (search.rs:333-349) ----
     const int efs = a.ef_search ? (int)a.ef_search : NIDX_EF_SEARCH;
     const int ef = k > efs ? k : efs;
-    if (!entry_mode) layer_search_block<NJ, EFL, EVR>(a.seg, a.g, 0, ef, q, sh, vis, a.vis_log2, res, st, top >= 1 ? NIDX_EPS_CARRIED : NIDX_EPS_PARKED);
+    if (!entry_mode) layer_search_block<NJ, EFL, EVR, SPLIT>(a.seg, a.g, 0, ef, q, sh, vis, a.vis_log2, res, st, top >= 1 ? NIDX_EPS_CARRIED : NIDX_EPS_PARKED);
     if (a.dump_vec) {
         // spill path: the walk below runs in hnsw_closest_spill_kernel, from these candidates
         if (ctl) {
@@ -98,6 +106,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
                 if (st.flags && a.flag_word) atomicOr(a.flag_word, st.flags);
                 if (a.flag_rows) a.flag_rows[qi] = st.flags;
             }
+        }
+        if constexpr (SPLIT) {
+            split_post(sh, NIDX_CMD_EXIT, 0, 0, lane);
+            split_close();
         }
         return;
     }
@@ -129,8 +141,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     // waves wait at one barrier for the verdict in sh.ctrl[1]) and walks only if the scan fails, or if the walk it replaces could
     // have overflowed the visited table (<= NIDX_L0_STRIDE - 1 edges per record: `lane <= deg`), whose flag and re-run then decide.  With
     // counters every launch walks, so they stay the reference's.  k >= ef never succeeds: the k-th member is the worst one.
+    // SPLIT: the verdict stays with the controller, no barrier.
     const uint32_t vis_cap = 1u << a.vis_log2;
     int n_res = 0;
+    bool scan_done = false;
     if (a.stats == nullptr && !entry_mode) {
         if (ctl) {
             bool done = false;
@@ -197,14 +211,21 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
                 }
             }
             if (!done) n_res = 0;
-            if (lane == 0) sh.ctrl[1] = done;
+            scan_done = done;
+            if (!SPLIT && lane == 0) sh.ctrl[1] = done;
         }
-        __syncthreads();
+        if constexpr (!SPLIT) __syncthreads();
     }
-    const bool from_set = a.stats == nullptr && !entry_mode && sh.ctrl[1] != 0;
+    const bool from_set = a.stats == nullptr && !entry_mode && (SPLIT ? scan_done : sh.ctrl[1] != 0);
     if (!from_set) {
-        vis_clear(vis, vis_cap);
-        __syncthreads();
+        if constexpr (SPLIT) {
+            split_post(sh, NIDX_CMD_CLEAR, 0, 0, lane);
+            vis_clear(vis, vis_cap);
+            split_close();
+        } else {
+            vis_clear(vis, vis_cap);
+            __syncthreads();
+        }
     }
     int pool_len = 0;
     uint32_t vis_count = 0;
@@ -256,9 +277,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         }
     }
     while (!from_set) {
+        // cont: the walk goes on, once the n_new addresses in sh.eps[from ..) are scored and pushed, 64 per turn of this loop
+        int cont = 1, n_new = 0;
         if (ctl) {
-            // cont: the walk goes on, once the n_new addresses in sh.eps[from ..) are scored and pushed, 64 per turn of this loop
-            int cont = 1, n_new = 0, from = 0;
+            int from = 0;
             const int waiting = sh.ctrl[10];
             if (waiting > 0) {
                 n_new = waiting;
@@ -356,17 +378,28 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
             }
             sh.nb[0].addr[lane] = sh.eps[from + lane];
             if (lane == 0) {
-                sh.ctrl[0] = cont;
-                sh.ctrl[1] = n_new > 64 ? 64 : n_new;
+                if (!SPLIT) {
+                    sh.ctrl[0] = cont;
+                    sh.ctrl[1] = n_new > 64 ? 64 : n_new;
+                }
                 sh.ctrl[10] = n_new > 64 ? n_new - 64 : 0;
                 sh.ctrl[11] = from + 64;
             }
+            n_new = n_new > 64 ? 64 : n_new;
         }
-        __syncthreads();
-        if (!sh.ctrl[0]) break;
-        int n_new = sh.ctrl[1];
-        eval_neighbours<NJ, EVR>(a.seg, q, sh.nb[0], n_new, cosine);
-        __syncthreads();
+        if constexpr (SPLIT) {
+            if (!cont) break;
+            if (n_new > 0) {   // nothing to score: no turn
+                split_post(sh, NIDX_CMD_EVAL, 0, n_new, lane);
+                split_close();
+            }
+        } else {
+            __syncthreads();
+            if (!sh.ctrl[0]) break;
+            n_new = sh.ctrl[1];
+            eval_neighbours<NJ, EVR>(a.seg, q, sh.nb[0], n_new, cosine);
+            __syncthreads();
+        }
         if (ctl && n_new > 0) {
             float s = lane < n_new ? score_from_sums(sh.nb[0].ab[lane], sh.nb[0].xx[lane], q.qq, q.sqrt_qq, cosine) : 0.f;
             uint32_t addr = sh.nb[0].addr[lane];
@@ -399,6 +432,10 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
         }
     }
 
+    if constexpr (SPLIT) {
+        split_post(sh, NIDX_CMD_EXIT, 0, 0, lane);
+        split_close();
+    }
     // ---- filtered_result.sort_by(|a, b| b.1.total_cmp(&a.1)) — stable (search.rs:381) ----
     if (ctl) {
         st.visited = st.visited > vis_count ? st.visited : vis_count;
@@ -442,41 +479,47 @@ __device__ __forceinline__ void hnsw_search_body(const HnswSearchArgs &a, const 
     }
 }
 
-template <int NJ, int EVR, int MINW, int EFL>
+template <int NJ, int EVR, int MINW, int EFL, bool SPLIT>
 __global__ __launch_bounds__(256, MINW) void hnsw_search_kernel(HnswSearchArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    hnsw_search_body<NJ, EVR, EFL>(a, blockIdx.x, smem);
+    hnsw_search_body<NJ, EVR, EFL, SPLIT>(a, blockIdx.x, smem);
 }
 
 // Searcher::_search's loop over the segments (nidx_vector/src/searcher.rs:270-287) as ONE grid: block b walks query b % nq of
 // segment b / nq.  The reference's indexes ARE many segments (merges stop at 200 k records, nidx/src/settings.rs:258-278: 10 M vectors
 // = 50 segments); a launch per segment leaves the device idle behind the longest walk of each of them 50 times per batch.  Blocks
 // of one segment are neighbours, so its upper layers and hub rows stay in the L2 of the XCDs that walk it.
-template <int NJ, int EVR, int MINW, int EFL>
+template <int NJ, int EVR, int MINW, int EFL, bool SPLIT>
 __global__ __launch_bounds__(256, MINW) void hnsw_search_segments_kernel(const HnswSearchArgs *__restrict__ table, uint32_t nq) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const uint32_t s = blockIdx.x / nq;
     const HnswSearchArgs a = table[s];   // uniform address, read-only: scalar loads
-    hnsw_search_body<NJ, EVR, EFL>(a, blockIdx.x - s * nq, smem);
+    hnsw_search_body<NJ, EVR, EFL, SPLIT>(a, blockIdx.x - s * nq, smem);
 }
 
-template <int NJ, int EVR, int MINW, int EFL>
-static hipError_t launch_v(const HnswSearchArgs &a, int waves, hipStream_t s) {
+template <int NJ, int EVR, int MINW, int EFL, bool SPLIT>
+static hipError_t launch_form(const HnswSearchArgs &a, int waves, hipStream_t s) {
     if (a.seg_table) {
         size_t smem = sizeof(SearchShared) + ((size_t)4 << a.vis_log2);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_segments_kernel<NJ, EVR, MINW, EFL>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_segments_kernel<NJ, EVR, MINW, EFL, SPLIT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((hnsw_search_segments_kernel<NJ, EVR, MINW, EFL>), dim3(a.n_queries * a.n_table), dim3(64 * waves), smem, s,
+        hipLaunchKernelGGL((hnsw_search_segments_kernel<NJ, EVR, MINW, EFL, SPLIT>), dim3(a.n_queries * a.n_table), dim3(64 * waves), smem, s,
                            a.seg_table, a.n_queries);
         return hipGetLastError();
     }
     size_t smem = sizeof(SearchShared) + ((size_t)4 << a.vis_log2);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_kernel<NJ, EVR, MINW, EFL>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_kernel<NJ, EVR, MINW, EFL, SPLIT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((hnsw_search_kernel<NJ, EVR, MINW, EFL>), dim3(a.n_queries), dim3(64 * waves), smem, s, a);
+    hipLaunchKernelGGL((hnsw_search_kernel<NJ, EVR, MINW, EFL, SPLIT>), dim3(a.n_queries), dim3(64 * waves), smem, s, a);
     return hipGetLastError();
+}
+
+// two or more waves per query: the role-split form; one wave: the combined one
+template <int NJ, int EVR, int MINW, int EFL>
+static hipError_t launch_v(const HnswSearchArgs &a, int waves, hipStream_t s) {
+    return waves >= 2 ? launch_form<NJ, EVR, MINW, EFL, true>(a, waves, s) : launch_form<NJ, EVR, MINW, EFL, false>(a, waves, s);
 }
 
 static uint32_t layer0_ef(const HnswSearchArgs &a) {
@@ -484,21 +527,32 @@ static uint32_t layer0_ef(const HnswSearchArgs &a) {
     return a.k > efs ? a.k : efs;
 }
 
+// This file is compiled once per part (Makefile: -DNIDX_HNSW_PART=p), so that the row-width classes build side by side: part p =
+// 1..4 holds launch_nj<p> and its kernels, part 0 the wide classes and the entry point.
 template <int NJ>
-static hipError_t launch_nj(const HnswSearchArgs &a, int waves, hipStream_t s) {
+hipError_t launch_nj(const HnswSearchArgs &a, int waves, hipStream_t s) {
     const uint32_t ef = layer0_ef(a);
     // large result pages (ef > 64) are the rare path: one shape each
     if (ef > 256) return launch_v<NJ, 2, 2, 8>(a, waves, s);
     if (ef > 128) return launch_v<NJ, 2, 2, 4>(a, waves, s);
     if (ef > 64) return launch_v<NJ, 2, 2, 2>(a, waves, s);
     // rows in flight per wave / register budget: tuned on MI355X (profiles/r01_tune_hnsw.txt, r02_tune_hnsw.txt).
-    // min_waves 5 / 6: <= 96 / 80 VGPRs, two rows in flight per wave; with vis_log2 <= 12 a CU then holds 5 / 6 walks.
+    // min_waves 5 / 6: <= 96 / 80 VGPRs; with vis_log2 <= 12 a CU then holds 5 / 6 walks.  The crowded shape the index picks by itself
+    // is min_waves 5 with four rows in flight (the role-split form fits them); a pinned min_waves keeps two rows.
     if (a.min_waves >= 6) return launch_v<NJ, 2, 6, 1>(a, waves, s);
-    if (a.min_waves == 5) return launch_v<NJ, 2, 5, 1>(a, waves, s);
+    if (a.min_waves == 5) return a.eval_rows == 4 ? launch_v<NJ, 4, 5, 1>(a, waves, s) : launch_v<NJ, 2, 5, 1>(a, waves, s);
     if (a.eval_rows == 3) return a.min_waves >= 4 ? launch_v<NJ, 3, 4, 1>(a, waves, s) : launch_v<NJ, 3, 2, 1>(a, waves, s);
     if (a.eval_rows == 2) return a.min_waves >= 4 ? launch_v<NJ, 2, 4, 1>(a, waves, s) : launch_v<NJ, 2, 2, 1>(a, waves, s);
     return a.min_waves >= 4 ? launch_v<NJ, 4, 4, 1>(a, waves, s) : launch_v<NJ, 4, 2, 1>(a, waves, s);
 }
+
+#if NIDX_HNSW_PART != 0
+template hipError_t launch_nj<NIDX_HNSW_PART>(const HnswSearchArgs &, int, hipStream_t);
+#else
+extern template hipError_t launch_nj<1>(const HnswSearchArgs &, int, hipStream_t);
+extern template hipError_t launch_nj<2>(const HnswSearchArgs &, int, hipStream_t);
+extern template hipError_t launch_nj<3>(const HnswSearchArgs &, int, hipStream_t);
+extern template hipError_t launch_nj<4>(const HnswSearchArgs &, int, hipStream_t);
 
 template <int NJ>
 static hipError_t launch_wide(const HnswSearchArgs &a, int waves, hipStream_t s) {
@@ -525,5 +579,6 @@ hipError_t launch_hnsw_search(const HnswSearchArgs &a, int waves_per_query, hipS
     if (nj <= 16) return launch_wide<16>(a, waves_per_query, s);   // D <= 4096
     return hipErrorInvalidValue;
 }
+#endif
 
 }  // namespace nidx

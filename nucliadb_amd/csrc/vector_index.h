@@ -141,11 +141,13 @@ struct VectorIndex {
     // launch shape of the HNSW kernels for a batch: a batch that leaves most CUs with at most one workgroup (<= 256 queries) is
     // latency-bound, not occupancy-bound — four rows in flight per wave and the 256-VGPR budget measured 10-11 % faster there
     // (batch 1: 0.48 -> 0.43 ms, batch 64: 0.65 -> 0.57 ms at 1 M x 768); large batches keep 2 rows / 128 VGPRs (16 waves per CU)
-    int rows_for(uint32_t nq) const { return (!shape_pinned && nq <= 256) ? 4 : eval_rows; }
+    // a pinned min_waves of 5 or 6 selects the two-row kernels of those register classes, whatever eval_rows says
+    int rows_for(uint32_t nq) const { return (!shape_pinned && nq <= 256) ? 4 : (shape_pinned && min_waves >= 5) ? 2 : eval_rows; }
     int waves_for(uint32_t nq) const { return (!shape_pinned && nq <= 256) ? 2 : (!shape_pinned && crowded_now()) ? 5 : min_waves; }
     // A large batch submitted while other batches are still on the device (serving.cpp sets this for the submitting thread): together
     // they oversubscribe the CUs' workgroup slots, and what counts then is how many walks a CU holds, not how fast one walk runs —
-    // <= 96 VGPRs and a 2^12 visited table (16 KiB of LDS less) make it FIVE workgroups per CU instead of four.  Measured, 10 M x 768,
+    // the five-walk register class (<= 96 VGPRs) and a 2^12 visited table (16 KiB of LDS less) make it at least FIVE workgroups per CU
+    // instead of four, with four rows in flight per worker wave since the role split (hnsw_device.h).  Measured before it, 10 M x 768,
     // three batches of 1 024 in flight: 4.02 M queries/s against 3.58 M; one launch alone in that shape takes 0.52 ms against 0.36 ms,
     // which is why a batch that finds the device idle keeps the faster walk (scripts/r5_shape.sh).  Same hits either way; a table that
     // fills up flags its query, which is then re-run with the larger one as ever.
