@@ -63,6 +63,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_PREFILTER_HANDOVER 64 /* nidx_gpu_bm25_prefilter_batch_resident, nidx_gpu_prefilter_rows_* / _link_*, nidx_gpu_vector_search_prefiltered_per_query */
 #define NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER 128 /* nidx_gpu_prefilter_term_link_*, nidx_gpu_bm25_search_prefiltered */
 #define NIDX_FEATURE_JSON_PREFILTER 256 /* nidx_gpu_json_*, nidx_gpu_prefilter_rows_combine / _state / _read_resources */
+#define NIDX_FEATURE_VECTOR_ROUTED_TICKETS 512 /* nidx_gpu_vector_search_submit_filtered_per_query_async, nidx_gpu_vector_search_wait_routed, nidx_gpu_use_hnsw_threshold, nidx_gpu_vector_routed_stats */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -473,6 +474,43 @@ int32_t nidx_gpu_vector_search_submit_filtered_per_query(nidx_gpu_vector_index_t
                                                          uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
                                                          const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
                                                          const uint32_t *filter_of_query, uint64_t *ticket_out);
+
+/* The same batch as a ticket that waits for nothing (present when nidx_gpu_build_features() & NIDX_FEATURE_VECTOR_ROUTED_TICKETS).
+ * Same arguments, same errors (codes and messages) and the same hits as nidx_gpu_vector_search_filtered_per_query, but everything is
+ * queued on a pipeline slot's stream and the call returns: the filters are evaluated there, a kernel routes every (query, segment) from
+ * the counts in HBM (OpenSegment::_search's choice is `matching >= nidx_gpu_use_hnsw_threshold`), the walks of all segments go out in
+ * one launch over the routed queries, the scans of each segment run over theirs, Fssc merges on the device and one transfer of the
+ * merged hits, the routing and the counts is queued behind them.  No stream or event is synchronised and nothing is read back before
+ * the wait.  The ticket takes a slot, holds the generation and counts against "pipeline_depth" like any other.  The programs and
+ * filter_of_query are copied before the call returns: when a walk of the batch overflowed a bounded on-chip structure the wait answers
+ * the whole batch through the blocking search (*n_retried_out = n_queries).
+ * Batches the routed path does not take — a program deeper than NIDX_FILTER_STACK, filters that do not fit one chunk of the filter
+ * scratch, more than 65 535 queries, a segment that searches its RaBitQ store or a forced RaBitQ method, multi-vector paragraphs, a
+ * forced NIDX_METHOD_HNSW on an index with a segment without a graph — are answered as nidx_gpu_vector_search_submit_filtered_per_query
+ * answers them (that call's kind of ticket; nidx_gpu_vector_routed_stats counts them as fallbacks). */
+int32_t nidx_gpu_vector_search_submit_filtered_per_query_async(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                               uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                               const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                               const uint32_t *filter_of_query, uint64_t *ticket_out);
+/* nidx_gpu_vector_search_wait for a ticket of any kind, which also hands over the routing of a routed ticket: out_method
+ * [n_queries][n_segments] and out_matching [n_filters][n_segments] as nidx_gpu_vector_search_filtered_per_query reports them (either
+ * may be NULL).  For the other kinds of ticket both are zero-filled. */
+int32_t nidx_gpu_vector_search_wait_routed(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,
+                                           uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method,
+                                           uint64_t *out_matching, uint32_t *n_retried_out);
+/* The smallest matching_nodes in [1, total_nodes] for which nidx_gpu_use_hnsw(total_nodes, matching_nodes, top_k, has_rabitq) holds —
+ * it holds for every larger one too, the cost model is monotone in matching_nodes — or UINT64_MAX when it never does.  Host only. */
+int32_t nidx_gpu_use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, int32_t has_rabitq, uint64_t *threshold_out);
+typedef struct nidx_gpu_vector_routed_stats {
+    uint64_t batches_routed;            /* batches nidx_gpu_vector_search_submit_filtered_per_query_async queued on a slot */
+    uint64_t batches_fallback;          /* batches it answered through nidx_gpu_vector_search_submit_filtered_per_query */
+    uint64_t submit_synchronisations;   /* stream or event synchronisations made inside routed submits */
+    uint64_t walk_items;                /* (query, segment) pairs routed to the walk, read at wait from the lists' lengths */
+    uint64_t scan_items;                /* ... to the exact scan */
+    uint64_t launches;                  /* kernels queued by routed submits */
+    uint64_t batches_flagged;           /* routed batches answered by the blocking search at wait (an overflowed walk) */
+} nidx_gpu_vector_routed_stats_t;
+int32_t nidx_gpu_vector_routed_stats(nidx_gpu_vector_index_t *index, nidx_gpu_vector_routed_stats_t *stats_out);
 
 /* One query per call, the shape of the reference's request path (one blocking thread per Search request,
  * src/searcher/shard_search.rs:139-153; one vector per request, nodereader.proto:402).  Thread safe:

@@ -145,6 +145,12 @@ class VectorSyncEntryC(C.Structure):
                 ("key_bytes", C.c_void_p), ("key_offsets", C.c_void_p), ("n_keys", C.c_uint32)]
 
 
+class VectorRoutedStatsC(C.Structure):
+    """nidx_gpu_vector_routed_stats_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("batches_routed", "batches_fallback", "submit_synchronisations", "walk_items", "scan_items",
+                                          "launches", "batches_flagged")]
+
+
 class VectorSyncStatsC(C.Structure):
     """nidx_gpu_vector_sync_stats_t"""
     _fields_ = [("generation", C.c_uint64), ("bytes_uploaded", C.c_uint64), ("paragraphs_cleared", C.c_uint64), ("hbm_released", C.c_uint64),
@@ -159,6 +165,7 @@ FEATURE_BM25_HIT_TERMS = 32   # nidx_gpu_build_features() bit: nidx_gpu_bm25_hit
 FEATURE_PREFILTER_HANDOVER = 64   # nidx_gpu_build_features() bit: resident prefilter rows, the text-to-vector link, nidx_gpu_vector_search_prefiltered_per_query
 FEATURE_PARAGRAPH_PREFILTER_HANDOVER = 128   # nidx_gpu_build_features() bit: the text-to-paragraph term link, nidx_gpu_bm25_search_prefiltered
 FEATURE_JSON_PREFILTER = 256   # nidx_gpu_build_features() bit: the resident JSON index, its prefilter batch, the resource link, nidx_gpu_prefilter_rows_combine
+FEATURE_VECTOR_ROUTED_TICKETS = 512   # nidx_gpu_build_features() bit: per-query filter tickets routed on the device, nidx_gpu_use_hnsw_threshold
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -386,6 +393,13 @@ SIGNATURES = {
     "nidx_gpu_vector_search_submit_filtered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                                      C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p,
                                                                      C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_submit_filtered_per_query_async": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                           C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                           C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_search_wait_routed": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "nidx_gpu_use_hnsw_threshold": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_routed_stats": (C.c_int32, [C.c_void_p, C.POINTER(VectorRoutedStatsC)]),
     "nidx_gpu_vector_search_one_filtered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(VectorSearchParamsC), C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "nidx_gpu_vector_spill_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),

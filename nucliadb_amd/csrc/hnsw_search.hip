@@ -497,8 +497,30 @@ __global__ __launch_bounds__(256, MINW) void hnsw_search_segments_kernel(const H
     hnsw_search_body<NJ, EVR, EFL, SPLIT>(a, blockIdx.x - s * nq, smem);
 }
 
+// The same grid for a batch routed on the device (vector_route.hip): record s walks the queries items[s * nq .. + n_items[s]) — the ones
+// whose filter leaves the walk the cheaper arm on that segment — and the blocks past that count return at once.  The body indexes
+// queries, outputs, flags and filter rows by the query index it is given, so a routed walk is the walk of that query.
+template <int NJ, int EVR, int MINW, int EFL, bool SPLIT>
+__global__ __launch_bounds__(256, MINW) void hnsw_search_routed_kernel(const HnswSearchArgs *__restrict__ table, const uint32_t *__restrict__ items,
+                                                                       const uint32_t *__restrict__ n_items, uint32_t nq) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const uint32_t s = blockIdx.x / nq, i = blockIdx.x - s * nq;
+    if (i >= n_items[s]) return;   // uniform per workgroup
+    const HnswSearchArgs a = table[s];
+    hnsw_search_body<NJ, EVR, EFL, SPLIT>(a, items[(size_t)s * nq + i], smem);
+}
+
 template <int NJ, int EVR, int MINW, int EFL, bool SPLIT>
 static hipError_t launch_form(const HnswSearchArgs &a, int waves, hipStream_t s) {
+    if (a.seg_table && a.route_items) {
+        size_t smem = sizeof(SearchShared) + ((size_t)4 << a.vis_log2);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_routed_kernel<NJ, EVR, MINW, EFL, SPLIT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((hnsw_search_routed_kernel<NJ, EVR, MINW, EFL, SPLIT>), dim3(a.n_queries * a.n_table), dim3(64 * waves), smem, s,
+                           a.seg_table, a.route_items, a.route_n_items, a.n_queries);
+        return hipGetLastError();
+    }
     if (a.seg_table) {
         size_t smem = sizeof(SearchShared) + ((size_t)4 << a.vis_log2);
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hnsw_search_segments_kernel<NJ, EVR, MINW, EFL, SPLIT>),

@@ -37,6 +37,12 @@ uint32_t scan_shared_stripes(uint32_t n, uint32_t n_queries, uint32_t dp, uint32
 hipError_t launch_scan_shared(const ScanArgs &a, uint32_t stripes, hipStream_t s);
 hipError_t launch_merge_topk(const uint64_t *partial, uint32_t n_queries, uint32_t lists_per_query, uint32_t k,
                              uint32_t *out_vec, float *out_score, uint32_t *out_count, hipStream_t s);
+// The routed forms (VectorIndex::pipeline_submit_routed): the number of queries is known on the device only.  `a` carries the upper
+// bound in n_queries (grid and query tile follow it) and compact rows: queries [*n_items][dp], filter_row [*n_items] (not nullptr);
+// tiles / blocks past *n_items return at once, the others see n_queries = *n_items.  Only the register-tile scan, per-query rows.
+hipError_t launch_scan_routed(ScanArgs a, const uint32_t *n_items, uint32_t nblk, hipStream_t s);
+hipError_t launch_merge_topk_routed(const uint64_t *partial, const uint32_t *n_items, uint32_t n_queries_max, uint32_t lists_per_query, uint32_t k,
+                                    uint32_t *out_vec, float *out_score, uint32_t *out_count, hipStream_t s);
 // the register-tile scans / merges of several segments in one launch each (table-driven: blockIdx.z / .y = segment)
 struct ScanMergeTab {
     const uint64_t *partial;
@@ -249,6 +255,11 @@ struct HnswSearchArgs {
     const uint32_t *filter_row = nullptr;
     const uint64_t *filter_table = nullptr;   // [rows][filter_words]: filter & alive of each distinct filter (launch_filter_batch)
     uint32_t filter_words = 0;
+    // launch_hnsw_search with seg_table only: nullptr, or the routed form (hnsw_search_routed_kernel) — route_items[s * n_queries + i] =
+    // the i-th query record s walks, route_n_items[s] = how many (both in HBM, written by launch_route: vector_route.hip).  The grid
+    // stays n_queries x n_table; a block past its record's count returns at once.  The kernels never read these two fields
+    const uint32_t *route_items = nullptr;
+    const uint32_t *route_n_items = nullptr;
 };
 #define NIDX_DUMP_STRIDE 512
 hipError_t launch_hnsw_search(const HnswSearchArgs &a, int waves_per_query, hipStream_t s);
@@ -457,6 +468,38 @@ hipError_t launch_bm25_prefilter_project(const uint64_t *const *rows, uint32_t n
                                          uint64_t *out, unsigned long long *stats, hipStream_t s);
 // dst[i] = src[idx[i]] for rows of dp floats (the queries one search arm of a batch takes)
 hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s);
+
+
+// ---- routing of a per-query filtered batch on the device (vector_route.hip) ----
+// OpenSegment::_search's choice of arm (segment.rs:506-555) for every (query, segment) of a batch whose filters were evaluated on the same
+// stream: the counts never leave HBM.  use_hnsw is monotone in `matching`, so the host hands over its smallest matching from which the
+// walk wins (use_hnsw_threshold) and the device compares.
+struct RouteSegDev {
+    unsigned long long alive_count;   // matching of an unfiltered query
+    unsigned long long threshold;     // NIDX_METHOD_AUTO: matching >= threshold takes the walk; UINT64_MAX: never
+    uint32_t n;                       // vectors (0: nothing is searched)
+    uint32_t has_graph;
+};
+struct RouteArgs {
+    const unsigned long long *counts;   // [n_segs][n_filters] |filter & alive| (launch_filter_combine)
+    const uint32_t *filter_of_query;    // [nq] the query's filter among the batch's n_filters, NIDX_FILTER_ROW_NONE = unfiltered
+    const uint8_t *has_program;         // [n_segs][n_filters] 0: the filter has no program on that segment (unfiltered there)
+    const RouteSegDev *segs;            // [n_segs]
+    uint32_t nq, n_filters, n_segs;
+    int method;                         // NIDX_METHOD_AUTO, NIDX_METHOD_HNSW (every segment has a graph) or NIDX_METHOD_BRUTE_FORCE
+    int32_t *out_method;                // [nq][n_segs] 0 = not searched
+    unsigned long long *out_matching;   // [n_filters][n_segs]
+    uint32_t *filter_row;               // [n_segs][nq] the row of the segment's filter table the query tests (NIDX_FILTER_ROW_NONE: none)
+    uint32_t *items_hnsw, *items_scan;  // [n_segs][nq] the queries of each arm, ascending; the first n_hnsw[s] / n_scan[s] entries count
+    uint32_t *n_hnsw, *n_scan;          // [n_segs]
+};
+hipError_t launch_route(const RouteArgs &a, hipStream_t s);
+// compact rows of one segment's scan arm: dst[i] = src[items[i]], dst_filter_row[i] = filter_row[items[i]] for i < *n_items (grid: n_max)
+hipError_t launch_route_gather(const float *src, const uint32_t *items, const uint32_t *n_items, const uint32_t *filter_row, uint32_t n_max,
+                               uint32_t dp, float *dst, uint32_t *dst_filter_row, hipStream_t s);
+// compact result row i -> row items[i] of the segment's [vectors | scores | counts] for i < *n_items
+hipError_t launch_route_scatter(const uint32_t *c_vec, const float *c_score, const uint32_t *c_count, const uint32_t *items, const uint32_t *n_items,
+                                uint32_t n_max, uint32_t k, uint32_t *out_vec, float *out_score, uint32_t *out_count, hipStream_t s);
 
 // ---- BM25 (bm25.hip) ----
 #define BM25_MAX_CLAUSES 64

@@ -166,7 +166,27 @@ void stage_query_rows(const float *src, float *dst, uint32_t nq, uint32_t d, uin
 
 void set_stage_threads(int32_t n) { g_stage_threads.store(std::max(0, std::min(n, 16)), std::memory_order_relaxed); }
 
+// What the wait of a routed ticket (pipeline_submit_routed) needs beyond the slot's block: the caller's filters of the batch's
+// rows, and deep copies of the request — a batch with an overflowed walk is answered by search_per_query from them
+struct RoutedBatch {
+    uint32_t n_filters = 0;
+    std::vector<uint32_t> filters;   // the batch's distinct filters in order of first use (row lf of the block's matching = filter filters[lf])
+    std::vector<float> rows;         // the raw query rows, kept only when the index normalises its queries (else the slot's staging holds them)
+    std::vector<nidx_gpu_filter_program_t> programs;   // [n_filters][n_segments], pointing into ops / lists
+    std::vector<std::vector<nidx_gpu_filter_op_t>> ops;
+    std::vector<std::vector<uint32_t>> lists;
+    std::vector<uint32_t> filter_of_query;
+    bool has_filter_of_query = false;
+};
+
 struct SearchSlot {
+    // a routed batch: its ticket's copies, the scratch of its filter stage, its routing lists and its scan arm — the slot's own, so
+    // batches in flight share none of it
+    bool routed = false;
+    std::unique_ptr<RoutedBatch> rb;
+    size_t rw = 0;   // words of the routing region between the merged hits and the per-segment rows
+    DevBuf d_rt_in, d_rt_table, d_rt_operands, d_rt_count, d_rt_lists, d_rt_queries, d_rt_rows, d_rt_compact;
+    PinBuf pin_rt_in;
     bool busy = false, waiting = false;
     uint64_t ticket = 0;
     hipStream_t stream = nullptr;
@@ -213,7 +233,7 @@ struct Pipeline {
     hipEvent_t gate[GATES] = {};      // gate[i % GATES]: completion of batch i
     // tickets of nidx_gpu_vector_search_submit_filtered_per_query: searched when submitted, their hits wait here for the ticket
     struct DoneBatch {
-        uint32_t nq = 0, k = 0;
+        uint32_t nq = 0, k = 0, n_filters = 0;
         std::vector<uint32_t> seg, par, vec, cnt;
         std::vector<float> sc;
     };
@@ -262,8 +282,10 @@ struct SlotRelease {   // hands the slot back on every exit path
             (void)hipStreamSynchronize(slot->stream);
             slot->dirty = false;
         }
+        slot->rb.reset();
         std::lock_guard<std::mutex> lk(P.mu);
         slot->busy = slot->waiting = false;
+        slot->routed = false;
         slot->ticket = 0;
         P.cv_free.notify_one();
     }
@@ -632,7 +654,7 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
 }
 
 int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
-                                   uint32_t *out_count, uint32_t *n_retried_out) {
+                                   uint32_t *out_count, uint32_t *n_retried_out, int32_t *out_method, uint64_t *out_matching) {
     Pipeline &P = *pipe;
     SearchSlot *slot = nullptr;
     {
@@ -648,6 +670,9 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
         if (db) {
             struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};   // the ticket's hold (pipeline_submit_per_query)
             if (n_retried_out) *n_retried_out = 0;
+            // (the routing of these tickets stayed with their submit: nidx_gpu_vector_search_wait_routed reports none)
+            if (out_method) std::fill(out_method, out_method + (size_t)db->nq * segs.size(), 0);
+            if (out_matching) std::fill(out_matching, out_matching + (size_t)db->n_filters * segs.size(), 0);
             for (uint32_t q = 0; q < db->nq; q++) {
                 const size_t at = (size_t)q * db->k, c = db->cnt[q];
                 out_count[q] = db->cnt[q];
@@ -673,9 +698,12 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
     const size_t S = segs.size();
     if (n_retried_out) *n_retried_out = 0;
     for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
+    if (out_method) std::fill(out_method, out_method + (size_t)nq * S, 0);
+    if (out_matching && sl.rb) std::fill(out_matching, out_matching + (size_t)sl.rb->n_filters * S, 0);
     if (!sl.launched) return NIDX_OK;
     NIDX_HIP(hipSetDevice(device));
     NIDX_HIP(hipEventSynchronize(sl.done));   // (a failure leaves the slot dirty: SlotRelease drains its stream)
+    if (sl.routed) return routed_wait(sl, out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching, n_retried_out);
     const size_t fw = flag_words(S), mw = sl.mw, sw = seg_words(nq, k);
     uint32_t *host = sl.pin_out.as<uint32_t>();
     // per searched segment: did a walk raise a flag?  The copy route reads the device's flag word of the segment; the host block
@@ -775,6 +803,7 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     auto db = std::make_unique<Pipeline::DoneBatch>();
     db->nq = nq;
     db->k = p.k;
+    db->n_filters = n_filters;
     const size_t kk = std::max<uint32_t>(p.k, 1);
     db->seg.resize(nq * kk), db->par.resize(nq * kk), db->vec.resize(nq * kk), db->sc.resize(nq * kk), db->cnt.resize(nq);
     const int32_t rc = search_per_query(queries, nq, p, programs, n_filters, filter_of_query, db->seg.data(), db->par.data(), db->vec.data(),
@@ -788,6 +817,366 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     *ticket_out = ticket;
     gen_hold.g = nullptr;
     return NIDX_OK;
+}
+
+// ---- the per-query filtered batch as a ticket that waits for nothing (nidx_gpu_vector_search_submit_filtered_per_query_async) -------
+// What forces pipeline_submit_per_query to the host is one decision: which arm a (query, segment) takes, from |filter & alive|.  That is a
+// comparison against a constant of the segment (use_hnsw_threshold), so here the filters are evaluated on the slot's stream, route_kernel
+// decides from the counts in HBM and writes each arm's queries per segment, one table-driven launch walks the routed queries of every
+// segment, each segment's scan runs over its compact rows, Fssc merges on the device as in pipeline_submit and ONE transfer of
+// [flag words | merged hits | routing] is queued.  The block of a routed slot:
+//   [flag words][merged hits][routing: method nq*S | n_hnsw S | n_scan S | (pad to 8 bytes) | matching F*S u64][per segment rows]
+namespace {
+inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
+}  // namespace
+
+int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                                            const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
+                                            uint64_t *ticket_out) {
+    Pipeline &P = *pipe;
+    if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
+    struct GenHold {
+        GenGate *g;
+        ~GenHold() { if (g) g->leave(); }
+    } gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
+    RoutedPlan plan;
+    int32_t rc = routed_plan(nq, p, programs, n_filters, filter_of_query, plan);
+    if (rc != NIDX_OK) return rc;
+    if (plan.fallback) {
+        gate.leave();   // (pipeline_submit_per_query takes its own hold)
+        gen_hold.g = nullptr;
+        rc = pipeline_submit_per_query(queries, nq, p, programs, n_filters, filter_of_query, ticket_out);
+        if (rc == NIDX_OK) routed_stats[RS_FALLBACK].fetch_add(1, std::memory_order_relaxed);
+        return rc;
+    }
+    const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const size_t S = segs.size();
+    const uint32_t F = (uint32_t)plan.filters.size();
+    NIDX_HIP(hipSetDevice(device));
+
+    SearchSlot *slot = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(P.mu);
+        uint32_t n_busy = (uint32_t)P.done.size();
+        for (auto &s : P.slots) n_busy += s->busy ? 1u : 0u;
+        if (n_busy >= P.depth) return fail(NIDX_ERR_BUSY, "all %u pipeline slots hold a ticket that has not been waited for", P.depth);
+        for (auto &s : P.slots)
+            if (!s->busy) { slot = s.get(); break; }
+        if (!slot) {
+            std::unique_ptr<SearchSlot> ns(new SearchSlot());
+            NIDX_HIP(hipStreamCreateWithFlags(&ns->stream, hipStreamNonBlocking));
+            NIDX_HIP(hipEventCreateWithFlags(&ns->done, hipEventDisableTiming));
+            P.slots.push_back(std::move(ns));
+            slot = P.slots.back().get();
+        }
+        slot->busy = true;
+        slot->waiting = false;
+        slot->routed = true;
+        slot->ticket = P.next_ticket++;
+    }
+    // (No crowded launch shape here, whatever else is on the device: its 2^12 visited table flags more walks, and one flagged walk costs
+    // a routed batch the blocking search of all its queries — measured 38 k against 69 k queries/s)
+    SlotRelease release{P, slot};
+    SearchSlot &sl = *slot;
+    sl.nq = nq;
+    sl.params = p;
+    sl.method.assign(S, 0);
+    sl.d_seg_filter.assign(S, nullptr);
+    sl.launched = false;
+    sl.merged = false;
+    sl.host_block = false;
+    sl.dq = nullptr;
+    sl.rw = 0;
+    // ---- the ticket's copies: "programs are read before the call returns", and a flagged batch is searched again from them ----
+    sl.rb.reset(new RoutedBatch());
+    RoutedBatch &rb = *sl.rb;
+    rb.n_filters = n_filters;
+    rb.filters = plan.filters;
+    if (!plan.nothing) {
+        if (cfg.normalize_vectors) rb.rows.assign(queries, queries + (size_t)nq * d);
+        rb.has_filter_of_query = filter_of_query != nullptr;
+        if (filter_of_query) rb.filter_of_query.assign(filter_of_query, filter_of_query + nq);
+        rb.programs.resize((size_t)n_filters * S);
+        rb.ops.resize(rb.programs.size());
+        rb.lists.resize(rb.programs.size());
+        for (size_t i = 0; i < rb.programs.size(); i++) {
+            const nidx_gpu_filter_program_t &src = programs[i];
+            if (src.ops && src.n_ops) rb.ops[i].assign(src.ops, src.ops + src.n_ops);
+            if (src.lists && src.n_lists) rb.lists[i].assign(src.lists, src.lists + src.n_lists);
+            rb.programs[i] = src;
+            rb.programs[i].ops = rb.ops[i].empty() ? nullptr : rb.ops[i].data();
+            rb.programs[i].lists = rb.lists[i].empty() ? nullptr : rb.lists[i].data();
+        }
+    }
+    uint64_t launches = 0;
+    if (!plan.nothing) {
+        // ---- queries -> HBM through the slot's pinned staging ----
+        NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
+        stage_query_rows(queries, sl.pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
+        NIDX_HIP(sl.d_queries.reserve((size_t)nq * dp * 4));
+        NIDX_HIP(hipMemcpyAsync(sl.d_queries.p, sl.pin_in.p, (size_t)nq * dp * 4, hipMemcpyHostToDevice, sl.stream));
+        sl.dq = sl.d_queries.as<float>();
+        // ---- result block (see pipeline_submit for the merge's two routes) ----
+        const bool big_dedup = p.with_duplicates == 0 && (uint64_t)S * k > 4096;
+        sl.merged = !(S == 1 && segs[0].key_ids.empty()) && !big_dedup && !getenv("NIDX_GPU_FSSC_HOST");
+        const size_t fw = flag_words(S), mw = sl.merged ? merged_words(nq, k) : 0, sw = seg_words(nq, k);
+        const size_t at_method = fw + mw, at_nh = at_method + (size_t)nq * S, at_ns = at_nh + S, at_match = (at_ns + S + 1) & ~(size_t)1;
+        const size_t rw = at_match + (size_t)F * S * 2 - at_method, words = fw + mw + rw + S * sw;
+        sl.mw = mw;
+        sl.rw = rw;
+        sl.dirty = true;   // from here on work is queued on the slot's stream: an error path must drain it (SlotRelease)
+        sl.flag_bytes = fw * 4;
+        if (words * 4 > sl.d_block.bytes) {
+            NIDX_HIP(sl.d_block.reserve(words * 4));
+            NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
+        }
+        NIDX_HIP(sl.pin_out.reserve(words * 4));
+        uint32_t *blk = sl.d_block.as<uint32_t>();
+        // ---- one upload: [segment records | program words | the queries' filters | has-program bytes] ----
+        const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + plan.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
+                     in_bytes = at_has + S * (size_t)F;
+        NIDX_HIP(sl.pin_rt_in.reserve(in_bytes));
+        NIDX_HIP(sl.d_rt_in.reserve(in_bytes));
+        {
+            unsigned char *h = sl.pin_rt_in.as<unsigned char>();
+            memcpy(h, plan.segs.data(), S * sizeof(RouteSegDev));
+            if (!plan.prog.empty()) memcpy(h + at_prog, plan.prog.data(), plan.prog.size() * 4);
+            memcpy(h + at_foq, plan.filter_of_query.data(), (size_t)nq * 4);
+            if (!plan.has_program.empty()) memcpy(h + at_has, plan.has_program.data(), plan.has_program.size());
+        }
+        NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in_bytes, hipMemcpyHostToDevice, sl.stream));
+        const unsigned char *din = sl.d_rt_in.as<unsigned char>();
+        const uint32_t *dprog = reinterpret_cast<const uint32_t *>(din + at_prog);
+        NIDX_HIP(sl.d_rt_table.reserve(std::max<size_t>(plan.tab_words, 1) * 8));
+        NIDX_HIP(sl.d_rt_operands.reserve(std::max<size_t>(plan.opnd_words, 1) * 8));
+        NIDX_HIP(sl.d_rt_count.reserve(std::max<size_t>(S * (size_t)F, 1) * 8));
+        NIDX_HIP(hipMemsetAsync(sl.d_rt_count.p, 0, std::max<size_t>(S * (size_t)F, 1) * 8, sl.stream));
+        NIDX_HIP(sl.d_rt_lists.reserve(S * (size_t)nq * 3 * 4));
+        uint32_t *d_filter_row = sl.d_rt_lists.as<uint32_t>(), *d_items_h = d_filter_row + S * (size_t)nq, *d_items_b = d_items_h + S * (size_t)nq;
+        uint32_t *d_nh = blk + at_nh, *d_ns = blk + at_ns;
+        // this batch's turn on the device (Pipeline::walks)
+        uint64_t my_seq = 0;
+        {
+            std::lock_guard<std::mutex> lk(P.mu);
+            my_seq = P.launched++;
+            if (my_seq >= P.walks && P.gate[(my_seq - P.walks) % Pipeline::GATES])
+                NIDX_HIP(hipStreamWaitEvent(sl.stream, P.gate[(my_seq - P.walks) % Pipeline::GATES], 0));
+        }
+        const size_t hnsw_tab_bytes = (S * sizeof(HnswSearchArgs) + 63) & ~(size_t)63, tab_bytes = hnsw_tab_bytes + S * sizeof(FsscSegDev);
+        NIDX_HIP(sl.pin_tables.reserve(tab_bytes));
+        NIDX_HIP(sl.d_tables.reserve(tab_bytes));
+        HnswSearchArgs *h_hnsw = sl.pin_tables.as<HnswSearchArgs>();
+        FsscSegDev *h_fssc = reinterpret_cast<FsscSegDev *>(sl.pin_tables.as<unsigned char>() + hnsw_tab_bytes);
+        uint32_t n_searched = 0;
+        {
+            // launches read index state (tunables): under the index lock, held for the launch calls only
+            std::lock_guard<std::mutex> lock(mu);
+            // ---- the filters of the batch on every segment: the operand rows are the segments' one after the other, in stream order ----
+            for (size_t s = 0; s < S; s++) {
+                if (!plan.any_prog[s]) continue;
+                VectorSegment &seg = segs[s];
+                const uint32_t n_bits = seg.n_paragraphs, fwords = (n_bits + 63) / 64;
+                if (plan.n_opnd[s]) NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, (size_t)plan.n_opnd[s] * fwords * 8, sl.stream));
+                NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), dprog + plan.at_work[s], plan.n_work[s], n_bits,
+                                               fwords, sl.d_rt_operands.as<uint64_t>(), sl.stream));
+                NIDX_HIP(launch_filter_combine(dprog + plan.at_ops[s], dprog + plan.at_first[s], F, sl.d_rt_operands.as<uint64_t>(),
+                                               seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), fwords, n_bits,
+                                               sl.d_rt_table.as<uint64_t>() + plan.tab_off[s], sl.d_rt_count.as<unsigned long long>() + s * F, sl.stream));
+                launches += (plan.n_work[s] ? 1 : 0) + (F && fwords ? 1 : 0);
+            }
+            // ---- routing: the counts stay where the combine launches left them ----
+            RouteArgs ra;
+            ra.counts = sl.d_rt_count.as<unsigned long long>();
+            ra.filter_of_query = reinterpret_cast<const uint32_t *>(din + at_foq);
+            ra.has_program = din + at_has;
+            ra.segs = reinterpret_cast<const RouteSegDev *>(din);
+            ra.nq = nq, ra.n_filters = F, ra.n_segs = (uint32_t)S;
+            ra.method = p.method;
+            ra.out_method = reinterpret_cast<int32_t *>(blk + at_method);
+            ra.out_matching = reinterpret_cast<unsigned long long *>(blk + at_match);
+            ra.filter_row = d_filter_row;
+            ra.items_hnsw = d_items_h, ra.items_scan = d_items_b;
+            ra.n_hnsw = d_nh, ra.n_scan = d_ns;
+            NIDX_HIP(launch_route(ra, sl.stream));
+            launches++;
+            // ---- per-segment rows, as pipeline_submit lays them out; a (query, segment) no arm takes keeps the cleared count ----
+            NIDX_HIP(hipMemsetAsync(blk + fw + mw + rw, 0, S * sw * 4, sl.stream));
+            const uint32_t walks = nq * (uint32_t)std::min<size_t>(S, 64);   // the launch shape follows the grid's upper bound
+            int shape_seg = -1;
+            uint32_t nblk = 1;
+            for (size_t s = 0; s < S; s++) {
+                VectorSegment &seg = segs[s];
+                uint32_t *d_vec = blk + fw + mw + rw + s * sw;
+                float *d_score = reinterpret_cast<float *>(d_vec + (size_t)nq * k);
+                uint32_t *d_count = d_vec + (size_t)nq * k * 2;
+                h_fssc[s] = FsscSegDev{seg.vectors.as<float>(), seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>(),
+                                       seg.key_ids.empty() ? nullptr : seg.key_ids_dev.as<unsigned long long>(), d_vec, nullptr, d_score, seg.dp, 0u};
+                if (seg.n) {
+                    h_fssc[s].count = d_count;
+                    n_searched++;
+                    nblk = std::max(nblk, scan_num_blocks(seg.n));
+                }
+                HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, nullptr, d_vec, d_score, d_count,
+                                              nullptr, vis_for(walks), blk + s);
+                ha.filter_row = d_filter_row + s * (size_t)nq;
+                ha.filter_table = plan.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + plan.tab_off[s] : nullptr;
+                ha.filter_words = (seg.n_paragraphs + 63) / 64;
+                h_hnsw[s] = ha;
+                if (shape_seg < 0 && seg.has_graph && seg.n) shape_seg = (int)s;
+            }
+            NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, tab_bytes, hipMemcpyHostToDevice, sl.stream));
+            // ---- the walk arm: every segment's routed queries in one launch ----
+            if (p.method != NIDX_METHOD_BRUTE_FORCE && shape_seg >= 0) {
+                HnswSearchArgs a = h_hnsw[shape_seg];
+                a.seg_table = sl.d_tables.as<HnswSearchArgs>();
+                a.n_table = (uint32_t)S;
+                a.route_items = d_items_h;
+                a.route_n_items = d_nh;
+                NIDX_HIP(launch_hnsw_search(a, waves_per_query, sl.stream));
+                launches++;
+            }
+            // ---- the scan arm: per segment gather -> register-tile scan with per-query rows -> merge -> scatter.  The compact rows, the
+            // per-block lists (sized by nq) and the compact hits are the segments' one after the other ----
+            if (p.method != NIDX_METHOD_HNSW) {
+                NIDX_HIP(sl.d_rt_queries.reserve((size_t)nq * dp * 4));
+                NIDX_HIP(sl.d_rt_rows.reserve((size_t)nq * 4));
+                NIDX_HIP(sl.d_rt_compact.reserve(((size_t)nq * k * 2 + nq) * 4));
+                NIDX_HIP(sl.d_bf_partial.reserve((size_t)nq * nblk * k * 8));
+                uint32_t *c_vec = sl.d_rt_compact.as<uint32_t>();
+                float *c_score = reinterpret_cast<float *>(c_vec + (size_t)nq * k);
+                uint32_t *c_count = c_vec + (size_t)nq * k * 2;
+                for (size_t s = 0; s < S; s++) {
+                    VectorSegment &seg = segs[s];
+                    if (!seg.n) continue;
+                    uint32_t *d_vec = blk + fw + mw + rw + s * sw;
+                    const uint32_t *items = d_items_b + s * (size_t)nq, *n_items = d_ns + s;
+                    NIDX_HIP(launch_route_gather(sl.dq, items, n_items, d_filter_row + s * (size_t)nq, nq, dp, sl.d_rt_queries.as<float>(),
+                                                 sl.d_rt_rows.as<uint32_t>(), sl.stream));
+                    ScanArgs a = scan_args((uint32_t)s, sl.d_rt_queries.as<float>(), nq, k, p.min_score, nullptr);
+                    a.filter_row = sl.d_rt_rows.as<uint32_t>();
+                    a.filter_table = plan.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + plan.tab_off[s] : nullptr;
+                    a.filter_words = (seg.n_paragraphs + 63) / 64;
+                    a.partial = sl.d_bf_partial.as<uint64_t>();
+                    const uint32_t sblk = scan_num_blocks(seg.n);
+                    NIDX_HIP(launch_scan_routed(a, n_items, sblk, sl.stream));
+                    NIDX_HIP(launch_merge_topk_routed(a.partial, n_items, nq, sblk, k, c_vec, c_score, c_count, sl.stream));
+                    NIDX_HIP(launch_route_scatter(c_vec, c_score, c_count, items, n_items, nq, k, d_vec, reinterpret_cast<float *>(d_vec + (size_t)nq * k),
+                                                  d_vec + (size_t)nq * k * 2, sl.stream));
+                    launches += 4;
+                }
+            }
+        }
+        // ---- Fssc on the device, or the per-segment rows for the host merge (pipeline_submit) ----
+        if (sl.merged) {
+            FsscArgs f;
+            f.segs = reinterpret_cast<const FsscSegDev *>(sl.d_tables.as<unsigned char>() + hnsw_tab_bytes);
+            f.n_segs = (uint32_t)S, f.nq = nq, f.k = k, f.dim = d;
+            f.with_duplicates = p.with_duplicates != 0;
+            f.offered = nullptr;
+            f.offered_stride = std::max<uint32_t>(n_searched, 1) * k;
+            if (!f.with_duplicates) {
+                NIDX_HIP(sl.d_offered.reserve((size_t)nq * f.offered_stride * 12));
+                f.offered = sl.d_offered.as<uint32_t>();
+            }
+            f.out_seg = blk + fw;
+            f.out_para = f.out_seg + (size_t)nq * k;
+            f.out_vec = f.out_para + (size_t)nq * k;
+            f.out_score = reinterpret_cast<float *>(f.out_vec + (size_t)nq * k);
+            f.out_count = f.out_vec + (size_t)nq * k * 2;
+            NIDX_HIP(launch_fssc_merge(f, sl.stream));
+            launches++;
+            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, (fw + mw + rw) * 4, hipMemcpyDeviceToHost, sl.stream));
+        } else {
+            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, words * 4, hipMemcpyDeviceToHost, sl.stream));
+        }
+        NIDX_HIP(hipEventRecord(sl.done, sl.stream));
+        {
+            std::lock_guard<std::mutex> lk(P.mu);
+            hipEvent_t &g = P.gate[my_seq % Pipeline::GATES];
+            if (!g) NIDX_HIP(hipEventCreateWithFlags(&g, hipEventDisableTiming));
+            NIDX_HIP(hipEventRecord(g, sl.stream));
+        }
+        sl.launched = true;
+    }
+    routed_stats[RS_ROUTED].fetch_add(1, std::memory_order_relaxed);
+    routed_stats[RS_LAUNCHES].fetch_add(launches, std::memory_order_relaxed);
+    *ticket_out = sl.ticket;
+    release.slot = nullptr;   // the ticket owns the slot until it is waited for
+    gen_hold.g = nullptr;     // ... and its hold on the generation
+    return NIDX_OK;
+}
+
+// The wait of a routed ticket, behind the slot's event (pipeline_wait)
+int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
+                                 uint32_t *out_count, int32_t *out_method, uint64_t *out_matching, uint32_t *n_retried_out) {
+    const uint32_t nq = sl.nq, k = sl.params.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const size_t S = segs.size();
+    const RoutedBatch &rb = *sl.rb;
+    const uint32_t F = (uint32_t)rb.filters.size();
+    const size_t fw = flag_words(S), mw = sl.mw, rw = sl.rw, sw = seg_words(nq, k);
+    const size_t at_method = fw + mw, at_nh = at_method + (size_t)nq * S, at_ns = at_nh + S, at_match = (at_ns + S + 1) & ~(size_t)1;
+    const uint32_t *host = sl.pin_out.as<uint32_t>();
+    uint64_t walk_items = 0, scan_items = 0;
+    bool flagged = false;
+    for (size_t s = 0; s < S; s++) {
+        walk_items += host[at_nh + s];
+        scan_items += host[at_ns + s];
+        if (host[s]) flagged = true;
+    }
+    routed_stats[RS_WALK_ITEMS].fetch_add(walk_items, std::memory_order_relaxed);
+    routed_stats[RS_SCAN_ITEMS].fetch_add(scan_items, std::memory_order_relaxed);
+    if (flagged) {
+        // A walk overflowed a bounded on-chip structure: the blocking search answers the whole batch from the ticket's copies (it
+        // repairs spills query by query), and the flag words are zero again before anybody else takes the slot
+        routed_stats[RS_FLAGGED].fetch_add(1, std::memory_order_relaxed);
+        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
+        NIDX_HIP(hipStreamSynchronize(sl.stream));
+        sl.dirty = false;
+        const float *rows = rb.rows.data();
+        std::vector<float> unpadded;
+        if (!cfg.normalize_vectors) {   // the staging holds the rows as they came, zero padded to dp
+            rows = sl.pin_in.as<float>();
+            if (dp != d) {
+                unpadded.resize((size_t)nq * d);
+                for (uint32_t q = 0; q < nq; q++) memcpy(unpadded.data() + (size_t)q * d, rows + (size_t)q * dp, (size_t)d * 4);
+                rows = unpadded.data();
+            }
+        }
+        if (n_retried_out) *n_retried_out = nq;
+        return search_per_query(rows, nq, sl.params, rb.programs.data(), rb.n_filters, rb.has_filter_of_query ? rb.filter_of_query.data() : nullptr,
+                                out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching);
+    }
+    sl.dirty = false;   // everything queued has completed and no flag word is set
+    if (out_method) memcpy(out_method, host + at_method, (size_t)nq * S * 4);
+    if (out_matching) {
+        const uint64_t *m = reinterpret_cast<const uint64_t *>(host + at_match);
+        for (uint32_t lf = 0; lf < F; lf++)
+            for (size_t s = 0; s < S; s++) out_matching[(size_t)rb.filters[lf] * S + s] = m[(size_t)lf * S + s];
+    }
+    if (sl.merged) {
+        const uint32_t *m = host + fw, *cnt = m + (size_t)nq * k * 4;
+        for (uint32_t q = 0; q < nq; q++) {
+            const uint32_t c = std::min(cnt[q], k);
+            out_count[q] = c;
+            const size_t at = (size_t)q * k;
+            if (out_segment) memcpy(out_segment + at, m + at, (size_t)c * 4);
+            if (out_paragraph) memcpy(out_paragraph + at, m + (size_t)nq * k + at, (size_t)c * 4);
+            if (out_vector) memcpy(out_vector + at, m + (size_t)nq * k * 2 + at, (size_t)c * 4);
+            if (out_score) memcpy(out_score + at, m + (size_t)nq * k * 3 + at, (size_t)c * 4);
+        }
+        return NIDX_OK;
+    }
+    // Fssc across the segments on the host (one plain segment, or more candidates than the device merge takes)
+    std::vector<const uint32_t *> pv(S, nullptr), pc(S, nullptr);
+    std::vector<const float *> ps(S, nullptr);
+    for (size_t s = 0; s < S; s++) {
+        if (!segs[s].n) continue;
+        const uint32_t *b = host + fw + mw + rw + s * sw;
+        pv[s] = b;
+        ps[s] = reinterpret_cast<const float *>(b + (size_t)nq * k);
+        pc[s] = b + (size_t)nq * k * 2;
+    }
+    return fssc_merge(nq, sl.params, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
 }
 
 // ---- search_multi_vector for batches (searcher.rs:345-394): first pass through the entries above, second stage on the device ----
@@ -1000,6 +1389,28 @@ int32_t nidx_gpu_vector_search_wait(nidx_gpu_vector_index_t *index, uint64_t tic
     if (idx->is_maxsim_ticket(ticket))
         return fail(NIDX_ERR_INVALID_ARGUMENT, "ticket %llu belongs to nidx_gpu_vector_search_maxsim_wait", (unsigned long long)ticket);
     return idx->pipeline_wait(ticket, out_segment, out_paragraph, out_vector, out_score, out_count, n_retried_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_submit_filtered_per_query_async(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,
+                                                               uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params,
+                                                               const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                                               const uint32_t *filter_of_query, uint64_t *ticket_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !ticket_out || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    return idx->pipeline_submit_routed(queries, n_queries, *params, programs, n_filters, filter_of_query, ticket_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_wait_routed(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,
+                                           uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method,
+                                           uint64_t *out_matching, uint32_t *n_retried_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (idx->is_maxsim_ticket(ticket))
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "ticket %llu belongs to nidx_gpu_vector_search_maxsim_wait", (unsigned long long)ticket);
+    return idx->pipeline_wait(ticket, out_segment, out_paragraph, out_vector, out_score, out_count, n_retried_out, out_method, out_matching);
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_search_maxsim_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,

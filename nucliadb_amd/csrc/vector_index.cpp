@@ -89,6 +89,20 @@ bool use_hnsw(uint64_t total_nodes, uint64_t matching_nodes, uint64_t top_k, boo
     return hnsw_cost < bf_cost;
 }
 
+// hnsw_cost does not grow with matching_nodes (its only term that depends on it is floor(k * M * total / matching)) and bf_cost grows
+// strictly, so use_hnsw turns from false to true once over [1, total]: the first such matching by bisection over use_hnsw itself — a
+// device that compares against it decides as the host does, without a logf of its own.
+uint64_t use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, bool has_rabitq) {
+    if (total_nodes == 0 || !use_hnsw(total_nodes, total_nodes, top_k, has_rabitq)) return UINT64_MAX;
+    uint64_t lo = 1, hi = total_nodes;   // use_hnsw holds at hi
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (use_hnsw(total_nodes, mid, top_k, has_rabitq)) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 // ---- utils::normalize_vector (utils.rs:20-23): f32 fold of x.powi(2), then x / sqrt ---------------
 void normalize_row(const float *in, float *out, uint32_t d) {
     float acc = 0.0f;
@@ -2005,6 +2019,114 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     return fssc_merge(nq, p, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
 }
 
+// ---- the same batch routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async): what the host decides -----------
+// search_per_query's checks in its order (same codes, same messages), then whether the routed path takes the batch, then the filter
+// stage laid out as search_per_query_chunk lays out a chunk's — the batch is one chunk here, or it falls back.
+int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                                 const uint32_t *filter_of_query, RoutedPlan &plan) {
+    std::lock_guard<std::mutex> lock(mu);
+    const uint32_t k = p.k;
+    const size_t S = segs.size();
+    if (nq == 0 || k == 0 || S == 0) {
+        plan.nothing = true;
+        return NIDX_OK;
+    }
+    if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
+    if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
+    if (p.method == NIDX_METHOD_BRUTE_FORCE_MFMA || p.method == NIDX_METHOD_BRUTE_FORCE_BF16)
+        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
+    if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
+    if (filter_of_query)
+        for (uint32_t q = 0; q < nq; q++)
+            if (filter_of_query[q] != UINT32_MAX && filter_of_query[q] >= n_filters)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u names filter %u of %u", q, filter_of_query[q], n_filters);
+    std::vector<uint64_t> cost(n_filters, 0);
+    bool deep = false;
+    for (uint32_t f = 0; f < n_filters; f++) {
+        char who[32];
+        snprintf(who, sizeof(who), "filter %u", f);
+        for (size_t s = 0; s < S; s++) {
+            uint32_t n_operands = 0;
+            bool dp = false;
+            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp);
+            if (rc != NIDX_OK) return rc;
+            deep = deep || dp;
+            cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
+        }
+    }
+    // ---- what the routed path leaves to the blocking one (decided before anything is queued) ----
+    plan.fallback = deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE;
+    for (size_t s = 0; s < S && !plan.fallback; s++) {
+        const VectorSegment &seg = segs[s];
+        // (a forced walk on an index with a graphless segment: the blocking path's error depends on a count)
+        plan.fallback = rabitq_enabled(seg) || seg.vmax > 1 || (p.method == NIDX_METHOD_HNSW && !seg.has_graph);
+    }
+    if (plan.fallback) return NIDX_OK;
+    // the batch's distinct filters in order of first use: one chunk by search_per_query's rule, or the blocking path chunks it
+    std::vector<uint32_t> local(n_filters, NIDX_FILTER_ROW_NONE);
+    plan.filter_of_query.assign(nq, NIDX_FILTER_ROW_NONE);
+    uint64_t bytes = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint32_t f = filter_of_query ? filter_of_query[q] : UINT32_MAX;
+        if (f == UINT32_MAX) continue;
+        if (local[f] == NIDX_FILTER_ROW_NONE) {
+            if (q > 0 && (bytes + cost[f] > pq_scratch_cap || plan.filters.size() == kPqMaxFilters)) {
+                plan.fallback = true;
+                return NIDX_OK;
+            }
+            bytes += cost[f];
+            local[f] = (uint32_t)plan.filters.size();
+            plan.filters.push_back(f);
+        }
+        plan.filter_of_query[q] = local[f];
+    }
+    const uint32_t F = (uint32_t)plan.filters.size();
+    plan.at_ops.assign(S, 0), plan.at_first.assign(S, 0), plan.at_work.assign(S, 0), plan.tab_off.assign(S, 0);
+    plan.n_work.assign(S, 0), plan.n_opnd.assign(S, 0), plan.any_prog.assign(S, 0);
+    plan.has_program.assign(S * (size_t)F, 0);
+    plan.segs.resize(S);
+    for (size_t s = 0; s < S; s++) {
+        const VectorSegment &seg = segs[s];
+        plan.segs[s] = RouteSegDev{seg.alive_count, seg.has_graph ? use_hnsw_threshold(seg.n_paragraphs, k, false) : UINT64_MAX, seg.n,
+                                   seg.has_graph ? 1u : 0u};
+        const uint32_t words = (seg.n_paragraphs + 63) / 64;
+        std::vector<uint32_t> ops, first(F + 1, 0), work;
+        for (uint32_t lf = 0; lf < F; lf++) {
+            const nidx_gpu_filter_program_t &prog = programs[(size_t)plan.filters[lf] * S + s];
+            first[lf] = (uint32_t)ops.size();
+            if (!has_program(prog)) continue;
+            plan.any_prog[s] = 1;
+            plan.has_program[s * (size_t)F + lf] = 1;
+            for (uint32_t i = 0; i < prog.n_ops; i++) {
+                const nidx_gpu_filter_op_t &op = prog.ops[i];
+                if (op.op == NIDX_FILTER_PUSH_LISTS) {
+                    const uint32_t o = plan.n_opnd[s]++;
+                    for (uint32_t l = op.a; l < op.b; l++) {
+                        work.push_back(o);
+                        work.push_back(prog.lists[l]);
+                    }
+                    ops.push_back((uint32_t)op.op | (o << 3));
+                } else {
+                    ops.push_back((uint32_t)op.op);
+                }
+            }
+        }
+        first[F] = (uint32_t)ops.size();
+        if (!plan.any_prog[s]) continue;
+        plan.n_work[s] = (uint32_t)(work.size() / 2);
+        plan.at_ops[s] = plan.prog.size();
+        plan.prog.insert(plan.prog.end(), ops.begin(), ops.end());
+        plan.at_first[s] = plan.prog.size();
+        plan.prog.insert(plan.prog.end(), first.begin(), first.end());
+        plan.at_work[s] = plan.prog.size();
+        plan.prog.insert(plan.prog.end(), work.begin(), work.end());
+        plan.tab_off[s] = plan.tab_words;
+        plan.tab_words += (size_t)F * words;
+        plan.opnd_words = std::max(plan.opnd_words, (size_t)plan.n_opnd[s] * words);
+    }
+    return NIDX_OK;
+}
+
 // ---- the host stage of search_multi_vector (searcher.rs:373-393): nidx_gpu_vector_search_maxsim's second stage, and what finishes
 //      the queries of a batch whose first-pass hits outgrow the on-chip list of maxsim_rerank_kernel.  Under `mu`, on `stream`. ----
 int32_t VectorIndex::maxsim_host_stage(const float *d_queries, const uint64_t *qoff, uint32_t nq, const std::vector<uint32_t> *which,
@@ -2100,7 +2222,7 @@ int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
 int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
-           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER;
+           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2521,6 +2643,26 @@ int32_t nidx_gpu_vector_segment_search_device_exact(nidx_gpu_vector_index_t *ind
 
 int32_t nidx_gpu_use_hnsw(uint64_t total_nodes, uint64_t matching_nodes, uint64_t top_k, int32_t has_rabitq) try {
     return use_hnsw(total_nodes, matching_nodes, top_k, has_rabitq != 0) ? 1 : 0;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, int32_t has_rabitq, uint64_t *threshold_out) try {
+    if (!threshold_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *threshold_out = use_hnsw_threshold(total_nodes, top_k, has_rabitq != 0);
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_routed_stats(nidx_gpu_vector_index_t *index, nidx_gpu_vector_routed_stats_t *stats_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !stats_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    auto get = [&](int i) { return idx->routed_stats[i].load(std::memory_order_relaxed); };
+    stats_out->batches_routed = get(VectorIndex::RS_ROUTED);
+    stats_out->batches_fallback = get(VectorIndex::RS_FALLBACK);
+    stats_out->submit_synchronisations = get(VectorIndex::RS_SYNCS);
+    stats_out->walk_items = get(VectorIndex::RS_WALK_ITEMS);
+    stats_out->scan_items = get(VectorIndex::RS_SCAN_ITEMS);
+    stats_out->launches = get(VectorIndex::RS_LAUNCHES);
+    stats_out->batches_flagged = get(VectorIndex::RS_FLAGGED);
+    return NIDX_OK;
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_similarity(const float *x, const float *y, uint32_t n_pairs, uint32_t dimension, int32_t similarity,

@@ -98,8 +98,26 @@ struct PrefilterSearch {
     uint32_t row_of_filter(uint32_t f) const;        // the filter's resident row, kPrefilterRowAll or kPrefilterRowNone
 };
 
+// The filter stage of one batch whose distinct filters fit one chunk, as search_per_query_chunk lays it out: per segment
+// [ops][prog_first][work] in `prog`, a table of F rows and the operand rows (shared by the segments one after the other)
+struct RoutedPlan {
+    bool nothing = false;    // no query, k == 0 or no segment: every count is 0
+    bool fallback = false;   // the routed path does not take the batch: nidx_gpu_vector_search_submit_filtered_per_query answers it
+    std::vector<uint32_t> filters;           // the batch's distinct filters in order of first use
+    std::vector<uint32_t> filter_of_query;   // [nq] index into `filters`, NIDX_FILTER_ROW_NONE = unfiltered
+    std::vector<uint32_t> prog;
+    std::vector<size_t> at_ops, at_first, at_work, tab_off;   // [S]
+    std::vector<uint32_t> n_work, n_opnd;                     // [S]
+    std::vector<uint8_t> any_prog;                            // [S]
+    std::vector<uint8_t> has_program;                         // [S][F]
+    std::vector<RouteSegDev> segs;                            // [S]
+    size_t tab_words = 0, opnd_words = 0;
+};
+uint64_t use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, bool has_rabitq);
+
 struct Coalescer;
 std::shared_ptr<Coalescer> make_coalescer();
+struct SearchSlot;
 struct Pipeline;
 std::shared_ptr<Pipeline> make_pipeline();
 double trace_slow_us();  // NIDX_GPU_TRACE_SLOW_US  // coalescer.cpp
@@ -268,6 +286,18 @@ struct VectorIndex {
     int32_t check_request_programs(const nidx_gpu_filter_program_t *segment_programs);
     int32_t pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                                       uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out);
+    // the same batch queued on a pipeline slot and routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async):
+    // routed_plan makes search_per_query's checks in its order and lays out the filter stage of the batch as search_per_query_chunk does
+    // (plan.fallback: the routed path does not take the batch); pipeline_submit_routed queues it (serving.cpp)
+    int32_t routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
+                        const uint32_t *filter_of_query, RoutedPlan &plan);
+    int32_t pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
+                                   uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out);
+    int32_t routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
+                        int32_t *out_method, uint64_t *out_matching, uint32_t *n_retried_out);
+    // nidx_gpu_vector_routed_stats, in the order of nidx_gpu_vector_routed_stats_t
+    enum { RS_ROUTED, RS_FALLBACK, RS_SYNCS, RS_WALK_ITEMS, RS_SCAN_ITEMS, RS_LAUNCHES, RS_FLAGGED, RS_COUNT };
+    std::atomic<uint64_t> routed_stats[RS_COUNT] = {};
     // Fssc over per-segment result rows (nullptr = segment not searched); shared by search_host and the pipeline's wait
     int32_t fssc_merge(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const uint32_t *const *seg_vec, const float *const *seg_score,
                        const uint32_t *const *seg_count, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,
@@ -278,7 +308,7 @@ struct VectorIndex {
     int32_t pipeline_submit(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                             const uint64_t *const *segment_filters, bool blocking, uint64_t *ticket_out);
     int32_t pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
-                          uint32_t *out_count, uint32_t *n_retried_out);
+                          uint32_t *out_count, uint32_t *n_retried_out, int32_t *out_method = nullptr, uint64_t *out_matching = nullptr);
     void pipeline_config(int32_t depth, int32_t walks = -1);
     // evaluates `prog` for segment s into scratch_filter (already intersected with alive); returns |filter ∩ alive|
     // (pf: the program is filter `filter` of a prefiltered search and may hold NIDX_FILTER_PUSH_PREFILTER)

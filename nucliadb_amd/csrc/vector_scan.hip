@@ -237,6 +237,15 @@ template <int NJ, int QT, int KL, bool PQ = false>
 __global__ __launch_bounds__(256) void scan_topk_kernel(ScanArgs a) {
     scan_topk_body<NJ, QT, KL, PQ>(a);
 }
+// The scan arm of a batch routed on the device (vector_route.hip): how many queries took the arm stands in HBM, so the grid is laid
+// out for the batch's size and the tiles past *n_items return at once; the others run the per-query body over *n_items compact rows.
+template <int NJ, int QT, int KL>
+__global__ __launch_bounds__(256) void scan_topk_routed_kernel(ScanArgs a, const uint32_t *__restrict__ n_items) {
+    const uint32_t n = *n_items;   // uniform
+    if (blockIdx.y * QT >= n) return;
+    a.n_queries = n;
+    scan_topk_body<NJ, QT, KL, true>(a);
+}
 // The exact scans of SEVERAL segments in one launch (a multi-segment index under a selective filter: OpenSegment::_search routes
 // every segment to brute force, segment.rs:506-555 — a launch pair per segment was 100 launches per batch on the reference's
 // 50-segment layout): blockIdx.z names the segment, whose arguments come from a table in HBM (uniform address: scalar loads).
@@ -305,6 +314,13 @@ template <int KL>
 __global__ __launch_bounds__(256) void merge_topk_kernel(const uint64_t *__restrict__ partial, uint32_t lists_per_query, uint32_t k,
                                                          uint32_t *__restrict__ out_vec, float *__restrict__ out_score,
                                                          uint32_t *__restrict__ out_count) {
+    merge_topk_body<KL>(partial, lists_per_query, k, out_vec, out_score, out_count);
+}
+template <int KL>
+__global__ __launch_bounds__(256) void merge_topk_routed_kernel(const uint64_t *__restrict__ partial, const uint32_t *__restrict__ n_items,
+                                                                uint32_t lists_per_query, uint32_t k, uint32_t *__restrict__ out_vec,
+                                                                float *__restrict__ out_score, uint32_t *__restrict__ out_count) {
+    if (blockIdx.x >= *n_items) return;   // (the scan wrote no lists for these rows)
     merge_topk_body<KL>(partial, lists_per_query, k, out_vec, out_score, out_count);
 }
 template <int KL>
@@ -379,6 +395,57 @@ hipError_t launch_scan(ScanArgs a, uint32_t nblk, hipStream_t s) {
     if (nj <= 12) return a.filter_row ? launch_scan_nj<12, false, true>(a, nblk, s) : launch_scan_nj<12, false, false>(a, nblk, s);
     if (nj <= 16) return a.filter_row ? launch_scan_nj<16, false, true>(a, nblk, s) : launch_scan_nj<16, false, false>(a, nblk, s);
     return hipErrorInvalidValue;
+}
+
+// the shapes of launch_scan_nj, over the upper bound a.n_queries
+template <int NJ, bool WIDE>
+static hipError_t launch_scan_routed_nj(const ScanArgs &a, const uint32_t *n_items, uint32_t nblk, hipStream_t s) {
+    const uint32_t nq = a.n_queries;
+    if (a.k > 256) {
+        hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, 1, 8>), dim3(nblk, nq), dim3(256), 0, s, a, n_items);
+    } else if (a.k > 64) {
+        if (a.qt == 1) hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, 1, 4>), dim3(nblk, nq), dim3(256), 0, s, a, n_items);
+        else hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, 4, 4>), dim3(nblk, (nq + 3) / 4), dim3(256), 0, s, a, n_items);
+    } else if (a.qt == 1) {
+        hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, 1, 1>), dim3(nblk, nq), dim3(256), 0, s, a, n_items);
+    } else if (a.qt == 4 || !WIDE) {
+        hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, 4, 1>), dim3(nblk, (nq + 3) / 4), dim3(256), 0, s, a, n_items);
+    } else {
+        hipLaunchKernelGGL((scan_topk_routed_kernel<NJ, (WIDE ? 8 : 4), 1>), dim3(nblk, (nq + 7) / 8), dim3(256), 0, s, a, n_items);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_routed(ScanArgs a, const uint32_t *n_items, uint32_t nblk, hipStream_t s) {
+    if (a.k == 0 || a.k > NIDX_K_MAX || !a.filter_row || !n_items) return hipErrorInvalidValue;
+    if (a.n_queries == 0) return hipSuccess;
+    if (a.n_queries > 65535u) return hipErrorInvalidValue;   // the grid's y dimension carries the query tiles
+    a.qt = scan_query_tile(a.n_queries, a.dp, a.k);
+    int nj = (int)((a.dp + 255u) / 256u);
+    if (nj <= 1) return launch_scan_routed_nj<1, true>(a, n_items, nblk, s);
+    if (nj <= 2) return launch_scan_routed_nj<2, true>(a, n_items, nblk, s);
+    if (nj <= 3) return launch_scan_routed_nj<3, true>(a, n_items, nblk, s);
+    if (nj <= 4) return launch_scan_routed_nj<4, true>(a, n_items, nblk, s);
+    if (nj <= 6) return launch_scan_routed_nj<6, false>(a, n_items, nblk, s);
+    if (nj <= 8) return launch_scan_routed_nj<8, false>(a, n_items, nblk, s);
+    if (nj <= 12) return launch_scan_routed_nj<12, false>(a, n_items, nblk, s);
+    if (nj <= 16) return launch_scan_routed_nj<16, false>(a, n_items, nblk, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_merge_topk_routed(const uint64_t *partial, const uint32_t *n_items, uint32_t n_queries_max, uint32_t lists_per_query, uint32_t k,
+                                    uint32_t *out_vec, float *out_score, uint32_t *out_count, hipStream_t s) {
+    if (n_queries_max == 0) return hipSuccess;
+    if (k > 256)
+        hipLaunchKernelGGL(merge_topk_routed_kernel<8>, dim3(n_queries_max), dim3(256), 0, s, partial, n_items, lists_per_query, k, out_vec, out_score,
+                           out_count);
+    else if (k > 64)
+        hipLaunchKernelGGL(merge_topk_routed_kernel<4>, dim3(n_queries_max), dim3(256), 0, s, partial, n_items, lists_per_query, k, out_vec, out_score,
+                           out_count);
+    else
+        hipLaunchKernelGGL(merge_topk_routed_kernel<1>, dim3(n_queries_max), dim3(256), 0, s, partial, n_items, lists_per_query, k, out_vec, out_score,
+                           out_count);
+    return hipGetLastError();
 }
 
 // `table` (device): n_seg records that agree with `shape` (host: one of them, qt filled like launch_scan does) in dp, k, n_queries, qt;

@@ -1296,6 +1296,67 @@ class VectorSearcher:
         return out  # type: ignore[return-value]
 
 
+    def search_many_submit(self, requests: Sequence[VectorSearchRequest], prefilters=None, method: int = _lib.METHOD_AUTO):
+        """search_many as tickets: every group of requests with equal (result_per_page, min_score, with_duplicates) is queued with
+        nidx_gpu_vector_search_submit_filtered_per_query_async — filters, routing, both arms and the merge run on the device without
+        a wait — and the call returns.  search_many_wait(handle) gives search_many's responses.  Host PrefilterResults and
+        single-vector indexes only; a group counts against the index's pipeline depth until it has been waited for."""
+        requests = list(requests)
+        if self.config.vector_cardinality == VectorCardinality.Multi:
+            raise NidxGpuError(_lib.NIDX_ERR_UNSUPPORTED, "search_many_submit serves single-vector indexes")
+        prefilters = [None] * len(requests) if prefilters is None else list(prefilters)
+        if len(prefilters) != len(requests):
+            raise ValueError("one prefilter per request")
+        prefilters = [p or PrefilterResult.all() for p in prefilters]
+        d = self.config.dimension
+        groups = []
+        try:
+            for members in group_requests(requests):
+                r0 = requests[members[0]]
+                k = max(0, int(r0.result_per_page))
+                queries = np.zeros((len(members), d), dtype=np.float32)
+                for row, i in enumerate(members):
+                    v = np.asarray(requests[i].vector, dtype=np.float32).reshape(-1)
+                    if v.size != d:
+                        raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS, f"Inconsistent dimensions. Index={d} Vector={v.size}")
+                    queries[row] = v
+                uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
+                progs, _keep = self._programs_c(uniq)   # (read before submit returns)
+                foq = np.array(filter_of, dtype=np.uint32)
+                params = _lib.VectorSearchParamsC(k, float(r0.min_score), int(r0.with_duplicates), method)
+                ticket = C.c_uint64()
+                _lib.check(_lib.lib().nidx_gpu_vector_search_submit_filtered_per_query_async(
+                    self._handle, queries.ctypes.data, len(members), d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
+                    C.byref(ticket)))
+                groups.append((ticket.value, members, k))
+        except Exception:
+            for ticket, members, k in groups:   # nothing stays outstanding behind a failed submit
+                cnt = np.zeros(len(members), np.uint32)
+                _lib.lib().nidx_gpu_vector_search_wait(self._handle, ticket, None, None, None, None, cnt.ctypes.data, None)
+            raise
+        return (len(requests), groups)
+
+    def search_many_wait(self, handle) -> List[VectorSearchResponse]:
+        """The responses of a search_many_submit handle (waited for once)."""
+        n, groups = handle
+        out: List[Optional[VectorSearchResponse]] = [None] * n
+        for ticket, members, k in groups:
+            B, kk = len(members), max(1, k)
+            out_seg, out_par = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.uint32)
+            out_vec, out_score, out_count = np.zeros((B, kk), np.uint32), np.zeros((B, kk), np.float32), np.zeros(B, np.uint32)
+            _lib.check(_lib.lib().nidx_gpu_vector_search_wait(self._handle, ticket, out_seg.ctypes.data, out_par.ctypes.data, out_vec.ctypes.data,
+                                                              out_score.ctypes.data, out_count.ctypes.data, None))
+            for row, i in enumerate(members):
+                docs = []
+                for j in range(int(out_count[row])):
+                    sg = self._segments[int(out_seg[row, j])]
+                    p = int(out_par[row, j])
+                    md = sg.metadata[p]
+                    docs.append(DocumentScored(sg.keys[p], float(out_score[row, j]), md if md else None, list(sg.labels[p])))
+                out[i] = VectorSearchResponse(docs)
+        return out  # type: ignore[return-value]
+
+
 def group_requests(requests: Sequence[VectorSearchRequest]) -> List[List[int]]:
     """Indices of the requests one native batch can serve together: equal (result_per_page, min_score as f32, with_duplicates), in
     order of first appearance."""

@@ -1,0 +1,332 @@
+"""Per-query filter tickets routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async / _wait_routed): hits, scores,
+methods and matching counts equal the blocking nidx_gpu_vector_search_filtered_per_query on the same index, bit for bit — whatever the
+mix of filters and arms, the page size, the number of tickets in flight and the order they are waited for in — and the submit waits
+for nothing."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from nucliadb_amd import _lib
+from nucliadb_amd.vector import And, Literal, PrefilterResult, Similarity, VectorSearchRequest
+from test_vector_query_filters_gpu import LABELS, _assert_equal_rows, _batch, _index, _programs, _requests
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+
+
+def _stats(searcher):
+    st = _lib.VectorRoutedStatsC()
+    _lib.check(_lib.lib().nidx_gpu_vector_routed_stats(searcher._handle, C.byref(st)))
+    return {f[0]: int(getattr(st, f[0])) for f in st._fields_}
+
+
+def _delta(before, after):
+    return {n: after[n] - before[n] for n in after}
+
+
+def _submit(searcher, q, k, with_duplicates, method, progs, n_filters, foq):
+    params = _lib.VectorSearchParamsC(k, -1e30, int(with_duplicates), method)
+    ticket = C.c_uint64()
+    rc = _lib.lib().nidx_gpu_vector_search_submit_filtered_per_query_async(
+        searcher._handle, q.ctypes.data, q.shape[0], q.shape[1], C.byref(params), progs, n_filters, foq.ctypes.data, C.byref(ticket))
+    return rc, ticket.value
+
+
+def _wait(searcher, ticket, B, k, n_filters, routed=True):
+    S = len(searcher._segments)
+    out = [np.zeros((B, k), np.uint32), np.zeros((B, k), np.uint32), np.zeros((B, k), np.uint32), np.zeros((B, k), np.float32),
+           np.zeros(B, np.uint32)]
+    meth, match = np.full((B, S), -1, np.int32), np.full((max(1, n_filters), S), 77, np.uint64)
+    retried = C.c_uint32(12345)
+    if routed:
+        rc = _lib.lib().nidx_gpu_vector_search_wait_routed(searcher._handle, ticket, *[o.ctypes.data for o in out], meth.ctypes.data,
+                                                           match.ctypes.data if n_filters else None, C.byref(retried))
+    else:
+        rc = _lib.lib().nidx_gpu_vector_search_wait(searcher._handle, ticket, *[o.ctypes.data for o in out], C.byref(retried))
+    return rc, out, meth, match, retried.value
+
+
+def _assert_same(got, want, n_filters, routing=True):
+    """got = _wait(...), want = _batch(...): every row up to its count, the methods and the matching counts as uint32 views."""
+    rc, out, meth, match, _ = got
+    wrc, wout, wmeth, wmatch = want
+    assert rc == 0 and wrc == 0, _lib.last_error()
+    assert np.array_equal(out[4], wout[4])
+    for i in range(out[4].shape[0]):
+        c = int(wout[4][i])
+        for g, w in zip(out[:4], wout[:4]):
+            assert np.array_equal(g[i, :c].view(np.uint32), w[i, :c].view(np.uint32)), i
+    if routing:
+        assert np.array_equal(meth.view(np.uint32), wmeth.view(np.uint32))
+        if n_filters:
+            assert np.array_equal(match.view(np.uint32), wmatch.view(np.uint32))
+
+
+def _round_trip(searcher, q, k, with_duplicates, method, progs, F, foq):
+    want = _batch(searcher, q, k, with_duplicates, method, progs, F, foq)
+    rc, ticket = _submit(searcher, q, k, with_duplicates, method, progs, F, foq)
+    assert rc == 0, _lib.last_error()
+    got = _wait(searcher, ticket, q.shape[0], k, F)
+    _assert_same(got, want, F)
+    return got, want
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    """Three segments of 1 500 x 32 with a deletion, graphs built; shared by the tests that only search it."""
+    searcher, rids, rng = _index(Similarity.Cosine, 32, 1500, 11, delete=True)
+    yield searcher, rids, rng
+    searcher.close()
+
+
+def test_mixed_batch_equals_the_blocking_call_and_waits_for_nothing(mixed):
+    searcher, rids, rng = mixed
+    q = rng.normal(size=(42, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    d = _delta(before, _stats(searcher))
+    wmeth = want[2]
+    assert {0, _lib.METHOD_HNSW, _lib.METHOD_BRUTE_FORCE} <= set(int(x) for x in wmeth.reshape(-1))
+    # both arms within the batch on one segment at least: the walk launch and that segment's scan each get a proper subset
+    assert any(_lib.METHOD_HNSW in set(wmeth[:, s].tolist()) and _lib.METHOD_BRUTE_FORCE in set(wmeth[:, s].tolist()) for s in range(wmeth.shape[1]))
+    assert d["batches_routed"] == 1 and d["batches_fallback"] == 0 and d["batches_flagged"] == 0
+    assert d["submit_synchronisations"] == 0
+    assert d["walk_items"] == int((wmeth == _lib.METHOD_HNSW).sum()) and d["scan_items"] == int((wmeth == _lib.METHOD_BRUTE_FORCE).sum())
+    assert d["walk_items"] + d["scan_items"] == int((wmeth != 0).sum())
+    assert d["launches"] > 0
+    assert got[4] == 0   # nothing re-run
+
+
+@pytest.mark.parametrize("k,with_duplicates,method", [
+    (10, True, _lib.METHOD_AUTO), (10, False, _lib.METHOD_AUTO), (1, False, _lib.METHOD_AUTO), (300, False, _lib.METHOD_AUTO),
+    (300, True, _lib.METHOD_AUTO), (10, False, _lib.METHOD_HNSW), (10, True, _lib.METHOD_BRUTE_FORCE)])
+def test_page_sizes_duplicates_and_forced_methods(mixed, k, with_duplicates, method):
+    searcher, rids, rng = mixed
+    q = np.random.default_rng(100 + k).normal(size=(21, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q, k=k, with_duplicates=with_duplicates)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, k, with_duplicates, method, progs, F, foq)
+    d = _delta(before, _stats(searcher))
+    assert d["batches_routed"] == 1 and d["batches_fallback"] == 0
+    if method != _lib.METHOD_AUTO and not d["batches_flagged"]:
+        assert set(int(x) for x in got[2].reshape(-1)) <= {0, method}
+
+
+def test_dot_similarity():
+    searcher, rids, rng = _index(Similarity.Dot, 32, 1500, 21)
+    q = rng.normal(size=(23, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    searcher.close()
+
+
+@pytest.mark.parametrize("nq", [1, 257])
+def test_one_query_and_a_batch_past_a_route_chunk(mixed, nq):
+    searcher, rids, rng = mixed
+    q = np.random.default_rng(200 + nq).normal(size=(nq, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    if nq == 1:   # the one query filtered (kind 1 of _requests)
+        reqs = [VectorSearchRequest(**{**reqs[0].__dict__, "filtering_formula": Literal("/l/a")})]
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    if nq == 257:   # the lists cross the 256-query chunk in both arms
+        assert int((want[2] == _lib.METHOD_HNSW).sum(axis=0).max()) > 64 and int((want[2] == _lib.METHOD_BRUTE_FORCE).sum(axis=0).max()) > 64
+
+
+def test_all_unfiltered_and_all_matching_nothing(mixed):
+    searcher, rids, rng = mixed
+    q = np.random.default_rng(300).normal(size=(19, 32)).astype(np.float32)
+    plain = [VectorSearchRequest(vector=q[i].tolist(), result_per_page=10, min_score=-1e30, with_duplicates=False) for i in range(19)]
+    progs, F, foq, _keep = _programs(searcher, plain, [PrefilterResult.All] * 19)
+    assert F == 0 and set(foq.tolist()) == {NONE}
+    got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    assert int(want[1][4].min()) > 0
+    nothing = [VectorSearchRequest(**{**r.__dict__, "filtering_formula": Literal("/l/none-such")}) for r in plain]
+    progs, F, foq, _keep = _programs(searcher, nothing, [PrefilterResult.All] * 19)
+    assert F == 1
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    d = _delta(before, _stats(searcher))
+    assert int(got[1][4].sum()) == 0 and not got[2].any() and not got[3].any()   # every grid is early returns, every count 0
+    assert d["walk_items"] == 0 and d["scan_items"] == 0 and d["batches_routed"] == 1
+
+
+def test_index_without_graphs_scans_everything():
+    searcher, rids, rng = _index(Similarity.Cosine, 32, 1500, 22, hnsw=False)
+    q = rng.normal(size=(15, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    d = _delta(before, _stats(searcher))
+    assert set(int(x) for x in got[2].reshape(-1)) <= {0, _lib.METHOD_BRUTE_FORCE}
+    assert d["walk_items"] == 0 and d["scan_items"] > 0 and d["batches_routed"] == 1
+    searcher.close()
+
+
+def test_tickets_of_every_kind_in_flight_and_busy(mixed):
+    searcher, rids, rng = mixed
+    L = _lib.lib()
+    _lib.check(L.nidx_gpu_vector_set_tunable(searcher._handle, b"pipeline_depth", 5))
+    try:
+        params = _lib.VectorSearchParamsC(10, -1e30, 0, _lib.METHOD_AUTO)
+        held = []   # (ticket, B, F, want, routed ticket?)
+        for t in range(5):
+            q = np.random.default_rng(400 + t).normal(size=(14 + t, 32)).astype(np.float32)
+            reqs, pres = _requests(rids, rng, q)
+            progs, F, foq, keep = _programs(searcher, reqs, pres)
+            ticket = C.c_uint64()
+            if t == 1:     # a plain ticket: the unfiltered batch
+                no_progs, _, no_foq, _k = _programs(searcher, [VectorSearchRequest(**{**r.__dict__, "filtering_formula": None, "segment_filtering_formula": None}) for r in reqs],
+                                                    [PrefilterResult.All] * len(reqs))
+                want = _batch(searcher, q, 10, False, _lib.METHOD_AUTO, no_progs, 0, no_foq)
+                _lib.check(L.nidx_gpu_vector_search_submit(searcher._handle, q.ctypes.data, q.shape[0], 32, C.byref(params), None, C.byref(ticket)))
+                held.append((ticket.value, q.shape[0], 0, want, False))
+                continue
+            want = _batch(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+            if t == 3:     # the ticket kind that searches inside its submit
+                _lib.check(L.nidx_gpu_vector_search_submit_filtered_per_query(searcher._handle, q.ctypes.data, q.shape[0], 32, C.byref(params), progs, F,
+                                                                              foq.ctypes.data, C.byref(ticket)))
+                held.append((ticket.value, q.shape[0], F, want, False))
+                continue
+            rc, tk = _submit(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+            assert rc == 0, _lib.last_error()
+            held.append((tk, q.shape[0], F, want, True))
+        before = _stats(searcher)
+        rc, tk = _submit(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)   # a sixth
+        assert rc == _lib.NIDX_ERR_BUSY and tk == 0
+        assert _stats(searcher) == before
+        for ticket, hB, hF, hwant, routed in reversed(held):
+            got = _wait(searcher, ticket, hB, 10, hF)
+            _assert_same(got, hwant, hF, routing=routed)
+            if not routed:   # the other kinds report no routing
+                assert not got[2].any() and (not hF or not got[3].any())
+        # a ticket is waited for once
+        assert _wait(searcher, held[0][0], held[0][1], 10, held[0][2])[0] == _lib.NIDX_ERR_INVALID_ARGUMENT
+        assert _wait(searcher, held[4][0], held[4][1], 10, held[4][2], routed=False)[0] == _lib.NIDX_ERR_INVALID_ARGUMENT
+        # nidx_gpu_vector_search_wait takes a routed ticket as well
+        rc, tk = _submit(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+        assert rc == 0, _lib.last_error()
+        _assert_same(_wait(searcher, tk, q.shape[0], 10, F, routed=False), want, F, routing=False)
+    finally:
+        _lib.check(L.nidx_gpu_vector_set_tunable(searcher._handle, b"pipeline_depth", 4))
+
+
+def test_overflowed_walks_are_answered_by_the_blocking_search():
+    """The shape of test_walk_overflow_explicit_hnsw: a forced walk under a filter that leaves a handful of nodes outgrows the on-chip pool."""
+    searcher, rids, rng = _index(Similarity.Cosine, 32, 3000, 13)
+    q = rng.normal(size=(16, 32)).astype(np.float32)
+    reqs = []
+    for i in range(16):
+        f = And([Literal("/l/rare"), Literal("/l/a")]) if i % 2 else None
+        reqs.append(VectorSearchRequest(vector=q[i].tolist(), result_per_page=10, min_score=-1e30, with_duplicates=True, filtering_formula=f))
+    progs, F, foq, _keep = _programs(searcher, reqs, [PrefilterResult.All] * 16)
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, 10, True, _lib.METHOD_HNSW, progs, F, foq)
+    d = _delta(before, _stats(searcher))
+    assert got[4] > 0 and d["batches_flagged"] == 1 and d["batches_routed"] == 1
+    # the same slot again, a batch that overflows nothing: the flag words were cleared
+    plain = [VectorSearchRequest(**{**r.__dict__, "filtering_formula": None}) for r in reqs]
+    progs, F, foq, _keep = _programs(searcher, plain, [PrefilterResult.All] * 16)
+    before = _stats(searcher)
+    got, want = _round_trip(searcher, q, 10, True, _lib.METHOD_HNSW, progs, F, foq)
+    assert got[4] == 0 and _delta(before, _stats(searcher))["batches_flagged"] == 0
+    searcher.close()
+
+
+def test_fallback_deep_program():
+    """The construction of test_program_deeper_than_the_combine_stack: 40 operands pushed before they are combined."""
+    searcher, rids, rng = _index(Similarity.Cosine, 32, 1500, 20, hnsw=False)
+    q = rng.normal(size=(6, 32)).astype(np.float32)
+    shallow = [Literal("/l/a"), None, Literal("/l/b")]
+    reqs = [VectorSearchRequest(vector=q[i].tolist(), result_per_page=10, min_score=-1e30, with_duplicates=False,
+                                filtering_formula=shallow[i % 3]) for i in range(6)]
+    progs, F, foq, keep = _programs(searcher, reqs, [PrefilterResult.All] * 6)
+    S = 3
+    lists_of = [searcher._request_programs(VectorSearchRequest(filtering_formula=Literal(l)), PrefilterResult.All) for l in LABELS[:3]]
+    deep_progs = (_lib.FilterProgramC * ((F + 1) * S))()
+    for j in range(F * S):
+        deep_progs[j] = progs[j]
+    for s in range(S):
+        ids = [lp[s][1][0] for lp in lists_of]
+        lists = np.array([ids[j % 3] for j in range(40)], dtype=np.uint32)
+        ops = [(_lib.FILTER_PUSH_LISTS, j, j + 1) for j in range(40)] + [(_lib.FILTER_OR, 0, 0)] * 39
+        c_ops = (_lib.FilterOpC * len(ops))(*[_lib.FilterOpC(*o) for o in ops])
+        keep += [c_ops, lists]
+        deep_progs[F * S + s] = _lib.FilterProgramC(C.addressof(c_ops), len(ops), lists.ctypes.data, len(ops) - 39)
+    foq = foq.copy()
+    foq[4] = F
+    before = _stats(searcher)
+    want = _batch(searcher, q, 10, False, _lib.METHOD_AUTO, deep_progs, F + 1, foq)
+    rc, ticket = _submit(searcher, q, 10, False, _lib.METHOD_AUTO, deep_progs, F + 1, foq)
+    assert rc == 0, _lib.last_error()
+    _assert_same(_wait(searcher, ticket, 6, 10, F + 1), want, F + 1, routing=False)
+    d = _delta(before, _stats(searcher))
+    assert d["batches_fallback"] == 1 and d["batches_routed"] == 0
+    searcher.close()
+
+
+def test_fallback_quantized_index():
+    searcher, rids, rng = _index(Similarity.Dot, 64, 1200, 12, quantize=True)
+    q = rng.normal(size=(12, 64)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q, with_duplicates=True)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    before = _stats(searcher)
+    want = _batch(searcher, q, 10, True, _lib.METHOD_AUTO, progs, F, foq)
+    rc, ticket = _submit(searcher, q, 10, True, _lib.METHOD_AUTO, progs, F, foq)
+    assert rc == 0, _lib.last_error()
+    _assert_same(_wait(searcher, ticket, 12, 10, F), want, F, routing=False)
+    d = _delta(before, _stats(searcher))
+    assert d["batches_fallback"] == 1 and d["batches_routed"] == 0
+    searcher.close()
+
+
+def test_errors_are_the_blocking_entrys_and_take_no_slot(mixed):
+    searcher, rids, rng = mixed
+    q = np.random.default_rng(500).normal(size=(4, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    progs, F, foq, _keep = _programs(searcher, reqs, pres)
+    before = _stats(searcher)
+    bad = foq.copy()
+    bad[0] = F + 3
+    ops = (_lib.FilterOpC * 2)(_lib.FilterOpC(_lib.FILTER_PUSH_ALL, 0, 0), _lib.FilterOpC(_lib.FILTER_AND, 0, 0))
+    under = (_lib.FilterProgramC * 3)()
+    under[1] = _lib.FilterProgramC(C.addressof(ops), 2, None, 0)
+    zero = np.zeros(4, np.uint32)
+    for args in ((10, _lib.METHOD_AUTO, progs, F, bad), (10, _lib.METHOD_AUTO, under, 1, zero), (10, _lib.METHOD_BRUTE_FORCE_MFMA, progs, F, foq),
+                 (513, _lib.METHOD_AUTO, progs, F, foq)):
+        k, method, pr, nf, fq = args
+        wrc = _batch(searcher, q, k, False, method, pr, nf, fq)[0]
+        werr = _lib.last_error()
+        rc, tk = _submit(searcher, q, k, False, method, pr, nf, fq)
+        assert rc == wrc != 0 and tk == 0, args[:2]
+        assert _lib.last_error() == werr
+    assert _stats(searcher) == before
+    # no slot stayed taken: pipeline_depth submits still go through
+    tickets = []
+    for t in range(4):
+        rc, tk = _submit(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+        assert rc == 0, _lib.last_error()
+        tickets.append(tk)
+    want = _batch(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+    for tk in tickets:
+        _assert_same(_wait(searcher, tk, 4, 10, F), want, F)
+
+
+def test_search_many_submit_wait_equals_search_many(mixed):
+    searcher, rids, rng = mixed
+    q = np.random.default_rng(600).normal(size=(30, 32)).astype(np.float32)
+    reqs, pres = _requests(rids, rng, q)
+    for i in range(0, 30, 4):   # a second group: other page size
+        reqs[i] = VectorSearchRequest(**{**reqs[i].__dict__, "result_per_page": 5})
+    want = searcher.search_many(reqs, pres)
+    got = searcher.search_many_wait(searcher.search_many_submit(reqs, pres))
+    for i in range(30):
+        assert [(d.doc_id, np.float32(d.score).view(np.uint32)) for d in got[i].documents] == \
+               [(d.doc_id, np.float32(d.score).view(np.uint32)) for d in want[i].documents], i
