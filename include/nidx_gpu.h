@@ -64,6 +64,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER 128 /* nidx_gpu_prefilter_term_link_*, nidx_gpu_bm25_search_prefiltered */
 #define NIDX_FEATURE_JSON_PREFILTER 256 /* nidx_gpu_json_*, nidx_gpu_prefilter_rows_combine / _state / _read_resources */
 #define NIDX_FEATURE_VECTOR_ROUTED_TICKETS 512 /* nidx_gpu_vector_search_submit_filtered_per_query_async, nidx_gpu_vector_search_wait_routed, nidx_gpu_use_hnsw_threshold, nidx_gpu_vector_routed_stats */
+#define NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS 1024 /* nidx_gpu_vector_search_submit_prefiltered_per_query_async, nidx_gpu_vector_prefiltered_ticket_stats */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -501,6 +502,8 @@ int32_t nidx_gpu_vector_search_wait_routed(nidx_gpu_vector_index_t *index, uint6
 /* The smallest matching_nodes in [1, total_nodes] for which nidx_gpu_use_hnsw(total_nodes, matching_nodes, top_k, has_rabitq) holds —
  * it holds for every larger one too, the cost model is monotone in matching_nodes — or UINT64_MAX when it never does.  Host only. */
 int32_t nidx_gpu_use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, int32_t has_rabitq, uint64_t *threshold_out);
+/* Cumulative per index.  A batch of nidx_gpu_vector_search_submit_prefiltered_per_query_async is a routed batch through the same
+ * function and counts here as well (its projection, and the two launches of its filter stage, are among `launches`). */
 typedef struct nidx_gpu_vector_routed_stats {
     uint64_t batches_routed;            /* batches nidx_gpu_vector_search_submit_filtered_per_query_async queued on a slot */
     uint64_t batches_fallback;          /* batches it answered through nidx_gpu_vector_search_submit_filtered_per_query */
@@ -1085,6 +1088,42 @@ int32_t nidx_gpu_vector_search_prefiltered_per_query(nidx_gpu_vector_index_t *in
                                                      const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint32_t *out_segment,
                                                      uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
                                                      int32_t *out_method, uint64_t *out_matching, nidx_gpu_prefilter_search_stats_t *stats_out);
+
+/* The same batch as a ticket that waits for nothing (present when nidx_gpu_build_features() & NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS):
+ * nidx_gpu_vector_search_submit_filtered_per_query_async for programs that may hold NIDX_FILTER_PUSH_PREFILTER.  Same hits, counts,
+ * out_method and out_matching as nidx_gpu_vector_search_prefiltered_per_query, and the same errors (codes and messages), all decided
+ * before anything is queued and before a slot is taken.  Queued on the slot's stream, from scratch the slot owns: one upload (the
+ * programs, the projection's segment table and the row pointers), one memset of the operand area, ONE projection of the distinct
+ * Some rows the batch names onto every segment's operand region, the batch's filters on ALL segments in two table-driven launches
+ * (scatter, combine: the filter stage is four launches whatever the number of segments), then routing, both arms, Fssc and one
+ * transfer as the routed ticket above.  No stream or event is synchronised and nothing is read back before the wait.
+ * The ticket is waited for with nidx_gpu_vector_search_wait_routed or nidx_gpu_vector_search_wait; it takes a slot, holds the vector
+ * generation and counts against "pipeline_depth" (NIDX_ERR_BUSY when that many tickets are outstanding or a sync is pending).
+ * LIFETIMES: queries, programs, filter_of_query and prefilter_of_filter are copied before the call returns.  `link` and `rows` are NOT:
+ * the stream reads them after the call has returned, and the wait reads them again when a walk of the batch overflowed a bounded
+ * on-chip structure (the blocking search then answers the whole batch from the ticket's copies, *n_retried_out = n_queries).  The
+ * caller keeps both alive, and frees neither, until the wait of the ticket has returned.  Both may be NULL when no program holds the op.
+ * Batches the routed path does not take — a program deeper than NIDX_FILTER_STACK, filters and rows that do not fit one chunk of the
+ * filter scratch by nidx_gpu_vector_search_prefiltered_per_query's own rule, more than 65 535 queries or segments, RaBitQ, multi-vector
+ * paragraphs, a forced NIDX_METHOD_HNSW on an index with a segment without a graph — are answered inside the submit by the blocking
+ * prefiltered search and wait as a ticket of nidx_gpu_vector_search_submit_filtered_per_query does. */
+int32_t nidx_gpu_vector_search_submit_prefiltered_per_query_async(
+    nidx_gpu_vector_index_t *index, const nidx_gpu_prefilter_link_t *link, const nidx_gpu_prefilter_rows_t *rows, const float *queries,
+    uint32_t n_queries, uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *programs,
+    uint32_t n_filters, const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint64_t *ticket_out);
+/* Cumulative per index, over the batches of nidx_gpu_vector_search_submit_prefiltered_per_query_async. */
+typedef struct nidx_gpu_vector_prefiltered_ticket_stats {
+    uint64_t batches_routed;            /* batches queued on a slot */
+    uint64_t batches_fallback;          /* batches answered inside the submit by the blocking prefiltered search */
+    uint64_t batches_flagged;           /* routed batches answered by the blocking prefiltered search at wait (an overflowed walk) */
+    uint64_t submit_synchronisations;   /* stream or event synchronisations made inside routed submits */
+    uint64_t rows_projected;            /* distinct Some rows the routed batches projected */
+    uint64_t projection_launches;       /* one per routed batch that names a Some row */
+    uint64_t filter_launches;           /* memset, projection, scatter and combine of the routed batches' filter stages: <= 4 each */
+    uint64_t documents_visited;         /* set bits of the projected rows, read at wait */
+    uint64_t paragraphs_written;        /* paragraph ids ORed into operand rows, read at wait */
+} nidx_gpu_vector_prefiltered_ticket_stats_t;
+int32_t nidx_gpu_vector_prefiltered_ticket_stats(nidx_gpu_vector_index_t *index, nidx_gpu_vector_prefiltered_ticket_stats_t *stats_out);
 
 /* ---- the paragraph half of the hand-over: the same resident rows go to the paragraph search ---------------------------------------
  * The reference hands the one PrefilterResult of a request to the paragraph search as well, where Some(fields) becomes a SetQuery over

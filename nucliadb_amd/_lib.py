@@ -166,6 +166,7 @@ FEATURE_PREFILTER_HANDOVER = 64   # nidx_gpu_build_features() bit: resident pref
 FEATURE_PARAGRAPH_PREFILTER_HANDOVER = 128   # nidx_gpu_build_features() bit: the text-to-paragraph term link, nidx_gpu_bm25_search_prefiltered
 FEATURE_JSON_PREFILTER = 256   # nidx_gpu_build_features() bit: the resident JSON index, its prefilter batch, the resource link, nidx_gpu_prefilter_rows_combine
 FEATURE_VECTOR_ROUTED_TICKETS = 512   # nidx_gpu_build_features() bit: per-query filter tickets routed on the device, nidx_gpu_use_hnsw_threshold
+FEATURE_VECTOR_PREFILTERED_TICKETS = 1024   # nidx_gpu_build_features() bit: routed tickets whose programs push resident prefilter rows
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -208,6 +209,12 @@ class PrefilterLinkStatsC(C.Structure):
     """nidx_gpu_prefilter_link_stats_t"""
     _fields_ = [("linked_documents", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64), ("bm25_generation", C.c_uint64),
                 ("vector_generation", C.c_uint64)]
+
+
+class VectorPrefilteredTicketStatsC(C.Structure):
+    """nidx_gpu_vector_prefiltered_ticket_stats_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("batches_routed", "batches_fallback", "batches_flagged", "submit_synchronisations", "rows_projected",
+                                          "projection_launches", "filter_launches", "documents_visited", "paragraphs_written")]
 
 
 class PrefilterSearchStatsC(C.Structure):
@@ -483,6 +490,10 @@ SIGNATURES = {
                                                                  C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                  C.POINTER(PrefilterSearchStatsC)]),
+    "nidx_gpu_vector_search_submit_prefiltered_per_query_async": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                                              C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                                              C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_prefiltered_ticket_stats": (C.c_int32, [C.c_void_p, C.POINTER(VectorPrefilteredTicketStatsC)]),
     "nidx_gpu_json_open": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(JsonOpenStatsC)]),
     "nidx_gpu_json_close": (None, [C.c_void_p]),
     "nidx_gpu_json_resources_read": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -126,6 +126,70 @@ __global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__r
     }
 }
 
+// ---- the same two kernels over ALL segments of a batch (VectorIndex::pipeline_submit_routed with prefilter rows) --------------------
+// Every segment owns its operand region, so nothing orders the segments: blockIdx.z picks the segment's record, everything else is as
+// in the two kernels above.  A segment with fewer work items or words than the grid was sized for lets the extra blocks go.
+__global__ __launch_bounds__(256) void filter_scatter_segments_kernel(const FilterSegDev *__restrict__ segs, const uint32_t *__restrict__ prog,
+                                                                      unsigned int *__restrict__ operands32) {
+    const FilterSegDev sg = segs[blockIdx.z];
+    const uint32_t *work = prog + sg.work_first;
+    unsigned int *seg32 = operands32 + sg.operand_word * 2ull;
+    for (uint32_t w = blockIdx.y; w < sg.n_work; w += gridDim.y) {
+        unsigned int *out32 = seg32 + (size_t)work[2 * w] * sg.words * 2;
+        const uint32_t list = work[2 * w + 1];
+        const unsigned long long b = sg.list_offsets[list], e = sg.list_offsets[list + 1];
+        for (unsigned long long i = b + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < e;
+             i += (unsigned long long)gridDim.x * blockDim.x) {
+            const uint32_t id = sg.ids[i];
+            if (id < sg.n_bits) atomicOr(&out32[id >> 5], 1u << (id & 31));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void filter_combine_segments_kernel(const FilterSegDev *__restrict__ segs, const uint32_t *__restrict__ prog,
+                                                                      const uint64_t *__restrict__ operands, uint64_t *__restrict__ table,
+                                                                      unsigned long long *__restrict__ counts) {
+    const FilterSegDev sg = segs[blockIdx.z];
+    const uint32_t words = sg.words, n_bits = sg.n_bits;
+    if (blockIdx.x * blockDim.x >= words) return;   // past this segment's words (uniform per workgroup, before the barrier)
+    const uint32_t f = blockIdx.y;
+    const uint32_t o0 = prog[sg.first_first + f], o1 = prog[sg.first_first + f + 1];
+    if (o0 == o1) return;   // no program on this segment (uniform per workgroup)
+    const uint32_t *ops = prog + sg.ops_first;
+    const uint64_t *opnd = operands + sg.operand_word;
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t v = 0;
+    if (w < words) {
+        const uint64_t tail = (w == words - 1 && (n_bits & 63)) ? (1ull << (n_bits & 63)) - 1ull : ~0ull;
+        uint64_t st[NIDX_FILTER_STACK];
+        int d = 0;
+        for (uint32_t i = o0; i < o1; i++) {
+            const uint32_t op = ops[i];
+            switch (op & 7u) {
+                case NIDX_FILTER_PUSH_LISTS: st[d++] = opnd[(size_t)(op >> 3) * words + w]; break;
+                case NIDX_FILTER_PUSH_ALL: st[d++] = tail; break;
+                case NIDX_FILTER_PUSH_NONE: st[d++] = 0; break;
+                case NIDX_FILTER_AND: d--; st[d - 1] &= st[d]; break;
+                case NIDX_FILTER_OR: d--; st[d - 1] |= st[d]; break;
+                case NIDX_FILTER_NOT: st[d - 1] = ~st[d - 1] & tail; break;
+            }
+        }
+        v = st[0];
+        if (sg.alive) v &= sg.alive[w];
+        table[sg.table_word + (size_t)f * words + w] = v;
+    }
+    unsigned long long c = (unsigned long long)__popcll(v);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
+        if (t) atomicAdd(&counts[sg.count_first + f], t);
+    }
+}
+
 __global__ __launch_bounds__(64) void gather_rows_kernel(const float *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t dp,
                                                          float *__restrict__ dst) {
     const float *s = src + (size_t)idx[blockIdx.x] * dp;
@@ -173,6 +237,22 @@ hipError_t launch_filter_combine(const uint32_t *ops, const uint32_t *prog_first
     if (n_filters > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(filter_combine_kernel, dim3((words + 255) / 256, n_filters), dim3(256), 0, s, ops, prog_first, operands, alive, words,
                        n_bits, table, matching);
+    return hipGetLastError();
+}
+hipError_t launch_filter_scatter_segments(const FilterSegDev *segs, uint32_t n_segs, const uint32_t *prog, uint32_t max_work, uint64_t *operands,
+                                          hipStream_t s) {
+    if (!n_segs || !max_work) return hipSuccess;
+    if (n_segs > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_scatter_segments_kernel, dim3(64, max_work < 65535 ? max_work : 65535, n_segs), dim3(256), 0, s, segs, prog,
+                       reinterpret_cast<unsigned int *>(operands));
+    return hipGetLastError();
+}
+hipError_t launch_filter_combine_segments(const FilterSegDev *segs, uint32_t n_segs, const uint32_t *prog, uint32_t n_filters, uint32_t max_words,
+                                          const uint64_t *operands, uint64_t *table, unsigned long long *counts, hipStream_t s) {
+    if (!n_segs || !n_filters || !max_words) return hipSuccess;
+    if (n_filters > 65535 || n_segs > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filter_combine_segments_kernel, dim3((max_words + 255) / 256, n_filters, n_segs), dim3(256), 0, s, segs, prog, operands,
+                       table, counts);
     return hipGetLastError();
 }
 hipError_t launch_gather_rows(const float *src, const uint32_t *idx, uint32_t n, uint32_t dp, float *dst, hipStream_t s) {

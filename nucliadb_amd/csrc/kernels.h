@@ -435,6 +435,25 @@ hipError_t launch_filter_scatter(const unsigned long long *list_offsets, const u
 hipError_t launch_filter_combine(const uint32_t *ops, const uint32_t *prog_first, uint32_t n_filters, const uint64_t *operands,
                                  const uint64_t *alive, uint32_t words, uint32_t n_bits, uint64_t *table, unsigned long long *matching,
                                  hipStream_t s);
+// The same two launches over ALL segments of a batch, whatever their number (S): every segment owns its operand region, so nothing
+// orders them.  One record per segment; `prog` holds every segment's [ops][prog_first F + 1][work] words (the one upload of the batch).
+struct FilterSegDev {
+    const unsigned long long *list_offsets;
+    const uint32_t *ids;
+    const uint64_t *alive;             // nullptr: every paragraph is alive
+    unsigned long long operand_word;   // the segment's operand rows begin at this 64-bit word of `operands` (row o at + o * words)
+    unsigned long long table_word;     // its F table rows begin at this word of `table`
+    uint32_t work_first, n_work;       // its work items (operand row, list): prog[work_first + 2 i], prog[work_first + 2 i + 1]
+    uint32_t ops_first, first_first;   // its ops at prog + ops_first, indexed by prog[first_first + f] .. prog[first_first + f + 1]
+    uint32_t n_bits, words;            // words == 0: no program on this segment, nothing is read or written
+    uint32_t count_first;              // counts[count_first + f] += |filter f & alive|
+    uint32_t reserved;
+};
+//   scatter: grid (64, min(max_work, 65535), S)      combine: grid (ceil(max_words / 256), F, S); F, S <= 65535
+hipError_t launch_filter_scatter_segments(const FilterSegDev *segs, uint32_t n_segs, const uint32_t *prog, uint32_t max_work, uint64_t *operands,
+                                          hipStream_t s);
+hipError_t launch_filter_combine_segments(const FilterSegDev *segs, uint32_t n_segs, const uint32_t *prog, uint32_t n_filters, uint32_t max_words,
+                                          const uint64_t *operands, uint64_t *table, unsigned long long *counts, hipStream_t s);
 // ---- the prefilter hand-over (vector_prefilter.hip) ----
 // The link between text documents and the vector segments' posting lists, built per vector segment over a chunk of documents whose
 // keys sit in qb / q_off (key d followed by the child separator byte when has_sep): document d is linked to the lists whose key equals

@@ -30,6 +30,7 @@
 #include <thread>
 
 #include "host_common.h"
+#include "prefilter_handover.h"
 #include "vector_index.h"
 
 namespace nidx {
@@ -177,6 +178,13 @@ struct RoutedBatch {
     std::vector<std::vector<uint32_t>> lists;
     std::vector<uint32_t> filter_of_query;
     bool has_filter_of_query = false;
+    // a prefiltered ticket (nidx_gpu_vector_search_submit_prefiltered_per_query_async): the caller's link and rows (kept alive by the
+    // caller until the wait returns), a copy of prefilter_of_filter, and where the projection's two counters sit in the block
+    bool prefiltered = false;
+    const PrefilterLink *link = nullptr;
+    const PrefilterRows *pf_rows = nullptr;
+    std::vector<uint32_t> prefilter_of_filter;
+    bool has_prefilter_of_filter = false;
 };
 
 struct SearchSlot {
@@ -783,7 +791,7 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
 // synchronisation routing needs), the searches and the exact fallback run, and the hits wait for nidx_gpu_vector_search_wait.
 int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                                const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
-                                               uint64_t *ticket_out) {
+                                               uint64_t *ticket_out, PrefilterSearch *pf) {
     Pipeline &P = *pipe;
     uint64_t ticket = 0;
     if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
@@ -807,7 +815,7 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     const size_t kk = std::max<uint32_t>(p.k, 1);
     db->seg.resize(nq * kk), db->par.resize(nq * kk), db->vec.resize(nq * kk), db->sc.resize(nq * kk), db->cnt.resize(nq);
     const int32_t rc = search_per_query(queries, nq, p, programs, n_filters, filter_of_query, db->seg.data(), db->par.data(), db->vec.data(),
-                                        db->sc.data(), db->cnt.data(), nullptr, nullptr);
+                                        db->sc.data(), db->cnt.data(), nullptr, nullptr, pf);
     std::lock_guard<std::mutex> lk(P.mu);
     if (rc != NIDX_OK) {
         P.done.erase(ticket);
@@ -832,7 +840,7 @@ inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                             const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
-                                            uint64_t *ticket_out) {
+                                            uint64_t *ticket_out, PrefilterSearch *pf) {
     Pipeline &P = *pipe;
     if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
     struct GenHold {
@@ -840,13 +848,14 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         ~GenHold() { if (g) g->leave(); }
     } gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
     RoutedPlan plan;
-    int32_t rc = routed_plan(nq, p, programs, n_filters, filter_of_query, plan);
+    int32_t rc = routed_plan(nq, p, programs, n_filters, filter_of_query, plan, pf);
     if (rc != NIDX_OK) return rc;
     if (plan.fallback) {
         gate.leave();   // (pipeline_submit_per_query takes its own hold)
         gen_hold.g = nullptr;
-        rc = pipeline_submit_per_query(queries, nq, p, programs, n_filters, filter_of_query, ticket_out);
+        rc = pipeline_submit_per_query(queries, nq, p, programs, n_filters, filter_of_query, ticket_out, pf);
         if (rc == NIDX_OK) routed_stats[RS_FALLBACK].fetch_add(1, std::memory_order_relaxed);
+        if (rc == NIDX_OK && pf) pf_ticket_stats[PT_FALLBACK].fetch_add(1, std::memory_order_relaxed);
         return rc;
     }
     const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
@@ -907,8 +916,16 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
             rb.programs[i].ops = rb.ops[i].empty() ? nullptr : rb.ops[i].data();
             rb.programs[i].lists = rb.lists[i].empty() ? nullptr : rb.lists[i].data();
         }
+        if (pf) {
+            rb.prefiltered = true;
+            rb.link = pf->link;
+            rb.pf_rows = pf->rows;
+            rb.has_prefilter_of_filter = pf->prefilter_of_filter != nullptr;
+            if (pf->prefilter_of_filter) rb.prefilter_of_filter.assign(pf->prefilter_of_filter, pf->prefilter_of_filter + n_filters);
+        }
     }
-    uint64_t launches = 0;
+    uint64_t launches = 0, filter_launches = 0;
+    const uint32_t D = (uint32_t)plan.pf_rows.size();
     if (!plan.nothing) {
         // ---- queries -> HBM through the slot's pinned staging ----
         NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
@@ -921,7 +938,8 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         sl.merged = !(S == 1 && segs[0].key_ids.empty()) && !big_dedup && !getenv("NIDX_GPU_FSSC_HOST");
         const size_t fw = flag_words(S), mw = sl.merged ? merged_words(nq, k) : 0, sw = seg_words(nq, k);
         const size_t at_method = fw + mw, at_nh = at_method + (size_t)nq * S, at_ns = at_nh + S, at_match = (at_ns + S + 1) & ~(size_t)1;
-        const size_t rw = at_match + (size_t)F * S * 2 - at_method, words = fw + mw + rw + S * sw;
+        // (a prefiltered batch: the projection's two counters behind the matching counts, 8-byte aligned as they are)
+        const size_t at_pf = at_match + (size_t)F * S * 2, rw = at_pf + (pf ? 4 : 0) - at_method, words = fw + mw + rw + S * sw;
         sl.mw = mw;
         sl.rw = rw;
         sl.dirty = true;   // from here on work is queued on the slot's stream: an error path must drain it (SlotRelease)
@@ -933,8 +951,10 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         NIDX_HIP(sl.pin_out.reserve(words * 4));
         uint32_t *blk = sl.d_block.as<uint32_t>();
         // ---- one upload: [segment records | program words | the queries' filters | has-program bytes] ----
+        // (a prefiltered batch adds [filter-stage records | projection records | row pointers])
         const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + plan.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
-                     in_bytes = at_has + S * (size_t)F;
+                     at_fseg = align8(at_has + S * (size_t)F), at_pseg = at_fseg + S * sizeof(FilterSegDev),
+                     at_rows = at_pseg + S * sizeof(PrefilterProjSeg), in_bytes = pf ? at_rows + D * sizeof(uint64_t *) : at_has + S * (size_t)F;
         NIDX_HIP(sl.pin_rt_in.reserve(in_bytes));
         NIDX_HIP(sl.d_rt_in.reserve(in_bytes));
         {
@@ -943,6 +963,12 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
             if (!plan.prog.empty()) memcpy(h + at_prog, plan.prog.data(), plan.prog.size() * 4);
             memcpy(h + at_foq, plan.filter_of_query.data(), (size_t)nq * 4);
             if (!plan.has_program.empty()) memcpy(h + at_has, plan.has_program.data(), plan.has_program.size());
+            if (pf) {
+                memcpy(h + at_fseg, plan.filter_segs.data(), S * sizeof(FilterSegDev));
+                memcpy(h + at_pseg, plan.proj_segs.data(), S * sizeof(PrefilterProjSeg));
+                const uint64_t **hr = reinterpret_cast<const uint64_t **>(h + at_rows);
+                for (uint32_t j = 0; j < D; j++) hr[j] = pf->rows->row_ptr[plan.pf_rows[j]];
+            }
         }
         NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in_bytes, hipMemcpyHostToDevice, sl.stream));
         const unsigned char *din = sl.d_rt_in.as<unsigned char>();
@@ -971,8 +997,33 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         {
             // launches read index state (tunables): under the index lock, held for the launch calls only
             std::lock_guard<std::mutex> lock(mu);
+            if (pf) {
+                // ---- the filters of the batch on ALL segments: every segment owns its operand region [D projected rows | its list
+                // operands], so one memset, one projection, one scatter and one combine serve them all.  The per-segment rows are
+                // cleared here already (see below), together with the projection's counters in front of them ----
+                NIDX_HIP(hipMemsetAsync(blk + at_pf, 0, (4 + S * sw) * 4, sl.stream));
+                const uint32_t n_words = D ? (uint32_t)pf->rows->layout.words() : 0;
+                if (plan.opnd_words) {
+                    NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, plan.opnd_words * 8, sl.stream));
+                    filter_launches++;
+                }
+                if (D && n_words) {
+                    NIDX_HIP(launch_prefilter_project(reinterpret_cast<const uint64_t *const *>(din + at_rows), D, n_words, pf->link->doc_off.as<uint32_t>(),
+                                                      pf->link->entries.as<uint2>(), reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg),
+                                                      sl.d_rt_operands.as<uint64_t>(), reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
+                    pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
+                    filter_launches++, launches++;
+                }
+                pf_ticket_stats[PT_ROWS].fetch_add(D, std::memory_order_relaxed);
+                const FilterSegDev *dseg = reinterpret_cast<const FilterSegDev *>(din + at_fseg);
+                NIDX_HIP(launch_filter_scatter_segments(dseg, (uint32_t)S, dprog, plan.max_work, sl.d_rt_operands.as<uint64_t>(), sl.stream));
+                NIDX_HIP(launch_filter_combine_segments(dseg, (uint32_t)S, dprog, F, plan.max_words, sl.d_rt_operands.as<uint64_t>(),
+                                                        sl.d_rt_table.as<uint64_t>(), sl.d_rt_count.as<unsigned long long>(), sl.stream));
+                const uint32_t n = (plan.max_work ? 1 : 0) + (F && plan.max_words ? 1 : 0);
+                filter_launches += n, launches += n;
+            }
             // ---- the filters of the batch on every segment: the operand rows are the segments' one after the other, in stream order ----
-            for (size_t s = 0; s < S; s++) {
+            for (size_t s = 0; s < S && !pf; s++) {
                 if (!plan.any_prog[s]) continue;
                 VectorSegment &seg = segs[s];
                 const uint32_t n_bits = seg.n_paragraphs, fwords = (n_bits + 63) / 64;
@@ -1000,7 +1051,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
             NIDX_HIP(launch_route(ra, sl.stream));
             launches++;
             // ---- per-segment rows, as pipeline_submit lays them out; a (query, segment) no arm takes keeps the cleared count ----
-            NIDX_HIP(hipMemsetAsync(blk + fw + mw + rw, 0, S * sw * 4, sl.stream));
+            if (!pf) NIDX_HIP(hipMemsetAsync(blk + fw + mw + rw, 0, S * sw * 4, sl.stream));
             const uint32_t walks = nq * (uint32_t)std::min<size_t>(S, 64);   // the launch shape follows the grid's upper bound
             int shape_seg = -1;
             uint32_t nblk = 1;
@@ -1100,6 +1151,10 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
     }
     routed_stats[RS_ROUTED].fetch_add(1, std::memory_order_relaxed);
     routed_stats[RS_LAUNCHES].fetch_add(launches, std::memory_order_relaxed);
+    if (pf) {
+        pf_ticket_stats[PT_ROUTED].fetch_add(1, std::memory_order_relaxed);
+        pf_ticket_stats[PT_FILTER_LAUNCHES].fetch_add(filter_launches, std::memory_order_relaxed);
+    }
     *ticket_out = sl.ticket;
     release.slot = nullptr;   // the ticket owns the slot until it is waited for
     gen_hold.g = nullptr;     // ... and its hold on the generation
@@ -1125,6 +1180,16 @@ int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t
     }
     routed_stats[RS_WALK_ITEMS].fetch_add(walk_items, std::memory_order_relaxed);
     routed_stats[RS_SCAN_ITEMS].fetch_add(scan_items, std::memory_order_relaxed);
+    PrefilterSearch pf;
+    if (rb.prefiltered) {
+        const uint64_t *c = reinterpret_cast<const uint64_t *>(host + at_match + (size_t)F * S * 2);   // the projection's counters
+        pf_ticket_stats[PT_DOCUMENTS].fetch_add(c[0], std::memory_order_relaxed);
+        pf_ticket_stats[PT_PARAGRAPHS].fetch_add(c[1], std::memory_order_relaxed);
+        pf.link = rb.link;
+        pf.rows = rb.pf_rows;
+        pf.prefilter_of_filter = rb.has_prefilter_of_filter ? rb.prefilter_of_filter.data() : nullptr;
+        if (flagged) pf_ticket_stats[PT_FLAGGED].fetch_add(1, std::memory_order_relaxed);
+    }
     if (flagged) {
         // A walk overflowed a bounded on-chip structure: the blocking search answers the whole batch from the ticket's copies (it
         // repairs spills query by query), and the flag words are zero again before anybody else takes the slot
@@ -1144,7 +1209,7 @@ int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t
         }
         if (n_retried_out) *n_retried_out = nq;
         return search_per_query(rows, nq, sl.params, rb.programs.data(), rb.n_filters, rb.has_filter_of_query ? rb.filter_of_query.data() : nullptr,
-                                out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching);
+                                out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching, rb.prefiltered ? &pf : nullptr);
     }
     sl.dirty = false;   // everything queued has completed and no flag word is set
     if (out_method) memcpy(out_method, host + at_method, (size_t)nq * S * 4);
@@ -1401,6 +1466,38 @@ int32_t nidx_gpu_vector_search_submit_filtered_per_query_async(nidx_gpu_vector_i
     if (query_dimension != idx->cfg.dimension)
         return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
     return idx->pipeline_submit_routed(queries, n_queries, *params, programs, n_filters, filter_of_query, ticket_out);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_search_submit_prefiltered_per_query_async(
+    nidx_gpu_vector_index_t *index, const nidx_gpu_prefilter_link_t *link, const nidx_gpu_prefilter_rows_t *rows, const float *queries,
+    uint32_t n_queries, uint32_t query_dimension, const nidx_gpu_vector_search_params_t *params, const nidx_gpu_filter_program_t *programs,
+    uint32_t n_filters, const uint32_t *prefilter_of_filter, const uint32_t *filter_of_query, uint64_t *ticket_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !params || !ticket_out || (n_queries && !queries)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    if (query_dimension != idx->cfg.dimension)
+        return fail(NIDX_ERR_INCONSISTENT_DIMENSIONS, "Inconsistent dimensions. Index=%u Vector=%u", idx->cfg.dimension, query_dimension);
+    PrefilterSearch pf;
+    pf.link = reinterpret_cast<const PrefilterLink *>(link);
+    pf.rows = reinterpret_cast<const PrefilterRows *>(rows);
+    pf.prefilter_of_filter = prefilter_of_filter;
+    return idx->pipeline_submit_routed(queries, n_queries, *params, programs, n_filters, filter_of_query, ticket_out, &pf);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_prefiltered_ticket_stats(nidx_gpu_vector_index_t *index, nidx_gpu_vector_prefiltered_ticket_stats_t *stats_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx || !stats_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    auto get = [&](int i) { return idx->pf_ticket_stats[i].load(std::memory_order_relaxed); };
+    stats_out->batches_routed = get(VectorIndex::PT_ROUTED);
+    stats_out->batches_fallback = get(VectorIndex::PT_FALLBACK);
+    stats_out->batches_flagged = get(VectorIndex::PT_FLAGGED);
+    stats_out->submit_synchronisations = get(VectorIndex::PT_SYNCS);
+    stats_out->rows_projected = get(VectorIndex::PT_ROWS);
+    stats_out->projection_launches = get(VectorIndex::PT_PROJECTIONS);
+    stats_out->filter_launches = get(VectorIndex::PT_FILTER_LAUNCHES);
+    stats_out->documents_visited = get(VectorIndex::PT_DOCUMENTS);
+    stats_out->paragraphs_written = get(VectorIndex::PT_PARAGRAPHS);
+    return NIDX_OK;
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_vector_search_wait_routed(nidx_gpu_vector_index_t *index, uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph,

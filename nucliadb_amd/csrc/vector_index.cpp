@@ -1664,6 +1664,49 @@ int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *seg
     return NIDX_OK;
 }
 
+// The prefilter hand-over's checks: everything about the link, the rows and the filters' requests, before any output is written (the
+// blocking search) or anything is queued (the ticket).  Under mu.
+int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters, uint64_t &pf_row_cost) {
+    const size_t S = segs.size();
+    if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
+    if ((pf.link == nullptr) != (pf.rows == nullptr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "a link without rows, or rows without a link");
+    if (pf.link) {
+        const PrefilterLink &lk = *pf.link;
+        if (lk.device != device || pf.rows->device != device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link, the rows and the index are on different devices");
+        if (lk.vector_generation != gate.generation.load() || lk.n_vector_segments != S)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the vector index, which is in generation %llu (build it again)",
+                        (unsigned long long)lk.vector_generation, (unsigned long long)gate.generation.load());
+        for (size_t s = 0; s < S; s++)
+            if (lk.segment_lists[s] != segs[s].f_n_lists)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: segment %zu had %u posting lists when it was built, now %u (build it again)", s,
+                            lk.segment_lists[s], segs[s].f_n_lists);
+        if (pf.rows->generation != lk.bm25_generation || !(pf.rows->layout == lk.layout))
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the text index, the rows are of generation %llu (build it again)",
+                        (unsigned long long)lk.bm25_generation, (unsigned long long)pf.rows->generation);
+    }
+    pf.has_op.assign((size_t)n_filters * S, 0);
+    for (uint32_t f = 0; f < n_filters; f++) {
+        char who[32];
+        snprintf(who, sizeof(who), "filter %u", f);
+        const uint32_t r = pf.prefilter_of_filter ? pf.prefilter_of_filter[f] : UINT32_MAX;
+        if (r != UINT32_MAX && (!pf.rows || r >= pf.rows->row_of_request.size()))
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u of %zu", f, r, pf.rows ? pf.rows->row_of_request.size() : (size_t)0);
+        if (r != UINT32_MAX && pf.rows->has_resources(r))   // (projecting resource rows needs a resource-to-lists link: DESIGN.md §8 item 5)
+            return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
+        for (size_t s = 0; s < S; s++) {
+            uint32_t n_operands = 0, n_pf = 0;
+            bool dp = false;
+            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, &n_pf);
+            if (rc != NIDX_OK) return rc;
+            if (n_pf && r == UINT32_MAX)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u, segment %zu: NIDX_FILTER_PUSH_PREFILTER in a filter without a prefilter request", f, s);
+            pf.has_op[(size_t)f * S + s] = n_pf ? 1 : 0;
+        }
+    }
+    for (size_t s = 0; s < S; s++) pf_row_cost += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8;
+    return NIDX_OK;
+}
+
 int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                       const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
                                       uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
@@ -1675,42 +1718,8 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
     // the prefilter hand-over: everything about the link, the rows and the filters' requests is checked before any output is written
     uint64_t pf_row_cost = 0;   // a projected row's operand rows: one on every segment
     if (pf) {
-        if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
-        if ((pf->link == nullptr) != (pf->rows == nullptr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "a link without rows, or rows without a link");
-        if (pf->link) {
-            const PrefilterLink &lk = *pf->link;
-            if (lk.device != device || pf->rows->device != device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link, the rows and the index are on different devices");
-            if (lk.vector_generation != gate.generation.load() || lk.n_vector_segments != S)
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the vector index, which is in generation %llu (build it again)",
-                            (unsigned long long)lk.vector_generation, (unsigned long long)gate.generation.load());
-            for (size_t s = 0; s < S; s++)
-                if (lk.segment_lists[s] != segs[s].f_n_lists)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: segment %zu had %u posting lists when it was built, now %u (build it again)", s,
-                                lk.segment_lists[s], segs[s].f_n_lists);
-            if (pf->rows->generation != lk.bm25_generation || !(pf->rows->layout == lk.layout))
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the text index, the rows are of generation %llu (build it again)",
-                            (unsigned long long)lk.bm25_generation, (unsigned long long)pf->rows->generation);
-        }
-        pf->has_op.assign((size_t)n_filters * S, 0);
-        for (uint32_t f = 0; f < n_filters; f++) {
-            char who[32];
-            snprintf(who, sizeof(who), "filter %u", f);
-            const uint32_t r = pf->prefilter_of_filter ? pf->prefilter_of_filter[f] : UINT32_MAX;
-            if (r != UINT32_MAX && (!pf->rows || r >= pf->rows->row_of_request.size()))
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u of %zu", f, r, pf->rows ? pf->rows->row_of_request.size() : (size_t)0);
-            if (r != UINT32_MAX && pf->rows->has_resources(r))   // (projecting resource rows needs a resource-to-lists link: DESIGN.md §8 item 5)
-                return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
-            for (size_t s = 0; s < S; s++) {
-                uint32_t n_operands = 0, n_pf = 0;
-                bool dp = false;
-                const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, &n_pf);
-                if (rc != NIDX_OK) return rc;
-                if (n_pf && r == UINT32_MAX)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u, segment %zu: NIDX_FILTER_PUSH_PREFILTER in a filter without a prefilter request", f, s);
-                pf->has_op[(size_t)f * S + s] = n_pf ? 1 : 0;
-            }
-        }
-        for (size_t s = 0; s < S; s++) pf_row_cost += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8;
+        const int32_t rc = check_prefilter(*pf, programs, n_filters, pf_row_cost);
+        if (rc != NIDX_OK) return rc;
         NIDX_HIP(scratch_pf_stats.reserve(16));
     }
     for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
@@ -2023,10 +2032,16 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
 // search_per_query's checks in its order (same codes, same messages), then whether the routed path takes the batch, then the filter
 // stage laid out as search_per_query_chunk lays out a chunk's — the batch is one chunk here, or it falls back.
 int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
-                                 const uint32_t *filter_of_query, RoutedPlan &plan) {
+                                 const uint32_t *filter_of_query, RoutedPlan &plan, PrefilterSearch *pf) {
     std::lock_guard<std::mutex> lock(mu);
     const uint32_t k = p.k;
     const size_t S = segs.size();
+    uint64_t pf_row_cost = 0;
+    if (pf) {   // (before everything else, as search_per_query checks)
+        const int32_t rc = check_prefilter(*pf, programs, n_filters, pf_row_cost);
+        if (rc != NIDX_OK) return rc;
+        plan.prefiltered = true;
+    }
     if (nq == 0 || k == 0 || S == 0) {
         plan.nothing = true;
         return NIDX_OK;
@@ -2048,14 +2063,16 @@ int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_param
         for (size_t s = 0; s < S; s++) {
             uint32_t n_operands = 0;
             bool dp = false;
-            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp);
+            uint32_t n_pf = 0;
+            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, pf ? &n_pf : nullptr);
             if (rc != NIDX_OK) return rc;
             deep = deep || dp;
             cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
         }
     }
     // ---- what the routed path leaves to the blocking one (decided before anything is queued) ----
-    plan.fallback = deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE;
+    plan.fallback = deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE ||
+                    (pf && S > 65535u);   // (the segment is a grid dimension of the table-driven filter stage)
     for (size_t s = 0; s < S && !plan.fallback; s++) {
         const VectorSegment &seg = segs[s];
         // (a forced walk on an index with a graphless segment: the blocking path's error depends on a count)
@@ -2066,23 +2083,44 @@ int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_param
     std::vector<uint32_t> local(n_filters, NIDX_FILTER_ROW_NONE);
     plan.filter_of_query.assign(nq, NIDX_FILTER_ROW_NONE);
     uint64_t bytes = 0;
+    // the Some row a filter's programs push (kPrefilterRowNone: none; All and None rows are no rows), and its slot among the batch's
+    std::unordered_map<uint32_t, uint32_t> pf_slot;
+    auto projected_row = [&](uint32_t f) -> uint32_t {
+        if (!pf) return kPrefilterRowNone;
+        bool named = false;
+        for (size_t s = 0; s < S; s++) named = named || pf->has_op[(size_t)f * S + s];
+        const uint32_t row = named ? pf->row_of_filter(f) : kPrefilterRowNone;
+        return row == kPrefilterRowAll ? kPrefilterRowNone : row;
+    };
     for (uint32_t q = 0; q < nq; q++) {
         const uint32_t f = filter_of_query ? filter_of_query[q] : UINT32_MAX;
         if (f == UINT32_MAX) continue;
         if (local[f] == NIDX_FILTER_ROW_NONE) {
-            if (q > 0 && (bytes + cost[f] > pq_scratch_cap || plan.filters.size() == kPqMaxFilters)) {
+            const uint32_t row = projected_row(f);
+            const bool new_row = row != kPrefilterRowNone && !pf_slot.count(row);
+            const uint64_t add = cost[f] + (new_row ? pf_row_cost : 0);   // (a row costs once per chunk)
+            if (q > 0 && (bytes + add > pq_scratch_cap || plan.filters.size() == kPqMaxFilters)) {
                 plan.fallback = true;
                 return NIDX_OK;
             }
-            bytes += cost[f];
+            bytes += add;
             local[f] = (uint32_t)plan.filters.size();
             plan.filters.push_back(f);
+            if (new_row) {
+                pf_slot.emplace(row, (uint32_t)plan.pf_rows.size());
+                plan.pf_rows.push_back(row);
+            }
         }
         plan.filter_of_query[q] = local[f];
     }
-    const uint32_t F = (uint32_t)plan.filters.size();
+    const uint32_t F = (uint32_t)plan.filters.size(), D = (uint32_t)plan.pf_rows.size();
     plan.at_ops.assign(S, 0), plan.at_first.assign(S, 0), plan.at_work.assign(S, 0), plan.tab_off.assign(S, 0);
-    plan.n_work.assign(S, 0), plan.n_opnd.assign(S, 0), plan.any_prog.assign(S, 0);
+    plan.n_work.assign(S, 0), plan.n_opnd.assign(S, D), plan.any_prog.assign(S, 0);
+    if (pf) {
+        plan.opnd_off.assign(S, 0);
+        plan.proj_segs.resize(S);
+        plan.filter_segs.resize(S);
+    }
     plan.has_program.assign(S * (size_t)F, 0);
     plan.segs.resize(S);
     for (size_t s = 0; s < S; s++) {
@@ -2106,12 +2144,21 @@ int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_param
                         work.push_back(prog.lists[l]);
                     }
                     ops.push_back((uint32_t)op.op | (o << 3));
+                } else if (op.op == NIDX_FILTER_PUSH_PREFILTER) {   // an operand row like any other for the combine kernel
+                    const uint32_t row = pf->row_of_filter(plan.filters[lf]);
+                    if (row == kPrefilterRowAll) ops.push_back((uint32_t)NIDX_FILTER_PUSH_ALL);
+                    else if (row == kPrefilterRowNone) ops.push_back((uint32_t)NIDX_FILTER_PUSH_NONE);
+                    else ops.push_back((uint32_t)NIDX_FILTER_PUSH_LISTS | (pf_slot.at(row) << 3));
                 } else {
                     ops.push_back((uint32_t)op.op);
                 }
             }
         }
         first[F] = (uint32_t)ops.size();
+        if (pf) {
+            plan.proj_segs[s] = PrefilterProjSeg{seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), ~0ull, words, seg.n_paragraphs};
+            plan.filter_segs[s] = FilterSegDev{};   // (words == 0: the launches pass the segment by)
+        }
         if (!plan.any_prog[s]) continue;
         plan.n_work[s] = (uint32_t)(work.size() / 2);
         plan.at_ops[s] = plan.prog.size();
@@ -2122,7 +2169,25 @@ int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_param
         plan.prog.insert(plan.prog.end(), work.begin(), work.end());
         plan.tab_off[s] = plan.tab_words;
         plan.tab_words += (size_t)F * words;
-        plan.opnd_words = std::max(plan.opnd_words, (size_t)plan.n_opnd[s] * words);
+        if (!pf) {
+            plan.opnd_words = std::max(plan.opnd_words, (size_t)plan.n_opnd[s] * words);
+            continue;
+        }
+        plan.opnd_off[s] = plan.opnd_words;
+        plan.opnd_words += (size_t)plan.n_opnd[s] * words;
+        if (D && words && seg.f_n_lists && seg.f_offsets.p) plan.proj_segs[s].out_word = plan.opnd_off[s];   // (project_prefilter_rows' rule)
+        FilterSegDev &fs = plan.filter_segs[s];
+        fs.list_offsets = seg.f_offsets.as<unsigned long long>();
+        fs.ids = seg.f_ids.as<uint32_t>();
+        fs.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
+        fs.operand_word = plan.opnd_off[s];
+        fs.table_word = plan.tab_off[s];
+        fs.work_first = (uint32_t)plan.at_work[s], fs.n_work = plan.n_work[s];
+        fs.ops_first = (uint32_t)plan.at_ops[s], fs.first_first = (uint32_t)plan.at_first[s];
+        fs.n_bits = seg.n_paragraphs, fs.words = words;
+        fs.count_first = (uint32_t)(s * F);
+        plan.max_work = std::max(plan.max_work, plan.n_work[s]);
+        plan.max_words = std::max(plan.max_words, words);
     }
     return NIDX_OK;
 }
@@ -2222,7 +2287,8 @@ int32_t nidx_gpu_abi_version(void) { return NIDX_GPU_ABI_VERSION; }
 int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
-           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS;
+           NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
+           NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {

@@ -112,6 +112,14 @@ struct RoutedPlan {
     std::vector<uint8_t> has_program;                         // [S][F]
     std::vector<RouteSegDev> segs;                            // [S]
     size_t tab_words = 0, opnd_words = 0;
+    // a batch of nidx_gpu_vector_search_submit_prefiltered_per_query_async: every segment owns an operand region [D projected rows | its
+    // list operands] at word opnd_off[s] (nothing orders the segments), and the filter stage is table driven (filter_segs)
+    bool prefiltered = false;
+    std::vector<uint32_t> pf_rows;            // [D] the distinct Some rows the batch's programs push, in order of first use
+    std::vector<size_t> opnd_off;             // [S]
+    std::vector<PrefilterProjSeg> proj_segs;  // [S]
+    std::vector<FilterSegDev> filter_segs;    // [S] prog offsets relative to `prog`
+    uint32_t max_work = 0, max_words = 0;
 };
 uint64_t use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, bool has_rabitq);
 
@@ -285,19 +293,26 @@ struct VectorIndex {
     // the checks search_per_query makes of one request's [n_segments] programs (nullptr: unfiltered), before it joins a coalesced batch
     int32_t check_request_programs(const nidx_gpu_filter_program_t *segment_programs);
     int32_t pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
-                                      uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out);
+                                      uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out, PrefilterSearch *pf = nullptr);
     // the same batch queued on a pipeline slot and routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async):
     // routed_plan makes search_per_query's checks in its order and lays out the filter stage of the batch as search_per_query_chunk does
     // (plan.fallback: the routed path does not take the batch); pipeline_submit_routed queues it (serving.cpp)
+    // (pf: nidx_gpu_vector_search_submit_prefiltered_per_query_async — the checks, the chunk rule and the layout of the blocking
+    // prefiltered search, the filter stage of all segments in one launch set)
     int32_t routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
-                        const uint32_t *filter_of_query, RoutedPlan &plan);
+                        const uint32_t *filter_of_query, RoutedPlan &plan, PrefilterSearch *pf = nullptr);
     int32_t pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
-                                   uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out);
+                                   uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out, PrefilterSearch *pf = nullptr);
+    // search_per_query's checks of the link, the rows and the filters' requests (under mu); fills pf.has_op and a projected row's cost
+    int32_t check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters, uint64_t &pf_row_cost);
     int32_t routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
                         int32_t *out_method, uint64_t *out_matching, uint32_t *n_retried_out);
     // nidx_gpu_vector_routed_stats, in the order of nidx_gpu_vector_routed_stats_t
     enum { RS_ROUTED, RS_FALLBACK, RS_SYNCS, RS_WALK_ITEMS, RS_SCAN_ITEMS, RS_LAUNCHES, RS_FLAGGED, RS_COUNT };
     std::atomic<uint64_t> routed_stats[RS_COUNT] = {};
+    // nidx_gpu_vector_prefiltered_ticket_stats, in the order of nidx_gpu_vector_prefiltered_ticket_stats_t
+    enum { PT_ROUTED, PT_FALLBACK, PT_FLAGGED, PT_SYNCS, PT_ROWS, PT_PROJECTIONS, PT_FILTER_LAUNCHES, PT_DOCUMENTS, PT_PARAGRAPHS, PT_COUNT };
+    std::atomic<uint64_t> pf_ticket_stats[PT_COUNT] = {};
     // Fssc over per-segment result rows (nullptr = segment not searched); shared by search_host and the pipeline's wait
     int32_t fssc_merge(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const uint32_t *const *seg_vec, const float *const *seg_score,
                        const uint32_t *const *seg_count, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,

@@ -1296,14 +1296,24 @@ class VectorSearcher:
         return out  # type: ignore[return-value]
 
 
-    def search_many_submit(self, requests: Sequence[VectorSearchRequest], prefilters=None, method: int = _lib.METHOD_AUTO):
+    def search_many_submit(self, requests: Sequence[VectorSearchRequest], prefilters=None, method: int = _lib.METHOD_AUTO,
+                           link: Optional[PrefilterLink] = None):
         """search_many as tickets: every group of requests with equal (result_per_page, min_score, with_duplicates) is queued with
         nidx_gpu_vector_search_submit_filtered_per_query_async — filters, routing, both arms and the merge run on the device without
-        a wait — and the call returns.  search_many_wait(handle) gives search_many's responses.  Host PrefilterResults and
-        single-vector indexes only; a group counts against the index's pipeline depth until it has been waited for."""
+        a wait — and the call returns.  search_many_wait(handle) gives search_many's responses.  Single-vector indexes only; a group
+        counts against the index's pipeline depth until it has been waited for.
+
+        prefilters may be the ResidentPrefilters of TextSearcher.prefilter_batch_resident with link = self.link_text(that searcher),
+        as in search_many: the groups then go through nidx_gpu_vector_search_submit_prefiltered_per_query_async, whose stream reads
+        the rows and the link after the call has returned — the handle keeps both referenced until search_many_wait."""
         requests = list(requests)
         if self.config.vector_cardinality == VectorCardinality.Multi:
             raise NidxGpuError(_lib.NIDX_ERR_UNSUPPORTED, "search_many_submit serves single-vector indexes")
+        resident = prefilters if hasattr(prefilters, "kinds") else None
+        if resident is not None:
+            if link is None or len(resident) != len(requests):
+                raise ValueError("resident prefilters need their link and one entry per request")
+            prefilters = None
         prefilters = [None] * len(requests) if prefilters is None else list(prefilters)
         if len(prefilters) != len(requests):
             raise ValueError("one prefilter per request")
@@ -1320,25 +1330,34 @@ class VectorSearcher:
                     if v.size != d:
                         raise NidxGpuError(_lib.NIDX_ERR_INCONSISTENT_DIMENSIONS, f"Inconsistent dimensions. Index={d} Vector={v.size}")
                     queries[row] = v
-                uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
+                if resident is not None:
+                    uniq, filter_of, prefilter_of = self._resident_filters(requests, members, resident)
+                else:
+                    uniq, filter_of = dedup_programs([self._request_programs(requests[i], prefilters[i]) for i in members])
                 progs, _keep = self._programs_c(uniq)   # (read before submit returns)
                 foq = np.array(filter_of, dtype=np.uint32)
                 params = _lib.VectorSearchParamsC(k, float(r0.min_score), int(r0.with_duplicates), method)
                 ticket = C.c_uint64()
-                _lib.check(_lib.lib().nidx_gpu_vector_search_submit_filtered_per_query_async(
-                    self._handle, queries.ctypes.data, len(members), d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
-                    C.byref(ticket)))
+                if resident is not None:
+                    pof = np.array(prefilter_of + [0], dtype=np.uint32)
+                    _lib.check(_lib.lib().nidx_gpu_vector_search_submit_prefiltered_per_query_async(
+                        self._handle, link.handle, resident.handle, queries.ctypes.data, len(members), d, C.byref(params),
+                        progs if uniq else None, len(uniq), pof.ctypes.data, foq.ctypes.data, C.byref(ticket)))
+                else:
+                    _lib.check(_lib.lib().nidx_gpu_vector_search_submit_filtered_per_query_async(
+                        self._handle, queries.ctypes.data, len(members), d, C.byref(params), progs if uniq else None, len(uniq), foq.ctypes.data,
+                        C.byref(ticket)))
                 groups.append((ticket.value, members, k))
         except Exception:
             for ticket, members, k in groups:   # nothing stays outstanding behind a failed submit
                 cnt = np.zeros(len(members), np.uint32)
                 _lib.lib().nidx_gpu_vector_search_wait(self._handle, ticket, None, None, None, None, cnt.ctypes.data, None)
             raise
-        return (len(requests), groups)
+        return (len(requests), groups, (resident, link))   # (the rows and the link stay referenced until the wait)
 
     def search_many_wait(self, handle) -> List[VectorSearchResponse]:
         """The responses of a search_many_submit handle (waited for once)."""
-        n, groups = handle
+        n, groups = handle[0], handle[1]
         out: List[Optional[VectorSearchResponse]] = [None] * n
         for ticket, members, k in groups:
             B, kk = len(members), max(1, k)
