@@ -67,33 +67,30 @@ __global__ void bitset_and_count_kernel(const uint64_t *a, const uint64_t *alive
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 
-// ---- all filter programs of a batch on one segment (VectorIndex::search_per_query) ----------------------------------------------
-// work item i = (operand row, posting list): one grid row per work item, the list's postings spread over the x blocks
-__global__ void filter_scatter_kernel(const unsigned long long *__restrict__ list_offsets, const uint32_t *__restrict__ ids,
-                                      const uint32_t *__restrict__ work, uint32_t n_work, uint32_t n_bits, uint32_t words,
-                                      unsigned int *__restrict__ operands32) {
+// ---- all filter programs of a batch on one segment (filter_stage.h lays them out; VectorIndex::launch_filter_stage) ---------------
+// work item i = (operand row, posting list): one grid row per work item, the list's postings spread over the x blocks (this thread
+// takes postings first, first + stride, ... of a list; the kernels work the two out, where the compiler folds blockDim into a scalar)
+__device__ __forceinline__ void filter_scatter_items(const unsigned long long *__restrict__ list_offsets, const uint32_t *__restrict__ ids,
+                                                     const uint32_t *__restrict__ work, uint32_t n_work, uint32_t n_bits, uint32_t words,
+                                                     unsigned int *__restrict__ operands32, unsigned long long first, unsigned long long stride) {
     for (uint32_t w = blockIdx.y; w < n_work; w += gridDim.y) {
         unsigned int *out32 = operands32 + (size_t)work[2 * w] * words * 2;
         const uint32_t list = work[2 * w + 1];
         const unsigned long long b = list_offsets[list], e = list_offsets[list + 1];
-        for (unsigned long long i = b + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < e;
-             i += (unsigned long long)gridDim.x * blockDim.x) {
+        for (unsigned long long i = b + first; i < e; i += stride) {
             const uint32_t id = ids[i];
             if (id < n_bits) atomicOr(&out32[id >> 5], 1u << (id & 31));
         }
     }
 }
+#define FILTER_SCATTER_SPAN (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, (unsigned long long)gridDim.x * blockDim.x
 
-// The per-op kernels above, fused: one thread per word runs filter blockIdx.y's postfix program over its operand rows (the same tail
-// masks as bitset_fill / bitset_not), then the word & alive goes to the filter's row and its popcount to matching[f].
-__global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__restrict__ ops, const uint32_t *__restrict__ prog_first,
-                                                             const uint64_t *__restrict__ operands, const uint64_t *__restrict__ alive,
-                                                             uint32_t words, uint32_t n_bits, uint64_t *__restrict__ table,
-                                                             unsigned long long *__restrict__ matching) {
-    const uint32_t f = blockIdx.y;
-    const uint32_t o0 = prog_first[f], o1 = prog_first[f + 1];
-    if (o0 == o1) return;   // no program on this segment (uniform per workgroup)
-    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+// The per-op kernels above, fused: thread w of a segment's words runs the postfix program ops[o0 .. o1) over the operand rows (the same tail masks
+// as bitset_fill / bitset_not), then the word & alive goes to the filter's row (at word row_word of the table) and the workgroup's popcount to *count in one atomic.
+// Called by EVERY thread of a 256-thread workgroup: it holds the barrier.
+__device__ __forceinline__ void filter_combine_word(const uint32_t *__restrict__ ops, uint32_t o0, uint32_t o1, const uint64_t *__restrict__ operands,
+                                                    const uint64_t *__restrict__ alive, uint32_t w, uint32_t words, uint32_t n_bits,
+                                                    uint64_t *__restrict__ table, size_t row_word, unsigned long long *__restrict__ count) {
     uint64_t v = 0;
     if (w < words) {
         const uint64_t tail = (w == words - 1 && (n_bits & 63)) ? (1ull << (n_bits & 63)) - 1ull : ~0ull;
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__r
         }
         v = st[0];
         if (alive) v &= alive[w];
-        table[(size_t)f * words + w] = v;
+        table[row_word + w] = v;
     }
     unsigned long long c = (unsigned long long)__popcll(v);
 #pragma unroll
@@ -122,8 +119,25 @@ __global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__r
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(&matching[f], t);
+        if (t) atomicAdd(count, t);
     }
+}
+
+__global__ void filter_scatter_kernel(const unsigned long long *__restrict__ list_offsets, const uint32_t *__restrict__ ids,
+                                      const uint32_t *__restrict__ work, uint32_t n_work, uint32_t n_bits, uint32_t words,
+                                      unsigned int *__restrict__ operands32) {
+    filter_scatter_items(list_offsets, ids, work, n_work, n_bits, words, operands32, FILTER_SCATTER_SPAN);
+}
+
+// filter blockIdx.y's program on one segment -> table[f], matching[f]
+__global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__restrict__ ops, const uint32_t *__restrict__ prog_first,
+                                                             const uint64_t *__restrict__ operands, const uint64_t *__restrict__ alive,
+                                                             uint32_t words, uint32_t n_bits, uint64_t *__restrict__ table,
+                                                             unsigned long long *__restrict__ matching) {
+    const uint32_t f = blockIdx.y;
+    const uint32_t o0 = prog_first[f], o1 = prog_first[f + 1];
+    if (o0 == o1) return;   // no program on this segment (uniform per workgroup, before the barrier)
+    filter_combine_word(ops, o0, o1, operands, alive, blockIdx.x * blockDim.x + threadIdx.x, words, n_bits, table, (size_t)f * words, &matching[f]);
 }
 
 // ---- the same two kernels over ALL segments of a batch (VectorIndex::pipeline_submit_routed with prefilter rows) --------------------
@@ -132,62 +146,20 @@ __global__ __launch_bounds__(256) void filter_combine_kernel(const uint32_t *__r
 __global__ __launch_bounds__(256) void filter_scatter_segments_kernel(const FilterSegDev *__restrict__ segs, const uint32_t *__restrict__ prog,
                                                                       unsigned int *__restrict__ operands32) {
     const FilterSegDev sg = segs[blockIdx.z];
-    const uint32_t *work = prog + sg.work_first;
-    unsigned int *seg32 = operands32 + sg.operand_word * 2ull;
-    for (uint32_t w = blockIdx.y; w < sg.n_work; w += gridDim.y) {
-        unsigned int *out32 = seg32 + (size_t)work[2 * w] * sg.words * 2;
-        const uint32_t list = work[2 * w + 1];
-        const unsigned long long b = sg.list_offsets[list], e = sg.list_offsets[list + 1];
-        for (unsigned long long i = b + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < e;
-             i += (unsigned long long)gridDim.x * blockDim.x) {
-            const uint32_t id = sg.ids[i];
-            if (id < sg.n_bits) atomicOr(&out32[id >> 5], 1u << (id & 31));
-        }
-    }
+    filter_scatter_items(sg.list_offsets, sg.ids, prog + sg.work_first, sg.n_work, sg.n_bits, sg.words, operands32 + sg.operand_word * 2ull,
+                         FILTER_SCATTER_SPAN);
 }
 
 __global__ __launch_bounds__(256) void filter_combine_segments_kernel(const FilterSegDev *__restrict__ segs, const uint32_t *__restrict__ prog,
                                                                       const uint64_t *__restrict__ operands, uint64_t *__restrict__ table,
                                                                       unsigned long long *__restrict__ counts) {
     const FilterSegDev sg = segs[blockIdx.z];
-    const uint32_t words = sg.words, n_bits = sg.n_bits;
-    if (blockIdx.x * blockDim.x >= words) return;   // past this segment's words (uniform per workgroup, before the barrier)
+    if (blockIdx.x * blockDim.x >= sg.words) return;   // past this segment's words (uniform per workgroup, before the barrier)
     const uint32_t f = blockIdx.y;
     const uint32_t o0 = prog[sg.first_first + f], o1 = prog[sg.first_first + f + 1];
-    if (o0 == o1) return;   // no program on this segment (uniform per workgroup)
-    const uint32_t *ops = prog + sg.ops_first;
-    const uint64_t *opnd = operands + sg.operand_word;
-    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t v = 0;
-    if (w < words) {
-        const uint64_t tail = (w == words - 1 && (n_bits & 63)) ? (1ull << (n_bits & 63)) - 1ull : ~0ull;
-        uint64_t st[NIDX_FILTER_STACK];
-        int d = 0;
-        for (uint32_t i = o0; i < o1; i++) {
-            const uint32_t op = ops[i];
-            switch (op & 7u) {
-                case NIDX_FILTER_PUSH_LISTS: st[d++] = opnd[(size_t)(op >> 3) * words + w]; break;
-                case NIDX_FILTER_PUSH_ALL: st[d++] = tail; break;
-                case NIDX_FILTER_PUSH_NONE: st[d++] = 0; break;
-                case NIDX_FILTER_AND: d--; st[d - 1] &= st[d]; break;
-                case NIDX_FILTER_OR: d--; st[d - 1] |= st[d]; break;
-                case NIDX_FILTER_NOT: st[d - 1] = ~st[d - 1] & tail; break;
-            }
-        }
-        v = st[0];
-        if (sg.alive) v &= sg.alive[w];
-        table[sg.table_word + (size_t)f * words + w] = v;
-    }
-    unsigned long long c = (unsigned long long)__popcll(v);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-    __shared__ unsigned long long part[4];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long t = part[0] + part[1] + part[2] + part[3];
-        if (t) atomicAdd(&counts[sg.count_first + f], t);
-    }
+    if (o0 == o1) return;   // no program on this segment (uniform per workgroup, before the barrier)
+    filter_combine_word(prog + sg.ops_first, o0, o1, operands + sg.operand_word, sg.alive, blockIdx.x * blockDim.x + threadIdx.x, sg.words, sg.n_bits,
+                        table, sg.table_word + (size_t)f * sg.words, &counts[sg.count_first + f]);
 }
 
 __global__ __launch_bounds__(64) void gather_rows_kernel(const float *__restrict__ src, const uint32_t *__restrict__ idx, uint32_t dp,

@@ -860,7 +860,8 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
     }
     const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
     const size_t S = segs.size();
-    const uint32_t F = (uint32_t)plan.filters.size();
+    const FilterLayout &L = plan.layout;
+    const uint32_t F = (uint32_t)L.filters.size();
     NIDX_HIP(hipSetDevice(device));
 
     SearchSlot *slot = nullptr;
@@ -900,7 +901,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
     sl.rb.reset(new RoutedBatch());
     RoutedBatch &rb = *sl.rb;
     rb.n_filters = n_filters;
-    rb.filters = plan.filters;
+    rb.filters = L.filters;
     if (!plan.nothing) {
         if (cfg.normalize_vectors) rb.rows.assign(queries, queries + (size_t)nq * d);
         rb.has_filter_of_query = filter_of_query != nullptr;
@@ -925,7 +926,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         }
     }
     uint64_t launches = 0, filter_launches = 0;
-    const uint32_t D = (uint32_t)plan.pf_rows.size();
+    const uint32_t D = (uint32_t)L.pf_rows.size();
     if (!plan.nothing) {
         // ---- queries -> HBM through the slot's pinned staging ----
         NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
@@ -952,7 +953,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         uint32_t *blk = sl.d_block.as<uint32_t>();
         // ---- one upload: [segment records | program words | the queries' filters | has-program bytes] ----
         // (a prefiltered batch adds [filter-stage records | projection records | row pointers])
-        const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + plan.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
+        const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + L.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
                      at_fseg = align8(at_has + S * (size_t)F), at_pseg = at_fseg + S * sizeof(FilterSegDev),
                      at_rows = at_pseg + S * sizeof(PrefilterProjSeg), in_bytes = pf ? at_rows + D * sizeof(uint64_t *) : at_has + S * (size_t)F;
         NIDX_HIP(sl.pin_rt_in.reserve(in_bytes));
@@ -960,21 +961,20 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         {
             unsigned char *h = sl.pin_rt_in.as<unsigned char>();
             memcpy(h, plan.segs.data(), S * sizeof(RouteSegDev));
-            if (!plan.prog.empty()) memcpy(h + at_prog, plan.prog.data(), plan.prog.size() * 4);
-            memcpy(h + at_foq, plan.filter_of_query.data(), (size_t)nq * 4);
-            if (!plan.has_program.empty()) memcpy(h + at_has, plan.has_program.data(), plan.has_program.size());
+            if (!L.prog.empty()) memcpy(h + at_prog, L.prog.data(), L.prog.size() * 4);
+            memcpy(h + at_foq, L.filter_of_query.data(), (size_t)nq * 4);
+            if (!L.has_program.empty()) memcpy(h + at_has, L.has_program.data(), L.has_program.size());
             if (pf) {
-                memcpy(h + at_fseg, plan.filter_segs.data(), S * sizeof(FilterSegDev));
-                memcpy(h + at_pseg, plan.proj_segs.data(), S * sizeof(PrefilterProjSeg));
+                filter_stage_records(L, reinterpret_cast<FilterSegDev *>(h + at_fseg), reinterpret_cast<PrefilterProjSeg *>(h + at_pseg));
                 const uint64_t **hr = reinterpret_cast<const uint64_t **>(h + at_rows);
-                for (uint32_t j = 0; j < D; j++) hr[j] = pf->rows->row_ptr[plan.pf_rows[j]];
+                for (uint32_t j = 0; j < D; j++) hr[j] = pf->rows->row_ptr[L.pf_rows[j]];
             }
         }
         NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in_bytes, hipMemcpyHostToDevice, sl.stream));
         const unsigned char *din = sl.d_rt_in.as<unsigned char>();
         const uint32_t *dprog = reinterpret_cast<const uint32_t *>(din + at_prog);
-        NIDX_HIP(sl.d_rt_table.reserve(std::max<size_t>(plan.tab_words, 1) * 8));
-        NIDX_HIP(sl.d_rt_operands.reserve(std::max<size_t>(plan.opnd_words, 1) * 8));
+        NIDX_HIP(sl.d_rt_table.reserve(std::max<size_t>(L.tab_words, 1) * 8));
+        NIDX_HIP(sl.d_rt_operands.reserve(std::max<size_t>(L.opnd_words, 1) * 8));
         NIDX_HIP(sl.d_rt_count.reserve(std::max<size_t>(S * (size_t)F, 1) * 8));
         NIDX_HIP(hipMemsetAsync(sl.d_rt_count.p, 0, std::max<size_t>(S * (size_t)F, 1) * 8, sl.stream));
         NIDX_HIP(sl.d_rt_lists.reserve(S * (size_t)nq * 3 * 4));
@@ -1003,8 +1003,8 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
                 // cleared here already (see below), together with the projection's counters in front of them ----
                 NIDX_HIP(hipMemsetAsync(blk + at_pf, 0, (4 + S * sw) * 4, sl.stream));
                 const uint32_t n_words = D ? (uint32_t)pf->rows->layout.words() : 0;
-                if (plan.opnd_words) {
-                    NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, plan.opnd_words * 8, sl.stream));
+                if (L.opnd_words) {
+                    NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, L.opnd_words * 8, sl.stream));
                     filter_launches++;
                 }
                 if (D && n_words) {
@@ -1016,24 +1016,17 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
                 }
                 pf_ticket_stats[PT_ROWS].fetch_add(D, std::memory_order_relaxed);
                 const FilterSegDev *dseg = reinterpret_cast<const FilterSegDev *>(din + at_fseg);
-                NIDX_HIP(launch_filter_scatter_segments(dseg, (uint32_t)S, dprog, plan.max_work, sl.d_rt_operands.as<uint64_t>(), sl.stream));
-                NIDX_HIP(launch_filter_combine_segments(dseg, (uint32_t)S, dprog, F, plan.max_words, sl.d_rt_operands.as<uint64_t>(),
+                NIDX_HIP(launch_filter_scatter_segments(dseg, (uint32_t)S, dprog, L.max_work, sl.d_rt_operands.as<uint64_t>(), sl.stream));
+                NIDX_HIP(launch_filter_combine_segments(dseg, (uint32_t)S, dprog, F, L.max_words, sl.d_rt_operands.as<uint64_t>(),
                                                         sl.d_rt_table.as<uint64_t>(), sl.d_rt_count.as<unsigned long long>(), sl.stream));
-                const uint32_t n = (plan.max_work ? 1 : 0) + (F && plan.max_words ? 1 : 0);
+                const uint32_t n = (L.max_work ? 1 : 0) + (F && L.max_words ? 1 : 0);
                 filter_launches += n, launches += n;
             }
             // ---- the filters of the batch on every segment: the operand rows are the segments' one after the other, in stream order ----
-            for (size_t s = 0; s < S && !pf; s++) {
-                if (!plan.any_prog[s]) continue;
-                VectorSegment &seg = segs[s];
-                const uint32_t n_bits = seg.n_paragraphs, fwords = (n_bits + 63) / 64;
-                if (plan.n_opnd[s]) NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, (size_t)plan.n_opnd[s] * fwords * 8, sl.stream));
-                NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), dprog + plan.at_work[s], plan.n_work[s], n_bits,
-                                               fwords, sl.d_rt_operands.as<uint64_t>(), sl.stream));
-                NIDX_HIP(launch_filter_combine(dprog + plan.at_ops[s], dprog + plan.at_first[s], F, sl.d_rt_operands.as<uint64_t>(),
-                                               seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), fwords, n_bits,
-                                               sl.d_rt_table.as<uint64_t>() + plan.tab_off[s], sl.d_rt_count.as<unsigned long long>() + s * F, sl.stream));
-                launches += (plan.n_work[s] ? 1 : 0) + (F && fwords ? 1 : 0);
+            if (!pf) {
+                rc = launch_filter_stage(L, dprog, sl.d_rt_operands.as<uint64_t>(), sl.d_rt_table.as<uint64_t>(), sl.d_rt_count.as<unsigned long long>(),
+                                         sl.stream, &launches);
+                if (rc != NIDX_OK) return rc;
             }
             // ---- routing: the counts stay where the combine launches left them ----
             RouteArgs ra;
@@ -1070,7 +1063,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
                 HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, nullptr, d_vec, d_score, d_count,
                                               nullptr, vis_for(walks), blk + s);
                 ha.filter_row = d_filter_row + s * (size_t)nq;
-                ha.filter_table = plan.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + plan.tab_off[s] : nullptr;
+                ha.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
                 ha.filter_words = (seg.n_paragraphs + 63) / 64;
                 h_hnsw[s] = ha;
                 if (shape_seg < 0 && seg.has_graph && seg.n) shape_seg = (int)s;
@@ -1105,7 +1098,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
                                                  sl.d_rt_rows.as<uint32_t>(), sl.stream));
                     ScanArgs a = scan_args((uint32_t)s, sl.d_rt_queries.as<float>(), nq, k, p.min_score, nullptr);
                     a.filter_row = sl.d_rt_rows.as<uint32_t>();
-                    a.filter_table = plan.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + plan.tab_off[s] : nullptr;
+                    a.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
                     a.filter_words = (seg.n_paragraphs + 63) / 64;
                     a.partial = sl.d_bf_partial.as<uint64_t>();
                     const uint32_t sblk = scan_num_blocks(seg.n);

@@ -1565,57 +1565,32 @@ uint64_t VectorIndex::popcount_filter(uint32_t s, const uint64_t *filt) const {
 // batch are evaluated together, two launches per segment (filter.hip: launch_filter_scatter / launch_filter_combine), their
 // |filter ∩ alive| counts come back in one transfer, use_hnsw routes every (query, segment) on the host as search_host routes a
 // segment, and each arm of a segment runs once over the queries routed to it, every query testing its own filter row.
+// What touches no device — the checks, the chunks of a batch and a chunk's layout — is filter_stage.h.
 namespace {
 // filter rows + operand rows of one chunk of a batch stay under VectorIndex::pq_scratch_cap (1 GiB); a larger batch is split into chunks
 // of queries (never refused)
 constexpr size_t kPqMaxFilters = 65535;   // filters per chunk: the combine launch's grid rows
+static_assert(kFilterStack == NIDX_FILTER_STACK && kFilterNone == NIDX_FILTER_ROW_NONE && kFilterRowAll == kPrefilterRowAll &&
+                  kFilterRowNone == kPrefilterRowNone, "filter_stage.h restates these");
 
-bool has_program(const nidx_gpu_filter_program_t &prog) { return prog.ops && prog.n_ops; }
-
-// the checks of eval_filter_program; counts the PUSH_LISTS operands and tells whether the program needs more than the combine kernel's
-// NIDX_FILTER_STACK bitsets of stack (`deep`: such a program is evaluated op by op, as search_host evaluates it).  `who` names the
-// program in the message ("filter 3", "the request's program").
-int32_t check_program(const VectorSegment &seg, const char *who, uint32_t s, const nidx_gpu_filter_program_t &prog, uint32_t &n_operands,
-                      bool &deep, uint32_t *n_prefilter = nullptr /* non-null: NIDX_FILTER_PUSH_PREFILTER is an op, counted here */) {
-    n_operands = 0;
-    deep = false;
-    if (n_prefilter) *n_prefilter = 0;
-    if (!has_program(prog)) return NIDX_OK;
-    if (prog.n_lists && !prog.lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: %u lists but no list table", who, s, prog.n_lists);
-    int depth = 0;
-    for (uint32_t i = 0; i < prog.n_ops; i++) {
-        const nidx_gpu_filter_op_t &op = prog.ops[i];
-        switch (op.op) {
-            case NIDX_FILTER_PUSH_LISTS:
-                if (op.a > op.b || op.b > prog.n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: list range out of bounds", who, s);
-                if (op.b > op.a && !seg.f_n_lists) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: the segment has no filter index", who, s);
-                for (uint32_t l = op.a; l < op.b; l++)
-                    if (prog.lists[l] >= seg.f_n_lists)
-                        return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown posting list %u", who, s, prog.lists[l]);
-                n_operands++;
-                depth++;
-                break;
-            case NIDX_FILTER_PUSH_PREFILTER:
-                if (!n_prefilter) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown op %d", who, s, op.op);
-                ++*n_prefilter;
-                depth++;
-                break;
-            case NIDX_FILTER_PUSH_ALL:
-            case NIDX_FILTER_PUSH_NONE: depth++; break;
-            case NIDX_FILTER_AND:
-            case NIDX_FILTER_OR:
-                if (depth < 2) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: stack underflow", who, s);
-                depth--;
-                break;
-            case NIDX_FILTER_NOT:
-                if (depth < 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: stack underflow", who, s);
-                break;
-            default: return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: unknown op %d", who, s, op.op);
-        }
-        if (depth > NIDX_FILTER_STACK) deep = true;
-    }
-    if (depth != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s, segment %u: the program must leave exactly one bitset (leaves %d)", who, s, depth);
-    return NIDX_OK;
+std::vector<FilterStageSeg> stage_segs(const std::vector<VectorSegment> &segs) {
+    std::vector<FilterStageSeg> out(segs.size());
+    for (size_t s = 0; s < segs.size(); s++) out[s] = FilterStageSeg{segs[s].n_paragraphs, segs[s].f_n_lists};
+    return out;
+}
+// a refusal of filter_stage.h, passed on with its code and message
+int32_t refuse(int32_t rc, const std::string &error) { return rc == NIDX_OK ? rc : fail(rc, "%s", error.c_str()); }
+// filter_check_program of one segment's program (the checks of eval_filter_program)
+int32_t check_program(const VectorSegment &seg, const char *who, size_t s, const nidx_gpu_filter_program_t &prog, bool prefilter_ops,
+                      FilterProgramInfo &info) {
+    std::string error;
+    return refuse(filter_check_program(FilterStageSeg{seg.n_paragraphs, seg.f_n_lists}, who, (uint32_t)s, prog, prefilter_ops, info, error), error);
+}
+// one segment as a projection launch sees it; out_word == ~0, or a segment without posting lists: not projected
+PrefilterProjSeg proj_seg(const VectorSegment &seg, unsigned long long out_word) {
+    const bool on = out_word != ~0ull && seg.f_n_lists && seg.f_offsets.p;
+    return PrefilterProjSeg{seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), on ? out_word : ~0ull, (seg.n_paragraphs + 63) / 64,
+                            seg.n_paragraphs};
 }
 }  // namespace
 
@@ -1630,15 +1605,7 @@ int32_t VectorIndex::project_prefilter_rows(PrefilterSearch &pf, const std::vect
     const size_t seg_bytes = S * sizeof(PrefilterProjSeg);
     pf_stage.resize(seg_bytes + D * sizeof(uint64_t *));   // (kept until the caller's synchronisation: the upload reads it)
     PrefilterProjSeg *hs = reinterpret_cast<PrefilterProjSeg *>(pf_stage.data());
-    for (size_t s = 0; s < S; s++) {
-        const VectorSegment &seg = segs[s];
-        const bool on = out_word[s] != ~0ull && seg.f_n_lists && seg.f_offsets.p;
-        hs[s].list_off = seg.f_offsets.as<unsigned long long>();
-        hs[s].ids = seg.f_ids.as<uint32_t>();
-        hs[s].out_word = on ? out_word[s] : ~0ull;
-        hs[s].words = (seg.n_paragraphs + 63) / 64;
-        hs[s].n_bits = seg.n_paragraphs;
-    }
+    for (size_t s = 0; s < S; s++) hs[s] = proj_seg(segs[s], out_word[s]);
     const uint64_t **hr = reinterpret_cast<const uint64_t **>(pf_stage.data() + seg_bytes);
     for (size_t j = 0; j < D; j++) hr[j] = pf.rows->row_ptr[rows[j]];
     NIDX_HIP(scratch_pf_in.reserve(pf_stage.size()));
@@ -1656,9 +1623,8 @@ int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *seg
     if (!segment_programs) return NIDX_OK;
     std::lock_guard<std::mutex> lock(mu);
     for (size_t s = 0; s < segs.size(); s++) {
-        uint32_t n_operands = 0;
-        bool dp = false;
-        const int32_t rc = check_program(segs[s], "the request's program", (uint32_t)s, segment_programs[s], n_operands, dp);
+        FilterProgramInfo info;
+        const int32_t rc = check_program(segs[s], "the request's program", s, segment_programs[s], false, info);
         if (rc != NIDX_OK) return rc;
     }
     return NIDX_OK;
@@ -1666,7 +1632,7 @@ int32_t VectorIndex::check_request_programs(const nidx_gpu_filter_program_t *seg
 
 // The prefilter hand-over's checks: everything about the link, the rows and the filters' requests, before any output is written (the
 // blocking search) or anything is queued (the ticket).  Under mu.
-int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters, uint64_t &pf_row_cost) {
+int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters) {
     const size_t S = segs.size();
     if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
     if ((pf.link == nullptr) != (pf.rows == nullptr)) return fail(NIDX_ERR_INVALID_ARGUMENT, "a link without rows, or rows without a link");
@@ -1694,18 +1660,29 @@ int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_
         if (r != UINT32_MAX && pf.rows->has_resources(r))   // (projecting resource rows needs a resource-to-lists link: DESIGN.md §8 item 5)
             return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
         for (size_t s = 0; s < S; s++) {
-            uint32_t n_operands = 0, n_pf = 0;
-            bool dp = false;
-            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, &n_pf);
+            FilterProgramInfo info;
+            const int32_t rc = check_program(segs[s], who, s, programs[(size_t)f * S + s], true, info);
             if (rc != NIDX_OK) return rc;
-            if (n_pf && r == UINT32_MAX)
+            if (info.n_prefilter && r == UINT32_MAX)
                 return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u, segment %zu: NIDX_FILTER_PUSH_PREFILTER in a filter without a prefilter request", f, s);
-            pf.has_op[(size_t)f * S + s] = n_pf ? 1 : 0;
+            pf.has_op[(size_t)f * S + s] = info.n_prefilter ? 1 : 0;
         }
     }
-    for (size_t s = 0; s < S; s++) pf_row_cost += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8;
+    pf.row_of.resize(n_filters);
+    for (uint32_t f = 0; f < n_filters; f++) pf.row_of[f] = pf.row_of_filter(f);
     return NIDX_OK;
 }
+
+namespace {
+// The batch as filter_stage.h reads it (pf: checked by check_prefilter) and its checks, search_per_query's and routed_plan's alike.
+int32_t check_filter_batch(const std::vector<FilterStageSeg> &ss, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
+                           const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query, const PrefilterSearch *pf,
+                           FilterBatch &b, FilterBatchInfo &info) {
+    b = FilterBatch{nq, p.k, p.method, programs, n_filters, filter_of_query, pf != nullptr, pf ? pf->row_of.data() : nullptr, pf ? pf->has_op.data() : nullptr};
+    std::string error;
+    return refuse(filter_check_batch(ss, b, NIDX_K_MAX, info, error), error);
+}
+}  // namespace
 
 int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                       const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
@@ -1716,108 +1693,69 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
     const uint32_t k = p.k;
     const size_t S = segs.size();
     // the prefilter hand-over: everything about the link, the rows and the filters' requests is checked before any output is written
-    uint64_t pf_row_cost = 0;   // a projected row's operand rows: one on every segment
     if (pf) {
-        const int32_t rc = check_prefilter(*pf, programs, n_filters, pf_row_cost);
+        const int32_t rc = check_prefilter(*pf, programs, n_filters);
         if (rc != NIDX_OK) return rc;
         NIDX_HIP(scratch_pf_stats.reserve(16));
     }
     for (uint32_t q = 0; q < nq; q++) out_count[q] = 0;
     if (out_method) std::fill(out_method, out_method + (size_t)nq * S, 0);
     if (out_matching) std::fill(out_matching, out_matching + (size_t)n_filters * S, 0);
-    if (nq == 0 || k == 0 || S == 0) return NIDX_OK;
-    if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
-    if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
-    if (p.method == NIDX_METHOD_BRUTE_FORCE_MFMA || p.method == NIDX_METHOD_BRUTE_FORCE_BF16)
-        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
-    if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
     // everything is checked before anything is launched
-    if (filter_of_query)
-        for (uint32_t q = 0; q < nq; q++)
-            if (filter_of_query[q] != UINT32_MAX && filter_of_query[q] >= n_filters)
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u names filter %u of %u", q, filter_of_query[q], n_filters);
-    // scratch of a filter: a row on every segment (the table of a segment holds a row per filter of the chunk) + its operand rows
-    std::vector<uint8_t> deep((size_t)n_filters * S, 0);
-    std::vector<uint64_t> cost(n_filters, 0);
-    for (uint32_t f = 0; f < n_filters; f++) {
-        char who[32];
-        snprintf(who, sizeof(who), "filter %u", f);
-        for (size_t s = 0; s < S; s++) {
-            uint32_t n_operands = 0;
-            bool dp = false;
-            uint32_t n_pf = 0;
-            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, pf ? &n_pf : nullptr);
-            if (rc != NIDX_OK) return rc;
-            deep[(size_t)f * S + s] = dp ? 1 : 0;
-            cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
-        }
-    }
-    // chunks of consecutive queries whose distinct filters fit the scratch cap and the combine grid (one query at least)
-    std::vector<uint8_t> in_chunk(n_filters, 0);
-    std::vector<uint32_t> filters;
-    // the projected rows of a chunk are shared by the filters that name them: a row costs once per chunk
-    auto projected_row = [&](uint32_t f) -> uint32_t {
-        if (!pf) return kPrefilterRowNone;
-        bool named = false;
-        for (size_t s = 0; s < S; s++) named = named || (pf->has_op[(size_t)f * S + s] && !deep[(size_t)f * S + s]);
-        return named ? pf->row_of_filter(f) : kPrefilterRowNone;   // (All and None rows are no rows)
-    };
-    std::vector<uint32_t> chunk_rows;
+    const std::vector<FilterStageSeg> ss = stage_segs(segs);
+    FilterBatch b;
+    FilterBatchInfo info;
+    const int32_t rc = check_filter_batch(ss, nq, p, programs, n_filters, filter_of_query, pf, b, info);
+    if (rc != NIDX_OK || info.nothing) return rc;
+    // chunks of consecutive queries whose distinct filters fit the scratch cap and the combine grid (one query at least).  Operand rows:
+    // without projected rows the segments use the same memory one after the other; with them every segment has a region of its own,
+    // because the projection fills all segments' rows at once
+    FilterChunk chunk;
+    FilterLayout layout;
     const uint32_t d = cfg.dimension;
-    for (uint32_t q0 = 0; q0 < nq;) {
-        filters.clear();
-        chunk_rows.clear();
-        uint64_t bytes = 0;
-        uint32_t q1 = q0;
-        for (; q1 < nq; q1++) {
-            const uint32_t f = filter_of_query ? filter_of_query[q1] : UINT32_MAX;
-            if (f == UINT32_MAX || in_chunk[f]) continue;
-            const uint32_t row = projected_row(f);
-            const bool new_row = row != kPrefilterRowAll && row != kPrefilterRowNone && std::find(chunk_rows.begin(), chunk_rows.end(), row) == chunk_rows.end();
-            const uint64_t add = cost[f] + (new_row ? pf_row_cost : 0);
-            if (q1 > q0 && (bytes + add > pq_scratch_cap || filters.size() == kPqMaxFilters)) break;
-            in_chunk[f] = 1;
-            bytes += add;
-            filters.push_back(f);
-            if (new_row) chunk_rows.push_back(row);
-        }
-        for (uint32_t f : filters) in_chunk[f] = 0;
+    for (uint32_t q0 = 0; q0 < nq; q0 = chunk.q1) {
+        filter_next_chunk(b, info, S, q0, pq_scratch_cap, kPqMaxFilters, chunk);
+        filter_layout(ss, b, info, chunk, !chunk.rows.empty(), layout);
         if (pf) pf->stats.chunks++;
         const size_t at = (size_t)q0 * k;
-        const int32_t rc = search_per_query_chunk(queries + (size_t)q0 * d, q1 - q0, p, programs, filter_of_query ? filter_of_query + q0 : nullptr,
-                                                  filters, deep, out_segment ? out_segment + at : nullptr,
+        const int32_t rc = search_per_query_chunk(queries + (size_t)q0 * d, chunk.q1 - q0, p, programs, layout, info.deep, out_segment ? out_segment + at : nullptr,
                                                   out_paragraph ? out_paragraph + at : nullptr, out_vector ? out_vector + at : nullptr,
                                                   out_score ? out_score + at : nullptr, out_count + q0,
                                                   out_method ? out_method + (size_t)q0 * S : nullptr, out_matching, pf);
         if (rc != NIDX_OK) return rc;
-        q0 = q1;
+    }
+    return NIDX_OK;
+}
+
+// The filter stage of a layout segment by segment: the segment's operand rows cleared (unless the caller cleared all regions at once
+// because a projection fills them), one scatter and one combine.  *launches += the kernel launches, as the routed path reports them.
+int32_t VectorIndex::launch_filter_stage(const FilterLayout &L, const uint32_t *d_prog, uint64_t *d_operands, uint64_t *d_table,
+                                         unsigned long long *d_counts, hipStream_t st, uint64_t *launches) {
+    const uint32_t F = (uint32_t)L.filters.size();
+    for (size_t s = 0; s < segs.size(); s++) {
+        if (!L.any_prog[s]) continue;
+        const VectorSegment &seg = segs[s];
+        const uint32_t n_bits = seg.n_paragraphs, words = L.words[s];
+        uint64_t *seg_operands = d_operands + L.opnd_off[s];
+        if (!L.own_operands && L.n_opnd[s]) NIDX_HIP(hipMemsetAsync(seg_operands, 0, (size_t)L.n_opnd[s] * words * 8, st));
+        NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), d_prog + L.at_work[s], L.n_work[s], n_bits, words,
+                                       seg_operands, st));
+        NIDX_HIP(launch_filter_combine(d_prog + L.at_ops[s], d_prog + L.at_first[s], F, seg_operands, seg.all_alive ? nullptr : seg.alive.as<uint64_t>(),
+                                       words, n_bits, d_table + L.tab_off[s], d_counts + s * F, st));
+        if (launches) *launches += (L.n_work[s] ? 1 : 0) + (F && words ? 1 : 0);
     }
     return NIDX_OK;
 }
 
 int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
-                                            const nidx_gpu_filter_program_t *programs, const uint32_t *filter_of_query,
-                                            const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
+                                            const nidx_gpu_filter_program_t *programs, const FilterLayout &L, const std::vector<uint8_t> &deep,
                                             uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                                             uint32_t *out_count, int32_t *out_method, uint64_t *out_matching, PrefilterSearch *pf) {
     const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
     const size_t S = segs.size();
+    const std::vector<uint32_t> &filters = L.filters;
+    const std::vector<size_t> &tab_off = L.tab_off;
     const uint32_t F = (uint32_t)filters.size();
-    // the distinct prefilter rows the chunk's programs push (not the deep ones': those project their own): operand rows 0 .. D of every
-    // segment, filled by one launch before the segments' loop and shared by the filters that name the same row
-    std::vector<uint32_t> pf_rows;
-    std::unordered_map<uint32_t, uint32_t> pf_slot;
-    if (pf)
-        for (uint32_t f : filters) {
-            const uint32_t row = pf->row_of_filter(f);
-            if (row == kPrefilterRowAll || row == kPrefilterRowNone || pf_slot.count(row)) continue;
-            bool named = false;
-            for (size_t s = 0; s < S; s++) named = named || (pf->has_op[(size_t)f * S + s] && !deep[(size_t)f * S + s]);
-            if (!named) continue;
-            pf_slot.emplace(row, (uint32_t)pf_rows.size());
-            pf_rows.push_back(row);
-        }
-    const uint32_t D = (uint32_t)pf_rows.size();
     // query batch -> HBM, as search_host stages it
     NIDX_HIP(pin_in.reserve((size_t)nq * dp * 4));
     stage_query_rows(queries, pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
@@ -1826,97 +1764,31 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     const size_t block_words = out_block_words(nq, k);
     NIDX_HIP(scratch_out_block.reserve(block_words * 4));
     NIDX_HIP(pin_out.reserve(block_words * 4));
-    std::unordered_map<uint32_t, uint32_t> local;   // filter -> its row in this chunk's tables
-    for (uint32_t i = 0; i < F; i++) local.emplace(filters[i], i);
     auto prog_of = [&](uint32_t lf, size_t s) -> const nidx_gpu_filter_program_t & { return programs[(size_t)filters[lf] * S + s]; };
 
-    // ---- every filter of the chunk on every segment: [ops][prog_first][work] per segment, one upload, two launches per segment ----
-    std::vector<uint32_t> host;
-    std::vector<size_t> at_ops(S), at_first(S), at_work(S), tab_off(S);
-    std::vector<uint32_t> n_work(S, 0), n_opnd(S, D);
-    std::vector<uint8_t> any_prog(S, 0);
-    // operand rows: without projected rows the segments use the same memory one after the other; with them every segment has a region
-    // of its own, [D projected rows | its posting-list operands], because the projection fills all segments' rows at once
-    std::vector<size_t> opnd_off(S, 0);
-    size_t tab_words = 0, opnd_words = 0;
-    for (size_t s = 0; s < S; s++) {
-        const uint32_t words = (segs[s].n_paragraphs + 63) / 64;
-        std::vector<uint32_t> ops, first(F + 1, 0), work;
-        for (uint32_t lf = 0; lf < F; lf++) {
-            const nidx_gpu_filter_program_t &prog = prog_of(lf, s);
-            first[lf] = (uint32_t)ops.size();
-            if (!has_program(prog)) continue;
-            any_prog[s] = 1;
-            if (deep[(size_t)filters[lf] * S + s]) continue;   // evaluated op by op below (its combine program stays empty)
-            for (uint32_t i = 0; i < prog.n_ops; i++) {
-                const nidx_gpu_filter_op_t &op = prog.ops[i];
-                if (op.op == NIDX_FILTER_PUSH_LISTS) {
-                    const uint32_t o = n_opnd[s]++;
-                    for (uint32_t l = op.a; l < op.b; l++) {
-                        work.push_back(o);
-                        work.push_back(prog.lists[l]);
-                    }
-                    ops.push_back((uint32_t)op.op | (o << 3));
-                } else if (op.op == NIDX_FILTER_PUSH_PREFILTER) {   // an operand row like any other for the combine kernel
-                    const uint32_t row = pf->row_of_filter(filters[lf]);
-                    if (row == kPrefilterRowAll) ops.push_back((uint32_t)NIDX_FILTER_PUSH_ALL);
-                    else if (row == kPrefilterRowNone) ops.push_back((uint32_t)NIDX_FILTER_PUSH_NONE);
-                    else ops.push_back((uint32_t)NIDX_FILTER_PUSH_LISTS | (pf_slot.at(row) << 3));
-                } else {
-                    ops.push_back((uint32_t)op.op);
-                }
-            }
-        }
-        first[F] = (uint32_t)ops.size();
-        if (!any_prog[s]) continue;
-        n_work[s] = (uint32_t)(work.size() / 2);
-        at_ops[s] = host.size();
-        host.insert(host.end(), ops.begin(), ops.end());
-        at_first[s] = host.size();
-        host.insert(host.end(), first.begin(), first.end());
-        at_work[s] = host.size();
-        host.insert(host.end(), work.begin(), work.end());
-        tab_off[s] = tab_words;
-        tab_words += (size_t)F * words;
-        if (D) {
-            opnd_off[s] = opnd_words;
-            opnd_words += (size_t)n_opnd[s] * words;
-        } else {
-            opnd_words = std::max(opnd_words, (size_t)n_opnd[s] * words);
-        }
-    }
+    // ---- every filter of the chunk on every segment: one upload, one projection of the rows its programs push (not the deep ones': those
+    // project their own), two launches per segment ----
     std::vector<unsigned long long> counts((size_t)S * F, 0);   // [segment][filter] |filter ∩ alive|
     unsigned long long pf_counts[2] = {0, 0};                  // the projection's documents visited, paragraph ids written
-    if (!host.empty()) {
-        NIDX_HIP(scratch_pq_prog.reserve(host.size() * 4));
-        NIDX_HIP(scratch_pq_table.reserve(std::max<size_t>(tab_words, 1) * 8));
-        NIDX_HIP(scratch_pq_operands.reserve(std::max<size_t>(opnd_words, 1) * 8));
+    if (!L.prog.empty()) {
+        NIDX_HIP(scratch_pq_prog.reserve(L.prog.size() * 4));
+        NIDX_HIP(scratch_pq_table.reserve(std::max<size_t>(L.tab_words, 1) * 8));
+        NIDX_HIP(scratch_pq_operands.reserve(std::max<size_t>(L.opnd_words, 1) * 8));
         NIDX_HIP(scratch_pq_count.reserve(counts.size() * 8));
-        NIDX_HIP(hipMemcpyAsync(scratch_pq_prog.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream));
+        NIDX_HIP(hipMemcpyAsync(scratch_pq_prog.p, L.prog.data(), L.prog.size() * 4, hipMemcpyHostToDevice, stream));
         NIDX_HIP(hipMemsetAsync(scratch_pq_count.p, 0, counts.size() * 8, stream));
-        const uint32_t *dprog = scratch_pq_prog.as<uint32_t>();
-        if (D) {   // every projected row onto every segment with programs: one launch
-            NIDX_HIP(hipMemsetAsync(scratch_pq_operands.p, 0, opnd_words * 8, stream));
+        if (!L.pf_rows.empty()) {   // every projected row onto every segment with programs: one launch
+            NIDX_HIP(hipMemsetAsync(scratch_pq_operands.p, 0, L.opnd_words * 8, stream));
             NIDX_HIP(hipMemsetAsync(scratch_pf_stats.p, 0, 16, stream));
-            std::vector<unsigned long long> out_word(S, ~0ull);
-            for (size_t s = 0; s < S; s++)
-                if (any_prog[s] && segs[s].n_paragraphs) out_word[s] = opnd_off[s];
-            const int32_t rc = project_prefilter_rows(*pf, pf_rows, out_word, scratch_pq_operands.as<uint64_t>());
+            std::vector<unsigned long long> out_word(S);
+            for (size_t s = 0; s < S; s++) out_word[s] = L.proj_word(s);
+            const int32_t rc = project_prefilter_rows(*pf, L.pf_rows, out_word, scratch_pq_operands.as<uint64_t>());
             if (rc != NIDX_OK) return rc;
             NIDX_HIP(hipMemcpyAsync(pf_counts, scratch_pf_stats.p, 16, hipMemcpyDeviceToHost, stream));
         }
-        for (size_t s = 0; s < S; s++) {
-            if (!any_prog[s]) continue;
-            VectorSegment &seg = segs[s];
-            const uint32_t n_bits = seg.n_paragraphs, words = (n_bits + 63) / 64;
-            uint64_t *seg_operands = scratch_pq_operands.as<uint64_t>() + opnd_off[s];
-            if (!D && n_opnd[s]) NIDX_HIP(hipMemsetAsync(seg_operands, 0, (size_t)n_opnd[s] * words * 8, stream));
-            NIDX_HIP(launch_filter_scatter(seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), dprog + at_work[s], n_work[s], n_bits,
-                                           words, seg_operands, stream));
-            NIDX_HIP(launch_filter_combine(dprog + at_ops[s], dprog + at_first[s], F, seg_operands,
-                                           seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), words, n_bits,
-                                           scratch_pq_table.as<uint64_t>() + tab_off[s], scratch_pq_count.as<unsigned long long>() + s * F, stream));
-        }
+        const int32_t rc = launch_filter_stage(L, scratch_pq_prog.as<uint32_t>(), scratch_pq_operands.as<uint64_t>(), scratch_pq_table.as<uint64_t>(),
+                                               scratch_pq_count.as<unsigned long long>(), stream, nullptr);
+        if (rc != NIDX_OK) return rc;
         NIDX_HIP(hipMemcpyAsync(counts.data(), scratch_pq_count.p, counts.size() * 8, hipMemcpyDeviceToHost, stream));
     }
     NIDX_HIP(hipStreamSynchronize(stream));
@@ -1939,11 +1811,8 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
         }
 
     // ---- routing of every (query, segment): OpenSegment::_search (segment.rs:506-555), exactly as search_host decides a segment ----
-    auto lf_of = [&](uint32_t q) -> uint32_t {
-        const uint32_t f = filter_of_query ? filter_of_query[q] : UINT32_MAX;
-        return f == UINT32_MAX ? NIDX_FILTER_ROW_NONE : local.at(f);
-    };
-    auto row_of = [&](uint32_t lf, size_t s) -> uint32_t { return lf != NIDX_FILTER_ROW_NONE && has_program(prog_of(lf, s)) ? lf : NIDX_FILTER_ROW_NONE; };
+    auto lf_of = [&](uint32_t q) -> uint32_t { return L.filter_of_query[q]; };
+    auto row_of = [&](uint32_t lf, size_t s) -> uint32_t { return lf != NIDX_FILTER_ROW_NONE && L.has_program[s * F + lf] ? lf : NIDX_FILTER_ROW_NONE; };
     auto matching_of = [&](uint32_t row, size_t s) -> uint64_t { return row == NIDX_FILTER_ROW_NONE ? segs[s].alive_count : counts[s * F + row]; };
     if (out_matching)
         for (uint32_t lf = 0; lf < F; lf++)
@@ -2029,167 +1898,63 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
 }
 
 // ---- the same batch routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async): what the host decides -----------
-// search_per_query's checks in its order (same codes, same messages), then whether the routed path takes the batch, then the filter
-// stage laid out as search_per_query_chunk lays out a chunk's — the batch is one chunk here, or it falls back.
+// search_per_query's checks, then whether the routed path takes the batch, then the filter stage of the batch as ONE chunk — a batch
+// of more than one chunk falls back.  A prefiltered batch gives every segment its own operand region: its filter stage is table driven.
 int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
                                  const uint32_t *filter_of_query, RoutedPlan &plan, PrefilterSearch *pf) {
     std::lock_guard<std::mutex> lock(mu);
-    const uint32_t k = p.k;
     const size_t S = segs.size();
-    uint64_t pf_row_cost = 0;
     if (pf) {   // (before everything else, as search_per_query checks)
-        const int32_t rc = check_prefilter(*pf, programs, n_filters, pf_row_cost);
+        const int32_t rc = check_prefilter(*pf, programs, n_filters);
         if (rc != NIDX_OK) return rc;
-        plan.prefiltered = true;
     }
-    if (nq == 0 || k == 0 || S == 0) {
-        plan.nothing = true;
-        return NIDX_OK;
-    }
-    if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
-    if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
-    if (p.method == NIDX_METHOD_BRUTE_FORCE_MFMA || p.method == NIDX_METHOD_BRUTE_FORCE_BF16)
-        return fail(NIDX_ERR_UNSUPPORTED, "the matrix-core scans share one row mask per batch: no per-query filters");
-    if (n_filters && !programs) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL programs with %u filters", n_filters);
-    if (filter_of_query)
-        for (uint32_t q = 0; q < nq; q++)
-            if (filter_of_query[q] != UINT32_MAX && filter_of_query[q] >= n_filters)
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "query %u names filter %u of %u", q, filter_of_query[q], n_filters);
-    std::vector<uint64_t> cost(n_filters, 0);
-    bool deep = false;
-    for (uint32_t f = 0; f < n_filters; f++) {
-        char who[32];
-        snprintf(who, sizeof(who), "filter %u", f);
-        for (size_t s = 0; s < S; s++) {
-            uint32_t n_operands = 0;
-            bool dp = false;
-            uint32_t n_pf = 0;
-            const int32_t rc = check_program(segs[s], who, (uint32_t)s, programs[(size_t)f * S + s], n_operands, dp, pf ? &n_pf : nullptr);
-            if (rc != NIDX_OK) return rc;
-            deep = deep || dp;
-            cost[f] += (uint64_t)((segs[s].n_paragraphs + 63) / 64) * 8 * (1 + (dp ? 0 : n_operands));
-        }
-    }
+    const std::vector<FilterStageSeg> ss = stage_segs(segs);
+    FilterBatch b;
+    FilterBatchInfo info;
+    const int32_t rc = check_filter_batch(ss, nq, p, programs, n_filters, filter_of_query, pf, b, info);
+    plan.nothing = info.nothing;
+    if (rc != NIDX_OK || info.nothing) return rc;
     // ---- what the routed path leaves to the blocking one (decided before anything is queued) ----
-    plan.fallback = deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE ||
+    plan.fallback = info.any_deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE ||
                     (pf && S > 65535u);   // (the segment is a grid dimension of the table-driven filter stage)
     for (size_t s = 0; s < S && !plan.fallback; s++) {
         const VectorSegment &seg = segs[s];
         // (a forced walk on an index with a graphless segment: the blocking path's error depends on a count)
         plan.fallback = rabitq_enabled(seg) || seg.vmax > 1 || (p.method == NIDX_METHOD_HNSW && !seg.has_graph);
     }
+    FilterChunk chunk;
+    if (!plan.fallback) filter_next_chunk(b, info, S, 0, pq_scratch_cap, kPqMaxFilters, chunk);
+    plan.fallback = plan.fallback || chunk.q1 < nq;
     if (plan.fallback) return NIDX_OK;
-    // the batch's distinct filters in order of first use: one chunk by search_per_query's rule, or the blocking path chunks it
-    std::vector<uint32_t> local(n_filters, NIDX_FILTER_ROW_NONE);
-    plan.filter_of_query.assign(nq, NIDX_FILTER_ROW_NONE);
-    uint64_t bytes = 0;
-    // the Some row a filter's programs push (kPrefilterRowNone: none; All and None rows are no rows), and its slot among the batch's
-    std::unordered_map<uint32_t, uint32_t> pf_slot;
-    auto projected_row = [&](uint32_t f) -> uint32_t {
-        if (!pf) return kPrefilterRowNone;
-        bool named = false;
-        for (size_t s = 0; s < S; s++) named = named || pf->has_op[(size_t)f * S + s];
-        const uint32_t row = named ? pf->row_of_filter(f) : kPrefilterRowNone;
-        return row == kPrefilterRowAll ? kPrefilterRowNone : row;
-    };
-    for (uint32_t q = 0; q < nq; q++) {
-        const uint32_t f = filter_of_query ? filter_of_query[q] : UINT32_MAX;
-        if (f == UINT32_MAX) continue;
-        if (local[f] == NIDX_FILTER_ROW_NONE) {
-            const uint32_t row = projected_row(f);
-            const bool new_row = row != kPrefilterRowNone && !pf_slot.count(row);
-            const uint64_t add = cost[f] + (new_row ? pf_row_cost : 0);   // (a row costs once per chunk)
-            if (q > 0 && (bytes + add > pq_scratch_cap || plan.filters.size() == kPqMaxFilters)) {
-                plan.fallback = true;
-                return NIDX_OK;
-            }
-            bytes += add;
-            local[f] = (uint32_t)plan.filters.size();
-            plan.filters.push_back(f);
-            if (new_row) {
-                pf_slot.emplace(row, (uint32_t)plan.pf_rows.size());
-                plan.pf_rows.push_back(row);
-            }
-        }
-        plan.filter_of_query[q] = local[f];
-    }
-    const uint32_t F = (uint32_t)plan.filters.size(), D = (uint32_t)plan.pf_rows.size();
-    plan.at_ops.assign(S, 0), plan.at_first.assign(S, 0), plan.at_work.assign(S, 0), plan.tab_off.assign(S, 0);
-    plan.n_work.assign(S, 0), plan.n_opnd.assign(S, D), plan.any_prog.assign(S, 0);
-    if (pf) {
-        plan.opnd_off.assign(S, 0);
-        plan.proj_segs.resize(S);
-        plan.filter_segs.resize(S);
-    }
-    plan.has_program.assign(S * (size_t)F, 0);
+    filter_layout(ss, b, info, chunk, pf != nullptr, plan.layout);
     plan.segs.resize(S);
     for (size_t s = 0; s < S; s++) {
         const VectorSegment &seg = segs[s];
-        plan.segs[s] = RouteSegDev{seg.alive_count, seg.has_graph ? use_hnsw_threshold(seg.n_paragraphs, k, false) : UINT64_MAX, seg.n,
+        plan.segs[s] = RouteSegDev{seg.alive_count, seg.has_graph ? use_hnsw_threshold(seg.n_paragraphs, p.k, false) : UINT64_MAX, seg.n,
                                    seg.has_graph ? 1u : 0u};
-        const uint32_t words = (seg.n_paragraphs + 63) / 64;
-        std::vector<uint32_t> ops, first(F + 1, 0), work;
-        for (uint32_t lf = 0; lf < F; lf++) {
-            const nidx_gpu_filter_program_t &prog = programs[(size_t)plan.filters[lf] * S + s];
-            first[lf] = (uint32_t)ops.size();
-            if (!has_program(prog)) continue;
-            plan.any_prog[s] = 1;
-            plan.has_program[s * (size_t)F + lf] = 1;
-            for (uint32_t i = 0; i < prog.n_ops; i++) {
-                const nidx_gpu_filter_op_t &op = prog.ops[i];
-                if (op.op == NIDX_FILTER_PUSH_LISTS) {
-                    const uint32_t o = plan.n_opnd[s]++;
-                    for (uint32_t l = op.a; l < op.b; l++) {
-                        work.push_back(o);
-                        work.push_back(prog.lists[l]);
-                    }
-                    ops.push_back((uint32_t)op.op | (o << 3));
-                } else if (op.op == NIDX_FILTER_PUSH_PREFILTER) {   // an operand row like any other for the combine kernel
-                    const uint32_t row = pf->row_of_filter(plan.filters[lf]);
-                    if (row == kPrefilterRowAll) ops.push_back((uint32_t)NIDX_FILTER_PUSH_ALL);
-                    else if (row == kPrefilterRowNone) ops.push_back((uint32_t)NIDX_FILTER_PUSH_NONE);
-                    else ops.push_back((uint32_t)NIDX_FILTER_PUSH_LISTS | (pf_slot.at(row) << 3));
-                } else {
-                    ops.push_back((uint32_t)op.op);
-                }
-            }
-        }
-        first[F] = (uint32_t)ops.size();
-        if (pf) {
-            plan.proj_segs[s] = PrefilterProjSeg{seg.f_offsets.as<unsigned long long>(), seg.f_ids.as<uint32_t>(), ~0ull, words, seg.n_paragraphs};
-            plan.filter_segs[s] = FilterSegDev{};   // (words == 0: the launches pass the segment by)
-        }
-        if (!plan.any_prog[s]) continue;
-        plan.n_work[s] = (uint32_t)(work.size() / 2);
-        plan.at_ops[s] = plan.prog.size();
-        plan.prog.insert(plan.prog.end(), ops.begin(), ops.end());
-        plan.at_first[s] = plan.prog.size();
-        plan.prog.insert(plan.prog.end(), first.begin(), first.end());
-        plan.at_work[s] = plan.prog.size();
-        plan.prog.insert(plan.prog.end(), work.begin(), work.end());
-        plan.tab_off[s] = plan.tab_words;
-        plan.tab_words += (size_t)F * words;
-        if (!pf) {
-            plan.opnd_words = std::max(plan.opnd_words, (size_t)plan.n_opnd[s] * words);
-            continue;
-        }
-        plan.opnd_off[s] = plan.opnd_words;
-        plan.opnd_words += (size_t)plan.n_opnd[s] * words;
-        if (D && words && seg.f_n_lists && seg.f_offsets.p) plan.proj_segs[s].out_word = plan.opnd_off[s];   // (project_prefilter_rows' rule)
-        FilterSegDev &fs = plan.filter_segs[s];
-        fs.list_offsets = seg.f_offsets.as<unsigned long long>();
-        fs.ids = seg.f_ids.as<uint32_t>();
-        fs.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
-        fs.operand_word = plan.opnd_off[s];
-        fs.table_word = plan.tab_off[s];
-        fs.work_first = (uint32_t)plan.at_work[s], fs.n_work = plan.n_work[s];
-        fs.ops_first = (uint32_t)plan.at_ops[s], fs.first_first = (uint32_t)plan.at_first[s];
-        fs.n_bits = seg.n_paragraphs, fs.words = words;
-        fs.count_first = (uint32_t)(s * F);
-        plan.max_work = std::max(plan.max_work, plan.n_work[s]);
-        plan.max_words = std::max(plan.max_words, words);
     }
     return NIDX_OK;
+}
+
+// The records of the table-driven filter stage and of its projection, one per segment, from a layout with own operand regions.
+void VectorIndex::filter_stage_records(const FilterLayout &L, FilterSegDev *fs, PrefilterProjSeg *ps) {
+    std::lock_guard<std::mutex> lock(mu);
+    const uint32_t F = (uint32_t)L.filters.size();
+    for (size_t s = 0; s < segs.size(); s++) {
+        const VectorSegment &seg = segs[s];
+        ps[s] = proj_seg(seg, L.proj_word(s));
+        fs[s] = FilterSegDev{};   // (words == 0: the launches pass the segment by)
+        if (!L.any_prog[s]) continue;
+        fs[s].list_offsets = seg.f_offsets.as<unsigned long long>();
+        fs[s].ids = seg.f_ids.as<uint32_t>();
+        fs[s].alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
+        fs[s].operand_word = L.opnd_off[s];
+        fs[s].table_word = L.tab_off[s];
+        fs[s].work_first = (uint32_t)L.at_work[s], fs[s].n_work = L.n_work[s];
+        fs[s].ops_first = (uint32_t)L.at_ops[s], fs[s].first_first = (uint32_t)L.at_first[s];
+        fs[s].n_bits = seg.n_paragraphs, fs[s].words = L.words[s];
+        fs[s].count_first = (uint32_t)(s * F);
+    }
 }
 
 // ---- the host stage of search_multi_vector (searcher.rs:373-393): nidx_gpu_vector_search_maxsim's second stage, and what finishes

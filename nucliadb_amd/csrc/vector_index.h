@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "filter_stage.h"
 #include "hnsw_graph.h"
 #include "host_common.h"
 #include "kernels.h"
@@ -94,32 +95,18 @@ struct PrefilterSearch {
     const PrefilterRows *rows = nullptr;
     const uint32_t *prefilter_of_filter = nullptr;   // [n_filters] request in `rows`, UINT32_MAX = none (nullptr: none for every filter)
     std::vector<uint8_t> has_op;                     // [n_filters][n_segments] the program holds NIDX_FILTER_PUSH_PREFILTER
+    std::vector<uint32_t> row_of;                    // [n_filters] row_of_filter(f), filled by check_prefilter
     nidx_gpu_prefilter_search_stats_t stats{};
     uint32_t row_of_filter(uint32_t f) const;        // the filter's resident row, kPrefilterRowAll or kPrefilterRowNone
 };
 
-// The filter stage of one batch whose distinct filters fit one chunk, as search_per_query_chunk lays it out: per segment
-// [ops][prog_first][work] in `prog`, a table of F rows and the operand rows (shared by the segments one after the other)
+// What the host decides about a routed batch: whether there is anything to do, whether the routed path takes it, each segment's routing
+// constants, and the filter stage of the batch as one chunk (filter_stage.h; a prefiltered batch: own operand regions)
 struct RoutedPlan {
     bool nothing = false;    // no query, k == 0 or no segment: every count is 0
     bool fallback = false;   // the routed path does not take the batch: nidx_gpu_vector_search_submit_filtered_per_query answers it
-    std::vector<uint32_t> filters;           // the batch's distinct filters in order of first use
-    std::vector<uint32_t> filter_of_query;   // [nq] index into `filters`, NIDX_FILTER_ROW_NONE = unfiltered
-    std::vector<uint32_t> prog;
-    std::vector<size_t> at_ops, at_first, at_work, tab_off;   // [S]
-    std::vector<uint32_t> n_work, n_opnd;                     // [S]
-    std::vector<uint8_t> any_prog;                            // [S]
-    std::vector<uint8_t> has_program;                         // [S][F]
-    std::vector<RouteSegDev> segs;                            // [S]
-    size_t tab_words = 0, opnd_words = 0;
-    // a batch of nidx_gpu_vector_search_submit_prefiltered_per_query_async: every segment owns an operand region [D projected rows | its
-    // list operands] at word opnd_off[s] (nothing orders the segments), and the filter stage is table driven (filter_segs)
-    bool prefiltered = false;
-    std::vector<uint32_t> pf_rows;            // [D] the distinct Some rows the batch's programs push, in order of first use
-    std::vector<size_t> opnd_off;             // [S]
-    std::vector<PrefilterProjSeg> proj_segs;  // [S]
-    std::vector<FilterSegDev> filter_segs;    // [S] prog offsets relative to `prog`
-    uint32_t max_work = 0, max_words = 0;
+    std::vector<RouteSegDev> segs;   // [S]
+    FilterLayout layout;
 };
 uint64_t use_hnsw_threshold(uint64_t total_nodes, uint64_t top_k, bool has_rabitq);
 
@@ -281,13 +268,14 @@ struct VectorIndex {
                         uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                         uint32_t *out_count, int32_t *out_method, uint64_t *out_matching);
     // one batch in which query q uses filter filter_of_query[q] (nidx_gpu_vector_search_filtered_per_query); chunks of queries whose
-    // filter rows fit kPqFilterScratchCap go through search_per_query_chunk one after the other
+    // filter and operand rows fit pq_scratch_cap (filter_next_chunk) go through search_per_query_chunk one after the other, each with
+    // its layout
     int32_t search_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                              uint32_t n_filters, const uint32_t *filter_of_query, uint32_t *out_segment, uint32_t *out_paragraph,
                              uint32_t *out_vector, float *out_score, uint32_t *out_count, int32_t *out_method, uint64_t *out_matching,
                              PrefilterSearch *pf = nullptr);
     int32_t search_per_query_chunk(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
-                                   const uint32_t *filter_of_query, const std::vector<uint32_t> &filters, const std::vector<uint8_t> &deep,
+                                   const FilterLayout &layout, const std::vector<uint8_t> &deep,
                                    uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
                                    int32_t *out_method, uint64_t *out_matching, PrefilterSearch *pf = nullptr);
     // the checks search_per_query makes of one request's [n_segments] programs (nullptr: unfiltered), before it joins a coalesced batch
@@ -295,16 +283,20 @@ struct VectorIndex {
     int32_t pipeline_submit_per_query(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                                       uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out, PrefilterSearch *pf = nullptr);
     // the same batch queued on a pipeline slot and routed on the device (nidx_gpu_vector_search_submit_filtered_per_query_async):
-    // routed_plan makes search_per_query's checks in its order and lays out the filter stage of the batch as search_per_query_chunk does
-    // (plan.fallback: the routed path does not take the batch); pipeline_submit_routed queues it (serving.cpp)
-    // (pf: nidx_gpu_vector_search_submit_prefiltered_per_query_async — the checks, the chunk rule and the layout of the blocking
-    // prefiltered search, the filter stage of all segments in one launch set)
+    // routed_plan makes search_per_query's checks and lays out the filter stage of the batch as one chunk (plan.fallback: the routed
+    // path does not take the batch); pipeline_submit_routed queues it (serving.cpp)
+    // (pf: nidx_gpu_vector_search_submit_prefiltered_per_query_async — the filter stage of all segments in one launch set)
     int32_t routed_plan(uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs, uint32_t n_filters,
                         const uint32_t *filter_of_query, RoutedPlan &plan, PrefilterSearch *pf = nullptr);
     int32_t pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p, const nidx_gpu_filter_program_t *programs,
                                    uint32_t n_filters, const uint32_t *filter_of_query, uint64_t *ticket_out, PrefilterSearch *pf = nullptr);
-    // search_per_query's checks of the link, the rows and the filters' requests (under mu); fills pf.has_op and a projected row's cost
-    int32_t check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters, uint64_t &pf_row_cost);
+    // search_per_query's checks of the link, the rows and the filters' requests (under mu); fills pf.has_op and pf.row_of
+    int32_t check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_program_t *programs, uint32_t n_filters);
+    // the per-segment form of a layout's filter stage: memset (shared operand rows), scatter, combine for every segment with a program
+    int32_t launch_filter_stage(const FilterLayout &layout, const uint32_t *d_prog, uint64_t *d_operands, uint64_t *d_table,
+                                unsigned long long *d_counts, hipStream_t st, uint64_t *launches);
+    // the table-driven form's records [S] and its projection's [S] (takes mu)
+    void filter_stage_records(const FilterLayout &layout, FilterSegDev *fs, PrefilterProjSeg *ps);
     int32_t routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score, uint32_t *out_count,
                         int32_t *out_method, uint64_t *out_matching, uint32_t *n_retried_out);
     // nidx_gpu_vector_routed_stats, in the order of nidx_gpu_vector_routed_stats_t

@@ -114,6 +114,94 @@ def test_unequal_segments_with_and_without_a_word_tail(text):
         w.close()
 
 
+def test_a_second_workgroup_of_one_tail_word_through_all_three_routes(text):
+    """16 385 paragraphs are 257 words: the combine grid's second workgroup holds one word, and of that word one bit.  64 paragraphs are
+    fewer blocks than the grid.  One batch — a NOT filter (the tail mask), a filter without a program on the small segment — through the
+    blocking per-query call, the routed ticket and the prefiltered ticket (own operand regions, table-driven launches), then with two
+    filters that push a projected row through the two prefiltered routes: every route gives the numpy model's counts and sets."""
+    w = T.VectorSide(text, (16385, 64), graphs=False, seed=23)
+    try:
+        sizes = [len(pk) for pk in w.par_keys]
+        big, small = sizes.index(16385), sizes.index(64)
+        last = 16384
+        assert w.alive[big][last] and not w.alive[big].all()
+        seg = w.vs._segments[big]
+        field = seg.list_id["F:" + seg._field_keys[last]]            # the posting list of the last paragraph's field: a few dozen paragraphs
+        in_field = [pk == w.par_keys[big][last] for pk in w.par_keys]
+        lab = [np.arange(n) % H.N_LABELS == T.LABEL for n in sizes]
+        assert 1 < in_field[big].sum() < 100 and not in_field[small].any()
+        atom, atom2 = (LISTS, 0, 1), (LISTS, 1, 2)
+
+        def both(big_prog, small_prog):
+            return tuple(big_prog if s == big else small_prog for s in range(2))
+
+        # (programs, the model's masks before `alive`); a segment without a program is unfiltered
+        filters = [
+            (both(((atom,), (field,)), None), both(in_field[big], np.ones(64, bool))),
+            (both(((atom, atom2, (NOT, 0, 0), (AND, 0, 0)), (field, w.label_list[big])), ((atom, (NOT, 0, 0)), (w.label_list[small],))),
+             both(in_field[big] & ~lab[big], ~lab[small])),
+            (both(((atom, (NOT, 0, 0)), (w.label_list[big],)), ((atom, (NOT, 0, 0)), (w.label_list[small],))), both(~lab[big], ~lab[small])),
+            (both(((atom,), (w.label_list[big],)), ((atom,), (w.label_list[small],))), both(lab[big], lab[small])),
+        ]
+        uniq = [f[0] for f in filters]
+        masks = [[m & w.alive[s] for s, m in enumerate(f[1])] for f in filters]
+        filter_of = [0, 1, 2, 3, NOROW, 1, 0, 3]
+        queries = np.random.default_rng(8).standard_normal((len(filter_of), H.DIM)).astype(np.float32)
+        method, k = _lib.METHOD_BRUTE_FORCE, 512
+
+        def check(got, uniq, masks, filter_of):
+            assert got.rc == 0, _lib.last_error()
+            for f in range(len(uniq)):
+                for s in range(2):
+                    assert got.matching[f][s] == int(masks[f][s].sum()), (f, s)
+            seen_last = 0
+            for q, f in enumerate(filter_of):
+                want = [np.flatnonzero(w.alive[s] if f == NOROW else masks[f][s]).tolist() for s in range(2)]
+                if sum(len(x) for x in want) > k:
+                    continue      # the page does not hold every match
+                n = int(got.count[q])
+                for s in range(2):
+                    assert sorted(int(p) for sg, p in zip(got.seg[q, :n], got.par[q, :n]) if sg == s) == want[s], (q, s)
+                seen_last += last in want[big]
+            return seen_last      # (the last paragraph of the large segment: the one bit of the tail word)
+
+        # 1. the blocking call
+        assert check(H.search(w.vs, queries, uniq, filter_of, method, k=k), uniq, masks, filter_of) >= 4
+        # 2. the routed ticket
+        progs, _keep = w.vs._programs_c(uniq)
+        foq = np.array(filter_of, dtype=np.uint32)
+        params = _lib.VectorSearchParamsC(k, -1e30, 0, method)
+        ticket = C.c_uint64(99)
+        before = T.routed_stats(w.vs)
+        rc = _lib.lib().nidx_gpu_vector_search_submit_filtered_per_query_async(w.vs._handle, queries.ctypes.data, len(filter_of), H.DIM, C.byref(params), progs,
+                                                                               len(uniq), foq.ctypes.data, C.byref(ticket))
+        assert rc == 0, _lib.last_error()
+        got, _r = T.wait(w.vs, ticket.value, len(filter_of), len(uniq), k=k)
+        assert check(got, uniq, masks, filter_of) >= 4
+        d = T.delta(before, T.routed_stats(w.vs))
+        assert d["batches_routed"] == 1 and d["batches_fallback"] == 0
+        # 3. the prefiltered ticket: no filter names a request, then two filters push a projected row
+        some = text.kinds.index("Some")
+        for extra in ((), ("not pf", "pf and lab")):
+            uniq3 = uniq + [w.program(shape) for shape in extra]
+            masks3 = masks + [[w.model(text, shape, some, s) for s in range(2)] for shape in extra]
+            filter_of3 = filter_of + list(range(len(uniq), len(uniq3)))
+            prefilter_of = [NOROW] * len(uniq) + [some] * len(extra)
+            queries3 = np.random.default_rng(9).standard_normal((len(filter_of3), H.DIM)).astype(np.float32)
+            before = T.ticket_stats(w.vs)
+            rc, ticket3 = T.submit(w.vs, queries3, uniq3, filter_of3, method, w.link, text.rows, prefilter_of, k=k)
+            assert rc == 0, _lib.last_error()
+            got, _r = T.wait(w.vs, ticket3, len(filter_of3), len(uniq3), k=k)
+            assert check(got, uniq3, masks3, filter_of3) >= 4
+            d = T.delta(before, T.ticket_stats(w.vs))
+            assert d["batches_routed"] == 1 and d["batches_fallback"] == 0 and d["rows_projected"] == (1 if extra else 0)
+            blocking = H.search(w.vs, queries3, uniq3, filter_of3, method, w.link, text.rows, prefilter_of, k=k)
+            assert check(blocking, uniq3, masks3, filter_of3) >= 4
+            T.assert_same(got, blocking)
+    finally:
+        w.close()
+
+
 # ---- 3. launches do not grow with S -----------------------------------------------------------------------------------------------------
 def test_filter_launches_do_not_grow_with_the_number_of_segments(text, world):
     one = T.VectorSide(text, (1500,), graphs=False, seed=19)
