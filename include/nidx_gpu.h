@@ -65,6 +65,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_JSON_PREFILTER 256 /* nidx_gpu_json_*, nidx_gpu_prefilter_rows_combine / _state / _read_resources */
 #define NIDX_FEATURE_VECTOR_ROUTED_TICKETS 512 /* nidx_gpu_vector_search_submit_filtered_per_query_async, nidx_gpu_vector_search_wait_routed, nidx_gpu_use_hnsw_threshold, nidx_gpu_vector_routed_stats */
 #define NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS 1024 /* nidx_gpu_vector_search_submit_prefiltered_per_query_async, nidx_gpu_vector_prefiltered_ticket_stats */
+#define NIDX_FEATURE_PREFILTER_RESOURCE_PARTS 2048 /* nidx_gpu_prefilter_link_set_resources, nidx_gpu_prefilter_term_link_set_resources, their _read_resources */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1074,8 +1075,8 @@ int32_t nidx_gpu_prefilter_link_read(const nidx_gpu_prefilter_link_t *link, uint
                                      uint64_t capacity, uint64_t *n_out);
 
 typedef struct nidx_gpu_prefilter_search_stats {
-    uint32_t rows_projected;       /* distinct prefilter rows projected, over all chunks and deep programs */
-    uint32_t projection_launches;  /* one per chunk that names a row, plus one per deep program and segment with the op */
+    uint32_t rows_projected;       /* distinct prefilter rows — (field row, resource row) pairs — projected, over all chunks and deep programs */
+    uint32_t projection_launches;  /* one per chunk that names a row, plus one per deep program and segment with the op; one more each when a resource row is named */
     uint32_t chunks;               /* chunks of queries the batch was cut into */
     uint32_t filter_synchronisations; /* stream synchronisations of the filter stage (one per chunk, one per deep program and segment) */
     uint64_t documents_visited;    /* set bits of the projected rows */
@@ -1118,7 +1119,7 @@ typedef struct nidx_gpu_vector_prefiltered_ticket_stats {
     uint64_t batches_flagged;           /* routed batches answered by the blocking prefiltered search at wait (an overflowed walk) */
     uint64_t submit_synchronisations;   /* stream or event synchronisations made inside routed submits */
     uint64_t rows_projected;            /* distinct Some rows the routed batches projected */
-    uint64_t projection_launches;       /* one per routed batch that names a Some row */
+    uint64_t projection_launches;       /* one per routed batch that names a Some row, one more when it names a resource row */
     uint64_t filter_launches;           /* memset, projection, scatter and combine of the routed batches' filter stages: <= 4 each */
     uint64_t documents_visited;         /* set bits of the projected rows, read at wait */
     uint64_t paragraphs_written;        /* paragraph ids ORed into operand rows, read at wait */
@@ -1174,7 +1175,7 @@ int32_t nidx_gpu_prefilter_term_link_read(const nidx_gpu_prefilter_term_link_t *
 
 typedef struct nidx_gpu_bm25_prefilter_search_stats {
     uint32_t rows_projected;      /* distinct prefilter rows the call names (the shared row of the All requests not counted) */
-    uint32_t projection_launches; /* one per resident segment */
+    uint32_t projection_launches; /* one per resident segment, one more each when a row set names a resource part */
     uint32_t compaction_launches; /* one per resident segment, over all distinct rows */
     uint32_t reserved;
     uint64_t documents_visited;   /* set bits of the projected rows, once per resident segment */
@@ -1237,8 +1238,46 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
  *    ("stale link"), JSON rows of another JSON index than the link's, a request index out of range, an unknown op.
  *
  * A combined handle whose request has no resource part is an ordinary field-row handle to both prefiltered searches.  A filter or term
- * set that names a request WITH a resource-granular part is refused before any launch with NIDX_ERR_UNSUPPORTED (the message names
- * the request); the other requests of the handle remain usable. */
+ * set that names a request WITH a resource-granular part is answered through the RESOURCE HALF of the search's link (below); through
+ * a link that has none it is refused before any launch with NIDX_ERR_UNSUPPORTED (the message names the request), and the other
+ * requests of the handle remain usable.
+ *
+ * ---- resource-granular parts on the device (present when nidx_gpu_build_features() & NIDX_FEATURE_PREFILTER_RESOURCE_PARTS) ----------
+ * Both links take a resource half, given once per pair of generations like the link itself.  A second call replaces the half; a
+ * refused call leaves the link as it was.  Like freeing the link, setting the half must not happen while a ticket that names the link
+ * is outstanding.  The JSON index is known by the serial number it got at nidx_gpu_json_open (never by its address, which a later
+ * open may reuse); a combined rows handle carries the serial number of the index its resource rows are over.
+ *
+ * 1. nidx_gpu_prefilter_link_set_resources: resource_key_*[r] is the key PREFIX of resource ordinal r of the JSON index's resource
+ *    table (nidx_gpu_json_resources_read order) in the encoding of the vector segments' key tables, which stays the caller's; an
+ *    empty prefix links to nothing.  List j of a segment belongs to the resource when key j STARTS WITH the prefix (every field of
+ *    the resource).  That is the documented intent of nidx_vector/src/searcher.rs:300-313; filter_clause as written compares
+ *    differently, and DESIGN-LOG.md records why the intent is followed here, as the Python mirror does.  A resource's lists in one
+ *    segment are one range of the sorted key table, so the half is a CSR over resource ordinals with entries (vector segment, first
+ *    list, n lists), non-empty ranges only, filled on the device.  NIDX_ERR_INVALID_ARGUMENT: n_resources is not the table's size,
+ *    the JSON index is on another device, vector_index is not in the generation the link was built for, descending offsets.
+ *    nidx_gpu_prefilter_link_read_resources: for tests, the (resource, first list, n lists) ranges of one vector segment, ascending
+ *    by resource.
+ *
+ *    NIDX_FILTER_PUSH_PREFILTER of a request with parts then pushes the UNION of the paragraphs in lists linked to the set documents
+ *    of its field row and the paragraphs in the lists of the set resources of its resource row.  Distinct operands are keyed by the
+ *    pair (field row, resource row); the resource rows of a chunk are projected by ONE more launch (vector_prefilter.hip) into the
+ *    operand rows the field projection ORs into.  This holds for nidx_gpu_vector_search_prefiltered_per_query (deep programs project
+ *    their own pair) and nidx_gpu_vector_search_submit_prefiltered_per_query_async (five filter-stage launches at most for a batch
+ *    that names a resource part; the repair at wait answers from the same link and rows); the coalescer and maxsim forms take no
+ *    prefilter rows at all.  In the stats rows_projected counts each distinct pair once, documents_visited includes the set
+ *    resources, paragraphs_written the ids written for them, projection_launches every projection launch.  Before any launch or
+ *    write (the message names the filter): NIDX_ERR_INVALID_ARGUMENT when the rows' resource part is of another JSON index than
+ *    the link's half or of another row width; NIDX_ERR_UNSUPPORTED, as above, when the link has no half.
+ *
+ * 2. nidx_gpu_prefilter_term_link_set_resources: resource_terms[r] is the paragraph index's `uuid` term of resource r (UINT32_MAX:
+ *    none), resolved by the caller (nidx_paragraph/src/search_query.rs:105-139 puts resource-granular entries into the SetQuery over
+ *    the uuid field).  NIDX_ERR_INVALID_ARGUMENT: a term id >= n_terms, n_resources is not the table's size, another device,
+ *    paragraph_index is not in the generation the link was built for.  _read_resources: for tests, the term of every resource.
+ *    A row set of nidx_gpu_bm25_search_prefiltered that names a request with parts is then the union of the posting lists linked
+ *    through the field row and the uuid lists of the set resources: one more projection launch per resident segment into the same
+ *    bitset, the same single compaction, and every output equal to the same call with the set spelled out as terms.  The checks
+ *    mirror the vector side's (the message names the term set). */
 #define NIDX_JSON_MAX_INTERVALS 512 /* distinct intervals of one (segment, column) per launch (they sit in LDS) */
 enum { NIDX_JSON_STR = 0, NIDX_JSON_I64 = 1, NIDX_JSON_F64 = 2, NIDX_JSON_BOOL = 3, NIDX_JSON_DATE = 4 };
 enum { NIDX_PREFILTER_AND = 0, NIDX_PREFILTER_OR = 1 };
@@ -1341,6 +1380,31 @@ int32_t nidx_gpu_prefilter_rows_combine(const nidx_gpu_prefilter_rows_t *text_ro
 int32_t nidx_gpu_prefilter_rows_state(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint32_t *state_out, uint32_t *parts_out);
 int32_t nidx_gpu_prefilter_rows_read_resources(const nidx_gpu_prefilter_rows_t *rows, uint32_t request, uint32_t *out_resources,
                                                uint64_t capacity, uint64_t *n_out);
+
+/* the resource halves of the two links (the comment block above) */
+typedef struct nidx_gpu_prefilter_resource_link_stats {
+    uint64_t linked_resources; /* resources with at least one range */
+    uint64_t ranges;           /* (vector segment, first list, n lists) entries */
+    uint64_t lists;            /* posting lists the ranges reach */
+    uint64_t bytes;            /* HBM the resource half takes */
+} nidx_gpu_prefilter_resource_link_stats_t;
+typedef struct nidx_gpu_prefilter_resource_term_link_stats {
+    uint64_t linked_resources; /* resources with a term */
+    uint64_t postings;         /* postings of their lists over all resident segments */
+    uint64_t bytes;
+    uint64_t paragraph_generation;
+} nidx_gpu_prefilter_resource_term_link_stats_t;
+int32_t nidx_gpu_prefilter_link_set_resources(nidx_gpu_prefilter_link_t *link, nidx_gpu_vector_index_t *vector_index,
+                                              nidx_gpu_json_index_t *json_index, const uint8_t *resource_key_bytes,
+                                              const uint64_t *resource_key_offsets /* [n_resources + 1] */, uint64_t n_resources,
+                                              nidx_gpu_prefilter_resource_link_stats_t *stats_out);
+int32_t nidx_gpu_prefilter_link_read_resources(const nidx_gpu_prefilter_link_t *link, uint32_t vector_segment, uint32_t *out_resource,
+                                               uint32_t *out_first_list, uint32_t *out_n_lists, uint64_t capacity, uint64_t *n_out);
+int32_t nidx_gpu_prefilter_term_link_set_resources(nidx_gpu_prefilter_term_link_t *link, nidx_gpu_bm25_index_t *paragraph_index,
+                                                   nidx_gpu_json_index_t *json_index, const uint32_t *resource_terms /* [n_resources] */,
+                                                   uint64_t n_resources, nidx_gpu_prefilter_resource_term_link_stats_t *stats_out);
+int32_t nidx_gpu_prefilter_term_link_read_resources(const nidx_gpu_prefilter_term_link_t *link, uint32_t *out_terms, uint64_t capacity,
+                                                    uint64_t *n_out);
 
 /* open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74), the device half: the caller maps the deletion keys that
  * are newer than the segment (`Seq(segment) < del_seq`) to term ids the way the DeletionQueryBuilders do (a key longer than 32

@@ -167,6 +167,7 @@ FEATURE_PARAGRAPH_PREFILTER_HANDOVER = 128   # nidx_gpu_build_features() bit: th
 FEATURE_JSON_PREFILTER = 256   # nidx_gpu_build_features() bit: the resident JSON index, its prefilter batch, the resource link, nidx_gpu_prefilter_rows_combine
 FEATURE_VECTOR_ROUTED_TICKETS = 512   # nidx_gpu_build_features() bit: per-query filter tickets routed on the device, nidx_gpu_use_hnsw_threshold
 FEATURE_VECTOR_PREFILTERED_TICKETS = 1024   # nidx_gpu_build_features() bit: routed tickets whose programs push resident prefilter rows
+FEATURE_PREFILTER_RESOURCE_PARTS = 2048   # nidx_gpu_build_features() bit: the links' resource halves (resource-granular prefilter parts on the device)
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -227,6 +228,16 @@ class PrefilterTermLinkStatsC(C.Structure):
     """nidx_gpu_prefilter_term_link_stats_t"""
     _fields_ = [("linked_documents", C.c_uint64), ("postings", C.c_uint64), ("bytes", C.c_uint64), ("text_generation", C.c_uint64),
                 ("paragraph_generation", C.c_uint64)]
+
+
+class PrefilterResourceLinkStatsC(C.Structure):
+    """nidx_gpu_prefilter_resource_link_stats_t"""
+    _fields_ = [("linked_resources", C.c_uint64), ("ranges", C.c_uint64), ("lists", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class PrefilterResourceTermLinkStatsC(C.Structure):
+    """nidx_gpu_prefilter_resource_term_link_stats_t"""
+    _fields_ = [("linked_resources", C.c_uint64), ("postings", C.c_uint64), ("bytes", C.c_uint64), ("paragraph_generation", C.c_uint64)]
 
 
 class Bm25PrefilterSearchStatsC(C.Structure):
@@ -482,6 +493,12 @@ SIGNATURES = {
     "nidx_gpu_prefilter_term_link_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p),
                                                         C.POINTER(PrefilterTermLinkStatsC)]),
     "nidx_gpu_prefilter_term_link_free": (None, [C.c_void_p]),
+    "nidx_gpu_prefilter_link_set_resources": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                          C.POINTER(PrefilterResourceLinkStatsC)]),
+    "nidx_gpu_prefilter_link_read_resources": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_prefilter_term_link_set_resources": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                               C.POINTER(PrefilterResourceTermLinkStatsC)]),
+    "nidx_gpu_prefilter_term_link_read_resources": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nidx_gpu_prefilter_term_link_read": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nidx_gpu_bm25_search_prefiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                      C.POINTER(Bm25SearchOptionsC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

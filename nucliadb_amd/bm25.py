@@ -286,6 +286,24 @@ class PrefilterTermLink:
         _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_read(self.handle, text_segment, out.ctypes.data, n.value, C.byref(n)))
         return out[: n.value]
 
+    def set_resources(self, paragraph_handle, json_handle, resource_terms) -> "_lib.PrefilterResourceTermLinkStatsC":
+        """The resource half (nidx_gpu_prefilter_term_link_set_resources): resource_terms[r] is the paragraph index's `uuid` term of
+        resource r of the JSON index's table (0xFFFFFFFF: none).  Not while a ticket that names the link is outstanding."""
+        terms = np.ascontiguousarray(resource_terms, dtype=np.uint32)
+        stats = _lib.PrefilterResourceTermLinkStatsC()
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_set_resources(self.handle, paragraph_handle, json_handle, terms.ctypes.data if terms.size else None,
+                                                                         terms.size, C.byref(stats)))
+        self.resource_stats = stats
+        return stats
+
+    def read_resources(self) -> np.ndarray:
+        """The term of every resource ordinal (0xFFFFFFFF: none), read back from the device: tests."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_read_resources(self.handle, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), np.uint32)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_read_resources(self.handle, out.ctypes.data, n.value, C.byref(n)))
+        return out[: n.value]
+
     def close(self):
         if self.handle:
             _lib.lib().nidx_gpu_prefilter_term_link_free(self.handle)

@@ -1680,6 +1680,10 @@ struct Bm25RowSets {
     const PrefilterRows *rows = nullptr;
     std::vector<uint32_t> row_of_set;   // [n_term_sets]; UINT32_MAX: an ordinary term set (a row set of a None request is one: empty)
     std::vector<uint32_t> distinct;     // rows->row_ptr index of every distinct row, kPrefilterRowAll for the shared row of the All requests
+    // a request with a resource part is keyed by the pair (field row, resource row): distinct[r] may then be kPrefilterRowNone (no
+    // field part), distinct_res[r] is its rows->res_row_ptr index (kPrefilterRowNone: no resource part)
+    std::vector<uint32_t> distinct_res;
+    bool any_res = false;
     nidx_gpu_bm25_prefilter_search_stats_t stats = {};
 };
 
@@ -1944,7 +1948,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         std::vector<unsigned long long> out_off(n_aux + 1, 0);
         // a projected row holds at most the postings the link reaches in this segment, and at most every document
         const uint64_t row_bound = !n_rows_d ? 0 : rs->distinct.back() == kPrefilterRowAll ? (uint64_t)seg.n_docs
-                                                 : std::min<uint64_t>(seg.n_docs, rs->link->segment_postings[s]);
+                                                 : std::min<uint64_t>(seg.n_docs, rs->link->segment_postings[s] + (rs->any_res ? rs->link->res_segment_postings[s] : 0));
         std::vector<PhraseDev> phrases(n_phrases);
         for (uint32_t j = 0; j < n_sets; j++) {
             uint64_t df = 0;
@@ -2064,15 +2068,29 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
             }
             if (n_proj) {
-                cx.w_row_ptrs.resize(n_proj);
-                for (uint32_t r = 0; r < n_proj; r++) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]];
-                NIDX_HIP(cx.s_row_ptrs.reserve((size_t)n_proj * sizeof(uint64_t *)));
-                NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), (size_t)n_proj * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
-                NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, (uint32_t)rs->rows->layout.words(),
-                                                       rs->link->doc_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
-                                                       seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
-                                                       cx.s_row_stats.as<unsigned long long>(), cx.stream));
-                rs->stats.projection_launches++;
+                // [n_proj field rows | n_proj resource rows]; nullptr: the row set has no such part
+                cx.w_row_ptrs.assign((size_t)n_proj * (rs->any_res ? 2 : 1), nullptr);
+                bool any_field = false;
+                for (uint32_t r = 0; r < n_proj; r++) {
+                    if (rs->distinct[r] != kPrefilterRowNone) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]], any_field = true;
+                    if (rs->any_res && rs->distinct_res[r] != kPrefilterRowNone) cx.w_row_ptrs[n_proj + r] = rs->rows->res_row_ptr[rs->distinct_res[r]];
+                }
+                NIDX_HIP(cx.s_row_ptrs.reserve(cx.w_row_ptrs.size() * sizeof(uint64_t *)));
+                NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), cx.w_row_ptrs.size() * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
+                if (any_field) {
+                    NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, (uint32_t)rs->rows->layout.words(),
+                                                           rs->link->doc_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
+                                                           seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
+                                                           cx.s_row_stats.as<unsigned long long>(), cx.stream));
+                    rs->stats.projection_launches++;
+                }
+                if (rs->any_res) {   // the uuid lists of the set resources, into the same bitsets: one more launch
+                    NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>() + n_proj, n_proj, (uint32_t)rs->rows->res_words,
+                                                           rs->link->res_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
+                                                           seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
+                                                           cx.s_row_stats.as<unsigned long long>(), cx.stream));
+                    rs->stats.projection_launches++;
+                }
             }
             NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, cx.s_aux_out_off.as<unsigned long long>() + n_own,
                                            cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_own, cx.stream));
@@ -2641,6 +2659,7 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
         if (!opt->term_set_offsets) return fail(NIDX_ERR_INVALID_ARGUMENT, "term sets without offsets");
         rs.row_of_set.assign(n_sets, 0xffffffffu);
         std::vector<uint32_t> slot_of_row;   // row -> its place in rs.distinct
+        std::map<std::pair<uint32_t, uint32_t>, uint32_t> slot_of_pair;   // (field row, resource row) of a request with parts -> its place
         bool any_all = false;
         for (uint32_t j = 0; j < n_sets; j++) {
             const uint32_t q = prefilter_of_term_set[j];
@@ -2661,15 +2680,33 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
                             (unsigned long long)r->generation, (unsigned long long)l->text_generation);
             if (q >= r->row_of_request.size())
                 return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u: request %u of %zu", j, q, r->row_of_request.size());
-            if (r->has_resources(q))   // (projecting resource rows needs a link to the paragraph index's uuid terms: DESIGN.md §8 item 5)
-                return fail(NIDX_ERR_UNSUPPORTED, "term set %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", j, q);
             const uint32_t row = r->row_of_request[q];
+            if (r->has_resources(q)) {   // (projected through the link's resource half)
+                if (!l->json_uid)
+                    return fail(NIDX_ERR_UNSUPPORTED, "term set %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", j, q);
+                if (r->res_index_uid != l->json_uid)
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u names prefilter request %u, whose resource part is of another JSON index than the link's resource half", j, q);
+                if (r->res_words != l->res_words)
+                    return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u names prefilter request %u, whose resource rows have %llu words, the link's resource half %llu", j, q,
+                                (unsigned long long)r->res_words, (unsigned long long)l->res_words);
+                if (row != kPrefilterRowAll) {   // keyed by the pair (field row, resource row)
+                    const auto it = slot_of_pair.emplace(std::make_pair(row, r->res_row_of_request[q]), (uint32_t)rs.distinct.size());
+                    if (it.second) {
+                        rs.distinct.push_back(row);
+                        rs.distinct_res.push_back(r->res_row_of_request[q]);
+                        rs.any_res = true;
+                    }
+                    rs.row_of_set[j] = it.first->second;
+                    continue;
+                }
+            }
             if (row == kPrefilterRowNone) continue;   // the empty set: the term set as it stands
             if (row == kPrefilterRowAll) { any_all = true; rs.row_of_set[j] = 0xfffffffeu; continue; }   // (placed below)
             if (slot_of_row.empty()) slot_of_row.assign(r->row_ptr.size(), 0xffffffffu);
             if (slot_of_row[row] == 0xffffffffu) {
                 slot_of_row[row] = (uint32_t)rs.distinct.size();
                 rs.distinct.push_back(row);
+                rs.distinct_res.push_back(kPrefilterRowNone);
             }
             rs.row_of_set[j] = slot_of_row[row];
         }
@@ -2677,12 +2714,14 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
             for (uint32_t &x : rs.row_of_set)
                 if (x == 0xfffffffeu) x = (uint32_t)rs.distinct.size();
             rs.distinct.push_back(kPrefilterRowAll);   // last: bm25_search_locked fills it with ones
+            rs.distinct_res.push_back(kPrefilterRowNone);
         }
         if (rs.distinct.size() > 65535) return fail(NIDX_ERR_UNSUPPORTED, "more than 65535 distinct prefilter rows in one search call");
         // the rows' scratch, as bm25_search_locked lays it out per resident segment: a bitset and a list region per distinct row
         const uint64_t scratch_max = idx->row_scratch_max;   // (read at open)
         for (size_t s = 0; s < idx->segs.size(); s++) {
-            const uint64_t n_docs = idx->segs[s].n_docs, bound = any_all ? n_docs : std::min<uint64_t>(n_docs, l->segment_postings[s]);
+            const uint64_t n_docs = idx->segs[s].n_docs,
+                           bound = any_all ? n_docs : std::min<uint64_t>(n_docs, l->segment_postings[s] + (rs.any_res ? l->res_segment_postings[s] : 0));
             const uint64_t bytes = (uint64_t)rs.distinct.size() * ((n_docs + 63) / 64 * 8 + bound * 4);
             if (bytes > scratch_max)
                 return fail(NIDX_ERR_UNSUPPORTED, "%zu distinct prefilter rows need %llu bytes of scratch on resident segment %zu (at most %llu): split the batch",

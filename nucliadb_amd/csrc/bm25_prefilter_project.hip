@@ -15,6 +15,11 @@ namespace nidx {
 // the zero ones by ballot and spreads the set bits of a word over its lanes; a set document whose linked term is not UINT32_MAX ORs
 // the doc ids of that term's posting list into output row blockIdx.y — a list of more than 64 postings by the whole wave, a shorter
 // one by its lane.  Two documents linked to the same term write the same bits twice: the OR makes that harmless.
+//
+// The RESOURCE part of a row set (search_query.rs:105-139: resource-granular entries go into the SetQuery over the `uuid` field) is the
+// same projection one level up: rows over resource ordinals, `doc_term` the link's uuid term of every resource ordinal, output row
+// blockIdx.y again — a second launch of this kernel per resident segment ORs it into the bitset the field part went into.  A row
+// pointer of nullptr is a row set without a part of the launch's kind.
 __global__ __launch_bounds__(256) void bm25_prefilter_project_kernel(const uint64_t *const *__restrict__ rows, uint32_t n_words,
                                                                      const uint32_t *__restrict__ doc_term,
                                                                      const unsigned long long *__restrict__ term_offsets,
@@ -25,6 +30,7 @@ __global__ __launch_bounds__(256) void bm25_prefilter_project_kernel(const uint6
     const uint64_t w = (uint64_t)span * 64u + lane;
     if ((uint64_t)span * 64u >= n_words) return;                  // (uniform per wave)
     const uint64_t *row = rows[blockIdx.y];
+    if (!row) return;                                             // (uniform per block: the row set has no part of this kind)
     const uint64_t word = w < n_words ? row[w] : 0ull;
     unsigned int *o = out32 + (unsigned long long)blockIdx.y * out_words * 2ull;
     unsigned long long nz = __ballot(word != 0ull);

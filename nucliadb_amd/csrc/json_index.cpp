@@ -77,6 +77,15 @@ uint64_t list_bits(const std::vector<uint64_t> &host, uint32_t *out, uint64_t ca
 }
 }  // namespace
 
+namespace nidx {
+int32_t json_index_identity(nidx_gpu_json_index_t *index, uint64_t &uid, int &device, uint64_t &n_resources) {
+    JsonIndex *idx = reinterpret_cast<JsonIndex *>(index);
+    std::lock_guard<std::mutex> lock(idx->mu);
+    uid = idx->uid, device = idx->device, n_resources = idx->n_resources();
+    return NIDX_OK;
+}
+}  // namespace nidx
+
 extern "C" {
 
 int32_t nidx_gpu_json_open(const nidx_gpu_json_segment_t *segments, uint32_t n_segments, nidx_gpu_json_index_t **index_out,
@@ -467,6 +476,7 @@ int32_t nidx_gpu_prefilter_rows_combine(const nidx_gpu_prefilter_rows_t *text_ro
     out->layout = L->layout;
     out->res_owner = J->chunks;
     out->res_words = J->res_words;
+    out->res_index_uid = J->index_uid;
     out->row_of_request.assign(n_requests, kPrefilterRowNone);
     out->res_row_of_request.assign(n_requests, kPrefilterRowNone);
     const uint64_t W = L->layout.words();

@@ -477,6 +477,21 @@ struct PrefilterProjSeg {
 // stats[0] += documents visited, stats[1] += paragraph ids written.
 hipError_t launch_prefilter_project(const uint64_t *const *rows, uint32_t n_rows, uint32_t n_words, const uint32_t *doc_off, const uint2 *entries,
                                     const PrefilterProjSeg *segs, uint64_t *out, unsigned long long *stats, hipStream_t s);
+// The resource half of the link: per vector segment over a chunk of resources whose key prefixes sit in qb / q_off, resource r is
+// linked to the ONE range of lists whose key starts with its prefix (an empty prefix, or an empty range: nothing).
+//   count: counts[r] += 1 per non-empty range                     fill: ranges[res_off[r] + cursor[r]++] = (segment, first list, n lists)
+struct PrefilterResRange {
+    uint32_t segment, first, n;
+};
+hipError_t launch_prefilter_resource_link(const uint8_t *tbl, const unsigned long long *tbl_off, uint32_t n_keys, const uint8_t *qb,
+                                          const unsigned long long *q_off, uint32_t n_q, uint32_t segment, uint32_t *counts,
+                                          const uint32_t *res_off /* nullptr: count */, PrefilterResRange *ranges, hipStream_t s);
+// Projects RESOURCE rows (bitsets over resource ordinals, n_words words each) through the resource half: same grid, same output rows and
+// same counters as launch_prefilter_project (stats[0] += set resources); rows[j] == nullptr: operand j has no resource part.  The field
+// projection passes a nullptr row by in the same way.
+hipError_t launch_prefilter_project_resources(const uint64_t *const *rows, uint32_t n_rows, uint32_t n_words, const uint32_t *res_off,
+                                              const PrefilterResRange *ranges, const PrefilterProjSeg *segs, uint64_t *out,
+                                              unsigned long long *stats, hipStream_t s);
 // The paragraph half (bm25_prefilter_project.hip): projects prefilter rows onto ONE resident segment of the paragraph index through
 // doc_term (the paragraph index's term id of every bit position of a row, UINT32_MAX = none): grid = (64-word spans of a row, rows),
 // one wave per span, zero words skipped by ballot; every set document ORs the doc ids of its term's posting list into output row

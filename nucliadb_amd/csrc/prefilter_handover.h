@@ -52,6 +52,7 @@ struct PrefilterRows {
     std::vector<const uint64_t *> res_row_ptr;  // [resource rows] in HBM, res_words words each
     std::vector<uint32_t> res_row_of_request;   // empty, or per request a resource row or kPrefilterRowNone
     uint64_t res_words = 0;
+    uint64_t res_index_uid = 0;                 // the JSON index the resource rows are over (its serial number, json_index.cpp)
     bool has_resources(uint32_t request) const {
         return request < res_row_of_request.size() && res_row_of_request[request] != kPrefilterRowNone;
     }
@@ -67,6 +68,11 @@ struct PrefilterLink {
     DevBuf doc_off;                        // [words * 64 + 1] u32
     DevBuf entries;                        // [n_entries] (vector segment, list)
     uint64_t n_entries = 0, linked_documents = 0;
+    // the resource half (nidx_gpu_prefilter_link_set_resources): CSR over the bit positions of a RESOURCE row; a resource's lists in
+    // one segment are one range of the sorted key table, only non-empty ranges are stored.  json_uid == 0: none yet
+    uint64_t json_uid = 0, n_resources = 0, res_words = 0, n_res_ranges = 0, linked_resources = 0, res_lists = 0;
+    DevBuf res_off;                        // [res_words * 64 + 1] u32
+    DevBuf res_ranges;                     // [n_res_ranges] PrefilterResRange
 };
 
 // nidx_gpu_prefilter_term_link_t: the paragraph index's term id of every bit position of a row (UINT32_MAX: none)
@@ -77,6 +83,11 @@ struct PrefilterTermLink {
     DevBuf doc_term;                       // [words * 64] u32
     std::vector<uint64_t> segment_postings;   // [resident paragraph segment] postings reachable through the link
     uint64_t linked_documents = 0, postings = 0;
+    // the resource half (nidx_gpu_prefilter_term_link_set_resources): the paragraph index's uuid term of every bit position of a
+    // RESOURCE row (UINT32_MAX: none).  json_uid == 0: none yet
+    uint64_t json_uid = 0, n_resources = 0, res_words = 0, linked_resources = 0, res_postings = 0;
+    DevBuf res_term;                           // [res_words * 64] u32
+    std::vector<uint64_t> res_segment_postings;   // [resident paragraph segment] postings reachable through the resource terms
 };
 
 // bm25_index.cpp: the layout, device and generation of an open index (takes the index's lock)
@@ -85,5 +96,8 @@ int32_t bm25_prefilter_row_layout(nidx_gpu_bm25_index_t *index, PrefilterRowLayo
 // positions (UINT32_MAX: none; any other id must be below the index's n_terms) the postings they reach in every resident segment
 int32_t bm25_term_link_target(nidx_gpu_bm25_index_t *index, const std::vector<uint32_t> &doc_term, int &device, uint64_t &generation,
                               std::vector<uint64_t> &segment_postings);
+
+// json_index.cpp: the identity (serial number given at nidx_gpu_json_open), device and resource table size of an open JSON index
+int32_t json_index_identity(nidx_gpu_json_index_t *index, uint64_t &uid, int &device, uint64_t &n_resources);
 
 }  // namespace nidx

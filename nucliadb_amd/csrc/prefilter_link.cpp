@@ -174,6 +174,126 @@ int32_t nidx_gpu_prefilter_link_read(const nidx_gpu_prefilter_link_t *link, uint
     return NIDX_OK;
 } NIDX_ABI_CATCH
 
+// ---- the resource half: resource ordinal of a JSON index -> its lists in every vector segment ----------------------------------------
+// A resource's lists are the keys that start with its prefix (every field of it): ONE range of a segment's sorted key table, so the CSR
+// holds (vector segment, first list, n lists) and only the non-empty ranges.  Built like the document half: per chunk and vector
+// segment one launch counts, the counts are scanned on the host, the same launches fill.  The new half replaces the old one only when
+// everything has succeeded.
+int32_t nidx_gpu_prefilter_link_set_resources(nidx_gpu_prefilter_link_t *link, nidx_gpu_vector_index_t *vector_index,
+                                              nidx_gpu_json_index_t *json_index, const uint8_t *resource_key_bytes,
+                                              const uint64_t *resource_key_offsets, uint64_t n_resources,
+                                              nidx_gpu_prefilter_resource_link_stats_t *stats_out) try {
+    PrefilterLink *l = reinterpret_cast<PrefilterLink *>(link);
+    VectorIndex *vec = reinterpret_cast<VectorIndex *>(vector_index);
+    if (!l || !vec || !json_index || (n_resources && !resource_key_offsets)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t uid = 0, table = 0;
+    int json_device = 0;
+    if (int32_t rc = json_index_identity(json_index, uid, json_device, table)) return rc;
+    if (json_device != l->device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link is on device %d, the JSON index on device %d", l->device, json_device);
+    if (n_resources != table)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "keys for %llu resources, the JSON index has %llu", (unsigned long long)n_resources, (unsigned long long)table);
+    for (uint64_t r = 0; r < n_resources; r++)
+        if (resource_key_offsets[r + 1] < resource_key_offsets[r])
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "resource key offsets decrease at resource %llu", (unsigned long long)r);
+    if (n_resources && resource_key_offsets[n_resources] > resource_key_offsets[0] && !resource_key_bytes) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL resource keys");
+    GenShared gen(vec->gate);
+    std::lock_guard<std::mutex> lock(vec->mu);
+    if (vec->device != l->device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link is on device %d, the vector index on device %d", l->device, vec->device);
+    bool stale = l->vector_generation != vec->gate.generation.load() || l->n_vector_segments != vec->segs.size();
+    for (size_t s = 0; s < vec->segs.size() && !stale; s++) stale = l->segment_lists[s] != vec->segs[s].f_n_lists;
+    if (stale)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the vector index, which is in generation %llu (build it again)",
+                    (unsigned long long)l->vector_generation, (unsigned long long)vec->gate.generation.load());
+    const uint64_t res_words = (n_resources + 63) / 64, n_bits = res_words * 64;
+    if (n_bits + 1 > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a resource row of more than 2^32 - 2 bits");
+    NIDX_HIP(hipSetDevice(vec->device));
+    hipStream_t st = vec->stream;
+
+    // the prefixes, rebased to offset 0 (the bits behind the last resource: empty prefixes)
+    std::vector<unsigned long long> offsets((size_t)n_bits + 1, 0);
+    const uint64_t base = n_resources ? resource_key_offsets[0] : 0, n_bytes = n_resources ? resource_key_offsets[n_resources] - base : 0;
+    for (uint64_t r = 0; r <= n_bits; r++) offsets[(size_t)r] = r <= n_resources ? resource_key_offsets[r] - base : n_bytes;
+    DevBuf res_off, res_ranges, counts, d_keys, d_koff;
+    NIDX_HIP(res_off.alloc((size_t)(n_bits + 1) * 4));
+    NIDX_HIP(counts.alloc(std::max<size_t>((size_t)n_bits, 1) * 4));
+    NIDX_HIP(d_koff.alloc(offsets.size() * 8));
+    NIDX_HIP(hipMemcpyAsync(d_koff.p, offsets.data(), offsets.size() * 8, hipMemcpyHostToDevice, st));
+    if (n_bytes) {
+        NIDX_HIP(d_keys.alloc((size_t)n_bytes));
+        NIDX_HIP(hipMemcpyAsync(d_keys.p, resource_key_bytes + base, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+    }
+    std::vector<uint32_t> host_off((size_t)n_bits + 1, 0);
+    uint64_t total = 0, linked = 0, lists = 0;
+    for (int fill = 0; fill < 2 && n_bytes; fill++) {
+        NIDX_HIP(hipMemsetAsync(counts.p, 0, (size_t)n_bits * 4, st));
+        for (size_t v = 0; v < vec->segs.size(); v++) {
+            const VectorSegment &seg = vec->segs[v];
+            if (!seg.f_n_keys || !seg.f_key_offsets.p) continue;   // no key table: links to nothing
+            NIDX_HIP(launch_prefilter_resource_link(seg.f_key_bytes.as<uint8_t>(), seg.f_key_offsets.as<unsigned long long>(), seg.f_n_keys,
+                                                    d_keys.as<uint8_t>(), d_koff.as<unsigned long long>(), (uint32_t)n_resources, (uint32_t)v,
+                                                    counts.as<uint32_t>(), fill ? res_off.as<uint32_t>() : nullptr, res_ranges.as<PrefilterResRange>(), st));
+        }
+        if (fill) break;
+        // scan: the counts come back, their prefix sums go up
+        std::vector<uint32_t> host_counts((size_t)n_bits, 0);
+        NIDX_HIP(hipMemcpyAsync(host_counts.data(), counts.p, (size_t)n_bits * 4, hipMemcpyDeviceToHost, st));
+        NIDX_HIP(hipStreamSynchronize(st));
+        for (uint64_t b = 0; b < n_bits; b++) {
+            host_off[(size_t)b] = (uint32_t)total;
+            total += host_counts[(size_t)b];
+            linked += host_counts[(size_t)b] ? 1 : 0;
+        }
+        host_off[(size_t)n_bits] = (uint32_t)total;   // (at most one range per resource and segment: far below 2^32)
+        NIDX_HIP(hipMemcpyAsync(res_off.p, host_off.data(), host_off.size() * 4, hipMemcpyHostToDevice, st));
+        NIDX_HIP(res_ranges.alloc(std::max<uint64_t>(total, 1) * sizeof(PrefilterResRange)));
+        if (!total) break;
+    }
+    if (!total) NIDX_HIP(hipMemcpyAsync(res_off.p, host_off.data(), host_off.size() * 4, hipMemcpyHostToDevice, st));
+    if (!res_ranges.p) NIDX_HIP(res_ranges.alloc(sizeof(PrefilterResRange)));
+    std::vector<PrefilterResRange> host_ranges((size_t)total);
+    if (total) NIDX_HIP(hipMemcpyAsync(host_ranges.data(), res_ranges.p, (size_t)total * sizeof(PrefilterResRange), hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));
+    for (const PrefilterResRange &rg : host_ranges) lists += rg.n;
+    // ---- nothing can fail from here on: the new half replaces the old one
+    l->res_off = std::move(res_off);
+    l->res_ranges = std::move(res_ranges);
+    l->json_uid = uid;
+    l->res_words = res_words;
+    l->n_resources = n_resources;
+    l->n_res_ranges = total;
+    l->linked_resources = linked;
+    l->res_lists = lists;
+    if (stats_out) {
+        stats_out->linked_resources = linked;
+        stats_out->ranges = total;
+        stats_out->lists = lists;
+        stats_out->bytes = l->res_off.bytes + l->res_ranges.bytes;
+    }
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_prefilter_link_read_resources(const nidx_gpu_prefilter_link_t *link, uint32_t vector_segment, uint32_t *out_resource,
+                                               uint32_t *out_first_list, uint32_t *out_n_lists, uint64_t capacity, uint64_t *n_out) try {
+    const PrefilterLink *l = reinterpret_cast<const PrefilterLink *>(link);
+    if (!l || !n_out || (capacity && (!out_resource || !out_first_list || !out_n_lists))) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!l->json_uid) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link has no resource half");
+    if (vector_segment >= l->n_vector_segments) return fail(NIDX_ERR_INVALID_ARGUMENT, "vector segment %u of %u", vector_segment, l->n_vector_segments);
+    NIDX_HIP(hipSetDevice(l->device));
+    std::vector<uint32_t> off((size_t)l->res_words * 64 + 1, 0);
+    std::vector<PrefilterResRange> rg((size_t)l->n_res_ranges);
+    NIDX_HIP(hipMemcpy(off.data(), l->res_off.p, off.size() * 4, hipMemcpyDeviceToHost));
+    if (!rg.empty()) NIDX_HIP(hipMemcpy(rg.data(), l->res_ranges.p, rg.size() * sizeof(PrefilterResRange), hipMemcpyDeviceToHost));
+    uint64_t n = 0;
+    for (size_t r = 0; r + 1 < off.size(); r++)
+        for (uint32_t e = off[r]; e < off[r + 1]; e++) {
+            if (rg[e].segment != vector_segment) continue;
+            if (n < capacity) out_resource[n] = (uint32_t)r, out_first_list[n] = rg[e].first, out_n_lists[n] = rg[e].n;
+            n++;
+        }
+    *n_out = n;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
 // ---- the paragraph half: text document -> term of the paragraph index ---------------------------------------------------------------
 // The reference turns a prefilter's fields into the paragraph index's field_uuid terms on each request
 // (nidx_paragraph/src/search_query.rs:87-146).  Which term a text document's field has depends on the two generations only: one u32
@@ -213,6 +333,67 @@ int32_t nidx_gpu_prefilter_term_link_create(nidx_gpu_bm25_index_t *text_index, n
         stats_out->paragraph_generation = link->paragraph_generation;
     }
     *link_out = reinterpret_cast<nidx_gpu_prefilter_term_link_t *>(link.release());
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// The resource half: the paragraph index's `uuid` term of every resource ordinal of a JSON index (search_query.rs:105-139 puts the
+// resource-granular entries into the SetQuery over the uuid field).  The new half replaces the old one only when everything has succeeded.
+int32_t nidx_gpu_prefilter_term_link_set_resources(nidx_gpu_prefilter_term_link_t *link, nidx_gpu_bm25_index_t *paragraph_index,
+                                                   nidx_gpu_json_index_t *json_index, const uint32_t *resource_terms, uint64_t n_resources,
+                                                   nidx_gpu_prefilter_resource_term_link_stats_t *stats_out) try {
+    PrefilterTermLink *l = reinterpret_cast<PrefilterTermLink *>(link);
+    if (!l || !paragraph_index || !json_index || (n_resources && !resource_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t uid = 0, table = 0;
+    int json_device = 0;
+    if (int32_t rc = json_index_identity(json_index, uid, json_device, table)) return rc;
+    if (json_device != l->device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link is on device %d, the JSON index on device %d", l->device, json_device);
+    if (n_resources != table)
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "terms for %llu resources, the JSON index has %llu", (unsigned long long)n_resources, (unsigned long long)table);
+    const uint64_t res_words = (n_resources + 63) / 64;
+    std::vector<uint32_t> terms((size_t)res_words * 64, 0xffffffffu);   // (the bits behind the last resource: no term)
+    uint64_t linked = 0, postings = 0;
+    for (uint64_t r = 0; r < n_resources; r++) {
+        terms[(size_t)r] = resource_terms[r];
+        linked += resource_terms[r] != 0xffffffffu ? 1 : 0;
+    }
+    int device = 0;
+    uint64_t generation = 0;
+    std::vector<uint64_t> segment_postings;
+    if (int32_t rc = bm25_term_link_target(paragraph_index, terms, device, generation, segment_postings)) return rc;
+    if (device != l->device) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link is on device %d, the paragraph index on device %d", l->device, device);
+    if (generation != l->paragraph_generation || segment_postings.size() != l->segment_postings.size())
+        return fail(NIDX_ERR_INVALID_ARGUMENT, "stale link: built for generation %llu of the paragraph index, which is in generation %llu (build it again)",
+                    (unsigned long long)l->paragraph_generation, (unsigned long long)generation);
+    for (uint64_t p : segment_postings) postings += p;
+    NIDX_HIP(hipSetDevice(l->device));
+    DevBuf res_term;
+    NIDX_HIP(res_term.alloc(std::max<size_t>(terms.size(), 1) * 4));
+    if (!terms.empty()) NIDX_HIP(hipMemcpy(res_term.p, terms.data(), terms.size() * 4, hipMemcpyHostToDevice));
+    l->res_term = std::move(res_term);
+    l->json_uid = uid;
+    l->res_words = res_words;
+    l->n_resources = n_resources;
+    l->linked_resources = linked;
+    l->res_postings = postings;
+    l->res_segment_postings = std::move(segment_postings);
+    if (stats_out) {
+        stats_out->linked_resources = linked;
+        stats_out->postings = postings;
+        stats_out->bytes = l->res_term.bytes;
+        stats_out->paragraph_generation = l->paragraph_generation;
+    }
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_prefilter_term_link_read_resources(const nidx_gpu_prefilter_term_link_t *link, uint32_t *out_terms, uint64_t capacity,
+                                                    uint64_t *n_out) try {
+    const PrefilterTermLink *l = reinterpret_cast<const PrefilterTermLink *>(link);
+    if (!l || !n_out || (capacity && !out_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!l->json_uid) return fail(NIDX_ERR_INVALID_ARGUMENT, "the link has no resource half");
+    const uint64_t n = l->n_resources, got = std::min<uint64_t>(n, capacity);
+    NIDX_HIP(hipSetDevice(l->device));
+    if (got) NIDX_HIP(hipMemcpy(out_terms, l->res_term.p, (size_t)got * 4, hipMemcpyDeviceToHost));
+    *n_out = n;
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

@@ -927,6 +927,7 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
     }
     uint64_t launches = 0, filter_launches = 0;
     const uint32_t D = (uint32_t)L.pf_rows.size();
+    bool any_field = false, any_res = false;   // an operand of the batch has a field row / a resource row
     if (!plan.nothing) {
         // ---- queries -> HBM through the slot's pinned staging ----
         NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
@@ -952,10 +953,10 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
         NIDX_HIP(sl.pin_out.reserve(words * 4));
         uint32_t *blk = sl.d_block.as<uint32_t>();
         // ---- one upload: [segment records | program words | the queries' filters | has-program bytes] ----
-        // (a prefiltered batch adds [filter-stage records | projection records | row pointers])
+        // (a prefiltered batch adds [filter-stage records | projection records | the operands' field rows | their resource rows])
         const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + L.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
                      at_fseg = align8(at_has + S * (size_t)F), at_pseg = at_fseg + S * sizeof(FilterSegDev),
-                     at_rows = at_pseg + S * sizeof(PrefilterProjSeg), in_bytes = pf ? at_rows + D * sizeof(uint64_t *) : at_has + S * (size_t)F;
+                     at_rows = at_pseg + S * sizeof(PrefilterProjSeg), in_bytes = pf ? at_rows + 2 * D * sizeof(uint64_t *) : at_has + S * (size_t)F;
         NIDX_HIP(sl.pin_rt_in.reserve(in_bytes));
         NIDX_HIP(sl.d_rt_in.reserve(in_bytes));
         {
@@ -967,7 +968,10 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
             if (pf) {
                 filter_stage_records(L, reinterpret_cast<FilterSegDev *>(h + at_fseg), reinterpret_cast<PrefilterProjSeg *>(h + at_pseg));
                 const uint64_t **hr = reinterpret_cast<const uint64_t **>(h + at_rows);
-                for (uint32_t j = 0; j < D; j++) hr[j] = pf->rows->row_ptr[L.pf_rows[j]];
+                for (uint32_t j = 0; j < D; j++) {
+                    any_res = pf->operand_rows(L.pf_rows[j], hr[j], hr[D + j]) || any_res;
+                    any_field = any_field || hr[j];
+                }
             }
         }
         NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in_bytes, hipMemcpyHostToDevice, sl.stream));
@@ -1007,10 +1011,19 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
                     NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, L.opnd_words * 8, sl.stream));
                     filter_launches++;
                 }
-                if (D && n_words) {
-                    NIDX_HIP(launch_prefilter_project(reinterpret_cast<const uint64_t *const *>(din + at_rows), D, n_words, pf->link->doc_off.as<uint32_t>(),
-                                                      pf->link->entries.as<uint2>(), reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg),
-                                                      sl.d_rt_operands.as<uint64_t>(), reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
+                const uint64_t *const *d_rows = reinterpret_cast<const uint64_t *const *>(din + at_rows);
+                if (any_field && n_words) {
+                    NIDX_HIP(launch_prefilter_project(d_rows, D, n_words, pf->link->doc_off.as<uint32_t>(), pf->link->entries.as<uint2>(),
+                                                      reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg), sl.d_rt_operands.as<uint64_t>(),
+                                                      reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
+                    pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
+                    filter_launches++, launches++;
+                }
+                if (any_res && pf->rows->res_words) {   // the operands' resource rows, into the same operand rows: the fifth launch
+                    NIDX_HIP(launch_prefilter_project_resources(d_rows + D, D, (uint32_t)pf->rows->res_words, pf->link->res_off.as<uint32_t>(),
+                                                                pf->link->res_ranges.as<PrefilterResRange>(),
+                                                                reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg), sl.d_rt_operands.as<uint64_t>(),
+                                                                reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
                     pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
                     filter_launches++, launches++;
                 }

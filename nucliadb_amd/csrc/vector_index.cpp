@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <unordered_map>
 #include <chrono>
+#include <map>
 #include <memory>
 #include <mutex>
 
@@ -1233,7 +1234,7 @@ int32_t VectorIndex::eval_filter_program(uint32_t si, const nidx_gpu_filter_prog
     // validate + stack depth
     int depth = 0, max_depth = 0;
     bool pf_projected = false;   // the filter's prefilter row is projected once, whatever the number of ops that push it
-    const uint32_t pf_row = pf ? pf->row_of_filter(filter) : kPrefilterRowNone;
+    const uint32_t pf_row = pf ? pf->row_of[filter] : kPrefilterRowNone;   // (the filter's operand: check_prefilter)
     for (uint32_t i = 0; i < prog.n_ops; i++) {
         const nidx_gpu_filter_op_t &op = prog.ops[i];
         switch (op.op) {
@@ -1594,27 +1595,43 @@ PrefilterProjSeg proj_seg(const VectorSegment &seg, unsigned long long out_word)
 }
 }  // namespace
 
-uint32_t PrefilterSearch::row_of_filter(uint32_t f) const {
-    const uint32_t r = prefilter_of_filter ? prefilter_of_filter[f] : UINT32_MAX;
-    return r == UINT32_MAX || !rows ? kPrefilterRowNone : rows->row_of_request[r];
+bool PrefilterSearch::operand_rows(uint32_t o, const uint64_t *&field_row, const uint64_t *&res_row) const {
+    const size_t n = rows->row_ptr.size();
+    const std::pair<uint32_t, uint32_t> p = o < n ? std::make_pair(o, kPrefilterRowNone) : pairs[o - n];
+    field_row = p.first == kPrefilterRowNone ? nullptr : rows->row_ptr[p.first];
+    res_row = p.second == kPrefilterRowNone ? nullptr : rows->res_row_ptr[p.second];
+    return res_row != nullptr;
 }
 
 int32_t VectorIndex::project_prefilter_rows(PrefilterSearch &pf, const std::vector<uint32_t> &rows, const std::vector<unsigned long long> &out_word,
                                             uint64_t *d_out) {
     const size_t S = segs.size(), D = rows.size();
     const size_t seg_bytes = S * sizeof(PrefilterProjSeg);
-    pf_stage.resize(seg_bytes + D * sizeof(uint64_t *));   // (kept until the caller's synchronisation: the upload reads it)
+    pf_stage.resize(seg_bytes + 2 * D * sizeof(uint64_t *));   // (kept until the caller's synchronisation: the upload reads it)
     PrefilterProjSeg *hs = reinterpret_cast<PrefilterProjSeg *>(pf_stage.data());
     for (size_t s = 0; s < S; s++) hs[s] = proj_seg(segs[s], out_word[s]);
-    const uint64_t **hr = reinterpret_cast<const uint64_t **>(pf_stage.data() + seg_bytes);
-    for (size_t j = 0; j < D; j++) hr[j] = pf.rows->row_ptr[rows[j]];
+    const uint64_t **hr = reinterpret_cast<const uint64_t **>(pf_stage.data() + seg_bytes);   // [D field rows | D resource rows]
+    bool any_field = false, any_res = false;
+    for (size_t j = 0; j < D; j++) {
+        any_res = pf.operand_rows(rows[j], hr[j], hr[D + j]) || any_res;
+        any_field = any_field || hr[j];
+    }
     NIDX_HIP(scratch_pf_in.reserve(pf_stage.size()));
     NIDX_HIP(hipMemcpyAsync(scratch_pf_in.p, pf_stage.data(), pf_stage.size(), hipMemcpyHostToDevice, stream));
     const uint8_t *dv = scratch_pf_in.as<uint8_t>();
-    NIDX_HIP(launch_prefilter_project(reinterpret_cast<const uint64_t *const *>(dv + seg_bytes), (uint32_t)D, (uint32_t)pf.rows->layout.words(),
-                                      pf.link->doc_off.as<uint32_t>(), pf.link->entries.as<uint2>(), reinterpret_cast<const PrefilterProjSeg *>(dv),
-                                      d_out, scratch_pf_stats.as<unsigned long long>(), stream));
-    pf.stats.projection_launches++;
+    const uint64_t *const *d_rows = reinterpret_cast<const uint64_t *const *>(dv + seg_bytes);
+    if (any_field) {
+        NIDX_HIP(launch_prefilter_project(d_rows, (uint32_t)D, (uint32_t)pf.rows->layout.words(), pf.link->doc_off.as<uint32_t>(),
+                                          pf.link->entries.as<uint2>(), reinterpret_cast<const PrefilterProjSeg *>(dv), d_out,
+                                          scratch_pf_stats.as<unsigned long long>(), stream));
+        pf.stats.projection_launches++;
+    }
+    if (any_res) {   // the operands' resource rows OR into the same operand rows: one more launch
+        NIDX_HIP(launch_prefilter_project_resources(d_rows + D, (uint32_t)D, (uint32_t)pf.rows->res_words, pf.link->res_off.as<uint32_t>(),
+                                                    pf.link->res_ranges.as<PrefilterResRange>(), reinterpret_cast<const PrefilterProjSeg *>(dv),
+                                                    d_out, scratch_pf_stats.as<unsigned long long>(), stream));
+        pf.stats.projection_launches++;
+    }
     pf.stats.rows_projected += (uint32_t)D;
     return NIDX_OK;
 }
@@ -1657,8 +1674,15 @@ int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_
         const uint32_t r = pf.prefilter_of_filter ? pf.prefilter_of_filter[f] : UINT32_MAX;
         if (r != UINT32_MAX && (!pf.rows || r >= pf.rows->row_of_request.size()))
             return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u of %zu", f, r, pf.rows ? pf.rows->row_of_request.size() : (size_t)0);
-        if (r != UINT32_MAX && pf.rows->has_resources(r))   // (projecting resource rows needs a resource-to-lists link: DESIGN.md §8 item 5)
-            return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
+        if (r != UINT32_MAX && pf.rows->has_resources(r)) {   // (projected through the link's resource half)
+            if (!pf.link->json_uid)
+                return fail(NIDX_ERR_UNSUPPORTED, "filter %u names prefilter request %u, which has a resource-granular part: answer it with host key sets", f, r);
+            if (pf.rows->res_index_uid != pf.link->json_uid)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u, whose resource part is of another JSON index than the link's resource half", f, r);
+            if (pf.rows->res_words != pf.link->res_words)
+                return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u, whose resource rows have %llu words, the link's resource half %llu", f, r,
+                            (unsigned long long)pf.rows->res_words, (unsigned long long)pf.link->res_words);
+        }
         for (size_t s = 0; s < S; s++) {
             FilterProgramInfo info;
             const int32_t rc = check_program(segs[s], who, s, programs[(size_t)f * S + s], true, info);
@@ -1668,8 +1692,22 @@ int32_t VectorIndex::check_prefilter(PrefilterSearch &pf, const nidx_gpu_filter_
             pf.has_op[(size_t)f * S + s] = info.n_prefilter ? 1 : 0;
         }
     }
+    // the filters' operands: a request with a resource part is keyed by its (field row, resource row) pair
     pf.row_of.resize(n_filters);
-    for (uint32_t f = 0; f < n_filters; f++) pf.row_of[f] = pf.row_of_filter(f);
+    pf.pairs.clear();
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> pair_ids;
+    for (uint32_t f = 0; f < n_filters; f++) {
+        const uint32_t r = pf.prefilter_of_filter ? pf.prefilter_of_filter[f] : UINT32_MAX;
+        uint32_t o = r == UINT32_MAX || !pf.rows ? kPrefilterRowNone : pf.rows->row_of_request[r];
+        if (o != kPrefilterRowNone && o != kPrefilterRowAll && o >= pf.rows->row_ptr.size())
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "filter %u names prefilter request %u, whose row %u is not one of the handle's %zu", f, r, o, pf.rows->row_ptr.size());
+        if (o != kPrefilterRowAll && r != UINT32_MAX && pf.rows && pf.rows->has_resources(r)) {
+            const auto it = pair_ids.emplace(std::make_pair(o, pf.rows->res_row_of_request[r]), (uint32_t)pf.pairs.size());
+            if (it.second) pf.pairs.push_back(it.first->first);
+            o = (uint32_t)pf.rows->row_ptr.size() + it.first->second;
+        }
+        pf.row_of[f] = o;
+    }
     return NIDX_OK;
 }
 
@@ -2053,7 +2091,7 @@ int32_t nidx_gpu_build_features(void) {
     return NIDX_FEATURE_VECTOR_SYNC | NIDX_FEATURE_BM25_SYNC | NIDX_FEATURE_VECTOR_MAXSIM_BATCH | NIDX_FEATURE_BM25_FUZZY_BATCH |
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
-           NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS;
+           NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {

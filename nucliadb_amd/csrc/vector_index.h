@@ -95,9 +95,15 @@ struct PrefilterSearch {
     const PrefilterRows *rows = nullptr;
     const uint32_t *prefilter_of_filter = nullptr;   // [n_filters] request in `rows`, UINT32_MAX = none (nullptr: none for every filter)
     std::vector<uint8_t> has_op;                     // [n_filters][n_segments] the program holds NIDX_FILTER_PUSH_PREFILTER
-    std::vector<uint32_t> row_of;                    // [n_filters] row_of_filter(f), filled by check_prefilter
+    // [n_filters] the filter's OPERAND, filled by check_prefilter: kPrefilterRowAll, kPrefilterRowNone, or an id that the planner
+    // (filter_stage.h) treats as opaque — the resident row of a request without a resource part, as ever; rows->row_ptr.size() + i
+    // for the request with parts whose (field row, resource row) is pairs[i] (kPrefilterRowNone: that part is absent).  Two requests
+    // share an operand only when both rows are the same
+    std::vector<uint32_t> row_of;
+    std::vector<std::pair<uint32_t, uint32_t>> pairs;
     nidx_gpu_prefilter_search_stats_t stats{};
-    uint32_t row_of_filter(uint32_t f) const;        // the filter's resident row, kPrefilterRowAll or kPrefilterRowNone
+    // the rows of operand `o` (nullptr: the operand has no such part); true when it has a resource row
+    bool operand_rows(uint32_t o, const uint64_t *&field_row, const uint64_t *&res_row) const;
 };
 
 // What the host decides about a routed batch: whether there is anything to do, whether the routed path takes it, each segment's routing
@@ -198,7 +204,7 @@ struct VectorIndex {
     // the prefilter hand-over: [segment table | row pointers] of a projection launch, its two counters, the row of a deep program
     DevBuf scratch_pf_in, scratch_pf_stats, scratch_pf_row;
     std::vector<uint8_t> pf_stage;
-    // One launch of prefilter_project_kernel: resident rows `rows` onto every segment s with out_word[s] != ~0 (row j of the launch at
+    // One launch of prefilter_project_kernel, and one of its resource sibling when an operand has a resource row: operands `rows` onto every segment s with out_word[s] != ~0 (row j of the launch at
     // word out_word[s] + j * words(s) of d_out, zeroed by the caller); the counters are added to scratch_pf_stats
     int32_t project_prefilter_rows(PrefilterSearch &pf, const std::vector<uint32_t> &rows, const std::vector<unsigned long long> &out_word,
                                    uint64_t *d_out);

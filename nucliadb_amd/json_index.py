@@ -19,6 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import (FILTER_AND, FILTER_NOT, FILTER_OR, FILTER_PUSH_LISTS, JSON_BOOL, JSON_DATE, JSON_F64, JSON_I64, JSON_STR, PREFILTER_AND,
                    PREFILTER_OR)
+from .bm25 import ResidentPrefilters
 from .vector import FieldId, FilterOperator, PrefilterResult
 
 _MASK = (1 << 64) - 1
@@ -383,11 +384,25 @@ class ResourceLink:
             self.handle = None
 
 
+class _BorrowedPrefilters(ResidentPrefilters):
+    """CombinedRows.resident(): the handle stays the CombinedRows' to free."""
+
+    def close(self):
+        self.handle = None
+
+
 class CombinedRows:
     """A nidx_gpu_prefilter_rows_t made by nidx_gpu_prefilter_rows_combine."""
 
-    def __init__(self, handle, stats):
-        self.handle, self.stats = handle, stats
+    def __init__(self, handle, stats, n_requests: int = 0):
+        self.handle, self.stats, self.n_requests = handle, stats, n_requests
+
+    def resident(self) -> ResidentPrefilters:
+        """The handle as VectorSearcher.search_many / search_many_submit and ParagraphSearcher.search_many take resident prefilters:
+        request i of the batch is request i of the handle.  A request with a resource part needs links with a resource half
+        (PrefilterLink.set_resources, PrefilterTermLink.set_resources); the library refuses it otherwise."""
+        names = {_lib.PREFILTER_STATE_NONE: "None", _lib.PREFILTER_STATE_ALL: "All", _lib.PREFILTER_STATE_SOME: "Some"}
+        return _BorrowedPrefilters(self.handle, [names[self.state(i)[0]] for i in range(self.n_requests)], None, None, self.stats)
 
     def state(self, i: int) -> Tuple[int, int]:
         """-> (PREFILTER_STATE_*, PREFILTER_PART_* bits)"""
@@ -419,7 +434,7 @@ def combine_rows(text_rows, json_rows: JsonRows, link: ResourceLink, requests: S
     handle, stats = C.c_void_p(), _lib.PrefilterCombineStatsC()
     _lib.check(_lib.lib().nidx_gpu_prefilter_rows_combine(text_rows, json_rows.handle, link.handle, C.addressof(reqs), len(requests), C.byref(handle),
                                                           C.byref(stats)))
-    return CombinedRows(handle, stats)
+    return CombinedRows(handle, stats, len(requests))
 
 
 class JsonSearcher:

@@ -1159,7 +1159,7 @@ class ParagraphSearcher:
                 members.append(nested(expr, occur))
 
         def prefilter_sets(occur: int, out: List[Clause]):
-            if isinstance(prefilter, ResidentPrefilter):   # the row stands for the field_uuid set; rows are field-granular: no uuid set
+            if isinstance(prefilter, ResidentPrefilter):   # the request's rows stand for both sets: its field row for the field_uuid set, its resource row (a combined handle) for the uuid set
                 out.append(Clause(0, occur, _lib.CONST_SCORE, boost, prefilter_request=prefilter.request))
                 return
             fields = sorted({"\x00fid:" + rid + "/" + fid.lstrip("/") for rid, fid in prefilter.fields if fid is not None})
@@ -1364,6 +1364,18 @@ class ParagraphSearcher:
         _lib.check(_lib.lib().nidx_gpu_prefilter_term_link_create(index.searcher._handle, self._index.searcher._handle, c_terms, n, C.byref(handle),
                                                                   C.byref(stats)))
         return PrefilterTermLink(handle, stats)
+
+    def link_resources(self, link: PrefilterTermLink, json_searcher) -> "_lib.PrefilterResourceTermLinkStatsC":
+        """Gives `link` its resource half (nidx_gpu_prefilter_term_link_set_resources): per resource of the JSON searcher's table the
+        id of "\\x00uuid:" + uuid — the term prefilter_sets looks up for a resource-granular entry of a host PrefilterResult — or
+        0xFFFFFFFF when this index has no such term.  Resolved once per pair of generations, like link_text."""
+        terms = []
+        for u in json_searcher.resources():
+            t = self._index.vocab.lookup("\x00uuid:" + u.hex)
+            if t is None:
+                t = self._index.vocab.lookup("\x00uuid:" + str(u))
+            terms.append(0xFFFFFFFF if t is None else t)
+        return link.set_resources(self._index.searcher._handle, json_searcher._handle, np.array(terms, dtype=np.uint32))
 
     @staticmethod
     def _per_request_prefilters(prefilters, n: int):

@@ -564,6 +564,29 @@ class PrefilterLink:
         _lib.check(_lib.lib().nidx_gpu_prefilter_link_read(self.handle, vector_segment, docs.ctypes.data, lists.ctypes.data, n.value, C.byref(n)))
         return docs[: n.value], lists[: n.value]
 
+    def set_resources(self, vector_searcher, json_searcher) -> "_lib.PrefilterResourceLinkStatsC":
+        """The resource half (nidx_gpu_prefilter_link_set_resources): resource r of the JSON index's table reaches the lists whose
+        key starts with "F:" + its 32 hex digits — every field of it, what _formula's _KeyPrefixSet looks up for FieldId(uuid, None).
+        Not while a ticket that names the link is outstanding."""
+        keys = [("F:" + u.hex).encode("utf-8") for u in json_searcher.resources()]
+        blob = np.frombuffer(b"".join(keys) + b"\0", np.uint8)
+        offs = np.zeros(len(keys) + 1, np.uint64)
+        offs[1:] = np.cumsum([len(k) for k in keys])
+        stats = _lib.PrefilterResourceLinkStatsC()
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_set_resources(self.handle, vector_searcher._handle, json_searcher._handle, blob.ctypes.data,
+                                                                    offs.ctypes.data, len(keys), C.byref(stats)))
+        self.resource_stats = stats
+        return stats
+
+    def read_resources(self, vector_segment: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(resource ordinal, first list, n lists) ranges of one vector segment, ascending by resource: tests."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_read_resources(self.handle, vector_segment, None, None, None, 0, C.byref(n)))
+        res, first, num = (np.zeros(max(1, n.value), np.uint32) for _ in range(3))
+        _lib.check(_lib.lib().nidx_gpu_prefilter_link_read_resources(self.handle, vector_segment, res.ctypes.data, first.ctypes.data, num.ctypes.data,
+                                                                     n.value, C.byref(n)))
+        return res[: n.value], first[: n.value], num[: n.value]
+
     def close(self):
         if self.handle:
             _lib.lib().nidx_gpu_prefilter_link_free(self.handle)
