@@ -66,6 +66,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_ROUTED_TICKETS 512 /* nidx_gpu_vector_search_submit_filtered_per_query_async, nidx_gpu_vector_search_wait_routed, nidx_gpu_use_hnsw_threshold, nidx_gpu_vector_routed_stats */
 #define NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS 1024 /* nidx_gpu_vector_search_submit_prefiltered_per_query_async, nidx_gpu_vector_prefiltered_ticket_stats */
 #define NIDX_FEATURE_PREFILTER_RESOURCE_PARTS 2048 /* nidx_gpu_prefilter_link_set_resources, nidx_gpu_prefilter_term_link_set_resources, their _read_resources */
+#define NIDX_FEATURE_BM25_PREFILTERED_TICKETS 4096 /* nidx_gpu_bm25_search_submit_prefiltered / _wait_prefiltered, nidx_gpu_bm25_ticket_stats */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1187,6 +1188,58 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
                                          const uint64_t *clause_offsets, uint32_t n_queries, const nidx_gpu_bm25_search_options_t *options,
                                          const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
                                          uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out);
+
+/* The same search as a ticket that waits for nothing (present when nidx_gpu_build_features() & NIDX_FEATURE_BM25_PREFILTERED_TICKETS).
+ * A hybrid request hands its one PrefilterResult to the vector search and to the paragraph search; with this entry neither half blocks
+ * the submitting thread.  Arguments and outputs mean what they mean for nidx_gpu_bm25_search_prefiltered; link, rows and
+ * prefilter_of_term_set may be NULL as there, and with prefilter_of_term_set NULL the call is the ticket form of nidx_gpu_bm25_search_ex.
+ * After the wait every output — docaddr, score, count, total, postings and, where asked for, every field of stats_out — equals the
+ * blocking call's on the same arguments, bit for bit.
+ *
+ * Checks: the blocking entry's, by the same function, with the same codes, messages and order (link and row generations, layout,
+ * device, the resource half, a request out of range, a row set with terms or the complement flag, 65 535 distinct rows,
+ * NIDX_GPU_BM25_ROW_SCRATCH_MAX).  They run before a slot is taken and before anything is queued: a refused submit issues no
+ * ticket (*ticket_out = 0) and touches no output.
+ *
+ * Tickets come from the slot pool of nidx_gpu_bm25_search_submit: at most NIDX_GPU_BM25_MAX_TICKETS outstanding over both submit
+ * entries (NIDX_ERR_BUSY beyond), a ticket is waited for once, from any thread, by EITHER wait function; the new wait also takes a
+ * ticket of nidx_gpu_bm25_search_submit and then writes zeros into stats_out.
+ *
+ * Lifetimes: clauses, clause_offsets, options (and everything it points to) and prefilter_of_term_set need not outlive the submit.
+ * link and rows stay the caller's until the wait returns — the rule of the vector tickets: the queued projections read the rows and
+ * the link on the device.  A ticket submitted before a nidx_gpu_bm25_sync commit delivers the answer of its own generation (the commit
+ * waits for the queued batches); the next submit with the old link is refused like the blocking call.
+ *
+ * What is pipelined — queued on the slot's stream with no synchronisation, no device-to-host read and without the lock the blocking
+ * entries serialise on: a batch whose aux lists are all term sets (with terms, empty, complemented) and row sets (field rows, resource
+ * parts, the shared All row), on an index resident as one segment (the concatenated layout), without facets, without fast-field
+ * order, not a debug run.  The aux lists' exact lengths then never reach the host: the work list is planned from estimates — a term
+ * set min(sum of its lists, documents), a complement and the All row every document, a row set its set documents times the postings
+ * a linked document reaches on average, at most the row bound — which only steer the number of doc-id slices and reach no output;
+ * the lists' regions stay sized by their bounds.  All term sets of the batch are materialised by one table-driven scatter, one
+ * complement launch and one compaction, the rows by their projections and one compaction, and one more launch writes the [begin, end)
+ * pairs the scoring kernels read: the number of launches does not depend on the number of queries or sets.  Phrases, nested queries,
+ * facets, order by a fast field and the NIDX_GPU_BM25_SEGMENT_LOOP layout run to completion inside the submit, as in
+ * nidx_gpu_bm25_search_submit, and give the blocking answer through the wait.  (Scratch that has to grow — the first batches of a
+ * slot — is reallocated inside the submit.) */
+int32_t nidx_gpu_bm25_search_submit_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
+                                                const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
+                                                const uint64_t *clause_offsets, uint32_t n_queries, const nidx_gpu_bm25_search_options_t *options,
+                                                const uint32_t *prefilter_of_term_set, uint64_t *ticket_out);
+int32_t nidx_gpu_bm25_search_wait_prefiltered(nidx_gpu_bm25_index_t *index, uint64_t ticket, uint64_t *out_docaddr, float *out_score,
+                                              uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings,
+                                              nidx_gpu_bm25_prefilter_search_stats_t *stats_out /* may be NULL */);
+/* Sums over the tickets of nidx_gpu_bm25_search_submit_prefiltered since the index was opened. */
+typedef struct nidx_gpu_bm25_ticket_stats {
+    uint64_t tickets;                 /* issued */
+    uint64_t pipelined;               /* queued without waiting for anything */
+    uint64_t ran_in_submit;           /* ran to completion inside the submit */
+    uint64_t submit_synchronisations; /* stream / event synchronisations and blocking copies inside pipelined submits: stays 0 */
+    uint64_t aux_launches;            /* kernel launches of the aux stages of the pipelined submits */
+    uint64_t row_sets;                /* term sets that named a prefilter request */
+    uint64_t term_sets;               /* the other term sets */
+} nidx_gpu_bm25_ticket_stats_t;
+int32_t nidx_gpu_bm25_ticket_stats(nidx_gpu_bm25_index_t *index, nidx_gpu_bm25_ticket_stats_t *out);
 
 /* ---- the JSON prefilter on the device, combined with the text prefilter's rows -------------------------------------------------------
  * Prefilter::run (src/searcher/query_planner/prefilter.rs:41-91) runs the text prefilter and the JSON prefilter side by side:

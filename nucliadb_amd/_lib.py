@@ -168,6 +168,7 @@ FEATURE_JSON_PREFILTER = 256   # nidx_gpu_build_features() bit: the resident JSO
 FEATURE_VECTOR_ROUTED_TICKETS = 512   # nidx_gpu_build_features() bit: per-query filter tickets routed on the device, nidx_gpu_use_hnsw_threshold
 FEATURE_VECTOR_PREFILTERED_TICKETS = 1024   # nidx_gpu_build_features() bit: routed tickets whose programs push resident prefilter rows
 FEATURE_PREFILTER_RESOURCE_PARTS = 2048   # nidx_gpu_build_features() bit: the links' resource halves (resource-granular prefilter parts on the device)
+FEATURE_BM25_PREFILTERED_TICKETS = 4096   # nidx_gpu_build_features() bit: BM25 tickets that take term sets and prefilter row sets
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -244,6 +245,11 @@ class Bm25PrefilterSearchStatsC(C.Structure):
     """nidx_gpu_bm25_prefilter_search_stats_t"""
     _fields_ = [("rows_projected", C.c_uint32), ("projection_launches", C.c_uint32), ("compaction_launches", C.c_uint32), ("reserved", C.c_uint32),
                 ("documents_visited", C.c_uint64), ("postings_written", C.c_uint64), ("list_entries", C.c_uint64)]
+
+
+class Bm25TicketStatsC(C.Structure):
+    """nidx_gpu_bm25_ticket_stats_t"""
+    _fields_ = [(n, C.c_uint64) for n in ("tickets", "pipelined", "ran_in_submit", "submit_synchronisations", "aux_launches", "row_sets", "term_sets")]
 
 
 JSON_STR, JSON_I64, JSON_F64, JSON_BOOL, JSON_DATE = 0, 1, 2, 3, 4
@@ -503,6 +509,11 @@ SIGNATURES = {
     "nidx_gpu_bm25_search_prefiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                      C.POINTER(Bm25SearchOptionsC), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.POINTER(Bm25PrefilterSearchStatsC)]),
+    "nidx_gpu_bm25_search_submit_prefiltered": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                            C.POINTER(Bm25SearchOptionsC), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_bm25_search_wait_prefiltered": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(Bm25PrefilterSearchStatsC)]),
+    "nidx_gpu_bm25_ticket_stats": (C.c_int32, [C.c_void_p, C.POINTER(Bm25TicketStatsC)]),
     "nidx_gpu_vector_search_prefiltered_per_query": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                                  C.POINTER(VectorSearchParamsC), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -550,14 +551,10 @@ class Bm25Searcher:
         kinds = ["None" if int(m) == 0 else "All" if int(m) == live.value else "Some" for m in matching]
         return ResidentPrefilters(handle, kinds, matching, live.value, stats)
 
-    def search_batch_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
-                        order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None,
-                        link: Optional[PrefilterTermLink] = None, rows: Optional[ResidentPrefilters] = None):
-        """The collectors around the scoring (nidx_text/src/reader.rs:367-451): term-set clauses, TopDocs ordered by a
-        fast field, facet counts (facets[q] = term ids to count among query q's matching documents).  Clauses with
-        `prefilter_request` are lowered to empty term sets that read a row of `rows` through `link`
-        (nidx_gpu_bm25_search_prefiltered, called only when there is one; its stats are kept in last_prefilter_search_stats).
-        -> dict(docaddr, score, count, total, postings, order_value, facet_counts[q] = counts aligned with facets[q])"""
+    def _lower_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
+                  order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None):
+        """The arguments of nidx_gpu_bm25_search_ex / _search_prefiltered (and of their ticket forms) for a batch -> a namespace of the
+        ctypes arguments, the output arrays and everything that has to stay alive while the library reads them."""
         B = len(queries)
         offsets = np.zeros(B + 1, dtype=np.uint64)
         flat = []
@@ -660,22 +657,68 @@ class Bm25Searcher:
             opt.facet_offsets = fo.ctypes.data
             opt.out_facet_counts = fc.ctypes.data
         opt.out_order_value = order_value.ctypes.data
-        if row_set_of:
-            sp = np.ascontiguousarray(set_prefilter, dtype=np.uint32)
+        sp = np.ascontiguousarray(set_prefilter, dtype=np.uint32) if row_set_of else None
+        return SimpleNamespace(B=B, cl=cl, offsets=offsets, opt=opt, sp=sp, docaddr=docaddr, score=score, order_value=order_value, count=count,
+                               total=total, postings=postings, facets=facets, fo=fo, fc=fc, keep=(af, st, so, sc, pt, po, ps, sub_cl, sub_off, ft))
+
+    @staticmethod
+    def _result_ex(a):
+        facet_counts = None
+        if a.facets is not None:
+            facet_counts = [a.fc[int(a.fo[q]): int(a.fo[q + 1])].astype(np.int64) for q in range(a.B)]
+        return {"docaddr": a.docaddr, "score": a.score, "count": a.count, "total": a.total, "postings": a.postings,
+                "order_value": a.order_value, "facet_counts": facet_counts}
+
+    def search_batch_ex(self, queries: Sequence[Sequence[Clause]], k: int, after: Optional[Sequence[Optional[SearchAfter]]] = None,
+                        order_field: int = -1, order_desc: bool = True, facets: Optional[Sequence[Sequence[int]]] = None,
+                        link: Optional[PrefilterTermLink] = None, rows: Optional[ResidentPrefilters] = None):
+        """The collectors around the scoring (nidx_text/src/reader.rs:367-451): term-set clauses, TopDocs ordered by a
+        fast field, facet counts (facets[q] = term ids to count among query q's matching documents).  Clauses with
+        `prefilter_request` are lowered to empty term sets that read a row of `rows` through `link`
+        (nidx_gpu_bm25_search_prefiltered, called only when there is one; its stats are kept in last_prefilter_search_stats).
+        -> dict(docaddr, score, count, total, postings, order_value, facet_counts[q] = counts aligned with facets[q])"""
+        a = self._lower_ex(queries, k, after, order_field, order_desc, facets)
+        if a.sp is not None:
             stats = _lib.Bm25PrefilterSearchStatsC()
             _lib.check(_lib.lib().nidx_gpu_bm25_search_prefiltered(self._handle, None if link is None else link.handle,
-                                                                   None if rows is None else rows.handle, cl, offsets.ctypes.data, B, C.byref(opt),
-                                                                   sp.ctypes.data, docaddr.ctypes.data, score.ctypes.data, count.ctypes.data,
-                                                                   total.ctypes.data, postings.ctypes.data, C.byref(stats)))
+                                                                   None if rows is None else rows.handle, a.cl, a.offsets.ctypes.data, a.B, C.byref(a.opt),
+                                                                   a.sp.ctypes.data, a.docaddr.ctypes.data, a.score.ctypes.data, a.count.ctypes.data,
+                                                                   a.total.ctypes.data, a.postings.ctypes.data, C.byref(stats)))
             self.last_prefilter_search_stats = stats
         else:
-            _lib.check(_lib.lib().nidx_gpu_bm25_search_ex(self._handle, cl, offsets.ctypes.data, B, C.byref(opt), docaddr.ctypes.data,
-                                                          score.ctypes.data, count.ctypes.data, total.ctypes.data, postings.ctypes.data))
-        facet_counts = None
-        if facets is not None:
-            facet_counts = [fc[int(fo[q]): int(fo[q + 1])].astype(np.int64) for q in range(B)]
-        return {"docaddr": docaddr, "score": score, "count": count, "total": total, "postings": postings,
-                "order_value": order_value, "facet_counts": facet_counts}
+            _lib.check(_lib.lib().nidx_gpu_bm25_search_ex(self._handle, a.cl, a.offsets.ctypes.data, a.B, C.byref(a.opt), a.docaddr.ctypes.data,
+                                                          a.score.ctypes.data, a.count.ctypes.data, a.total.ctypes.data, a.postings.ctypes.data))
+        return self._result_ex(a)
+
+    def submit_ex(self, queries: Sequence[Sequence[Clause]], k: int, link: Optional[PrefilterTermLink] = None,
+                  rows: Optional[ResidentPrefilters] = None, **options):
+        """search_batch_ex as a ticket (nidx_gpu_bm25_search_submit_prefiltered): `options` are search_batch_ex's after / order_field /
+        order_desc / facets.  A batch whose aux clauses are term sets and row sets is queued without waiting for anything; any other
+        runs inside this call.  `link` and `rows` must stay open until wait_ex(ticket) has returned.  -> ticket"""
+        a = self._lower_ex(queries, k, **options)
+        t = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_bm25_search_submit_prefiltered(self._handle, None if link is None else link.handle,
+                                                                      None if rows is None else rows.handle, a.cl, a.offsets.ctypes.data, a.B,
+                                                                      C.byref(a.opt), None if a.sp is None else a.sp.ctypes.data, C.byref(t)))
+        self._tickets_ex = getattr(self, "_tickets_ex", {})
+        self._tickets_ex[t.value] = (a, link, rows)
+        return t.value
+
+    def wait_ex(self, ticket: int):
+        """-> the dict search_batch_ex returns, of the batch submitted under `ticket` by submit_ex."""
+        a, _link, _rows = self._tickets_ex.pop(ticket)
+        stats = _lib.Bm25PrefilterSearchStatsC()
+        _lib.check(_lib.lib().nidx_gpu_bm25_search_wait_prefiltered(self._handle, ticket, a.docaddr.ctypes.data, a.score.ctypes.data, a.count.ctypes.data,
+                                                                    a.total.ctypes.data, a.postings.ctypes.data, C.byref(stats)))
+        if a.sp is not None:
+            self.last_prefilter_search_stats = stats
+        return self._result_ex(a)
+
+    def ticket_stats(self) -> "_lib.Bm25TicketStatsC":
+        """nidx_gpu_bm25_ticket_stats: sums over the tickets of submit_ex since the index was opened."""
+        stats = _lib.Bm25TicketStatsC()
+        _lib.check(_lib.lib().nidx_gpu_bm25_ticket_stats(self._handle, C.byref(stats)))
+        return stats
 
     def submit(self, queries: Sequence[Sequence[Clause]], k: int) -> int:
         """nidx_gpu_bm25_search_submit for a batch of plain term clauses -> ticket; the host side of this batch overlaps the kernels of

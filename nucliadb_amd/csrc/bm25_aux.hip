@@ -140,6 +140,81 @@ hipError_t launch_bitset_compact(const uint64_t *bits, uint32_t n_words, uint32_
     return hipGetLastError();
 }
 
+// ---- the aux stage of a pipelined batch: every term set of the batch in a fixed number of launches ---------------------------------
+// One WAVE per work item (bm25_aux_plan.h: at most kBm25ScatterChunk consecutive postings of one list): the fuzzy clause shape is
+// thousands of lists of a few postings, where a workgroup per list would idle three waves in four; a long list is many items.
+// HBM-bound: 4 bytes per posting in, one 32-bit atomic OR per posting out (most land in L2: a bitset is n_docs / 8 bytes).
+__global__ __launch_bounds__(256) void bm25_set_scatter_kernel(const Bm25ScatterItem *__restrict__ items, uint32_t n_items,
+                                                               const uint32_t *__restrict__ doc_ids, uint32_t n_docs, uint32_t words,
+                                                               unsigned int *__restrict__ bits32) {
+    const uint32_t it = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (it >= n_items) return;
+    const Bm25ScatterItem w = items[it];
+    unsigned int *out32 = bits32 + (size_t)w.slot * words * 2;
+    const uint32_t *ids = doc_ids + w.begin;
+    for (uint32_t i = threadIdx.x & 63u; i < w.count; i += 64u) {
+        const uint32_t id = ids[i];
+        if (id < n_docs) atomicOr(&out32[id >> 5], 1u << (id & 31));
+    }
+}
+
+// the flagged bitsets become their complements: whole 64-bit words, each loaded and stored once by one lane — no atomics
+__global__ __launch_bounds__(256) void bm25_set_complement_kernel(uint64_t *__restrict__ bits, const uint32_t *__restrict__ flags, uint32_t n_slots,
+                                                                  uint32_t words, uint32_t n_docs) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= words) return;
+    const uint64_t tail = (w == words - 1 && (n_docs & 63)) ? (1ull << (n_docs & 63)) - 1ull : ~0ull;
+    for (uint32_t s = blockIdx.y; s < n_slots; s += gridDim.y) {
+        if (!flags[s]) continue;
+        uint64_t *p = bits + (size_t)s * words + w;
+        *p = ~*p & tail;
+    }
+}
+
+// one lane per list: what the host's aux_pairs upload was, from the counts on the device
+__global__ __launch_bounds__(256) void bm25_aux_ranges_kernel(const unsigned long long *__restrict__ out_off, const uint32_t *__restrict__ count_of,
+                                                              const uint32_t *__restrict__ counts, uint32_t n_aux, unsigned long long *__restrict__ pairs,
+                                                              uint32_t n_first_row, uint32_t *__restrict__ host_counts,
+                                                              const unsigned long long *__restrict__ row_stats, unsigned long long *__restrict__ host_row_stats) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j == 0 && host_row_stats) {
+        host_row_stats[0] = row_stats[0];
+        host_row_stats[1] = row_stats[1];
+    }
+    if (j > n_aux) return;
+    if (j == n_aux) {
+        pairs[2 * (size_t)j] = 0;
+        pairs[2 * (size_t)j + 1] = 0;
+        return;
+    }
+    const uint32_t c = count_of[j] == 0xffffffffu ? 0u : counts[count_of[j]];
+    const unsigned long long b = out_off[j];
+    pairs[2 * (size_t)j] = b;
+    pairs[2 * (size_t)j + 1] = b + c;
+    if (j >= n_first_row && host_counts) host_counts[j - n_first_row] = c;
+}
+
+hipError_t launch_bm25_set_scatter(const Bm25ScatterItem *items, uint32_t n_items, const uint32_t *doc_ids, uint32_t n_docs, uint32_t words,
+                                   uint64_t *bits, hipStream_t s) {
+    if (!n_items || !words) return hipSuccess;
+    hipLaunchKernelGGL(bm25_set_scatter_kernel, dim3((n_items + 3) / 4), dim3(256), 0, s, items, n_items, doc_ids, n_docs, words,
+                       reinterpret_cast<unsigned int *>(bits));
+    return hipGetLastError();
+}
+hipError_t launch_bm25_set_complement(uint64_t *bits, const uint32_t *flags, uint32_t n_slots, uint32_t words, uint32_t n_docs, hipStream_t s) {
+    if (!n_slots || !words) return hipSuccess;
+    hipLaunchKernelGGL(bm25_set_complement_kernel, dim3((words + 255) / 256, std::min<uint32_t>(n_slots, 65535u)), dim3(256), 0, s, bits, flags, n_slots,
+                       words, n_docs);
+    return hipGetLastError();
+}
+hipError_t launch_bm25_aux_ranges(const unsigned long long *out_off, const uint32_t *count_of, const uint32_t *counts, uint32_t n_aux,
+                                  unsigned long long *pairs, uint32_t n_first_row, uint32_t *host_counts, const unsigned long long *row_stats,
+                                  unsigned long long *host_row_stats, hipStream_t s) {
+    hipLaunchKernelGGL(bm25_aux_ranges_kernel, dim3(n_aux / 256 + 1), dim3(256), 0, s, out_off, count_of, counts, n_aux, pairs, n_first_row, host_counts,
+                       row_stats, host_row_stats);
+    return hipGetLastError();
+}
+
 // ---- PhraseQuery ---------------------------------------------------------------------------------------------------
 // first index in [b, e) whose doc id is >= d
 __device__ inline unsigned long long lower_bound_doc(const uint32_t *doc_ids, unsigned long long b, unsigned long long e, uint32_t d) {

@@ -92,6 +92,11 @@ struct Bm25Ctx {
     // packed staging: [clauses | clause offsets], [item_first | work list] in; [doc | score | count | total | postings] out
     DevBuf s_in_q, s_in_w;
     PinBuf h_in_q, h_in_w, h_outpack;
+    // the aux stage of a pipelined batch (nidx_gpu_bm25_search_submit_prefiltered): its tables in one pinned block and one transfer —
+    // [list offsets | offsets of the slots' lists | row sources | scatter work items | count index per list | complement flag per slot]
+    DevBuf s_in_a;
+    PinBuf h_in_a, h_after;
+    std::vector<Bm25ScatterItem> w_scatter;
     float kernel_ms = 0.f;   // scoring kernels of the last call through this context
     Bm25Ctx() = default;
     Bm25Ctx(const Bm25Ctx &) = delete;
@@ -134,6 +139,19 @@ struct Bm25Slot {
     std::vector<uint64_t> r_docaddr, r_total, r_postings;
     std::vector<float> r_score;
     std::vector<uint32_t> r_count;
+    // nidx_gpu_bm25_search_wait_prefiltered: what of the stats the host knew at submit; of a launched batch with row sets the counts
+    // of the n_stat_rows rows' lists and the projections' two counters lie at o_stats of cx.h_outpack ([2] u64 | [n_stat_rows] u32)
+    nidx_gpu_bm25_prefilter_search_stats_t pf_stats = {};
+    uint32_t n_stat_rows = 0;
+    size_t o_stats = 0;
+};
+
+// What nidx_gpu_bm25_search_submit_prefiltered asks of bm25_search_locked and learns from it.
+struct Bm25TicketRun {
+    bool allow_aux = true;     // term sets and row sets may be pipelined
+    bool pipelined = false;    // the batch was queued, nothing waited for
+    uint32_t syncs = 0;        // stream synchronisations and blocking copies the call made
+    uint32_t aux_launches = 0; // kernel launches of the aux stage of a pipelined batch
 };
 
 // What is kept of every segment the caller opened when the resident layout is the term-major concatenation (Bm25Index::seg_base)
@@ -192,6 +210,8 @@ struct Bm25Index {
     float last_kernel_ms = 0.f;
     std::vector<std::unique_ptr<Bm25Slot>> slots;   // nidx_gpu_bm25_search_submit / _wait
     uint64_t next_ticket = 1;
+    // nidx_gpu_bm25_ticket_stats (sums over the tickets of nidx_gpu_bm25_search_submit_prefiltered)
+    std::atomic<uint64_t> ts_tickets{0}, ts_pipelined{0}, ts_ran_in_submit{0}, ts_submit_syncs{0}, ts_aux_launches{0}, ts_row_sets{0}, ts_term_sets{0};
     Bm25Index() = default;
     Bm25Index(const Bm25Index &) = delete;
     bool concatenated() const { return !real.empty(); }
@@ -1300,6 +1320,7 @@ static int32_t bm25_prefilter_batch_locked(Bm25Index *idx, const nidx_gpu_bm25_p
         if (resident && list_len(pg)) {
             row_of_program[p] = (uint32_t)resident->row_ptr.size();
             resident->row_ptr.push_back(row.as<uint64_t>());
+            resident->row_docs.push_back(pg.matching);
             resident->bytes += row_bytes;
             resident->chunks.push_back(std::move(row));
         }
@@ -1459,6 +1480,7 @@ static int32_t bm25_prefilter_batch_locked(Bm25Index *idx, const nidx_gpu_bm25_p
                 NIDX_HIP(hipMemcpyAsync(dst, d_results + (size_t)j * W, (size_t)row_bytes, hipMemcpyDeviceToDevice, st));
                 row_of_program[pass[j]] = (uint32_t)resident->row_ptr.size();
                 resident->row_ptr.push_back(dst);
+                resident->row_docs.push_back(programs[pass[j]].matching);
             }
             resident->bytes += n_some * row_bytes;
             resident->chunks.push_back(std::move(chunk));
@@ -1689,10 +1711,13 @@ struct Bm25RowSets {
 
 // The search itself, on the context `cx` (the caller owns it for the duration and holds idx->rw shared).  With `async_slot` set and a
 // request the pipeline covers it returns after the last asynchronous call (launches + the device-to-host transfer of the result block
-// are queued on the slot's stream).
+// are queued on the slot's stream).  With `tr` (nidx_gpu_bm25_search_submit_prefiltered) the pipeline also covers batches whose aux
+// lists are all term sets and row sets: their exact lengths then never reach the host — the work list is planned from estimates
+// (bm25_aux_plan.h), the [begin, end) pairs the scoring kernels read are written by bm25_aux_ranges_kernel.
 static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_slot, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
                                   uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *out_docaddr, float *out_score,
-                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings, Bm25RowSets *rs = nullptr) {
+                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings, Bm25RowSets *rs = nullptr,
+                                  Bm25TicketRun *tr = nullptr) {
     const double t_entry = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     NIDX_HIP(hipSetDevice(idx->device));
     // other tickets are out: this batch's launches will share the GPU with theirs (the throughput shape of the work list, below)
@@ -1847,6 +1872,10 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         }
         dev_clauses[c] = Bm25ClauseDev{cl.term, cl.occur, cl.mode, w};
     }
+    // The pipelined aux stage: every aux list is a term set or a distinct row, one resident segment, no facets, no fast-field order, no
+    // debug run.  Nothing below may then wait for the stream or read from the device.
+    const bool pipe_aux = tr && tr->allow_aux && async_slot && idx->segs.size() == 1 && n_sets + n_rows_d > 0 && n_phrases == 0 && n_sub == 0 &&
+                          n_pairs == 0 && order_field < 0 && !getenv("NIDX_GPU_BM25_DEBUG");
     const uint32_t kk = std::max<uint32_t>(k, 1);
     // clauses and clause offsets travel as one pinned block
     const size_t cl_bytes = (std::max<size_t>(n_clauses, 1) * sizeof(Bm25ClauseDev) + 7) & ~(size_t)7;
@@ -1892,6 +1921,11 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             }
             src = cx.w_after.data();
         }
+        if (pipe_aux) {   // pinned staging: the transfer neither blocks nor reads the caller's memory after the submit
+            NIDX_HIP(cx.h_after.reserve((size_t)nq * sizeof(Bm25AfterDev)));
+            memcpy(cx.h_after.p, src, (size_t)nq * sizeof(Bm25AfterDev));
+            src = cx.h_after.p;
+        }
         NIDX_HIP(hipMemcpyAsync(cx.s_after.p, src, (size_t)nq * sizeof(Bm25AfterDev), hipMemcpyHostToDevice, cx.stream));
     }
     // facets: one matching-document bitset per query that asks for counts
@@ -1919,7 +1953,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         NIDX_HIP(hipMemcpyAsync(cx.s_pair_slot.p, pair_slot.data(), n_pairs * 4, hipMemcpyHostToDevice, cx.stream));
         NIDX_HIP(hipMemsetAsync(cx.s_facet_counts.p, 0, n_pairs * 8, cx.stream));
     }
-    if (n_sets) {
+    if (n_sets && !pipe_aux) {   // (the pipelined aux stage scatters from a work table of posting ranges: the terms stay on the host)
         const uint64_t n_set_terms = opt->term_set_offsets[n_sets];
         NIDX_HIP(cx.s_set_terms.reserve(std::max<uint64_t>(n_set_terms, 1) * 4));
         if (n_set_terms) NIDX_HIP(hipMemcpyAsync(cx.s_set_terms.p, opt->term_set_terms, n_set_terms * 4, hipMemcpyHostToDevice, cx.stream));
@@ -2020,8 +2054,119 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             NIDX_HIP(cx.s_aux_tfs.reserve(std::max<uint64_t>(out_off[n_own], 1) * 4 + BM25_LIST_PAD_BYTES));
             NIDX_HIP(cx.s_set_counts.reserve((size_t)n_aux * 4 + 4));   // + the count of the union candidates
             NIDX_HIP(hipMemsetAsync(cx.s_set_counts.p, 0, (size_t)n_aux * 4 + 4, cx.stream));
-            NIDX_HIP(cx.s_aux_out_off.reserve((size_t)(n_aux + 1) * 8));
-            NIDX_HIP(hipMemcpyAsync(cx.s_aux_out_off.p, out_off.data(), (size_t)(n_aux + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+            if (!pipe_aux) {   // (the pipelined aux stage sends the offsets with its other tables)
+                NIDX_HIP(cx.s_aux_out_off.reserve((size_t)(n_aux + 1) * 8));
+                NIDX_HIP(hipMemcpyAsync(cx.s_aux_out_off.p, out_off.data(), (size_t)(n_aux + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+            }
+        }
+        // the sources of the rows to project: [n_proj field rows | n_proj resource rows], nullptr: the row set has no such part
+        auto row_sources = [&](uint32_t n_proj) {
+            cx.w_row_ptrs.assign((size_t)n_proj * (rs->any_res ? 2 : 1), nullptr);
+            bool any_field = false;
+            for (uint32_t r = 0; r < n_proj; r++) {
+                if (rs->distinct[r] != kPrefilterRowNone) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]], any_field = true;
+                if (rs->any_res && rs->distinct_res[r] != kPrefilterRowNone) cx.w_row_ptrs[n_proj + r] = rs->rows->res_row_ptr[rs->distinct_res[r]];
+            }
+            return any_field;
+        };
+        // every distinct row onto this segment in one launch (one more for the resource parts), every row's list in one compaction
+        auto project_rows = [&](const uint64_t *const *d_row_ptrs, uint32_t n_proj, bool any_field, const unsigned long long *d_out_off,
+                                uint32_t *d_counts) -> int32_t {
+            if (n_proj && any_field) {
+                NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs, n_proj, (uint32_t)rs->rows->layout.words(), rs->link->doc_term.as<uint32_t>(),
+                                                       seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
+                                                       cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
+                rs->stats.projection_launches++;
+            }
+            if (n_proj && rs->any_res) {   // the uuid lists of the set resources, into the same bitsets: one more launch
+                NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs + n_proj, n_proj, (uint32_t)rs->rows->res_words, rs->link->res_term.as<uint32_t>(),
+                                                       seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
+                                                       cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
+                rs->stats.projection_launches++;
+            }
+            NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, d_out_off, cx.s_aux_ids.as<uint32_t>(), d_counts, cx.stream));
+            rs->stats.compaction_launches++;
+            return NIDX_OK;
+        };
+        // ---- the pipelined aux stage: a fixed number of launches, one transfer in, nothing out ----
+        uint32_t n_pipe_slots = 0;
+        size_t pa_count_of = 0;   // the count index per list, in cx.s_in_a
+        if (pipe_aux) {
+            std::vector<uint32_t> slot_of_set, comp_of_slot;
+            n_pipe_slots = bm25_assign_slots(opt->term_set_offsets, opt->term_set_complement, n_sets, slot_of_set, comp_of_slot);
+            bool any_comp = false;
+            for (uint32_t f : comp_of_slot) any_comp |= f != 0;
+            std::vector<Bm25ScatterItem> &items = cx.w_scatter;
+            bm25_scatter_table(opt->term_set_offsets, opt->term_set_terms, n_sets, slot_of_set.data(), seg.term_offsets_host.data(), kBm25ScatterChunk, items);
+            uint32_t n_proj = n_rows_d;
+            const bool all_row = n_rows_d && rs->distinct.back() == kPrefilterRowAll;   // (the entry lists it last)
+            if (all_row) n_proj--;
+            const bool any_field = n_proj ? row_sources(n_proj) : false;
+            const size_t n_ptrs = n_proj ? cx.w_row_ptrs.size() : 0;
+            // the tables' block; the lists' counts live in s_set_counts as [slots | distinct rows]
+            const size_t pa_off = 0, pa_slot_off = pa_off + (size_t)(n_aux + 1) * 8, pa_ptrs = pa_slot_off + (size_t)n_pipe_slots * 8,
+                         pa_items = pa_ptrs + n_ptrs * 8, pa_flags = pa_items + items.size() * sizeof(Bm25ScatterItem) + (size_t)n_aux * 4,
+                         pa_bytes = pa_flags + (size_t)n_pipe_slots * 4;
+            pa_count_of = pa_items + items.size() * sizeof(Bm25ScatterItem);
+            NIDX_HIP(cx.h_in_a.reserve(pa_bytes));
+            NIDX_HIP(cx.s_in_a.reserve(pa_bytes));
+            unsigned char *h_a = cx.h_in_a.as<unsigned char>(), *d_a = cx.s_in_a.as<unsigned char>();
+            memcpy(h_a + pa_off, out_off.data(), (size_t)(n_aux + 1) * 8);
+            unsigned long long *h_slot_off = reinterpret_cast<unsigned long long *>(h_a + pa_slot_off);
+            uint32_t *h_count_of = reinterpret_cast<uint32_t *>(h_a + pa_count_of);
+            for (uint32_t j = 0; j < n_sets; j++) {
+                h_count_of[j] = slot_of_set[j];   // (kBm25NoSlot: the empty list)
+                if (slot_of_set[j] != kBm25NoSlot) h_slot_off[slot_of_set[j]] = out_off[j];
+            }
+            for (uint32_t r = 0; r < n_rows_d; r++) h_count_of[n_own + r] = n_pipe_slots + r;
+            if (n_ptrs) memcpy(h_a + pa_ptrs, cx.w_row_ptrs.data(), n_ptrs * 8);
+            if (!items.empty()) memcpy(h_a + pa_items, items.data(), items.size() * sizeof(Bm25ScatterItem));
+            if (n_pipe_slots) memcpy(h_a + pa_flags, comp_of_slot.data(), (size_t)n_pipe_slots * 4);
+            NIDX_HIP(hipMemcpyAsync(cx.s_in_a.p, cx.h_in_a.p, pa_bytes, hipMemcpyHostToDevice, cx.stream));
+            if (n_pipe_slots && words) {
+                NIDX_HIP(cx.s_set_bits.reserve((size_t)n_pipe_slots * words * 8));
+                NIDX_HIP(hipMemsetAsync(cx.s_set_bits.p, 0, (size_t)n_pipe_slots * words * 8, cx.stream));
+                if (!items.empty()) {
+                    NIDX_HIP(launch_bm25_set_scatter(reinterpret_cast<const Bm25ScatterItem *>(d_a + pa_items), (uint32_t)items.size(), seg.doc_ids.as<uint32_t>(),
+                                                     seg.n_docs, words, cx.s_set_bits.as<uint64_t>(), cx.stream));
+                    tr->aux_launches++;
+                }
+                if (any_comp) {
+                    NIDX_HIP(launch_bm25_set_complement(cx.s_set_bits.as<uint64_t>(), reinterpret_cast<const uint32_t *>(d_a + pa_flags), n_pipe_slots, words,
+                                                        seg.n_docs, cx.stream));
+                    tr->aux_launches++;
+                }
+                NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>(), words, n_pipe_slots, reinterpret_cast<const unsigned long long *>(d_a + pa_slot_off),
+                                               cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>(), cx.stream));
+                tr->aux_launches++;
+            }
+            if (n_rows_d && words) {
+                NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
+                NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
+                if (all_row) {
+                    NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
+                    tr->aux_launches++;
+                }
+                const uint32_t before = rs->stats.projection_launches + rs->stats.compaction_launches;
+                if (int32_t rc = project_rows(reinterpret_cast<const uint64_t *const *>(d_a + pa_ptrs), n_proj, any_field,
+                                              reinterpret_cast<const unsigned long long *>(d_a + pa_off) + n_own, cx.s_set_counts.as<uint32_t>() + n_pipe_slots))
+                    return rc;
+                tr->aux_launches += rs->stats.projection_launches + rs->stats.compaction_launches - before;
+            }
+            // the estimates the work list is planned from (set_counts stays a host-side guess: the exact counts are on the device)
+            for (uint32_t j = 0; j < n_sets; j++) set_counts[j] = (uint32_t)(out_off[j + 1] - out_off[j]);   // min(sum df, n_docs), n_docs of a complement
+            for (uint32_t r = 0; r < n_rows_d; r++) {
+                uint64_t est = bm25_estimate_all(seg.n_docs);
+                if (!(all_row && r == n_rows_d - 1)) {
+                    const PrefilterRows &R = *rs->rows;
+                    const uint32_t fr = rs->distinct[r], rr = rs->any_res ? rs->distinct_res[r] : kPrefilterRowNone;
+                    const uint64_t f_docs = fr == kPrefilterRowNone ? 0 : fr < R.row_docs.size() ? R.row_docs[fr] : ~0ull;
+                    const uint64_t r_docs = rr == kPrefilterRowNone ? 0 : rr < R.res_row_docs.size() ? R.res_row_docs[rr] : ~0ull;
+                    est = bm25_estimate_row(row_bound, bm25_estimate_row_part(f_docs, rs->link->segment_postings[s], rs->link->linked_documents),
+                                            bm25_estimate_row_part(r_docs, rs->any_res ? rs->link->res_segment_postings[s] : 0, rs->link->linked_resources));
+                }
+                set_counts[n_own + r] = (uint32_t)est;
+            }
         }
         // A set owns a bitset when it has terms or the complement flag.  A set with neither — every row set is one — is the empty
         // list its zeroed count already says: no bitset, no place in a compaction.  Scratch follows the sets that scatter, not the queries.
@@ -2030,7 +2175,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         };
         uint32_t n_bitsets = 0;
         for (uint32_t j = 0; j < n_sets; j++) n_bitsets += owns_bits(j) ? 1u : 0u;
-        if (n_bitsets && words) {
+        if (n_bitsets && words && !pipe_aux) {
             NIDX_HIP(cx.s_set_bits.reserve(std::max<size_t>((size_t)n_bitsets * words, 1) * 8));
             NIDX_HIP(launch_bitset_fill(cx.s_set_bits.as<uint64_t>(), n_bitsets * words, 0, 0, cx.stream));   // (n_bits matters when filling with ones only)
             uint32_t slot = 0;
@@ -2058,7 +2203,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 j = j1;
             }
         }
-        if (n_rows_d && words) {
+        if (n_rows_d && words && !pipe_aux) {
             // every distinct row onto this segment in one launch, every row's list in one compaction; the All requests share a row of ones
             NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
             NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
@@ -2067,34 +2212,15 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                 n_proj--;
                 NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
             }
+            bool any_field = false;
             if (n_proj) {
-                // [n_proj field rows | n_proj resource rows]; nullptr: the row set has no such part
-                cx.w_row_ptrs.assign((size_t)n_proj * (rs->any_res ? 2 : 1), nullptr);
-                bool any_field = false;
-                for (uint32_t r = 0; r < n_proj; r++) {
-                    if (rs->distinct[r] != kPrefilterRowNone) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]], any_field = true;
-                    if (rs->any_res && rs->distinct_res[r] != kPrefilterRowNone) cx.w_row_ptrs[n_proj + r] = rs->rows->res_row_ptr[rs->distinct_res[r]];
-                }
+                any_field = row_sources(n_proj);
                 NIDX_HIP(cx.s_row_ptrs.reserve(cx.w_row_ptrs.size() * sizeof(uint64_t *)));
                 NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), cx.w_row_ptrs.size() * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
-                if (any_field) {
-                    NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, (uint32_t)rs->rows->layout.words(),
-                                                           rs->link->doc_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
-                                                           seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
-                                                           cx.s_row_stats.as<unsigned long long>(), cx.stream));
-                    rs->stats.projection_launches++;
-                }
-                if (rs->any_res) {   // the uuid lists of the set resources, into the same bitsets: one more launch
-                    NIDX_HIP(launch_bm25_prefilter_project(cx.s_row_ptrs.as<const uint64_t *>() + n_proj, n_proj, (uint32_t)rs->rows->res_words,
-                                                           rs->link->res_term.as<uint32_t>(), seg.term_offsets.as<unsigned long long>(),
-                                                           seg.doc_ids.as<uint32_t>(), seg.n_docs, words, cx.s_row_bits.as<uint64_t>(),
-                                                           cx.s_row_stats.as<unsigned long long>(), cx.stream));
-                    rs->stats.projection_launches++;
-                }
             }
-            NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, cx.s_aux_out_off.as<unsigned long long>() + n_own,
-                                           cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_own, cx.stream));
-            rs->stats.compaction_launches++;
+            if (int32_t rc = project_rows(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, any_field, cx.s_aux_out_off.as<unsigned long long>() + n_own,
+                                          cx.s_set_counts.as<uint32_t>() + n_own))
+                return rc;
         }
         for (uint32_t j = 0; j < n_phrases; j++) {
             const uint64_t n_driver = out_off[n_sets + j + 1] - out_off[n_sets + j];
@@ -2143,10 +2269,12 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
                                                  cx.s_aux_tfs.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_sets + n_phrases + j, cx.stream));
             }
         }
-        if (n_aux) {
+        if (n_aux && pipe_aux) NIDX_HIP(cx.s_aux_off.reserve((2 * (size_t)n_aux + 2) * 8));   // (written by bm25_aux_ranges_kernel, below)
+        if (n_aux && !pipe_aux) {
             NIDX_HIP(hipMemcpyAsync(set_counts.data(), cx.s_set_counts.p, (size_t)n_aux * 4, hipMemcpyDeviceToHost, cx.stream));
             if (n_rows_d) NIDX_HIP(hipMemcpyAsync(row_stats, cx.s_row_stats.p, 16, hipMemcpyDeviceToHost, cx.stream));   // (running sums over the segments)
             NIDX_HIP(hipStreamSynchronize(cx.stream));
+            if (tr) tr->syncs++;
             for (uint32_t r = 0; r < n_rows_d; r++) rs->stats.list_entries += set_counts[n_own + r];
             if (n_rows_d) rs->stats.documents_visited = row_stats[0], rs->stats.postings_written = row_stats[1];
             for (uint32_t j = 0; j < n_aux; j++) {
@@ -2373,10 +2501,21 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         const size_t o_total = (o_count + (size_t)nq * 4 + 7) & ~(size_t)7, o_post = o_total + (size_t)nq * 8, o_seg = o_post + (size_t)nq * 8;
         const bool cat = idx->concatenated();
         const size_t out_bytes = o_seg + (cat ? (size_t)nq * kk * 4 : 0);   // concatenated layout: + segment u32 [nq][kk]
-        NIDX_HIP(cx.h_outpack.reserve(out_bytes));
+        // a pipelined batch with row sets: behind the result block what the wait's stats need, [2] u64 of the projections | [rows] u32 counts
+        const size_t o_stats = (out_bytes + 7) & ~(size_t)7, stats_bytes = pipe_aux && n_rows_d ? 16 + (size_t)n_rows_d * 4 : 0;
+        NIDX_HIP(cx.h_outpack.reserve(stats_bytes ? o_stats + stats_bytes : out_bytes));
         void *dp = nullptr;
         NIDX_HIP(hipHostGetDevicePointer(&dp, cx.h_outpack.p, 0));
         unsigned char *d_out = static_cast<unsigned char *>(dp);
+        if (pipe_aux) {
+            const unsigned char *d_a = cx.s_in_a.as<unsigned char>();
+            NIDX_HIP(launch_bm25_aux_ranges(reinterpret_cast<const unsigned long long *>(d_a), reinterpret_cast<const uint32_t *>(d_a + pa_count_of),
+                                            cx.s_set_counts.as<uint32_t>(), n_aux, cx.s_aux_off.as<unsigned long long>(), n_own,
+                                            stats_bytes ? reinterpret_cast<uint32_t *>(d_out + o_stats + 16) : nullptr,
+                                            stats_bytes ? cx.s_row_stats.as<unsigned long long>() : nullptr,
+                                            stats_bytes ? reinterpret_cast<unsigned long long *>(d_out + o_stats) : nullptr, cx.stream));
+            tr->aux_launches++;
+        }
         NIDX_HIP(cx.s_count.reserve(nw * 4));
         NIDX_HIP(cx.s_total.reserve(nw * 8));
         NIDX_HIP(cx.s_postings.reserve(nw * 8));
@@ -2489,7 +2628,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         const unsigned long long *h_total = reinterpret_cast<const unsigned long long *>(h_out + o_total);
         const unsigned long long *h_post = reinterpret_cast<const unsigned long long *>(h_out + o_post);
         const uint32_t *h_seg = reinterpret_cast<const uint32_t *>(h_out + o_seg);   // (concatenated layout only)
-        if (async_slot && idx->segs.size() == 1 && n_aux == 0 && n_slots == 0 && order_field < 0 && !a.dbg) {
+        if (async_slot && idx->segs.size() == 1 && (n_aux == 0 || pipe_aux) && n_slots == 0 && order_field < 0 && !a.dbg) {
             // pipelined: the collect step runs in nidx_gpu_bm25_search_wait (the buffers are the slot's: swapped in by submit)
             if (host_dbg)
                 fprintf(stderr, "[bm25 host submit] total=%.0f us: clauses=%.0f set-up=%.0f work list=%.0f staging+upload=%.0f launches=%.0f\n", now_us() - t_entry,
@@ -2499,10 +2638,15 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             sl.nq = nq, sl.k = k, sl.kk = kk;
             sl.cat = cat;
             sl.o_doc = o_doc, sl.o_score = o_score, sl.o_count = o_count, sl.o_total = o_total, sl.o_post = o_post, sl.o_seg = o_seg;
+            sl.pf_stats = rs ? rs->stats : nidx_gpu_bm25_prefilter_search_stats_t{};
+            sl.n_stat_rows = stats_bytes ? n_rows_d : 0u;
+            sl.o_stats = o_stats;
+            if (tr) tr->pipelined = true;
             return NIDX_OK;
         }
         const double t_s0 = now_us();
         NIDX_HIP(hipStreamSynchronize(cx.stream));
+        if (tr) tr->syncs++;
         t_sync += now_us() - t_s0;
         const double t_c0 = now_us();
         float ms = 0.f;
@@ -2637,20 +2781,10 @@ int32_t nidx_gpu_bm25_search_ex(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm2
     return rc;
 } NIDX_ABI_CATCH
 
-// nidx_gpu_bm25_search_ex whose term sets may be row sets: the documents of the posting lists linked to the documents set in a
-// resident prefilter row (prefilter_handover.h).  Everything is checked here, before the search writes an output.
-int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
-                                         const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
-                                         const uint64_t *clause_offsets, uint32_t nq, const nidx_gpu_bm25_search_options_t *opt,
-                                         const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
-                                         uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out) try {
-    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
-    if (!idx || !clause_offsets || !out_count || !opt) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    const PrefilterTermLink *l = reinterpret_cast<const PrefilterTermLink *>(link);
-    const PrefilterRows *r = reinterpret_cast<const PrefilterRows *>(rows);
-    std::lock_guard<std::mutex> lock(idx->mu);
-    std::shared_lock<std::shared_mutex> rlock(idx->rw);
-    Bm25RowSets rs;
+// The checks of the row sets of nidx_gpu_bm25_search_prefiltered and of nidx_gpu_bm25_search_submit_prefiltered, and the distinct rows the
+// call names -> rs.  The caller holds idx->rw (shared); nothing is launched, queued or written to an output here.
+static int32_t bm25_row_sets_check(const Bm25Index *idx, const PrefilterTermLink *l, const PrefilterRows *r, const nidx_gpu_bm25_search_options_t *opt,
+                                   const uint32_t *prefilter_of_term_set, Bm25RowSets &rs) {
     rs.link = l, rs.rows = r;
     const uint32_t n_sets = opt->n_term_sets;
     bool any = false;
@@ -2729,6 +2863,24 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
         }
     }
     rs.stats.rows_projected = (uint32_t)rs.distinct.size() - (!rs.distinct.empty() && rs.distinct.back() == kPrefilterRowAll ? 1u : 0u);
+    return NIDX_OK;
+}
+
+// nidx_gpu_bm25_search_ex whose term sets may be row sets: the documents of the posting lists linked to the documents set in a
+// resident prefilter row (prefilter_handover.h).  Everything is checked here, before the search writes an output.
+int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
+                                         const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
+                                         const uint64_t *clause_offsets, uint32_t nq, const nidx_gpu_bm25_search_options_t *opt,
+                                         const uint32_t *prefilter_of_term_set, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
+                                         uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !clause_offsets || !out_count || !opt) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    std::shared_lock<std::shared_mutex> rlock(idx->rw);
+    Bm25RowSets rs;
+    if (int32_t rc_check = bm25_row_sets_check(idx, reinterpret_cast<const PrefilterTermLink *>(link), reinterpret_cast<const PrefilterRows *>(rows), opt,
+                                               prefilter_of_term_set, rs))
+        return rc_check;
     const int32_t rc = bm25_search_locked(idx, idx->main, nullptr, clauses, clause_offsets, nq, opt, out_docaddr, out_score, out_count, out_total, out_postings,
                                           rs.distinct.empty() ? nullptr : &rs);
     {
@@ -2744,11 +2896,11 @@ int32_t nidx_gpu_bm25_search_prefiltered(nidx_gpu_bm25_index_t *index, const nid
 // more than its kernels cost the device) ----------
 #define NIDX_BM25_PIPELINE_DEPTH NIDX_GPU_BM25_MAX_TICKETS   /* include/nidx_gpu.h */
 
-int32_t nidx_gpu_bm25_search_submit(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
-                                    uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *ticket_out) try {
-    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
-    if (!idx || !clause_offsets || !opt || !ticket_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
-    *ticket_out = 0;
+// Takes a slot, runs the batch on it and hands out its ticket.  `rlock` is idx->rw's shared lock: taken here once the slot is this
+// thread's (nidx_gpu_bm25_search_submit), or held already by a caller that checked its row sets under it.
+static int32_t bm25_submit_ticket(Bm25Index *idx, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets, uint32_t nq,
+                                  const nidx_gpu_bm25_search_options_t *opt, Bm25RowSets *rs, Bm25TicketRun *tr,
+                                  std::shared_lock<std::shared_mutex> &rlock, uint64_t *ticket_out) {
     NIDX_HIP(hipSetDevice(idx->device));
     Bm25Slot *slot = nullptr;
     {
@@ -2792,20 +2944,71 @@ int32_t nidx_gpu_bm25_search_submit(nidx_gpu_bm25_index_t *index, const nidx_gpu
         // (resize, not assign: the search zeroes the counts itself and nothing is read beyond a query's count)
         slot->r_docaddr.resize((size_t)nq * kk1), slot->r_score.resize((size_t)nq * kk1);
         slot->r_count.resize(nq), slot->r_total.resize(nq), slot->r_postings.resize(nq);
-        std::shared_lock<std::shared_mutex> rlock(idx->rw);
+        slot->pf_stats = nidx_gpu_bm25_prefilter_search_stats_t{};
+        slot->n_stat_rows = 0;
+        if (!rlock.owns_lock()) rlock.lock();
         rc = bm25_search_locked(idx, slot->cx, slot, clauses, clause_offsets, nq, opt, slot->r_docaddr.data(), slot->r_score.data(), slot->r_count.data(),
-                                slot->r_total.data(), slot->r_postings.data());
+                                slot->r_total.data(), slot->r_postings.data(), rs, tr);
+        if (rc == NIDX_OK && !slot->launched && rs) slot->pf_stats = rs->stats;   // (ran to completion in here: the stats are final)
         prep.ok = rc == NIDX_OK;
     }
     if (rc != NIDX_OK) return rc;
     *ticket_out = slot->ticket;   // (set by ~Prepare; the slot is this thread's until its ticket is handed out)
     return NIDX_OK;
+}
+
+int32_t nidx_gpu_bm25_search_submit(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
+                                    uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *ticket_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !clause_offsets || !opt || !ticket_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    std::shared_lock<std::shared_mutex> rlock(idx->rw, std::defer_lock);
+    return bm25_submit_ticket(idx, clauses, clause_offsets, nq, opt, nullptr, nullptr, rlock, ticket_out);
 } NIDX_ABI_CATCH
 
-int32_t nidx_gpu_bm25_search_wait(nidx_gpu_bm25_index_t *index, uint64_t ticket, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
-                                  uint64_t *out_total, uint64_t *out_postings) try {
+// nidx_gpu_bm25_search_prefiltered as a ticket.  The row sets are checked first, under the index's shared lock alone (no idx->mu: the
+// blocking entries of this index go on side by side); a refusal takes no slot and queues nothing.
+int32_t nidx_gpu_bm25_search_submit_prefiltered(nidx_gpu_bm25_index_t *index, const nidx_gpu_prefilter_term_link_t *link,
+                                                const nidx_gpu_prefilter_rows_t *rows, const nidx_gpu_bm25_clause_t *clauses,
+                                                const uint64_t *clause_offsets, uint32_t nq, const nidx_gpu_bm25_search_options_t *opt,
+                                                const uint32_t *prefilter_of_term_set, uint64_t *ticket_out) try {
     Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
-    if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!idx || !clause_offsets || !opt || !ticket_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    *ticket_out = 0;
+    std::shared_lock<std::shared_mutex> rlock(idx->rw);
+    Bm25RowSets rs;
+    if (int32_t rc_check = bm25_row_sets_check(idx, reinterpret_cast<const PrefilterTermLink *>(link), reinterpret_cast<const PrefilterRows *>(rows), opt,
+                                               prefilter_of_term_set, rs))
+        return rc_check;
+    Bm25TicketRun tr;
+    if (int32_t rc = bm25_submit_ticket(idx, clauses, clause_offsets, nq, opt, rs.distinct.empty() ? nullptr : &rs, &tr, rlock, ticket_out)) return rc;
+    idx->ts_tickets++;
+    if (tr.pipelined) {
+        idx->ts_pipelined++;
+        idx->ts_submit_syncs += tr.syncs;
+        idx->ts_aux_launches += tr.aux_launches;
+    } else {
+        idx->ts_ran_in_submit++;
+    }
+    uint64_t n_row_sets = 0;
+    for (uint32_t j = 0; prefilter_of_term_set && j < opt->n_term_sets; j++) n_row_sets += prefilter_of_term_set[j] != 0xffffffffu ? 1u : 0u;
+    idx->ts_row_sets += n_row_sets;
+    idx->ts_term_sets += opt->n_term_sets - n_row_sets;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_bm25_ticket_stats(nidx_gpu_bm25_index_t *index, nidx_gpu_bm25_ticket_stats_t *out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    out->tickets = idx->ts_tickets.load(), out->pipelined = idx->ts_pipelined.load(), out->ran_in_submit = idx->ts_ran_in_submit.load();
+    out->submit_synchronisations = idx->ts_submit_syncs.load(), out->aux_launches = idx->ts_aux_launches.load();
+    out->row_sets = idx->ts_row_sets.load(), out->term_sets = idx->ts_term_sets.load();
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// Both wait entries: a ticket of either submit entry; stats_out (may be NULL) gets the row sets' stats, zeros for a batch without any.
+static int32_t bm25_wait_ticket(Bm25Index *idx, uint64_t ticket, uint64_t *out_docaddr, float *out_score, uint32_t *out_count, uint64_t *out_total,
+                                uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out) {
     Bm25Slot *slot = nullptr;
     {
         std::lock_guard<std::mutex> lock(idx->slots_mu);
@@ -2852,6 +3055,15 @@ int32_t nidx_gpu_bm25_search_wait(nidx_gpu_bm25_index_t *index, uint64_t ticket,
                 if (out_score) out_score[(size_t)q * k + i] = h_score[(size_t)q * kk + i];
             }
         }
+        if (stats_out) {
+            *stats_out = slot->pf_stats;
+            if (slot->n_stat_rows) {   // what bm25_aux_ranges_kernel left behind the result block
+                const unsigned long long *h_row_stats = reinterpret_cast<const unsigned long long *>(h_out + slot->o_stats);
+                const uint32_t *h_rows = reinterpret_cast<const uint32_t *>(h_out + slot->o_stats + 16);
+                stats_out->documents_visited = h_row_stats[0], stats_out->postings_written = h_row_stats[1];
+                for (uint32_t r = 0; r < slot->n_stat_rows; r++) stats_out->list_entries += h_rows[r];
+            }
+        }
         return NIDX_OK;
     }
     for (uint32_t q = 0; q < nq; q++) {
@@ -2863,7 +3075,22 @@ int32_t nidx_gpu_bm25_search_wait(nidx_gpu_bm25_index_t *index, uint64_t ticket,
             if (out_score) out_score[(size_t)q * k + i] = slot->r_score[(size_t)q * k + i];
         }
     }
+    if (stats_out) *stats_out = slot->pf_stats;
     return NIDX_OK;
+}
+
+int32_t nidx_gpu_bm25_search_wait(nidx_gpu_bm25_index_t *index, uint64_t ticket, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
+                                  uint64_t *out_total, uint64_t *out_postings) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    return bm25_wait_ticket(idx, ticket, out_docaddr, out_score, out_count, out_total, out_postings, nullptr);
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_bm25_search_wait_prefiltered(nidx_gpu_bm25_index_t *index, uint64_t ticket, uint64_t *out_docaddr, float *out_score, uint32_t *out_count,
+                                              uint64_t *out_total, uint64_t *out_postings, nidx_gpu_bm25_prefilter_search_stats_t *stats_out) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !out_count) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    return bm25_wait_ticket(idx, ticket, out_docaddr, out_score, out_count, out_total, out_postings, stats_out);
 } NIDX_ABI_CATCH
 
 // open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74): the documents of every posting list in `terms` (the

@@ -487,7 +487,7 @@ int32_t nidx_gpu_prefilter_rows_combine(const nidx_gpu_prefilter_rows_t *text_ro
     std::map<uint32_t, uint32_t> res_ids;
     auto resources = [&](uint32_t i, uint32_t jrow) {
         auto it = res_ids.emplace(jrow, (uint32_t)out->res_row_ptr.size());
-        if (it.second) out->res_row_ptr.push_back(J->row_ptr[jrow]);
+        if (it.second) out->res_row_ptr.push_back(J->row_ptr[jrow]), out->res_row_docs.push_back(J->count[jrow]);
         out->res_row_of_request[i] = it.first->second;
     };
     for (uint32_t i = 0; i < n_requests; i++) {
@@ -560,6 +560,7 @@ int32_t nidx_gpu_prefilter_rows_combine(const nidx_gpu_prefilter_rows_t *text_ro
         if (row_of_item[k] == kPrefilterRowNone) {
             row_of_item[k] = (uint32_t)out->row_ptr.size();
             out->row_ptr.push_back(items[k].out_row);
+            out->row_docs.push_back(counts[k]);
         }
         out->row_of_request[i] = row_of_item[k];
     }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bm25_aux_plan.h"
+
 namespace nidx {
 
 // ---- exact scan (vector_scan.hip) ----
@@ -667,6 +669,21 @@ hipError_t launch_fuzzy_batch(const uint8_t *dict_bytes, const unsigned long lon
 // set bits -> ascending ids (one block per bitset): out[out_offsets[b] ..), counts[b] = number written
 hipError_t launch_bitset_compact(const uint64_t *bits, uint32_t n_words, uint32_t n_sets, const unsigned long long *out_offsets,
                                  uint32_t *out, uint32_t *counts, hipStream_t s);
+// ---- the aux stage of a pipelined batch (nidx_gpu_bm25_search_submit_prefiltered): a fixed number of launches for any number of
+// queries and sets, nothing read back ----
+// every (term set, term) pair of a batch in one launch: work item i (bm25_aux_plan.h) ORs doc_ids[begin, begin + count) into bitset
+// `slot` of `bits` ([n_slots][words], zeroed by the caller); ids >= n_docs are dropped
+hipError_t launch_bm25_set_scatter(const Bm25ScatterItem *items, uint32_t n_items, const uint32_t *doc_ids, uint32_t n_docs, uint32_t words,
+                                   uint64_t *bits, hipStream_t s);
+// bitset `slot` becomes its complement over [0, n_docs) where flags[slot] != 0 (the bits past n_docs stay clear)
+hipError_t launch_bm25_set_complement(uint64_t *bits, const uint32_t *flags, uint32_t n_slots, uint32_t words, uint32_t n_docs, hipStream_t s);
+// the [begin, end) pairs the scoring kernels read (Bm25Args::aux_offsets), from the counts the compactions left on the device:
+// pairs[2 j] = out_off[j], pairs[2 j + 1] = out_off[j] + (count_of[j] == UINT32_MAX ? 0 : counts[count_of[j]]) for j < n_aux, and one
+// closing pair of zeros.  The counts of the lists j >= n_first_row go to host_counts[j - n_first_row] and row_stats[0 .. 2) to
+// host_row_stats (both device-visible host memory, or NULL): what the wait's stats need, written where the result block lands.
+hipError_t launch_bm25_aux_ranges(const unsigned long long *out_off, const uint32_t *count_of, const uint32_t *counts, uint32_t n_aux,
+                                  unsigned long long *pairs, uint32_t n_first_row, uint32_t *host_counts, const unsigned long long *row_stats,
+                                  unsigned long long *host_row_stats, hipStream_t s);
 // PhraseQuery: for every posting i of the driver term (the rarest of the phrase) tmp_tf[i] = number of matches of the phrase in
 // that document (0 = the document does not match); then the matches are compacted in document order into (out_ids, out_tfs)[out_begin ..)
 // and *out_count is set.  slop 0: the number of start positions at which all terms follow each other in order.  slop > 0: tantivy's

@@ -46,6 +46,10 @@ struct PrefilterRows {
     std::vector<DevBuf> chunks;                 // the rows' memory: one allocation per pass or fallback program with Some rows
     std::vector<const uint64_t *> row_ptr;      // [rows] in HBM, layout.words() words each
     std::vector<uint32_t> row_of_request;       // a row, kPrefilterRowAll or kPrefilterRowNone
+    // documents set in every row, as its producer counted them: what the pipelined paragraph search estimates a projected list's
+    // length from (bm25_aux_plan.h) — a planning figure only, never an output
+    std::vector<uint64_t> row_docs;             // [rows]
+    std::vector<uint64_t> res_row_docs;         // [resource rows] resources set
     uint64_t bytes = 0;
     // the resource-granular part of a combined handle (json_index.cpp); empty for the rows of a prefilter batch
     std::shared_ptr<const void> res_owner;      // keeps the JSON rows' memory

@@ -29,6 +29,7 @@ import bisect
 import ctypes as C
 
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
@@ -1414,6 +1415,15 @@ class ParagraphSearcher:
                 rq = requests[i]
                 if not response.results and rq.result_per_page > 0 and rq.min_score == 0.0 and not rq.only_faceted:
                     missed.setdefault(key, []).append(i)
+
+        def run_groups(reruns):
+            return [self._run_group([requests[i] for i in members], fuzzy, True, link, rows) for members, fuzzy in reruns]
+
+        return self._rerun_missed(requests, prefilters, out, missed, run_groups)
+
+    def _rerun_missed(self, requests, prefilters, out, missed: Dict[tuple, List[int]], run_groups) -> List[ParagraphSearchResponse]:
+        """The fuzzy rerun of a batch: `missed` = per group the requests that found nothing and qualify; run_groups([(members, their
+        fuzzy queries)]) -> per group what _run_group returns.  ONE fuzzy_terms_batch before the searches, ONE hit_terms_batch after."""
         if not missed:
             return out
         # the words to expand, each distinct (word, prefix) once
@@ -1427,15 +1437,71 @@ class ParagraphSearcher:
             for key, found in zip(keys, self._index.fuzzy_terms_batch(keys)):
                 pairs[key] = found
         items = []
-        for members in missed.values():
-            fuzzy = [self._fuzzy_clauses(requests[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in members]
-            answers = self._run_group([requests[i] for i in members], fuzzy, True, link, rows)
+        reruns = [(members, [self._fuzzy_clauses(requests[i], prefilters[i], lambda w, p: pairs[(w, p)]) for i in members]) for members in missed.values()]
+        for (members, _), answers in zip(reruns, run_groups(reruns)):
             for i, (response, addrs) in zip(members, answers):
                 out[i] = response
                 # one FuzzyTermQuery per fuzzy word, each logging on its own: a word given twice is two sets
                 items.append((response.results, addrs, [pairs[key] for key in self._fuzzy_words(self._tokens(requests[i])).values()]))
         self._set_matches(items)
         return out
+
+    # ---- the batch form as tickets ---------------------------------------------------------------------------------------------
+    def _submit_group(self, requests: Sequence[ParagraphSearchRequest], queries: Sequence[List[Clause]], link=None, rows=None):
+        """_run_group's search as a ticket of Bm25Searcher.submit_ex -> what _collect_group takes."""
+        k, order, only_faceted, cursors = self._group_key(requests[0])
+        requested = [self._index.facet_request(rq.faceted) for rq in requests]
+        fterms = [[tid for _, _, tid in pairs] for _, pairs in requested] if any(pairs for _, pairs in requested) else None
+        if only_faceted:
+            ticket = self._index.searcher.submit_ex(list(queries), 0, link, rows, facets=fterms)
+        else:
+            after = [rq.search_after for rq in requests] if cursors else None
+            ticket = self._index.searcher.submit_ex(list(queries), k + 1, link, rows, after=after, order_field=-1 if order is None else order[0],
+                                                    order_desc=True if order is None else order[1], facets=fterms)
+        return ticket, requested
+
+    def _collect_group(self, requests: Sequence[ParagraphSearchRequest], pending, fuzzy: bool):
+        ticket, requested = pending
+        r = self._index.searcher.wait_ex(ticket)
+        return [self._assemble(rq, r, row, fuzzy, *requested[row]) for row, rq in enumerate(requests)]
+
+    def search_many_submit(self, requests: Sequence[ParagraphSearchRequest], prefilters=None, link: Optional[PrefilterTermLink] = None):
+        """search_many whose searches are tickets: one Bm25Searcher.submit_ex per _group_key group is queued and the call returns; a
+        filtered group (term sets, or row sets of ResidentPrefilters with `link`) waits for nothing.  `prefilters` and `link` must stay
+        open until search_many_wait(handle) has returned.  -> handle"""
+        requests = list(requests)
+        n = len(requests)
+        prefilters, rows = self._per_request_prefilters(prefilters, n)
+        out: List[Optional[ParagraphSearchResponse]] = [None] * n
+        groups: Dict[tuple, List[int]] = {}
+        for i, (rq, pf) in enumerate(zip(requests, prefilters)):
+            if pf is not None and pf.kind == "None":
+                out[i] = ParagraphSearchResponse(0, [], False, rq.body, {}, False)
+            else:
+                groups.setdefault(self._group_key(rq), []).append(i)
+        pending = {key: self._submit_group([requests[i] for i in members], [self._clauses(requests[i], prefilters[i]) for i in members], link, rows)
+                   for key, members in groups.items()}
+        return SimpleNamespace(requests=requests, prefilters=prefilters, rows=rows, link=link, out=out, groups=groups, pending=pending)
+
+    def search_many_wait(self, handle) -> List[ParagraphSearchResponse]:
+        """-> what search_many(requests, prefilters, link) returns, for the handle of search_many_submit: the responses are assembled,
+        the requests that found nothing and qualify share one fuzzy_terms_batch, their reruns go out as tickets side by side, and one
+        hit_terms_batch sets the matches."""
+        requests, prefilters, out = handle.requests, handle.prefilters, handle.out
+        missed: Dict[tuple, List[int]] = {}
+        for key, members in handle.groups.items():
+            answers = self._collect_group([requests[i] for i in members], handle.pending.pop(key), False)
+            for i, (response, _) in zip(members, answers):
+                out[i] = response
+                rq = requests[i]
+                if not response.results and rq.result_per_page > 0 and rq.min_score == 0.0 and not rq.only_faceted:
+                    missed.setdefault(key, []).append(i)
+
+        def run_groups(reruns):
+            tickets = [self._submit_group([requests[i] for i in members], fuzzy, handle.link, handle.rows) for members, fuzzy in reruns]
+            return [self._collect_group([requests[i] for i in members], t, True) for (members, _), t in zip(reruns, tickets)]
+
+        return self._rerun_missed(requests, prefilters, out, missed, run_groups)
 
     # ---- suggest ------------------------------------------------------------------------------------------------------------
     @staticmethod
