@@ -79,6 +79,7 @@ struct Bm25Ctx {
     std::vector<Bm25Work> w_work;
     std::vector<uint8_t> w_q_union;
     std::vector<uint64_t> w_postings, w_clause_len;
+    std::vector<uint32_t> w_clause_term;
     std::vector<Bm25ClauseDev> w_dev_clauses;
     std::vector<Bm25StreamClause> w_ucl;   // (entries of queries that are not union queries keep whatever they held: never read)
     std::vector<Bm25AfterDev> w_after;
@@ -130,20 +131,17 @@ struct Bm25Slot {
     bool busy = false, preparing = false, launched = false;
     uint64_t ticket = 0;
     Bm25Ctx cx;
-    // layout of cx.h_outpack for the collect step
-    uint32_t nq = 0, k = 0, kk = 0;
-    bool cat = false;   // the resident layout at submit was the concatenation (a sync may have replaced it by the time of the wait)
-    size_t o_doc = 0, o_score = 0, o_count = 0, o_total = 0, o_post = 0, o_seg = 0;
+    uint32_t nq = 0, k = 0;
+    // layout of cx.h_outpack for the collect step, as it was at submit (out.cat: a sync may have replaced the resident layout by the
+    // time of the wait).  Of a launched batch with row sets the counts of the out.n_stat_rows rows' lists and the projections' two
+    // counters lie at out.o_stats ([2] u64 | [n_stat_rows] u32): what nidx_gpu_bm25_search_wait_prefiltered adds to pf_stats.
+    Bm25ResultLayout out;
     // a request the pipeline does not cover (term sets, phrases, nested queries, facets, order by a field) runs synchronously inside
     // submit; its results wait here
     std::vector<uint64_t> r_docaddr, r_total, r_postings;
     std::vector<float> r_score;
     std::vector<uint32_t> r_count;
-    // nidx_gpu_bm25_search_wait_prefiltered: what of the stats the host knew at submit; of a launched batch with row sets the counts
-    // of the n_stat_rows rows' lists and the projections' two counters lie at o_stats of cx.h_outpack ([2] u64 | [n_stat_rows] u32)
-    nidx_gpu_bm25_prefilter_search_stats_t pf_stats = {};
-    uint32_t n_stat_rows = 0;
-    size_t o_stats = 0;
+    nidx_gpu_bm25_prefilter_search_stats_t pf_stats = {};   // nidx_gpu_bm25_search_wait_prefiltered: what of the stats the host knew at submit
 };
 
 // What nidx_gpu_bm25_search_submit_prefiltered asks of bm25_search_locked and learns from it.
@@ -1709,54 +1707,88 @@ struct Bm25RowSets {
     nidx_gpu_bm25_prefilter_search_stats_t stats = {};
 };
 
-// The search itself, on the context `cx` (the caller owns it for the duration and holds idx->rw shared).  With `async_slot` set and a
-// request the pipeline covers it returns after the last asynchronous call (launches + the device-to-host transfer of the result block
-// are queued on the slot's stream).  With `tr` (nidx_gpu_bm25_search_submit_prefiltered) the pipeline also covers batches whose aux
-// lists are all term sets and row sets: their exact lengths then never reach the host — the work list is planned from estimates
-// (bm25_aux_plan.h), the [begin, end) pairs the scoring kernels read are written by bm25_aux_ranges_kernel.
-static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_slot, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
-                                  uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *out_docaddr, float *out_score,
-                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings, Bm25RowSets *rs = nullptr,
-                                  Bm25TicketRun *tr = nullptr) {
-    const double t_entry = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    NIDX_HIP(hipSetDevice(idx->device));
-    // other tickets are out: this batch's launches will share the GPU with theirs (the throughput shape of the work list, below)
-    bool crowded = false;
-    if (async_slot) {
-        std::lock_guard<std::mutex> lock(idx->slots_mu);
-        for (auto &sl : idx->slots)
-            if (sl.get() != async_slot && (sl->busy || sl->preparing)) crowded = true;
+// ---- the stages of bm25_search_locked ------------------------------------------------------------------------------------------------
+// Where one call's results go (total and postings may be NULL; docaddr and score too when k == 0).
+struct Bm25Outputs {
+    uint64_t *docaddr;
+    float *score;
+    uint32_t *count;
+    uint64_t *total, *postings;
+};
+
+// The request as its checks left it: sizes, the nested-query records, the facet tables.  Host memory only; the clause weights are in
+// cx.w_dev_clauses.
+struct Bm25Request {
+    const nidx_gpu_bm25_clause_t *clauses = nullptr;
+    const uint64_t *clause_offsets = nullptr;
+    uint32_t nq = 0;
+    const nidx_gpu_bm25_search_options_t *opt = nullptr;
+    Bm25RowSets *rs = nullptr;
+    uint32_t k = 0, kk = 1;
+    int order_field = -1;
+    const nidx_gpu_bm25_search_after_t *after = nullptr;
+    uint64_t n_clauses = 0, n_pairs = 0;
+    // the aux lists of every segment, in this order: term sets, phrases, nested queries, the distinct rows of the row sets
+    uint32_t n_sets = 0, n_phrases = 0, n_sub = 0, n_rows_d = 0;
+    std::vector<SubqueryDev> subs;   // (`driver` is chosen per segment: bm25_aux_layout)
+    // facets: one matching-document bitset per query that asks for counts
+    std::vector<int> match_slot, pair_slot;
+    std::vector<uint32_t> pair_term;
+    uint32_t n_slots = 0;
+    uint32_t n_own() const { return n_sets + n_phrases + n_sub; }
+    uint32_t n_aux() const { return n_own() + n_rows_d; }
+    // the aux list term set j reads: its own, or — a row set — the list of its distinct row
+    uint32_t aux_of_set(uint32_t j) const {
+        const uint32_t r = n_rows_d ? rs->row_of_set[j] : 0xffffffffu;
+        return r == 0xffffffffu ? j : n_own() + r;
     }
-    if (const char *e = getenv("NIDX_GPU_BM25_CROWDED")) crowded = atoi(e) != 0;   // measurement: 0 / 1 pins the shape
-    const uint32_t k = opt->k;
-    const nidx_gpu_bm25_search_after_t *after = opt->after;
+};
+static_assert(BM25_AUX_TERM == NIDX_BM25_TERM_SET, "a term-set clause of the caller is already the device's aux clause of the same index");
+
+// Bm25Weight::for_terms of a phrase: the idf of every term, summed in order
+static float bm25_phrase_weight(const Bm25Index *idx, const nidx_gpu_bm25_search_options_t *opt, uint32_t j, float boost) {
+    float idf_sum = 0.0f;
+    for (uint64_t i = opt->phrase_offsets[j]; i < opt->phrase_offsets[j + 1]; i++) {
+        uint64_t df = 0;
+        for (const Bm25Segment &sg : idx->segs) df += sg.term_offsets_host[opt->phrase_terms[i] + 1] - sg.term_offsets_host[opt->phrase_terms[i]];
+        idf_sum += bm25_idf(df, idx->total_docs);
+    }
+    return idf_sum * (1.0f + kK1) * boost;
+}
+
+// Stage 1, host only: zero the outputs, check every argument (in this order: a request with several defects reports the first), build
+// the nested-query records, the clause weights (cx.w_dev_clauses) and the facet tables.  rq comes in with the caller's pointers set.
+static int32_t bm25_compile_request(const Bm25Index *idx, Bm25Ctx &cx, Bm25Request &rq, const Bm25Outputs &out) {
+    const nidx_gpu_bm25_search_options_t *opt = rq.opt;
+    const uint32_t nq = rq.nq;
+    rq.k = opt->k, rq.kk = std::max<uint32_t>(opt->k, 1);
+    rq.after = opt->after;
     for (uint32_t q = 0; q < nq; q++) {
-        out_count[q] = 0;
-        if (out_total) out_total[q] = 0;
-        if (out_postings) out_postings[q] = 0;
+        out.count[q] = 0;
+        if (out.total) out.total[q] = 0;
+        if (out.postings) out.postings[q] = 0;
     }
-    const uint64_t n_pairs = opt->facet_offsets ? opt->facet_offsets[nq] : 0;
+    const uint64_t n_pairs = rq.n_pairs = opt->facet_offsets ? opt->facet_offsets[nq] : 0;
     for (uint64_t p = 0; p < n_pairs && opt->out_facet_counts; p++) opt->out_facet_counts[p] = 0;
     if (nq == 0) return NIDX_OK;
     // the paragraph search asks for result_per_page + 1 with pages up to max(top_k, fusion / reranker window) = 500
-    if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "TopDocs limit > %d is not supported (got %u)", NIDX_K_MAX, k);
-    const int order_field = opt->order_field;
+    if (rq.k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "TopDocs limit > %d is not supported (got %u)", NIDX_K_MAX, rq.k);
+    const int order_field = rq.order_field = opt->order_field;
     if (order_field > 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown fast field %d", order_field);
     if (order_field >= 0) {
-        if (after) return fail(NIDX_ERR_UNSUPPORTED, "search-after applies to the score order only");
+        if (rq.after) return fail(NIDX_ERR_UNSUPPORTED, "search-after applies to the score order only");
         for (const Bm25Segment &sg : idx->segs)
             if (sg.n_docs && !sg.order_key[order_field].p) return fail(NIDX_ERR_INVALID_ARGUMENT, "fast field %d was not registered for every segment", order_field);
     }
     if (n_pairs && (!opt->facet_terms || !opt->out_facet_counts)) return fail(NIDX_ERR_INVALID_ARGUMENT, "facets without terms / output");
-    const uint32_t n_sets = opt->n_term_sets;
+    const uint32_t n_sets = rq.n_sets = opt->n_term_sets;
     if (n_sets && (!opt->term_set_offsets || (opt->term_set_offsets[n_sets] && !opt->term_set_terms)))
         return fail(NIDX_ERR_INVALID_ARGUMENT, "term sets without terms");
     for (uint64_t i = 0; n_sets && i < opt->term_set_offsets[n_sets]; i++)
         if (opt->term_set_terms[i] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set: term id %u out of range", opt->term_set_terms[i]);
     // row sets (nidx_gpu_bm25_search_prefiltered): the distinct rows are aux lists behind the term sets, phrases and nested queries
-    const uint32_t n_rows_d = rs ? (uint32_t)rs->distinct.size() : 0u;
-    auto row_of_set = [&](uint32_t j) { return n_rows_d ? rs->row_of_set[j] : 0xffffffffu; };
-    const uint32_t n_phrases = opt->n_phrases;
+    rq.n_rows_d = rq.rs ? (uint32_t)rq.rs->distinct.size() : 0u;
+    const uint32_t n_phrases = rq.n_phrases = opt->n_phrases;
     if (n_phrases && (!opt->phrase_offsets || !opt->phrase_terms)) return fail(NIDX_ERR_INVALID_ARGUMENT, "phrases without terms");
     for (uint32_t j = 0; j < n_phrases; j++) {
         const uint64_t m = opt->phrase_offsets[j + 1] - opt->phrase_offsets[j];
@@ -1771,27 +1803,17 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
     for (uint32_t j = 0; j < n_phrases && opt->phrase_slops; j++)
         if (opt->phrase_slops[j] && opt->phrase_offsets[j + 1] - opt->phrase_offsets[j] < 2)
             return fail(NIDX_ERR_INVALID_ARGUMENT, "a phrase with slop has at least two terms");
-    // Bm25Weight::for_terms of a phrase: the idf of every term, summed in order
-    auto phrase_weight = [&](uint32_t j, float boost) {
-        float idf_sum = 0.0f;
-        for (uint64_t i = opt->phrase_offsets[j]; i < opt->phrase_offsets[j + 1]; i++) {
-            uint64_t df = 0;
-            for (const Bm25Segment &sg : idx->segs) df += sg.term_offsets_host[opt->phrase_terms[i] + 1] - sg.term_offsets_host[opt->phrase_terms[i]];
-            idf_sum += bm25_idf(df, idx->total_docs);
-        }
-        return idf_sum * (1.0f + kK1) * boost;
-    };
     // nested BooleanQuerys (NIDX_BM25_SUBQUERY): up to 32 leaves each — terms of the dictionary, term sets, phrases, or nested queries
     // with a LOWER index (the caller lists a tree's queries children first), so they are materialised in index order
-    const uint32_t n_sub = opt->n_subqueries;
+    const uint32_t n_sub = rq.n_sub = opt->n_subqueries;
     if (n_sub && (!opt->subquery_offsets || !opt->subquery_clauses)) return fail(NIDX_ERR_INVALID_ARGUMENT, "sub-queries without clauses");
-    std::vector<SubqueryDev> subs(n_sub);
+    rq.subs.resize(n_sub);
     for (uint32_t j = 0; j < n_sub; j++) {
         if (opt->subquery_offsets[j + 1] < opt->subquery_offsets[j]) return fail(NIDX_ERR_INVALID_ARGUMENT, "subquery_offsets not monotone");
         const uint64_t m = opt->subquery_offsets[j + 1] - opt->subquery_offsets[j];
         if (m == 0 || m > BM25_MAX_SUBQUERY_LEAVES)
             return fail(NIDX_ERR_UNSUPPORTED, "a nested query has 1..%d leaves (got %llu)", BM25_MAX_SUBQUERY_LEAVES, (unsigned long long)m);
-        SubqueryDev &sq = subs[j];
+        SubqueryDev &sq = rq.subs[j];
         sq.n = (uint32_t)m;
         sq.driver = 0;
         for (uint32_t t = 0; t < sq.n; t++) {
@@ -1801,12 +1823,12 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             if (cl.term & NIDX_BM25_TERM_SET) {   // ConstScorer(boost) over the union
                 const uint32_t a = cl.term & ~NIDX_BM25_TERM_SET;
                 if (a >= n_sets) return fail(NIDX_ERR_INVALID_ARGUMENT, "nested query %u: term set %u out of range", j, a);
-                sq.src[t] = BM25_AUX_TERM | (row_of_set(a) == 0xffffffffu ? a : n_sets + n_phrases + opt->n_subqueries + row_of_set(a));
+                sq.src[t] = BM25_AUX_TERM | rq.aux_of_set(a);
                 sq.mode[t] = NIDX_CONST_SCORE, sq.weight[t] = cl.boost;
             } else if (cl.term & NIDX_BM25_PHRASE) {
                 const uint32_t a = cl.term & ~NIDX_BM25_PHRASE;
                 if (a >= n_phrases) return fail(NIDX_ERR_INVALID_ARGUMENT, "nested query %u: phrase %u out of range", j, a);
-                sq.src[t] = BM25_AUX_TERM | (n_sets + a), sq.mode[t] = NIDX_TF_FREQ, sq.weight[t] = phrase_weight(a, cl.boost);
+                sq.src[t] = BM25_AUX_TERM | (n_sets + a), sq.mode[t] = NIDX_TF_FREQ, sq.weight[t] = bm25_phrase_weight(idx, opt, a, cl.boost);
             } else if (cl.term & NIDX_BM25_SUBQUERY) {
                 const uint32_t a = cl.term & ~NIDX_BM25_SUBQUERY;
                 if (a >= j) return fail(NIDX_ERR_INVALID_ARGUMENT, "nested query %u refers to nested query %u: children come first", j, a);
@@ -1820,27 +1842,17 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             }
         }
     }
-    const uint64_t n_clauses = clause_offsets[nq];
+    const nidx_gpu_bm25_clause_t *clauses = rq.clauses;
+    const uint64_t n_clauses = rq.n_clauses = rq.clause_offsets[nq];
     if (n_clauses && !clauses) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL clauses");
     // Bm25Weight per clause from searcher-wide statistics
     std::vector<Bm25ClauseDev> &dev_clauses = cx.w_dev_clauses;
     dev_clauses.resize(n_clauses);
-    uint32_t max_clauses = 0;
     for (uint32_t q = 0; q < nq; q++) {
-        if (clause_offsets[q + 1] < clause_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "clause_offsets not monotone");
-        if (clause_offsets[q + 1] - clause_offsets[q] > BM25_MAX_CLAUSES)
+        if (rq.clause_offsets[q + 1] < rq.clause_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "clause_offsets not monotone");
+        if (rq.clause_offsets[q + 1] - rq.clause_offsets[q] > BM25_MAX_CLAUSES)
             return fail(NIDX_ERR_UNSUPPORTED, "more than %d clauses in one query", BM25_MAX_CLAUSES);
-        max_clauses = std::max<uint32_t>(max_clauses, (uint32_t)(clause_offsets[q + 1] - clause_offsets[q]));
     }
-    // launch shape knobs (no effect on results): postings rows per window and postings per work item
-    uint64_t slice_postings = BM25_SLICE_POSTINGS;
-    const bool force_wide = getenv("NIDX_GPU_BM25_WIDE") != nullptr;   // every query through the general kernel (tests)
-    // NIDX_GPU_BM25_UNION: 0 = never a union kernel, 1 = rare-meeting unions through bm25_stream_kernel (default), 2 = every query of
-    // <= 8 plain term clauses through it (tests drive its slow paths with it)
-    int union_mode = 1;
-    if (const char *e = getenv("NIDX_GPU_BM25_UNION")) union_mode = atoi(e);
-    (void)max_clauses;
-    if (const char *e = getenv("NIDX_GPU_BM25_SLICE")) slice_postings = (uint64_t)std::max(256, atoi(e));
     for (uint64_t c = 0; c < n_clauses; c++) {
         const nidx_gpu_bm25_clause_t &cl = clauses[c];
         if (cl.occur < 0 || cl.occur > NIDX_OCCUR_SHOULD_GROUP + 7 || cl.mode < 0 || cl.mode > 2) return fail(NIDX_ERR_INVALID_ARGUMENT, "bad clause");
@@ -1855,14 +1867,12 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             const uint32_t j = cl.term & ~NIDX_BM25_PHRASE;
             if (j >= n_phrases) return fail(NIDX_ERR_INVALID_ARGUMENT, "phrase %u out of range", j);
             // the phrase's matches are materialised per segment as aux list n_sets + j, with their frequencies
-            dev_clauses[c] = Bm25ClauseDev{BM25_AUX_TERM | (n_sets + j), cl.occur, NIDX_TF_FREQ, phrase_weight(j, cl.boost)};
+            dev_clauses[c] = Bm25ClauseDev{BM25_AUX_TERM | (n_sets + j), cl.occur, NIDX_TF_FREQ, bm25_phrase_weight(idx, opt, j, cl.boost)};
             continue;
         }
         if (cl.term & NIDX_BM25_TERM_SET) {
             if ((cl.term & ~NIDX_BM25_TERM_SET) >= n_sets) return fail(NIDX_ERR_INVALID_ARGUMENT, "term set %u out of range", cl.term & ~NIDX_BM25_TERM_SET);
-            const uint32_t j = cl.term & ~NIDX_BM25_TERM_SET, r = row_of_set(j);
-            dev_clauses[c] = Bm25ClauseDev{r == 0xffffffffu ? cl.term : BM25_AUX_TERM | (n_sets + n_phrases + n_sub + r), cl.occur, NIDX_CONST_SCORE,
-                                           cl.boost};  // ConstScorer(boost)
+            dev_clauses[c] = Bm25ClauseDev{BM25_AUX_TERM | rq.aux_of_set(cl.term & ~NIDX_BM25_TERM_SET), cl.occur, NIDX_CONST_SCORE, cl.boost};  // ConstScorer(boost)
             continue;
         }
         if (cl.term >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "term id %u out of range", cl.term);
@@ -1872,38 +1882,98 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         }
         dev_clauses[c] = Bm25ClauseDev{cl.term, cl.occur, cl.mode, w};
     }
-    // The pipelined aux stage: every aux list is a term set or a distinct row, one resident segment, no facets, no fast-field order, no
-    // debug run.  Nothing below may then wait for the stream or read from the device.
-    const bool pipe_aux = tr && tr->allow_aux && async_slot && idx->segs.size() == 1 && n_sets + n_rows_d > 0 && n_phrases == 0 && n_sub == 0 &&
-                          n_pairs == 0 && order_field < 0 && !getenv("NIDX_GPU_BM25_DEBUG");
-    const uint32_t kk = std::max<uint32_t>(k, 1);
-    // clauses and clause offsets travel as one pinned block
-    const size_t cl_bytes = (std::max<size_t>(n_clauses, 1) * sizeof(Bm25ClauseDev) + 7) & ~(size_t)7;
-    const size_t inq_bytes = cl_bytes + (size_t)(nq + 1) * 8;
-    // One resident segment (the common case, several opened segments included): the clause block travels at the head of the work
-    // list's transfer — every dependent operation queued on a stream costs ~10 us of hand-over between the copy engine and the compute
-    // queue, and a batch's kernels are ~70 us.  The per-segment loop (NIDX_GPU_BM25_SEGMENT_LOOP) keeps two transfers: its clause block
-    // outlives the work lists.
-    const bool fused_in = idx->segs.size() == 1;
-    const size_t inq_al = (inq_bytes + 255) & ~(size_t)255;
+    // facets: one matching-document bitset per query that asks for counts
+    rq.match_slot.assign(nq, -1);
+    rq.pair_term.resize(n_pairs);
+    rq.pair_slot.assign(n_pairs, -1);
+    for (uint32_t q = 0; q < nq && n_pairs; q++) {
+        if (opt->facet_offsets[q + 1] < opt->facet_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "facet_offsets not monotone");
+        if (opt->facet_offsets[q + 1] == opt->facet_offsets[q]) continue;
+        rq.match_slot[q] = (int)rq.n_slots++;
+        for (uint64_t p = opt->facet_offsets[q]; p < opt->facet_offsets[q + 1]; p++) {
+            if (opt->facet_terms[p] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "facet term id %u out of range", opt->facet_terms[p]);
+            rq.pair_term[p] = opt->facet_terms[p];
+            rq.pair_slot[p] = rq.match_slot[q];
+        }
+    }
+    return NIDX_OK;
+}
+
+// Stage 2: the mode of the call, decided once.  `pipelined`: the call returns after its last asynchronous call and the collect step runs
+// in the wait — one resident segment, no facets, no fast-field order, no debug run, and aux lists only where their stage is pipelined too.
+// `pipe_aux`: that stage (nidx_gpu_bm25_search_submit_prefiltered) — every aux list is a term set or a distinct row.  A pipelined call
+// reaches no stage that waits for the stream or reads from the device: bm25_search_locked gives those no call site on its path.
+struct Bm25Mode {
+    bool pipelined = false, pipe_aux = false;
+    bool debug = false;   // NIDX_GPU_BM25_DEBUG
+};
+static Bm25Mode bm25_decide_mode(const Bm25Index *idx, const Bm25Request &rq, const Bm25Slot *async_slot, const Bm25TicketRun *tr) {
+    Bm25Mode m;
+    m.debug = getenv("NIDX_GPU_BM25_DEBUG") != nullptr;
+    const bool can_pipeline = async_slot && idx->segs.size() == 1 && rq.n_slots == 0 && rq.order_field < 0 && !m.debug;
+    m.pipe_aux = can_pipeline && tr && tr->allow_aux && rq.n_aux() > 0 && rq.n_phrases == 0 && rq.n_sub == 0 && rq.n_pairs == 0;
+    m.pipelined = can_pipeline && (rq.n_aux() == 0 || m.pipe_aux);
+    return m;
+}
+
+// The launch shape knobs of this call (bm25_work_plan.h), from the environment: the tests change the variables between calls.
+static Bm25PlanKnobs bm25_plan_knobs(Bm25Index *idx, const Bm25Slot *async_slot) {
+    Bm25PlanKnobs kn;
+    // other tickets are out: this batch's launches will share the GPU with theirs (the throughput shape of the work list)
+    if (async_slot) {
+        std::lock_guard<std::mutex> lock(idx->slots_mu);
+        for (auto &sl : idx->slots)
+            if (sl.get() != async_slot && (sl->busy || sl->preparing)) kn.crowded = true;
+    }
+    if (const char *e = getenv("NIDX_GPU_BM25_CROWDED")) kn.crowded = atoi(e) != 0;   // measurement: 0 / 1 pins the shape
+    kn.force_wide = getenv("NIDX_GPU_BM25_WIDE") != nullptr;
+    if (const char *e = getenv("NIDX_GPU_BM25_UNION")) kn.union_mode = atoi(e);
+    if (const char *e = getenv("NIDX_GPU_BM25_SLICE")) kn.slice_pinned = true, kn.slice = (uint64_t)std::max(256, atoi(e));
+    return kn;
+}
+
+// The host-trace timestamps of one call (NIDX_GPU_BM25_DEBUG / NIDX_GPU_BM25_HOST_TRACE), in microseconds.
+struct Bm25HostTrace {
+    bool on = false;
+    double t_entry = 0, t_begin = 0, t_seg0 = 0, t_up0 = 0, t_up1 = 0;   // entry, request uploaded, aux stage done, staging begun / done
+    double t_work = 0, t_sync = 0, t_collect = 0;                       // sums over the segments
+    static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+};
+
+// Clauses and clause offsets travel as one pinned block.  One resident segment (the common case, several opened segments included):
+// the block travels at the head of the work list's transfer — every dependent operation queued on a stream costs ~10 us of hand-over
+// between the copy engine and the compute queue, and a batch's kernels are ~70 us.  The per-segment loop (NIDX_GPU_BM25_SEGMENT_LOOP)
+// keeps two transfers: its clause block outlives the work lists.
+struct Bm25ClauseBlock {
+    size_t cl_bytes = 0, inq_bytes = 0, inq_al = 0;
+    bool fused_in = false;
     const Bm25ClauseDev *d_clauses = nullptr;
     const unsigned long long *d_clause_offsets = nullptr;
-    if (!fused_in) {
-        NIDX_HIP(cx.s_in_q.reserve(inq_bytes));
-        NIDX_HIP(cx.h_in_q.reserve(inq_bytes));
-        if (n_clauses) memcpy(cx.h_in_q.p, dev_clauses.data(), n_clauses * sizeof(Bm25ClauseDev));
-        memcpy(cx.h_in_q.as<unsigned char>() + cl_bytes, clause_offsets, (size_t)(nq + 1) * 8);
-        NIDX_HIP(hipMemcpyAsync(cx.s_in_q.p, cx.h_in_q.p, inq_bytes, hipMemcpyHostToDevice, cx.stream));
-        d_clauses = cx.s_in_q.as<Bm25ClauseDev>();
-        d_clause_offsets = reinterpret_cast<const unsigned long long *>(cx.s_in_q.as<unsigned char>() + cl_bytes);
+};
+
+// Stage 3: what every segment reads of the request goes to the device (asynchronously): the clause block when there is not one resident
+// segment, the search-after cursors, the facet tables, the set terms; the projections' counters are zeroed.
+static int32_t bm25_upload_request(const Bm25Index *idx, Bm25Ctx &cx, const Bm25Request &rq, const Bm25Mode &mode, Bm25ClauseBlock &cb) {
+    const nidx_gpu_bm25_search_options_t *opt = rq.opt;
+    const uint32_t nq = rq.nq;
+    const uint64_t n_clauses = rq.n_clauses, n_pairs = rq.n_pairs;
+    cb.cl_bytes = (std::max<size_t>(n_clauses, 1) * sizeof(Bm25ClauseDev) + 7) & ~(size_t)7;
+    cb.inq_bytes = cb.cl_bytes + (size_t)(nq + 1) * 8;
+    cb.fused_in = idx->segs.size() == 1;
+    cb.inq_al = (cb.inq_bytes + 255) & ~(size_t)255;
+    if (!cb.fused_in) {
+        NIDX_HIP(cx.s_in_q.reserve(cb.inq_bytes));
+        NIDX_HIP(cx.h_in_q.reserve(cb.inq_bytes));
+        if (n_clauses) memcpy(cx.h_in_q.p, cx.w_dev_clauses.data(), n_clauses * sizeof(Bm25ClauseDev));
+        memcpy(cx.h_in_q.as<unsigned char>() + cb.cl_bytes, rq.clause_offsets, (size_t)(nq + 1) * 8);
+        NIDX_HIP(hipMemcpyAsync(cx.s_in_q.p, cx.h_in_q.p, cb.inq_bytes, hipMemcpyHostToDevice, cx.stream));
+        cb.d_clauses = cx.s_in_q.as<Bm25ClauseDev>();
+        cb.d_clause_offsets = reinterpret_cast<const unsigned long long *>(cx.s_in_q.as<unsigned char>() + cb.cl_bytes);
     }
-    // The merged hits are written by bm25_merge_kernel straight into the pinned result block (device-visible host memory: ~190 KB of
-    // fire-and-forget stores over PCIe per batch) instead of into HBM + a device-to-host transfer queued behind it: one dependent
-    // operation less per batch.
     static_assert(sizeof(Bm25AfterDev) == sizeof(nidx_gpu_bm25_search_after_t), "search-after layout");
-    if (after) {
+    if (rq.after) {
         NIDX_HIP(cx.s_after.reserve((size_t)nq * sizeof(Bm25AfterDev)));
-        const void *src = after;
+        const void *src = rq.after;
         if (idx->concatenated()) {
             // the cursor's DocAddress in the resident numbering (segment_ord 0, doc + base): (segment, doc) order is kept.  A cursor
             // beyond the end of its segment sits just before the next segment's first document.
@@ -1911,7 +1981,7 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             const uint32_t S = idx->n_segments;
             for (uint32_t q = 0; q < nq; q++) {
                 Bm25AfterDev c;
-                memcpy(&c, &after[q], sizeof(c));
+                memcpy(&c, &rq.after[q], sizeof(c));
                 const uint64_t seg = c.docaddr >> 32, d = c.docaddr & 0xffffffffull;
                 if (seg >= S) c.docaddr = 0xffffffffull;   // behind every document (resident doc ids are < 2^32 - 1 .. and compared strictly)
                 else if (d < idx->real[seg].n_docs) c.docaddr = (uint64_t)idx->seg_base[seg] + d;
@@ -1921,846 +1991,851 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
             }
             src = cx.w_after.data();
         }
-        if (pipe_aux) {   // pinned staging: the transfer neither blocks nor reads the caller's memory after the submit
+        if (mode.pipe_aux) {   // pinned staging: the transfer neither blocks nor reads the caller's memory after the submit
             NIDX_HIP(cx.h_after.reserve((size_t)nq * sizeof(Bm25AfterDev)));
             memcpy(cx.h_after.p, src, (size_t)nq * sizeof(Bm25AfterDev));
             src = cx.h_after.p;
         }
         NIDX_HIP(hipMemcpyAsync(cx.s_after.p, src, (size_t)nq * sizeof(Bm25AfterDev), hipMemcpyHostToDevice, cx.stream));
     }
-    // facets: one matching-document bitset per query that asks for counts
-    std::vector<int> match_slot(nq, -1);
-    std::vector<uint32_t> pair_term(n_pairs);
-    std::vector<int> pair_slot(n_pairs, -1);
-    uint32_t n_slots = 0;
-    for (uint32_t q = 0; q < nq && n_pairs; q++) {
-        if (opt->facet_offsets[q + 1] < opt->facet_offsets[q]) return fail(NIDX_ERR_INVALID_ARGUMENT, "facet_offsets not monotone");
-        if (opt->facet_offsets[q + 1] == opt->facet_offsets[q]) continue;
-        match_slot[q] = (int)n_slots++;
-        for (uint64_t p = opt->facet_offsets[q]; p < opt->facet_offsets[q + 1]; p++) {
-            if (opt->facet_terms[p] >= idx->n_terms) return fail(NIDX_ERR_INVALID_ARGUMENT, "facet term id %u out of range", opt->facet_terms[p]);
-            pair_term[p] = opt->facet_terms[p];
-            pair_slot[p] = match_slot[q];
-        }
-    }
-    if (n_slots) {
+    if (rq.n_slots) {
         NIDX_HIP(cx.s_match_slot.reserve((size_t)nq * 4));
         NIDX_HIP(cx.s_pair_term.reserve(n_pairs * 4));
         NIDX_HIP(cx.s_pair_slot.reserve(n_pairs * 4));
         NIDX_HIP(cx.s_facet_counts.reserve(n_pairs * 8));
-        NIDX_HIP(hipMemcpyAsync(cx.s_match_slot.p, match_slot.data(), (size_t)nq * 4, hipMemcpyHostToDevice, cx.stream));
-        NIDX_HIP(hipMemcpyAsync(cx.s_pair_term.p, pair_term.data(), n_pairs * 4, hipMemcpyHostToDevice, cx.stream));
-        NIDX_HIP(hipMemcpyAsync(cx.s_pair_slot.p, pair_slot.data(), n_pairs * 4, hipMemcpyHostToDevice, cx.stream));
+        NIDX_HIP(hipMemcpyAsync(cx.s_match_slot.p, rq.match_slot.data(), (size_t)nq * 4, hipMemcpyHostToDevice, cx.stream));
+        NIDX_HIP(hipMemcpyAsync(cx.s_pair_term.p, rq.pair_term.data(), n_pairs * 4, hipMemcpyHostToDevice, cx.stream));
+        NIDX_HIP(hipMemcpyAsync(cx.s_pair_slot.p, rq.pair_slot.data(), n_pairs * 4, hipMemcpyHostToDevice, cx.stream));
         NIDX_HIP(hipMemsetAsync(cx.s_facet_counts.p, 0, n_pairs * 8, cx.stream));
     }
-    if (n_sets && !pipe_aux) {   // (the pipelined aux stage scatters from a work table of posting ranges: the terms stay on the host)
-        const uint64_t n_set_terms = opt->term_set_offsets[n_sets];
+    if (rq.n_sets && !mode.pipe_aux) {   // (the pipelined aux stage scatters from a work table of posting ranges: the terms stay on the host)
+        const uint64_t n_set_terms = opt->term_set_offsets[rq.n_sets];
         NIDX_HIP(cx.s_set_terms.reserve(std::max<uint64_t>(n_set_terms, 1) * 4));
         if (n_set_terms) NIDX_HIP(hipMemcpyAsync(cx.s_set_terms.p, opt->term_set_terms, n_set_terms * 4, hipMemcpyHostToDevice, cx.stream));
     }
-    cx.kernel_ms = 0.f;
-    const bool host_dbg = getenv("NIDX_GPU_BM25_DEBUG") != nullptr || getenv("NIDX_GPU_BM25_HOST_TRACE") != nullptr;
-    auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now_us();
-    double t_work = 0, t_sync = 0, t_collect = 0;
-    struct Hit { float score; uint64_t docaddr; int64_t value; };
-    std::vector<std::vector<Hit>> merged(idx->segs.size() == 1 ? 0 : nq);
-    std::vector<Bm25Work> &work = cx.w_work;
-    unsigned long long row_stats[2] = {0, 0};   // documents visited, postings written by the projections of this call
-    if (n_rows_d) {
+    if (rq.n_rows_d) {
         NIDX_HIP(cx.s_row_stats.reserve(16));
         NIDX_HIP(hipMemsetAsync(cx.s_row_stats.p, 0, 16, cx.stream));
     }
-    for (size_t s = 0; s < idx->segs.size(); s++) {
-        Bm25Segment &seg = idx->segs[s];
-        // ---- the aux lists of this segment, in dependency order: term sets (union bitset -> ascending doc list,
-        // AutomatonWeight::scorer), phrases, nested queries (children before parents); one host round trip for all their counts ----
-        const uint32_t n_own = n_sets + n_phrases + n_sub, n_aux = n_own + n_rows_d;   // (the distinct rows of the row sets come last)
-        std::vector<unsigned long long> aux_pairs(2 * (size_t)n_aux + 2, 0);  // [begin, end) per aux list into s_aux_ids
-        std::vector<uint32_t> set_counts(n_aux, 0);
-        // layout of the aux arrays: one region per list, sized by an upper bound of its length
-        std::vector<unsigned long long> out_off(n_aux + 1, 0);
-        // a projected row holds at most the postings the link reaches in this segment, and at most every document
-        const uint64_t row_bound = !n_rows_d ? 0 : rs->distinct.back() == kPrefilterRowAll ? (uint64_t)seg.n_docs
-                                                 : std::min<uint64_t>(seg.n_docs, rs->link->segment_postings[s] + (rs->any_res ? rs->link->res_segment_postings[s] : 0));
-        std::vector<PhraseDev> phrases(n_phrases);
-        for (uint32_t j = 0; j < n_sets; j++) {
-            uint64_t df = 0;
-            for (uint64_t i = opt->term_set_offsets[j]; i < opt->term_set_offsets[j + 1]; i++)
-                df += seg.term_offsets_host[opt->term_set_terms[i] + 1] - seg.term_offsets_host[opt->term_set_terms[i]];
-            const bool comp = opt->term_set_complement && opt->term_set_complement[j];
-            out_off[j + 1] = out_off[j] + (comp ? (uint64_t)seg.n_docs : std::min<uint64_t>(df, seg.n_docs));
-        }
-        for (uint32_t j = 0; j < n_phrases; j++) {
-            PhraseDev &ph = phrases[j];
-            ph.n_terms = (uint32_t)(opt->phrase_offsets[j + 1] - opt->phrase_offsets[j]);
-            ph.slop = opt->phrase_slops ? opt->phrase_slops[j] : 0u;
-            ph.driver = 0;
-            uint64_t best = ~0ull;
-            for (uint32_t t = 0; t < ph.n_terms; t++) {
-                ph.terms[t] = opt->phrase_terms[opt->phrase_offsets[j] + t];
-                const uint64_t df = seg.term_offsets_host[ph.terms[t] + 1] - seg.term_offsets_host[ph.terms[t]];
-                if (df < best) { best = df; ph.driver = t; }
-            }
-            out_off[n_sets + j + 1] = out_off[n_sets + j] + best;
-        }
-        // nested queries: the candidates are the shortest Must leaf (by upper bound: an aux leaf's exact length is on the device only),
-        // else the union of the smallest required Should group, else the union of the Should leaves
-        struct SubPlan { uint32_t union_mask = 0; uint64_t n_cand_max = 0; };
-        std::vector<SubPlan> plans(n_sub);
-        uint64_t max_cand = 0;
-        bool any_union = false;
-        for (uint32_t j = 0; j < n_sub; j++) {
-            SubqueryDev &sq = subs[j];
-            auto upper = [&](uint32_t t) -> uint64_t {
-                if (sq.src[t] & BM25_AUX_TERM) {
-                    const uint32_t a = sq.src[t] & ~BM25_AUX_TERM;
-                    return a >= n_own ? row_bound : out_off[a + 1] - out_off[a];   // (the rows' regions are laid out behind this loop)
-                }
-                return seg.term_offsets_host[sq.src[t] + 1] - seg.term_offsets_host[sq.src[t]];
-            };
-            uint64_t best = ~0ull, group_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, should_sum = 0;
-            uint32_t group_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0}, should_mask = 0;
-            bool any_must = false;
-            for (uint32_t t = 0; t < sq.n; t++) {
-                const uint64_t ub = upper(t);
-                if (sq.occur[t] == NIDX_OCCUR_MUST) {
-                    any_must = true;
-                    if (ub < best) { best = ub; sq.driver = t; }
-                } else if (sq.occur[t] >= NIDX_OCCUR_SHOULD_GROUP) {
-                    group_sum[sq.occur[t] - NIDX_OCCUR_SHOULD_GROUP] += ub, group_mask[sq.occur[t] - NIDX_OCCUR_SHOULD_GROUP] |= 1u << t;
-                } else if (sq.occur[t] == NIDX_OCCUR_SHOULD) should_sum += ub, should_mask |= 1u << t;
-            }
-            SubPlan &pl = plans[j];
-            if (any_must) pl.n_cand_max = best;
-            else {
-                sq.driver = BM25_SUB_DRIVER_UNION;
-                uint64_t sum = ~0ull;
-                for (int g = 0; g < 8; g++)
-                    if (group_mask[g] && group_sum[g] < sum) sum = group_sum[g], pl.union_mask = group_mask[g];
-                if (!pl.union_mask) sum = should_sum, pl.union_mask = should_mask;   // no positive leaf at all: nothing matches
-                pl.n_cand_max = pl.union_mask ? std::min<uint64_t>(sum, seg.n_docs) : 0;
-                any_union |= pl.union_mask != 0;
-            }
-            if (pl.n_cand_max > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a posting list of one segment holds more than 2^32 - 1 postings");
-            max_cand = std::max(max_cand, pl.n_cand_max);
-            out_off[n_sets + n_phrases + j + 1] = out_off[n_sets + n_phrases + j] + pl.n_cand_max;
-        }
-        for (uint32_t r = 0; r < n_rows_d; r++) out_off[n_own + r + 1] = out_off[n_own + r] + row_bound;
-        const uint32_t words = (seg.n_docs + 63) / 64;
-        if (n_aux) {
-            NIDX_HIP(cx.s_aux_ids.reserve(std::max<uint64_t>(out_off[n_aux], 1) * 4 + BM25_LIST_PAD_BYTES));
-            // (the rows' lists come last and are ConstScorer lists, whose frequencies no kernel reads: no parallel region for them)
-            NIDX_HIP(cx.s_aux_tfs.reserve(std::max<uint64_t>(out_off[n_own], 1) * 4 + BM25_LIST_PAD_BYTES));
-            NIDX_HIP(cx.s_set_counts.reserve((size_t)n_aux * 4 + 4));   // + the count of the union candidates
-            NIDX_HIP(hipMemsetAsync(cx.s_set_counts.p, 0, (size_t)n_aux * 4 + 4, cx.stream));
-            if (!pipe_aux) {   // (the pipelined aux stage sends the offsets with its other tables)
-                NIDX_HIP(cx.s_aux_out_off.reserve((size_t)(n_aux + 1) * 8));
-                NIDX_HIP(hipMemcpyAsync(cx.s_aux_out_off.p, out_off.data(), (size_t)(n_aux + 1) * 8, hipMemcpyHostToDevice, cx.stream));
-            }
-        }
-        // the sources of the rows to project: [n_proj field rows | n_proj resource rows], nullptr: the row set has no such part
-        auto row_sources = [&](uint32_t n_proj) {
-            cx.w_row_ptrs.assign((size_t)n_proj * (rs->any_res ? 2 : 1), nullptr);
-            bool any_field = false;
-            for (uint32_t r = 0; r < n_proj; r++) {
-                if (rs->distinct[r] != kPrefilterRowNone) cx.w_row_ptrs[r] = rs->rows->row_ptr[rs->distinct[r]], any_field = true;
-                if (rs->any_res && rs->distinct_res[r] != kPrefilterRowNone) cx.w_row_ptrs[n_proj + r] = rs->rows->res_row_ptr[rs->distinct_res[r]];
-            }
-            return any_field;
-        };
-        // every distinct row onto this segment in one launch (one more for the resource parts), every row's list in one compaction
-        auto project_rows = [&](const uint64_t *const *d_row_ptrs, uint32_t n_proj, bool any_field, const unsigned long long *d_out_off,
-                                uint32_t *d_counts) -> int32_t {
-            if (n_proj && any_field) {
-                NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs, n_proj, (uint32_t)rs->rows->layout.words(), rs->link->doc_term.as<uint32_t>(),
-                                                       seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
-                                                       cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
-                rs->stats.projection_launches++;
-            }
-            if (n_proj && rs->any_res) {   // the uuid lists of the set resources, into the same bitsets: one more launch
-                NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs + n_proj, n_proj, (uint32_t)rs->rows->res_words, rs->link->res_term.as<uint32_t>(),
-                                                       seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
-                                                       cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
-                rs->stats.projection_launches++;
-            }
-            NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, d_out_off, cx.s_aux_ids.as<uint32_t>(), d_counts, cx.stream));
-            rs->stats.compaction_launches++;
-            return NIDX_OK;
-        };
-        // ---- the pipelined aux stage: a fixed number of launches, one transfer in, nothing out ----
-        uint32_t n_pipe_slots = 0;
-        size_t pa_count_of = 0;   // the count index per list, in cx.s_in_a
-        if (pipe_aux) {
-            std::vector<uint32_t> slot_of_set, comp_of_slot;
-            n_pipe_slots = bm25_assign_slots(opt->term_set_offsets, opt->term_set_complement, n_sets, slot_of_set, comp_of_slot);
-            bool any_comp = false;
-            for (uint32_t f : comp_of_slot) any_comp |= f != 0;
-            std::vector<Bm25ScatterItem> &items = cx.w_scatter;
-            bm25_scatter_table(opt->term_set_offsets, opt->term_set_terms, n_sets, slot_of_set.data(), seg.term_offsets_host.data(), kBm25ScatterChunk, items);
-            uint32_t n_proj = n_rows_d;
-            const bool all_row = n_rows_d && rs->distinct.back() == kPrefilterRowAll;   // (the entry lists it last)
-            if (all_row) n_proj--;
-            const bool any_field = n_proj ? row_sources(n_proj) : false;
-            const size_t n_ptrs = n_proj ? cx.w_row_ptrs.size() : 0;
-            // the tables' block; the lists' counts live in s_set_counts as [slots | distinct rows]
-            const size_t pa_off = 0, pa_slot_off = pa_off + (size_t)(n_aux + 1) * 8, pa_ptrs = pa_slot_off + (size_t)n_pipe_slots * 8,
-                         pa_items = pa_ptrs + n_ptrs * 8, pa_flags = pa_items + items.size() * sizeof(Bm25ScatterItem) + (size_t)n_aux * 4,
-                         pa_bytes = pa_flags + (size_t)n_pipe_slots * 4;
-            pa_count_of = pa_items + items.size() * sizeof(Bm25ScatterItem);
-            NIDX_HIP(cx.h_in_a.reserve(pa_bytes));
-            NIDX_HIP(cx.s_in_a.reserve(pa_bytes));
-            unsigned char *h_a = cx.h_in_a.as<unsigned char>(), *d_a = cx.s_in_a.as<unsigned char>();
-            memcpy(h_a + pa_off, out_off.data(), (size_t)(n_aux + 1) * 8);
-            unsigned long long *h_slot_off = reinterpret_cast<unsigned long long *>(h_a + pa_slot_off);
-            uint32_t *h_count_of = reinterpret_cast<uint32_t *>(h_a + pa_count_of);
-            for (uint32_t j = 0; j < n_sets; j++) {
-                h_count_of[j] = slot_of_set[j];   // (kBm25NoSlot: the empty list)
-                if (slot_of_set[j] != kBm25NoSlot) h_slot_off[slot_of_set[j]] = out_off[j];
-            }
-            for (uint32_t r = 0; r < n_rows_d; r++) h_count_of[n_own + r] = n_pipe_slots + r;
-            if (n_ptrs) memcpy(h_a + pa_ptrs, cx.w_row_ptrs.data(), n_ptrs * 8);
-            if (!items.empty()) memcpy(h_a + pa_items, items.data(), items.size() * sizeof(Bm25ScatterItem));
-            if (n_pipe_slots) memcpy(h_a + pa_flags, comp_of_slot.data(), (size_t)n_pipe_slots * 4);
-            NIDX_HIP(hipMemcpyAsync(cx.s_in_a.p, cx.h_in_a.p, pa_bytes, hipMemcpyHostToDevice, cx.stream));
-            if (n_pipe_slots && words) {
-                NIDX_HIP(cx.s_set_bits.reserve((size_t)n_pipe_slots * words * 8));
-                NIDX_HIP(hipMemsetAsync(cx.s_set_bits.p, 0, (size_t)n_pipe_slots * words * 8, cx.stream));
-                if (!items.empty()) {
-                    NIDX_HIP(launch_bm25_set_scatter(reinterpret_cast<const Bm25ScatterItem *>(d_a + pa_items), (uint32_t)items.size(), seg.doc_ids.as<uint32_t>(),
-                                                     seg.n_docs, words, cx.s_set_bits.as<uint64_t>(), cx.stream));
-                    tr->aux_launches++;
-                }
-                if (any_comp) {
-                    NIDX_HIP(launch_bm25_set_complement(cx.s_set_bits.as<uint64_t>(), reinterpret_cast<const uint32_t *>(d_a + pa_flags), n_pipe_slots, words,
-                                                        seg.n_docs, cx.stream));
-                    tr->aux_launches++;
-                }
-                NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>(), words, n_pipe_slots, reinterpret_cast<const unsigned long long *>(d_a + pa_slot_off),
-                                               cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>(), cx.stream));
-                tr->aux_launches++;
-            }
-            if (n_rows_d && words) {
-                NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
-                NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
-                if (all_row) {
-                    NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
-                    tr->aux_launches++;
-                }
-                const uint32_t before = rs->stats.projection_launches + rs->stats.compaction_launches;
-                if (int32_t rc = project_rows(reinterpret_cast<const uint64_t *const *>(d_a + pa_ptrs), n_proj, any_field,
-                                              reinterpret_cast<const unsigned long long *>(d_a + pa_off) + n_own, cx.s_set_counts.as<uint32_t>() + n_pipe_slots))
-                    return rc;
-                tr->aux_launches += rs->stats.projection_launches + rs->stats.compaction_launches - before;
-            }
-            // the estimates the work list is planned from (set_counts stays a host-side guess: the exact counts are on the device)
-            for (uint32_t j = 0; j < n_sets; j++) set_counts[j] = (uint32_t)(out_off[j + 1] - out_off[j]);   // min(sum df, n_docs), n_docs of a complement
-            for (uint32_t r = 0; r < n_rows_d; r++) {
-                uint64_t est = bm25_estimate_all(seg.n_docs);
-                if (!(all_row && r == n_rows_d - 1)) {
-                    const PrefilterRows &R = *rs->rows;
-                    const uint32_t fr = rs->distinct[r], rr = rs->any_res ? rs->distinct_res[r] : kPrefilterRowNone;
-                    const uint64_t f_docs = fr == kPrefilterRowNone ? 0 : fr < R.row_docs.size() ? R.row_docs[fr] : ~0ull;
-                    const uint64_t r_docs = rr == kPrefilterRowNone ? 0 : rr < R.res_row_docs.size() ? R.res_row_docs[rr] : ~0ull;
-                    est = bm25_estimate_row(row_bound, bm25_estimate_row_part(f_docs, rs->link->segment_postings[s], rs->link->linked_documents),
-                                            bm25_estimate_row_part(r_docs, rs->any_res ? rs->link->res_segment_postings[s] : 0, rs->link->linked_resources));
-                }
-                set_counts[n_own + r] = (uint32_t)est;
-            }
-        }
-        // A set owns a bitset when it has terms or the complement flag.  A set with neither — every row set is one — is the empty
-        // list its zeroed count already says: no bitset, no place in a compaction.  Scratch follows the sets that scatter, not the queries.
-        auto owns_bits = [&](uint32_t j) {
-            return opt->term_set_offsets[j + 1] != opt->term_set_offsets[j] || (opt->term_set_complement && opt->term_set_complement[j]);
-        };
-        uint32_t n_bitsets = 0;
-        for (uint32_t j = 0; j < n_sets; j++) n_bitsets += owns_bits(j) ? 1u : 0u;
-        if (n_bitsets && words && !pipe_aux) {
-            NIDX_HIP(cx.s_set_bits.reserve(std::max<size_t>((size_t)n_bitsets * words, 1) * 8));
-            NIDX_HIP(launch_bitset_fill(cx.s_set_bits.as<uint64_t>(), n_bitsets * words, 0, 0, cx.stream));   // (n_bits matters when filling with ones only)
-            uint32_t slot = 0;
-            for (uint32_t j = 0; j < n_sets; j++) {
-                if (!owns_bits(j)) continue;
-                const uint32_t nl = (uint32_t)(opt->term_set_offsets[j + 1] - opt->term_set_offsets[j]);
-                if (nl)
-                    NIDX_HIP(launch_bitset_scatter(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(),
-                                                   cx.s_set_terms.as<uint32_t>() + opt->term_set_offsets[j], nl, seg.n_docs,
-                                                   cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, cx.stream));
-                if (opt->term_set_complement && opt->term_set_complement[j])
-                    NIDX_HIP(launch_bitset_not(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, seg.n_docs, cx.stream));
-                slot++;
-            }
-            // one compaction per run of consecutive sets that own a bitset (all sets do, and it is one, unless empty sets lie between)
-            slot = 0;
-            for (uint32_t j = 0; j < n_sets;) {
-                if (!owns_bits(j)) { j++; continue; }
-                uint32_t j1 = j;
-                while (j1 < n_sets && owns_bits(j1)) j1++;
-                NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, j1 - j,
-                                               cx.s_aux_out_off.as<unsigned long long>() + j, cx.s_aux_ids.as<uint32_t>(),
-                                               cx.s_set_counts.as<uint32_t>() + j, cx.stream));
-                slot += j1 - j;
-                j = j1;
-            }
-        }
-        if (n_rows_d && words && !pipe_aux) {
-            // every distinct row onto this segment in one launch, every row's list in one compaction; the All requests share a row of ones
-            NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
-            NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
-            uint32_t n_proj = n_rows_d;
-            if (rs->distinct.back() == kPrefilterRowAll) {   // (the entry lists it last)
-                n_proj--;
-                NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
-            }
-            bool any_field = false;
-            if (n_proj) {
-                any_field = row_sources(n_proj);
-                NIDX_HIP(cx.s_row_ptrs.reserve(cx.w_row_ptrs.size() * sizeof(uint64_t *)));
-                NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), cx.w_row_ptrs.size() * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
-            }
-            if (int32_t rc = project_rows(cx.s_row_ptrs.as<const uint64_t *>(), n_proj, any_field, cx.s_aux_out_off.as<unsigned long long>() + n_own,
-                                          cx.s_set_counts.as<uint32_t>() + n_own))
-                return rc;
-        }
-        for (uint32_t j = 0; j < n_phrases; j++) {
-            const uint64_t n_driver = out_off[n_sets + j + 1] - out_off[n_sets + j];
-            if (n_driver == 0) continue;
-            NIDX_HIP(cx.s_phrase_tf.reserve(n_driver * 4));
-            uint32_t *slop_left = nullptr;
-            if (phrases[j].slop) {
-                // PhraseScorer's `left` list per document: as many entries as the first term has positions in this segment
-                const uint64_t tb = seg.term_offsets_host[phrases[j].terms[0]], te = seg.term_offsets_host[phrases[j].terms[0] + 1];
-                unsigned long long pr[2] = {0, 0};
-                NIDX_HIP(hipMemcpyAsync(&pr[0], seg.pos_offsets.as<unsigned long long>() + tb, 8, hipMemcpyDeviceToHost, cx.stream));
-                NIDX_HIP(hipMemcpyAsync(&pr[1], seg.pos_offsets.as<unsigned long long>() + te, 8, hipMemcpyDeviceToHost, cx.stream));
-                NIDX_HIP(hipStreamSynchronize(cx.stream));
-                NIDX_HIP(cx.s_slop_left.reserve(std::max<uint64_t>(pr[1] - pr[0], 1) * 8));   // (position, budget used) pairs
-                slop_left = cx.s_slop_left.as<uint32_t>();
-            }
-            NIDX_HIP(launch_phrase_match(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.pos_offsets.as<unsigned long long>(),
-                                         seg.positions.as<uint32_t>(), phrases[j], (uint32_t)n_driver, cx.s_phrase_tf.as<uint32_t>(), slop_left, cx.stream));
-            NIDX_HIP(launch_phrase_compact(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), phrases[j], cx.s_phrase_tf.as<uint32_t>(), seg.fieldnorm_ids.as<uint8_t>(),
-                                           out_off[n_sets + j], cx.s_aux_ids.as<uint32_t>(), cx.s_aux_tfs.as<uint32_t>(),
-                                           cx.s_set_counts.as<uint32_t>() + n_sets + j, cx.stream));
-        }
-        if (n_sub) {
-            NIDX_HIP(cx.s_phrase_tf.reserve(std::max<uint64_t>(max_cand, 1) * 8));   // [n] match flags | [n] score bits
-            if (any_union) {
-                NIDX_HIP(cx.s_sub_bits.reserve(std::max<size_t>(words, 1) * 8));
-                NIDX_HIP(cx.s_sub_union.reserve(std::max<uint64_t>(max_cand, 1) * 4));
-            }
-            SubqueryLists L{seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.tfs.as<uint32_t>(), cx.s_aux_ids.as<uint32_t>(),
-                            cx.s_aux_tfs.as<uint32_t>(), cx.s_aux_out_off.as<unsigned long long>(), cx.s_set_counts.as<uint32_t>(),
-                            cx.s_sub_union.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_aux};
-            for (uint32_t j = 0; j < n_sub; j++) {
-                const SubPlan &pl = plans[j];
-                if (pl.n_cand_max == 0) continue;
-                if (subs[j].driver == BM25_SUB_DRIVER_UNION) {
-                    NIDX_HIP(launch_bitset_fill(cx.s_sub_bits.as<uint64_t>(), words, seg.n_docs, 0, cx.stream));
-                    for (uint32_t t = 0; t < subs[j].n; t++)
-                        if (pl.union_mask >> t & 1) NIDX_HIP(launch_subquery_scatter(L, subs[j].src[t], pl.n_cand_max, cx.s_sub_bits.as<uint64_t>(), cx.stream));
-                    // out_off[0] == 0: the union list starts at the head of its own buffer
-                    NIDX_HIP(launch_bitset_compact(cx.s_sub_bits.as<uint64_t>(), words, 1, cx.s_aux_out_off.as<unsigned long long>(),
-                                                   cx.s_sub_union.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_aux, cx.stream));
-                }
-                uint32_t *tmp_ok = cx.s_phrase_tf.as<uint32_t>(), *tmp_score = tmp_ok + max_cand;
-                NIDX_HIP(launch_subquery_match(L, idx->tf_cache.as<float>(), subs[j], (uint32_t)pl.n_cand_max, tmp_ok, tmp_score, cx.stream));
-                NIDX_HIP(launch_subquery_compact(L, subs[j], tmp_ok, tmp_score, out_off[n_sets + n_phrases + j], cx.s_aux_ids.as<uint32_t>(),
-                                                 cx.s_aux_tfs.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_sets + n_phrases + j, cx.stream));
-            }
-        }
-        if (n_aux && pipe_aux) NIDX_HIP(cx.s_aux_off.reserve((2 * (size_t)n_aux + 2) * 8));   // (written by bm25_aux_ranges_kernel, below)
-        if (n_aux && !pipe_aux) {
-            NIDX_HIP(hipMemcpyAsync(set_counts.data(), cx.s_set_counts.p, (size_t)n_aux * 4, hipMemcpyDeviceToHost, cx.stream));
-            if (n_rows_d) NIDX_HIP(hipMemcpyAsync(row_stats, cx.s_row_stats.p, 16, hipMemcpyDeviceToHost, cx.stream));   // (running sums over the segments)
-            NIDX_HIP(hipStreamSynchronize(cx.stream));
-            if (tr) tr->syncs++;
-            for (uint32_t r = 0; r < n_rows_d; r++) rs->stats.list_entries += set_counts[n_own + r];
-            if (n_rows_d) rs->stats.documents_visited = row_stats[0], rs->stats.postings_written = row_stats[1];
-            for (uint32_t j = 0; j < n_aux; j++) {
-                aux_pairs[2 * j] = out_off[j];
-                aux_pairs[2 * j + 1] = out_off[j] + set_counts[j];
-            }
-            NIDX_HIP(cx.s_aux_off.reserve(aux_pairs.size() * 8));
-            NIDX_HIP(hipMemcpyAsync(cx.s_aux_off.p, aux_pairs.data(), aux_pairs.size() * 8, hipMemcpyHostToDevice, cx.stream));
-        }
-        const double t_seg0 = now_us();
-        auto postings_of = [&](const nidx_gpu_bm25_clause_t &cl) -> uint64_t {
-            if (cl.term & NIDX_BM25_TERM_SET) {
-                const uint32_t j = cl.term & ~NIDX_BM25_TERM_SET, r = row_of_set(j);
-                return set_counts[r == 0xffffffffu ? j : n_own + r];
-            }
-            if (cl.term & NIDX_BM25_PHRASE) return set_counts[n_sets + (cl.term & ~NIDX_BM25_PHRASE)];
-            if (cl.term & NIDX_BM25_SUBQUERY) return set_counts[n_sets + n_phrases + (cl.term & ~NIDX_BM25_SUBQUERY)];
-            return seg.term_offsets_host[cl.term + 1] - seg.term_offsets_host[cl.term];
-        };
-        // work list: every query cut into doc-id slices of ~BM25_SLICE_POSTINGS postings.  Three launches over disjoint item lists: term
-        // unions whose lists rarely meet (bm25_stream.hip), the other narrow queries (bm25_fast_kernel), the rest (bm25_rows_kernel).  A
-        // query is a "rare-meeting union" when it has at most 8 plain term clauses and the number of documents two of its lists are
-        // expected to share (independent lists: len_a * len_b / n_docs, summed over the pairs) is at most 1/8 of its postings — the union
-        // kernels are exact for any input, that bound only keeps their slow paths rare.
-        const double t_w0 = now_us();
-        // every clause's list length in this segment, looked up once (two random reads of an 8 MB table per plain term)
-        std::vector<uint64_t> &clen = cx.w_clause_len;
-        clen.resize(n_clauses);
-        for (uint64_t c = 0; c < n_clauses; c++) {
-            if (c + 16 < n_clauses && !(clauses[c + 16].term & (NIDX_BM25_TERM_SET | NIDX_BM25_PHRASE | NIDX_BM25_SUBQUERY)))
-                __builtin_prefetch(&seg.term_offsets_host[clauses[c + 16].term]);
-            clen[c] = postings_of(clauses[c]);
-        }
-        work.clear();
-        std::vector<uint32_t> &item_first = cx.w_item_first;
-        std::vector<uint8_t> &q_union = cx.w_q_union;
-        item_first.assign(nq + 1, 0);
-        q_union.assign(nq, 0);
-        const double inv_docs = 1.0 / std::max<double>(1.0, (double)seg.n_docs);
-        // Postings per work item.  A launch lasts as long as its slowest item while every workgroup of it is resident at once (5 per CU,
-        // 4 items each); past that the tail of the grid runs as a second round.  So: the smallest slice between 1 024 and the default
-        // that still fits the batch into one round (the bench batch: ~1 900 instead of 2 048, its slowest items 7 % shorter); batches
-        // too large for one round keep the default.  NIDX_GPU_BM25_SLICE pins it.
-        uint64_t slice_now = slice_postings;
-        uint64_t short_weight = 1;   // what a posting outside the query's longest clause counts when the slices are cut (the longest clause's count 1)
-        auto weigh = [&](uint64_t sum, uint64_t longest) { return longest + short_weight * (sum - longest); };
-        // Other batches are resident (the pipelined entries know): the launch does not have to fill the GPU alone, and what counts is
-        // the work per posting.  With k = 20 a wave that filters n postings offers ~k ln(n / k) candidates to its list and merges them
-        // 64 at a time — candidates and merges are half of the kernel's vector instructions at ~1 900 postings per item and fall per
-        // posting as the item grows (measured, scripts/r6_bm25_probe.py: long lists 214 -> 248 G postings/s at 4 096).  So a union query is cut
-        // into the FEWEST slices of up to BM25_SLICE_CROWDED postings whose expected number of involved postings — true meetings and the
-        // collisions of the kernel's two bitmaps (bm25_stream.hip: 32 Kibit A, 2 Kibit B) — stays inside the 192-entry list:
-        // a balanced query keeps ~1 900 postings per slice (the bitmaps allow no more), a long list with two short ones gets ~8 000.
-        // A batch alone on the GPU (the blocking entries, the first ticket) keeps the latency shape below.
-        const bool crowded_shape = crowded && !getenv("NIDX_GPU_BM25_SLICE");
-        if (crowded_shape) {
-            slice_now = BM25_SLICE_CROWDED;
-        } else if (!getenv("NIDX_GPU_BM25_SLICE")) {
-            const uint64_t budget = (uint64_t)idx->n_cus * 5u * 4u * 15u / 16u;
-            // A launch alone lasts as long as its slowest item, so the items are cut to equal COST, not equal length: a posting of the
-            // longest clause is streamed once (phase 2), one of any other clause twice (marked in phase 1, scored in phase 3).  Measured on
-            // the bench batch (DESIGN-LOG R6.8): with one-bit bitmaps, when a third of the kernel went into falsely involved
-            // postings, weight 3 took a launch from 49.5 to 44.5 us; with the three-bit filter of bitmap A weights 1 .. 3 are within
-            // 2 us of each other (43.3 - 45.7) and 2 is kept.
-            std::vector<uint64_t> &pq = cx.w_postings;
-            pq.assign(nq, 0);
-            short_weight = 2;
-            for (uint32_t q = 0; q < nq; q++) {
-                uint64_t sum = 0, longest = 0;
-                for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1]; c++) sum += clen[c], longest = std::max<uint64_t>(longest, clen[c]);
-                pq[q] = weigh(sum, longest);
-            }
-            // (the item count falls as the slice grows: bisection over the candidates, and a multiplication by the reciprocal instead of
-            // a 64-bit division per query and candidate — the count only steers this choice, the slicing below divides exactly)
-            auto fits = [&](uint64_t cand) {
-                const double inv = 1.0 / (double)cand;
-                uint64_t items = 0;
-                for (uint32_t q = 0; q < nq; q++) items += (uint64_t)((double)pq[q] * inv) + 1u;
-                return items <= budget;
-            };
-            uint64_t lo = 1024, hi = slice_postings * (short_weight > 1 ? 2u : 1u);   // candidates lo, lo + 128, ..; hi: the default length (in weighted postings)
-            while (lo < hi) {
-                const uint64_t mid = lo + ((hi - lo) / 256) * 128;
-                if (fits(mid)) hi = mid;
-                else lo = mid + 128;
-            }
-            slice_now = hi;
-        }
-        for (uint32_t q = 0; q < nq; q++) {
-            item_first[q] = (uint32_t)work.size();
-            const uint64_t c0 = clause_offsets[q], c1 = clause_offsets[q + 1];
-            uint64_t p = 0, p_longest = 0;
-            bool plain = true;
-            double sum_sq = 0.0;
-            for (uint64_t c = c0; c < c1; c++) {
-                const uint64_t l = clen[c];
-                p += l;
-                p_longest = std::max(p_longest, l);
-                sum_sq += (double)l * (double)l;
-                if (clauses[c].term & (NIDX_BM25_TERM_SET | NIDX_BM25_PHRASE | NIDX_BM25_SUBQUERY)) plain = false;
-            }
-            uint32_t slices = (uint32_t)std::min<uint64_t>(BM25_MAX_SLICES, std::max<uint64_t>(1, (weigh(p, p_longest) + slice_now - 1) / slice_now));
-            if (union_mode != 0 && plain && c1 > c0 && c1 - c0 <= BM25_FAST_CLAUSES && !force_wide) {
-                const double sum = (double)p, shared = (sum * sum - sum_sq) * 0.5 * inv_docs;
-                // the same term twice: those two lists meet in every document (the estimate above assumes independent lists)
-                double repeated = 0.0;
-                for (uint64_t c = c0; c < c1; c++)
-                    for (uint64_t e = c + 1; e < c1; e++)
-                        if (clauses[c].term == clauses[e].term) repeated += (double)clen[c];
-                // the stream kernel resolves up to 192 involved postings per item without cutting its doc range: enough slices to keep
-                // the expected number (two postings per meeting) around 96
-                double want = std::ceil((shared + repeated) * 2.0 / 96.0);
-                if (crowded_shape) {
-                    // involved postings of one of n slices: b = postings that find their three bits of A set (bm25_stream.hip: a document
-                    // owns one of 1 024 words and three of its bits; with lambda = marked documents per word a stranger passes with probability
-                    // ~ (27 / 32 768) (lambda^3 + 3 lambda^2 + lambda): the third moment of a Poisson count of three-bit marks) — the longest
-                    // clause's postings against the full filter, the shorter clauses' against the filter as it fills (a quarter of that) —
-                    // plus two per true meeting; each sets a bit of B, and every short posting then meets B with probability b / 2 048
-                    double l_max = 0.0;
-                    for (uint64_t c = c0; c < c1; c++) l_max = std::max(l_max, (double)clen[c]);
-                    const double s_all = sum - l_max, meet2 = (shared + repeated) * 2.0;
-                    double n = std::max(1.0, (double)slices);
-                    for (int it = 0; it < 24; it++) {
-                        const double ss = s_all / n, ll = l_max / n, lam = ss / 1024.0;
-                        const double p_a = std::min(1.0, (27.0 / 32768.0) * (lam * lam * lam + 3.0 * lam * lam + lam));
-                        const double b = ll * p_a + ss * p_a * 0.25 + meet2 / n;
-                        if (b * (1.0 + ss / 2048.0) <= 96.0) break;
-                        n = std::ceil(n * 1.25);
-                    }
-                    // (never fewer postings per slice than the latency shape would give: the estimate above is the only reason to cut finer)
-                    want = std::max(want, std::min(n, std::ceil(sum / 1024.0)));
-                }
-                if (union_mode == 2) q_union[q] = 1;
-                else if (shared * 8.0 <= sum && want <= (double)BM25_MAX_SLICES) q_union[q] = 1;
-                if (q_union[q]) slices = (uint32_t)std::min<double>(BM25_MAX_SLICES, std::max<double>(slices, want));
+    return NIDX_OK;
+}
 
-            }
-            const Bm25Work w{q, 0, slices, (uint32_t)c0, (uint32_t)(c1 - c0)};
-            work.resize(work.size() + slices, w);
-            Bm25Work *wp = work.data() + work.size() - slices;
-            for (uint32_t sl = 1; sl < slices; sl++) wp[sl].slice = sl;
+// ---- per resident segment: the aux lists, in dependency order: term sets (union bitset -> ascending doc list, AutomatonWeight::scorer),
+// phrases, nested queries (children before parents), the distinct rows of the row sets ----
+// Layout of the aux arrays: one region per list, sized by an upper bound of its length.
+struct Bm25AuxLayout {
+    uint32_t n_own = 0, n_aux = 0;   // (the distinct rows of the row sets come last)
+    uint32_t words = 0;              // of a document bitset of this segment
+    uint64_t row_bound = 0;          // a projected row holds at most the postings the link reaches in this segment, and at most every document
+    std::vector<unsigned long long> out_off;   // [n_aux + 1]: list j's region is [out_off[j], out_off[j + 1]) of s_aux_ids
+    // [n_aux] the lists' lengths: read back by the blocking aux stage, estimates after the pipelined one (the exact counts are on the device)
+    std::vector<uint32_t> set_counts;
+    std::vector<PhraseDev> phrases;
+    // nested queries: the candidates are the shortest Must leaf (by upper bound: an aux leaf's exact length is on the device only),
+    // else the union of the smallest required Should group, else the union of the Should leaves
+    struct SubPlan { uint32_t union_mask = 0; uint64_t n_cand_max = 0; };
+    std::vector<SubPlan> plans;
+    uint64_t max_cand = 0;
+    bool any_union = false;
+    std::vector<unsigned long long> aux_pairs;   // the blocking stage: [begin, end) per aux list into s_aux_ids (read by its transfer)
+    size_t pa_count_of = 0;   // the pipelined stage: where the count index per list lies in cx.s_in_a
+};
+
+// Host only: region offsets, phrase drivers, nested-query plans (rq.subs[j].driver is chosen here), the row bound.
+static int32_t bm25_aux_layout(const Bm25Segment &seg, size_t s, Bm25Request &rq, Bm25AuxLayout &al) {
+    const nidx_gpu_bm25_search_options_t *opt = rq.opt;
+    const Bm25RowSets *rs = rq.rs;
+    const uint32_t n_sets = rq.n_sets, n_phrases = rq.n_phrases, n_sub = rq.n_sub, n_rows_d = rq.n_rows_d;
+    const uint32_t n_own = al.n_own = rq.n_own(), n_aux = al.n_aux = rq.n_aux();
+    al.words = (seg.n_docs + 63) / 64;
+    al.set_counts.assign(n_aux, 0);
+    std::vector<unsigned long long> &out_off = al.out_off;
+    out_off.assign(n_aux + 1, 0);
+    const uint64_t row_bound = al.row_bound =
+        !n_rows_d ? 0 : rs->distinct.back() == kPrefilterRowAll ? (uint64_t)seg.n_docs
+                      : std::min<uint64_t>(seg.n_docs, rs->link->segment_postings[s] + (rs->any_res ? rs->link->res_segment_postings[s] : 0));
+    al.phrases.assign(n_phrases, PhraseDev{});
+    for (uint32_t j = 0; j < n_sets; j++) {
+        uint64_t df = 0;
+        for (uint64_t i = opt->term_set_offsets[j]; i < opt->term_set_offsets[j + 1]; i++)
+            df += seg.term_offsets_host[opt->term_set_terms[i] + 1] - seg.term_offsets_host[opt->term_set_terms[i]];
+        const bool comp = opt->term_set_complement && opt->term_set_complement[j];
+        out_off[j + 1] = out_off[j] + (comp ? (uint64_t)seg.n_docs : std::min<uint64_t>(df, seg.n_docs));
+    }
+    for (uint32_t j = 0; j < n_phrases; j++) {
+        PhraseDev &ph = al.phrases[j];
+        ph.n_terms = (uint32_t)(opt->phrase_offsets[j + 1] - opt->phrase_offsets[j]);
+        ph.slop = opt->phrase_slops ? opt->phrase_slops[j] : 0u;
+        ph.driver = 0;
+        uint64_t best = ~0ull;
+        for (uint32_t t = 0; t < ph.n_terms; t++) {
+            ph.terms[t] = opt->phrase_terms[opt->phrase_offsets[j] + t];
+            const uint64_t df = seg.term_offsets_host[ph.terms[t] + 1] - seg.term_offsets_host[ph.terms[t]];
+            if (df < best) { best = df; ph.driver = t; }
         }
-        const size_t nw = work.size();
-        item_first[nq] = (uint32_t)nw;
-        std::vector<uint32_t> &item_list = cx.w_item_list;
-        item_list.resize(nw);
-        uint32_t n_union = 0, n_fast = 0, n_wide = 0, wide_max_clauses = 0;
-        for (size_t w = 0; w < nw; w++)
-            if (q_union[work[w].query]) item_list[n_union++] = (uint32_t)w;
-        if (n_union < nw) {
-            for (size_t w = 0; w < nw; w++) {
-                const uint32_t nc = work[w].n_clauses;
-                if (!q_union[work[w].query] && nc <= BM25_FAST_CLAUSES && !force_wide) item_list[n_union + n_fast++] = (uint32_t)w;
+        out_off[n_sets + j + 1] = out_off[n_sets + j] + best;
+    }
+    al.plans.assign(n_sub, Bm25AuxLayout::SubPlan{});
+    al.max_cand = 0;
+    al.any_union = false;
+    for (uint32_t j = 0; j < n_sub; j++) {
+        SubqueryDev &sq = rq.subs[j];
+        uint64_t best = ~0ull, group_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, should_sum = 0;
+        uint32_t group_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0}, should_mask = 0;
+        bool any_must = false;
+        for (uint32_t t = 0; t < sq.n; t++) {
+            uint64_t ub;   // the upper bound of leaf t's list
+            if (sq.src[t] & BM25_AUX_TERM) {
+                const uint32_t a = sq.src[t] & ~BM25_AUX_TERM;
+                ub = a >= n_own ? row_bound : out_off[a + 1] - out_off[a];   // (the rows' regions are laid out behind this loop)
+            } else {
+                ub = seg.term_offsets_host[sq.src[t] + 1] - seg.term_offsets_host[sq.src[t]];
             }
-            for (size_t w = 0; w < nw; w++) {
-                const uint32_t nc = work[w].n_clauses;
-                if (!q_union[work[w].query] && !(nc <= BM25_FAST_CLAUSES && !force_wide)) {
-                    item_list[n_union + n_fast + n_wide++] = (uint32_t)w;
-                    wide_max_clauses = std::max(wide_max_clauses, nc);
-                }
-            }
+            if (sq.occur[t] == NIDX_OCCUR_MUST) {
+                any_must = true;
+                if (ub < best) { best = ub; sq.driver = t; }
+            } else if (sq.occur[t] >= NIDX_OCCUR_SHOULD_GROUP) {
+                group_sum[sq.occur[t] - NIDX_OCCUR_SHOULD_GROUP] += ub, group_mask[sq.occur[t] - NIDX_OCCUR_SHOULD_GROUP] |= 1u << t;
+            } else if (sq.occur[t] == NIDX_OCCUR_SHOULD) should_sum += ub, should_mask |= 1u << t;
         }
-        // the stream kernel's clause table: list base / length / weight / attributes per clause of this segment
-        std::vector<Bm25StreamClause> &ucl = cx.w_ucl;
-        ucl.resize(n_union ? n_clauses : 0);
-        // A floor under the k-th best score of a query whose clauses are all Should terms (every document of any clause is a hit): clause c
-        // alone gives >= BM25_FLOOR_RANKS[j] >= k documents a score >= weight(c) * quotient(tf = 1, floor_fn[term][j]); the best clause's bound
-        // is the query's.  Only where nothing removes documents behind the scorer's back: no deletions, no cursor, no fast-field order
-        // (those launches run the kernel's EXTRAS form, which never reads the floor).
-        static const uint32_t floor_ranks[BM25_FLOOR_NR] = BM25_FLOOR_RANKS;
-        int floor_j = -1;
-        if (!idx->floor_fn.empty() && seg.all_alive && !after && order_field < 0)
-            for (int j = 0; j < BM25_FLOOR_NR && floor_j < 0; j++)
-                if (floor_ranks[j] >= kk) floor_j = j;
-        for (uint32_t q = 0; q < nq && n_union; q++) {
-            if (!q_union[q]) continue;
-            float q_floor = -INFINITY;
-            bool floor_ok = floor_j >= 0;
-            for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1] && floor_ok; c++) {
-                const Bm25ClauseDev &dc = dev_clauses[c];
-                if (dc.occur != 0 || (dc.mode != NIDX_TF_FREQ && dc.mode != 1) || !(dc.weight > 0.0f) || !(dc.weight < INFINITY)) floor_ok = false;
-            }
-            for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1] && floor_ok; c++) {
-                const uint8_t fn = idx->floor_fn[(size_t)clauses[c].term * BM25_FLOOR_NR + (size_t)floor_j];
-                if (fn != 255u) q_floor = std::max(q_floor, dev_clauses[c].weight * idx->quot1[fn]);
-            }
-            uint32_t floor_bits;
-            memcpy(&floor_bits, &q_floor, 4);
-            for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1]; c++) {
-                const uint64_t b = seg.term_offsets_host[clauses[c].term];
-                const uint64_t l = clen[c];
-                if (l > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a posting list of one segment holds more than 2^32 - 1 postings");
-                ucl[c] = Bm25StreamClause{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)l, dev_clauses[c].weight,
-                                          (uint32_t)dev_clauses[c].occur | ((uint32_t)dev_clauses[c].mode << 8), floor_bits, 0u, 0u};
-            }
+        Bm25AuxLayout::SubPlan &pl = al.plans[j];
+        if (any_must) pl.n_cand_max = best;
+        else {
+            sq.driver = BM25_SUB_DRIVER_UNION;
+            uint64_t sum = ~0ull;
+            for (int g = 0; g < 8; g++)
+                if (group_mask[g] && group_sum[g] < sum) sum = group_sum[g], pl.union_mask = group_mask[g];
+            if (!pl.union_mask) sum = should_sum, pl.union_mask = should_mask;   // no positive leaf at all: nothing matches
+            pl.n_cand_max = pl.union_mask ? std::min<uint64_t>(sum, seg.n_docs) : 0;
+            al.any_union |= pl.union_mask != 0;
         }
-        t_work += now_us() - t_w0;
-        const double t_up0 = now_us();
-        NIDX_HIP(cx.s_key.reserve(nw * kk * 8));
-        const size_t if_bytes = ((size_t)(nq + 1) * 4 + 31) & ~(size_t)31;   // 32-byte pieces: the clause table is read with 16-byte scalar loads
-        const size_t work_bytes = (nw * sizeof(Bm25Work) + 31) & ~(size_t)31;
-        const size_t items_bytes = (nw * 4 + 31) & ~(size_t)31;
-        const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl.size() * sizeof(Bm25StreamClause);
-        const size_t w_at = fused_in ? inq_al : 0;   // the work list's place in the block: behind the clause block, or at its head
-        NIDX_HIP(cx.s_in_w.reserve(w_at + inw_bytes));
-        NIDX_HIP(cx.h_in_w.reserve(w_at + inw_bytes));
-        unsigned char *h_w = cx.h_in_w.as<unsigned char>() + w_at, *d_w = cx.s_in_w.as<unsigned char>() + w_at;
-        if (fused_in) {
-            if (n_clauses) memcpy(cx.h_in_w.p, dev_clauses.data(), n_clauses * sizeof(Bm25ClauseDev));
-            memcpy(cx.h_in_w.as<unsigned char>() + cl_bytes, clause_offsets, (size_t)(nq + 1) * 8);
-            d_clauses = cx.s_in_w.as<Bm25ClauseDev>();
-            d_clause_offsets = reinterpret_cast<const unsigned long long *>(cx.s_in_w.as<unsigned char>() + cl_bytes);
-        }
-        memcpy(h_w, item_first.data(), (size_t)(nq + 1) * 4);
-        memcpy(h_w + if_bytes, work.data(), nw * sizeof(Bm25Work));
-        memcpy(h_w + if_bytes + work_bytes, item_list.data(), nw * 4);
-        if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl.size() * sizeof(Bm25StreamClause));
-        NIDX_HIP(hipMemcpyAsync(cx.s_in_w.p, cx.h_in_w.p, w_at + inw_bytes, hipMemcpyHostToDevice, cx.stream));
-        const uint32_t *d_item_first = reinterpret_cast<const uint32_t *>(d_w);
-        const Bm25Work *d_work = reinterpret_cast<const Bm25Work *>(d_w + if_bytes);
-        const uint32_t *d_items = reinterpret_cast<const uint32_t *>(d_w + if_bytes + work_bytes);
-        // per-query outputs of the merge kernel, one block: doc u32 [nq][kk] | score f32 [nq][kk] | count u32 [nq] | total u64 [nq] | postings u64 [nq]
-        const size_t o_doc = 0, o_score = (size_t)nq * kk * 4, o_count = o_score + (size_t)nq * kk * 4;
-        const size_t o_total = (o_count + (size_t)nq * 4 + 7) & ~(size_t)7, o_post = o_total + (size_t)nq * 8, o_seg = o_post + (size_t)nq * 8;
-        const bool cat = idx->concatenated();
-        const size_t out_bytes = o_seg + (cat ? (size_t)nq * kk * 4 : 0);   // concatenated layout: + segment u32 [nq][kk]
-        // a pipelined batch with row sets: behind the result block what the wait's stats need, [2] u64 of the projections | [rows] u32 counts
-        const size_t o_stats = (out_bytes + 7) & ~(size_t)7, stats_bytes = pipe_aux && n_rows_d ? 16 + (size_t)n_rows_d * 4 : 0;
-        NIDX_HIP(cx.h_outpack.reserve(stats_bytes ? o_stats + stats_bytes : out_bytes));
-        void *dp = nullptr;
-        NIDX_HIP(hipHostGetDevicePointer(&dp, cx.h_outpack.p, 0));
-        unsigned char *d_out = static_cast<unsigned char *>(dp);
-        if (pipe_aux) {
-            const unsigned char *d_a = cx.s_in_a.as<unsigned char>();
-            NIDX_HIP(launch_bm25_aux_ranges(reinterpret_cast<const unsigned long long *>(d_a), reinterpret_cast<const uint32_t *>(d_a + pa_count_of),
-                                            cx.s_set_counts.as<uint32_t>(), n_aux, cx.s_aux_off.as<unsigned long long>(), n_own,
-                                            stats_bytes ? reinterpret_cast<uint32_t *>(d_out + o_stats + 16) : nullptr,
-                                            stats_bytes ? cx.s_row_stats.as<unsigned long long>() : nullptr,
-                                            stats_bytes ? reinterpret_cast<unsigned long long *>(d_out + o_stats) : nullptr, cx.stream));
+        if (pl.n_cand_max > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a posting list of one segment holds more than 2^32 - 1 postings");
+        al.max_cand = std::max(al.max_cand, pl.n_cand_max);
+        out_off[n_sets + n_phrases + j + 1] = out_off[n_sets + n_phrases + j] + pl.n_cand_max;
+    }
+    for (uint32_t r = 0; r < n_rows_d; r++) out_off[n_own + r + 1] = out_off[n_own + r] + row_bound;
+    return NIDX_OK;
+}
+
+// Both aux stages begin here: the regions of the lists, and their counts zeroed.
+static int32_t bm25_aux_reserve(Bm25Ctx &cx, const Bm25AuxLayout &al) {
+    NIDX_HIP(cx.s_aux_ids.reserve(std::max<uint64_t>(al.out_off[al.n_aux], 1) * 4 + BM25_LIST_PAD_BYTES));
+    // (the rows' lists come last and are ConstScorer lists, whose frequencies no kernel reads: no parallel region for them)
+    NIDX_HIP(cx.s_aux_tfs.reserve(std::max<uint64_t>(al.out_off[al.n_own], 1) * 4 + BM25_LIST_PAD_BYTES));
+    NIDX_HIP(cx.s_set_counts.reserve((size_t)al.n_aux * 4 + 4));   // + the count of the union candidates
+    NIDX_HIP(hipMemsetAsync(cx.s_set_counts.p, 0, (size_t)al.n_aux * 4 + 4, cx.stream));
+    return NIDX_OK;
+}
+
+// The rows to project: the All requests share a row of ones, which the entry lists last — project the rest.  Their sources go to
+// cx.w_row_ptrs as [n_proj field rows | n_proj resource rows], nullptr: the row set has no such part.
+struct Bm25RowSources {
+    uint32_t n_proj = 0;
+    bool all_row = false, any_field = false;
+};
+static Bm25RowSources bm25_row_sources(const Bm25RowSets &rs, Bm25Ctx &cx) {
+    Bm25RowSources src;
+    src.n_proj = (uint32_t)rs.distinct.size();
+    src.all_row = src.n_proj && rs.distinct.back() == kPrefilterRowAll;
+    if (src.all_row) src.n_proj--;
+    cx.w_row_ptrs.assign((size_t)src.n_proj * (rs.any_res ? 2 : 1), nullptr);
+    for (uint32_t r = 0; r < src.n_proj; r++) {
+        if (rs.distinct[r] != kPrefilterRowNone) cx.w_row_ptrs[r] = rs.rows->row_ptr[rs.distinct[r]], src.any_field = true;
+        if (rs.any_res && rs.distinct_res[r] != kPrefilterRowNone) cx.w_row_ptrs[src.n_proj + r] = rs.rows->res_row_ptr[rs.distinct_res[r]];
+    }
+    return src;
+}
+
+// The rows' lists of this segment: the bitsets zeroed, the shared row of ones, every distinct row onto this segment in one launch (one
+// more for the resource parts), every row's list in one compaction.  d_row_ptrs: the sources on the device, or nullptr — they are sent
+// here, from cx.w_row_ptrs (the pipelined stage sent them with its tables).  *launches counts the kernel launches.
+static int32_t bm25_project_rows(Bm25Ctx &cx, const Bm25Segment &seg, Bm25RowSets *rs, const Bm25RowSources &src, uint32_t words,
+                                 const uint64_t *const *d_row_ptrs, const unsigned long long *d_out_off, uint32_t *d_counts, uint32_t *launches) {
+    const uint32_t n_rows_d = (uint32_t)rs->distinct.size(), n_proj = src.n_proj;
+    NIDX_HIP(cx.s_row_bits.reserve((size_t)n_rows_d * words * 8));
+    NIDX_HIP(hipMemsetAsync(cx.s_row_bits.p, 0, (size_t)n_rows_d * words * 8, cx.stream));
+    if (src.all_row) {
+        NIDX_HIP(launch_bitset_fill(cx.s_row_bits.as<uint64_t>() + (size_t)n_proj * words, words, seg.n_docs, 1, cx.stream));
+        ++*launches;
+    }
+    if (n_proj && !d_row_ptrs) {
+        NIDX_HIP(cx.s_row_ptrs.reserve(cx.w_row_ptrs.size() * sizeof(uint64_t *)));
+        NIDX_HIP(hipMemcpyAsync(cx.s_row_ptrs.p, cx.w_row_ptrs.data(), cx.w_row_ptrs.size() * sizeof(uint64_t *), hipMemcpyHostToDevice, cx.stream));
+    }
+    if (!d_row_ptrs) d_row_ptrs = cx.s_row_ptrs.as<const uint64_t *>();
+    if (n_proj && src.any_field) {
+        NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs, n_proj, (uint32_t)rs->rows->layout.words(), rs->link->doc_term.as<uint32_t>(),
+                                               seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
+                                               cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
+        rs->stats.projection_launches++, ++*launches;
+    }
+    if (n_proj && rs->any_res) {   // the uuid lists of the set resources, into the same bitsets: one more launch
+        NIDX_HIP(launch_bm25_prefilter_project(d_row_ptrs + n_proj, n_proj, (uint32_t)rs->rows->res_words, rs->link->res_term.as<uint32_t>(),
+                                               seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.n_docs, words,
+                                               cx.s_row_bits.as<uint64_t>(), cx.s_row_stats.as<unsigned long long>(), cx.stream));
+        rs->stats.projection_launches++, ++*launches;
+    }
+    NIDX_HIP(launch_bitset_compact(cx.s_row_bits.as<uint64_t>(), words, n_rows_d, d_out_off, cx.s_aux_ids.as<uint32_t>(), d_counts, cx.stream));
+    rs->stats.compaction_launches++, ++*launches;
+    return NIDX_OK;
+}
+
+// The pipelined aux stage: a fixed number of launches, one transfer in, nothing out.  The lists' exact lengths stay on the device:
+// al.set_counts gets the estimates the work list is planned from (bm25_aux_plan.h).
+static int32_t bm25_aux_pipelined(Bm25Ctx &cx, const Bm25Segment &seg, size_t s, const Bm25Request &rq, Bm25AuxLayout &al, Bm25TicketRun *tr) {
+    const nidx_gpu_bm25_search_options_t *opt = rq.opt;
+    Bm25RowSets *rs = rq.rs;
+    const uint32_t n_sets = rq.n_sets, n_rows_d = rq.n_rows_d, n_own = al.n_own, n_aux = al.n_aux, words = al.words;
+    const std::vector<unsigned long long> &out_off = al.out_off;
+    if (int32_t rc = bm25_aux_reserve(cx, al)) return rc;
+    std::vector<uint32_t> slot_of_set, comp_of_slot;
+    const uint32_t n_pipe_slots = bm25_assign_slots(opt->term_set_offsets, opt->term_set_complement, n_sets, slot_of_set, comp_of_slot);
+    bool any_comp = false;
+    for (uint32_t f : comp_of_slot) any_comp |= f != 0;
+    std::vector<Bm25ScatterItem> &items = cx.w_scatter;
+    bm25_scatter_table(opt->term_set_offsets, opt->term_set_terms, n_sets, slot_of_set.data(), seg.term_offsets_host.data(), kBm25ScatterChunk, items);
+    const Bm25RowSources src = n_rows_d ? bm25_row_sources(*rs, cx) : Bm25RowSources{};
+    const size_t n_ptrs = src.n_proj ? cx.w_row_ptrs.size() : 0;
+    // the tables' block; the lists' counts live in s_set_counts as [slots | distinct rows]
+    const size_t pa_off = 0, pa_slot_off = pa_off + (size_t)(n_aux + 1) * 8, pa_ptrs = pa_slot_off + (size_t)n_pipe_slots * 8,
+                 pa_items = pa_ptrs + n_ptrs * 8, pa_flags = pa_items + items.size() * sizeof(Bm25ScatterItem) + (size_t)n_aux * 4,
+                 pa_bytes = pa_flags + (size_t)n_pipe_slots * 4;
+    al.pa_count_of = pa_items + items.size() * sizeof(Bm25ScatterItem);
+    NIDX_HIP(cx.h_in_a.reserve(pa_bytes));
+    NIDX_HIP(cx.s_in_a.reserve(pa_bytes));
+    unsigned char *h_a = cx.h_in_a.as<unsigned char>(), *d_a = cx.s_in_a.as<unsigned char>();
+    memcpy(h_a + pa_off, out_off.data(), (size_t)(n_aux + 1) * 8);
+    unsigned long long *h_slot_off = reinterpret_cast<unsigned long long *>(h_a + pa_slot_off);
+    uint32_t *h_count_of = reinterpret_cast<uint32_t *>(h_a + al.pa_count_of);
+    for (uint32_t j = 0; j < n_sets; j++) {
+        h_count_of[j] = slot_of_set[j];   // (kBm25NoSlot: the empty list)
+        if (slot_of_set[j] != kBm25NoSlot) h_slot_off[slot_of_set[j]] = out_off[j];
+    }
+    for (uint32_t r = 0; r < n_rows_d; r++) h_count_of[n_own + r] = n_pipe_slots + r;
+    if (n_ptrs) memcpy(h_a + pa_ptrs, cx.w_row_ptrs.data(), n_ptrs * 8);
+    if (!items.empty()) memcpy(h_a + pa_items, items.data(), items.size() * sizeof(Bm25ScatterItem));
+    if (n_pipe_slots) memcpy(h_a + pa_flags, comp_of_slot.data(), (size_t)n_pipe_slots * 4);
+    NIDX_HIP(hipMemcpyAsync(cx.s_in_a.p, cx.h_in_a.p, pa_bytes, hipMemcpyHostToDevice, cx.stream));
+    if (n_pipe_slots && words) {
+        NIDX_HIP(cx.s_set_bits.reserve((size_t)n_pipe_slots * words * 8));
+        NIDX_HIP(hipMemsetAsync(cx.s_set_bits.p, 0, (size_t)n_pipe_slots * words * 8, cx.stream));
+        if (!items.empty()) {
+            NIDX_HIP(launch_bm25_set_scatter(reinterpret_cast<const Bm25ScatterItem *>(d_a + pa_items), (uint32_t)items.size(), seg.doc_ids.as<uint32_t>(),
+                                             seg.n_docs, words, cx.s_set_bits.as<uint64_t>(), cx.stream));
             tr->aux_launches++;
         }
-        NIDX_HIP(cx.s_count.reserve(nw * 4));
-        NIDX_HIP(cx.s_total.reserve(nw * 8));
-        NIDX_HIP(cx.s_postings.reserve(nw * 8));
-        const uint32_t match_words = (seg.n_docs + 31) / 32;
-        if (n_slots) {
-            const uint64_t bytes = (uint64_t)n_slots * std::max<uint32_t>(match_words, 1) * 4;
-            if (bytes > (1ull << 30))
-                return fail(NIDX_ERR_UNSUPPORTED, "%u faceted queries over a %u-document segment need %llu bytes of match bitsets (limit 1 GiB): split the batch",
-                            n_slots, seg.n_docs, (unsigned long long)bytes);
-            NIDX_HIP(cx.s_match_bits.reserve(bytes));
-            NIDX_HIP(hipMemsetAsync(cx.s_match_bits.p, 0, bytes, cx.stream));
+        if (any_comp) {
+            NIDX_HIP(launch_bm25_set_complement(cx.s_set_bits.as<uint64_t>(), reinterpret_cast<const uint32_t *>(d_a + pa_flags), n_pipe_slots, words,
+                                                seg.n_docs, cx.stream));
+            tr->aux_launches++;
         }
-        const double t_up1 = now_us();
-        Bm25Args a;
-        a.work = d_work;
-        a.n_docs = seg.n_docs;
-        a.term_offsets = seg.term_offsets.as<unsigned long long>();
-        a.doc_ids = seg.doc_ids.as<uint32_t>();
-        a.tfs = seg.tfs.as<uint32_t>();
-        a.fieldnorm_ids = seg.fieldnorm_ids.as<uint8_t>();
-        a.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
-        a.tf_cache = idx->tf_cache.as<float>();
-        a.clauses = d_clauses;
-        a.clause_offsets = d_clause_offsets;
-        a.after = after ? cx.s_after.as<Bm25AfterDev>() : nullptr;
-        a.k = kk;
-        a.segment_ord = (uint32_t)s;
-        a.out_key = cx.s_key.as<unsigned long long>();
-        a.out_count = cx.s_count.as<uint32_t>();
-        a.out_total = cx.s_total.as<unsigned long long>();
-        a.out_postings = cx.s_postings.as<unsigned long long>();
-        a.aux_offsets = n_aux ? cx.s_aux_off.as<unsigned long long>() : nullptr;
-        a.aux_doc_ids = n_aux ? cx.s_aux_ids.as<uint32_t>() : nullptr;
-        a.aux_tfs = n_aux ? cx.s_aux_tfs.as<uint32_t>() : nullptr;
-        a.order_key = order_field >= 0 ? seg.order_key[order_field].as<uint32_t>() : nullptr;
-        a.order_desc = opt->order_desc ? 1 : 0;
-        a.match_bits = n_slots ? cx.s_match_bits.as<uint32_t>() : nullptr;
-        a.match_slot = n_slots ? cx.s_match_slot.as<int>() : nullptr;
-        a.match_words = match_words;
-        a.uclauses = reinterpret_cast<const Bm25StreamClause *>(d_w + if_bytes + work_bytes + items_bytes);
-        a.dbg = nullptr;
-        DevBuf dbgbuf;
-        if (getenv("NIDX_GPU_BM25_DEBUG")) {
-            NIDX_HIP(dbgbuf.alloc((16 + 8 * nw) * 8));
-            NIDX_HIP(hipMemsetAsync(dbgbuf.p, 0, (16 + 8 * nw) * 8, cx.stream));
-            a.dbg = dbgbuf.as<unsigned long long>();
+        NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>(), words, n_pipe_slots, reinterpret_cast<const unsigned long long *>(d_a + pa_slot_off),
+                                       cx.s_aux_ids.as<uint32_t>(), cx.s_set_counts.as<uint32_t>(), cx.stream));
+        tr->aux_launches++;
+    }
+    if (n_rows_d && words)
+        if (int32_t rc = bm25_project_rows(cx, seg, rs, src, words, reinterpret_cast<const uint64_t *const *>(d_a + pa_ptrs),
+                                           reinterpret_cast<const unsigned long long *>(d_a + pa_off) + n_own, cx.s_set_counts.as<uint32_t>() + n_pipe_slots,
+                                           &tr->aux_launches))
+            return rc;
+    // the estimates the work list is planned from (set_counts stays a host-side guess: the exact counts are on the device)
+    for (uint32_t j = 0; j < n_sets; j++) al.set_counts[j] = (uint32_t)(out_off[j + 1] - out_off[j]);   // min(sum df, n_docs), n_docs of a complement
+    for (uint32_t r = 0; r < n_rows_d; r++) {
+        uint64_t est = bm25_estimate_all(seg.n_docs);
+        if (!(src.all_row && r == n_rows_d - 1)) {
+            const PrefilterRows &R = *rs->rows;
+            const uint32_t fr = rs->distinct[r], rr = rs->any_res ? rs->distinct_res[r] : kPrefilterRowNone;
+            const uint64_t f_docs = fr == kPrefilterRowNone ? 0 : fr < R.row_docs.size() ? R.row_docs[fr] : ~0ull;
+            const uint64_t r_docs = rr == kPrefilterRowNone ? 0 : rr < R.res_row_docs.size() ? R.res_row_docs[rr] : ~0ull;
+            est = bm25_estimate_row(al.row_bound, bm25_estimate_row_part(f_docs, rs->link->segment_postings[s], rs->link->linked_documents),
+                                    bm25_estimate_row_part(r_docs, rs->any_res ? rs->link->res_segment_postings[s] : 0, rs->link->linked_resources));
+        }
+        al.set_counts[n_own + r] = (uint32_t)est;
+    }
+    NIDX_HIP(cx.s_aux_off.reserve((2 * (size_t)n_aux + 2) * 8));   // (written by bm25_aux_ranges_kernel: bm25_stage_and_launch)
+    return NIDX_OK;
+}
 
+// The blocking aux stage: sets, rows, phrases, nested queries, then one host round trip for all their counts (al.set_counts) and the
+// [begin, end) pairs the scoring kernels read.  row_stats: the projections' running sums over the segments.
+static int32_t bm25_aux_blocking(const Bm25Index *idx, Bm25Ctx &cx, const Bm25Segment &seg, const Bm25Request &rq, Bm25AuxLayout &al, Bm25TicketRun *tr) {
+    const nidx_gpu_bm25_search_options_t *opt = rq.opt;
+    Bm25RowSets *rs = rq.rs;
+    const uint32_t n_sets = rq.n_sets, n_phrases = rq.n_phrases, n_sub = rq.n_sub, n_rows_d = rq.n_rows_d, n_own = al.n_own, n_aux = al.n_aux, words = al.words;
+    const std::vector<unsigned long long> &out_off = al.out_off;
+    if (int32_t rc = bm25_aux_reserve(cx, al)) return rc;
+    NIDX_HIP(cx.s_aux_out_off.reserve((size_t)(n_aux + 1) * 8));
+    NIDX_HIP(hipMemcpyAsync(cx.s_aux_out_off.p, out_off.data(), (size_t)(n_aux + 1) * 8, hipMemcpyHostToDevice, cx.stream));
+    // A set owns a bitset when it has terms or the complement flag.  A set with neither — every row set is one — is the empty
+    // list its zeroed count already says: no bitset, no place in a compaction.  Scratch follows the sets that scatter, not the queries.
+    auto owns_bits = [opt](uint32_t j) {
+        return opt->term_set_offsets[j + 1] != opt->term_set_offsets[j] || (opt->term_set_complement && opt->term_set_complement[j]);
+    };
+    uint32_t n_bitsets = 0;
+    for (uint32_t j = 0; j < n_sets; j++) n_bitsets += owns_bits(j) ? 1u : 0u;
+    if (n_bitsets && words) {
+        NIDX_HIP(cx.s_set_bits.reserve(std::max<size_t>((size_t)n_bitsets * words, 1) * 8));
+        NIDX_HIP(launch_bitset_fill(cx.s_set_bits.as<uint64_t>(), n_bitsets * words, 0, 0, cx.stream));   // (n_bits matters when filling with ones only)
+        uint32_t slot = 0;
+        for (uint32_t j = 0; j < n_sets; j++) {
+            if (!owns_bits(j)) continue;
+            const uint32_t nl = (uint32_t)(opt->term_set_offsets[j + 1] - opt->term_set_offsets[j]);
+            if (nl)
+                NIDX_HIP(launch_bitset_scatter(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(),
+                                               cx.s_set_terms.as<uint32_t>() + opt->term_set_offsets[j], nl, seg.n_docs,
+                                               cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, cx.stream));
+            if (opt->term_set_complement && opt->term_set_complement[j])
+                NIDX_HIP(launch_bitset_not(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, seg.n_docs, cx.stream));
+            slot++;
         }
-        Bm25MergeArgs mg;
-        mg.item_first = d_item_first;
-        mg.item_key = cx.s_key.as<unsigned long long>();
-        mg.item_count = cx.s_count.as<uint32_t>();
-        mg.item_total = cx.s_total.as<unsigned long long>();
-        mg.item_postings = cx.s_postings.as<unsigned long long>();
-        mg.k = kk;
-        mg.out_doc = reinterpret_cast<uint32_t *>(d_out + o_doc);
-        mg.out_score = reinterpret_cast<float *>(d_out + o_score);
-        mg.out_count = reinterpret_cast<uint32_t *>(d_out + o_count);
-        mg.out_total = reinterpret_cast<unsigned long long *>(d_out + o_total);
-        mg.out_postings = reinterpret_cast<unsigned long long *>(d_out + o_post);
-        if (cat) {
-            mg.seg_base = idx->d_seg_base.as<uint32_t>();
-            mg.n_seg = idx->n_segments;
-            mg.out_seg = reinterpret_cast<uint32_t *>(d_out + o_seg);
+        // one compaction per run of consecutive sets that own a bitset (all sets do, and it is one, unless empty sets lie between)
+        slot = 0;
+        for (uint32_t j = 0; j < n_sets;) {
+            if (!owns_bits(j)) { j++; continue; }
+            uint32_t j1 = j;
+            while (j1 < n_sets && owns_bits(j1)) j1++;
+            NIDX_HIP(launch_bitset_compact(cx.s_set_bits.as<uint64_t>() + (size_t)slot * words, words, j1 - j,
+                                           cx.s_aux_out_off.as<unsigned long long>() + j, cx.s_aux_ids.as<uint32_t>(),
+                                           cx.s_set_counts.as<uint32_t>() + j, cx.stream));
+            slot += j1 - j;
+            j = j1;
         }
-        // When every item of the batch goes through the stream kernel and k <= 64, the scoring launch merges as well (Bm25FusedMerge): the last wave
-        // of every query's slices does what bm25_merge_kernel would do in a launch of its own.  NIDX_GPU_BM25_FUSED_MERGE=0 keeps the two launches.
-        bool fused_merge = n_union == nw && nw > 0 && kk <= 64 && !a.dbg;
-        if (const char *fe = getenv("NIDX_GPU_BM25_FUSED_MERGE")) fused_merge = fused_merge && atoi(fe) != 0;
-        if (fused_merge) {
-            const size_t done_bytes = (size_t)nq * (BM25_FUSE_MAX_GROUPS + 1u) * 4;
-            if (cx.s_fuse_done.bytes < done_bytes) {
-                NIDX_HIP(cx.s_fuse_done.reserve(done_bytes));
-                NIDX_HIP(hipMemsetAsync(cx.s_fuse_done.p, 0, cx.s_fuse_done.bytes, cx.stream));
-            }
-            NIDX_HIP(cx.s_fuse_key.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * kk * 8));
-            NIDX_HIP(cx.s_fuse_count.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 4));
-            NIDX_HIP(cx.s_fuse_total.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 8));
-            NIDX_HIP(cx.s_fuse_postings.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 8));
-            a.fm.done = cx.s_fuse_done.as<uint32_t>();
-            a.fm.g_key = cx.s_fuse_key.as<unsigned long long>();
-            a.fm.g_count = cx.s_fuse_count.as<uint32_t>();
-            a.fm.g_total = cx.s_fuse_total.as<unsigned long long>();
-            a.fm.g_postings = cx.s_fuse_postings.as<unsigned long long>();
-            a.fm.out_doc = mg.out_doc;
-            a.fm.out_score = mg.out_score;
-            a.fm.out_count = mg.out_count;
-            a.fm.out_total = mg.out_total;
-            a.fm.out_postings = mg.out_postings;
-            a.fm.seg_base = mg.seg_base;
-            a.fm.n_seg = mg.n_seg;
-            a.fm.out_seg = mg.out_seg;
-        }
-        NIDX_HIP(hipEventRecord(cx.ev0, cx.stream));
-        {
-            const bool extras = a.alive != nullptr || a.match_bits != nullptr || a.order_key != nullptr || a.after != nullptr;
-            NIDX_HIP(launch_bm25_stream(a, d_items, n_union, extras, cx.stream));
-        }
-        NIDX_HIP(launch_bm25_search(a, d_items + n_union, n_fast, d_items + n_union + n_fast, n_wide, wide_max_clauses, cx.stream));
-        NIDX_HIP(hipEventRecord(cx.ev1, cx.stream));
-        if (!fused_merge) NIDX_HIP(launch_bm25_merge(mg, nq, cx.stream));
-        if (n_slots)
-            NIDX_HIP(launch_facet_count(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), cx.s_pair_term.as<uint32_t>(),
-                                        cx.s_pair_slot.as<int>(), (uint32_t)n_pairs, cx.s_match_bits.as<uint32_t>(), match_words,
-                                        cx.s_facet_counts.as<unsigned long long>(), cx.stream));
-        const unsigned char *h_out = cx.h_outpack.as<unsigned char>();
-        const uint32_t *h_doc = reinterpret_cast<const uint32_t *>(h_out + o_doc);
-        const float *h_score = reinterpret_cast<const float *>(h_out + o_score);
-        const uint32_t *h_count = reinterpret_cast<const uint32_t *>(h_out + o_count);
-        const unsigned long long *h_total = reinterpret_cast<const unsigned long long *>(h_out + o_total);
-        const unsigned long long *h_post = reinterpret_cast<const unsigned long long *>(h_out + o_post);
-        const uint32_t *h_seg = reinterpret_cast<const uint32_t *>(h_out + o_seg);   // (concatenated layout only)
-        if (async_slot && idx->segs.size() == 1 && (n_aux == 0 || pipe_aux) && n_slots == 0 && order_field < 0 && !a.dbg) {
-            // pipelined: the collect step runs in nidx_gpu_bm25_search_wait (the buffers are the slot's: swapped in by submit)
-            if (host_dbg)
-                fprintf(stderr, "[bm25 host submit] total=%.0f us: clauses=%.0f set-up=%.0f work list=%.0f staging+upload=%.0f launches=%.0f\n", now_us() - t_entry,
-                        t_begin - t_entry, t_seg0 - t_begin, t_work, t_up1 - t_up0, now_us() - t_up1);
-            Bm25Slot &sl = *async_slot;
-            sl.launched = true;
-            sl.nq = nq, sl.k = k, sl.kk = kk;
-            sl.cat = cat;
-            sl.o_doc = o_doc, sl.o_score = o_score, sl.o_count = o_count, sl.o_total = o_total, sl.o_post = o_post, sl.o_seg = o_seg;
-            sl.pf_stats = rs ? rs->stats : nidx_gpu_bm25_prefilter_search_stats_t{};
-            sl.n_stat_rows = stats_bytes ? n_rows_d : 0u;
-            sl.o_stats = o_stats;
-            if (tr) tr->pipelined = true;
-            return NIDX_OK;
-        }
-        const double t_s0 = now_us();
-        NIDX_HIP(hipStreamSynchronize(cx.stream));
-        if (tr) tr->syncs++;
-        t_sync += now_us() - t_s0;
-        const double t_c0 = now_us();
-        float ms = 0.f;
-        NIDX_HIP(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
-        cx.kernel_ms += ms;
-        if (a.dbg) {
-            unsigned long long d[9];
-            NIDX_HIP(hipMemcpy(d, a.dbg, 72, hipMemcpyDeviceToHost));
-            if (n_union) {
-                std::vector<unsigned long long> tr(8 * nw);
-                NIDX_HIP(hipMemcpy(tr.data(), a.dbg + 16, tr.size() * 8, hipMemcpyDeviceToHost));
-                std::vector<std::pair<unsigned long long, uint32_t>> by;
-                for (uint32_t w = 0; w < nw; w++)
-                    if (tr[8 * w]) by.push_back({tr[8 * w], w});
-                std::sort(by.begin(), by.end());
-                auto pct = [&](double p) { return by.empty() ? 0ull : by[(size_t)(p * (by.size() - 1))].first; };
-                unsigned long long t_min = ~0ull, t_max = 0;
-                for (auto &e : by) {
-                    const unsigned long long st = tr[8 * e.second + 3] & 0xffffffffull;
-                    t_min = std::min(t_min, st);
-                    t_max = std::max(t_max, st);
-                }
-                fprintf(stderr, "[bm25 dbg] union items %zu: cycles p10 %llu p50 %llu p90 %llu p99 %llu max %llu; entry clocks (low 32 bits) span %llu\n", by.size(),
-                        pct(0.1), pct(0.5), pct(0.9), pct(0.99), pct(1.0), t_max - t_min);
-                {   // phase cycles per window by the number of slices of the item's query
-                    const uint32_t edges[5] = {1, 2, 4, 16, 0xffffffffu};
-                    for (int g = 0; g < 5; g++) {
-                        unsigned long long n = 0, wins = 0, ld = 0, fi = 0, fn = 0, rs = 0, st = 0, po = 0;
-                        for (auto &e : by) {
-                            const uint32_t w = e.second, ns = work[w].n_slices;
-                            if (ns > edges[g] || (g > 0 && ns <= edges[g - 1])) continue;
-                            n++, wins += tr[8 * w + 2] & 0xffffffffull, ld += tr[8 * w + 4], fi += tr[8 * w + 5], fn += tr[8 * w + 6], rs += tr[8 * w + 7], st += tr[8 * w + 1], po += tr[8 * w + 3] >> 32;
-                        }
-                        if (n) fprintf(stderr, "[bm25 dbg]   queries of <= %u slices: %llu items, %.1f windows and %.0f postings per item, setup %.0f; per window: load %.0f filter %.0f final %.0f resolve %.0f cycles\n",
-                                       edges[g], n, (double)wins / n, (double)po / n, (double)st / n, (double)ld / wins, (double)fi / wins, (double)fn / wins, (double)rs / wins);
-                    }
-                }
-                for (size_t i = by.size() >= 6 ? by.size() - 6 : 0; i < by.size(); i++) {
-                    const uint32_t w = by[i].second;
-                    fprintf(stderr, "[bm25 dbg]   slow item %u: %llu cycles (setup %llu; load %llu filter %llu final %llu resolve %llu), %llu windows, %llu inserts, %llu postings, query %u slice %u/%u\n", w, tr[8 * w],
-                            tr[8 * w + 1], tr[8 * w + 4], tr[8 * w + 5], tr[8 * w + 6], tr[8 * w + 7], tr[8 * w + 2] & 0xffffffffull, tr[8 * w + 2] >> 32, tr[8 * w + 3] >> 32, work[w].query, work[w].slice, work[w].n_slices);
-                }
-                for (size_t i = 0; i < std::min<size_t>(3, by.size()); i++) {
-                    const uint32_t w = by[i].second;
-                    fprintf(stderr, "[bm25 dbg]   fast item %u: %llu cycles (setup %llu; load %llu filter %llu final %llu resolve %llu), %llu windows, %llu inserts, %llu postings, query %u slice %u/%u\n", w, tr[8 * w],
-                            tr[8 * w + 1], tr[8 * w + 4], tr[8 * w + 5], tr[8 * w + 6], tr[8 * w + 7], tr[8 * w + 2] & 0xffffffffull, tr[8 * w + 2] >> 32, tr[8 * w + 3] >> 32, work[w].query, work[w].slice, work[w].n_slices);
-                }
-            }
-            fprintf(stderr, "[bm25 dbg] items=%llu windows=%llu (max %llu per item) cycles/item: setup=%llu load=%llu apply=%llu fold=%llu windows total=%llu; longest item (entry to exit) %llu cycles; kernel_ms=%.3f\n",
-                    d[5], d[4], d[8], d[6] / (d[5] ? d[5] : 1), d[0] / (d[5] ? d[5] : 1), d[1] / (d[5] ? d[5] : 1), d[2] / (d[5] ? d[5] : 1), d[3] / (d[5] ? d[5] : 1), d[7], ms);
-        }
-        const bool direct = idx->segs.size() == 1;   // one segment: the device list is the answer, no host merge
-        for (uint32_t q = 0; q < nq; q++) {  // per segment the device already merged the slices
-            if (out_total) out_total[q] += h_total[q];
-            if (out_postings) out_postings[q] += h_post[q];
-            if (k == 0) continue;
-            if (direct) {
-                const uint32_t n = std::min<uint32_t>(h_count[q], k);
-                out_count[q] = n;
-                for (uint32_t i = 0; i < n; i++) {
-                    const uint32_t d = h_doc[(size_t)q * kk + i];   // concatenated layout: already the doc inside its segment
-                    const uint32_t sg = cat ? h_seg[(size_t)q * kk + i] : (uint32_t)s;
-                    if (out_docaddr) out_docaddr[(size_t)q * k + i] = ((uint64_t)sg << 32) | d;
-                    if (out_score) out_score[(size_t)q * k + i] = order_field >= 0 ? 0.f : h_score[(size_t)q * kk + i];
-                    if (opt->out_order_value)
-                        opt->out_order_value[(size_t)q * k + i] = order_field >= 0 ? seg.fast_host[order_field][cat ? idx->seg_base[sg] + d : d] : 0;
-                }
-                continue;
-            }
-            for (uint32_t i = 0; i < h_count[q]; i++) {
-                const uint32_t d = h_doc[(size_t)q * kk + i];
-                if (order_field >= 0) merged[q].push_back(Hit{0.f, ((uint64_t)s << 32) | d, seg.fast_host[order_field][d]});
-                else merged[q].push_back(Hit{h_score[(size_t)q * kk + i], ((uint64_t)s << 32) | d, 0});
-            }
-        }
-        t_collect += now_us() - t_c0;
     }
-    const double t_merge0 = now_us();
+    if (n_rows_d && words) {
+        uint32_t launches = 0;
+        if (int32_t rc = bm25_project_rows(cx, seg, rs, bm25_row_sources(*rs, cx), words, nullptr, cx.s_aux_out_off.as<unsigned long long>() + n_own,
+                                           cx.s_set_counts.as<uint32_t>() + n_own, &launches))
+            return rc;
+    }
+    for (uint32_t j = 0; j < n_phrases; j++) {
+        const PhraseDev &ph = al.phrases[j];
+        const uint64_t n_driver = out_off[n_sets + j + 1] - out_off[n_sets + j];
+        if (n_driver == 0) continue;
+        NIDX_HIP(cx.s_phrase_tf.reserve(n_driver * 4));
+        uint32_t *slop_left = nullptr;
+        if (ph.slop) {
+            // PhraseScorer's `left` list per document: as many entries as the first term has positions in this segment
+            const uint64_t tb = seg.term_offsets_host[ph.terms[0]], te = seg.term_offsets_host[ph.terms[0] + 1];
+            unsigned long long pr[2] = {0, 0};
+            NIDX_HIP(hipMemcpyAsync(&pr[0], seg.pos_offsets.as<unsigned long long>() + tb, 8, hipMemcpyDeviceToHost, cx.stream));
+            NIDX_HIP(hipMemcpyAsync(&pr[1], seg.pos_offsets.as<unsigned long long>() + te, 8, hipMemcpyDeviceToHost, cx.stream));
+            NIDX_HIP(hipStreamSynchronize(cx.stream));
+            NIDX_HIP(cx.s_slop_left.reserve(std::max<uint64_t>(pr[1] - pr[0], 1) * 8));   // (position, budget used) pairs
+            slop_left = cx.s_slop_left.as<uint32_t>();
+        }
+        NIDX_HIP(launch_phrase_match(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.pos_offsets.as<unsigned long long>(),
+                                     seg.positions.as<uint32_t>(), ph, (uint32_t)n_driver, cx.s_phrase_tf.as<uint32_t>(), slop_left, cx.stream));
+        NIDX_HIP(launch_phrase_compact(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), ph, cx.s_phrase_tf.as<uint32_t>(), seg.fieldnorm_ids.as<uint8_t>(),
+                                       out_off[n_sets + j], cx.s_aux_ids.as<uint32_t>(), cx.s_aux_tfs.as<uint32_t>(),
+                                       cx.s_set_counts.as<uint32_t>() + n_sets + j, cx.stream));
+    }
+    if (n_sub) {
+        const uint64_t max_cand = al.max_cand;
+        NIDX_HIP(cx.s_phrase_tf.reserve(std::max<uint64_t>(max_cand, 1) * 8));   // [n] match flags | [n] score bits
+        if (al.any_union) {
+            NIDX_HIP(cx.s_sub_bits.reserve(std::max<size_t>(words, 1) * 8));
+            NIDX_HIP(cx.s_sub_union.reserve(std::max<uint64_t>(max_cand, 1) * 4));
+        }
+        SubqueryLists L{seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), seg.tfs.as<uint32_t>(), cx.s_aux_ids.as<uint32_t>(),
+                        cx.s_aux_tfs.as<uint32_t>(), cx.s_aux_out_off.as<unsigned long long>(), cx.s_set_counts.as<uint32_t>(),
+                        cx.s_sub_union.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_aux};
+        for (uint32_t j = 0; j < n_sub; j++) {
+            const Bm25AuxLayout::SubPlan &pl = al.plans[j];
+            const SubqueryDev &sq = rq.subs[j];
+            if (pl.n_cand_max == 0) continue;
+            if (sq.driver == BM25_SUB_DRIVER_UNION) {
+                NIDX_HIP(launch_bitset_fill(cx.s_sub_bits.as<uint64_t>(), words, seg.n_docs, 0, cx.stream));
+                for (uint32_t t = 0; t < sq.n; t++)
+                    if (pl.union_mask >> t & 1) NIDX_HIP(launch_subquery_scatter(L, sq.src[t], pl.n_cand_max, cx.s_sub_bits.as<uint64_t>(), cx.stream));
+                // out_off[0] == 0: the union list starts at the head of its own buffer
+                NIDX_HIP(launch_bitset_compact(cx.s_sub_bits.as<uint64_t>(), words, 1, cx.s_aux_out_off.as<unsigned long long>(),
+                                               cx.s_sub_union.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_aux, cx.stream));
+            }
+            uint32_t *tmp_ok = cx.s_phrase_tf.as<uint32_t>(), *tmp_score = tmp_ok + max_cand;
+            NIDX_HIP(launch_subquery_match(L, idx->tf_cache.as<float>(), sq, (uint32_t)pl.n_cand_max, tmp_ok, tmp_score, cx.stream));
+            NIDX_HIP(launch_subquery_compact(L, sq, tmp_ok, tmp_score, out_off[n_sets + n_phrases + j], cx.s_aux_ids.as<uint32_t>(),
+                                             cx.s_aux_tfs.as<uint32_t>(), cx.s_set_counts.as<uint32_t>() + n_sets + n_phrases + j, cx.stream));
+        }
+    }
+    // the one read-back: every list's count, and the projections' counters
+    unsigned long long row_stats[2] = {0, 0};   // documents visited, postings written by the projections of this call so far
+    NIDX_HIP(hipMemcpyAsync(al.set_counts.data(), cx.s_set_counts.p, (size_t)n_aux * 4, hipMemcpyDeviceToHost, cx.stream));
+    if (n_rows_d) NIDX_HIP(hipMemcpyAsync(row_stats, cx.s_row_stats.p, 16, hipMemcpyDeviceToHost, cx.stream));   // (running sums over the segments)
+    NIDX_HIP(hipStreamSynchronize(cx.stream));
+    if (tr) tr->syncs++;
+    for (uint32_t r = 0; r < n_rows_d; r++) rs->stats.list_entries += al.set_counts[n_own + r];
+    if (n_rows_d) rs->stats.documents_visited = row_stats[0], rs->stats.postings_written = row_stats[1];
+    std::vector<unsigned long long> &aux_pairs = al.aux_pairs;
+    aux_pairs.assign(2 * (size_t)n_aux + 2, 0);
+    for (uint32_t j = 0; j < n_aux; j++) {
+        aux_pairs[2 * j] = out_off[j];
+        aux_pairs[2 * j + 1] = out_off[j] + al.set_counts[j];
+    }
+    NIDX_HIP(cx.s_aux_off.reserve(aux_pairs.size() * 8));
+    NIDX_HIP(hipMemcpyAsync(cx.s_aux_off.p, aux_pairs.data(), aux_pairs.size() * 8, hipMemcpyHostToDevice, cx.stream));
+    return NIDX_OK;
+}
+
+// Every clause's list length in this segment, looked up once (two random reads of an 8 MB table per plain term), then the work list
+// (bm25_work_plan.h) into cx.w_work / w_item_first / w_q_union / w_item_list.
+static Bm25WorkPlan bm25_plan_segment(const Bm25Index *idx, const Bm25Segment &seg, const Bm25Request &rq, const Bm25AuxLayout &al, const Bm25PlanKnobs &knobs,
+                                      Bm25Ctx &cx) {
+    const nidx_gpu_bm25_clause_t *clauses = rq.clauses;
+    const uint64_t n_clauses = rq.n_clauses;
+    std::vector<uint64_t> &clen = cx.w_clause_len;
+    std::vector<uint32_t> &cterm = cx.w_clause_term;
+    clen.resize(n_clauses);
+    cterm.resize(n_clauses);
+    for (uint64_t c = 0; c < n_clauses; c++) {
+        if (c + 16 < n_clauses && !(clauses[c + 16].term & (NIDX_BM25_TERM_SET | NIDX_BM25_PHRASE | NIDX_BM25_SUBQUERY)))
+            __builtin_prefetch(&seg.term_offsets_host[clauses[c + 16].term]);
+        const uint32_t term = cterm[c] = clauses[c].term;
+        if (term & NIDX_BM25_TERM_SET) clen[c] = al.set_counts[rq.aux_of_set(term & ~NIDX_BM25_TERM_SET)];
+        else if (term & NIDX_BM25_PHRASE) clen[c] = al.set_counts[rq.n_sets + (term & ~NIDX_BM25_PHRASE)];
+        else if (term & NIDX_BM25_SUBQUERY) clen[c] = al.set_counts[rq.n_sets + rq.n_phrases + (term & ~NIDX_BM25_SUBQUERY)];
+        else clen[c] = seg.term_offsets_host[term + 1] - seg.term_offsets_host[term];
+    }
+    Bm25PlanBatch batch;
+    batch.clause_offsets = rq.clause_offsets, batch.clause_len = clen.data(), batch.clause_term = cterm.data();
+    batch.special_bits = NIDX_BM25_TERM_SET | NIDX_BM25_PHRASE | NIDX_BM25_SUBQUERY;
+    batch.nq = rq.nq, batch.n_docs = seg.n_docs, batch.n_cus = (uint32_t)idx->n_cus;
+    return bm25_plan_work(knobs, batch, cx.w_postings, cx.w_work, cx.w_item_first, cx.w_q_union, cx.w_item_list);
+}
+
+// The stream kernel's clause table (cx.w_ucl): list base / length / weight / attributes per clause of this segment, with the score floors.
+static int32_t bm25_stream_clauses(const Bm25Index *idx, const Bm25Segment &seg, const Bm25Request &rq, uint32_t n_union, Bm25Ctx &cx) {
+    const nidx_gpu_bm25_clause_t *clauses = rq.clauses;
+    const uint64_t *clause_offsets = rq.clause_offsets;
+    const std::vector<Bm25ClauseDev> &dev_clauses = cx.w_dev_clauses;
+    std::vector<Bm25StreamClause> &ucl = cx.w_ucl;
+    ucl.resize(n_union ? rq.n_clauses : 0);
+    // A floor under the k-th best score of a query whose clauses are all Should terms (every document of any clause is a hit): clause c
+    // alone gives >= BM25_FLOOR_RANKS[j] >= k documents a score >= weight(c) * quotient(tf = 1, floor_fn[term][j]); the best clause's bound
+    // is the query's.  Only where nothing removes documents behind the scorer's back: no deletions, no cursor, no fast-field order
+    // (those launches run the kernel's EXTRAS form, which never reads the floor).
+    static const uint32_t floor_ranks[BM25_FLOOR_NR] = BM25_FLOOR_RANKS;
+    int floor_j = -1;
+    if (!idx->floor_fn.empty() && seg.all_alive && !rq.after && rq.order_field < 0)
+        for (int j = 0; j < BM25_FLOOR_NR && floor_j < 0; j++)
+            if (floor_ranks[j] >= rq.kk) floor_j = j;
+    for (uint32_t q = 0; q < rq.nq && n_union; q++) {
+        if (!cx.w_q_union[q]) continue;
+        float q_floor = -INFINITY;
+        bool floor_ok = floor_j >= 0;
+        for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1] && floor_ok; c++) {
+            const Bm25ClauseDev &dc = dev_clauses[c];
+            if (dc.occur != 0 || (dc.mode != NIDX_TF_FREQ && dc.mode != 1) || !(dc.weight > 0.0f) || !(dc.weight < INFINITY)) floor_ok = false;
+        }
+        for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1] && floor_ok; c++) {
+            const uint8_t fn = idx->floor_fn[(size_t)clauses[c].term * BM25_FLOOR_NR + (size_t)floor_j];
+            if (fn != 255u) q_floor = std::max(q_floor, dev_clauses[c].weight * idx->quot1[fn]);
+        }
+        uint32_t floor_bits;
+        memcpy(&floor_bits, &q_floor, 4);
+        for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1]; c++) {
+            const uint64_t b = seg.term_offsets_host[clauses[c].term];
+            const uint64_t l = cx.w_clause_len[c];
+            if (l > 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "a posting list of one segment holds more than 2^32 - 1 postings");
+            ucl[c] = Bm25StreamClause{(uint32_t)b, (uint32_t)(b >> 32), (uint32_t)l, dev_clauses[c].weight,
+                                      (uint32_t)dev_clauses[c].occur | ((uint32_t)dev_clauses[c].mode << 8), floor_bits, 0u, 0u};
+        }
+    }
+    return NIDX_OK;
+}
+
+// What a segment's launches leave for the steps behind them.
+struct Bm25Launch {
+    Bm25ResultLayout out;   // of cx.h_outpack
+    DevBuf dbg;             // the kernels' counters of a NIDX_GPU_BM25_DEBUG run
+};
+
+// Staging and launch of one segment, all asynchronous: the pinned input block [clause block (one resident segment) | item_first | work
+// list | item list | stream clauses] in one transfer, the pinned result block, the pipelined aux stage's [begin, end) pairs, then the
+// scoring launches between the context's two events, the merge (unless the stream launch merges itself) and the facet counts.
+static int32_t bm25_stage_and_launch(const Bm25Index *idx, Bm25Ctx &cx, const Bm25Segment &seg, size_t s, const Bm25Request &rq, const Bm25Mode &mode,
+                                     Bm25ClauseBlock &cb, const Bm25AuxLayout &al, const Bm25WorkPlan &plan, Bm25TicketRun *tr, Bm25HostTrace &trace,
+                                     Bm25Launch &ln) {
+    const uint32_t nq = rq.nq, kk = rq.kk, n_aux = al.n_aux, n_slots = rq.n_slots;
+    const uint64_t n_clauses = rq.n_clauses;
+    const std::vector<Bm25StreamClause> &ucl = cx.w_ucl;
+    const size_t nw = cx.w_work.size();
+    trace.t_up0 = Bm25HostTrace::now();
+    NIDX_HIP(cx.s_key.reserve(nw * kk * 8));
+    const size_t if_bytes = ((size_t)(nq + 1) * 4 + 31) & ~(size_t)31;   // 32-byte pieces: the clause table is read with 16-byte scalar loads
+    const size_t work_bytes = (nw * sizeof(Bm25Work) + 31) & ~(size_t)31;
+    const size_t items_bytes = (nw * 4 + 31) & ~(size_t)31;
+    const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl.size() * sizeof(Bm25StreamClause);
+    const size_t w_at = cb.fused_in ? cb.inq_al : 0;   // the work list's place in the block: behind the clause block, or at its head
+    NIDX_HIP(cx.s_in_w.reserve(w_at + inw_bytes));
+    NIDX_HIP(cx.h_in_w.reserve(w_at + inw_bytes));
+    unsigned char *h_w = cx.h_in_w.as<unsigned char>() + w_at, *d_w = cx.s_in_w.as<unsigned char>() + w_at;
+    if (cb.fused_in) {
+        if (n_clauses) memcpy(cx.h_in_w.p, cx.w_dev_clauses.data(), n_clauses * sizeof(Bm25ClauseDev));
+        memcpy(cx.h_in_w.as<unsigned char>() + cb.cl_bytes, rq.clause_offsets, (size_t)(nq + 1) * 8);
+        cb.d_clauses = cx.s_in_w.as<Bm25ClauseDev>();
+        cb.d_clause_offsets = reinterpret_cast<const unsigned long long *>(cx.s_in_w.as<unsigned char>() + cb.cl_bytes);
+    }
+    memcpy(h_w, cx.w_item_first.data(), (size_t)(nq + 1) * 4);
+    memcpy(h_w + if_bytes, cx.w_work.data(), nw * sizeof(Bm25Work));
+    memcpy(h_w + if_bytes + work_bytes, cx.w_item_list.data(), nw * 4);
+    if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl.size() * sizeof(Bm25StreamClause));
+    NIDX_HIP(hipMemcpyAsync(cx.s_in_w.p, cx.h_in_w.p, w_at + inw_bytes, hipMemcpyHostToDevice, cx.stream));
+    const uint32_t *d_item_first = reinterpret_cast<const uint32_t *>(d_w);
+    const Bm25Work *d_work = reinterpret_cast<const Bm25Work *>(d_w + if_bytes);
+    const uint32_t *d_items = reinterpret_cast<const uint32_t *>(d_w + if_bytes + work_bytes);
+    // The merged hits are written by bm25_merge_kernel straight into the pinned result block (device-visible host memory: ~190 KB of
+    // fire-and-forget stores over PCIe per batch) instead of into HBM + a device-to-host transfer queued behind it: one dependent
+    // operation less per batch.  A pipelined batch with row sets: behind the result block what the wait's stats need.
+    const Bm25ResultLayout &out = ln.out = bm25_result_layout(nq, rq.k, idx->concatenated(), mode.pipe_aux ? rq.n_rows_d : 0u);
+    NIDX_HIP(cx.h_outpack.reserve(out.bytes));
+    void *dp = nullptr;
+    NIDX_HIP(hipHostGetDevicePointer(&dp, cx.h_outpack.p, 0));
+    unsigned char *d_out = static_cast<unsigned char *>(dp);
+    if (mode.pipe_aux) {
+        const unsigned char *d_a = cx.s_in_a.as<unsigned char>();
+        const bool stats = out.n_stat_rows != 0;
+        NIDX_HIP(launch_bm25_aux_ranges(reinterpret_cast<const unsigned long long *>(d_a), reinterpret_cast<const uint32_t *>(d_a + al.pa_count_of),
+                                        cx.s_set_counts.as<uint32_t>(), n_aux, cx.s_aux_off.as<unsigned long long>(), al.n_own,
+                                        stats ? reinterpret_cast<uint32_t *>(d_out + out.o_stats + 16) : nullptr,
+                                        stats ? cx.s_row_stats.as<unsigned long long>() : nullptr,
+                                        stats ? reinterpret_cast<unsigned long long *>(d_out + out.o_stats) : nullptr, cx.stream));
+        tr->aux_launches++;
+    }
+    NIDX_HIP(cx.s_count.reserve(nw * 4));
+    NIDX_HIP(cx.s_total.reserve(nw * 8));
+    NIDX_HIP(cx.s_postings.reserve(nw * 8));
+    const uint32_t match_words = (seg.n_docs + 31) / 32;
     if (n_slots) {
-        std::vector<unsigned long long> fc(n_pairs);
-        NIDX_HIP(hipMemcpy(fc.data(), cx.s_facet_counts.p, n_pairs * 8, hipMemcpyDeviceToHost));
-        for (uint64_t p = 0; p < n_pairs; p++) opt->out_facet_counts[p] = fc[p];
+        const uint64_t bytes = (uint64_t)n_slots * std::max<uint32_t>(match_words, 1) * 4;
+        if (bytes > (1ull << 30))
+            return fail(NIDX_ERR_UNSUPPORTED, "%u faceted queries over a %u-document segment need %llu bytes of match bitsets (limit 1 GiB): split the batch",
+                        n_slots, seg.n_docs, (unsigned long long)bytes);
+        NIDX_HIP(cx.s_match_bits.reserve(bytes));
+        NIDX_HIP(hipMemsetAsync(cx.s_match_bits.p, 0, bytes, cx.stream));
     }
-    const bool desc = opt->order_desc != 0;
-    const bool single_segment = idx->segs.size() == 1;
-    for (uint32_t q = 0; q < nq && k > 0 && !single_segment; q++) {
-        std::vector<Hit> &m = merged[q];
-        if (single_segment) {
-            // one segment: the device list is already in TopDocs order
-        } else if (order_field >= 0) {
+    trace.t_up1 = Bm25HostTrace::now();
+    Bm25Args a;
+    a.work = d_work;
+    a.n_docs = seg.n_docs;
+    a.term_offsets = seg.term_offsets.as<unsigned long long>();
+    a.doc_ids = seg.doc_ids.as<uint32_t>();
+    a.tfs = seg.tfs.as<uint32_t>();
+    a.fieldnorm_ids = seg.fieldnorm_ids.as<uint8_t>();
+    a.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
+    a.tf_cache = idx->tf_cache.as<float>();
+    a.clauses = cb.d_clauses;
+    a.clause_offsets = cb.d_clause_offsets;
+    a.after = rq.after ? cx.s_after.as<Bm25AfterDev>() : nullptr;
+    a.k = kk;
+    a.segment_ord = (uint32_t)s;
+    a.out_key = cx.s_key.as<unsigned long long>();
+    a.out_count = cx.s_count.as<uint32_t>();
+    a.out_total = cx.s_total.as<unsigned long long>();
+    a.out_postings = cx.s_postings.as<unsigned long long>();
+    a.aux_offsets = n_aux ? cx.s_aux_off.as<unsigned long long>() : nullptr;
+    a.aux_doc_ids = n_aux ? cx.s_aux_ids.as<uint32_t>() : nullptr;
+    a.aux_tfs = n_aux ? cx.s_aux_tfs.as<uint32_t>() : nullptr;
+    a.order_key = rq.order_field >= 0 ? seg.order_key[rq.order_field].as<uint32_t>() : nullptr;
+    a.order_desc = rq.opt->order_desc ? 1 : 0;
+    a.match_bits = n_slots ? cx.s_match_bits.as<uint32_t>() : nullptr;
+    a.match_slot = n_slots ? cx.s_match_slot.as<int>() : nullptr;
+    a.match_words = match_words;
+    a.uclauses = reinterpret_cast<const Bm25StreamClause *>(d_w + if_bytes + work_bytes + items_bytes);
+    a.dbg = nullptr;
+    if (mode.debug) {
+        NIDX_HIP(ln.dbg.alloc((16 + 8 * nw) * 8));
+        NIDX_HIP(hipMemsetAsync(ln.dbg.p, 0, (16 + 8 * nw) * 8, cx.stream));
+        a.dbg = ln.dbg.as<unsigned long long>();
+    }
+    Bm25MergeArgs mg;
+    mg.item_first = d_item_first;
+    mg.item_key = cx.s_key.as<unsigned long long>();
+    mg.item_count = cx.s_count.as<uint32_t>();
+    mg.item_total = cx.s_total.as<unsigned long long>();
+    mg.item_postings = cx.s_postings.as<unsigned long long>();
+    mg.k = kk;
+    mg.out_doc = reinterpret_cast<uint32_t *>(d_out + out.o_doc);
+    mg.out_score = reinterpret_cast<float *>(d_out + out.o_score);
+    mg.out_count = reinterpret_cast<uint32_t *>(d_out + out.o_count);
+    mg.out_total = reinterpret_cast<unsigned long long *>(d_out + out.o_total);
+    mg.out_postings = reinterpret_cast<unsigned long long *>(d_out + out.o_post);
+    if (out.cat) {
+        mg.seg_base = idx->d_seg_base.as<uint32_t>();
+        mg.n_seg = idx->n_segments;
+        mg.out_seg = reinterpret_cast<uint32_t *>(d_out + out.o_seg);
+    }
+    // When every item of the batch goes through the stream kernel and k <= 64, the scoring launch merges as well (Bm25FusedMerge): the last wave
+    // of every query's slices does what bm25_merge_kernel would do in a launch of its own.  NIDX_GPU_BM25_FUSED_MERGE=0 keeps the two launches.
+    bool fused_merge = plan.n_union == nw && nw > 0 && kk <= 64 && !a.dbg;
+    if (const char *fe = getenv("NIDX_GPU_BM25_FUSED_MERGE")) fused_merge = fused_merge && atoi(fe) != 0;
+    if (fused_merge) {
+        const size_t done_bytes = (size_t)nq * (BM25_FUSE_MAX_GROUPS + 1u) * 4;
+        if (cx.s_fuse_done.bytes < done_bytes) {
+            NIDX_HIP(cx.s_fuse_done.reserve(done_bytes));
+            NIDX_HIP(hipMemsetAsync(cx.s_fuse_done.p, 0, cx.s_fuse_done.bytes, cx.stream));
+        }
+        NIDX_HIP(cx.s_fuse_key.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * kk * 8));
+        NIDX_HIP(cx.s_fuse_count.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 4));
+        NIDX_HIP(cx.s_fuse_total.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 8));
+        NIDX_HIP(cx.s_fuse_postings.reserve((size_t)nq * BM25_FUSE_MAX_GROUPS * 8));
+        a.fm.done = cx.s_fuse_done.as<uint32_t>();
+        a.fm.g_key = cx.s_fuse_key.as<unsigned long long>();
+        a.fm.g_count = cx.s_fuse_count.as<uint32_t>();
+        a.fm.g_total = cx.s_fuse_total.as<unsigned long long>();
+        a.fm.g_postings = cx.s_fuse_postings.as<unsigned long long>();
+        a.fm.out_doc = mg.out_doc;
+        a.fm.out_score = mg.out_score;
+        a.fm.out_count = mg.out_count;
+        a.fm.out_total = mg.out_total;
+        a.fm.out_postings = mg.out_postings;
+        a.fm.seg_base = mg.seg_base;
+        a.fm.n_seg = mg.n_seg;
+        a.fm.out_seg = mg.out_seg;
+    }
+    NIDX_HIP(hipEventRecord(cx.ev0, cx.stream));
+    {
+        const bool extras = a.alive != nullptr || a.match_bits != nullptr || a.order_key != nullptr || a.after != nullptr;
+        NIDX_HIP(launch_bm25_stream(a, d_items, plan.n_union, extras, cx.stream));
+    }
+    NIDX_HIP(launch_bm25_search(a, d_items + plan.n_union, plan.n_fast, d_items + plan.n_union + plan.n_fast, plan.n_wide, plan.wide_max_clauses, cx.stream));
+    NIDX_HIP(hipEventRecord(cx.ev1, cx.stream));
+    if (!fused_merge) NIDX_HIP(launch_bm25_merge(mg, nq, cx.stream));
+    if (n_slots)
+        NIDX_HIP(launch_facet_count(seg.term_offsets.as<unsigned long long>(), seg.doc_ids.as<uint32_t>(), cx.s_pair_term.as<uint32_t>(),
+                                    cx.s_pair_slot.as<int>(), (uint32_t)rq.n_pairs, cx.s_match_bits.as<uint32_t>(), match_words,
+                                    cx.s_facet_counts.as<unsigned long long>(), cx.stream));
+    return NIDX_OK;
+}
+
+// The NIDX_GPU_BM25_DEBUG report of one segment's launches (reads the kernels' counters back).
+static int32_t bm25_debug_report(const unsigned long long *dbg, const std::vector<Bm25Work> &work, uint32_t n_union, float ms) {
+    const size_t nw = work.size();
+    unsigned long long d[9];
+    NIDX_HIP(hipMemcpy(d, dbg, 72, hipMemcpyDeviceToHost));
+    if (n_union) {
+        std::vector<unsigned long long> tr(8 * nw);
+        NIDX_HIP(hipMemcpy(tr.data(), dbg + 16, tr.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<std::pair<unsigned long long, uint32_t>> by;
+        for (uint32_t w = 0; w < nw; w++)
+            if (tr[8 * w]) by.push_back({tr[8 * w], w});
+        std::sort(by.begin(), by.end());
+        auto pct = [&by](double p) { return by.empty() ? 0ull : by[(size_t)(p * (by.size() - 1))].first; };
+        unsigned long long t_min = ~0ull, t_max = 0;
+        for (auto &e : by) {
+            const unsigned long long st = tr[8 * e.second + 3] & 0xffffffffull;
+            t_min = std::min(t_min, st);
+            t_max = std::max(t_max, st);
+        }
+        fprintf(stderr, "[bm25 dbg] union items %zu: cycles p10 %llu p50 %llu p90 %llu p99 %llu max %llu; entry clocks (low 32 bits) span %llu\n", by.size(),
+                pct(0.1), pct(0.5), pct(0.9), pct(0.99), pct(1.0), t_max - t_min);
+        {   // phase cycles per window by the number of slices of the item's query
+            const uint32_t edges[5] = {1, 2, 4, 16, 0xffffffffu};
+            for (int g = 0; g < 5; g++) {
+                unsigned long long n = 0, wins = 0, ld = 0, fi = 0, fn = 0, rs = 0, st = 0, po = 0;
+                for (auto &e : by) {
+                    const uint32_t w = e.second, ns = work[w].n_slices;
+                    if (ns > edges[g] || (g > 0 && ns <= edges[g - 1])) continue;
+                    n++, wins += tr[8 * w + 2] & 0xffffffffull, ld += tr[8 * w + 4], fi += tr[8 * w + 5], fn += tr[8 * w + 6], rs += tr[8 * w + 7], st += tr[8 * w + 1], po += tr[8 * w + 3] >> 32;
+                }
+                if (n) fprintf(stderr, "[bm25 dbg]   queries of <= %u slices: %llu items, %.1f windows and %.0f postings per item, setup %.0f; per window: load %.0f filter %.0f final %.0f resolve %.0f cycles\n",
+                               edges[g], n, (double)wins / n, (double)po / n, (double)st / n, (double)ld / wins, (double)fi / wins, (double)fn / wins, (double)rs / wins);
+            }
+        }
+        for (size_t i = by.size() >= 6 ? by.size() - 6 : 0; i < by.size(); i++) {
+            const uint32_t w = by[i].second;
+            fprintf(stderr, "[bm25 dbg]   slow item %u: %llu cycles (setup %llu; load %llu filter %llu final %llu resolve %llu), %llu windows, %llu inserts, %llu postings, query %u slice %u/%u\n", w, tr[8 * w],
+                    tr[8 * w + 1], tr[8 * w + 4], tr[8 * w + 5], tr[8 * w + 6], tr[8 * w + 7], tr[8 * w + 2] & 0xffffffffull, tr[8 * w + 2] >> 32, tr[8 * w + 3] >> 32, work[w].query, work[w].slice, work[w].n_slices);
+        }
+        for (size_t i = 0; i < std::min<size_t>(3, by.size()); i++) {
+            const uint32_t w = by[i].second;
+            fprintf(stderr, "[bm25 dbg]   fast item %u: %llu cycles (setup %llu; load %llu filter %llu final %llu resolve %llu), %llu windows, %llu inserts, %llu postings, query %u slice %u/%u\n", w, tr[8 * w],
+                    tr[8 * w + 1], tr[8 * w + 4], tr[8 * w + 5], tr[8 * w + 6], tr[8 * w + 7], tr[8 * w + 2] & 0xffffffffull, tr[8 * w + 2] >> 32, tr[8 * w + 3] >> 32, work[w].query, work[w].slice, work[w].n_slices);
+        }
+    }
+    fprintf(stderr, "[bm25 dbg] items=%llu windows=%llu (max %llu per item) cycles/item: setup=%llu load=%llu apply=%llu fold=%llu windows total=%llu; longest item (entry to exit) %llu cycles; kernel_ms=%.3f\n",
+            d[5], d[4], d[8], d[6] / (d[5] ? d[5] : 1), d[0] / (d[5] ? d[5] : 1), d[1] / (d[5] ? d[5] : 1), d[2] / (d[5] ? d[5] : 1), d[3] / (d[5] ? d[5] : 1), d[7], ms);
+    return NIDX_OK;
+}
+
+// The regions of a result block on the host.
+struct Bm25ResultView {
+    const uint32_t *doc, *count, *seg;   // (seg: concatenated layout only)
+    const float *score;
+    const unsigned long long *total, *post;
+    Bm25ResultView(const Bm25ResultLayout &l, const unsigned char *h_out)
+        : doc(reinterpret_cast<const uint32_t *>(h_out + l.o_doc)), count(reinterpret_cast<const uint32_t *>(h_out + l.o_count)),
+          seg(reinterpret_cast<const uint32_t *>(h_out + l.o_seg)), score(reinterpret_cast<const float *>(h_out + l.o_score)),
+          total(reinterpret_cast<const unsigned long long *>(h_out + l.o_total)), post(reinterpret_cast<const unsigned long long *>(h_out + l.o_post)) {}
+};
+
+// TopDocs::order_by_fast_field on the blocking path: the hits' scores are zero, out_value (may be NULL) gets their fast values.
+// fast == nullptr: the order is by score, out_value gets zeros.
+struct Bm25OrderValues {
+    int64_t *out_value;
+    const int64_t *fast;        // of the resident segment, by resident doc id
+    const uint32_t *seg_base;   // concatenated layout: the first resident doc of every opened segment
+};
+
+// The collect step of a single resident segment (bm25_search_locked and the wait of a ticket): the device list is the answer, already
+// in TopDocs order and — concatenated layout — already split into (segment, doc inside it) by the merge.  Totals are assigned: the
+// blocking path zeroed its outputs at entry, so this equals the sum over its one segment.
+static void bm25_collect_single(const Bm25ResultLayout &l, const unsigned char *h_out, uint32_t nq, uint32_t k, const Bm25Outputs &out,
+                                const Bm25OrderValues *order = nullptr) {
+    const Bm25ResultView h(l, h_out);
+    const uint32_t kk = l.kk;
+    for (uint32_t q = 0; q < nq; q++) {
+        if (out.total) out.total[q] = h.total[q];
+        if (out.postings) out.postings[q] = h.post[q];
+        const uint32_t n = k ? std::min<uint32_t>(h.count[q], k) : 0u;
+        out.count[q] = n;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t d = h.doc[(size_t)q * kk + i];
+            const uint64_t sg = l.cat ? h.seg[(size_t)q * kk + i] : 0u;
+            if (out.docaddr) out.docaddr[(size_t)q * k + i] = (sg << 32) | d;
+            if (out.score) out.score[(size_t)q * k + i] = order && order->fast ? 0.f : h.score[(size_t)q * kk + i];
+            if (order && order->out_value) order->out_value[(size_t)q * k + i] = order->fast ? order->fast[l.cat ? order->seg_base[sg] + d : d] : 0;
+        }
+    }
+}
+
+// Several resident segments: per segment the device already merged the slices; the host merges the segments' lists.
+struct Bm25Hit { float score; uint64_t docaddr; int64_t value; };
+static void bm25_gather_segment(const Bm25ResultLayout &l, const unsigned char *h_out, uint32_t nq, uint32_t k, size_t s, const int64_t *fast,
+                                const Bm25Outputs &out, std::vector<std::vector<Bm25Hit>> &merged) {
+    const Bm25ResultView h(l, h_out);
+    for (uint32_t q = 0; q < nq; q++) {
+        if (out.total) out.total[q] += h.total[q];
+        if (out.postings) out.postings[q] += h.post[q];
+        if (k == 0) continue;
+        for (uint32_t i = 0; i < h.count[q]; i++) {
+            const uint32_t d = h.doc[(size_t)q * l.kk + i];
+            if (fast) merged[q].push_back(Bm25Hit{0.f, ((uint64_t)s << 32) | d, fast[d]});
+            else merged[q].push_back(Bm25Hit{h.score[(size_t)q * l.kk + i], ((uint64_t)s << 32) | d, 0});
+        }
+    }
+}
+static void bm25_merge_segments(std::vector<std::vector<Bm25Hit>> &merged, const Bm25Request &rq, const Bm25Outputs &out) {
+    const uint32_t k = rq.k;
+    const bool desc = rq.opt->order_desc != 0;
+    for (uint32_t q = 0; q < rq.nq && k > 0; q++) {
+        std::vector<Bm25Hit> &m = merged[q];
+        if (rq.order_field >= 0) {
             // order_by_fast_field across segments: the fast value, then DocAddress asc
-            std::sort(m.begin(), m.end(), [desc](const Hit &x, const Hit &y) {
+            std::sort(m.begin(), m.end(), [desc](const Bm25Hit &x, const Bm25Hit &y) {
                 if (x.value != y.value) return desc ? x.value > y.value : x.value < y.value;
                 return x.docaddr < y.docaddr;
             });
         } else {
             // TopDocs order across segments: score desc (total order), DocAddress asc
-            std::sort(m.begin(), m.end(), [](const Hit &x, const Hit &y) {
+            std::sort(m.begin(), m.end(), [](const Bm25Hit &x, const Bm25Hit &y) {
                 int32_t kx = total_key(x.score), ky = total_key(y.score);
                 if (kx != ky) return kx > ky;
                 return x.docaddr < y.docaddr;
             });
         }
         uint32_t n = (uint32_t)std::min<size_t>(m.size(), k);
-        out_count[q] = n;
+        out.count[q] = n;
         for (uint32_t i = 0; i < n; i++) {
-            if (out_docaddr) out_docaddr[(size_t)q * k + i] = m[i].docaddr;
-            if (out_score) out_score[(size_t)q * k + i] = m[i].score;
-            if (opt->out_order_value) opt->out_order_value[(size_t)q * k + i] = m[i].value;
+            if (out.docaddr) out.docaddr[(size_t)q * k + i] = m[i].docaddr;
+            if (out.score) out.score[(size_t)q * k + i] = m[i].score;
+            if (rq.opt->out_order_value) rq.opt->out_order_value[(size_t)q * k + i] = m[i].value;
         }
     }
-    if (host_dbg)
-        fprintf(stderr, "[bm25 host] total=%.0f us: clauses=%.0f work list=%.0f sync wait=%.0f collect=%.0f merge=%.0f\n", now_us() - t_entry, t_begin - t_entry,
-                t_work, t_sync, t_collect, now_us() - t_merge0);
+}
+
+// The search itself, on the context `cx` (the caller owns it for the duration and holds idx->rw shared).  With `async_slot` set and a
+// request the pipeline covers it returns after the last asynchronous call (launches + the device-to-host transfer of the result block
+// are queued on the slot's stream).  With `tr` (nidx_gpu_bm25_search_submit_prefiltered) the pipeline also covers batches whose aux
+// lists are all term sets and row sets: their exact lengths then never reach the host — the work list is planned from estimates
+// (bm25_aux_plan.h), the [begin, end) pairs the scoring kernels read are written by bm25_aux_ranges_kernel.
+// Compile, decide, upload, then per resident segment: aux layout, aux stage, work plan, stream clauses, staging and launch, and —
+// the blocking path only — wait and collect; last the host merge of several segments.
+static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_slot, const nidx_gpu_bm25_clause_t *clauses, const uint64_t *clause_offsets,
+                                  uint32_t nq, const nidx_gpu_bm25_search_options_t *opt, uint64_t *out_docaddr, float *out_score,
+                                  uint32_t *out_count, uint64_t *out_total, uint64_t *out_postings, Bm25RowSets *rs = nullptr,
+                                  Bm25TicketRun *tr = nullptr) {
+    Bm25HostTrace trace;
+    trace.t_entry = Bm25HostTrace::now();
+    NIDX_HIP(hipSetDevice(idx->device));
+    const Bm25Outputs out{out_docaddr, out_score, out_count, out_total, out_postings};
+    Bm25Request rq;
+    rq.clauses = clauses, rq.clause_offsets = clause_offsets, rq.nq = nq, rq.opt = opt, rq.rs = rs;
+    if (int32_t rc = bm25_compile_request(idx, cx, rq, out)) return rc;
+    if (nq == 0) return NIDX_OK;
+    const Bm25Mode mode = bm25_decide_mode(idx, rq, async_slot, tr);
+    const Bm25PlanKnobs knobs = bm25_plan_knobs(idx, async_slot);
+    trace.on = mode.debug || getenv("NIDX_GPU_BM25_HOST_TRACE") != nullptr;
+    Bm25ClauseBlock cb;
+    if (int32_t rc = bm25_upload_request(idx, cx, rq, mode, cb)) return rc;
+    cx.kernel_ms = 0.f;
+    trace.t_begin = Bm25HostTrace::now();
+    Bm25AuxLayout al;
+    if (mode.pipelined) {
+        // One resident segment, and no stage on this path waits for the stream or reads from the device: the collect step runs in
+        // nidx_gpu_bm25_search_wait (the buffers are the slot's: swapped in by submit).
+        const Bm25Segment &seg = idx->segs[0];
+        if (int32_t rc = bm25_aux_layout(seg, 0, rq, al)) return rc;
+        if (mode.pipe_aux)
+            if (int32_t rc = bm25_aux_pipelined(cx, seg, 0, rq, al, tr)) return rc;
+        trace.t_seg0 = Bm25HostTrace::now();
+        const Bm25WorkPlan plan = bm25_plan_segment(idx, seg, rq, al, knobs, cx);
+        if (int32_t rc = bm25_stream_clauses(idx, seg, rq, plan.n_union, cx)) return rc;
+        trace.t_work = Bm25HostTrace::now() - trace.t_seg0;
+        Bm25Launch ln;
+        if (int32_t rc = bm25_stage_and_launch(idx, cx, seg, 0, rq, mode, cb, al, plan, tr, trace, ln)) return rc;
+        if (trace.on)
+            fprintf(stderr, "[bm25 host submit] total=%.0f us: clauses=%.0f set-up=%.0f work list=%.0f staging+upload=%.0f launches=%.0f\n",
+                    Bm25HostTrace::now() - trace.t_entry, trace.t_begin - trace.t_entry, trace.t_seg0 - trace.t_begin, trace.t_work, trace.t_up1 - trace.t_up0,
+                    Bm25HostTrace::now() - trace.t_up1);
+        async_slot->launched = true;
+        async_slot->nq = nq, async_slot->k = rq.k;
+        async_slot->out = ln.out;
+        async_slot->pf_stats = rs ? rs->stats : nidx_gpu_bm25_prefilter_search_stats_t{};
+        if (tr) tr->pipelined = true;
+        return NIDX_OK;
+    }
+    const bool single_segment = idx->segs.size() == 1;   // one segment: the device list is the answer, no host merge
+    std::vector<std::vector<Bm25Hit>> merged(single_segment ? 0 : nq);
+    for (size_t s = 0; s < idx->segs.size(); s++) {
+        const Bm25Segment &seg = idx->segs[s];
+        if (int32_t rc = bm25_aux_layout(seg, s, rq, al)) return rc;
+        if (al.n_aux)
+            if (int32_t rc = bm25_aux_blocking(idx, cx, seg, rq, al, tr)) return rc;
+        const double t_w0 = Bm25HostTrace::now();
+        const Bm25WorkPlan plan = bm25_plan_segment(idx, seg, rq, al, knobs, cx);
+        if (int32_t rc = bm25_stream_clauses(idx, seg, rq, plan.n_union, cx)) return rc;
+        trace.t_work += Bm25HostTrace::now() - t_w0;
+        Bm25Launch ln;
+        if (int32_t rc = bm25_stage_and_launch(idx, cx, seg, s, rq, mode, cb, al, plan, tr, trace, ln)) return rc;
+        const double t_s0 = Bm25HostTrace::now();
+        NIDX_HIP(hipStreamSynchronize(cx.stream));
+        if (tr) tr->syncs++;
+        const double t_c0 = Bm25HostTrace::now();
+        trace.t_sync += t_c0 - t_s0;
+        float ms = 0.f;
+        NIDX_HIP(hipEventElapsedTime(&ms, cx.ev0, cx.ev1));
+        cx.kernel_ms += ms;
+        if (mode.debug)
+            if (int32_t rc = bm25_debug_report(ln.dbg.as<unsigned long long>(), cx.w_work, plan.n_union, ms)) return rc;
+        const int64_t *fast = rq.order_field >= 0 ? seg.fast_host[rq.order_field].data() : nullptr;
+        if (single_segment) {
+            const Bm25OrderValues order{opt->out_order_value, fast, idx->seg_base.data()};
+            bm25_collect_single(ln.out, cx.h_outpack.as<unsigned char>(), nq, rq.k, out, &order);
+        } else {
+            bm25_gather_segment(ln.out, cx.h_outpack.as<unsigned char>(), nq, rq.k, s, fast, out, merged);
+        }
+        trace.t_collect += Bm25HostTrace::now() - t_c0;
+    }
+    const double t_merge0 = Bm25HostTrace::now();
+    if (rq.n_slots) {
+        std::vector<unsigned long long> fc(rq.n_pairs);
+        NIDX_HIP(hipMemcpy(fc.data(), cx.s_facet_counts.p, rq.n_pairs * 8, hipMemcpyDeviceToHost));
+        for (uint64_t p = 0; p < rq.n_pairs; p++) opt->out_facet_counts[p] = fc[p];
+    }
+    if (!single_segment) bm25_merge_segments(merged, rq, out);
+    if (trace.on)
+        fprintf(stderr, "[bm25 host] total=%.0f us: clauses=%.0f work list=%.0f sync wait=%.0f collect=%.0f merge=%.0f\n", Bm25HostTrace::now() - trace.t_entry,
+                trace.t_begin - trace.t_entry, trace.t_work, trace.t_sync, trace.t_collect, Bm25HostTrace::now() - t_merge0);
     return NIDX_OK;
 }
 
@@ -2945,7 +3020,7 @@ static int32_t bm25_submit_ticket(Bm25Index *idx, const nidx_gpu_bm25_clause_t *
         slot->r_docaddr.resize((size_t)nq * kk1), slot->r_score.resize((size_t)nq * kk1);
         slot->r_count.resize(nq), slot->r_total.resize(nq), slot->r_postings.resize(nq);
         slot->pf_stats = nidx_gpu_bm25_prefilter_search_stats_t{};
-        slot->n_stat_rows = 0;
+        slot->out = Bm25ResultLayout{};
         if (!rlock.owns_lock()) rlock.lock();
         rc = bm25_search_locked(idx, slot->cx, slot, clauses, clause_offsets, nq, opt, slot->r_docaddr.data(), slot->r_score.data(), slot->r_count.data(),
                                 slot->r_total.data(), slot->r_postings.data(), rs, tr);
@@ -3036,32 +3111,14 @@ static int32_t bm25_wait_ticket(Bm25Index *idx, uint64_t ticket, uint64_t *out_d
             idx->last_kernel_ms = ms;
         }
         const unsigned char *h_out = slot->cx.h_outpack.as<unsigned char>();
-        const uint32_t *h_doc = reinterpret_cast<const uint32_t *>(h_out + slot->o_doc);
-        const float *h_score = reinterpret_cast<const float *>(h_out + slot->o_score);
-        const uint32_t *h_count = reinterpret_cast<const uint32_t *>(h_out + slot->o_count);
-        const unsigned long long *h_total = reinterpret_cast<const unsigned long long *>(h_out + slot->o_total);
-        const unsigned long long *h_post = reinterpret_cast<const unsigned long long *>(h_out + slot->o_post);
-        const uint32_t kk = slot->kk;
-        const bool cat = slot->cat;   // (as it was at submit: the index may be in a later generation by now)
-        const uint32_t *h_seg = reinterpret_cast<const uint32_t *>(h_out + slot->o_seg);   // (concatenated layout only)
-        for (uint32_t q = 0; q < nq; q++) {   // one resident segment: the device list is the answer
-            if (out_total) out_total[q] = h_total[q];
-            if (out_postings) out_postings[q] = h_post[q];
-            const uint32_t n = k ? std::min<uint32_t>(h_count[q], k) : 0u;
-            out_count[q] = n;
-            for (uint32_t i = 0; i < n; i++) {
-                const uint64_t sg = cat ? h_seg[(size_t)q * kk + i] : 0u;   // (the merge kernel already split resident docs into segment, doc)
-                if (out_docaddr) out_docaddr[(size_t)q * k + i] = (sg << 32) | h_doc[(size_t)q * kk + i];
-                if (out_score) out_score[(size_t)q * k + i] = h_score[(size_t)q * kk + i];
-            }
-        }
+        bm25_collect_single(slot->out, h_out, nq, k, Bm25Outputs{out_docaddr, out_score, out_count, out_total, out_postings});
         if (stats_out) {
             *stats_out = slot->pf_stats;
-            if (slot->n_stat_rows) {   // what bm25_aux_ranges_kernel left behind the result block
-                const unsigned long long *h_row_stats = reinterpret_cast<const unsigned long long *>(h_out + slot->o_stats);
-                const uint32_t *h_rows = reinterpret_cast<const uint32_t *>(h_out + slot->o_stats + 16);
+            if (slot->out.n_stat_rows) {   // what bm25_aux_ranges_kernel left behind the result block
+                const unsigned long long *h_row_stats = reinterpret_cast<const unsigned long long *>(h_out + slot->out.o_stats);
+                const uint32_t *h_rows = reinterpret_cast<const uint32_t *>(h_out + slot->out.o_stats + 16);
                 stats_out->documents_visited = h_row_stats[0], stats_out->postings_written = h_row_stats[1];
-                for (uint32_t r = 0; r < slot->n_stat_rows; r++) stats_out->list_entries += h_rows[r];
+                for (uint32_t r = 0; r < slot->out.n_stat_rows; r++) stats_out->list_entries += h_rows[r];
             }
         }
         return NIDX_OK;

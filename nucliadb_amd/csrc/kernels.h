@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bm25_aux_plan.h"
+#include "bm25_work_plan.h"
 
 namespace nidx {
 
@@ -551,9 +552,6 @@ struct Bm25AfterDev {  // same layout as nidx_gpu_bm25_search_after_t
     int tie_break;
     unsigned long long docaddr;
 };
-struct Bm25Work {  // one work item: query `query`, doc-id slice `slice` of `n_slices`; its clause records [clause_first, + n_clauses)
-    uint32_t query, slice, n_slices, clause_first, n_clauses;
-};
 // bm25_stream_kernel's clause table (one record per query clause, per segment): the list's first posting, its length, the
 // Bm25Weight (or constant score), occur | mode << 8 and the query's score floor — everything the kernel needs of a clause without
 // touching term_offsets
@@ -565,9 +563,6 @@ struct Bm25StreamClause {
     uint32_t pad1, pad2;
 };
 #define BM25_ITEM_THREADS 64      /* threads per work item (64 = one wave: no block barriers) */
-#define BM25_SLICE_POSTINGS 2048  /* target postings per work item */
-#define BM25_SLICE_CROWDED 8192   /* ... of a union query when other batches are resident (bm25_index.cpp: crowded_shape) */
-#define BM25_MAX_SLICES 256
 // bm25_stream_kernel's fused merge (k <= 64, every item of the launch a stream item): the LAST wave to finish among a group of eight slices of
 // a query merges the group's lists, the last group to finish merges the groups' lists and writes what bm25_merge_kernel would have written —
 // no second launch behind the scoring kernel (3.4 us of every 30 us batch in the pipelined bench; DESIGN-LOG R6.8).  A wave merges at
@@ -639,7 +634,6 @@ struct Bm25MergeArgs {  // per query: merge the key lists of its work items [ite
     uint32_t *out_seg = nullptr;
 };
 hipError_t launch_bm25_merge(const Bm25MergeArgs &m, uint32_t n_queries, hipStream_t s);
-#define BM25_FAST_CLAUSES 8   /* queries of at most this many clauses take bm25_fast_kernel */
 #define BM25_LIST_PAD_BYTES 8192  /* slack behind the posting arrays: the kernels load whole 64-posting rows unconditionally */
 hipError_t launch_bm25_search(const Bm25Args &a, const uint32_t *fast_items, uint32_t n_fast, const uint32_t *wide_items, uint32_t n_wide,
                               uint32_t max_clauses, hipStream_t s);

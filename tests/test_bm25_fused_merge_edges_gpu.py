@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 S, M = _lib.OCCUR_SHOULD, _lib.OCCUR_MUST
 BASIC = _lib.TF_BASIC
 SLICE = 256        # NIDX_GPU_BM25_SLICE (bm25_index.cpp clamps it to >= 256)
-MAX_SLICES = 256   # kernels.h: BM25_MAX_SLICES
+MAX_SLICES = 256   # bm25_work_plan.h: BM25_MAX_SLICES
 GROUP = 8          # kernels.h: BM25_FUSE_GROUP
 
 N_DOCS = 66_560
@@ -39,7 +39,7 @@ WINNER_LEN = 20    # winners are 20 .. 31 tokens long, the other documents 33 ..
 
 def n_slices(list_lens, n_docs):
     """Slices of a plain query with these (distinct) terms' list lengths under NIDX_GPU_BM25_UNION=2 and NIDX_GPU_BM25_SLICE=256 — a restatement
-    of bm25_index.cpp, bm25_search_locked ("work list: every query cut into doc-id slices"): slices = min(BM25_MAX_SLICES, max(1, ceil(weigh(p,
+    of bm25_work_plan.h, bm25_plan_query ("every query is cut into doc-id slices"): slices = min(BM25_MAX_SLICES, max(1, ceil(weigh(p,
     longest) / slice_now))) with weigh(p, longest) = p while the slice is pinned (short_weight stays 1), then for a union query
     slices = min(BM25_MAX_SLICES, max(slices, want)), want = ceil(shared * 2 / 96), shared = (sum^2 - sum of squares) / 2 / n_docs."""
     p = int(sum(list_lens))
