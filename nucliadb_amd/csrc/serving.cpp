@@ -11,13 +11,27 @@
 //           n_queries x n_segments walks (hnsw_search_segments_kernel: the reference's index at 10 M vectors IS 50 segments,
 //           nidx/src/settings.rs:258-278), the other arms one launch each — merges them per query on the device (Fssc,
 //           fssc_device.hip) and returns.  When every searched segment takes the plain HNSW arm the kernels store the hits and
-//           one flag word per walk straight into the slot's pinned block (SearchSlot::host_block) and nothing follows them;
+//           one flag word per walk straight into the slot's pinned block (SlotBlock::host_block) and nothing follows them;
 //           otherwise ONE device-to-host transfer of [flag words | merged hits] is queued behind them;
 //   wait    blocks until the slot's event has passed and fills the caller's arrays; only when a segment's flags say a bounded
 //           on-chip structure overflowed it fetches the per-segment rows, re-runs that segment through the exact fallback
 //           (segment_search_exact) and merges on the host (the same Fssc, csrc/vector_index.cpp: fssc_merge).
 //
 // Results are those of nidx_gpu_vector_search for the same batch (tests/test_serving_gpu.py, tests/test_serving_host_block_gpu.py).
+//
+// How the file reads.  Where everything lies in a slot's result block, in a routed batch's upload and in the argument-table block, and
+// the decisions that depend on numbers alone (device merge, ticket budget, gate index) are serving_layout.h: no HIP, tested without a
+// device (tests/test_serving_layout_cpu.py).  The submit lays the block out once (SearchSlot::block), the waits read it.  Both submits
+// are a sequence of stages — hold, check, slot, stage, layout, turn, launches, merge, finish:
+//   shared            GenHold / GenRelease, read_switches, tickets_held, acquire_slot, reset_slot, stage_queries, reserve_block,
+//                     take_turn / finish_turn, reserve_tables / upload_tables, seg_rows, fssc_seg_record, queue_fssc, queue_final_copy
+//   pipeline_submit   choose_methods, upload_segment_filters, launch_segments (launch_segment_alone), launch_brute_force_group,
+//                     launch_rabitq_group, launch_walk_table
+//   pipeline_submit_routed   copy_request, pack_routed_input, reserve_routing_scratch, launch_prefiltered_filter_stage |
+//                     launch_filter_stage, launch_route_stage, fill_routed_tables, launch_walk_arm, launch_scan_arm
+//   pipeline_wait / routed_wait   copy_done_batch, repair_flagged_segments, copy_merged_hits, host_merge
+// The launch stages run under the index lock `mu`, which is held for launch calls only, never across a synchronisation; Pipeline::mu
+// is never held across a HIP wait.
 #include <pthread.h>
 #include <atomic>
 #include <condition_variable>
@@ -31,6 +45,7 @@
 
 #include "host_common.h"
 #include "prefilter_handover.h"
+#include "serving_layout.h"
 #include "vector_index.h"
 
 namespace nidx {
@@ -179,7 +194,7 @@ struct RoutedBatch {
     std::vector<uint32_t> filter_of_query;
     bool has_filter_of_query = false;
     // a prefiltered ticket (nidx_gpu_vector_search_submit_prefiltered_per_query_async): the caller's link and rows (kept alive by the
-    // caller until the wait returns), a copy of prefilter_of_filter, and where the projection's two counters sit in the block
+    // caller until the wait returns) and a copy of prefilter_of_filter
     bool prefiltered = false;
     const PrefilterLink *link = nullptr;
     const PrefilterRows *pf_rows = nullptr;
@@ -192,7 +207,6 @@ struct SearchSlot {
     // batches in flight share none of it
     bool routed = false;
     std::unique_ptr<RoutedBatch> rb;
-    size_t rw = 0;   // words of the routing region between the merged hits and the per-segment rows
     DevBuf d_rt_in, d_rt_table, d_rt_operands, d_rt_count, d_rt_lists, d_rt_queries, d_rt_rows, d_rt_compact;
     PinBuf pin_rt_in;
     bool busy = false, waiting = false;
@@ -204,10 +218,10 @@ struct SearchSlot {
     DevBuf d_bf_partial, d_bf_table;                 // brute-force segments of a one-launch batch: per-block lists, argument tables
     PinBuf pin_in, pin_out, pin_tables, pin_rq_table, pin_bf_table;
     bool dirty = false;                      // work may be queued on `stream` / the flag words may be set: clean before reuse
-    bool merged = false;                     // the block carries the device Fssc's hits
-    bool host_block = false;                 // the kernels of the batch wrote hits and flag rows into pin_out themselves (no copy follows them)
-    size_t flag_bytes = 0;                   // flag words at the head of d_block
-    size_t mw = 0;                           // words of the merged region behind them (0: the batch is merged on the host)
+    // where everything lies in d_block / pin_out for the batch in flight (serving_layout.h): laid out once by the submit
+    // (reserve_block), read by the wait.  block.merged: the block carries the device Fssc's hits; block.host_block: the kernels of
+    // the batch wrote hits and flag rows into pin_out themselves (no copy follows them)
+    SlotBlock block;
     // the batch in flight
     uint32_t nq = 0;
     nidx_gpu_vector_search_params_t params{};
@@ -215,6 +229,9 @@ struct SearchSlot {
     std::vector<int> method;                 // per segment; 0 = not searched (nothing can match)
     std::vector<const uint64_t *> d_seg_filter;
     std::atomic<bool> launched{false};   // (read by other submitters: are there batches on the device?)
+    // the rows of the block's segments as the kernels of the batch see them: in pin_out when the walks write a host block that the
+    // device does not merge, in d_block otherwise (a batch with a scan or a RaBitQ segment never has a host block: choose_methods)
+    uint32_t *row_base() const { return block.host_block && !block.merged ? pin_out.as<uint32_t>() : d_block.as<uint32_t>(); }
     ~SearchSlot() {
         if (stream) {
             (void)hipStreamSynchronize(stream);
@@ -234,7 +251,8 @@ struct Pipeline {
     // batch i wait (on the device, hipStreamWaitEvent) for the completion of batch i - walks.  Four or more 1 024-walk launches
     // oversubscribe the wave slots (3.5 M queries/s with three in flight, < 2 M with four: DESIGN 4.1) — but a batch that arrives as
     // HOST rows first spends ~0.1 ms in its upload, and with only `walks` tickets outstanding the device then runs one launch short
-    // for that long.  So: more tickets than walks; the uploads of the extra ones run ahead, their launches take their turn.
+    // for that long.  So: more tickets than walks; the uploads of the extra ones run ahead, their launches take their turn
+    // (take_turn / finish_turn).
     static constexpr uint32_t GATES = 32;
     uint32_t walks = 3;
     uint64_t launched = 0;            // batches whose launches were queued
@@ -269,13 +287,32 @@ void VectorIndex::pipeline_config(int32_t depth, int32_t walks) {
     if (walks >= 1) pipe->walks = (uint32_t)std::min(walks, 16);
 }
 
+// ---- the stages both submits share ---------------------------------------------------------------------------------------------------
+#define NIDX_TRY(expr)                          \
+    do {                                        \
+        const int32_t _rc = (expr);             \
+        if (_rc != NIDX_OK) return _rc;         \
+    } while (0)
+
+// The argument tables of the two table-driven kernels travel as one pinned block: [HnswSearchArgs x S | FsscSegDev x S]
+struct SlotTables {
+    TableBlock at;
+    HnswSearchArgs *hnsw = nullptr;   // the pinned records the submit fills
+    FsscSegDev *fssc = nullptr;
+    uint32_t n_hnsw = 0;              // (plain submit) walk records filled so far: the segments whose walks join the one grid
+};
+
 namespace {
-// result block of a slot: [flag word per segment, padded to 16 words][merged hits: nq*k segments | paragraphs | vectors | scores,
-// nq counts][per segment: nq*k vectors | nq*k scores | nq counts]; the host block of an all-HNSW batch (SearchSlot::host_block) has the
-// same layout, its flag words unused, and behind it [per segment: nq flag rows] (HnswSearchArgs::flag_rows)
-inline size_t flag_words(size_t S) { return (S + 15) / 16 * 16; }
-inline size_t merged_words(uint32_t nq, uint32_t k) { return (size_t)nq * k * 4 + nq; }
-inline size_t seg_words(uint32_t nq, uint32_t k) { return (size_t)nq * k * 2 + nq; }
+// A ticket's hold on the generation: taken by its submit (released there on every error path, handed to the ticket with g = nullptr)
+// and released by its wait (GenGate, vector_index.h)
+struct GenHold {
+    GenGate *g;
+    ~GenHold() { if (g) g->leave(); }
+};
+struct GenRelease {
+    GenGate &g;
+    ~GenRelease() { g.leave(); }
+};
 
 struct SlotRelease {   // hands the slot back on every exit path
     Pipeline &P;
@@ -286,7 +323,7 @@ struct SlotRelease {   // hands the slot back on every exit path
             // an error left the slot half way: nothing may still be queued that reads its staging, and the invariant "flag words are
             // zero while the slot is idle" is restored before anybody else takes it
             (void)hipStreamSynchronize(slot->stream);
-            if (slot->d_block.p) (void)hipMemsetAsync(slot->d_block.p, 0, std::min(slot->d_block.bytes, slot->flag_bytes), slot->stream);
+            if (slot->d_block.p) (void)hipMemsetAsync(slot->d_block.p, 0, std::min(slot->d_block.bytes, slot->block.fw * 4), slot->stream);
             (void)hipStreamSynchronize(slot->stream);
             slot->dirty = false;
         }
@@ -307,8 +344,420 @@ bool is_device_pointer(const void *p) {
     }
     return at.type == hipMemoryTypeDevice;
 }
+
+// The two comparison switches, read once per submit — not at open: the tests flip them on an open index
+struct Switches {
+    bool fssc_host;          // NIDX_GPU_FSSC_HOST: the segments' hits are merged on the host
+    bool segment_launches;   // NIDX_GPU_SEGMENT_LAUNCHES: a launch per segment
+};
+Switches read_switches() { return Switches{getenv("NIDX_GPU_FSSC_HOST") != nullptr, getenv("NIDX_GPU_SEGMENT_LAUNCHES") != nullptr}; }
+
+// the tickets that count against the budget of a submit (serving_layout.h: ticket_budget); under P.mu
+uint32_t tickets_held(const Pipeline &P, bool blocking) {
+    uint32_t busy = 0;
+    for (auto &s : P.slots) busy += s->busy ? 1u : 0u;
+    return tickets_counted(busy, (uint32_t)P.done.size(), blocking);
+}
+
+// A slot for a new ticket, under P.mu (`lk`): a blocking caller waits for room in its budget, a ticket submit is turned away; an idle
+// slot is taken, or a new one made
+int32_t acquire_slot(Pipeline &P, std::unique_lock<std::mutex> &lk, bool blocking, bool routed, SearchSlot *&slot) {
+    while (tickets_held(P, blocking) >= ticket_budget(P.depth, blocking)) {
+        if (!blocking) return fail(NIDX_ERR_BUSY, "all %u pipeline slots hold a ticket that has not been waited for", P.depth);
+        P.cv_free.wait(lk);
+    }
+    slot = nullptr;
+    for (auto &s : P.slots)
+        if (!s->busy) { slot = s.get(); break; }
+    if (!slot) {
+        std::unique_ptr<SearchSlot> ns(new SearchSlot());
+        NIDX_HIP(hipStreamCreateWithFlags(&ns->stream, hipStreamNonBlocking));
+        NIDX_HIP(hipEventCreateWithFlags(&ns->done, hipEventDisableTiming));
+        P.slots.push_back(std::move(ns));
+        slot = P.slots.back().get();
+    }
+    slot->busy = true;
+    slot->waiting = false;
+    slot->routed = routed;
+    slot->ticket = P.next_ticket++;
+    return NIDX_OK;
+}
+
+void reset_slot(SearchSlot &sl, uint32_t nq, const nidx_gpu_vector_search_params_t &p, size_t S) {
+    sl.nq = nq;
+    sl.params = p;
+    sl.method.assign(S, 0);
+    sl.d_seg_filter.assign(S, nullptr);
+    sl.launched = false;
+    sl.block = SlotBlock{};
+    sl.dq = nullptr;
+}
+
+// The result block of the batch; its flag words are zero whenever the slot is idle (a flagged batch clears them in wait), so they are
+// zeroed only when d_block grows.  From here on work is queued on the slot's stream: an error path must drain it (SlotRelease).
+// dev_rows: a kernel of the batch writes to d_block.
+// An all-HNSW batch (block.host_block): the rows pipeline_wait reads live in pin_out and the kernels get pointers into it — the walks'
+// final sort writes [vectors | scores | counts] and one flag row per walk there, or, when the device merges, Fssc writes the merged
+// block there and the per-segment rows stay on the device for it (they are fetched only for a flagged batch).  No copy follows the
+// last kernel.  pin_out is hipHostMalloc memory with the default flags: host memory mapped into the device's address space,
+// coherent and fine-grained, which the download kernel of the other route writes from the device as well.  The kernels only
+// store to it (plain stores, no atomic, nothing read back), the end of a kernel releases its stores to the system for such
+// memory, and the host reads the block only after hipEventSynchronize(sl.done), recorded behind the last kernel.
+int32_t reserve_block(SearchSlot &sl, const SlotBlock &block, bool dev_rows) {
+    sl.block = block;
+    sl.dirty = true;
+    if (dev_rows && block.words * 4 > sl.d_block.bytes) {
+        NIDX_HIP(sl.d_block.reserve(block.words * 4));
+        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, block.fw * 4, sl.stream));
+    }
+    NIDX_HIP(sl.pin_out.reserve(block.pinned_words() * 4));
+    return NIDX_OK;
+}
+
+// This batch's turn on the device (see Pipeline::walks): its launches queue behind the completion of the batch `walks` before it
+int32_t take_turn(Pipeline &P, SearchSlot &sl, uint64_t &seq) {
+    std::lock_guard<std::mutex> lk(P.mu);
+    seq = P.launched++;
+    if (waits_for_turn(seq, P.walks))
+        if (hipEvent_t before = P.gate[turn_gate(seq, P.walks, Pipeline::GATES)]) NIDX_HIP(hipStreamWaitEvent(sl.stream, before, 0));
+    return NIDX_OK;
+}
+// ... and its end: the slot's event for the wait, the gate for the batch `walks` behind it
+int32_t finish_turn(Pipeline &P, SearchSlot &sl, uint64_t seq) {
+    NIDX_HIP(hipEventRecord(sl.done, sl.stream));
+    {
+        std::lock_guard<std::mutex> lk(P.mu);
+        hipEvent_t &g = P.gate[own_gate(seq, Pipeline::GATES)];
+        if (!g) NIDX_HIP(hipEventCreateWithFlags(&g, hipEventDisableTiming));
+        NIDX_HIP(hipEventRecord(g, sl.stream));
+    }
+    sl.launched = true;
+    return NIDX_OK;
+}
+
+int32_t reserve_tables(SearchSlot &sl, size_t S, SlotTables &t) {
+    t.at = table_block(S, sizeof(HnswSearchArgs), sizeof(FsscSegDev));
+    NIDX_HIP(sl.pin_tables.reserve(t.at.bytes));
+    NIDX_HIP(sl.d_tables.reserve(t.at.bytes));
+    t.hnsw = sl.pin_tables.as<HnswSearchArgs>();
+    t.fssc = reinterpret_cast<FsscSegDev *>(sl.pin_tables.as<unsigned char>() + t.at.hnsw_bytes);
+    return NIDX_OK;
+}
+int32_t upload_tables(SearchSlot &sl, const SlotTables &t) {
+    NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, t.at.bytes, hipMemcpyHostToDevice, sl.stream));
+    return NIDX_OK;
+}
+
+// a segment's rows in the block that starts at `base`
+struct RowPtrs {
+    uint32_t *vec;
+    float *score;
+    uint32_t *count;
+};
+RowPtrs seg_rows(uint32_t *base, const SlotBlock &b, size_t s) {
+    const SlotBlock::Rows r = b.rows(s);
+    return RowPtrs{base + r.vec, reinterpret_cast<float *>(base + r.score), base + r.count};
+}
+
+// what Fssc needs of a segment and its rows; `searched` = false: nothing of the segment can match (no count row)
+FsscSegDev fssc_seg_record(const VectorSegment &seg, const RowPtrs &r, bool searched) {
+    return FsscSegDev{seg.vectors.as<float>(), seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>(),
+                      seg.key_ids.empty() ? nullptr : seg.key_ids_dev.as<unsigned long long>(), r.vec, searched ? r.count : nullptr, r.score, seg.dp, 0u};
+}
+
+// Fssc on the device: the hits a caller gets are k per query, whatever the number of segments.  Reads the uploaded Fssc records and
+// writes the merged region of the block that starts at `out_base`
+int32_t queue_fssc(SearchSlot &sl, const SlotTables &t, uint32_t n_searched, uint32_t dim, uint32_t *out_base) {
+    const SlotBlock &b = sl.block;
+    const SlotBlock::Merged m = b.merged_at();
+    FsscArgs f;
+    f.segs = reinterpret_cast<const FsscSegDev *>(sl.d_tables.as<unsigned char>() + t.at.hnsw_bytes);
+    f.n_segs = (uint32_t)b.S, f.nq = sl.nq, f.k = sl.params.k, f.dim = dim;
+    f.with_duplicates = sl.params.with_duplicates != 0;
+    f.offered = nullptr;
+    f.offered_stride = std::max<uint32_t>(n_searched, 1) * sl.params.k;
+    if (!f.with_duplicates) {
+        NIDX_HIP(sl.d_offered.reserve((size_t)sl.nq * f.offered_stride * 12));
+        f.offered = sl.d_offered.as<uint32_t>();
+    }
+    f.out_seg = out_base + m.seg;
+    f.out_para = out_base + m.para;
+    f.out_vec = out_base + m.vec;
+    f.out_score = reinterpret_cast<float *>(out_base + m.score);
+    f.out_count = out_base + m.count;
+    NIDX_HIP(launch_fssc_merge(f, sl.stream));
+    return NIDX_OK;
+}
+
+// ONE device-to-host transfer behind the last kernel (nothing for a host block)
+int32_t queue_final_copy(SearchSlot &sl) {
+    if (const size_t words = sl.block.copy_words()) NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, words * 4, hipMemcpyDeviceToHost, sl.stream));
+    return NIDX_OK;
+}
+
+// ---- what both waits share --------------------------------------------------------------------------------------------------------------
+// the device merged the segments: k hits per query in [segments | paragraphs | vectors | scores | counts]
+void copy_merged_hits(const uint32_t *host, const SlotBlock &b, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,
+                      float *out_score, uint32_t *out_count) {
+    const SlotBlock::Merged m = b.merged_at();
+    const uint32_t k = (uint32_t)b.k;
+    for (uint32_t q = 0; q < b.nq; q++) {
+        const uint32_t c = std::min(host[m.count + q], k);
+        out_count[q] = c;
+        const size_t at = (size_t)q * k;
+        if (out_segment) memcpy(out_segment + at, host + m.seg + at, (size_t)c * 4);
+        if (out_paragraph) memcpy(out_paragraph + at, host + m.para + at, (size_t)c * 4);
+        if (out_vector) memcpy(out_vector + at, host + m.vec + at, (size_t)c * 4);
+        if (out_score) memcpy(out_score + at, host + m.score + at, (size_t)c * 4);
+    }
+}
+
+// Fssc across the segments on the host (searcher.rs:149-199, 270-287), from the per-segment rows of the slot's pinned block;
+// searched(s): the segment has rows
+template <typename Searched>
+int32_t host_merge(VectorIndex &idx, const SearchSlot &sl, Searched searched, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,
+                   float *out_score, uint32_t *out_count) {
+    const SlotBlock &b = sl.block;
+    const uint32_t *host = sl.pin_out.as<uint32_t>();
+    std::vector<const uint32_t *> pv(b.S, nullptr), pc(b.S, nullptr);
+    std::vector<const float *> ps(b.S, nullptr);
+    for (size_t s = 0; s < b.S; s++) {
+        if (!searched(s)) continue;
+        const SlotBlock::Rows r = b.rows(s);
+        pv[s] = host + r.vec;
+        ps[s] = reinterpret_cast<const float *>(host + r.score);
+        pc[s] = host + r.count;
+    }
+    return idx.fssc_merge(sl.nq, sl.params, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
+}
 }  // namespace
 
+// queries: a device pointer is searched where it lies (the plain submit only); host rows go through the slot's pinned staging
+int32_t VectorIndex::stage_queries(SearchSlot &sl, const float *queries, uint32_t nq, bool device_pointer_allowed) {
+    const uint32_t d = cfg.dimension, dp = (d + 3u) & ~3u;
+    if (device_pointer_allowed && is_device_pointer(queries)) {
+        if ((d & 3u) || cfg.normalize_vectors)
+            return fail(NIDX_ERR_UNSUPPORTED, "device-resident queries need a dimension that is a multiple of 4 and an index that does not normalise its queries");
+        sl.dq = queries;
+        return NIDX_OK;
+    }
+    NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
+    stage_query_rows(queries, sl.pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
+    NIDX_HIP(sl.d_queries.reserve((size_t)nq * dp * 4));
+    NIDX_HIP(hipMemcpyAsync(sl.d_queries.p, sl.pin_in.p, (size_t)nq * dp * 4, hipMemcpyHostToDevice, sl.stream));
+    sl.dq = sl.d_queries.as<float>();
+    return NIDX_OK;
+}
+
+// ---- the stages of the plain submit ---------------------------------------------------------------------------------------------------
+// What every segment runs (OpenSegment::_search's routing): decided before the result block is laid out, because a batch whose
+// searched segments all run the plain HNSW walk gets its hits written straight into host memory (host_block).  method[s] stays 0
+// for a segment of which nothing can match
+int32_t VectorIndex::choose_methods(const nidx_gpu_vector_search_params_t &p, const uint64_t *const *segment_filters, std::vector<int> &method,
+                                    std::vector<uint64_t> &matching, bool &host_block) {
+    const size_t S = segs.size();
+    matching.assign(S, 0);
+    host_block = true;
+    std::lock_guard<std::mutex> lock(mu);   // (rabitq_enabled / use_hnsw read tunables)
+    for (size_t s = 0; s < S; s++) {
+        const VectorSegment &seg = segs[s];
+        const uint64_t *filt = segment_filters ? segment_filters[s] : nullptr;
+        // matching = |filter ∩ alive| (segment.rs:516-531)
+        matching[s] = filt ? popcount_filter((uint32_t)s, filt) : seg.alive_count;
+        if (matching[s] == 0 || seg.n == 0) continue;
+        int m = p.method;
+        if (m == NIDX_METHOD_AUTO) {
+            // OpenSegment::_search (segment.rs:506-513,535-555), like search_host
+            const bool rabitq = rabitq_enabled(seg);
+            const bool hnsw = seg.has_graph && use_hnsw(seg.n_paragraphs, matching[s], p.k, rabitq);
+            m = rabitq ? (hnsw ? NIDX_METHOD_RABITQ_HNSW : NIDX_METHOD_RABITQ_BRUTE_FORCE) : (hnsw ? NIDX_METHOD_HNSW : NIDX_METHOD_BRUTE_FORCE);
+        }
+        if ((m == NIDX_METHOD_HNSW || m == NIDX_METHOD_RABITQ_HNSW) && !seg.has_graph)
+            return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %zu has no HNSW graph", s);
+        method[s] = m;
+        if (m != NIDX_METHOD_HNSW) host_block = false;   // the other kernels keep device rows and the copy behind them
+    }
+    return NIDX_OK;
+}
+
+// per-segment filters (bitsets over paragraph addresses) -> the slot's d_filter
+int32_t VectorIndex::upload_segment_filters(SearchSlot &sl, const uint64_t *const *segment_filters) {
+    if (!segment_filters) return NIDX_OK;
+    const size_t S = segs.size();
+    size_t fwords = 0;
+    for (size_t s = 0; s < S; s++)
+        if (segment_filters[s]) fwords += (segs[s].n_paragraphs + 63) / 64;
+    NIDX_HIP(sl.d_filter.reserve(fwords * 8));
+    size_t at = 0;
+    for (size_t s = 0; s < S; s++) {
+        if (!segment_filters[s]) continue;
+        const size_t w = (segs[s].n_paragraphs + 63) / 64;
+        uint64_t *dst = sl.d_filter.as<uint64_t>() + at;
+        NIDX_HIP(hipMemcpyAsync(dst, segment_filters[s], w * 8, hipMemcpyHostToDevice, sl.stream));
+        sl.d_seg_filter[s] = dst;
+        at += w;
+    }
+    return NIDX_OK;
+}
+
+// RaBitQ is the reference's default arm of a Dot index with D % 64 == 0 (config.rs:170-173, segment.rs:506-513): the walks of
+// every such segment join ONE table-driven launch too (rabitq_hnsw_segments_kernel), their closest_up_nodes the plain
+// segments' grid in entry mode — while the visited bitsets of the launch (n_queries x vectors of those segments bits) stay under 4 GiB.
+// (a single RaBitQ segment takes the same path: its scratch is the slot's own, so batches in flight overlap — the per-segment
+// route stages through index-owned scratch, one batch at a time)
+bool VectorIndex::rabitq_group_fits(uint32_t nq) const {
+    uint64_t vis_words = 0;
+    for (const VectorSegment &seg : segs)
+        if (seg.has_quant) vis_words += (seg.n + 31u) / 32u;
+    return vis_words * 4ull * nq <= (4ull << 30);
+}
+
+// The segment loop (under mu): every segment's Fssc record; a walk of the plain HNSW arm joins the one grid (t.hnsw) or is launched
+// alone, RaBitQ walks and tile scans are collected for their group launches, everything else takes segment_search_device
+int32_t VectorIndex::launch_segments(SearchSlot &sl, const std::vector<uint64_t> &matching, bool one_launch, bool rq_one_launch, uint32_t walks,
+                                     SlotTables &t, uint32_t &n_searched, std::vector<uint32_t> &rq_segs, std::vector<uint32_t> &bf_segs) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const SlotBlock &b = sl.block;
+    const uint32_t nq = sl.nq, k = p.k;
+    uint32_t *blk = sl.d_block.as<uint32_t>(), *hblk = sl.pin_out.as<uint32_t>();
+    for (size_t s = 0; s < b.S; s++) {
+        const VectorSegment &seg = segs[s];
+        const RowPtrs r = seg_rows(sl.row_base(), b, s);
+        const int method = sl.method[s];
+        t.fssc[s] = fssc_seg_record(seg, r, method != 0);
+        if (!method) continue;   // nothing of it can match
+        n_searched++;
+        if (method == NIDX_METHOD_HNSW && (one_launch || b.host_block)) {
+            HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], r.vec, r.score,
+                                          r.count, nullptr, vis_for(walks), b.host_block ? nullptr : blk + s);
+            if (b.host_block) ha.flag_rows = hblk + b.flag_row(s);
+            if (one_launch) t.hnsw[t.n_hnsw++] = ha;   // its walks join the one grid (launch_walk_table)
+            else NIDX_HIP(launch_hnsw_search(ha, waves_per_query, sl.stream));
+            continue;
+        }
+        if (method == NIDX_METHOD_RABITQ_HNSW && rq_one_launch && seg.has_quant) {
+            rq_segs.push_back((uint32_t)s);   // launched together behind this loop
+            continue;
+        }
+        if (method == NIDX_METHOD_BRUTE_FORCE && one_launch && k <= NIDX_K_MAX && scan_takes_tile_kernel((uint32_t)s, nq, k, matching[s])) {
+            bf_segs.push_back((uint32_t)s);   // their scans share one launch, their merges another
+            continue;
+        }
+        NIDX_TRY(launch_segment_alone(sl, (uint32_t)s, method, matching[s]));
+    }
+    return NIDX_OK;
+}
+
+// one segment through the per-segment route, into its rows of the block (under mu)
+int32_t VectorIndex::launch_segment_alone(SearchSlot &sl, uint32_t s, int method, uint64_t matching) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const RowPtrs r = seg_rows(sl.row_base(), sl.block, s);
+    scan_matching_hint = matching;
+    const int32_t rc = segment_search_device(s, sl.dq, sl.nq, p.k, p.min_score, p.with_duplicates != 0, method, sl.d_seg_filter[s], r.vec, r.score, r.count,
+                                             nullptr, vis_for(sl.nq), sl.stream, sl.d_block.as<uint32_t>() + s);
+    scan_matching_hint = ~0ull;
+    return rc;
+}
+
+// Brute-force segments (a selective filter sends every segment of an index there, segment.rs:506-555): ONE launch scans
+// them all (blockIdx.z = segment), one more merges every segment's per-block lists.  The lists of the launch stay under
+// 2 GiB; past that (pages of hundreds of hits over dozens of large segments) the segments keep a launch pair each.  (under mu)
+int32_t VectorIndex::launch_brute_force_group(SearchSlot &sl, const std::vector<uint32_t> &bf_segs, const std::vector<uint64_t> &matching) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const uint32_t nq = sl.nq, k = p.k;
+    uint32_t nblk = 1;
+    for (uint32_t s : bf_segs) nblk = std::max(nblk, scan_num_blocks(segs[s].n));
+    const size_t per_seg = (size_t)nq * nblk * k * 8, n_bf = bf_segs.size();
+    if (per_seg * n_bf > ((size_t)2 << 30)) {
+        for (uint32_t s : bf_segs) NIDX_TRY(launch_segment_alone(sl, s, NIDX_METHOD_BRUTE_FORCE, matching[s]));
+        return NIDX_OK;
+    }
+    const size_t scan_tab = (n_bf * sizeof(ScanArgs) + 63) & ~(size_t)63, tab = scan_tab + n_bf * sizeof(ScanMergeTab);
+    NIDX_HIP(sl.d_bf_partial.reserve(per_seg * n_bf));
+    NIDX_HIP(sl.pin_bf_table.reserve(tab));
+    NIDX_HIP(sl.d_bf_table.reserve(tab));
+    ScanArgs *h_scan = sl.pin_bf_table.as<ScanArgs>();
+    ScanMergeTab *h_merge = reinterpret_cast<ScanMergeTab *>(sl.pin_bf_table.as<unsigned char>() + scan_tab);
+    for (size_t i = 0; i < n_bf; i++) {
+        const uint32_t s = bf_segs[i];
+        const RowPtrs r = seg_rows(sl.row_base(), sl.block, s);
+        ScanArgs a = scan_args(s, sl.dq, nq, k, p.min_score, sl.d_seg_filter[s]);
+        a.partial = reinterpret_cast<uint64_t *>(sl.d_bf_partial.as<unsigned char>() + per_seg * i);
+        a.qt = scan_query_tile(nq, a.dp, k);
+        h_scan[i] = a;
+        h_merge[i] = ScanMergeTab{a.partial, r.vec, r.score, r.count};
+    }
+    NIDX_HIP(hipMemcpyAsync(sl.d_bf_table.p, sl.pin_bf_table.p, tab, hipMemcpyHostToDevice, sl.stream));
+    NIDX_HIP(launch_scan_segments(sl.d_bf_table.as<ScanArgs>(), (uint32_t)n_bf, h_scan[0], nblk, sl.stream));
+    NIDX_HIP(launch_merge_topk_segments(reinterpret_cast<const ScanMergeTab *>(sl.d_bf_table.as<unsigned char>() + scan_tab), (uint32_t)n_bf, nq, nblk, k,
+                                        sl.stream));
+    return NIDX_OK;
+}
+
+// The RaBitQ walks of the batch in one launch (see rabitq_group_fits), and for each of their segments an entry-mode record of the
+// plain walks' grid (t.hnsw).  (under mu)
+int32_t VectorIndex::launch_rabitq_group(SearchSlot &sl, const std::vector<uint32_t> &rq_segs, uint32_t walks, SlotTables &t) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const uint32_t nq = sl.nq, k = p.k, dp = (cfg.dimension + 3u) & ~3u;
+    uint32_t *blk = sl.d_block.as<uint32_t>();
+    const uint32_t dim = segs[rq_segs[0]].dim, nw = dim / 64u, n_rq = (uint32_t)rq_segs.size();
+    // the queries' 4-bit codes and constants once per batch (they depend on the query alone)
+    const size_t qd_bytes = ((size_t)nq * sizeof(RabitqQueryDev) + 63) & ~(size_t)63;
+    NIDX_HIP(sl.d_rq.reserve(qd_bytes + (size_t)nq * 4 * nw * 8));
+    RabitqQueryDev *d_qd = sl.d_rq.as<RabitqQueryDev>();
+    uint64_t *d_planes = reinterpret_cast<uint64_t *>(sl.d_rq.as<unsigned char>() + qd_bytes);
+    NIDX_HIP(launch_rabitq_query(sl.dq, nq, dp, dim, d_qd, d_planes, sl.stream));
+    uint64_t vis_words = 0;
+    for (uint32_t s : rq_segs) vis_words += (segs[s].n + 31u) / 32u;
+    NIDX_HIP(sl.d_rq_vis.reserve((size_t)vis_words * 4 * nq));
+    NIDX_HIP(hipMemsetAsync(sl.d_rq_vis.p, 0, (size_t)vis_words * 4 * nq, sl.stream));
+    const uint32_t tie_stride = rabitq_tie_stride(std::min<uint32_t>(k * 100u, 2000u));   // (rabitq_hnsw_args: ef)
+    NIDX_HIP(sl.d_rq_ties.reserve((size_t)n_rq * nq * tie_stride * 8));
+    const size_t entry_words = (size_t)nq * k * 2 + nq;   // per segment: vectors | scores | counts
+    NIDX_HIP(sl.d_rq_entry.reserve((size_t)n_rq * entry_words * 4));
+    NIDX_HIP(sl.pin_rq_table.reserve((size_t)n_rq * sizeof(RabitqSearchArgs)));
+    NIDX_HIP(sl.d_rq_table.reserve((size_t)n_rq * sizeof(RabitqSearchArgs)));
+    RabitqSearchArgs *h_rq = sl.pin_rq_table.as<RabitqSearchArgs>();
+    uint64_t vis_at = 0;
+    for (uint32_t i = 0; i < n_rq; i++) {
+        const uint32_t s = rq_segs[i];
+        uint32_t *e_vec = sl.d_rq_entry.as<uint32_t>() + (size_t)i * entry_words;
+        float *e_score = reinterpret_cast<float *>(e_vec + (size_t)nq * k);
+        uint32_t *e_count = e_vec + (size_t)nq * k * 2;
+        RabitqSearchArgs r = rabitq_hnsw_args(s, sl.dq, nq, k, p.min_score, blk + s);
+        r.qd = d_qd;
+        r.planes = d_planes;
+        r.visited = sl.d_rq_vis.as<uint32_t>() + vis_at * nq;
+        vis_at += r.vis_words;
+        r.tie_stride = tie_stride;
+        r.tie_spill = rabitq_tie_spill_enabled() ? sl.d_rq_ties.as<uint64_t>() + (size_t)i * nq * tie_stride : nullptr;
+        r.out_vec = e_vec, r.out_score = e_score, r.out_count = e_count;
+        h_rq[i] = r;
+        // closest_up_nodes from the re-ranked entry points, on the raw query (search.rs:369-375): an entry-mode record of the grid
+        const RowPtrs rows = seg_rows(sl.row_base(), sl.block, s);
+        HnswSearchArgs ha = hnsw_args(s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], rows.vec, rows.score, rows.count,
+                                      nullptr, vis_for(walks), blk + s);
+        ha.entry_vec = e_vec, ha.entry_score = e_score, ha.entry_count = e_count;
+        t.hnsw[t.n_hnsw++] = ha;
+    }
+    NIDX_HIP(hipMemcpyAsync(sl.d_rq_table.p, sl.pin_rq_table.p, (size_t)n_rq * sizeof(RabitqSearchArgs), hipMemcpyHostToDevice, sl.stream));
+    NIDX_HIP(launch_rabitq_hnsw_segments(sl.d_rq_table.as<RabitqSearchArgs>(), n_rq, h_rq[0], sl.stream));
+    return NIDX_OK;
+}
+
+// The one grid of the batch's walks.  The tables go up only for a kernel of this batch that reads them: the table-driven walk or
+// Fssc.  (under mu)
+int32_t VectorIndex::launch_walk_table(SearchSlot &sl, const SlotTables &t) {
+    if (t.n_hnsw || sl.block.merged) NIDX_TRY(upload_tables(sl, t));
+    if (!t.n_hnsw) return NIDX_OK;
+    HnswSearchArgs a = t.hnsw[0];
+    a.seg_table = sl.d_tables.as<HnswSearchArgs>();
+    a.n_table = t.n_hnsw;
+    NIDX_HIP(launch_hnsw_search(a, waves_per_query, sl.stream));
+    return NIDX_OK;
+}
+
+// hold, check, slot, stage, layout, turn, launches, merge, finish
 int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                      const uint64_t *const *segment_filters, bool blocking, uint64_t *ticket_out) {
     Pipeline &P = *pipe;
@@ -317,48 +766,19 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
     if (blocking) gate.enter_nested();
     else if (!gate.try_enter())
         return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
-    struct GenHold {
-        GenGate *g;
-        ~GenHold() { if (g) g->leave(); }
-    } gen_hold{&gate};
-    const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    GenHold gen_hold{&gate};
+    const uint32_t k = p.k;
     const size_t S = segs.size();
     if (k > NIDX_K_MAX) return fail(NIDX_ERR_UNSUPPORTED, "result_per_page > %d is not supported (got %u)", NIDX_K_MAX, k);
     if (p.method < 0 || p.method > 6) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown search method %d", p.method);
     NIDX_HIP(hipSetDevice(device));
+    const Switches switches = read_switches();
 
     SearchSlot *slot = nullptr;
     bool crowded = false;
     {
         std::unique_lock<std::mutex> lk(P.mu);
-        for (;;) {
-            // `depth` bounds the tickets outstanding, also after it was lowered below the number of slots that exist
-            // A blocking search (nidx_gpu_vector_search of a multi-segment index) may take one of 4 slots beyond the budget: its caller
-            // may itself hold `depth` tickets it has not waited for yet and would otherwise wait here for a slot only it can free;
-            // the extra slots are held by blocking calls alone, which give them back by themselves.
-            // (a ticket submit also counts the per-query tickets whose hits wait in `done`: all kinds share the one budget)
-            uint32_t n_busy = blocking ? 0u : (uint32_t)P.done.size();
-            for (auto &s : P.slots) n_busy += s->busy ? 1u : 0u;
-            const uint32_t budget = blocking ? P.depth + 4u : P.depth;
-            if (n_busy < budget)
-                for (auto &s : P.slots)
-                    if (!s->busy) { slot = s.get(); break; }
-            if (slot) break;
-            if (n_busy < budget) {
-                std::unique_ptr<SearchSlot> ns(new SearchSlot());
-                NIDX_HIP(hipStreamCreateWithFlags(&ns->stream, hipStreamNonBlocking));
-                NIDX_HIP(hipEventCreateWithFlags(&ns->done, hipEventDisableTiming));
-                P.slots.push_back(std::move(ns));
-                slot = P.slots.back().get();
-                break;
-            }
-            if (!blocking)
-                return fail(NIDX_ERR_BUSY, "all %u pipeline slots hold a ticket that has not been waited for", P.depth);
-            P.cv_free.wait(lk);
-        }
-        slot->busy = true;
-        slot->waiting = false;
-        slot->ticket = P.next_ticket++;
+        NIDX_TRY(acquire_slot(P, lk, blocking, false, slot));
         // other batches still on the device?  (their launches + this one's oversubscribe the workgroup slots: VectorIndex::crowded_launch)
         // (asked only for the batches whose shape depends on it: small batches take the latency shape whatever else runs)
         if (nq > 256)
@@ -371,294 +791,59 @@ int32_t VectorIndex::pipeline_submit(const float *queries, uint32_t nq, const ni
     } crowded_scope(crowded);
     SlotRelease release{P, slot};
     SearchSlot &sl = *slot;
-    sl.nq = nq;
-    sl.params = p;
-    sl.method.assign(S, 0);
-    sl.d_seg_filter.assign(S, nullptr);
-    sl.launched = false;
-    sl.merged = false;
-    sl.host_block = false;
-    sl.dq = nullptr;
+    reset_slot(sl, nq, p, S);
     if (nq > 0 && k > 0 && S > 0) {
-        // ---- queries: a device pointer is searched where it lies; host rows go through the slot's pinned staging --------------
-        if (is_device_pointer(queries)) {
-            if ((d & 3u) || cfg.normalize_vectors)
-                return fail(NIDX_ERR_UNSUPPORTED, "device-resident queries need a dimension that is a multiple of 4 and an index that does not normalise its queries");
-            sl.dq = queries;
-        } else {
-            NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
-            float *qpad = sl.pin_in.as<float>();
-            stage_query_rows(queries, qpad, nq, d, dp, cfg.normalize_vectors);
-            NIDX_HIP(sl.d_queries.reserve((size_t)nq * dp * 4));
-            NIDX_HIP(hipMemcpyAsync(sl.d_queries.p, qpad, (size_t)nq * dp * 4, hipMemcpyHostToDevice, sl.stream));
-            sl.dq = sl.d_queries.as<float>();
-        }
-        // ---- what every segment runs (OpenSegment::_search's routing): decided before the result block is laid out, because a batch
-        // whose searched segments all run the plain HNSW walk gets its hits written straight into host memory ------------------------
-        std::vector<uint64_t> matching(S, 0);
-        bool host_block = true;
-        {
-            std::lock_guard<std::mutex> lock(mu);   // (rabitq_enabled / use_hnsw read tunables)
-            for (size_t s = 0; s < S; s++) {
-                const VectorSegment &seg = segs[s];
-                const uint64_t *filt = segment_filters ? segment_filters[s] : nullptr;
-                // matching = |filter ∩ alive| (segment.rs:516-531)
-                matching[s] = filt ? popcount_filter((uint32_t)s, filt) : seg.alive_count;
-                if (matching[s] == 0 || seg.n == 0) continue;
-                int method = p.method;
-                if (method == NIDX_METHOD_AUTO) {
-                    // OpenSegment::_search (segment.rs:506-513,535-555), like search_host
-                    const bool rabitq = rabitq_enabled(seg);
-                    const bool hnsw = seg.has_graph && use_hnsw(seg.n_paragraphs, matching[s], k, rabitq);
-                    method = rabitq ? (hnsw ? NIDX_METHOD_RABITQ_HNSW : NIDX_METHOD_RABITQ_BRUTE_FORCE)
-                                    : (hnsw ? NIDX_METHOD_HNSW : NIDX_METHOD_BRUTE_FORCE);
-                }
-                if ((method == NIDX_METHOD_HNSW || method == NIDX_METHOD_RABITQ_HNSW) && !seg.has_graph)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %zu has no HNSW graph", s);
-                sl.method[s] = method;
-                if (method != NIDX_METHOD_HNSW) host_block = false;   // the other kernels keep device rows and the copy behind them
-            }
-        }
-        sl.host_block = host_block;
-        // ---- result block; its flag words are zero whenever the slot is idle (a flagged batch clears them in wait) -------------
-        // One plain segment (no cross-segment paragraph keys): Fssc is the identity on a falling score list, which the host checks while it
-        // copies the row (fssc_merge's fast path) — a merge kernel would only add a launch that, with other batches in flight, waits for
-        // workgroup slots behind their walks (8 us alone, 60 us in the hybrid trace) for nothing.
-        // Fssc's `seen` set (with_duplicates = false, the default) compares a candidate with everything offered before it: on the device
-        // that is one wave scanning the offered list per candidate, O((segments x k)^2 / 64) dependent steps — fine at the 500 candidates
-        // of 50 segments x k = 10, seconds at nucliadb's page sizes (k up to 500).  Past 4 096 candidates per query the per-segment rows go
-        // to the host merge (a hash set there).
-        const bool big_dedup = p.with_duplicates == 0 && (uint64_t)S * k > 4096;
-        sl.merged = !(S == 1 && segs[0].key_ids.empty()) && !big_dedup && !getenv("NIDX_GPU_FSSC_HOST");   // the variable: merge on the host (comparison)
-        const size_t fw = flag_words(S), mw = sl.merged ? merged_words(nq, k) : 0, sw = seg_words(nq, k), words = fw + mw + S * sw;
-        sl.mw = mw;
-        sl.dirty = true;   // from here on work is queued on the slot's stream: an error path must drain it (SlotRelease)
-        sl.flag_bytes = fw * 4;
-        // An all-HNSW batch: the rows pipeline_wait reads live in pin_out and the kernels get pointers into it — the walks' final sort
-        // writes [vectors | scores | counts] and one flag row per walk there, or, when the device merges, Fssc writes the merged block
-        // there and the per-segment rows stay on the device for it (they are fetched only for a flagged batch).  No copy follows the
-        // last kernel.  pin_out is hipHostMalloc memory with the default flags: host memory mapped into the device's address space,
-        // coherent and fine-grained, which the download kernel of the other route writes from the device as well.  The kernels only
-        // store to it (plain stores, no atomic, nothing read back), the end of a kernel releases its stores to the system for such
-        // memory, and the host reads the block only after hipEventSynchronize(sl.done), recorded behind the last kernel.
-        const bool dev_rows = !host_block || sl.merged;
-        if (dev_rows && words * 4 > sl.d_block.bytes) {
-            NIDX_HIP(sl.d_block.reserve(words * 4));
-            NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
-        }
-        NIDX_HIP(sl.pin_out.reserve((words + (host_block ? S * (size_t)nq : 0)) * 4));
-        // ---- per-segment filters (bitsets over paragraph addresses) ------------------------------------------------------------
-        if (segment_filters) {
-            size_t fwords = 0;
-            for (size_t s = 0; s < S; s++)
-                if (segment_filters[s]) fwords += (segs[s].n_paragraphs + 63) / 64;
-            NIDX_HIP(sl.d_filter.reserve(fwords * 8));
-            size_t at = 0;
-            for (size_t s = 0; s < S; s++) {
-                if (!segment_filters[s]) continue;
-                const size_t w = (segs[s].n_paragraphs + 63) / 64;
-                uint64_t *dst = sl.d_filter.as<uint64_t>() + at;
-                NIDX_HIP(hipMemcpyAsync(dst, segment_filters[s], w * 8, hipMemcpyHostToDevice, sl.stream));
-                sl.d_seg_filter[s] = dst;
-                at += w;
-            }
-        }
-        // this batch's turn on the device (see Pipeline::walks): its launches queue behind the completion of the batch `walks` before it
-        uint64_t my_seq = 0;
-        {
-            std::lock_guard<std::mutex> lk(P.mu);
-            my_seq = P.launched++;
-            if (my_seq >= P.walks && P.gate[(my_seq - P.walks) % Pipeline::GATES])
-                NIDX_HIP(hipStreamWaitEvent(sl.stream, P.gate[(my_seq - P.walks) % Pipeline::GATES], 0));
-        }
-        uint32_t *blk = sl.d_block.as<uint32_t>(), *hblk = sl.pin_out.as<uint32_t>();
-        uint32_t *rows = dev_rows ? blk : hblk;   // where the per-segment rows go
-        // the argument tables of the two table-driven kernels travel as one pinned block: [HnswSearchArgs x S | FsscSegDev x S]
-        const size_t hnsw_tab_bytes = (S * sizeof(HnswSearchArgs) + 63) & ~(size_t)63, tab_bytes = hnsw_tab_bytes + S * sizeof(FsscSegDev);
-        NIDX_HIP(sl.pin_tables.reserve(tab_bytes));
-        NIDX_HIP(sl.d_tables.reserve(tab_bytes));
-        HnswSearchArgs *h_hnsw = sl.pin_tables.as<HnswSearchArgs>();
-        FsscSegDev *h_fssc = reinterpret_cast<FsscSegDev *>(sl.pin_tables.as<unsigned char>() + hnsw_tab_bytes);
-        uint32_t n_hnsw = 0, n_searched = 0;
-        const bool one_launch = S > 1 && !getenv("NIDX_GPU_SEGMENT_LAUNCHES");   // the variable: a launch per segment (comparison)
-        // RaBitQ is the reference's default arm of a Dot index with D % 64 == 0 (config.rs:170-173, segment.rs:506-513): the walks of
-        // every such segment join ONE table-driven launch too (rabitq_hnsw_segments_kernel), their closest_up_nodes the plain
-        // segments' grid in entry mode.  The visited bitsets of the launch (n_queries x vectors of those segments bits) stay under 4 GiB.
-        std::vector<uint32_t> rq_segs, bf_segs;
-        // (a single RaBitQ segment takes the same path: its scratch is the slot's own, so batches in flight overlap — the per-segment
-        // route stages through index-owned scratch, one batch at a time)
-        bool rq_one_launch = !getenv("NIDX_GPU_SEGMENT_LAUNCHES") && k <= NIDX_K_MAX;
-        if (rq_one_launch) {
-            uint64_t vis_words = 0;
-            for (size_t s = 0; s < S; s++)
-                if (segs[s].has_quant) vis_words += (segs[s].n + 31u) / 32u;
-            if (vis_words * 4ull * nq > (4ull << 30)) rq_one_launch = false;
-        }
+        NIDX_TRY(stage_queries(sl, queries, nq, true));
+        std::vector<uint64_t> matching;
+        bool host_block = false;
+        NIDX_TRY(choose_methods(p, segment_filters, sl.method, matching, host_block));
+        const bool merged = device_merges(S, !segs[0].key_ids.empty(), p.with_duplicates != 0, k, switches.fssc_host);
+        // (a host block that the device merges keeps its per-segment rows on the device, for Fssc)
+        NIDX_TRY(reserve_block(sl, slot_block(S, nq, k, merged, host_block, false, 0, false), !host_block || merged));
+        NIDX_TRY(upload_segment_filters(sl, segment_filters));
+        uint64_t seq = 0;
+        NIDX_TRY(take_turn(P, sl, seq));
+        SlotTables t;
+        NIDX_TRY(reserve_tables(sl, S, t));
+        uint32_t n_searched = 0;
+        const bool one_launch = S > 1 && !switches.segment_launches;
+        const bool rq_one_launch = !switches.segment_launches && k <= NIDX_K_MAX && rabitq_group_fits(nq);
         {
             // launches read index state (tunables, the scratch the scans stage through): under the index lock, which is held for
             // the launch calls only — never across a synchronisation
             std::lock_guard<std::mutex> lock(mu);
             const uint32_t walks = one_launch ? nq * (uint32_t)std::min<size_t>(S, 64) : nq;   // the launch shape follows the grid
-            for (size_t s = 0; s < S; s++) {
-                VectorSegment &seg = segs[s];
-                uint32_t *d_vec = rows + fw + mw + s * sw;
-                float *d_score = reinterpret_cast<float *>(d_vec + (size_t)nq * k);
-                uint32_t *d_count = d_vec + (size_t)nq * k * 2;
-                h_fssc[s] = FsscSegDev{seg.vectors.as<float>(), seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>(),
-                                       seg.key_ids.empty() ? nullptr : seg.key_ids_dev.as<unsigned long long>(), d_vec, nullptr, d_score, seg.dp, 0u};
-                const int method = sl.method[s];
-                if (!method) continue;   // nothing of it can match
-                h_fssc[s].count = d_count;
-                n_searched++;
-                if (method == NIDX_METHOD_HNSW && (one_launch || host_block)) {
-                    HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], d_vec, d_score,
-                                                  d_count, nullptr, vis_for(walks), host_block ? nullptr : blk + s);
-                    if (host_block) ha.flag_rows = hblk + words + s * (size_t)nq;
-                    if (one_launch) h_hnsw[n_hnsw++] = ha;   // its walks join the one grid below
-                    else NIDX_HIP(launch_hnsw_search(ha, waves_per_query, sl.stream));
-                    continue;
-                }
-                if (method == NIDX_METHOD_RABITQ_HNSW && rq_one_launch && seg.has_quant) {
-                    rq_segs.push_back((uint32_t)s);   // launched together behind this loop
-                    continue;
-                }
-                if (method == NIDX_METHOD_BRUTE_FORCE && one_launch && k <= NIDX_K_MAX && scan_takes_tile_kernel((uint32_t)s, nq, k, matching[s])) {
-                    bf_segs.push_back((uint32_t)s);   // their scans share one launch, their merges another
-                    continue;
-                }
-                scan_matching_hint = matching[s];
-                const int32_t rc = segment_search_device((uint32_t)s, sl.dq, nq, k, p.min_score, p.with_duplicates != 0, method, sl.d_seg_filter[s],
-                                                         d_vec, d_score, d_count, nullptr, vis_for(nq), sl.stream, blk + s);
-                scan_matching_hint = ~0ull;
-                if (rc != NIDX_OK) return rc;
-            }
-            if (!bf_segs.empty()) {
-                // Brute-force segments (a selective filter sends every segment of an index there, segment.rs:506-555): ONE launch scans
-                // them all (blockIdx.z = segment), one more merges every segment's per-block lists.  The lists of the launch stay under
-                // 2 GiB; past that (pages of hundreds of hits over dozens of large segments) the segments keep a launch pair each.
-                uint32_t nblk = 1;
-                for (uint32_t s : bf_segs) nblk = std::max(nblk, scan_num_blocks(segs[s].n));
-                const size_t per_seg = (size_t)nq * nblk * k * 8, n_bf = bf_segs.size();
-                if (per_seg * n_bf > ((size_t)2 << 30)) {
-                    for (uint32_t s : bf_segs) {
-                        uint32_t *d_vec = blk + fw + mw + (size_t)s * sw;
-                        scan_matching_hint = matching[s];
-                        const int32_t rc = segment_search_device(s, sl.dq, nq, k, p.min_score, p.with_duplicates != 0, NIDX_METHOD_BRUTE_FORCE, sl.d_seg_filter[s],
-                                                                 d_vec, reinterpret_cast<float *>(d_vec + (size_t)nq * k), d_vec + (size_t)nq * k * 2, nullptr,
-                                                                 vis_for(nq), sl.stream, blk + s);
-                        scan_matching_hint = ~0ull;
-                        if (rc != NIDX_OK) return rc;
-                    }
-                } else {
-                    const size_t scan_tab = (n_bf * sizeof(ScanArgs) + 63) & ~(size_t)63, tab = scan_tab + n_bf * sizeof(ScanMergeTab);
-                    NIDX_HIP(sl.d_bf_partial.reserve(per_seg * n_bf));
-                    NIDX_HIP(sl.pin_bf_table.reserve(tab));
-                    NIDX_HIP(sl.d_bf_table.reserve(tab));
-                    ScanArgs *h_scan = sl.pin_bf_table.as<ScanArgs>();
-                    ScanMergeTab *h_merge = reinterpret_cast<ScanMergeTab *>(sl.pin_bf_table.as<unsigned char>() + scan_tab);
-                    for (size_t i = 0; i < n_bf; i++) {
-                        const uint32_t s = bf_segs[i];
-                        uint32_t *d_vec = blk + fw + mw + (size_t)s * sw;
-                        ScanArgs a = scan_args(s, sl.dq, nq, k, p.min_score, sl.d_seg_filter[s]);
-                        a.partial = reinterpret_cast<uint64_t *>(sl.d_bf_partial.as<unsigned char>() + per_seg * i);
-                        a.qt = scan_query_tile(nq, a.dp, k);
-                        h_scan[i] = a;
-                        h_merge[i] = ScanMergeTab{a.partial, d_vec, reinterpret_cast<float *>(d_vec + (size_t)nq * k), d_vec + (size_t)nq * k * 2};
-                    }
-                    NIDX_HIP(hipMemcpyAsync(sl.d_bf_table.p, sl.pin_bf_table.p, tab, hipMemcpyHostToDevice, sl.stream));
-                    NIDX_HIP(launch_scan_segments(sl.d_bf_table.as<ScanArgs>(), (uint32_t)n_bf, h_scan[0], nblk, sl.stream));
-                    NIDX_HIP(launch_merge_topk_segments(reinterpret_cast<const ScanMergeTab *>(sl.d_bf_table.as<unsigned char>() + scan_tab), (uint32_t)n_bf, nq, nblk,
-                                                        k, sl.stream));
-                }
-            }
-            if (!rq_segs.empty()) {
-                const uint32_t dim = segs[rq_segs[0]].dim, nw = dim / 64u, n_rq = (uint32_t)rq_segs.size();
-                // the queries' 4-bit codes and constants once per batch (they depend on the query alone)
-                const size_t qd_bytes = ((size_t)nq * sizeof(RabitqQueryDev) + 63) & ~(size_t)63;
-                NIDX_HIP(sl.d_rq.reserve(qd_bytes + (size_t)nq * 4 * nw * 8));
-                RabitqQueryDev *d_qd = sl.d_rq.as<RabitqQueryDev>();
-                uint64_t *d_planes = reinterpret_cast<uint64_t *>(sl.d_rq.as<unsigned char>() + qd_bytes);
-                NIDX_HIP(launch_rabitq_query(sl.dq, nq, dp, dim, d_qd, d_planes, sl.stream));
-                uint64_t vis_words = 0;
-                for (uint32_t s : rq_segs) vis_words += (segs[s].n + 31u) / 32u;
-                NIDX_HIP(sl.d_rq_vis.reserve((size_t)vis_words * 4 * nq));
-                NIDX_HIP(hipMemsetAsync(sl.d_rq_vis.p, 0, (size_t)vis_words * 4 * nq, sl.stream));
-                const uint32_t tie_stride = rabitq_tie_stride(std::min<uint32_t>(k * 100u, 2000u));   // (rabitq_hnsw_args: ef)
-                NIDX_HIP(sl.d_rq_ties.reserve((size_t)n_rq * nq * tie_stride * 8));
-                const size_t entry_words = (size_t)nq * k * 2 + nq;   // per segment: vectors | scores | counts
-                NIDX_HIP(sl.d_rq_entry.reserve((size_t)n_rq * entry_words * 4));
-                NIDX_HIP(sl.pin_rq_table.reserve((size_t)n_rq * sizeof(RabitqSearchArgs)));
-                NIDX_HIP(sl.d_rq_table.reserve((size_t)n_rq * sizeof(RabitqSearchArgs)));
-                RabitqSearchArgs *h_rq = sl.pin_rq_table.as<RabitqSearchArgs>();
-                uint64_t vis_at = 0;
-                for (uint32_t i = 0; i < n_rq; i++) {
-                    const uint32_t s = rq_segs[i];
-                    uint32_t *e_vec = sl.d_rq_entry.as<uint32_t>() + (size_t)i * entry_words;
-                    float *e_score = reinterpret_cast<float *>(e_vec + (size_t)nq * k);
-                    uint32_t *e_count = e_vec + (size_t)nq * k * 2;
-                    RabitqSearchArgs r = rabitq_hnsw_args(s, sl.dq, nq, k, p.min_score, blk + s);
-                    r.qd = d_qd;
-                    r.planes = d_planes;
-                    r.visited = sl.d_rq_vis.as<uint32_t>() + vis_at * nq;
-                    vis_at += r.vis_words;
-                    r.tie_stride = tie_stride;
-                    r.tie_spill = rabitq_tie_spill_enabled() ? sl.d_rq_ties.as<uint64_t>() + (size_t)i * nq * tie_stride : nullptr;
-                    r.out_vec = e_vec, r.out_score = e_score, r.out_count = e_count;
-                    h_rq[i] = r;
-                    // closest_up_nodes from the re-ranked entry points, on the raw query (search.rs:369-375): an entry-mode record of the grid
-                    uint32_t *d_vec = blk + fw + mw + (size_t)s * sw;
-                    HnswSearchArgs ha = hnsw_args(s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, sl.d_seg_filter[s], d_vec,
-                                                  reinterpret_cast<float *>(d_vec + (size_t)nq * k), d_vec + (size_t)nq * k * 2, nullptr, vis_for(walks), blk + s);
-                    ha.entry_vec = e_vec, ha.entry_score = e_score, ha.entry_count = e_count;
-                    h_hnsw[n_hnsw++] = ha;
-                }
-                NIDX_HIP(hipMemcpyAsync(sl.d_rq_table.p, sl.pin_rq_table.p, (size_t)n_rq * sizeof(RabitqSearchArgs), hipMemcpyHostToDevice, sl.stream));
-                NIDX_HIP(launch_rabitq_hnsw_segments(sl.d_rq_table.as<RabitqSearchArgs>(), n_rq, h_rq[0], sl.stream));
-            }
-            // the tables go up only for a kernel of this batch that reads them: the table-driven walk or Fssc
-            if (n_hnsw || sl.merged) NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, tab_bytes, hipMemcpyHostToDevice, sl.stream));
-            if (n_hnsw) {
-                HnswSearchArgs a = h_hnsw[0];
-                a.seg_table = sl.d_tables.as<HnswSearchArgs>();
-                a.n_table = n_hnsw;
-                NIDX_HIP(launch_hnsw_search(a, waves_per_query, sl.stream));
-            }
+            std::vector<uint32_t> rq_segs, bf_segs;
+            NIDX_TRY(launch_segments(sl, matching, one_launch, rq_one_launch, walks, t, n_searched, rq_segs, bf_segs));
+            if (!bf_segs.empty()) NIDX_TRY(launch_brute_force_group(sl, bf_segs, matching));
+            if (!rq_segs.empty()) NIDX_TRY(launch_rabitq_group(sl, rq_segs, walks, t));
+            NIDX_TRY(launch_walk_table(sl, t));
         }
-        // ---- Fssc on the device: the hits a caller gets are k per query, whatever the number of segments -------------------------
-        if (sl.merged) {
-            FsscArgs f;
-            f.segs = reinterpret_cast<const FsscSegDev *>(sl.d_tables.as<unsigned char>() + hnsw_tab_bytes);
-            f.n_segs = (uint32_t)S, f.nq = nq, f.k = k, f.dim = d;
-            f.with_duplicates = p.with_duplicates != 0;
-            f.offered = nullptr;
-            f.offered_stride = std::max<uint32_t>(n_searched, 1) * k;
-            if (!f.with_duplicates) {
-                NIDX_HIP(sl.d_offered.reserve((size_t)nq * f.offered_stride * 12));
-                f.offered = sl.d_offered.as<uint32_t>();
-            }
-            f.out_seg = (host_block ? hblk : blk) + fw;
-            f.out_para = f.out_seg + (size_t)nq * k;
-            f.out_vec = f.out_para + (size_t)nq * k;
-            f.out_score = reinterpret_cast<float *>(f.out_vec + (size_t)nq * k);
-            f.out_count = f.out_vec + (size_t)nq * k * 2;
-            NIDX_HIP(launch_fssc_merge(f, sl.stream));
-            if (!host_block) NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, (fw + mw) * 4, hipMemcpyDeviceToHost, sl.stream));
-        } else if (!host_block) {
-            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, words * 4, hipMemcpyDeviceToHost, sl.stream));
-        }
-        NIDX_HIP(hipEventRecord(sl.done, sl.stream));
-        {
-            std::lock_guard<std::mutex> lk(P.mu);
-            hipEvent_t &g = P.gate[my_seq % Pipeline::GATES];
-            if (!g) NIDX_HIP(hipEventCreateWithFlags(&g, hipEventDisableTiming));
-            NIDX_HIP(hipEventRecord(g, sl.stream));
-        }
-        sl.launched = true;
+        if (merged) NIDX_TRY(queue_fssc(sl, t, n_searched, cfg.dimension, host_block ? sl.pin_out.as<uint32_t>() : sl.d_block.as<uint32_t>()));
+        NIDX_TRY(queue_final_copy(sl));
+        NIDX_TRY(finish_turn(P, sl, seq));
     }
     *ticket_out = sl.ticket;
     release.slot = nullptr;   // the ticket owns the slot until it is waited for
     gen_hold.g = nullptr;     // ... and its hold on the generation
     return NIDX_OK;
+}
+
+// the hits of a per-query ticket (pipeline_submit_per_query), searched when it was submitted
+static void copy_done_batch(const Pipeline::DoneBatch &db, size_t S, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector,
+                            float *out_score, uint32_t *out_count, uint32_t *n_retried_out, int32_t *out_method, uint64_t *out_matching) {
+    if (n_retried_out) *n_retried_out = 0;
+    // (the routing of these tickets stayed with their submit: nidx_gpu_vector_search_wait_routed reports none)
+    if (out_method) std::fill(out_method, out_method + (size_t)db.nq * S, 0);
+    if (out_matching) std::fill(out_matching, out_matching + (size_t)db.n_filters * S, 0);
+    for (uint32_t q = 0; q < db.nq; q++) {
+        const size_t at = (size_t)q * db.k, c = db.cnt[q];
+        out_count[q] = db.cnt[q];
+        if (out_segment) memcpy(out_segment + at, db.seg.data() + at, c * 4);
+        if (out_paragraph) memcpy(out_paragraph + at, db.par.data() + at, c * 4);
+        if (out_vector) memcpy(out_vector + at, db.vec.data() + at, c * 4);
+        if (out_score) memcpy(out_score + at, db.sc.data() + at, c * 4);
+    }
 }
 
 int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
@@ -676,19 +861,8 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
             }
         }
         if (db) {
-            struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};   // the ticket's hold (pipeline_submit_per_query)
-            if (n_retried_out) *n_retried_out = 0;
-            // (the routing of these tickets stayed with their submit: nidx_gpu_vector_search_wait_routed reports none)
-            if (out_method) std::fill(out_method, out_method + (size_t)db->nq * segs.size(), 0);
-            if (out_matching) std::fill(out_matching, out_matching + (size_t)db->n_filters * segs.size(), 0);
-            for (uint32_t q = 0; q < db->nq; q++) {
-                const size_t at = (size_t)q * db->k, c = db->cnt[q];
-                out_count[q] = db->cnt[q];
-                if (out_segment) memcpy(out_segment + at, db->seg.data() + at, c * 4);
-                if (out_paragraph) memcpy(out_paragraph + at, db->par.data() + at, c * 4);
-                if (out_vector) memcpy(out_vector + at, db->vec.data() + at, c * 4);
-                if (out_score) memcpy(out_score + at, db->sc.data() + at, c * 4);
-            }
+            GenRelease gen_release{gate};   // the ticket's hold (pipeline_submit_per_query)
+            copy_done_batch(*db, segs.size(), out_segment, out_paragraph, out_vector, out_score, out_count, n_retried_out, out_method, out_matching);
             return NIDX_OK;
         }
     }
@@ -699,7 +873,8 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
         if (!slot || slot->waiting) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown ticket %llu (a ticket is waited for once)", (unsigned long long)ticket);
         slot->waiting = true;
     }
-    struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};   // the ticket's hold, after the slot is back (declared first)
+    // the ticket's hold on the generation is released AFTER the slot is handed back: gen_release is declared first, so destroyed last
+    GenRelease gen_release{gate};
     SlotRelease release{P, slot};
     SearchSlot &sl = *slot;
     const uint32_t nq = sl.nq, k = sl.params.k;
@@ -712,79 +887,63 @@ int32_t VectorIndex::pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint3
     NIDX_HIP(hipSetDevice(device));
     NIDX_HIP(hipEventSynchronize(sl.done));   // (a failure leaves the slot dirty: SlotRelease drains its stream)
     if (sl.routed) return routed_wait(sl, out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching, n_retried_out);
-    const size_t fw = flag_words(S), mw = sl.mw, sw = seg_words(nq, k);
-    uint32_t *host = sl.pin_out.as<uint32_t>();
+    const SlotBlock &b = sl.block;
+    const uint32_t *host = sl.pin_out.as<uint32_t>();
     // per searched segment: did a walk raise a flag?  The copy route reads the device's flag word of the segment; the host block
     // carries one row per walk (written unconditionally, so a row of an earlier batch never shows through), ORed here
     std::vector<uint32_t> seg_flags(S, 0);
     bool flagged = false;
     for (size_t s = 0; s < S; s++) {
         if (!sl.method[s]) continue;
-        if (sl.host_block) {
-            const uint32_t *row = host + fw + mw + S * sw + s * (size_t)nq;
+        if (b.host_block) {
+            const uint32_t *row = host + b.flag_row(s);
             for (uint32_t q = 0; q < nq; q++) seg_flags[s] |= row[q];
         } else {
             seg_flags[s] = host[s];
         }
         if (seg_flags[s]) flagged = true;
     }
-    if (!flagged) {
-        sl.dirty = false;   // everything queued has completed and no flag word is set
-        if (k == 0) return NIDX_OK;
-        if (sl.merged) {
-            // the device merged the segments: k hits per query in [segments | paragraphs | vectors | scores | counts]
-            const uint32_t *m = host + fw, *cnt = m + (size_t)nq * k * 4;
-            for (uint32_t q = 0; q < nq; q++) {
-                const uint32_t c = std::min(cnt[q], k);
-                out_count[q] = c;
-                const size_t at = (size_t)q * k;
-                if (out_segment) memcpy(out_segment + at, m + at, (size_t)c * 4);
-                if (out_paragraph) memcpy(out_paragraph + at, m + (size_t)nq * k + at, (size_t)c * 4);
-                if (out_vector) memcpy(out_vector + at, m + (size_t)nq * k * 2 + at, (size_t)c * 4);
-                if (out_score) memcpy(out_score + at, m + (size_t)nq * k * 3 + at, (size_t)c * 4);
-            }
-            return NIDX_OK;
-        }
-    } else {
-        if (sl.merged) {
-            // the merged hits rest on a walk that overflowed: fetch the per-segment rows, repair, merge again on the host
-            NIDX_HIP(hipMemcpyAsync(host + fw + mw, sl.d_block.as<uint32_t>() + fw + mw, S * sw * 4, hipMemcpyDeviceToHost, sl.stream));
-            NIDX_HIP(hipStreamSynchronize(sl.stream));
-        }
-        for (size_t s = 0; s < S; s++) {
-            if (!seg_flags[s]) continue;
-            if (sl.method[s] != NIDX_METHOD_HNSW && sl.method[s] != NIDX_METHOD_RABITQ_HNSW) continue;
-            // a bounded on-chip structure overflowed for some query of this segment: the complete OpenSegment::search (larger visited
-            // table / HBM-resident walk for the flagged queries), synchronously, into the index's own block, then over the slot's rows
-            std::lock_guard<std::mutex> lock(mu);
-            const size_t bw = out_block_words(nq, k);
-            NIDX_HIP(scratch_out_block.reserve(bw * 4));
-            NIDX_HIP(pin_out.reserve(bw * 4));
-            uint32_t retried = 0;
-            const int32_t rc = segment_search_exact((uint32_t)s, sl.dq, nq, k, sl.params.min_score, sl.params.with_duplicates != 0, sl.method[s],
-                                                    sl.d_seg_filter[s], scratch_out_block.as<uint32_t>(), pin_out.as<uint32_t>(), sl.stream, &retried);
-            if (rc != NIDX_OK) return rc;
-            memcpy(host + fw + mw + s * sw, pin_out.p, sw * 4);
-            if (n_retried_out) *n_retried_out += retried;
-        }
-        if (!sl.host_block) {   // (the host block's flag rows are rewritten by the next batch: nothing to clear)
-            NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
-            NIDX_HIP(hipStreamSynchronize(sl.stream));
-        }
-        sl.dirty = false;
-    }
+    if (flagged) NIDX_TRY(repair_flagged_segments(sl, seg_flags, n_retried_out));
+    sl.dirty = false;   // everything queued has completed and no flag word is set
     if (k == 0) return NIDX_OK;
-    // Fssc across the segments (searcher.rs:149-199, 270-287)
-    std::vector<const uint32_t *> pv(S, nullptr), pc(S, nullptr);
-    std::vector<const float *> ps(S, nullptr);
-    for (size_t s = 0; s < S; s++) {
-        if (!sl.method[s]) continue;
-        const uint32_t *b = host + fw + mw + s * sw;
-        pv[s] = b;
-        ps[s] = reinterpret_cast<const float *>(b + (size_t)nq * k);
-        pc[s] = b + (size_t)nq * k * 2;
+    if (b.merged && !flagged) {
+        copy_merged_hits(host, b, out_segment, out_paragraph, out_vector, out_score, out_count);
+        return NIDX_OK;
     }
-    return fssc_merge(nq, sl.params, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
+    return host_merge(*this, sl, [&](size_t s) { return sl.method[s] != 0; }, out_segment, out_paragraph, out_vector, out_score, out_count);
+}
+
+// A walk of the batch raised a flag.  When the device merged, the merged hits rest on a walk that overflowed: fetch the per-segment
+// rows.  Then every flagged segment again through the exact fallback, over the slot's rows in pin_out (the host merges them), and the
+// flag words are zero again before anybody else takes the slot
+int32_t VectorIndex::repair_flagged_segments(SearchSlot &sl, const std::vector<uint32_t> &seg_flags, uint32_t *n_retried_out) {
+    const SlotBlock &b = sl.block;
+    const uint32_t nq = sl.nq, k = sl.params.k;
+    uint32_t *host = sl.pin_out.as<uint32_t>();
+    if (b.merged) {
+        NIDX_HIP(hipMemcpyAsync(host + b.rows_at(), sl.d_block.as<uint32_t>() + b.rows_at(), b.rows_words() * 4, hipMemcpyDeviceToHost, sl.stream));
+        NIDX_HIP(hipStreamSynchronize(sl.stream));
+    }
+    for (size_t s = 0; s < b.S; s++) {
+        if (!seg_flags[s]) continue;
+        if (sl.method[s] != NIDX_METHOD_HNSW && sl.method[s] != NIDX_METHOD_RABITQ_HNSW) continue;
+        // a bounded on-chip structure overflowed for some query of this segment: the complete OpenSegment::search (larger visited
+        // table / HBM-resident walk for the flagged queries), synchronously, into the index's own block, then over the slot's rows
+        std::lock_guard<std::mutex> lock(mu);
+        const size_t bw = out_block_words(nq, k);
+        NIDX_HIP(scratch_out_block.reserve(bw * 4));
+        NIDX_HIP(pin_out.reserve(bw * 4));
+        uint32_t retried = 0;
+        NIDX_TRY(segment_search_exact((uint32_t)s, sl.dq, nq, k, sl.params.min_score, sl.params.with_duplicates != 0, sl.method[s], sl.d_seg_filter[s],
+                                      scratch_out_block.as<uint32_t>(), pin_out.as<uint32_t>(), sl.stream, &retried));
+        memcpy(host + b.rows(s).vec, pin_out.p, b.sw * 4);
+        if (n_retried_out) *n_retried_out += retried;
+    }
+    if (!b.host_block) {   // (the host block's flag rows are rewritten by the next batch: nothing to clear)
+        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, b.fw * 4, sl.stream));
+        NIDX_HIP(hipStreamSynchronize(sl.stream));
+    }
+    return NIDX_OK;
 }
 
 // The per-query filtered batch through the ticket interface: the filters are evaluated and their counts read back once (the one
@@ -795,16 +954,12 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
     Pipeline &P = *pipe;
     uint64_t ticket = 0;
     if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
-    struct GenHold {
-        GenGate *g;
-        ~GenHold() { if (g) g->leave(); }
-    } gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
+    GenHold gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
     {
         // these tickets count against pipeline_depth like the others: a caller that never waits meets NIDX_ERR_BUSY
         std::lock_guard<std::mutex> lk(P.mu);
-        uint32_t held = (uint32_t)P.done.size();
-        for (auto &sl : P.slots) held += sl->busy ? 1u : 0u;
-        if (held >= P.depth) return fail(NIDX_ERR_BUSY, "%u tickets are outstanding (pipeline_depth)", held);
+        const uint32_t held = tickets_held(P, false);
+        if (held >= ticket_budget(P.depth, false)) return fail(NIDX_ERR_BUSY, "%u tickets are outstanding (pipeline_depth)", held);
         ticket = P.next_ticket++;
         P.done.emplace(ticket, nullptr);   // reserved: filled below, erased on failure
     }
@@ -832,328 +987,312 @@ int32_t VectorIndex::pipeline_submit_per_query(const float *queries, uint32_t nq
 // comparison against a constant of the segment (use_hnsw_threshold), so here the filters are evaluated on the slot's stream, route_kernel
 // decides from the counts in HBM and writes each arm's queries per segment, one table-driven launch walks the routed queries of every
 // segment, each segment's scan runs over its compact rows, Fssc merges on the device as in pipeline_submit and ONE transfer of
-// [flag words | merged hits | routing] is queued.  The block of a routed slot:
-//   [flag words][merged hits][routing: method nq*S | n_hnsw S | n_scan S | (pad to 8 bytes) | matching F*S u64][per segment rows]
+// [flag words | merged hits | routing] is queued (the block of a routed slot: serving_layout.h).
+
+// the ticket's copies: "programs are read before the call returns", and a flagged batch is searched again from them
+void VectorIndex::copy_request(RoutedBatch &rb, const RoutedPlan &plan, const float *queries, uint32_t nq, const nidx_gpu_filter_program_t *programs,
+                               uint32_t n_filters, const uint32_t *filter_of_query, const PrefilterSearch *pf) {
+    const size_t S = segs.size();
+    rb.n_filters = n_filters;
+    rb.filters = plan.layout.filters;
+    if (plan.nothing) return;
+    if (cfg.normalize_vectors) rb.rows.assign(queries, queries + (size_t)nq * cfg.dimension);
+    rb.has_filter_of_query = filter_of_query != nullptr;
+    if (filter_of_query) rb.filter_of_query.assign(filter_of_query, filter_of_query + nq);
+    rb.programs.resize((size_t)n_filters * S);
+    rb.ops.resize(rb.programs.size());
+    rb.lists.resize(rb.programs.size());
+    for (size_t i = 0; i < rb.programs.size(); i++) {
+        const nidx_gpu_filter_program_t &src = programs[i];
+        if (src.ops && src.n_ops) rb.ops[i].assign(src.ops, src.ops + src.n_ops);
+        if (src.lists && src.n_lists) rb.lists[i].assign(src.lists, src.lists + src.n_lists);
+        rb.programs[i] = src;
+        rb.programs[i].ops = rb.ops[i].empty() ? nullptr : rb.ops[i].data();
+        rb.programs[i].lists = rb.lists[i].empty() ? nullptr : rb.lists[i].data();
+    }
+    if (pf) {
+        rb.prefiltered = true;
+        rb.link = pf->link;
+        rb.pf_rows = pf->rows;
+        rb.has_prefilter_of_filter = pf->prefilter_of_filter != nullptr;
+        if (pf->prefilter_of_filter) rb.prefilter_of_filter.assign(pf->prefilter_of_filter, pf->prefilter_of_filter + n_filters);
+    }
+}
+
+// one upload of everything the filter stage and the routing read (RoutedInput, serving_layout.h); any_field / any_res: an operand of a
+// prefiltered batch has a field row / a resource row
+int32_t VectorIndex::pack_routed_input(SearchSlot &sl, const RoutedPlan &plan, const RoutedInput &in, const PrefilterSearch *pf, bool &any_field,
+                                       bool &any_res) {
+    const FilterLayout &L = plan.layout;
+    const size_t S = segs.size();
+    const uint32_t D = (uint32_t)L.pf_rows.size();
+    NIDX_HIP(sl.pin_rt_in.reserve(in.bytes));
+    NIDX_HIP(sl.d_rt_in.reserve(in.bytes));
+    unsigned char *h = sl.pin_rt_in.as<unsigned char>();
+    memcpy(h, plan.segs.data(), S * sizeof(RouteSegDev));
+    if (!L.prog.empty()) memcpy(h + in.at_prog, L.prog.data(), L.prog.size() * 4);
+    memcpy(h + in.at_foq, L.filter_of_query.data(), (size_t)sl.nq * 4);
+    if (!L.has_program.empty()) memcpy(h + in.at_has, L.has_program.data(), L.has_program.size());
+    if (pf) {
+        filter_stage_records(L, reinterpret_cast<FilterSegDev *>(h + in.at_fseg), reinterpret_cast<PrefilterProjSeg *>(h + in.at_pseg));
+        const uint64_t **hr = reinterpret_cast<const uint64_t **>(h + in.at_rows);
+        for (uint32_t j = 0; j < D; j++) {
+            any_res = pf->operand_rows(L.pf_rows[j], hr[j], hr[D + j]) || any_res;
+            any_field = any_field || hr[j];
+        }
+    }
+    NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in.bytes, hipMemcpyHostToDevice, sl.stream));
+    return NIDX_OK;
+}
+
 namespace {
-inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
+// the slot's scratch of the filter stage (table, operand rows, cleared counts) and the routing lists
+int32_t reserve_routing_scratch(SearchSlot &sl, const FilterLayout &L, size_t S) {
+    const size_t F = L.filters.size();
+    NIDX_HIP(sl.d_rt_table.reserve(std::max<size_t>(L.tab_words, 1) * 8));
+    NIDX_HIP(sl.d_rt_operands.reserve(std::max<size_t>(L.opnd_words, 1) * 8));
+    NIDX_HIP(sl.d_rt_count.reserve(std::max<size_t>(S * F, 1) * 8));
+    NIDX_HIP(hipMemsetAsync(sl.d_rt_count.p, 0, std::max<size_t>(S * F, 1) * 8, sl.stream));
+    NIDX_HIP(sl.d_rt_lists.reserve(S * (size_t)sl.nq * 3 * 4));
+    return NIDX_OK;
+}
+// the routing lists of a batch, [S][nq] each: the filter-table row every query tests, and each arm's queries
+struct RouteLists {
+    uint32_t *filter_row, *items_hnsw, *items_scan;
+};
+RouteLists route_lists(const SearchSlot &sl) {
+    const size_t n = sl.block.S * (size_t)sl.nq;
+    uint32_t *base = sl.d_rt_lists.as<uint32_t>();
+    return RouteLists{base, base + n, base + 2 * n};
+}
+const uint32_t *routed_programs(const SearchSlot &sl, const RoutedInput &in) {
+    return reinterpret_cast<const uint32_t *>(sl.d_rt_in.as<unsigned char>() + in.at_prog);
+}
 }  // namespace
 
+// The filters of a prefiltered batch on ALL segments (the table-driven form): every segment owns its operand region [D projected
+// rows | its list operands], so one memset, one projection (one more for resource rows), one scatter and one combine serve them all.
+// The per-segment rows are cleared here already, together with the projection's counters in front of them.  (under mu)
+int32_t VectorIndex::launch_prefiltered_filter_stage(SearchSlot &sl, const FilterLayout &L, const RoutedInput &in, const PrefilterSearch &pf, bool any_field,
+                                                     bool any_res, uint64_t &launches, uint64_t &filter_launches) {
+    const SlotBlock &b = sl.block;
+    const uint32_t S = (uint32_t)b.S, F = (uint32_t)L.filters.size(), D = (uint32_t)L.pf_rows.size();
+    uint32_t *blk = sl.d_block.as<uint32_t>();
+    const unsigned char *din = sl.d_rt_in.as<unsigned char>();
+    const uint32_t *dprog = routed_programs(sl, in);
+    unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(blk + b.at_pf);
+    NIDX_HIP(hipMemsetAsync(blk + b.at_pf, 0, (b.words - b.at_pf) * 4, sl.stream));
+    const uint32_t n_words = D ? (uint32_t)pf.rows->layout.words() : 0;
+    if (L.opnd_words) {
+        NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, L.opnd_words * 8, sl.stream));
+        filter_launches++;
+    }
+    const uint64_t *const *d_rows = reinterpret_cast<const uint64_t *const *>(din + in.at_rows);
+    const PrefilterProjSeg *d_pseg = reinterpret_cast<const PrefilterProjSeg *>(din + in.at_pseg);
+    if (any_field && n_words) {
+        NIDX_HIP(launch_prefilter_project(d_rows, D, n_words, pf.link->doc_off.as<uint32_t>(), pf.link->entries.as<uint2>(), d_pseg,
+                                          sl.d_rt_operands.as<uint64_t>(), d_counters, sl.stream));
+        pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
+        filter_launches++, launches++;
+    }
+    if (any_res && pf.rows->res_words) {   // the operands' resource rows, into the same operand rows: the fifth launch
+        NIDX_HIP(launch_prefilter_project_resources(d_rows + D, D, (uint32_t)pf.rows->res_words, pf.link->res_off.as<uint32_t>(),
+                                                    pf.link->res_ranges.as<PrefilterResRange>(), d_pseg, sl.d_rt_operands.as<uint64_t>(), d_counters,
+                                                    sl.stream));
+        pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
+        filter_launches++, launches++;
+    }
+    pf_ticket_stats[PT_ROWS].fetch_add(D, std::memory_order_relaxed);
+    const FilterSegDev *dseg = reinterpret_cast<const FilterSegDev *>(din + in.at_fseg);
+    NIDX_HIP(launch_filter_scatter_segments(dseg, S, dprog, L.max_work, sl.d_rt_operands.as<uint64_t>(), sl.stream));
+    NIDX_HIP(launch_filter_combine_segments(dseg, S, dprog, F, L.max_words, sl.d_rt_operands.as<uint64_t>(), sl.d_rt_table.as<uint64_t>(),
+                                            sl.d_rt_count.as<unsigned long long>(), sl.stream));
+    const uint32_t n = (L.max_work ? 1 : 0) + (F && L.max_words ? 1 : 0);
+    filter_launches += n, launches += n;
+    return NIDX_OK;
+}
+
+namespace {
+// routing: the counts stay where the combine launches left them; route_kernel writes every (query, segment)'s method, the matching
+// counts, the filter rows and each arm's queries
+int32_t launch_route_stage(SearchSlot &sl, const RoutedInput &in, uint32_t n_filters, uint64_t &launches) {
+    const SlotBlock &b = sl.block;
+    uint32_t *blk = sl.d_block.as<uint32_t>();
+    const unsigned char *din = sl.d_rt_in.as<unsigned char>();
+    const RouteLists lists = route_lists(sl);
+    RouteArgs ra;
+    ra.counts = sl.d_rt_count.as<unsigned long long>();
+    ra.filter_of_query = reinterpret_cast<const uint32_t *>(din + in.at_foq);
+    ra.has_program = din + in.at_has;
+    ra.segs = reinterpret_cast<const RouteSegDev *>(din);
+    ra.nq = sl.nq, ra.n_filters = n_filters, ra.n_segs = (uint32_t)b.S;
+    ra.method = sl.params.method;
+    ra.out_method = reinterpret_cast<int32_t *>(blk + b.at_method);
+    ra.out_matching = reinterpret_cast<unsigned long long *>(blk + b.at_match);
+    ra.filter_row = lists.filter_row;
+    ra.items_hnsw = lists.items_hnsw, ra.items_scan = lists.items_scan;
+    ra.n_hnsw = blk + b.at_nh, ra.n_scan = blk + b.at_ns;
+    NIDX_HIP(launch_route(ra, sl.stream));
+    launches++;
+    return NIDX_OK;
+}
+}  // namespace
+
+// Every segment's Fssc record and walk record, per-segment rows as pipeline_submit lays them out.  shape_seg: the first segment with a
+// graph (-1: none), whose record shapes the walk launch; nblk: the most scan blocks of a segment  (under mu)
+void VectorIndex::fill_routed_tables(SearchSlot &sl, const FilterLayout &L, SlotTables &t, uint32_t walks, uint32_t &n_searched, uint32_t &nblk,
+                                     int &shape_seg) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const RouteLists lists = route_lists(sl);
+    uint32_t *blk = sl.d_block.as<uint32_t>();
+    for (size_t s = 0; s < sl.block.S; s++) {
+        const VectorSegment &seg = segs[s];
+        const RowPtrs r = seg_rows(blk, sl.block, s);
+        t.fssc[s] = fssc_seg_record(seg, r, seg.n != 0);
+        if (seg.n) {
+            n_searched++;
+            nblk = std::max(nblk, scan_num_blocks(seg.n));
+        }
+        HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, sl.nq, walks, p.k, p.min_score, p.with_duplicates != 0, nullptr, r.vec, r.score, r.count, nullptr,
+                                      vis_for(walks), blk + s);
+        ha.filter_row = lists.filter_row + s * (size_t)sl.nq;
+        ha.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
+        ha.filter_words = (seg.n_paragraphs + 63) / 64;
+        t.hnsw[s] = ha;
+        if (shape_seg < 0 && seg.has_graph && seg.n) shape_seg = (int)s;
+    }
+}
+
+// the walk arm: every segment's routed queries in one launch  (under mu)
+int32_t VectorIndex::launch_walk_arm(SearchSlot &sl, const SlotTables &t, int shape_seg) {
+    HnswSearchArgs a = t.hnsw[shape_seg];
+    a.seg_table = sl.d_tables.as<HnswSearchArgs>();
+    a.n_table = (uint32_t)sl.block.S;
+    a.route_items = route_lists(sl).items_hnsw;
+    a.route_n_items = sl.d_block.as<uint32_t>() + sl.block.at_nh;
+    NIDX_HIP(launch_hnsw_search(a, waves_per_query, sl.stream));
+    return NIDX_OK;
+}
+
+// The scan arm: per segment gather -> register-tile scan with per-query rows -> merge -> scatter.  The compact rows, the per-block
+// lists (sized by nq) and the compact hits are the segments' one after the other  (under mu)
+int32_t VectorIndex::launch_scan_arm(SearchSlot &sl, const FilterLayout &L, uint32_t nblk, uint64_t &launches) {
+    const nidx_gpu_vector_search_params_t &p = sl.params;
+    const uint32_t nq = sl.nq, k = p.k, dp = (cfg.dimension + 3u) & ~3u;
+    const RouteLists lists = route_lists(sl);
+    uint32_t *blk = sl.d_block.as<uint32_t>();
+    NIDX_HIP(sl.d_rt_queries.reserve((size_t)nq * dp * 4));
+    NIDX_HIP(sl.d_rt_rows.reserve((size_t)nq * 4));
+    NIDX_HIP(sl.d_rt_compact.reserve(((size_t)nq * k * 2 + nq) * 4));
+    NIDX_HIP(sl.d_bf_partial.reserve((size_t)nq * nblk * k * 8));
+    uint32_t *c_vec = sl.d_rt_compact.as<uint32_t>();
+    float *c_score = reinterpret_cast<float *>(c_vec + (size_t)nq * k);
+    uint32_t *c_count = c_vec + (size_t)nq * k * 2;
+    for (size_t s = 0; s < sl.block.S; s++) {
+        const VectorSegment &seg = segs[s];
+        if (!seg.n) continue;
+        const RowPtrs r = seg_rows(blk, sl.block, s);
+        const uint32_t *items = lists.items_scan + s * (size_t)nq, *n_items = blk + sl.block.at_ns + s;
+        NIDX_HIP(launch_route_gather(sl.dq, items, n_items, lists.filter_row + s * (size_t)nq, nq, dp, sl.d_rt_queries.as<float>(),
+                                     sl.d_rt_rows.as<uint32_t>(), sl.stream));
+        ScanArgs a = scan_args((uint32_t)s, sl.d_rt_queries.as<float>(), nq, k, p.min_score, nullptr);
+        a.filter_row = sl.d_rt_rows.as<uint32_t>();
+        a.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
+        a.filter_words = (seg.n_paragraphs + 63) / 64;
+        a.partial = sl.d_bf_partial.as<uint64_t>();
+        const uint32_t sblk = scan_num_blocks(seg.n);
+        NIDX_HIP(launch_scan_routed(a, n_items, sblk, sl.stream));
+        NIDX_HIP(launch_merge_topk_routed(a.partial, n_items, nq, sblk, k, c_vec, c_score, c_count, sl.stream));
+        NIDX_HIP(launch_route_scatter(c_vec, c_score, c_count, items, n_items, nq, k, r.vec, r.score, r.count, sl.stream));
+        launches += 4;
+    }
+    return NIDX_OK;
+}
+
+// hold, check, slot, stage, layout, turn, launches, merge, finish
 int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, const nidx_gpu_vector_search_params_t &p,
                                             const nidx_gpu_filter_program_t *programs, uint32_t n_filters, const uint32_t *filter_of_query,
                                             uint64_t *ticket_out, PrefilterSearch *pf) {
     Pipeline &P = *pipe;
     if (!gate.try_enter()) return fail(NIDX_ERR_BUSY, "a sync of the index is pending: wait for the outstanding tickets, then submit again");
-    struct GenHold {
-        GenGate *g;
-        ~GenHold() { if (g) g->leave(); }
-    } gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
+    GenHold gen_hold{&gate};   // the ticket's hold on the generation, released by pipeline_wait
     RoutedPlan plan;
-    int32_t rc = routed_plan(nq, p, programs, n_filters, filter_of_query, plan, pf);
-    if (rc != NIDX_OK) return rc;
+    NIDX_TRY(routed_plan(nq, p, programs, n_filters, filter_of_query, plan, pf));
     if (plan.fallback) {
         gate.leave();   // (pipeline_submit_per_query takes its own hold)
         gen_hold.g = nullptr;
-        rc = pipeline_submit_per_query(queries, nq, p, programs, n_filters, filter_of_query, ticket_out, pf);
+        const int32_t rc = pipeline_submit_per_query(queries, nq, p, programs, n_filters, filter_of_query, ticket_out, pf);
         if (rc == NIDX_OK) routed_stats[RS_FALLBACK].fetch_add(1, std::memory_order_relaxed);
         if (rc == NIDX_OK && pf) pf_ticket_stats[PT_FALLBACK].fetch_add(1, std::memory_order_relaxed);
         return rc;
     }
-    const uint32_t k = p.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const uint32_t k = p.k;
     const size_t S = segs.size();
     const FilterLayout &L = plan.layout;
     const uint32_t F = (uint32_t)L.filters.size();
     NIDX_HIP(hipSetDevice(device));
+    const Switches switches = read_switches();
 
     SearchSlot *slot = nullptr;
     {
-        std::lock_guard<std::mutex> lk(P.mu);
-        uint32_t n_busy = (uint32_t)P.done.size();
-        for (auto &s : P.slots) n_busy += s->busy ? 1u : 0u;
-        if (n_busy >= P.depth) return fail(NIDX_ERR_BUSY, "all %u pipeline slots hold a ticket that has not been waited for", P.depth);
-        for (auto &s : P.slots)
-            if (!s->busy) { slot = s.get(); break; }
-        if (!slot) {
-            std::unique_ptr<SearchSlot> ns(new SearchSlot());
-            NIDX_HIP(hipStreamCreateWithFlags(&ns->stream, hipStreamNonBlocking));
-            NIDX_HIP(hipEventCreateWithFlags(&ns->done, hipEventDisableTiming));
-            P.slots.push_back(std::move(ns));
-            slot = P.slots.back().get();
-        }
-        slot->busy = true;
-        slot->waiting = false;
-        slot->routed = true;
-        slot->ticket = P.next_ticket++;
+        std::unique_lock<std::mutex> lk(P.mu);
+        NIDX_TRY(acquire_slot(P, lk, false, true, slot));
     }
     // (No crowded launch shape here, whatever else is on the device: its 2^12 visited table flags more walks, and one flagged walk costs
     // a routed batch the blocking search of all its queries — measured 38 k against 69 k queries/s)
     SlotRelease release{P, slot};
     SearchSlot &sl = *slot;
-    sl.nq = nq;
-    sl.params = p;
-    sl.method.assign(S, 0);
-    sl.d_seg_filter.assign(S, nullptr);
-    sl.launched = false;
-    sl.merged = false;
-    sl.host_block = false;
-    sl.dq = nullptr;
-    sl.rw = 0;
-    // ---- the ticket's copies: "programs are read before the call returns", and a flagged batch is searched again from them ----
+    reset_slot(sl, nq, p, S);
     sl.rb.reset(new RoutedBatch());
-    RoutedBatch &rb = *sl.rb;
-    rb.n_filters = n_filters;
-    rb.filters = L.filters;
-    if (!plan.nothing) {
-        if (cfg.normalize_vectors) rb.rows.assign(queries, queries + (size_t)nq * d);
-        rb.has_filter_of_query = filter_of_query != nullptr;
-        if (filter_of_query) rb.filter_of_query.assign(filter_of_query, filter_of_query + nq);
-        rb.programs.resize((size_t)n_filters * S);
-        rb.ops.resize(rb.programs.size());
-        rb.lists.resize(rb.programs.size());
-        for (size_t i = 0; i < rb.programs.size(); i++) {
-            const nidx_gpu_filter_program_t &src = programs[i];
-            if (src.ops && src.n_ops) rb.ops[i].assign(src.ops, src.ops + src.n_ops);
-            if (src.lists && src.n_lists) rb.lists[i].assign(src.lists, src.lists + src.n_lists);
-            rb.programs[i] = src;
-            rb.programs[i].ops = rb.ops[i].empty() ? nullptr : rb.ops[i].data();
-            rb.programs[i].lists = rb.lists[i].empty() ? nullptr : rb.lists[i].data();
-        }
-        if (pf) {
-            rb.prefiltered = true;
-            rb.link = pf->link;
-            rb.pf_rows = pf->rows;
-            rb.has_prefilter_of_filter = pf->prefilter_of_filter != nullptr;
-            if (pf->prefilter_of_filter) rb.prefilter_of_filter.assign(pf->prefilter_of_filter, pf->prefilter_of_filter + n_filters);
-        }
-    }
+    copy_request(*sl.rb, plan, queries, nq, programs, n_filters, filter_of_query, pf);
     uint64_t launches = 0, filter_launches = 0;
-    const uint32_t D = (uint32_t)L.pf_rows.size();
-    bool any_field = false, any_res = false;   // an operand of the batch has a field row / a resource row
     if (!plan.nothing) {
-        // ---- queries -> HBM through the slot's pinned staging ----
-        NIDX_HIP(sl.pin_in.reserve((size_t)nq * dp * 4));
-        stage_query_rows(queries, sl.pin_in.as<float>(), nq, d, dp, cfg.normalize_vectors);
-        NIDX_HIP(sl.d_queries.reserve((size_t)nq * dp * 4));
-        NIDX_HIP(hipMemcpyAsync(sl.d_queries.p, sl.pin_in.p, (size_t)nq * dp * 4, hipMemcpyHostToDevice, sl.stream));
-        sl.dq = sl.d_queries.as<float>();
-        // ---- result block (see pipeline_submit for the merge's two routes) ----
-        const bool big_dedup = p.with_duplicates == 0 && (uint64_t)S * k > 4096;
-        sl.merged = !(S == 1 && segs[0].key_ids.empty()) && !big_dedup && !getenv("NIDX_GPU_FSSC_HOST");
-        const size_t fw = flag_words(S), mw = sl.merged ? merged_words(nq, k) : 0, sw = seg_words(nq, k);
-        const size_t at_method = fw + mw, at_nh = at_method + (size_t)nq * S, at_ns = at_nh + S, at_match = (at_ns + S + 1) & ~(size_t)1;
-        // (a prefiltered batch: the projection's two counters behind the matching counts, 8-byte aligned as they are)
-        const size_t at_pf = at_match + (size_t)F * S * 2, rw = at_pf + (pf ? 4 : 0) - at_method, words = fw + mw + rw + S * sw;
-        sl.mw = mw;
-        sl.rw = rw;
-        sl.dirty = true;   // from here on work is queued on the slot's stream: an error path must drain it (SlotRelease)
-        sl.flag_bytes = fw * 4;
-        if (words * 4 > sl.d_block.bytes) {
-            NIDX_HIP(sl.d_block.reserve(words * 4));
-            NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
-        }
-        NIDX_HIP(sl.pin_out.reserve(words * 4));
-        uint32_t *blk = sl.d_block.as<uint32_t>();
-        // ---- one upload: [segment records | program words | the queries' filters | has-program bytes] ----
-        // (a prefiltered batch adds [filter-stage records | projection records | the operands' field rows | their resource rows])
-        const size_t at_prog = align8(S * sizeof(RouteSegDev)), at_foq = at_prog + L.prog.size() * 4, at_has = at_foq + (size_t)nq * 4,
-                     at_fseg = align8(at_has + S * (size_t)F), at_pseg = at_fseg + S * sizeof(FilterSegDev),
-                     at_rows = at_pseg + S * sizeof(PrefilterProjSeg), in_bytes = pf ? at_rows + 2 * D * sizeof(uint64_t *) : at_has + S * (size_t)F;
-        NIDX_HIP(sl.pin_rt_in.reserve(in_bytes));
-        NIDX_HIP(sl.d_rt_in.reserve(in_bytes));
-        {
-            unsigned char *h = sl.pin_rt_in.as<unsigned char>();
-            memcpy(h, plan.segs.data(), S * sizeof(RouteSegDev));
-            if (!L.prog.empty()) memcpy(h + at_prog, L.prog.data(), L.prog.size() * 4);
-            memcpy(h + at_foq, L.filter_of_query.data(), (size_t)nq * 4);
-            if (!L.has_program.empty()) memcpy(h + at_has, L.has_program.data(), L.has_program.size());
-            if (pf) {
-                filter_stage_records(L, reinterpret_cast<FilterSegDev *>(h + at_fseg), reinterpret_cast<PrefilterProjSeg *>(h + at_pseg));
-                const uint64_t **hr = reinterpret_cast<const uint64_t **>(h + at_rows);
-                for (uint32_t j = 0; j < D; j++) {
-                    any_res = pf->operand_rows(L.pf_rows[j], hr[j], hr[D + j]) || any_res;
-                    any_field = any_field || hr[j];
-                }
-            }
-        }
-        NIDX_HIP(hipMemcpyAsync(sl.d_rt_in.p, sl.pin_rt_in.p, in_bytes, hipMemcpyHostToDevice, sl.stream));
-        const unsigned char *din = sl.d_rt_in.as<unsigned char>();
-        const uint32_t *dprog = reinterpret_cast<const uint32_t *>(din + at_prog);
-        NIDX_HIP(sl.d_rt_table.reserve(std::max<size_t>(L.tab_words, 1) * 8));
-        NIDX_HIP(sl.d_rt_operands.reserve(std::max<size_t>(L.opnd_words, 1) * 8));
-        NIDX_HIP(sl.d_rt_count.reserve(std::max<size_t>(S * (size_t)F, 1) * 8));
-        NIDX_HIP(hipMemsetAsync(sl.d_rt_count.p, 0, std::max<size_t>(S * (size_t)F, 1) * 8, sl.stream));
-        NIDX_HIP(sl.d_rt_lists.reserve(S * (size_t)nq * 3 * 4));
-        uint32_t *d_filter_row = sl.d_rt_lists.as<uint32_t>(), *d_items_h = d_filter_row + S * (size_t)nq, *d_items_b = d_items_h + S * (size_t)nq;
-        uint32_t *d_nh = blk + at_nh, *d_ns = blk + at_ns;
-        // this batch's turn on the device (Pipeline::walks)
-        uint64_t my_seq = 0;
-        {
-            std::lock_guard<std::mutex> lk(P.mu);
-            my_seq = P.launched++;
-            if (my_seq >= P.walks && P.gate[(my_seq - P.walks) % Pipeline::GATES])
-                NIDX_HIP(hipStreamWaitEvent(sl.stream, P.gate[(my_seq - P.walks) % Pipeline::GATES], 0));
-        }
-        const size_t hnsw_tab_bytes = (S * sizeof(HnswSearchArgs) + 63) & ~(size_t)63, tab_bytes = hnsw_tab_bytes + S * sizeof(FsscSegDev);
-        NIDX_HIP(sl.pin_tables.reserve(tab_bytes));
-        NIDX_HIP(sl.d_tables.reserve(tab_bytes));
-        HnswSearchArgs *h_hnsw = sl.pin_tables.as<HnswSearchArgs>();
-        FsscSegDev *h_fssc = reinterpret_cast<FsscSegDev *>(sl.pin_tables.as<unsigned char>() + hnsw_tab_bytes);
+        NIDX_TRY(stage_queries(sl, queries, nq, false));
+        // (see device_merges for the merge's two routes; a routed batch always keeps device rows and the copy behind them)
+        const bool merged = device_merges(S, !segs[0].key_ids.empty(), p.with_duplicates != 0, k, switches.fssc_host);
+        NIDX_TRY(reserve_block(sl, slot_block(S, nq, k, merged, false, true, F, pf != nullptr), true));
+        const SlotBlock &b = sl.block;
+        const RoutedInput in = routed_input(S, nq, F, L.prog.size(), L.pf_rows.size(), pf != nullptr, sizeof(RouteSegDev), sizeof(FilterSegDev),
+                                            sizeof(PrefilterProjSeg));
+        bool any_field = false, any_res = false;
+        NIDX_TRY(pack_routed_input(sl, plan, in, pf, any_field, any_res));
+        NIDX_TRY(reserve_routing_scratch(sl, L, S));
+        uint64_t seq = 0;
+        NIDX_TRY(take_turn(P, sl, seq));
+        SlotTables t;
+        NIDX_TRY(reserve_tables(sl, S, t));
         uint32_t n_searched = 0;
+        uint32_t *blk = sl.d_block.as<uint32_t>();
         {
             // launches read index state (tunables): under the index lock, held for the launch calls only
             std::lock_guard<std::mutex> lock(mu);
-            if (pf) {
-                // ---- the filters of the batch on ALL segments: every segment owns its operand region [D projected rows | its list
-                // operands], so one memset, one projection, one scatter and one combine serve them all.  The per-segment rows are
-                // cleared here already (see below), together with the projection's counters in front of them ----
-                NIDX_HIP(hipMemsetAsync(blk + at_pf, 0, (4 + S * sw) * 4, sl.stream));
-                const uint32_t n_words = D ? (uint32_t)pf->rows->layout.words() : 0;
-                if (L.opnd_words) {
-                    NIDX_HIP(hipMemsetAsync(sl.d_rt_operands.p, 0, L.opnd_words * 8, sl.stream));
-                    filter_launches++;
-                }
-                const uint64_t *const *d_rows = reinterpret_cast<const uint64_t *const *>(din + at_rows);
-                if (any_field && n_words) {
-                    NIDX_HIP(launch_prefilter_project(d_rows, D, n_words, pf->link->doc_off.as<uint32_t>(), pf->link->entries.as<uint2>(),
-                                                      reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg), sl.d_rt_operands.as<uint64_t>(),
-                                                      reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
-                    pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
-                    filter_launches++, launches++;
-                }
-                if (any_res && pf->rows->res_words) {   // the operands' resource rows, into the same operand rows: the fifth launch
-                    NIDX_HIP(launch_prefilter_project_resources(d_rows + D, D, (uint32_t)pf->rows->res_words, pf->link->res_off.as<uint32_t>(),
-                                                                pf->link->res_ranges.as<PrefilterResRange>(),
-                                                                reinterpret_cast<const PrefilterProjSeg *>(din + at_pseg), sl.d_rt_operands.as<uint64_t>(),
-                                                                reinterpret_cast<unsigned long long *>(blk + at_pf), sl.stream));
-                    pf_ticket_stats[PT_PROJECTIONS].fetch_add(1, std::memory_order_relaxed);
-                    filter_launches++, launches++;
-                }
-                pf_ticket_stats[PT_ROWS].fetch_add(D, std::memory_order_relaxed);
-                const FilterSegDev *dseg = reinterpret_cast<const FilterSegDev *>(din + at_fseg);
-                NIDX_HIP(launch_filter_scatter_segments(dseg, (uint32_t)S, dprog, L.max_work, sl.d_rt_operands.as<uint64_t>(), sl.stream));
-                NIDX_HIP(launch_filter_combine_segments(dseg, (uint32_t)S, dprog, F, L.max_words, sl.d_rt_operands.as<uint64_t>(),
-                                                        sl.d_rt_table.as<uint64_t>(), sl.d_rt_count.as<unsigned long long>(), sl.stream));
-                const uint32_t n = (L.max_work ? 1 : 0) + (F && L.max_words ? 1 : 0);
-                filter_launches += n, launches += n;
-            }
-            // ---- the filters of the batch on every segment: the operand rows are the segments' one after the other, in stream order ----
-            if (!pf) {
-                rc = launch_filter_stage(L, dprog, sl.d_rt_operands.as<uint64_t>(), sl.d_rt_table.as<uint64_t>(), sl.d_rt_count.as<unsigned long long>(),
-                                         sl.stream, &launches);
-                if (rc != NIDX_OK) return rc;
-            }
-            // ---- routing: the counts stay where the combine launches left them ----
-            RouteArgs ra;
-            ra.counts = sl.d_rt_count.as<unsigned long long>();
-            ra.filter_of_query = reinterpret_cast<const uint32_t *>(din + at_foq);
-            ra.has_program = din + at_has;
-            ra.segs = reinterpret_cast<const RouteSegDev *>(din);
-            ra.nq = nq, ra.n_filters = F, ra.n_segs = (uint32_t)S;
-            ra.method = p.method;
-            ra.out_method = reinterpret_cast<int32_t *>(blk + at_method);
-            ra.out_matching = reinterpret_cast<unsigned long long *>(blk + at_match);
-            ra.filter_row = d_filter_row;
-            ra.items_hnsw = d_items_h, ra.items_scan = d_items_b;
-            ra.n_hnsw = d_nh, ra.n_scan = d_ns;
-            NIDX_HIP(launch_route(ra, sl.stream));
-            launches++;
-            // ---- per-segment rows, as pipeline_submit lays them out; a (query, segment) no arm takes keeps the cleared count ----
-            if (!pf) NIDX_HIP(hipMemsetAsync(blk + fw + mw + rw, 0, S * sw * 4, sl.stream));
+            // the filters of the batch on every segment: table-driven for a prefiltered batch, else the operand rows are the segments'
+            // one after the other, in stream order
+            if (pf) NIDX_TRY(launch_prefiltered_filter_stage(sl, L, in, *pf, any_field, any_res, launches, filter_launches));
+            else
+                NIDX_TRY(launch_filter_stage(L, routed_programs(sl, in), sl.d_rt_operands.as<uint64_t>(), sl.d_rt_table.as<uint64_t>(),
+                                             sl.d_rt_count.as<unsigned long long>(), sl.stream, &launches));
+            NIDX_TRY(launch_route_stage(sl, in, F, launches));
+            // a (query, segment) no arm takes keeps the cleared count (a prefiltered batch cleared its rows with the counters)
+            if (!pf) NIDX_HIP(hipMemsetAsync(blk + b.rows_at(), 0, b.rows_words() * 4, sl.stream));
             const uint32_t walks = nq * (uint32_t)std::min<size_t>(S, 64);   // the launch shape follows the grid's upper bound
-            int shape_seg = -1;
             uint32_t nblk = 1;
-            for (size_t s = 0; s < S; s++) {
-                VectorSegment &seg = segs[s];
-                uint32_t *d_vec = blk + fw + mw + rw + s * sw;
-                float *d_score = reinterpret_cast<float *>(d_vec + (size_t)nq * k);
-                uint32_t *d_count = d_vec + (size_t)nq * k * 2;
-                h_fssc[s] = FsscSegDev{seg.vectors.as<float>(), seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>(),
-                                       seg.key_ids.empty() ? nullptr : seg.key_ids_dev.as<unsigned long long>(), d_vec, nullptr, d_score, seg.dp, 0u};
-                if (seg.n) {
-                    h_fssc[s].count = d_count;
-                    n_searched++;
-                    nblk = std::max(nblk, scan_num_blocks(seg.n));
-                }
-                HnswSearchArgs ha = hnsw_args((uint32_t)s, sl.dq, nq, walks, k, p.min_score, p.with_duplicates != 0, nullptr, d_vec, d_score, d_count,
-                                              nullptr, vis_for(walks), blk + s);
-                ha.filter_row = d_filter_row + s * (size_t)nq;
-                ha.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
-                ha.filter_words = (seg.n_paragraphs + 63) / 64;
-                h_hnsw[s] = ha;
-                if (shape_seg < 0 && seg.has_graph && seg.n) shape_seg = (int)s;
-            }
-            NIDX_HIP(hipMemcpyAsync(sl.d_tables.p, sl.pin_tables.p, tab_bytes, hipMemcpyHostToDevice, sl.stream));
-            // ---- the walk arm: every segment's routed queries in one launch ----
+            int shape_seg = -1;
+            fill_routed_tables(sl, L, t, walks, n_searched, nblk, shape_seg);
+            NIDX_TRY(upload_tables(sl, t));
             if (p.method != NIDX_METHOD_BRUTE_FORCE && shape_seg >= 0) {
-                HnswSearchArgs a = h_hnsw[shape_seg];
-                a.seg_table = sl.d_tables.as<HnswSearchArgs>();
-                a.n_table = (uint32_t)S;
-                a.route_items = d_items_h;
-                a.route_n_items = d_nh;
-                NIDX_HIP(launch_hnsw_search(a, waves_per_query, sl.stream));
+                NIDX_TRY(launch_walk_arm(sl, t, shape_seg));
                 launches++;
             }
-            // ---- the scan arm: per segment gather -> register-tile scan with per-query rows -> merge -> scatter.  The compact rows, the
-            // per-block lists (sized by nq) and the compact hits are the segments' one after the other ----
-            if (p.method != NIDX_METHOD_HNSW) {
-                NIDX_HIP(sl.d_rt_queries.reserve((size_t)nq * dp * 4));
-                NIDX_HIP(sl.d_rt_rows.reserve((size_t)nq * 4));
-                NIDX_HIP(sl.d_rt_compact.reserve(((size_t)nq * k * 2 + nq) * 4));
-                NIDX_HIP(sl.d_bf_partial.reserve((size_t)nq * nblk * k * 8));
-                uint32_t *c_vec = sl.d_rt_compact.as<uint32_t>();
-                float *c_score = reinterpret_cast<float *>(c_vec + (size_t)nq * k);
-                uint32_t *c_count = c_vec + (size_t)nq * k * 2;
-                for (size_t s = 0; s < S; s++) {
-                    VectorSegment &seg = segs[s];
-                    if (!seg.n) continue;
-                    uint32_t *d_vec = blk + fw + mw + rw + s * sw;
-                    const uint32_t *items = d_items_b + s * (size_t)nq, *n_items = d_ns + s;
-                    NIDX_HIP(launch_route_gather(sl.dq, items, n_items, d_filter_row + s * (size_t)nq, nq, dp, sl.d_rt_queries.as<float>(),
-                                                 sl.d_rt_rows.as<uint32_t>(), sl.stream));
-                    ScanArgs a = scan_args((uint32_t)s, sl.d_rt_queries.as<float>(), nq, k, p.min_score, nullptr);
-                    a.filter_row = sl.d_rt_rows.as<uint32_t>();
-                    a.filter_table = L.any_prog[s] ? sl.d_rt_table.as<uint64_t>() + L.tab_off[s] : nullptr;
-                    a.filter_words = (seg.n_paragraphs + 63) / 64;
-                    a.partial = sl.d_bf_partial.as<uint64_t>();
-                    const uint32_t sblk = scan_num_blocks(seg.n);
-                    NIDX_HIP(launch_scan_routed(a, n_items, sblk, sl.stream));
-                    NIDX_HIP(launch_merge_topk_routed(a.partial, n_items, nq, sblk, k, c_vec, c_score, c_count, sl.stream));
-                    NIDX_HIP(launch_route_scatter(c_vec, c_score, c_count, items, n_items, nq, k, d_vec, reinterpret_cast<float *>(d_vec + (size_t)nq * k),
-                                                  d_vec + (size_t)nq * k * 2, sl.stream));
-                    launches += 4;
-                }
-            }
+            if (p.method != NIDX_METHOD_HNSW) NIDX_TRY(launch_scan_arm(sl, L, nblk, launches));
         }
-        // ---- Fssc on the device, or the per-segment rows for the host merge (pipeline_submit) ----
-        if (sl.merged) {
-            FsscArgs f;
-            f.segs = reinterpret_cast<const FsscSegDev *>(sl.d_tables.as<unsigned char>() + hnsw_tab_bytes);
-            f.n_segs = (uint32_t)S, f.nq = nq, f.k = k, f.dim = d;
-            f.with_duplicates = p.with_duplicates != 0;
-            f.offered = nullptr;
-            f.offered_stride = std::max<uint32_t>(n_searched, 1) * k;
-            if (!f.with_duplicates) {
-                NIDX_HIP(sl.d_offered.reserve((size_t)nq * f.offered_stride * 12));
-                f.offered = sl.d_offered.as<uint32_t>();
-            }
-            f.out_seg = blk + fw;
-            f.out_para = f.out_seg + (size_t)nq * k;
-            f.out_vec = f.out_para + (size_t)nq * k;
-            f.out_score = reinterpret_cast<float *>(f.out_vec + (size_t)nq * k);
-            f.out_count = f.out_vec + (size_t)nq * k * 2;
-            NIDX_HIP(launch_fssc_merge(f, sl.stream));
+        // Fssc on the device, or the per-segment rows for the host merge (pipeline_submit)
+        if (merged) {
+            NIDX_TRY(queue_fssc(sl, t, n_searched, cfg.dimension, blk));
             launches++;
-            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, (fw + mw + rw) * 4, hipMemcpyDeviceToHost, sl.stream));
-        } else {
-            NIDX_HIP(hipMemcpyAsync(sl.pin_out.p, sl.d_block.p, words * 4, hipMemcpyDeviceToHost, sl.stream));
         }
-        NIDX_HIP(hipEventRecord(sl.done, sl.stream));
-        {
-            std::lock_guard<std::mutex> lk(P.mu);
-            hipEvent_t &g = P.gate[my_seq % Pipeline::GATES];
-            if (!g) NIDX_HIP(hipEventCreateWithFlags(&g, hipEventDisableTiming));
-            NIDX_HIP(hipEventRecord(g, sl.stream));
-        }
-        sl.launched = true;
+        NIDX_TRY(queue_final_copy(sl));
+        NIDX_TRY(finish_turn(P, sl, seq));
     }
     routed_stats[RS_ROUTED].fetch_add(1, std::memory_order_relaxed);
     routed_stats[RS_LAUNCHES].fetch_add(launches, std::memory_order_relaxed);
@@ -1170,25 +1309,24 @@ int32_t VectorIndex::pipeline_submit_routed(const float *queries, uint32_t nq, c
 // The wait of a routed ticket, behind the slot's event (pipeline_wait)
 int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                                  uint32_t *out_count, int32_t *out_method, uint64_t *out_matching, uint32_t *n_retried_out) {
-    const uint32_t nq = sl.nq, k = sl.params.k, d = cfg.dimension, dp = (d + 3u) & ~3u;
-    const size_t S = segs.size();
+    const uint32_t nq = sl.nq, d = cfg.dimension, dp = (d + 3u) & ~3u;
+    const SlotBlock &b = sl.block;
+    const size_t S = b.S;
     const RoutedBatch &rb = *sl.rb;
     const uint32_t F = (uint32_t)rb.filters.size();
-    const size_t fw = flag_words(S), mw = sl.mw, rw = sl.rw, sw = seg_words(nq, k);
-    const size_t at_method = fw + mw, at_nh = at_method + (size_t)nq * S, at_ns = at_nh + S, at_match = (at_ns + S + 1) & ~(size_t)1;
     const uint32_t *host = sl.pin_out.as<uint32_t>();
     uint64_t walk_items = 0, scan_items = 0;
     bool flagged = false;
     for (size_t s = 0; s < S; s++) {
-        walk_items += host[at_nh + s];
-        scan_items += host[at_ns + s];
+        walk_items += host[b.at_nh + s];
+        scan_items += host[b.at_ns + s];
         if (host[s]) flagged = true;
     }
     routed_stats[RS_WALK_ITEMS].fetch_add(walk_items, std::memory_order_relaxed);
     routed_stats[RS_SCAN_ITEMS].fetch_add(scan_items, std::memory_order_relaxed);
     PrefilterSearch pf;
     if (rb.prefiltered) {
-        const uint64_t *c = reinterpret_cast<const uint64_t *>(host + at_match + (size_t)F * S * 2);   // the projection's counters
+        const uint64_t *c = reinterpret_cast<const uint64_t *>(host + b.at_pf);   // the projection's counters
         pf_ticket_stats[PT_DOCUMENTS].fetch_add(c[0], std::memory_order_relaxed);
         pf_ticket_stats[PT_PARAGRAPHS].fetch_add(c[1], std::memory_order_relaxed);
         pf.link = rb.link;
@@ -1200,7 +1338,7 @@ int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t
         // A walk overflowed a bounded on-chip structure: the blocking search answers the whole batch from the ticket's copies (it
         // repairs spills query by query), and the flag words are zero again before anybody else takes the slot
         routed_stats[RS_FLAGGED].fetch_add(1, std::memory_order_relaxed);
-        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, fw * 4, sl.stream));
+        NIDX_HIP(hipMemsetAsync(sl.d_block.p, 0, b.fw * 4, sl.stream));
         NIDX_HIP(hipStreamSynchronize(sl.stream));
         sl.dirty = false;
         const float *rows = rb.rows.data();
@@ -1218,37 +1356,22 @@ int32_t VectorIndex::routed_wait(SearchSlot &sl, uint32_t *out_segment, uint32_t
                                 out_segment, out_paragraph, out_vector, out_score, out_count, out_method, out_matching, rb.prefiltered ? &pf : nullptr);
     }
     sl.dirty = false;   // everything queued has completed and no flag word is set
-    if (out_method) memcpy(out_method, host + at_method, (size_t)nq * S * 4);
+    if (out_method) memcpy(out_method, host + b.at_method, (size_t)nq * S * 4);
     if (out_matching) {
-        const uint64_t *m = reinterpret_cast<const uint64_t *>(host + at_match);
+        const uint64_t *m = reinterpret_cast<const uint64_t *>(host + b.at_match);
         for (uint32_t lf = 0; lf < F; lf++)
             for (size_t s = 0; s < S; s++) out_matching[(size_t)rb.filters[lf] * S + s] = m[(size_t)lf * S + s];
     }
-    if (sl.merged) {
-        const uint32_t *m = host + fw, *cnt = m + (size_t)nq * k * 4;
-        for (uint32_t q = 0; q < nq; q++) {
-            const uint32_t c = std::min(cnt[q], k);
-            out_count[q] = c;
-            const size_t at = (size_t)q * k;
-            if (out_segment) memcpy(out_segment + at, m + at, (size_t)c * 4);
-            if (out_paragraph) memcpy(out_paragraph + at, m + (size_t)nq * k + at, (size_t)c * 4);
-            if (out_vector) memcpy(out_vector + at, m + (size_t)nq * k * 2 + at, (size_t)c * 4);
-            if (out_score) memcpy(out_score + at, m + (size_t)nq * k * 3 + at, (size_t)c * 4);
-        }
+    if (b.merged) {
+        copy_merged_hits(host, b, out_segment, out_paragraph, out_vector, out_score, out_count);
         return NIDX_OK;
     }
     // Fssc across the segments on the host (one plain segment, or more candidates than the device merge takes)
-    std::vector<const uint32_t *> pv(S, nullptr), pc(S, nullptr);
-    std::vector<const float *> ps(S, nullptr);
-    for (size_t s = 0; s < S; s++) {
-        if (!segs[s].n) continue;
-        const uint32_t *b = host + fw + mw + rw + s * sw;
-        pv[s] = b;
-        ps[s] = reinterpret_cast<const float *>(b + (size_t)nq * k);
-        pc[s] = b + (size_t)nq * k * 2;
-    }
-    return fssc_merge(nq, sl.params, pv.data(), ps.data(), pc.data(), out_segment, out_paragraph, out_vector, out_score, out_count);
+    return host_merge(*this, sl, [&](size_t s) { return segs[s].n != 0; }, out_segment, out_paragraph, out_vector, out_score, out_count);
 }
+
+
+
 
 // ---- search_multi_vector for batches (searcher.rs:345-394): first pass through the entries above, second stage on the device ----
 namespace {
@@ -1410,7 +1533,7 @@ int32_t VectorIndex::maxsim_wait(uint64_t ticket, uint32_t *out_segment, uint32_
     if (!mb) return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown maxsim ticket %llu (a ticket is waited for once, by the wait of its kind)", (unsigned long long)ticket);
     // the ticket holds the generation until its first pass has been waited for; the second stage reads `segs` too
     gate.enter_nested();
-    struct GenRelease { GenGate &g; ~GenRelease() { g.leave(); } } gen_release{gate};
+    GenRelease gen_release{gate};
     const uint32_t nq = mb->nq, k1 = mb->k1;
     const size_t T = (size_t)mb->qoff[nq];
     std::vector<uint32_t> s1(T * k1), pa1(T * k1), c1(std::max<size_t>(T, 1));

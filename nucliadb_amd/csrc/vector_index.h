@@ -120,6 +120,9 @@ struct Coalescer;
 std::shared_ptr<Coalescer> make_coalescer();
 struct SearchSlot;
 struct Pipeline;
+struct RoutedBatch;   // serving.cpp
+struct SlotTables;
+struct RoutedInput;   // serving_layout.h
 std::shared_ptr<Pipeline> make_pipeline();
 double trace_slow_us();  // NIDX_GPU_TRACE_SLOW_US  // coalescer.cpp
 
@@ -322,6 +325,27 @@ struct VectorIndex {
                             const uint64_t *const *segment_filters, bool blocking, uint64_t *ticket_out);
     int32_t pipeline_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, uint32_t *out_vector, float *out_score,
                           uint32_t *out_count, uint32_t *n_retried_out, int32_t *out_method = nullptr, uint64_t *out_matching = nullptr);
+    // the stages of the submits and the waits that read index state (serving.cpp, where each is described); the launch stages run under mu
+    int32_t stage_queries(SearchSlot &sl, const float *queries, uint32_t nq, bool device_pointer_allowed);
+    int32_t choose_methods(const nidx_gpu_vector_search_params_t &p, const uint64_t *const *segment_filters, std::vector<int> &method,
+                           std::vector<uint64_t> &matching, bool &host_block);
+    int32_t upload_segment_filters(SearchSlot &sl, const uint64_t *const *segment_filters);
+    bool rabitq_group_fits(uint32_t nq) const;
+    int32_t launch_segments(SearchSlot &sl, const std::vector<uint64_t> &matching, bool one_launch, bool rq_one_launch, uint32_t walks, SlotTables &t,
+                            uint32_t &n_searched, std::vector<uint32_t> &rq_segs, std::vector<uint32_t> &bf_segs);
+    int32_t launch_segment_alone(SearchSlot &sl, uint32_t s, int method, uint64_t matching);
+    int32_t launch_brute_force_group(SearchSlot &sl, const std::vector<uint32_t> &bf_segs, const std::vector<uint64_t> &matching);
+    int32_t launch_rabitq_group(SearchSlot &sl, const std::vector<uint32_t> &rq_segs, uint32_t walks, SlotTables &t);
+    int32_t launch_walk_table(SearchSlot &sl, const SlotTables &t);
+    int32_t repair_flagged_segments(SearchSlot &sl, const std::vector<uint32_t> &seg_flags, uint32_t *n_retried_out);
+    void copy_request(RoutedBatch &rb, const RoutedPlan &plan, const float *queries, uint32_t nq, const nidx_gpu_filter_program_t *programs,
+                      uint32_t n_filters, const uint32_t *filter_of_query, const PrefilterSearch *pf);
+    int32_t pack_routed_input(SearchSlot &sl, const RoutedPlan &plan, const RoutedInput &in, const PrefilterSearch *pf, bool &any_field, bool &any_res);
+    int32_t launch_prefiltered_filter_stage(SearchSlot &sl, const FilterLayout &L, const RoutedInput &in, const PrefilterSearch &pf, bool any_field,
+                                            bool any_res, uint64_t &launches, uint64_t &filter_launches);
+    void fill_routed_tables(SearchSlot &sl, const FilterLayout &L, SlotTables &t, uint32_t walks, uint32_t &n_searched, uint32_t &nblk, int &shape_seg);
+    int32_t launch_walk_arm(SearchSlot &sl, const SlotTables &t, int shape_seg);
+    int32_t launch_scan_arm(SearchSlot &sl, const FilterLayout &L, uint32_t nblk, uint64_t &launches);
     void pipeline_config(int32_t depth, int32_t walks = -1);
     // evaluates `prog` for segment s into scratch_filter (already intersected with alive); returns |filter ∩ alive|
     // (pf: the program is filter `filter` of a prefiltered search and may hold NIDX_FILTER_PUSH_PREFILTER)

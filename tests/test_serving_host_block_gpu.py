@@ -240,6 +240,46 @@ def test_three_segments_merged_on_the_device_or_on_the_host(three_segments, monk
         assert retried == 0 and same(got, want), (host_merge, with_dup)
 
 
+@pytest.mark.parametrize("route", ("host block", "copy route"))
+def test_flagged_walks_of_a_batch_the_device_merged(orc, route):
+    """Three segments of 1 500 x 32: the device merges them (Fssc), so when a walk raises its flag the merged hits rest on a walk that
+    overflowed — wait() fetches the per-segment rows from the device, re-runs the flagged segments exactly and merges again on the
+    host.  Against the blocking search segment at a time (tunable serial_segments); a clean batch on the slot afterwards re-runs nothing.
+      host block: forced HNSW under the one-row-in-300 filter of test_flag_rows_of_one_ticket_among_three on every segment: each walk
+                  outgrows the on-chip pool and says so in the batch's flag rows;
+      copy route: METHOD_AUTO with that filter on the last segment only sends it to the exact scan (5 rows match), so the batch keeps
+                  the device block and its flag words.  The unfiltered walks of the other two do not flag at this size by themselves:
+                  the tunable vis_log2 = 10 (a 1 024-slot visited table, flagged at three quarters) makes them; k = 20 so that all
+                  three segments have hits on the page."""
+    rng = np.random.default_rng(53)
+    n, d = 1500, 32
+    xs = [unit_rows(rng, n, d) for _ in range(3)]
+    xs[1][5] = xs[0][40]      # the same vector bytes in two segments
+    graphs = [bytes(orc.Segment(x, similarity=orc.SIM_COSINE, order=orc.ORDER_WAVE64).build_graph(seed=3).serialize_v2(n)[0]) for x in xs]
+    filt = orc.bitset(n, ones=list(range(0, n, 300)))
+    q = np.ascontiguousarray(np.vstack([xs[0][40][None, :], unit_rows(rng, 15, d)]))
+    method, filters, clean_filters, k = ((_lib.METHOD_HNSW, [filt] * 3, None, 10) if route == "host block" else
+                                         (_lib.METHOD_AUTO, [None, None, filt], [None, None, filt], 20))
+    idx = Index(xs, graphs=graphs)
+    try:
+        for with_dup in (True, False):
+            if route == "copy route":
+                idx.tunable("vis_log2", 10)
+            idx.tunable("serial_segments", 1)
+            want = idx.search(q, k, method, with_dup, filters=filters)
+            idx.tunable("serial_segments", 0)
+            got, retried = idx.wait(idx.submit(q.ctypes.data, 16, k, method, with_dup, filters=filters), 16, k)
+            assert retried > 0 and same(got, want), (route, with_dup)
+            assert set(np.concatenate([got[0][i, :int(got[4][i])] for i in range(16)]).tolist()) == {0, 1, 2}
+            if route == "copy route":
+                idx.tunable("vis_log2", 13)
+            clean = idx.search(q, k, method, with_dup, filters=clean_filters)
+            got, retried = idx.wait(idx.submit(q.ctypes.data, 16, k, method, with_dup, filters=clean_filters), 16, k)
+            assert retried == 0 and same(got, clean), (route, with_dup)
+    finally:
+        idx.close()
+
+
 def test_a_batch_that_mixes_methods_keeps_the_copy_route(orc):
     """One segment without a graph under METHOD_AUTO is scanned exactly while the other walks its graph: the batch mixes methods,
     keeps the device block and the copy behind it, and equals the blocking search; an all-HNSW batch on the same slots before and

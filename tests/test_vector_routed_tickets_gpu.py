@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from nucliadb_amd import _lib
-from nucliadb_amd.vector import And, Literal, PrefilterResult, Similarity, VectorSearchRequest
+from nucliadb_amd.vector import And, Literal, PrefilterResult, Similarity, VectorSearcher, VectorSearchRequest
 from test_vector_query_filters_gpu import LABELS, _assert_equal_rows, _batch, _index, _programs, _requests
 
 pytestmark = pytest.mark.gpu
@@ -155,6 +155,39 @@ def test_all_unfiltered_and_all_matching_nothing(mixed):
     d = _delta(before, _stats(searcher))
     assert int(got[1][4].sum()) == 0 and not got[2].any() and not got[3].any()   # every grid is early returns, every count 0
     assert d["walk_items"] == 0 and d["scan_items"] == 0 and d["batches_routed"] == 1
+
+
+class _UnkeyedSearcher(VectorSearcher):
+    """Its segments go in without paragraph key ids (nidx_gpu_vector_segment_t::paragraph_key_ids = NULL): a paragraph's identity
+    across segments is (segment, paragraph)."""
+
+    def _fill_segment_c(self, c_seg, seg, alive):
+        super()._fill_segment_c(c_seg, seg, alive)
+        c_seg.paragraph_key_ids = None
+
+
+def test_one_plain_segment_is_merged_on_the_host():
+    """One segment without key ids: Fssc is the identity on its rows, so the device does not merge — the ticket's transfer carries
+    [flags | routing | the segment's rows] and the wait runs the host merge over them, with no comparison switch set.  (The other
+    indexes of this file have three segments and at most 900 candidates per query: the device merges them.)  A mixed batch of 21
+    queries at k = 10, both arms, against the blocking call bit for bit."""
+    three, rids, rng = _index(Similarity.Cosine, 32, 1500, 31, hnsw=False)
+    seg, config = three._segments[0], three.config
+    three.close()
+    searcher = _UnkeyedSearcher.open(config, [(seg, 1)])
+    try:
+        searcher.build_hnsw(0)
+        q = rng.normal(size=(21, 32)).astype(np.float32)
+        reqs, pres = _requests(rids, rng, q)
+        progs, F, foq, _keep = _programs(searcher, reqs, pres)
+        before = _stats(searcher)
+        got, want = _round_trip(searcher, q, 10, False, _lib.METHOD_AUTO, progs, F, foq)
+        d = _delta(before, _stats(searcher))
+        assert d["batches_routed"] == 1 and d["batches_fallback"] == 0 and d["batches_flagged"] == 0 and got[4] == 0
+        assert {_lib.METHOD_HNSW, _lib.METHOD_BRUTE_FORCE} <= set(int(x) for x in want[2].reshape(-1))
+        assert d["walk_items"] > 0 and d["scan_items"] > 0 and int(want[1][4].max()) == 10
+    finally:
+        searcher.close()
 
 
 def test_index_without_graphs_scans_everything():
