@@ -67,6 +67,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS 1024 /* nidx_gpu_vector_search_submit_prefiltered_per_query_async, nidx_gpu_vector_prefiltered_ticket_stats */
 #define NIDX_FEATURE_PREFILTER_RESOURCE_PARTS 2048 /* nidx_gpu_prefilter_link_set_resources, nidx_gpu_prefilter_term_link_set_resources, their _read_resources */
 #define NIDX_FEATURE_BM25_PREFILTERED_TICKETS 4096 /* nidx_gpu_bm25_search_submit_prefiltered / _wait_prefiltered, nidx_gpu_bm25_ticket_stats */
+#define NIDX_FEATURE_JSON_SYNC 8192 /* nidx_gpu_json_sync / nidx_gpu_json_generation */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1256,8 +1257,8 @@ int32_t nidx_gpu_bm25_ticket_stats(nidx_gpu_bm25_index_t *index, nidx_gpu_bm25_t
  *    else complement all bits (the caller never hands over a NaN); date -> tantivy's i64 nanoseconds mapped like i64; bool -> 0 or 1.
  *    (The mapping restates tantivy's and, like the other oracle-defined values, is not yet pinned against the crate: DESIGN.md §8
  *    item 4.)  The index owns a RESOURCE TABLE: the distinct uuids of all segments, ascending as unsigned 128-bit numbers, and per
- *    document the ordinal of its resource.  A segment holds at most one column per (path, type).  There is no sync of a JSON index: a
- *    new generation is close and open.
+ *    document the ordinal of its resource.  A segment holds at most one column per (path, type).  nidx_gpu_json_sync (below) moves an
+ *    open index to the shard's next generation in place.
  *
  * 2. A batch of JSON prefilters.  Request i is a postfix program over its leaves: NIDX_FILTER_PUSH_LISTS with a = the leaf's index
  *    in the request (b is not read), AND, OR, NOT (every alive document minus the operand: the AllQuery + MustNot of search.rs:181-189),
@@ -1298,8 +1299,8 @@ int32_t nidx_gpu_bm25_ticket_stats(nidx_gpu_bm25_index_t *index, nidx_gpu_bm25_t
  * ---- resource-granular parts on the device (present when nidx_gpu_build_features() & NIDX_FEATURE_PREFILTER_RESOURCE_PARTS) ----------
  * Both links take a resource half, given once per pair of generations like the link itself.  A second call replaces the half; a
  * refused call leaves the link as it was.  Like freeing the link, setting the half must not happen while a ticket that names the link
- * is outstanding.  The JSON index is known by the serial number it got at nidx_gpu_json_open (never by its address, which a later
- * open may reuse); a combined rows handle carries the serial number of the index its resource rows are over.
+ * is outstanding.  The JSON index is known by the serial number it got at nidx_gpu_json_open, and anew at every nidx_gpu_json_sync
+ * (never by its address, which a later open may reuse); a combined rows handle carries the serial number of the index its resource rows are over.
  *
  * 1. nidx_gpu_prefilter_link_set_resources: resource_key_*[r] is the key PREFIX of resource ordinal r of the JSON index's resource
  *    table (nidx_gpu_json_resources_read order) in the encoding of the vector segments' key tables, which stays the caller's; an
@@ -1537,6 +1538,75 @@ int32_t nidx_gpu_bm25_sync(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_syn
                            const int64_t *deletion_seqs, uint32_t n_deletions, const uint8_t *dict_bytes,
                            const uint64_t *dict_offsets, nidx_gpu_bm25_sync_stats_t *stats_out);
 int32_t nidx_gpu_bm25_generation(const nidx_gpu_bm25_index_t *index, uint64_t *generation_out);
+
+/* ---- moving an open JSON index to a new generation (present when nidx_gpu_build_features() & NIDX_FEATURE_JSON_SYNC) ---------------
+ * The JSON counterpart of nidx_gpu_vector_sync and nidx_gpu_bm25_sync.  IndexCache::reload (nidx/src/searcher/index_cache.rs:180-241)
+ * reopens the JSON index for every generation; there an open only mmaps files, here nidx_gpu_json_open checks every value, sorts
+ * every document's uuid and uploads every column.  nidx_gpu_json_sync instead moves the open index on the device: a kept segment's
+ * columns stay where they are, its slice of the alive row and of the ordinal row is carried to its new word offset by kernel, and no
+ * per-document or per-value datum of a kept segment crosses the bus in either direction.  The number of launches depends neither on
+ * the number of kept segments nor on the number of deletions (both are tables the kernels read).
+ *
+ *   entries          the new segment array, in order.  An old segment may be named once (keep); old segments no entry names are
+ *                    dropped.  n_entries == 0 gives an empty index (0 documents, 0 resources), exactly like nidx_gpu_json_open
+ *                    with no segments; an index opened with no segments can be synced.
+ *   deletion_*       open_index_with_deletions (nidx_tantivy/src/index_reader.rs:39-74): the entry of seq s loses every document
+ *                    of the resource deletion_ids[i] for each i with deletion_seqs[i] > s (strict) — new segments too.  The ids
+ *                    are uuid pairs in the encoding of resource_ids; mapping deletion keys to uuids stays with the caller
+ *                    (JsonDeletionQueryBuilder, nidx_json/src/lib.rs:46-61: a key longer than 32 bytes is cut to its first 32 and
+ *                    dropped when it is no uuid).  A uuid the new table does not hold is ignored; a uuid named several times counts
+ *                    with its largest seq.  Deletions land on top of the alive set a kept segment already has and only remove:
+ *                    repeating a call that keeps every segment changes nothing except the generation.
+ *
+ * The RESOURCE TABLE of the new generation is what a fresh nidx_gpu_json_open of that generation would build: the distinct uuids of
+ * all documents of its segments, dead ones included, ascending; a resource that only dropped segments held is gone, and every
+ * document's ordinal is renumbered to match.
+ *
+ * Everything is validated before anything is allocated, uploaded or launched (a keep that is out of range or repeated, a NULL segment
+ * where keep == -1, NULL deletion arrays with n_deletions > 0, and every check nidx_gpu_json_open makes of a segment:
+ * NIDX_ERR_INVALID_ARGUMENT, the message names the entry; 2^31 documents or more: NIDX_ERR_UNSUPPORTED), and on ANY error the index
+ * is exactly what it was: table, alive sets, answers, generation, serial number, bytes.
+ *
+ * Concurrency: the new state is built in fresh buffers on a stream of its own while nidx_gpu_json_prefilter_batch_resident calls go
+ * on.  Syncs serialise with each other; only the commit — a swap of pointers under the index's mutex after the stream has drained,
+ * which cannot fail — excludes other calls.  A batch answers for the generation it ran in.  PEAK MEMORY: both generations' alive
+ * and ordinal rows and tables are resident until the commit; the columns of kept segments are moved, never copied.
+ *
+ * At the commit the index takes a NEW SERIAL NUMBER and its generation goes up by one (0 after open).  Everything made before the
+ * sync is therefore refused by the checks that compare serial numbers: a rows handle of an earlier generation in
+ * nidx_gpu_prefilter_rows_combine against a link made afterwards (and the reverse), the resource link, the resource halves of both
+ * prefilter links, and combined rows handles.  Handles made earlier stay readable: nidx_gpu_json_rows_read answers in the ordinals
+ * of the table the handle was made over.  The shim builds the resource link and sets the links' resource halves again after a sync,
+ * as it does after open. */
+typedef struct nidx_gpu_json_sync_entry {
+    int32_t keep;                            /* >= 0: that segment of the open index, nothing of it uploaded; -1: upload `segment` */
+    int64_t seq;                             /* nidx_types::Seq of the segment (kept or new) */
+    const nidx_gpu_json_segment_t *segment;  /* keep == -1: as for nidx_gpu_json_open (alive_bitset = its starting alive set) */
+} nidx_gpu_json_sync_entry_t;
+
+typedef struct nidx_gpu_json_sync_stats {
+    uint64_t generation;        /* the generation the index is in now */
+    uint64_t bytes_uploaded;    /* host to device, everything the call sent: the new segments' columns, uuids and alive words, the
+                                 * distinct uuids of the new documents (those the old table lacks once more), the distinct
+                                 * deletions, one table row per entry */
+    uint64_t bytes_downloaded;  /* device to host: the new table for the host mirror (16 per resource), one word per distinct uuid of
+                                 * the new documents, two counts */
+    uint64_t documents_carried; /* documents of kept segments */
+    uint64_t docs_cleared;      /* alive bits this call cleared */
+    uint64_t hbm_released;      /* the dropped segments' columns and their share of the alive and ordinal rows */
+    uint64_t resources;         /* the new table's size */
+    uint64_t resources_added;   /* uuids the old table did not hold */
+    uint64_t resources_dropped; /* uuids of the old table that no kept or new document names */
+    uint32_t kept, added, dropped;
+    uint32_t deletions_applied; /* deletions whose seq is above at least one segment's seq */
+    uint32_t launches;          /* kernels and device memsets */
+    uint32_t synchronisations;
+} nidx_gpu_json_sync_stats_t;
+
+int32_t nidx_gpu_json_sync(nidx_gpu_json_index_t *index, const nidx_gpu_json_sync_entry_t *entries, uint32_t n_entries,
+                           const uint64_t *deletion_ids /* [n_deletions][2] */, const int64_t *deletion_seqs, uint32_t n_deletions,
+                           nidx_gpu_json_sync_stats_t *stats_out);
+int32_t nidx_gpu_json_generation(const nidx_gpu_json_index_t *index, uint64_t *generation_out);
 
 /* Device time (HIP events on the handle's stream) spent in the scoring kernel(s) of the last
  * nidx_gpu_bm25_search call, summed over segments.  For batches of term unions with k <= 64 the scoring launch

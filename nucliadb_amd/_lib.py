@@ -169,6 +169,7 @@ FEATURE_VECTOR_ROUTED_TICKETS = 512   # nidx_gpu_build_features() bit: per-query
 FEATURE_VECTOR_PREFILTERED_TICKETS = 1024   # nidx_gpu_build_features() bit: routed tickets whose programs push resident prefilter rows
 FEATURE_PREFILTER_RESOURCE_PARTS = 2048   # nidx_gpu_build_features() bit: the links' resource halves (resource-granular prefilter parts on the device)
 FEATURE_BM25_PREFILTERED_TICKETS = 4096   # nidx_gpu_build_features() bit: BM25 tickets that take term sets and prefilter row sets
+FEATURE_JSON_SYNC = 8192   # nidx_gpu_build_features() bit: nidx_gpu_json_sync / nidx_gpu_json_generation
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
@@ -274,6 +275,19 @@ class JsonSegmentC(C.Structure):
 class JsonOpenStatsC(C.Structure):
     """nidx_gpu_json_open_stats_t"""
     _fields_ = [("documents", C.c_uint64), ("resources", C.c_uint64), ("columns", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class JsonSyncEntryC(C.Structure):
+    """nidx_gpu_json_sync_entry_t"""
+    _fields_ = [("keep", C.c_int32), ("seq", C.c_int64), ("segment", C.POINTER(JsonSegmentC))]
+
+
+class JsonSyncStatsC(C.Structure):
+    """nidx_gpu_json_sync_stats_t"""
+    _fields_ = [("generation", C.c_uint64), ("bytes_uploaded", C.c_uint64), ("bytes_downloaded", C.c_uint64), ("documents_carried", C.c_uint64),
+                ("docs_cleared", C.c_uint64), ("hbm_released", C.c_uint64), ("resources", C.c_uint64), ("resources_added", C.c_uint64),
+                ("resources_dropped", C.c_uint64), ("kept", C.c_uint32), ("added", C.c_uint32), ("dropped", C.c_uint32),
+                ("deletions_applied", C.c_uint32), ("launches", C.c_uint32), ("synchronisations", C.c_uint32)]
 
 
 class JsonLeafC(C.Structure):
@@ -525,6 +539,9 @@ SIGNATURES = {
     "nidx_gpu_json_open": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(JsonOpenStatsC)]),
     "nidx_gpu_json_close": (None, [C.c_void_p]),
     "nidx_gpu_json_resources_read": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_json_sync": (C.c_int32, [C.c_void_p, C.POINTER(JsonSyncEntryC), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.POINTER(JsonSyncStatsC)]),
+    "nidx_gpu_json_generation": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_json_prefilter_batch_resident": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                                            C.POINTER(JsonPrefilterBatchStatsC), C.POINTER(C.c_void_p)]),
     "nidx_gpu_json_rows_free": (None, [C.c_void_p]),

@@ -1,6 +1,7 @@
 // json_index.cpp — nidx_gpu_json_*: the resident JSON index, a batch of JSON prefilters as resource rows in HBM, the text-document ->
 // resource link, and nidx_gpu_prefilter_rows_combine (PrefilterResult::combine, nidx_types/src/prefilter.rs:46-92) over the text
-// prefilter's resident rows.  The kernels are in json_prefilter.hip, the device-free planning in json_plan.h.
+// prefilter's resident rows.  The kernels are in json_prefilter.hip, the device-free planning in json_plan.h; nidx_gpu_json_sync moves
+// the open index to the next generation (json_sync.hip, json_sync_plan.h).
 //
 // A document row spans the segments like a text row: segment s owns words [word0[s], word0[s + 1]); the index keeps an alive row of
 // that shape (zero in the padding) and, per bit position, the ordinal of the document's resource in the resource table.
@@ -11,6 +12,7 @@
 #include <mutex>
 
 #include "json_plan.h"
+#include "json_sync_plan.h"
 #include "kernels.h"
 #include "prefilter_handover.h"
 
@@ -23,6 +25,7 @@ struct JsonColumn {
 };
 struct JsonSegment {
     uint32_t n_docs = 0;
+    uint64_t bytes = 0;   // HBM of the columns
     std::vector<JsonColumn> columns;
 };
 std::atomic<uint64_t> g_json_index_uid{1};
@@ -30,9 +33,11 @@ std::atomic<uint64_t> g_json_index_uid{1};
 // nidx_gpu_json_index_t
 struct JsonIndex {
     int device = 0;
-    uint64_t uid = 0;   // what rows and links remember of the index that made them
-    hipStream_t stream = nullptr;
-    std::mutex mu;
+    uint64_t uid = 0;   // what rows and links remember of the index that made them; a sync's commit takes a new one
+    uint64_t generation = 0;
+    hipStream_t stream = nullptr, sync_stream = nullptr;   // (sync_stream: created by the first sync)
+    mutable std::mutex mu;   // uid, generation and everything below: held by a call that reads them, and by a sync's commit
+    std::mutex sync_mu;      // held by nidx_gpu_json_sync from start to end; taken before mu
     std::vector<JsonSegment> segs;
     std::vector<JsonPlanSegment> meta;
     std::vector<uint64_t> word0;          // [segments + 1]
@@ -43,8 +48,28 @@ struct JsonIndex {
     uint64_t words() const { return word0.back(); }
     ~JsonIndex() {
         if (stream) (void)hipStreamDestroy(stream);
+        if (sync_stream) (void)hipStreamDestroy(sync_stream);
     }
 };
+
+// The columns of a checked segment into HBM (st == nullptr: synchronous copies).
+hipError_t upload_columns(const nidx_gpu_json_segment_t &sg, JsonSegment &out, hipStream_t st) {
+    out.n_docs = sg.n_docs;
+    out.columns.resize(sg.n_columns);
+    auto upload = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
+        if (hipError_t e = b.alloc(std::max<size_t>(bytes, 8))) return e;
+        out.bytes += b.bytes;
+        if (!bytes) return hipSuccess;
+        return st ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) : hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+    };
+    for (uint32_t c = 0; c < sg.n_columns; c++) {
+        JsonColumn &col = out.columns[c];
+        col.n_values = sg.columns[c].n_values;
+        if (hipError_t e = upload(col.docs, sg.columns[c].docs, (size_t)col.n_values * 4)) return e;
+        if (hipError_t e = upload(col.values, sg.columns[c].values, (size_t)col.n_values * 8)) return e;
+    }
+    return hipSuccess;
+}
 
 // nidx_gpu_json_rows_t
 struct JsonRows {
@@ -93,25 +118,10 @@ int32_t nidx_gpu_json_open(const nidx_gpu_json_segment_t *segments, uint32_t n_s
     if (!index_out || (n_segments && !segments)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
     // ---- everything is checked before anything is uploaded
     uint64_t total_docs = 0;
+    std::string error;
     for (uint32_t s = 0; s < n_segments; s++) {
-        const nidx_gpu_json_segment_t &sg = segments[s];
-        if (sg.n_docs && !sg.resource_ids) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u: NULL resource ids", s);
-        if (sg.n_columns && !sg.columns) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u: NULL columns", s);
-        total_docs += sg.n_docs;
-        for (uint32_t c = 0; c < sg.n_columns; c++) {
-            const nidx_gpu_json_column_t &col = sg.columns[c];
-            if (col.type < NIDX_JSON_STR || col.type > NIDX_JSON_DATE) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: unknown type %d", s, c, col.type);
-            if ((col.path_len && !col.path) || (col.n_values && (!col.docs || !col.values)))
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: NULL path, docs or values", s, c);
-            if (col.type == NIDX_JSON_STR && (!col.dict_offsets || (col.n_dict && col.dict_offsets[col.n_dict] && !col.dict_bytes)))
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: a STR column without its dictionary", s, c);
-            for (uint64_t i = 0; i < col.n_values; i++) {
-                if (col.docs[i] >= sg.n_docs) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: document %u of %u", s, c, col.docs[i], sg.n_docs);
-                if (i && col.docs[i] < col.docs[i - 1]) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: docs descend at value %llu", s, c, (unsigned long long)i);
-                if (col.type == NIDX_JSON_STR && col.values[i] >= col.n_dict)
-                    return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: ordinal %llu of %u", s, c, (unsigned long long)col.values[i], col.n_dict);
-            }
-        }
+        if (!json_check_segment(segments[s], "segment", s, error)) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s", error.c_str());
+        total_docs += segments[s].n_docs;
     }
     if (total_docs + 64ull * n_segments >= (1ull << 31)) return fail(NIDX_ERR_UNSUPPORTED, "a JSON index of 2^31 documents or more");
     std::unique_ptr<JsonIndex> idx(new JsonIndex());
@@ -120,22 +130,8 @@ int32_t nidx_gpu_json_open(const nidx_gpu_json_segment_t *segments, uint32_t n_s
     idx->meta.resize(n_segments);
     idx->segs.resize(n_segments);
     for (uint32_t s = 0; s < n_segments; s++) {
-        const nidx_gpu_json_segment_t &sg = segments[s];
-        idx->word0[s + 1] = idx->word0[s] + ((uint64_t)sg.n_docs + 63) / 64;
-        JsonPlanSegment &meta = idx->meta[s];
-        meta.dict.resize(sg.n_columns);
-        for (uint32_t c = 0; c < sg.n_columns; c++) {
-            const nidx_gpu_json_column_t &col = sg.columns[c];
-            const std::string path(reinterpret_cast<const char *>(col.path), col.path_len);
-            if (!meta.column_of.emplace(std::make_pair(path, (int)col.type), c).second)
-                return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: a second column of the same path and type", s, c);
-            if (col.type != NIDX_JSON_STR) continue;
-            for (uint32_t t = 0; t < col.n_dict; t++) {
-                if (col.dict_offsets[t + 1] < col.dict_offsets[t]) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: dictionary offsets decrease", s, c);
-                meta.dict[c].emplace_back(reinterpret_cast<const char *>(col.dict_bytes) + col.dict_offsets[t], (size_t)(col.dict_offsets[t + 1] - col.dict_offsets[t]));
-                if (t && !(meta.dict[c][t - 1] < meta.dict[c][t])) return fail(NIDX_ERR_INVALID_ARGUMENT, "segment %u column %u: the dictionary is not sorted and distinct", s, c);
-            }
-        }
+        idx->word0[s + 1] = idx->word0[s] + ((uint64_t)segments[s].n_docs + 63) / 64;
+        if (!json_segment_meta(segments[s], "segment", s, idx->meta[s], error)) return fail(NIDX_ERR_INVALID_ARGUMENT, "%s", error.c_str());
     }
     // ---- the resource table and every document's ordinal in it
     typedef std::pair<uint64_t, uint64_t> Rid;
@@ -174,16 +170,9 @@ int32_t nidx_gpu_json_open(const nidx_gpu_json_segment_t *segments, uint32_t n_s
     NIDX_HIP(upload(idx->doc_resource, doc_res.data(), doc_res.size() * 4));
     NIDX_HIP(upload(idx->d_resources, idx->resources.data(), idx->resources.size() * 8));
     for (uint32_t s = 0; s < n_segments; s++) {
-        const nidx_gpu_json_segment_t &sg = segments[s];
-        idx->segs[s].n_docs = sg.n_docs;
-        idx->segs[s].columns.resize(sg.n_columns);
-        for (uint32_t c = 0; c < sg.n_columns; c++) {
-            JsonColumn &col = idx->segs[s].columns[c];
-            col.n_values = sg.columns[c].n_values;
-            NIDX_HIP(upload(col.docs, sg.columns[c].docs, (size_t)col.n_values * 4));
-            NIDX_HIP(upload(col.values, sg.columns[c].values, (size_t)col.n_values * 8));
-            idx->n_columns++;
-        }
+        NIDX_HIP(upload_columns(segments[s], idx->segs[s], nullptr));
+        idx->bytes += idx->segs[s].bytes;
+        idx->n_columns += segments[s].n_columns;
     }
     idx->n_docs = total_docs;
     if (stats_out) {
@@ -206,10 +195,195 @@ void nidx_gpu_json_close(nidx_gpu_json_index_t *index) {
 int32_t nidx_gpu_json_resources_read(const nidx_gpu_json_index_t *index, uint64_t *out_ids, uint64_t capacity, uint64_t *n_out) try {
     const JsonIndex *idx = reinterpret_cast<const JsonIndex *>(index);
     if (!idx || !n_out || (capacity && !out_ids)) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);   // (a sync's commit replaces the table)
     const uint64_t n = idx->n_resources(), got = std::min(n, capacity);
     if (got) memcpy(out_ids, idx->resources.data(), (size_t)got * 16);
     *n_out = n;
     return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_json_generation(const nidx_gpu_json_index_t *index, uint64_t *generation_out) try {
+    const JsonIndex *idx = reinterpret_cast<const JsonIndex *>(index);
+    if (!idx || !generation_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    *generation_out = idx->generation;
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// ---- nidx_gpu_json_sync: the next generation in fresh buffers on a stream of its own, then a swap --------------------------------------
+// The kernels are in json_sync.hip, the device-free planning in json_sync_plan.h.  The old rows and the old table are only read; a
+// prefilter batch reads them too (under mu, on the index's stream) and nothing but the commit below writes them.
+int32_t nidx_gpu_json_sync(nidx_gpu_json_index_t *index, const nidx_gpu_json_sync_entry_t *entries, uint32_t n_entries,
+                           const uint64_t *deletion_ids, const int64_t *deletion_seqs, uint32_t n_deletions,
+                           nidx_gpu_json_sync_stats_t *stats_out) try {
+    JsonIndex *idx = reinterpret_cast<JsonIndex *>(index);
+    if (!idx || (n_entries && !entries) || (n_deletions && (!deletion_ids || !deletion_seqs))) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> sync_lock(idx->sync_mu);
+    // ---- everything is checked before anything is allocated, uploaded or launched
+    std::vector<uint32_t> old_docs(idx->segs.size());
+    for (size_t s = 0; s < old_docs.size(); s++) old_docs[s] = idx->segs[s].n_docs;
+    JsonSyncPlan plan;
+    std::string error;
+    if (int32_t rc = json_sync_plan(old_docs, entries, n_entries, deletion_ids, deletion_seqs, n_deletions, plan, error)) return fail(rc, "%s", error.c_str());
+    NIDX_HIP(hipSetDevice(idx->device));
+    if (!idx->sync_stream) NIDX_HIP(hipStreamCreateWithFlags(&idx->sync_stream, hipStreamNonBlocking));
+    hipStream_t st = idx->sync_stream;
+    nidx_gpu_json_sync_stats_t stats;
+    memset(&stats, 0, sizeof stats);
+    const uint32_t R_old = idx->n_resources();
+    const uint64_t W_new = plan.word0.back(), used_words = ((uint64_t)R_old + 63) / 64 + 1;
+    const uint32_t n_new_ids = (uint32_t)(plan.new_ids.size() / 2), n_dels = (uint32_t)plan.deletion_seqs.size();
+    auto send = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
+        if (hipError_t e = b.alloc(std::max<size_t>(bytes, 8))) return e;
+        stats.bytes_uploaded += bytes;
+        return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    };
+    // ---- mark: the old ordinals the new generation still names
+    DevBuf d_word0, d_rows, d_new_ids, d_found, used, word_rank, d_counts;
+    NIDX_HIP(send(d_word0, plan.word0.data(), plan.word0.size() * 8));
+    NIDX_HIP(send(d_rows, plan.rows.data(), plan.rows.size() * sizeof(JsonSyncRow)));
+    NIDX_HIP(send(d_new_ids, plan.new_ids.data(), plan.new_ids.size() * 8));
+    NIDX_HIP(d_found.alloc(std::max<size_t>((size_t)n_new_ids * 4, 8)));
+    NIDX_HIP(used.alloc((size_t)used_words * 8));
+    NIDX_HIP(word_rank.alloc((size_t)used_words * 4));
+    NIDX_HIP(d_counts.alloc(16));   // [0] the survivors, [1] the alive bits cleared
+    NIDX_HIP(hipMemsetAsync(used.p, 0, used.bytes, st));
+    NIDX_HIP(hipMemsetAsync(d_counts.p, 0, 16, st));
+    stats.launches += 2;
+    if (n_new_ids) {
+        NIDX_HIP(launch_json_link(idx->d_resources.as<uint64_t>(), R_old, d_new_ids.as<uint64_t>(), n_new_ids, d_found.as<uint32_t>(), st));
+        NIDX_HIP(launch_json_sync_mark_ids(d_found.as<uint32_t>(), n_new_ids, R_old, used.as<unsigned long long>(), st));
+        stats.launches += 2;
+    }
+    if (W_new) {
+        NIDX_HIP(launch_json_sync_mark_rows(d_word0.as<uint64_t>(), d_rows.as<JsonSyncRow>(), n_entries, W_new, idx->doc_resource.as<uint32_t>(), R_old,
+                                            used.as<unsigned long long>(), st));
+        stats.launches++;
+    }
+    NIDX_HIP(launch_json_sync_rank(used.as<unsigned long long>(), (uint32_t)used_words, word_rank.as<uint32_t>(), d_counts.as<unsigned long long>(), st));
+    stats.launches++;
+    std::vector<uint32_t> found(n_new_ids);
+    unsigned long long n_survivors = 0;
+    if (n_new_ids) NIDX_HIP(hipMemcpyAsync(found.data(), d_found.p, (size_t)n_new_ids * 4, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipMemcpyAsync(&n_survivors, d_counts.p, 8, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));   // the counts size the new table
+    stats.synchronisations++;
+    stats.bytes_downloaded += (uint64_t)n_new_ids * 4 + 8;
+    std::vector<uint64_t> new_only;
+    for (uint32_t i = 0; i < n_new_ids; i++)
+        if (found[i] == 0xffffffffu) new_only.push_back(plan.new_ids[2 * (size_t)i]), new_only.push_back(plan.new_ids[2 * (size_t)i + 1]);
+    const uint32_t n_new_only = (uint32_t)(new_only.size() / 2);
+    if (n_survivors + n_new_only >= 0xffffffffull) return fail(NIDX_ERR_UNSUPPORTED, "more than 2^32 - 2 resources");
+    const uint32_t R_new = (uint32_t)n_survivors + n_new_only;
+    // ---- table: survivors merged with the new-only uuids; remap; del_seq
+    DevBuf alive, doc_resource, d_resources, d_new_only, remap, del_seq, d_del_ids, d_del_seqs, d_del_ord, d_doc_ids;
+    uint64_t bytes = 0;
+    auto own = [&](DevBuf &b, size_t n) -> hipError_t {   // a buffer the new generation keeps
+        if (hipError_t e = b.alloc(std::max<size_t>(n, 8))) return e;
+        bytes += b.bytes;
+        return hipSuccess;
+    };
+    NIDX_HIP(own(alive, (size_t)W_new * 8));
+    NIDX_HIP(own(doc_resource, (size_t)W_new * 64 * 4));
+    NIDX_HIP(own(d_resources, (size_t)R_new * 16));
+    NIDX_HIP(send(d_new_only, new_only.data(), new_only.size() * 8));
+    NIDX_HIP(remap.alloc(std::max<size_t>((size_t)R_old * 4, 8)));
+    NIDX_HIP(del_seq.alloc(std::max<size_t>((size_t)R_new * 8, 8)));
+    if ((uint64_t)R_old + n_new_only) {
+        NIDX_HIP(launch_json_sync_table(idx->d_resources.as<uint64_t>(), R_old, used.as<unsigned long long>(), word_rank.as<uint32_t>(),
+                                        d_new_only.as<uint64_t>(), n_new_only, d_resources.as<uint64_t>(), remap.as<uint32_t>(), del_seq.as<long long>(), st));
+        stats.launches++;
+    }
+    std::vector<uint64_t> resources((size_t)R_new * 2);
+    if (R_new) NIDX_HIP(hipMemcpyAsync(resources.data(), d_resources.p, (size_t)R_new * 16, hipMemcpyDeviceToHost, st));   // the host mirror
+    stats.bytes_downloaded += (uint64_t)R_new * 16;
+    if (n_dels) {
+        NIDX_HIP(send(d_del_ids, plan.deletion_ids.data(), (size_t)n_dels * 16));
+        NIDX_HIP(send(d_del_seqs, plan.deletion_seqs.data(), (size_t)n_dels * 8));
+        NIDX_HIP(d_del_ord.alloc((size_t)n_dels * 4));
+        NIDX_HIP(launch_json_link(d_resources.as<uint64_t>(), R_new, d_del_ids.as<uint64_t>(), n_dels, d_del_ord.as<uint32_t>(), st));
+        NIDX_HIP(launch_json_sync_deletions(d_del_ord.as<uint32_t>(), d_del_seqs.as<long long>(), n_dels, R_new, del_seq.as<long long>(), st));
+        stats.launches += 2;
+    }
+    // ---- the new segments: columns, ordinals over the new table, the given alive words
+    std::vector<JsonSegment> segs(n_entries);
+    std::vector<uint64_t> doc_ids, words;   // of all new segments, end to end
+    doc_ids.reserve((size_t)plan.documents_new * 2);
+    for (uint32_t e = 0; e < n_entries; e++) {
+        if (entries[e].keep != -1) continue;
+        const nidx_gpu_json_segment_t &sg = *entries[e].segment;
+        NIDX_HIP(upload_columns(sg, segs[e], st));
+        for (const JsonColumn &col : segs[e].columns) stats.bytes_uploaded += col.n_values * 12;
+        doc_ids.insert(doc_ids.end(), sg.resource_ids, sg.resource_ids + 2 * (size_t)sg.n_docs);
+        for (uint32_t w = 0; w < (sg.n_docs + 63u) / 64u; w++) {
+            const uint32_t n = std::min<uint32_t>(64u, sg.n_docs - w * 64u);
+            const uint64_t mask = n == 64u ? ~0ull : (1ull << n) - 1ull;
+            words.push_back((sg.alive_bitset ? sg.alive_bitset[w] : ~0ull) & mask);
+        }
+    }
+    if (W_new) {
+        NIDX_HIP(hipMemsetAsync(doc_resource.p, 0xff, doc_resource.bytes, st));   // (the padding, and the kept entries until the carry)
+        stats.launches++;
+    }
+    NIDX_HIP(send(d_doc_ids, doc_ids.data(), doc_ids.size() * 8));
+    size_t at_doc = 0, at_word = 0;
+    for (uint32_t e = 0; e < n_entries; e++) {
+        if (entries[e].keep != -1 || !plan.n_docs[e]) continue;
+        const uint32_t n = plan.n_docs[e], nw = (n + 63u) / 64u;
+        NIDX_HIP(launch_json_link(d_resources.as<uint64_t>(), R_new, d_doc_ids.as<uint64_t>() + 2 * at_doc, n, doc_resource.as<uint32_t>() + plan.word0[e] * 64, st));
+        NIDX_HIP(hipMemcpyAsync(alive.as<uint64_t>() + plan.word0[e], words.data() + at_word, (size_t)nw * 8, hipMemcpyHostToDevice, st));
+        stats.bytes_uploaded += (uint64_t)nw * 8;
+        stats.launches++;
+        at_doc += n, at_word += nw;
+    }
+    // ---- carry: the kept entries to their new offsets, and the deletions over every entry
+    if (W_new) {
+        NIDX_HIP(launch_json_sync_carry(d_word0.as<uint64_t>(), d_rows.as<JsonSyncRow>(), n_entries, W_new, idx->alive.as<uint64_t>(),
+                                        idx->doc_resource.as<uint32_t>(), remap.as<uint32_t>(), R_old, del_seq.as<long long>(), R_new, alive.as<uint64_t>(),
+                                        doc_resource.as<uint32_t>(), d_counts.as<unsigned long long>() + 1, st));
+        stats.launches++;
+    }
+    unsigned long long cleared = 0;
+    NIDX_HIP(hipMemcpyAsync(&cleared, d_counts.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost, st));
+    NIDX_HIP(hipStreamSynchronize(st));   // the stream has drained: nothing below can fail
+    stats.synchronisations++;
+    stats.bytes_downloaded += 8;
+    // ---- the host side of the new generation, then the commit
+    uint64_t n_columns = 0, released = 0;
+    for (uint32_t s : plan.dropped) released += idx->segs[s].bytes + (idx->word0[s + 1] - idx->word0[s]) * (8 + 64 * 4);
+    {
+        std::lock_guard<std::mutex> lock(idx->mu);   // (waits for a running prefilter batch, which synchronises before it returns)
+        for (uint32_t e = 0; e < n_entries; e++) {
+            if (entries[e].keep >= 0) {
+                segs[e] = std::move(idx->segs[entries[e].keep]);
+                plan.meta[e] = std::move(idx->meta[entries[e].keep]);
+            }
+            bytes += segs[e].bytes;
+            n_columns += segs[e].columns.size();
+        }
+        idx->segs.swap(segs);
+        idx->meta.swap(plan.meta);
+        idx->word0.swap(plan.word0);
+        idx->resources.swap(resources);
+        std::swap(idx->alive, alive);
+        std::swap(idx->doc_resource, doc_resource);
+        std::swap(idx->d_resources, d_resources);
+        idx->n_docs = plan.documents;
+        idx->n_columns = n_columns;
+        idx->bytes = bytes;
+        idx->uid = g_json_index_uid.fetch_add(1);
+        stats.generation = ++idx->generation;
+    }
+    stats.documents_carried = plan.documents_carried;
+    stats.docs_cleared = cleared;
+    stats.hbm_released = released;
+    stats.resources = R_new;
+    stats.resources_added = n_new_only;
+    stats.resources_dropped = R_old - n_survivors;
+    stats.kept = plan.kept, stats.added = plan.added, stats.dropped = (uint32_t)plan.dropped.size();
+    stats.deletions_applied = plan.deletions_applied;
+    if (stats_out) *stats_out = stats;
+    return NIDX_OK;   // (the old generation's buffers and the dropped segments' columns are freed as the locals go)
 } NIDX_ABI_CATCH
 
 int32_t nidx_gpu_json_prefilter_batch_resident(nidx_gpu_json_index_t *index, const nidx_gpu_json_prefilter_t *requests, uint32_t n_requests,

@@ -50,6 +50,58 @@ struct JsonScanChunk {
     std::vector<uint64_t> intervals;
 };
 
+// What nidx_gpu_json_open and nidx_gpu_json_sync check of one segment before anything is uploaded.  false: `error` holds the message,
+// which begins "<what> <s>" ("segment 3", "entry 3").
+inline bool json_check_segment(const nidx_gpu_json_segment_t &sg, const char *what, uint32_t s, std::string &error) {
+    char buf[200];
+    auto bad = [&](const char *fmt, unsigned long long a = 0, unsigned long long b = 0, unsigned long long c = 0) {
+        snprintf(buf, sizeof buf, "%s %u", what, s);
+        error = buf;
+        snprintf(buf, sizeof buf, fmt, a, b, c);
+        error += buf;
+        return false;
+    };
+    if (sg.n_docs && !sg.resource_ids) return bad(": NULL resource ids");
+    if (sg.n_columns && !sg.columns) return bad(": NULL columns");
+    for (uint32_t c = 0; c < sg.n_columns; c++) {
+        const nidx_gpu_json_column_t &col = sg.columns[c];
+        if (col.type < NIDX_JSON_STR || col.type > NIDX_JSON_DATE) return bad(" column %llu: unknown type %lld", c, (unsigned long long)(long long)col.type);
+        if ((col.path_len && !col.path) || (col.n_values && (!col.docs || !col.values))) return bad(" column %llu: NULL path, docs or values", c);
+        if (col.type == NIDX_JSON_STR && (!col.dict_offsets || (col.n_dict && col.dict_offsets[col.n_dict] && !col.dict_bytes)))
+            return bad(" column %llu: a STR column without its dictionary", c);
+        for (uint64_t i = 0; i < col.n_values; i++) {
+            if (col.docs[i] >= sg.n_docs) return bad(" column %llu: document %llu of %llu", c, col.docs[i], sg.n_docs);
+            if (i && col.docs[i] < col.docs[i - 1]) return bad(" column %llu: docs descend at value %llu", c, i);
+            if (col.type == NIDX_JSON_STR && col.values[i] >= col.n_dict) return bad(" column %llu: ordinal %llu of %llu", c, col.values[i], col.n_dict);
+        }
+    }
+    return true;
+}
+
+// The plan's view of a checked segment: its columns by (path, type) and the STR dictionaries, which must be sorted and distinct.
+inline bool json_segment_meta(const nidx_gpu_json_segment_t &sg, const char *what, uint32_t s, JsonPlanSegment &meta, std::string &error) {
+    char buf[200];
+    auto bad = [&](uint32_t c, const char *msg) {
+        snprintf(buf, sizeof buf, "%s %u column %u: %s", what, s, c, msg);
+        error = buf;
+        return false;
+    };
+    meta.column_of.clear();
+    meta.dict.assign(sg.n_columns, std::vector<std::string>());
+    for (uint32_t c = 0; c < sg.n_columns; c++) {
+        const nidx_gpu_json_column_t &col = sg.columns[c];
+        const std::string path(reinterpret_cast<const char *>(col.path), col.path_len);
+        if (!meta.column_of.emplace(std::make_pair(path, (int)col.type), c).second) return bad(c, "a second column of the same path and type");
+        if (col.type != NIDX_JSON_STR) continue;
+        for (uint32_t t = 0; t < col.n_dict; t++) {
+            if (col.dict_offsets[t + 1] < col.dict_offsets[t]) return bad(c, "dictionary offsets decrease");
+            meta.dict[c].emplace_back(reinterpret_cast<const char *>(col.dict_bytes) + col.dict_offsets[t], (size_t)(col.dict_offsets[t + 1] - col.dict_offsets[t]));
+            if (t && !(meta.dict[c][t - 1] < meta.dict[c][t])) return bad(c, "the dictionary is not sorted and distinct");
+        }
+    }
+    return true;
+}
+
 // Checks every request and fills leaves, programs and program_of.  false: `error` holds the message ("request i: ...").
 inline bool json_plan_requests(const nidx_gpu_json_prefilter_t *requests, uint32_t n_requests, JsonPlan &plan, std::string &error) {
     char buf[160];

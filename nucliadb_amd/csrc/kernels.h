@@ -832,6 +832,29 @@ hipError_t launch_json_count_rows(const uint64_t *rows, size_t row_words, uint32
 hipError_t launch_json_link(const uint64_t *table, uint32_t n_resources, const uint64_t *ids, uint32_t n, uint32_t *out, hipStream_t s);
 hipError_t launch_json_combine_rows(const JsonCombineItem *items, uint32_t n_items, uint32_t n_words, const uint32_t *doc_resource,
                                     unsigned long long *counts, hipStream_t s);
+// ---- nidx_gpu_json_sync (json_sync.hip): the open JSON index moves to a new generation on the device ---------------------------------
+// word0[n_entries + 1] and rows[n_entries] (json_sync_plan.h) describe the NEW rows; every kernel finds its entry there.
+//   mark_rows: the old ordinals named by the kept entries' documents -> bits of used[(n_old + 63) / 64 + 1] (zeroed by the caller)
+//   mark_ids:  found[i] < n_old_resources -> its bit of used
+//   rank:      word_rank[w] = the used bits below word w, w in [0, n_words); *n_used = their total
+//   table:     new_table = survivors merged with new_only[n_new_only][2] by rank; remap[n_old]; del_seq[new ordinal] = LLONG_MIN
+//   deletions: del_seq[ordinals[i]] = seqs[i] where ordinals[i] < n_resources
+//   carry:     kept entries: ordinals through remap, alive words from the old row; new entries: already in new_alive /
+//              new_doc_resource; both lose the documents whose resource has del_seq > seq(entry); *cleared += the bits cleared
+struct JsonSyncRow;
+hipError_t launch_json_sync_mark_rows(const uint64_t *word0, const JsonSyncRow *rows, uint32_t n_entries, uint64_t n_words,
+                                      const uint32_t *old_doc_resource, uint32_t n_old_resources, unsigned long long *used, hipStream_t s);
+hipError_t launch_json_sync_mark_ids(const uint32_t *found, uint32_t n, uint32_t n_old_resources, unsigned long long *used, hipStream_t s);
+hipError_t launch_json_sync_rank(const unsigned long long *used, uint32_t n_words, uint32_t *word_rank, unsigned long long *n_used, hipStream_t s);
+hipError_t launch_json_sync_table(const uint64_t *old_table, uint32_t n_old, const unsigned long long *used, const uint32_t *word_rank,
+                                  const uint64_t *new_only, uint32_t n_new_only, uint64_t *new_table, uint32_t *remap, long long *del_seq,
+                                  hipStream_t s);
+hipError_t launch_json_sync_deletions(const uint32_t *ordinals, const long long *seqs, uint32_t n, uint32_t n_resources, long long *del_seq,
+                                      hipStream_t s);
+hipError_t launch_json_sync_carry(const uint64_t *word0, const JsonSyncRow *rows, uint32_t n_entries, uint64_t n_words, const uint64_t *old_alive,
+                                  const uint32_t *old_doc_resource, const uint32_t *remap, uint32_t n_old_resources, const long long *del_seq,
+                                  uint32_t n_resources, uint64_t *new_alive, uint32_t *new_doc_resource, unsigned long long *cleared,
+                                  hipStream_t s);
 // ---- nidx_gpu_bm25_hit_terms_batch (bm25_hit_terms.hip): the accepted terms of the fuzzy query that occur in each hit ---------------
 // Query q owns the hits [q_hit_off[q], q_hit_off[q + 1]) and the set members [q_mem_off[q], q_mem_off[q + 1]) (its sets laid end to end).
 // ent_doc = the local doc ids of its hits, ascending per query, ent_hit[i] = which hit of the query entry i is.  A resident posting

@@ -318,6 +318,123 @@ def segments_c(segments: Sequence[JsonSegment]):
     return segs, keep
 
 
+# ---- generations: deletion keys, and the models of nidx_gpu_json_sync ---------------------------------------------------------------------
+_LOWER_HEX = frozenset(b"0123456789abcdef")
+_NO_ORDINAL = 0xFFFFFFFF
+_I64_MIN = -(1 << 63)
+
+
+def deletion_uuids(keys: Iterable[str]) -> List[_uuid.UUID]:
+    """JsonDeletionQueryBuilder (nidx_json/src/lib.rs:46-61) for nucliadb's spelling of a resource id, 32 lower-case hex digits: a key
+    longer than 32 bytes is cut to its first 32 (so "{uuid}/{field}" deletes by resource), the key is dropped when it is no uuid, and
+    what remains is a term over the `uuid` bytes field, compared byte by byte with the id AS IT WAS INDEXED.  So a hyphenated key (cut to
+    32 bytes it is no uuid) and an upper-case key (a uuid, but other bytes than the indexed ones) match nothing."""
+    out = []
+    for k in keys:
+        raw = k.encode()[:32]
+        if len(raw) == 32 and all(b in _LOWER_HEX for b in raw):
+            out.append(_uuid.UUID(hex=raw.decode()))
+    return out
+
+
+def _pair_ints(pairs) -> List[int]:
+    return [(int(h) << 64) | int(l) for h, l in np.asarray(pairs, np.uint64).reshape(-1, 2)]
+
+
+def _int_pairs(ints) -> np.ndarray:
+    return np.array([(u >> 64, u & _MASK) for u in ints], dtype=np.uint64).reshape(-1, 2)
+
+
+def _alive_words(bits: np.ndarray) -> np.ndarray:
+    packed = np.packbits(np.asarray(bits, bool), bitorder="little").tobytes()
+    return np.frombuffer(packed + b"\0" * (-len(packed) % 8), np.uint64).copy()
+
+
+def _alive_bits(words: np.ndarray, n: int) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(words, np.uint64).view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def _largest_seq(deletions) -> Dict[int, int]:
+    out: Dict[int, int] = {}
+    for u, s in deletions:
+        out[u.int] = max(s, out.get(u.int, _I64_MIN))
+    return out
+
+
+def open_model(segments: Sequence[JsonSegment], seqs: Sequence[int], deletions: Sequence[Tuple[_uuid.UUID, int]] = ()):
+    """The rows of a fresh index over `segments` (alive = each segment's starting alive set) after open_index_with_deletions: segment s
+    loses the documents of every deleted resource whose deletion has seq(s) < del_seq.  -> {"table": uint64 [R][2], "word0": uint64
+    [S + 1], "doc_resource": uint32 [W * 64] (UINT32_MAX in the padding), "alive": uint64 [W]}"""
+    table = sorted({d.uuid.int for sg in segments for d in sg.documents})
+    ordinal = {u: i for i, u in enumerate(table)}
+    word0 = np.zeros(len(segments) + 1, np.uint64)
+    word0[1:] = np.cumsum([(sg.n_docs + 63) // 64 for sg in segments])
+    doc_resource = np.full(int(word0[-1]) * 64, _NO_ORDINAL, np.uint32)
+    alive = np.zeros(int(word0[-1]), np.uint64)
+    for s, sg in enumerate(segments):
+        w0, w1 = int(word0[s]), int(word0[s + 1])
+        doc_resource[w0 * 64: w0 * 64 + sg.n_docs] = [ordinal[d.uuid.int] for d in sg.documents]
+        dead = {u.int for u, del_seq in deletions if seqs[s] < del_seq}
+        alive[w0:w1] = _alive_words([bool(a) and d.uuid.int not in dead for a, d in zip(sg.alive, sg.documents)])
+    return {"table": _int_pairs(table), "word0": word0, "doc_resource": doc_resource, "alive": alive}
+
+
+def sync_model(table, word0, doc_resource, alive, entries, deletions: Sequence[Tuple[_uuid.UUID, int]] = ()):
+    """A numpy model of nidx_gpu_json_sync's transform, step by step as the device does it (mark, table, carry): the old rows (as
+    open_model returns them) + entries [(keep | None, seq, JsonSegment | None)] + deletions -> the new rows, plus "cleared"."""
+    old = _pair_ints(table)
+    word0, doc_resource, alive = np.asarray(word0, np.uint64), np.asarray(doc_resource, np.uint32), np.asarray(alive, np.uint64)
+    # mark: the old ordinals the kept documents name, and the new documents' uuids the old table holds
+    used = np.zeros(len(old), bool)
+    for keep, _seq, _sg in entries:
+        if keep is not None:
+            r = doc_resource[int(word0[keep]) * 64: int(word0[keep + 1]) * 64]
+            used[r[r != _NO_ORDINAL]] = True
+    old_ordinal = {u: i for i, u in enumerate(old)}
+    new_ids = sorted({d.uuid.int for keep, _seq, sg in entries if keep is None for d in sg.documents})
+    new_only = [u for u in new_ids if u not in old_ordinal]
+    used[[old_ordinal[u] for u in new_ids if u in old_ordinal]] = True
+    # table: the survivors and the new-only uuids, each at its own rank plus the number of the other list's uuids below it
+    survivors = [u for u, keep in zip(old, used) if keep]
+    new_table = [0] * (len(survivors) + len(new_only))
+    remap = np.full(len(old), _NO_ORDINAL, np.uint32)
+    below =np.searchsorted(np.array(new_only, dtype=object), np.array(survivors, dtype=object)) if survivors and new_only else np.zeros(len(survivors), np.int64)
+    for rank, (i, u) in enumerate(zip(np.flatnonzero(used), survivors)):
+        remap[i] = rank + int(below[rank])
+        new_table[int(remap[i])] = u
+    below = np.searchsorted(np.array(survivors, dtype=object), np.array(new_only, dtype=object)) if survivors and new_only else np.zeros(len(new_only), np.int64)
+    for j, u in enumerate(new_only):
+        new_table[j + int(below[j])] = u
+    ordinal = {u: i for i, u in enumerate(new_table)}
+    del_seq = np.full(max(1, len(new_table)), _I64_MIN, np.int64)
+    for u, s in _largest_seq(deletions).items():
+        if u in ordinal:
+            del_seq[ordinal[u]] = s
+    # carry
+    new_word0 = np.zeros(len(entries) + 1, np.uint64)
+    new_word0[1:] = np.cumsum([int(word0[keep + 1] - word0[keep]) if keep is not None else (sg.n_docs + 63) // 64 for keep, _seq, sg in entries])
+    new_doc_resource = np.full(int(new_word0[-1]) * 64, _NO_ORDINAL, np.uint32)
+    new_alive = np.zeros(int(new_word0[-1]), np.uint64)
+    cleared = 0
+    for e, (keep, seq, sg) in enumerate(entries):
+        w0, w1 = int(new_word0[e]), int(new_word0[e + 1])
+        if keep is not None:
+            r = doc_resource[int(word0[keep]) * 64: int(word0[keep + 1]) * 64]
+            if len(old):
+                r = np.where(r != _NO_ORDINAL, remap[np.where(r != _NO_ORDINAL, r, 0)], _NO_ORDINAL).astype(np.uint32)
+            a = _alive_bits(alive[int(word0[keep]): int(word0[keep + 1])], (w1 - w0) * 64)
+        else:
+            r = np.full((w1 - w0) * 64, _NO_ORDINAL, np.uint32)
+            r[: sg.n_docs] = [ordinal[d.uuid.int] for d in sg.documents]
+            a = np.zeros((w1 - w0) * 64, bool)
+            a[: sg.n_docs] = sg.alive
+        clear = a & (r != _NO_ORDINAL) & (del_seq[np.minimum(r, len(del_seq) - 1)] > seq)
+        cleared += int(clear.sum())
+        new_doc_resource[w0 * 64: w1 * 64] = r
+        new_alive[w0:w1] = _alive_words(a & ~clear)
+    return {"table": _int_pairs(new_table), "word0": new_word0, "doc_resource": new_doc_resource, "alive": new_alive, "cleared": cleared}
+
+
 def requests_c(programs: Sequence[Tuple[Sequence[Tuple[int, int, int]], Sequence[JsonLeaf]]]):
     """(ops, leaves) per request -> (array of nidx_gpu_json_prefilter_t, keep-alive list)"""
     keep: list = []
@@ -463,6 +580,38 @@ class JsonSearcher:
             _lib.check(_lib.lib().nidx_gpu_json_resources_read(self._handle, out.ctypes.data, n.value, C.byref(n)))
             self._resources = [_uuid.UUID(int=(int(h) << 64) | int(l)) for h, l in out[: n.value]]
         return self._resources
+
+    def sync(self, entries: Sequence[Tuple[Optional[int], int, Optional[JsonSegment]]], deletions: Sequence[Tuple[object, int]] = ()) -> _lib.JsonSyncStatsC:
+        """nidx_gpu_json_sync: the open index moves to the generation `entries` describes, in order: (keep, seq, None) names a segment of
+        the open index, (None, seq, JsonSegment) uploads a new one (its `alive` is the starting alive set).  `deletions` are (key or
+        uuid, seq) pairs; a key goes through deletion_uuids.  A deletion applies to the segments of a lower seq.  On an error nothing has
+        changed.  Rows handles, resource links and the links' resource halves made before are stale afterwards: build them again."""
+        fresh = [sg for keep, _seq, sg in entries if keep is None and sg is not None]
+        segs, _keep = segments_c(fresh)
+        arr = (_lib.JsonSyncEntryC * max(1, len(entries)))()
+        j = 0
+        for i, (keep, seq, sg) in enumerate(entries):
+            arr[i].keep, arr[i].seq = (-1 if keep is None else keep), seq
+            if keep is None and sg is not None:
+                arr[i].segment = C.pointer(segs[j])
+                j += 1
+        dels = []
+        for key, seq in deletions:
+            dels += [(u, seq) for u in ([key] if isinstance(key, _uuid.UUID) else deletion_uuids([key]))]
+        ids = np.array([uuid_pair(u) for u, _ in dels], dtype=np.uint64).reshape(-1, 2)
+        seqs = np.array([s for _, s in dels], dtype=np.int64)
+        st = _lib.JsonSyncStatsC()
+        _lib.check(_lib.lib().nidx_gpu_json_sync(self._handle, arr, len(entries), ids.ctypes.data if len(dels) else None,
+                                                 seqs.ctypes.data if len(dels) else None, len(dels), C.byref(st)))
+        self._segments = [self._segments[keep] if keep is not None else sg for keep, _seq, sg in entries]
+        self._resources = None
+        return st
+
+    def generation(self) -> int:
+        """0 after open, + 1 per successful sync."""
+        out = C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_json_generation(self._handle, C.byref(out)))
+        return out.value
 
     def search_programs(self, programs, max_scratch_bytes: int = 0) -> JsonRows:
         reqs, _keep = requests_c(programs)
