@@ -68,6 +68,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_PREFILTER_RESOURCE_PARTS 2048 /* nidx_gpu_prefilter_link_set_resources, nidx_gpu_prefilter_term_link_set_resources, their _read_resources */
 #define NIDX_FEATURE_BM25_PREFILTERED_TICKETS 4096 /* nidx_gpu_bm25_search_submit_prefiltered / _wait_prefiltered, nidx_gpu_bm25_ticket_stats */
 #define NIDX_FEATURE_JSON_SYNC 8192 /* nidx_gpu_json_sync / nidx_gpu_json_generation */
+#define NIDX_FEATURE_RELATION_GRAPH_SEARCH 16384 /* nidx_gpu_relation_open / _close / _space_usage / _graph_search_batch */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1607,6 +1608,133 @@ int32_t nidx_gpu_json_sync(nidx_gpu_json_index_t *index, const nidx_gpu_json_syn
                            const uint64_t *deletion_ids /* [n_deletions][2] */, const int64_t *deletion_seqs, uint32_t n_deletions,
                            nidx_gpu_json_sync_stats_t *stats_out);
 int32_t nidx_gpu_json_generation(const nidx_gpu_json_index_t *index, uint64_t *generation_out);
+
+/* =====================================================================================
+ * Relation index — replaces the search half of nidx_relation::RelationSearcher (nidx_relation/src/reader.rs): a serving batch of
+ * GraphSearch requests (paths, nodes, relations) in a fixed number of launches per chunk of the batch.  All present when
+ * nidx_gpu_build_features() & NIDX_FEATURE_RELATION_GRAPH_SEARCH.
+ *
+ * Every leaf of a graph query (graph_query_parser.rs) scores a constant the host knows before the search, and a relation document is a
+ * fixed-width row of small integers, so the library sees columns of ORDINALS and trees of leaves over them; strings (normalisation,
+ * prefixes, fuzzy and word matches, the vector results) stay with the caller, who resolves them to ordinals, ordinal ranges, bitmaps
+ * and scored ordinal lists (nucliadb_amd/relation.py is that caller here, the Rust shim in production: INTEGRATION.md).
+ *
+ * THE COLUMNS of a segment, one uint32_t[n_docs] each (NIDX_REL_COL_*):
+ *    SRC_VALUE, DST_VALUE         ordinal of Schema::normalize(value) (schema.rs:123-137) in ONE byte-sorted dictionary of normalized
+ *                                 values shared by both positions: a prefix is an ordinal range
+ *    SRC_TYPE, DST_TYPE, REL_TYPE the u64 codes of io_maps.rs
+ *    SRC_SUBTYPE, DST_SUBTYPE, LABEL   ordinals of the raw strings
+ *    RESOURCE_FIELD               ordinal of the resource_field_id bytes (encode_field_id, schema.rs:23-27)
+ *    SRC_NODE, DST_NODE           ordinal of the distinct encode_node(value, type, subtype) key (schema.rs:213-265): what
+ *                                 encoded_source_id / encoded_target_id hold and TopUniqueCollector dedupes by; one dictionary for
+ *                                 both positions (nodes_graph_search merges them by the encoded key)
+ *    RELATION                     ordinal of the distinct encode_relation(type, label) key (schema.rs:365-390)
+ * plus a CSR of facet ordinals per document (NIDX_REL_COL_FACETS names its dictionary; a document lists every ancestor of its
+ * facets, as tantivy's facet field indexes them).  Ordinals are index-wide and the caller's; dict_sizes[column] bounds them. */
+enum {
+    NIDX_REL_COL_SRC_VALUE = 0, NIDX_REL_COL_DST_VALUE = 1, NIDX_REL_COL_SRC_TYPE = 2, NIDX_REL_COL_DST_TYPE = 3,
+    NIDX_REL_COL_REL_TYPE = 4, NIDX_REL_COL_SRC_SUBTYPE = 5, NIDX_REL_COL_DST_SUBTYPE = 6, NIDX_REL_COL_LABEL = 7,
+    NIDX_REL_COL_RESOURCE_FIELD = 8, NIDX_REL_COL_SRC_NODE = 9, NIDX_REL_COL_DST_NODE = 10, NIDX_REL_COL_RELATION = 11,
+    NIDX_REL_COL_FACETS = 12 /* the facet CSR: a dictionary size, not a fixed-width column */
+};
+#define NIDX_REL_N_COLUMNS 12
+#define NIDX_REL_N_DICTS 13
+enum { NIDX_REL_PATHS = 0, NIDX_REL_NODES = 1, NIDX_REL_RELATIONS = 2 };
+enum {
+    NIDX_REL_LEAF_ALL = 0, NIDX_REL_LEAF_EQ = 1, NIDX_REL_LEAF_RANGE = 2, NIDX_REL_LEAF_SET = 3, NIDX_REL_LEAF_SCORED_SET = 4,
+    NIDX_REL_LEAF_FACET = 5, NIDX_REL_LEAF_SUBQUERY = 6
+};
+#define NIDX_RELATION_MAX_TOP_K 512
+#define NIDX_RELATION_MAX_LEAVES 32  /* leaves of one boolean query, as for NIDX_BM25_SUBQUERY */
+#define NIDX_RELATION_MAX_QUERIES 16 /* boolean queries of one tree */
+
+typedef struct nidx_gpu_relation_index nidx_gpu_relation_index_t;
+typedef struct nidx_gpu_relation_segment {
+    uint32_t n_docs;
+    const uint64_t *alive_bitset;   /* NULL: every document is alive (open_index_with_deletions) */
+    const uint32_t *columns[NIDX_REL_N_COLUMNS];
+    const uint64_t *facet_offsets;  /* [n_docs + 1]; NULL: no document has a facet */
+    const uint32_t *facet_ordinals;
+} nidx_gpu_relation_segment_t;
+typedef struct nidx_gpu_relation_open_stats {
+    uint64_t documents, alive, facet_entries, bytes;
+} nidx_gpu_relation_open_stats_t;
+/* RelationSearcher::open (nidx_relation/src/lib.rs).  Segments lie one after the other over doc + base[segment] as in the BM25
+ * index; doc addresses in and out are (segment_ord << 32) | doc.  Every value is checked against dict_sizes[NIDX_REL_N_DICTS]: one
+ * out of range is NIDX_ERR_INVALID_ARGUMENT, and so are sizes that differ between the two positions of a shared dictionary
+ * (dict_sizes[SRC_NODE] != dict_sizes[DST_NODE], dict_sizes[SRC_VALUE] != dict_sizes[DST_VALUE]). */
+int32_t nidx_gpu_relation_open(const nidx_gpu_relation_segment_t *segments, uint32_t n_segments, const uint32_t *dict_sizes,
+                               nidx_gpu_relation_index_t **index_out, nidx_gpu_relation_open_stats_t *stats_out);
+void nidx_gpu_relation_close(nidx_gpu_relation_index_t *index);
+/* RelationSearcher::space_usage: bytes of HBM held by the handle. */
+int32_t nidx_gpu_relation_space_usage(const nidx_gpu_relation_index_t *index, uint64_t *bytes_out);
+
+/* A leaf {column, kind, a, b, occur, score} matches a document and scores:
+ *    ALL          always                                                              score   (AllQuery: 1.0)
+ *    EQ           col[doc] == a                                                       score
+ *    RANGE        a <= col[doc] < b                                                   score
+ *    SET          bit col[doc] of bitmap a of the batch (one bit per dictionary       score
+ *                 entry of `column`)
+ *    SCORED_SET   col[doc] is in the batch's sorted ordinal list a                    the list's score for that ordinal
+ *    FACET        the document's facet list holds ordinal a                           score
+ *    SUBQUERY     boolean query a of the same tree matches                            score x its score
+ * A tree is a list of boolean queries, children first and the root last: the convention of NIDX_BM25_SUBQUERY, with the same occurs
+ * (NIDX_OCCUR_SHOULD / MUST / MUST_NOT) and the same semantics.  Query j owns leaves [query_offsets[j], query_offsets[j + 1]), at most
+ * NIDX_RELATION_MAX_LEAVES; a SUBQUERY leaf of query j names a query < j.  A query matches when every Must leaf does and no MustNot
+ * leaf does, and, if it has no Must leaf, at least one Should leaf does (only MustNot leaves, or none: nothing matches).  Its score
+ * is the f32 sum, in leaf order, of the scores of its matching Must and Should leaves. */
+typedef struct nidx_gpu_relation_leaf {
+    uint32_t column;  /* NIDX_REL_COL_*; not read for ALL, FACET and SUBQUERY */
+    int32_t kind;     /* NIDX_REL_LEAF_* */
+    uint32_t a, b;
+    int32_t occur;    /* NIDX_OCCUR_SHOULD / MUST / MUST_NOT */
+    float score;
+} nidx_gpu_relation_leaf_t;
+typedef struct nidx_gpu_relation_tree {
+    const nidx_gpu_relation_leaf_t *leaves;
+    const uint32_t *query_offsets; /* [n_queries + 1] */
+    uint32_t n_queries;            /* 1 .. NIDX_RELATION_MAX_QUERIES */
+} nidx_gpu_relation_tree_t;
+typedef struct nidx_gpu_relation_query {
+    int32_t kind;   /* NIDX_REL_PATHS / NODES / RELATIONS */
+    uint32_t top_k; /* 0: an empty result; more than NIDX_RELATION_MAX_TOP_K: NIDX_ERR_UNSUPPORTED */
+    nidx_gpu_relation_tree_t tree;     /* NODES: the source tree of parse_bool_node */
+    nidx_gpu_relation_tree_t dst_tree; /* NODES only: the destination tree */
+} nidx_gpu_relation_query_t;
+/* The bitmaps and scored lists of a batch, each one concatenated array plus offsets; uploaded once per call. */
+typedef struct nidx_gpu_relation_sets {
+    const uint64_t *set_bits;
+    const uint64_t *set_offsets;   /* [n_sets + 1], in words; set i covers the dictionary of every column that reads it */
+    const uint32_t *list_ordinals; /* every list strictly ascending */
+    const float *list_scores;
+    const uint64_t *list_offsets;  /* [n_lists + 1] */
+    uint32_t n_sets, n_lists;
+} nidx_gpu_relation_sets_t;
+typedef struct nidx_gpu_relation_search_stats {
+    uint64_t documents_scanned; /* documents x chunks */
+    uint64_t matches;           /* (tree, alive document) pairs that matched */
+    uint64_t scratch_bytes;     /* the largest chunk's per-key arrays and partial lists */
+    uint32_t chunks, launches;  /* counted where they are issued: NIDX_RELATION_LAUNCHES_PER_CHUNK x chunks, whatever n_queries is */
+} nidx_gpu_relation_search_stats_t;
+#define NIDX_RELATION_LAUNCHES_PER_CHUNK 3 /* clear the per-key arrays, match + collect, merge / select */
+/* RelationsReaderService::graph_search (reader.rs:100-259) for a batch.  out_id[n_queries][k_max] / out_score[n_queries][k_max] with
+ * k_max = the largest top_k of the batch, out_count[n_queries].  Per query:
+ *    PATHS      paths_graph_search: TopDocs::with_limit(top_k).order_by_score() — alive matching documents by score descending, then
+ *               doc address ascending (tantivy's order); out_id = doc address
+ *    RELATIONS  relations_graph_search: the maximum score per RELATION[doc] key over the alive matching documents, the top_k keys by
+ *               (score descending, key ordinal ascending); out_id = relation-dictionary ordinal
+ *    NODES      nodes_graph_search: the source tree collected by SRC_NODE and the destination tree by DST_NODE into ONE per-key
+ *               maximum, then the same top-k; out_id = node-dictionary ordinal.  (The reference truncates each side to top_k before
+ *               it merges them: the same result.)
+ * TIES: TopUniqueN (top_unique_n.rs) leaves equal scores at the cut to HashMap iteration order and sorts with sort_unstable_by
+ * inside truncate_top_n, so the reference itself is not deterministic there; "key ordinal ascending" is this library's choice, like
+ * rank_key elsewhere.  Away from ties TopUniqueN returns exactly the top N of the per-key maxima.
+ * The batch is cut into chunks bounded by what the compiled trees take in LDS and by max_scratch_bytes (0: the library's default)
+ * for the per-key arrays and partial lists; a budget too small for one query is NIDX_ERR_UNSUPPORTED.  Safe from several threads on
+ * one index (the calls take turns on the index's scratch). */
+int32_t nidx_gpu_relation_graph_search_batch(nidx_gpu_relation_index_t *index, const nidx_gpu_relation_query_t *queries, uint32_t n_queries,
+                                             const nidx_gpu_relation_sets_t *sets, uint64_t max_scratch_bytes, uint64_t *out_id,
+                                             float *out_score, uint32_t *out_count, nidx_gpu_relation_search_stats_t *stats_out);
 
 /* Device time (HIP events on the handle's stream) spent in the scoring kernel(s) of the last
  * nidx_gpu_bm25_search call, summed over segments.  For batches of term unions with k <= 64 the scoring launch

@@ -322,6 +322,54 @@ class PrefilterCombineRequestC(C.Structure):
     _fields_ = [("text_request", C.c_uint32), ("json_request", C.c_uint32), ("op", C.c_int32)]
 
 
+FEATURE_RELATION_GRAPH_SEARCH = 16384   # nidx_gpu_build_features() bit: the resident relation index and nidx_gpu_relation_graph_search_batch
+(REL_COL_SRC_VALUE, REL_COL_DST_VALUE, REL_COL_SRC_TYPE, REL_COL_DST_TYPE, REL_COL_REL_TYPE, REL_COL_SRC_SUBTYPE, REL_COL_DST_SUBTYPE,
+ REL_COL_LABEL, REL_COL_RESOURCE_FIELD, REL_COL_SRC_NODE, REL_COL_DST_NODE, REL_COL_RELATION, REL_COL_FACETS) = range(13)
+REL_N_COLUMNS, REL_N_DICTS = 12, 13
+REL_PATHS, REL_NODES, REL_RELATIONS = 0, 1, 2
+REL_LEAF_ALL, REL_LEAF_EQ, REL_LEAF_RANGE, REL_LEAF_SET, REL_LEAF_SCORED_SET, REL_LEAF_FACET, REL_LEAF_SUBQUERY = range(7)
+RELATION_MAX_TOP_K, RELATION_MAX_LEAVES, RELATION_MAX_QUERIES, RELATION_LAUNCHES_PER_CHUNK = 512, 32, 16, 3
+OCCUR_SHOULD, OCCUR_MUST, OCCUR_MUST_NOT = 0, 1, 2   # NIDX_OCCUR_*
+
+
+class RelationSegmentC(C.Structure):
+    """nidx_gpu_relation_segment_t"""
+    _fields_ = [("n_docs", C.c_uint32), ("alive_bitset", C.c_void_p), ("columns", C.c_void_p * REL_N_COLUMNS), ("facet_offsets", C.c_void_p),
+                ("facet_ordinals", C.c_void_p)]
+
+
+class RelationOpenStatsC(C.Structure):
+    """nidx_gpu_relation_open_stats_t"""
+    _fields_ = [("documents", C.c_uint64), ("alive", C.c_uint64), ("facet_entries", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class RelationLeafC(C.Structure):
+    """nidx_gpu_relation_leaf_t"""
+    _fields_ = [("column", C.c_uint32), ("kind", C.c_int32), ("a", C.c_uint32), ("b", C.c_uint32), ("occur", C.c_int32), ("score", C.c_float)]
+
+
+class RelationTreeC(C.Structure):
+    """nidx_gpu_relation_tree_t"""
+    _fields_ = [("leaves", C.c_void_p), ("query_offsets", C.c_void_p), ("n_queries", C.c_uint32)]
+
+
+class RelationQueryC(C.Structure):
+    """nidx_gpu_relation_query_t"""
+    _fields_ = [("kind", C.c_int32), ("top_k", C.c_uint32), ("tree", RelationTreeC), ("dst_tree", RelationTreeC)]
+
+
+class RelationSetsC(C.Structure):
+    """nidx_gpu_relation_sets_t"""
+    _fields_ = [("set_bits", C.c_void_p), ("set_offsets", C.c_void_p), ("list_ordinals", C.c_void_p), ("list_scores", C.c_void_p),
+                ("list_offsets", C.c_void_p), ("n_sets", C.c_uint32), ("n_lists", C.c_uint32)]
+
+
+class RelationSearchStatsC(C.Structure):
+    """nidx_gpu_relation_search_stats_t"""
+    _fields_ = [("documents_scanned", C.c_uint64), ("matches", C.c_uint64), ("scratch_bytes", C.c_uint64), ("chunks", C.c_uint32),
+                ("launches", C.c_uint32)]
+
+
 class PrefilterCombineStatsC(C.Structure):
     """nidx_gpu_prefilter_combine_stats_t"""
     _fields_ = [("field_rows", C.c_uint32), ("resource_rows", C.c_uint32), ("launches", C.c_uint32), ("synchronisations", C.c_uint32),
@@ -555,6 +603,11 @@ SIGNATURES = {
                                                     C.POINTER(PrefilterCombineStatsC)]),
     "nidx_gpu_prefilter_rows_state": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nidx_gpu_prefilter_rows_read_resources": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_relation_open": (C.c_int32, [C.POINTER(RelationSegmentC), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(RelationOpenStatsC)]),
+    "nidx_gpu_relation_close": (None, [C.c_void_p]),
+    "nidx_gpu_relation_space_usage": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "nidx_gpu_relation_graph_search_batch": (C.c_int32, [C.c_void_p, C.POINTER(RelationQueryC), C.c_uint32, C.POINTER(RelationSetsC), C.c_uint64,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RelationSearchStatsC)]),
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nidx_gpu.h"
 #include "bm25_aux_plan.h"
 #include "bm25_work_plan.h"
 
@@ -887,5 +888,36 @@ struct HitTermsArgs {
 };
 hipError_t launch_hit_terms_count(const HitTermsArgs &a, uint32_t n_queries, unsigned long long n_hits, unsigned long long *offsets, hipStream_t s);
 hipError_t launch_hit_terms_emit(const HitTermsArgs &a, uint32_t n_queries, unsigned long long n_hits, hipStream_t s);
+
+// ---- graph search over the resident relation index (relation_search.hip; the tables' limits are in relation_plan.h) -------------------
+// Every array of the index is padded to whole tiles of REL_TILE_DOCS documents: zero columns, dead documents, empty facet lists.
+struct RelIndexView {
+    const uint32_t *cols[NIDX_REL_N_COLUMNS];   // [n_tiles * REL_TILE_DOCS]
+    const uint64_t *alive;                      // [n_tiles * REL_TILE_DOCS / 64]
+    const uint32_t *facet_offsets;              // [n_tiles * REL_TILE_DOCS + 4], into facet_ordinals
+    const uint32_t *facet_ordinals;
+    uint32_t n_tiles;
+};
+// A chunk's compiled trees.  programs[i] = (first boolean query, their number, collector | key column << 8 | lists << 16, first 64-key
+// block of its partial lists (collector 0: TopDocs) / first word of its per-key array in `best` (collector 1: TopUnique));
+// queries[i] = its leaves [x, y); leaves[i] = (column | kind << 8 | occur << 16, a, b, score bits) with a SET's a = the first word
+// of its bitmap and b = its dictionary's size, a SCORED_SET's [a, b) = its entries of the lists' arrays.
+struct RelChunkView {
+    const uint4 *programs;
+    const uint2 *queries;
+    const uint4 *leaves;
+    uint32_t n_programs, n_queries, n_leaves;
+    uint32_t column_mask;   // bit NIDX_REL_COL_*: some tree (or collector) of the chunk reads it
+};
+struct RelSetsView {
+    const uint64_t *set_bits;
+    const uint32_t *list_ordinals;
+    const float *list_scores;
+};
+// best: [REL_BEST_PAD_WORDS (the chunk's match counter, 64 bits) | the per-key arrays], zeroed by the caller on the same stream
+hipError_t launch_relation_match(const RelIndexView &ix, const RelChunkView &ck, const RelSetsView &sets, uint32_t *best, uint64_t *partial,
+                                 hipStream_t s);
+hipError_t launch_relation_finish(const uint4 *finish, uint32_t n_finish, const uint32_t *best, const uint64_t *partial, uint64_t *out_id,
+                                  float *out_score, uint32_t *out_count, uint32_t k_max, unsigned long long *matches_out, hipStream_t s);
 
 }  // namespace nidx
