@@ -69,6 +69,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_PREFILTERED_TICKETS 4096 /* nidx_gpu_bm25_search_submit_prefiltered / _wait_prefiltered, nidx_gpu_bm25_ticket_stats */
 #define NIDX_FEATURE_JSON_SYNC 8192 /* nidx_gpu_json_sync / nidx_gpu_json_generation */
 #define NIDX_FEATURE_RELATION_GRAPH_SEARCH 16384 /* nidx_gpu_relation_open / _close / _space_usage / _graph_search_batch */
+#define NIDX_FEATURE_RELATION_STRINGS 32768 /* nidx_gpu_relation_set_strings / _graph_search_strings_batch / _match_strings_batch */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -1616,8 +1617,9 @@ int32_t nidx_gpu_json_generation(const nidx_gpu_json_index_t *index, uint64_t *g
  *
  * Every leaf of a graph query (graph_query_parser.rs) scores a constant the host knows before the search, and a relation document is a
  * fixed-width row of small integers, so the library sees columns of ORDINALS and trees of leaves over them; strings (normalisation,
- * prefixes, fuzzy and word matches, the vector results) stay with the caller, who resolves them to ordinals, ordinal ranges, bitmaps
- * and scored ordinal lists (nucliadb_amd/relation.py is that caller here, the Rust shim in production: INTEGRATION.md).
+ * prefixes, the vector results) stay with the caller, who resolves them to ordinals, ordinal ranges, bitmaps and scored ordinal lists
+ * (nucliadb_amd/relation.py is that caller here, the Rust shim in production: INTEGRATION.md).  Fuzzy and word matches are either
+ * resolved by the caller the same way or, with the dictionaries resident, expanded on the device ("the string leaves" below).
  *
  * THE COLUMNS of a segment, one uint32_t[n_docs] each (NIDX_REL_COL_*):
  *    SRC_VALUE, DST_VALUE         ordinal of Schema::normalize(value) (schema.rs:123-137) in ONE byte-sorted dictionary of normalized
@@ -1735,6 +1737,87 @@ typedef struct nidx_gpu_relation_search_stats {
 int32_t nidx_gpu_relation_graph_search_batch(nidx_gpu_relation_index_t *index, const nidx_gpu_relation_query_t *queries, uint32_t n_queries,
                                              const nidx_gpu_relation_sets_t *sets, uint64_t max_scratch_bytes, uint64_t *out_id,
                                              float *out_score, uint32_t *out_count, nidx_gpu_relation_search_stats_t *stats_out);
+
+/* ---- the string leaves on the device (all present when nidx_gpu_build_features() & NIDX_FEATURE_RELATION_STRINGS) ---------------------
+ * Term::Fuzzy, Term::ExactWord and Term::FuzzyWord of graph_query_parser.rs (:535-560) walk tantivy's term dictionaries; with the
+ * dictionaries resident, a batch hands the library WORDS instead of host-built bitmaps, and RelationSearcher::suggest
+ * (nidx_relation/src/lib.rs:216-261: a Nodes search over an Or of undirected paths whose sources are fuzzy prefixes) needs nothing else.
+ *
+ * THE TABLES, in HBM for the life of the handle (nidx_gpu_relation_space_usage counts them; a second call replaces them):
+ *    value dictionary   the normalized values the SRC_VALUE / DST_VALUE ordinals index: a blob plus value_offsets
+ *                       [dict_sizes[SRC_VALUE] + 1], strictly ascending bytewise (what the ordinals already promise)
+ *    token dictionary   the distinct tokens of tantivy's "default" tokenizer over the raw node values (the term dictionary of the
+ *                       tokenized source_value / target_value fields): a blob plus token_offsets [n_tokens + 1], strictly ascending
+ *    node tokens        a CSR from node ordinal to token ordinals: node_token_offsets [dict_sizes[SRC_NODE] + 1] (from 0), node_tokens
+ *                       ascending and distinct within a node
+ * Offsets that decrease, an order that is not strict, a token ordinal >= n_tokens: NIDX_ERR_INVALID_ARGUMENT, before any upload.  The
+ * call takes its turn on the index like a search. */
+typedef struct nidx_gpu_relation_strings {
+    const uint8_t *value_bytes;
+    const uint64_t *value_offsets;
+    const uint8_t *token_bytes;
+    const uint64_t *token_offsets;
+    const uint64_t *node_token_offsets;
+    const uint32_t *node_tokens;
+    uint32_t n_tokens;
+} nidx_gpu_relation_strings_t;
+typedef struct nidx_gpu_relation_strings_stats {
+    uint64_t values, tokens, node_tokens, bytes; /* bytes: HBM the three tables hold */
+} nidx_gpu_relation_strings_stats_t;
+int32_t nidx_gpu_relation_set_strings(nidx_gpu_relation_index_t *index, const nidx_gpu_relation_strings_t *strings,
+                                      nidx_gpu_relation_strings_stats_t *stats_out);
+
+/* A batch's string leaves are PATTERNS over a shared blob of words (word w = word_bytes[word_offsets[w] .. word_offsets[w + 1])):
+ *    VALUE       Term::Fuzzy: exactly one word, already normalized by the caller, against the value dictionary; the result is a
+ *                bitmap over the VALUE dictionary (read it through SRC_VALUE / DST_VALUE)
+ *    WORDS_ANY   Term::ExactWord (a TermSetQuery): a node is in the set when any of its tokens equals any word; distance 0, no prefix
+ *    WORDS_ALL   Term::FuzzyWord: a node is in the set when every word is matched by at least one of its tokens (two words may be
+ *                satisfied by one token; a word may occur twice); both word kinds give a bitmap over the NODE dictionary
+ * A word matches a dictionary string when their optimal-string-alignment distance in Unicode scalar values (an adjacent transposition
+ * costs one edit: transposition_cost_one) is at most `distance`; with `prefix`, when that holds for some prefix of the string.
+ * Refused before any launch: a distance above 2 (NIDX_ERR_INVALID_ARGUMENT — tantivy's FuzzyTermQuery builds its automata for distances
+ * 0, 1 and 2 and errors above; restated from tantivy's documented behaviour, its source is not part of the reference tree), a word of no
+ * code points, a pattern of no words, a word of more than NIDX_RELATION_MAX_PATTERN_CPS code points (NIDX_ERR_UNSUPPORTED; the constant
+ * is what lets the match kernel's head tile and word tables fit 64 KiB of LDS), any pattern on an index without strings
+ * (NIDX_ERR_UNSUPPORTED).  The leaf's score stays the caller's: 1.0 for VALUE and WORDS_ANY, the number of words for WORDS_ALL. */
+enum { NIDX_REL_PATTERN_VALUE = 0, NIDX_REL_PATTERN_WORDS_ANY = 1, NIDX_REL_PATTERN_WORDS_ALL = 2 };
+#define NIDX_RELATION_MAX_PATTERN_CPS 48
+#define NIDX_RELATION_STRING_LAUNCHES_PER_CHUNK 2 /* match over both dictionaries, project the word patterns onto the nodes */
+typedef struct nidx_gpu_relation_pattern {
+    int32_t kind;       /* NIDX_REL_PATTERN_* */
+    uint32_t distance;  /* 0, 1 or 2 */
+    uint32_t prefix;    /* 0 or 1 */
+    uint32_t first_word, n_words;
+} nidx_gpu_relation_pattern_t;
+typedef struct nidx_gpu_relation_patterns {
+    const nidx_gpu_relation_pattern_t *patterns;
+    uint32_t n_patterns;
+    const uint8_t *word_bytes;
+    const uint64_t *word_offsets; /* [n_words + 1] */
+    uint32_t n_words;
+} nidx_gpu_relation_patterns_t;
+/* nidx_gpu_relation_search_stats_t plus the string stage.  (A struct of its own: nidx_gpu_relation_graph_search_batch keeps writing
+ * exactly what it wrote before.)  The words are cut into chunks of at most 256 words; a pass over a chunk is the match launch and, when
+ * the chunk has a word pattern, the projection launch, whatever the chunk holds; a chunk of VALUE patterns alone is one launch. */
+typedef struct nidx_gpu_relation_strings_search_stats {
+    uint64_t documents_scanned, matches, scratch_bytes; /* as in nidx_gpu_relation_search_stats_t */
+    uint32_t chunks, launches;
+    uint32_t string_chunks, string_launches; /* counted where they are issued */
+} nidx_gpu_relation_strings_search_stats_t;
+/* nidx_gpu_relation_graph_search_batch with string leaves: pattern i is set number sets->n_sets + i of the batch, and a SET leaf names
+ * it by that number.  Such a leaf must read a column of the pattern's dictionary (SRC_VALUE / DST_VALUE for VALUE, SRC_NODE / DST_NODE
+ * for the word kinds), otherwise NIDX_ERR_INVALID_ARGUMENT.  The pattern sets are expanded on the device behind the caller's sets, every
+ * string chunk in front of the first search chunk on the index's stream, with no synchronisation or read-back in between; if the sets'
+ * words together do not fit 32 bits, NIDX_ERR_UNSUPPORTED.  patterns == NULL (or no patterns): the plain call. */
+int32_t nidx_gpu_relation_graph_search_strings_batch(nidx_gpu_relation_index_t *index, const nidx_gpu_relation_query_t *queries, uint32_t n_queries,
+                                                     const nidx_gpu_relation_sets_t *sets, const nidx_gpu_relation_patterns_t *patterns,
+                                                     uint64_t max_scratch_bytes, uint64_t *out_id, float *out_score, uint32_t *out_count,
+                                                     nidx_gpu_relation_strings_search_stats_t *stats_out);
+/* The expansion alone, for a caller that wants the sets: out_offsets [n_patterns + 1], in 64-bit words, and out_bits, which the caller
+ * sizes from the dictionaries: (dict_sizes[SRC_VALUE] + 63) / 64 words for a VALUE pattern, (dict_sizes[SRC_NODE] + 63) / 64 for a word
+ * pattern, one after the other; bits past the dictionary are zero. */
+int32_t nidx_gpu_relation_match_strings_batch(nidx_gpu_relation_index_t *index, const nidx_gpu_relation_patterns_t *patterns, uint64_t *out_bits,
+                                              uint64_t *out_offsets, nidx_gpu_relation_strings_search_stats_t *stats_out);
 
 /* Device time (HIP events on the handle's stream) spent in the scoring kernel(s) of the last
  * nidx_gpu_bm25_search call, summed over segments.  For batches of term unions with k <= 64 the scoring launch

@@ -329,6 +329,10 @@ REL_N_COLUMNS, REL_N_DICTS = 12, 13
 REL_PATHS, REL_NODES, REL_RELATIONS = 0, 1, 2
 REL_LEAF_ALL, REL_LEAF_EQ, REL_LEAF_RANGE, REL_LEAF_SET, REL_LEAF_SCORED_SET, REL_LEAF_FACET, REL_LEAF_SUBQUERY = range(7)
 RELATION_MAX_TOP_K, RELATION_MAX_LEAVES, RELATION_MAX_QUERIES, RELATION_LAUNCHES_PER_CHUNK = 512, 32, 16, 3
+FEATURE_RELATION_STRINGS = 32768   # nidx_gpu_build_features() bit: the resident string tables and the pattern (string leaf) entry points
+REL_PATTERN_VALUE, REL_PATTERN_WORDS_ANY, REL_PATTERN_WORDS_ALL = 0, 1, 2
+RELATION_MAX_PATTERN_CPS, RELATION_STRING_LAUNCHES_PER_CHUNK = 48, 2
+RELATION_STRING_CHUNK_WORDS, RELATION_STRING_CHUNK_CPS = 256, 2816   # what one chunk (so: one pattern) holds: REL_STR_MAX_WORDS / REL_STR_LDS_CPS of csrc/relation_string_plan.h
 OCCUR_SHOULD, OCCUR_MUST, OCCUR_MUST_NOT = 0, 1, 2   # NIDX_OCCUR_*
 
 
@@ -368,6 +372,34 @@ class RelationSearchStatsC(C.Structure):
     """nidx_gpu_relation_search_stats_t"""
     _fields_ = [("documents_scanned", C.c_uint64), ("matches", C.c_uint64), ("scratch_bytes", C.c_uint64), ("chunks", C.c_uint32),
                 ("launches", C.c_uint32)]
+
+
+class RelationStringsC(C.Structure):
+    """nidx_gpu_relation_strings_t"""
+    _fields_ = [("value_bytes", C.c_void_p), ("value_offsets", C.c_void_p), ("token_bytes", C.c_void_p), ("token_offsets", C.c_void_p),
+                ("node_token_offsets", C.c_void_p), ("node_tokens", C.c_void_p), ("n_tokens", C.c_uint32)]
+
+
+class RelationStringsStatsC(C.Structure):
+    """nidx_gpu_relation_strings_stats_t"""
+    _fields_ = [("values", C.c_uint64), ("tokens", C.c_uint64), ("node_tokens", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class RelationPatternC(C.Structure):
+    """nidx_gpu_relation_pattern_t"""
+    _fields_ = [("kind", C.c_int32), ("distance", C.c_uint32), ("prefix", C.c_uint32), ("first_word", C.c_uint32), ("n_words", C.c_uint32)]
+
+
+class RelationPatternsC(C.Structure):
+    """nidx_gpu_relation_patterns_t"""
+    _fields_ = [("patterns", C.c_void_p), ("n_patterns", C.c_uint32), ("word_bytes", C.c_void_p), ("word_offsets", C.c_void_p),
+                ("n_words", C.c_uint32)]
+
+
+class RelationStringsSearchStatsC(C.Structure):
+    """nidx_gpu_relation_strings_search_stats_t"""
+    _fields_ = [("documents_scanned", C.c_uint64), ("matches", C.c_uint64), ("scratch_bytes", C.c_uint64), ("chunks", C.c_uint32),
+                ("launches", C.c_uint32), ("string_chunks", C.c_uint32), ("string_launches", C.c_uint32)]
 
 
 class PrefilterCombineStatsC(C.Structure):
@@ -608,6 +640,12 @@ SIGNATURES = {
     "nidx_gpu_relation_space_usage": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_relation_graph_search_batch": (C.c_int32, [C.c_void_p, C.POINTER(RelationQueryC), C.c_uint32, C.POINTER(RelationSetsC), C.c_uint64,
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RelationSearchStatsC)]),
+    "nidx_gpu_relation_set_strings": (C.c_int32, [C.c_void_p, C.POINTER(RelationStringsC), C.POINTER(RelationStringsStatsC)]),
+    "nidx_gpu_relation_graph_search_strings_batch": (C.c_int32, [C.c_void_p, C.POINTER(RelationQueryC), C.c_uint32, C.POINTER(RelationSetsC),
+                                                                 C.POINTER(RelationPatternsC), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                 C.POINTER(RelationStringsSearchStatsC)]),
+    "nidx_gpu_relation_match_strings_batch": (C.c_int32, [C.c_void_p, C.POINTER(RelationPatternsC), C.c_void_p, C.c_void_p,
+                                                          C.POINTER(RelationStringsSearchStatsC)]),
     "nidx_gpu_bm25_fuzzy_terms": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nidx_gpu_bm25_fuzzy_terms_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]),

@@ -920,4 +920,34 @@ hipError_t launch_relation_match(const RelIndexView &ix, const RelChunkView &ck,
 hipError_t launch_relation_finish(const uint4 *finish, uint32_t n_finish, const uint32_t *best, const uint64_t *partial, uint64_t *out_id,
                                   float *out_score, uint32_t *out_count, uint32_t k_max, unsigned long long *matches_out, hipStream_t s);
 
+// ---- the string leaves of a graph query over the resident dictionaries (relation_strings.hip; the limits are in relation_string_plan.h)
+// A word's table entry: meta = offset of its code points in its side's `cps` | n << 16 | distance << 24 | prefix << 26.
+struct RelStrDict {
+    const uint8_t *bytes;
+    const unsigned long long *offsets;   // [n + 1]
+    uint32_t n;
+    const uint32_t *meta, *cps;          // the chunk's words over this dictionary
+    uint32_t n_words, n_cps;
+    uint32_t head;                       // code points of an entry's head: the longest word plus the largest distance
+};
+struct RelStrMatchArgs {
+    RelStrDict value, token;
+    const uint32_t *value_rows;          // [value.n_words] the first word of each VALUE word's row in set_bits
+    unsigned long long *set_bits;        // the batch's set region; a VALUE row is (value.n + 63) / 64 words
+    unsigned long long *token_bits;      // [token.n_words][token_row_words]
+    uint32_t token_row_words;
+};
+struct RelStrProjectArgs {
+    const uint32_t *node_token_offsets;  // [n_nodes + 1]
+    const uint32_t *node_tokens;
+    uint32_t n_nodes;
+    const uint4 *patterns;               // (kind, first token word of the chunk, words, first word of the pattern's row in set_bits)
+    uint32_t n_patterns;
+    const unsigned long long *token_bits;
+    uint32_t token_row_words;
+    unsigned long long *set_bits;        // a pattern's row is (n_nodes + 63) / 64 words
+};
+hipError_t launch_relation_string_match(const RelStrMatchArgs &a, hipStream_t s);
+hipError_t launch_relation_words_project(const RelStrProjectArgs &a, hipStream_t s);
+
 }  // namespace nidx

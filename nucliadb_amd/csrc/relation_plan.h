@@ -53,9 +53,10 @@ inline RelQueryCost rel_query_cost(int32_t kind, uint32_t top_k, uint32_t n_quer
     return c;
 }
 
-// One tree against the limits, the dictionaries and the batch's sets.  false: `error` holds the message.
+// One tree against the limits, the dictionaries and the batch's sets.  false: `error` holds the message.  With `patterns`, set number
+// n_sets + p is the set pattern p expands to on the device: a bitmap over the value dictionary (VALUE) or the node dictionary (words).
 inline bool rel_check_tree(const nidx_gpu_relation_tree_t &t, const uint32_t *dict_sizes, const nidx_gpu_relation_sets_t *sets, const char *what,
-                           uint32_t i, std::string &error) {
+                           uint32_t i, std::string &error, const nidx_gpu_relation_patterns_t *patterns = nullptr) {
     char buf[200];
     auto bad = [&](const char *fmt, unsigned long long a = 0, unsigned long long b = 0) {
         snprintf(buf, sizeof buf, "query %u %s: ", i, what);
@@ -86,6 +87,13 @@ inline bool rel_check_tree(const nidx_gpu_relation_tree_t &t, const uint32_t *di
                 case NIDX_REL_LEAF_FACET:
                     break;
                 case NIDX_REL_LEAF_SET:
+                    if (lf.a >= n_sets && patterns && lf.a - n_sets < patterns->n_patterns) {
+                        const bool value = patterns->patterns[lf.a - n_sets].kind == NIDX_REL_PATTERN_VALUE;
+                        const bool fits = value ? lf.column == NIDX_REL_COL_SRC_VALUE || lf.column == NIDX_REL_COL_DST_VALUE
+                                                : lf.column == NIDX_REL_COL_SRC_NODE || lf.column == NIDX_REL_COL_DST_NODE;
+                        if (!fits) return bad("leaf %llu reads pattern set %llu through a column of another dictionary", l, lf.a);
+                        break;
+                    }
                     if (lf.a >= n_sets) return bad("leaf %llu names set %llu", l, lf.a);
                     if ((sets->set_offsets[lf.a + 1] - sets->set_offsets[lf.a]) * 64 < dict_sizes[lf.column])
                         return bad("leaf %llu: set %llu is shorter than its column's dictionary", l, lf.a);

@@ -2092,7 +2092,7 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
-           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH;
+           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {

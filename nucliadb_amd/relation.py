@@ -25,13 +25,17 @@ from . import _lib
 from ._lib import (OCCUR_MUST, OCCUR_MUST_NOT, OCCUR_SHOULD, REL_COL_DST_NODE, REL_COL_DST_SUBTYPE, REL_COL_DST_TYPE, REL_COL_DST_VALUE,
                    REL_COL_FACETS, REL_COL_LABEL, REL_COL_REL_TYPE, REL_COL_RELATION, REL_COL_RESOURCE_FIELD, REL_COL_SRC_NODE,
                    REL_COL_SRC_SUBTYPE, REL_COL_SRC_TYPE, REL_COL_SRC_VALUE, REL_LEAF_ALL, REL_LEAF_EQ, REL_LEAF_FACET, REL_LEAF_RANGE,
-                   REL_LEAF_SCORED_SET, REL_LEAF_SET, REL_LEAF_SUBQUERY, REL_N_COLUMNS, REL_N_DICTS, REL_NODES, REL_PATHS, REL_RELATIONS)
+                   REL_LEAF_SCORED_SET, REL_LEAF_SET, REL_LEAF_SUBQUERY, REL_N_COLUMNS, REL_N_DICTS, REL_NODES, REL_PATHS, REL_PATTERN_VALUE,
+                   REL_PATTERN_WORDS_ALL, REL_PATTERN_WORDS_ANY, REL_RELATIONS, RELATION_MAX_PATTERN_CPS)
 from .vector import FieldId, PrefilterResult
 
 # io_maps.rs
 NODE_TYPES = {"Entity": 0, "Label": 1, "Resource": 2, "User": 3}
 RELATION_TYPES = {"Child": 0, "About": 1, "Entity": 2, "Colab": 3, "Synonym": 4, "Other": 5}
 K1, B = np.float32(1.2), np.float32(0.75)
+MIN_SUGGEST_PREFIX_LENGTH = 2   # lib.rs: in BYTES (String::len)
+FUZZY_DISTANCE = 1              # reader.rs:33
+MAX_DEVICE_DISTANCE = 2         # the library refuses more, as tantivy's FuzzyTermQuery does
 
 
 # ---- schema.rs -----------------------------------------------------------------------------------------------------------------------------
@@ -207,6 +211,13 @@ class RelationIndexData:
         self.resource_field_ord, self.node_ord, self.relation_ord = _ordinals(self.resource_fields), _ordinals(self.nodes), _ordinals(self.relations)
         self.facet_ord = _ordinals(self.facets)
         self.node_values = [decode_node(k)[0] for k in self.nodes]
+        # the string tables of nidx_gpu_relation_set_strings: the token dictionary of the tokenized value fields and, per node, its tokens
+        node_tokens = [set(tokenize(v)) for v in self.node_values]
+        self.tokens = sorted(set().union(*node_tokens), key=lambda s: s.encode())
+        self.token_ord = _ordinals(self.tokens)
+        self.node_token_offsets = np.zeros(len(self.nodes) + 1, np.uint64)
+        self.node_token_offsets[1:] = np.cumsum([len(ts) for ts in node_tokens], dtype=np.uint64) if self.nodes else 0
+        self.node_tokens = np.array([o for ts in node_tokens for o in sorted(self.token_ord[t] for t in ts)], np.uint32)
         self.dict_sizes = np.zeros(REL_N_DICTS, np.uint32)
         for c, n in ((REL_COL_SRC_VALUE, len(self.values)), (REL_COL_DST_VALUE, len(self.values)), (REL_COL_SRC_TYPE, 256), (REL_COL_DST_TYPE, 256),
                      (REL_COL_REL_TYPE, 256), (REL_COL_SRC_SUBTYPE, len(self.subtypes)), (REL_COL_DST_SUBTYPE, len(self.subtypes)),
@@ -354,6 +365,7 @@ class Leaf:
     b: int = 0
     occur: int = OCCUR_MUST
     score: float = 1.0
+    pattern: Optional[int] = None   # a SET leaf over pattern set `pattern` of the batch (SetTable.patterns); `a` is filled when marshalled
 
 
 @dataclass
@@ -366,11 +378,21 @@ class CompiledQuery:
 
 
 class SetTable:
-    """The bitmaps and scored lists of a batch."""
+    """The bitmaps, scored lists and patterns (string leaves the library expands on the device) of a batch."""
 
     def __init__(self):
         self.sets: List[np.ndarray] = []                              # uint64 words
         self.lists: List[Tuple[np.ndarray, np.ndarray]] = []          # (uint32 ordinals ascending, float32 scores)
+        self.patterns: List[Tuple[int, int, bool, Tuple[str, ...]]] = []   # (REL_PATTERN_*, distance, prefix, words)
+        self._pattern_ord: Dict[Tuple, int] = {}
+
+    def add_pattern(self, kind: int, distance: int, prefix: bool, words: Sequence[str]) -> int:
+        """Identical patterns of a batch are one pattern."""
+        key = (kind, distance, bool(prefix), tuple(words))
+        if key not in self._pattern_ord:
+            self._pattern_ord[key] = len(self.patterns)
+            self.patterns.append(key)
+        return self._pattern_ord[key]
 
     def add_set(self, ordinals, size: int) -> int:
         words = np.zeros((size + 63) // 64, np.uint64)
@@ -401,8 +423,9 @@ _DST = dict(value=REL_COL_DST_VALUE, type=REL_COL_DST_TYPE, subtype=REL_COL_DST_
 class GraphQueryParser:
     """graph_query_parser.rs over RelationIndexData: the same queries, as _Bool / Leaf trees with the leaves' scores filled in."""
 
-    def __init__(self, data: RelationIndexData, sets: SetTable, vector_results: Optional[VectorQueryResults] = None):
+    def __init__(self, data: RelationIndexData, sets: SetTable, vector_results: Optional[VectorQueryResults] = None, device_strings: bool = False):
         self.data, self.sets, self.vector_results = data, sets, vector_results or VectorQueryResults()
+        self.device_strings = device_strings   # fuzzy and word leaves as patterns for the library, not as bitmaps built here
 
     # -- parse_bool / parse_bool_node
     def parse_bool(self, q: Optional[PathQuery]):
@@ -542,19 +565,33 @@ class GraphQueryParser:
             if distance == 0:
                 lo, hi = d.prefix_range(nv) if is_prefix else ((d.value_ord[nv], d.value_ord[nv] + 1) if nv in d.value_ord else (0, 0))
                 return Leaf(cols["value"], REL_LEAF_RANGE, lo, hi, score=1.0)
+            if self._on_device([nv], distance):
+                # over the VALUE column: the same documents, SRC_VALUE[doc] is the ordinal of the normalized value of SRC_NODE[doc]
+                return Leaf(cols["value"], REL_LEAF_SET, score=1.0, pattern=self.sets.add_pattern(REL_PATTERN_VALUE, distance, is_prefix, [nv]))
             hit = [i for i, v in enumerate(d.node_values) if within_distance(nv, normalize(v), distance, is_prefix)]
             return Leaf(cols["node"], REL_LEAF_SET, self.sets.add_set(hit, len(d.nodes)), 0, score=1.0)
         tokens = tokenize(text)
         if not tokens:
             return _nothing()
         if not fuzzy and loc == "words":                                  # Term::ExactWord: TermSetQuery, ConstScorer(1.0)
+            if self._on_device(tokens, 0):
+                return Leaf(cols["node"], REL_LEAF_SET, score=1.0, pattern=self.sets.add_pattern(REL_PATTERN_WORDS_ANY, 0, False, tokens))
             hit = [i for i, v in enumerate(d.node_values) if set(tokens) & set(tokenize(v))]
             return Leaf(cols["node"], REL_LEAF_SET, self.sets.add_set(hit, len(d.nodes)), 0, score=1.0)
         # Term::FuzzyWord: one FuzzyTermQuery per token, all of them required; each scores 1.0, so n tokens sum to n
         is_prefix = loc == "prefix_words"
+        if self._on_device(tokens, distance):
+            return Leaf(cols["node"], REL_LEAF_SET, score=float(len(tokens)),
+                        pattern=self.sets.add_pattern(REL_PATTERN_WORDS_ALL, distance, is_prefix, tokens))
         hit = [i for i, v in enumerate(d.node_values)
                if all(any(within_distance(t, w, distance, is_prefix) for w in tokenize(v)) for t in tokens)]
         return Leaf(cols["node"], REL_LEAF_SET, self.sets.add_set(hit, len(d.nodes)), 0, score=float(len(tokens)))
+
+    def _on_device(self, words: Sequence[str], distance: int) -> bool:
+        """A leaf the library would refuse (an empty word, one over the cap, a distance above 2, more words or code points than one
+        chunk of the string stage holds) is expanded here, that leaf alone."""
+        return (self.device_strings and distance <= MAX_DEVICE_DISTANCE and all(0 < len(w) <= RELATION_MAX_PATTERN_CPS for w in words) and
+                len(words) <= _lib.RELATION_STRING_CHUNK_WORDS and sum(len(w) for w in words) <= _lib.RELATION_STRING_CHUNK_CPS)
 
     # -- apply_prefilter (reader.rs:261-271) and AddMetadataFieldIterator (reader.rs:50-97)
     def apply_prefilter(self, q, prefilter: Optional[PrefilterResult]):
@@ -587,7 +624,7 @@ def flatten(q) -> List[List[Leaf]]:
             if isinstance(child, _Bool):
                 leaves.append(Leaf(0, REL_LEAF_SUBQUERY, add(child), 0, occur, 1.0))
             else:
-                leaves.append(Leaf(child.column, child.kind, child.a, child.b, occur, child.score))
+                leaves.append(Leaf(child.column, child.kind, child.a, child.b, occur, child.score, child.pattern))
         out.append(leaves)
         return len(out) - 1
 
@@ -596,11 +633,11 @@ def flatten(q) -> List[List[Leaf]]:
 
 
 def compile_request(data: RelationIndexData, sets: SetTable, request: GraphSearchRequest, prefilter: Optional[PrefilterResult] = None,
-                    vector_results: Optional[VectorQueryResults] = None) -> CompiledQuery:
+                    vector_results: Optional[VectorQueryResults] = None, device_strings: bool = False) -> CompiledQuery:
     """RelationsReaderService::graph_search up to the search itself."""
     if request.query is None:
         return CompiledQuery(request.kind, request.top_k, [[]], empty=True)
-    parser = GraphQueryParser(data, sets, vector_results)
+    parser = GraphQueryParser(data, sets, vector_results, device_strings)
     if request.kind == REL_NODES:
         src, dst = parser.parse_bool_node(request.query)
         src, dst = parser.apply_prefilter(src, prefilter), parser.apply_prefilter(dst, prefilter)
@@ -662,11 +699,25 @@ def build_response(data: RelationIndexData, kind: int, ids: Sequence[int], score
     return out
 
 
+def marshal_patterns(patterns: Sequence[Tuple[int, int, bool, Sequence[str]]], keep: list) -> _lib.RelationPatternsC:
+    """nidx_gpu_relation_patterns_t over (kind, distance, prefix, words); the buffers go to `keep`."""
+    arr = (_lib.RelationPatternC * max(len(patterns), 1))()
+    words: List[bytes] = []
+    for i, (kind, distance, prefix, ws) in enumerate(patterns):
+        arr[i] = _lib.RelationPatternC(kind, distance, 1 if prefix else 0, len(words), len(ws))
+        words += [w.encode() if isinstance(w, str) else bytes(w) for w in ws]
+    blob = np.frombuffer(b"".join(words) + b"\0", np.uint8).copy()
+    offsets = np.cumsum([0] + [len(w) for w in words]).astype(np.uint64)
+    keep += [arr, blob, offsets]
+    return _lib.RelationPatternsC(C.addressof(arr), len(patterns), blob.ctypes.data, offsets.ctypes.data, len(words))
+
+
 class _Marshalled:
     """The ctypes form of compiled queries and their sets; keeps every buffer alive."""
 
     def __init__(self, queries: Sequence[CompiledQuery], sets: SetTable):
         self.keep = []
+        self.n_sets = len(sets.sets)   # pattern i is set n_sets + i
         self.queries = (_lib.RelationQueryC * max(len(queries), 1))()
         for i, q in enumerate(queries):
             self.queries[i].kind, self.queries[i].top_k = q.kind, q.top_k
@@ -679,6 +730,7 @@ class _Marshalled:
         self.list_ordinals = cat([l[0] for l in sets.lists], np.uint32)
         self.list_scores = cat([l[1] for l in sets.lists], np.float32)
         self.list_offsets = np.cumsum([0] + [len(l[0]) for l in sets.lists]).astype(np.uint64)
+        self.patterns = marshal_patterns(sets.patterns, self.keep)
         self.sets = _lib.RelationSetsC(self.set_bits.ctypes.data, self.set_offsets.ctypes.data, self.list_ordinals.ctypes.data,
                                        self.list_scores.ctypes.data, self.list_offsets.ctypes.data, len(sets.sets), len(sets.lists))
 
@@ -688,7 +740,7 @@ class _Marshalled:
         at = 0
         for b in tree:
             for lf in b:
-                leaves[at] = _lib.RelationLeafC(lf.column, lf.kind, lf.a, lf.b, lf.occur, lf.score)
+                leaves[at] = _lib.RelationLeafC(lf.column, lf.kind, lf.a if lf.pattern is None else self.n_sets + lf.pattern, lf.b, lf.occur, lf.score)
                 at += 1
         offsets = np.cumsum([0] + [len(b) for b in tree]).astype(np.uint32)
         self.keep += [leaves, offsets]
@@ -696,7 +748,7 @@ class _Marshalled:
 
 
 class RelationSearcher:
-    """RelationSearcher (nidx_relation/src/lib.rs) over libnidx_gpu.so.  `suggest` is not part of it."""
+    """RelationSearcher (nidx_relation/src/lib.rs) over libnidx_gpu.so."""
 
     def __init__(self, data: RelationIndexData, handle):
         self.data, self._h = data, handle
@@ -726,7 +778,39 @@ class RelationSearcher:
         _lib.check(_lib.lib().nidx_gpu_relation_open(segs, len(data.segments), data.dict_sizes.ctypes.data, C.byref(h), C.byref(stats)))
         out = cls(data, h)
         out.open_stats = stats
+        out.strings_stats = None
+        if _lib.lib().nidx_gpu_build_features() & _lib.FEATURE_RELATION_STRINGS:
+            try:
+                out.set_strings()
+            except Exception:
+                out.close()
+                raise
         return out
+
+    def set_strings(self) -> None:
+        """The value dictionary, the token dictionary and the node-to-token CSR into HBM (nidx_gpu_relation_set_strings)."""
+        d = self.data
+        blob = lambda strs: (np.frombuffer(b"".join(strs) + b"\0", np.uint8).copy(), np.cumsum([0] + [len(b) for b in strs]).astype(np.uint64))
+        vb, vo = blob(d.value_bytes)
+        tb, to = blob([t.encode() for t in d.tokens])
+        nt = d.node_tokens if len(d.node_tokens) else np.zeros(1, np.uint32)
+        st = _lib.RelationStringsC(vb.ctypes.data, vo.ctypes.data, tb.ctypes.data, to.ctypes.data, d.node_token_offsets.ctypes.data, nt.ctypes.data,
+                                   len(d.tokens))
+        stats = _lib.RelationStringsStatsC()
+        _lib.check(_lib.lib().nidx_gpu_relation_set_strings(self._h, C.byref(st), C.byref(stats)))
+        self.strings_stats = stats
+
+    def match_strings(self, patterns: Sequence[Tuple[int, int, bool, Sequence[str]]]) -> List[np.ndarray]:
+        """The expansion alone: one uint64 bitmap per pattern, over the value dictionary (VALUE) or the node dictionary (the word kinds)."""
+        keep: list = []
+        pc = marshal_patterns(patterns, keep)
+        rows = [(len(self.data.values if p[0] == REL_PATTERN_VALUE else self.data.nodes) + 63) // 64 for p in patterns]
+        bits, offsets = np.zeros(max(sum(rows), 1), np.uint64), np.zeros(len(patterns) + 1, np.uint64)
+        stats = _lib.RelationStringsSearchStatsC()
+        _lib.check(_lib.lib().nidx_gpu_relation_match_strings_batch(self._h, C.byref(pc), bits.ctypes.data, offsets.ctypes.data, C.byref(stats)))
+        self.last_stats = stats
+        assert [int(o) for o in offsets] == [int(o) for o in np.cumsum([0] + rows)]
+        return [bits[int(offsets[i]):int(offsets[i + 1])] for i in range(len(patterns))]
 
     def close(self) -> None:
         if self._h:
@@ -747,6 +831,13 @@ class RelationSearcher:
         counts = np.zeros(max(n, 1), np.uint32)
         if k_max == 0:
             ids, scores = ids[:, :0], scores[:, :0]
+        if sets.patterns:   # string leaves for the device: the whole batch is still one call
+            stats = _lib.RelationStringsSearchStatsC()
+            _lib.check(_lib.lib().nidx_gpu_relation_graph_search_strings_batch(self._h, m.queries, n, C.byref(m.sets), C.byref(m.patterns),
+                                                                                max_scratch_bytes, ids.ctypes.data, scores.ctypes.data,
+                                                                                counts.ctypes.data, C.byref(stats)))
+            self.last_stats = stats
+            return ids, scores, counts[:n]
         stats = _lib.RelationSearchStatsC()   # (a struct per call: several threads may search one index)
         _lib.check(_lib.lib().nidx_gpu_relation_graph_search_batch(self._h, m.queries, n, C.byref(m.sets), max_scratch_bytes, ids.ctypes.data,
                                                                     scores.ctypes.data, counts.ctypes.data, C.byref(stats)))
@@ -754,9 +845,9 @@ class RelationSearcher:
         return ids, scores, counts[:n]
 
     def graph_search_batch(self, requests: Sequence[Tuple[GraphSearchRequest, Optional[PrefilterResult], Optional[VectorQueryResults]]],
-                           max_scratch_bytes: int = 0) -> List[GraphSearchResponse]:
+                           max_scratch_bytes: int = 0, device_strings: bool = False) -> List[GraphSearchResponse]:
         sets = SetTable()
-        compiled = [compile_request(self.data, sets, r, p, v) for r, p, v in requests]
+        compiled = [compile_request(self.data, sets, r, p, v, device_strings) for r, p, v in requests]
         live = [i for i, c in enumerate(compiled) if not c.empty]
         out = [GraphSearchResponse() for _ in compiled]
         if live:
@@ -767,5 +858,30 @@ class RelationSearcher:
         return out
 
     def graph_search(self, request: GraphSearchRequest, prefilter: Optional[PrefilterResult] = None,
-                     vector_results: Optional[VectorQueryResults] = None) -> GraphSearchResponse:
-        return self.graph_search_batch([(request, prefilter, vector_results)])[0]
+                     vector_results: Optional[VectorQueryResults] = None, device_strings: bool = False) -> GraphSearchResponse:
+        return self.graph_search_batch([(request, prefilter, vector_results)], device_strings=device_strings)[0]
+
+    def suggest_batch(self, requests: Sequence[Tuple[Sequence[str], Optional[PrefilterResult], int]]) -> List[List[RelationNode]]:
+        """RelationSearcher::suggest (lib.rs:216-261) for a serving batch of (prefixes, prefilter, top_k): ONE library call, with the
+        fuzzy prefixes expanded on the device."""
+        live = [(i, suggest_request(prefixes, top_k), prefilter) for i, (prefixes, prefilter, top_k) in enumerate(requests)]
+        live = [(i, r, p) for i, r, p in live if r is not None]
+        out: List[List[RelationNode]] = [[] for _ in requests]
+        if live:
+            for (i, _r, _p), resp in zip(live, self.graph_search_batch([(r, p, None) for _i, r, p in live], device_strings=True)):
+                out[i] = resp.nodes
+        return out
+
+    def suggest(self, prefixes: Sequence[str], prefilter: Optional[PrefilterResult] = None, top_k: int = 10) -> List[RelationNode]:
+        return self.suggest_batch([(prefixes, prefilter, top_k)])[0]
+
+
+def suggest_request(prefixes: Sequence[str], top_k: int) -> Optional[GraphSearchRequest]:
+    """The graph request RelationSearcher::suggest makes (lib.rs:216-261): prefixes of fewer than MIN_SUGGEST_PREFIX_LENGTH bytes are
+    dropped; none left: None (an empty answer without a search); else a Nodes search over an Or of undirected paths whose sources are
+    Entity nodes matched by fuzzy prefix at FUZZY_DISTANCE."""
+    kept = [p for p in prefixes if len(p.encode()) >= MIN_SUGGEST_PREFIX_LENGTH]
+    if not kept:
+        return None
+    paths = [PathQuery.Path(source=Node(p, "fuzzy", "prefix", FUZZY_DISTANCE, NODE_TYPES["Entity"]), undirected=True) for p in kept]
+    return GraphSearchRequest(PathQuery.Or(paths), REL_NODES, top_k)
