@@ -70,6 +70,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_JSON_SYNC 8192 /* nidx_gpu_json_sync / nidx_gpu_json_generation */
 #define NIDX_FEATURE_RELATION_GRAPH_SEARCH 16384 /* nidx_gpu_relation_open / _close / _space_usage / _graph_search_batch */
 #define NIDX_FEATURE_RELATION_STRINGS 32768 /* nidx_gpu_relation_set_strings / _graph_search_strings_batch / _match_strings_batch */
+#define NIDX_FEATURE_VECTOR_MAXSIM_MFMA 65536 /* nidx_gpu_vector_set_tunable "maxsim_stage" = 1: the maxsim second stage on the f32 matrix cores */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -167,7 +168,10 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * One knob DOES change results: "ef_search" (0 = the reference's constant EF_SEARCH = 30, hnsw/params.rs:46; up to 512): the
  * layer-0 search keeps max(k, ef_search) candidates.  The reference reaches its recall at 10 M vectors by searching 50 segments
  * of <= 200 k records each at ef = 30 (searcher.rs:270-287); a flat graph over the same vectors matches that recall at a larger
- * ef — bench.py reports both.  The RaBitQ arm keeps its own ef = min(100 k, 2000) (hnsw/search.rs:333-340). */
+ * ef — bench.py reports both.  The RaBitQ arm keeps its own ef = min(100 k, 2000) (hnsw/search.rs:333-340).
+ * "maxsim_stage" (present when nidx_gpu_build_features() & NIDX_FEATURE_VECTOR_MAXSIM_MFMA) changes score BITS: the second stage of
+ * every maxsim entry below — 0 (default) = the WAVE64 stage, 1 = the same stage on the f32 matrix cores, every similarity summed in
+ * NIDX_ORDER_SERIAL_FMA; any other value is NIDX_ERR_INVALID_ARGUMENT.  A ticket uses the value in force when its wait runs. */
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value);
 
 /* NIDX_METHOD_BRUTE_FORCE_MFMA: the same exact scan as a dense GEMM on the f32 matrix cores (one
@@ -321,6 +325,9 @@ typedef struct {
  * scored with maxsim_similarity (multivector.rs:33-46: sum over the query vectors of the best similarity among the
  * paragraph's vectors), those with score > min_score are ranked (score desc; ties by segment, paragraph) and cut to
  * k.  Paragraphs are de-duplicated by their address alone, like the reference (searcher.rs:375-377).
+ * Summation order of the similarities (and of |x|^2, |q|^2 for Cosine): NIDX_ORDER_WAVE64 with the tunable "maxsim_stage" = 0 (the
+ * default, maxsim_kernel), NIDX_ORDER_SERIAL_FMA with "maxsim_stage" = 1 (maxsim_mfma_list_kernel on the f32 matrix cores).  The first
+ * pass is the method the request names either way; the maximum from 0.0f and the f32 sum in query-vector order are the same in both.
  * out_segment / out_paragraph / out_score: [n_queries][k]. */
 int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
                                       uint32_t n_queries, const nidx_gpu_vector_search_params_t *params,
@@ -341,6 +348,9 @@ int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const floa
  *                The kernel holds NIDX_MAXSIM_DEVICE_CANDIDATES (2 048) first-pass hits of one query on chip; a query with more (more
  *                than 204 query vectors at k <= 10) is finished on the host by the stage nidx_gpu_vector_search_maxsim runs — the
  *                result is the same, nidx_gpu_vector_maxsim_stats counts how often that happened.
+ *                Summation order: NIDX_ORDER_WAVE64 (maxsim_rerank_kernel) with "maxsim_stage" = 0, NIDX_ORDER_SERIAL_FMA with
+ *                "maxsim_stage" = 1 — maxsim_mfma_rerank_kernel, the same stage as a packed GEMM on the f32 matrix cores plus one small
+ *                launch for the query norms; a flagged query is then finished by the matrix-core list kernel, so it has the same bits.
  * query_dimension != dimension: NIDX_ERR_INCONSISTENT_DIMENSIONS.  n_queries == 0, k == 0, no query vectors: counts of 0.
  * Queries live in host memory.  out_segment / out_paragraph / out_score: [n_queries][k]. */
 int32_t nidx_gpu_vector_search_maxsim_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,

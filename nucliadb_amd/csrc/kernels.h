@@ -67,6 +67,7 @@ struct MaxsimSegDev {
     const uint32_t *para_first, *para_num;  // [n_paragraphs]; unread when identity
     uint32_t identity;                      // paragraph p is vector p
     uint32_t n_paragraphs;
+    const float *norm2_serial;              // [n] SERIAL_FMA-order |x|^2: read by the matrix-core stage alone (cosine), else nullptr
 };
 struct MaxsimRerankArgs {
     const MaxsimSegDev *segs;      // [n_segs] in HBM, index order
@@ -78,6 +79,7 @@ struct MaxsimRerankArgs {
     const uint32_t *query_vec_offsets;   // [n_queries + 1]
     const float *queries;          // [T][dp] the RAW query rows, zero padded
     float *query_norm2;            // [T] scratch (cosine): |q|^2 of every query vector, written once per query
+    const float *query_norm2_serial;   // [T] SERIAL_FMA-order |q|^2: read by the matrix-core stage alone (cosine), else nullptr
     uint32_t dp;
     int similarity;
     float min_score;
@@ -88,6 +90,12 @@ struct MaxsimRerankArgs {
     uint32_t *out_flag;            // [n_queries] 1 = more than NIDX_MAXSIM_DEVICE_CANDIDATES hits: nothing was written, the host stage finishes it
 };
 hipError_t launch_maxsim_rerank(const MaxsimRerankArgs &a, hipStream_t s);
+// ---- the same stage on the f32 matrix cores (maxsim_mfma.hip): every similarity in the SERIAL_FMA order, all else the same ----
+hipError_t launch_maxsim_mfma_rerank(const MaxsimRerankArgs &a, hipStream_t s);
+// launch_maxsim's candidate-list form in that order: norm2_serial / q_norm2_serial are the SERIAL_FMA-order |x|^2 [n] and |q|^2 [T]
+hipError_t launch_maxsim_mfma(const float *vectors, const float *norm2_serial, uint32_t dp, int similarity, const float *queries,
+                              const float *q_norm2_serial, const uint32_t *cand_qfirst, const uint32_t *cand_qnum, const uint32_t *cand_first,
+                              const uint32_t *cand_num, uint32_t n_cand, float *out, hipStream_t s);
 hipError_t launch_para_best(const uint32_t *in_vec, const float *in_score, const uint32_t *in_count, uint32_t n_queries, uint32_t k_in,
                             const uint32_t *para_of_vec, uint32_t k, uint32_t *out_vec, float *out_score, uint32_t *out_count,
                             hipStream_t s);

@@ -12,94 +12,22 @@
 // flag and writes nothing — the host stage finishes that query alone, so the bound never changes a result.
 #include "device_common.h"
 #include "kernels.h"
+#include "maxsim_stages.h"
 
 namespace nidx {
 
-namespace {
-constexpr uint32_t kCap = NIDX_MAXSIM_DEVICE_CANDIDATES;
-constexpr uint32_t kThreads = 256, kWaves = kThreads / NIDX_WAVE;
-static_assert((kCap & (kCap - 1)) == 0 && kCap % kThreads == 0, "the LDS sorts want a power of two");
-
-// ascending bitonic sort of n2 (a power of two <= kCap) entries in LDS by (a, b); a == nullptr: by b alone
-template <bool HAS_A>
-__device__ inline void lds_bitonic(uint32_t *a, uint64_t *b, uint32_t n2, uint32_t tid) {
-    for (uint32_t size = 2; size <= n2; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (uint32_t t = tid; t < n2 / 2; t += kThreads) {
-                const uint32_t i = 2 * t - (t & (stride - 1)), j = i + stride;
-                const bool up = (i & size) == 0;
-                const uint64_t bi = b[i], bj = b[j];
-                bool gt;
-                if constexpr (HAS_A) {
-                    const uint32_t ai = a[i], aj = a[j];
-                    gt = ai != aj ? ai > aj : bi > bj;
-                    if (gt == up) { a[i] = aj; a[j] = ai; }
-                } else {
-                    gt = bi > bj;
-                }
-                if (gt == up) { b[i] = bj; b[j] = bi; }
-            }
-        }
-    __syncthreads();
-}
-}  // namespace
+using namespace maxsim_stage;
 
 __global__ __launch_bounds__(256) void maxsim_rerank_kernel(MaxsimRerankArgs a) {
     __shared__ uint64_t s_key[kCap];    // gathered hits (paragraph << 32 | segment); afterwards its memory holds the order keys
     __shared__ uint64_t s_cand[kCap];   // de-duplicated candidates (segment << 32 | paragraph)
     __shared__ float s_score[kCap];
-    __shared__ uint32_t s_n, s_pass, s_heads[kWaves];
+    __shared__ Scalars s_sc;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, q = blockIdx.x;
     const uint32_t t0 = a.query_vec_offsets[q], t1 = a.query_vec_offsets[q + 1];
-    if (tid == 0) s_n = 0, s_pass = 0;
-    __syncthreads();
-    // ---- 1. gather, sort, de-duplicate by address ----
-    for (uint32_t t = t0 + wave; t < t1; t += kWaves) {
-        const uint32_t c = min(a.hit_count[t], a.k1);
-        for (uint32_t i = lane; i < c; i += 64) {
-            const uint32_t seg = a.hit_segment[(size_t)t * a.k1 + i], para = a.hit_paragraph[(size_t)t * a.k1 + i];
-            if (seg >= a.n_segs || para >= a.segs[seg].n_paragraphs) continue;   // (no search returns such a hit)
-            const uint32_t pos = atomicAdd(&s_n, 1u);
-            if (pos < kCap) s_key[pos] = ((uint64_t)para << 32) | seg;
-        }
-    }
-    __syncthreads();
-    const uint32_t n = s_n;
-    if (n > kCap || n == 0) {
-        if (tid == 0) {
-            a.out_flag[q] = n > kCap ? 1u : 0u;
-            a.out_count[q] = 0;
-        }
-        return;
-    }
-    uint32_t n2 = 2;
-    while (n2 < n) n2 <<= 1;
-    for (uint32_t i = n + tid; i < n2; i += kThreads) s_key[i] = ~0ull;
-    lds_bitonic<false>(nullptr, s_key, n2, tid);
-    // heads of the runs of equal address, compacted in order: each wave owns a quarter of the list
-    const uint32_t w_lo = wave * (kCap / kWaves), w_hi = w_lo + kCap / kWaves;
-    uint32_t heads = 0;
-    for (uint32_t base = w_lo; base < w_hi && base < n; base += 64) {
-        const uint32_t i = base + lane;
-        const bool head = i < n && (i == 0 || (uint32_t)(s_key[i] >> 32) != (uint32_t)(s_key[i - 1] >> 32));
-        heads += (uint32_t)__popcll(__ballot(head));
-    }
-    if (lane == 0) s_heads[wave] = heads;
-    __syncthreads();
-    uint32_t at = 0, n_cand = 0;
-    for (uint32_t w = 0; w < kWaves; w++) {
-        if (w < wave) at += s_heads[w];
-        n_cand += s_heads[w];
-    }
-    for (uint32_t base = w_lo; base < w_hi && base < n; base += 64) {
-        const uint32_t i = base + lane;
-        const uint64_t key = i < n ? s_key[i] : 0ull;
-        const bool head = i < n && (i == 0 || (uint32_t)(key >> 32) != (uint32_t)(s_key[i - 1] >> 32));
-        const unsigned long long m = __ballot(head);
-        if (head) s_cand[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (key << 32) | (key >> 32);
-        at += (uint32_t)__popcll(m);
-    }
+    // ---- 1. gather, sort, de-duplicate by address (maxsim_stages.h) ----
+    const uint32_t n_cand = gather_dedup(a, q, t0, t1, s_key, s_cand, s_sc);
+    if (n_cand == 0) return;
     // ---- 2. |q|^2 once per query vector, then the candidates shared among the waves ----
     const int nj = (int)((a.dp + 255u) / 256u);
     if (a.similarity == 1)
@@ -154,36 +82,8 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(MaxsimRerankArgs a) 
         if (lane == 0) s_score[c] = summaxsim;
     }
     __syncthreads();
-    // ---- 3. `score > min_score`, (score desc, segment asc, paragraph asc), the first k ----
-    // order key: the complement of the unsigned-monotone image of the score, so that ascending = best first; what fails the cut
-    // sorts behind everything (a kept score is never NaN: `>` is false for it)
-    uint32_t *s_ord = reinterpret_cast<uint32_t *>(s_key);
-    uint32_t c2 = 2;
-    while (c2 < n_cand) c2 <<= 1;
-    for (uint32_t i = tid; i < c2; i += kThreads) {
-        const bool keep = i < n_cand && s_score[i] > a.min_score;
-        if (keep) {
-            s_ord[i] = ~((uint32_t)total_key(s_score[i]) ^ 0x80000000u);
-            atomicAdd(&s_pass, 1u);
-        } else {
-            s_ord[i] = 0xffffffffu;
-            s_cand[i] = ~0ull;
-        }
-    }
-    lds_bitonic<true>(s_ord, s_cand, c2, tid);
-    const uint32_t n_out = min(s_pass, a.k);
-    for (uint32_t i = tid; i < n_out; i += kThreads) {
-        const uint64_t ck = s_cand[i];
-        int32_t b = (int32_t)(~s_ord[i] ^ 0x80000000u);   // total_key is its own inverse
-        b ^= (int32_t)(((uint32_t)(b >> 31)) >> 1);
-        a.out_segment[(size_t)q * a.k + i] = (uint32_t)(ck >> 32);
-        a.out_paragraph[(size_t)q * a.k + i] = (uint32_t)ck;
-        a.out_score[(size_t)q * a.k + i] = __builtin_bit_cast(float, b);
-    }
-    if (tid == 0) {
-        a.out_flag[q] = 0;
-        a.out_count[q] = n_out;
-    }
+    // ---- 3. `score > min_score`, (score desc, segment asc, paragraph asc), the first k (maxsim_stages.h) ----
+    select_write(a, q, n_cand, reinterpret_cast<uint32_t *>(s_key), s_cand, s_score, s_sc);
 }
 
 hipError_t launch_maxsim_rerank(const MaxsimRerankArgs &a, hipStream_t s) {

@@ -1410,11 +1410,18 @@ int32_t VectorIndex::maxsim_rerank(const float *queries, const uint64_t *qoff, u
     NIDX_HIP(pin_maxsim_in.reserve(in_bytes));
     NIDX_HIP(scratch_maxsim_in.reserve(in_bytes));
     unsigned char *h = pin_maxsim_in.as<unsigned char>();
+    // "maxsim_stage" = 1: the matrix-core stage, with every segment's SERIAL_FMA-order norms (a segment that came by sync gets them here)
+    const bool mfma = maxsim_stage == 1, mfma_cosine = mfma && cfg.similarity == NIDX_SIMILARITY_COSINE;
     MaxsimSegDev *tab = reinterpret_cast<MaxsimSegDev *>(h);
     for (size_t s = 0; s < S; s++) {
-        const VectorSegment &seg = segs[s];
+        VectorSegment &seg = segs[s];
+        if (mfma) {
+            const int32_t rc = ensure_norm2_serial(seg, stream);
+            if (rc != NIDX_OK) return rc;
+        }
         tab[s] = MaxsimSegDev{seg.vectors.as<float>(), seg.norm2.as<float>(), seg.identity_para ? nullptr : seg.para_first.as<uint32_t>(),
-                              seg.identity_para ? nullptr : seg.para_num.as<uint32_t>(), seg.identity_para ? 1u : 0u, seg.n_paragraphs};
+                              seg.identity_para ? nullptr : seg.para_num.as<uint32_t>(), seg.identity_para ? 1u : 0u, seg.n_paragraphs,
+                              mfma_cosine ? seg.norm2_serial.as<float>() : nullptr};
     }
     uint32_t *h_off = reinterpret_cast<uint32_t *>(h + at_off);
     for (uint32_t q = 0; q <= nq; q++) h_off[q] = (uint32_t)qoff[q];
@@ -1441,11 +1448,17 @@ int32_t VectorIndex::maxsim_rerank(const float *queries, const uint64_t *qoff, u
     a.query_vec_offsets = reinterpret_cast<const uint32_t *>(din + at_off);
     a.queries = reinterpret_cast<const float *>(din + at_rows);
     a.query_norm2 = scratch_maxsim_qnorm.as<float>();
+    a.query_norm2_serial = nullptr;
+    if (mfma_cosine) {   // one more small launch in front of the re-rank, no more transfers
+        NIDX_HIP(scratch_maxsim_qnorm_serial.reserve(std::max<size_t>(T, 1) * 4));
+        NIDX_HIP(launch_serial_norms(reinterpret_cast<const float *>(din + at_rows), (uint32_t)T, dp, scratch_maxsim_qnorm_serial.as<float>(), stream));
+        a.query_norm2_serial = scratch_maxsim_qnorm_serial.as<float>();
+    }
     a.dp = dp, a.similarity = cfg.similarity, a.min_score = p.min_score, a.k = k;
     a.out_segment = dout, a.out_paragraph = dout + (size_t)nq * k;
     a.out_score = reinterpret_cast<float *>(dout + (size_t)nq * k * 2);
     a.out_count = dout + (size_t)nq * k * 3, a.out_flag = a.out_count + nq;
-    NIDX_HIP(launch_maxsim_rerank(a, stream));
+    NIDX_HIP(mfma ? launch_maxsim_mfma_rerank(a, stream) : launch_maxsim_rerank(a, stream));
     NIDX_HIP(hipMemcpyAsync(pin_maxsim_out.p, dout, out_words * 4, hipMemcpyDeviceToHost, stream));
     NIDX_HIP(hipStreamSynchronize(stream));
     const uint32_t *o = pin_maxsim_out.as<uint32_t>(), *o_cnt = o + (size_t)nq * k * 3, *o_flag = o_cnt + nq;

@@ -672,6 +672,14 @@ int32_t VectorIndex::segment_search_device(uint32_t s, const float *d_queries, u
                                          d_out_count, d_stats, vis_log2, st, d_flag_word);
 }
 
+int32_t VectorIndex::ensure_norm2_serial(VectorSegment &seg, hipStream_t st) {
+    if (cfg.similarity != NIDX_SIMILARITY_COSINE || seg.norm2_serial.p) return NIDX_OK;
+    NIDX_HIP(seg.norm2_serial.alloc((size_t)seg.n * 4));
+    NIDX_HIP(launch_serial_norms(seg.vectors.as<float>(), seg.n, seg.dp, seg.norm2_serial.as<float>(), st));
+    NIDX_HIP(hipStreamSynchronize(st));   // once per segment: its later readers run on other streams too
+    return NIDX_OK;
+}
+
 int32_t VectorIndex::scratch_acquire(hipStream_t st) {
     if (scratch_event_recorded) NIDX_HIP(hipStreamWaitEvent(st, scratch_event, 0));
     return NIDX_OK;
@@ -923,10 +931,8 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
     };
     if (method == NIDX_METHOD_BRUTE_FORCE_MFMA) {
         if (k > NIDX_MFMA_KMAX) return fail(NIDX_ERR_UNSUPPORTED, "the MFMA scan keeps at most %d hits per query (got k=%u)", NIDX_MFMA_KMAX, k);
-        if (cfg.similarity == NIDX_SIMILARITY_COSINE && !seg.norm2_serial.p) {
-            NIDX_HIP(seg.norm2_serial.alloc((size_t)seg.n * 4));
-            NIDX_HIP(launch_serial_norms(seg.vectors.as<float>(), seg.n, seg.dp, seg.norm2_serial.as<float>(), st));
-        }
+        const int32_t rc_norms = ensure_norm2_serial(seg, st);
+        if (rc_norms != NIDX_OK) return rc_norms;
         NIDX_HIP(scratch_qnorm.reserve((size_t)nq * 4));
         NIDX_HIP(launch_serial_norms(d_queries, nq, seg.dp, scratch_qnorm.as<float>(), st));
         const uint32_t stripes = mfma_scan_stripes(seg.n, nq);
@@ -2017,6 +2023,13 @@ int32_t VectorIndex::maxsim_host_stage(const float *d_queries, const uint64_t *q
             if (i == 0 || found[i].first != found[i - 1].first) cands.push_back(Cand{q, found[i].second, found[i].first});
     }
     std::vector<float> score(cands.size(), 0.f);
+    // "maxsim_stage" = 1: the list kernel of the matrix-core stage, so that a query finished here has the bits of one finished on chip
+    const bool mfma = maxsim_stage == 1, cosine = cfg.similarity == NIDX_SIMILARITY_COSINE;
+    if (mfma && cosine && !cands.empty()) {
+        const uint32_t T = (uint32_t)qoff[nq];
+        NIDX_HIP(scratch_maxsim_qnorm_serial.reserve(std::max<size_t>(T, 1) * 4));
+        NIDX_HIP(launch_serial_norms(d_queries, T, (cfg.dimension + 3u) & ~3u, scratch_maxsim_qnorm_serial.as<float>(), stream));
+    }
     for (size_t sgi = 0; sgi < segs.size(); sgi++) {
         VectorSegment &seg = segs[sgi];
         std::vector<uint32_t> meta;  // qfirst, qnum, first, num per candidate of this segment
@@ -2037,8 +2050,16 @@ int32_t VectorIndex::maxsim_host_stage(const float *d_queries, const uint64_t *q
         NIDX_HIP(scratch_cand_score.reserve(n * 4));
         NIDX_HIP(hipMemcpyAsync(scratch_cand_vec.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, stream));
         const uint32_t *dm = scratch_cand_vec.as<uint32_t>();
-        NIDX_HIP(launch_maxsim(seg.vectors.as<float>(), seg.norm2.as<float>(), seg.dp, cfg.similarity, d_queries, dm, dm + n, dm + 2 * n, dm + 3 * n,
-                               (uint32_t)n, scratch_cand_score.as<float>(), stream));
+        if (mfma) {
+            const int32_t rc = ensure_norm2_serial(seg, stream);
+            if (rc != NIDX_OK) return rc;
+            NIDX_HIP(launch_maxsim_mfma(seg.vectors.as<float>(), seg.norm2_serial.as<float>(), seg.dp, cfg.similarity, d_queries,
+                                        cosine ? scratch_maxsim_qnorm_serial.as<float>() : nullptr, dm, dm + n, dm + 2 * n, dm + 3 * n, (uint32_t)n,
+                                        scratch_cand_score.as<float>(), stream));
+        } else {
+            NIDX_HIP(launch_maxsim(seg.vectors.as<float>(), seg.norm2.as<float>(), seg.dp, cfg.similarity, d_queries, dm, dm + n, dm + 2 * n, dm + 3 * n,
+                                   (uint32_t)n, scratch_cand_score.as<float>(), stream));
+        }
         std::vector<float> sc(n);
         NIDX_HIP(hipMemcpyAsync(sc.data(), scratch_cand_score.p, n * 4, hipMemcpyDeviceToHost, stream));
         NIDX_HIP(hipStreamSynchronize(stream));
@@ -2092,7 +2113,7 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
-           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS;
+           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2205,6 +2226,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "ef_upper") {   // 0 = the reference's greedy descent (one result per upper layer)
         if (value < 0 || value > 64) return fail(NIDX_ERR_INVALID_ARGUMENT, "ef_upper must be in 0..64");
         idx->ef_upper = (uint32_t)value;
+    }
+    else if (n == "maxsim_stage") {   // the second stage of every maxsim entry: 0 = WAVE64 order (default), 1 = the f32 matrix cores (SERIAL_FMA order)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "maxsim_stage must be 0 or 1");
+        idx->maxsim_stage = (int)value;
     }
     else return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown tunable %s", name);
     return NIDX_OK;

@@ -24,7 +24,7 @@ struct VectorSegment {
     uint32_t n = 0, dim = 0, dp = 0, n_paragraphs = 0;
     DevBuf vectors;      // [n][dp] f32, zero padded
     DevBuf norm2;        // [n] f32, WAVE64-order |x|^2
-    DevBuf norm2_serial; // [n] f32, SERIAL_FMA-order |x|^2 (filled on the first MFMA scan)
+    DevBuf norm2_serial; // [n] f32, SERIAL_FMA-order |x|^2 (filled on first use: VectorIndex::ensure_norm2_serial)
     DevBuf vectors16;    // tiled bf16 copy (vector_bf16.hip "Operand layout"), filled on the first bf16 scan
     uint32_t dp16 = 0;
     DevBuf para_of_vec;  // [n] u32 (absent when identity)
@@ -184,6 +184,7 @@ struct VectorIndex {
     uint32_t ef_search = 0;   // 0 = EF_SEARCH (hnsw/params.rs:46); tunable "ef_search"
     uint32_t ef_upper = 0;    // 0 = 1: the greedy descent of hnsw/search.rs:318-324; tunable "ef_upper"
     bool closest_prefetch = true;   // tunable "closest_prefetch" (measurement)
+    int maxsim_stage = 0;           // tunable "maxsim_stage": 0 = the WAVE64 second stage of the maxsim entries, 1 = the matrix-core one (SERIAL_FMA order)
     bool serial_segments = false;   // tunable "serial_segments": the blocking search of a multi-segment index one segment at a time
     uint32_t default_vis_log2 = 13;
     uint32_t build_vis_log2 = 14;
@@ -230,7 +231,10 @@ struct VectorIndex {
                           const uint32_t *filter_of_query, uint64_t *ticket_out);
     int32_t maxsim_wait(uint64_t ticket, uint32_t *out_segment, uint32_t *out_paragraph, float *out_score, uint32_t *out_count);
     bool is_maxsim_ticket(uint64_t ticket);
-    DevBuf scratch_maxsim_in, scratch_maxsim_out, scratch_maxsim_qnorm;
+    DevBuf scratch_maxsim_in, scratch_maxsim_out, scratch_maxsim_qnorm, scratch_maxsim_qnorm_serial;
+    // the SERIAL_FMA-order |x|^2 of a cosine segment, computed on its first use by a matrix-core kernel (the MFMA scan, the maxsim
+    // stage 1); complete when this returns.  Under `mu`.
+    int32_t ensure_norm2_serial(VectorSegment &seg, hipStream_t st);
     PinBuf pin_maxsim_in, pin_maxsim_out;
     std::atomic<uint64_t> maxsim_queries{0}, maxsim_host_finished{0};   // nidx_gpu_vector_maxsim_stats
     uint64_t spill_queries = 0;  // queries re-run by the exact fallback since open (tunable "spill_queries" reads it)

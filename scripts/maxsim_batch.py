@@ -8,7 +8,11 @@ Paths (multi-vector queries/s, median of --reps runs each, in one process):
              filter's bitset (packed before the clock starts)
   new-own    the same batch in one call of the new entry, the filters as programs
 
-usage: python scripts/maxsim_batch.py [--paragraphs N] [--reps N] [--only new]
+usage: python scripts/maxsim_batch.py [--paragraphs N] [--reps N] [--only new] [--stage {0,1}] [--query-vectors N] [--similarity {dot,cosine}]
+                                       [--first-pass {auto,brute}]
+  --stage 1    the second stage on the f32 matrix cores (tunable "maxsim_stage": maxsim_mfma_rerank_kernel, SERIAL_FMA order); 0 = WAVE64
+  --query-vectors / --similarity   the second shape: 128 vectors per query, Cosine
+  --first-pass brute   exact first pass, no graph is built (the second stage sees the same kind of candidate list)
   --only new   just the unfiltered new entry (for a `rocprofv3 --kernel-trace --stats` run of its own: the time per launch of
                maxsim_rerank_kernel is read from its kernel statistics)
 Prints one line per path and a JSON line at the end.
@@ -32,7 +36,7 @@ V, D, NQ, QV, K = 8, 128, 256, 32, 10
 N_LABELS, P_LABEL = 48, 0.113
 
 
-def build_index(n_para, seed=1234567890):
+def build_index(n_para, seed=1234567890, similarity=0, graph=True):
     import torch
 
     dev = torch.device("cuda", 0)
@@ -45,16 +49,17 @@ def build_index(n_para, seed=1234567890):
     q = (x[pick] + 0.2 * torch.randn((NQ * QV, D), generator=g, device=dev)).contiguous().cpu().numpy()
     pov = np.repeat(np.arange(n_para, dtype=np.uint32), V)
     L = _lib.lib()
-    cfg = _lib.VectorConfigC(D, 0, 0, 1, 0)
+    cfg = _lib.VectorConfigC(D, similarity, 0, 1, 0)
     cseg = _lib.VectorSegmentC(x.data_ptr(), D * 4, n_para * V, pov.ctypes.data, n_para, None, 0, 0, None, 0, None, None)
     h = C.c_void_p()
     torch.cuda.synchronize()
     _lib.check(L.nidx_gpu_vector_open(C.byref(cfg), C.byref(cseg), 1, C.byref(h)))
     del x, centers
     torch.cuda.empty_cache()
-    t = time.perf_counter()
-    _lib.check(L.nidx_gpu_vector_build_hnsw(h, 0, 2))
-    print("graph built in %.1f s" % (time.perf_counter() - t), flush=True)
+    if graph:
+        t = time.perf_counter()
+        _lib.check(L.nidx_gpu_vector_build_hnsw(h, 0, 2))
+        print("graph built in %.1f s" % (time.perf_counter() - t), flush=True)
     rng = np.random.default_rng(seed)
     masks = rng.random((N_LABELS, n_para), dtype=np.float32) < P_LABEL
     lists = [np.nonzero(m)[0].astype(np.uint32) for m in masks]
@@ -88,15 +93,22 @@ def timed(fn, reps):
 
 
 def main():
+    global QV
     ap = argparse.ArgumentParser()
     ap.add_argument("--paragraphs", type=int, default=200_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="all", choices=["all", "new"])
+    ap.add_argument("--stage", type=int, default=0, choices=[0, 1])
+    ap.add_argument("--query-vectors", type=int, default=QV)
+    ap.add_argument("--similarity", default="dot", choices=["dot", "cosine"])
+    ap.add_argument("--first-pass", default="auto", choices=["auto", "brute"])
     args = ap.parse_args()
+    QV = args.query_vectors
     L = _lib.lib()
-    h, q, masks = build_index(args.paragraphs)
+    h, q, masks = build_index(args.paragraphs, similarity=int(args.similarity == "cosine"), graph=args.first_pass == "auto")
+    _lib.check(L.nidx_gpu_vector_set_tunable(h, b"maxsim_stage", args.stage))
     qoff = (QV * np.arange(NQ + 1)).astype(np.uint64)
-    params = _lib.VectorSearchParamsC(K, -1.0e30, 1, _lib.METHOD_AUTO)
+    params = _lib.VectorSearchParamsC(K, -1.0e30, 1, _lib.METHOD_AUTO if args.first_pass == "auto" else _lib.METHOD_BRUTE_FORCE)
     out_old, out_new = outputs(NQ), outputs(NQ)
 
     def old():
@@ -151,7 +163,7 @@ def main():
             print("%-8s %9.0f queries/s (median of %d; %0.f .. %.0f)" % (name, r["median_qps"], args.reps, r["min_qps"], r["max_qps"]), flush=True)
     L.nidx_gpu_vector_close(h)
     print(json.dumps({"maxsim_batch": result, "paragraphs": args.paragraphs, "vectors_per_paragraph": V, "dim": D, "queries": NQ,
-                      "vectors_per_query": QV, "k": K}))
+                      "vectors_per_query": QV, "k": K, "stage": args.stage, "similarity": args.similarity, "first_pass": args.first_pass}))
 
 
 if __name__ == "__main__":
