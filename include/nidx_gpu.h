@@ -71,6 +71,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_RELATION_GRAPH_SEARCH 16384 /* nidx_gpu_relation_open / _close / _space_usage / _graph_search_batch */
 #define NIDX_FEATURE_RELATION_STRINGS 32768 /* nidx_gpu_relation_set_strings / _graph_search_strings_batch / _match_strings_batch */
 #define NIDX_FEATURE_VECTOR_MAXSIM_MFMA 65536 /* nidx_gpu_vector_set_tunable "maxsim_stage" = 1: the maxsim second stage on the f32 matrix cores */
+#define NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA (1u << 17) /* = 131072; nidx_gpu_vector_set_tunable "pq_scan_stage" = 1: the brute-force arm of the per-query-filter searches as packed GEMMs on the f32 matrix cores */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -171,7 +172,11 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * ef — bench.py reports both.  The RaBitQ arm keeps its own ef = min(100 k, 2000) (hnsw/search.rs:333-340).
  * "maxsim_stage" (present when nidx_gpu_build_features() & NIDX_FEATURE_VECTOR_MAXSIM_MFMA) changes score BITS: the second stage of
  * every maxsim entry below — 0 (default) = the WAVE64 stage, 1 = the same stage on the f32 matrix cores, every similarity summed in
- * NIDX_ORDER_SERIAL_FMA; any other value is NIDX_ERR_INVALID_ARGUMENT.  A ticket uses the value in force when its wait runs. */
+ * NIDX_ORDER_SERIAL_FMA; any other value is NIDX_ERR_INVALID_ARGUMENT.  A ticket uses the value in force when its wait runs.
+ * "pq_scan_stage" (present with NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA) changes score BITS too: the brute-force arm of
+ * nidx_gpu_vector_search_filtered_per_query and of everything that runs through it — 0 (default) = the register-tile scan (WAVE64
+ * order), 1 = packed GEMMs on the f32 matrix cores (NIDX_ORDER_SERIAL_FMA, like NIDX_METHOD_BRUTE_FORCE_MFMA); any other value is
+ * NIDX_ERR_INVALID_ARGUMENT.  See that entry. */
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value);
 
 /* NIDX_METHOD_BRUTE_FORCE_MFMA: the same exact scan as a dense GEMM on the f32 matrix cores (one
@@ -351,6 +356,11 @@ int32_t nidx_gpu_vector_search_maxsim(nidx_gpu_vector_index_t *index, const floa
  *                Summation order: NIDX_ORDER_WAVE64 (maxsim_rerank_kernel) with "maxsim_stage" = 0, NIDX_ORDER_SERIAL_FMA with
  *                "maxsim_stage" = 1 — maxsim_mfma_rerank_kernel, the same stage as a packed GEMM on the f32 matrix cores plus one small
  *                launch for the query norms; a flagged query is then finished by the matrix-core list kernel, so it has the same bits.
+ *   "pq_scan_stage" = 1: the brute-force arm of the first pass (blocking entry and per-query tickets, which then run through the
+ *                blocking path) is the packed matrix-core scan of nidx_gpu_vector_search_filtered_per_query: a query's vectors share
+ *                its filter, so they form one GEMM over the rows that filter lets through.  The first-pass scores — and so, on ties and
+ *                near ties, the candidates — are those of NIDX_ORDER_SERIAL_FMA; k1 x (vectors of the largest paragraph) is no limit
+ *                there, k1 <= 64 is.  Together with "maxsim_stage" = 1 every bit of the entry follows NIDX_ORDER_SERIAL_FMA.
  * query_dimension != dimension: NIDX_ERR_INCONSISTENT_DIMENSIONS.  n_queries == 0, k == 0, no query vectors: counts of 0.
  * Queries live in host memory.  out_segment / out_paragraph / out_score: [n_queries][k]. */
 int32_t nidx_gpu_vector_search_maxsim_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, const uint64_t *query_vec_offsets,
@@ -401,6 +411,17 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
  *   - The filter rows of one pass stay under 1 GiB (a row of n_paragraphs bits per filter and segment, plus one per posting-list
  *     operand) and 65 535 filters: a batch whose distinct filters need more is searched in consecutive chunks of queries.
  *   - Each (segment, arm) with queries is one search plus one synchronisation: up to 4 per segment.
+ *   - Tunable "pq_scan_stage" = 1 (NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA): every query routed to the brute-force arm (forced or chosen by
+ *     use_hnsw, filtered or not) is scanned on the f32 matrix cores instead.  The arm's queries are grouped by filter; for every
+ *     filter in use the rows it lets through on the segment are packed into a list, and each group is ONE GEMM over its list
+ *     (blocks of <= 128 queries; a group of one is legal and merely inefficient: the stage is meant for batches whose queries share
+ *     filters, such as the vectors of a maxsim query or requests with the same label formula).  Scores and norms are summed in
+ *     NIDX_ORDER_SERIAL_FMA, as by NIDX_METHOD_BRUTE_FORCE_MFMA, so score bits differ from stage 0 in the last places and the
+ *     stage is never chosen silently; a query's bits do not depend on what else is in the batch.  Multi-vector segments keep k
+ *     PARAGRAPHS per query on chip, so k x (vectors of the largest paragraph) is no limit.  A page of k > 64 that reaches the arm is
+ *     NIDX_ERR_UNSUPPORTED (the message names the tunable).  The HNSW and RaBitQ arms are unchanged; the routed and prefiltered
+ *     tickets are answered by this blocking path while the stage is 1, with the same bits.  Still one search plus one
+ *     synchronisation per (segment, arm): the plan's upload, the norms of the arm's queries, three packing launches, one GEMM, one merge.
  * out_method: NULL or [n_queries][n_segments] (0 = segment not searched for that query); out_matching: NULL or
  * [n_filters][n_segments] (0 for a filter no query names). */
 int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,

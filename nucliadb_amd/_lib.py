@@ -173,6 +173,7 @@ FEATURE_JSON_SYNC = 8192   # nidx_gpu_build_features() bit: nidx_gpu_json_sync /
 FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs of nidx_gpu_vector_search_prefiltered_per_query only
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 FEATURE_VECTOR_MAXSIM_MFMA = 65536   # nidx_gpu_build_features() bit: set_tunable "maxsim_stage" = 1, the maxsim second stage on the f32 matrix cores (SERIAL_FMA order)
+FEATURE_VECTOR_PQ_SCAN_MFMA = 131072   # nidx_gpu_build_features() bit: set_tunable "pq_scan_stage" = 1, the per-query-filter brute-force arm as packed GEMMs on the f32 matrix cores (SERIAL_FMA order)
 MAXSIM_DEVICE_CANDIDATES = 2048   # NIDX_MAXSIM_DEVICE_CANDIDATES (csrc/kernels.h): first-pass hits of one query the device stage holds on chip
 
 

@@ -123,6 +123,38 @@ hipError_t launch_serial_norms(const float *rows, uint32_t n, uint32_t dp, float
 uint32_t mfma_scan_stripes(uint32_t n, uint32_t n_queries);
 hipError_t launch_mfma_scan(const MfmaScanArgs &a, uint32_t stripes, hipStream_t s);
 
+// ---- the per-query-filter exact scan as a packed GEMM on the f32 matrix cores (vector_mfma_pq.hip; planned by pq_mfma_plan.h) ----
+// `region` is the plan's scratch region of 4-byte words: block records (6 words), list records (4 words), query indices — uploaded —
+// then the packing kernels' span counts, the lists' lengths and the lists.
+struct PqPackArgs {
+    const uint64_t *filter_table;   // [rows][words] filter AND alive
+    const uint64_t *alive;          // [words]: the bitset of a list whose row is NIDX_FILTER_ROW_NONE (never read on an all-alive segment)
+    uint32_t words, n_paragraphs;
+    const uint32_t *para_first, *para_num;   // [n_paragraphs] or nullptr (paragraph p is vector p)
+    uint32_t *region;
+    uint32_t at_lists, at_totals;   // words of `region`
+    uint32_t n_packed, spans;       // lists 0 .. n_packed - 1 are filled; spans of 64 words per filter row
+};
+hipError_t launch_pq_pack(const PqPackArgs &a, hipStream_t s);   // count, scan, fill
+struct PqMfmaArgs {
+    const float *vectors;           // [n][dp]
+    const float *norm2;             // [n] SERIAL_FMA-order |x|^2 (cosine) or nullptr
+    uint32_t n, dp;
+    const float *queries;           // [n_queries][dp] the arm's compact query array
+    const float *q_norm2;           // [n_queries] SERIAL_FMA-order |q|^2
+    uint32_t n_queries;
+    const uint32_t *para_of_vec;    // multi-vector segments: [n]
+    int similarity;
+    float min_score;
+    uint32_t k;                     // <= NIDX_MFMA_KMAX
+    uint64_t *partial;              // [n_queries][lists_per_query][k]
+    uint32_t lists_per_query;       // the plan's max_stripes
+    const uint32_t *region;
+    uint32_t at_blocks, at_lists, at_totals, n_blocks;
+};
+// multi: the segment has paragraphs of more than one vector — lists of at most k distinct paragraphs, stripes cut at paragraph boundaries
+hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s);
+
 // ---- bf16-MFMA brute-force fallback with exact re-scoring (vector_bf16.hip) ----
 #define NIDX_BF16_CAND 32  /* approximate candidates kept per query before the exact re-score */
 struct Bf16ScanArgs {

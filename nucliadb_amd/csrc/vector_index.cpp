@@ -1086,6 +1086,7 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
         return reduce_paragraphs();
     }
     // brute force
+    if (pq_mfma) return segment_pq_mfma(s, d_queries, nq, k, min_score, d_out_vec, d_out_score, d_out_count, st);
     uint32_t nblk = scan_num_blocks(seg.n);
     uint32_t shared_stripes = 0;  // > 0: the shared-row scan (large batches) with that many row stripes
     // multi-vector paragraphs: the k best paragraphs are covered by the k * vmax best vectors (each better paragraph
@@ -1147,6 +1148,56 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
                                scratch_cand_count.as<uint32_t>(), st));
     NIDX_HIP(launch_para_best(scratch_cand_vec.as<uint32_t>(), scratch_cand_score.as<float>(), scratch_cand_count.as<uint32_t>(), nq, k,
                               seg.para_of_vec.as<uint32_t>(), k_out, d_out_vec, d_out_score, d_out_count, st));
+    return NIDX_OK;
+}
+
+// ---- the brute-force arm of one (segment, arm) visit of search_per_query_chunk under "pq_scan_stage" = 1 (vector_mfma_pq.hip): the
+//      plan's upload, the SERIAL_FMA norms of the segment (first use) and of the arm's queries, the packing launches, ONE GEMM launch
+//      over every block and stripe, one merge.  Multi-vector segments need no para_best_kernel: the lists hold paragraphs. ----
+int32_t VectorIndex::segment_pq_mfma(uint32_t s, const float *d_queries, uint32_t nq, uint32_t k, float min_score, uint32_t *d_out_vec,
+                                     float *d_out_score, uint32_t *d_out_count, hipStream_t st) {
+    VectorSegment &seg = segs[s];
+    const PqMfmaPlan &P = *pq_mfma;
+    if (k > NIDX_MFMA_KMAX)
+        return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query (got k=%u)", NIDX_MFMA_KMAX, k);
+    if (P.n_unplaced || P.blocks.empty()) return fail(NIDX_ERR_INTERNAL, "the packed scan of segment %u has queries without a list", s);
+    if (P.total_words > 0xffffffffull) return fail(NIDX_ERR_OUT_OF_MEMORY, "the packed lists of segment %u outgrow one scratch region", s);
+    const int32_t rc_norms = ensure_norm2_serial(seg, st);
+    if (rc_norms != NIDX_OK) return rc_norms;
+    NIDX_HIP(scratch_qnorm.reserve((size_t)nq * 4));
+    NIDX_HIP(launch_serial_norms(d_queries, nq, seg.dp, scratch_qnorm.as<float>(), st));
+    NIDX_HIP(scratch_pq_mfma.reserve(P.total_words * 4));
+    NIDX_HIP(hipMemcpyAsync(scratch_pq_mfma.p, P.upload.data(), P.upload_words * 4, hipMemcpyHostToDevice, st));
+    PqPackArgs pk;
+    pk.filter_table = pq_mfma_table;
+    pk.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
+    pk.words = (seg.n_paragraphs + 63) / 64;
+    pk.n_paragraphs = seg.n_paragraphs;
+    pk.para_first = seg.identity_para ? nullptr : seg.para_first.as<uint32_t>();
+    pk.para_num = seg.identity_para ? nullptr : seg.para_num.as<uint32_t>();
+    pk.region = scratch_pq_mfma.as<uint32_t>();
+    pk.at_lists = (uint32_t)P.at_lists, pk.at_totals = (uint32_t)P.at_totals;
+    pk.n_packed = P.n_packed, pk.spans = P.spans;
+    NIDX_HIP(launch_pq_pack(pk, st));
+    NIDX_HIP(scratch_partial.reserve((size_t)nq * P.max_stripes * k * 8));
+    PqMfmaArgs m;
+    m.vectors = seg.vectors.as<float>();
+    m.norm2 = seg.norm2_serial.as<float>();
+    m.n = seg.n, m.dp = seg.dp;
+    m.queries = d_queries;
+    m.q_norm2 = scratch_qnorm.as<float>();
+    m.n_queries = nq;
+    m.para_of_vec = seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>();
+    m.similarity = cfg.similarity;
+    m.min_score = min_score;
+    m.k = k;
+    m.partial = scratch_partial.as<uint64_t>();
+    m.lists_per_query = P.max_stripes;
+    m.region = scratch_pq_mfma.as<uint32_t>();
+    m.at_blocks = (uint32_t)P.at_blocks, m.at_lists = (uint32_t)P.at_lists, m.at_totals = (uint32_t)P.at_totals;
+    m.n_blocks = (uint32_t)P.blocks.size();
+    NIDX_HIP(launch_pq_mfma(m, seg.vmax > 1, st));
+    NIDX_HIP(launch_merge_topk(m.partial, nq, P.max_stripes, k, d_out_vec, d_out_score, d_out_count, st));
     return NIDX_OK;
 }
 
@@ -1880,6 +1931,10 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
         }
     }
     if (out_method) std::copy(method.begin(), method.end(), out_method);
+    const bool packed = pq_scan_stage == 1;   // the brute-force arm as packed GEMMs on the matrix cores (vector_mfma_pq.hip)
+    if (packed && k > NIDX_MFMA_KMAX && std::find(method.begin(), method.end(), (int32_t)NIDX_METHOD_BRUTE_FORCE) != method.end())
+        return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query in the brute-force arm (got k=%u)", NIDX_MFMA_KMAX, k);
+    PqMfmaPlan pq_plan;
 
     // ---- per segment, each arm once over the queries routed to it (gathered rows; hits scattered back to their rows) ----
     std::vector<std::vector<uint32_t>> hv(S), hc(S);
@@ -1910,7 +1965,14 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
             uint32_t *d_idx = scratch_pq_rows.as<uint32_t>();
             NIDX_HIP(hipMemcpyAsync(d_idx, idx_rows.data(), (size_t)n * 2 * 4, hipMemcpyHostToDevice, stream));
             NIDX_HIP(launch_gather_rows(scratch_queries.as<float>(), d_idx, n, dp, scratch_pq_queries.as<float>(), stream));
-            if (filtered) {   // (an arm whose queries are all unfiltered here runs the plain launches)
+            if (packed && arm == NIDX_METHOD_BRUTE_FORCE) {   // every query of the arm, filtered or not, in groups that share a row
+                const VectorSegment &seg = segs[s];
+                pq_mfma_plan(idx_rows.data() + n, n, [&](uint32_t row) -> uint32_t {   // vector rows: exact, or paragraphs x vmax at most
+                    return (uint32_t)std::min<uint64_t>(matching_of(row, s) * seg.vmax, seg.n); },
+                             seg.all_alive, words, kPqMfmaWorkgroups, pq_plan);
+                pq_mfma = &pq_plan;
+                pq_mfma_table = scratch_pq_table.as<uint64_t>() + (F ? tab_off[s] : 0);
+            } else if (filtered) {   // (an arm whose queries are all unfiltered here runs the plain launches)
                 pq_filter_row = d_idx + n;
                 pq_filter_table = scratch_pq_table.as<uint64_t>() + tab_off[s];
                 pq_filter_words = words;
@@ -1920,6 +1982,8 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
             pq_filter_row = nullptr;
             pq_filter_table = nullptr;
             pq_filter_words = 0;
+            pq_mfma = nullptr;
+            pq_mfma_table = nullptr;
             if (rc != NIDX_OK) return rc;
             const uint32_t *blk = pin_out.as<uint32_t>();
             for (uint32_t i = 0; i < n; i++) {
@@ -1959,7 +2023,8 @@ int32_t VectorIndex::routed_plan(uint32_t nq, const nidx_gpu_vector_search_param
     plan.nothing = info.nothing;
     if (rc != NIDX_OK || info.nothing) return rc;
     // ---- what the routed path leaves to the blocking one (decided before anything is queued) ----
-    plan.fallback = info.any_deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE ||
+    // ("pq_scan_stage" = 1: the blocking path answers, so that a ticket has the bits of the blocking call)
+    plan.fallback = pq_scan_stage == 1 || info.any_deep || nq > 65535u || p.method == NIDX_METHOD_RABITQ_HNSW || p.method == NIDX_METHOD_RABITQ_BRUTE_FORCE ||
                     (pf && S > 65535u);   // (the segment is a grid dimension of the table-driven filter stage)
     for (size_t s = 0; s < S && !plan.fallback; s++) {
         const VectorSegment &seg = segs[s];
@@ -2113,7 +2178,8 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_BM25_PREFILTER_BATCH | NIDX_FEATURE_BM25_HIT_TERMS | NIDX_FEATURE_PREFILTER_HANDOVER |
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
-           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA;
+           NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA |
+           NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2230,6 +2296,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "maxsim_stage") {   // the second stage of every maxsim entry: 0 = WAVE64 order (default), 1 = the f32 matrix cores (SERIAL_FMA order)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "maxsim_stage must be 0 or 1");
         idx->maxsim_stage = (int)value;
+    }
+    else if (n == "pq_scan_stage") {   // the brute-force arm of the per-query-filter searches: 0 = the register-tile scan (default), 1 = packed GEMMs on the f32 matrix cores (SERIAL_FMA order)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_stage must be 0 or 1");
+        idx->pq_scan_stage = (int)value;
     }
     else return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown tunable %s", name);
     return NIDX_OK;

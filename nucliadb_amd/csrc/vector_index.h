@@ -10,6 +10,7 @@
 #include "hnsw_graph.h"
 #include "host_common.h"
 #include "kernels.h"
+#include "pq_mfma_plan.h"
 
 namespace nidx {
 
@@ -203,6 +204,16 @@ struct VectorIndex {
     const uint32_t *pq_filter_row = nullptr;
     const uint64_t *pq_filter_table = nullptr;
     uint32_t pq_filter_words = 0;
+    // tunable "pq_scan_stage" = 1: the brute-force arm of search_per_query_chunk runs packed GEMMs on the f32 matrix cores, one per
+    // group of queries that share a filter row, over only the rows that row lets through (vector_mfma_pq.hip; SERIAL_FMA order).
+    // While pq_mfma is set, the brute-force branch of segment_search_device_scratch is segment_pq_mfma with that plan
+    int pq_scan_stage = 0;
+    const PqMfmaPlan *pq_mfma = nullptr;
+    const uint64_t *pq_mfma_table = nullptr;   // the segment's rows of the chunk's filter table
+    static constexpr uint32_t kPqMfmaWorkgroups = 512;   // what one GEMM launch aims at: two workgroups on each of 256 CUs
+    DevBuf scratch_pq_mfma;                    // the plan's region
+    int32_t segment_pq_mfma(uint32_t s, const float *d_queries, uint32_t nq, uint32_t k, float min_score, uint32_t *d_out_vec,
+                            float *d_out_score, uint32_t *d_out_count, hipStream_t st);
     DevBuf scratch_pq_table, scratch_pq_operands, scratch_pq_prog, scratch_pq_count, scratch_pq_rows, scratch_pq_queries;
     uint64_t pq_scratch_cap = 1ull << 30;   // filter + operand rows of one chunk; tunable "per_query_filter_scratch_kib" (tests: small caps)
     // the prefilter hand-over: [segment table | row pointers] of a projection launch, its two counters, the row of a deep program

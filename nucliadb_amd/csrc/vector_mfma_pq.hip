@@ -1,0 +1,384 @@
+// vector_mfma_pq.hip — the exact scan of a per-query-filter batch as a packed GEMM on the f32 matrix cores (gfx950); tunable
+// "pq_scan_stage" = 1, planned by pq_mfma_plan.h.
+//
+// The register-tile scan (vector_scan.hip, PQ = true) reads a row whenever any query of its 8-query tile passes it and is FMA-bound
+// above ~40 queries; the dense matrix-core scan (vector_mfma.hip) shares one row mask per batch.  Here the batch is cut into GROUPS of
+// queries that share a filter row, and each group is one GEMM over only the rows its filter lets through:
+//
+//   pack   (pq_count_kernel, pq_scan_kernel, pq_fill_kernel) — for every distinct filter row in use, the ascending list of the vector
+//          rows whose paragraph has its bit set (the table is filter AND alive; the alive bitset itself for unfiltered queries; on a
+//          multi-vector segment all vectors of a passing paragraph, contiguous).  One wave per span of 64 bitset words: count, an
+//          exclusive scan over the spans, fill — zero words are skipped by ballot, a set bit's slot is its rank in the word.
+//   GEMM   (pq_mfma_kernel) — workgroup = 4 waves, tile = 128 queries of one block x 128 consecutive ENTRIES of the block's list, K chunk
+//          16, v_mfma_f32_32x32x2_f32 (exact f32: every score is a k-ordered fmaf chain, NIDX_ORDER_SERIAL_FMA).  Both operands are
+//          GATHERED: the tile's row ids and the block's query ids sit in LDS, a thread keeps the two ids of each operand it stages in
+//          registers, and entries / queries past the end are zero rows that never pass.  LDS as vector_mfma.hip: even / odd-k planes,
+//          double buffered, 12-float lines.  A workgroup walks one STRIPE — a contiguous range of the list — and leaves
+//          [query][stripe][k] partial lists at the query's own index for merge_topk_kernel.
+//   epilogue, single-vector segments: f32 pre-test against the query's k-th score, exact cosine_from_sums on survivors, sorted rank-key
+//          lists in LDS.  No filter test is left: a listed row passed.
+//   epilogue, multi-vector segments (MULTI): a query's list holds at most k distinct PARAGRAPHS, each by its best vector and, on a
+//          bit-equal score, by the LAST such vector (Iterator::max_by) — what para_best_kernel makes of the full ranking.  A later
+//          vector with an equal score has a LOWER rank key than the entry it must replace, so admission compares the score (>= the
+//          k-th), and the same-paragraph rule decides; only a survivor of an unlisted paragraph has to beat the k-th key.  Paragraphs own
+//          disjoint address ranges, so the order among paragraphs does not depend on which of their vectors is listed.  Stripes start
+//          at paragraph boundaries, so no paragraph is in two stripes and the merge needs no reduction after it.
+//
+// Bounds: GEMM 2 * (queries in blocks) * (list length) * dp flop at 157.3 Tflop/s; a block reads its list's rows once per stripe walk.
+#include "device_common.h"
+#include "kernels.h"
+
+namespace nidx {
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+#define PQ_BM 128
+#define PQ_BN 128
+#define PQ_BK 16
+#define PQ_PITCH 12 /* floats per (row, parity) line: 8 + 4 pad => b128 reads hit 16 distinct slots */
+#define PQ_NO_ID 0xffffffffu
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// packing
+// ---------------------------------------------------------------------------------------------------------------------------------
+// word `lane` of span `span` of the list's bitset, bits past n_paragraphs cleared
+__device__ inline uint64_t pq_span_word(const PqPackArgs &a, uint32_t row, uint32_t span, int lane) {
+    const uint32_t w = span * 64u + (uint32_t)lane;
+    if (w >= a.words) return 0;
+    const uint64_t *bits = row == PQ_NO_ID ? a.alive : a.filter_table + (size_t)row * a.words;
+    uint64_t v = bits[w];
+    const uint32_t base = w * 64u;
+    if (base >= a.n_paragraphs) v = 0;
+    else if (a.n_paragraphs - base < 64u) v &= ~0ull >> (64u - (a.n_paragraphs - base));
+    return v;
+}
+// vector rows of the paragraphs of one word
+__device__ inline uint32_t pq_word_rows(const PqPackArgs &a, uint64_t v, uint32_t base) {
+    if (!a.para_num) return (uint32_t)__popcll(v);
+    uint32_t c = 0;
+    for (uint64_t t = v; t; t &= t - 1) c += a.para_num[base + (uint32_t)__ffsll((long long)t) - 1u];
+    return c;
+}
+__device__ inline uint32_t pq_wave_inclusive(uint32_t x, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+
+// grid (spans, packed lists), one wave: span_counts[list][span] = vector rows of the span
+__global__ __launch_bounds__(64) void pq_count_kernel(PqPackArgs a) {
+    const int lane = threadIdx.x;
+    const uint32_t *rec = a.region + a.at_lists + 4u * blockIdx.y;
+    const uint64_t v = pq_span_word(a, rec[0], blockIdx.x, lane);
+    const uint32_t c = pq_word_rows(a, v, (blockIdx.x * 64u + (uint32_t)lane) * 64u);
+    const uint32_t total = wave_reduce_u32(c, [](uint32_t x, uint32_t y) { return x + y; });
+    if (lane == 0) a.region[rec[3] + blockIdx.x] = total;
+}
+// grid (packed lists), one wave: the span counts become exclusive prefixes, totals[list] = the list's length
+__global__ __launch_bounds__(64) void pq_scan_kernel(PqPackArgs a) {
+    const int lane = threadIdx.x;
+    const uint32_t *rec = a.region + a.at_lists + 4u * blockIdx.x;
+    uint32_t *counts = a.region + rec[3];
+    uint32_t carry = 0;
+    for (uint32_t s0 = 0; s0 < a.spans; s0 += 64) {
+        const uint32_t s = s0 + (uint32_t)lane;
+        const uint32_t x = s < a.spans ? counts[s] : 0u;
+        const uint32_t incl = pq_wave_inclusive(x, lane);
+        if (s < a.spans) counts[s] = carry + incl - x;
+        carry += lane_bcast_u32(incl, 63);
+    }
+    if (lane == 0) a.region[a.at_totals + blockIdx.x] = carry;
+}
+// grid (spans, packed lists), one wave: the entries of the span, ascending
+__global__ __launch_bounds__(64) void pq_fill_kernel(PqPackArgs a) {
+    const int lane = threadIdx.x;
+    const uint32_t *rec = a.region + a.at_lists + 4u * blockIdx.y;
+    const uint32_t cap = rec[1];
+    uint32_t *out = a.region + rec[2];
+    const uint64_t v = pq_span_word(a, rec[0], blockIdx.x, lane);
+    const uint32_t c = pq_word_rows(a, v, (blockIdx.x * 64u + (uint32_t)lane) * 64u);
+    const uint32_t word_at = a.region[rec[3] + blockIdx.x] + pq_wave_inclusive(c, lane) - c;
+    unsigned long long m = __ballot(v != 0);
+    while (m) {   // one non-empty word per turn: lane b is bit b
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const uint64_t wv = lane_bcast_u64(v, src);
+        const uint32_t at = lane_bcast_u32(word_at, src);
+        const uint32_t p = (blockIdx.x * 64u + (uint32_t)src) * 64u + (uint32_t)lane;
+        const bool set = (wv >> lane) & 1ull;
+        if (!a.para_num) {
+            const uint32_t pos = at + (uint32_t)__popcll(wv & ((1ull << lane) - 1ull));
+            if (set && pos < cap) out[pos] = p;
+        } else {
+            const uint32_t num = set ? a.para_num[p] : 0u;
+            const uint32_t pos = at + pq_wave_inclusive(num, lane) - num;
+            const uint32_t first = set ? a.para_first[p] : 0u;
+            for (uint32_t i = 0; i < num; i++)
+                if (pos + i < cap) out[pos + i] = first + i;
+        }
+    }
+}
+
+hipError_t launch_pq_pack(const PqPackArgs &a, hipStream_t s) {
+    if (a.n_packed == 0 || a.spans == 0) return hipSuccess;
+    if (a.n_packed > 65535u) return hipErrorInvalidValue;   // (the lists are the grid's y dimension)
+    hipLaunchKernelGGL(pq_count_kernel, dim3(a.spans, a.n_packed), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pq_scan_kernel, dim3(a.n_packed), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pq_fill_kernel, dim3(a.spans, a.n_packed), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the packed GEMM
+// ---------------------------------------------------------------------------------------------------------------------------------
+// KMAX = 16: 71 KiB of LDS, two workgroups per CU; KMAX = 64: 117 KiB, one.
+template <int KMAX>
+struct PqShared {
+    float q[2][2][PQ_BM][PQ_PITCH];  // [stage][k parity][query][k/2]
+    float x[2][2][PQ_BN][PQ_PITCH];  // [stage][k parity][entry][k/2]
+    uint64_t lists[PQ_BM][KMAX];     // per-query sorted top-k (rank keys), owned by the query's wave
+    uint64_t thr_key[PQ_BM];         // k-th key (EMPTY while the list is short)
+    float thr_score[PQ_BM];          // its score (-inf while short; +inf: no such query)
+    float q_qq[PQ_BM], q_rinv[PQ_BM];
+    float row_xx[PQ_BN], row_rinv[PQ_BN];
+    uint32_t q_id[PQ_BM];            // the block's queries in the arm's compact query array (PQ_NO_ID past the end)
+    uint32_t row_id[PQ_BN];          // the tile's vector rows (PQ_NO_ID past the end of the stripe)
+};
+
+// 128 gathered rows x 16 floats: thread t loads float4 #(t%4) of rows ids[0] (slot t/4) and ids[1] (slot t/4 + 64)
+__device__ inline void pq_stage_load(const float *base, const uint32_t (&ids)[2], uint32_t dp, uint32_t k0, int tid, float4 (&regs)[2]) {
+    const uint32_t k = k0 + 4u * (uint32_t)(tid & 3);
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        if (ids[it] != PQ_NO_ID && k < dp) regs[it] = *reinterpret_cast<const float4 *>(base + (size_t)ids[it] * dp + k);
+        else regs[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+__device__ inline void pq_stage_store(float (&plane)[2][PQ_BM][PQ_PITCH], int tid, const float4 (&regs)[2]) {
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int row = (tid >> 2) + 64 * it;
+        const int c = 2 * (tid & 3);
+        *reinterpret_cast<float2 *>(&plane[0][row][c]) = make_float2(regs[it].x, regs[it].z);  // even k
+        *reinterpret_cast<float2 *>(&plane[1][row][c]) = make_float2(regs[it].y, regs[it].w);  // odd k
+    }
+}
+
+// the first entry at or after `pos` whose paragraph differs from the previous entry's (uniform over the workgroup)
+__device__ inline uint32_t pq_para_boundary(const uint32_t *entries, const uint32_t *para_of_vec, uint32_t n, uint32_t pos, uint32_t len) {
+    if (pos == 0 || pos >= len) return pos < len ? pos : len;
+    const uint32_t before = entries ? entries[pos - 1] : pos - 1;
+    if (before >= n) return pos;
+    const uint32_t prev = para_of_vec[before];
+    while (pos < len) {
+        const uint32_t id = entries ? entries[pos] : pos;
+        if (id >= n || para_of_vec[id] != prev) break;
+        pos++;
+    }
+    return pos;
+}
+
+template <int KMAX, bool MULTI>
+__global__ __launch_bounds__(256, (KMAX <= 16 ? 2 : 1)) void pq_mfma_kernel(PqMfmaArgs a) {
+    __shared__ PqShared<KMAX> sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, half = lane >> 5;
+    const bool cosine = a.similarity == 1;
+    const int k = (int)a.k;
+    const uint32_t nk = (a.dp + PQ_BK - 1) / PQ_BK;
+    // the block, its list and this workgroup's stripe (all uniform)
+    const uint32_t *blk = a.region + a.at_blocks + 6u * blockIdx.y;
+    const uint32_t list = blk[0], q_at = blk[1], n_q = blk[2], stripes = blk[3], stripe_len = blk[4];
+    const uint32_t *rec = a.region + a.at_lists + 4u * list;
+    const uint32_t cap = rec[1];
+    const uint32_t *entries = rec[2] == PQ_NO_ID ? nullptr : a.region + rec[2];   // nullptr: the identity list
+    uint32_t len = cap;
+    if (entries) {
+        const uint32_t filled = a.region[a.at_totals + list];
+        len = filled < cap ? filled : cap;
+    }
+    if (len > a.n) len = a.n;
+    uint32_t begin = len, end = len;
+    if (blockIdx.x < stripes) {
+        const uint64_t b = (uint64_t)blockIdx.x * stripe_len, e = b + stripe_len;
+        begin = b < len ? (uint32_t)b : len;
+        end = (blockIdx.x + 1 == stripes || e >= len) ? len : (uint32_t)e;
+        if (MULTI) {
+            begin = pq_para_boundary(entries, a.para_of_vec, a.n, begin, len);
+            end = pq_para_boundary(entries, a.para_of_vec, a.n, end, len);
+        }
+    }
+
+    if (tid < PQ_BM) {
+        uint32_t qi = (uint32_t)tid < n_q ? a.region[q_at + tid] : PQ_NO_ID;
+        if (qi >= a.n_queries) qi = PQ_NO_ID;
+        const float qq = qi != PQ_NO_ID ? a.q_norm2[qi] : 0.f;
+        sh.q_id[tid] = qi;
+        sh.q_qq[tid] = qq;
+        sh.q_rinv[tid] = qi != PQ_NO_ID ? 1.0f / sqrtf(qq) : 0.f;
+        sh.thr_key[tid] = NIDX_EMPTY_KEY;
+        sh.thr_score[tid] = qi != PQ_NO_ID ? -INFINITY : INFINITY;   // (a missing query admits nothing)
+    }
+    for (int i = tid; i < PQ_BM * KMAX; i += 256) (&sh.lists[0][0])[i] = NIDX_EMPTY_KEY;
+    __syncthreads();
+    const uint32_t qr[2] = {sh.q_id[tid >> 2], sh.q_id[(tid >> 2) + 64]};
+
+    for (uint32_t e0 = begin; e0 < end; e0 += PQ_BN) {
+        __syncthreads();  // previous tile's epilogue is done with row_* and the stage buffers
+        if (tid < PQ_BN) {
+            const uint32_t e = e0 + (uint32_t)tid;
+            uint32_t id = e < end ? (entries ? entries[e] : e) : PQ_NO_ID;
+            if (id >= a.n) id = PQ_NO_ID;
+            const float xx = (id != PQ_NO_ID && cosine) ? a.norm2[id] : 0.f;
+            sh.row_id[tid] = id;
+            sh.row_xx[tid] = xx;
+            sh.row_rinv[tid] = 1.0f / sqrtf(xx);
+        }
+        __syncthreads();
+        const uint32_t xr[2] = {sh.row_id[tid >> 2], sh.row_id[(tid >> 2) + 64]};
+        floatx16 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+
+        // software pipeline: the gathers of chunk kc+2 are issued before the MFMAs of chunk kc and written to LDS at the end of kc+1
+        float4 gq[2], gx[2], nq_[2], nx_[2];
+        pq_stage_load(a.queries, qr, a.dp, 0, tid, gq);
+        pq_stage_load(a.vectors, xr, a.dp, 0, tid, gx);
+        pq_stage_store(sh.q[0], tid, gq);
+        pq_stage_store(sh.x[0], tid, gx);
+        if (nk > 1) {
+            pq_stage_load(a.queries, qr, a.dp, PQ_BK, tid, gq);
+            pq_stage_load(a.vectors, xr, a.dp, PQ_BK, tid, gx);
+        }
+        __syncthreads();
+        for (uint32_t kc = 0; kc < nk; kc++) {
+            const int st = (int)(kc & 1);
+            if (kc + 2 < nk) {
+                pq_stage_load(a.queries, qr, a.dp, (kc + 2) * PQ_BK, tid, nq_);
+                pq_stage_load(a.vectors, xr, a.dp, (kc + 2) * PQ_BK, tid, nx_);
+            }
+            // operands of the 8 k-steps of this chunk: lane (li, half) takes parity `half`
+            const float4 a0 = *reinterpret_cast<const float4 *>(&sh.q[st][half][32 * wave + li][0]);
+            const float4 a1 = *reinterpret_cast<const float4 *>(&sh.q[st][half][32 * wave + li][4]);
+            const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const float4 b0 = *reinterpret_cast<const float4 *>(&sh.x[st][half][32 * t + li][0]);
+                const float4 b1 = *reinterpret_cast<const float4 *>(&sh.x[st][half][32 * t + li][4]);
+                const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                for (int s = 0; s < 8; s++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc[t], 0, 0, 0);
+            }
+            if (kc + 1 < nk) {
+                pq_stage_store(sh.q[st ^ 1], tid, gq);
+                pq_stage_store(sh.x[st ^ 1], tid, gx);
+            }
+#pragma unroll
+            for (int it = 0; it < 2; it++) {
+                gq[it] = nq_[it];
+                gx[it] = nx_[it];
+            }
+            __syncthreads();
+        }
+
+        // ---- epilogue: fold the 32 x 128 scores of this wave into its queries' lists ----
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int j = 32 * t + li;
+            const uint32_t row = sh.row_id[j];
+            const bool row_ok = row != PQ_NO_ID;
+            const float rinv = sh.row_rinv[j];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int qi = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const float ab = acc[t][r];
+                // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
+                const float approx = cosine ? ab * rinv * sh.q_rinv[qi] + 1e-5f : ab;
+                const bool pre = row_ok && !(approx < sh.thr_score[qi]);
+                unsigned long long m = __ballot(pre);
+                if (!m) continue;
+                float score = ab;
+                if (pre && cosine) score = cosine_from_sums(ab, sh.row_xx[j], sh.q_qq[qi]);
+                const uint64_t key = rank_key(score, row);
+                // MULTI: the score decides (an equal score may be the later vector of a listed paragraph)
+                const bool beats = MULTI ? (uint32_t)(key >> 32) >= (uint32_t)(sh.thr_key[qi] >> 32) : key > sh.thr_key[qi];
+                m = __ballot(pre && (score >= a.min_score) && beats);
+                while (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const int sq = (int)lane_bcast_u32((uint32_t)qi, src);
+                    const uint64_t nk_ = lane_bcast_u64(key, src);
+                    const uint64_t bar = sh.thr_key[sq];   // (an earlier insert of this round may have raised it)
+                    WaveSortedList l;
+                    if (!MULTI) {
+                        if (!(nk_ > bar)) continue;
+                        l.key = lane < KMAX ? sh.lists[sq][lane] : NIDX_EMPTY_KEY;
+                        l.insert(nk_, lane);
+                    } else {
+                        if ((uint32_t)(nk_ >> 32) < (uint32_t)(bar >> 32)) continue;
+                        l.key = lane < KMAX ? sh.lists[sq][lane] : NIDX_EMPTY_KEY;
+                        const uint32_t para = a.para_of_vec[rank_key_addr(nk_)];
+                        const bool same = l.key != NIDX_EMPTY_KEY && a.para_of_vec[rank_key_addr(l.key)] == para;
+                        const unsigned long long f = __ballot(same);
+                        if (f) {   // the paragraph is listed: a better vector moves it up, an equal later one becomes its representative
+                            const int at = __ffsll((long long)f) - 1;
+                            const uint64_t old = l.at(at);
+                            if ((uint32_t)(nk_ >> 32) > (uint32_t)(old >> 32)) {
+                                const uint64_t next = shfl_u64(l.key, lane < 63 ? lane + 1 : 63);
+                                if (lane >= at) l.key = lane < 63 ? next : NIDX_EMPTY_KEY;
+                                l.insert(nk_, lane);
+                            } else if ((uint32_t)(nk_ >> 32) == (uint32_t)(old >> 32) && nk_ < old) {
+                                if (lane == at) l.key = nk_;
+                            } else {
+                                continue;
+                            }
+                        } else {
+                            if (!(nk_ > bar)) continue;
+                            l.insert(nk_, lane);
+                        }
+                    }
+                    if (lane < k) sh.lists[sq][lane] = l.key;
+                    const uint64_t kth = l.at(k - 1);
+                    if (lane == 0 && kth != NIDX_EMPTY_KEY) {
+                        sh.thr_key[sq] = kth;
+                        sh.thr_score[sq] = rank_key_score(kth);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- partial lists, at the query's own index: [query][stripe][k] (a workgroup without entries leaves empty lists) ----
+    for (int i = tid; i < PQ_BM * k; i += 256) {
+        const int q = i / k, e = i % k;
+        const uint32_t qi = sh.q_id[q];
+        if (qi != PQ_NO_ID) a.partial[((size_t)qi * a.lists_per_query + blockIdx.x) * k + e] = sh.lists[q][e];
+    }
+}
+
+hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s) {
+    if (a.n_blocks == 0 || a.lists_per_query == 0) return hipSuccess;
+    if (a.k == 0 || a.k > NIDX_MFMA_KMAX || (multi && !a.para_of_vec)) return hipErrorInvalidValue;
+    // the grid's y dimension carries the blocks: more than 65 535 of them (a chunk of that many singleton groups) go in slices
+    for (uint32_t b0 = 0; b0 < a.n_blocks; b0 += 65535u) {
+        PqMfmaArgs part = a;
+        part.at_blocks = a.at_blocks + 6u * b0;
+        part.n_blocks = a.n_blocks - b0 < 65535u ? a.n_blocks - b0 : 65535u;
+        const dim3 grid(a.lists_per_query, part.n_blocks);
+        if (a.k <= 16) {
+            if (multi) hipLaunchKernelGGL((pq_mfma_kernel<16, true>), grid, dim3(256), 0, s, part);
+            else hipLaunchKernelGGL((pq_mfma_kernel<16, false>), grid, dim3(256), 0, s, part);
+        } else {
+            if (multi) hipLaunchKernelGGL((pq_mfma_kernel<NIDX_MFMA_KMAX, true>), grid, dim3(256), 0, s, part);
+            else hipLaunchKernelGGL((pq_mfma_kernel<NIDX_MFMA_KMAX, false>), grid, dim3(256), 0, s, part);
+        }
+    }
+    return hipGetLastError();
+}
+
+}  // namespace nidx

@@ -939,6 +939,16 @@ class VectorSearcher:
         _lib.check(_lib.lib().nidx_gpu_vector_generation(self._handle, C.byref(out)))
         return out.value
 
+    def set_tunable(self, name: str, value: int) -> None:
+        """nidx_gpu_vector_set_tunable.  Two tunables change score BITS (NIDX_ORDER_SERIAL_FMA instead of WAVE64) and are therefore never
+        on by default: "maxsim_stage" = 1 (FEATURE_VECTOR_MAXSIM_MFMA) and "pq_scan_stage" = 1 (FEATURE_VECTOR_PQ_SCAN_MFMA: the
+        brute-force arm of every per-query-filter search as packed GEMMs on the f32 matrix cores, meant for batches whose queries share
+        filters; pages of at most 64 hits)."""
+        need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA}.get(name, 0)
+        if need and not _lib.lib().nidx_gpu_build_features() & need:
+            raise RuntimeError(f"this libnidx_gpu build does not know the tunable {name!r}")
+        _lib.check(_lib.lib().nidx_gpu_vector_set_tunable(self._handle, name.encode(), int(value)))
+
     def close(self):
         if self._handle:
             _lib.lib().nidx_gpu_vector_close(self._handle)

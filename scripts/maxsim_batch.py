@@ -9,10 +9,12 @@ Paths (multi-vector queries/s, median of --reps runs each, in one process):
   new-own    the same batch in one call of the new entry, the filters as programs
 
 usage: python scripts/maxsim_batch.py [--paragraphs N] [--reps N] [--only new] [--stage {0,1}] [--query-vectors N] [--similarity {dot,cosine}]
-                                       [--first-pass {auto,brute}]
+                                       [--first-pass {auto,brute}] [--scan-stage {0,1}]
   --stage 1    the second stage on the f32 matrix cores (tunable "maxsim_stage": maxsim_mfma_rerank_kernel, SERIAL_FMA order); 0 = WAVE64
   --query-vectors / --similarity   the second shape: 128 vectors per query, Cosine
   --first-pass brute   exact first pass, no graph is built (the second stage sees the same kind of candidate list)
+  --scan-stage 1   the brute-force arm of the first pass as packed GEMMs on the f32 matrix cores (tunable "pq_scan_stage":
+               pq_mfma_kernel, SERIAL_FMA order); 0 = the register-tile scan.  With --first-pass brute the whole first pass is that arm
   --only new   just the unfiltered new entry (for a `rocprofv3 --kernel-trace --stats` run of its own: the time per launch of
                maxsim_rerank_kernel is read from its kernel statistics)
 Prints one line per path and a JSON line at the end.
@@ -102,11 +104,13 @@ def main():
     ap.add_argument("--query-vectors", type=int, default=QV)
     ap.add_argument("--similarity", default="dot", choices=["dot", "cosine"])
     ap.add_argument("--first-pass", default="auto", choices=["auto", "brute"])
+    ap.add_argument("--scan-stage", type=int, default=0, choices=[0, 1])
     args = ap.parse_args()
     QV = args.query_vectors
     L = _lib.lib()
     h, q, masks = build_index(args.paragraphs, similarity=int(args.similarity == "cosine"), graph=args.first_pass == "auto")
     _lib.check(L.nidx_gpu_vector_set_tunable(h, b"maxsim_stage", args.stage))
+    _lib.check(L.nidx_gpu_vector_set_tunable(h, b"pq_scan_stage", args.scan_stage))
     qoff = (QV * np.arange(NQ + 1)).astype(np.uint64)
     params = _lib.VectorSearchParamsC(K, -1.0e30, 1, _lib.METHOD_AUTO if args.first_pass == "auto" else _lib.METHOD_BRUTE_FORCE)
     out_old, out_new = outputs(NQ), outputs(NQ)
@@ -163,7 +167,7 @@ def main():
             print("%-8s %9.0f queries/s (median of %d; %0.f .. %.0f)" % (name, r["median_qps"], args.reps, r["min_qps"], r["max_qps"]), flush=True)
     L.nidx_gpu_vector_close(h)
     print(json.dumps({"maxsim_batch": result, "paragraphs": args.paragraphs, "vectors_per_paragraph": V, "dim": D, "queries": NQ,
-                      "vectors_per_query": QV, "k": K, "stage": args.stage, "similarity": args.similarity, "first_pass": args.first_pass}))
+                      "vectors_per_query": QV, "k": K, "stage": args.stage, "scan_stage": args.scan_stage, "similarity": args.similarity, "first_pass": args.first_pass}))
 
 
 if __name__ == "__main__":
