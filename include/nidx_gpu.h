@@ -176,7 +176,10 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * "pq_scan_stage" (present with NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA) changes score BITS too: the brute-force arm of
  * nidx_gpu_vector_search_filtered_per_query and of everything that runs through it — 0 (default) = the register-tile scan (WAVE64
  * order), 1 = packed GEMMs on the f32 matrix cores (NIDX_ORDER_SERIAL_FMA, like NIDX_METHOD_BRUTE_FORCE_MFMA); any other value is
- * NIDX_ERR_INVALID_ARGUMENT.  See that entry. */
+ * NIDX_ERR_INVALID_ARGUMENT.  See that entry.
+ * "pq_scan_pages" (read only while "pq_scan_stage" is 1): 0 (default) = that arm keeps at most 64 hits per query and refuses larger
+ * pages; 1 = pages of 65 .. 512 hits on single-vector segments are served by a second kernel with the same score bits (a multi-vector
+ * segment still refuses them); any other value is NIDX_ERR_INVALID_ARGUMENT.  k <= 64 is unaffected. */
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value);
 
 /* NIDX_METHOD_BRUTE_FORCE_MFMA: the same exact scan as a dense GEMM on the f32 matrix cores (one
@@ -419,7 +422,9 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
  *     NIDX_ORDER_SERIAL_FMA, as by NIDX_METHOD_BRUTE_FORCE_MFMA, so score bits differ from stage 0 in the last places and the
  *     stage is never chosen silently; a query's bits do not depend on what else is in the batch.  Multi-vector segments keep k
  *     PARAGRAPHS per query on chip, so k x (vectors of the largest paragraph) is no limit.  A page of k > 64 that reaches the arm is
- *     NIDX_ERR_UNSUPPORTED (the message names the tunable).  The HNSW and RaBitQ arms are unchanged; the routed and prefiltered
+ *     NIDX_ERR_UNSUPPORTED (the message names the tunables) unless "pq_scan_pages" is 1 and the arm's segments are single-vector:
+ *     then a query's page of up to 512 hits is kept in the merge scratch and fed from a 64-key buffer on chip (same bits, same
+ *     launches; a batch whose scratch would pass the 1 GiB cap is searched in chunks of queries).  The HNSW and RaBitQ arms are unchanged; the routed and prefiltered
  *     tickets are answered by this blocking path while the stage is 1, with the same bits.  Still one search plus one
  *     synchronisation per (segment, arm): the plan's upload, the norms of the arm's queries, three packing launches, one GEMM, one merge.
  * out_method: NULL or [n_queries][n_segments] (0 = segment not searched for that query); out_matching: NULL or

@@ -151,14 +151,15 @@ struct FilterChunk {
     std::vector<uint32_t> local;           // [n_filters] the filter's index in `filters`, kFilterNone outside the chunk (kept between the
                                            // chunks of one batch)
 };
-inline void filter_next_chunk(const FilterBatch &b, const FilterBatchInfo &info, size_t S, uint32_t q0, uint64_t cap, size_t max_filters, FilterChunk &c) {
+inline void filter_next_chunk(const FilterBatch &b, const FilterBatchInfo &info, size_t S, uint32_t q0, uint64_t cap, size_t max_filters, FilterChunk &c,
+                              uint32_t max_queries = UINT32_MAX) {
     c.local.resize(b.n_filters, kFilterNone);
     for (uint32_t f : c.filters) c.local[f] = kFilterNone;
     c.filters.clear();
     c.rows.clear();
     c.slot.clear();
     uint64_t bytes = 0;
-    for (c.q0 = c.q1 = q0; c.q1 < b.nq; c.q1++) {
+    for (c.q0 = c.q1 = q0; c.q1 < b.nq && c.q1 - q0 < max_queries; c.q1++) {
         const uint32_t f = b.filter_of_query ? b.filter_of_query[c.q1] : UINT32_MAX;
         if (f == UINT32_MAX || c.local[f] != kFilterNone) continue;
         bool named = false;

@@ -146,7 +146,7 @@ struct PqMfmaArgs {
     const uint32_t *para_of_vec;    // multi-vector segments: [n]
     int similarity;
     float min_score;
-    uint32_t k;                     // <= NIDX_MFMA_KMAX
+    uint32_t k;                     // <= NIDX_MFMA_KMAX (launch_pq_mfma_wide: NIDX_MFMA_KMAX < k <= NIDX_K_MAX)
     uint64_t *partial;              // [n_queries][lists_per_query][k]
     uint32_t lists_per_query;       // the plan's max_stripes
     const uint32_t *region;
@@ -154,6 +154,9 @@ struct PqMfmaArgs {
 };
 // multi: the segment has paragraphs of more than one vector — lists of at most k distinct paragraphs, stripes cut at paragraph boundaries
 hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s);
+// the same launch for pages of NIDX_MFMA_KMAX < k <= NIDX_K_MAX hits (pq_mfma_wide_kernel): a query's page lives in its row of `partial`, LDS
+// holds a 64-key append buffer per query.  Single-vector segments only: hipErrorInvalidValue for multi, k <= NIDX_MFMA_KMAX, k > NIDX_K_MAX
+hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s);
 
 // ---- bf16-MFMA brute-force fallback with exact re-scoring (vector_bf16.hip) ----
 #define NIDX_BF16_CAND 32  /* approximate candidates kept per query before the exact re-score */

@@ -1151,6 +1151,24 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
     return NIDX_OK;
 }
 
+namespace {
+// "pq_scan_pages" = 1 on a multi-vector segment: refused, and why
+int32_t fail_pq_wide_multi(size_t s, uint32_t k) {
+    return fail(NIDX_ERR_UNSUPPORTED,
+                "\"pq_scan_pages\" = 1 serves single-vector segments only: a page of segment %zu lists paragraphs, and the same-paragraph rule needs the "
+                "whole list at hand on every admission (got k=%u; ask for k <= %d, or set \"pq_scan_stage\" = 0)", s, k, NIDX_MFMA_KMAX);
+}
+}  // namespace
+// The queries of one chunk under "pq_scan_pages" = 1.  The partial region holds [n][max_stripes][k] keys, and the planner gives a block at
+// most max(1, kPqMfmaWorkgroups / blocks) stripes with at least ceil(n / 128) blocks: halve n until that bound fits `cap` (one query at least).
+uint32_t VectorIndex::pq_wide_chunk_queries(uint32_t n, uint32_t k, uint64_t cap) {
+    for (; n > 1; n /= 2) {
+        const uint64_t stripes = std::max<uint32_t>(1, kPqMfmaWorkgroups / ((n + kPqBlockQueries - 1) / kPqBlockQueries));
+        if ((uint64_t)n * stripes * k * 8 <= cap) break;
+    }
+    return n;
+}
+
 // ---- the brute-force arm of one (segment, arm) visit of search_per_query_chunk under "pq_scan_stage" = 1 (vector_mfma_pq.hip): the
 //      plan's upload, the SERIAL_FMA norms of the segment (first use) and of the arm's queries, the packing launches, ONE GEMM launch
 //      over every block and stripe, one merge.  Multi-vector segments need no para_best_kernel: the lists hold paragraphs. ----
@@ -1158,8 +1176,11 @@ int32_t VectorIndex::segment_pq_mfma(uint32_t s, const float *d_queries, uint32_
                                      float *d_out_score, uint32_t *d_out_count, hipStream_t st) {
     VectorSegment &seg = segs[s];
     const PqMfmaPlan &P = *pq_mfma;
-    if (k > NIDX_MFMA_KMAX)
-        return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query (got k=%u)", NIDX_MFMA_KMAX, k);
+    const bool wide = k > NIDX_MFMA_KMAX;   // pq_mfma_wide_kernel: the page in the partial region, an append buffer in LDS
+    if (wide && pq_scan_pages != 1)
+        return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query (got k=%u): set \"pq_scan_pages\" = 1 for pages of up to %d",
+                    NIDX_MFMA_KMAX, k, NIDX_K_MAX);
+    if (wide && seg.vmax > 1) return fail_pq_wide_multi(s, k);
     if (P.n_unplaced || P.blocks.empty()) return fail(NIDX_ERR_INTERNAL, "the packed scan of segment %u has queries without a list", s);
     if (P.total_words > 0xffffffffull) return fail(NIDX_ERR_OUT_OF_MEMORY, "the packed lists of segment %u outgrow one scratch region", s);
     const int32_t rc_norms = ensure_norm2_serial(seg, st);
@@ -1196,7 +1217,8 @@ int32_t VectorIndex::segment_pq_mfma(uint32_t s, const float *d_queries, uint32_
     m.region = scratch_pq_mfma.as<uint32_t>();
     m.at_blocks = (uint32_t)P.at_blocks, m.at_lists = (uint32_t)P.at_lists, m.at_totals = (uint32_t)P.at_totals;
     m.n_blocks = (uint32_t)P.blocks.size();
-    NIDX_HIP(launch_pq_mfma(m, seg.vmax > 1, st));
+    if (wide) NIDX_HIP(launch_pq_mfma_wide(m, seg.vmax > 1, st));
+    else NIDX_HIP(launch_pq_mfma(m, seg.vmax > 1, st));
     NIDX_HIP(launch_merge_topk(m.partial, nq, P.max_stripes, k, d_out_vec, d_out_score, d_out_count, st));
     return NIDX_OK;
 }
@@ -1808,8 +1830,10 @@ int32_t VectorIndex::search_per_query(const float *queries, uint32_t nq, const n
     FilterChunk chunk;
     FilterLayout layout;
     const uint32_t d = cfg.dimension;
+    // (wide pages: the chunking above bounds filter rows, not queries, and a partial row is 4 KiB at k = 512)
+    const bool wide_pages = pq_scan_stage == 1 && pq_scan_pages == 1 && k > NIDX_MFMA_KMAX;
     for (uint32_t q0 = 0; q0 < nq; q0 = chunk.q1) {
-        filter_next_chunk(b, info, S, q0, pq_scratch_cap, kPqMaxFilters, chunk);
+        filter_next_chunk(b, info, S, q0, pq_scratch_cap, kPqMaxFilters, chunk, wide_pages ? pq_wide_chunk_queries(nq - q0, k, pq_scratch_cap) : UINT32_MAX);
         filter_layout(ss, b, info, chunk, !chunk.rows.empty(), layout);
         if (pf) pf->stats.chunks++;
         const size_t at = (size_t)q0 * k;
@@ -1932,8 +1956,16 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     }
     if (out_method) std::copy(method.begin(), method.end(), out_method);
     const bool packed = pq_scan_stage == 1;   // the brute-force arm as packed GEMMs on the matrix cores (vector_mfma_pq.hip)
-    if (packed && k > NIDX_MFMA_KMAX && std::find(method.begin(), method.end(), (int32_t)NIDX_METHOD_BRUTE_FORCE) != method.end())
-        return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query in the brute-force arm (got k=%u)", NIDX_MFMA_KMAX, k);
+    if (packed && k > NIDX_MFMA_KMAX) {   // before anything is launched: pages of more than 64 hits need "pq_scan_pages" = 1 and single-vector segments
+        for (size_t i = 0; i < method.size(); i++) {
+            if (method[i] != NIDX_METHOD_BRUTE_FORCE) continue;
+            if (pq_scan_pages != 1)
+                return fail(NIDX_ERR_UNSUPPORTED,
+                            "\"pq_scan_stage\" = 1 keeps at most %d hits per query in the brute-force arm (got k=%u): set \"pq_scan_pages\" = 1 for pages of up "
+                            "to %d hits on single-vector segments", NIDX_MFMA_KMAX, k, NIDX_K_MAX);
+            if (segs[i % S].vmax > 1) return fail_pq_wide_multi(i % S, k);
+        }
+    }
     PqMfmaPlan pq_plan;
 
     // ---- per segment, each arm once over the queries routed to it (gathered rows; hits scattered back to their rows) ----
@@ -2300,6 +2332,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "pq_scan_stage") {   // the brute-force arm of the per-query-filter searches: 0 = the register-tile scan (default), 1 = packed GEMMs on the f32 matrix cores (SERIAL_FMA order)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_stage must be 0 or 1");
         idx->pq_scan_stage = (int)value;
+    }
+    else if (n == "pq_scan_pages") {   // under "pq_scan_stage" = 1: 0 = at most 64 hits per query (default), 1 = pages of up to NIDX_K_MAX hits on single-vector segments (pq_mfma_wide_kernel)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_pages must be 0 or 1");
+        idx->pq_scan_pages = (int)value;
     }
     else return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown tunable %s", name);
     return NIDX_OK;

@@ -208,6 +208,10 @@ struct VectorIndex {
     // group of queries that share a filter row, over only the rows that row lets through (vector_mfma_pq.hip; SERIAL_FMA order).
     // While pq_mfma is set, the brute-force branch of segment_search_device_scratch is segment_pq_mfma with that plan
     int pq_scan_stage = 0;
+    // tunable "pq_scan_pages" = 1 (with pq_scan_stage = 1): pages of NIDX_MFMA_KMAX < k <= NIDX_K_MAX hits on single-vector segments by
+    // pq_mfma_wide_kernel; search_per_query cuts its chunks so that the [queries][stripes][k] partial region stays under pq_scratch_cap
+    int pq_scan_pages = 0;
+    static uint32_t pq_wide_chunk_queries(uint32_t n, uint32_t k, uint64_t cap);
     const PqMfmaPlan *pq_mfma = nullptr;
     const uint64_t *pq_mfma_table = nullptr;   // the segment's rows of the chunk's filter table
     static constexpr uint32_t kPqMfmaWorkgroups = 512;   // what one GEMM launch aims at: two workgroups on each of 256 CUs

@@ -23,10 +23,13 @@
 //          k-th), and the same-paragraph rule decides; only a survivor of an unlisted paragraph has to beat the k-th key.  Paragraphs own
 //          disjoint address ranges, so the order among paragraphs does not depend on which of their vectors is listed.  Stripes start
 //          at paragraph boundaries, so no paragraph is in two stripes and the merge needs no reduction after it.
+//   pages of 65 .. 512 hits (pq_mfma_wide_kernel; tunable "pq_scan_pages" = 1, single-vector segments): the same plan, packing and GEMM;
+//          the page lives in the query's row of the partial region and LDS holds a 64-key append buffer per query — see the kernel.
 //
 // Bounds: GEMM 2 * (queries in blocks) * (list length) * dp flop at 157.3 Tflop/s; a block reads its list's rows once per stripe walk.
 #include "device_common.h"
 #include "kernels.h"
+#include "wave_bitonic.h"
 
 namespace nidx {
 
@@ -377,6 +380,243 @@ hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s) {
             if (multi) hipLaunchKernelGGL((pq_mfma_kernel<NIDX_MFMA_KMAX, true>), grid, dim3(256), 0, s, part);
             else hipLaunchKernelGGL((pq_mfma_kernel<NIDX_MFMA_KMAX, false>), grid, dim3(256), 0, s, part);
         }
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the packed GEMM with result pages of 65 .. NIDX_K_MAX hits (tunable "pq_scan_pages" = 1; single-vector segments)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A page of 512 keys for each of 128 queries is 512 KiB, so a query's page lives where merge_topk_kernel will read it: its row
+// partial[(query * lists_per_query + stripe) * k .. + k) of the partial region, sorted best first, in blocks of 64 keys of which lane l of
+// the owning wave holds (and alone ever touches) entry 64 i + l.  LDS holds a 64-key APPEND buffer per query.  The epilogue of a
+// `t` step (the wave's 32 queries x 32 entries) appends its survivors — at most 32 per query, slot = the query's count + the lane's rank
+// among the passing lanes of its half — and a buffer with more than 32 keys is FLUSHED by the whole wave before the next step: sorted
+// (bs_sort_stages, worst first), then chained through the page's blocks with bs_merge_sorted_both, the better 64 staying in the block and
+// the worse 64 carried on, until the carry is empty or falls off the page.  The floor (thr_key / thr_score) is the k-th key as of the
+// last flush: a stale floor only admits more, and the page is the top k of a totally ordered set whenever the flushes happen.
+// Wave w owns queries 32w .. 32w + 31 — accumulators, buffers, rows — so the epilogue has no atomics and no workgroup barrier.
+// LDS: 48 KiB of stage buffers + 64 KiB of append buffers + 5.5 KiB = 117.5 KiB, one workgroup per CU.
+struct PqWideShared {
+    float q[2][2][PQ_BM][PQ_PITCH];  // [stage][k parity][query][k/2]
+    float x[2][2][PQ_BN][PQ_PITCH];  // [stage][k parity][entry][k/2]
+    uint64_t buf[PQ_BM][64];         // per-query append buffer, owned by the query's wave
+    // written by one lane and read by all lanes of the owning wave (a wave's LDS accesses complete in order)
+    volatile uint64_t thr_key[PQ_BM];   // k-th key as of the last flush (EMPTY while the page is short; all ones: no such query)
+    volatile float thr_score[PQ_BM];    // its score (-inf while short; +inf: no such query)
+    volatile uint32_t cnt[PQ_BM];       // keys in the buffer
+    volatile uint32_t live[PQ_BM];      // keys in the page: entries of the row past it were never written and read as EMPTY
+    float q_qq[PQ_BM], q_rinv[PQ_BM];
+    float row_xx[PQ_BN], row_rinv[PQ_BN];
+    uint32_t q_id[PQ_BM];
+    uint32_t row_id[PQ_BN];
+};
+
+// The prologue and the mainloop are pq_mfma_kernel's, as functions (that kernel keeps its own text: calling these changed the register
+// allocation of its KMAX = 64 instantiations).
+// the block of this workgroup, its list (nullptr: the identity list) and its stripe [begin, end) of the list's entries (all uniform)
+struct PqStripe {
+    const uint32_t *entries;
+    uint32_t q_at, n_q, begin, end;
+};
+__device__ __forceinline__ PqStripe pq_stripe(const PqMfmaArgs &a) {
+    const uint32_t *blk = a.region + a.at_blocks + 6u * blockIdx.y;
+    const uint32_t list = blk[0], q_at = blk[1], n_q = blk[2], stripes = blk[3], stripe_len = blk[4];
+    const uint32_t *rec = a.region + a.at_lists + 4u * list;
+    const uint32_t cap = rec[1];
+    const uint32_t *entries = rec[2] == PQ_NO_ID ? nullptr : a.region + rec[2];   // nullptr: the identity list
+    uint32_t len = cap;
+    if (entries) {
+        const uint32_t filled = a.region[a.at_totals + list];
+        len = filled < cap ? filled : cap;
+    }
+    if (len > a.n) len = a.n;
+    uint32_t begin = len, end = len;
+    if (blockIdx.x < stripes) {
+        const uint64_t b = (uint64_t)blockIdx.x * stripe_len, e = b + stripe_len;
+        begin = b < len ? (uint32_t)b : len;
+        end = (blockIdx.x + 1 == stripes || e >= len) ? len : (uint32_t)e;
+    }
+    return PqStripe{entries, q_at, n_q, begin, end};
+}
+
+// one 128 x 128 tile over every K chunk, by the whole workgroup: acc[t] = the wave's 32 queries x the entries 32t .. 32t + 31
+__device__ __forceinline__ void pq_tile_gemm(PqWideShared &sh, const PqMfmaArgs &a, const uint32_t (&qr)[2], const uint32_t (&xr)[2], uint32_t nk,
+                                             int tid, floatx16 (&acc)[4]) {
+    const int lane = tid & 63, wave = tid >> 6, li = lane & 31, half = lane >> 5;
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[t][r] = 0.f;
+
+    // software pipeline: the gathers of chunk kc+2 are issued before the MFMAs of chunk kc and written to LDS at the end of kc+1
+    float4 gq[2], gx[2], nq_[2], nx_[2];
+    pq_stage_load(a.queries, qr, a.dp, 0, tid, gq);
+    pq_stage_load(a.vectors, xr, a.dp, 0, tid, gx);
+    pq_stage_store(sh.q[0], tid, gq);
+    pq_stage_store(sh.x[0], tid, gx);
+    if (nk > 1) {
+        pq_stage_load(a.queries, qr, a.dp, PQ_BK, tid, gq);
+        pq_stage_load(a.vectors, xr, a.dp, PQ_BK, tid, gx);
+    }
+    __syncthreads();
+    for (uint32_t kc = 0; kc < nk; kc++) {
+        const int st = (int)(kc & 1);
+        if (kc + 2 < nk) {
+            pq_stage_load(a.queries, qr, a.dp, (kc + 2) * PQ_BK, tid, nq_);
+            pq_stage_load(a.vectors, xr, a.dp, (kc + 2) * PQ_BK, tid, nx_);
+        }
+        // operands of the 8 k-steps of this chunk: lane (li, half) takes parity `half`
+        const float4 a0 = *reinterpret_cast<const float4 *>(&sh.q[st][half][32 * wave + li][0]);
+        const float4 a1 = *reinterpret_cast<const float4 *>(&sh.q[st][half][32 * wave + li][4]);
+        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const float4 b0 = *reinterpret_cast<const float4 *>(&sh.x[st][half][32 * t + li][0]);
+            const float4 b1 = *reinterpret_cast<const float4 *>(&sh.x[st][half][32 * t + li][4]);
+            const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int s = 0; s < 8; s++) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], bv[s], acc[t], 0, 0, 0);
+        }
+        if (kc + 1 < nk) {
+            pq_stage_store(sh.q[st ^ 1], tid, gq);
+            pq_stage_store(sh.x[st ^ 1], tid, gx);
+        }
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            gq[it] = nq_[it];
+            gx[it] = nx_[it];
+        }
+        __syncthreads();
+    }
+}
+
+// every query of the wave with more than `over` buffered keys: buffer -> page (the whole wave, all lanes active)
+__device__ inline void pq_wide_flush(PqWideShared &sh, const PqMfmaArgs &a, int wave, int lane, uint32_t over) {
+    const uint32_t k = a.k, blocks = (k + 63u) >> 6;
+    uint32_t pending = (uint32_t)__ballot(sh.cnt[32 * wave + (lane & 31)] > over);   // (both halves vote alike: the low word)
+    while (pending) {
+        const int q = 32 * wave + __ffs((int)pending) - 1;
+        pending &= pending - 1;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh.cnt[q]);
+        const uint32_t live = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh.live[q]);
+        const uint32_t qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh.q_id[q]);
+        if (qi == PQ_NO_ID) continue;   // (never buffered: its floor admits nothing)
+        uint64_t *row = a.partial + ((size_t)qi * a.lists_per_query + blockIdx.x) * k;
+        uint64_t carry = bs_sort_stages<64>((uint32_t)lane < n ? sh.buf[q][lane] : NIDX_EMPTY_KEY);   // worst first
+        for (uint32_t i = 0; i < blocks; i++) {
+            if (!__ballot(carry != NIDX_EMPTY_KEY)) break;   // the blocks behind are unchanged, and so is the floor
+            const uint32_t e = 64u * i + (uint32_t)lane;
+            const uint64_t old = e < live ? row[e] : NIDX_EMPTY_KEY;
+            uint64_t blk = old;
+            bs_merge_sorted_both(blk, carry);
+            if (e >= k) blk = NIDX_EMPTY_KEY;   // ranks past the page (the last carry is dropped likewise)
+            if (blk != old) row[e] = blk;
+            if (i + 1 == blocks) {
+                const uint64_t kth = lane_bcast_u64(blk, (int)((k - 1u) & 63u));
+                if (lane == 0 && kth != NIDX_EMPTY_KEY) {
+                    sh.thr_key[q] = kth;
+                    sh.thr_score[q] = rank_key_score(kth);
+                }
+            }
+        }
+        if (lane == 0) {
+            sh.cnt[q] = 0;
+            sh.live[q] = live + n < k ? live + n : k;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
+    __shared__ PqWideShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, half = lane >> 5;
+    const bool cosine = a.similarity == 1;
+    const uint32_t k = a.k;
+    const uint32_t nk = (a.dp + PQ_BK - 1) / PQ_BK;
+    const PqStripe sp = pq_stripe(a);
+    const uint32_t *entries = sp.entries;
+    const uint32_t begin = sp.begin, end = sp.end;
+
+    if (tid < PQ_BM) {
+        uint32_t qi = (uint32_t)tid < sp.n_q ? a.region[sp.q_at + tid] : PQ_NO_ID;
+        if (qi >= a.n_queries) qi = PQ_NO_ID;
+        const float qq = qi != PQ_NO_ID ? a.q_norm2[qi] : 0.f;
+        sh.q_id[tid] = qi;
+        sh.q_qq[tid] = qq;
+        sh.q_rinv[tid] = qi != PQ_NO_ID ? 1.0f / sqrtf(qq) : 0.f;
+        sh.thr_key[tid] = qi != PQ_NO_ID ? NIDX_EMPTY_KEY : ~0ull;   // (a missing query admits nothing, whatever its scores are)
+        sh.thr_score[tid] = qi != PQ_NO_ID ? -INFINITY : INFINITY;
+        sh.cnt[tid] = 0;
+        sh.live[tid] = 0;
+    }
+    __syncthreads();
+    const uint32_t qr[2] = {sh.q_id[tid >> 2], sh.q_id[(tid >> 2) + 64]};
+
+    for (uint32_t e0 = begin; e0 < end; e0 += PQ_BN) {
+        __syncthreads();  // previous tile's epilogue is done with row_* and the stage buffers
+        if (tid < PQ_BN) {
+            const uint32_t e = e0 + (uint32_t)tid;
+            uint32_t id = e < end ? (entries ? entries[e] : e) : PQ_NO_ID;
+            if (id >= a.n) id = PQ_NO_ID;
+            const float xx = (id != PQ_NO_ID && cosine) ? a.norm2[id] : 0.f;
+            sh.row_id[tid] = id;
+            sh.row_xx[tid] = xx;
+            sh.row_rinv[tid] = 1.0f / sqrtf(xx);
+        }
+        __syncthreads();
+        const uint32_t xr[2] = {sh.row_id[tid >> 2], sh.row_id[(tid >> 2) + 64]};
+        floatx16 acc[4];
+        pq_tile_gemm(sh, a, qr, xr, nk, tid, acc);
+
+        // ---- epilogue: the survivors of the 32 x 128 scores of this wave go to its queries' append buffers ----
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            pq_wide_flush(sh, a, wave, lane, 32u);   // every buffer has room for the 32 survivors a step can bring
+            const int j = 32 * t + li;
+            const uint32_t row = sh.row_id[j];
+            const bool row_ok = row != PQ_NO_ID;
+            const float rinv = sh.row_rinv[j];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int qi = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;   // one query per half
+                const float ab = acc[t][r];
+                // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
+                const float approx = cosine ? ab * rinv * sh.q_rinv[qi] + 1e-5f : ab;
+                const bool pre = row_ok && !(approx < sh.thr_score[qi]);
+                if (!__ballot(pre)) continue;
+                float score = ab;
+                if (pre && cosine) score = cosine_from_sums(ab, sh.row_xx[j], sh.q_qq[qi]);
+                const uint64_t key = rank_key(score, row);
+                const bool pass = pre && (score >= a.min_score) && key > sh.thr_key[qi];
+                const unsigned long long m = __ballot(pass);
+                if (!m) continue;
+                const uint32_t mine = half ? (uint32_t)(m >> 32) : (uint32_t)m;   // the passing lanes of this lane's query
+                const uint32_t at = sh.cnt[qi];
+                if (pass) sh.buf[qi][at + (uint32_t)__popc(mine & ((1u << li) - 1u))] = key;
+                if (li == 0 && mine) sh.cnt[qi] = at + (uint32_t)__popc(mine);
+            }
+        }
+    }
+    // ---- what is still buffered, then EMPTY behind every page: merge_topk_kernel reads all k entries of a row (a workgroup without
+    //      entries, or of a stripe past its block's own, leaves empty rows) ----
+    pq_wide_flush(sh, a, wave, lane, 0u);
+    for (int ql = 0; ql < 32; ql++) {
+        const uint32_t qi = sh.q_id[32 * wave + ql];
+        if (qi == PQ_NO_ID) continue;
+        uint64_t *row = a.partial + ((size_t)qi * a.lists_per_query + blockIdx.x) * k;
+        for (uint32_t e = sh.live[32 * wave + ql] + (uint32_t)lane; e < k; e += 64u) row[e] = NIDX_EMPTY_KEY;
+    }
+}
+
+hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s) {
+    if (a.k <= NIDX_MFMA_KMAX || a.k > NIDX_K_MAX || multi) return hipErrorInvalidValue;
+    if (a.n_blocks == 0 || a.lists_per_query == 0) return hipSuccess;
+    for (uint32_t b0 = 0; b0 < a.n_blocks; b0 += 65535u) {   // (the blocks in slices, as launch_pq_mfma)
+        PqMfmaArgs part = a;
+        part.at_blocks = a.at_blocks + 6u * b0;
+        part.n_blocks = a.n_blocks - b0 < 65535u ? a.n_blocks - b0 : 65535u;
+        hipLaunchKernelGGL(pq_mfma_wide_kernel, dim3(a.lists_per_query, part.n_blocks), dim3(256), 0, s, part);
     }
     return hipGetLastError();
 }

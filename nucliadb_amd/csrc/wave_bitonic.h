@@ -68,4 +68,20 @@ __device__ inline uint64_t bs_merge_sorted(uint64_t top, uint64_t other_reversed
     return bs_merge_steps<32>(m);
 }
 
+template <int J>
+__device__ inline uint64_t bs_merge_steps_up(uint64_t v) {   // the same merge with the worst key first
+    v = bs_cmpx<J>(v, ~bs_merge_mask(J));
+    if constexpr (J > 1) return bs_merge_steps_up<J / 2>(v);
+    else return v;
+}
+// The merge that keeps BOTH halves: `top` sorted best first, `other_reversed` worst first -> the 64 best of the 128 in `top`, best first,
+// and the 64 worst in `other_reversed`, worst first again, so that it goes into the next merge of a chain as it is.  The element-wise
+// compare-exchange leaves two bitonic runs, every key of the first at least every key of the second.
+__device__ inline void bs_merge_sorted_both(uint64_t &top, uint64_t &other_reversed) {
+    const bool keep = top > other_reversed;
+    const uint64_t hi = keep ? top : other_reversed, lo = keep ? other_reversed : top;
+    top = bs_merge_steps<32>(hi);
+    other_reversed = bs_merge_steps_up<32>(lo);
+}
+
 }  // namespace nidx

@@ -943,7 +943,7 @@ class VectorSearcher:
         """nidx_gpu_vector_set_tunable.  Two tunables change score BITS (NIDX_ORDER_SERIAL_FMA instead of WAVE64) and are therefore never
         on by default: "maxsim_stage" = 1 (FEATURE_VECTOR_MAXSIM_MFMA) and "pq_scan_stage" = 1 (FEATURE_VECTOR_PQ_SCAN_MFMA: the
         brute-force arm of every per-query-filter search as packed GEMMs on the f32 matrix cores, meant for batches whose queries share
-        filters; pages of at most 64 hits)."""
+        filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well)."""
         need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA}.get(name, 0)
         if need and not _lib.lib().nidx_gpu_build_features() & need:
             raise RuntimeError(f"this libnidx_gpu build does not know the tunable {name!r}")
