@@ -72,6 +72,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_RELATION_STRINGS 32768 /* nidx_gpu_relation_set_strings / _graph_search_strings_batch / _match_strings_batch */
 #define NIDX_FEATURE_VECTOR_MAXSIM_MFMA 65536 /* nidx_gpu_vector_set_tunable "maxsim_stage" = 1: the maxsim second stage on the f32 matrix cores */
 #define NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA (1u << 17) /* = 131072; nidx_gpu_vector_set_tunable "pq_scan_stage" = 1: the brute-force arm of the per-query-filter searches as packed GEMMs on the f32 matrix cores */
+#define NIDX_FEATURE_BM25_DENSE_PROBE (1u << 18) /* = 262144; nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats: dense Must / MustNot / Should clauses of a BM25 query as bitmap probes */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -794,6 +795,23 @@ int32_t nidx_gpu_bm25_open(const nidx_gpu_bm25_segment_t *segments, uint32_t n_s
                            nidx_gpu_bm25_index_t **index_out);
 void nidx_gpu_bm25_close(nidx_gpu_bm25_index_t *index);
 int32_t nidx_gpu_bm25_space_usage(const nidx_gpu_bm25_index_t *index, uint64_t *bytes_out);
+
+/* Search knobs of an open BM25 index (present when nidx_gpu_build_features() & NIDX_FEATURE_BM25_DENSE_PROBE).  One name:
+ * "dense_probe": 0 (default) = off, every search runs exactly as without the knob.  n in 1 .. 1024: a plain dictionary term whose posting
+ * list in the resident layout holds list_length * n >= n_docs documents is DENSE, and a query of at most 8 clauses with one to four dense
+ * TF_BASIC / CONST_SCORE clauses (any occur) whose every possible match holds a posting of a sparse clause — a sparse Must, or a required
+ * Should group without a dense member — is scored by streaming its sparse lists only: a dense clause is one bit gathered per candidate
+ * from a bitmap over the doc ids, its score added at its place in the clause order.  Hits, scores, counts and totals are bit for bit
+ * those of the default path; out_postings of such a query counts its SPARSE postings (the diagnostic of which path served it).  32 is
+ * the recommended value (the bitmap is then no larger than the id list).  The paragraph searcher's default request
+ * (keyword group + Must repeated_in_field:0 + filters) is the shape this is for.  Any other query, and any call with facets, an order
+ * by fast field, NIDX_GPU_BM25_SEGMENT_LOOP or NIDX_GPU_BM25_DEBUG, ignores the knob.  At most 64 bitmaps are kept per generation, each
+ * built on first use (that call waits for one launch); a dense term beyond that is treated as sparse.  nidx_gpu_bm25_sync drops them.
+ * Any other name or value is NIDX_ERR_INVALID_ARGUMENT. */
+int32_t nidx_gpu_bm25_set_tunable(nidx_gpu_bm25_index_t *index, const char *name, int64_t value);
+/* out[0] bitmaps resident, out[1] bitmaps built since open, out[2] queries served by the probe kernel, out[3] probes made (documents x
+ * dense clauses; waits for nothing: the launches that have finished). */
+int32_t nidx_gpu_bm25_dense_probe_stats(const nidx_gpu_bm25_index_t *index, uint64_t out[4]);
 
 /* NIDX_OCCUR_SHOULD_GROUP: a Should clause of a nested Must(BooleanQuery[Should ...]) — the paragraph
  * keyword query under its Must filters (nidx_paragraph/src/search_query.rs:185-243): it scores like a

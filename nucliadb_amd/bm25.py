@@ -395,6 +395,19 @@ class Bm25Searcher:
         _lib.check(_lib.lib().nidx_gpu_bm25_space_usage(self._handle, C.byref(out)))
         return out.value
 
+    def set_tunable(self, name: str, value: int) -> None:
+        """nidx_gpu_bm25_set_tunable.  "dense_probe": 0 (default) = off; n in 1 .. 1024 (32 recommended) = a term in at least 1 / n of
+        the documents is dense, and the dense TF_BASIC / CONST_SCORE clauses of a query whose candidates its sparse clauses name (the
+        paragraph searcher's default request: keyword group + Must repeated_in_field:0 + filters) are bitmap probes instead of posting
+        streams.  Same hits and score bits; `postings` of such a query counts its sparse postings only."""
+        _lib.check(_lib.lib().nidx_gpu_bm25_set_tunable(self._handle, name.encode(), int(value)))
+
+    def dense_probe_stats(self) -> dict:
+        """nidx_gpu_bm25_dense_probe_stats: bitmaps resident, bitmaps built since open, queries served by the probe kernel, probes made."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().nidx_gpu_bm25_dense_probe_stats(self._handle, out))
+        return {"resident": int(out[0]), "built": int(out[1]), "queries": int(out[2]), "probes": int(out[3])}
+
     def set_fast_field(self, segment: int, field: int, values) -> None:
         """`created` (0) / `modified` (1) fast field of one segment: int64 per document."""
         v = np.ascontiguousarray(values, dtype=np.int64)

@@ -83,6 +83,12 @@ struct Bm25Ctx {
     std::vector<Bm25ClauseDev> w_dev_clauses;
     std::vector<Bm25StreamClause> w_ucl;   // (entries of queries that are not union queries keep whatever they held: never read)
     std::vector<Bm25AfterDev> w_after;
+    // dense-probe planning (nidx_gpu_bm25_set_tunable "dense_probe"): per clause the dense flag, the bitmap's device address, occur and
+    // mode as the planner reads them, and bm25_plan_work's scratch
+    std::vector<uint8_t> w_dense;
+    std::vector<unsigned long long> w_dense_bits;
+    std::vector<int32_t> w_occur, w_mode;
+    std::vector<uint64_t> w_sparse_len;
     DevBuf s_after, s_count, s_total, s_postings, s_key;
     DevBuf s_fuse_done, s_fuse_key, s_fuse_count, s_fuse_total, s_fuse_postings;   // Bm25FusedMerge (s_fuse_done is zeroed when it grows and stays zero between launches)
     DevBuf s_phrase_tf, s_aux_tfs, s_slop_left, s_sub_bits, s_sub_union;
@@ -209,9 +215,29 @@ struct Bm25Index {
     std::vector<std::unique_ptr<Bm25Slot>> slots;   // nidx_gpu_bm25_search_submit / _wait
     uint64_t next_ticket = 1;
     // nidx_gpu_bm25_ticket_stats (sums over the tickets of nidx_gpu_bm25_search_submit_prefiltered)
+    // Dense-term bitmaps (nidx_gpu_bm25_set_tunable "dense_probe"; kernels: bm25_probe.hip): at most BM25_DENSE_CACHE bitmaps of
+    // ceil(n_docs / 64) words over the resident doc ids, keyed by term id within the current generation (nidx_gpu_bm25_sync drops them:
+    // term ids belong to a generation; deletions leave them alone: the alive bitset is tested separately).  Built on first use under
+    // dense_mu on dense_stream, which is synchronised before the bitmap is published: every later batch finds it without waiting.
+    std::atomic<int64_t> dense_probe{0};
+    mutable std::mutex dense_mu;
+    struct DenseBitmap {
+        uint32_t term;
+        DevBuf bits;
+    };
+    std::vector<DenseBitmap> dense;
+    hipStream_t dense_stream = nullptr;
+    DevBuf dense_probes;   // u64: probes made (bm25_probe_kernel adds to it)
+    std::atomic<uint64_t> dense_built{0}, dense_queries{0};
     std::atomic<uint64_t> ts_tickets{0}, ts_pipelined{0}, ts_ran_in_submit{0}, ts_submit_syncs{0}, ts_aux_launches{0}, ts_row_sets{0}, ts_term_sets{0};
     Bm25Index() = default;
     Bm25Index(const Bm25Index &) = delete;
+    ~Bm25Index() {
+        if (dense_stream) {
+            (void)hipStreamSynchronize(dense_stream);
+            (void)hipStreamDestroy(dense_stream);
+        }
+    }
     bool concatenated() const { return !real.empty(); }
     // DocAddress of resident (segment, doc)
     uint64_t docaddr(size_t resident_segment, uint32_t d) const {
@@ -546,9 +572,74 @@ int32_t nidx_gpu_bm25_space_usage(const nidx_gpu_bm25_index_t *index, uint64_t *
     if (!idx || !bytes_out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
     uint64_t b = idx->tf_cache.bytes;
     for (const Bm25Segment &s : idx->segs) b += s.bytes();
+    {
+        std::lock_guard<std::mutex> lock(idx->dense_mu);
+        for (const Bm25Index::DenseBitmap &d : idx->dense) b += d.bits.bytes;
+    }
     *bytes_out = b;
     return NIDX_OK;
 } NIDX_ABI_CATCH
+
+#define BM25_DENSE_CACHE 64   /* bitmaps kept per index and generation */
+
+int32_t nidx_gpu_bm25_set_tunable(nidx_gpu_bm25_index_t *index, const char *name, int64_t value) try {
+    Bm25Index *idx = reinterpret_cast<Bm25Index *>(index);
+    if (!idx || !name) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (strcmp(name, "dense_probe") != 0) return fail(NIDX_ERR_INVALID_ARGUMENT, "nidx_gpu_bm25_set_tunable: unknown tunable '%s'", name);
+    if (value < 0 || value > 1024) return fail(NIDX_ERR_INVALID_ARGUMENT, "nidx_gpu_bm25_set_tunable: dense_probe takes 0 (off) or 1 .. 1024");
+    if (value > 0) {
+        std::lock_guard<std::mutex> lock(idx->dense_mu);
+        if (!idx->dense_probes.p) {
+            NIDX_HIP(hipSetDevice(idx->device));
+            NIDX_HIP(idx->dense_probes.alloc(8));
+            NIDX_HIP(hipMemset(idx->dense_probes.p, 0, 8));
+        }
+    }
+    idx->dense_probe.store(value);
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_bm25_dense_probe_stats(const nidx_gpu_bm25_index_t *index, uint64_t out[4]) try {
+    const Bm25Index *idx = reinterpret_cast<const Bm25Index *>(index);
+    if (!idx || !out) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::lock_guard<std::mutex> lock(idx->dense_mu);
+    out[0] = idx->dense.size();
+    out[1] = idx->dense_built.load();
+    out[2] = idx->dense_queries.load();
+    out[3] = 0;
+    if (idx->dense_probes.p) {
+        NIDX_HIP(hipSetDevice(idx->device));
+        NIDX_HIP(hipMemcpy(&out[3], idx->dense_probes.p, 8, hipMemcpyDeviceToHost));
+    }
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+// The bitmap of dense term `term` of the resident segment: found in the cache, or built now — one launch on the cache's own stream and
+// one wait, once per term and generation.  *bits_out = 0: the cache is full, the caller treats the term as sparse.
+static int32_t bm25_dense_bitmap(Bm25Index *idx, const Bm25Segment &seg, uint32_t term, unsigned long long *bits_out) {
+    std::lock_guard<std::mutex> lock(idx->dense_mu);
+    *bits_out = 0;
+    for (const Bm25Index::DenseBitmap &d : idx->dense)
+        if (d.term == term) {
+            *bits_out = (unsigned long long)(uintptr_t)d.bits.p;
+            return NIDX_OK;
+        }
+    if (idx->dense.size() >= BM25_DENSE_CACHE) return NIDX_OK;
+    if (!idx->dense_stream) NIDX_HIP(hipStreamCreateWithFlags(&idx->dense_stream, hipStreamNonBlocking));
+    const size_t bytes = ((size_t)seg.n_docs + 63) / 64 * 8;
+    Bm25Index::DenseBitmap d;
+    d.term = term;
+    NIDX_HIP(d.bits.alloc(bytes));
+    const uint64_t b = seg.term_offsets_host[term], e = seg.term_offsets_host[term + 1];
+    NIDX_HIP(hipMemsetAsync(d.bits.p, 0, bytes, idx->dense_stream));
+    NIDX_HIP(launch_bm25_dense_bitmap(seg.doc_ids.as<uint32_t>() + b, e - b, d.bits.as<unsigned long long>(), idx->dense_stream));
+    NIDX_HIP(hipStreamSynchronize(idx->dense_stream));
+    *bits_out = (unsigned long long)(uintptr_t)d.bits.p;
+    idx->dense.reserve(BM25_DENSE_CACHE);
+    idx->dense.push_back(std::move(d));
+    idx->dense_built++;
+    return NIDX_OK;
+}
 
 // Before an exclusive operation rewrites what the scoring kernels read (alive bitsets, fast-field ranks): the batches already submitted
 // finish on the state they were planned against — a reopened searcher is a snapshot (nidx_tantivy/src/index_reader.rs:39-74).  The caller
@@ -2377,9 +2468,11 @@ static int32_t bm25_aux_blocking(const Bm25Index *idx, Bm25Ctx &cx, const Bm25Se
 }
 
 // Every clause's list length in this segment, looked up once (two random reads of an 8 MB table per plain term), then the work list
-// (bm25_work_plan.h) into cx.w_work / w_item_first / w_q_union / w_item_list.
-static Bm25WorkPlan bm25_plan_segment(const Bm25Index *idx, const Bm25Segment &seg, const Bm25Request &rq, const Bm25AuxLayout &al, const Bm25PlanKnobs &knobs,
-                                      Bm25Ctx &cx) {
+// (bm25_work_plan.h) into cx.w_work / w_item_first / w_q_union / w_item_list.  `allow_probe`: the call is one the dense probe may serve
+// (one resident segment, no facets, no order by fast field, no debug run); with the "dense_probe" tunable on, the dense clauses are
+// flagged for the planner and the bitmaps of the queries that would qualify are fetched (cx.w_dense / w_dense_bits).
+static int32_t bm25_plan_segment(Bm25Index *idx, const Bm25Segment &seg, const Bm25Request &rq, const Bm25AuxLayout &al, const Bm25PlanKnobs &knobs,
+                                 bool allow_probe, Bm25Ctx &cx, Bm25WorkPlan &plan) {
     const nidx_gpu_bm25_clause_t *clauses = rq.clauses;
     const uint64_t n_clauses = rq.n_clauses;
     std::vector<uint64_t> &clen = cx.w_clause_len;
@@ -2399,7 +2492,38 @@ static Bm25WorkPlan bm25_plan_segment(const Bm25Index *idx, const Bm25Segment &s
     batch.clause_offsets = rq.clause_offsets, batch.clause_len = clen.data(), batch.clause_term = cterm.data();
     batch.special_bits = NIDX_BM25_TERM_SET | NIDX_BM25_PHRASE | NIDX_BM25_SUBQUERY;
     batch.nq = rq.nq, batch.n_docs = seg.n_docs, batch.n_cus = (uint32_t)idx->n_cus;
-    return bm25_plan_work(knobs, batch, cx.w_postings, cx.w_work, cx.w_item_first, cx.w_q_union, cx.w_item_list);
+    const uint64_t dense_n = allow_probe ? (uint64_t)idx->dense_probe.load() : 0u;
+    const uint8_t *dense = nullptr;
+    if (dense_n) {
+        bool any = false;
+        cx.w_dense.assign(n_clauses, 0);
+        cx.w_dense_bits.assign(n_clauses, 0);
+        cx.w_occur.resize(n_clauses);
+        cx.w_mode.resize(n_clauses);
+        for (uint64_t c = 0; c < n_clauses; c++) {
+            cx.w_occur[c] = clauses[c].occur, cx.w_mode[c] = clauses[c].mode;
+            if (!(cterm[c] & batch.special_bits) && clen[c] > 0 && clen[c] * dense_n >= seg.n_docs) cx.w_dense[c] = 1, any = true;
+        }
+        batch.clause_occur = cx.w_occur.data(), batch.clause_mode = cx.w_mode.data();
+        // the bitmaps of the queries the planner would send to the probe kernel; a term the cache has no room for is sparse after all
+        // (the planner, below, then decides on the flags that are left)
+        for (uint32_t q = 0; q < rq.nq && any; q++) {
+            if (!bm25_plan_probe(knobs, batch, cx.w_dense.data(), q)) continue;
+            for (uint64_t c = rq.clause_offsets[q]; c < rq.clause_offsets[q + 1]; c++) {
+                if (!cx.w_dense[c]) continue;
+                if (int32_t rc = bm25_dense_bitmap(idx, seg, cterm[c], &cx.w_dense_bits[c])) return rc;
+                if (!cx.w_dense_bits[c]) cx.w_dense[c] = 0;
+            }
+        }
+        if (any) dense = cx.w_dense.data();
+    }
+    plan = bm25_plan_work(knobs, batch, cx.w_postings, cx.w_work, cx.w_item_first, cx.w_q_union, cx.w_item_list, dense, &cx.w_sparse_len);
+    if (plan.n_probe) {
+        uint64_t served = 0;
+        for (uint32_t q = 0; q < rq.nq; q++) served += cx.w_q_union[q] == 2 ? 1u : 0u;
+        idx->dense_queries += served;
+    }
+    return NIDX_OK;
 }
 
 // The stream kernel's clause table (cx.w_ucl): list base / length / weight / attributes per clause of this segment, with the score floors.
@@ -2419,7 +2543,7 @@ static int32_t bm25_stream_clauses(const Bm25Index *idx, const Bm25Segment &seg,
         for (int j = 0; j < BM25_FLOOR_NR && floor_j < 0; j++)
             if (floor_ranks[j] >= rq.kk) floor_j = j;
     for (uint32_t q = 0; q < rq.nq && n_union; q++) {
-        if (!cx.w_q_union[q]) continue;
+        if (cx.w_q_union[q] != 1) continue;
         float q_floor = -INFINITY;
         bool floor_ok = floor_j >= 0;
         for (uint64_t c = clause_offsets[q]; c < clause_offsets[q + 1] && floor_ok; c++) {
@@ -2464,7 +2588,9 @@ static int32_t bm25_stage_and_launch(const Bm25Index *idx, Bm25Ctx &cx, const Bm
     const size_t if_bytes = ((size_t)(nq + 1) * 4 + 31) & ~(size_t)31;   // 32-byte pieces: the clause table is read with 16-byte scalar loads
     const size_t work_bytes = (nw * sizeof(Bm25Work) + 31) & ~(size_t)31;
     const size_t items_bytes = (nw * 4 + 31) & ~(size_t)31;
-    const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl.size() * sizeof(Bm25StreamClause);
+    const size_t ucl_bytes = ucl.size() * sizeof(Bm25StreamClause);
+    const size_t dense_bytes = plan.n_probe ? (size_t)n_clauses * 8 : 0;   // the probe items' bitmap addresses, per clause of the batch
+    const size_t inw_bytes = if_bytes + work_bytes + items_bytes + ucl_bytes + dense_bytes;
     const size_t w_at = cb.fused_in ? cb.inq_al : 0;   // the work list's place in the block: behind the clause block, or at its head
     NIDX_HIP(cx.s_in_w.reserve(w_at + inw_bytes));
     NIDX_HIP(cx.h_in_w.reserve(w_at + inw_bytes));
@@ -2478,7 +2604,8 @@ static int32_t bm25_stage_and_launch(const Bm25Index *idx, Bm25Ctx &cx, const Bm
     memcpy(h_w, cx.w_item_first.data(), (size_t)(nq + 1) * 4);
     memcpy(h_w + if_bytes, cx.w_work.data(), nw * sizeof(Bm25Work));
     memcpy(h_w + if_bytes + work_bytes, cx.w_item_list.data(), nw * 4);
-    if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl.size() * sizeof(Bm25StreamClause));
+    if (!ucl.empty()) memcpy(h_w + if_bytes + work_bytes + items_bytes, ucl.data(), ucl_bytes);
+    if (dense_bytes) memcpy(h_w + if_bytes + work_bytes + items_bytes + ucl_bytes, cx.w_dense_bits.data(), dense_bytes);
     NIDX_HIP(hipMemcpyAsync(cx.s_in_w.p, cx.h_in_w.p, w_at + inw_bytes, hipMemcpyHostToDevice, cx.stream));
     const uint32_t *d_item_first = reinterpret_cast<const uint32_t *>(d_w);
     const Bm25Work *d_work = reinterpret_cast<const Bm25Work *>(d_w + if_bytes);
@@ -2541,6 +2668,8 @@ static int32_t bm25_stage_and_launch(const Bm25Index *idx, Bm25Ctx &cx, const Bm
     a.match_slot = n_slots ? cx.s_match_slot.as<int>() : nullptr;
     a.match_words = match_words;
     a.uclauses = reinterpret_cast<const Bm25StreamClause *>(d_w + if_bytes + work_bytes + items_bytes);
+    a.dense_bits = dense_bytes ? reinterpret_cast<const unsigned long long *>(d_w + if_bytes + work_bytes + items_bytes + ucl_bytes) : nullptr;
+    a.probe_count = idx->dense_probes.as<unsigned long long>();
     a.dbg = nullptr;
     if (mode.debug) {
         NIDX_HIP(ln.dbg.alloc((16 + 8 * nw) * 8));
@@ -2598,6 +2727,7 @@ static int32_t bm25_stage_and_launch(const Bm25Index *idx, Bm25Ctx &cx, const Bm
         NIDX_HIP(launch_bm25_stream(a, d_items, plan.n_union, extras, cx.stream));
     }
     NIDX_HIP(launch_bm25_search(a, d_items + plan.n_union, plan.n_fast, d_items + plan.n_union + plan.n_fast, plan.n_wide, plan.wide_max_clauses, cx.stream));
+    NIDX_HIP(launch_bm25_probe(a, d_items + plan.n_union + plan.n_fast + plan.n_wide, plan.n_probe, cx.stream));
     NIDX_HIP(hipEventRecord(cx.ev1, cx.stream));
     if (!fused_merge) NIDX_HIP(launch_bm25_merge(mg, nq, cx.stream));
     if (n_slots)
@@ -2770,6 +2900,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
     cx.kernel_ms = 0.f;
     trace.t_begin = Bm25HostTrace::now();
     Bm25AuxLayout al;
+    // the calls the "dense_probe" tunable applies to (bm25_plan_segment)
+    const bool allow_probe = idx->segs.size() == 1 && rq.n_slots == 0 && rq.order_field < 0 && !mode.debug;
     if (mode.pipelined) {
         // One resident segment, and no stage on this path waits for the stream or reads from the device: the collect step runs in
         // nidx_gpu_bm25_search_wait (the buffers are the slot's: swapped in by submit).
@@ -2778,7 +2910,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         if (mode.pipe_aux)
             if (int32_t rc = bm25_aux_pipelined(cx, seg, 0, rq, al, tr)) return rc;
         trace.t_seg0 = Bm25HostTrace::now();
-        const Bm25WorkPlan plan = bm25_plan_segment(idx, seg, rq, al, knobs, cx);
+        Bm25WorkPlan plan;
+        if (int32_t rc = bm25_plan_segment(idx, seg, rq, al, knobs, allow_probe, cx, plan)) return rc;
         if (int32_t rc = bm25_stream_clauses(idx, seg, rq, plan.n_union, cx)) return rc;
         trace.t_work = Bm25HostTrace::now() - trace.t_seg0;
         Bm25Launch ln;
@@ -2802,7 +2935,8 @@ static int32_t bm25_search_locked(Bm25Index *idx, Bm25Ctx &cx, Bm25Slot *async_s
         if (al.n_aux)
             if (int32_t rc = bm25_aux_blocking(idx, cx, seg, rq, al, tr)) return rc;
         const double t_w0 = Bm25HostTrace::now();
-        const Bm25WorkPlan plan = bm25_plan_segment(idx, seg, rq, al, knobs, cx);
+        Bm25WorkPlan plan;
+        if (int32_t rc = bm25_plan_segment(idx, seg, rq, al, knobs, allow_probe, cx, plan)) return rc;
         if (int32_t rc = bm25_stream_clauses(idx, seg, rq, plan.n_union, cx)) return rc;
         trace.t_work += Bm25HostTrace::now() - t_w0;
         Bm25Launch ln;
@@ -3735,6 +3869,11 @@ int32_t nidx_gpu_bm25_sync(nidx_gpu_bm25_index_t *index, const nidx_gpu_bm25_syn
         idx->idf_of_term.swap(g.idf_of_term);
         idx->floor_fn.swap(g.floor_fn);
         memcpy(idx->quot1, g.quot1, sizeof(idx->quot1));
+        {
+            // the dense-term bitmaps are keyed by the old generation's term ids (no search reads them now: mu, rw and the drain above)
+            std::lock_guard<std::mutex> dlock(idx->dense_mu);
+            idx->dense.clear();
+        }
         stats.generation = idx->generation.fetch_add(1) + 1;
     }
     if (stats_out) *stats_out = stats;

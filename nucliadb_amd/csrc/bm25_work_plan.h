@@ -18,6 +18,7 @@ struct Bm25Work {  // one work item: query `query`, doc-id slice `slice` of `n_s
 #define BM25_SLICE_CROWDED 8192   /* ... of a union query when other batches are resident (the crowded shape, below) */
 #define BM25_MAX_SLICES 256
 #define BM25_FAST_CLAUSES 8   /* queries of at most this many clauses take bm25_fast_kernel */
+#define BM25_PROBE_MAX_DENSE 4   /* dense clauses of a query bm25_probe_kernel serves (bm25_plan_probe) */
 
 // ---- the knobs of one call (no effect on results) ----------------------------------------------------------------------------------
 struct Bm25PlanKnobs {
@@ -36,6 +37,7 @@ struct Bm25PlanBatch {
     const uint64_t *clause_offsets = nullptr;   // [nq + 1]
     const uint64_t *clause_len = nullptr;       // [n_clauses]
     const uint32_t *clause_term = nullptr;      // [n_clauses]
+    const int32_t *clause_occur = nullptr, *clause_mode = nullptr;   // [n_clauses] each; read only with dense flags (bm25_plan_probe)
     uint32_t special_bits = 0;
     uint32_t nq = 0;
     uint32_t n_docs = 0;   // of the segment
@@ -112,7 +114,7 @@ struct Bm25QueryPlan {
     uint32_t slices = 1;
     bool is_union = false;
 };
-inline Bm25QueryPlan bm25_plan_query(const Bm25PlanKnobs &kn, const Bm25PlanBatch &b, const Bm25SliceShape &sh, uint32_t q) {
+inline Bm25QueryPlan bm25_plan_query(const Bm25PlanKnobs &kn, const Bm25PlanBatch &b, const Bm25SliceShape &sh, uint32_t q, bool never_union = false) {
     const double inv_docs = 1.0 / std::max<double>(1.0, (double)b.n_docs);
     const uint64_t c0 = b.clause_offsets[q], c1 = b.clause_offsets[q + 1];
     const uint64_t *clen = b.clause_len;
@@ -128,7 +130,7 @@ inline Bm25QueryPlan bm25_plan_query(const Bm25PlanKnobs &kn, const Bm25PlanBatc
     }
     Bm25QueryPlan out;
     uint32_t slices = (uint32_t)std::min<uint64_t>(BM25_MAX_SLICES, std::max<uint64_t>(1, (sh.weigh(p, p_longest) + sh.slice - 1) / sh.slice));
-    if (kn.union_mode != 0 && plain && c1 > c0 && c1 - c0 <= BM25_FAST_CLAUSES && !kn.force_wide) {
+    if (kn.union_mode != 0 && plain && c1 > c0 && c1 - c0 <= BM25_FAST_CLAUSES && !kn.force_wide && !never_union) {
         const double sum = (double)p, shared = (sum * sum - sum_sq) * 0.5 * inv_docs;
         // the same term twice: those two lists meet in every document (the estimate above assumes independent lists)
         double repeated = 0.0;
@@ -166,27 +168,73 @@ inline Bm25QueryPlan bm25_plan_query(const Bm25PlanKnobs &kn, const Bm25PlanBatc
     return out;
 }
 
+// ---- dense clauses answered by a bitmap probe (bm25_probe.hip) ---------------------------------------------------------------------------
+// `dense` [n_clauses of the batch]: 1 = the clause is a plain term whose list holds so large a share of the documents that a bitmap over
+// the doc ids stands for it (bm25_index.cpp decides: list_length * "dense_probe" >= n_docs, and the bitmap is resident unless the mode
+// is TF_FREQ).  A query goes to bm25_probe_kernel when it has at most BM25_FAST_CLAUSES clauses, one to BM25_PROBE_MAX_DENSE of them dense
+// and each of those TF_BASIC (1) or CONST_SCORE (2) — a dense TF_FREQ clause would need its tf — and when every document that can match
+// holds a posting of a SPARSE clause: a sparse Must, or a required Should group (occur 3 + g) without a dense member.  Then the sparse
+// lists alone name the candidates and a dense clause costs a candidate one gathered bit.
+inline bool bm25_plan_probe(const Bm25PlanKnobs &kn, const Bm25PlanBatch &b, const uint8_t *dense, uint32_t q) {
+    const uint64_t c0 = b.clause_offsets[q], c1 = b.clause_offsets[q + 1];
+    if (!dense || kn.force_wide || c1 == c0 || c1 - c0 > BM25_FAST_CLAUSES) return false;
+    uint32_t n_dense = 0, groups = 0, groups_dense = 0;
+    bool sparse_must = false;
+    for (uint64_t c = c0; c < c1; c++) {
+        const int32_t occur = b.clause_occur[c], mode = b.clause_mode[c];
+        const uint32_t group_bit = occur >= 3 ? 1u << ((occur - 3) & 31) : 0u;
+        groups |= group_bit;
+        if (dense[c]) {
+            if ((b.clause_term[c] & b.special_bits) || (mode != 1 && mode != 2)) return false;
+            n_dense++;
+            groups_dense |= group_bit;
+        } else if (occur == 1) {
+            sparse_must = true;
+        }
+    }
+    return n_dense >= 1 && n_dense <= BM25_PROBE_MAX_DENSE && (sparse_must || (groups & ~groups_dense) != 0);
+}
+
 // ---- the work list and its partition ---------------------------------------------------------------------------------------------------
-// Three launches over disjoint item lists: term unions whose lists rarely meet (bm25_stream.hip), the other narrow queries
-// (bm25_fast_kernel), the rest (bm25_rows_kernel).  item_list holds the items' indices into `work` as union | fast | wide.
+// Four launches over disjoint item lists: term unions whose lists rarely meet (bm25_stream.hip), the other narrow queries
+// (bm25_fast_kernel), the rest (bm25_rows_kernel), and the queries whose dense clauses are probed (bm25_probe_kernel; none without
+// dense flags).  item_list holds the items' indices into `work` as union | fast | wide | probe.
 struct Bm25WorkPlan {
     Bm25SliceShape shape;
-    uint32_t n_union = 0, n_fast = 0, n_wide = 0;
+    uint32_t n_union = 0, n_fast = 0, n_wide = 0, n_probe = 0;
     uint32_t wide_max_clauses = 0;   // the most clauses any wide item has
 };
 // work: the items, query by query, slice by slice; item_first [nq + 1]: query q's items are [item_first[q], item_first[q + 1]);
-// q_union [nq]: 1 = a union query.  The vectors are the caller's, kept for their capacity; `weighted` is bm25_plan_slice's scratch.
-inline Bm25WorkPlan bm25_plan_work(const Bm25PlanKnobs &kn, const Bm25PlanBatch &b, std::vector<uint64_t> &weighted, std::vector<Bm25Work> &work,
-                                   std::vector<uint32_t> &item_first, std::vector<uint8_t> &q_union, std::vector<uint32_t> &item_list) {
+// q_union [nq]: 1 = a union query, 2 = a probe query.  The vectors are the caller's, kept for their capacity; `weighted` is
+// bm25_plan_slice's scratch.  `dense` (nullptr = none: the plan is what it was before there were probes) marks the dense clauses; a probe
+// query is cut over its SPARSE postings alone — its dense clauses weigh 0 in `sparse_len`, the caller's scratch like `weighted` — and
+// is tested before the union rule.
+inline Bm25WorkPlan bm25_plan_work(const Bm25PlanKnobs &kn, const Bm25PlanBatch &b_in, std::vector<uint64_t> &weighted, std::vector<Bm25Work> &work,
+                                   std::vector<uint32_t> &item_first, std::vector<uint8_t> &q_union, std::vector<uint32_t> &item_list,
+                                   const uint8_t *dense = nullptr, std::vector<uint64_t> *sparse_len = nullptr) {
     Bm25WorkPlan plan;
+    Bm25PlanBatch b = b_in;
     work.clear();
     item_first.assign((size_t)b.nq + 1, 0);
     q_union.assign(b.nq, 0);
+    if (dense && sparse_len) {
+        bool any = false;
+        for (uint32_t q = 0; q < b.nq; q++)
+            if (bm25_plan_probe(kn, b, dense, q)) q_union[q] = 2, any = true;
+        if (any) {
+            sparse_len->assign(b.clause_len, b.clause_len + b.clause_offsets[b.nq]);
+            for (uint32_t q = 0; q < b.nq; q++)
+                for (uint64_t c = b.clause_offsets[q]; c < b.clause_offsets[q + 1] && q_union[q] == 2; c++)
+                    if (dense[c]) (*sparse_len)[c] = 0;
+            b.clause_len = sparse_len->data();
+        }
+    }
     plan.shape = bm25_plan_slice(kn, b, weighted);
     for (uint32_t q = 0; q < b.nq; q++) {
         item_first[q] = (uint32_t)work.size();
-        const Bm25QueryPlan qp = bm25_plan_query(kn, b, plan.shape, q);
-        q_union[q] = qp.is_union ? 1 : 0;
+        const bool probe = q_union[q] == 2;
+        const Bm25QueryPlan qp = bm25_plan_query(kn, b, plan.shape, q, probe);
+        if (!probe) q_union[q] = qp.is_union ? 1 : 0;
         const uint64_t c0 = b.clause_offsets[q], c1 = b.clause_offsets[q + 1];
         const Bm25Work w{q, 0, qp.slices, (uint32_t)c0, (uint32_t)(c1 - c0)};
         work.resize(work.size() + qp.slices, w);
@@ -197,7 +245,7 @@ inline Bm25WorkPlan bm25_plan_work(const Bm25PlanKnobs &kn, const Bm25PlanBatch 
     item_first[b.nq] = (uint32_t)nw;
     item_list.resize(nw);
     for (size_t w = 0; w < nw; w++)
-        if (q_union[work[w].query]) item_list[plan.n_union++] = (uint32_t)w;
+        if (q_union[work[w].query] == 1) item_list[plan.n_union++] = (uint32_t)w;
     if (plan.n_union < nw) {
         for (size_t w = 0; w < nw; w++) {
             const uint32_t nc = work[w].n_clauses;
@@ -210,6 +258,8 @@ inline Bm25WorkPlan bm25_plan_work(const Bm25PlanKnobs &kn, const Bm25PlanBatch 
                 plan.wide_max_clauses = std::max(plan.wide_max_clauses, nc);
             }
         }
+        for (size_t w = 0; w < nw; w++)
+            if (q_union[work[w].query] == 2) item_list[plan.n_union + plan.n_fast + plan.n_wide + plan.n_probe++] = (uint32_t)w;
     }
     return plan;
 }

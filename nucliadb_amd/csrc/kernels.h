@@ -659,6 +659,10 @@ struct Bm25Args {
     uint32_t match_words;
     const Bm25StreamClause *uclauses;       // [n_clauses of the batch] (bm25_stream_kernel), parallel to `clauses`
     Bm25FusedMerge fm;                      // bm25_stream_kernel only
+    // bm25_probe_kernel only (bm25_probe.hip): per clause of the batch the device address of its dense bitmap (ceil(n_docs / 64) u64 words
+    // over the resident doc ids), 0 = a sparse clause; and the index's counter of probes made (nullptr: not counted)
+    const unsigned long long *dense_bits = nullptr;
+    unsigned long long *probe_count = nullptr;
 };
 #define BM25_AUX_TERM 0x80000000u
 struct Bm25MergeArgs {  // per query: merge the key lists of its work items [item_first[q], item_first[q + 1])
@@ -684,6 +688,10 @@ hipError_t launch_bm25_search(const Bm25Args &a, const uint32_t *fast_items, uin
 // term unions whose lists rarely meet, term at a time (bm25_stream.hip); extras = alive bitset / facet bitsets / order by a fast field /
 // search-after
 hipError_t launch_bm25_stream(const Bm25Args &a, const uint32_t *items, uint32_t n_items, bool extras, hipStream_t s);
+// queries whose dense clauses are bitmap probes (bm25_probe.hip): the contract of bm25_fast_kernel; out_postings counts sparse postings
+hipError_t launch_bm25_probe(const Bm25Args &a, const uint32_t *items, uint32_t n_items, hipStream_t s);
+// bit d of the zeroed `bits` for every doc id d of the ascending list ids[0, n)
+hipError_t launch_bm25_dense_bitmap(const uint32_t *ids, unsigned long long n, unsigned long long *bits, hipStream_t s);
 
 // ---- BM25 surroundings (bm25_aux.hip) ----
 // FuzzyTermQuery's automaton over the whole term dictionary: flags[t] = 1 when term t is accepted
