@@ -73,6 +73,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_MAXSIM_MFMA 65536 /* nidx_gpu_vector_set_tunable "maxsim_stage" = 1: the maxsim second stage on the f32 matrix cores */
 #define NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA (1u << 17) /* = 131072; nidx_gpu_vector_set_tunable "pq_scan_stage" = 1: the brute-force arm of the per-query-filter searches as packed GEMMs on the f32 matrix cores */
 #define NIDX_FEATURE_BM25_DENSE_PROBE (1u << 18) /* = 262144; nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats: dense Must / MustNot / Should clauses of a BM25 query as bitmap probes */
+#define NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA (1u << 19) /* = 524288; nidx_gpu_vector_set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats: the estimates of NIDX_METHOD_RABITQ_BRUTE_FORCE as an int8 GEMM on the matrix cores */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -180,8 +181,20 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * NIDX_ERR_INVALID_ARGUMENT.  See that entry.
  * "pq_scan_pages" (read only while "pq_scan_stage" is 1): 0 (default) = that arm keeps at most 64 hits per query and refuses larger
  * pages; 1 = pages of 65 .. 512 hits on single-vector segments are served by a second kernel with the same score bits (a multi-vector
- * segment still refuses them); any other value is NIDX_ERR_INVALID_ARGUMENT.  k <= 64 is unaffected. */
+ * segment still refuses them); any other value is NIDX_ERR_INVALID_ARGUMENT.  k <= 64 is unaffected.
+ * "rabitq_scan_stage" (present with NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA) changes NO bit: 0 (default) = NIDX_METHOD_RABITQ_BRUTE_FORCE
+ * scores every passing row with one wave per query; 1 = the passing rows are packed into one ascending list, the estimates of the whole
+ * batch are one int8 GEMM on the matrix cores (an estimate is an integer dot product: no summation order), and a wave per query replays
+ * the re-rank over the list.  Single-vector segments with one filter for the batch; a multi-vector segment and the per-query-filter
+ * entries keep stage 0, silently.  Any other value is NIDX_ERR_INVALID_ARGUMENT.
+ * "rabitq_scan_scratch_kib": the cap, in KiB, of that stage's scratch matrix of upper bounds (4 bytes x queries x rows of the segment
+ * rounded up to 128); a batch that needs more is searched in consecutive chunks of queries.  0 = the default, 1 GiB; negative values are
+ * NIDX_ERR_INVALID_ARGUMENT. */
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value);
+/* Since open: queries of NIDX_METHOD_RABITQ_BRUTE_FORCE answered by "rabitq_scan_stage" = 1, and queries that reached the arm while the
+ * stage was 1 but were handed to the one-wave-per-query kernel (multi-vector segment, per-query filter rows).  Either pointer may be
+ * NULL. */
+int32_t nidx_gpu_vector_rabitq_scan_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *fallback_queries_out);
 
 /* NIDX_METHOD_BRUTE_FORCE_MFMA: the same exact scan as a dense GEMM on the f32 matrix cores (one
  * pass over the corpus per batch, k <= 64; pages of k <= 16 keep two workgroups per CU).  It sums in
@@ -428,6 +441,9 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
  *     launches; a batch whose scratch would pass the 1 GiB cap is searched in chunks of queries).  The HNSW and RaBitQ arms are unchanged; the routed and prefiltered
  *     tickets are answered by this blocking path while the stage is 1, with the same bits.  Still one search plus one
  *     synchronisation per (segment, arm): the plan's upload, the norms of the arm's queries, three packing launches, one GEMM, one merge.
+ *   - Tunable "rabitq_scan_stage" = 1 (NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA) does NOT cover this entry: its queries test their own
+ *     filter rows, so the RaBitQ brute-force arm here stays the one-wave-per-query kernel whatever the tunable says.  The bits are the
+ *     same either way; nidx_gpu_vector_rabitq_scan_stats counts such queries as fallbacks.
  * out_method: NULL or [n_queries][n_segments] (0 = segment not searched for that query); out_matching: NULL or
  * [n_filters][n_segments] (0 for a filter no query names). */
 int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,

@@ -414,6 +414,47 @@ hipError_t launch_rabitq_query(const float *queries, uint32_t nq, uint32_t dp, u
                                uint64_t *planes, hipStream_t s);
 hipError_t launch_rabitq_bf(const RabitqSearchArgs &a, hipStream_t s);
 hipError_t launch_rabitq_hnsw(const RabitqSearchArgs &a, hipStream_t s);
+// ---- the brute-force arm's estimates as an int8 GEMM on the matrix cores (rabitq_mfma.hip; tunable "rabitq_scan_stage" = 1) ----
+// One packed list per launch: the ascending rows that pass alive AND filter, made by launch_pq_pack from the bitset that
+// launch_rabitq_scan_list writes.  `region` (4-byte words) is launch_pq_pack's: the list record at 0, the list's length at at_total,
+// the span counts, then the entries.
+struct RabitqScanList {
+    uint32_t words, spans;                       // 64-bit words of the bitset, spans of 64 words
+    uint32_t at_total, at_counts, at_entries;    // words of the region
+    uint32_t total_words;
+};
+inline RabitqScanList rabitq_scan_list(uint32_t n) {
+    RabitqScanList l;
+    l.words = (n + 63u) / 64u;
+    l.spans = (l.words + 63u) / 64u;
+    l.at_total = 4;
+    l.at_counts = 8;
+    l.at_entries = (8u + l.spans + 3u) & ~3u;
+    l.total_words = l.at_entries + n;
+    return l;
+}
+// the pitch of a query's row of upper bounds: the list cannot be longer than the segment (its length is known on the device only)
+inline uint32_t rabitq_scan_pitch(uint32_t n) { return (n + 127u) / 128u * 128u; }
+#define NIDX_RABITQ_SCAN_QUERY_PAD 128   /* zero rows behind the batch's int8 queries: a ragged last query block reads them */
+struct RabitqScanArgs {
+    const uint8_t *quant;         // [n][rec_len]
+    uint32_t rec_len, dim, n;
+    const uint32_t *region;
+    uint32_t at_total, at_entries;
+    const int8_t *q8;             // [the chunk's queries, then at least NIDX_RABITQ_SCAN_QUERY_PAD more rows][dim] values 0..15
+    const RabitqQueryDev *qd;     // [n_queries] the chunk's
+    uint32_t n_queries;
+    float *ub;                    // [n_queries][pitch]: est + err of list entry e at [q][e]
+    uint32_t pitch;
+};
+// bits[w] = alive[w] & filter[w] (either may be nullptr: all ones) and the region's list record; the length starts at 0
+hipError_t launch_rabitq_scan_list(const uint64_t *alive, const uint64_t *filter, uint32_t n, const RabitqScanList &l, uint64_t *bits,
+                                   uint32_t *region, hipStream_t s);
+// planes [nq][4][nw] -> q8 [nq + NIDX_RABITQ_SCAN_QUERY_PAD][64 nw]; plane word w, bit i = element 64 w + i
+hipError_t launch_rabitq_scan_expand(const uint64_t *planes, uint32_t nq, uint32_t nw, int8_t *q8, hipStream_t s);
+hipError_t launch_rabitq_scan_gemm(const RabitqScanArgs &m, hipStream_t s);
+// rabitq_bf_kernel's re-rank over the list and its upper bounds; `a` as for launch_rabitq_bf (queries, out_*, stats of the chunk)
+hipError_t launch_rabitq_scan_rerank(const RabitqSearchArgs &a, const RabitqScanArgs &m, hipStream_t s);
 // several segments' walks in one launch: `table` (device, n_table records agreeing in shape with `shape`); block b = query b % nq of record b / nq
 uint32_t rabitq_seen_log2();   // 9; NIDX_GPU_RABITQ_SEEN=0 / 8...13 (measurement)
 hipError_t launch_rabitq_hnsw_segments(const RabitqSearchArgs *table, uint32_t n_table, const RabitqSearchArgs &shape, hipStream_t s);

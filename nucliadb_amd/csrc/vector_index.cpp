@@ -841,6 +841,14 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
             r.out_vec = d_out_vec;
             r.out_score = d_out_score;
             r.out_count = d_out_count;
+            if (rabitq_scan_stage == 1) {
+                if (seg.identity_para && !pq_filter_row) {
+                    const int32_t rc = segment_rabitq_scan(seg, r, st);
+                    if (rc == NIDX_OK) rabitq_scan_queries.fetch_add(nq, std::memory_order_relaxed);
+                    return rc;
+                }
+                rabitq_scan_fallback_queries.fetch_add(nq, std::memory_order_relaxed);   // multi-vector / per-query rows: the same bits below
+            }
             NIDX_HIP(launch_rabitq_bf(r, st));
             return NIDX_OK;
         }
@@ -1148,6 +1156,59 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
                                scratch_cand_count.as<uint32_t>(), st));
     NIDX_HIP(launch_para_best(scratch_cand_vec.as<uint32_t>(), scratch_cand_score.as<float>(), scratch_cand_count.as<uint32_t>(), nq, k,
                               seg.para_of_vec.as<uint32_t>(), k_out, d_out_vec, d_out_score, d_out_count, st));
+    return NIDX_OK;
+}
+
+// ---- NIDX_METHOD_RABITQ_BRUTE_FORCE under "rabitq_scan_stage" = 1 (rabitq_mfma.hip), single-vector segment, one filter for the batch:
+//      `r` is launch_rabitq_bf's record.  Pack (the AND bitset, launch_pq_pack's one list), the queries' planes as int8 rows, then per
+//      chunk of queries one GEMM launch into the [chunk][pitch] matrix of upper bounds and one re-rank launch.  Nothing waits for the
+//      list's length: the pitch is the segment's size, which is what the chunking is cut by. ----
+int32_t VectorIndex::segment_rabitq_scan(const VectorSegment &seg, const RabitqSearchArgs &r, hipStream_t st) {
+    const uint32_t nq = r.n_queries, nw = seg.dim / 64u;
+    if (nq == 0) return NIDX_OK;
+    const RabitqScanList L = rabitq_scan_list(seg.n);
+    NIDX_HIP(scratch_rqs_bits.reserve((size_t)std::max<uint32_t>(L.words, 1) * 8));
+    NIDX_HIP(scratch_rqs_list.reserve((size_t)L.total_words * 4));
+    NIDX_HIP(launch_rabitq_scan_list(seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), r.filter, seg.n, L, scratch_rqs_bits.as<uint64_t>(),
+                                     scratch_rqs_list.as<uint32_t>(), st));
+    PqPackArgs pk;
+    pk.filter_table = scratch_rqs_bits.as<uint64_t>();
+    pk.alive = nullptr;   // (the list's row is row 0 of the table, never NIDX_FILTER_ROW_NONE)
+    pk.words = L.words;
+    pk.n_paragraphs = seg.n;
+    pk.para_first = nullptr, pk.para_num = nullptr;
+    pk.region = scratch_rqs_list.as<uint32_t>();
+    pk.at_lists = 0, pk.at_totals = L.at_total;
+    pk.n_packed = 1, pk.spans = L.spans;
+    NIDX_HIP(launch_pq_pack(pk, st));
+    NIDX_HIP(scratch_rqs_q8.reserve(((size_t)nq + NIDX_RABITQ_SCAN_QUERY_PAD) * seg.dim));
+    NIDX_HIP(launch_rabitq_scan_expand(r.planes, nq, nw, scratch_rqs_q8.as<int8_t>(), st));
+    const uint32_t pitch = rabitq_scan_pitch(seg.n);
+    const uint64_t row_bytes = std::max<uint64_t>((uint64_t)pitch * 4, 1);
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nq, rabitq_scan_scratch_cap / row_bytes));
+    NIDX_HIP(scratch_rqs_ub.reserve(std::max<size_t>((size_t)chunk * pitch * 4, 4)));
+    RabitqScanArgs m;
+    m.quant = r.quant;
+    m.rec_len = r.rec_len, m.dim = seg.dim, m.n = seg.n;
+    m.region = scratch_rqs_list.as<uint32_t>();
+    m.at_total = L.at_total, m.at_entries = L.at_entries;
+    m.ub = scratch_rqs_ub.as<float>();
+    m.pitch = pitch;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t cnt = std::min(chunk, nq - q0);
+        m.q8 = scratch_rqs_q8.as<int8_t>() + (size_t)q0 * seg.dim;
+        m.qd = r.qd + q0;
+        m.n_queries = cnt;
+        NIDX_HIP(launch_rabitq_scan_gemm(m, st));
+        RabitqSearchArgs rs = r;
+        rs.n_queries = cnt;
+        rs.queries = r.queries + (size_t)q0 * seg.dp;
+        rs.out_vec = r.out_vec + (size_t)q0 * r.k;
+        rs.out_score = r.out_score + (size_t)q0 * r.k;
+        rs.out_count = r.out_count + q0;
+        rs.stats = r.stats ? r.stats + (size_t)q0 * NIDX_STAT_STRIDE : nullptr;
+        NIDX_HIP(launch_rabitq_scan_rerank(rs, m, st));
+    }
     return NIDX_OK;
 }
 
@@ -2211,7 +2272,7 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
            NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA |
-           NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE;
+           NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE | NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2337,7 +2398,23 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_pages must be 0 or 1");
         idx->pq_scan_pages = (int)value;
     }
+    else if (n == "rabitq_scan_stage") {   // NIDX_METHOD_RABITQ_BRUTE_FORCE: 0 = one wave per query (default), 1 = the estimates as an int8 GEMM on the matrix cores (the same bits)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_stage must be 0 or 1");
+        idx->rabitq_scan_stage = (int)value;
+    }
+    else if (n == "rabitq_scan_scratch_kib") {   // the cap of that stage's matrix of upper bounds, which cuts a batch into chunks of queries (0 = 1 GiB)
+        if (value < 0) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_scratch_kib must not be negative");
+        idx->rabitq_scan_scratch_cap = value > 0 ? (uint64_t)value << 10 : 1ull << 30;
+    }
     else return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown tunable %s", name);
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_rabitq_scan_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *fallback_queries_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (queries_out) *queries_out = idx->rabitq_scan_queries.load(std::memory_order_relaxed);
+    if (fallback_queries_out) *fallback_queries_out = idx->rabitq_scan_fallback_queries.load(std::memory_order_relaxed);
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

@@ -252,6 +252,15 @@ struct VectorIndex {
     int32_t ensure_norm2_serial(VectorSegment &seg, hipStream_t st);
     PinBuf pin_maxsim_in, pin_maxsim_out;
     std::atomic<uint64_t> maxsim_queries{0}, maxsim_host_finished{0};   // nidx_gpu_vector_maxsim_stats
+    // tunable "rabitq_scan_stage" = 1: NIDX_METHOD_RABITQ_BRUTE_FORCE on a single-vector segment without per-query filter rows takes its
+    // estimates from an int8 GEMM on the matrix cores (rabitq_mfma.hip: pack, GEMM, re-rank stream) — the same bits as rabitq_bf_kernel,
+    // which keeps multi-vector segments and the per-query-filter arm (counted as fallbacks).  The [queries][pitch] matrix of upper bounds
+    // stays under rabitq_scan_scratch_cap (tunable "rabitq_scan_scratch_kib"): a batch that needs more goes in chunks of queries
+    int rabitq_scan_stage = 0;
+    uint64_t rabitq_scan_scratch_cap = 1ull << 30;
+    std::atomic<uint64_t> rabitq_scan_queries{0}, rabitq_scan_fallback_queries{0};   // nidx_gpu_vector_rabitq_scan_stats
+    DevBuf scratch_rqs_bits, scratch_rqs_list, scratch_rqs_q8, scratch_rqs_ub;
+    int32_t segment_rabitq_scan(const VectorSegment &seg, const RabitqSearchArgs &r, hipStream_t st);
     uint64_t spill_queries = 0;  // queries re-run by the exact fallback since open (tunable "spill_queries" reads it)
     bool rabitq_enabled(const VectorSegment &seg) const { return seg.has_quant && !(cfg.flags & NIDX_CONFIG_DISABLE_RABITQ_SEARCH); }
     int32_t quantize(uint32_t segment);

@@ -943,8 +943,14 @@ class VectorSearcher:
         """nidx_gpu_vector_set_tunable.  Two tunables change score BITS (NIDX_ORDER_SERIAL_FMA instead of WAVE64) and are therefore never
         on by default: "maxsim_stage" = 1 (FEATURE_VECTOR_MAXSIM_MFMA) and "pq_scan_stage" = 1 (FEATURE_VECTOR_PQ_SCAN_MFMA: the
         brute-force arm of every per-query-filter search as packed GEMMs on the f32 matrix cores, meant for batches whose queries share
-        filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well)."""
-        need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA}.get(name, 0)
+        filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well).
+        "rabitq_scan_stage" = 1 and "rabitq_scan_scratch_kib" (FEATURE_VECTOR_RABITQ_SCAN_MFMA) change NO bit: the estimates of
+        METHOD_RABITQ_BRUTE_FORCE come from an int8 GEMM on the matrix cores instead of one wave per query (single-vector segments, one
+        filter per batch; anything else keeps the old kernel, see rabitq_scan_stats), and the second caps that stage's scratch in KiB
+        (0 = 1 GiB), cutting a batch into chunks of queries."""
+        need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA,
+                "rabitq_scan_stage": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA,
+                "rabitq_scan_scratch_kib": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA}.get(name, 0)
         if need and not _lib.lib().nidx_gpu_build_features() & need:
             raise RuntimeError(f"this libnidx_gpu build does not know the tunable {name!r}")
         _lib.check(_lib.lib().nidx_gpu_vector_set_tunable(self._handle, name.encode(), int(value)))
@@ -977,6 +983,12 @@ class VectorSearcher:
         out = C.c_uint64(0)
         _lib.check(_lib.lib().nidx_gpu_vector_space_usage(self._handle, C.byref(out)))
         return out.value
+
+    def rabitq_scan_stats(self) -> Tuple[int, int]:
+        """Since open: (queries answered by "rabitq_scan_stage" = 1, queries the stage handed to the one-wave-per-query kernel)."""
+        done, fallback = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_vector_rabitq_scan_stats(self._handle, C.byref(done), C.byref(fallback)))
+        return done.value, fallback.value
 
     def spill_queries(self) -> int:
         """Queries re-run by the exact HBM-resident closest_up_nodes fallback since open."""
