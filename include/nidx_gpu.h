@@ -74,6 +74,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA (1u << 17) /* = 131072; nidx_gpu_vector_set_tunable "pq_scan_stage" = 1: the brute-force arm of the per-query-filter searches as packed GEMMs on the f32 matrix cores */
 #define NIDX_FEATURE_BM25_DENSE_PROBE (1u << 18) /* = 262144; nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats: dense Must / MustNot / Should clauses of a BM25 query as bitmap probes */
 #define NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA (1u << 19) /* = 524288; nidx_gpu_vector_set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats: the estimates of NIDX_METHOD_RABITQ_BRUTE_FORCE as an int8 GEMM on the matrix cores */
+#define NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS (1u << 20) /* = 1048576; nidx_gpu_vector_set_tunable "rabitq_scan_groups" = 1: that stage for per-query filter rows and multi-vector segments, as grouped GEMMs and a grouped re-rank */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -186,7 +187,14 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * scores every passing row with one wave per query; 1 = the passing rows are packed into one ascending list, the estimates of the whole
  * batch are one int8 GEMM on the matrix cores (an estimate is an integer dot product: no summation order), and a wave per query replays
  * the re-rank over the list.  Single-vector segments with one filter for the batch; a multi-vector segment and the per-query-filter
- * entries keep stage 0, silently.  Any other value is NIDX_ERR_INVALID_ARGUMENT.
+ * entries keep stage 0, silently, unless "rabitq_scan_groups" is 1.  Any other value is NIDX_ERR_INVALID_ARGUMENT.
+ * "rabitq_scan_groups" (present with NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS; read only while "rabitq_scan_stage" is 1) changes NO bit
+ * either: 0 (default) = as above; 1 = those two cases take the stage too.  The arm's queries are grouped by filter row into blocks of at
+ * most 128 queries that share one packed list (on a multi-vector segment the vectors of the passing paragraphs, in paragraph order);
+ * every block is one int8 GEMM over its own list, and the re-rank of a multi-vector segment reduces a paragraph's estimates to the
+ * best, the last of equal ones (segment.rs:586-593), before it feeds.  Such queries count in queries_out of
+ * nidx_gpu_vector_rabitq_scan_stats.  A block's scratch matrix is its queries x its list's capacity rounded up to 128; blocks run in
+ * as many consecutive launches as "rabitq_scan_scratch_kib" asks for.  Any other value is NIDX_ERR_INVALID_ARGUMENT.
  * "rabitq_scan_scratch_kib": the cap, in KiB, of that stage's scratch matrix of upper bounds (4 bytes x queries x rows of the segment
  * rounded up to 128); a batch that needs more is searched in consecutive chunks of queries.  0 = the default, 1 GiB; negative values are
  * NIDX_ERR_INVALID_ARGUMENT. */
@@ -443,7 +451,10 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
  *     synchronisation per (segment, arm): the plan's upload, the norms of the arm's queries, three packing launches, one GEMM, one merge.
  *   - Tunable "rabitq_scan_stage" = 1 (NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA) does NOT cover this entry: its queries test their own
  *     filter rows, so the RaBitQ brute-force arm here stays the one-wave-per-query kernel whatever the tunable says.  The bits are the
- *     same either way; nidx_gpu_vector_rabitq_scan_stats counts such queries as fallbacks.
+ *     same either way; nidx_gpu_vector_rabitq_scan_stats counts such queries as fallbacks.  With "rabitq_scan_groups" = 1
+ *     (NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS) as well it does: the arm's queries on a segment are grouped by filter row, each group is
+ *     an int8 GEMM over the rows its filter lets through, and the queries count as answered by the stage (an arm without a filtered
+ *     query on a single-vector segment takes the one-list path of the blocking search).  The same bits again.
  * out_method: NULL or [n_queries][n_segments] (0 = segment not searched for that query); out_matching: NULL or
  * [n_filters][n_segments] (0 for a filter no query names). */
 int32_t nidx_gpu_vector_search_filtered_per_query(nidx_gpu_vector_index_t *index, const float *queries, uint32_t n_queries,

@@ -455,6 +455,29 @@ hipError_t launch_rabitq_scan_expand(const uint64_t *planes, uint32_t nq, uint32
 hipError_t launch_rabitq_scan_gemm(const RabitqScanArgs &m, hipStream_t s);
 // rabitq_bf_kernel's re-rank over the list and its upper bounds; `a` as for launch_rabitq_bf (queries, out_*, stats of the chunk)
 hipError_t launch_rabitq_scan_rerank(const RabitqSearchArgs &a, const RabitqScanArgs &m, hipStream_t s);
+// ---- the same stage for groups of queries that share a list (tunable "rabitq_scan_groups" = 1): per-query filter rows, multi-vector
+// segments.  `region` is pq_mfma_plan's, filled by launch_pq_pack.  One launch pair serves a RUN of the plan's blocks whose scratch
+// matrices fit the cap: item i is slots [first, first + slots) of a block's queries against the block's list, and owns the
+// [slots][pitch] floats at ub + 128 * offset, pitch = rabitq_scan_pitch(the list's planned capacity). ----
+#define NIDX_RABITQ_GROUP_NONE 0xffffffffu
+struct RabitqGroupArgs {
+    const uint8_t *quant;         // [n][rec_len]
+    uint32_t rec_len, dim, n;
+    const uint32_t *region;
+    uint32_t at_blocks, at_lists, at_totals;
+    const uint32_t *items;        // [n_items][4]: block, first slot, slots, offset (in units of 128 floats)
+    uint32_t n_items, max_stripes;
+    const uint32_t *waves;        // [n_waves][2]: (item, slot of the item), or (NIDX_RABITQ_GROUP_NONE, query) for a query in no block
+    uint32_t n_waves;
+    const int8_t *q8;             // [n_queries + NIDX_RABITQ_SCAN_QUERY_PAD][dim] the arm's compact query array, expanded
+    const RabitqQueryDev *qd;     // [n_queries]
+    uint32_t n_queries;
+    float *ub;                    // single-vector: est + err; multi-vector: est (the re-rank adds the winning vector's err)
+    const uint32_t *para_of_vec;  // multi-vector segments: [n]; nullptr: entry = paragraph
+};
+hipError_t launch_rabitq_scan_group_gemm(const RabitqGroupArgs &m, hipStream_t s);
+// one wave per entry of `waves`; `a` as for launch_rabitq_bf over the arm's compact query array (outputs indexed by query)
+hipError_t launch_rabitq_scan_group_rerank(const RabitqSearchArgs &a, const RabitqGroupArgs &m, hipStream_t s);
 // several segments' walks in one launch: `table` (device, n_table records agreeing in shape with `shape`); block b = query b % nq of record b / nq
 uint32_t rabitq_seen_log2();   // 9; NIDX_GPU_RABITQ_SEEN=0 / 8...13 (measurement)
 hipError_t launch_rabitq_hnsw_segments(const RabitqSearchArgs *table, uint32_t n_table, const RabitqSearchArgs &shape, hipStream_t s);

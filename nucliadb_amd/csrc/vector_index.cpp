@@ -842,8 +842,31 @@ int32_t VectorIndex::segment_search_device_scratch(uint32_t s, const float *d_qu
             r.out_score = d_out_score;
             r.out_count = d_out_count;
             if (rabitq_scan_stage == 1) {
-                if (seg.identity_para && !pq_filter_row) {
+                if (seg.identity_para && !pq_filter_row && !pq_mfma) {
                     const int32_t rc = segment_rabitq_scan(seg, r, st);
+                    if (rc == NIDX_OK) rabitq_scan_queries.fetch_add(nq, std::memory_order_relaxed);
+                    return rc;
+                }
+                if (rabitq_scan_groups == 1 && (pq_mfma || !pq_filter_row)) {   // per-query rows as a plan, or one filter on a multi-vector segment
+                    const PqMfmaPlan *plan = pq_mfma;
+                    const uint64_t *table = pq_mfma_table;
+                    if (!plan) {   // one list for the batch: the paragraphs that pass alive AND the filter, as rabitq_scan_list_kernel makes them
+                        const uint32_t words = (seg.n_paragraphs + 63u) / 64u;
+                        if (d_filter) {
+                            const RabitqScanList L = rabitq_scan_list(seg.n_paragraphs);
+                            NIDX_HIP(scratch_rqs_bits.reserve((size_t)std::max<uint32_t>(L.words, 1) * 8));
+                            NIDX_HIP(scratch_rqs_list.reserve((size_t)L.at_entries * 4));   // (the kernel's one-list record: not used here)
+                            NIDX_HIP(launch_rabitq_scan_list(seg.all_alive ? nullptr : seg.alive.as<uint64_t>(), d_filter, seg.n_paragraphs, L,
+                                                             scratch_rqs_bits.as<uint64_t>(), scratch_rqs_list.as<uint32_t>(), st));
+                            table = scratch_rqs_bits.as<uint64_t>();
+                        }
+                        const std::vector<uint32_t> rows(nq, d_filter ? 0u : kPqRowNone);
+                        pq_mfma_plan(rows.data(), nq, [&](uint32_t row) -> uint32_t {   // the filter's count is on the device only: every paragraph
+                            return (uint32_t)std::min<uint64_t>((uint64_t)(row == kPqRowNone ? seg.alive_count : seg.n_paragraphs) * seg.vmax, seg.n); },
+                                     seg.all_alive, words, kRabitqGroupWorkgroups, rqg_plan);
+                        plan = &rqg_plan;
+                    }
+                    const int32_t rc = segment_rabitq_groups(seg, r, *plan, table, st);
                     if (rc == NIDX_OK) rabitq_scan_queries.fetch_add(nq, std::memory_order_relaxed);
                     return rc;
                 }
@@ -1208,6 +1231,90 @@ int32_t VectorIndex::segment_rabitq_scan(const VectorSegment &seg, const RabitqS
         rs.out_count = r.out_count + q0;
         rs.stats = r.stats ? r.stats + (size_t)q0 * NIDX_STAT_STRIDE : nullptr;
         NIDX_HIP(launch_rabitq_scan_rerank(rs, m, st));
+    }
+    return NIDX_OK;
+}
+
+// ---- the same arm under "rabitq_scan_groups" = 1: the queries of `r` (the arm's compact array) in the blocks of plan P, whose packed
+//      lists come from `table` (rows of filter AND alive over paragraphs) or the alive bitset.  The plan's upload, the packing launches,
+//      the queries' planes as int8 rows, then per RUN of blocks one grouped GEMM and one grouped re-rank.  Block b's matrix is n_q x
+//      pitch(its list's planned capacity); a run is as many consecutive blocks as fit rabitq_scan_scratch_cap, and a block that does not
+//      fit alone is cut by queries.  The lists' true lengths stay on the device.  Queries in no block (an empty list) ride with the first
+//      run's re-rank, which writes their empty hit lists. ----
+int32_t VectorIndex::segment_rabitq_groups(const VectorSegment &seg, const RabitqSearchArgs &r, const PqMfmaPlan &P, const uint64_t *table,
+                                           hipStream_t st) {
+    const uint32_t nq = r.n_queries, nw = seg.dim / 64u;
+    if (nq == 0) return NIDX_OK;
+    if (P.total_words > 0xffffffffull) return fail(NIDX_ERR_OUT_OF_MEMORY, "the packed lists of a RaBitQ scan outgrow one scratch region");
+    NIDX_HIP(scratch_rqg_region.reserve(std::max<size_t>(P.total_words, 1) * 4));
+    if (P.upload_words) NIDX_HIP(hipMemcpyAsync(scratch_rqg_region.p, P.upload.data(), P.upload_words * 4, hipMemcpyHostToDevice, st));
+    PqPackArgs pk;
+    pk.filter_table = table;
+    pk.alive = seg.all_alive ? nullptr : seg.alive.as<uint64_t>();
+    pk.words = (seg.n_paragraphs + 63) / 64;
+    pk.n_paragraphs = seg.n_paragraphs;
+    pk.para_first = seg.identity_para ? nullptr : seg.para_first.as<uint32_t>();
+    pk.para_num = seg.identity_para ? nullptr : seg.para_num.as<uint32_t>();
+    pk.region = scratch_rqg_region.as<uint32_t>();
+    pk.at_lists = (uint32_t)P.at_lists, pk.at_totals = (uint32_t)P.at_totals;
+    pk.n_packed = P.n_packed, pk.spans = P.spans;
+    NIDX_HIP(launch_pq_pack(pk, st));
+    NIDX_HIP(scratch_rqs_q8.reserve(((size_t)nq + NIDX_RABITQ_SCAN_QUERY_PAD) * seg.dim));
+    NIDX_HIP(launch_rabitq_scan_expand(r.planes, nq, nw, scratch_rqs_q8.as<int8_t>(), st));
+
+    // ---- the runs: items [block, first slot, slots, offset / 128] and waves [item of the run, slot] ----
+    struct Run { size_t item0, n_items, wave0, n_waves; uint32_t max_stripes; uint64_t floats; };
+    std::vector<Run> runs(1, Run{0, 0, 0, 0, 0, 0});
+    std::vector<uint32_t> items, waves;
+    std::vector<uint8_t> placed(nq, 0);
+    for (const PqMfmaBlock &b : P.blocks)
+        for (uint32_t i = 0; i < b.n_q; i++) placed[P.upload[b.q_at + i]] = 1;
+    for (uint32_t q = 0; q < nq; q++)
+        if (!placed[q]) waves.insert(waves.end(), {NIDX_RABITQ_GROUP_NONE, q});
+    runs[0].n_waves = waves.size() / 2;
+    const uint64_t cap_floats = rabitq_scan_scratch_cap / 4;
+    uint64_t most = 0;
+    for (size_t b = 0; b < P.blocks.size(); b++) {
+        const PqMfmaBlock &blk = P.blocks[b];
+        const uint64_t pitch = rabitq_scan_pitch(P.lists[blk.list].len);
+        const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blk.n_q, cap_floats / pitch));
+        for (uint32_t s0 = 0; s0 < blk.n_q; s0 += per) {
+            const uint32_t ns = std::min(per, blk.n_q - s0);
+            if (runs.back().n_items && (runs.back().floats + ns * pitch > cap_floats || runs.back().n_items == 65535u))
+                runs.push_back(Run{items.size() / 4, 0, waves.size() / 2, 0, 0, 0});
+            Run &run = runs.back();
+            if (run.floats / 128u > 0xffffffffull) return fail(NIDX_ERR_OUT_OF_MEMORY, "the scratch matrix of a RaBitQ scan outgrows its offsets");
+            items.insert(items.end(), {(uint32_t)b, s0, ns, (uint32_t)(run.floats / 128u)});
+            for (uint32_t i = 0; i < ns; i++) waves.insert(waves.end(), {(uint32_t)run.n_items, i});
+            run.n_items++;
+            run.n_waves += ns;
+            run.max_stripes = std::max(run.max_stripes, blk.stripes);
+            run.floats += ns * pitch;
+            most = std::max(most, run.floats);
+        }
+    }
+    rqg_aux = items;
+    rqg_aux.insert(rqg_aux.end(), waves.begin(), waves.end());
+    NIDX_HIP(scratch_rqg_aux.reserve(std::max<size_t>(rqg_aux.size(), 1) * 4));
+    if (!rqg_aux.empty()) NIDX_HIP(hipMemcpyAsync(scratch_rqg_aux.p, rqg_aux.data(), rqg_aux.size() * 4, hipMemcpyHostToDevice, st));
+    NIDX_HIP(scratch_rqs_ub.reserve(std::max<size_t>(most * 4, 4)));
+    RabitqGroupArgs m;
+    m.quant = r.quant;
+    m.rec_len = r.rec_len, m.dim = seg.dim, m.n = seg.n;
+    m.region = scratch_rqg_region.as<uint32_t>();
+    m.at_blocks = (uint32_t)P.at_blocks, m.at_lists = (uint32_t)P.at_lists, m.at_totals = (uint32_t)P.at_totals;
+    m.q8 = scratch_rqs_q8.as<int8_t>();
+    m.qd = r.qd;
+    m.n_queries = nq;
+    m.ub = scratch_rqs_ub.as<float>();
+    m.para_of_vec = seg.identity_para ? nullptr : seg.para_of_vec.as<uint32_t>();
+    for (const Run &run : runs) {
+        m.items = scratch_rqg_aux.as<uint32_t>() + run.item0 * 4;
+        m.n_items = (uint32_t)run.n_items, m.max_stripes = run.max_stripes;
+        m.waves = scratch_rqg_aux.as<uint32_t>() + items.size() + run.wave0 * 2;
+        m.n_waves = (uint32_t)run.n_waves;
+        NIDX_HIP(launch_rabitq_scan_group_gemm(m, st));
+        NIDX_HIP(launch_rabitq_scan_group_rerank(r, m, st));
     }
     return NIDX_OK;
 }
@@ -2065,6 +2172,14 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
                              seg.all_alive, words, kPqMfmaWorkgroups, pq_plan);
                 pq_mfma = &pq_plan;
                 pq_mfma_table = scratch_pq_table.as<uint64_t>() + (F ? tab_off[s] : 0);
+            } else if (arm == NIDX_METHOD_RABITQ_BRUTE_FORCE && rabitq_scan_stage == 1 && rabitq_scan_groups == 1 &&
+                       (filtered || !segs[s].identity_para)) {   // the same plan for the grouped int8 GEMMs (segment_rabitq_groups); an
+                const VectorSegment &seg = segs[s];              // unfiltered arm on a single-vector segment stays segment_rabitq_scan
+                pq_mfma_plan(idx_rows.data() + n, n, [&](uint32_t row) -> uint32_t {
+                    return (uint32_t)std::min<uint64_t>(matching_of(row, s) * seg.vmax, seg.n); },
+                             seg.all_alive, words, kRabitqGroupWorkgroups, pq_plan);
+                pq_mfma = &pq_plan;
+                pq_mfma_table = scratch_pq_table.as<uint64_t>() + (F ? tab_off[s] : 0);
             } else if (filtered) {   // (an arm whose queries are all unfiltered here runs the plain launches)
                 pq_filter_row = d_idx + n;
                 pq_filter_table = scratch_pq_table.as<uint64_t>() + tab_off[s];
@@ -2272,7 +2387,8 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_PARAGRAPH_PREFILTER_HANDOVER | NIDX_FEATURE_JSON_PREFILTER | NIDX_FEATURE_VECTOR_ROUTED_TICKETS |
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
            NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA |
-           NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE | NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA;
+           NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE | NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA |
+           NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2401,6 +2517,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "rabitq_scan_stage") {   // NIDX_METHOD_RABITQ_BRUTE_FORCE: 0 = one wave per query (default), 1 = the estimates as an int8 GEMM on the matrix cores (the same bits)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_stage must be 0 or 1");
         idx->rabitq_scan_stage = (int)value;
+    }
+    else if (n == "rabitq_scan_groups") {   // under "rabitq_scan_stage" = 1: 0 = per-query filter rows and multi-vector segments keep the one-wave-per-query kernel (default), 1 = grouped GEMMs and a grouped re-rank (the same bits)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_groups must be 0 or 1");
+        idx->rabitq_scan_groups = (int)value;
     }
     else if (n == "rabitq_scan_scratch_kib") {   // the cap of that stage's matrix of upper bounds, which cuts a batch into chunks of queries (0 = 1 GiB)
         if (value < 0) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_scratch_kib must not be negative");

@@ -254,13 +254,23 @@ struct VectorIndex {
     std::atomic<uint64_t> maxsim_queries{0}, maxsim_host_finished{0};   // nidx_gpu_vector_maxsim_stats
     // tunable "rabitq_scan_stage" = 1: NIDX_METHOD_RABITQ_BRUTE_FORCE on a single-vector segment without per-query filter rows takes its
     // estimates from an int8 GEMM on the matrix cores (rabitq_mfma.hip: pack, GEMM, re-rank stream) — the same bits as rabitq_bf_kernel,
-    // which keeps multi-vector segments and the per-query-filter arm (counted as fallbacks).  The [queries][pitch] matrix of upper bounds
+    // which keeps multi-vector segments and the per-query-filter arm (counted as fallbacks; see rabitq_scan_groups below).  The [queries][pitch] matrix of upper bounds
     // stays under rabitq_scan_scratch_cap (tunable "rabitq_scan_scratch_kib"): a batch that needs more goes in chunks of queries
     int rabitq_scan_stage = 0;
     uint64_t rabitq_scan_scratch_cap = 1ull << 30;
     std::atomic<uint64_t> rabitq_scan_queries{0}, rabitq_scan_fallback_queries{0};   // nidx_gpu_vector_rabitq_scan_stats
     DevBuf scratch_rqs_bits, scratch_rqs_list, scratch_rqs_q8, scratch_rqs_ub;
     int32_t segment_rabitq_scan(const VectorSegment &seg, const RabitqSearchArgs &r, hipStream_t st);
+    // tunable "rabitq_scan_groups" = 1 (read while rabitq_scan_stage is 1): the two cases above that stage 1 hands to rabitq_bf_kernel —
+    // per-query filter rows (search_per_query_chunk plans them with pq_mfma_plan and hands the plan over in pq_mfma / pq_mfma_table) and
+    // multi-vector segments — run grouped GEMMs over the plan's blocks and a grouped re-rank (rabitq_mfma.hip), the same bits again.
+    // A block's matrix is [its queries][its list's capacity rounded up to 128]; blocks go in runs that fit rabitq_scan_scratch_cap.
+    int rabitq_scan_groups = 0;
+    static constexpr uint32_t kRabitqGroupWorkgroups = 2048;   // what one grouped GEMM launch aims at, as launch_rabitq_scan_gemm
+    DevBuf scratch_rqg_region, scratch_rqg_aux;
+    PqMfmaPlan rqg_plan;             // the one-list plan of a blocking batch on a multi-vector segment (alive while its upload is in flight)
+    std::vector<uint32_t> rqg_aux;   // the runs' item and wave tables (the same)
+    int32_t segment_rabitq_groups(const VectorSegment &seg, const RabitqSearchArgs &r, const PqMfmaPlan &P, const uint64_t *table, hipStream_t st);
     uint64_t spill_queries = 0;  // queries re-run by the exact fallback since open (tunable "spill_queries" reads it)
     bool rabitq_enabled(const VectorSegment &seg) const { return seg.has_quant && !(cfg.flags & NIDX_CONFIG_DISABLE_RABITQ_SEARCH); }
     int32_t quantize(uint32_t segment);

@@ -947,9 +947,11 @@ class VectorSearcher:
         "rabitq_scan_stage" = 1 and "rabitq_scan_scratch_kib" (FEATURE_VECTOR_RABITQ_SCAN_MFMA) change NO bit: the estimates of
         METHOD_RABITQ_BRUTE_FORCE come from an int8 GEMM on the matrix cores instead of one wave per query (single-vector segments, one
         filter per batch; anything else keeps the old kernel, see rabitq_scan_stats), and the second caps that stage's scratch in KiB
-        (0 = 1 GiB), cutting a batch into chunks of queries."""
+        (0 = 1 GiB), cutting a batch into chunks of queries.  "rabitq_scan_groups" = 1 (FEATURE_VECTOR_RABITQ_SCAN_GROUPS, read while
+        "rabitq_scan_stage" is 1) extends the stage to per-query filter rows (search_many) and multi-vector segments: the same bits."""
         need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA,
                 "rabitq_scan_stage": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA,
+                "rabitq_scan_groups": _lib.FEATURE_VECTOR_RABITQ_SCAN_GROUPS,
                 "rabitq_scan_scratch_kib": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA}.get(name, 0)
         if need and not _lib.lib().nidx_gpu_build_features() & need:
             raise RuntimeError(f"this libnidx_gpu build does not know the tunable {name!r}")
