@@ -75,6 +75,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_BM25_DENSE_PROBE (1u << 18) /* = 262144; nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats: dense Must / MustNot / Should clauses of a BM25 query as bitmap probes */
 #define NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA (1u << 19) /* = 524288; nidx_gpu_vector_set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats: the estimates of NIDX_METHOD_RABITQ_BRUTE_FORCE as an int8 GEMM on the matrix cores */
 #define NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS (1u << 20) /* = 1048576; nidx_gpu_vector_set_tunable "rabitq_scan_groups" = 1: that stage for per-query filter rows and multi-vector segments, as grouped GEMMs and a grouped re-rank */
+#define NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES (1u << 21) /* = 2097152; nidx_gpu_vector_set_tunable "pq_scan_multi_pages" = 1: pages of 65 .. 512 hits from the packed matrix-core scan on multi-vector segments */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -183,6 +184,9 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * "pq_scan_pages" (read only while "pq_scan_stage" is 1): 0 (default) = that arm keeps at most 64 hits per query and refuses larger
  * pages; 1 = pages of 65 .. 512 hits on single-vector segments are served by a second kernel with the same score bits (a multi-vector
  * segment still refuses them); any other value is NIDX_ERR_INVALID_ARGUMENT.  k <= 64 is unaffected.
+ * "pq_scan_multi_pages" (present with NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES; read only while "pq_scan_stage" and "pq_scan_pages" are
+ * both 1): 0 (default) = a multi-vector segment refuses pages of more than 64 hits; 1 = it serves pages of 65 .. 512 PARAGRAPHS, each by
+ * its best (on a bit-equal score its last) vector, with the same score bits; any other value is NIDX_ERR_INVALID_ARGUMENT.
  * "rabitq_scan_stage" (present with NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA) changes NO bit: 0 (default) = NIDX_METHOD_RABITQ_BRUTE_FORCE
  * scores every passing row with one wave per query; 1 = the passing rows are packed into one ascending list, the estimates of the whole
  * batch are one int8 GEMM on the matrix cores (an estimate is an integer dot product: no summation order), and a wave per query replays
@@ -444,7 +448,9 @@ int32_t nidx_gpu_vector_search_filtered(nidx_gpu_vector_index_t *index, const fl
  *     NIDX_ORDER_SERIAL_FMA, as by NIDX_METHOD_BRUTE_FORCE_MFMA, so score bits differ from stage 0 in the last places and the
  *     stage is never chosen silently; a query's bits do not depend on what else is in the batch.  Multi-vector segments keep k
  *     PARAGRAPHS per query on chip, so k x (vectors of the largest paragraph) is no limit.  A page of k > 64 that reaches the arm is
- *     NIDX_ERR_UNSUPPORTED (the message names the tunables) unless "pq_scan_pages" is 1 and the arm's segments are single-vector:
+ *     NIDX_ERR_UNSUPPORTED (the message names the tunables) unless "pq_scan_pages" is 1 and the arm's segments are single-vector, or
+ *     "pq_scan_multi_pages" is 1 as well (NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES; the page then lists up to 512 paragraphs of a
+ *     multi-vector segment, and the first pass of a maxsim entry may ask for more than 64 hits per query vector):
  *     then a query's page of up to 512 hits is kept in the merge scratch and fed from a 64-key buffer on chip (same bits, same
  *     launches; a batch whose scratch would pass the 1 GiB cap is searched in chunks of queries).  The HNSW and RaBitQ arms are unchanged; the routed and prefiltered
  *     tickets are answered by this blocking path while the stage is 1, with the same bits.  Still one search plus one

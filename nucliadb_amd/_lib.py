@@ -174,6 +174,7 @@ FILTER_PUSH_PREFILTER = 8   # NIDX_FILTER_PUSH_PREFILTER: valid in the programs 
 FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched maxsim entries (per-query filters, tickets, device second stage)
 FEATURE_VECTOR_MAXSIM_MFMA = 65536   # nidx_gpu_build_features() bit: set_tunable "maxsim_stage" = 1, the maxsim second stage on the f32 matrix cores (SERIAL_FMA order)
 FEATURE_VECTOR_PQ_SCAN_MFMA = 131072   # nidx_gpu_build_features() bit: set_tunable "pq_scan_stage" = 1, the per-query-filter brute-force arm as packed GEMMs on the f32 matrix cores (SERIAL_FMA order)
+FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES = 2097152   # nidx_gpu_build_features() bit: set_tunable "pq_scan_multi_pages" = 1 (pages of 65 .. 512 hits from the packed matrix-core scan on multi-vector segments)
 FEATURE_VECTOR_RABITQ_SCAN_GROUPS = 1048576   # nidx_gpu_build_features() bit: set_tunable "rabitq_scan_groups" = 1 (that stage for per-query filter rows and multi-vector segments: grouped GEMMs, grouped re-rank; the same bits)
 FEATURE_VECTOR_RABITQ_SCAN_MFMA = 524288  # nidx_gpu_build_features() bit: set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats (the RaBitQ brute-force arm's estimates as an int8 GEMM on the matrix cores; the same bits)
 FEATURE_BM25_DENSE_PROBE = 262144   # nidx_gpu_build_features() bit: nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats (dense BM25 clauses as bitmap probes)

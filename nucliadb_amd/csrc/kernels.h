@@ -155,7 +155,8 @@ struct PqMfmaArgs {
 // multi: the segment has paragraphs of more than one vector — lists of at most k distinct paragraphs, stripes cut at paragraph boundaries
 hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s);
 // the same launch for pages of NIDX_MFMA_KMAX < k <= NIDX_K_MAX hits (pq_mfma_wide_kernel): a query's page lives in its row of `partial`, LDS
-// holds a 64-key append buffer per query.  Single-vector segments only: hipErrorInvalidValue for multi, k <= NIDX_MFMA_KMAX, k > NIDX_K_MAX
+// holds a 64-key append buffer per query.  multi as above (needs para_of_vec): a page of k paragraphs, each reduced to its representative
+// before it is appended.  hipErrorInvalidValue for k <= NIDX_MFMA_KMAX, k > NIDX_K_MAX, multi without para_of_vec
 hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s);
 
 // ---- bf16-MFMA brute-force fallback with exact re-scoring (vector_bf16.hip) ----

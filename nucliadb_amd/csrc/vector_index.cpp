@@ -1320,11 +1320,11 @@ int32_t VectorIndex::segment_rabitq_groups(const VectorSegment &seg, const Rabit
 }
 
 namespace {
-// "pq_scan_pages" = 1 on a multi-vector segment: refused, and why
+// "pq_scan_pages" = 1 on a multi-vector segment without "pq_scan_multi_pages" = 1: refused, and what to do
 int32_t fail_pq_wide_multi(size_t s, uint32_t k) {
     return fail(NIDX_ERR_UNSUPPORTED,
-                "\"pq_scan_pages\" = 1 serves single-vector segments only: a page of segment %zu lists paragraphs, and the same-paragraph rule needs the "
-                "whole list at hand on every admission (got k=%u; ask for k <= %d, or set \"pq_scan_stage\" = 0)", s, k, NIDX_MFMA_KMAX);
+                "\"pq_scan_pages\" = 1 alone serves single-vector segments only, and a page of segment %zu lists paragraphs (got k=%u): set "
+                "\"pq_scan_multi_pages\" = 1 as well, ask for k <= %d, or set \"pq_scan_stage\" = 0", s, k, NIDX_MFMA_KMAX);
 }
 }  // namespace
 // The queries of one chunk under "pq_scan_pages" = 1.  The partial region holds [n][max_stripes][k] keys, and the planner gives a block at
@@ -1348,7 +1348,7 @@ int32_t VectorIndex::segment_pq_mfma(uint32_t s, const float *d_queries, uint32_
     if (wide && pq_scan_pages != 1)
         return fail(NIDX_ERR_UNSUPPORTED, "\"pq_scan_stage\" = 1 keeps at most %d hits per query (got k=%u): set \"pq_scan_pages\" = 1 for pages of up to %d",
                     NIDX_MFMA_KMAX, k, NIDX_K_MAX);
-    if (wide && seg.vmax > 1) return fail_pq_wide_multi(s, k);
+    if (wide && seg.vmax > 1 && pq_scan_multi_pages != 1) return fail_pq_wide_multi(s, k);
     if (P.n_unplaced || P.blocks.empty()) return fail(NIDX_ERR_INTERNAL, "the packed scan of segment %u has queries without a list", s);
     if (P.total_words > 0xffffffffull) return fail(NIDX_ERR_OUT_OF_MEMORY, "the packed lists of segment %u outgrow one scratch region", s);
     const int32_t rc_norms = ensure_norm2_serial(seg, st);
@@ -2124,14 +2124,14 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
     }
     if (out_method) std::copy(method.begin(), method.end(), out_method);
     const bool packed = pq_scan_stage == 1;   // the brute-force arm as packed GEMMs on the matrix cores (vector_mfma_pq.hip)
-    if (packed && k > NIDX_MFMA_KMAX) {   // before anything is launched: pages of more than 64 hits need "pq_scan_pages" = 1 and single-vector segments
+    if (packed && k > NIDX_MFMA_KMAX) {   // before anything is launched: pages of more than 64 hits need "pq_scan_pages" = 1, and on multi-vector segments "pq_scan_multi_pages" = 1
         for (size_t i = 0; i < method.size(); i++) {
             if (method[i] != NIDX_METHOD_BRUTE_FORCE) continue;
             if (pq_scan_pages != 1)
                 return fail(NIDX_ERR_UNSUPPORTED,
                             "\"pq_scan_stage\" = 1 keeps at most %d hits per query in the brute-force arm (got k=%u): set \"pq_scan_pages\" = 1 for pages of up "
                             "to %d hits on single-vector segments", NIDX_MFMA_KMAX, k, NIDX_K_MAX);
-            if (segs[i % S].vmax > 1) return fail_pq_wide_multi(i % S, k);
+            if (segs[i % S].vmax > 1 && pq_scan_multi_pages != 1) return fail_pq_wide_multi(i % S, k);
         }
     }
     PqMfmaPlan pq_plan;
@@ -2388,7 +2388,7 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
            NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA |
            NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE | NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA |
-           NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS;
+           NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS | NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2513,6 +2513,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
     else if (n == "pq_scan_pages") {   // under "pq_scan_stage" = 1: 0 = at most 64 hits per query (default), 1 = pages of up to NIDX_K_MAX hits on single-vector segments (pq_mfma_wide_kernel)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_pages must be 0 or 1");
         idx->pq_scan_pages = (int)value;
+    }
+    else if (n == "pq_scan_multi_pages") {   // under "pq_scan_stage" = 1 and "pq_scan_pages" = 1: 0 = multi-vector segments refuse pages of more than 64 hits (default), 1 = they are served too (pq_mfma_wide_kernel<true>)
+        if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_multi_pages must be 0 or 1");
+        idx->pq_scan_multi_pages = (int)value;
     }
     else if (n == "rabitq_scan_stage") {   // NIDX_METHOD_RABITQ_BRUTE_FORCE: 0 = one wave per query (default), 1 = the estimates as an int8 GEMM on the matrix cores (the same bits)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_stage must be 0 or 1");

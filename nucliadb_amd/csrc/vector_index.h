@@ -211,6 +211,9 @@ struct VectorIndex {
     // tunable "pq_scan_pages" = 1 (with pq_scan_stage = 1): pages of NIDX_MFMA_KMAX < k <= NIDX_K_MAX hits on single-vector segments by
     // pq_mfma_wide_kernel; search_per_query cuts its chunks so that the [queries][stripes][k] partial region stays under pq_scratch_cap
     int pq_scan_pages = 0;
+    // tunable "pq_scan_multi_pages" = 1 (with both of the above = 1): such pages on multi-vector segments too, k paragraphs each, by
+    // pq_mfma_wide_kernel<true>; at 0 a multi-vector segment refuses them (fail_pq_wide_multi)
+    int pq_scan_multi_pages = 0;
     static uint32_t pq_wide_chunk_queries(uint32_t n, uint32_t k, uint64_t cap);
     const PqMfmaPlan *pq_mfma = nullptr;
     const uint64_t *pq_mfma_table = nullptr;   // the segment's rows of the chunk's filter table

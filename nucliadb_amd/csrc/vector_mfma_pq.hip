@@ -23,8 +23,11 @@
 //          k-th), and the same-paragraph rule decides; only a survivor of an unlisted paragraph has to beat the k-th key.  Paragraphs own
 //          disjoint address ranges, so the order among paragraphs does not depend on which of their vectors is listed.  Stripes start
 //          at paragraph boundaries, so no paragraph is in two stripes and the merge needs no reduction after it.
-//   pages of 65 .. 512 hits (pq_mfma_wide_kernel; tunable "pq_scan_pages" = 1, single-vector segments): the same plan, packing and GEMM;
-//          the page lives in the query's row of the partial region and LDS holds a 64-key append buffer per query — see the kernel.
+//   pages of 65 .. 512 hits (pq_mfma_wide_kernel; tunable "pq_scan_pages" = 1): the same plan, packing and GEMM; the page lives in the
+//          query's row of the partial region and LDS holds a 64-key append buffer per query — see the kernel.  Multi-vector segments
+//          (pq_mfma_wide_kernel<true>; tunable "pq_scan_multi_pages" = 1 as well): a paragraph's vectors are neighbours in the list, so
+//          the epilogue reduces every paragraph to its representative BEFORE the page sees it — a segmented scan over the 32 entries
+//          of a step, one open paragraph per query carried across steps and tiles — and the page needs no same-paragraph rule.
 //
 // Bounds: GEMM 2 * (queries in blocks) * (list length) * dp flop at 157.3 Tflop/s; a block reads its list's rows once per stripe walk.
 #include "device_common.h"
@@ -385,7 +388,7 @@ hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// the packed GEMM with result pages of 65 .. NIDX_K_MAX hits (tunable "pq_scan_pages" = 1; single-vector segments)
+// the packed GEMM with result pages of 65 .. NIDX_K_MAX hits (tunable "pq_scan_pages" = 1; multi-vector segments: "pq_scan_multi_pages" = 1)
 // ---------------------------------------------------------------------------------------------------------------------------------
 // A page of 512 keys for each of 128 queries is 512 KiB, so a query's page lives where merge_topk_kernel will read it: its row
 // partial[(query * lists_per_query + stripe) * k .. + k) of the partial region, sorted best first, in blocks of 64 keys of which lane l of
@@ -411,6 +414,14 @@ struct PqWideShared {
     uint32_t q_id[PQ_BM];
     uint32_t row_id[PQ_BN];
 };
+// MULTI: + 2 KiB.  The open paragraph of a query is the last run of entries its wave has seen: it may go on in the next step or tile.
+struct PqWideMultiShared : PqWideShared {
+    uint32_t row_para[PQ_BN];            // the tile's paragraphs (PQ_NO_ID past the end of the stripe)
+    volatile uint64_t open_key[PQ_BM];   // the open paragraph's best passing vector so far (EMPTY: none), owned by the query's wave
+    volatile uint32_t open_para[PQ_BM];  // its id (PQ_NO_ID: none yet)
+};
+template <bool MULTI> struct PqWideSharedOf { typedef PqWideShared type; };
+template <> struct PqWideSharedOf<true> { typedef PqWideMultiShared type; };
 
 // The prologue and the mainloop are pq_mfma_kernel's, as functions (that kernel keeps its own text: calling these changed the register
 // allocation of its KMAX = 64 instantiations).
@@ -419,6 +430,7 @@ struct PqStripe {
     const uint32_t *entries;
     uint32_t q_at, n_q, begin, end;
 };
+template <bool MULTI>
 __device__ __forceinline__ PqStripe pq_stripe(const PqMfmaArgs &a) {
     const uint32_t *blk = a.region + a.at_blocks + 6u * blockIdx.y;
     const uint32_t list = blk[0], q_at = blk[1], n_q = blk[2], stripes = blk[3], stripe_len = blk[4];
@@ -436,6 +448,10 @@ __device__ __forceinline__ PqStripe pq_stripe(const PqMfmaArgs &a) {
         const uint64_t b = (uint64_t)blockIdx.x * stripe_len, e = b + stripe_len;
         begin = b < len ? (uint32_t)b : len;
         end = (blockIdx.x + 1 == stripes || e >= len) ? len : (uint32_t)e;
+        if (MULTI) {   // no paragraph in two stripes
+            begin = pq_para_boundary(entries, a.para_of_vec, a.n, begin, len);
+            end = pq_para_boundary(entries, a.para_of_vec, a.n, end, len);
+        }
     }
     return PqStripe{entries, q_at, n_q, begin, end};
 }
@@ -527,14 +543,98 @@ __device__ inline void pq_wide_flush(PqWideShared &sh, const PqMfmaArgs &a, int 
     }
 }
 
+// ---- multi-vector segments (pq_mfma_wide_kernel<true>) ----
+// A page lists PARAGRAPHS, each by its best vector and, on a bit-equal score, by the LAST such vector (Iterator::max_by).  pq_fill_kernel
+// writes the vectors of a paragraph next to each other and stripes are cut at paragraph boundaries, so a paragraph is one RUN of
+// entries of one stripe, and the epilogue reduces each run to its representative before anything reaches the append buffer: per
+// (query, step) a segmented inclusive scan over the 32 lanes of a half leaves a run's representative in its last lane; the last run of
+// a step stays OPEN (open_key / open_para, it may go on in the next step or tile) and every other run is closed and appended.  The
+// page is then the top k of distinct paragraph representatives, a totally ordered set, and the append buffer, the flush chain and
+// merge_topk_kernel serve it as they serve vectors.  The result does not depend on timing (when the flushes happen, how stale a floor is):
+//   - a stale floor only admits more;
+//   - a vector that fails the floor cannot be the representative of a paragraph that belongs on the page;
+//   - no other paragraph's key lies between two vectors of one paragraph, because paragraphs own disjoint address ranges, so the floor
+//     test treats a paragraph's equal-score vectors alike: the representative is the same whichever floor its vectors met;
+//   - each paragraph is appended at most once, so whenever the flushes happen the page is the top k of distinct representatives.
+
+// max_by over two candidates of one paragraph, `later` at the higher address: the higher score word wins, the later vector on a
+// bit-equal one (its rank key is the LOWER of the two); EMPTY loses to everything
+__device__ __forceinline__ uint64_t pq_para_best(uint64_t earlier, uint64_t later) {
+    const bool take_later = later != NIDX_EMPTY_KEY && (earlier == NIDX_EMPTY_KEY || (uint32_t)(later >> 32) >= (uint32_t)(earlier >> 32));
+    return take_later ? later : earlier;
+}
+
+// The epilogue of step `t` (the wave's 32 queries x the entries 32t .. 32t + 31; acc = acc[t]).  In register r the 32 lanes of a half
+// hold ONE query against the 32 entries, so the scan runs in both halves at once, on runs that are the same for every r.
+// A step appends at most 32 keys to a query's buffer — the entries form at most 32 runs of which the last stays open: an open paragraph
+// that goes on in the first run is part of it (at most 31 closed runs), one that does not is one append plus at most 31 closed runs —
+// so "flush above 32" leaves room as in the single-vector form.  Closing is lazy: a (query, step) in which no lane passes is skipped,
+// since the open paragraph keeps its id, only ever combines with the same id, and only has to reach the page before the stripe ends.
+__device__ __forceinline__ void pq_wide_multi_step(PqWideMultiShared &sh, const PqMfmaArgs &a, const floatx16 &acc, int t, int wave, int li,
+                                                   int half, bool cosine) {
+    const int j = 32 * t + li;
+    const uint32_t row = sh.row_id[j], para = sh.row_para[j], first_para = sh.row_para[32 * t];
+    const bool row_ok = row != PQ_NO_ID;
+    const float rinv = sh.row_rinv[j];
+    uint32_t take = 0;   // bit s: the entry 2^s to the left is of this lane's paragraph, so every entry between is too
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) {
+        const uint32_t left = __shfl_up(para, o, 32);
+        if (li >= o && left == para) take |= (uint32_t)o;
+    }
+    const uint32_t right = __shfl_down(para, 1, 32);
+    const bool tail = li == 31 || right != para;   // the last lane of a run: it ends up with the run's representative
+    const bool in_first = para == first_para;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int qi = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;   // one query per half
+        const float ab = acc[r];
+        // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
+        const float approx = cosine ? ab * rinv * sh.q_rinv[qi] + 1e-5f : ab;
+        const bool pre = row_ok && !(approx < sh.thr_score[qi]);
+        if (!__ballot(pre)) continue;
+        float score = ab;
+        if (pre && cosine) score = cosine_from_sums(ab, sh.row_xx[j], sh.q_qq[qi]);
+        const uint64_t key = rank_key(score, row);
+        const uint64_t thr = sh.thr_key[qi];
+        const bool pass = pre && (score >= a.min_score) && key > thr;
+        const unsigned long long m = __ballot(pass);
+        if (!m) continue;
+        const bool active = (half ? (uint32_t)(m >> 32) : (uint32_t)m) != 0;   // (the other half's query may have nothing: it changes nothing)
+        uint64_t c = pass ? key : NIDX_EMPTY_KEY;
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {   // segmented inclusive scan: lane li holds the best of its run's entries up to li
+            const uint64_t left = __shfl_up((unsigned long long)c, o, 32);
+            if (take & (uint32_t)o) c = pq_para_best(left, c);
+        }
+        const uint64_t okey = sh.open_key[qi];
+        const bool merge = sh.open_para[qi] == first_para;   // the open paragraph goes on in this step's first run
+        if (merge && in_first && tail) c = pq_para_best(okey, c);
+        // closed: every run but the last, and the open paragraph if it ended before this step (the floor may have risen since it passed)
+        const bool closed = active && tail && li != 31 && c != NIDX_EMPTY_KEY && c > thr;
+        const unsigned long long cm = __ballot(closed);
+        const uint32_t mine = half ? (uint32_t)(cm >> 32) : (uint32_t)cm;
+        const uint32_t old = (!merge && okey != NIDX_EMPTY_KEY && okey > thr) ? 1u : 0u;
+        const uint32_t at = sh.cnt[qi];
+        if (closed) sh.buf[qi][at + old + (uint32_t)__popc(mine & ((1u << li) - 1u))] = c;
+        if (active && li == 31) {   // (never a closed lane) the count, and the last run as the open paragraph
+            if (old) sh.buf[qi][at] = okey;
+            sh.cnt[qi] = at + old + (uint32_t)__popc(mine);
+            sh.open_key[qi] = c;
+            sh.open_para[qi] = para;
+        }
+    }
+}
+
+template <bool MULTI>
 __global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
-    __shared__ PqWideShared sh;
+    __shared__ typename PqWideSharedOf<MULTI>::type sh;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, half = lane >> 5;
     const bool cosine = a.similarity == 1;
     const uint32_t k = a.k;
     const uint32_t nk = (a.dp + PQ_BK - 1) / PQ_BK;
-    const PqStripe sp = pq_stripe(a);
+    const PqStripe sp = pq_stripe<MULTI>(a);
     const uint32_t *entries = sp.entries;
     const uint32_t begin = sp.begin, end = sp.end;
 
@@ -549,6 +649,10 @@ __global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
         sh.thr_score[tid] = qi != PQ_NO_ID ? -INFINITY : INFINITY;
         sh.cnt[tid] = 0;
         sh.live[tid] = 0;
+        if constexpr (MULTI) {
+            sh.open_key[tid] = NIDX_EMPTY_KEY;
+            sh.open_para[tid] = PQ_NO_ID;
+        }
     }
     __syncthreads();
     const uint32_t qr[2] = {sh.q_id[tid >> 2], sh.q_id[(tid >> 2) + 64]};
@@ -563,6 +667,7 @@ __global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
             sh.row_id[tid] = id;
             sh.row_xx[tid] = xx;
             sh.row_rinv[tid] = 1.0f / sqrtf(xx);
+            if constexpr (MULTI) sh.row_para[tid] = id != PQ_NO_ID ? a.para_of_vec[id] : PQ_NO_ID;
         }
         __syncthreads();
         const uint32_t xr[2] = {sh.row_id[tid >> 2], sh.row_id[(tid >> 2) + 64]};
@@ -570,36 +675,50 @@ __global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
         pq_tile_gemm(sh, a, qr, xr, nk, tid, acc);
 
         // ---- epilogue: the survivors of the 32 x 128 scores of this wave go to its queries' append buffers ----
-#pragma unroll
+#pragma clang loop unroll(full)   // (acc[t] must stay in registers: the MULTI body is past what a plain `unroll` takes whole)
         for (int t = 0; t < 4; t++) {
             pq_wide_flush(sh, a, wave, lane, 32u);   // every buffer has room for the 32 survivors a step can bring
-            const int j = 32 * t + li;
-            const uint32_t row = sh.row_id[j];
-            const bool row_ok = row != PQ_NO_ID;
-            const float rinv = sh.row_rinv[j];
+            if constexpr (MULTI) {
+                pq_wide_multi_step(sh, a, acc[t], t, wave, li, half, cosine);
+            } else {
+                const int j = 32 * t + li;
+                const uint32_t row = sh.row_id[j];
+                const bool row_ok = row != PQ_NO_ID;
+                const float rinv = sh.row_rinv[j];
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int qi = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;   // one query per half
-                const float ab = acc[t][r];
-                // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
-                const float approx = cosine ? ab * rinv * sh.q_rinv[qi] + 1e-5f : ab;
-                const bool pre = row_ok && !(approx < sh.thr_score[qi]);
-                if (!__ballot(pre)) continue;
-                float score = ab;
-                if (pre && cosine) score = cosine_from_sums(ab, sh.row_xx[j], sh.q_qq[qi]);
-                const uint64_t key = rank_key(score, row);
-                const bool pass = pre && (score >= a.min_score) && key > sh.thr_key[qi];
-                const unsigned long long m = __ballot(pass);
-                if (!m) continue;
-                const uint32_t mine = half ? (uint32_t)(m >> 32) : (uint32_t)m;   // the passing lanes of this lane's query
-                const uint32_t at = sh.cnt[qi];
-                if (pass) sh.buf[qi][at + (uint32_t)__popc(mine & ((1u << li) - 1u))] = key;
-                if (li == 0 && mine) sh.cnt[qi] = at + (uint32_t)__popc(mine);
+                for (int r = 0; r < 16; r++) {
+                    const int qi = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;   // one query per half
+                    const float ab = acc[t][r];
+                    // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
+                    const float approx = cosine ? ab * rinv * sh.q_rinv[qi] + 1e-5f : ab;
+                    const bool pre = row_ok && !(approx < sh.thr_score[qi]);
+                    if (!__ballot(pre)) continue;
+                    float score = ab;
+                    if (pre && cosine) score = cosine_from_sums(ab, sh.row_xx[j], sh.q_qq[qi]);
+                    const uint64_t key = rank_key(score, row);
+                    const bool pass = pre && (score >= a.min_score) && key > sh.thr_key[qi];
+                    const unsigned long long m = __ballot(pass);
+                    if (!m) continue;
+                    const uint32_t mine = half ? (uint32_t)(m >> 32) : (uint32_t)m;   // the passing lanes of this lane's query
+                    const uint32_t at = sh.cnt[qi];
+                    if (pass) sh.buf[qi][at + (uint32_t)__popc(mine & ((1u << li) - 1u))] = key;
+                    if (li == 0 && mine) sh.cnt[qi] = at + (uint32_t)__popc(mine);
+                }
             }
         }
     }
     // ---- what is still buffered, then EMPTY behind every page: merge_topk_kernel reads all k entries of a row (a workgroup without
     //      entries, or of a stripe past its block's own, leaves empty rows) ----
+    if constexpr (MULTI) {   // the stripe ends at a paragraph boundary: every open paragraph is complete, and the last of its query
+        pq_wide_flush(sh, a, wave, lane, 32u);
+        const int q = 32 * wave + li;
+        const uint64_t okey = sh.open_key[q];
+        if (half == 0 && okey != NIDX_EMPTY_KEY && okey > sh.thr_key[q]) {
+            const uint32_t at = sh.cnt[q];
+            sh.buf[q][at] = okey;
+            sh.cnt[q] = at + 1u;
+        }
+    }
     pq_wide_flush(sh, a, wave, lane, 0u);
     for (int ql = 0; ql < 32; ql++) {
         const uint32_t qi = sh.q_id[32 * wave + ql];
@@ -610,13 +729,14 @@ __global__ __launch_bounds__(256, 1) void pq_mfma_wide_kernel(PqMfmaArgs a) {
 }
 
 hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s) {
-    if (a.k <= NIDX_MFMA_KMAX || a.k > NIDX_K_MAX || multi) return hipErrorInvalidValue;
+    if (a.k <= NIDX_MFMA_KMAX || a.k > NIDX_K_MAX || (multi && !a.para_of_vec)) return hipErrorInvalidValue;
     if (a.n_blocks == 0 || a.lists_per_query == 0) return hipSuccess;
     for (uint32_t b0 = 0; b0 < a.n_blocks; b0 += 65535u) {   // (the blocks in slices, as launch_pq_mfma)
         PqMfmaArgs part = a;
         part.at_blocks = a.at_blocks + 6u * b0;
         part.n_blocks = a.n_blocks - b0 < 65535u ? a.n_blocks - b0 : 65535u;
-        hipLaunchKernelGGL(pq_mfma_wide_kernel, dim3(a.lists_per_query, part.n_blocks), dim3(256), 0, s, part);
+        if (multi) hipLaunchKernelGGL(pq_mfma_wide_kernel<true>, dim3(a.lists_per_query, part.n_blocks), dim3(256), 0, s, part);
+        else hipLaunchKernelGGL(pq_mfma_wide_kernel<false>, dim3(a.lists_per_query, part.n_blocks), dim3(256), 0, s, part);
     }
     return hipGetLastError();
 }

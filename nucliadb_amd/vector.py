@@ -943,13 +943,15 @@ class VectorSearcher:
         """nidx_gpu_vector_set_tunable.  Two tunables change score BITS (NIDX_ORDER_SERIAL_FMA instead of WAVE64) and are therefore never
         on by default: "maxsim_stage" = 1 (FEATURE_VECTOR_MAXSIM_MFMA) and "pq_scan_stage" = 1 (FEATURE_VECTOR_PQ_SCAN_MFMA: the
         brute-force arm of every per-query-filter search as packed GEMMs on the f32 matrix cores, meant for batches whose queries share
-        filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well).
+        filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well, and on multi-vector
+        segments with "pq_scan_multi_pages" = 1 on top of that, FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES).
         "rabitq_scan_stage" = 1 and "rabitq_scan_scratch_kib" (FEATURE_VECTOR_RABITQ_SCAN_MFMA) change NO bit: the estimates of
         METHOD_RABITQ_BRUTE_FORCE come from an int8 GEMM on the matrix cores instead of one wave per query (single-vector segments, one
         filter per batch; anything else keeps the old kernel, see rabitq_scan_stats), and the second caps that stage's scratch in KiB
         (0 = 1 GiB), cutting a batch into chunks of queries.  "rabitq_scan_groups" = 1 (FEATURE_VECTOR_RABITQ_SCAN_GROUPS, read while
         "rabitq_scan_stage" is 1) extends the stage to per-query filter rows (search_many) and multi-vector segments: the same bits."""
         need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA,
+                "pq_scan_multi_pages": _lib.FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES,
                 "rabitq_scan_stage": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA,
                 "rabitq_scan_groups": _lib.FEATURE_VECTOR_RABITQ_SCAN_GROUPS,
                 "rabitq_scan_scratch_kib": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA}.get(name, 0)
