@@ -76,6 +76,7 @@ int32_t nidx_gpu_abi_version(void);
 #define NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA (1u << 19) /* = 524288; nidx_gpu_vector_set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats: the estimates of NIDX_METHOD_RABITQ_BRUTE_FORCE as an int8 GEMM on the matrix cores */
 #define NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS (1u << 20) /* = 1048576; nidx_gpu_vector_set_tunable "rabitq_scan_groups" = 1: that stage for per-query filter rows and multi-vector segments, as grouped GEMMs and a grouped re-rank */
 #define NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES (1u << 21) /* = 2097152; nidx_gpu_vector_set_tunable "pq_scan_multi_pages" = 1: pages of 65 .. 512 hits from the packed matrix-core scan on multi-vector segments */
+#define NIDX_FEATURE_VECTOR_PQ_SCAN_THIN (1u << 22) /* = 4194304; nidx_gpu_vector_set_tunable "pq_scan_thin" = T, nidx_gpu_vector_pq_scan_stats: blocks of at most T queries of the packed matrix-core scan on a list-gather kernel */
 int32_t nidx_gpu_build_features(void);
 /* nidx_gpu_bm25_search_submit: tickets that may be outstanding per index before it returns NIDX_ERR_BUSY */
 #define NIDX_GPU_BM25_MAX_TICKETS 16
@@ -187,6 +188,12 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * "pq_scan_multi_pages" (present with NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES; read only while "pq_scan_stage" and "pq_scan_pages" are
  * both 1): 0 (default) = a multi-vector segment refuses pages of more than 64 hits; 1 = it serves pages of 65 .. 512 PARAGRAPHS, each by
  * its best (on a bit-equal score its last) vector, with the same score bits; any other value is NIDX_ERR_INVALID_ARGUMENT.
+ * "pq_scan_thin" (present with NIDX_FEATURE_VECTOR_PQ_SCAN_THIN; read only while "pq_scan_stage" is 1) changes NO bit relative to
+ * "pq_scan_stage" = 1: 0 (default) = every group of queries that share a filter runs 128-query GEMM tiles, however few its queries;
+ * T in 1 .. 16 = a block of at most T queries (a query with a filter of its own, the remainder of a group) is scored by a list-gather
+ * kernel without matrix instructions, one wave per stripe of the block's list, in the same k-ordered fmaf chains.  Single-vector
+ * segments and k <= 64 only; a multi-vector segment and larger pages keep the GEMM kernels, silently.  Any other value is
+ * NIDX_ERR_INVALID_ARGUMENT.  nidx_gpu_vector_pq_scan_stats counts the queries either kernel answered.
  * "rabitq_scan_stage" (present with NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA) changes NO bit: 0 (default) = NIDX_METHOD_RABITQ_BRUTE_FORCE
  * scores every passing row with one wave per query; 1 = the passing rows are packed into one ascending list, the estimates of the whole
  * batch are one int8 GEMM on the matrix cores (an estimate is an integer dot product: no summation order), and a wave per query replays
@@ -203,6 +210,9 @@ int32_t nidx_gpu_vector_segment_records(const nidx_gpu_vector_index_t *index, ui
  * rounded up to 128); a batch that needs more is searched in consecutive chunks of queries.  0 = the default, 1 GiB; negative values are
  * NIDX_ERR_INVALID_ARGUMENT. */
 int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *name, int32_t value);
+/* Since open: queries whose brute-force arm was answered by "pq_scan_stage" = 1 (each once, on however many segments), and, of those, the
+ * queries answered by the list-gather kernel of "pq_scan_thin".  Either pointer may be NULL. */
+int32_t nidx_gpu_vector_pq_scan_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *thin_queries_out);
 /* Since open: queries of NIDX_METHOD_RABITQ_BRUTE_FORCE answered by "rabitq_scan_stage" = 1, and queries that reached the arm while the
  * stage was 1 but were handed to the one-wave-per-query kernel (multi-vector segment, per-query filter rows).  Either pointer may be
  * NULL. */

@@ -175,6 +175,7 @@ FEATURE_VECTOR_MAXSIM_BATCH = 4   # nidx_gpu_build_features() bit: the batched m
 FEATURE_VECTOR_MAXSIM_MFMA = 65536   # nidx_gpu_build_features() bit: set_tunable "maxsim_stage" = 1, the maxsim second stage on the f32 matrix cores (SERIAL_FMA order)
 FEATURE_VECTOR_PQ_SCAN_MFMA = 131072   # nidx_gpu_build_features() bit: set_tunable "pq_scan_stage" = 1, the per-query-filter brute-force arm as packed GEMMs on the f32 matrix cores (SERIAL_FMA order)
 FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES = 2097152   # nidx_gpu_build_features() bit: set_tunable "pq_scan_multi_pages" = 1 (pages of 65 .. 512 hits from the packed matrix-core scan on multi-vector segments)
+FEATURE_VECTOR_PQ_SCAN_THIN = 4194304   # nidx_gpu_build_features() bit: set_tunable "pq_scan_thin" = T, nidx_gpu_vector_pq_scan_stats (blocks of at most T queries of the packed matrix-core scan on a list-gather kernel; the same bits)
 FEATURE_VECTOR_RABITQ_SCAN_GROUPS = 1048576   # nidx_gpu_build_features() bit: set_tunable "rabitq_scan_groups" = 1 (that stage for per-query filter rows and multi-vector segments: grouped GEMMs, grouped re-rank; the same bits)
 FEATURE_VECTOR_RABITQ_SCAN_MFMA = 524288  # nidx_gpu_build_features() bit: set_tunable "rabitq_scan_stage" = 1, nidx_gpu_vector_rabitq_scan_stats (the RaBitQ brute-force arm's estimates as an int8 GEMM on the matrix cores; the same bits)
 FEATURE_BM25_DENSE_PROBE = 262144   # nidx_gpu_build_features() bit: nidx_gpu_bm25_set_tunable "dense_probe", nidx_gpu_bm25_dense_probe_stats (dense BM25 clauses as bitmap probes)
@@ -546,6 +547,7 @@ SIGNATURES = {
                                                                             C.c_void_p, C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_search_maxsim_wait": (C.c_int32, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nidx_gpu_vector_maxsim_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "nidx_gpu_vector_pq_scan_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_rabitq_scan_stats": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "nidx_gpu_vector_quantize": (C.c_int32, [C.c_void_p, C.c_uint32]),
     "nidx_gpu_vector_serialize_quantized": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -158,6 +158,10 @@ hipError_t launch_pq_mfma(const PqMfmaArgs &a, bool multi, hipStream_t s);
 // holds a 64-key append buffer per query.  multi as above (needs para_of_vec): a page of k paragraphs, each reduced to its representative
 // before it is appended.  hipErrorInvalidValue for k <= NIDX_MFMA_KMAX, k > NIDX_K_MAX, multi without para_of_vec
 hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s);
+// the plan's THIN blocks (at_blocks / n_blocks name their range; every one holds at most `thin` <= 16 queries) on the list-gather kernel
+// (pq_thin_kernel: one wave per block and stripe, no matrix instructions, the same score bits and the same partial lists).  Single-vector
+// segments and k <= NIDX_MFMA_KMAX only: hipErrorInvalidValue for thin = 0, thin > 16, k = 0 or k > NIDX_MFMA_KMAX
+hipError_t launch_pq_thin(const PqMfmaArgs &a, uint32_t thin, hipStream_t s);
 
 // ---- bf16-MFMA brute-force fallback with exact re-scoring (vector_bf16.hip) ----
 #define NIDX_BF16_CAND 32  /* approximate candidates kept per query before the exact re-score */

@@ -1384,9 +1384,19 @@ int32_t VectorIndex::segment_pq_mfma(uint32_t s, const float *d_queries, uint32_
     m.lists_per_query = P.max_stripes;
     m.region = scratch_pq_mfma.as<uint32_t>();
     m.at_blocks = (uint32_t)P.at_blocks, m.at_lists = (uint32_t)P.at_lists, m.at_totals = (uint32_t)P.at_totals;
-    m.n_blocks = (uint32_t)P.blocks.size();
+    m.n_blocks = P.n_wide_blocks;   // the GEMM blocks, then the thin ones (either range may be empty): both fill the one partial region
+    const uint32_t n_thin = (uint32_t)P.blocks.size() - P.n_wide_blocks;
+    if (n_thin && (wide || seg.vmax > 1 || pq_mfma_thin == 0))
+        return fail(NIDX_ERR_INTERNAL, "the packed scan of segment %u was planned with thin blocks it cannot serve", s);
+    for (size_t b = P.n_wide_blocks; b < P.blocks.size(); b++)
+        if (P.blocks[b].n_q > pq_mfma_thin) return fail(NIDX_ERR_INTERNAL, "a thin block of segment %u holds %u queries", s, P.blocks[b].n_q);
     if (wide) NIDX_HIP(launch_pq_mfma_wide(m, seg.vmax > 1, st));
     else NIDX_HIP(launch_pq_mfma(m, seg.vmax > 1, st));
+    if (n_thin) {
+        m.at_blocks = (uint32_t)P.at_blocks + 6u * P.n_wide_blocks;
+        m.n_blocks = n_thin;
+        NIDX_HIP(launch_pq_thin(m, pq_mfma_thin, st));
+    }
     NIDX_HIP(launch_merge_topk(m.partial, nq, P.max_stripes, k, d_out_vec, d_out_score, d_out_count, st));
     return NIDX_OK;
 }
@@ -2135,6 +2145,7 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
         }
     }
     PqMfmaPlan pq_plan;
+    std::vector<uint8_t> pq_answered(packed ? nq : 0, 0);
 
     // ---- per segment, each arm once over the queries routed to it (gathered rows; hits scattered back to their rows) ----
     std::vector<std::vector<uint32_t>> hv(S), hc(S);
@@ -2167,11 +2178,16 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
             NIDX_HIP(launch_gather_rows(scratch_queries.as<float>(), d_idx, n, dp, scratch_pq_queries.as<float>(), stream));
             if (packed && arm == NIDX_METHOD_BRUTE_FORCE) {   // every query of the arm, filtered or not, in groups that share a row
                 const VectorSegment &seg = segs[s];
+                // thin blocks ("pq_scan_thin"): single-vector segments and pages of at most 64 hits; everything else keeps the GEMM kernels
+                pq_mfma_thin = (seg.vmax == 1 && k <= NIDX_MFMA_KMAX) ? (uint32_t)pq_scan_thin : 0u;
                 pq_mfma_plan(idx_rows.data() + n, n, [&](uint32_t row) -> uint32_t {   // vector rows: exact, or paragraphs x vmax at most
                     return (uint32_t)std::min<uint64_t>(matching_of(row, s) * seg.vmax, seg.n); },
-                             seg.all_alive, words, kPqMfmaWorkgroups, pq_plan);
+                             seg.all_alive, words, kPqMfmaWorkgroups, pq_plan, pq_mfma_thin);
                 pq_mfma = &pq_plan;
                 pq_mfma_table = scratch_pq_table.as<uint64_t>() + (F ? tab_off[s] : 0);
+                for (size_t b = 0; b < pq_plan.blocks.size(); b++)   // nidx_gpu_vector_pq_scan_stats: bit 0 answered by the stage, bit 1 by the thin kernel
+                    for (uint32_t i = 0; i < pq_plan.blocks[b].n_q; i++)
+                        pq_answered[idx_rows[pq_plan.upload[pq_plan.blocks[b].q_at + i]]] |= b < pq_plan.n_wide_blocks ? 1 : 3;
             } else if (arm == NIDX_METHOD_RABITQ_BRUTE_FORCE && rabitq_scan_stage == 1 && rabitq_scan_groups == 1 &&
                        (filtered || !segs[s].identity_para)) {   // the same plan for the grouped int8 GEMMs (segment_rabitq_groups); an
                 const VectorSegment &seg = segs[s];              // unfiltered arm on a single-vector segment stays segment_rabitq_scan
@@ -2192,6 +2208,7 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
             pq_filter_words = 0;
             pq_mfma = nullptr;
             pq_mfma_table = nullptr;
+            pq_mfma_thin = 0;
             if (rc != NIDX_OK) return rc;
             const uint32_t *blk = pin_out.as<uint32_t>();
             for (uint32_t i = 0; i < n; i++) {
@@ -2202,6 +2219,8 @@ int32_t VectorIndex::search_per_query_chunk(const float *queries, uint32_t nq, c
             }
         }
     }
+    pq_scan_queries.fetch_add((uint64_t)std::count_if(pq_answered.begin(), pq_answered.end(), [](uint8_t f) { return f != 0; }), std::memory_order_relaxed);
+    pq_scan_thin_queries.fetch_add((uint64_t)std::count(pq_answered.begin(), pq_answered.end(), (uint8_t)3), std::memory_order_relaxed);
     std::vector<const uint32_t *> pv(S), pc(S);
     std::vector<const float *> ps(S);
     for (size_t s = 0; s < S; s++) {
@@ -2388,7 +2407,7 @@ int32_t nidx_gpu_build_features(void) {
            NIDX_FEATURE_VECTOR_PREFILTERED_TICKETS | NIDX_FEATURE_PREFILTER_RESOURCE_PARTS | NIDX_FEATURE_BM25_PREFILTERED_TICKETS |
            NIDX_FEATURE_JSON_SYNC | NIDX_FEATURE_RELATION_GRAPH_SEARCH | NIDX_FEATURE_RELATION_STRINGS | NIDX_FEATURE_VECTOR_MAXSIM_MFMA |
            NIDX_FEATURE_VECTOR_PQ_SCAN_MFMA | NIDX_FEATURE_BM25_DENSE_PROBE | NIDX_FEATURE_VECTOR_RABITQ_SCAN_MFMA |
-           NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS | NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES;
+           NIDX_FEATURE_VECTOR_RABITQ_SCAN_GROUPS | NIDX_FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES | NIDX_FEATURE_VECTOR_PQ_SCAN_THIN;
 }
 
 int32_t nidx_gpu_device_count(int32_t *count_out) try {
@@ -2518,6 +2537,10 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_multi_pages must be 0 or 1");
         idx->pq_scan_multi_pages = (int)value;
     }
+    else if (n == "pq_scan_thin") {   // under "pq_scan_stage" = 1: 0 = every block is a GEMM block (default), T in 1 .. 16 = blocks of at most T queries go to the list-gather kernel (pq_thin_kernel; single-vector segments, k <= 64; the same bits)
+        if (value < 0 || value > 16) return fail(NIDX_ERR_INVALID_ARGUMENT, "pq_scan_thin must be in 0..16");
+        idx->pq_scan_thin = (int)value;
+    }
     else if (n == "rabitq_scan_stage") {   // NIDX_METHOD_RABITQ_BRUTE_FORCE: 0 = one wave per query (default), 1 = the estimates as an int8 GEMM on the matrix cores (the same bits)
         if (value != 0 && value != 1) return fail(NIDX_ERR_INVALID_ARGUMENT, "rabitq_scan_stage must be 0 or 1");
         idx->rabitq_scan_stage = (int)value;
@@ -2531,6 +2554,14 @@ int32_t nidx_gpu_vector_set_tunable(nidx_gpu_vector_index_t *index, const char *
         idx->rabitq_scan_scratch_cap = value > 0 ? (uint64_t)value << 10 : 1ull << 30;
     }
     else return fail(NIDX_ERR_INVALID_ARGUMENT, "unknown tunable %s", name);
+    return NIDX_OK;
+} NIDX_ABI_CATCH
+
+int32_t nidx_gpu_vector_pq_scan_stats(nidx_gpu_vector_index_t *index, uint64_t *queries_out, uint64_t *thin_queries_out) try {
+    VectorIndex *idx = reinterpret_cast<VectorIndex *>(index);
+    if (!idx) return fail(NIDX_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (queries_out) *queries_out = idx->pq_scan_queries.load(std::memory_order_relaxed);
+    if (thin_queries_out) *thin_queries_out = idx->pq_scan_thin_queries.load(std::memory_order_relaxed);
     return NIDX_OK;
 } NIDX_ABI_CATCH
 

@@ -214,6 +214,11 @@ struct VectorIndex {
     // tunable "pq_scan_multi_pages" = 1 (with both of the above = 1): such pages on multi-vector segments too, k paragraphs each, by
     // pq_mfma_wide_kernel<true>; at 0 a multi-vector segment refuses them (fail_pq_wide_multi)
     int pq_scan_multi_pages = 0;
+    // tunable "pq_scan_thin" = T in 1 .. 16 (with pq_scan_stage = 1): on single-vector segments and k <= NIDX_MFMA_KMAX the plan's blocks of
+    // at most T queries go to pq_thin_kernel (pq_mfma_thin: the T of the visit in flight), the same bits; 0: every block is a GEMM block
+    int pq_scan_thin = 0;
+    uint32_t pq_mfma_thin = 0;
+    std::atomic<uint64_t> pq_scan_queries{0}, pq_scan_thin_queries{0};   // nidx_gpu_vector_pq_scan_stats
     static uint32_t pq_wide_chunk_queries(uint32_t n, uint32_t k, uint64_t cap);
     const PqMfmaPlan *pq_mfma = nullptr;
     const uint64_t *pq_mfma_table = nullptr;   // the segment's rows of the chunk's filter table

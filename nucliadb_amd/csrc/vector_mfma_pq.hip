@@ -741,4 +741,215 @@ hipError_t launch_pq_mfma_wide(const PqMfmaArgs &a, bool multi, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// thin blocks: the list-gather kernel (tunable "pq_scan_thin" = T; single-vector segments, k <= 64)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// A block of 1 .. 16 queries — a filter of its own, the remainder of a group — would run the 128-query tile almost empty.  Its work is
+// memory-shaped: the list's rows once (len * dp * 4 bytes) against n_q * len * dp FMAs.  One WAVE walks a stripe in steps of 64 entries:
+// lane l owns entry l and keeps one accumulator per query, advanced by acc = fmaf(x[k], q[k], acc) for k ascending from +0.0f — the
+// chain of the v_mfma_f32_32x32x2_f32 mainloop, so the bits are those of pq_mfma_kernel.  The rows come through LDS: per K chunk of 16
+// floats four lanes fetch the four float4 of one row (64 contiguous bytes, 16 rows per load instruction), the chunk is written at a
+// pitch of 17 floats and read back lane-per-row, conflict free; the queries' chunk lies beside it and is read by broadcast.  Two stage
+// buffers: the loads of the next chunk — the first chunk of the next step after the last of this one — are issued before the FMAs of
+// the current one and written behind them.  The row ids of step s + 1 are in LDS while step s runs, those of s + 2 in flight.
+// The epilogue is pq_mfma_kernel's single-vector one with the query uniform over the wave; the sorted lists [query][k] are in LDS.
+// LDS: 9 600 bytes static + (128 + 8 k) bytes per query of the launch's capacity (T rounded up to a power of two): 9.7 .. 19.6 KiB.
+#define PT_ROWS 64
+#define PT_BK 16
+#define PT_PITCH 17 /* floats per staged row: odd, so the 64 lanes of a lane-per-row read hit 64 distinct banks */
+#define PT_QMAX 16
+
+struct alignas(16) PqThinShared {
+    float x[2][PT_ROWS * PT_PITCH];  // [stage][entry][k]
+    uint32_t row_id[2][PT_ROWS];     // [step parity]: the step's vector rows (PQ_NO_ID past the end of the stripe)
+    // written by lane 0 and read by all lanes (a wave's LDS accesses complete in order; volatile: every read is a read — the compiler
+    // would forward lane 0's store to lane 0 alone and leave the other lanes the value from before the insert loop)
+    volatile uint64_t thr_key[PT_QMAX];   // k-th key (EMPTY while the list is short)
+    volatile float thr_score[PT_QMAX];    // its score (-inf while short; +inf: no such query)
+    float q_qq[PT_QMAX], q_rinv[PT_QMAX];
+    uint32_t q_id[PT_QMAX];          // the block's queries in the arm's compact query array (PQ_NO_ID past the end)
+};
+
+// 64 gathered rows x 16 floats: lane l loads float4 #(l % 4) of rows ids[i] (slot l / 4 + 16 i); lanes 0 .. 4 NQ - 1 that float4 of query l / 4
+template <int NQ>
+__device__ __forceinline__ void pq_thin_load(const PqMfmaArgs &a, const uint32_t (&ids)[4], uint32_t qid, uint32_t k0, int lane, float4 (&rx)[4], float4 &rq) {
+    const uint32_t k = k0 + 4u * (uint32_t)(lane & 3);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (ids[i] != PQ_NO_ID && k < a.dp) rx[i] = *reinterpret_cast<const float4 *>(a.vectors + (size_t)ids[i] * a.dp + k);
+        else rx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (lane < 4 * NQ) {
+        if (qid != PQ_NO_ID && k < a.dp) rq = *reinterpret_cast<const float4 *>(a.queries + (size_t)qid * a.dp + k);
+        else rq = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+template <int NQ>
+__device__ __forceinline__ void pq_thin_store(float *xs, float *qs, int lane, const float4 (&rx)[4], const float4 &rq) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        float *p = xs + ((lane >> 2) + 16 * i) * PT_PITCH + 4 * (lane & 3);
+        p[0] = rx[i].x, p[1] = rx[i].y, p[2] = rx[i].z, p[3] = rx[i].w;
+    }
+    if (lane < 4 * NQ) *reinterpret_cast<float4 *>(qs + 4 * lane) = rq;   // [query][16]
+}
+
+// the 64 scores of query j against the step's entries (lane l: entry l, vector row `row`) into the query's sorted list: pq_mfma_kernel's
+// single-vector epilogue with the query uniform over the wave
+__device__ __forceinline__ void pq_thin_fold(PqThinShared &sh, uint64_t *list, const PqMfmaArgs &a, int j, float ab, uint32_t row, float xx, float rinv,
+                                             bool cosine, int k, int lane) {
+    // cheap pre-test in f32 (cosine: ab/(|x||q|) within 1e-5 of the exact value)
+    const float approx = cosine ? ab * rinv * sh.q_rinv[j] + 1e-5f : ab;
+    const bool pre = row != PQ_NO_ID && !(approx < sh.thr_score[j]);
+    if (!__ballot(pre)) return;
+    float score = ab;
+    if (pre && cosine) score = cosine_from_sums(ab, xx, sh.q_qq[j]);
+    const uint64_t key = rank_key(score, row);
+    unsigned long long m = __ballot(pre && (score >= a.min_score) && key > sh.thr_key[j]);
+    while (m) {
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const uint64_t nk_ = lane_bcast_u64(key, src);
+        if (!(nk_ > sh.thr_key[j])) continue;   // (an earlier insert of this round may have raised it)
+        WaveSortedList l;
+        l.key = lane < k ? list[lane] : NIDX_EMPTY_KEY;
+        l.insert(nk_, lane);
+        if (lane < k) list[lane] = l.key;
+        const uint64_t kth = l.at(k - 1);
+        if (lane == 0 && kth != NIDX_EMPTY_KEY) {
+            sh.thr_key[j] = kth;
+            sh.thr_score[j] = rank_key_score(kth);
+        }
+    }
+}
+
+// the stripe with NQ accumulators per lane (NQ >= the block's queries; the q_id of a query past them is PQ_NO_ID: a zero row that never passes)
+template <int NQ>
+__device__ __forceinline__ void pq_thin_walk(PqThinShared &sh, float *qs, uint64_t *lists, const PqMfmaArgs &a, const PqStripe &sp, uint32_t n_q, int lane) {
+    const bool cosine = a.similarity == 1;
+    const int k = (int)a.k;
+    const uint32_t nk = (a.dp + PT_BK - 1) / PT_BK;
+    const uint32_t steps = (sp.end - sp.begin + PT_ROWS - 1) / PT_ROWS;
+    auto id_of = [&](uint32_t step) -> uint32_t {   // the vector row of this lane's entry of a step
+        const uint64_t e = (uint64_t)sp.begin + (uint64_t)step * PT_ROWS + (uint32_t)lane;
+        uint32_t id = e < sp.end ? (sp.entries ? sp.entries[e] : (uint32_t)e) : PQ_NO_ID;
+        if (id >= a.n) id = PQ_NO_ID;
+        return id;
+    };
+    const uint32_t qid = lane < 4 * NQ ? sh.q_id[lane >> 2] : PQ_NO_ID;
+    sh.row_id[0][lane] = id_of(0);
+    uint32_t nid = id_of(1);
+    lds_barrier();
+    uint32_t sid[4];
+    float4 rx[4], rq;
+#pragma unroll
+    for (int i = 0; i < 4; i++) sid[i] = sh.row_id[0][(lane >> 2) + 16 * i];
+    pq_thin_load<NQ>(a, sid, qid, 0, lane, rx, rq);
+    pq_thin_store<NQ>(sh.x[0], qs, lane, rx, rq);
+    int buf = 0;
+    for (uint32_t step = 0; step < steps; step++) {
+        const int par = (int)(step & 1);
+        sh.row_id[par ^ 1][lane] = nid;   // (the previous step is done with that half)
+        nid = id_of(step + 2);
+        lds_barrier();                    // the ids of the next step and the first chunk of this one are in LDS
+        const uint32_t row = sh.row_id[par][lane];
+#pragma unroll
+        for (int i = 0; i < 4; i++) sid[i] = sh.row_id[par][(lane >> 2) + 16 * i];
+        const float xx = (row != PQ_NO_ID && cosine) ? a.norm2[row] : 0.f;
+        float acc[NQ];
+#pragma unroll
+        for (int j = 0; j < NQ; j++) acc[j] = 0.f;
+        for (uint32_t kc = 0; kc < nk; kc++) {
+            const bool more = kc + 1 < nk, next_step = !more && step + 1 < steps;
+            if (more) {
+                pq_thin_load<NQ>(a, sid, qid, (kc + 1) * PT_BK, lane, rx, rq);
+            } else if (next_step) {
+                uint32_t t[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) t[i] = sh.row_id[par ^ 1][(lane >> 2) + 16 * i];
+                pq_thin_load<NQ>(a, t, qid, 0, lane, rx, rq);
+            }
+            asm volatile("" ::: "memory");   // (the LDS reads below stay below: hoisted over the branch they all end up in registers at once)
+            const float *xs = sh.x[buf] + lane * PT_PITCH;
+            const float *qb = qs + buf * (NQ * PT_BK);
+#pragma unroll
+            for (int kk = 0; kk < PT_BK; kk += 4) {
+                const float x0 = xs[kk], x1 = xs[kk + 1], x2 = xs[kk + 2], x3 = xs[kk + 3];
+#pragma unroll
+                for (int j = 0; j < NQ; j++) {
+                    const float4 qv = *reinterpret_cast<const float4 *>(qb + j * PT_BK + kk);   // the same address in every lane
+                    acc[j] = fmaf(x0, qv.x, acc[j]);
+                    acc[j] = fmaf(x1, qv.y, acc[j]);
+                    acc[j] = fmaf(x2, qv.z, acc[j]);
+                    acc[j] = fmaf(x3, qv.w, acc[j]);
+                    // four queries at a time (left alone every broadcast read of the chunk is issued first: 16 registers per query)
+                    asm volatile("" : "+v"(acc[j]));   // (the chain stays here)
+                    if ((j & 3) == 3) asm volatile("" ::: "memory");
+                }
+            }
+            if (more || next_step) pq_thin_store<NQ>(sh.x[buf ^ 1], qs + (buf ^ 1) * (NQ * PT_BK), lane, rx, rq);
+            lds_barrier();
+            buf ^= 1;
+        }
+
+        // ---- epilogue: fold the step's 64 scores of every query into the query's list ----
+        const float rinv = 1.0f / sqrtf(xx);
+#pragma unroll
+        for (int j = 0; j < NQ; j++)
+            if ((uint32_t)j < n_q) pq_thin_fold(sh, lists + j * k, a, j, acc[j], row, xx, rinv, cosine, k, lane);
+    }
+}
+
+// grid (stripes, thin blocks), one wave; qcap: the queries a block of this launch may hold (a power of two <= 16), which sizes the
+// dynamic LDS: [2][qcap][16] floats of query chunks, then [qcap][k] keys
+__global__ __launch_bounds__(64, 4) void pq_thin_kernel(PqMfmaArgs a, uint32_t qcap) {
+    __shared__ PqThinShared sh;
+    extern __shared__ float4 pq_thin_dyn[];
+    const int lane = threadIdx.x;
+    const int k = (int)a.k;
+    const PqStripe sp = pq_stripe<false>(a);
+    const uint32_t n_q = sp.n_q < qcap ? sp.n_q : qcap;   // (the planner gives a thin block at most T <= qcap queries)
+    float *qs = reinterpret_cast<float *>(pq_thin_dyn);
+    uint64_t *lists = reinterpret_cast<uint64_t *>(qs + 2 * qcap * PT_BK);
+    if (lane < PT_QMAX) {
+        uint32_t qi = (uint32_t)lane < n_q ? a.region[sp.q_at + lane] : PQ_NO_ID;
+        if (qi >= a.n_queries) qi = PQ_NO_ID;
+        const float qq = qi != PQ_NO_ID ? a.q_norm2[qi] : 0.f;
+        sh.q_id[lane] = qi;
+        sh.q_qq[lane] = qq;
+        sh.q_rinv[lane] = qi != PQ_NO_ID ? 1.0f / sqrtf(qq) : 0.f;
+        sh.thr_key[lane] = NIDX_EMPTY_KEY;
+        sh.thr_score[lane] = qi != PQ_NO_ID ? -INFINITY : INFINITY;   // (a missing query admits nothing)
+    }
+    for (int i = lane; i < (int)qcap * k; i += 64) lists[i] = NIDX_EMPTY_KEY;
+    lds_barrier();
+    if (n_q <= 1) pq_thin_walk<1>(sh, qs, lists, a, sp, n_q, lane);
+    else if (n_q <= 2) pq_thin_walk<2>(sh, qs, lists, a, sp, n_q, lane);
+    else if (n_q <= 4) pq_thin_walk<4>(sh, qs, lists, a, sp, n_q, lane);
+    else if (n_q <= 8) pq_thin_walk<8>(sh, qs, lists, a, sp, n_q, lane);
+    else pq_thin_walk<16>(sh, qs, lists, a, sp, n_q, lane);
+    lds_barrier();
+    // ---- partial lists, at the query's own index: [query][stripe][k] (a wave without entries, or of a stripe past its block's own, leaves
+    //      empty lists) ----
+    for (int i = lane; i < (int)n_q * k; i += 64) {
+        const uint32_t qi = sh.q_id[i / k];
+        if (qi != PQ_NO_ID) a.partial[((size_t)qi * a.lists_per_query + blockIdx.x) * k + i % k] = lists[i];
+    }
+}
+
+hipError_t launch_pq_thin(const PqMfmaArgs &a, uint32_t thin, hipStream_t s) {
+    if (thin == 0 || thin > PT_QMAX || a.k == 0 || a.k > NIDX_MFMA_KMAX) return hipErrorInvalidValue;
+    if (a.n_blocks == 0 || a.lists_per_query == 0) return hipSuccess;
+    uint32_t qcap = 1;
+    while (qcap < thin) qcap *= 2;
+    const size_t dyn = (size_t)qcap * (2 * PT_BK * sizeof(float) + a.k * sizeof(uint64_t));
+    for (uint32_t b0 = 0; b0 < a.n_blocks; b0 += 65535u) {   // (the blocks in slices, as launch_pq_mfma)
+        PqMfmaArgs part = a;
+        part.at_blocks = a.at_blocks + 6u * b0;
+        part.n_blocks = a.n_blocks - b0 < 65535u ? a.n_blocks - b0 : 65535u;
+        hipLaunchKernelGGL(pq_thin_kernel, dim3(a.lists_per_query, part.n_blocks), dim3(64), dyn, s, part, qcap);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace nidx

@@ -944,14 +944,17 @@ class VectorSearcher:
         on by default: "maxsim_stage" = 1 (FEATURE_VECTOR_MAXSIM_MFMA) and "pq_scan_stage" = 1 (FEATURE_VECTOR_PQ_SCAN_MFMA: the
         brute-force arm of every per-query-filter search as packed GEMMs on the f32 matrix cores, meant for batches whose queries share
         filters; pages of at most 64 hits — up to 512 on single-vector segments with "pq_scan_pages" = 1 as well, and on multi-vector
-        segments with "pq_scan_multi_pages" = 1 on top of that, FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES).
+        segments with "pq_scan_multi_pages" = 1 on top of that, FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES).  "pq_scan_thin" = T in 1 .. 16
+        (FEATURE_VECTOR_PQ_SCAN_THIN, read while "pq_scan_stage" is 1) changes no further bit: groups of at most T queries — a filter
+        of their own — are scored by a list-gather kernel instead of an almost empty 128-query tile (single-vector segments, k <= 64;
+        see pq_scan_stats).
         "rabitq_scan_stage" = 1 and "rabitq_scan_scratch_kib" (FEATURE_VECTOR_RABITQ_SCAN_MFMA) change NO bit: the estimates of
         METHOD_RABITQ_BRUTE_FORCE come from an int8 GEMM on the matrix cores instead of one wave per query (single-vector segments, one
         filter per batch; anything else keeps the old kernel, see rabitq_scan_stats), and the second caps that stage's scratch in KiB
         (0 = 1 GiB), cutting a batch into chunks of queries.  "rabitq_scan_groups" = 1 (FEATURE_VECTOR_RABITQ_SCAN_GROUPS, read while
         "rabitq_scan_stage" is 1) extends the stage to per-query filter rows (search_many) and multi-vector segments: the same bits."""
         need = {"maxsim_stage": _lib.FEATURE_VECTOR_MAXSIM_MFMA, "pq_scan_stage": _lib.FEATURE_VECTOR_PQ_SCAN_MFMA,
-                "pq_scan_multi_pages": _lib.FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES,
+                "pq_scan_multi_pages": _lib.FEATURE_VECTOR_PQ_SCAN_MULTI_PAGES, "pq_scan_thin": _lib.FEATURE_VECTOR_PQ_SCAN_THIN,
                 "rabitq_scan_stage": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA,
                 "rabitq_scan_groups": _lib.FEATURE_VECTOR_RABITQ_SCAN_GROUPS,
                 "rabitq_scan_scratch_kib": _lib.FEATURE_VECTOR_RABITQ_SCAN_MFMA}.get(name, 0)
@@ -987,6 +990,12 @@ class VectorSearcher:
         out = C.c_uint64(0)
         _lib.check(_lib.lib().nidx_gpu_vector_space_usage(self._handle, C.byref(out)))
         return out.value
+
+    def pq_scan_stats(self) -> Tuple[int, int]:
+        """Since open: (queries whose brute-force arm "pq_scan_stage" = 1 answered, of those the ones the "pq_scan_thin" kernel answered)."""
+        done, thin = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().nidx_gpu_vector_pq_scan_stats(self._handle, C.byref(done), C.byref(thin)))
+        return done.value, thin.value
 
     def rabitq_scan_stats(self) -> Tuple[int, int]:
         """Since open: (queries answered by "rabitq_scan_stage" = 1, queries the stage handed to the one-wave-per-query kernel)."""
